@@ -5,14 +5,18 @@ attention), free-running inference, on BASELINE.json config 2:
 B = 32 utterances per GPU, 256 -> 258 frames (86 decode steps, r = 3), L = 43, n_mels = 80, fp32,
 prenet dropout 0.5 active (it never turns off in the reference), synthetic weights and inputs.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c5|c3|train]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c5|c3|train|cycle] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-One "step" = one pass of the hot path over one batch.  Weak scaling: every rank works on its own batch
+One "step" = one pass of the hot path over one batch; exactly K steps are timed.  Weak scaling: every rank works on its own batch
 (utterances are independent; inference has no data-path collective, training all-reduces gradients).
 With --gpus N > 1 and no WORLD_SIZE in the environment this process starts N ranks itself
 (python -m torch.distributed.run, one per GPU, RCCL) BEFORE touching the GPU, and exits with their code.
 Prints ONE JSON line on rank 0.
+--dump-outputs DIR: rank 0 also writes what the timed path returned in its last timed step as DIR/<name>.npy (decode: mel,
+alignments, stop; c3: p_code, idx, out of every case; train / cycle: the step's statistics and the updated parameters).  Weights,
+inputs and the device generators that draw the dropout masks are seeded, so two runs with the same arguments -- of two builds of
+the project, say -- compute on the same inputs and compare file for file.
 
 Secondary workloads (not the headline):
   c5     BASELINE config 5 (bin/gen_specgram.py long form: B=64, L=171, 355 decode steps)
@@ -374,6 +378,40 @@ def event_timer(lib):
     return Timer
 
 
+DEVICE_SEED = 1234                    # device random generators (dropout masks) of rank r: DEVICE_SEED + r
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # array data of one dump: under 64 MB with the .npy headers
+DUMP_WHOLE_BYTES = 1 << 16            # arrays up to this size are always written whole
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: tensor / array / number} as out_dir/<name>.npy, float64 values as float64 and everything else as
+    float32.  At most DUMP_BUDGET_BYTES in all: when the arrays are larger together, every array of more than DUMP_WHOLE_BYTES is
+    replaced by a fixed, seeded sample of its flattened elements (sorted positions, the same share of each), so two runs with the
+    same arguments write files that compare element for element."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v)
+        host[name] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    small = sum(v.nbytes for v in host.values() if v.nbytes <= DUMP_WHOLE_BYTES)
+    large = sum(v.nbytes for v in host.values() if v.nbytes > DUMP_WHOLE_BYTES)
+    share = max(0.0, (DUMP_BUDGET_BYTES - small) / float(large)) if small + large > DUMP_BUDGET_BYTES else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (name, v) in enumerate(host.items()):
+        note = 'shape %s' % (tuple(v.shape),)
+        if share < 1.0 and v.nbytes > DUMP_WHOLE_BYTES:
+            k = int(v.size * share)
+            pos = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED + i).choice(v.size, k, replace=False))
+            v = v.reshape(-1)[pos]
+            note += ', sample of %d elements (seed %d)' % (k, DUMP_SAMPLE_SEED + i)
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+        sys.stderr.write('bench.py: dumped %s (%s, %s)\n' % (name, v.dtype, note))
+
+
 # ===================================================================================== decode (c2 / c5)
 def lstm_probe(dec, dev, Bsz):
     """Roofline probe of the dominant kernel (the weight-streaming LSTM cell), measured with HIP events on the stream the
@@ -485,6 +523,9 @@ def bench_decode(args, rk):
         # a starved in-launch hand-off makes a replay NaN (GraphedDecoder.check() would recover, but a timed region with such a replay
         # in it is not a measurement)
         assert not ops.handoff_starved(dec.handoff_status), 'a timed replay was starved of compute units (shared GPU?)' 
+    if args.dump_outputs and rk.rank == 0:
+        # what Decoder.forward returned in the last timed pass (views of the graph's buffers: copied before anything else runs)
+        dump_outputs(args.dump_outputs, dict(zip(('mel', 'alignments', 'stop'), state['out'])))
     if rk.rank != 0:
         return None
 
@@ -563,6 +604,7 @@ def bench_vq(args, rk):
     g = torch.Generator().manual_seed(7 + rk.rank)
     rows = []
     head = None
+    dumps = {}
     for Bn, V in (((32, 512),) if args.vq_head_only else ((32, 512), (256, 512), (32, 43), (256, 43))):
         n, D = Bn * 129, 64
         x = torch.randn(Bn, 129, D, generator=g).to(dev)
@@ -581,7 +623,7 @@ def bench_vq(args, rk):
             lib.st_vq_l2_fwd(ops._p(x), ops._p(table), ops._p(temp), ops._p(p_buf), ops._p(idx_buf, torch.int64),
                              ops._p(out_buf), ops._p(ws), n, D, V, ops.stream_handle())
         inner = 20
-        reps = max(args.steps, 5)
+        reps = args.steps
         timed = {}
         for key, fn in (('with_pack', launch_with_pack), ('packed', launch)):
             gph = ops.Graph()
@@ -596,6 +638,9 @@ def bench_vq(args, rk):
                     gph.launch()
             timed[key] = tm.ms * 1e3 / (reps * inner)
             assert torch.equal(idx_buf, idx)
+        if args.dump_outputs:                      # what the last timed replay (the 'packed' lookup) wrote
+            tag = 'b%d_v%d_' % (Bn, V)
+            dumps.update({tag + 'p_code': p_buf.cpu(), tag + 'idx': idx_buf.cpu(), tag + 'out': out_buf.cpu()})
         us = timed['packed']
         alg = n * (520 + 4 * V) + V * D * 4
         row = {'utterances': Bn, 'vectors': n, 'V': V, 'us_per_launch': round(us, 3), 'us_with_pack_launch': round(timed['with_pack'], 3),
@@ -605,6 +650,8 @@ def bench_vq(args, rk):
         rows.append(row)
         if (Bn, V) == (32, 512):
             head = row
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(args.dump_outputs, dumps)
     if rk.rank != 0:
         return None
     cpu = None
@@ -635,6 +682,14 @@ def bench_vq(args, rk):
 
 
 # ===================================================================================== training (C4)
+def trainer_outputs(tr, st):
+    """--dump-outputs of a training workload: the statistics the last timed step returned (stat_<key>) and every parameter as
+    that step left it (param_<name>)"""
+    out = {'stat_' + k: v for k, v in st.items() if isinstance(v, (int, float)) and not isinstance(v, bool)}
+    out.update({'param_' + k: p for k, p in tr.model.named_parameters()})
+    return out
+
+
 def bench_train(args, rk):
     """BASELINE config 4: config/semi-multi-spkr-paired-data.yaml, utterance-level data parallelism -- every rank runs the
     paired TTS training step on its own B=32 synthetic batch (109 speakers), BatchNorm statistics over the global batch
@@ -660,6 +715,8 @@ def bench_train(args, rk):
     step()
     variants = {}
     elapsed = rk.timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rk.rank == 0:            # (before the untimed variants below take more steps)
+        dump_outputs(args.dump_outputs, trainer_outputs(tr, last['st']))
     variants['full'] = elapsed
     issue_ms = rk.issue_seconds / args.steps * 1e3
     counts = parallel.collective_counts()
@@ -751,10 +808,12 @@ def bench_cycle(args, rk):
     tr.async_stats = not args.sync_stats
     pair, unpair = tr.fetch_data('pair_iter'), tr.fetch_data('unpair_iter')
     last = {}
+    ran = []                                      # the kind of every step of the alternating loop, in order
 
     def loop_step():
         kind, use = tr.cycle_kind(tr.step)
         last[kind] = tr.cycle_step(pair, unpair if use else None)
+        ran.append(kind)
 
     def only(kind):
         def f():
@@ -764,8 +823,11 @@ def bench_cycle(args, rk):
 
     tr.step = 2                                   # past unpair_speech_start_step (0): the unpaired batch joins from the first timed step on
     loop_step(); loop_step()
-    steps = args.steps + (args.steps % 2)         # whole pairs of cycles
+    steps = args.steps
     elapsed = rk.timed(loop_step, steps, args.warmup + (args.warmup % 2))
+    timed_kinds = ran[-steps:]
+    if args.dump_outputs and rk.rank == 0:        # (before the timed steps of each kind below)
+        dump_outputs(args.dump_outputs, trainer_outputs(tr, last[timed_kinds[-1]]))
     issue_ms = rk.issue_seconds / steps * 1e3
     kinds = {}
     for kind in ('speech_first', 'text_first'):
@@ -794,8 +856,8 @@ def bench_cycle(args, rk):
                            'frac': round(tf / MFMA_F32_PEAK_TFLOPS, 4), 'traffic': None},
                  last={k: float(last[kind][k]) for k in ('loss', 'grad_norm', 'asr_loss', 'tts_loss') if k in last[kind]})
     kinds['speech_first']['unpair_text_len'] = Lu
-    total_frames = rk.world * (frames['speech_first'] + frames['text_first']) * (steps // 2)
-    total_fl = (fl['speech_first'] + fl['text_first']) * (steps // 2)
+    total_frames = rk.world * sum(frames[k] for k in timed_kinds)
+    total_fl = sum(fl[k] for k in timed_kinds)
     tf = total_fl / elapsed / 1e12
     cpu = None
     if not args.no_cpu_baseline and rk.world == 1:
@@ -906,7 +968,12 @@ def main():
     ap.add_argument('--workload', choices=['c2', 'c5', 'c3', 'train', 'cycle'], default='c2',
                     help="c2 = the headline configuration; c5 / c3 / train = secondary lines (see the module docstring)")
     ap.add_argument('--rccl-probe', action='store_true', help=argparse.SUPPRESS)        # child of a rank: see Ranks._probe_rccl
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (rank 0; '
+                         'float32 / float64, at most 64 MB in all: a fixed seeded sample of larger outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.rccl_probe:
         return rccl_probe_main()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -918,6 +985,10 @@ def main():
     real_stdout = os.dup(1)
     os.dup2(2, 1)
     rk = Ranks(args)
+    # torch seeds its device generators at random in every process: the dropout masks (prenet of the decode loop, the training steps)
+    # would differ from run to run.  Fixed per rank, so that two runs with the same arguments compute on the same inputs.
+    import torch
+    torch.cuda.manual_seed_all(DEVICE_SEED + rk.rank)
     fn = {'c2': bench_decode, 'c5': bench_decode, 'c3': bench_vq, 'train': bench_train, 'cycle': bench_cycle}[args.workload]
     res = fn(args, rk)
     if rk.rank == 0:

@@ -110,10 +110,11 @@ def _step12(m, batch, rows, dev, weight=1.0):
     return float(loss.detach())
 
 
-_SIZES8 = [3, 2, 2, 1, 1, 1, 1, 1]
+# Five ranks: with the test process itself that is six processes holding the GPU, the most one box may carry at once
+_SIZES5 = [5, 3, 2, 1, 1]
 
 
-def _worker8(rank, world, port, out_path):
+def _worker5(rank, world, port, out_path):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     dist.init_process_group('gloo', rank=rank, world_size=world)
@@ -123,8 +124,8 @@ def _worker8(rank, world, port, out_path):
     batch = _batch12(A)
     parallel.sync_batchnorm(True)
     parallel.broadcast_parameters(m)
-    lo = sum(_SIZES8[:rank])
-    n_r = _SIZES8[rank]
+    lo = sum(_SIZES5[:rank])
+    n_r = _SIZES5[rank]
     red = parallel.GradReducer(m.parameters(), bucket_bytes=64 << 10, average=True, defer_average=True)
     loss = _step12(m, batch, slice(lo, lo + n_r), dev, weight=n_r * world / 12.0)
     n_coll = red.finish()
@@ -137,10 +138,12 @@ def _worker8(rank, world, port, out_path):
     dist.destroy_process_group()
 
 
-def test_eight_rank_sync_bn_training_with_unequal_shards_equals_single_process(tmp_path):
-    """Eight ranks before an 8-GPU box sees them (here: eight processes sharing the test GPU, gloo for the collectives): shards of 3 / 2 / 2 /
-    1 / 1 / 1 / 1 / 1 utterances of a batch of 12, SyncBN statistics merged over the ranks' true row counts, gradients born in their buckets,
-    the sums all-reduced and 1 / world applied afterwards: averaged gradients and running statistics = the single-process full batch."""
+def test_five_rank_sync_bn_training_with_unequal_shards_equals_single_process(tmp_path):
+    """Five ranks sharing the test GPU (gloo for the collectives): shards of 5 / 3 / 2 / 1 / 1 utterances of a batch of 12, two of them a
+    single utterance, SyncBN statistics merged over the ranks' true row counts, gradients born in their buckets, the sums all-reduced and
+    1 / world applied afterwards: averaged gradients and running statistics = the single-process full batch.  A worker that dies fails
+    the test."""
+    import socket
     import time
     import torch.multiprocessing as mp
     dev = torch.device('cuda:0')
@@ -148,29 +151,17 @@ def test_eight_rank_sync_bn_training_with_unequal_shards_equals_single_process(t
     _step12(m, _batch12(A), slice(0, 12), dev)
     ref = {k: p.grad.cpu() for k, p in m.named_parameters() if p.grad is not None}
     ref_stats = {k: v.cpu() for k, v in m.state_dict().items() if 'running_' in k}
-    out = str(tmp_path / 'dp8.pt')
-    import socket
-    from torch.multiprocessing.spawn import ProcessExitedException
-    for attempt in range(3):
-        with socket.socket() as sk:                 # a port nobody holds (fixed offsets collided once with a lingering listener)
-            sk.bind(('127.0.0.1', 0))
-            port = sk.getsockname()[1]
-        ctx = mp.start_processes(_worker8, args=(8, port, out), nprocs=8, join=False, start_method='spawn')
-        deadline = time.time() + 240
-        try:
-            while not ctx.join(timeout=5):
-                if time.time() > deadline:
-                    for p in ctx.processes:
-                        p.kill()
-                    pytest.fail('eight data-parallel workers did not finish within 240 s')
-            break
-        except ProcessExitedException as e:
-            # Eight processes time-sharing ONE device is outside what this test is about (and what the runtime is tuned for): about one run
-            # in four a worker is killed by the driver (HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION while its code objects load).  A worker that
-            # dies by a SIGNAL is retried; a failed assertion inside a worker arrives as ProcessRaisedException and fails the test at once.
-            if attempt == 2:
-                raise
-            print('retrying after a worker was killed by a signal: %s' % e)
+    out = str(tmp_path / 'dp5.pt')
+    with socket.socket() as sk:                     # a port nobody holds (fixed offsets collided once with a lingering listener)
+        sk.bind(('127.0.0.1', 0))
+        port = sk.getsockname()[1]
+    ctx = mp.start_processes(_worker5, args=(len(_SIZES5), port, out), nprocs=len(_SIZES5), join=False, start_method='spawn')
+    deadline = time.time() + 240
+    while not ctx.join(timeout=5):
+        if time.time() > deadline:
+            for p in ctx.processes:
+                p.kill()
+            pytest.fail('five data-parallel workers did not finish within 240 s')
     got = torch.load(out)
     worst = 0.0
     for k, g in ref.items():
@@ -183,7 +174,7 @@ def test_eight_rank_sync_bn_training_with_unequal_shards_equals_single_process(t
         assert e < 1e-4, (k, e)
     for k, v in ref_stats.items():
         assert maxdiff(got['stats'][k], v) < 1e-5, k
-    print('worst relative gradient difference, 8 ranks vs single process: %.2e' % worst)
+    print('worst relative gradient difference, 5 ranks vs single process: %.2e' % worst)
 
 
 @pytest.mark.parametrize('N', [80, 128, 7])

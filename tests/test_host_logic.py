@@ -568,3 +568,29 @@ def test_main_names_the_solvers_the_reference_tree_lacks(flag, capsys):
     with pytest.raises(SystemExit):
         entry.parse_args(['--config', 'config/supervised.yaml', flag])
     assert 'not part of the reference tree' in capsys.readouterr().err
+
+
+def test_bench_dump_outputs_are_float_capped_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one <name>.npy per output, float64 kept and everything else float32; past the size budget the large
+    arrays become the same seeded sample on every run while small ones (step statistics) stay whole"""
+    import bench
+    outs = dict(mel=torch.arange(3000, dtype=torch.float32).view(10, 300), idx=torch.arange(40), loss=2.5,
+                table=np.linspace(0.0, 1.0, 9000))
+    bench.dump_outputs(str(tmp_path / 'whole'), outs)
+    got = {n[:-4]: np.load(str(tmp_path / 'whole' / n)) for n in os.listdir(str(tmp_path / 'whole'))}
+    assert sorted(got) == ['idx', 'loss', 'mel', 'table']
+    assert got['mel'].dtype == np.float32 and np.array_equal(got['mel'], outs['mel'].numpy())
+    assert got['idx'].dtype == np.float32 and np.array_equal(got['idx'], np.arange(40))
+    assert got['table'].dtype == np.float64 and got['loss'] == 2.5
+    monkeypatch.setattr(bench, 'DUMP_WHOLE_BYTES', 1024)
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 20000)
+    runs = []
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), outs)
+        runs.append({n: np.load(str(tmp_path / d / n)) for n in os.listdir(str(tmp_path / d))})
+    assert sum(v.nbytes for v in runs[0].values()) <= 20000
+    assert np.array_equal(runs[0]['idx.npy'], np.arange(40)) and runs[0]['loss.npy'] == 2.5
+    for n, v in runs[0].items():
+        assert np.array_equal(v, runs[1][n]), n
+    mel = runs[0]['mel.npy']
+    assert 0 < mel.size < 3000 and np.all(np.diff(mel) > 0)      # a sample of the elements, in their order
