@@ -1122,6 +1122,33 @@ int st_copy2d(float* dst, int ldd, const float* src, int lds, int rows, int cols
 /* dst(b, :) = mean over t of src(b, t, :)    ref: teacher.mean(dim=1) src/module.py:194 */
 int st_mean_rows(const float* src, float* dst, int B, int T, int D, void* stream);
 
+/* ------------------------------------------------------------------ Griffin-Lim vocoder (linear spectrogram -> waveform)
+ * Replaces AudioProcessor.specgram_to_waveform / _griffin_lim / _stft / _istft / _inv_preemphasis (ref: src/audio.py:179-192,
+ * 208-262, 274-288) for the linear branch of feat_to_wave (:397-407).  STFT conventions of the reference: center=True,
+ * pad_mode='reflect', onesided, unnormalised, periodic Hann window of `win` samples zero-padded to n_fft at offset
+ * (n_fft - win) / 2; the iSTFT divides the overlap-add by the window-square envelope and trims n_fft / 2 at both ends (no
+ * `length`: hop * (T - 1) samples; lib/istft.py).  Supported: n_fft in {512, 1024, 2048, 4096}, 0 < 2 * hop <= win <= n_fft,
+ * signals longer than n_fft / 2 samples (anything else returns -22).  Spectra are frame-major (B, T, n_fft / 2 + 1) complex
+ * (re, im interleaved): the (B, F, T) tensor of torch.stft transposed.  No atomics: results are bitwise repeatable.  The first
+ * call on a device uploads the FFT twiddle tables (computed in double on the host) and may not be inside a stream capture. */
+/* workspace floats of st_istft / st_griffin_lim */
+size_t st_istft_workspace_floats(int B, int T, int n_fft, int hop, int win);
+size_t st_gl_workspace_floats(int B, int T, int n_fft, int hop, int win);
+/* spec (B, 1 + L / hop, n_fft / 2 + 1, 2) = torch.stft(x (B, L), ...)    ref: AudioProcessor._stft src/audio.py:234-246 */
+int st_stft_fwd(const float* x, float* spec, int B, int L, int n_fft, int hop, int win, void* stream);
+/* x (B, hop * (T - 1)) = istft(spec (B, T, n_fft / 2 + 1, 2))    ref: AudioProcessor._istft src/audio.py:248-262, lib/istft.py
+ * ws: st_istft_workspace_floats() floats.  3 launches. */
+int st_istft(const float* spec, float* x, int B, int T, int n_fft, int hop, int win, float* ws, void* stream);
+/* wav (B, hop * (T - 1)) = Griffin-Lim of n_iter iterations (ref: _griffin_lim src/audio.py:208-226, GFL_ITER = 30).
+ * feat(b, t, f) = feat[b * sb + t * st + f * sf] (strides in floats; the decoder's (B, T, F) is sb = T F, st = F, sf = 1);
+ * normalized = 1: feat is the normalised spectrogram and the magnitude is _db_to_amp(_denormalize(feat) + REF_LEVEL_DB) ** power
+ * (:186-188, :281-288); 0: feat is the magnitude.  phases: initial phases (B, F, T) contiguous (:214-216, drawn by the caller).
+ * post: bit 0 = inverse pre-emphasis y[n] = x[n] + 0.97 y[n-1] (the literal of :274-276, scipy.signal.lfilter([1], [1, -0.97])),
+ * bit 1 = clip to [-1, 1] (:192).  ws: st_gl_workspace_floats() floats.  n_iter + 3 launches (setup, first iSTFT, one per
+ * iteration, final overlap-add). */
+int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases, float* wav,
+                   int B, int T, int n_fft, int hop, int win, int n_iter, int post, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,7 @@ parser.add_argument('--no-msg', action='store_true', help='Hide all messages.')
 parser.add_argument('--actual-len', action='store_true', help='Using actual len for CTC loss. (synthetic inputs are full length: no effect)')
 parser.add_argument('--store-best-per', action='store_true', help='Only store the model with best PER. (no dev corpus: no effect)')
 parser.add_argument('--asr-only', action='store_true', help='(the reference dispatches to bin/train_asr.py, which its tree lacks)')
-parser.add_argument('--gen-wav', action='store_true', help='Generate waveform using Griffin-Lim. (audio back end out of scope: ignored)')
+parser.add_argument('--gen-wav', action='store_true', help='Generate waveform using Griffin-Lim. (--gen-specgram: writes <name>-pred.wav)')
 # synthetic-data knobs (the reference reads these from the corpus)
 parser.add_argument('--frames', default=256, type=int, help='mel frames per synthetic utterance')
 parser.add_argument('--batch-size', default=None, type=int)
@@ -50,7 +50,7 @@ parser.add_argument('--async-stats', action='store_true', help='training: no hos
                     'a NaN gradient norm skips the update on the device)')
 
 
-# Flags of the reference (main.py:23-33) with nothing to do on this path, and those whose solver files are
+# Flags of the reference (main.py:23-33) with nothing to do on this path (--gen-wav outside --gen-specgram), and those whose solver files are
 # absent from the reference tree itself (main.py:49-60 import bin/asr_decode.py, bin/gen_gt_specgram.py,
 # bin/train_asr.py, none of which exist): accepted by the parser so that existing launch lines keep working.
 IGNORED_FLAGS = ('debug', 'no_pin', 'actual_len', 'store_best_per', 'gen_wav')
@@ -71,6 +71,8 @@ def parse_args(argv=None):
                          'only the default (training) and --gen-specgram modes exist' % (flag.replace('_', '-'), path))
     if paras.verbose:
         for flag in IGNORED_FLAGS:
+            if flag == 'gen_wav' and paras.gen_specgram:
+                continue             # read by gen_specgram alone (bin/gen_specgram.py:114-126), as in the reference
             if getattr(paras, flag):
                 print('[INFO] --%s accepted for compatibility; it has no effect on this path' % flag.replace('_', '-'))
     return paras

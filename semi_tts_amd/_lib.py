@@ -337,11 +337,16 @@ SIGNATURES = {
     'st_fill': [P, F, Z, P],
     'st_copy2d': [P, I, P, I, I, I, P],
     'st_mean_rows': [P, P, I, I, I, P],
+    'st_istft_workspace_floats': [I, I, I, I, I],
+    'st_gl_workspace_floats': [I, I, I, I, I],
+    'st_stft_fwd': [P, P, I, I, I, I, I, P],
+    'st_istft': [P, P, I, I, I, I, I, P, P],
+    'st_griffin_lim': [P, C.c_long, C.c_long, C.c_long, I, F, P, P, I, I, I, I, I, I, I, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,
              'st_gemm_wgrad_workspace_floats': C.c_size_t, 'st_gemm_wgrad_batch_workspace_floats': C.c_size_t, 'st_freq_loss_workspace_floats': C.c_size_t, 'st_attn_fin_split_workspace_floats': C.c_size_t, 'st_attn_rng_xchg_words': C.c_size_t, 'st_colreduce_workspace_floats': C.c_size_t, 'st_mt_blocks': C.c_size_t, 'st_mt_table_misses': C.c_long,
-             'st_bn_bank_workspace_floats': C.c_size_t}
+             'st_bn_bank_workspace_floats': C.c_size_t, 'st_istft_workspace_floats': C.c_size_t, 'st_gl_workspace_floats': C.c_size_t}
 
 _lib = None
 

@@ -1,0 +1,513 @@
+// audio.hip -- Griffin-Lim vocoder: linear spectrogram -> waveform (ref: src/audio.py:179-262, 274-288)
+//
+// Every FFT is a real n_fft-point transform done as an (n_fft/2)-point complex Stockham FFT in LDS (radix 4, one radix-2 stage
+// when log2(n_fft/2) is odd) plus the real split pass.  Twiddles e^{-2 pi i k / n_fft} come from tables computed in double on the
+// host and uploaded once per device.  The time-domain state between launches is the windowed inverse FFT of every frame (its
+// `win` support only): the next launch gathers the overlap-add of a frame's neighbours straight from it, so one Griffin-Lim
+// iteration (iSTFT -> STFT -> phase projection) is ONE launch of one workgroup per (utterance, frame), with no atomics (every
+// result is bitwise repeatable).
+#include "st_common.h"
+#include <math.h>
+#include <mutex>
+
+namespace {
+
+constexpr int GL_THREADS = 256;
+constexpr int OLA_THREADS = 1024;
+constexpr int OLA_CHUNK = 16;                               // samples per thread per tile of the final overlap-add + de-emphasis
+constexpr int OLA_TILE = OLA_THREADS * OLA_CHUNK;
+constexpr float INV_PREEMPH = 0.97f;                        // the literal of src/audio.py:276 (not data.audio.preemphasis_coeff)
+constexpr float MIN_LEVEL_DB = -100.0f;                     // src/audio.py:17-18
+constexpr float REF_LEVEL_DB = 20.0f;
+
+// ------------------------------------------------------------------ twiddle tables, e^{-2 pi i k / N} for k in [0, N)
+__device__ float2 g_tw512[512];
+__device__ float2 g_tw1024[1024];
+__device__ float2 g_tw2048[2048];
+__device__ float2 g_tw4096[4096];
+
+template <int N> __device__ __forceinline__ const float2* tw_table();
+template <> __device__ __forceinline__ const float2* tw_table<512>() { return g_tw512; }
+template <> __device__ __forceinline__ const float2* tw_table<1024>() { return g_tw1024; }
+template <> __device__ __forceinline__ const float2* tw_table<2048>() { return g_tw2048; }
+template <> __device__ __forceinline__ const float2* tw_table<4096>() { return g_tw4096; }
+
+std::mutex g_tw_mu;
+bool g_tw_done[64];
+
+template <int N>
+int upload_table(const void* sym) {
+    static float2 h[N];
+    for (int k = 0; k < N; ++k) {
+        const double a = -2.0 * M_PI * (double)k / (double)N;
+        h[k] = make_float2((float)cos(a), (float)sin(a));
+    }
+    ST_HIP(hipMemcpyToSymbol(sym, h, sizeof(h)));
+    return 0;
+}
+
+// First use on a device uploads the four tables (a synchronous copy): that first call may not be inside a stream capture.
+int ensure_twiddles(void* stream) {
+    int dev = 0;
+    ST_HIP(hipGetDevice(&dev));
+    ST_CHECK_ARG(dev >= 0 && dev < 64, "audio: device index %d out of range", dev);
+    std::lock_guard<std::mutex> lk(g_tw_mu);
+    if (g_tw_done[dev]) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    ST_HIP(hipStreamIsCapturing((hipStream_t)stream, &cs));
+    ST_CHECK_ARG(cs == hipStreamCaptureStatusNone,
+                 "audio: the first FFT call on a device uploads its twiddle tables and may not be captured; call once before capturing");
+    int rc;
+    if ((rc = upload_table<512>(HIP_SYMBOL(g_tw512))) != 0) return rc;
+    if ((rc = upload_table<1024>(HIP_SYMBOL(g_tw1024))) != 0) return rc;
+    if ((rc = upload_table<2048>(HIP_SYMBOL(g_tw2048))) != 0) return rc;
+    if ((rc = upload_table<4096>(HIP_SYMBOL(g_tw4096))) != 0) return rc;
+    g_tw_done[dev] = true;
+    return 0;
+}
+
+// ------------------------------------------------------------------ complex helpers
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
+__device__ __forceinline__ float2 cmul_negi(float2 a) { return make_float2(a.y, -a.x); }   // a * (-i)
+__device__ __forceinline__ float2 cmul_i(float2 a) { return make_float2(-a.y, a.x); }      // a * i
+
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
+
+// In-place forward (e^{-}) M-point complex FFT of buf (LDS), natural order in and out: Stockham autosort, each butterfly's inputs
+// read into registers before a barrier, outputs written after it.  tw: the N = 2M table.  Ends with a barrier.
+template <int M>
+__device__ __forceinline__ void fft_lds(float2* buf, const float2* __restrict__ tw) {
+    constexpr int LOG2M = ilog2(M);
+    const int tid = threadIdx.x;
+    int Ns = 1;
+    if constexpr (LOG2M & 1) {              // radix-2 first stage (Ns = 1: no twiddle)
+        constexpr int NB = M / 2, PER = (NB + GL_THREADS - 1) / GL_THREADS;
+        float2 v0[PER], v1[PER];
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+            const int j = tid + p * GL_THREADS;
+            if (j < NB) { v0[p] = buf[j]; v1[p] = buf[j + NB]; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+            const int j = tid + p * GL_THREADS;
+            if (j < NB) { buf[2 * j] = cadd(v0[p], v1[p]); buf[2 * j + 1] = csub(v0[p], v1[p]); }
+        }
+        __syncthreads();
+        Ns = 2;
+    }
+    constexpr int NB = M / 4, PER = (NB + GL_THREADS - 1) / GL_THREADS;
+#pragma unroll
+    for (int stage = 0; stage < LOG2M / 2; ++stage) {
+        float2 v[PER][4];
+        int jj[PER];
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+            const int j = tid + p * GL_THREADS;
+            jj[p] = j;
+            if (j < NB) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[p][r] = buf[j + r * NB];
+            }
+        }
+        __syncthreads();
+        const int tstep = (2 * M) / (Ns * 4);          // table index step per (j % Ns) * r, in N units
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+            const int j = jj[p];
+            if (j < NB) {
+                const int jm = j & (Ns - 1);
+                if (Ns > 1) {
+#pragma unroll
+                    for (int r = 1; r < 4; ++r) v[p][r] = cmul(v[p][r], tw[jm * r * tstep]);
+                }
+                const float2 a0 = cadd(v[p][0], v[p][2]), a1 = csub(v[p][0], v[p][2]);
+                const float2 a2 = cadd(v[p][1], v[p][3]), a3 = cmul_negi(csub(v[p][1], v[p][3]));
+                const int o = (j - jm) * 4 + jm;
+                buf[o] = cadd(a0, a2);
+                buf[o + Ns] = cadd(a1, a3);
+                buf[o + 2 * Ns] = csub(a0, a2);
+                buf[o + 3 * Ns] = csub(a1, a3);
+            }
+        }
+        __syncthreads();
+        Ns *= 4;
+    }
+}
+
+// Real split after the forward FFT of z[m] = x[2m] + i x[2m+1]: the one-sided spectrum X[k], X[M-k] of x from Z[k], Z[M-k]
+// (k in [0, M/2]; k = 0 gives X[0] and X[M]).
+__device__ __forceinline__ void real_split(float2 zk, float2 zc, float2 w, float2& xk, float2& xc) {
+    const float2 e = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y - zc.y));
+    const float2 o = make_float2(0.5f * (zk.y + zc.y), -0.5f * (zk.x - zc.x));
+    const float2 wo = cmul(w, o);
+    xk = cadd(e, wo);
+    xc = cconj(csub(e, wo));
+}
+
+// Inverse of real_split for a C2R transform: Z'[k], Z'[M-k] from Y[k], Y[M-k] (k = 0: Y[0] and Y[M]); the caller zeroes the
+// imaginary parts of Y[0] and Y[M] (irfft ignores them).  The inverse M-point FFT of Z' is x[2m] + i x[2m+1] times M.
+__device__ __forceinline__ void real_merge(float2 yk, float2 yc, float2 w, float2& zk, float2& zc) {
+    const float2 e = make_float2(0.5f * (yk.x + yc.x), 0.5f * (yk.y - yc.y));
+    const float2 o = cmul(make_float2(0.5f * (yk.x - yc.x), 0.5f * (yk.y + yc.y)), cconj(w));
+    zk = cadd(e, cmul_i(o));
+    zc = cadd(cconj(e), cmul_i(cconj(o)));
+}
+
+// x index of frame t's sample n (0 <= n < N) with center=True, pad_mode='reflect' (ref: src/audio.py:234-246); L > N/2.
+__device__ __forceinline__ int reflect_index(int i, int L) { return i < 0 ? -i : (i >= L ? 2 * (L - 1) - i : i); }
+
+// Overlap-add of the windowed frames at x index i (ref: lib/istft.py conv_transpose1d + window_envelop), without the
+// envelope: frames (T, win) of one utterance, frame t' covering padded positions [t' hop + left, t' hop + left + win).
+__device__ __forceinline__ float ola_at(const float* __restrict__ fr, int i, int T, int hop, int win, int half, int left) {
+    const int s = i + half - left;                 // >= 0 since half >= left
+    const int hi = min(T - 1, s / hop);
+    const int lo = s - win + 1 <= 0 ? 0 : (s - win + hop) / hop;
+    float acc = 0.0f;
+    for (int tp = lo; tp <= hi; ++tp) acc += fr[(size_t)tp * win + (s - tp * hop)];
+    return acc;
+}
+
+// C2R of the frame's spectrum (already merged + conjugated into buf) -> window -> frames_out.  buf holds conj(Z').
+template <int N>
+__device__ __forceinline__ void inverse_to_frame(float2* buf, const float2* __restrict__ tw, const float* __restrict__ wnd,
+                                                 float* __restrict__ out, int win) {
+    constexpr int M = N / 2;
+    fft_lds<M>(buf, tw);
+    const float* xr = reinterpret_cast<const float*>(buf);
+    const int left = (N - win) / 2;
+    const float scale = 1.0f / (float)M;          // exact (power of two)
+    for (int n2 = threadIdx.x; n2 < win; n2 += GL_THREADS) {
+        const int n = n2 + left;
+        const float v = (n & 1) ? -xr[n] : xr[n];    // x = conj(FFT(conj(Z'))) / M
+        out[n2] = v * scale * wnd[n2];
+    }
+}
+
+// ------------------------------------------------------------------ setup: window and inverse envelope (double)
+// wnd[n] = hann_window(win, periodic)[n] (ref: src/audio.py:35); inv_env[i] = 1 / sum_t' wpad(i + N/2 - t' hop)^2 for the
+// trimmed iSTFT output i in [0, L) (ref: lib/istft.py window_envelop, trimmed by n_fft//2).
+__global__ void gl_setup_kernel(float* __restrict__ wnd, float* __restrict__ inv_env, int N, int T, int hop, int win, int L) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < win) wnd[idx] = (float)(0.5 - 0.5 * cospi(2.0 * (double)idx / (double)win));
+    if (inv_env && idx < L) {
+        const int half = N / 2, left = (N - win) / 2;
+        const int s = idx + half - left;
+        const int hi = min(T - 1, s / hop);
+        const int lo = s - win + 1 <= 0 ? 0 : (s - win + hop) / hop;
+        double env = 0.0;
+        for (int tp = lo; tp <= hi; ++tp) {
+            const double w = 0.5 - 0.5 * cospi(2.0 * (double)(s - tp * hop) / (double)win);
+            env += w * w;
+        }
+        inv_env[idx] = (float)(1.0 / env);
+    }
+}
+
+// ------------------------------------------------------------------ first iSTFT
+// FROM_FEAT: Y = amp * e^{i phase} with amp from the (normalised) decoder output read through strides (the (B, T, F) -> (B, F, T)
+// transpose of src/audio.py:401 and the denormalisation of :186-188, :281-288 fused here; amp is also written to amp_out as
+// (B, T, F) for the iterations).  Else Y is a complex spectrum (B, T, F, 2).  Grid (T, B).
+template <int N, bool FROM_FEAT>
+__global__ __launch_bounds__(GL_THREADS) void gl_first_istft_kernel(const float* __restrict__ feat, long sb, long st, long sf,
+                                                                  int normalized, float power, const float* __restrict__ phases,
+                                                                  const float2* __restrict__ spec, float* __restrict__ amp_out,
+                                                                  const float* __restrict__ wnd, float* __restrict__ frames, int T,
+                                                                  int win) {
+    constexpr int M = N / 2, F = M + 1;
+    __shared__ float2 buf[M];
+    const float2* tw = tw_table<N>();
+    const int t = blockIdx.x, b = blockIdx.y;
+    const size_t frame = (size_t)b * T + t;
+    auto load_y = [&](int k) -> float2 {
+        if constexpr (FROM_FEAT) {
+            float a = feat[b * sb + t * st + k * sf];
+            if (normalized) {
+                a = MIN_LEVEL_DB + fminf(fmaxf(a, 0.0f), 1.0f) * -MIN_LEVEL_DB;     // _denormalize  (:287-288)
+                a = powf(10.0f, 0.05f * (a + REF_LEVEL_DB));                        // _db_to_amp(x + REF_LEVEL_DB)  (:187, :284)
+                if (power != 1.0f) a = powf(a, power);                               // ** power  (:188)
+            }
+            a = fabsf(a);                                                            // magnitude = specgram.abs()  (:217)
+            amp_out[frame * F + k] = a;
+            const float ph = phases[((size_t)b * F + k) * T + t];
+            return make_float2(a * cosf(ph), a * sinf(ph));                         // _to_complex  (:264-268)
+        } else {
+            return spec[frame * F + k];
+        }
+    };
+    for (int k = threadIdx.x; k <= M / 2; k += GL_THREADS) {
+        float2 yk = load_y(k), yc = load_y(M - k);
+        if (k == 0) { yk.y = 0.0f; yc.y = 0.0f; }
+        float2 zk, zc;
+        real_merge(yk, yc, tw[k], zk, zc);
+        buf[k] = cconj(zk);
+        if (k != 0 && k != M / 2) buf[M - k] = cconj(zc);
+    }
+    __syncthreads();
+    inverse_to_frame<N>(buf, tw, wnd, frames + frame * win, win);
+}
+
+// ------------------------------------------------------------------ one Griffin-Lim iteration (ref: src/audio.py:219-225)
+// x = istft(Y_prev) gathered from the previous frames (overlap-add / envelope, reflect-padded), STFT frame t of x, phase
+// projection Y = amp * X / |X| (angle(0) = 0: amp + 0i), then this frame of the next istft.  Grid (T, B).
+template <int N>
+__global__ __launch_bounds__(GL_THREADS) void gl_iter_kernel(const float* __restrict__ frames_in, float* __restrict__ frames_out,
+                                                           const float* __restrict__ amp, const float* __restrict__ wnd,
+                                                           const float* __restrict__ inv_env, int T, int hop, int win, int L) {
+    constexpr int M = N / 2, F = M + 1, HALF = N / 2;
+    __shared__ float2 buf[M];
+    float* xr = reinterpret_cast<float*>(buf);
+    const float2* tw = tw_table<N>();
+    const int t = blockIdx.x, b = blockIdx.y;
+    const int left = (N - win) / 2;
+    const float* fr = frames_in + (size_t)b * T * win;
+    for (int n = threadIdx.x; n < N; n += GL_THREADS) {
+        const int nn = n - left;
+        float v = 0.0f;
+        if (nn >= 0 && nn < win) {
+            const int i = reflect_index(t * hop + n - HALF, L);
+            v = ola_at(fr, i, T, hop, win, HALF, left) * inv_env[i] * wnd[nn];
+        }
+        xr[n] = v;
+    }
+    __syncthreads();
+    fft_lds<M>(buf, tw);
+    const float* a = amp + ((size_t)b * T + t) * F;
+    for (int k = threadIdx.x; k <= M / 2; k += GL_THREADS) {
+        const int c = M - k;
+        float2 xk, xc;
+        real_split(buf[k], buf[c & (M - 1)], tw[k], xk, xc);
+        const float ak = a[k], ac = a[c];
+        const float rk = sqrtf(xk.x * xk.x + xk.y * xk.y), rc = sqrtf(xc.x * xc.x + xc.y * xc.y);
+        float2 yk = rk > 0.0f ? make_float2(xk.x * (ak / rk), xk.y * (ak / rk)) : make_float2(ak, 0.0f);
+        float2 yc = rc > 0.0f ? make_float2(xc.x * (ac / rc), xc.y * (ac / rc)) : make_float2(ac, 0.0f);
+        if (k == 0) { yk.y = 0.0f; yc.y = 0.0f; }
+        float2 zk, zc;
+        real_merge(yk, yc, tw[k], zk, zc);
+        buf[k] = cconj(zk);
+        if (k != 0 && k != M / 2) buf[c] = cconj(zc);
+    }
+    __syncthreads();
+    inverse_to_frame<N>(buf, tw, wnd, frames_out + ((size_t)b * T + t) * win, win);
+}
+
+// ------------------------------------------------------------------ standalone STFT (ref: src/audio.py:234-246)
+// x (B, L) -> spec (B, T, F, 2), T = 1 + L / hop.  Grid (T, B).
+template <int N>
+__global__ __launch_bounds__(GL_THREADS) void stft_kernel(const float* __restrict__ x, float2* __restrict__ spec, int T, int hop,
+                                                        int win, int L) {
+    constexpr int M = N / 2, F = M + 1, HALF = N / 2;
+    __shared__ float2 buf[M];
+    float* xr = reinterpret_cast<float*>(buf);
+    const float2* tw = tw_table<N>();
+    const int t = blockIdx.x, b = blockIdx.y;
+    const int left = (N - win) / 2;
+    const float* xb = x + (size_t)b * L;
+    for (int n = threadIdx.x; n < N; n += GL_THREADS) {
+        const int nn = n - left;
+        float v = 0.0f;
+        if (nn >= 0 && nn < win) {
+            const float w = (float)(0.5 - 0.5 * cospi(2.0 * (double)nn / (double)win));
+            v = xb[reflect_index(t * hop + n - HALF, L)] * w;
+        }
+        xr[n] = v;
+    }
+    __syncthreads();
+    fft_lds<M>(buf, tw);
+    float2* out = spec + ((size_t)b * T + t) * F;
+    for (int k = threadIdx.x; k <= M / 2; k += GL_THREADS) {
+        float2 xk, xc;
+        real_split(buf[k], buf[(M - k) & (M - 1)], tw[k], xk, xc);
+        out[k] = xk;
+        if (k != M / 2) out[M - k] = xc;
+    }
+}
+
+// ------------------------------------------------------------------ final overlap-add (+ inverse pre-emphasis, clip)
+// One workgroup per utterance.  x[i] = OLA(frames)[i] * inv_env[i] (ref: lib/istft.py); post & 1: y[n] = x[n] + 0.97 y[n-1]
+// (scipy.signal.lfilter([1], [1, -0.97]), src/audio.py:274-276) as a blocked scan -- 16 samples per thread, an inclusive scan of
+// the 1024 chunk ends, the carry of one 16384-sample tile into the next; post & 2: clip to [-1, 1] (:192).
+__device__ __forceinline__ int ola_slot(int j) { return (j >> 4) * (OLA_CHUNK + 1) + (j & (OLA_CHUNK - 1)); }   // padded: no bank conflicts
+
+__global__ __launch_bounds__(OLA_THREADS) void gl_ola_post_kernel(const float* __restrict__ frames, const float* __restrict__ inv_env,
+                                                                 float* __restrict__ out, int N, int T, int hop, int win, int L, int post) {
+    __shared__ float xs[OLA_THREADS * (OLA_CHUNK + 1)];
+    __shared__ float scan[2][OLA_THREADS];
+    __shared__ float carry;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int half = N / 2, left = (N - win) / 2;
+    const float* fr = frames + (size_t)b * T * win;
+    float* ob = out + (size_t)b * L;
+    const float m16 = powf(INV_PREEMPH, (float)OLA_CHUNK);
+    if (tid == 0) carry = 0.0f;
+    for (int base = 0; base < L; base += OLA_TILE) {
+#pragma unroll 4
+        for (int q = 0; q < OLA_CHUNK; ++q) {
+            const int j = q * OLA_THREADS + tid, i = base + j;
+            xs[ola_slot(j)] = i < L ? ola_at(fr, i, T, hop, win, half, left) * inv_env[i] : 0.0f;
+        }
+        __syncthreads();
+        if (post & 1) {
+            float y = 0.0f;
+            float* mine = xs + tid * (OLA_CHUNK + 1);
+#pragma unroll
+            for (int q = 0; q < OLA_CHUNK; ++q) y = fmaf(INV_PREEMPH, y, mine[q]);
+            // inclusive scan of the chunk ends: V_j = v_j + m16 V_{j-1}
+            int cur = 0;
+            scan[cur][tid] = y;
+            __syncthreads();
+            float mult = m16;
+            for (int off = 1; off < OLA_THREADS; off <<= 1) {
+                const float v = scan[cur][tid] + (tid >= off ? mult * scan[cur][tid - off] : 0.0f);
+                scan[cur ^ 1][tid] = v;
+                cur ^= 1;
+                mult *= mult;
+                __syncthreads();
+            }
+            const float cin = carry;
+            // y just before this chunk: the scan of the chunks before it plus the tile's carry decayed over 16 * tid samples
+            float yp = tid == 0 ? cin : scan[cur][tid - 1] + powf(m16, (float)tid) * cin;
+#pragma unroll
+            for (int q = 0; q < OLA_CHUNK; ++q) {
+                yp = fmaf(INV_PREEMPH, yp, mine[q]);
+                mine[q] = yp;
+            }
+            __syncthreads();                                   // every thread has read `carry`
+            if (tid == OLA_THREADS - 1) carry = yp;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int q = 0; q < OLA_CHUNK; ++q) {
+            const int j = q * OLA_THREADS + tid, i = base + j;
+            if (i < L) {
+                float v = xs[ola_slot(j)];
+                if (post & 2) v = fminf(fmaxf(v, -1.0f), 1.0f);
+                ob[i] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ host side
+struct GlDims {
+    int N, hop, win, T, L;
+};
+
+size_t round64(size_t n) { return (n + 63) & ~(size_t)63; }
+constexpr size_t WND_FLOATS = 4096;
+
+// Supported: n_fft a power of two in [512, 4096], 0 < 2 hop <= win <= n_fft (every output sample then has a frame whose window
+// is non-zero there: the envelope never vanishes), and a signal of L > n_fft / 2 samples (reflect padding, as torch requires).
+int check_dims(const char* what, int B, int n_fft, int hop, int win, int T, long L) {
+    ST_CHECK_ARG(n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096,
+                 "%s: n_fft %d not supported (512, 1024, 2048, 4096)", what, n_fft);
+    ST_CHECK_ARG(hop > 0 && win <= n_fft && 2 * hop <= win,
+                 "%s: need 0 < 2 * hop <= win <= n_fft (hop %d, win %d, n_fft %d)", what, hop, win, n_fft);
+    ST_CHECK_ARG(L > n_fft / 2 && L < (1L << 30),
+                 "%s: reflect padding needs more than n_fft / 2 = %d samples (T %d frames, hop %d: %ld)", what, n_fft / 2, T, hop, L);
+    ST_CHECK_ARG(B > 0 && B <= 65535 && T >= 2 && (long)T * B * 4096 < (1L << 40), "%s: bad batch %d / frames %d", what, B, T);
+    return 0;
+}
+
+template <int N>
+void launch_first(bool from_feat, const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases,
+                  const float* spec, float* amp, const float* wnd, float* frames, int B, int T, int win, hipStream_t s) {
+    if (from_feat)
+        hipLaunchKernelGGL((gl_first_istft_kernel<N, true>), dim3(T, B), dim3(GL_THREADS), 0, s, feat, sb, st, sf, normalized, power,
+                           phases, (const float2*)nullptr, amp, wnd, frames, T, win);
+    else
+        hipLaunchKernelGGL((gl_first_istft_kernel<N, false>), dim3(T, B), dim3(GL_THREADS), 0, s, (const float*)nullptr, 0L, 0L, 0L,
+                           0, 1.0f, (const float*)nullptr, (const float2*)spec, (float*)nullptr, wnd, frames, T, win);
+}
+
+template <int N>
+void launch_iter(const float* fin, float* fout, const float* amp, const float* wnd, const float* inv_env, int B, int T, int hop, int win,
+                 int L, hipStream_t s) {
+    hipLaunchKernelGGL((gl_iter_kernel<N>), dim3(T, B), dim3(GL_THREADS), 0, s, fin, fout, amp, wnd, inv_env, T, hop, win, L);
+}
+
+#define ST_AUDIO_DISPATCH(n_fft, F, ...) \
+    switch (n_fft) {                     \
+        case 512: F<512>(__VA_ARGS__); break;   \
+        case 1024: F<1024>(__VA_ARGS__); break; \
+        case 2048: F<2048>(__VA_ARGS__); break; \
+        default: F<4096>(__VA_ARGS__); break;   \
+    }
+
+template <int N>
+void launch_stft(const float* x, float* spec, int B, int T, int hop, int win, int L, hipStream_t s) {
+    hipLaunchKernelGGL((stft_kernel<N>), dim3(T, B), dim3(GL_THREADS), 0, s, x, (float2*)spec, T, hop, win, L);
+}
+
+}  // namespace
+
+extern "C" size_t st_istft_workspace_floats(int B, int T, int n_fft, int hop, int win) {
+    if (B <= 0 || T <= 1 || hop <= 0 || win <= 0 || n_fft <= 0) return 0;
+    (void)n_fft;
+    return WND_FLOATS + round64((size_t)hop * (T - 1)) + round64((size_t)B * T * win);
+}
+
+extern "C" size_t st_gl_workspace_floats(int B, int T, int n_fft, int hop, int win) {
+    if (B <= 0 || T <= 1 || hop <= 0 || win <= 0 || n_fft <= 0) return 0;
+    return WND_FLOATS + round64((size_t)hop * (T - 1)) + round64((size_t)B * T * (n_fft / 2 + 1)) + 2 * round64((size_t)B * T * win);
+}
+
+extern "C" int st_stft_fwd(const float* x, float* spec, int B, int L, int n_fft, int hop, int win, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(x && spec && hop > 0 && L > 0, "st_stft_fwd: bad arguments");
+    const int T = 1 + L / hop;
+    int rc = check_dims("st_stft_fwd", B, n_fft, hop, win, T, L);
+    if (rc) return rc;
+    if ((rc = ensure_twiddles(stream)) != 0) return rc;
+    ST_AUDIO_DISPATCH(n_fft, launch_stft, x, spec, B, T, hop, win, L, (hipStream_t)stream);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_istft(const float* spec, float* x, int B, int T, int n_fft, int hop, int win, float* ws, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(spec && x && ws, "st_istft: null pointer");
+    int rc = check_dims("st_istft", B, n_fft, hop, win, T, (long)hop * (T - 1));
+    if (rc) return rc;
+    if ((rc = ensure_twiddles(stream)) != 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int L = hop * (T - 1);
+    float* wnd = ws;
+    float* inv_env = wnd + WND_FLOATS;
+    float* frames = inv_env + round64(L);
+    hipLaunchKernelGGL(gl_setup_kernel, dim3((max(L, win) + 255) / 256), dim3(256), 0, s, wnd, inv_env, n_fft, T, hop, win, L);
+    ST_AUDIO_DISPATCH(n_fft, launch_first, false, nullptr, 0, 0, 0, 0, 1.0f, nullptr, spec, nullptr, wnd, frames, B, T, win, s);
+    hipLaunchKernelGGL(gl_ola_post_kernel, dim3(B), dim3(OLA_THREADS), 0, s, frames, inv_env, x, n_fft, T, hop, win, L, 0);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases, float* wav,
+                              int B, int T, int n_fft, int hop, int win, int n_iter, int post, float* ws, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(feat && phases && wav && ws, "st_griffin_lim: null pointer");
+    ST_CHECK_ARG(n_iter >= 0 && (post & ~3) == 0 && power > 0.0f, "st_griffin_lim: bad n_iter %d / post %d / power", n_iter, post);
+    int rc = check_dims("st_griffin_lim", B, n_fft, hop, win, T, (long)hop * (T - 1));
+    if (rc) return rc;
+    if ((rc = ensure_twiddles(stream)) != 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int L = hop * (T - 1);
+    const int F = n_fft / 2 + 1;
+    float* wnd = ws;
+    float* inv_env = wnd + WND_FLOATS;
+    float* amp = inv_env + round64(L);
+    float* fr[2] = {amp + round64((size_t)B * T * F), nullptr};
+    fr[1] = fr[0] + round64((size_t)B * T * win);
+    hipLaunchKernelGGL(gl_setup_kernel, dim3((max(L, win) + 255) / 256), dim3(256), 0, s, wnd, inv_env, n_fft, T, hop, win, L);
+    ST_AUDIO_DISPATCH(n_fft, launch_first, true, feat, sb, st, sf, normalized, power, phases, nullptr, amp, wnd, fr[0], B, T, win, s);
+    for (int it = 0; it < n_iter; ++it)
+        ST_AUDIO_DISPATCH(n_fft, launch_iter, fr[it & 1], fr[(it + 1) & 1], amp, wnd, inv_env, B, T, hop, win, L, s);
+    hipLaunchKernelGGL(gl_ola_post_kernel, dim3(B), dim3(OLA_THREADS), 0, s, fr[n_iter & 1], inv_env, wav, n_fft, T, hop, win, L, post);
+    ST_LAUNCH_CHECK();
+    return 0;
+}

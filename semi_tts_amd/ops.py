@@ -1561,3 +1561,50 @@ def device_info():
     name = C.create_string_buffer(128)
     check(lib.st_device_info(C.byref(ncu), C.byref(lds), name, 128), 'st_device_info')
     return {'n_cu': ncu.value, 'lds_bytes': lds.value, 'name': name.value.decode()}
+
+
+# --------------------------------------------------------------------------------------------- Griffin-Lim vocoder (src/audio.py)
+def _audio_ws(fn, B, T, n_fft, hop, win, device):
+    n = fn(B, T, n_fft, hop, win)
+    if n == 0:
+        raise RuntimeError('semi_tts_amd: bad STFT dimensions B=%d T=%d n_fft=%d hop=%d win=%d' % (B, T, n_fft, hop, win))
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def stft_fwd(x, n_fft, hop, win):
+    """torch.stft(x (B, L), n_fft, hop, win, hann_window(win), center=True, pad_mode='reflect', onesided) on the HIP kernel:
+    -> (B, T, n_fft // 2 + 1, 2) float32, frame-major (re, im), T = 1 + L // hop."""
+    assert x.dim() == 2 and x.is_contiguous()
+    B, L = x.shape
+    spec = torch.empty(B, 1 + L // hop, n_fft // 2 + 1, 2, device=x.device, dtype=torch.float32)
+    check(_lib.load().st_stft_fwd(_p(x), _p(spec), B, L, n_fft, hop, win, stream_handle()), 'st_stft_fwd')
+    return spec
+
+
+def istft(spec, n_fft, hop, win):
+    """inverse of stft_fwd (lib/istft.py semantics, no `length`): spec (B, T, n_fft // 2 + 1, 2) -> (B, hop * (T - 1))"""
+    assert spec.dim() == 4 and spec.shape[2] == n_fft // 2 + 1 and spec.shape[3] == 2 and spec.is_contiguous()
+    B, T = spec.shape[:2]
+    lib = _lib.load()
+    ws = _audio_ws(lib.st_istft_workspace_floats, B, T, n_fft, hop, win, spec.device)
+    x = torch.empty(B, hop * (T - 1), device=spec.device, dtype=torch.float32)
+    check(lib.st_istft(_p(spec), _p(x), B, T, n_fft, hop, win, _p(ws), stream_handle()), 'st_istft')
+    return x
+
+
+GL_INV_PREEMPHASIS, GL_CLIP = 1, 2
+
+
+def griffin_lim(feat, phases, n_fft, hop, win, n_iter=30, normalized=False, power=1.0, post=0):
+    """st_griffin_lim: feat (B, T, F) in any strides (the decoder's (B, T, F) output or a transposed (B, F, T) magnitude),
+    phases (B, F, T) contiguous -> waveform (B, hop * (T - 1)).  post: GL_INV_PREEMPHASIS | GL_CLIP."""
+    assert feat.dim() == 3 and feat.shape[2] == n_fft // 2 + 1
+    B, T, F = feat.shape
+    assert phases.shape == (B, F, T) and phases.is_contiguous()
+    lib = _lib.load()
+    ws = _audio_ws(lib.st_gl_workspace_floats, B, T, n_fft, hop, win, feat.device)
+    wav = torch.empty(B, hop * (T - 1), device=feat.device, dtype=torch.float32)
+    sb, st, sf = feat.stride()
+    check(lib.st_griffin_lim(_p(feat), sb, st, sf, int(bool(normalized)), float(power), _p(phases), _p(wav), B, T, n_fft, hop, win,
+                             int(n_iter), int(post), _p(ws), stream_handle()), 'st_griffin_lim')
+    return wav

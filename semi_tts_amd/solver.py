@@ -117,6 +117,10 @@ class SpecgramGenerator(BaseSolver):
         cnt, frames_out, t0 = 0, 0, time.perf_counter()
         rank, world = getattr(self, 'rank', 0), getattr(self, 'world', 1)
         from .parallel import shard_range
+        gen_wav = bool(getattr(self.paras, 'gen_wav', False))
+        if gen_wav:
+            from .audio import load_audio_transform, write_wav
+            self.audio_converter = load_audio_transform(**self.config['data']['audio'])
         next_first = 0
         for frames, text, sid in self.test_set:
             batch_first, next_first = next_first, next_first + text.shape[0]
@@ -134,6 +138,9 @@ class SpecgramGenerator(BaseSolver):
             ops.check_persist_status(self.device)
             if not (bool(torch.isfinite(mel).all()) and bool(torch.isfinite(lin).all())):
                 raise RuntimeError('gen_specgram: non-finite spectrogram for batch starting at %s -- nothing written' % names[0])
+            wavs = None
+            if gen_wav:                                 # gen_specgram.py:114-115: Griffin-Lim of this rank's lin, on the device
+                wavs = self.audio_converter.gen_wav_device(lin).cpu().numpy()
             enc_step = (text != 0).sum(dim=-1).cpu().tolist()
             dec_step = [int(n * FRAME_PHN_RATIO) // r for n in enc_step]
             for i, (msp, sp, ali) in enumerate(zip(mel, lin, align)):
@@ -141,6 +148,8 @@ class SpecgramGenerator(BaseSolver):
                 np.save(name + '-mel.npy', msp.cpu().numpy().astype(np.float32), allow_pickle=False)
                 np.save(name + '-spec.npy', sp.cpu().numpy().astype(np.float32), allow_pickle=False)
                 np.save(name + '-align.npy', ali[:dec_step[i], :enc_step[i]].cpu().numpy())
+                if wavs is not None:                    # gen_specgram.py:125-126: the full padded length, as wavs[idx]
+                    write_wav(name + '-pred.wav', wavs[i], self.audio_converter.sr)
                 cnt += 1
                 frames_out += msp.shape[0]
         dt = time.perf_counter() - t0
