@@ -1149,6 +1149,32 @@ int st_istft(const float* spec, float* x, int B, int T, int n_fft, int hop, int 
 int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases, float* wav,
                    int B, int T, int n_fft, int hop, int win, int n_iter, int post, float* ws, void* stream);
 
+/* ------------------------------------------------------------------ feature extraction (waveforms -> normalised spectrograms)
+ * Replaces AudioProcessor.extract_feature_from_waveform (ref: src/audio.py:156-177) and AudioConverter.wave_to_feat's feature
+ * and augmentation steps (:329-395, add_noise / snr_coeff :409-416, :434-437) for a ragged batch: utterance b is
+ * x[off[b] .. off[b] + len[b]).  Each frame is the torch.stft frame (same conventions as st_stft_fwd, reflect padding at the
+ * utterance's own length) of the pre-emphasised signal y[0] = s[0], y[i] = s[i] - preemph * s[i-1] (preemph 0: none), built on
+ * the fly; the magnitude |X| gives linear = norm(|X|) and mel[m] = norm(sum_j |X|[fb_start[m] + j] * fb_w[fb_off[m] + j], j <
+ * fb_cnt[m]) -- the Slaney / area-normalised filterbank as contiguous bands -- with norm(a) = clamp((20 log10(max(a, 1e-5)) - 20
+ * + 100) / 100, 0, 1) (_amp_to_db, _normalize).  Outputs are time-major: mel (B, T_pad, n_mels), linear (B, T_pad, n_fft / 2 + 1)
+ * (null: not written), frames t >= 1 + len[b] / hop written as 0 (SPEC_PAD_VALUE), T_pad >= 1 + max len / hop.
+ * aug (B, Ta_pad, n_mels) (null: not written) is the augmented mel: its own framing aug_win[b] / aug_hop[b] (the time-stretched
+ * win / hop of :366-373), and s = x + coeff_b n with coeff_b = sqrt(sum x^2 / sum n^2 * 10^(-snr_db[b] / 10)) over the utterance
+ * (snr_db null, or NaN for an utterance: no noise).  n: `noise`, packed like x, or, when null, the built-in counter-based
+ * generator (Philox4x32-10, standard normal by Box-Muller) of (seed, b, sample index): no noise buffer exists.
+ * Host arrays: off, len, aug_win, aug_hop, snr_db (B entries, read before the call returns); everything else is on the device.
+ * Supported: n_fft in {512, 1024, 2048, 4096}, 0 < 2 * hop <= win <= n_fft for both framings, len[b] > n_fft / 2, B <= 64
+ * (anything else returns -22).  ws: st_features_workspace_floats(B) floats.  One launch (clean + augmented framings as the
+ * two z-slices of one grid), plus one before it for the per-utterance power sums when there is noise.  No atomics: bitwise
+ * repeatable for a given seed. */
+size_t st_features_workspace_floats(int B);
+int st_audio_features(const float* x, long n_samples, const float* noise, unsigned long long seed, const long* off, const int* len,
+                      const int* aug_win, const int* aug_hop, const float* snr_db, int B, int n_fft, int win, int hop, float preemph,
+                      const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels, float* mel,
+                      float* linear, int T_pad, float* aug, int Ta_pad, float* ws, void* stream);
+/* out[i] = the built-in generator's standard normal for (seed, utterance utt, sample i), i < n (for tests) */
+int st_feature_noise(float* out, long n, int utt, unsigned long long seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

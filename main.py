@@ -42,6 +42,9 @@ parser.add_argument('--batch-size', default=None, type=int)
 parser.add_argument('--n-batches', default=1, type=int)
 parser.add_argument('--unpair-batch-size', default=None, type=int, help='utterances per synthetic unpaired batch (default: --batch-size)')
 parser.add_argument('--unpair-frames', default=None, type=int, help='mel frames per synthetic unpaired utterance (default: --frames)')
+parser.add_argument('--unpair-wav-dir', default=None, type=str, help='unpaired batches: (mel, aug_mel, linear) extracted on the GPU from the '
+                    '.wav files of this directory, sorted by name, batched by --unpair-batch-size, fresh augmentation every fetch '
+                    '(text / sid stay synthetic)')
 parser.add_argument('--stretch', action='store_true', help='aug_mel lengths drawn from data.audio.time_stretch_range (default: unstretched)')
 parser.add_argument('--tts-only', action='store_true', help='train the paired TTS branch alone (TtsTrainer) instead of the two cycles')
 parser.add_argument('--max-step', default=None, type=int, help='training steps (default: hparas.max_step)')
@@ -69,6 +72,9 @@ def parse_args(argv=None):
         if getattr(paras, flag):
             parser.error('--%s: the reference dispatches this mode to %s, which is not part of the reference tree; '
                          'only the default (training) and --gen-specgram modes exist' % (flag.replace('_', '-'), path))
+    if paras.unpair_wav_dir is not None and (paras.tts_only or paras.gen_specgram):
+        parser.error('--unpair-wav-dir feeds the unpaired batches of the two cycles; it does not combine with --%s'
+                     % ('tts-only' if paras.tts_only else 'gen-specgram'))
     if paras.verbose:
         for flag in IGNORED_FLAGS:
             if flag == 'gen_wav' and paras.gen_specgram:

@@ -1,13 +1,20 @@
-"""Synthesis side of the reference's src/audio.py: linear spectrogram -> waveform by Griffin-Lim on the HIP kernels
-(semi_tts_amd/csrc/audio.hip, include/semitts.h st_griffin_lim / st_stft_fwd / st_istft).
+"""The reference's src/audio.py on the HIP kernels (semi_tts_amd/csrc/audio.hip, include/semitts.h).  Synthesis side: linear
+spectrogram -> waveform by Griffin-Lim (st_griffin_lim / st_stft_fwd / st_istft).
 
     conv = load_audio_transform(**config['data']['audio'])
     wav, sr = conv.feat_to_wave(linear_pred)          # (T, F) or (B, T, F), CPU or device tensor -> float64 numpy
     write_wav('utt-pred.wav', wav[0], sr)
 
-Only the linear branch of feat_to_wave (src/audio.py:397-407) is here: the mel -> linear pseudo-inverse (:194-205) needs the
-reference's librosa filterbank (lib/filters.py) and raises NotImplementedError.  Training-side feature extraction is not here.
+Only the linear branch of feat_to_wave (src/audio.py:397-407) is here: the mel -> linear pseudo-inverse (:194-205) raises
+NotImplementedError.
+
+Analysis side (st_audio_features): waveform -> normalised mel / linear spectrograms and the augmented mel of the training loader.
+
+    conv = load_audio_transform(**config['data']['audio'])
+    msp, msp_aug, sp = conv.wave_to_feat('utt.wav')              # (T, n_mels), (T', n_mels), (T, F): src/audio.py:329-395
+    mel, aug_mel, linear = conv.extract_batch(wavs, r=5)       # a ragged batch on the device, longest first (src/data.py:130)
 """
+import random
 import wave
 
 import numpy as np
@@ -20,6 +27,7 @@ MIN_LEVEL_DB = -100               # src/audio.py:17
 REF_LEVEL_DB = 20                 # src/audio.py:18
 INV_PREEMPHASIS_COEFF = 0.97      # the literal of src/audio.py:276 (_inv_preemphasis ignores preemphasis_coeff)
 SUPPORTED_N_FFT = (512, 1024, 2048, 4096)
+SNR_OFF = float('nan')            # extract_batch(snr=SNR_OFF): no noise (the reference's -1 in snr_range)
 
 # the shipped configs' data.audio (identical in all three YAMLs): num_freq 1025, 12.5 / 50 ms at 22050 Hz
 DEFAULT_N_FFT, DEFAULT_HOP, DEFAULT_WIN = 2048, 275, 1102
@@ -82,11 +90,15 @@ def griffin_lim(amp, phases=None, n_iter=GFL_ITER, n_fft=DEFAULT_N_FFT, hop=DEFA
 
 
 class AudioConverter:
-    """The synthesis methods of the reference's AudioProcessor / AudioConverter (src/audio.py:23, :292) for the linear branch."""
+    """The reference's AudioProcessor / AudioConverter (src/audio.py:23, :292): feature extraction (clean and augmented) and
+    the synthesis methods for the linear branch."""
 
     def __init__(self, num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear=True,
-                 **_unused):
+                 snr_range=(-1, -1), time_stretch_range=(1.0, 1.0), **_unused):
         self.n_fft, self.hop_length, self.win_length = stft_dims(num_freq, frame_shift_ms, frame_length_ms, sample_rate)
+        self.frame_length_ms, self.frame_shift_ms = frame_length_ms, frame_shift_ms
+        self.snr_range, self.time_stretch_range = list(snr_range), list(time_stretch_range)
+        self._fb = {}
         self.num_freq, self.n_mels = num_freq, num_mels
         self.preemphasis_coeff = preemphasis_coeff       # read by the reference's _preemphasis only, never by the inverse (:274-276)
         self.sr = sample_rate
@@ -114,6 +126,101 @@ class AudioConverter:
                                       "needs librosa's filterbank and is not implemented; pass the linear spectrogram" % feat.size(-1))
         return self.specgram_to_waveform(feat.transpose(-2, -1), phases=phases), self.sr
 
+    # -- analysis side (src/audio.py:68-77, 156-177, 329-395)
+    def load(self, wav_path):
+        """src/audio.py:68-77: (channels, samples) float32; a different sample rate raises"""
+        return load_wav(wav_path, self.sr)
+
+    def stretch_dims(self, rate):
+        """(win, hop) of the augmented framing at stretch `rate`, exactly as src/audio.py:366-373"""
+        stretch_sr = int(self.sr * rate)
+        return int(self.frame_length_ms / 1000 * stretch_sr), int(self.frame_shift_ms / 1000 * stretch_sr)
+
+    def filterbank(self, device):
+        """the mel filterbank as the kernel takes it, cached per device: (start bin, count, offset) per mel + packed weights"""
+        key = str(device)
+        if key not in self._fb:
+            start, cnt, off, w = band_pack(mel_filterbank(self.sr, self.n_fft, self.n_mels))
+            self._fb[key] = tuple(torch.from_numpy(a).to(device) for a in (start, cnt, off, w))
+        return self._fb[key]
+
+    def _check(self, lens, aug_dims=()):
+        """every refusal of st_audio_features, raised before any device is touched"""
+        if self.n_fft not in SUPPORTED_N_FFT:
+            raise ValueError('features: n_fft %d not supported (one of %s)' % (self.n_fft, SUPPORTED_N_FFT))
+        for win, hop, what in [(self.win_length, self.hop_length, 'clean')] + [(w, h, 'augmented') for w, h in aug_dims]:
+            if not (0 < 2 * hop <= win <= self.n_fft):
+                raise ValueError('features: the %s framing needs 0 < 2 * hop <= win <= n_fft (hop %d, win %d, n_fft %d)'
+                                 % (what, hop, win, self.n_fft))
+        for L in lens:
+            if L <= self.n_fft // 2:
+                raise ValueError('features: an utterance of %d samples is too short: reflect padding needs more than n_fft // 2 = %d'
+                                 % (L, self.n_fft // 2))
+
+    def extract_feature_from_waveform(self, waveform, preemphasis=True, channel=0):
+        """src/audio.py:156-177: waveform (channels, samples) -> (specgram (F, T), melspecgram (n_mels, T)) of `channel`, normalised,
+        on the waveform's device (computed on the GPU either way)"""
+        x = torch.as_tensor(waveform)
+        x = x[channel] if x.dim() == 2 else x
+        self._check([x.shape[-1]])
+        dev = x.device if x.is_cuda else _device()
+        xd = x.to(dev, torch.float32).contiguous()
+        T = 1 + xd.numel() // self.hop_length
+        mel, lin, _ = ops.audio_features(xd, [0], [xd.numel()], self.n_fft, self.win_length, self.hop_length,
+                                         self.preemphasis_coeff if preemphasis else 0.0, self.filterbank(dev), T)
+        return lin[0].t().to(x.device), mel[0].t().to(x.device)
+
+    def _draw(self):
+        """one utterance's augmentation draws in the order of src/audio.py:356-364: (snr or None, stretch rate)"""
+        snr = None if -1 in self.snr_range else random.uniform(self.snr_range[0], self.snr_range[1])
+        return snr, random.uniform(self.time_stretch_range[0], self.time_stretch_range[1])
+
+    def wave_to_feat(self, file):
+        """src/audio.py:329-395: -> (msp (T, n_mels), msp_aug (T', n_mels), sp (T, F) or None) as CPU tensors.  The SNR and the
+        stretch rate are drawn from `random`; the noise comes from the kernel's generator, seeded from torch's."""
+        wave = self.load(file)
+        mel, aug, lin = self.extract_batch([wave[0]])
+        return mel[0].cpu(), aug[0].cpu(), lin[0].cpu() if lin is not None else None
+
+    def extract_batch(self, wavs, r=None, seed=None, snr=None, stretch=None, noise=None):
+        """The training loader's features for a ragged batch in one launch sequence (collect_fn + fetch_data, src/data.py:120-140,
+        bin/train_vqvae.py:33-53): wavs, a list of 1-D waveforms (or a WaveBatch), sorted longest first.  -> device tensors
+        (mel (B, T_pad, n_mels), aug_mel (B, Ta_pad, n_mels), linear (B, T_pad, F) or None when use_linear is off); mel / linear
+        padded with zero frames to a multiple of r with at least one extra frame (r None: to the longest), aug_mel to its own
+        longest.  snr / stretch: None draws them per utterance as wave_to_feat does; else one value or one per utterance (in the
+        sorted order); an SNR of SNR_OFF (NaN), or None inside a list, means no noise.  noise: explicit noise waveforms, one per utterance of wavs (for
+        tests); else the generator of `seed` (None: drawn from torch's generator)."""
+        wb = wavs if isinstance(wavs, WaveBatch) else WaveBatch(wavs)
+        B = len(wb.lens)
+        per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * B    # noqa: E731
+        if snr is None or stretch is None:
+            draws = [self._draw() for _ in range(B)]
+            snr = [d[0] for d in draws] if snr is None else snr
+            stretch = [d[1] for d in draws] if stretch is None else stretch
+        snr, stretch = per(snr), per(stretch)
+        if len(snr) != B or len(stretch) != B:
+            raise ValueError('features: %d utterances, %d SNRs and %d stretch rates' % (B, len(snr), len(stretch)))
+        aug_dims = [self.stretch_dims(s) for s in stretch]
+        self._check(wb.lens, aug_dims)
+        snr_db = np.array([np.nan if v is None else v for v in snr], np.float32)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)))
+        dev = wb.device if wb.device is not None else _device()
+        x = wb.packed(dev)
+        nz = None
+        if noise is not None:
+            nz = WaveBatch(noise, order=wb.order).packed(dev)
+            if nz.shape != x.shape:
+                raise ValueError('features: the noise waveforms do not have the lengths of the utterances')
+        T = 1 + wb.lens // self.hop_length
+        T_pad = int(T.max()) if r is None else int(T.max()) + r - int(T.max()) % r
+        Ta_pad = max(1 + L // h for L, (_, h) in zip(wb.lens, aug_dims))
+        mel, lin, aug = ops.audio_features(x, wb.offsets, wb.lens, self.n_fft, self.win_length, self.hop_length, self.preemphasis_coeff,
+                                           self.filterbank(dev), T_pad, with_linear=self.use_linear,
+                                           aug_win=[d[0] for d in aug_dims], aug_hop=[d[1] for d in aug_dims], Ta_pad=Ta_pad,
+                                           snr_db=snr_db, noise=nz, seed=seed)
+        return mel, aug, lin
+
     def gen_wav_device(self, lin, phases=None):
         """feat_to_wave for a device batch (B, T, F) without the host copy: -> (B, hop * (T - 1)) device tensor (SpecgramGenerator)"""
         if lin.size(-1) != self.num_freq:
@@ -124,8 +231,85 @@ class AudioConverter:
 
 def load_audio_transform(num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear=True,
                          **kwargs):
-    """src/audio.py:439-448 (the training-side arguments -- snr_range, time_stretch_range, segment_* -- are accepted and unused)"""
+    """src/audio.py:439-448 (segment_file / segment_feat / min_segment_len -- the phone-segment features -- are accepted and unused)"""
     return AudioConverter(num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear, **kwargs)
+
+
+class WaveBatch:
+    """a ragged batch of 1-D waveforms sorted longest first (stable: src/data.py:130), packed into one float32 buffer the first
+    time a device asks for it and kept there: `order[i]` is the index in the given list of the i-th utterance"""
+
+    def __init__(self, wavs, order=None):
+        wavs = [torch.as_tensor(w).reshape(-1) for w in wavs]
+        if not wavs:
+            raise ValueError('features: an empty batch')
+        lens = np.array([w.numel() for w in wavs], np.int64)
+        self.order = np.argsort(-lens, kind='stable') if order is None else np.asarray(order)
+        self._wavs = [wavs[i] for i in self.order]
+        self.lens = lens[self.order]
+        self.offsets = np.concatenate([[0], np.cumsum(self.lens)[:-1]]).astype(np.int64)
+        self.device = self._wavs[0].device if self._wavs[0].is_cuda else None
+        self._packed = {}
+
+    def packed(self, device):
+        key = str(device)
+        if key not in self._packed:
+            self._packed[key] = torch.cat([w.to(device, torch.float32) for w in self._wavs]).contiguous()
+        return self._packed[key]
+
+
+def hz_to_mel(f):
+    """Slaney's mel scale (Auditory Toolbox): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per factor 6.4)"""
+    f = np.asarray(f, np.float64)
+    lin = f / (200.0 / 3)
+    logs = 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / (np.log(6.4) / 27.0)
+    return np.where(f >= 1000.0, logs, lin)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), (200.0 / 3) * m)
+
+
+def mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None):
+    """(n_mels, n_fft // 2 + 1) float32 filterbank: triangles between n_mels + 2 points equally spaced on the Slaney mel scale
+    from fmin to fmax (default sr / 2), each scaled by 2 / (f[m + 2] - f[m]) to unit area (Slaney normalisation).  Float64
+    throughout, cast at the end (the reference's create_mel_filterbank, lib/filters.py)."""
+    fmax = sr / 2.0 if fmax is None else fmax
+    freqs = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
+    f = mel_to_hz(np.linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2))
+    rise = (freqs[None, :] - f[:-2, None]) / (f[1:-1] - f[:-2])[:, None]
+    fall = (f[2:, None] - freqs[None, :]) / (f[2:] - f[1:-1])[:, None]
+    w = np.maximum(0.0, np.minimum(rise, fall)) * (2.0 / (f[2:] - f[:-2]))[:, None]
+    return w.astype(np.float32)
+
+
+def band_pack(fb):
+    """a filterbank (n_mels, F) whose rows are single contiguous bands -> int32 (start, count, offset) per row and the packed
+    float32 weights of every band, back to back"""
+    start, cnt, w = [], [], []
+    for row in np.asarray(fb, np.float32):
+        nz = np.flatnonzero(row)
+        s, e = (int(nz[0]), int(nz[-1]) + 1) if nz.size else (0, 0)
+        start.append(s)
+        cnt.append(e - s)
+        w.append(row[s:e])
+    off = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+    return (np.array(start, np.int32), np.array(cnt, np.int32), off.astype(np.int32),
+            np.concatenate(w).astype(np.float32) if w else np.zeros(0, np.float32))
+
+
+def load_wav(path, sample_rate=None):
+    """16-bit PCM .wav through the standard library, scaled by 1 / 32768 as torchaudio.load: -> (channels, samples) float32.
+    A sample rate other than `sample_rate` raises (src/audio.py:70-77)."""
+    with wave.open(str(path), 'rb') as w:
+        sr, ch, width = w.getframerate(), w.getnchannels(), w.getsampwidth()
+        if width != 2:
+            raise ValueError('load_wav: %s is %d-bit; only 16-bit PCM is read' % (path, 8 * width))
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2')
+    if sample_rate is not None and sr != sample_rate:
+        raise ValueError('Sample rate mismatch. Expected %d but get %d (%s)' % (sample_rate, sr, path))
+    return torch.from_numpy(np.ascontiguousarray(pcm.reshape(-1, ch).T, dtype=np.float32) / 32768.0)
 
 
 def write_wav(path, wav, sr):

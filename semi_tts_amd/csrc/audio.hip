@@ -1,4 +1,5 @@
-// audio.hip -- Griffin-Lim vocoder: linear spectrogram -> waveform (ref: src/audio.py:179-262, 274-288)
+// audio.hip -- Griffin-Lim vocoder: linear spectrogram -> waveform (ref: src/audio.py:179-262, 274-288), and feature extraction:
+// waveforms -> normalised mel / linear spectrograms, clean and augmented (ref: src/audio.py:156-177, 329-395)
 //
 // Every FFT is a real n_fft-point transform done as an (n_fft/2)-point complex Stockham FFT in LDS (radix 4, one radix-2 stage
 // when log2(n_fft/2) is odd) plus the real split pass.  Twiddles e^{-2 pi i k / n_fft} come from tables computed in double on the
@@ -393,6 +394,186 @@ __global__ __launch_bounds__(OLA_THREADS) void gl_ola_post_kernel(const float* _
     }
 }
 
+// ------------------------------------------------------------------ feature extraction (ref: src/audio.py:156-177, 329-395, 409-437)
+// Waveforms -> normalised mel (+ linear) spectrograms, the clean framing and the augmented one (noise at an SNR, time-stretched
+// win / hop) in one launch of one workgroup per (frame, utterance, framing).  The per-utterance metadata travels by value.
+constexpr int FEAT_MAX_B = 64;
+constexpr float AMP_FLOOR = 1e-5f;                           // _amp_to_db's minimum (:278)
+
+struct FeatMeta {
+    long off[FEAT_MAX_B];      // first sample of utterance b in the packed buffer
+    int len[FEAT_MAX_B];       // its length L_b
+    int awin[FEAT_MAX_B];      // augmented framing: win, hop of the stretched rate (:366-373)
+    int ahop[FEAT_MAX_B];
+    float snr[FEAT_MAX_B];     // dB; NaN: no noise for this utterance (:356-359)
+};
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter (i, b, 0, 0), key = the seed.
+__device__ __forceinline__ uint4 philox4x32(uint4 c, uint2 k) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
+        const unsigned lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
+        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
+        k.x += 0x9E3779B9u;
+        k.y += 0xBB67AE85u;
+    }
+    return c;
+}
+
+// standard normal for (seed, utterance b, sample i): Box-Muller on two 24-bit uniforms, u1 in (0, 1], u2 in [0, 1)
+__device__ __forceinline__ float feat_normal(unsigned long long seed, int b, long i) {
+    const uint4 r = philox4x32(make_uint4((unsigned)i, (unsigned)(i >> 32), (unsigned)b, 0u),
+                               make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
+    const float u1 = (float)((r.x >> 8) + 1u) * (1.0f / 16777216.0f);
+    const float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
+
+__global__ void feat_noise_kernel(float* __restrict__ out, long n, int b, unsigned long long seed) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = feat_normal(seed, b, i);
+}
+
+// The power sums of snr_coeff (:434-437): sum x^2 and sum n^2 of utterance b in POW_PARTS fixed slices, one workgroup each,
+// fixed-order double sums into part[(b * POW_PARTS + p) * 2 + {0, 1}]; the frame kernel adds the slices in order (feat_coeff).
+// No atomics: deterministic.
+constexpr int POW_THREADS = 256;
+constexpr int POW_PARTS = 64;
+__global__ __launch_bounds__(POW_THREADS) void feat_power_kernel(const float* __restrict__ x, const float* __restrict__ noise,
+                                                                 unsigned long long seed, FeatMeta meta, double* __restrict__ part) {
+    __shared__ double sx[POW_THREADS], sn[POW_THREADS];
+    const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const long off = meta.off[b];
+    const int L = meta.len[b];
+    const int chunk = (L + POW_PARTS - 1) / POW_PARTS;
+    const int i0 = p * chunk, i1 = min(L, i0 + chunk);
+    double ax = 0.0, an = 0.0;
+    if (!isnan(meta.snr[b])) {
+        for (int i = i0 + tid; i < i1; i += POW_THREADS) {
+            const double v = x[off + i];
+            const double n = noise ? (double)noise[off + i] : (double)feat_normal(seed, b, i);
+            ax += v * v;
+            an += n * n;
+        }
+    }
+    sx[tid] = ax;
+    sn[tid] = an;
+    __syncthreads();
+    for (int s = POW_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            sx[tid] += sx[tid + s];
+            sn[tid] += sn[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        part[((size_t)b * POW_PARTS + p) * 2] = sx[0];
+        part[((size_t)b * POW_PARTS + p) * 2 + 1] = sn[0];
+    }
+}
+
+// coeff = sqrt(sum x^2 / sum n^2 * 10^(-snr / 10)); 0 without noise
+__device__ __forceinline__ float feat_coeff(const double* __restrict__ part, int b, float snr) {
+    if (isnan(snr)) return 0.0f;
+    double ax = 0.0, an = 0.0;
+    for (int p = 0; p < POW_PARTS; ++p) {
+        ax += part[((size_t)b * POW_PARTS + p) * 2];
+        an += part[((size_t)b * POW_PARTS + p) * 2 + 1];
+    }
+    return an > 0.0 ? (float)sqrt(ax / an * pow(10.0, -0.1 * (double)snr)) : 0.0f;
+}
+
+// clamp((20 log10(max(a, 1e-5)) - REF_LEVEL_DB - MIN_LEVEL_DB) / -MIN_LEVEL_DB, 0, 1)    (_amp_to_db, _normalize: :278-285)
+__device__ __forceinline__ float feat_norm_db(float a) {
+    const float db = 20.0f * log10f(fmaxf(a, AMP_FLOOR)) - REF_LEVEL_DB;
+    return fminf(fmaxf((db - MIN_LEVEL_DB) / -MIN_LEVEL_DB, 0.0f), 1.0f);
+}
+
+// Grid (max(T_pad, Ta_pad), B, 1 or 2).  z = 0: the clean framing (win, hop) -> mel (B, T_pad, n_mels) and linear (B, T_pad, F)
+// when non-null; z = 1: the augmented framing (meta.awin / ahop, noise times coeff[b]) -> aug (B, Ta_pad, n_mels).  Frame t of
+// utterance b is the torch.stft frame (centre, reflect padding at L_b) of y[i] = s[i] - c s[i-1], s = x + coeff n; frames
+// t >= 1 + L_b / hop are written as 0 (SPEC_PAD_VALUE).  Mel m sums mag[fb_start[m] + j] * fb_w[fb_off[m] + j], j < fb_cnt[m].
+template <int N>
+__global__ __launch_bounds__(GL_THREADS) void features_kernel(const float* __restrict__ x, const float* __restrict__ noise,
+                                                            unsigned long long seed, const double* __restrict__ part, FeatMeta meta,
+                                                            float c, int win, int hop, const int* __restrict__ fb_start,
+                                                            const int* __restrict__ fb_cnt, const int* __restrict__ fb_off,
+                                                            const float* __restrict__ fb_w, int n_mels, float* __restrict__ mel,
+                                                            float* __restrict__ linear, float* __restrict__ aug, int T_pad, int Ta_pad) {
+    constexpr int M = N / 2, F = M + 1, HALF = N / 2;
+    __shared__ float2 buf[M];
+    __shared__ float mag[F];
+    float* xr = reinterpret_cast<float*>(buf);
+    const float2* tw = tw_table<N>();
+    const int t = blockIdx.x, b = blockIdx.y;
+    const bool is_aug = blockIdx.z == 1;
+    const int Tp = is_aug ? Ta_pad : T_pad;
+    if (t >= Tp) return;
+    const int L = meta.len[b];
+    if (is_aug) {
+        win = meta.awin[b];
+        hop = meta.ahop[b];
+    }
+    float* mrow = (is_aug ? aug : mel) + ((size_t)b * Tp + t) * n_mels;
+    float* lrow = is_aug || !linear ? nullptr : linear + ((size_t)b * Tp + t) * F;
+    if (t >= 1 + L / hop) {                                  // padding frame
+        for (int m = threadIdx.x; m < n_mels; m += GL_THREADS) mrow[m] = 0.0f;
+        if (lrow)
+            for (int k = threadIdx.x; k < F; k += GL_THREADS) lrow[k] = 0.0f;
+        return;
+    }
+    const float* xb = x + meta.off[b];
+    const float* nb = noise ? noise + meta.off[b] : nullptr;
+    __shared__ float cn_s;
+    if (threadIdx.x == 0) cn_s = is_aug && part ? feat_coeff(part, b, meta.snr[b]) : 0.0f;
+    __syncthreads();
+    const float cn = cn_s;
+    auto sample = [&](int i) -> float {                      // x + coeff n (add_noise, :411-416)
+        float v = xb[i];
+        if (cn != 0.0f) v = fmaf(cn, nb ? nb[i] : feat_normal(seed, b, i), v);
+        return v;
+    };
+    const int left = (N - win) / 2;
+    for (int n = threadIdx.x; n < N; n += GL_THREADS) {
+        const int nn = n - left;
+        float v = 0.0f;
+        if (nn >= 0 && nn < win) {
+            const float w = (float)(0.5 - 0.5 * cospi(2.0 * (double)nn / (double)win));
+            const int i = reflect_index(t * hop + n - HALF, L);
+            const float y = i == 0 ? sample(0) : fmaf(-c, sample(i - 1), sample(i));     // _preemphasis (:228-232)
+            v = y * w;
+        }
+        xr[n] = v;
+    }
+    __syncthreads();
+    fft_lds<M>(buf, tw);
+    for (int k = threadIdx.x; k <= M / 2; k += GL_THREADS) {
+        float2 xk, xc;
+        real_split(buf[k], buf[(M - k) & (M - 1)], tw[k], xk, xc);
+        mag[k] = sqrtf(xk.x * xk.x + xk.y * xk.y);
+        if (k != M / 2) mag[M - k] = sqrtf(xc.x * xc.x + xc.y * xc.y);
+    }
+    __syncthreads();
+    if (lrow)
+        for (int k = threadIdx.x; k < F; k += GL_THREADS) lrow[k] = feat_norm_db(mag[k]);
+    for (int m = threadIdx.x; m < n_mels; m += GL_THREADS) {
+        const int k0 = min(max(fb_start[m], 0), F), cnt = min(fb_cnt[m], F - k0);       // (a malformed band reads nothing outside mag)
+        const float* w = fb_w + fb_off[m];
+        float a = 0.0f;
+        for (int j = 0; j < cnt; ++j) a = fmaf(mag[k0 + j], w[j], a);
+        mrow[m] = feat_norm_db(a);
+    }
+}
+
+template <int N>
+void launch_features(const float* x, const float* noise, unsigned long long seed, const double* part, const FeatMeta& meta, float c,
+                     int win, int hop, const int* fs, const int* fc, const int* fo, const float* fw, int n_mels, float* mel,
+                     float* linear, float* aug, int B, int T_pad, int Ta_pad, hipStream_t s) {
+    const dim3 grid(max(T_pad, aug ? Ta_pad : 0), B, aug ? 2 : 1);
+    hipLaunchKernelGGL((features_kernel<N>), grid, dim3(GL_THREADS), 0, s, x, noise, seed, part, meta, c, win, hop, fs, fc, fo, fw,
+                       n_mels, mel, linear, aug, T_pad, Ta_pad);
+}
+
 // ------------------------------------------------------------------ host side
 struct GlDims {
     int N, hop, win, T, L;
@@ -508,6 +689,66 @@ extern "C" int st_griffin_lim(const float* feat, long sb, long st, long sf, int 
     for (int it = 0; it < n_iter; ++it)
         ST_AUDIO_DISPATCH(n_fft, launch_iter, fr[it & 1], fr[(it + 1) & 1], amp, wnd, inv_env, B, T, hop, win, L, s);
     hipLaunchKernelGGL(gl_ola_post_kernel, dim3(B), dim3(OLA_THREADS), 0, s, fr[n_iter & 1], inv_env, wav, n_fft, T, hop, win, L, post);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+
+extern "C" size_t st_features_workspace_floats(int B) { return B > 0 ? round64((size_t)B * POW_PARTS * 4) : 0; }
+
+extern "C" int st_feature_noise(float* out, long n, int utt, unsigned long long seed, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(out && n > 0 && utt >= 0, "st_feature_noise: bad arguments");
+    hipLaunchKernelGGL(feat_noise_kernel, dim3((unsigned)min((n + 255) / 256, 4096L)), dim3(256), 0, (hipStream_t)stream, out, n, utt, seed);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_audio_features(const float* x, long n_samples, const float* noise, unsigned long long seed, const long* off, const int* len,
+                                 const int* aug_win, const int* aug_hop, const float* snr_db, int B, int n_fft, int win, int hop,
+                                 float preemph, const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels,
+                                 float* mel, float* linear, int T_pad, float* aug, int Ta_pad, float* ws, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(x && off && len && fb_start && fb_cnt && fb_off && fb_w && mel && ws, "st_audio_features: null pointer");
+    ST_CHECK_ARG(!aug || (aug_win && aug_hop), "st_audio_features: the augmented framing needs aug_win / aug_hop");
+    ST_CHECK_ARG(B > 0 && B <= FEAT_MAX_B, "st_audio_features: batch %d outside [1, %d]", B, FEAT_MAX_B);
+    ST_CHECK_ARG(n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096,
+                 "st_audio_features: n_fft %d not supported (512, 1024, 2048, 4096)", n_fft);
+    ST_CHECK_ARG(n_mels > 0 && n_mels <= n_fft / 2 + 1, "st_audio_features: %d mels for n_fft %d", n_mels, n_fft);
+    ST_CHECK_ARG(hop > 0 && 2 * hop <= win && win <= n_fft, "st_audio_features: need 0 < 2 * hop <= win <= n_fft (hop %d, win %d, n_fft %d)",
+                 hop, win, n_fft);
+    FeatMeta meta;
+    int tmax = 0, tamax = 0;
+    for (int b = 0; b < B; ++b) {
+        ST_CHECK_ARG(len[b] > n_fft / 2, "st_audio_features: utterance %d has %d samples: reflect padding needs more than n_fft / 2 = %d",
+                     b, len[b], n_fft / 2);
+        ST_CHECK_ARG(off[b] >= 0 && off[b] + len[b] <= n_samples, "st_audio_features: utterance %d [%ld, +%d) outside the %ld samples", b,
+                     off[b], len[b], n_samples);
+        meta.off[b] = off[b];
+        meta.len[b] = len[b];
+        tmax = max(tmax, 1 + len[b] / hop);
+        meta.awin[b] = win;
+        meta.ahop[b] = hop;
+        meta.snr[b] = snr_db ? snr_db[b] : NAN;
+        if (aug) {
+            ST_CHECK_ARG(aug_hop[b] > 0 && 2 * aug_hop[b] <= aug_win[b] && aug_win[b] <= n_fft,
+                         "st_audio_features: utterance %d: augmented framing needs 0 < 2 * hop <= win <= n_fft (hop %d, win %d, n_fft %d)",
+                         b, aug_hop[b], aug_win[b], n_fft);
+            meta.awin[b] = aug_win[b];
+            meta.ahop[b] = aug_hop[b];
+            tamax = max(tamax, 1 + len[b] / aug_hop[b]);
+        }
+    }
+    ST_CHECK_ARG(T_pad >= tmax && (!aug || Ta_pad >= tamax), "st_audio_features: T_pad %d / Ta_pad %d below the longest framing (%d / %d)",
+                 T_pad, Ta_pad, tmax, tamax);
+    int rc = ensure_twiddles(stream);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool noisy = aug && snr_db;
+    double* part = reinterpret_cast<double*>(ws);
+    if (noisy) hipLaunchKernelGGL(feat_power_kernel, dim3(POW_PARTS, B), dim3(POW_THREADS), 0, s, x, noise, seed, meta, part);
+    ST_AUDIO_DISPATCH(n_fft, launch_features, x, noise, seed, noisy ? part : nullptr, meta, preemph, win, hop, fb_start, fb_cnt, fb_off, fb_w,
+                      n_mels, mel, linear, aug, B, T_pad, Ta_pad, s);
     ST_LAUNCH_CHECK();
     return 0;
 }

@@ -8,6 +8,7 @@ import os
 import ctypes as C
 from contextlib import contextmanager
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1608,3 +1609,50 @@ def griffin_lim(feat, phases, n_fft, hop, win, n_iter=30, normalized=False, powe
     check(lib.st_griffin_lim(_p(feat), sb, st, sf, int(bool(normalized)), float(power), _p(phases), _p(wav), B, T, n_fft, hop, win,
                              int(n_iter), int(post), _p(ws), stream_handle()), 'st_griffin_lim')
     return wav
+
+
+# --------------------------------------------------------------------------------------------- feature extraction (src/audio.py)
+FEATURES_MAX_BATCH = 64          # utterances per st_audio_features call (its per-utterance metadata travels by value)
+
+
+def audio_features(x, off, lens, n_fft, win, hop, preemph, fb, T_pad, with_linear=True, aug_win=None, aug_hop=None, Ta_pad=None,
+                   snr_db=None, noise=None, seed=0):
+    """st_audio_features on a ragged batch: x the packed float32 waveforms (device), utterance b = x[off[b]:off[b] + lens[b]];
+    fb = (start, count, offset, weights) device tensors of the banded mel filterbank.  -> (mel (B, T_pad, n_mels),
+    linear (B, T_pad, n_fft // 2 + 1) or None, aug (B, Ta_pad, n_mels) or None); the augmented mel when aug_win / aug_hop (per
+    utterance) are given, with noise at snr_db[b] (NaN: none) from `noise` (packed like x) or the built-in generator of `seed`.
+    Batches above FEATURES_MAX_BATCH are issued in chunks of it."""
+    assert x.dim() == 1 and x.is_contiguous() and (noise is None or (noise.shape == x.shape and noise.is_contiguous()))
+    fs, fc, fo, fw = fb
+    n_mels, F = fs.shape[0], n_fft // 2 + 1
+    B = len(lens)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    use_aug = aug_win is not None
+    dev = x.device
+    mel = torch.empty(B, T_pad, n_mels, device=dev, dtype=torch.float32)
+    lin = torch.empty(B, T_pad, F, device=dev, dtype=torch.float32) if with_linear else None
+    aug = torch.empty(B, Ta_pad, n_mels, device=dev, dtype=torch.float32) if use_aug else None
+    if use_aug:
+        aug_win = np.ascontiguousarray(aug_win, dtype=np.int32)
+        aug_hop = np.ascontiguousarray(aug_hop, dtype=np.int32)
+    if snr_db is not None:
+        snr_db = np.ascontiguousarray(snr_db, dtype=np.float32)
+    lib = _lib.load()
+    ws = torch.empty(lib.st_features_workspace_floats(min(B, FEATURES_MAX_BATCH)), device=dev, dtype=torch.float32)
+    hp = lambda a, b0: None if a is None else a.ctypes.data + b0 * a.itemsize     # noqa: E731  (host array from row b0)
+    for b0 in range(0, B, FEATURES_MAX_BATCH):
+        nb = min(FEATURES_MAX_BATCH, B - b0)
+        check(lib.st_audio_features(_p(x), x.numel(), _p(noise), int(seed) & (2 ** 64 - 1), hp(off, b0), hp(lens, b0),
+                                    hp(aug_win, b0), hp(aug_hop, b0), hp(snr_db, b0), nb, n_fft, win, hop, float(preemph),
+                                    _p(fs, torch.int32), _p(fc, torch.int32), _p(fo, torch.int32), _p(fw), n_mels, _p(mel[b0:]),
+                                    _p(lin[b0:]) if lin is not None else None, T_pad, _p(aug[b0:]) if aug is not None else None,
+                                    Ta_pad or 0, _p(ws), stream_handle()), 'st_audio_features')
+    return mel, lin, aug
+
+
+def feature_noise(n, utt, seed, device):
+    """the built-in noise generator of st_audio_features: (n,) standard normals of (seed, utterance utt, sample index)"""
+    out = torch.empty(n, device=device, dtype=torch.float32)
+    check(_lib.load().st_feature_noise(_p(out), n, utt, int(seed) & (2 ** 64 - 1), stream_handle()), 'st_feature_noise')
+    return out

@@ -731,16 +731,41 @@ class VqvaeTrainer(TtsTrainer):
                                                     stretch=float(rs.uniform(lo, hi)))
         self.pair_set = [mk(B, frames, 1000 * rank + i + seed) for i in range(n)]
         self.unpair_set = [mk(Bu, uframes, 500000 + 1000 * rank + i + seed) for i in range(n)]
+        self.unpair_waves = None
+        if getattr(pa, 'unpair_wav_dir', None):
+            self._load_unpair_waves(pa.unpair_wav_dir, Bu, uframes, rank, seed, mk)
         self.pair_iter, self.unpair_iter = 0, 0
         # (mel, aug_mel, linear, text, sid) -> the paired TTS step's (text, sid, mel, linear): TtsTrainer.exec on the same data
         self.batches = [(b[3], b[4], b[0], b[2]) for b in self.pair_set]
         return self
+
+    def _load_unpair_waves(self, wav_dir, Bu, uframes, rank, seed, mk):
+        """--unpair-wav-dir: the unpaired set's (mel, aug_mel, linear) come from the .wav files of wav_dir, sorted by name, rank k of
+        a world of w taking files k::w, in batches of Bu.  The waveforms are read once and stay on the device; fetch_data extracts
+        the features again on every fetch (fresh SNR / stretch draws, as the reference's loader does every epoch).  text / sid stay
+        synthetic: the speech-first cycle does not read the unpaired text."""
+        from .audio import WaveBatch, load_audio_transform
+        world = int(os.environ.get('WORLD_SIZE', 1))
+        files = sorted(f for f in os.listdir(wav_dir) if f.lower().endswith('.wav'))[rank::world]
+        if not files:
+            raise ValueError('--unpair-wav-dir %s: no .wav files for rank %d of %d' % (wav_dir, rank, world))
+        self.audio_converter = load_audio_transform(**self.config['data']['audio'])
+        if self.audio_converter.n_mels != self.n_mels:
+            raise ValueError('--unpair-wav-dir: data.audio has %d mels, the model %d' % (self.audio_converter.n_mels, self.n_mels))
+        waves = [self.audio_converter.load(os.path.join(wav_dir, f))[0].to(self.device) for f in files]
+        self.unpair_waves = [WaveBatch(waves[i:i + Bu]) for i in range(0, len(waves), Bu)]
+        self.unpair_set = [mk(len(wb.lens), uframes, 500000 + 1000 * rank + i + seed) for i, wb in enumerate(self.unpair_waves)]
 
     def fetch_data(self, iter_name):
         """the next batch of `pair_iter` / `unpair_iter` on the device, the set restarting when it is exhausted (:33-41)"""
         data = getattr(self, iter_name.replace('iter', 'set'))
         i = getattr(self, iter_name)
         setattr(self, iter_name, i + 1)
+        if iter_name == 'unpair_iter' and self.unpair_waves is not None:
+            j = i % len(self.unpair_waves)
+            mel, aug_mel, linear = self.audio_converter.extract_batch(self.unpair_waves[j], r=self.r)
+            text, sid = self.unpair_set[j][3].to(self.device), self.unpair_set[j][4].to(self.device)
+            return mel, aug_mel, linear, text, sid
         cache = self.__dict__.setdefault('_dev_batches', {})
         key = (iter_name, i % len(data))
         if key not in cache:                     # (the synthetic sets are small and fixed: on the device once)
@@ -770,6 +795,10 @@ class VqvaeTrainer(TtsTrainer):
         self.drain_stats()
         self.check_device_status()
         dt = time.perf_counter() - t0
+        if self.log and not (self.step == 1 or self.step % 10 == 0):          # the last step's statistics, when not logged above
+            st = self.log[-1]
+            self.verbose('Tr stat | step %d (%s) | Loss - %.4f (CTC-nan/unp-sph/unp-txt=%d/%d/%d) | Grad. Norm - %.3f | lr %.2e' %
+                         (self.step, kind, st['loss'], self.ctc_nan, cnt['unp_sph'], cnt['unp_txt'], st['grad_norm'], st['lr']))
         if getattr(self.paras, 'save', False):
             self.save_checkpoint('latest.pth', self.log[-1]['loss'] if self.log else 0.0)
         self.verbose('%d steps, %d frames in %.2f s (%.0f frames/s incl. first-step set-up)' %
