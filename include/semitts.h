@@ -1032,6 +1032,23 @@ size_t st_ctc_workspace_floats(int B, int T);
 int st_ctc_loss(const float* prob, const int64_t* text, float eps, float* loss, float* dprob, float* ws,
                 int B, int T, int V, int L, int log_input, void* stream);
 
+/* greedy CTC transcript and its edit distance to the reference transcript (ref: src/util.py:169-181, cal_per -- which copies the argmax to
+ * the host and runs a Python loop and editdistance.eval per utterance).  Per utterance b of prob (B, T, V), text (B, L) int64:
+ *   p[t] = argmax_v prob[b, t, v] over all T frames (ties: the first maximal index; a NaN is the maximum, the first NaN wins: torch.argmax);
+ *   hyp  = p[t] where t == 0 or p[t] != p[t-1] (runs collapse FIRST), then every id of ignore[0 .. n_ignore) dropped;
+ *   ref  = text[b, :] with every ignored id dropped, wherever it sits;
+ *   dist[b] = Levenshtein(hyp, ref) with unit costs (editdistance.eval), ref_len[b] = len(ref) (int32).
+ * hyp (B, T) int64: the transcript left-aligned, padded with 0, and hyp_len (B) int32 -- both NULL, or both given.
+ * Integer arithmetic only, no atomics: exact and bitwise repeatable.  One launch, no host read.
+ * Limits (-22 past them): 1 <= T <= 4096, 1 <= V <= 10240, 1 <= L <= 1024, 0 <= n_ignore <= 64.
+ * st_ids_edit_distance: the same with pred (B, T) int64 ids already argmaxed (cal_per's 2-D input); no V. */
+int st_ctc_greedy_edit_distance(const float* prob, int B, int T, int V, const int64_t* text, int L,
+                                const int32_t* ignore, int n_ignore,
+                                int32_t* dist, int32_t* ref_len, int64_t* hyp /* NULL = not written */, int32_t* hyp_len /* NULL */,
+                                void* stream);
+int st_ids_edit_distance(const int64_t* pred, int B, int T, const int64_t* text, int L, const int32_t* ignore, int n_ignore,
+                         int32_t* dist, int32_t* ref_len, int64_t* hyp, int32_t* hyp_len, void* stream);
+
 /* The trainer's scalar arithmetic on loss values as one launch (ref: bin/train_vqvae.py:208-233: total_loss = asr_weight * asr_loss +
  * tts_weight * (mel_loss + linear_loss) + unpair_speech_weight * ... -- a chain of one-element torch kernels there):
  * *outs[j] = sum_i W[j * n + i] * *xs[i] for j < m (m <= 4 outputs, n <= ST_SCALAR_MAX terms, W on the host; in rows j > 0 a zero weight means the term is not a member of that sum).

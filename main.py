@@ -5,8 +5,13 @@ The dispatch is the reference's (main.py:49-63): `--gen-specgram` runs batched f
 text -> speech -> text cycles of bin/train_vqvae.py:111-270 (CTC speech encoder, codebook, run-length merge,
 TTS branch, CTC + freq losses, backward, clip + Adam, all on the HIP kernels) -- on synthetic paired and
 unpaired batches (the corpus is not available).  `--tts-only` keeps the paired TTS step alone (TtsTrainer).
+`--dev-batches K` adds the reference's validation (bin/train_vqvae.py:313-314,330-428) on K synthetic dev batches: at step 1
+and every `--valid-step` (hparas.valid_step) steps it logs `Dv stat` (dev TTS loss, PER, post PER) and writes tts_<step>.pth /
+asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-per, best_per.pth / best_post_per.pth -- under
+--ckpdir/<name>.  Without it nothing is validated and no checkpoint is written (only --save's latest.pth).
 
     python main.py --config config/semi-single-spkr-paired-data.yaml --max-step 20 [--frames 256 --batch-size 8]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --max-step 20000 --dev-batches 4 [--valid-step 5000] [--store-best-per]
     python main.py --config config/supervised.yaml --gen-specgram [--load ckpt.pth] [--frames 256 --batch-size 32]
     python main.py --config config/supervised.yaml --tts-only --max-step 20 [--frames 256 --batch-size 32]
 """
@@ -33,7 +38,7 @@ parser.add_argument('--gen-specgram', action='store_true', help='Generating mel/
 parser.add_argument('--gen-gt-specgram', action='store_true', help='(the reference dispatches to bin/gen_gt_specgram.py, which its tree lacks)')
 parser.add_argument('--no-msg', action='store_true', help='Hide all messages.')
 parser.add_argument('--actual-len', action='store_true', help='Using actual len for CTC loss. (synthetic inputs are full length: no effect)')
-parser.add_argument('--store-best-per', action='store_true', help='Only store the model with best PER. (no dev corpus: no effect)')
+parser.add_argument('--store-best-per', action='store_true', help='Only store the model with best PER. (with --dev-batches; without a dev set: no effect)')
 parser.add_argument('--asr-only', action='store_true', help='(the reference dispatches to bin/train_asr.py, which its tree lacks)')
 parser.add_argument('--gen-wav', action='store_true', help='Generate waveform using Griffin-Lim. (--gen-specgram: writes <name>-pred.wav)')
 # synthetic-data knobs (the reference reads these from the corpus)
@@ -49,6 +54,9 @@ parser.add_argument('--stretch', action='store_true', help='aug_mel lengths draw
 parser.add_argument('--tts-only', action='store_true', help='train the paired TTS branch alone (TtsTrainer) instead of the two cycles')
 parser.add_argument('--max-step', default=None, type=int, help='training steps (default: hparas.max_step)')
 parser.add_argument('--save', action='store_true', help='write ckpt/<name>/latest.pth ({model, optimizer, global_step}) after training')
+parser.add_argument('--dev-batches', default=0, type=int, help='validate on K synthetic dev batches (paired shapes) at step 1 and every '
+                    'valid step: dev TTS loss, PER, post PER, checkpoints by the reference\'s rules (default 0: no validation)')
+parser.add_argument('--valid-step', default=None, type=int, help='steps between validations (default: hparas.valid_step)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -75,10 +83,17 @@ def parse_args(argv=None):
     if paras.unpair_wav_dir is not None and (paras.tts_only or paras.gen_specgram):
         parser.error('--unpair-wav-dir feeds the unpaired batches of the two cycles; it does not combine with --%s'
                      % ('tts-only' if paras.tts_only else 'gen-specgram'))
+    if paras.dev_batches < 0 or (paras.valid_step is not None and paras.valid_step < 1):
+        parser.error('--dev-batches must be >= 0 and --valid-step >= 1')
+    if paras.dev_batches > 0 and (paras.tts_only or paras.gen_specgram):
+        parser.error('--dev-batches validates the two cycles (VqvaeTrainer); it does not combine with --%s'
+                     % ('tts-only' if paras.tts_only else 'gen-specgram'))
     if paras.verbose:
         for flag in IGNORED_FLAGS:
             if flag == 'gen_wav' and paras.gen_specgram:
                 continue             # read by gen_specgram alone (bin/gen_specgram.py:114-126), as in the reference
+            if flag == 'store_best_per' and paras.dev_batches > 0:
+                continue             # read by VqvaeTrainer.validate (bin/train_vqvae.py:376-382)
             if getattr(paras, flag):
                 print('[INFO] --%s accepted for compatibility; it has no effect on this path' % flag.replace('_', '-'))
     return paras

@@ -205,6 +205,8 @@ SIGNATURES = {
     'st_vq_l2_workspace_floats': [I, I],
     'st_ctc_workspace_floats': [I, I],
     'st_ctc_loss': [P, P, C.c_float, P, P, P, I, I, I, I, I, P],
+    'st_ctc_greedy_edit_distance': [P, I, I, I, P, I, P, I, P, P, P, P, P],
+    'st_ids_edit_distance': [P, I, I, P, I, P, I, P, P, P, P, P],
     'st_scalar_combine': [P, I, P, I, P, P],
     'st_scalar_fanout': [P, P, I, P, P],
     'st_softmax_bwd': [P, P, P, C.c_float, P, P, I, I, P],

@@ -360,3 +360,189 @@ extern "C" int st_scale_by(const float* x, const float* scalar, float* y, size_t
     ST_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- greedy CTC transcript and its edit distance (ref: src/util.py:169-181, cal_per) ---------------------------------------------------
+//   p[t] = argmax_v prob(b, t, v) (first maximal index; a NaN is the maximum, the first NaN wins: torch.argmax)
+//   hyp  = p[t] where t == 0 or p[t] != p[t-1], THEN without the ignored ids;  ref = text(b, :) without the ignored ids
+//   dist = Levenshtein(hyp, ref) with unit costs (editdistance.eval)
+// One workgroup per utterance.  Its four waves take the argmax of one frame each at a time and compact hyp and ref into LDS with a block
+// prefix sum; wave 0 then runs the DP alone: one row per hyp token, the ref columns spread over the 64 lanes (lane l owns the CPT
+// consecutive columns l * CPT ...).  The left dependency of a row is a prefix minimum:
+//   X[0] = i,  X[j] = min(D[i-1][j-1] + (h_i != r_j), D[i-1][j] + 1),  D[i][j] = j + min_{k <= j} (X[k] - k)
+// (per lane in its registers, then across the lanes with shuffles) -- integers only, no atomics: exact and bitwise repeatable.
+namespace {
+
+constexpr int GED_NT = 256, GED_MAX_T = 4096, GED_MAX_L = 1024, GED_MAX_V = 10240, GED_MAX_IGNORE = 64;
+constexpr int GED_CPT = (GED_MAX_L + 1 + 63) / 64;          // DP columns per lane at the largest L (17)
+
+// (value, index) of the larger of two argmax candidates: NaN above every number, then the value, then the LOWER index (a total order, so
+// the result does not depend on the order of the reduction); idx < 0 = no candidate
+__device__ __forceinline__ void ged_pick(float& v, int& i, float v2, int i2) {
+    if (i2 < 0) return;
+    bool take;
+    if (i < 0) take = true;
+    else {
+        const bool n1 = v != v, n2 = v2 != v2;
+        if (n1 || n2) take = n2 && (!n1 || i2 < i);
+        else take = v2 > v || (v2 == v && i2 < i);
+    }
+    if (take) { v = v2; i = i2; }
+}
+
+__device__ __forceinline__ bool ged_ignored(int64_t x, const int* ign, int n_ign) {
+    for (int k = 0; k < n_ign; ++k) if (x == (int64_t)ign[k]) return true;
+    return false;
+}
+
+// exclusive prefix sum of one int per thread over the workgroup; *total = the sum (every thread).  Two barriers; `scr` >= 4 ints.
+__device__ __forceinline__ int ged_block_scan(int x, int* scr, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int s = x;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(s, d);
+        if (lane >= d) s += y;
+    }
+    if (lane == 63) scr[w] = s;
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int k = 0; k < GED_NT / 64; ++k) { if (k < w) off += scr[k]; tot += scr[k]; }
+    __syncthreads();                              // (scr is free again for the next scan)
+    *total = tot;
+    return off + s - x;
+}
+
+// ids != NULL: p[t] = ids(b, t) (already argmaxed, int64) and prob is not read
+__global__ __launch_bounds__(GED_NT) void ctc_greedy_ed_kernel(const float* prob, const int64_t* ids, int T, int V, const int64_t* text, int L,
+                                                               const int32_t* ignore, int n_ignore, int32_t* dist, int32_t* ref_len,
+                                                               int64_t* hyp_out, int32_t* hyp_len_out) {
+    extern __shared__ int64_t ged_dyn[];          // hyp[T], ref[L] (int64), then p[T] (int32, posterior mode)
+    int64_t* hyp = ged_dyn;
+    int64_t* ref = ged_dyn + T;
+    int* p = reinterpret_cast<int*>(ged_dyn + T + L);
+    __shared__ int ign[GED_MAX_IGNORE];
+    __shared__ int scr[GED_NT / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int k = tid; k < n_ignore; k += GED_NT) ign[k] = ignore[k];
+    const int64_t* idb = ids ? ids + (size_t)b * T : nullptr;
+    if (!ids) {
+        // ---- argmax: one wave per frame, each lane its classes in ascending order, then the 64 candidates
+        const float* pb = prob + (size_t)b * T * V;
+        for (int t = w; t < T; t += GED_NT / 64) {
+            const float* row = pb + (size_t)t * V;
+            float bv = 0.0f;
+            int bi = -1;
+            for (int v = lane; v < V; v += 64) ged_pick(bv, bi, row[v], v);
+            for (int d = 32; d >= 1; d >>= 1) {
+                const float ov = __shfl_xor(bv, d);
+                const int oi = __shfl_xor(bi, d);
+                ged_pick(bv, bi, ov, oi);
+            }
+            if (lane == 0) p[t] = bi;
+        }
+    }
+    __syncthreads();
+    auto tok = [&](int t) -> int64_t { return idb ? idb[t] : (int64_t)p[t]; };
+    // ---- hyp: collapse the runs, then drop the ignored ids (thread tid takes the frames [tid * ct, tid * ct + ct))
+    const int ct = (T + GED_NT - 1) / GED_NT, t0 = min(T, tid * ct), t1 = min(T, t0 + ct);
+    int cnt = 0;
+    for (int t = t0; t < t1; ++t) {
+        const int64_t x = tok(t);
+        cnt += (t == 0 || x != tok(t - 1)) && !ged_ignored(x, ign, n_ignore);
+    }
+    int m;
+    int pos = ged_block_scan(cnt, scr, &m);
+    for (int t = t0; t < t1; ++t) {
+        const int64_t x = tok(t);
+        if ((t == 0 || x != tok(t - 1)) && !ged_ignored(x, ign, n_ignore)) hyp[pos++] = x;
+    }
+    // ---- ref: the transcript without the ignored ids, wherever they sit
+    const int64_t* tb = text + (size_t)b * L;
+    const int cl = (L + GED_NT - 1) / GED_NT, l0 = min(L, tid * cl), l1 = min(L, l0 + cl);
+    cnt = 0;
+    for (int l = l0; l < l1; ++l) cnt += !ged_ignored(tb[l], ign, n_ignore);
+    int n;
+    pos = ged_block_scan(cnt, scr, &n);
+    for (int l = l0; l < l1; ++l) {
+        const int64_t x = tb[l];
+        if (!ged_ignored(x, ign, n_ignore)) ref[pos++] = x;
+    }
+    __syncthreads();
+    if (hyp_out) {
+        int64_t* ho = hyp_out + (size_t)b * T;
+        for (int t = tid; t < T; t += GED_NT) ho[t] = t < m ? hyp[t] : 0;
+        if (tid == 0) hyp_len_out[b] = m;
+    }
+    if (w != 0) return;
+    // ---- DP, wave 0: columns j = 0 .. n, lane `lane` owns j = lane * cpt + k, k < cpt
+    const int cpt = (n + 1 + 63) / 64;
+    int D[GED_CPT];
+    int64_t r[GED_CPT];
+#pragma unroll
+    for (int k = 0; k < GED_CPT; ++k) {
+        const int j = lane * cpt + k;
+        D[k] = j;                                             // row 0: j insertions
+        r[k] = (k < cpt && j >= 1 && j <= n) ? ref[j - 1] : -1;
+    }
+    for (int i = 1; i <= m; ++i) {
+        const int64_t h = hyp[i - 1];
+        int last = 0;                                         // D[i-1][lane * cpt + cpt - 1]
+#pragma unroll
+        for (int k = 0; k < GED_CPT; ++k) if (k == cpt - 1) last = D[k];
+        const int left = __shfl_up(last, 1);                  // D[i-1] of the column before this lane's first one
+        int pm = INT_MAX, Y[GED_CPT];
+        int prev = left;
+#pragma unroll
+        for (int k = 0; k < GED_CPT; ++k) {
+            if (k < cpt) {
+                const int j = lane * cpt + k;
+                const int X = j == 0 ? i : min(prev + (h != r[k] ? 1 : 0), D[k] + 1);
+                prev = D[k];
+                pm = min(pm, X - j);
+                Y[k] = pm;                                    // inclusive prefix minimum within the lane
+            }
+        }
+        int s = pm;                                           // inclusive prefix minimum over the lanes
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(s, d);
+            if (lane >= d) s = min(s, y);
+        }
+        int e = __shfl_up(s, 1);                              // ... exclusive
+        if (lane == 0) e = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < GED_CPT; ++k) if (k < cpt) D[k] = lane * cpt + k + min(e, Y[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < GED_CPT; ++k) {
+        if (k < cpt && lane * cpt + k == n) { dist[b] = D[k]; ref_len[b] = n; }
+    }
+}
+
+}  // namespace
+
+static int ged_launch(const float* prob, const int64_t* ids, int B, int T, int V, const int64_t* text, int L, const int32_t* ignore, int n_ignore,
+               int32_t* dist, int32_t* ref_len, int64_t* hyp, int32_t* hyp_len, void* stream, const char* what) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG((prob || ids) && text && dist && ref_len && B > 0 && T > 0 && L > 0, "%s: bad arguments", what);
+    ST_CHECK_ARG(T <= GED_MAX_T, "%s: at most %d frames (T=%d)", what, GED_MAX_T, T);
+    ST_CHECK_ARG(L <= GED_MAX_L, "%s: transcripts of at most %d tokens (L=%d)", what, GED_MAX_L, L);
+    ST_CHECK_ARG(ids || (V > 0 && V <= GED_MAX_V), "%s: 1..%d classes (V=%d)", what, GED_MAX_V, V);
+    ST_CHECK_ARG(n_ignore >= 0 && n_ignore <= GED_MAX_IGNORE && (n_ignore == 0 || ignore), "%s: 0..%d ignored ids", what, GED_MAX_IGNORE);
+    ST_CHECK_ARG((hyp == nullptr) == (hyp_len == nullptr), "%s: hyp and hyp_len go together", what);
+    const size_t lds = ((size_t)T + L) * sizeof(int64_t) + (ids ? 0 : (size_t)T * sizeof(int));      // <= 56 KiB at the limits
+    hipLaunchKernelGGL(ctc_greedy_ed_kernel, dim3(B), dim3(GED_NT), lds, (hipStream_t)stream, prob, ids, T, V, text, L, ignore, n_ignore,
+                       dist, ref_len, hyp, hyp_len);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_ctc_greedy_edit_distance(const float* prob, int B, int T, int V, const int64_t* text, int L, const int32_t* ignore,
+                                           int n_ignore, int32_t* dist, int32_t* ref_len, int64_t* hyp, int32_t* hyp_len, void* stream) {
+    ST_CHECK_ARG(prob, "st_ctc_greedy_edit_distance: null prob");
+    return ged_launch(prob, nullptr, B, T, V, text, L, ignore, n_ignore, dist, ref_len, hyp, hyp_len, stream, "st_ctc_greedy_edit_distance");
+}
+
+extern "C" int st_ids_edit_distance(const int64_t* pred, int B, int T, const int64_t* text, int L, const int32_t* ignore, int n_ignore,
+                                    int32_t* dist, int32_t* ref_len, int64_t* hyp, int32_t* hyp_len, void* stream) {
+    ST_CHECK_ARG(pred, "st_ids_edit_distance: null pred");
+    return ged_launch(nullptr, pred, B, T, 0, text, L, ignore, n_ignore, dist, ref_len, hyp, hyp_len, stream, "st_ids_edit_distance");
+}

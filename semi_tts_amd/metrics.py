@@ -1,0 +1,49 @@
+"""Phone error rate of greedy CTC transcripts on the device (ref: src/util.py:169-181, cal_per).
+
+The reference copies the argmax to the host and runs a Python loop and the C `editdistance` package per
+utterance.  Here one HIP launch per batch (st_ctc_greedy_edit_distance) gives every utterance's edit distance
+and reference length as device tensors; nothing is read back until somebody asks for a Python number.
+
+    from semi_tts_amd.metrics import cal_per        # replaces `from src.util import cal_per` (bin/train_vqvae.py:11)
+"""
+import math
+
+import torch
+
+from . import ops
+
+# <pad>, <space>, <eos> and id 42, exactly as src/util.py:16.  Id 42 is the last phoneme of the reference's 43-entry vocabulary
+# (data/cmu_phn.vocab), not a special token: the reference drops it from both transcripts all the same, and so does this module,
+# so that the numbers agree with the reference's.
+IGNORE_INDICES = (0, 1, 2, 42)
+
+
+def _on_device(pred, truth):
+    """both on one GPU: a host tensor (what the reference's loop passes after .cpu()) goes to the other one's device, or the current one"""
+    dev = pred.device if pred.is_cuda else truth.device if truth.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    return pred.to(dev), truth.to(dev)
+
+
+def edit_distances(pred, truth, ignore=IGNORE_INDICES):
+    """-> (dist, ref_len): int32 (B,) device tensors, no host read.  pred: (B, T, V) float32 posteriors or log-posteriors (the greedy
+    transcript is their argmax over V), or (B, T) int64 ids already argmaxed -- cal_per accepts both (`len(pred.shape) >= 3`).
+    truth: (B, L) int64 transcripts.  dist[b] = edit distance between the collapsed, filtered argmax and truth[b] without the
+    ignored ids; ref_len[b] = the length of the latter."""
+    pred, truth = _on_device(pred, truth)
+    return ops.ctc_greedy_edit_distance(pred, truth, ignore)
+
+
+def per_sum(pred, truth, ignore=IGNORE_INDICES):
+    """sum over the batch of dist / ref_len as a float64 device scalar (no host read).  An utterance whose transcript is empty once the
+    ignored ids are gone (ref_len == 0) makes the sum NaN -- the reference raises ZeroDivisionError there."""
+    dist, ref_len = edit_distances(pred, truth, ignore)
+    d, n = dist.to(torch.float64), ref_len.to(torch.float64)
+    rate = torch.where(ref_len > 0, d / n.clamp_min(1.0), torch.full_like(d, math.nan))
+    return rate.sum()
+
+
+def cal_per(pred, truth):
+    """drop-in for src/util.py:cal_per: the mean phone error rate of the batch as a Python float (one host read); None gives nan"""
+    if pred is None:
+        return math.nan
+    return float(per_sum(pred, truth)) / pred.shape[0]

@@ -856,6 +856,57 @@ def ctc_loss(prob, text, eps, want_grad=True, log_input=False):
     return loss, dprob
 
 
+GED_MAX_T, GED_MAX_V, GED_MAX_L, GED_MAX_IGNORE = 4096, 10240, 1024, 64      # st_ctc_greedy_edit_distance's limits
+_IGNORE_DEV = {}
+
+
+def ctc_greedy_edit_distance(prob, text, ignore, want_hyp=False):
+    """greedy CTC transcript of `prob` and its edit distance to `text`, per utterance (see st_ctc_greedy_edit_distance):
+    prob (B, T, V) fp32 posteriors / log-posteriors, or (B, T) int64 ids already argmaxed (st_ids_edit_distance); text (B, L) int64;
+    ignore: the ids dropped from both sides.  -> (dist, ref_len) int32 (B,) device tensors [+ (hyp (B, T) int64, hyp_len (B,) int32)
+    with want_hyp].  One launch, no host read.  Anything the kernel would refuse raises ValueError before the launch."""
+    if not (torch.is_tensor(prob) and torch.is_tensor(text)):
+        raise ValueError('ctc_greedy_edit_distance: prob and text must be tensors')
+    if not (prob.is_cuda and text.is_cuda and prob.device == text.device):
+        raise ValueError('ctc_greedy_edit_distance: prob and text must be on one GPU (got %s, %s)' % (prob.device, text.device))
+    ids = prob.dim() == 2
+    if ids and prob.dtype != torch.int64 or not ids and (prob.dim() != 3 or prob.dtype != torch.float32):
+        raise ValueError('ctc_greedy_edit_distance: prob must be (B, T, V) float32 or (B, T) int64 (got %s %s)'
+                         % (tuple(prob.shape), prob.dtype))
+    if text.dim() != 2 or text.dtype != torch.int64:
+        raise ValueError('ctc_greedy_edit_distance: text must be (B, L) int64 (got %s %s)' % (tuple(text.shape), text.dtype))
+    B, T = prob.shape[:2]
+    V = 0 if ids else prob.shape[2]
+    L = text.shape[1]
+    ignore = tuple(int(i) for i in ignore)
+    if text.shape[0] != B or B < 1:
+        raise ValueError('ctc_greedy_edit_distance: %d utterances of prob, %d of text (at least one)' % (B, text.shape[0]))
+    if not (1 <= T <= GED_MAX_T and (ids or 1 <= V <= GED_MAX_V) and 1 <= L <= GED_MAX_L and len(ignore) <= GED_MAX_IGNORE):
+        raise ValueError('ctc_greedy_edit_distance: T=%d, V=%d, L=%d, %d ignored ids outside 1 <= T <= %d, 1 <= V <= %d, 1 <= L <= %d, '
+                         '<= %d ignored ids' % (T, V, L, len(ignore), GED_MAX_T, GED_MAX_V, GED_MAX_L, GED_MAX_IGNORE))
+    if any(not -2 ** 31 <= i < 2 ** 31 for i in ignore):
+        raise ValueError('ctc_greedy_edit_distance: ignored ids must fit int32')
+    dev = prob.device
+    ign = _IGNORE_DEV.get((dev, ignore))
+    if ign is None:
+        ign = _IGNORE_DEV[(dev, ignore)] = torch.tensor(ignore if ignore else [0], dtype=torch.int32).to(dev)
+    prob, text = prob.contiguous(), text.contiguous()
+    dist = torch.empty(B, device=dev, dtype=torch.int32)
+    ref_len = torch.empty(B, device=dev, dtype=torch.int32)
+    hyp = torch.empty(B, T, device=dev, dtype=torch.int64) if want_hyp else None
+    hyp_len = torch.empty(B, device=dev, dtype=torch.int32) if want_hyp else None
+    lib = _lib.load()
+    if ids:
+        check(lib.st_ids_edit_distance(_p(prob, torch.int64), B, T, _p(text, torch.int64), L, _p(ign, torch.int32), len(ignore),
+                                       _p(dist, torch.int32), _p(ref_len, torch.int32), _p(hyp, torch.int64), _p(hyp_len, torch.int32),
+                                       stream_handle()), 'st_ids_edit_distance')
+    else:
+        check(lib.st_ctc_greedy_edit_distance(_p(prob), B, T, V, _p(text, torch.int64), L, _p(ign, torch.int32), len(ignore),
+                                              _p(dist, torch.int32), _p(ref_len, torch.int32), _p(hyp, torch.int64), _p(hyp_len, torch.int32),
+                                              stream_handle()), 'st_ctc_greedy_edit_distance')
+    return (dist, ref_len, hyp, hyp_len) if want_hyp else (dist, ref_len)
+
+
 def softmax_argmax(logits):
     lib = _lib.load()
     V = logits.shape[-1]

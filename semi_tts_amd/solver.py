@@ -486,6 +486,39 @@ class TtsTrainer(BaseSolver):
 
 
 EPS = 1e-10                      # ref: bin/train_vqvae.py:18
+CKPT_STEP = 10000                # ref: bin/train_vqvae.py:17
+BEST_TTS_LOSS_INIT, BEST_PER_INIT = 100.0, 2.0          # ref: bin/train_vqvae.py:26-27 (a PER of 2.0 or more never saves)
+
+
+def validation_checkpoints(step, tts_loss, per, post_per, best, store_best_per):
+    """The checkpoint rules of VqvaeTrainer.validate (bin/train_vqvae.py:376-403) as a pure function.  best = (best_tts_loss, best_per);
+    post_per is None for a model without an ASR postnet.  -> ([(file name, score), ...] in the order the reference saves them, new best).
+    Kept as the reference has them: a post-net PER is compared with best_per AFTER the encoder's PER has updated it, best_post_per.pth
+    is written at step 1 too, and best_per records whichever of the two was lower last."""
+    best_tts, best_per = best
+    files = []
+    if store_best_per:
+        if per < best_per:
+            best_per = per
+            files.append(('best_per.pth', per))
+        if post_per is not None and post_per < best_per:
+            best_per = post_per
+            files.append(('best_post_per.pth', post_per))
+    else:
+        if tts_loss < best_tts:
+            best_tts = tts_loss
+            if step > 1:
+                files.append(('tts_%d.pth' % step, tts_loss))
+        if per < best_per:
+            best_per = per
+            if step > 1:
+                files.append(('asr_%d.pth' % step, per))
+        if post_per is not None and post_per < best_per:
+            best_per = post_per
+            files.append(('best_post_per.pth', post_per))
+        if step > 1 and step % CKPT_STEP == 0:
+            files.append(('step_%d.pth' % step, tts_loss))
+    return files, (best_tts, best_per)
 
 
 class VqvaeTrainer(TtsTrainer):
@@ -734,6 +767,12 @@ class VqvaeTrainer(TtsTrainer):
         self.unpair_waves = None
         if getattr(pa, 'unpair_wav_dir', None):
             self._load_unpair_waves(pa.unpair_wav_dir, Bu, uframes, rank, seed, mk)
+        # --dev-batches K: the dev set validate() walks, drawn like the paired set (same batch size and frames, unstretched) from seeds of
+        # its own, per rank.  Without it (K = 0, the default) nothing is drawn and the run is what it was before validation existed.
+        k = int(getattr(pa, 'dev_batches', 0) or 0)
+        self.dev_set = [synthetic_cycle_batch(B, frames, self.r, self.vocab_size, self.n_spkr, self.n_mels, self.linear_dim,
+                                              seed=900000 + 1000 * rank + i + seed, stretch=1.0) for i in range(k)]
+        self.dev_iter = 0
         self.pair_iter, self.unpair_iter = 0, 0
         # (mel, aug_mel, linear, text, sid) -> the paired TTS step's (text, sid, mel, linear): TtsTrainer.exec on the same data
         self.batches = [(b[3], b[4], b[0], b[2]) for b in self.pair_set]
@@ -772,6 +811,58 @@ class VqvaeTrainer(TtsTrainer):
             cache[key] = tuple(t.to(self.device) for t in data[i % len(data)])
         return cache[key]
 
+    def validate(self):
+        """VqvaeTrainer.validate (bin/train_vqvae.py:330-428) without the tensorboard writes: in eval mode and without gradients, per dev
+        batch the phone error rate of speech_to_text on the clean mel (and of the ASR postnet, when the model has one) and the freq_loss
+        of free-running synthesis; each is the mean over the dev batches of the batch value.  Everything stays on the device until ONE
+        host read after the cross-rank sum; the checkpoint rules are validation_checkpoints (rank 0 writes).  Parameters, gradients,
+        optimiser state and BatchNorm statistics are left as they were; the dropout masks and teacher-forcing draws it makes (as the
+        reference's do) move the torch / numpy generators, so a run with validation takes other draws afterwards than one without.
+        -> (dev_tts_loss, dev_per, dev_post_per or None)"""
+        from . import parallel
+        from .metrics import per_sum
+        # what the last training step left queued: its deferred weight-gradient products and the postnet branch's second stream
+        ops.flush_wgrads()
+        ev = self.__dict__.get('_side_event')
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
+        ops.side_pending(None)
+        self.model.eval()
+        tts, per, post = [], [], []
+        try:
+            with torch.no_grad():
+                for _ in range(len(self.dev_set)):
+                    mel, _, linear, text, sid = self.fetch_data('dev_iter')
+                    B = text.shape[0]
+                    pair_prob, _, _, _, _, pair_post_prob, _ = self.model.speech_to_text(paired_mel=mel, unpaired_mel=None)     # :342-343
+                    per.append(per_sum(pair_prob, text) / B)
+                    if pair_post_prob is not None:
+                        post.append(per_sum(pair_post_prob, text) / B)
+                    mel_pred, lin_pred, _, _, _, _, _, _ = self.model.text_to_speech(text, sid, None, None, None, None, mel.shape[1], None,
+                                                                                   tf_rate=0.0)      # :350-358
+                    tts.append((self.freq_loss(mel_pred, mel) + self.freq_loss(lin_pred, linear)).to(torch.float64))
+                zero = torch.zeros((), dtype=torch.float64, device=self.device)
+                acc = torch.stack([sum(tts, zero), sum(per, zero), sum(post, zero),
+                                   zero + len(tts), zero + len(post)])
+                if parallel.dist_on():
+                    parallel.all_reduce_sum_(acc)
+                s_tts, s_per, s_post, n, n_post = acc.tolist()                                  # the one host read of the pass
+        finally:
+            self.model.train()
+        dev_tts, dev_per = s_tts / n, s_per / n
+        dev_post = s_post / n_post if n_post > 0 else None
+        best = (getattr(self, 'best_tts_loss', BEST_TTS_LOSS_INIT), getattr(self, 'best_per', BEST_PER_INIT))
+        files, (self.best_tts_loss, self.best_per) = validation_checkpoints(self.step, dev_tts, dev_per, dev_post, best,
+                                                                            bool(getattr(self.paras, 'store_best_per', False)))
+        rank, _ = parallel.rank_world()
+        if rank == 0:
+            for name, score in files:
+                self.save_checkpoint(name, score)
+            self.verbose('Dv stat | step %d | TTS loss - %.6f | PER - %.6f | post PER - %s' %
+                         (self.step, dev_tts, dev_per, 'None' if dev_post is None else '%.6f' % dev_post))
+        self.__dict__.setdefault('dev_log', []).append(dict(step=self.step, tts_loss=dev_tts, per=dev_per, post_per=dev_post, files=[f for f, _ in files]))
+        return dev_tts, dev_per, dev_post
+
     def exec(self):
         """VqvaeTrainer.exec's loop (bin/train_vqvae.py:111-150,270-300) without the corpus-side logging: paired batch every step,
         the unpaired batch fetched only when the step's cycle uses it, cycles alternating"""
@@ -779,6 +870,10 @@ class VqvaeTrainer(TtsTrainer):
         frames = 0
         cnt = {'unp_sph': 0, 'unp_txt': 0}
         self.ctc_nan = 0
+        self.dev_log = []
+        self.valid_step = int(getattr(self.paras, 'valid_step', None) or self.hp.get('valid_step', 1))
+        if not hasattr(self, 'dev_set'):
+            self.dev_set = []
         while self.step < self.max_step:
             pair = self.fetch_data('pair_iter')
             kind, use_unpair = self.cycle_kind(self.step)
@@ -791,6 +886,8 @@ class VqvaeTrainer(TtsTrainer):
             if self.step == 1 or self.step % 10 == 0:
                 self.verbose('Tr stat | step %d (%s) | Loss - %.4f (CTC-nan/unp-sph/unp-txt=%d/%d/%d) | Grad. Norm - %.3f | lr %.2e' %
                              (self.step, kind, st['loss'], self.ctc_nan, cnt['unp_sph'], cnt['unp_txt'], st['grad_norm'], st['lr']))
+            if self.dev_set and (self.step == 1 or self.step % self.valid_step == 0):                 # :313-314
+                self.validate()
         torch.cuda.synchronize()
         self.drain_stats()
         self.check_device_status()
