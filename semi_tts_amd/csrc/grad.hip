@@ -853,10 +853,14 @@ __global__ __launch_bounds__(512) void scatter_add_rows_kernel(const float* dout
     const int per = (n + 7) / 8, r0 = q * per, r1 = min(n, r0 + per);
     float acc = 0.0f;
     if (d < D) {
-        // every row is loaded (a wave reads one 256-byte run) and kept or dropped by a 0 / 1 factor: `if (idx == v) acc += dout[..]` is a
-        // branch around the load with a full wait behind it, `per` dependent round trips (finite gradients assumed: 0 * x = 0)
+        // every row is loaded (a wave reads one 256-byte run) and then kept or dropped by a select: `if (idx == v) acc += dout[..]` is a
+        // branch around the load with a full wait behind it, `per` dependent round trips.  A select, not a 0 / 1 factor: 0 * inf = NaN
+        // would spread one non-finite gradient to every table row (acc never holds -0, so acc + 0 == acc)
 #pragma unroll 8
-        for (int r = r0; r < r1; ++r) acc = fmaf(idx[r] == (int64_t)v ? 1.0f : 0.0f, dout[(size_t)r * D + d], acc);
+        for (int r = r0; r < r1; ++r) {
+            const float x = dout[(size_t)r * D + d];
+            acc += idx[r] == (int64_t)v ? x : 0.0f;
+        }
     }
     red[q][c] = acc;
     __syncthreads();

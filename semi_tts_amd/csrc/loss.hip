@@ -213,7 +213,8 @@ __global__ __launch_bounds__(CTC_NT) void ctc_grad_kernel(const float* prob, con
     const bool on = tid < SP;
     const int my = on ? lab[tid] : 0;
     const float nll = nll_in[b];
-    const float gr = bad_s ? __builtin_nanf("") : 1.0f / ((float)max(S, 1) * (float)B);
+    // an infeasible alignment (nll = +inf: T too short for the target) gets a NaN gradient, as torch's CTCLoss(zero_infinity=False)
+    const float gr = (bad_s || nll == INFINITY) ? __builtin_nanf("") : 1.0f / ((float)max(S, 1) * (float)B);
     const float* la = log_alpha + (size_t)b * T * CTC_NT;
     const float* lb = log_beta + (size_t)b * T * CTC_NT;
     const int t0 = blockIdx.y * CTC_TC, t1 = min(T, t0 + CTC_TC);

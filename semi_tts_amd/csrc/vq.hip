@@ -51,6 +51,9 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* table, co
     }
 }
 
+// F.relu of the temperature: NaN stays NaN (fmaxf would turn it into 0 and hide it behind a uniform p_code)
+__device__ __forceinline__ float vq_relu(float t) { return t > 0.0f ? t : (t == t ? 0.0f : t); }
+
 // wave-level argmax with "first maximum wins": larger value, or equal value and smaller index
 __device__ __forceinline__ void wave_argmax(float& val, int& idx) {
 #pragma unroll
@@ -77,7 +80,7 @@ __device__ __forceinline__ int wave_softmax_argmax(float* sims, int V, int lane,
         if (p > best) { best = p; bi = v; }   // ascending v per lane: strict > keeps the first
     }
     wave_argmax(best, bi);
-    return bi;
+    return bi < V ? bi : 0;     // no p qualified (a NaN row: NaN, +inf or all -inf similarities): torch's argmax of an all-NaN row is 0
 }
 
 __global__ __launch_bounds__(VQ_WAVES * 64) void vq_l2_kernel(const float* x, const float* table, const float* temp,
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(VQ_WAVES * 64) void vq_l2_kernel(const float* x, co
         e2[v] = acc;
     }
     __syncthreads();
-    const float tscale = fmaxf(temp[0], 0.0f);          // F.relu(self.temp)
+    const float tscale = vq_relu(temp[0]);               // F.relu(self.temp)
     float* myx = xs + wave * D;
     float* mysim = sims + wave * V;
     for (int r = blockIdx.x * VQ_WAVES + wave; r < n; r += gridDim.x * VQ_WAVES) {
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(NW * 64, WPS * NW / 4) void vq_l2_mfma_kernel(const
 #pragma unroll
         for (int q = 0; q < 4; ++q) bq[t][q] = q < ks4n ? wsp[((size_t)pt * ks4n + q) * 64 + lane] : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const float tscale = fmaxf(temp[0], 0.0f);          // F.relu(self.temp)
+    const float tscale = vq_relu(temp[0]);               // F.relu(self.temp)
     // every barrier of the loop orders LDS traffic only (st_lds_barrier): __syncthreads() also waits for the global stores of p_code
     // and for the prefetched vectors of the next tile -- a memory round trip per barrier, seven per tile
     f32x4 oe = {0.f, 0.f, 0.f, 0.f};                    // the previous tile's picked code row (in flight)
@@ -422,6 +425,7 @@ __global__ __launch_bounds__(NW * 64, WPS * NW / 4) void vq_l2_mfma_kernel(const
             int i = redi[0][tid];
 #pragma unroll
             for (int w = 1; w < NW; ++w) i = min(i, redi[w][tid]);
+            if (i >= V) i = 0;                          // no p equals pmax (a NaN row): torch's argmax of an all-NaN row is 0
             fidx[tid] = i;
             if (v0 + tid < n) idx_out[v0 + tid] = i;
         }
@@ -460,7 +464,7 @@ __global__ __launch_bounds__(VQ_WAVES * 64) void softmax_argmax_kernel(const flo
 __global__ __launch_bounds__(VQ_WAVES * 64) void softmax_bwd_kernel(const float* p, const float* dp, const float* scale_ptr, float scale,
                                                                     float* dz, float* rowsum, int n, int V) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float sc = scale_ptr ? fmaxf(scale_ptr[0], 0.0f) * scale : scale;       // relu(temp) of the L2 codebook
+    const float sc = scale_ptr ? vq_relu(scale_ptr[0]) * scale : scale;       // relu(temp) of the L2 codebook
     for (int r = blockIdx.x * VQ_WAVES + wave; r < n; r += gridDim.x * VQ_WAVES) {
         const float* pr = p + (size_t)r * V;
         const float* dr = dp + (size_t)r * V;
