@@ -373,6 +373,19 @@ typedef struct st_gemm_job {
     st_gemm_epilogue ep;
 } st_gemm_job;
 int st_gemm_fwd_batch(const st_gemm_job* jobs, int n, void* stream);
+/* What st_gemm_fwd / st_gemm_fwd_batch would launch for these arguments (host only: pointers are looked at for their alignment, never
+ * read; negative on bad arguments).  st_gemm_fwd_variant = kernel | slabs << 8 | finish << 16 with
+ *   kernel: 0-2 the LDS-DMA kernel with 64x64 / 32x64 / 64x32 tiles; 3 + 4 VW + 2 PL + (MT == 1): the pipelined kernel (VW: 16-byte
+ *           weight pieces, PL: fused max-pool, MT == 1: 32-row tiles); 11 / 12: its element-wise form for rows that are not 16-byte
+ *           addressable (weights adjacent in ci / torch Conv1d layout); 13 / 14: the one-block kernel with / without 16-byte weights;
+ *   slabs:  split-K slab count (1 = none);  finish: 0 none, 1 four columns per thread (compile-time slab count), 2 the same with a
+ *           run-time count, 3 one column per thread (N % 4 != 0).
+ * st_gemm_fwd_batch_variant = OR of: 1 separate st_gemm_fwd calls, 2 / 4 batched LDS-DMA launches with 64x32 / 64x64 tiles,
+ * 8 batched pipelined launches. */
+int st_gemm_fwd_variant(const float* A, int lda, const float* W, const float* C, int ldc, int coff,
+                        int Bn, int Tin, int Tout, int Cin, int N, int KT, int pad, int stride, int pool_prev,
+                        const st_gemm_epilogue* ep);
+int st_gemm_fwd_batch_variant(const st_gemm_job* jobs, int n);
 
 /* The highway stack of the CBHG in one launch (eval mode): n_layers times y = relu(W_H x + b_H) * T + x * (1 - T), T = sigmoid(W_T x + b_T),
  * x (M, C) rows; w_h / w_t: n_layers pointers to torch Linear weights (C, C), b_h / b_t: their biases (NULL entries = no bias).
@@ -1075,6 +1088,17 @@ typedef struct st_wgrad_job {
 } st_wgrad_job;
 size_t st_gemm_wgrad_batch_workspace_floats(const st_wgrad_job* jobs, int n);
 int st_gemm_wgrad_batch(const st_wgrad_job* jobs, int n, float* ws, void* stream);
+/* What st_gemm_wgrad[_db] (with_db) / st_gemm_wgrad_split (with_split) would launch (host only: pointers are looked at for their
+ * alignment, never read; negative on bad arguments): product | sum << 8 | Z << 16 with
+ *   product: 0 the few-channel kernel, 1 LDS-DMA 64-tiles, 2 LDS-DMA 128-tiles on 16-row chunks, 3 / 4 register-staged 64 / 128-tiles;
+ *            + 8 folded (channel, tap) columns, + 16 Linear rows, + 32 fused max-pool, + 64 written straight to dW (one slab);
+ *   sum:     0 none, 1 one thread per element, 2 slab groups met in LDS (many slabs), 3 with the bias-gradient slabs, 4 the same
+ *            cut into two outputs;  Z: slab count.
+ * st_gemm_wgrad_batch_variant: codes[i] = 1 + the group launch job i of st_gemm_wgrad_batch joins, 0 when it runs as a call of its
+ * own; returns the number of group launches. */
+int st_gemm_wgrad_variant(const float* dC, int lddc, int dcoff, const float* A, int lda, int Bn, int Tin, int Tout, int Cin,
+                          int N, int KT, int pad, int pool_prev, int accumulate, int with_db, int with_split);
+int st_gemm_wgrad_batch_variant(const st_wgrad_job* jobs, int n, int* codes);
 /* st_gemm_wgrad[_db] of a Linear over CONCATENATED inputs (KT = 1; M rows), the result cut at input column `split`:
  * dW0 (N, split) and dW1 (N, Cin - split) are the gradients of the two weights whose columns the product saw side by side -- an
  * nn.LSTMCell fed with [x | h] has gates = [W_ih | W_hh] [x | h]^T (ref: src/module.py:227-231,275-280), so the BPTT weight gradient

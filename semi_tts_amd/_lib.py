@@ -186,6 +186,8 @@ SIGNATURES = {
     'st_attn_step_fwd': [P, P, P, P, I, P, P, I, P, P, P, P, P, I, P, I, P, P, P, I, I, I, I, I, I, I, P],
     'st_gemm_fwd': [P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, C.POINTER(StGemmEpilogue), P],
     'st_gemm_fwd_batch': [C.POINTER(StGemmJob), I, P],
+    'st_gemm_fwd_variant': [P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, C.POINTER(StGemmEpilogue)],
+    'st_gemm_fwd_batch_variant': [C.POINTER(StGemmJob), I],
     'st_highway_stack_supported': [I, I],
     'st_highway_stack_fwd': [P, I, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), I, P, I, I, I, P],
     'st_gemm_splitk_slabs': [I, I, I, I, I],
@@ -308,6 +310,8 @@ SIGNATURES = {
     'st_gemm_wgrad_db': [P, I, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, P],
     'st_gemm_wgrad_batch_workspace_floats': [C.POINTER(StWgradJob), I],
     'st_gemm_wgrad_batch': [C.POINTER(StWgradJob), I, P, P],
+    'st_gemm_wgrad_variant': [P, I, I, P, I, I, I, I, I, I, I, I, I, I, I, I],
+    'st_gemm_wgrad_batch_variant': [C.POINTER(StWgradJob), I, C.POINTER(I)],
     'st_gemm_wgrad_split': [P, I, I, P, I, P, I, P, P, P, P, I, I, I, I, P],
     'st_colsum': [P, I, I, P, I, I, I, I, P, I, P, P],
     'st_act_bwd': [P, I, P, I, I, P, I, P, I, I, I, P],

@@ -919,13 +919,55 @@ static int gm_prepare(const float* A, int lda, const float* W, float* C, int ldc
     return 0;
 }
 
+// The forward dispatch: which kernel, how many split-K slabs, which finish.  st_gemm_fwd launches what gm_plan() says and
+// st_gemm_fwd_variant() reports it (codes: include/semitts.h); the choice looks at pointer VALUES (alignment) only.
+enum {
+    GK_GD_64x64 = 0, GK_GD_32x64 = 1, GK_GD_64x32 = 2,       // gd_kernel<BM, BN> (= gd_tile())
+    GK_PIPE = 3,                                               // gm_pipe_kernel<VW, PL, MT>: GK_PIPE + 4 VW + 2 PL + (MT == 1)
+    GK_PIPE_ELEM_ADJ = 11, GK_PIPE_ELEM = 12,                  // gm_pipe_kernel<true / false, false, 2, false>
+    GK_GM_VW = 13, GK_GM = 14                                  // gm_kernel<false, true / false>
+};
+enum { GF_NONE = 0, GF_VEC4 = 1, GF_VEC4_RT = 2, GF_SCALAR = 3 };   // gm_splitk_finish_kernel<true, S>, <true, 0>, <false, 0>
+struct GmPlan { int kernel, S, finish; };
+
+// gm_prepare + the plan; with a split, g.kb_per_split / g.split_ws are set for the kernel the plan names
+static int gm_plan(const float* A, int lda, const float* W, float* C, int ldc, int coff,
+                   int Bn, int Tin, int Tout, int Cin, int N, int KT, int pad, int stride, int pool_prev,
+                   const st_gemm_epilogue* ep, GmArgs& g, GmPlan& p) {
+    bool veca, vecw;
+    { const int rc = gm_prepare(A, lda, W, C, ldc, coff, Bn, Tin, Tout, Cin, N, KT, pad, stride, pool_prev, ep, g, veca, vecw); if (rc) return rc; }
+    // split-K: the caller passes slabs = st_gemm_splitk_slabs(...) and a workspace of slabs * M * N floats in the epilogue struct
+    p.S = (ep && ep->splitk_ws && veca) ? ep->splitk_slabs : 1;
+    if (p.S > 1) {
+        ST_CHECK_ARG(p.S == st_gemm_splitk_slabs(Bn, Tout, Cin, N, KT) && st_aligned16(ep->splitk_ws), "st_gemm_fwd: splitk_slabs=%d does not match st_gemm_splitk_slabs()", p.S);
+        g.kb_per_split = (KT * g.cpb + p.S - 1) / p.S;
+        g.split_ws = ep->splitk_ws;
+    }
+    const size_t tiles64 = (size_t)((g.M + GM_BM - 1) / GM_BM) * ((N + GM_BN - 1) / GM_BN);
+    if (veca && vecw && !pool_prev && (KT == 1 || lda == Cin)) {      // the LDS-DMA kernel (gd_kernel)
+        if (p.S > 1) g.kb_per_split = ((KT * Cin + 31) / 32 + p.S - 1) / p.S;          // (in 32-float chunks)
+        p.kernel = GK_GD_64x64 + gd_tile(g.M, N, p.S);
+    } else if (veca) {      // (16-byte addressable A: Cin % 4 == 0, so Cin >= 4) the pipelined kernel; otherwise the generic one-block form
+        // 32-row tiles when 64-row tiles would leave compute units with fewer than two workgroups (st_device_info: 256 CUs)
+        const bool small = p.S == 1 && tiles64 < 512;
+        p.kernel = GK_PIPE + (vecw ? 4 : 0) + (pool_prev ? 2 : 0) + (small ? 1 : 0);
+    } else if (!pool_prev && Cin >= 4 && p.S == 1) {
+        // rows that are not 16-byte addressable: the pipelined kernel in its element-wise form.  W counts as "adjacent in ci" when it is
+        // a Linear weight or tap-major, whatever its alignment
+        p.kernel = (KT == 1 || (ep && ep->w_tap_major)) ? GK_PIPE_ELEM_ADJ : GK_PIPE_ELEM;
+    } else p.kernel = vecw ? GK_GM_VW : GK_GM;
+    p.finish = p.S <= 1 ? GF_NONE : N % 4 != 0 ? GF_SCALAR : p.S <= 8 ? GF_VEC4 : GF_VEC4_RT;
+    return 0;
+}
+
 // Several independent GEMM / conv jobs in ONE launch (the CBHG conv bank: K convolutions of the same input, src/module.py:590-598).
 // Jobs the pipelined kernel can take without pooling or split-K go out in launches of up to GM_MAX_BATCH jobs, longest reduction
 // first; a batch with any other job runs as separate st_gemm_fwd launches.
-extern "C" int st_gemm_fwd_batch(const st_gemm_job* jobs, int n, void* stream) {
-    (void)hipGetLastError();
+enum { GB_SEPARATE = 1, GB_GD_64x32 = 2, GB_GD_64x64 = 4, GB_PIPE = 8 };     // st_gemm_fwd_batch_variant() bits
+// -> 0, and the jobs' kernel arguments in g[order[...]] with forms[c] (one GB_ bit) for the launch of jobs [c * 8, c * 8 + 8) of
+// `order`, or *separate = true
+static int gm_batch_plan(const st_gemm_job* jobs, int n, GmArgs* g, int* order, int* forms, bool& separate) {
     ST_CHECK_ARG(jobs && n > 0 && n <= 64, "st_gemm_fwd_batch: bad arguments");
-    GmArgs g[64];
     bool all_ok = true;
     for (int j = 0; j < n; ++j) {
         const st_gemm_job& q = jobs[j];
@@ -935,7 +977,36 @@ extern "C" int st_gemm_fwd_batch(const st_gemm_job* jobs, int n, void* stream) {
         if (rc) return rc;
         all_ok = all_ok && veca && vecw && !q.pool_prev && !(q.ep.splitk_ws && q.ep.splitk_slabs > 1);
     }
-    if (!all_ok || n == 1) {
+    separate = !all_ok || n == 1;
+    if (separate) return 0;
+    for (int j = 0; j < n; ++j) order[j] = j;
+    for (int i = 1; i < n; ++i)        // longest reductions first (insertion sort, stable)
+        for (int j = i; j > 0 && g[order[j]].KT * g[order[j]].cpb > g[order[j - 1]].KT * g[order[j - 1]].cpb; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+    for (int c0 = 0; c0 < n; c0 += GM_MAX_BATCH) {
+        const int cnt = n - c0 < GM_MAX_BATCH ? n - c0 : GM_MAX_BATCH;
+        // LDS-DMA kernel when every job can take it (see st_gemm_fwd); 64 x 32 tiles for the narrow outputs of the conv bank
+        // The pipelined kernel walks each tap in 16-float blocks, the LDS-DMA kernel the flat (tap, channel) index: their k orders, and
+        // so their results, agree only where a tap is whole blocks.  A job that takes the LDS-DMA kernel on its own joins a pipelined
+        // launch only then; otherwise the jobs of this launch run as separate calls.
+        bool dma = true, narrow = true, pipe_ok = true;
+        for (int j = 0; j < cnt; ++j) {
+            const GmArgs& a = g[order[c0 + j]];
+            dma = dma && (a.KT == 1 || a.lda == a.Cin);
+            narrow = narrow && gd_tile(a.M, a.N, 1) == 2;
+            pipe_ok = pipe_ok && (a.KT == 1 || a.lda != a.Cin || a.Cin % GM_BK == 0);
+        }
+        forms[c0 / GM_MAX_BATCH] = dma && narrow ? GB_GD_64x32 : dma ? GB_GD_64x64 : pipe_ok ? GB_PIPE : GB_SEPARATE;
+    }
+    return 0;
+}
+
+extern "C" int st_gemm_fwd_batch(const st_gemm_job* jobs, int n, void* stream) {
+    (void)hipGetLastError();
+    GmArgs g[64];
+    int order[64], forms[64 / GM_MAX_BATCH];
+    bool separate;
+    { const int rc = gm_batch_plan(jobs, n, g, order, forms, separate); if (rc) return rc; }
+    if (separate) {
         for (int j = 0; j < n; ++j) {
             const st_gemm_job& q = jobs[j];
             const int rc = st_gemm_fwd(q.A, q.lda, q.W, q.C, q.ldc, q.coff, q.Bn, q.Tin, q.Tout, q.Cin, q.N, q.KT, q.pad, q.stride, q.pool_prev,
@@ -944,12 +1015,18 @@ extern "C" int st_gemm_fwd_batch(const st_gemm_job* jobs, int n, void* stream) {
         }
         return 0;
     }
-    int order[64];
-    for (int j = 0; j < n; ++j) order[j] = j;
-    for (int i = 1; i < n; ++i)        // longest reductions first (insertion sort, stable)
-        for (int j = i; j > 0 && g[order[j]].KT * g[order[j]].cpb > g[order[j - 1]].KT * g[order[j - 1]].cpb; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
     for (int c0 = 0; c0 < n; c0 += GM_MAX_BATCH) {
         const int cnt = n - c0 < GM_MAX_BATCH ? n - c0 : GM_MAX_BATCH;
+        const int form = forms[c0 / GM_MAX_BATCH];
+        if (form == GB_SEPARATE) {
+            for (int j = 0; j < cnt; ++j) {
+                const st_gemm_job& q = jobs[order[c0 + j]];
+                const int rc = st_gemm_fwd(q.A, q.lda, q.W, q.C, q.ldc, q.coff, q.Bn, q.Tin, q.Tout, q.Cin, q.N, q.KT, q.pad, q.stride,
+                                           q.pool_prev, &q.ep, stream);
+                if (rc) return rc;
+            }
+            continue;
+        }
         GmBatch b;
         memset(&b, 0, sizeof(b));
         int maxM = 0, maxN = 0;
@@ -958,18 +1035,32 @@ extern "C" int st_gemm_fwd_batch(const st_gemm_job* jobs, int n, void* stream) {
             maxM = b.g[j].M > maxM ? b.g[j].M : maxM;
             maxN = b.g[j].N > maxN ? b.g[j].N : maxN;
         }
-        // LDS-DMA kernel when every job can take it (see st_gemm_fwd); 64 x 32 tiles for the narrow outputs of the conv bank
-        bool dma = true, narrow = true;
-        for (int j = 0; j < cnt; ++j) {
-            dma = dma && (b.g[j].KT == 1 || b.g[j].lda == b.g[j].Cin);
-            narrow = narrow && gd_tile(b.g[j].M, b.g[j].N, 1) == 2;
-        }
-        if (dma && narrow) hipLaunchKernelGGL((gd_batch_kernel<64, 32>), dim3((maxM + 63) / 64, (maxN + 31) / 32, cnt), dim3(256), 0, (hipStream_t)stream, b);
-        else if (dma) hipLaunchKernelGGL((gd_batch_kernel<64, 64>), dim3((maxM + 63) / 64, (maxN + 63) / 64, cnt), dim3(256), 0, (hipStream_t)stream, b);
+        if (form == GB_GD_64x32) hipLaunchKernelGGL((gd_batch_kernel<64, 32>), dim3((maxM + 63) / 64, (maxN + 31) / 32, cnt), dim3(256), 0, (hipStream_t)stream, b);
+        else if (form == GB_GD_64x64) hipLaunchKernelGGL((gd_batch_kernel<64, 64>), dim3((maxM + 63) / 64, (maxN + 63) / 64, cnt), dim3(256), 0, (hipStream_t)stream, b);
         else hipLaunchKernelGGL((gm_pipe_batch_kernel<true, 2>), dim3((maxM + 63) / 64, (maxN + GM_BN - 1) / GM_BN, cnt), dim3(GM_THREADS), 0, (hipStream_t)stream, b);
         ST_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int st_gemm_fwd_batch_variant(const st_gemm_job* jobs, int n) {
+    GmArgs g[64];
+    int order[64], forms[64 / GM_MAX_BATCH];
+    bool separate;
+    { const int rc = gm_batch_plan(jobs, n, g, order, forms, separate); if (rc) return rc; }
+    if (separate) return GB_SEPARATE;
+    int bits = 0;
+    for (int c = 0; c * GM_MAX_BATCH < n; ++c) bits |= forms[c];
+    return bits;
+}
+
+extern "C" int st_gemm_fwd_variant(const float* A, int lda, const float* W, const float* C, int ldc, int coff,
+                                   int Bn, int Tin, int Tout, int Cin, int N, int KT, int pad, int stride, int pool_prev,
+                                   const st_gemm_epilogue* ep) {
+    GmArgs g;
+    GmPlan p;
+    { const int rc = gm_plan(A, lda, W, const_cast<float*>(C), ldc, coff, Bn, Tin, Tout, Cin, N, KT, pad, stride, pool_prev, ep, g, p); if (rc) return rc; }
+    return p.kernel | (p.S << 8) | (p.finish << 16);
 }
 
 extern "C" int st_gemm_fwd(const float* A, int lda, const float* W, float* C, int ldc, int coff,
@@ -977,53 +1068,38 @@ extern "C" int st_gemm_fwd(const float* A, int lda, const float* W, float* C, in
                            const st_gemm_epilogue* ep, void* stream) {
     (void)hipGetLastError();  // drop stale errors left by other HIP users of this thread
     GmArgs g;
-    bool veca, vecw;
-    { const int rc = gm_prepare(A, lda, W, C, ldc, coff, Bn, Tin, Tout, Cin, N, KT, pad, stride, pool_prev, ep, g, veca, vecw); if (rc) return rc; }
-    dim3 grid((g.M + GM_BM - 1) / GM_BM, (N + GM_BN - 1) / GM_BN);
+    GmPlan p;
+    { const int rc = gm_plan(A, lda, W, C, ldc, coff, Bn, Tin, Tout, Cin, N, KT, pad, stride, pool_prev, ep, g, p); if (rc) return rc; }
+    const int S = p.S;
+    const dim3 grid((g.M + GM_BM - 1) / GM_BM, (N + GM_BN - 1) / GM_BN, S);
+    const dim3 grid32((g.M + 31) / 32, grid.y);
     hipStream_t st = (hipStream_t)stream;
-    // split-K: the caller passes slabs = st_gemm_splitk_slabs(...) and a workspace of slabs * M * N floats in the epilogue struct
-    const int S = (ep && ep->splitk_ws && veca) ? ep->splitk_slabs : 1;
-    if (S > 1) {
-        ST_CHECK_ARG(S == st_gemm_splitk_slabs(Bn, Tout, Cin, N, KT) && st_aligned16(ep->splitk_ws), "st_gemm_fwd: splitk_slabs=%d does not match st_gemm_splitk_slabs()", S);
-        g.kb_per_split = (KT * g.cpb + S - 1) / S;
-        g.split_ws = ep->splitk_ws;
-        grid.z = S;
+    switch (p.kernel) {
+    case GK_GD_64x64: hipLaunchKernelGGL((gd_kernel<64, 64>), dim3((g.M + 63) / 64, (N + 63) / 64, S), dim3(256), 0, st, g); break;
+    case GK_GD_32x64: hipLaunchKernelGGL((gd_kernel<32, 64>), dim3((g.M + 31) / 32, (N + 63) / 64, S), dim3(256), 0, st, g); break;
+    case GK_GD_64x32: hipLaunchKernelGGL((gd_kernel<64, 32>), dim3((g.M + 63) / 64, (N + 31) / 32, S), dim3(256), 0, st, g); break;
+    case GK_PIPE + 0: hipLaunchKernelGGL((gm_pipe_kernel<false, false, 2>), grid, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE + 1: hipLaunchKernelGGL((gm_pipe_kernel<false, false, 1>), grid32, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE + 2: hipLaunchKernelGGL((gm_pipe_kernel<false, true, 2>), grid, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE + 3: hipLaunchKernelGGL((gm_pipe_kernel<false, true, 1>), grid32, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE + 4: hipLaunchKernelGGL((gm_pipe_kernel<true, false, 2>), grid, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE + 5: hipLaunchKernelGGL((gm_pipe_kernel<true, false, 1>), grid32, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE + 6: hipLaunchKernelGGL((gm_pipe_kernel<true, true, 2>), grid, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE + 7: hipLaunchKernelGGL((gm_pipe_kernel<true, true, 1>), grid32, dim3(GM_THREADS), 0, st, g); break;
+    // (64-row tiles whatever the grid: with 32-row tiles half the threads sit out the scalar A loads -- 124 vs 68 us measured)
+    case GK_PIPE_ELEM_ADJ: hipLaunchKernelGGL((gm_pipe_kernel<true, false, 2, false>), grid, dim3(GM_THREADS), 0, st, g); break;
+    case GK_PIPE_ELEM: hipLaunchKernelGGL((gm_pipe_kernel<false, false, 2, false>), grid, dim3(GM_THREADS), 0, st, g); break;
+    case GK_GM_VW: hipLaunchKernelGGL((gm_kernel<false, true>), grid, dim3(GM_THREADS), 0, st, g); break;
+    default: hipLaunchKernelGGL((gm_kernel<false, false>), grid, dim3(GM_THREADS), 0, st, g); break;
     }
-    if (veca && vecw && !pool_prev && (KT == 1 || lda == Cin)) {      // the LDS-DMA kernel (gd_kernel)
-        if (S > 1) g.kb_per_split = ((KT * Cin + 31) / 32 + S - 1) / S;          // (in 32-float chunks)
-        const int tile = gd_tile(g.M, N, S);
-        if (tile == 0) hipLaunchKernelGGL((gd_kernel<64, 64>), dim3((g.M + 63) / 64, (N + 63) / 64, S), dim3(256), 0, st, g);
-        else if (tile == 1) hipLaunchKernelGGL((gd_kernel<32, 64>), dim3((g.M + 31) / 32, (N + 63) / 64, S), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((gd_kernel<64, 32>), dim3((g.M + 63) / 64, (N + 31) / 32, S), dim3(256), 0, st, g);
-    } else if (veca) {      // (16-byte addressable A: Cin % 4 == 0, so Cin >= 4) the pipelined kernel; otherwise the generic one-block form
-        // 32-row tiles when 64-row tiles would leave compute units with fewer than two workgroups (st_device_info: 256 CUs)
-        const bool small = S == 1 && (size_t)grid.x * grid.y < 512;
-        const dim3 grid32((g.M + 31) / 32, grid.y);
-#define GM_LAUNCH(VW, PL) do { if (small) hipLaunchKernelGGL((gm_pipe_kernel<VW, PL, 1>), grid32, dim3(GM_THREADS), 0, st, g); \
-                               else hipLaunchKernelGGL((gm_pipe_kernel<VW, PL, 2>), grid, dim3(GM_THREADS), 0, st, g); } while (0)
-        if (vecw && pool_prev) GM_LAUNCH(true, true);
-        else if (vecw) GM_LAUNCH(true, false);
-        else if (pool_prev) GM_LAUNCH(false, true);
-        else GM_LAUNCH(false, false);
-#undef GM_LAUNCH
-    } else if (!pool_prev && Cin >= 4 && S == 1) {
-        // rows that are not 16-byte addressable: the pipelined kernel in its element-wise form.  W counts as "adjacent in ci" when it is
-        // a Linear weight or tap-major, whatever its alignment
-        const bool adj = KT == 1 || (ep && ep->w_tap_major);
-        // (64-row tiles whatever the grid: with 32-row tiles half the threads sit out the scalar A loads -- 124 vs 68 us measured)
-        if (adj) hipLaunchKernelGGL((gm_pipe_kernel<true, false, 2, false>), grid, dim3(GM_THREADS), 0, st, g);
-        else hipLaunchKernelGGL((gm_pipe_kernel<false, false, 2, false>), grid, dim3(GM_THREADS), 0, st, g);
-    } else if (vecw) hipLaunchKernelGGL((gm_kernel<false, true>), grid, dim3(GM_THREADS), 0, st, g);
-    else hipLaunchKernelGGL((gm_kernel<false, false>), grid, dim3(GM_THREADS), 0, st, g);
     ST_LAUNCH_CHECK();
     if (S > 1) {
-        const bool vec4 = N % 4 == 0;
-        const size_t items = (size_t)g.M * N / (vec4 ? 4 : 1);
+        const size_t items = (size_t)g.M * N / (p.finish == GF_SCALAR ? 1 : 4);
         size_t blocks = (items + 255) / 256;
         if (blocks > 4096) blocks = 4096;
 #define GM_FIN(SS) hipLaunchKernelGGL((gm_splitk_finish_kernel<true, SS>), dim3((unsigned)blocks), dim3(256), 0, st, g, S)
-        if (vec4) switch (S) { case 2: GM_FIN(2); break; case 3: GM_FIN(3); break; case 4: GM_FIN(4); break; case 5: GM_FIN(5); break;
-                               case 6: GM_FIN(6); break; case 7: GM_FIN(7); break; case 8: GM_FIN(8); break; default: GM_FIN(0); }
+        if (p.finish != GF_SCALAR) switch (S) { case 2: GM_FIN(2); break; case 3: GM_FIN(3); break; case 4: GM_FIN(4); break; case 5: GM_FIN(5); break;
+                                                case 6: GM_FIN(6); break; case 7: GM_FIN(7); break; case 8: GM_FIN(8); break; default: GM_FIN(0); }
         else hipLaunchKernelGGL((gm_splitk_finish_kernel<false, 0>), dim3((unsigned)blocks), dim3(256), 0, st, g, S);
 #undef GM_FIN
         ST_LAUNCH_CHECK();

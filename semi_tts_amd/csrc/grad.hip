@@ -473,10 +473,13 @@ __global__ __launch_bounds__(256) void convw_small_kernel(const CsArgs g) {
         const float* dc = dcs[buf];
         const float* ap = as_[buf];
         const int t0 = (u % tblocks) * CS_TB;
-        const int nsteps = (min(CS_TB, g.Tout - t0) + 3) >> 2;      // (rows past the sequence are zero: whole steps of them are skipped)
+        const int tn = min(CS_TB, g.Tout - t0);
+        const int nsteps = (tn + 3) >> 2;      // (rows past the sequence are zero: whole steps of them are skipped)
         for (int s = 0; s < nsteps; ++s) {
             const int t = 4 * s + q;
-            const float bv = colok ? ap[(t + kk) * 4 + ci] : 0.0f;
+            // (the input of a row past the sequence is not taken either: its dC row is zero, but the input row may be one no output
+            //  reads, and 0 * inf would leave a NaN in every filter)
+            const float bv = colok && t < tn ? ap[(t + kk) * 4 + ci] : 0.0f;
 #pragma unroll
             for (int ft = 0; ft < 4; ++ft) {
                 if (ft < NT) acc[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(dc[t * 68 + ft * 16 + ar], bv, acc[ft], 0, 0, 0);
@@ -514,32 +517,6 @@ __global__ __launch_bounds__(TN_THREADS) void tn_dma_batch_kernel(const TnBatch 
     tn_dma_body<TM>(b.g[j], rr - by * gx, by, bz);
 }
 
-// the slab sums of such a batch in one launch (each job's elements in its own block range; same per-element order as sum_partials*)
-struct SumBatch { const float* part[TN_MAXJ]; float* out[TN_MAXJ]; const float* part_b[TN_MAXJ]; float* out_b[TN_MAXJ];
-                  unsigned per[TN_MAXJ]; int nb[TN_MAXJ], Z[TN_MAXJ], acc[TN_MAXJ]; int blk0[TN_MAXJ + 1]; int n; };
-
-__global__ __launch_bounds__(256) void sum_partials_batch_kernel(const SumBatch b) {
-    int j = 0;
-    while (j + 1 < b.n && (int)blockIdx.x >= b.blk0[j + 1]) ++j;
-    const size_t n = b.per[j], nb = (size_t)b.nb[j];
-    const int Z = b.Z[j], nblk = b.blk0[j + 1] - b.blk0[j];
-    const float* part = b.part[j]; const float* part_b = b.part_b[j];
-    for (size_t i = (size_t)((int)blockIdx.x - b.blk0[j]) * blockDim.x + threadIdx.x; i < n + nb; i += (size_t)nblk * blockDim.x) {
-        const bool isb = i >= n;
-        const float* p = isb ? part_b + (i - n) : part + i;
-        const size_t stride = isb ? nb : n;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int z = 0;
-        for (; z + 4 <= Z; z += 4) {
-            s0 += p[(size_t)z * stride]; s1 += p[(size_t)(z + 1) * stride]; s2 += p[(size_t)(z + 2) * stride]; s3 += p[(size_t)(z + 3) * stride];
-        }
-        for (; z < Z; ++z) s0 += p[(size_t)z * stride];
-        const float sm = (s0 + s1) + (s2 + s3);
-        if (isb) b.out_b[j][i - n] = sm;
-        else b.out[j][i] = b.acc[j] ? b.out[j][i] + sm : sm;
-    }
-}
-
 // out[i] (+)= sum_z part[z][i]   (fixed order)
 __global__ __launch_bounds__(256) void sum_partials_kernel(const float* part, float* out, size_t n, int Z, int accumulate) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -559,10 +536,10 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* part, fl
 // very many slabs of a small matrix (the location conv's gradient: 256 slabs of 2k elements): with one thread per element the sum is a
 // chain of Z dependent-latency loads on a handful of workgroups.  Here a workgroup takes 32 elements, its eight 32-lane groups every
 // eighth slab each (four interleaved sums), and the eight partial sums meet in LDS in group order.
-__global__ __launch_bounds__(256) void sum_partials_tall_kernel(const float* part, float* out, size_t n, int Z, int accumulate) {
+__device__ __forceinline__ void sum_partials_tall_body(const float* part, float* out, size_t n, int Z, int accumulate, int blk) {
     __shared__ float red[8][32];
     const int e = threadIdx.x & 31, zg = threadIdx.x >> 5;
-    const size_t i = (size_t)blockIdx.x * 32 + e;
+    const size_t i = (size_t)blk * 32 + e;
     const bool ok = i < n;
     const float* p = part + (ok ? i : 0);
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -574,6 +551,37 @@ __global__ __launch_bounds__(256) void sum_partials_tall_kernel(const float* par
     if (zg == 0 && ok) {
         const float s = ((red[0][e] + red[1][e]) + (red[2][e] + red[3][e])) + ((red[4][e] + red[5][e]) + (red[6][e] + red[7][e]));
         out[i] = accumulate ? out[i] + s : s;
+    }
+}
+__global__ __launch_bounds__(256) void sum_partials_tall_kernel(const float* part, float* out, size_t n, int Z, int accumulate) {
+    sum_partials_tall_body(part, out, n, Z, accumulate, (int)blockIdx.x);
+}
+
+// the slab sums of such a batch in one launch (each job's elements in its own block range; per element the order of the kernel its
+// single call takes: sum_partials / sum_partials2, or sum_partials_tall for the jobs flagged `tall`)
+struct SumBatch { const float* part[TN_MAXJ]; float* out[TN_MAXJ]; const float* part_b[TN_MAXJ]; float* out_b[TN_MAXJ];
+                  unsigned per[TN_MAXJ]; int nb[TN_MAXJ], Z[TN_MAXJ], acc[TN_MAXJ], tall[TN_MAXJ]; int blk0[TN_MAXJ + 1]; int n; };
+
+__global__ __launch_bounds__(256) void sum_partials_batch_kernel(const SumBatch b) {
+    int j = 0;
+    while (j + 1 < b.n && (int)blockIdx.x >= b.blk0[j + 1]) ++j;
+    const size_t n = b.per[j], nb = (size_t)b.nb[j];
+    const int Z = b.Z[j], nblk = b.blk0[j + 1] - b.blk0[j];
+    const float* part = b.part[j]; const float* part_b = b.part_b[j];
+    if (b.tall[j]) { sum_partials_tall_body(part, b.out[j], n, Z, b.acc[j], (int)blockIdx.x - b.blk0[j]); return; }   // (uniform per block)
+    for (size_t i = (size_t)((int)blockIdx.x - b.blk0[j]) * blockDim.x + threadIdx.x; i < n + nb; i += (size_t)nblk * blockDim.x) {
+        const bool isb = i >= n;
+        const float* p = isb ? part_b + (i - n) : part + i;
+        const size_t stride = isb ? nb : n;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int z = 0;
+        for (; z + 4 <= Z; z += 4) {
+            s0 += p[(size_t)z * stride]; s1 += p[(size_t)(z + 1) * stride]; s2 += p[(size_t)(z + 2) * stride]; s3 += p[(size_t)(z + 3) * stride];
+        }
+        for (; z < Z; ++z) s0 += p[(size_t)z * stride];
+        const float sm = (s0 + s1) + (s2 + s3);
+        if (isb) b.out_b[j][i - n] = sm;
+        else b.out[j][i] = b.acc[j] ? b.out[j][i] + sm : sm;
     }
 }
 
@@ -1326,29 +1334,70 @@ extern "C" size_t st_gemm_wgrad_workspace_floats(int Bn, int Tout, int Cin, int 
     return (size_t)Z * N * Cin * KT + (size_t)Z * N;      // (+ the bias-gradient slabs of st_gemm_wgrad_db)
 }
 
-static int tn_impl(const float* dC, int lddc, int dcoff, const float* A, int lda, float* dW, float* db, float* ws,
-                   int Bn, int Tin, int Tout, int Cin, int N, int KT, int pad, int pool_prev, int accumulate,
-                   void* stream, float* dW1 = nullptr, int split = 0, float* db_dup = nullptr) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(dC && A && dW && ws && Bn > 0 && Tin > 0 && Tout > 0 && Cin > 0 && N > 0 && KT > 0, "st_gemm_wgrad: bad arguments");
-    TnArgs g;
+// The weight-gradient dispatch: the product kernel (with its layout flags), the slab-sum kernel and the slab count Z.  tn_impl launches
+// what tn_plan() says and st_gemm_wgrad_variant() reports it (codes: include/semitts.h); the choice looks at pointer VALUES only.
+enum { TP_CONVW_SMALL = 0, TP_DMA_64 = 1, TP_DMA_RC16_128 = 2, TP_TN_64 = 3, TP_TN_128 = 4 };          // product kernel
+enum { TP_FOLD = 8, TP_LIN = 16, TP_POOL = 32, TP_DIRECT = 64 };                                         // its flags
+enum { TS_NONE = 0, TS_PARTIALS = 1, TS_TALL = 2, TS_PARTIALS2 = 3, TS_PARTIALS2_SPLIT = 4 };             // slab sum
+struct TnPlan { TnArgs g; int Z, TM, product, sum; bool direct; size_t per; dim3 grid; };
+
+// the slab sum a single call runs on Z slabs of per elements (st_gemm_wgrad_batch sums its jobs in the same order)
+static inline int tn_sum_kind(int Z, size_t per, bool db, bool split, bool direct, bool cs) {
+    if (direct) return TS_NONE;
+    if (cs) return TS_TALL;
+    if (split) return TS_PARTIALS2_SPLIT;
+    if (db) return TS_PARTIALS2;
+    return Z >= 64 && per <= 65536 ? TS_TALL : TS_PARTIALS;
+}
+
+static int tn_plan(TnPlan& p, const float* dC, int lddc, int dcoff, const float* A, int lda, bool has_db, bool has_split,
+                   int Bn, int Tin, int Tout, int Cin, int N, int KT, int pad, int pool_prev, int accumulate) {
+    ST_CHECK_ARG(dC && A && Bn > 0 && Tin > 0 && Tout > 0 && Cin > 0 && N > 0 && KT > 0, "st_gemm_wgrad: bad arguments");
+    TnArgs& g = p.g;
     memset(&g, 0, sizeof(g));
-    g.dC = dC; g.lddc = lddc; g.dcoff = dcoff; g.A = A; g.lda = lda; g.part = ws;
+    g.dC = dC; g.lddc = lddc; g.dcoff = dcoff; g.A = A; g.lda = lda;
     g.Bn = Bn; g.Tin = Tin; g.Tout = Tout; g.Cin = Cin; g.N = N; g.KT = KT; g.pad = pad; g.pool_prev = pool_prev;
     g.M = Bn * Tout;
-    const size_t per = (size_t)N * Cin * KT;
-    const int Z = (int)(st_gemm_wgrad_workspace_floats(Bn, Tout, Cin, N, KT) / (per + N));
-    g.rows_per_z = (((g.M + Z - 1) / Z) + 31) / 32 * 32;          // (whole 32-row chunks: the DMA form's unit)
+    p.per = (size_t)N * Cin * KT;
+    p.Z = (int)(st_gemm_wgrad_workspace_floats(Bn, Tout, Cin, N, KT) / (p.per + N));
+    g.rows_per_z = (((g.M + p.Z - 1) / p.Z) + 31) / 32 * 32;          // (whole 32-row chunks: the DMA form's unit)
     // the workspace (hence Z) is sized for the folded layout whenever Cin < 16; a pooled input falls back to the per-tap grid
     g.fold = tn_fold(Cin, KT, pool_prev) ? 1 : 0;
     g.lin = (KT == 1 && pad == 0 && Tin == Tout && !pool_prev) ? 1 : 0;
     g.vecx = st_aligned16(dC) && (lddc % 4 == 0) && (dcoff % 4 == 0);
     g.vecy = st_aligned16(A) && (lda % 4 == 0);
-    const int TM = tn_tile(Cin, N, KT);
-    dim3 grid((N + TM - 1) / TM, g.fold ? (Cin * KT + TM - 1) / TM : ((Cin + TM - 1) / TM) * KT, Z);
+    p.TM = tn_tile(Cin, N, KT);
+    p.grid = dim3((N + p.TM - 1) / p.TM, g.fold ? (Cin * KT + p.TM - 1) / p.TM : ((Cin + p.TM - 1) / p.TM) * KT, p.Z);
+    const int flags = (g.fold ? TP_FOLD : 0) | (g.lin ? TP_LIN : 0) | (pool_prev ? TP_POOL : 0);
+    // few input channels: the im2col columns come out of LDS (convw_small_kernel), Z workgroups = Z slabs
+    const bool cs = cs_shape(Cin, N, KT) && !has_db && !has_split && !pool_prev && g.vecx;
+    // one slab and nothing to add to: the product goes straight to dW (the decoder LSTMs' weight gradients are 29 and 42 MB --
+    // the "sum" of one slab was a 17 us copy)
+    p.direct = !cs && p.Z == 1 && !accumulate && !has_split;      // (a split result always leaves through the slab sum)
+    // the LDS-DMA form where every piece is whole (or wholly outside) and 16-byte addressable, no fold, no fused max-pool
+    const bool whole = N % 4 == 0 && Cin % 4 == 0;
+    const bool dma = !g.fold && !pool_prev && g.vecx && g.vecy && whole && g.rows_per_z % 32 == 0;
+    if (cs) p.product = TP_CONVW_SMALL;
+    else if (dma) p.product = p.TM == 128 ? TP_DMA_RC16_128 : TP_DMA_64;
+    else p.product = p.TM == 128 ? TP_TN_128 : TP_TN_64;
+    if (!cs) p.product |= flags | (p.direct ? TP_DIRECT : 0);
+    p.sum = tn_sum_kind(p.Z, p.per, has_db, has_split, p.direct, cs);
+    return 0;
+}
+
+static int tn_impl(const float* dC, int lddc, int dcoff, const float* A, int lda, float* dW, float* db, float* ws,
+                   int Bn, int Tin, int Tout, int Cin, int N, int KT, int pad, int pool_prev, int accumulate,
+                   void* stream, float* dW1 = nullptr, int split = 0, float* db_dup = nullptr) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(dC && A && dW && ws && Bn > 0 && Tin > 0 && Tout > 0 && Cin > 0 && N > 0 && KT > 0, "st_gemm_wgrad: bad arguments");
+    TnPlan p;
+    { const int rc = tn_plan(p, dC, lddc, dcoff, A, lda, db != nullptr, dW1 != nullptr, Bn, Tin, Tout, Cin, N, KT, pad, pool_prev, accumulate); if (rc) return rc; }
+    TnArgs& g = p.g;
+    const int Z = p.Z;
+    const size_t per = p.per;
+    g.part = ws;
     hipStream_t st = (hipStream_t)stream;
-    if (cs_shape(Cin, N, KT) && !db && !dW1 && !pool_prev && g.vecx) {
-        // few input channels: the im2col columns come out of LDS (convw_small_kernel), Z workgroups = Z slabs
+    if ((p.product & 7) == TP_CONVW_SMALL) {
         CsArgs c;
         c.dC = dC + dcoff; c.lddc = lddc; c.A = A; c.lda = lda; c.part = ws; c.Bn = Bn; c.Tin = Tin; c.Tout = Tout; c.Cin = Cin; c.N = N;
         c.KT = KT; c.pad = pad; c.Z = Z;
@@ -1358,31 +1407,38 @@ static int tn_impl(const float* dC, int lddc, int dcoff, const float* A, int lda
         ST_LAUNCH_CHECK();
         return 0;
     }
-    // one slab and nothing to add to: the product goes straight to dW (the decoder LSTMs' weight gradients are 29 and 42 MB --
-    // the "sum" of one slab was a 17 us copy)
-    const bool direct = Z == 1 && !accumulate && !dW1;      // (a split result always leaves through the slab sum)
-    if (direct) g.part = dW;
-    if (db) g.db_part = direct ? db : ws + (size_t)Z * per;
-    // the LDS-DMA form where every piece is whole (or wholly outside) and 16-byte addressable, no fold, no fused max-pool
-    const bool whole = N % 4 == 0 && Cin % 4 == 0;
-    const bool dma = !g.fold && !pool_prev && g.vecx && g.vecy && whole && g.rows_per_z % 32 == 0;
-    if (dma) {
-        const size_t lds = (size_t)3 * 2 * 32 * TM * sizeof(float);       // 48 KB at TM = 64, 96 KB at 128
-        // (128 tiles: 16-row chunks, 48 KB -- three workgroups per compute unit; 64 tiles: 32-row chunks, 48 KB: 16-row chunks change nothing)
-        if (TM == 128) hipLaunchKernelGGL((tn_dma_rc16_kernel<128>), grid, dim3(TN_THREADS), lds / 2, st, g);
-        else hipLaunchKernelGGL((tn_dma_kernel<64>), grid, dim3(TN_THREADS), lds, st, g);
-    } else if (TM == 128) hipLaunchKernelGGL((tn_kernel<128>), grid, dim3(TN_THREADS), 0, st, g);
-    else hipLaunchKernelGGL((tn_kernel<64>), grid, dim3(TN_THREADS), 0, st, g);
+    if (p.direct) g.part = dW;
+    if (db) g.db_part = p.direct ? db : ws + (size_t)Z * per;
+    switch (p.product & 7) {
+    // (128 tiles: 16-row chunks, 48 KB -- three workgroups per compute unit; 64 tiles: 32-row chunks, 48 KB: 16-row chunks change nothing)
+    case TP_DMA_RC16_128: hipLaunchKernelGGL((tn_dma_rc16_kernel<128>), p.grid, dim3(TN_THREADS), (size_t)3 * 2 * 16 * 128 * sizeof(float), st, g); break;
+    case TP_DMA_64: hipLaunchKernelGGL((tn_dma_kernel<64>), p.grid, dim3(TN_THREADS), (size_t)3 * 2 * 32 * 64 * sizeof(float), st, g); break;
+    case TP_TN_128: hipLaunchKernelGGL((tn_kernel<128>), p.grid, dim3(TN_THREADS), 0, st, g); break;
+    default: hipLaunchKernelGGL((tn_kernel<64>), p.grid, dim3(TN_THREADS), 0, st, g); break;
+    }
     ST_LAUNCH_CHECK();
-    if (direct) return 0;
-    if (dW1) hipLaunchKernelGGL(sum_partials2_kernel<true>, dim3(blocks_for(per + (db ? N : 0))), dim3(256), 0, st, ws, dW, per, Z, accumulate,
-                                db ? g.db_part : nullptr, db, (size_t)(db ? N : 0), dW1, Cin, split, db ? db_dup : nullptr);
-    else if (db) hipLaunchKernelGGL(sum_partials2_kernel<false>, dim3(blocks_for(per + N)), dim3(256), 0, st, ws, dW, per, Z, accumulate, g.db_part, db, (size_t)N,
-                                    nullptr, 0, 0, nullptr);
-    else if (Z >= 64 && per <= 65536) hipLaunchKernelGGL(sum_partials_tall_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, ws, dW, per, Z, accumulate);
-    else hipLaunchKernelGGL(sum_partials_kernel, dim3(blocks_for(per)), dim3(256), 0, st, ws, dW, per, Z, accumulate);
+    switch (p.sum) {
+    case TS_NONE: return 0;
+    case TS_PARTIALS2_SPLIT:
+        hipLaunchKernelGGL(sum_partials2_kernel<true>, dim3(blocks_for(per + (db ? N : 0))), dim3(256), 0, st, ws, dW, per, Z, accumulate,
+                           db ? g.db_part : nullptr, db, (size_t)(db ? N : 0), dW1, Cin, split, db ? db_dup : nullptr);
+        break;
+    case TS_PARTIALS2:
+        hipLaunchKernelGGL(sum_partials2_kernel<false>, dim3(blocks_for(per + N)), dim3(256), 0, st, ws, dW, per, Z, accumulate, g.db_part, db, (size_t)N,
+                           nullptr, 0, 0, nullptr);
+        break;
+    case TS_TALL: hipLaunchKernelGGL(sum_partials_tall_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, ws, dW, per, Z, accumulate); break;
+    default: hipLaunchKernelGGL(sum_partials_kernel, dim3(blocks_for(per)), dim3(256), 0, st, ws, dW, per, Z, accumulate); break;
+    }
     ST_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int st_gemm_wgrad_variant(const float* dC, int lddc, int dcoff, const float* A, int lda, int Bn, int Tin, int Tout, int Cin,
+                                     int N, int KT, int pad, int pool_prev, int accumulate, int with_db, int with_split) {
+    TnPlan p;
+    { const int rc = tn_plan(p, dC, lddc, dcoff, A, lda, with_db != 0, with_split != 0, Bn, Tin, Tout, Cin, N, KT, pad, pool_prev, accumulate); if (rc) return rc; }
+    return p.product | (p.sum << 8) | (p.Z << 16);
 }
 
 // Several st_gemm_wgrad[_db] (no pooling, no accumulate): the jobs that take the LDS-DMA form with 64-tiles (the small matrices this is
@@ -1390,10 +1446,33 @@ static int tn_impl(const float* dC, int lddc, int dcoff, const float* A, int lda
 // slab count and the summation order it has on its own: the results are bit for bit those of the separate calls.
 static size_t tn_ws4(const st_wgrad_job& j) { return (st_gemm_wgrad_workspace_floats(j.Bn, j.Tout, j.Cin, j.N, j.KT) + 3) / 4 * 4; }
 
+// the plan of job j on its own; true when it joins a group launch (the LDS-DMA product on 64-tiles)
+static bool tn_batch_job(const st_wgrad_job& j, TnPlan& p) {
+    if (tn_plan(p, j.dC, j.lddc, j.dcoff, j.A, j.lda, j.db != nullptr, false, j.Bn, j.Tin, j.Tout, j.Cin, j.N, j.KT, j.pad, 0, 0)) return false;
+    return (p.product & 7) == TP_DMA_64 && p.per < (1ull << 32);
+}
+
 extern "C" size_t st_gemm_wgrad_batch_workspace_floats(const st_wgrad_job* jobs, int n) {
     size_t t = 0;
     for (int i = 0; i < n; ++i) t += tn_ws4(jobs[i]);
     return t;
+}
+
+// codes[i] = 1 + the group launch job i joins, 0 when it runs as a call of its own; returns the number of group launches
+extern "C" int st_gemm_wgrad_batch_variant(const st_wgrad_job* jobs, int n, int* codes) {
+    ST_CHECK_ARG(jobs && n > 0 && codes, "st_gemm_wgrad_batch_variant: bad arguments");
+    int m = 0, groups = 0, last = -1;
+    for (int i = 0; i < n; ++i) {
+        TnPlan p;
+        codes[i] = 0;
+        if (!tn_batch_job(jobs[i], p)) continue;
+        codes[i] = groups + 1;
+        last = i;
+        if (++m == TN_MAXJ) { ++groups; m = 0; }
+    }
+    if (m == 1) codes[last] = 0;          // (a group of one is a single call)
+    else if (m > 1) ++groups;
+    return groups;
 }
 
 extern "C" int st_gemm_wgrad_batch(const st_wgrad_job* jobs, int n, float* ws, void* stream) {
@@ -1428,25 +1507,16 @@ extern "C" int st_gemm_wgrad_batch(const st_wgrad_job* jobs, int n, float* ws, v
     for (int i = 0; i < n; ++i) {
         const st_wgrad_job& j = jobs[i];
         ST_CHECK_ARG(j.dC && j.A && j.dW && j.Bn > 0 && j.Tin > 0 && j.Tout > 0 && j.Cin > 0 && j.N > 0 && j.KT > 0, "st_gemm_wgrad_batch: bad job %d", i);
-        TnArgs g;
-        memset(&g, 0, sizeof(g));
-        g.dC = j.dC; g.lddc = j.lddc; g.dcoff = j.dcoff; g.A = j.A; g.lda = j.lda;
-        g.Bn = j.Bn; g.Tin = j.Tin; g.Tout = j.Tout; g.Cin = j.Cin; g.N = j.N; g.KT = j.KT; g.pad = j.pad; g.pool_prev = 0;
-        g.M = j.Bn * j.Tout;
-        const size_t per = (size_t)j.N * j.Cin * j.KT;
-        const int Z = (int)(st_gemm_wgrad_workspace_floats(j.Bn, j.Tout, j.Cin, j.N, j.KT) / (per + j.N));
-        g.rows_per_z = (((g.M + Z - 1) / Z) + 31) / 32 * 32;
-        g.fold = tn_fold(j.Cin, j.KT, 0) ? 1 : 0;
-        g.lin = (j.KT == 1 && j.pad == 0 && j.Tin == j.Tout) ? 1 : 0;
-        g.vecx = st_aligned16(j.dC) && (j.lddc % 4 == 0) && (j.dcoff % 4 == 0);
-        g.vecy = st_aligned16(j.A) && (j.lda % 4 == 0);
-        const bool dma = !g.fold && g.vecx && g.vecy && j.N % 4 == 0 && j.Cin % 4 == 0 && g.rows_per_z % 32 == 0;
-        if (!dma || tn_tile(j.Cin, j.N, j.KT) != 64 || per >= (1ull << 32)) {
+        TnPlan p;
+        if (!tn_batch_job(j, p)) {
             const int rc = single(i, off);
             if (rc) return rc;
         } else {
+            TnArgs& g = p.g;
+            const int Z = p.Z;
+            const size_t per = p.per;
             float* wsj = ws + off;
-            const bool direct = Z == 1;
+            const bool direct = p.direct;
             g.part = direct ? j.dW : wsj;
             if (j.db) g.db_part = direct ? j.db : wsj + (size_t)Z * per;
             tb.g[m] = g;
@@ -1456,8 +1526,9 @@ extern "C" int st_gemm_wgrad_batch(const st_wgrad_job* jobs, int n, float* ws, v
             if (!direct) {
                 sb.part[nsum] = wsj; sb.out[nsum] = j.dW; sb.part_b[nsum] = j.db ? wsj + (size_t)Z * per : wsj; sb.out_b[nsum] = j.db;
                 sb.per[nsum] = (unsigned)per; sb.nb[nsum] = j.db ? j.N : 0; sb.Z[nsum] = Z; sb.acc[nsum] = 0;
+                sb.tall[nsum] = p.sum == TS_TALL;
                 sb.blk0[nsum] = sblocks;
-                sblocks += blocks_for(per + (j.db ? j.N : 0));
+                sblocks += p.sum == TS_TALL ? (int)((per + 31) / 32) : blocks_for(per + (j.db ? j.N : 0));
                 ++nsum;
             }
             gi[m] = i; goff[m] = off;
