@@ -916,7 +916,10 @@ typedef struct st_decoder_bwd_io {
  * fails (instead of falling back to the six-launch loop, which reads a zero slot) when fuse_pw is set and cannot be honoured. */
 int st_decoder_bwd_fuse_dims(const st_decoder_dims* d);
 /* which forms st_decoder_backward will take for these dimensions and buffers: bit 0 split attention backward, bit 1 partial decoder-cell
- * product, bit 2 partial query-cell product (dxq_part holds the gradient w.r.t. the query cell's inputs as slabs) */
+ * product, bit 2 partial query-cell product (dxq_part holds the gradient w.r.t. the query cell's inputs as slabs), bit 3 the fused loop
+ * (io.fuse_pw and dimensions st_decoder_bwd_fuse_dims takes), bit 4 the overlapped loop (fused, overlap_attn, attn_s_tape); bits 8..11 the
+ * attention workgroups per utterance (1, 2 or 4), bits 12..15 the decoder cell's K-split slabs (0 without the partial product), bits
+ * 16..19 the query cell's (0 without it) */
 int st_decoder_bwd_forms(const st_decoder_dims* d, const st_decoder_bwd_io* io);
 /* st_attn_step_bwd with S = pm + W_l loc of the step given (s_in, (B,L,A)): loc_t is not written (may be NULL) */
 int st_attn_step_bwd_s(const float* pq, const float* pm, const float* memory,
@@ -979,6 +982,18 @@ int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, const st_t1
                                               const st_lstm_pw_job* job, const st_attn_bwd_job* ab, void* stream);
 /* 1 when the attention backward's 48-position block (+ a hosting product's 8 KB) fits the LDS for these dims: what parts > 1 needs */
 int st_attn_bwd_wide_fits(int L, int A, int E, int F, int K);
+/* The launch an attention-step backward takes, from shapes alone (touches no memory): hosted = 0 st_attn_step_bwd[_s|_t16] (parts must be
+ * 1), 1 st_skinny_linear_packed_lstm_bwd_attn_bwd beside a product of N outputs for B rows, 2 st_skinny_partial_attn_bwd; has_s: the
+ * forward's S is given (s_in); loc_lin_w only for its alignment.  Returns kernel | wide << 4 | opt_in << 5 | s << 6 | wl_fast << 7 |
+ * mem_pf << 8 --
+ *   kernel: 0 plain, 1 hosted, 2 hosted fallback to two launches (the other bits: the plain launch), 3 dual (parts 2, both batch
+ *           tiles of a product row tile in one 16-wave workgroup), 4 NB2 (ST_AB_NB2), 5 generic parts 2 (ST_AB_NO_DUAL, or not 16 < B <= 32),
+ *           6 lean split parts 4, 7 partial product, 8 partial product with 16-wave workgroups (ST_PART_KW16);
+ *   wide: the 48-position block (else 16); opt_in: the dynamic LDS exceeds the kernel's default limit and is raised first (the plain
+ *   launch: > 64 KiB); s: the kernel starts from S; wl_fast: F == 32 and W_l 16-byte aligned; mem_pf: E <= 512 (memory rows prefetched)
+ * -- or a refusal: -1 bad dims, -2 the plain launch needs more than 160 KiB of LDS, -3 hosted without S, -4 parts not possible (not 2 or
+ * 4, A does not split, or the lean image does not fit), -5 not the partial form's two-part job or rows */
+int st_attn_bwd_variant(int L, int A, int E, int F, int K, int has_s, int parts, int hosted, int B, int N, const float* loc_lin_w);
 /* st_skinny_linear_packed_lstm_bwd_fwd with an st_attn_hist_job beside it in the same launch (the BPTT step's W_q^T dpq product, which
  * occupies half of the compute units, hosts the history part of the step's split attention backward) */
 int st_skinny_linear_packed_lstm_bwd_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,

@@ -266,6 +266,7 @@ SIGNATURES = {
     'st_skinny_linear_packed_lstm_bwd_fwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), P],
     'st_skinny_linear_packed_lstm_bwd_attn_bwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), C.POINTER(StAttnBwdJob), P],
     'st_attn_bwd_wide_fits': [I, I, I, I, I],
+    'st_attn_bwd_variant': [I, I, I, I, I, I, I, I, I, I, P],
     'st_skinny_linear_packed_attn_hist': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StAttnHistJob), P],
     'st_skinny_partial_attn_hist': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StAttnHistJob), P],
     'st_decoder_bwd_forms': [C.POINTER(StDecoderDims), C.POINTER(StDecoderBwdIO)],

@@ -1097,7 +1097,9 @@ class _DecoderFn(Function):
                     io.dpre_norm_w[l], io.dpre_norm_b[l] = ops._p(dnorm[2 * l]), ops._p(dnorm[2 * l + 1])
                 io.pre_norm_eps = float(dec.prenet.layers[0].norm.eps)
         # (does the loop leave the gradient w.r.t. the query cell's inputs as K-split slabs?  The library decides by shape; ask it)
-        dxq_slabs = bool(int(lib.st_decoder_bwd_forms(C.byref(dims), C.byref(io))) & 4)
+        forms = int(lib.st_decoder_bwd_forms(C.byref(dims), C.byref(io)))
+        dec._last_bwd_forms = forms       # (which loop form ran: tests check they reach the one they mean)
+        dxq_slabs = bool(forms & 4)
         _lib.check(lib.st_decoder_backward(C.byref(bw), C.byref(dims), C.byref(io), ops.stream_handle()), 'st_decoder_backward')
 
         # weight gradients: TN GEMMs over the tapes (rows = (step, utterance); pad rows are zero)

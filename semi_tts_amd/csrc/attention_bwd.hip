@@ -115,11 +115,12 @@ static int ab_step_impl(const st_t16_view* dpq_t16, const float* pq, const float
                 dw_direct, ld_dw, n_dw, dcum, dcum_add, ld_dcum_add, dpq, dhist, ds_t, loc_t, dloc_t, hist_t, dctx_t, dv_t, s_in,
                 B, L, A, E, F, K)) return -1;
     // the wide block when the forward kept S and its LDS image fits; two workgroups of it never share a compute unit anyway (B workgroups)
-    const bool wide = ab_wide(a);
-    const size_t lds = ab_lds_bytes(a, wide);
-    ST_CHECK_ARG(lds <= 160 * 1024, "st_attn_step_bwd: L=%d needs %zu bytes of LDS (> 160 KiB)", L, lds);
+    const AbPlan pl = ab_plan(L, A, E, F, K, s_in != nullptr, 1, 0, B, B, 0, st_aligned16(loc_lin_w));
+    ST_CHECK_ARG(pl.code >= 0, "st_attn_step_bwd: L=%d needs %zu bytes of LDS (> 160 KiB)", L, pl.lds);
+    const bool wide = pl.wide;
+    const size_t lds = pl.lds;
     static size_t lds_enabled = 0;
-    if (lds > 64 * 1024 && lds > lds_enabled) {
+    if (pl.opt_in && lds > lds_enabled) {
         ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_kernel<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_kernel<true, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_kernel<true, AB_LBLK_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -130,6 +131,13 @@ static int ab_step_impl(const st_t16_view* dpq_t16, const float* pq, const float
     else hipLaunchKernelGGL((ab_kernel<false, 16>), dim3(B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
     ST_LAUNCH_CHECK();
     return 0;
+}
+
+// the launch st_attn_step_bwd[_s|_t16] (hosted = 0), st_skinny_linear_packed_lstm_bwd_attn_bwd (1) or st_skinny_partial_attn_bwd (2) takes
+// for these dims (see AbPlan); touches no memory
+extern "C" int st_attn_bwd_variant(int L, int A, int E, int F, int K, int has_s, int parts, int hosted, int B, int N, const float* loc_lin_w) {
+    if (hosted < 0 || hosted > 2 || (hosted == 0 && parts > 1)) return AB_R_DIMS;
+    return ab_plan(L, A, E, F, K, has_s != 0, parts, hosted, B, B, N, st_aligned16(loc_lin_w)).code;
 }
 
 // does the wide (48-position) block of the attention backward fit the LDS next to a hosting product's 8 KB? (what the split form needs)

@@ -700,4 +700,73 @@ inline size_t ab_lds_bytes(const AbArgs& a, bool wide, int parts = 1) {
     return (size_t)ab_layout(a.L, a.A / parts, a.E, a.F, a.K, wide ? AB_LBLK_MAX : 16, a.s_in != nullptr, parts > 1).total * sizeof(float);
 }
 
+// The launch an attention-step backward takes: one plan for the plain entry points (ab_step_impl) and the two hosted ones
+// (st_skinny_linear_packed_lstm_bwd_attn_bwd, st_skinny_partial_attn_bwd).  Shapes and flags only -- pointer checks stay with the callers.
+// st_attn_bwd_variant reports `code` (include/semitts.h); a refusal is a negative code and the callers' error message.
+enum AbKernel { AB_K_PLAIN = 0, AB_K_HOSTED = 1, AB_K_FALLBACK = 2, AB_K_DUAL = 3, AB_K_NB2 = 4, AB_K_PARTS2 = 5, AB_K_PARTS4 = 6,
+                AB_K_PARTIAL = 7, AB_K_PARTIAL_KW16 = 8 };
+enum AbRefusal { AB_R_DIMS = -1, AB_R_LDS = -2, AB_R_NEEDS_S = -3, AB_R_PARTS = -4, AB_R_PARTIAL = -5 };
+struct AbPlan {
+    int kernel;       // AbKernel (the fallback: the plain launch below is the attention's)
+    int parts;        // attention workgroups per utterance
+    bool wide;        // the 48-position block (else 16)
+    bool opt_in;      // the launch raises the kernel's dynamic-LDS limit first
+    size_t lds;       // dynamic LDS bytes of the attention's launch
+    int code;         // kernel | wide << 4 | opt_in << 5 | has_s << 6 | wl_fast << 7 | mem_pf << 8, or an AbRefusal
+};
+
+// hosted: 0 the plain launch, 1 beside a product of N outputs (B_prod rows), 2 beside the K-split partial product.  wl_aligned: W_l is
+// 16-byte aligned (with F == 32 every part's rows then are: wl_fast)
+inline AbPlan ab_plan(int L, int A, int E, int F, int K, bool has_s, int parts, int hosted, int B, int B_prod, int N, bool wl_aligned) {
+    AbPlan p = {AB_K_PLAIN, 1, false, false, 0, 0};
+    auto refuse = [&](int r) { p.code = r; return p; };
+    if (!(B > 0 && L > 0 && A > 0 && E > 0 && F > 0 && K > 0 && (K & 1)) || !(A <= AB_THREADS / 2 && AB_THREADS % A == 0) || (E & 3) != 0 ||
+        F > AB_FMAX) return refuse(AB_R_DIMS);
+    const size_t full48 = (size_t)ab_layout(L, A, E, F, K, AB_LBLK_MAX, true).total * sizeof(float);
+    if (hosted == 0) {
+        p.wide = has_s && full48 <= 160 * 1024;
+        p.lds = (size_t)ab_layout(L, A, E, F, K, p.wide ? AB_LBLK_MAX : 16, has_s).total * sizeof(float);
+        if (p.lds > 160 * 1024) return refuse(AB_R_LDS);
+        p.opt_in = p.lds > 64 * 1024;
+    } else if (hosted == 1) {
+        if (!has_s) return refuse(AB_R_NEEDS_S);
+        const size_t red = (size_t)8 * 1 * 64 * sizeof(f32x4);          // the product's static LDS in the same workgroup
+        p.parts = parts > 1 ? parts : 1;
+        p.wide = full48 + red <= 160 * 1024;
+        if (p.parts > 1) {
+            p.wide = true;                                               // (the split form always runs the 48-position block, on its lean image)
+            if (p.parts != 2 && p.parts != 4) return refuse(AB_R_PARTS);
+            const int As = A / p.parts;
+            p.lds = (size_t)ab_layout(L, As, E, F, K, AB_LBLK_MAX, true, true).total * sizeof(float);
+            if (!(p.lds + red <= 160 * 1024 && A % p.parts == 0 && AB_THREADS % As == 0 && As % 16 == 0 && AB_THREADS / As >= 2 * p.parts &&
+                  As <= AB_THREADS / (2 * p.parts))) return refuse(AB_R_PARTS);
+        } else p.lds = (size_t)ab_layout(L, A, E, F, K, p.wide ? AB_LBLK_MAX : 16, true).total * sizeof(float);
+        const int tiles = (N + 15) / 16, BT = (B_prod + 15) >> 4;
+        const bool one_round = p.parts == 2 && BT == 2 && tiles + 2 * B <= 256;
+        if (p.lds + red > 160 * 1024) {
+            // a text so long that the attention backward needs (nearly) all the LDS of a compute unit: the two launches one after the other
+            // (a refusal there is the plain entry point's: the product still runs first)
+            AbPlan q = ab_plan(L, A, E, F, K, true, 1, 0, B, B_prod, N, wl_aligned);
+            q.kernel = AB_K_FALLBACK;
+            if (q.code < 0) return q;
+            p = q;
+        } else if (one_round && getenv("ST_AB_NB2")) { p.kernel = AB_K_NB2; p.opt_in = p.lds > 32 * 1024; }
+        else if (one_round && !getenv("ST_AB_NO_DUAL")) { p.kernel = AB_K_DUAL; p.opt_in = p.lds > 32 * 1024; }
+        else { p.kernel = p.parts == 4 ? AB_K_PARTS4 : p.parts == 2 ? AB_K_PARTS2 : AB_K_HOSTED; p.opt_in = p.lds > 48 * 1024; }
+    } else {
+        if (!(B_prod > 16 && B_prod <= 32)) return refuse(AB_R_PARTIAL);
+        const size_t red = (size_t)8 * 4 * 64 * sizeof(f32x4);
+        p.parts = 2; p.wide = true;
+        p.lds = (size_t)ab_layout(L, A / 2, E, F, K, AB_LBLK_MAX, true, true).total * sizeof(float);
+        if (!(parts == 2 && has_s && p.lds + red <= 160 * 1024 && A % 32 == 0 && AB_THREADS % (A / 2) == 0 && AB_THREADS / (A / 2) >= 4))
+            return refuse(AB_R_PARTIAL);
+        p.kernel = getenv("ST_PART_KW16") ? AB_K_PARTIAL_KW16 : AB_K_PARTIAL;
+        p.opt_in = p.lds > 32 * 1024;
+    }
+    const bool s_kernel = has_s || hosted != 0;
+    const bool wl_fast = F == AB_FMAX && wl_aligned;       // (A / parts * F <= 4 (4 / parts) 512 always holds with A <= 256)
+    p.code = p.kernel | (p.wide ? 16 : 0) | (p.opt_in ? 32 : 0) | (s_kernel ? 64 : 0) | (wl_fast ? 128 : 0) | (E <= 512 ? 256 : 0);
+    return p;
+}
+
 }  // namespace

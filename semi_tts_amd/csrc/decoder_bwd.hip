@@ -84,7 +84,9 @@ extern "C" int st_decoder_bwd_fuse_dims(const st_decoder_dims* d) { return d && 
 extern "C" int st_decoder_bwd_forms(const st_decoder_dims* d, const st_decoder_bwd_io* io) {
     if (!d || !io) return 0;
     const BwdForms f = bwd_forms(d, io);
-    return (f.parts > 1 ? 1 : 0) | (f.partial_d ? 2 : 0) | (f.partial_q ? 4 : 0);
+    const bool fused = io->fuse_pw && st_decoder_bwd_fuse_dims(d), overlap = fused && io->overlap_attn && io->attn_s_tape;
+    return (f.parts > 1 ? 1 : 0) | (f.partial_d ? 2 : 0) | (f.partial_q ? 4 : 0) | (fused ? 8 : 0) | (overlap ? 16 : 0) | (f.parts << 8) |
+           ((f.partial_d ? f.dsplits : 0) << 12) | ((f.partial_q ? f.qsplits : 0) << 16);
 }
 
 static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_decoder_dims* d, const st_decoder_bwd_io* io, void* stream);

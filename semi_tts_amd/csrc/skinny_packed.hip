@@ -1968,20 +1968,19 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
     AbArgs t;
     if (ab_fill_job(t, ab)) return -1;
     ST_CHECK_ARG(t.s_in, "st_skinny_linear_packed_lstm_bwd_attn_bwd: the hosted attention backward starts from the forward's S (s_in)");
-    const size_t red_bytes = (size_t)8 * 1 * 64 * sizeof(f32x4);          // the product's static LDS in the same workgroup
-    const bool wide = ab_wide(t, red_bytes);
-    // parts > 1: the split form (see pk_pw_ab_kernel); the caller then runs st_skinny_linear_packed_lstm_bwd_attn_hist next
-    const int parts = ab->parts > 1 ? ab->parts : 1;
-    const size_t lds = ab_lds_bytes(t, wide || parts > 1, parts);      // (the split form always runs the 48-position block, on its lean image)
+    // the launch (AbPlan, attention_bwd_body.h): parts > 1 is the split form (see pk_pw_ab_kernel); the caller then runs
+    // st_skinny_linear_packed_lstm_bwd_attn_hist next
+    const AbPlan pl = ab_plan(t.L, t.A, t.E, t.F, t.K, true, ab->parts, 1, t.B, B, N, st_aligned16(t.loc_lin_w));
+    const int parts = pl.parts;
+    const size_t lds = pl.lds;
     if (parts > 1) {
         ST_CHECK_ARG(parts == 2 || parts == 4, "st_skinny_linear_packed_lstm_bwd_attn_bwd: parts = %d (1, 2 or 4)", parts);
-        ST_CHECK_ARG(ab->dloc_part && !ab->dcum_add && t.s_in && lds + red_bytes <= 160 * 1024 && t.A % parts == 0 && AB_THREADS % (t.A / parts) == 0 &&
-                     (t.A / parts) % 16 == 0 && AB_THREADS / (t.A / parts) >= 2 * parts && t.A / parts <= AB_THREADS / (2 * parts),
+        ST_CHECK_ARG(ab->dloc_part && !ab->dcum_add && pl.code >= 0,
                      "st_skinny_linear_packed_lstm_bwd_attn_bwd: parts = %d needs dloc_part, no dcum_add (the history job keeps dcum), the wide block "
                      "and A = %d splitting into parts of a multiple of 16 dims that divide %d", parts, t.A, AB_THREADS);
         t.dloc_part = ab->dloc_part;
     }
-    if (lds + red_bytes > 160 * 1024) {
+    if (pl.kernel == AB_K_FALLBACK) {
         // a text so long that the attention backward needs (nearly) all the LDS of a compute unit for itself: the two launches one after
         // the other (they are independent: any order)
         if (job) rc = st_skinny_linear_packed_lstm_bwd_fwd(packed_w, x, K, y, ldy, B, N, job, stream);
@@ -1994,12 +1993,12 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
                                     ab->hist_t, ab->dctx_t, ab->dv_t, ab->s_in, ab->B, ab->L, ab->A, ab->E, ab->F, ab->K, stream);
     }
     const int tiles = (N + 15) / 16, BT = (B + 15) >> 4;
-    if (parts == 2 && BT == 2 && tiles + 2 * t.B <= 256 && getenv("ST_AB_NB2")) {
+    if (pl.kernel == AB_K_NB2) {
         // both batch tiles of a row tile in ONE eight-wave workgroup (pk_body NB = 2: every weight fragment feeds two MFMAs): N / 16 product
         // workgroups + 2 B attention workgroups <= 256: one round, a compute unit each
         auto k2 = pk_pw_ab_kernel<2, 8, 2, AB_LBLK_MAX, 2>;
         static size_t lds_nb2 = 0;
-        if (lds > 32 * 1024 && lds > lds_nb2) {
+        if (pl.opt_in && lds > lds_nb2) {
             ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             lds_nb2 = lds;
         }
@@ -2008,10 +2007,10 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
         ST_LAUNCH_CHECK();
         return 0;
     }
-    if (parts == 2 && BT == 2 && tiles + 2 * t.B <= 256 && !getenv("ST_AB_NO_DUAL")) {
+    if (pl.kernel == AB_K_DUAL) {
         auto kd = pk_pw_ab_dual_kernel<8, 2, AB_LBLK_MAX, 2>;
         static size_t lds_dual = 0;
-        if (lds > 32 * 1024 && lds > lds_dual) {
+        if (pl.opt_in && lds > lds_dual) {
             ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             lds_dual = lds;
         }
@@ -2020,11 +2019,12 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
         ST_LAUNCH_CHECK();
         return 0;
     }
+    const bool wide = pl.wide;
     auto kern = parts == 4 ? pk_pw_ab_kernel<1, 8, 2, AB_LBLK_MAX, 4> : parts == 2 ? pk_pw_ab_kernel<1, 8, 2, AB_LBLK_MAX, 2>
                 : wide ? pk_pw_ab_kernel<1, 8, 2, AB_LBLK_MAX, 1> : pk_pw_ab_kernel<1, 8, 2, 16, 1>;
     static size_t lds_set[4] = {0, 0, 0, 0};
     const int ki = parts == 4 ? 3 : parts == 2 ? 2 : wide ? 1 : 0;
-    if (lds > 48 * 1024 && lds > lds_set[ki]) {
+    if (pl.opt_in && lds > lds_set[ki]) {
         ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set[ki] = lds;
     }
@@ -2175,17 +2175,16 @@ extern "C" int st_skinny_partial_attn_bwd(const float* packed_w, const st_t16_vi
     }
     AbArgs t;
     if (ab_fill_job(t, ab)) return -1;
-    const size_t red_bytes = (size_t)8 * 4 * 64 * sizeof(f32x4);
-    ST_CHECK_ARG(ab->parts == 2 && ab->dloc_part && !ab->dcum_add && t.s_in && ab_lds_bytes(t, true, 2) + red_bytes <= 160 * 1024 && t.A % 32 == 0 &&
-                 AB_THREADS % (t.A / 2) == 0 && AB_THREADS / (t.A / 2) >= 4, "st_skinny_partial_attn_bwd: the attention job must be the two-part form (parts = 2, dloc_part, S kept, "
+    const AbPlan pl = ab_plan(t.L, t.A, t.E, t.F, t.K, t.s_in != nullptr, ab->parts, 2, t.B, B, N, st_aligned16(t.loc_lin_w));
+    ST_CHECK_ARG(ab->dloc_part && !ab->dcum_add && pl.code >= 0, "st_skinny_partial_attn_bwd: the attention job must be the two-part form (parts = 2, dloc_part, S kept, "
                  "no dcum_add) with A = %d splitting into halves that divide %d", t.A, AB_THREADS);
     t.dloc_part = ab->dloc_part;
-    const size_t lds = ab_lds_bytes(t, true, 2);
-    const int kw16 = getenv("ST_PART_KW16") ? 1 : 0;
+    const size_t lds = pl.lds;
+    const int kw16 = pl.kernel == AB_K_PARTIAL_KW16 ? 1 : 0;
     auto kern = kw16 ? pk_part_ab_kernel<16, 2, AB_LBLK_MAX, 2> : pk_part_ab_kernel<8, 2, AB_LBLK_MAX, 2>;      // (TRIP = 3 / 4, i.e. deeper groups in flight: 14.4 / 13.8 us against 12.8)
     const int trip = 2 + kw16;
     static size_t lds_set[5] = {0, 0, 0, 0, 0};
-    if (lds > 32 * 1024 && lds > lds_set[trip]) {
+    if (pl.opt_in && lds > lds_set[trip]) {
         ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set[trip] = lds;
     }

@@ -384,6 +384,7 @@ class Decoder(nn.Module):
         self.bwd_dxq_splits = int(os.environ.get('ST_DXQ_SPLITS', '4'))   # ... and the query cell's product likewise (0 = whole)
         self.bwd_dxd_splits = int(os.environ.get('ST_DXD_SPLITS', '2'))   # ... with the decoder cell's product of that launch K-split into slabs (0 = whole)
         self.bwd_attn_parts = int(os.environ.get('ST_ATTN_PARTS', '2'))          # ... that attention backward as 2 workgroups per utterance over halves of the attention dims (1 = whole)
+        self._last_bwd_forms = None      # st_decoder_bwd_forms word of the last backward (which loop form ran)
         self.fwd_pair_cells = True       # teacher-forced forward: the decoder cell of step t and the query cell of step t+1 in one launch
         self.attn_rng_one_launch = True   # long texts: query projection + fin part over position ranges + combine in one launch
 
