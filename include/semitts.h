@@ -629,6 +629,15 @@ int st_gru_seq_fwd(const float* gi_fwd, const float* gi_bwd, const float* w_hh_f
 int st_gru_seq_bwd(const float* dout, int ldd, const float* out, int ldo, const float* tape,
                    const float* w_hh_fwd, const float* w_hh_bwd, float* dgi_fwd, float* dgi_bwd,
                    float* dgh_fwd, float* dgh_bwd, int B, int T, int H, int ndir, void* stream);
+/* The kernel st_gru_seq_fwd (backward = 0) or st_gru_seq_bwd (backward = 1) launches for hidden size H, from H alone: ST_GRU_TRI
+ * (H <= 84: three lanes per hidden unit split the reduction), ST_GRU_QUAD (forward, H <= 128: one lane per gate row, four lanes per unit),
+ * ST_GRU_REG32 (backward, H <= 128: W_hh columns in registers, padded to 128), ST_GRU_GENERAL (H <= 341: W_hh read from memory each
+ * step) -- or -1: no kernel takes H (H < 1, or 3H > 1024), and both calls refuse it. */
+#define ST_GRU_TRI 0
+#define ST_GRU_QUAD 1
+#define ST_GRU_REG32 2
+#define ST_GRU_GENERAL 3
+int st_gru_seq_variant(int H, int backward);
 
 /* ------------------------------------------------------------------ VQ codebook */
 /* table(v, :) = cat[learnable(v, 0:Dl), attr(v,:) W_attr^T + b_attr]      (V, Dl + Da)

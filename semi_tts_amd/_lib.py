@@ -199,6 +199,7 @@ SIGNATURES = {
     'st_lstm_seq_bwd': [P, I, I, P, P, P, P, P, I, I, I, I, P],
     'st_gru_seq_fwd': [P, P, P, P, P, P, P, I, P, I, I, I, I, P],
     'st_gru_seq_bwd': [P, I, P, I, P, P, P, P, P, P, P, I, I, I, I, P],
+    'st_gru_seq_variant': [I, I],
     'st_vq_build_table': [P, I, P, I, P, P, I, P, I, P],
     'st_gather_rows': [P, P, P, I, I, I, P],
     'st_vq_l2_fwd': [P, P, P, P, P, P, P, I, I, I, P],

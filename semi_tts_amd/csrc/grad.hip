@@ -931,7 +931,8 @@ __global__ __launch_bounds__(256) void highway_fwd_kernel(const float* H, const 
 
 // ---- the K BatchNorm1d layers of a conv bank, one launch per phase (see st_bn_bank_fwd) ----------------------------------------------------
 // The per-layer kernels above with a segment index in the grid: same chunking of the rows per segment, same merge order, so a bank of one
-// segment gives what st_bn_stats / st_bn_norm_fwd / st_bn_bwd give.  part: [seg][chunk][2][N].
+// segment gives bit for bit the statistics, output and sums of st_bn_stats / st_bn_norm_fwd / st_bn_bwd.  Its dx agrees to rounding: the two
+// apply kernels compile to different multiply-add sequences.  part: [seg][chunk][2][N].
 struct BnBank { st_bn_bank_seg s[ST_BN_BANK_MAX]; int nseg, Bn, N; };
 
 __global__ __launch_bounds__(256) void bnb_stats_chunk_kernel(const BnBank a, float* part, int max_chunks) {

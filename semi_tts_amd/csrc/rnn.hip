@@ -761,6 +761,19 @@ __global__ __launch_bounds__(256) void lstm_bwd_pw_pair_kernel(const LstmPwArgs 
 extern "C" int st_gru_debug_stamps(unsigned long long* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(gru_stamps), sizeof(gru_stamps)); }
 #endif
 
+// The kernel a GRU layer of hidden size H runs on, forward or backward (one workgroup per (utterance, direction) either way):
+//   forward:  H <= 84 gru_seq_tri_kernel, H <= 128 gru_seq_quad_kernel<32>, else gru_seq_kernel<false>;
+//   backward: H <= GB_LD = 84 gru_seq_bwd_tri_kernel, H <= 128 gru_seq_bwd_kernel<true, 32>, else gru_seq_bwd_kernel<false>;
+// -1 when no kernel takes H (H < 1, or 3H > 1024: one thread per gate row).
+static int gru_plan(int H, bool backward) {
+    if (H < 1 || 3 * H > 1024) return -1;
+    if (H <= (backward ? GB_LD : 3 * GRU_SL)) return ST_GRU_TRI;
+    if (H <= GRU_HMAX) return backward ? ST_GRU_REG32 : ST_GRU_QUAD;
+    return ST_GRU_GENERAL;
+}
+
+extern "C" int st_gru_seq_variant(int H, int backward) { return gru_plan(H, backward != 0); }
+
 extern "C" int st_gru_seq_fwd(const float* gi_fwd, const float* gi_bwd, const float* w_hh_fwd, const float* w_hh_bwd,
                               const float* b_hh_fwd, const float* b_hh_bwd, float* out, int ldo,
                               float* tape, int B, int T, int H, int ndir, void* stream) {
@@ -776,11 +789,15 @@ extern "C" int st_gru_seq_fwd(const float* gi_fwd, const float* gi_bwd, const fl
     const int threads = ((3 * H + 63) / 64) * 64;
     const size_t lds = (size_t)(((H + 3) & ~3) + 3 * H) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (H <= GRU_HMAX) {
+    switch (gru_plan(H, false)) {
+    case ST_GRU_TRI: hipLaunchKernelGGL(gru_seq_tri_kernel, dim3(B, ndir), dim3(256), 0, st, a); break;
+    case ST_GRU_QUAD: {
         const int qthreads = ((4 * H + 63) / 64) * 64;             // <= 512
-        if (H <= 3 * GRU_SL && H <= 84) hipLaunchKernelGGL(gru_seq_tri_kernel, dim3(B, ndir), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(gru_seq_quad_kernel<32>, dim3(B, ndir), dim3(qthreads), (size_t)2 * 128 * sizeof(float), st, a);
-    } else hipLaunchKernelGGL((gru_seq_kernel<false>), dim3(B, ndir), dim3(threads), lds, st, a);
+        hipLaunchKernelGGL(gru_seq_quad_kernel<32>, dim3(B, ndir), dim3(qthreads), (size_t)2 * 128 * sizeof(float), st, a);
+        break;
+    }
+    default: hipLaunchKernelGGL((gru_seq_kernel<false>), dim3(B, ndir), dim3(threads), lds, st, a);
+    }
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -1241,13 +1258,15 @@ extern "C" int st_gru_seq_bwd(const float* dout, int ldd, const float* out, int 
     a.w_hh[0] = w_hh_fwd; a.w_hh[1] = w_hh_bwd; a.dgi[0] = dgi_fwd; a.dgi[1] = dgi_bwd; a.dgh[0] = dgh_fwd; a.dgh[1] = dgh_bwd;
     a.B = B; a.T = T; a.H = H;
     const int threads = ((3 * H + 63) / 64) * 64;
-    const int hpad = H <= 80 ? 80 : (H <= GRU_HMAX ? GRU_HMAX : ((H + 3) & ~3));      // the REG forms pad the dgh rows to 4 KQ entries
+    const int plan = gru_plan(H, true);
+    const int hpad = plan == ST_GRU_REG32 ? GRU_HMAX : ((H + 3) & ~3);      // the REG form pads the dgh rows to 4 KQ = 128 entries
     const size_t lds = (size_t)(3 * hpad + 3 * H + H) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (H <= GB_LD) hipLaunchKernelGGL(gru_seq_bwd_tri_kernel, dim3(B, ndir), dim3(256), 0, st, a);
-    else if (H <= 80) hipLaunchKernelGGL((gru_seq_bwd_kernel<true, 20>), dim3(B, ndir), dim3(threads), lds, st, a);
-    else if (H <= GRU_HMAX) hipLaunchKernelGGL((gru_seq_bwd_kernel<true, 32>), dim3(B, ndir), dim3(threads), lds, st, a);
-    else hipLaunchKernelGGL((gru_seq_bwd_kernel<false>), dim3(B, ndir), dim3(threads), lds, st, a);
+    switch (plan) {
+    case ST_GRU_TRI: hipLaunchKernelGGL(gru_seq_bwd_tri_kernel, dim3(B, ndir), dim3(256), 0, st, a); break;
+    case ST_GRU_REG32: hipLaunchKernelGGL((gru_seq_bwd_kernel<true, 32>), dim3(B, ndir), dim3(threads), lds, st, a); break;
+    default: hipLaunchKernelGGL((gru_seq_bwd_kernel<false>), dim3(B, ndir), dim3(threads), lds, st, a);
+    }
     ST_LAUNCH_CHECK();
     return 0;
 }
