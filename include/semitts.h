@@ -224,18 +224,9 @@ typedef struct st_attn_pre_job {
     int L, A, F, K;
     int parts;      /* workgroups per utterance (ranges of positions): 1, 2 or 4 */
     float* cf_out;  /* optional (B, L, F): the location features of the step, kept for the backward pass */
-    /* optional (p2_packed_w != NULL): ONE MORE packed linear inside the same launch whose operand is the product's THIRD range
-     * (act2 / mask2 applied) -- prenet layer 2 of the next decoder input behind proj (+) gate (+) prenet layer 1 (src/module.py:192,
-     * :337-339).  The third range also leaves as 8-byte {value, tag = p2_epoch} granules, (B, p2_K) words in p2_gran (zeroed by the
-     * caller before the first use of an epoch sequence), and (p2_N / 16) x batch-tile workgroups behind the attention ones wait for
-     * them.  p2_K = N - n_split2, a multiple of 16, at most 512; every workgroup of the launch must be resident at once (checked
-     * against the device's compute units).  A wait that does not complete sets bit 0 of *p2_status and leaves NaN. */
-    const float* p2_packed_w; int p2_K, p2_N, p2_act; const float* p2_mask; int p2_ldmask;
-    st_t16_view p2_dst;
-    unsigned long long* p2_gran; unsigned p2_epoch; unsigned* p2_status;
     /* optional: a K-split partial product (st_partial_product_job, below) on the compute units the launch leaves idle -- teacher-forced
      * training hosts the tail of the decoder cell's gate reduction beside the query projection + attention pre part (B = 17..32; the
-     * launch then has N / 16 x 2 + B x parts + job->N / 32 workgroups).  Not together with p2 */
+     * launch then has N / 16 x 2 + B x parts + job->N / 32 workgroups) */
     const struct st_partial_product_job* part;
 } st_attn_pre_job;
 int st_skinny_linear_packed_attnpre_fwd(const float* packed_w, const st_t16_view* x, int K,
@@ -795,10 +786,6 @@ typedef struct st_decoder_io {
                                         * step t+1 share one launch (st_lstm_cell_packed_pair_fwd) -- neither needs the other's output */
     float* pre_nat_tape;               /* optional (steps, 2, B, P): with prenet_norm, the Linear outputs of both prenet layers of every
                                         * own-output feedback are kept here (instead of pre_nat) for the backward */
-    unsigned long long* pre1_granules; /* optional (B, P) 64-bit words: with fuse_pre0 and the split attention step, prenet layer 2 of the next
-                                        * input runs INSIDE the proj (+) gate (+) prenet-layer-1 launch (st_attn_pre_job.p2_*), its operand
-                                        * handed over as granules -- one launch less per free-running decode step.  Zeroed by the callee per
-                                        * forward; time-outs go to handoff_status */
     float* gate_part;                  /* optional (B, 4 D) scratch: in the one-launch pq + fin form (pq_granules) with 16 < B <= 32 the decoder
                                         * cell's gate products over operands that are known BEFORE the attention runs -- the tail of the cell's
                                         * reduction [ctx | AdaIN(h_q(t)) | h_d(t-1)] from column gate_part_k on -- ride beside the pq / fin launch
@@ -819,6 +806,15 @@ size_t st_decoder_tape_floats(const st_decoder_dims* d, int which);
 int st_decoder_pack(const st_decoder_weights* w, const st_decoder_dims* d, float* packed, void* stream);
 int st_decoder_forward(const st_decoder_weights* w, const st_decoder_dims* d, const st_decoder_io* io,
                        void* stream);
+/* which forms st_decoder_forward will take for these dimensions and buffers, on a device with `cus` compute units that holds
+ * `rng_capacity` workgroups of the one-launch range form at once (<= 0: this device's, which is what st_decoder_forward uses).  Host
+ * arithmetic only.  Bits 0..2 the attention step (with the query projection): 0 whole step in one launch, 1 pre part elsewhere + fin
+ * launch, 2 fin over position ranges + combine launch, 3 pq + fin as one launch, 4 pq + fin over position ranges + combine as one
+ * launch; bits 4..5 where the decoder cell's partial gate product (gate_part) runs: 0 nowhere, 1 a launch of its own, 2 beside pq + fin,
+ * 3 beside pq + attention pre (step 0: its own launch); bit 8 pure teacher forcing, bit 9 deferred projection, bit 10 the attention pre
+ * part inside the pq launch, bit 11 paired cells; bits 12..15 the fin part's workgroups per utterance; bits 16..27 the k-blocks the
+ * cell keeps with a partial product (0 without one).  -1 for a null pointer. */
+int st_decoder_fwd_forms(const st_decoder_dims* d, const st_decoder_io* io, int cus, int rng_capacity);
 
 /* ------------------------------------------------------------------ decoder backward (training, teacher forcing)
  * ref: what torch autograd derives for Decoder.forward / decode_one_step, src/module.py:184-288 */

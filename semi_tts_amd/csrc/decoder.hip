@@ -173,6 +173,106 @@ extern "C" size_t st_decoder_tape_floats(const st_decoder_dims* d, int which) {
     return which == 0 ? sv.q_floats : (which == 1 ? sv.d_floats : sv.o_floats);
 }
 
+namespace {
+
+// How the decode loop issues its steps, decided once per forward (st_decoder_fwd_forms reports it).  Host arithmetic only: no HIP call,
+// no device memory read; step_src is the one host array it looks into.  `cus` = the device's compute units, `rng_capacity` = the
+// workgroups of the one-launch range form (pk_attnrng_kernel) the device holds at once: the forms whose workgroups wait for each other
+// inside a launch need all of them resident.
+enum FwdAttn {          // steps 2 + 3: query projection and attention
+    ATTN_WHOLE,         //   pq launch, then the whole attention step
+    ATTN_PRE_FIN,       //   pq launch, then the fin part from S (the pre part ran in the proj launch of the step before, or in the pq launch)
+    ATTN_FIN_SPLIT,     //   pq launch, then the fin part over position ranges + a combine launch (long texts)
+    ATTN_PQ_FIN,        //   pq + fin part as one launch (pq handed over inside the launch as granules)
+    ATTN_PQ_RNG         //   pq + fin part over position ranges + combine as one launch (long texts)
+};
+enum FwdProd {          // where the decoder cell's partial gate product (io->gate_part) runs
+    PROD_NONE,          //   nowhere: the cell reduces its whole K
+    PROD_OWN,           //   in a launch of its own before the cell
+    PROD_PQ_FIN,        //   beside the pq + fin launch
+    PROD_PQ_PRE         //   beside the pq + attention-pre launch (step 0 has no pre part: a launch of its own there)
+};
+struct FwdForms {
+    bool pure_tf;       // every next input is a teacher frame for every row: the inputs of all steps are tiled before the loop
+    bool defer;         // no proj (+) gate launch per step: the caller computes mel / stop of all steps after the loop
+    bool pre_in_pq;     // the attention pre part of step t rides in the pq launch of step t (else in the proj launch of step t-1)
+    bool pair_cells;    // the decoder cell of step t and the query cell of step t+1 as one launch
+    FwdAttn attn;
+    FwdProd prod;
+    int fin_parts;      // workgroups per utterance of the fin part (ATTN_PRE_FIN, ATTN_PQ_FIN)
+    int pq_pre_parts;   // ... of the pre part inside the pq launch
+    int d_k0;           // k-blocks of the decoder cell's reduction that stay in the cell launch (with a partial product)
+};
+
+FwdForms fwd_forms(const st_decoder_dims* d, const st_decoder_io* io, int cus, int rng_capacity) {
+    FwdForms f;
+    const int B = d->B, L = d->L, E = d->E, Q = d->Q, D = d->D, A = d->A, BT = (B + 15) / 16;
+    // pure teacher forcing (every next input is teacher frame min(t, Tt-1), all rows have a teacher): the inputs of all
+    // steps are tiled into the tape up front, and with io->defer_proj the projection is left to the caller (one GEMM
+    // over all steps instead of one launch per step -- no step's input depends on an earlier output)
+    f.pure_tf = io->teacher_pre && io->Bt == B && io->Tt > 0;
+    for (int t = 0; t + 1 < io->steps && f.pure_tf; ++t) f.pure_tf = io->step_src[t] == (t < io->Tt ? t : io->Tt - 1);
+    f.defer = io->defer_proj != 0;
+    // teacher-forced training (deferred projection): [decoder cell of t | query cell of t+1] as one launch
+    f.pair_cells = f.defer && f.pure_tf && io->pair_cells;
+    // Attention in two parts (io->attn_s_buf set by the host): the location part of step t+1 ("pre": conv + W_l + processed
+    // memory -> S) only needs the attention weights of step t, so it rides as extra workgroups of a small launch that runs
+    // anyway -- the proj launch of step t when the loop has one, otherwise (deferred projection = teacher-forced training) the
+    // query-projection launch of step t+1 itself.  The attention launch then starts from S ("fin").
+    // Measured and removed (DESIGN.md section 3): early LSTM inputs on a second stream, as side jobs of the small launches, and as
+    // distributed side jobs over four launches of the step -- all slower than the plain chain of dependent launches.
+    const bool split_attn = io->attn_s_buf != nullptr;
+    f.pre_in_pq = split_attn && f.defer;
+    const int fp_req = io->attn_fin_parts;
+    f.fin_parts = (fp_req == 2 || fp_req == 4 || fp_req == 8) && E % (4 * fp_req) == 0 ? fp_req : 1;
+    // long texts: the fin part split over position ranges + a combine launch (see at_split_kernel) ...
+    const int sp = io->attn_split_parts;
+    const bool fin_split = split_attn && io->attn_split_ws && sp >= 2 && sp <= 64 && A % 4 == 0 && A <= 256 && E % 4 == 0 &&
+                           E / 4 <= 512 && 512 % (E / 4) == 0 && (L + sp - 1) / sp <= 512;
+    // ... or, when the device holds all its workgroups at once, query projection + fin part over position ranges + combine as ONE launch
+    const bool fin_rng = fin_split && !f.pre_in_pq && io->pq_granules && io->attn_xchg && sp <= 8 && A % 16 == 0 && E % (4 * sp) == 0 &&
+                         E / sp <= 256 && (sp - 1) * ((L + sp - 1) / sp) < L && (A / 16) * BT + B * sp <= rng_capacity;
+    // query projection + attention fin part as one launch with an in-launch hand-off of pq (st_query_attn_fin_fwd): needs the split
+    // attention step and every workgroup of the launch resident at once
+    const bool fuse_pq_fin = !fin_split && split_attn && !f.pre_in_pq && io->pq_granules && A % 16 == 0 && A <= 256 && E % 4 == 0 &&
+                             (A / 16) * BT + B * f.fin_parts <= cus;
+    f.attn = !split_attn ? ATTN_WHOLE : fin_rng ? ATTN_PQ_RNG : fin_split ? ATTN_FIN_SPLIT : fuse_pq_fin ? ATTN_PQ_FIN : ATTN_PRE_FIN;
+    // io->gate_part: the decoder cell's gate products over [AdaIN(h_q(t)) | h_d(t-1)] -- known before the attention of step t runs -- ride
+    // beside the pq / fin launch; the cell launch reduces the context columns and adds the slab.  Measured (round 6, two boxes, A/B in
+    // one process): 2.71 -> 2.79 and 2.78 -> 2.84 M mel-frames/s.  The same for the query cell, or the two halves at two sites, LOSE
+    // (DESIGN.md section 3.5): a hosted product costs ~7 us + 3 us per 1024 columns whatever its host's length.
+    // (the other forms of the attention step issue the partial product as a launch of its own: same arithmetic bit for bit, so a starved
+    // hand-off that degrades to the two-launch form changes nothing but the speed)
+    // Teacher-forced training (deferred projection) has the same split: there the product rides beside the query projection + attention pre
+    // part of the step (its operands come from the paired cell launch of the step before), the paired launch adds the slab.
+    const bool split_d = io->gate_part && (!f.defer || f.pre_in_pq) && B > 16 && B <= 32 && D % 16 == 0 && (D / 4) % 2 == 0 &&
+                         E % 16 == 0 && Q % 16 == 0 && st_aligned16(io->gate_part);
+    // (two attention-pre workgroups per utterance beside the product: with four, 16 + 128 + 128 workgroups would not fit the device in one round)
+    const int pre_parts_split = io->attn_pre_parts > 2 ? 2 : io->attn_pre_parts;
+    const bool split_pre = split_d && f.pre_in_pq && A <= 16 * 128 &&
+                           ((A + 15) / 16) * BT + B * (pre_parts_split > 1 ? pre_parts_split : 1) + (4 * D) / 32 <= cus;
+    f.pq_pre_parts = split_pre ? pre_parts_split : io->attn_pre_parts;
+    if (!split_d) f.prod = PROD_NONE;
+    else if (split_pre) f.prod = PROD_PQ_PRE;
+    else if (fuse_pq_fin && (A / 16) * BT + B * f.fin_parts + (4 * D) / 32 <= cus) f.prod = PROD_PQ_FIN;
+    else f.prod = PROD_OWN;
+    // ... how much of it: measured at C2 (hosted 512 / 768 / 1024 / 1280 / 1536 / 2048 columns: 2.78 / 2.83 / 2.88 / 2.89 / 2.86 / 2.81 M
+    // mel-frames/s, whole rounds of 16 k-blocks for the 8 waves x 2 only -- 1088 ... 1408 in steps of 64 all lose to 1280): the cell keeps half.
+    f.d_k0 = (io->gate_part_k ? io->gate_part_k : st_decoder_gate_split_k(d)) / 16;
+    return f;
+}
+
+}  // namespace
+
+int pk_attnrng_capacity();      // (skinny_packed.hip)
+
+extern "C" int st_decoder_fwd_forms(const st_decoder_dims* d, const st_decoder_io* io, int cus, int rng_capacity) {
+    if (!d || !io || (io->steps > 1 && !io->step_src)) return -1;
+    const FwdForms f = fwd_forms(d, io, cus > 0 ? cus : st_device_cus(), rng_capacity > 0 ? rng_capacity : pk_attnrng_capacity());
+    return (int)f.attn | ((int)f.prod << 4) | (f.pure_tf ? 1 << 8 : 0) | (f.defer ? 1 << 9 : 0) | (f.pre_in_pq ? 1 << 10 : 0) |
+           (f.pair_cells ? 1 << 11 : 0) | (f.fin_parts << 12) | ((f.prod != PROD_NONE ? f.d_k0 & 0xfff : 0) << 16);
+}
+
 static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_dims* d, const st_decoder_io* io, void* stream);
 
 static stlg::Cache g_fwd_graphs;
@@ -229,20 +329,29 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         ST_CHECK_ARG(src != -2 || io->teacher_mean, "st_decoder_forward: step_src[%d]=-2 without teacher_mean", t);
         ST_CHECK_ARG(src == -1 || (io->Bt > 0 && io->Bt <= B), "st_decoder_forward: Bt=%d invalid", io->Bt);
     }
-    // pure teacher forcing (every next input is teacher frame min(t, Tt-1), all rows have a teacher): the inputs of all
-    // steps are tiled into the tape up front, and with io->defer_proj the projection is left to the caller (one GEMM
-    // over all steps instead of one launch per step -- no step's input depends on an earlier output)
-    bool pure_tf = io->teacher_pre && io->Bt == B && io->Tt > 0;
-    for (int t = 0; t + 1 < steps && pure_tf; ++t) pure_tf = io->step_src[t] == (t < io->Tt ? t : io->Tt - 1);
-    const bool defer = io->defer_proj != 0;
-    ST_CHECK_ARG(!defer || (pure_tf && !d->fuse_pre0), "st_decoder_forward: defer_proj needs pure teacher forcing");
+    const StepViews sv = step_views(d);
+    ST_CHECK_ARG(io->gate_part_k == 0 || !io->gate_part || (io->gate_part_k % 16 == 0 && io->gate_part_k >= 16 * sv.d_ha && io->gate_part_k < 16 * sv.d_kbs),
+                 "st_decoder_forward: gate_part_k = %d must be a multiple of 16 in [%d, %d)", io->gate_part_k, 16 * sv.d_ha, 16 * sv.d_kbs);
+    FwdForms f = fwd_forms(d, io, st_device_cus(), pk_attnrng_capacity());
+    ST_CHECK_ARG(!f.defer || (f.pure_tf && !d->fuse_pre0), "st_decoder_forward: defer_proj needs pure teacher forcing");
+    // Ablation (timing experiments only: tools/gpu_ablate.sh builds a SEPARATE library with -DST_ABLATE and times the loop with the
+    // launches of the bit mask ST_SKIP left out; the outputs are garbage then).  Bits: 0 query cell, 1 query projection, 2 attention,
+    // 3 decoder cell (paired or not), 4 proj (+) gate, 5 own-output prenet, 6 the attention pre part inside the proj launch, 7 the proj
+    // launch over a quarter of its reduction.  Bit 1 or bit 2 skips a merged pq + fin launch.  A skipped launch takes the partial product
+    // it hosts with it, and so does bit 3: the cell then reduces its whole K.
+#ifdef ST_ABLATE
+    const int skip = getenv("ST_SKIP") ? atoi(getenv("ST_SKIP")) : 0;
+    if ((skip & 8) || (f.prod == PROD_PQ_FIN && (skip & 6)) || (f.prod == PROD_PQ_PRE && (skip & 2))) f.prod = PROD_NONE;
+#define ST_SKIPPED(bit) (skip & (1 << (bit)))
+#else
+#define ST_SKIPPED(bit) 0
+#endif
     hipStream_t st = (hipStream_t)stream;
     const PackedLayout pl = packed_layout(d);
-    const StepViews sv = step_views(d);
     const size_t BQ = (size_t)B * Q, BD = (size_t)B * D, BL = (size_t)B * L;
     // The tiled tapes are handed in zero-filled (torch.zeros): slot 0 of xq / the h_d part of xd slot 0
     // are the initial zero state (src/module.py:290-303) and dec_in_0 = prenet(go frame) = 0 (:161,:183).
-    // (one launch for all of them, together with the hand-off words further down: eight memset nodes were 25 us of every forward)
+    // (one launch for all of them, together with the hand-off words: eight memset nodes were 25 us of every forward)
     ZeroArgs za;
     memset(&za, 0, sizeof(za));
     auto zero = [&](void* p, size_t bytes) { za.p[za.n] = (float*)p; za.floats[za.n] = bytes / sizeof(float); ++za.n; };
@@ -253,47 +362,11 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
     zero(io->xq_tape, sv.q_floats * sizeof(float));
     zero(io->xd_tape, sv.d_floats * sizeof(float));
     if (io->attn_loc_tape) zero(io->attn_loc_tape, BL * d->F * sizeof(float));      // (slot 0: no step writes it -- there is no history yet)
-
-    const size_t ldmel = (size_t)steps * in_dim;
-    const int ldal = steps * L;
-    const int Kq = 16 * sv.q_kbs, Kd = 16 * sv.d_kbs, Ko = 16 * sv.o_kbs;
-    int rc = 0;
-    // Attention in two parts (io->attn_s_buf set by the host): the location part of step t+1 ("pre": conv + W_l + processed
-    // memory -> S) only needs the attention weights of step t, so it rides as extra workgroups of a small launch that runs
-    // anyway -- the proj launch of step t when the loop has one, otherwise (deferred projection = teacher-forced training) the
-    // query-projection launch of step t+1 itself.  The attention launch then starts from S ("fin").
-    // Measured and removed (DESIGN.md section 3): early LSTM inputs on a second stream, as side jobs of the small launches, and as
-    // distributed side jobs over four launches of the step -- all slower than the plain chain of dependent launches.
-    const bool split_attn = io->attn_s_buf != nullptr;
-    const bool pre_in_pq = split_attn && defer;
-    const int fp_req = io->attn_fin_parts;
-    const int fin_parts = (fp_req == 2 || fp_req == 4 || fp_req == 8) && E % (4 * fp_req) == 0 ? fp_req : 1;
-#ifdef ST_ABLATE   // timing experiments only (tools/gpu_ablate.sh builds a SEPARATE library with this macro): skip launches by bit mask
-    const int skip = getenv("ST_SKIP") ? atoi(getenv("ST_SKIP")) : 0;
-#define ST_SKIPPED(bit) (skip & (1 << (bit)))
-#else
-#define ST_SKIPPED(bit) 0
-#endif
-    // query projection + attention fin part as one launch with an in-launch hand-off of pq (st_query_attn_fin_fwd): needs the split
-    // attention step, every workgroup of the launch resident at once, and the granule words zeroed before the first step (a memset
-    // node when the loop is captured: a replay must not see the tags of the previous one)
-    // long texts: the fin part split over position ranges + a combine launch (see at_split_kernel)
+    // the granule words of the in-launch hand-offs, zeroed before the first step (a memset node when the loop is captured: a replay must
+    // not see the tags of the previous one)
     const int sp_parts = io->attn_split_parts;
-    const bool fin_split = split_attn && io->attn_split_ws && sp_parts >= 2 && sp_parts <= 64 && A % 4 == 0 && A <= 256 && E % 4 == 0 &&
-                           E / 4 <= 512 && 512 % (E / 4) == 0 && (L + sp_parts - 1) / sp_parts <= 512;
-    // ... or, when the device holds all its workgroups at once, query projection + fin part over position ranges + combine as ONE launch
-    const bool fin_rng = fin_split && !pre_in_pq && io->pq_granules && io->attn_xchg && sp_parts <= 8 && A % 16 == 0 && E % (4 * sp_parts) == 0 &&
-                         E / sp_parts <= 256 && (sp_parts - 1) * ((L + sp_parts - 1) / sp_parts) < L && st_query_attn_rng_fits(B, A, sp_parts);
-    const bool fuse_pq_fin = !fin_split && split_attn && !pre_in_pq && io->pq_granules && A % 16 == 0 && A <= 256 && E % 4 == 0 &&
-                             (A / 16) * ((B + 15) / 16) + B * fin_parts <= st_device_cus();
-    if (fin_rng || fuse_pq_fin) zero(io->pq_granules, (size_t)B * A * sizeof(unsigned long long));
-    // prenet layer 2 of the next input inside the proj (+) gate (+) prenet-layer-1 launch (st_attn_pre_job.p2_*): free-running steps with
-    // the folded layer 1, the split attention step (that launch exists), every workgroup of the launch resident at once
-    const int pre_parts_eff = (io->attn_pre_parts >= 2 && io->attn_pre_parts <= 64 && (io->attn_pre_parts & (io->attn_pre_parts - 1)) == 0) ? io->attn_pre_parts : 1;
-    const bool fuse_p2 = d->fuse_pre0 && split_attn && !defer && io->pre1_granules && P % 16 == 0 && P <= 512 &&
-                         ((in_dim + 1 + P + 15) / 16) * ((B + 15) / 16) + B * pre_parts_eff + (P / 16) * ((B + 15) / 16) <= st_device_cus();
-    if (fuse_p2) zero(io->pre1_granules, (size_t)B * P * sizeof(unsigned long long));
-    if (fin_rng) zero(io->attn_xchg, st_attn_rng_xchg_words(B, E, sp_parts) * sizeof(unsigned long long));
+    if (f.attn == ATTN_PQ_FIN || f.attn == ATTN_PQ_RNG) zero(io->pq_granules, (size_t)B * A * sizeof(unsigned long long));
+    if (f.attn == ATTN_PQ_RNG) zero(io->attn_xchg, st_attn_rng_xchg_words(B, E, sp_parts) * sizeof(unsigned long long));
     {
         size_t most = 0;
         for (int i = 0; i < za.n; ++i) most = za.floats[i] > most ? za.floats[i] : most;
@@ -307,7 +380,7 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         int rc0 = st_tile_rows(io->dec_in0, P, &xq0, B, P, stream);
         if (rc0) return rc0;
     }
-    if (pure_tf && steps > 1) {
+    if (f.pure_tf && steps > 1) {
         const size_t total = (size_t)(steps - 1) * B * P;
         size_t blocks = (total + 255) / 256;
         if (blocks > 4096) blocks = 4096;
@@ -315,38 +388,21 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
                            sv.q_floats, sv.q_kbs, steps, B, P);
         ST_LAUNCH_CHECK();
     }
-    // teacher-forced training (deferred projection): [decoder cell of t | query cell of t+1] as one launch
-    const bool pair_cells = defer && pure_tf && io->pair_cells;
-    // io->gate_part: the decoder cell's gate products over [AdaIN(h_q(t)) | h_d(t-1)] -- known before the attention of step t runs -- ride
-    // beside the pq / fin launch; the cell launch reduces the context columns and adds the slab.  Measured (round 6, two boxes, A/B in
-    // one process): 2.71 -> 2.79 and 2.78 -> 2.84 M mel-frames/s.  The same for the query cell, or the two halves at two sites, LOSE
-    // (DESIGN.md section 3.5): a hosted product costs ~7 us + 3 us per 1024 columns whatever its host's length.
-    // (the other forms of the attention step issue the partial product as a launch of its own: same arithmetic bit for bit, so a starved
-    // hand-off that degrades to the two-launch form changes nothing but the speed)
-    // Teacher-forced training (deferred projection) has the same split: there the product rides beside the query projection + attention pre
-    // part of the step (pre_in_pq; its operands come from the paired cell launch of the step before), the paired launch adds the slab.
-    const bool split_d = io->gate_part && (!defer || pre_in_pq) && B > 16 && B <= 32 && D % 16 == 0 && (D / 4) % 2 == 0 &&
-                         E % 16 == 0 && Q % 16 == 0 && st_aligned16(io->gate_part);
-    const bool split_hosted = split_d && fuse_pq_fin && (A / 16) * ((B + 15) / 16) + B * fin_parts + (4 * D) / 32 <= st_device_cus();
-    // (two attention-pre workgroups per utterance then: with four, 16 + 128 + 128 workgroups would not fit the device in one round)
-    const int pre_parts_split = io->attn_pre_parts > 2 ? 2 : io->attn_pre_parts;
-    const bool split_pre = split_d && pre_in_pq && A <= 16 * 128 &&
-                           ((A + 15) / 16) * ((B + 15) / 16) + B * (pre_parts_split > 1 ? pre_parts_split : 1) + (4 * D) / 32 <= st_device_cus();
-    st_partial_product_job pj_d;
+
+    const size_t ldmel = (size_t)steps * in_dim;
+    const int ldal = steps * L;
+    const int Kq = 16 * sv.q_kbs, Kd = 16 * sv.d_kbs, Ko = 16 * sv.o_kbs;
+    st_partial_product_job pj_d;      // the tail of the decoder cell's gate product (f.prod), wherever it runs
     memset(&pj_d, 0, sizeof(pj_d));
-    // ... how much of it: measured at C2 (hosted 512 / 768 / 1024 / 1280 / 1536 / 2048 columns: 2.78 / 2.83 / 2.88 / 2.89 / 2.86 / 2.81 M
-    // mel-frames/s, whole rounds of 16 k-blocks for the 8 waves x 2 only -- 1088 ... 1408 in steps of 64 all lose to 1280): the cell keeps half.
-    ST_CHECK_ARG(io->gate_part_k == 0 || !io->gate_part || (io->gate_part_k % 16 == 0 && io->gate_part_k >= 16 * sv.d_ha && io->gate_part_k < 16 * sv.d_kbs),
-                 "st_decoder_forward: gate_part_k = %d must be a multiple of 16 in [%d, %d)", io->gate_part_k, 16 * sv.d_ha, 16 * sv.d_kbs);
-    const int d_k0 = (io->gate_part_k ? io->gate_part_k : st_decoder_gate_split_k(d)) / 16;
-    pj_d.packed_w = io->packed + pl.d; pj_d.w_kbs = sv.d_kbs; pj_d.kb0 = d_k0; pj_d.KB = sv.d_kbs - d_k0; pj_d.N = 4 * D; pj_d.part = io->gate_part;
+    pj_d.packed_w = io->packed + pl.d; pj_d.w_kbs = sv.d_kbs; pj_d.kb0 = f.d_k0; pj_d.KB = sv.d_kbs - f.d_k0; pj_d.N = 4 * D; pj_d.part = io->gate_part;
+    int rc = 0;
     for (int t = 0; t < steps; ++t) {
         float* xq = io->xq_tape + (size_t)t * sv.q_floats;
         float* xq_next = io->xq_tape + (size_t)(t + 1) * sv.q_floats;
         float* xd = io->xd_tape + (size_t)t * sv.d_floats;
         float* xd_next = io->xd_tape + (size_t)(t + 1) * sv.d_floats;
         float* xo = io->xo_tape + (size_t)t * sv.o_floats;
-        bool prod_done = false;          // the hosted part of the decoder cell's gate product of this step has been issued
+        pj_d.x = st_t16_view{xd, sv.d_kbs, f.d_k0};
 
         // 1. query LSTM (+ AdaIN of the new hidden state)                ref: :227-231, :267-269
         //    h_q_t -> xq_{t+1}[h part] (next step's recurrent input, also the query projection's input)
@@ -355,166 +411,159 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         st_t16_view hq_dst = {xq_next, sv.q_kbs, sv.q_h};
         st_t16_view ha_dst = {xd, sv.d_kbs, sv.d_ha};
         // (pair_cells: the query cell of step t > 0 ran beside the decoder cell of step t-1, see step 4)
-        if (!ST_SKIPPED(0) && !(pair_cells && t > 0))
-                            rc = st_lstm_cell_packed_fwd(io->packed + pl.q, &xq_v, Kq, w->q_b_ih, w->q_b_hh,
-                                     io->cq_tape + (size_t)t * BQ, Q, io->q_mask ? io->q_mask + (size_t)t * BQ : nullptr,
-                                     &hq_dst, nullptr, io->cq_tape + (size_t)(t + 1) * BQ, Q,
-                                     io->gates_q_tape ? io->gates_q_tape + (size_t)t * 4 * BQ : nullptr,
-                                     io->ada_std, io->ada_mean, &ha_dst, B, Q, stream);
-        if (rc) return rc;
+        if (!(f.pair_cells && t > 0) && !ST_SKIPPED(0)) {
+            rc = st_lstm_cell_packed_fwd(io->packed + pl.q, &xq_v, Kq, w->q_b_ih, w->q_b_hh,
+                                         io->cq_tape + (size_t)t * BQ, Q, io->q_mask ? io->q_mask + (size_t)t * BQ : nullptr,
+                                         &hq_dst, nullptr, io->cq_tape + (size_t)(t + 1) * BQ, Q,
+                                         io->gates_q_tape ? io->gates_q_tape + (size_t)t * 4 * BQ : nullptr,
+                                         io->ada_std, io->ada_mean, &ha_dst, B, Q, stream);
+            if (rc) return rc;
+        }
 
-        // 2. processed query                                             ref: :380
-        if (fuse_pq_fin || fin_rng) rc = 0;    // (rides with step 3)
-        else if (pre_in_pq && t > 0) {   // attention pre part of THIS step rides along (needs only the weights of step t-1)
-            st_attn_pre_job job = {io->pm, io->align_out + (size_t)(t - 1) * L, ldal, io->wcum_tape + (size_t)t * BL,
-                                   w->attn_loc_conv_w, w->attn_loc_lin_w, io->attn_s_buf + (size_t)t * io->attn_s_step_floats, L, A, d->F,
-                                   d->K, split_pre ? pre_parts_split : io->attn_pre_parts,
-                                   io->attn_loc_tape ? io->attn_loc_tape + (size_t)t * BL * d->F : nullptr};
-            if (split_pre) {             // ... and the tail of the decoder cell's gate product of this step
-                pj_d.x = st_t16_view{xd, sv.d_kbs, d_k0};
-                job.part = &pj_d;
-                prod_done = true;
-            }
-            rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), nullptr, ST_ACT_NONE, nullptr, 0,
-                                                     io->pq_buf, A, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, A,
-                                                     &job, stream);
-        } else if (!ST_SKIPPED(1))
-            rc = st_skinny_linear_packed_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), nullptr, ST_ACT_NONE, nullptr, 0,
-                                             io->pq_buf, A, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, A, stream);
-        if (rc) return rc;
+        // 2. processed query (the merged forms issue it with step 3)    ref: :380
+        if (f.attn != ATTN_PQ_FIN && f.attn != ATTN_PQ_RNG && !ST_SKIPPED(1)) {
+            if (f.pre_in_pq && t > 0) {   // attention pre part of THIS step rides along (needs only the weights of step t-1)
+                st_attn_pre_job job = {io->pm, io->align_out + (size_t)(t - 1) * L, ldal, io->wcum_tape + (size_t)t * BL,
+                                       w->attn_loc_conv_w, w->attn_loc_lin_w, io->attn_s_buf + (size_t)t * io->attn_s_step_floats, L, A, d->F,
+                                       d->K, f.pq_pre_parts, io->attn_loc_tape ? io->attn_loc_tape + (size_t)t * BL * d->F : nullptr};
+                if (f.prod == PROD_PQ_PRE) job.part = &pj_d;      // ... and the tail of the decoder cell's gate product of this step
+                rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), nullptr, ST_ACT_NONE, nullptr, 0,
+                                                         io->pq_buf, A, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, A,
+                                                         &job, stream);
+            } else
+                rc = st_skinny_linear_packed_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), nullptr, ST_ACT_NONE, nullptr, 0,
+                                                 io->pq_buf, A, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, A, stream);
+            if (rc) return rc;
+        }
 
         // 3. attention + state update                                    ref: :256-264, :371-407
         //    ctx_t -> xq_{t+1}[ctx part], xd_t[ctx part], xo_t[ctx part]
-        const float* w_prev = t == 0 ? io->zero_row : io->align_out + (size_t)(t - 1) * L;
         st_t16_view ctx_dst[3] = {{xq_next, sv.q_kbs, sv.q_ctx}, {xd, sv.d_kbs, 0}, {xo, sv.o_kbs, sv.o_ctx}};
-        if (fin_rng && !(ST_SKIPPED(1) || ST_SKIPPED(2))) {   // 2 + 3 + combine as one launch (long texts)
+        // S of this step: written by the pre part (step 0: no history yet, S = pm)
+        const float* s_t = t == 0 || f.attn == ATTN_WHOLE ? io->pm : io->attn_s_buf + (size_t)t * io->attn_s_step_floats;
+        auto fin_job = [&](int parts) {      // the attention of the merged launches
             st_attn_fin_job fj;
             memset(&fj, 0, sizeof(fj));
-            fj.s_buf = t == 0 ? io->pm : io->attn_s_buf + (size_t)t * io->attn_s_step_floats;
-            fj.memory = io->memory; fj.w_cum_prev = io->wcum_tape + (size_t)t * BL;
+            fj.s_buf = s_t; fj.memory = io->memory; fj.w_cum_prev = io->wcum_tape + (size_t)t * BL;
             fj.w_out = io->align_out + (size_t)t * L; fj.ld_wout = ldal; fj.w_cum_out = io->wcum_tape + (size_t)(t + 1) * BL; fj.v = w->attn_v;
             for (int c = 0; c < 3; ++c) fj.ctx_dst[c] = ctx_dst[c];
             fj.status = io->handoff_status;
-            fj.n_ctx_dst = 3; fj.parts = sp_parts; fj.L = L; fj.A = A; fj.E = E; fj.F = d->F; fj.K = d->K;
-            rc = st_query_attn_rng_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, io->attn_xchg, (unsigned)(t + 1), &fj, B, stream);
+            fj.n_ctx_dst = 3; fj.parts = parts; fj.L = L; fj.A = A; fj.E = E; fj.F = d->F; fj.K = d->K;
+            return fj;
+        };
+        switch (f.attn) {
+        case ATTN_WHOLE:
+            if (!ST_SKIPPED(2))
+                rc = st_attn_step_t16_fwd(io->pq_buf, io->pm, io->memory, t == 0 ? io->zero_row : io->align_out + (size_t)(t - 1) * L,
+                                          t == 0 ? L : ldal, io->wcum_tape + (size_t)t * BL, io->align_out + (size_t)t * L, ldal,
+                                          io->wcum_tape + (size_t)(t + 1) * BL,
+                                          w->attn_loc_conv_w, w->attn_loc_lin_w, w->attn_v, ctx_dst, 3, nullptr, 0,
+                                          B, L, A, E, d->F, d->K, stream);
+            break;
+        case ATTN_PRE_FIN:
+            if (!ST_SKIPPED(2))
+                rc = st_attn_fin_t16_fwd(io->pq_buf, s_t, io->memory, io->wcum_tape + (size_t)t * BL,
+                                         io->align_out + (size_t)t * L, ldal, io->wcum_tape + (size_t)(t + 1) * BL, w->attn_v,
+                                         ctx_dst, 3, nullptr, 0, f.fin_parts, B, L, A, E, d->F, d->K, stream);
+            break;
+        case ATTN_FIN_SPLIT:
+            if (!ST_SKIPPED(2))
+                rc = st_attn_fin_split_fwd(io->pq_buf, s_t, io->memory, io->wcum_tape + (size_t)t * BL, io->align_out + (size_t)t * L, ldal,
+                                           io->wcum_tape + (size_t)(t + 1) * BL, w->attn_v, ctx_dst, 3, nullptr, 0, io->attn_split_ws, sp_parts,
+                                           B, L, A, E, stream);
+            break;
+        case ATTN_PQ_FIN:       // 2 + 3 as one launch: the fin workgroups wait for pq inside the launch (granule hand-off)
+            if (!(ST_SKIPPED(1) || ST_SKIPPED(2))) {
+                const st_attn_fin_job fj = fin_job(f.fin_parts);
+                rc = f.prod == PROD_PQ_FIN
+                         ? st_query_attn_fin_part_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, (unsigned)(t + 1), &fj, B, &pj_d, stream)
+                         : st_query_attn_fin_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, (unsigned)(t + 1), &fj, B, stream);
+            }
+            break;
+        case ATTN_PQ_RNG:       // 2 + 3 + combine as one launch (long texts)
+            if (!(ST_SKIPPED(1) || ST_SKIPPED(2))) {
+                const st_attn_fin_job fj = fin_job(sp_parts);
+                rc = st_query_attn_rng_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, io->attn_xchg, (unsigned)(t + 1), &fj, B, stream);
+            }
+            break;
         }
-        else if (fin_rng) rc = 0;
-        else if (fin_split && !ST_SKIPPED(2))
-            rc = st_attn_fin_split_fwd(io->pq_buf, t == 0 ? io->pm : io->attn_s_buf + (size_t)t * io->attn_s_step_floats, io->memory,
-                                       io->wcum_tape + (size_t)t * BL, io->align_out + (size_t)t * L, ldal,
-                                       io->wcum_tape + (size_t)(t + 1) * BL, w->attn_v, ctx_dst, 3, nullptr, 0, io->attn_split_ws, sp_parts,
-                                       B, L, A, E, stream);
-        else if (fin_split) rc = 0;
-        else if (fuse_pq_fin && (ST_SKIPPED(1) || ST_SKIPPED(2))) rc = 0;
-        else if (fuse_pq_fin) {   // 2 + 3 as one launch: the fin workgroups wait for pq inside the launch (granule hand-off)
-            st_attn_fin_job fj;
-            memset(&fj, 0, sizeof(fj));
-            fj.s_buf = t == 0 ? io->pm : io->attn_s_buf + (size_t)t * io->attn_s_step_floats;
-            fj.memory = io->memory; fj.w_cum_prev = io->wcum_tape + (size_t)t * BL;
-            fj.w_out = io->align_out + (size_t)t * L; fj.ld_wout = ldal; fj.w_cum_out = io->wcum_tape + (size_t)(t + 1) * BL; fj.v = w->attn_v;
-            for (int c = 0; c < 3; ++c) fj.ctx_dst[c] = ctx_dst[c];
-            fj.status = io->handoff_status;
-            fj.n_ctx_dst = 3; fj.parts = fin_parts; fj.L = L; fj.A = A; fj.E = E; fj.F = d->F; fj.K = d->K;
-            if (split_hosted && !ST_SKIPPED(3)) {
-                pj_d.x = st_t16_view{xd, sv.d_kbs, d_k0};
-                prod_done = true;
-                rc = st_query_attn_fin_part_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, (unsigned)(t + 1), &fj, B, &pj_d, stream);
-            } else
-            rc = st_query_attn_fin_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, (unsigned)(t + 1), &fj, B, stream);
-        }
-        else if (ST_SKIPPED(2)) rc = 0;
-        else if (split_attn)     // S of this step was written by the pre part (step 0: no history yet, S = pm)
-            rc = st_attn_fin_t16_fwd(io->pq_buf, t == 0 ? io->pm : io->attn_s_buf + (size_t)t * io->attn_s_step_floats, io->memory,
-                                     io->wcum_tape + (size_t)t * BL,
-                                     io->align_out + (size_t)t * L, ldal, io->wcum_tape + (size_t)(t + 1) * BL, w->attn_v,
-                                     ctx_dst, 3, nullptr, 0, fin_parts, B, L, A, E, d->F, d->K, stream);
-        else
-            rc = st_attn_step_t16_fwd(io->pq_buf, io->pm, io->memory, w_prev, t == 0 ? L : ldal,
-                                      io->wcum_tape + (size_t)t * BL, io->align_out + (size_t)t * L, ldal,
-                                      io->wcum_tape + (size_t)(t + 1) * BL,
-                                      w->attn_loc_conv_w, w->attn_loc_lin_w, w->attn_v, ctx_dst, 3, nullptr, 0,
-                                      B, L, A, E, d->F, d->K, stream);
         if (rc) return rc;
 
         // 4. decoder LSTM: h_d_t -> xd_{t+1}[h part], xo_t[h part]        ref: :275-280
-        st_t16_view xd_v = {xd, sv.d_kbs, 0};
-        st_t16_view hd_dst0 = {xd_next, sv.d_kbs, sv.d_h};
-        st_t16_view hd_dst1 = {xo, sv.o_kbs, 0};
-        if (split_d && !prod_done && !ST_SKIPPED(3) && !(split_hosted && (ST_SKIPPED(1) || ST_SKIPPED(2)))) {       // (no launch of this step could host the product: one of its own, same arithmetic)
-            pj_d.x = st_t16_view{xd, sv.d_kbs, d_k0};
+        if (f.prod == PROD_OWN || (f.prod == PROD_PQ_PRE && t == 0)) {     // (no launch of this step hosts the product: one of its own, same arithmetic)
             rc = st_partial_product_fwd(&pj_d, B, stream);
             if (rc) return rc;
         }
-        if (pair_cells && t + 1 < steps) {
-            // teacher forcing: the query cell of step t+1 needs ctx_t, h_q_t and a teacher frame -- not h_d_t.  Both cells in one launch.
-            st_lstm_cell_packed_job jd, jq;
-            memset(&jd, 0, sizeof(jd)); memset(&jq, 0, sizeof(jq));
-            jd.packed_w = io->packed + pl.d; jd.x = xd_v; jd.K = Kd; jd.b_ih = w->d_b_ih; jd.b_hh = w->d_b_hh;
-            if (split_d) { jd.K = 16 * d_k0; jd.part = io->gate_part; jd.w_kbs = sv.d_kbs; }
-            jd.c_prev = io->cd_tape + (size_t)t * BD; jd.ldc_prev = D; jd.mask = io->d_mask ? io->d_mask + (size_t)t * BD : nullptr;
-            jd.h_dst0 = hd_dst0; jd.h_dst1 = hd_dst1; jd.c_out = io->cd_tape + (size_t)(t + 1) * BD; jd.ldc = D;
-            jd.gates_out = io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr;
-            jd.B = B; jd.H = D;
-            float* xq_next2 = io->xq_tape + (size_t)(t + 2) * sv.q_floats;
-            jq.packed_w = io->packed + pl.q; jq.x = st_t16_view{xq_next, sv.q_kbs, 0}; jq.K = Kq; jq.b_ih = w->q_b_ih; jq.b_hh = w->q_b_hh;
-            jq.c_prev = io->cq_tape + (size_t)(t + 1) * BQ; jq.ldc_prev = Q; jq.mask = io->q_mask ? io->q_mask + (size_t)(t + 1) * BQ : nullptr;
-            jq.h_dst0 = st_t16_view{xq_next2, sv.q_kbs, sv.q_h}; jq.c_out = io->cq_tape + (size_t)(t + 2) * BQ; jq.ldc = Q;
-            jq.gates_out = io->gates_q_tape ? io->gates_q_tape + (size_t)(t + 1) * 4 * BQ : nullptr;
-            jq.ada_std = io->ada_std; jq.ada_mean = io->ada_mean; jq.hadapt_dst = st_t16_view{xd_next, sv.d_kbs, sv.d_ha};
-            jq.B = B; jq.H = Q;
-            rc = st_lstm_cell_packed_pair_fwd(&jd, &jq, stream);
-        } else {
-        if (split_d && !ST_SKIPPED(3) && !(split_hosted && (ST_SKIPPED(1) || ST_SKIPPED(2))))
-            rc = st_lstm_cell_packed_part_fwd(io->packed + pl.d, sv.d_kbs, &xd_v, 16 * d_k0, io->gate_part, w->d_b_ih, w->d_b_hh,
-                                              io->cd_tape + (size_t)t * BD, D, io->d_mask ? io->d_mask + (size_t)t * BD : nullptr,
-                                              &hd_dst0, &hd_dst1, io->cd_tape + (size_t)(t + 1) * BD, D,
-                                              io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr, B, D, stream);
-        else
-        if (!ST_SKIPPED(3)) rc = st_lstm_cell_packed_fwd(io->packed + pl.d, &xd_v, Kd, w->d_b_ih, w->d_b_hh,
-                                     io->cd_tape + (size_t)t * BD, D, io->d_mask ? io->d_mask + (size_t)t * BD : nullptr,
-                                     &hd_dst0, &hd_dst1, io->cd_tape + (size_t)(t + 1) * BD, D,
-                                     io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr,
-                                     nullptr, nullptr, nullptr, B, D, stream);
+        st_t16_view xd_v = {xd, sv.d_kbs, 0};
+        st_t16_view hd_dst0 = {xd_next, sv.d_kbs, sv.d_h};
+        st_t16_view hd_dst1 = {xo, sv.o_kbs, 0};
+        const bool part = f.prod != PROD_NONE;      // the cell reduces its first d_k0 k-blocks and adds the slab
+        if (!ST_SKIPPED(3)) {
+            if (f.pair_cells && t + 1 < steps) {
+                // teacher forcing: the query cell of step t+1 needs ctx_t, h_q_t and a teacher frame -- not h_d_t.  Both cells in one launch.
+                st_lstm_cell_packed_job jd, jq;
+                memset(&jd, 0, sizeof(jd)); memset(&jq, 0, sizeof(jq));
+                jd.packed_w = io->packed + pl.d; jd.x = xd_v; jd.K = Kd; jd.b_ih = w->d_b_ih; jd.b_hh = w->d_b_hh;
+                if (part) { jd.K = 16 * f.d_k0; jd.part = io->gate_part; jd.w_kbs = sv.d_kbs; }
+                jd.c_prev = io->cd_tape + (size_t)t * BD; jd.ldc_prev = D; jd.mask = io->d_mask ? io->d_mask + (size_t)t * BD : nullptr;
+                jd.h_dst0 = hd_dst0; jd.h_dst1 = hd_dst1; jd.c_out = io->cd_tape + (size_t)(t + 1) * BD; jd.ldc = D;
+                jd.gates_out = io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr;
+                jd.B = B; jd.H = D;
+                float* xq_next2 = io->xq_tape + (size_t)(t + 2) * sv.q_floats;
+                jq.packed_w = io->packed + pl.q; jq.x = st_t16_view{xq_next, sv.q_kbs, 0}; jq.K = Kq; jq.b_ih = w->q_b_ih; jq.b_hh = w->q_b_hh;
+                jq.c_prev = io->cq_tape + (size_t)(t + 1) * BQ; jq.ldc_prev = Q; jq.mask = io->q_mask ? io->q_mask + (size_t)(t + 1) * BQ : nullptr;
+                jq.h_dst0 = st_t16_view{xq_next2, sv.q_kbs, sv.q_h}; jq.c_out = io->cq_tape + (size_t)(t + 2) * BQ; jq.ldc = Q;
+                jq.gates_out = io->gates_q_tape ? io->gates_q_tape + (size_t)(t + 1) * 4 * BQ : nullptr;
+                jq.ada_std = io->ada_std; jq.ada_mean = io->ada_mean; jq.hadapt_dst = st_t16_view{xd_next, sv.d_kbs, sv.d_ha};
+                jq.B = B; jq.H = Q;
+                rc = st_lstm_cell_packed_pair_fwd(&jd, &jq, stream);
+            } else if (part)
+                rc = st_lstm_cell_packed_part_fwd(io->packed + pl.d, sv.d_kbs, &xd_v, 16 * f.d_k0, io->gate_part, w->d_b_ih, w->d_b_hh,
+                                                  io->cd_tape + (size_t)t * BD, D, io->d_mask ? io->d_mask + (size_t)t * BD : nullptr,
+                                                  &hd_dst0, &hd_dst1, io->cd_tape + (size_t)(t + 1) * BD, D,
+                                                  io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr, B, D, stream);
+            else
+                rc = st_lstm_cell_packed_fwd(io->packed + pl.d, &xd_v, Kd, w->d_b_ih, w->d_b_hh,
+                                             io->cd_tape + (size_t)t * BD, D, io->d_mask ? io->d_mask + (size_t)t * BD : nullptr,
+                                             &hd_dst0, &hd_dst1, io->cd_tape + (size_t)(t + 1) * BD, D,
+                                             io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr,
+                                             nullptr, nullptr, nullptr, B, D, stream);
+            if (rc) return rc;
         }
-        if (rc) return rc;
 
         // 5. mel frames + stop logit (+ prenet layer 1 of the next input when fused)   ref: :282-287
         st_t16_view xo_v = {xo, sv.o_kbs, 0};
         st_t16_view mel_dst = {io->mel_t16, kb16(in_dim), 0};
         st_t16_view pre1_dst = {io->pre1_t16 + (size_t)t * io->pre1_step_floats, kb16(P), 0};
         const bool fuse = d->fuse_pre0 != 0;
-        if (defer) continue;         // mel / stop of all steps come from one GEMM over the xo tape (caller)
+        if (f.defer) continue;         // mel / stop of all steps come from one GEMM over the xo tape (caller)
+        const bool split_attn = f.attn != ATTN_WHOLE;
         st_attn_pre_job job = {io->pm, io->align_out + (size_t)t * L, ldal, io->wcum_tape + (size_t)(t + 1) * BL,
                                w->attn_loc_conv_w, w->attn_loc_lin_w,
                                split_attn ? io->attn_s_buf + (size_t)(t + 1) * io->attn_s_step_floats : nullptr, L, A, d->F, d->K,
                                io->attn_pre_parts, io->attn_loc_tape ? io->attn_loc_tape + (size_t)(t + 1) * BL * d->F : nullptr};
-        const bool p2_now = fuse_p2 && t + 1 < steps && !ST_SKIPPED(6) && !ST_SKIPPED(5);
-        if (p2_now) {
-            job.p2_packed_w = io->packed + pl.p1; job.p2_K = P; job.p2_N = P; job.p2_act = ST_ACT_RELU;
-            job.p2_mask = io->prenet_mask ? io->prenet_mask + ((size_t)t * 2 + 1) * B * P : nullptr; job.p2_ldmask = P;
-            job.p2_dst = st_t16_view{xq_next, sv.q_kbs, 0};
-            job.p2_gran = io->pre1_granules; job.p2_epoch = (unsigned)(t + 1); job.p2_status = io->handoff_status;
+        if (!ST_SKIPPED(4)) {
+            rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pg, &xo_v, ST_SKIPPED(7) ? Ko / 4 : Ko, w->projgate_b, ST_ACT_NONE, nullptr, 0,
+                                                     io->mel_out + (size_t)t * in_dim, (int)ldmel, fuse ? nullptr : &mel_dst, in_dim,
+                                                     io->stop_out + (size_t)t * d->r, steps * d->r, d->r,
+                                                     fuse ? in_dim + 1 : 0, ST_ACT_RELU,
+                                                     io->prenet_mask ? io->prenet_mask + (size_t)t * 2 * B * P : nullptr, P,
+                                                     fuse ? &pre1_dst : nullptr, B, in_dim + 1 + (fuse ? P : 0),
+                                                     split_attn && t + 1 < steps && !ST_SKIPPED(6) ? &job : nullptr, stream);
+            if (rc) return rc;
         }
-        if (!ST_SKIPPED(4)) rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pg, &xo_v, ST_SKIPPED(7) ? Ko / 4 : Ko, w->projgate_b, ST_ACT_NONE, nullptr, 0,
-                                                 io->mel_out + (size_t)t * in_dim, (int)ldmel, fuse ? nullptr : &mel_dst, in_dim,
-                                                 io->stop_out + (size_t)t * d->r, steps * d->r, d->r,
-                                                 fuse ? in_dim + 1 : 0, ST_ACT_RELU,
-                                                 io->prenet_mask ? io->prenet_mask + (size_t)t * 2 * B * P : nullptr, P,
-                                                 fuse ? &pre1_dst : nullptr, B, in_dim + 1 + (fuse ? P : 0),
-                                                 split_attn && t + 1 < steps && !ST_SKIPPED(6) ? &job : nullptr, stream);
-        if (rc) return rc;
 
         // 6. next decoder input -> xq_{t+1}[dec_in part]                 ref: :190-206
         if (t + 1 < steps) {
             const int src = io->step_src[t];
             st_t16_view next = {xq_next, sv.q_kbs, 0};
-            if ((src == -1 || io->Bt < B) && !ST_SKIPPED(5) && !p2_now) {   // rows without a teacher feed their own output back
-                rc = prenet_own(w, d, io, pl, sv, t, fuse, stream);             // (p2_now: layer 2 rode in the launch above)
+            if ((src == -1 || io->Bt < B) && !ST_SKIPPED(5)) {    // rows without a teacher feed their own output back
+                rc = prenet_own(w, d, io, pl, sv, t, fuse, stream);
                 if (rc) return rc;
             }
-            if (pure_tf) rc = 0;             // tiled for all steps before the loop
-            else if (src >= 0) rc = st_tile_rows(io->teacher_pre + (size_t)src * P, io->Tt * P, &next, io->Bt, P, stream);
-            else if (src == -2) rc = st_tile_rows(io->teacher_mean, P, &next, io->Bt, P, stream);
+            // (pure teacher forcing: tiled for all steps before the loop)
+            if (!f.pure_tf && src >= 0) rc = st_tile_rows(io->teacher_pre + (size_t)src * P, io->Tt * P, &next, io->Bt, P, stream);
+            else if (!f.pure_tf && src == -2) rc = st_tile_rows(io->teacher_mean, P, &next, io->Bt, P, stream);
             if (rc) return rc;
         } else if (d->prenet_norm == 3 && (io->step_src[t] == -1 || io->Bt < B)) {
             // the reference forms the next input after the LAST step too (:192,:197-198,:205-206).  Nothing reads it, but a training-mode

@@ -24,6 +24,18 @@ def maxdiff(a, b):
     return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
 
 
+FWD_ATTN = ('whole', 'pre_fin', 'fin_split', 'pq_fin', 'pq_rng')      # bits 0..2 of an st_decoder_fwd_forms word
+FWD_PROD = ('none', 'own', 'pq_fin', 'pq_pre')                        # bits 4..5
+
+
+def fwd_forms(word):
+    """(attention form, host of the decoder cell's partial gate product, flags) of an st_decoder_fwd_forms word
+    (Decoder._last_fwd_forms); flags is a subset of {'tf', 'defer', 'pre_in_pq', 'pair'}"""
+    assert word is not None and word >= 0, word
+    flags = {n for b, n in ((8, 'tf'), (9, 'defer'), (10, 'pre_in_pq'), (11, 'pair')) if word >> b & 1}
+    return FWD_ATTN[word & 7], FWD_PROD[(word >> 4) & 3], flags
+
+
 def coin_source(coins):
     it = iter(np.asarray(coins, dtype=np.float64).tolist())
     return lambda: next(it)

@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import maxdiff, report
+from helpers import fwd_forms, maxdiff, report
 
 pytestmark = pytest.mark.gpu
 
@@ -1254,6 +1254,7 @@ def test_bptt_loop_with_hosted_attention_backward_is_bitwise_the_plain_loop(dev)
         torch.manual_seed(77)                                   # the same dropout masks in every pass
         mem, spk = mem0.clone().requires_grad_(), spk0.clone().requires_grad_()
         mel, align, stop = dec(mem, None, teacher, spk, tf_rate=1.0)
+        assert ('pair' in fwd_forms(dec._last_fwd_forms)[2]) == dec.fwd_pair_cells, (mode, hex(dec._last_fwd_forms))
         if douts is None:
             douts = [rnd(*mel.shape, seed=5).to(dev), rnd(*align.shape, seed=6).to(dev), rnd(*stop.shape, seed=7).to(dev)]
         torch.autograd.backward([mel, align, stop], douts)

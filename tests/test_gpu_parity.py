@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import load_golden
-from helpers import (coin_source, full_hp, full_tacotron, masks_to, maxdiff, report, split_masks, tiny_tacotron)
+from helpers import (coin_source, full_hp, full_tacotron, fwd_forms, masks_to, maxdiff, report, split_masks, tiny_tacotron)
 
 pytestmark = pytest.mark.gpu
 
@@ -622,9 +622,12 @@ def test_headline_shape_c2_against_oracle(dev):
     with torch.no_grad():
         mel, lin, align, stop = m(txt.to(dev), None, 258, spk.to(dev), tf_rate=0.0)
         # the unsplit attention launch and other part counts must give the same values up to re-association
+        assert fwd_forms(m.decoder._last_fwd_forms)[:2] == ('pq_fin', 'pq_fin')
         for split, fin in ((False, 2), (True, 1), (True, 4)):
             m.decoder.attn_split, m.decoder.attn_fin_parts = split, fin
             mel_o, _, align_o, _ = m(txt.to(dev), None, 258, spk.to(dev), tf_rate=0.0)
+            assert fwd_forms(m.decoder._last_fwd_forms)[0] == ('pq_fin' if split else 'whole')
+            assert (m.decoder._last_fwd_forms >> 12) & 15 == (fin if split else 1)
             report('tts_c2_attn_variants', split=int(split), fin=fin, mel=maxdiff(mel_o, mel), align=maxdiff(align_o, align))
             assert maxdiff(mel_o, mel) < 2e-5 and maxdiff(align_o, align) < 1e-5
         m.decoder.attn_split, m.decoder.attn_fin_parts = True, 2
@@ -632,8 +635,10 @@ def test_headline_shape_c2_against_oracle(dev):
         # arithmetic as the two launches: bit-identical outputs, and again on a second pass (the tags of the first must not leak)
         m.decoder.attn_pq_in_fin = False
         mel_2, _, align_2, _ = m(txt.to(dev), None, 258, spk.to(dev), tf_rate=0.0)
+        assert fwd_forms(m.decoder._last_fwd_forms)[:2] == ('pre_fin', 'own')
         m.decoder.attn_pq_in_fin = True
         mel_1, _, align_1, _ = m(txt.to(dev), None, 258, spk.to(dev), tf_rate=0.0)
+        assert fwd_forms(m.decoder._last_fwd_forms)[:2] == ('pq_fin', 'pq_fin')
         assert torch.equal(mel_2, mel) and torch.equal(align_2, align) and torch.equal(mel_1, mel) and torch.equal(align_1, align)
     torch.set_num_threads(8)
     with torch.no_grad():
@@ -1024,7 +1029,7 @@ def test_query_projection_and_fin_part_over_position_ranges_in_one_launch(dev, B
 def test_long_text_decode_uses_the_one_launch_form_and_matches_the_three_launch_form(dev):
     """Decoder.forward at L = 171 (free running): the loop with query projection + range fin part + combine as one launch per step
     == the loop with the split + combine launches (same split of the softmax; ~1e-7), both finite"""
-    from helpers import full_tacotron
+    from helpers import full_tacotron, fwd_forms
     from semi_tts_amd.synthetic import synthetic_batch
     B, L, T = 8, 171, 36
     m = full_tacotron(dev, seed=21, prenet_dropout=0.0)
@@ -1034,10 +1039,10 @@ def test_long_text_decode_uses_the_one_launch_form_and_matches_the_three_launch_
         mem = m.encoder(txt, None).contiguous()
         m.decoder.attn_rng_one_launch = True
         mel1, al1, _ = m.decoder(mem, None, T, spk, tf_rate=0.0)
-        assert 'attn_xchg' in m.decoder.last_tapes
+        assert 'attn_xchg' in m.decoder.last_tapes and fwd_forms(m.decoder._last_fwd_forms)[0] == 'pq_rng'
         m.decoder.attn_rng_one_launch = False
         mel2, al2, _ = m.decoder(mem, None, T, spk, tf_rate=0.0)
-        assert 'attn_xchg' not in m.decoder.last_tapes
+        assert 'attn_xchg' not in m.decoder.last_tapes and fwd_forms(m.decoder._last_fwd_forms)[0] == 'fin_split'
     errs = dict(mel=maxdiff(mel1, mel2), align=maxdiff(al1, al2))
     report('decode_long_text_one_launch', **errs)
     assert errs['mel'] < 5e-6 and errs['align'] < 1e-6 and bool(torch.isfinite(mel1).all())

@@ -22,7 +22,7 @@ import pytest
 import torch
 
 from conftest import load_golden, REPO
-from helpers import full_hp, full_tacotron, masks_to, maxdiff, report, split_masks
+from helpers import full_hp, full_tacotron, fwd_forms, masks_to, maxdiff, report, split_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -458,7 +458,12 @@ def test_decoder_gate_split_at_every_cut_agrees_with_the_whole_cell_and_the_orac
     def run(split, k=0, pq_in_fin=True):
         dec.split_gates, dec.split_cell_k, dec.attn_pq_in_fin = split, k, pq_in_fin
         with torch.no_grad():
-            return [t.clone() for t in dec(mem, None, T, spk.to(dev), tf_rate=0.0)]
+            out = [t.clone() for t in dec(mem, None, T, spk.to(dev), tf_rate=0.0)]
+        # the form that ran: the product beside pq + fin, in a launch of its own beside the two-launch attention, or none
+        want = ('pq_fin', 'pq_fin' if split else 'none') if pq_in_fin else ('pre_fin', 'own' if split else 'none')
+        assert fwd_forms(dec._last_fwd_forms)[:2] == want, hex(dec._last_fwd_forms)
+        assert dec._last_fwd_forms >> 16 == ((k or 1280) // 16 if split else 0)
+        return out
     try:
         whole = run(False)
         torch.set_num_threads(min(os.cpu_count() or 1, 16))
@@ -505,6 +510,7 @@ def test_training_loop_with_the_gate_split_agrees_with_the_unsplit_loop(dev):
             torch.manual_seed(77)
             mem, spk = mem0.clone().requires_grad_(), spk0.clone().requires_grad_()
             mel, align, stop = dec(mem, None, teacher, spk, tf_rate=1.0)
+            assert fwd_forms(dec._last_fwd_forms)[:2] == ('pre_fin', 'pq_pre' if split else 'none'), hex(dec._last_fwd_forms)
             if douts is None:
                 douts = [torch.randn(t.shape, generator=g).to(dev) for t in (mel, align, stop)]
             torch.autograd.backward([mel, align, stop], douts)
