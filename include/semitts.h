@@ -1081,6 +1081,31 @@ int st_ctc_greedy_edit_distance(const float* prob, int B, int T, int V, const in
                                 void* stream);
 int st_ids_edit_distance(const int64_t* pred, int B, int T, const int64_t* text, int L, const int32_t* ignore, int n_ignore,
                          int32_t* dist, int32_t* ref_len, int64_t* hyp, int32_t* hyp_len, void* stream);
+/* st_hyp_edit_distance: the same distance for hypotheses that are already transcripts (st_ctc_beam_search's): hyp (B, Lh) int64, utterance
+ * b's tokens hyp[b, 0 .. hyp_len[b]) (hyp_len (B) int32, clamped to [0, Lh]), the ignored ids dropped from both sides, runs NOT collapsed
+ * ("a <blank> a" stays two tokens).  Limits: 1 <= Lh <= 4096, 1 <= L <= 1024, 0 <= n_ignore <= 64. */
+int st_hyp_edit_distance(const int64_t* hyp, const int32_t* hyp_len, int B, int Lh, const int64_t* text, int L, const int32_t* ignore,
+                         int n_ignore, int32_t* dist, int32_t* ref_len, void* stream);
+
+/* CTC prefix beam search (the ASR side's transcription; the reference's --asr-decode solver is absent from its tree).
+ * prob (B, T, V) fp32: log-probability log(prob + eps) when log_input == 0 (compute_ctcloss(apply_log=True), bin/train_vqvae.py:430-433),
+ * prob itself when log_input != 0 (ASRPostnet's log_softmax).  Utterance b reads frames [0, lengths[b]) (lengths (B) int32 on the device,
+ * NULL = all T; clamped to [0, T]); nothing beyond is read for its value, so NaN there changes nothing.
+ * Each prefix carries (log p_blank, log p_nonblank) and scores their logaddexp.  Start: the empty prefix, p_blank = log 1, p_nonblank = -inf.
+ * Per frame every prefix of the beam makes candidates: its stay (blank into p_blank, its last symbol repeated into p_nonblank) and one
+ * extension per non-blank symbol c (fed by p_blank alone when c is its last symbol).  An extension equal to a prefix of the beam is
+ * merged into that prefix's stay (exact sequence identity, never a hash).  The W best candidates form the next beam.
+ * Order: score descending, then candidate index ascending; the index counts the stays first in slot order, then the extensions by
+ * (slot, symbol).  Outputs, the N best prefixes after the last frame in that order: hyp (B, N, T) int64 label ids 0-padded, hyp_len (B, N)
+ * int32, score (B, N) fp32 natural-log prefix probability.  lengths[b] == 0: one empty hypothesis of score 0.  A NaN log-probability in the
+ * valid frames: every path of the utterance has length 0 and score NaN.  Fewer than N distinct prefixes: the surplus paths have length 0 and
+ * score -inf.  No float atomics; an utterance's result depends on it alone (bitwise repeatable, independent of B).
+ * Limits (-22 past them): 1 <= T <= 4096, 2 <= V <= 1024, 1 <= W <= 128, 1 <= N <= W, 0 <= blank < V.  ws:
+ * st_ctc_beam_workspace_bytes(B, T, W) bytes (the prefix tree; no initialisation needed).  One launch, no host read. */
+size_t st_ctc_beam_workspace_bytes(int B, int T, int W);
+int st_ctc_beam_search(const float* prob, int B, int T, int V, const int32_t* lengths /* NULL = all T */, int W, int N, int blank,
+                       int log_input, float eps, int64_t* hyp /* (B, N, T), 0-padded */, int32_t* hyp_len /* (B, N) */,
+                       float* score /* (B, N) */, void* ws, void* stream);
 
 /* The trainer's scalar arithmetic on loss values as one launch (ref: bin/train_vqvae.py:208-233: total_loss = asr_weight * asr_loss +
  * tts_weight * (mel_loss + linear_loss) + unpair_speech_weight * ... -- a chain of one-element torch kernels there):

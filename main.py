@@ -14,6 +14,8 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/semi-single-spkr-paired-data.yaml --max-step 20000 --dev-batches 4 [--valid-step 5000] [--store-best-per]
     python main.py --config config/supervised.yaml --gen-specgram [--load ckpt.pth] [--frames 256 --batch-size 32]
     python main.py --config config/supervised.yaml --tts-only --max-step 20 [--frames 256 --batch-size 32]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR [--beam-width 16 --top-paths 1 --vocab FILE]
+`--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber).
 """
 import argparse
 import random
@@ -57,6 +59,14 @@ parser.add_argument('--save', action='store_true', help='write ckpt/<name>/lates
 parser.add_argument('--dev-batches', default=0, type=int, help='validate on K synthetic dev batches (paired shapes) at step 1 and every '
                     'valid step: dev TTS loss, PER, post PER, checkpoints by the reference\'s rules (default 0: no validation)')
 parser.add_argument('--valid-step', default=None, type=int, help='steps between validations (default: hparas.valid_step)')
+parser.add_argument('--transcribe-wav-dir', default=None, type=str, help='transcribe the .wav files of this directory (sorted by name, '
+                    'batched by --batch-size) by CTC prefix beam search into <logdir>/<name>/<file>.phn: --top-paths lines of score<TAB>tokens')
+parser.add_argument('--beam-width', default=16, type=int, help='--transcribe-wav-dir: beam width (1 .. 128)')
+parser.add_argument('--top-paths', default=1, type=int, help='--transcribe-wav-dir: paths written per file (1 .. --beam-width)')
+parser.add_argument('--vocab', default=None, type=str, help='--transcribe-wav-dir: phone list, one per line (id = 3 + line index); '
+                    'without it the .phn files hold ids')
+parser.add_argument('--asr-output', default='code', choices=('code', 'post'), help='--transcribe-wav-dir: search the codebook posteriors '
+                    '(code) or the ASR postnet log-posteriors (post)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -88,6 +98,14 @@ def parse_args(argv=None):
     if paras.dev_batches > 0 and (paras.tts_only or paras.gen_specgram):
         parser.error('--dev-batches validates the two cycles (VqvaeTrainer); it does not combine with --%s'
                      % ('tts-only' if paras.tts_only else 'gen-specgram'))
+    if paras.transcribe_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir'):
+            if getattr(paras, flag):
+                parser.error('--transcribe-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--transcribe-wav-dir does not combine with --dev-batches')
+        if not (1 <= paras.top_paths <= paras.beam_width <= 128):
+            parser.error('--transcribe-wav-dir needs 1 <= --top-paths <= --beam-width <= 128')
     if paras.verbose:
         for flag in IGNORED_FLAGS:
             if flag == 'gen_wav' and paras.gen_specgram:
@@ -115,7 +133,10 @@ def main(argv=None):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('nccl')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    if paras.gen_specgram:
+    if paras.transcribe_wav_dir is not None:
+        from semi_tts_amd.solver import Transcriber as Solver
+        mode = 'test'
+    elif paras.gen_specgram:
         from semi_tts_amd.solver import SpecgramGenerator as Solver
         mode = 'test'
     elif paras.tts_only:

@@ -412,6 +412,69 @@ __device__ __forceinline__ int ged_block_scan(int x, int* scr, int* total) {
     return off + s - x;
 }
 
+// ref = text(b, :) without the ignored ids, wherever they sit, compacted into `ref` in LDS; -> its length (every thread)
+__device__ __forceinline__ int ged_compact_ref(const int64_t* text, int L, const int* ign, int n_ignore, int64_t* ref, int* scr) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t* tb = text + (size_t)b * L;
+    const int cl = (L + GED_NT - 1) / GED_NT, l0 = min(L, tid * cl), l1 = min(L, l0 + cl);
+    int cnt = 0;
+    for (int l = l0; l < l1; ++l) cnt += !ged_ignored(tb[l], ign, n_ignore);
+    int n;
+    int pos = ged_block_scan(cnt, scr, &n);
+    for (int l = l0; l < l1; ++l) {
+        const int64_t x = tb[l];
+        if (!ged_ignored(x, ign, n_ignore)) ref[pos++] = x;
+    }
+    return n;
+}
+
+// dist[b] = Levenshtein(hyp[0 .. m), ref[0 .. n)), ref_len[b] = n; run by wave 0 alone (lane = its lane), hyp / ref in LDS
+__device__ __forceinline__ void ged_levenshtein(const int64_t* hyp, int m, const int64_t* ref, int n, int lane, int32_t* dist, int32_t* ref_len) {
+    const int b = blockIdx.x;
+    // ---- DP, wave 0: columns j = 0 .. n, lane `lane` owns j = lane * cpt + k, k < cpt
+    const int cpt = (n + 1 + 63) / 64;
+    int D[GED_CPT];
+    int64_t r[GED_CPT];
+#pragma unroll
+    for (int k = 0; k < GED_CPT; ++k) {
+        const int j = lane * cpt + k;
+        D[k] = j;                                             // row 0: j insertions
+        r[k] = (k < cpt && j >= 1 && j <= n) ? ref[j - 1] : -1;
+    }
+    for (int i = 1; i <= m; ++i) {
+        const int64_t h = hyp[i - 1];
+        int last = 0;                                         // D[i-1][lane * cpt + cpt - 1]
+#pragma unroll
+        for (int k = 0; k < GED_CPT; ++k) if (k == cpt - 1) last = D[k];
+        const int left = __shfl_up(last, 1);                  // D[i-1] of the column before this lane's first one
+        int pm = INT_MAX, Y[GED_CPT];
+        int prev = left;
+#pragma unroll
+        for (int k = 0; k < GED_CPT; ++k) {
+            if (k < cpt) {
+                const int j = lane * cpt + k;
+                const int X = j == 0 ? i : min(prev + (h != r[k] ? 1 : 0), D[k] + 1);
+                prev = D[k];
+                pm = min(pm, X - j);
+                Y[k] = pm;                                    // inclusive prefix minimum within the lane
+            }
+        }
+        int s = pm;                                           // inclusive prefix minimum over the lanes
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(s, d);
+            if (lane >= d) s = min(s, y);
+        }
+        int e = __shfl_up(s, 1);                              // ... exclusive
+        if (lane == 0) e = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < GED_CPT; ++k) if (k < cpt) D[k] = lane * cpt + k + min(e, Y[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < GED_CPT; ++k) {
+        if (k < cpt && lane * cpt + k == n) { dist[b] = D[k]; ref_len[b] = n; }
+    }
+}
+
 // ids != NULL: p[t] = ids(b, t) (already argmaxed, int64) and prob is not read
 __global__ __launch_bounds__(GED_NT) void ctc_greedy_ed_kernel(const float* prob, const int64_t* ids, int T, int V, const int64_t* text, int L,
                                                                const int32_t* ignore, int n_ignore, int32_t* dist, int32_t* ref_len,
@@ -457,16 +520,7 @@ __global__ __launch_bounds__(GED_NT) void ctc_greedy_ed_kernel(const float* prob
         if ((t == 0 || x != tok(t - 1)) && !ged_ignored(x, ign, n_ignore)) hyp[pos++] = x;
     }
     // ---- ref: the transcript without the ignored ids, wherever they sit
-    const int64_t* tb = text + (size_t)b * L;
-    const int cl = (L + GED_NT - 1) / GED_NT, l0 = min(L, tid * cl), l1 = min(L, l0 + cl);
-    cnt = 0;
-    for (int l = l0; l < l1; ++l) cnt += !ged_ignored(tb[l], ign, n_ignore);
-    int n;
-    pos = ged_block_scan(cnt, scr, &n);
-    for (int l = l0; l < l1; ++l) {
-        const int64_t x = tb[l];
-        if (!ged_ignored(x, ign, n_ignore)) ref[pos++] = x;
-    }
+    const int n = ged_compact_ref(text, L, ign, n_ignore, ref, scr);
     __syncthreads();
     if (hyp_out) {
         int64_t* ho = hyp_out + (size_t)b * T;
@@ -474,48 +528,36 @@ __global__ __launch_bounds__(GED_NT) void ctc_greedy_ed_kernel(const float* prob
         if (tid == 0) hyp_len_out[b] = m;
     }
     if (w != 0) return;
-    // ---- DP, wave 0: columns j = 0 .. n, lane `lane` owns j = lane * cpt + k, k < cpt
-    const int cpt = (n + 1 + 63) / 64;
-    int D[GED_CPT];
-    int64_t r[GED_CPT];
-#pragma unroll
-    for (int k = 0; k < GED_CPT; ++k) {
-        const int j = lane * cpt + k;
-        D[k] = j;                                             // row 0: j insertions
-        r[k] = (k < cpt && j >= 1 && j <= n) ? ref[j - 1] : -1;
+    ged_levenshtein(hyp, m, ref, n, lane, dist, ref_len);
+}
+
+// hypotheses that are already transcripts (a beam search's): hyp(b, 0 .. hyp_len[b]) without the ignored ids -- runs are NOT
+// collapsed -- against text(b, :) without them
+__global__ __launch_bounds__(GED_NT) void hyp_ed_kernel(const int64_t* hyp_in, const int32_t* hyp_len_in, int Lh, const int64_t* text, int L,
+                                                        const int32_t* ignore, int n_ignore, int32_t* dist, int32_t* ref_len) {
+    extern __shared__ int64_t ged_dyn[];          // hyp[Lh], ref[L]
+    int64_t* hyp = ged_dyn;
+    int64_t* ref = ged_dyn + Lh;
+    __shared__ int ign[GED_MAX_IGNORE];
+    __shared__ int scr[GED_NT / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int k = tid; k < n_ignore; k += GED_NT) ign[k] = ignore[k];
+    __syncthreads();
+    const int64_t* hb = hyp_in + (size_t)b * Lh;
+    const int len = min(max(hyp_len_in[b], 0), Lh);
+    const int ct = (len + GED_NT - 1) / GED_NT, t0 = min(len, tid * ct), t1 = min(len, t0 + ct);
+    int cnt = 0;
+    for (int t = t0; t < t1; ++t) cnt += !ged_ignored(hb[t], ign, n_ignore);
+    int m;
+    int pos = ged_block_scan(cnt, scr, &m);
+    for (int t = t0; t < t1; ++t) {
+        const int64_t x = hb[t];
+        if (!ged_ignored(x, ign, n_ignore)) hyp[pos++] = x;
     }
-    for (int i = 1; i <= m; ++i) {
-        const int64_t h = hyp[i - 1];
-        int last = 0;                                         // D[i-1][lane * cpt + cpt - 1]
-#pragma unroll
-        for (int k = 0; k < GED_CPT; ++k) if (k == cpt - 1) last = D[k];
-        const int left = __shfl_up(last, 1);                  // D[i-1] of the column before this lane's first one
-        int pm = INT_MAX, Y[GED_CPT];
-        int prev = left;
-#pragma unroll
-        for (int k = 0; k < GED_CPT; ++k) {
-            if (k < cpt) {
-                const int j = lane * cpt + k;
-                const int X = j == 0 ? i : min(prev + (h != r[k] ? 1 : 0), D[k] + 1);
-                prev = D[k];
-                pm = min(pm, X - j);
-                Y[k] = pm;                                    // inclusive prefix minimum within the lane
-            }
-        }
-        int s = pm;                                           // inclusive prefix minimum over the lanes
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(s, d);
-            if (lane >= d) s = min(s, y);
-        }
-        int e = __shfl_up(s, 1);                              // ... exclusive
-        if (lane == 0) e = INT_MAX;
-#pragma unroll
-        for (int k = 0; k < GED_CPT; ++k) if (k < cpt) D[k] = lane * cpt + k + min(e, Y[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < GED_CPT; ++k) {
-        if (k < cpt && lane * cpt + k == n) { dist[b] = D[k]; ref_len[b] = n; }
-    }
+    const int n = ged_compact_ref(text, L, ign, n_ignore, ref, scr);
+    __syncthreads();
+    if (w != 0) return;
+    ged_levenshtein(hyp, m, ref, n, lane, dist, ref_len);
 }
 
 }  // namespace
@@ -546,4 +588,19 @@ extern "C" int st_ids_edit_distance(const int64_t* pred, int B, int T, const int
                                     int32_t* dist, int32_t* ref_len, int64_t* hyp, int32_t* hyp_len, void* stream) {
     ST_CHECK_ARG(pred, "st_ids_edit_distance: null pred");
     return ged_launch(nullptr, pred, B, T, 0, text, L, ignore, n_ignore, dist, ref_len, hyp, hyp_len, stream, "st_ids_edit_distance");
+}
+
+extern "C" int st_hyp_edit_distance(const int64_t* hyp, const int32_t* hyp_len, int B, int Lh, const int64_t* text, int L, const int32_t* ignore,
+                                    int n_ignore, int32_t* dist, int32_t* ref_len, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(hyp && hyp_len && text && dist && ref_len && B > 0 && Lh > 0 && L > 0, "st_hyp_edit_distance: bad arguments");
+    ST_CHECK_ARG(Lh <= GED_MAX_T, "st_hyp_edit_distance: hypotheses of at most %d tokens (Lh=%d)", GED_MAX_T, Lh);
+    ST_CHECK_ARG(L <= GED_MAX_L, "st_hyp_edit_distance: transcripts of at most %d tokens (L=%d)", GED_MAX_L, L);
+    ST_CHECK_ARG(n_ignore >= 0 && n_ignore <= GED_MAX_IGNORE && (n_ignore == 0 || ignore), "st_hyp_edit_distance: 0..%d ignored ids",
+                 GED_MAX_IGNORE);
+    const size_t lds = ((size_t)Lh + L) * sizeof(int64_t);      // <= 40 KiB at the limits
+    hipLaunchKernelGGL(hyp_ed_kernel, dim3(B), dim3(GED_NT), lds, (hipStream_t)stream, hyp, hyp_len, Lh, text, L, ignore, n_ignore, dist,
+                       ref_len);
+    ST_LAUNCH_CHECK();
+    return 0;
 }

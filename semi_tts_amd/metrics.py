@@ -36,10 +36,24 @@ def edit_distances(pred, truth, ignore=IGNORE_INDICES):
 def per_sum(pred, truth, ignore=IGNORE_INDICES):
     """sum over the batch of dist / ref_len as a float64 device scalar (no host read).  An utterance whose transcript is empty once the
     ignored ids are gone (ref_len == 0) makes the sum NaN -- the reference raises ZeroDivisionError there."""
-    dist, ref_len = edit_distances(pred, truth, ignore)
+    return _rate_sum(*edit_distances(pred, truth, ignore))
+
+
+def _rate_sum(dist, ref_len):
     d, n = dist.to(torch.float64), ref_len.to(torch.float64)
     rate = torch.where(ref_len > 0, d / n.clamp_min(1.0), torch.full_like(d, math.nan))
     return rate.sum()
+
+
+def beam_per_sum(prob, truth, beam_width, lengths=None, ignore=IGNORE_INDICES, log_input=False):
+    """per_sum of the top-1 CTC prefix beam search transcripts (ctc_decode.beam_search, blank 0) instead of the greedy ones: prob
+    (B, T, V) float32 posteriors (log-posteriors with log_input), truth (B, L) int64, lengths the valid frames per utterance (None: all).
+    The hypotheses are already collapsed, so the distance does not merge runs (st_hyp_edit_distance).  cal_per and the trainer's
+    validation stay greedy, as the reference's are."""
+    from .ctc_decode import beam_search
+    prob, truth = _on_device(prob, truth)
+    hyp, hyp_len, _ = beam_search(prob, lengths, beam_width, 1, log_input=log_input)
+    return _rate_sum(*ops.hyp_edit_distance(hyp[:, 0], hyp_len[:, 0], truth, ignore))
 
 
 def cal_per(pred, truth):

@@ -907,6 +907,86 @@ def ctc_greedy_edit_distance(prob, text, ignore, want_hyp=False):
     return (dist, ref_len, hyp, hyp_len) if want_hyp else (dist, ref_len)
 
 
+CB_MAX_T, CB_MIN_V, CB_MAX_V, CB_MAX_W = 4096, 2, 1024, 128          # st_ctc_beam_search's limits
+
+
+def ctc_beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log_input=False, eps=1e-10):
+    """CTC prefix beam search of prob (B, T, V) fp32 on one GPU (see st_ctc_beam_search).  lengths: None (all T frames), or (B,) integer
+    frame counts -- a host tensor / sequence is checked against [0, T] here, a device tensor is taken as it is (the kernel clamps it).
+    -> (hyp (B, top_paths, T) int64 0-padded, hyp_len (B, top_paths) int32, score (B, top_paths) float32) device tensors; one launch,
+    no host read.  Anything the kernel would refuse raises ValueError before the device is touched."""
+    if not torch.is_tensor(prob) or not prob.is_cuda or prob.dim() != 3 or prob.dtype != torch.float32:
+        raise ValueError('ctc_beam_search: prob must be a (B, T, V) float32 GPU tensor (got %s)'
+                         % ('%s %s on %s' % (tuple(prob.shape), prob.dtype, prob.device) if torch.is_tensor(prob) else type(prob).__name__))
+    B, T, V = prob.shape
+    W, N, blank = int(beam_width), int(top_paths), int(blank)
+    if B < 1 or not (1 <= T <= CB_MAX_T and CB_MIN_V <= V <= CB_MAX_V):
+        raise ValueError('ctc_beam_search: B=%d, T=%d, V=%d outside B >= 1, 1 <= T <= %d, %d <= V <= %d' % (B, T, V, CB_MAX_T, CB_MIN_V, CB_MAX_V))
+    if not (1 <= W <= CB_MAX_W and 1 <= N <= W):
+        raise ValueError('ctc_beam_search: need 1 <= top_paths <= beam_width <= %d (beam_width %d, top_paths %d)' % (CB_MAX_W, W, N))
+    if not 0 <= blank < V:
+        raise ValueError('ctc_beam_search: blank %d outside [0, %d)' % (blank, V))
+    if not eps >= 0.0:
+        raise ValueError('ctc_beam_search: eps must be >= 0 (got %r)' % (eps,))
+    dev = prob.device
+    if lengths is not None:
+        if torch.is_tensor(lengths) and lengths.is_cuda:
+            if lengths.device != dev or lengths.shape != (B,) or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError('ctc_beam_search: lengths must be (B,) integers on the device of prob (got %s %s on %s)'
+                                 % (tuple(lengths.shape), lengths.dtype, lengths.device))
+        else:
+            host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths)
+            if host.shape != (B,) or host.dtype.kind not in 'iu' or (host < 0).any() or (host > T).any():
+                raise ValueError('ctc_beam_search: lengths must be %d integers in [0, %d] (got %s)' % (B, T, host.tolist()))
+        lengths = torch.as_tensor(lengths).to(dev, torch.int32).contiguous()
+    lib = _lib.load()
+    prob = prob.contiguous()
+    hyp = torch.empty(B, N, T, device=dev, dtype=torch.int64)
+    hyp_len = torch.empty(B, N, device=dev, dtype=torch.int32)
+    score = torch.empty(B, N, device=dev, dtype=torch.float32)
+    ws = torch.empty(int(lib.st_ctc_beam_workspace_bytes(B, T, W)), device=dev, dtype=torch.uint8)
+    check(lib.st_ctc_beam_search(_p(prob), B, T, V, _p(lengths, torch.int32), W, N, blank, 1 if log_input else 0, float(eps),
+                                 _p(hyp, torch.int64), _p(hyp_len, torch.int32), _p(score), _p(ws, torch.uint8), stream_handle()),
+          'st_ctc_beam_search')
+    return hyp, hyp_len, score
+
+
+def hyp_edit_distance(hyp, hyp_len, text, ignore):
+    """edit distance of transcripts that are already collapsed (a beam search's) to `text`, per utterance (see st_hyp_edit_distance):
+    hyp (B, Lh) int64 with hyp_len (B,) int32 tokens each, text (B, L) int64, ignore: the ids dropped from both sides.  -> (dist,
+    ref_len) int32 (B,) device tensors; one launch, no host read.  Anything the kernel would refuse raises ValueError first."""
+    if not all(torch.is_tensor(x) for x in (hyp, hyp_len, text)):
+        raise ValueError('hyp_edit_distance: hyp, hyp_len and text must be tensors')
+    if not (hyp.is_cuda and hyp.device == hyp_len.device == text.device):
+        raise ValueError('hyp_edit_distance: hyp, hyp_len and text must be on one GPU (got %s, %s, %s)' % (hyp.device, hyp_len.device, text.device))
+    if hyp.dim() != 2 or hyp.dtype != torch.int64 or text.dim() != 2 or text.dtype != torch.int64:
+        raise ValueError('hyp_edit_distance: hyp and text must be 2-D int64 (got %s %s, %s %s)'
+                         % (tuple(hyp.shape), hyp.dtype, tuple(text.shape), text.dtype))
+    B, Lh = hyp.shape
+    L = text.shape[1]
+    if hyp_len.shape != (B,) or hyp_len.dtype != torch.int32:
+        raise ValueError('hyp_edit_distance: hyp_len must be (%d,) int32 (got %s %s)' % (B, tuple(hyp_len.shape), hyp_len.dtype))
+    ignore = tuple(int(i) for i in ignore)
+    if text.shape[0] != B or B < 1:
+        raise ValueError('hyp_edit_distance: %d hypotheses, %d transcripts (at least one)' % (B, text.shape[0]))
+    if not (1 <= Lh <= GED_MAX_T and 1 <= L <= GED_MAX_L and len(ignore) <= GED_MAX_IGNORE):
+        raise ValueError('hyp_edit_distance: Lh=%d, L=%d, %d ignored ids outside 1 <= Lh <= %d, 1 <= L <= %d, <= %d ignored ids'
+                         % (Lh, L, len(ignore), GED_MAX_T, GED_MAX_L, GED_MAX_IGNORE))
+    if any(not -2 ** 31 <= i < 2 ** 31 for i in ignore):
+        raise ValueError('hyp_edit_distance: ignored ids must fit int32')
+    dev = hyp.device
+    ign = _IGNORE_DEV.get((dev, ignore))
+    if ign is None:
+        ign = _IGNORE_DEV[(dev, ignore)] = torch.tensor(ignore if ignore else [0], dtype=torch.int32).to(dev)
+    hyp, hyp_len, text = hyp.contiguous(), hyp_len.contiguous(), text.contiguous()
+    dist = torch.empty(B, device=dev, dtype=torch.int32)
+    ref_len = torch.empty(B, device=dev, dtype=torch.int32)
+    check(_lib.load().st_hyp_edit_distance(_p(hyp, torch.int64), _p(hyp_len, torch.int32), B, Lh, _p(text, torch.int64), L,
+                                           _p(ign, torch.int32), len(ignore), _p(dist, torch.int32), _p(ref_len, torch.int32),
+                                           stream_handle()), 'st_hyp_edit_distance')
+    return dist, ref_len
+
+
 def softmax_argmax(logits):
     lib = _lib.load()
     V = logits.shape[-1]

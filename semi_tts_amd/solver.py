@@ -159,6 +159,82 @@ class SpecgramGenerator(BaseSolver):
         return cnt
 
 
+SPECIAL_TOKENS = ('<pad>', '<space>', '<eos>')     # ids 0, 1, 2 of the phone vocabulary (src/text.py); phones start at id 3
+
+
+def read_vocab(path):
+    """the phone symbols of a vocabulary file as the reference's data/cmu_phn.vocab lists them, one per line: -> list indexed by id
+    (ids 0 .. 2 the special tokens, line k -> id 3 + k)"""
+    with open(path) as f:
+        phones = [ln.strip() for ln in f if ln.strip()]
+    return list(SPECIAL_TOKENS) + phones
+
+
+def format_phn(scores, hyps, vocab=None):
+    """the text of one utterance's .phn file: one line per path, `score<TAB>tokens`, tokens space-separated phone symbols (vocab) or ids.
+    An id outside the vocabulary is written as its number."""
+    lines = []
+    for sc, h in zip(scores, hyps):
+        toks = [vocab[i] if vocab is not None and 0 <= i < len(vocab) else str(i) for i in h]
+        lines.append('%.6f\t%s' % (sc, ' '.join(toks)))
+    return '\n'.join(lines) + '\n'
+
+
+class Transcriber(BaseSolver):
+    """main.py --transcribe-wav-dir: the .wav files of a directory, sorted by name, in batches of --batch-size -> clean mel on the device
+    (AudioConverter.extract_batch without noise or stretch) -> VQVAE.transcribe (speech encoder, codebook or ASR postnet, CTC prefix
+    beam search) -> <logdir>/<name>.phn with --top-paths lines `score<TAB>tokens`.  Without --load the synthetic weights are used."""
+
+    def load_data(self):
+        from .audio import load_audio_transform
+        wav_dir = self.paras.transcribe_wav_dir
+        self.files = sorted(f for f in os.listdir(wav_dir) if f.lower().endswith('.wav'))
+        if not self.files:
+            raise ValueError('--transcribe-wav-dir %s: no .wav files' % wav_dir)
+        self.audio_converter = load_audio_transform(**self.config['data']['audio'])
+        if self.audio_converter.n_mels != self.n_mels:
+            raise ValueError('--transcribe-wav-dir: data.audio has %d mels, the model %d' % (self.audio_converter.n_mels, self.n_mels))
+        vocab = getattr(self.paras, 'vocab', None)
+        self.vocab = read_vocab(vocab) if vocab else None
+        return self
+
+    def set_model(self):
+        self.model = self._build_model().eval()
+        if not self.load_ckpt():
+            from .synthetic import load_synthetic
+            load_synthetic(self.model, seed=getattr(self.paras, 'seed', 0) + 1234)
+        return self
+
+    def transcribe_batch(self, waves):
+        """waves: 1-D waveforms on the device -> (hyp, hyp_len, score) as numpy arrays in the order of `waves`"""
+        from .audio import WaveBatch, SNR_OFF
+        wb = WaveBatch(waves)
+        mel, _, _ = self.audio_converter.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
+        frames = 1 + wb.lens // self.audio_converter.hop_length
+        hyp, hyp_len, score = self.model.transcribe(mel, frames, int(self.paras.beam_width), int(self.paras.top_paths),
+                                                    source=self.paras.asr_output)
+        back = np.empty_like(wb.order)
+        back[wb.order] = np.arange(len(wb.order))                   # sorted position of the i-th given utterance
+        return hyp.cpu().numpy()[back], hyp_len.cpu().numpy()[back], score.cpu().numpy()[back]
+
+    def exec(self):
+        os.makedirs(self.logdir, exist_ok=True)
+        B = int(self.paras.batch_size)
+        t0, n = time.perf_counter(), 0
+        wav_dir = self.paras.transcribe_wav_dir
+        for i in range(0, len(self.files), B):
+            names = self.files[i:i + B]
+            waves = [self.audio_converter.load(os.path.join(wav_dir, f))[0].to(self.device) for f in names]
+            hyp, hyp_len, score = self.transcribe_batch(waves)
+            for f, h, hl, sc in zip(names, hyp, hyp_len, score):
+                with open(os.path.join(self.logdir, os.path.splitext(f)[0] + '.phn'), 'w') as out:
+                    out.write(format_phn(sc.tolist(), [h[k, :hl[k]].tolist() for k in range(len(hl))], self.vocab))
+                n += 1
+        self.verbose('Transcribed %d files (beam %d, %d paths, %s posteriors) into %s, %.2f s'
+                     % (n, self.paras.beam_width, self.paras.top_paths, self.paras.asr_output, self.logdir, time.perf_counter() - t0))
+        return n
+
+
 class LazyStats(dict):
     """step statistics whose device scalars become Python floats when they are READ (st['loss'], st.items(), ...): a training loop
     that only logs every n-th step never waits for the GPU in between (TtsTrainer.async_stats)"""

@@ -121,6 +121,36 @@ class VQVAE(nn.Module):
             unpair_prob = unpair_latent = unpair_latent_len = None
         return pair_prob, pair_latent, unpair_prob, unpair_latent, unpair_latent_len, paired_post_prob, rest
 
+    def encoder_lengths(self, mel_lengths):
+        """frames of the encoder output for mel_lengths input frames: each conv layer's out_len in turn (the LSTMs keep the length)"""
+        t = torch.as_tensor(mel_lengths, dtype=torch.int64)
+        for l in range(self.asr.layers):
+            t = getattr(self.asr, 'layer' + str(l)).out_len(t)
+        return t
+
+    def transcribe(self, mel, mel_lengths, beam_width=16, top_paths=1, source='code'):
+        """CTC prefix beam search of the speech encoder's posteriors, in eval mode without gradients (the mode is restored after).
+        mel (B, T, n_mels) padded batch on the device, mel_lengths its valid frames per utterance (host integers).  source 'code':
+        the codebook posteriors of speech_to_text (probabilities, searched as log(p + 1e-10)); 'post': the ASRPostnet's log-posteriors
+        (refused when the model has no postnet).  The encoder runs on the padded batch, as the reference's validate does, so its
+        BiLSTM sees the padding frames; the search reads only each utterance's own encoder frames (encoder_lengths).
+        -> (hyp (B, top_paths, T') int64, hyp_len (B, top_paths) int32, score (B, top_paths) float32) device tensors, best first."""
+        from .ctc_decode import beam_search
+        if source not in ('code', 'post'):
+            raise ValueError("transcribe: source must be 'code' or 'post' (got %r)" % (source,))
+        if source == 'post' and not self.use_asr_postnet:
+            raise ValueError("transcribe: source 'post' needs an ASRPostnet (model.asr_postnet_weight > 0)")
+        lengths = self.encoder_lengths(mel_lengths)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                p_code, _, _, _, _, post, _ = self.speech_to_text(paired_mel=mel, unpaired_mel=None)
+                prob = post if source == 'post' else p_code
+                return beam_search(prob, lengths.clamp(0, prob.shape[1]), beam_width, top_paths, log_input=source == 'post')
+        finally:
+            self.train(was_training)
+
     def text_to_speech(self, paired_text, paired_sid, unpaired_sid, unpaired_latent, unpaired_text, unpaired_latent_len,
                        paired_teacher, unpaired_teacher, tf_rate, _masks=None):
         """same contract and return tuple as the reference (:143-207); `_masks` (tests only) = explicit dropout masks"""
