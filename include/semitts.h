@@ -1107,6 +1107,34 @@ int st_ctc_beam_search(const float* prob, int B, int T, int V, const int32_t* le
                        int log_input, float eps, int64_t* hyp /* (B, N, T), 0-padded */, int32_t* hyp_len /* (B, N) */,
                        float* score /* (B, N) */, void* ws, void* stream);
 
+/* CTC forced alignment: the single most probable CTC alignment of a transcript (Viterbi over the blank-expanded targets), its
+ * log-probability, the label of every frame and the frame span of every target token.  (The reference has no aligner: its AudioConverter
+ * reads phone boundaries "found by MFA" from a segment_file, src/audio.py:310-327.)
+ * lp[t][v] = log(prob[b,t,v] + eps) in fp32 when log_input == 0, prob[b,t,v] itself otherwise.  Utterance b reads frames [0, lengths[b])
+ * (lengths (B) int32 on the device, NULL = all T; clamped to [0, T]); nothing beyond is read for its value.
+ * Targets: the entries of text[b, 0 .. text_lengths[b]) (int32 on the device, NULL = all L; clamped to [0, L]) that are not `blank`, in
+ * order -- with blank = 0 and text_lengths = NULL the targets st_ctc_loss trains on.  S targets give the states
+ * ext = [blank, y0, blank, y1, ..., blank], n = 2 S + 1.
+ * Start: a[0] = lp[0][blank], a[1] = lp[0][y0], the rest -inf.  Step: a'[s] = best + lp[t][ext[s]] (one fp32 addition), best the maximum of
+ * a[s], a[s-1] and -- only when ext[s] != blank and ext[s] != ext[s-2] -- a[s-2].  Ties: the stay wins, then s-1, then s-2 (a candidate
+ * replaces the best only when strictly greater).  End: the larger of a[n-1] and a[n-2], n-1 on a tie; the path is traced back from there.
+ * Outputs: score (B) the end value; path (B, T) int32, path[b,t] = ext[state_t] for t < length, -1 beyond; tok_start / tok_end (B, L) int32:
+ * the first frame and one past the last frame spent in state 2k+1, -1 for k >= S.
+ * Without raising: S = 0 gives the all-blank path (score sum of lp[t][blank]; 0 when the length is 0 too).  A target outside [0, V): score
+ * NaN.  Otherwise, infeasible (length < S + the number of adjacent equal targets; any S > 0 at length 0): score -inf.  Otherwise, a NaN among
+ * the log-probabilities of the valid frames in the columns of ext: score NaN.  In all three cases path and the spans are -1 everywhere.
+ * Integers and fp32 max / add only, no float atomics: an utterance's result depends on it alone (bitwise repeatable, independent of B and of
+ * what lies past its lengths).  One launch, no host read.
+ * Limits (-22 past them): B >= 1, 1 <= T <= 4096, 2 <= V <= 10240, 1 <= L <= 1024, 0 <= blank < V.
+ * ws: st_ctc_align_workspace_bytes(B, T, L) bytes, no initialisation needed -- 0 (ws may be NULL) when the 2-bit back-pointers of a
+ * (T, 2 L + 1) trellis fit LDS, which the shipped shapes do. */
+size_t st_ctc_align_workspace_bytes(int B, int T, int L);
+int st_ctc_forced_align(const float* prob, int B, int T, int V, const int32_t* lengths /* NULL = all T */,
+                        const int64_t* text /* (B, L) */, int L, const int32_t* text_lengths /* NULL = all L */,
+                        int blank, int log_input, float eps,
+                        float* score /* (B) */, int32_t* path /* (B, T) */,
+                        int32_t* tok_start /* (B, L) */, int32_t* tok_end /* (B, L) */, void* ws, void* stream);
+
 /* The trainer's scalar arithmetic on loss values as one launch (ref: bin/train_vqvae.py:208-233: total_loss = asr_weight * asr_loss +
  * tts_weight * (mel_loss + linear_loss) + unpair_speech_weight * ... -- a chain of one-element torch kernels there):
  * *outs[j] = sum_i W[j * n + i] * *xs[i] for j < m (m <= 4 outputs, n <= ST_SCALAR_MAX terms, W on the host; in rows j > 0 a zero weight means the term is not a member of that sum).

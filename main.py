@@ -15,7 +15,10 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --gen-specgram [--load ckpt.pth] [--frames 256 --batch-size 32]
     python main.py --config config/supervised.yaml --tts-only --max-step 20 [--frames 256 --batch-size 32]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR [--beam-width 16 --top-paths 1 --vocab FILE]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --align-wav-dir DIR [--phn-dir DIR2 --vocab FILE]
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber).
+`--align-wav-dir` (not a mode of the reference either) aligns .wav files to their .phn transcripts by CTC forced alignment
+(solver.Aligner): <file>.ali per utterance and segments.csv in the layout of the reference's segment_file.
 """
 import argparse
 import random
@@ -63,10 +66,14 @@ parser.add_argument('--transcribe-wav-dir', default=None, type=str, help='transc
                     'batched by --batch-size) by CTC prefix beam search into <logdir>/<name>/<file>.phn: --top-paths lines of score<TAB>tokens')
 parser.add_argument('--beam-width', default=16, type=int, help='--transcribe-wav-dir: beam width (1 .. 128)')
 parser.add_argument('--top-paths', default=1, type=int, help='--transcribe-wav-dir: paths written per file (1 .. --beam-width)')
-parser.add_argument('--vocab', default=None, type=str, help='--transcribe-wav-dir: phone list, one per line (id = 3 + line index); '
+parser.add_argument('--vocab', default=None, type=str, help='--transcribe-wav-dir / --align-wav-dir: phone list, one per line (id = 3 + line index); '
                     'without it the .phn files hold ids')
-parser.add_argument('--asr-output', default='code', choices=('code', 'post'), help='--transcribe-wav-dir: search the codebook posteriors '
-                    '(code) or the ASR postnet log-posteriors (post)')
+parser.add_argument('--asr-output', default='code', choices=('code', 'post'), help='--transcribe-wav-dir / --align-wav-dir: use the codebook '
+                    'posteriors (code) or the ASR postnet log-posteriors (post)')
+parser.add_argument('--align-wav-dir', default=None, type=str, help='align the .wav files of this directory (sorted by name, batched by '
+                    '--batch-size) to their transcripts <name>.phn by CTC forced alignment: <logdir>/<name>/<file>.ali (one line per token: '
+                    'symbol, start / end frame, start / end second) and segments.csv (file,seg); reads --vocab and --asr-output')
+parser.add_argument('--phn-dir', default=None, type=str, help='--align-wav-dir: directory of the .phn transcripts (default: the .wav directory)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -106,6 +113,14 @@ def parse_args(argv=None):
             parser.error('--transcribe-wav-dir does not combine with --dev-batches')
         if not (1 <= paras.top_paths <= paras.beam_width <= 128):
             parser.error('--transcribe-wav-dir needs 1 <= --top-paths <= --beam-width <= 128')
+    if paras.align_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir'):
+            if getattr(paras, flag):
+                parser.error('--align-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--align-wav-dir does not combine with --dev-batches')
+    elif paras.phn_dir is not None:
+        parser.error('--phn-dir names the transcripts of --align-wav-dir; it needs that flag')
     if paras.verbose:
         for flag in IGNORED_FLAGS:
             if flag == 'gen_wav' and paras.gen_specgram:
@@ -135,6 +150,9 @@ def main(argv=None):
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
     if paras.transcribe_wav_dir is not None:
         from semi_tts_amd.solver import Transcriber as Solver
+        mode = 'test'
+    elif paras.align_wav_dir is not None:
+        from semi_tts_amd.solver import Aligner as Solver
         mode = 'test'
     elif paras.gen_specgram:
         from semi_tts_amd.solver import SpecgramGenerator as Solver

@@ -951,6 +951,65 @@ def ctc_beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log
     return hyp, hyp_len, score
 
 
+CA_MAX_T, CA_MIN_V, CA_MAX_V, CA_MAX_L = 4096, 2, 10240, 1024          # st_ctc_forced_align's limits
+
+
+def _ca_lengths(name, x, B, hi, dev):
+    """lengths / text_lengths of ctc_forced_align: None, or (B,) integers -- a host tensor / sequence is checked against [0, hi] here, a
+    device tensor is taken as it is (the kernel clamps it) -> int32 device tensor or None"""
+    if x is None:
+        return None
+    if torch.is_tensor(x) and x.is_cuda:
+        if x.device != dev or x.shape != (B,) or x.dtype.is_floating_point or x.dtype == torch.bool:
+            raise ValueError('ctc_forced_align: %s must be (B,) integers on the device of prob (got %s %s on %s)'
+                             % (name, tuple(x.shape), x.dtype, x.device))
+    else:
+        host = np.asarray(x.cpu() if torch.is_tensor(x) else x)
+        if host.shape != (B,) or host.dtype.kind not in 'iu' or (host < 0).any() or (host > hi).any():
+            raise ValueError('ctc_forced_align: %s must be %d integers in [0, %d] (got %s)' % (name, B, hi, host.tolist()))
+    return torch.as_tensor(x).to(dev, torch.int32).contiguous()
+
+
+def ctc_forced_align(prob, text, lengths=None, text_lengths=None, blank=0, log_input=False, eps=1e-10):
+    """CTC forced alignment (Viterbi) of text (B, L) int64 to prob (B, T, V) fp32 on one GPU (see st_ctc_forced_align).  lengths /
+    text_lengths: None (all T frames / all L entries), or (B,) integers -- a host tensor / sequence is checked against [0, T] / [0, L]
+    here, a device tensor is taken as it is (the kernel clamps it).  The targets are the non-blank entries of each row of text.
+    -> (score (B,) float32, path (B, T) int32, tok_start (B, L) int32, tok_end (B, L) int32) device tensors; one launch, no host read.
+    Anything the kernel would refuse raises ValueError before the device is touched."""
+    if not torch.is_tensor(prob) or not prob.is_cuda or prob.dim() != 3 or prob.dtype != torch.float32:
+        raise ValueError('ctc_forced_align: prob must be a (B, T, V) float32 GPU tensor (got %s)'
+                         % ('%s %s on %s' % (tuple(prob.shape), prob.dtype, prob.device) if torch.is_tensor(prob) else type(prob).__name__))
+    dev = prob.device
+    if not torch.is_tensor(text) or not text.is_cuda or text.device != dev or text.dim() != 2 or text.dtype != torch.int64:
+        raise ValueError('ctc_forced_align: text must be a (B, L) int64 tensor on the device of prob (got %s)'
+                         % ('%s %s on %s' % (tuple(text.shape), text.dtype, text.device) if torch.is_tensor(text) else type(text).__name__))
+    B, T, V = prob.shape
+    L, blank = text.shape[1], int(blank)
+    if text.shape[0] != B:
+        raise ValueError('ctc_forced_align: %d utterances of prob, %d of text' % (B, text.shape[0]))
+    if B < 1 or not (1 <= T <= CA_MAX_T and CA_MIN_V <= V <= CA_MAX_V and 1 <= L <= CA_MAX_L):
+        raise ValueError('ctc_forced_align: B=%d, T=%d, V=%d, L=%d outside B >= 1, 1 <= T <= %d, %d <= V <= %d, 1 <= L <= %d'
+                         % (B, T, V, L, CA_MAX_T, CA_MIN_V, CA_MAX_V, CA_MAX_L))
+    if not 0 <= blank < V:
+        raise ValueError('ctc_forced_align: blank %d outside [0, %d)' % (blank, V))
+    if not eps >= 0.0:
+        raise ValueError('ctc_forced_align: eps must be >= 0 (got %r)' % (eps,))
+    lengths = _ca_lengths('lengths', lengths, B, T, dev)
+    text_lengths = _ca_lengths('text_lengths', text_lengths, B, L, dev)
+    lib = _lib.load()
+    prob, text = prob.contiguous(), text.contiguous()
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    path = torch.empty(B, T, device=dev, dtype=torch.int32)
+    tok_start = torch.empty(B, L, device=dev, dtype=torch.int32)
+    tok_end = torch.empty(B, L, device=dev, dtype=torch.int32)
+    nbytes = int(lib.st_ctc_align_workspace_bytes(B, T, L))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    check(lib.st_ctc_forced_align(_p(prob), B, T, V, _p(lengths, torch.int32), _p(text, torch.int64), L, _p(text_lengths, torch.int32),
+                                  blank, 1 if log_input else 0, float(eps), _p(score), _p(path, torch.int32), _p(tok_start, torch.int32),
+                                  _p(tok_end, torch.int32), _p(ws, torch.uint8), stream_handle()), 'st_ctc_forced_align')
+    return score, path, tok_start, tok_end
+
+
 def hyp_edit_distance(hyp, hyp_len, text, ignore):
     """edit distance of transcripts that are already collapsed (a beam search's) to `text`, per utterance (see st_hyp_edit_distance):
     hyp (B, Lh) int64 with hyp_len (B,) int32 tokens each, text (B, L) int64, ignore: the ids dropped from both sides.  -> (dist,

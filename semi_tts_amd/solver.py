@@ -185,15 +185,18 @@ class Transcriber(BaseSolver):
     (AudioConverter.extract_batch without noise or stretch) -> VQVAE.transcribe (speech encoder, codebook or ASR postnet, CTC prefix
     beam search) -> <logdir>/<name>.phn with --top-paths lines `score<TAB>tokens`.  Without --load the synthetic weights are used."""
 
+    WAV_DIR_FLAG = 'transcribe_wav_dir'          # the attribute of paras that names the .wav directory
+
     def load_data(self):
         from .audio import load_audio_transform
-        wav_dir = self.paras.transcribe_wav_dir
+        flag = '--' + self.WAV_DIR_FLAG.replace('_', '-')
+        self.wav_dir = wav_dir = getattr(self.paras, self.WAV_DIR_FLAG)
         self.files = sorted(f for f in os.listdir(wav_dir) if f.lower().endswith('.wav'))
         if not self.files:
-            raise ValueError('--transcribe-wav-dir %s: no .wav files' % wav_dir)
+            raise ValueError('%s %s: no .wav files' % (flag, wav_dir))
         self.audio_converter = load_audio_transform(**self.config['data']['audio'])
         if self.audio_converter.n_mels != self.n_mels:
-            raise ValueError('--transcribe-wav-dir: data.audio has %d mels, the model %d' % (self.audio_converter.n_mels, self.n_mels))
+            raise ValueError('%s: data.audio has %d mels, the model %d' % (flag, self.audio_converter.n_mels, self.n_mels))
         vocab = getattr(self.paras, 'vocab', None)
         self.vocab = read_vocab(vocab) if vocab else None
         return self
@@ -232,6 +235,71 @@ class Transcriber(BaseSolver):
                 n += 1
         self.verbose('Transcribed %d files (beam %d, %d paths, %s posteriors) into %s, %.2f s'
                      % (n, self.paras.beam_width, self.paras.top_paths, self.paras.asr_output, self.logdir, time.perf_counter() - t0))
+        return n
+
+
+class Aligner(Transcriber):
+    """main.py --align-wav-dir: the .wav files of a directory (sorted by name, batches of --batch-size) and their transcripts
+    <name>.phn from --phn-dir (default: the same directory; ctc_align.read_phn) -> clean mel on the device -> VQVAE.align (speech
+    encoder, codebook or ASR postnet, CTC forced alignment) -> <logdir>/<name>/<file>.ali (ctc_align.format_ali) and segments.csv in
+    the reference's segment_file layout (ctc_align.segment_row).  Every transcript is read in load_data: a missing or malformed one
+    stops the run before anything is written.  Without --load the synthetic weights are used."""
+
+    WAV_DIR_FLAG = 'align_wav_dir'
+
+    def load_data(self):
+        from .ctc_align import read_phn
+        super().load_data()
+        phn_dir = getattr(self.paras, 'phn_dir', None) or self.wav_dir
+        self.transcripts = [read_phn(os.path.join(phn_dir, os.path.splitext(f)[0] + '.phn'), self.vocab) for f in self.files]
+        return self
+
+    def align_batch(self, waves, transcripts):
+        """waves: 1-D waveforms on the device, transcripts: their id lists -> (score, tok_start, tok_end, encoder frames) as numpy
+        arrays in the order of `waves`"""
+        from .audio import WaveBatch, SNR_OFF
+        wb = WaveBatch(waves)
+        mel, _, _ = self.audio_converter.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
+        frames = 1 + wb.lens // self.audio_converter.hop_length
+        L = max(1, max(len(t) for t in transcripts))
+        text = np.zeros((len(waves), L), np.int64)
+        tl = np.zeros(len(waves), np.int32)
+        for row, k in enumerate(wb.order):                          # the batch is sorted by length: row `row` is waves[k]
+            text[row, :len(transcripts[k])], tl[row] = transcripts[k], len(transcripts[k])
+        score, path, ts, te = self.model.align(mel, frames, torch.from_numpy(text).to(self.device), tl.tolist(), source=self.paras.asr_output)
+        t_enc = self.model.encoder_lengths(frames).clamp(0, path.shape[1]).numpy()
+        back = np.empty_like(wb.order)
+        back[wb.order] = np.arange(len(wb.order))                   # sorted position of the i-th given utterance
+        return score.cpu().numpy()[back], ts.cpu().numpy()[back], te.cpu().numpy()[back], t_enc[back]
+
+    def exec(self):
+        from .ctc_align import format_ali, segment_row, SEGMENTS_HEADER
+        os.makedirs(self.logdir, exist_ok=True)
+        B = int(self.paras.batch_size)
+        t0, n, n_bad = time.perf_counter(), 0, 0
+        frame_s = self.model.time_reduce_factor * self.audio_converter.hop_length / self.audio_converter.sr
+        rows = [SEGMENTS_HEADER]
+        for i in range(0, len(self.files), B):
+            names, trs = self.files[i:i + B], self.transcripts[i:i + B]
+            waves = [self.audio_converter.load(os.path.join(self.wav_dir, f))[0].to(self.device) for f in names]
+            score, ts, te, t_enc = self.align_batch(waves, trs)
+            for f, tr, sc, a, b, T in zip(names, trs, score.tolist(), ts, te, t_enc.tolist()):
+                targets = [x for x in tr if x != 0]                 # id 0 is the blank: not a target
+                S = len(targets)
+                with open(os.path.join(self.logdir, os.path.splitext(f)[0] + '.ali'), 'w') as out:
+                    out.write(format_ali(sc, T, frame_s, targets, a[:S].tolist(), b[:S].tolist(), self.vocab))
+                if sc == sc and sc != float('-inf'):
+                    row = segment_row(f, a[:S].tolist(), T, frame_s)
+                    if row is not None:
+                        rows.append(row)
+                else:
+                    n_bad += 1
+                    print('[WARNING] %s: no alignment (score %s: %d tokens, %d encoder frames)' % (f, sc, S, T))
+                n += 1
+        with open(os.path.join(self.logdir, 'segments.csv'), 'w') as out:
+            out.write('\n'.join(rows) + '\n')
+        self.verbose('Aligned %d files (%d without an alignment, %s posteriors) into %s, %.2f s'
+                     % (n, n_bad, self.paras.asr_output, self.logdir, time.perf_counter() - t0))
         return n
 
 

@@ -151,6 +151,30 @@ class VQVAE(nn.Module):
         finally:
             self.train(was_training)
 
+    def align(self, mel, mel_lengths, text, text_lengths=None, source='code'):
+        """CTC forced alignment of transcripts to the speech encoder's posteriors, in eval mode without gradients (the mode is restored
+        after).  mel (B, T, n_mels) padded batch on the device, mel_lengths its valid frames per utterance (host integers); text (B, L)
+        int64 on the device, its non-blank (non-zero) entries the targets, text_lengths as in ctc_align.forced_align.  source 'code':
+        the codebook posteriors of speech_to_text (probabilities, scored as log(p + 1e-10)); 'post': the ASRPostnet's log-posteriors
+        (refused when the model has no postnet).  The encoder runs on the padded batch, as in transcribe, so its BiLSTM sees the
+        padding frames; the aligner reads only each utterance's own encoder frames (encoder_lengths).
+        -> (score (B,) float32, path (B, T') int32, tok_start (B, L) int32, tok_end (B, L) int32) device tensors, in encoder frames."""
+        from .ctc_align import forced_align
+        if source not in ('code', 'post'):
+            raise ValueError("align: source must be 'code' or 'post' (got %r)" % (source,))
+        if source == 'post' and not self.use_asr_postnet:
+            raise ValueError("align: source 'post' needs an ASRPostnet (model.asr_postnet_weight > 0)")
+        lengths = self.encoder_lengths(mel_lengths)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                p_code, _, _, _, _, post, _ = self.speech_to_text(paired_mel=mel, unpaired_mel=None)
+                prob = post if source == 'post' else p_code
+                return forced_align(prob, text, lengths.clamp(0, prob.shape[1]), text_lengths, log_input=source == 'post')
+        finally:
+            self.train(was_training)
+
     def text_to_speech(self, paired_text, paired_sid, unpaired_sid, unpaired_latent, unpaired_text, unpaired_latent_len,
                        paired_teacher, unpaired_teacher, tf_rate, _masks=None):
         """same contract and return tuple as the reference (:143-207); `_masks` (tests only) = explicit dropout masks"""
