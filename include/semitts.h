@@ -1106,6 +1106,22 @@ size_t st_ctc_beam_workspace_bytes(int B, int T, int W);
 int st_ctc_beam_search(const float* prob, int B, int T, int V, const int32_t* lengths /* NULL = all T */, int W, int N, int blank,
                        int log_input, float eps, int64_t* hyp /* (B, N, T), 0-padded */, int32_t* hyp_len /* (B, N) */,
                        float* score /* (B, N) */, void* ws, void* stream);
+/* st_ctc_beam_search_lm: the same search with an n-gram table fused into the candidate scoring.  Everything above holds (candidates,
+ * merge rule, order and tie-break, outputs, NaN rule, limits, workspace, one launch, no host read, no float atomics, result independent of
+ * B), with one addition.  bonus (V^(order-1), V) fp32 on the device, row-major: row r = sum_i ctx[i] V^(order-2-i) of the last order-1
+ * symbols ctx (the reference's NgramPrior layout, src/lm.py:233-290), one row for order 1.  Every prefix carries its row: the empty prefix
+ * row 0 when order == 1, else the row of (0, ..., 0, bos) -- NgramPrior's start, zeros then the start id.  Extending prefix A by symbol c
+ * adds bonus[row(A) V + c] to the extension's log-probability -- one fp32 addition, after lp[c] -- and the new prefix has row
+ * (row(A) V + c) mod V^(order-1) (0 for order 1).  Stays add nothing.  The bonus is a function of the prefix alone, so an extension merged
+ * into a stay carries the same total as that stay, and a prefix scores log(its CTC prefix probability) + the sum of its extension bonuses:
+ * that fused score is what `score` reports.  The column bonus[:, blank] is never read.  -inf entries are legal (a forbidden transition:
+ * the candidate exists with score -inf, as structurally impossible candidates do); NaN and +inf are outside the contract and the table is
+ * NOT checked here (the Python layers refuse them for host arrays; a device table is trusted).
+ * Extra limits (-22 past them): 1 <= order <= 4, V^order <= 2^26 table elements, 0 <= bos < V, bonus != NULL. */
+int st_ctc_beam_search_lm(const float* prob, int B, int T, int V, const int32_t* lengths /* NULL = all T */, int W, int N, int blank,
+                          int log_input, float eps, const float* bonus /* (V^(order-1), V) */, int order, int bos,
+                          int64_t* hyp /* (B, N, T), 0-padded */, int32_t* hyp_len /* (B, N) */, float* score /* (B, N) */, void* ws,
+                          void* stream);
 
 /* CTC forced alignment: the single most probable CTC alignment of a transcript (Viterbi over the blank-expanded targets), its
  * log-probability, the label of every frame and the frame span of every target token.  (The reference has no aligner: its AudioConverter

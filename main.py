@@ -16,7 +16,11 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --tts-only --max-step 20 [--frames 256 --batch-size 32]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR [--beam-width 16 --top-paths 1 --vocab FILE]
     python main.py --config config/semi-single-spkr-paired-data.yaml --align-wav-dir DIR [--phn-dir DIR2 --vocab FILE]
-`--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber).
+    python main.py --config config/semi-single-spkr-paired-data.yaml --build-lm-phn-dir DIR --lm-order 2 --lm FILE [--lm-smooth 1 --vocab F]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --lm FILE [--lm-weight 0.5 --ins-bonus 0]
+`--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
+`--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
+(semi_tts_amd/ngram.py: a plain .npy of shape (V^(order-1), V) in the layout of the reference's NgramPrior, src/lm.py:233-290) on the host.
 `--align-wav-dir` (not a mode of the reference either) aligns .wav files to their .phn transcripts by CTC forced alignment
 (solver.Aligner): <file>.ali per utterance and segments.csv in the layout of the reference's segment_file.
 """
@@ -74,6 +78,15 @@ parser.add_argument('--align-wav-dir', default=None, type=str, help='align the .
                     '--batch-size) to their transcripts <name>.phn by CTC forced alignment: <logdir>/<name>/<file>.ali (one line per token: '
                     'symbol, start / end frame, start / end second) and segments.csv (file,seg); reads --vocab and --asr-output')
 parser.add_argument('--phn-dir', default=None, type=str, help='--align-wav-dir: directory of the .phn transcripts (default: the .wav directory)')
+parser.add_argument('--lm', default=None, type=str, help='--transcribe-wav-dir: fuse this phone n-gram table (.npy, (V^(order-1), V) '
+                    'probabilities, contexts starting at (0, ..., 0, 1)) into the beam search; --build-lm-phn-dir: the table to write')
+parser.add_argument('--lm-weight', default=None, type=float, help='--lm with --transcribe-wav-dir: weight of log P(phone | context) per '
+                    'new phone (default 0.5)')
+parser.add_argument('--ins-bonus', default=None, type=float, help='--lm with --transcribe-wav-dir: constant added per new phone (default 0)')
+parser.add_argument('--build-lm-phn-dir', default=None, type=str, help='count an n-gram table of order --lm-order from the .phn '
+                    'transcripts of this directory (ids or --vocab symbols, id 0 skipped) and write it to --lm; no GPU, no other mode')
+parser.add_argument('--lm-order', default=None, type=int, help='--build-lm-phn-dir: order of the table (1 .. 4)')
+parser.add_argument('--lm-smooth', default=None, type=float, help='--build-lm-phn-dir: add-K smoothing over the non-blank phones (default 1)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -121,6 +134,37 @@ def parse_args(argv=None):
             parser.error('--align-wav-dir does not combine with --dev-batches')
     elif paras.phn_dir is not None:
         parser.error('--phn-dir names the transcripts of --align-wav-dir; it needs that flag')
+    if paras.build_lm_phn_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir'):
+            if getattr(paras, flag):
+                parser.error('--build-lm-phn-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--build-lm-phn-dir does not combine with --dev-batches')
+        if paras.lm is None or paras.lm_order is None:
+            parser.error('--build-lm-phn-dir needs --lm FILE (the table to write) and --lm-order N')
+        if not 1 <= paras.lm_order <= 4:
+            parser.error('--build-lm-phn-dir needs 1 <= --lm-order <= 4')
+        if paras.lm_smooth is not None and not (0.0 <= paras.lm_smooth < float('inf')):
+            parser.error('--lm-smooth must be finite and >= 0')
+        if paras.lm_weight is not None or paras.ins_bonus is not None:
+            parser.error('--lm-weight and --ins-bonus belong to --transcribe-wav-dir --lm; --build-lm-phn-dir writes probabilities')
+    else:
+        if paras.lm_order is not None or paras.lm_smooth is not None:
+            parser.error('--lm-order and --lm-smooth belong to --build-lm-phn-dir; they need that flag')
+        if paras.lm is not None and paras.transcribe_wav_dir is None:
+            parser.error('--lm names the n-gram table of --transcribe-wav-dir or --build-lm-phn-dir; it needs one of them')
+        if paras.lm is None and (paras.lm_weight is not None or paras.ins_bonus is not None):
+            parser.error('--lm-weight and --ins-bonus weight the table of --lm; they need that flag')
+        for flag in ('lm_weight', 'ins_bonus'):
+            v = getattr(paras, flag)
+            if v is not None and not float('-inf') < v < float('inf'):
+                parser.error('--%s must be finite' % flag.replace('_', '-'))
+    if paras.lm_weight is None:
+        paras.lm_weight = 0.5
+    if paras.ins_bonus is None:
+        paras.ins_bonus = 0.0
+    if paras.lm_smooth is None:
+        paras.lm_smooth = 1.0
     if paras.verbose:
         for flag in IGNORED_FLAGS:
             if flag == 'gen_wav' and paras.gen_specgram:
@@ -134,6 +178,12 @@ def parse_args(argv=None):
 
 def main(argv=None):
     paras = parse_args(argv)
+    if paras.build_lm_phn_dir is not None:                  # host only: no config, no seed, no device
+        from semi_tts_amd.ngram import build_lm_from_phn_dir
+        from semi_tts_amd.solver import read_vocab
+        print(build_lm_from_phn_dir(paras.build_lm_phn_dir, paras.lm, paras.lm_order, smooth=paras.lm_smooth,
+                                    vocab=read_vocab(paras.vocab) if paras.vocab else None)['summary'])
+        return
     config = yaml.load(open(paras.config, 'r'), Loader=yaml.FullLoader)
     if paras.batch_size is None:
         paras.batch_size = config['data']['corpus'].get('batch_size', 8)

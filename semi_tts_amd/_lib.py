@@ -211,6 +211,7 @@ SIGNATURES = {
     'st_hyp_edit_distance': [P, P, I, I, P, I, P, I, P, P, P],
     'st_ctc_beam_workspace_bytes': [I, I, I],
     'st_ctc_beam_search': [P, I, I, I, P, I, I, I, I, F, P, P, P, P, P],
+    'st_ctc_beam_search_lm': [P, I, I, I, P, I, I, I, I, F, P, I, I, P, P, P, P, P],
     'st_ctc_align_workspace_bytes': [I, I, I],
     'st_ctc_forced_align': [P, I, I, I, P, P, I, P, I, I, F, P, P, P, P, P, P],
     'st_scalar_combine': [P, I, P, I, P, P],

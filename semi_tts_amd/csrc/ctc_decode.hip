@@ -12,12 +12,20 @@
 //      prefixes symbol by symbol through the prefix tree (rare, and it stops at the first difference or the first common node).
 // Every prefix that ever enters the beam as an extension gets a node (parent node, symbol) in the workspace; the N outputs are
 // read back along those chains.  Only integer LDS atomics (histogram counts, bitmap bits), no float atomics: results are bitwise repeatable.
+//
+// LM fusion (st_ctc_beam_search_lm, the LM = true instantiation): every slot carries the row `ctx` of its n-gram context; an extension of
+// slot s by c scores (.. + lp[c]) + bonus[ctx[s] V + c] in the three places an extension's score is formed (the merge of step 2, the keys
+// of step 3, the new entry of step 4), always through ext_score(), so the three agree bit for bit.  The table is read through L2 where
+// the score is formed: copying the nb live rows into LDS once a frame was built and measured, and was worth 1 % at most.
+// LM = false compiles to the kernel without any of it.
+#include <type_traits>
 #include "st_common.h"
 
 namespace {
 
 constexpr int CB_NT = 256, CB_MAX_T = 4096, CB_MAX_V = 1024, CB_MIN_V = 2, CB_MAX_W = 128;
 constexpr int CB_MASK_WORDS = CB_MAX_W * CB_MAX_V / 32;
+constexpr int CB_MAX_ORDER = 4, CB_MAX_TABLE = 1 << 26;   // LM fusion: n-gram order, elements of the (V^(order-1), V) table
 
 __device__ __forceinline__ float cb_lae(float a, float b) {     // log(exp a + exp b); -inf, -inf -> -inf
     const float m = fmaxf(a, b), n = fminf(a, b);
@@ -53,11 +61,21 @@ struct CbBeam {                  // one beam (double-buffered in LDS)
     float pb[CB_MAX_W], pnb[CB_MAX_W];
     int last[CB_MAX_W], link[CB_MAX_W], node[CB_MAX_W], len[CB_MAX_W];
 };
+struct CbBeamLm : CbBeam {       // with LM fusion: the table row of each prefix's context
+    int ctx[CB_MAX_W];
+};
 
+// what the fused kernel takes on top (nothing for LM = false): bonus (ctx_mod, V) fp32, ctx_mod = V^(order-1); ctx0 the empty prefix's row
+template <bool LM> struct CbLmArgs {};
+template <> struct CbLmArgs<true> { const float* bonus; int ctx_mod, ctx0; };
+
+template <bool LM>
 __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict__ prob, int T, int V, const int32_t* __restrict__ lengths,
                                                          int W, int N, int blank, int log_input, float eps, int64_t* __restrict__ hyp,
-                                                         int32_t* __restrict__ hyp_len, float* __restrict__ score, int2* __restrict__ ws) {
-    __shared__ CbBeam bm[2];
+                                                         int32_t* __restrict__ hyp_len, float* __restrict__ score, int2* __restrict__ ws,
+                                                         CbLmArgs<LM> lm) {
+    using Beam = std::conditional_t<LM, CbBeamLm, CbBeam>;
+    __shared__ Beam bm[2];
     __shared__ float lp[CB_MAX_V];
     __shared__ float tot[CB_MAX_W];                       // score of each slot of the current beam
     __shared__ float cpb[CB_MAX_W], cpnb[CB_MAX_W];       // stay candidates (merges included)
@@ -76,14 +94,15 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
         bm[0].pb[0] = 0.0f; bm[0].pnb[0] = -INFINITY;
         bm[0].last[0] = -1; bm[0].link[0] = -1; bm[0].node[0] = 0; bm[0].len[0] = 0;
         tot[0] = 0.0f;
+        if constexpr (LM) bm[0].ctx[0] = lm.ctx0;
         s_nan = 0;
         nodes[0] = make_int2(-1, -1);
     }
     int nb = 1, cur = 0;
     __syncthreads();
     for (int t = 0; t < Tb; ++t) {
-        CbBeam& o = bm[cur];
-        CbBeam& n = bm[cur ^ 1];
+        Beam& o = bm[cur];
+        Beam& n = bm[cur ^ 1];
         // ---- 1. the frame's log-probabilities
         const float* row = prob + ((size_t)b * T + t) * V;
         for (int v = tid; v < V; v += CB_NT) {
@@ -95,13 +114,19 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
         for (int k = tid; k < (nb * V + 31) / 32; k += CB_NT) mask[k] = 0u;
         __syncthreads();
         if (s_nan) break;
+        // the score of slot s extended by c; with LM one more fp32 addition, after lp[c]
+        auto ext_score = [&](int s, int c) -> float {
+            const float e = (c == o.last[s] ? o.pb[s] : tot[s]) + lp[c];
+            if constexpr (LM) return e + lm.bonus[(size_t)o.ctx[s] * V + c];
+            else return e;
+        };
         // ---- 2. stays, with the merged extension A + last(B) of A = link(B)
         if (tid < nb) {
             const int s = tid, c = o.last[s], a = o.link[s];
             const float spb = tot[s] + lp[blank];
             float spnb = c >= 0 ? o.pnb[s] + lp[c] : -INFINITY;
             if (a >= 0) {
-                spnb = cb_lae(spnb, (c == o.last[a] ? o.pb[a] : tot[a]) + lp[c]);
+                spnb = cb_lae(spnb, ext_score(a, c));
                 const int bit = a * V + c;
                 atomicOr(&mask[bit >> 5], 1u << (bit & 31));
             }
@@ -116,7 +141,7 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
             const int j = i - nb, s = j / Vm, r = j - s * Vm, c = r < blank ? r : r + 1;
             const int bit = s * V + c;
             if (mask[bit >> 5] & (1u << (bit & 31))) return 0u;
-            return cb_key((c == o.last[s] ? o.pb[s] : tot[s]) + lp[c]);
+            return cb_key(ext_score(s, c));
         };
         // ---- 3a. how many candidates are real (M minus the merged ones), then the W-th key by radix select
         int n_real;
@@ -189,13 +214,15 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
             if (i < nb) {
                 n.pb[r] = cpb[i]; n.pnb[r] = cpnb[i];
                 n.last[r] = o.last[i]; n.node[r] = o.node[i]; n.len[r] = o.len[i];
+                if constexpr (LM) n.ctx[r] = o.ctx[i];
                 stay_slot[i] = r;
             } else {
                 const int j = i - nb, s = j / Vm, rr = j - s * Vm, c = rr < blank ? rr : rr + 1;
                 const int id = 1 + t * W + r;
                 n.pb[r] = -INFINITY;
-                n.pnb[r] = (c == o.last[s] ? o.pb[s] : tot[s]) + lp[c];
+                n.pnb[r] = ext_score(s, c);
                 n.last[r] = c; n.len[r] = o.len[s] + 1; n.node[r] = id;
+                if constexpr (LM) n.ctx[r] = (o.ctx[s] * V + c) % lm.ctx_mod;       // (< V^order <= 2^26: no overflow; order 1: always 0)
                 nodes[id] = make_int2(o.node[s], c);
             }
         }
@@ -230,7 +257,7 @@ __global__ __launch_bounds__(CB_NT) void ctc_beam_kernel(const float* __restrict
         __syncthreads();
     }
     // ---- outputs: path k < N along its node chain (thread k walks path k), 0-padded
-    const CbBeam& f = bm[cur];
+    const Beam& f = bm[cur];
     const bool nan = s_nan != 0;
     for (int k = 0; k < N; ++k) {
         const int L = (nan || k >= nb) ? 0 : f.len[k];
@@ -267,8 +294,30 @@ extern "C" int st_ctc_beam_search(const float* prob, int B, int T, int V, const 
     ST_CHECK_ARG(W >= 1 && W <= CB_MAX_W, "st_ctc_beam_search: beam width 1..%d (W=%d)", CB_MAX_W, W);
     ST_CHECK_ARG(N >= 1 && N <= W, "st_ctc_beam_search: 1 <= N <= W (N=%d, W=%d)", N, W);
     ST_CHECK_ARG(blank >= 0 && blank < V, "st_ctc_beam_search: blank %d outside [0, %d)", blank, V);
-    hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, prob, T, V, lengths, W, N, blank, log_input, eps, hyp,
-                       hyp_len, score, reinterpret_cast<int2*>(ws));
+    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, prob, T, V, lengths, W, N, blank, log_input, eps,
+                       hyp, hyp_len, score, reinterpret_cast<int2*>(ws), CbLmArgs<false>{});
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_ctc_beam_search_lm(const float* prob, int B, int T, int V, const int32_t* lengths, int W, int N, int blank, int log_input,
+                                     float eps, const float* bonus, int order, int bos, int64_t* hyp, int32_t* hyp_len, float* score, void* ws,
+                                     void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(prob && hyp && hyp_len && score && ws && B > 0, "st_ctc_beam_search_lm: bad arguments");
+    ST_CHECK_ARG(T >= 1 && T <= CB_MAX_T, "st_ctc_beam_search_lm: 1..%d frames (T=%d)", CB_MAX_T, T);
+    ST_CHECK_ARG(V >= CB_MIN_V && V <= CB_MAX_V, "st_ctc_beam_search_lm: %d..%d classes (V=%d)", CB_MIN_V, CB_MAX_V, V);
+    ST_CHECK_ARG(W >= 1 && W <= CB_MAX_W, "st_ctc_beam_search_lm: beam width 1..%d (W=%d)", CB_MAX_W, W);
+    ST_CHECK_ARG(N >= 1 && N <= W, "st_ctc_beam_search_lm: 1 <= N <= W (N=%d, W=%d)", N, W);
+    ST_CHECK_ARG(blank >= 0 && blank < V, "st_ctc_beam_search_lm: blank %d outside [0, %d)", blank, V);
+    ST_CHECK_ARG(bonus != nullptr, "st_ctc_beam_search_lm: no bonus table");
+    ST_CHECK_ARG(order >= 1 && order <= CB_MAX_ORDER, "st_ctc_beam_search_lm: order 1..%d (order=%d)", CB_MAX_ORDER, order);
+    ST_CHECK_ARG(bos >= 0 && bos < V, "st_ctc_beam_search_lm: bos %d outside [0, %d)", bos, V);
+    long long rows = 1;
+    for (int k = 1; k < order; ++k) rows *= V;            // (<= 1024^3: no overflow)
+    ST_CHECK_ARG(rows * V <= CB_MAX_TABLE, "st_ctc_beam_search_lm: V^order = %lld table elements, at most %d", rows * V, CB_MAX_TABLE);
+    hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(CB_NT), 0, (hipStream_t)stream, prob, T, V, lengths, W, N, blank, log_input, eps,
+                       hyp, hyp_len, score, reinterpret_cast<int2*>(ws), CbLmArgs<true>{bonus, (int)rows, order == 1 ? 0 : bos});
     ST_LAUNCH_CHECK();
     return 0;
 }

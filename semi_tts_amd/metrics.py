@@ -45,14 +45,15 @@ def _rate_sum(dist, ref_len):
     return rate.sum()
 
 
-def beam_per_sum(prob, truth, beam_width, lengths=None, ignore=IGNORE_INDICES, log_input=False):
+def beam_per_sum(prob, truth, beam_width, lengths=None, ignore=IGNORE_INDICES, log_input=False, lm=None, lm_weight=0.5, ins_bonus=0.0):
     """per_sum of the top-1 CTC prefix beam search transcripts (ctc_decode.beam_search, blank 0) instead of the greedy ones: prob
     (B, T, V) float32 posteriors (log-posteriors with log_input), truth (B, L) int64, lengths the valid frames per utterance (None: all).
-    The hypotheses are already collapsed, so the distance does not merge runs (st_hyp_edit_distance).  cal_per and the trainer's
-    validation stay greedy, as the reference's are."""
+    The hypotheses are already collapsed, so the distance does not merge runs (st_hyp_edit_distance).  lm, lm_weight, ins_bonus: the
+    n-gram fusion of ctc_decode.beam_search (None: the acoustic search).  cal_per and the trainer's validation stay greedy, as the
+    reference's are."""
     from .ctc_decode import beam_search
     prob, truth = _on_device(prob, truth)
-    hyp, hyp_len, _ = beam_search(prob, lengths, beam_width, 1, log_input=log_input)
+    hyp, hyp_len, _ = beam_search(prob, lengths, beam_width, 1, log_input=log_input, lm=lm, lm_weight=lm_weight, ins_bonus=ins_bonus)
     return _rate_sum(*ops.hyp_edit_distance(hyp[:, 0], hyp_len[:, 0], truth, ignore))
 
 

@@ -908,13 +908,16 @@ def ctc_greedy_edit_distance(prob, text, ignore, want_hyp=False):
 
 
 CB_MAX_T, CB_MIN_V, CB_MAX_V, CB_MAX_W = 4096, 2, 1024, 128          # st_ctc_beam_search's limits
+from .ngram import MAX_ORDER as CB_MAX_ORDER, MAX_TABLE as CB_MAX_TABLE, order_of as _ngram_order_of   # noqa: E402  (st_ctc_beam_search_lm's limits)
 
 
-def ctc_beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log_input=False, eps=1e-10):
+def ctc_beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log_input=False, eps=1e-10, bonus=None, order=None, bos=1):
     """CTC prefix beam search of prob (B, T, V) fp32 on one GPU (see st_ctc_beam_search).  lengths: None (all T frames), or (B,) integer
     frame counts -- a host tensor / sequence is checked against [0, T] here, a device tensor is taken as it is (the kernel clamps it).
     -> (hyp (B, top_paths, T) int64 0-padded, hyp_len (B, top_paths) int32, score (B, top_paths) float32) device tensors; one launch,
-    no host read.  Anything the kernel would refuse raises ValueError before the device is touched."""
+    no host read.  bonus: None (st_ctc_beam_search, the acoustic search), or the fused n-gram table of st_ctc_beam_search_lm: a contiguous
+    (V^(order-1), V) float32 tensor on the device of prob (order: None = from the shape; bos: the start id of the empty prefix's
+    context); its values are not read here.  Anything the kernel would refuse raises ValueError before the device is touched."""
     if not torch.is_tensor(prob) or not prob.is_cuda or prob.dim() != 3 or prob.dtype != torch.float32:
         raise ValueError('ctc_beam_search: prob must be a (B, T, V) float32 GPU tensor (got %s)'
                          % ('%s %s on %s' % (tuple(prob.shape), prob.dtype, prob.device) if torch.is_tensor(prob) else type(prob).__name__))
@@ -929,6 +932,25 @@ def ctc_beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log
     if not eps >= 0.0:
         raise ValueError('ctc_beam_search: eps must be >= 0 (got %r)' % (eps,))
     dev = prob.device
+    if bonus is not None:
+        if not torch.is_tensor(bonus) or not bonus.is_cuda or bonus.device != dev or bonus.dim() != 2 or bonus.dtype != torch.float32 \
+                or not bonus.is_contiguous():
+            raise ValueError('ctc_beam_search: bonus must be a contiguous (V^(order-1), V) float32 tensor on the device of prob (got %s)'
+                             % ('%s %s on %s' % (tuple(bonus.shape), bonus.dtype, bonus.device) if torch.is_tensor(bonus)
+                                else type(bonus).__name__))
+        found = _ngram_order_of(bonus.shape[0], V) if bonus.shape[1] == V else None
+        if found is None:
+            raise ValueError('ctc_beam_search: a bonus table of shape %s is no (V^(order-1), V) table for V = %d, 1 <= order <= %d'
+                             % (tuple(bonus.shape), V, CB_MAX_ORDER))
+        if order is not None and int(order) != found:
+            raise ValueError('ctc_beam_search: order %r, but the bonus table of shape %s has order %d' % (order, tuple(bonus.shape), found))
+        order, bos = found, int(bos)
+        if V ** order > CB_MAX_TABLE:
+            raise ValueError('ctc_beam_search: V^order = %d^%d table elements, at most 2^26' % (V, order))
+        if not 0 <= bos < V:
+            raise ValueError('ctc_beam_search: bos %d outside [0, %d)' % (bos, V))
+    elif order is not None:
+        raise ValueError('ctc_beam_search: order %r without a bonus table' % (order,))
     if lengths is not None:
         if torch.is_tensor(lengths) and lengths.is_cuda:
             if lengths.device != dev or lengths.shape != (B,) or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
@@ -945,9 +967,14 @@ def ctc_beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log
     hyp_len = torch.empty(B, N, device=dev, dtype=torch.int32)
     score = torch.empty(B, N, device=dev, dtype=torch.float32)
     ws = torch.empty(int(lib.st_ctc_beam_workspace_bytes(B, T, W)), device=dev, dtype=torch.uint8)
-    check(lib.st_ctc_beam_search(_p(prob), B, T, V, _p(lengths, torch.int32), W, N, blank, 1 if log_input else 0, float(eps),
-                                 _p(hyp, torch.int64), _p(hyp_len, torch.int32), _p(score), _p(ws, torch.uint8), stream_handle()),
-          'st_ctc_beam_search')
+    if bonus is None:
+        check(lib.st_ctc_beam_search(_p(prob), B, T, V, _p(lengths, torch.int32), W, N, blank, 1 if log_input else 0, float(eps),
+                                     _p(hyp, torch.int64), _p(hyp_len, torch.int32), _p(score), _p(ws, torch.uint8), stream_handle()),
+              'st_ctc_beam_search')
+    else:
+        check(lib.st_ctc_beam_search_lm(_p(prob), B, T, V, _p(lengths, torch.int32), W, N, blank, 1 if log_input else 0, float(eps),
+                                        _p(bonus), order, bos, _p(hyp, torch.int64), _p(hyp_len, torch.int32), _p(score),
+                                        _p(ws, torch.uint8), stream_handle()), 'st_ctc_beam_search_lm')
     return hyp, hyp_len, score
 
 

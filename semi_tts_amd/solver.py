@@ -183,7 +183,9 @@ def format_phn(scores, hyps, vocab=None):
 class Transcriber(BaseSolver):
     """main.py --transcribe-wav-dir: the .wav files of a directory, sorted by name, in batches of --batch-size -> clean mel on the device
     (AudioConverter.extract_batch without noise or stretch) -> VQVAE.transcribe (speech encoder, codebook or ASR postnet, CTC prefix
-    beam search) -> <logdir>/<name>.phn with --top-paths lines `score<TAB>tokens`.  Without --load the synthetic weights are used."""
+    beam search) -> <logdir>/<name>.phn with --top-paths lines `score<TAB>tokens`.  Without --load the synthetic weights are used.
+    --lm FILE fuses a phone n-gram table (ngram.load_table) into the search with --lm-weight and --ins-bonus; the table is read in
+    load_data and refused there when its width is not that of the searched posteriors, before anything is written."""
 
     WAV_DIR_FLAG = 'transcribe_wav_dir'          # the attribute of paras that names the .wav directory
 
@@ -199,6 +201,16 @@ class Transcriber(BaseSolver):
             raise ValueError('%s: data.audio has %d mels, the model %d' % (flag, self.audio_converter.n_mels, self.n_mels))
         vocab = getattr(self.paras, 'vocab', None)
         self.vocab = read_vocab(vocab) if vocab else None
+        self.lm = None
+        lm = getattr(self.paras, 'lm', None)
+        if lm:
+            from .ngram import load_table
+            self.lm = load_table(lm)
+            # the codebook has one entry per phone id; the ASR postnet is built with latent_dim classes (VQVAE.__init__)
+            width = self.vocab_size if getattr(self.paras, 'asr_output', 'code') == 'code' else int(self.config['model']['codebook']['latent_dim'])
+            if self.lm.shape[1] != width:
+                raise ValueError('--lm %s: the table has %d classes, the %s posteriors %d'
+                                 % (lm, self.lm.shape[1], getattr(self.paras, 'asr_output', 'code'), width))
         return self
 
     def set_model(self):
@@ -206,6 +218,11 @@ class Transcriber(BaseSolver):
         if not self.load_ckpt():
             from .synthetic import load_synthetic
             load_synthetic(self.model, seed=getattr(self.paras, 'seed', 0) + 1234)
+        self.bonus = None
+        if getattr(self, 'lm', None) is not None:               # fused once, kept on the device for every batch
+            from .ngram import fusion_table
+            host = fusion_table(self.lm, float(getattr(self.paras, 'lm_weight', 0.5)), float(getattr(self.paras, 'ins_bonus', 0.0)))
+            self.bonus = torch.from_numpy(host).to(self.device)
         return self
 
     def transcribe_batch(self, waves):
@@ -215,7 +232,7 @@ class Transcriber(BaseSolver):
         mel, _, _ = self.audio_converter.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
         frames = 1 + wb.lens // self.audio_converter.hop_length
         hyp, hyp_len, score = self.model.transcribe(mel, frames, int(self.paras.beam_width), int(self.paras.top_paths),
-                                                    source=self.paras.asr_output)
+                                                    source=self.paras.asr_output, bonus=getattr(self, 'bonus', None))
         back = np.empty_like(wb.order)
         back[wb.order] = np.arange(len(wb.order))                   # sorted position of the i-th given utterance
         return hyp.cpu().numpy()[back], hyp_len.cpu().numpy()[back], score.cpu().numpy()[back]
@@ -233,8 +250,11 @@ class Transcriber(BaseSolver):
                 with open(os.path.join(self.logdir, os.path.splitext(f)[0] + '.phn'), 'w') as out:
                     out.write(format_phn(sc.tolist(), [h[k, :hl[k]].tolist() for k in range(len(hl))], self.vocab))
                 n += 1
-        self.verbose('Transcribed %d files (beam %d, %d paths, %s posteriors) into %s, %.2f s'
-                     % (n, self.paras.beam_width, self.paras.top_paths, self.paras.asr_output, self.logdir, time.perf_counter() - t0))
+        from .ngram import order_of as ngram_order_of
+        fused = '' if getattr(self, 'lm', None) is None else ', %d-gram weight %g bonus %g' % (
+            ngram_order_of(*self.lm.shape), self.paras.lm_weight, self.paras.ins_bonus)
+        self.verbose('Transcribed %d files (beam %d, %d paths, %s posteriors%s) into %s, %.2f s'
+                     % (n, self.paras.beam_width, self.paras.top_paths, self.paras.asr_output, fused, self.logdir, time.perf_counter() - t0))
         return n
 
 

@@ -128,12 +128,14 @@ class VQVAE(nn.Module):
             t = getattr(self.asr, 'layer' + str(l)).out_len(t)
         return t
 
-    def transcribe(self, mel, mel_lengths, beam_width=16, top_paths=1, source='code'):
+    def transcribe(self, mel, mel_lengths, beam_width=16, top_paths=1, source='code', lm=None, lm_weight=0.5, ins_bonus=0.0, bonus=None):
         """CTC prefix beam search of the speech encoder's posteriors, in eval mode without gradients (the mode is restored after).
         mel (B, T, n_mels) padded batch on the device, mel_lengths its valid frames per utterance (host integers).  source 'code':
         the codebook posteriors of speech_to_text (probabilities, searched as log(p + 1e-10)); 'post': the ASRPostnet's log-posteriors
         (refused when the model has no postnet).  The encoder runs on the padded batch, as the reference's validate does, so its
-        BiLSTM sees the padding frames; the search reads only each utterance's own encoder frames (encoder_lengths).
+        BiLSTM sees the padding frames; the search reads only each utterance's own encoder frames (encoder_lengths).  lm, lm_weight,
+        ins_bonus: the n-gram fusion of ctc_decode.beam_search (None: the acoustic search); bonus: instead of lm, a fused table already
+        on the device.
         -> (hyp (B, top_paths, T') int64, hyp_len (B, top_paths) int32, score (B, top_paths) float32) device tensors, best first."""
         from .ctc_decode import beam_search
         if source not in ('code', 'post'):
@@ -147,7 +149,8 @@ class VQVAE(nn.Module):
             with torch.no_grad():
                 p_code, _, _, _, _, post, _ = self.speech_to_text(paired_mel=mel, unpaired_mel=None)
                 prob = post if source == 'post' else p_code
-                return beam_search(prob, lengths.clamp(0, prob.shape[1]), beam_width, top_paths, log_input=source == 'post')
+                return beam_search(prob, lengths.clamp(0, prob.shape[1]), beam_width, top_paths, log_input=source == 'post',
+                                   lm=lm, lm_weight=lm_weight, ins_bonus=ins_bonus, bonus=bonus)
         finally:
             self.train(was_training)
 
