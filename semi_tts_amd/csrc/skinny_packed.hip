@@ -790,7 +790,12 @@ __device__ __forceinline__ void pk_part_body(const PkPartArgs& p, const int j, f
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
         rw[rt] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w + ((size_t)(tp * RT + rt) * p.w_kbs + kb_lo) * 64), 0, KBs * 1024, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)kb_lo * 64), 0, ((NB - 1) * p.x_kbs + KBs) * 1024, 0x00020000);
+    // (one descriptor per batch tile, each ending with the split's range: behind it in the first tile lie the second tile's k-blocks, which
+    // nobody may have written yet -- NaN there times the zeros of the weights would be NaN)
+    __amdgpu_buffer_rsrc_t rx[NB];
+#pragma unroll
+    for (int bt = 0; bt < NB; ++bt)
+        rx[bt] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + ((size_t)bt * p.x_kbs + kb_lo) * 64), 0, KBs * 1024, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     constexpr int STEP = KW * TRIP;
     const int G = (KBs + STEP - 1) / STEP;
@@ -804,7 +809,7 @@ __device__ __forceinline__ void pk_part_body(const PkPartArgs& p, const int j, f
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) r.w[t][rt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw[rt], vo, 0, 0));
 #pragma unroll
-            for (int bt = 0; bt < NB; ++bt) r.x[t][bt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, vo, bt * p.x_kbs * 1024, 0));
+            for (int bt = 0; bt < NB; ++bt) r.x[t][bt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx[bt], vo, 0, 0));
         }
     };
     f32x4 acc[RT][NB];

@@ -80,6 +80,36 @@ def split_masks(masks, hp, training, tf_rate, B, Bt, steps, step_src, P):
     return out
 
 
+def decoder_fp64_reference(W, memory, teacher, spk, hp, tf_rate=0.0, unpair_max_frame=None, training=False, seed=11, grad=False):
+    """oracle.tts_oracle.decoder_forward in float64 on float64 copies of the weights `W` ('decoder.'-prefixed) and inputs.  The dropout
+    masks are drawn in float32 from a generator seeded with `seed` and kept in draw order, so that split_masks can replay them through
+    the HIP path (and DropoutSource('list', ...) through a float32 run of the oracle).  `teacher`: an int (free running) or a tensor;
+    hp: the decoder section plus n_mels.  grad=True makes the float64 weights, memory and speaker embedding leaves that require grad.
+    Returns (outs, masks, Wd, memory64, spk64) with outs = (mel, alignment, stop)."""
+    from oracle import tts_oracle as O
+
+    class Drop64(O.DropoutSource):
+        def __call__(self, x, p, training):
+            if (not training) or p == 0.0:
+                return x
+            keep = torch.full(x.shape, 1.0 - p, dtype=torch.float32)
+            mk = torch.bernoulli(keep, generator=self.gen) / (1.0 - p)
+            self.used.append(mk)
+            return x * mk.double()
+
+    torch.set_default_dtype(torch.float64)       # the oracle creates its zero states in the default dtype
+    try:
+        Wd = {k: v.double().requires_grad_(grad) for k, v in W.items()}
+        mem_r, spk_r = memory.double().requires_grad_(grad), spk.double().requires_grad_(grad)
+        drop = Drop64('rng', generator=torch.Generator().manual_seed(seed))
+        with torch.set_grad_enabled(grad):
+            outs = O.decoder_forward(Wd, mem_r, teacher if isinstance(teacher, int) else teacher.double(), spk_r, hp, tf_rate,
+                                     unpair_max_frame, training, drop, lambda: 0.0)
+    finally:
+        torch.set_default_dtype(torch.float32)
+    return outs, drop.used, Wd, mem_r, spk_r
+
+
 def masks_to(masks, device):
     out = {}
     for k, v in masks.items():

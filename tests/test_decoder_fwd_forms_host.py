@@ -1,7 +1,10 @@
 """Which forms the decode loop (st_decoder_forward) takes -- host arithmetic only, no GPU: st_decoder_fwd_forms looks at shapes, flags,
 pointer values and the host array step_src and never reads through the device pointers, so fake addresses stand in for the buffers.
 Every row of the table reaches the forms named in it, and together the rows reach every attention form, every host of the decoder
-cell's partial gate product, paired cells, deferred projection and the fall-back when a workgroup budget does not fit the device."""
+cell's partial gate product, paired cells, deferred projection and the fall-back when a workgroup budget does not fit the device.
+
+The second half does the same for decoder_fwd_cases.CASES, the small-size cases that tests/test_gpu_decoder_fwd_forms.py runs on the GPU
+against float64: st_decoder_io filled the way Decoder._run_loop fills it for the case's knobs and mode, on an MI355X's 256 compute units."""
 import ctypes as C
 import os
 import sys
@@ -9,6 +12,7 @@ import sys
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import decoder_fwd_cases as FC   # noqa: E402
 from helpers import FWD_ATTN as ATTN, FWD_PROD as PROD, fwd_forms as decode   # noqa: E402
 from semi_tts_amd import _lib   # noqa: E402
 
@@ -146,3 +150,77 @@ def test_null_arguments(lib):
     dims = _lib.StDecoderDims(**FULL_DIMS, n_mels=80, r=3)
     assert lib.st_decoder_fwd_forms(None, None, 256, 512) == -1
     assert lib.st_decoder_fwd_forms(C.byref(dims), C.byref(io), 256, 512) == -1
+
+
+# ------------------------------------------------------------------------------------ the cases the GPU test runs
+def case_word(lib, c):
+    """the planner's word for a decoder_fwd_cases case: the io fields of decoder_fwd_cases.io_plan, fake addresses for the buffers"""
+    p = FC.io_plan(c)
+    dims = _lib.StDecoderDims(B=c['B'], L=c['L'], n_mels=FC.COMMON['n_mels'], r=FC.COMMON['r'], F=FC.COMMON['F'], K=FC.COMMON['K'],
+                              **FC.DIMS[c['dims']])
+    io = _lib.StDecoderIO()
+    io.steps = p['steps']
+    src_arr = (C.c_int * p['steps'])(*p['step_src'])
+    io.step_src = C.cast(src_arr, C.POINTER(C.c_int))
+    if p['teacher']:
+        io.teacher_pre, io.Tt = BASE + 0x10000, p['Tt']
+    io.Bt = p['Bt']
+    io.defer_proj, io.pair_cells = int(p['defer']), int(p['pair'])
+    io.attn_s_buf = BASE + 0x100000 if p['s_buf'] else None
+    io.attn_fin_parts, io.attn_pre_parts = p['fin_parts'], p['pre_parts']
+    if p['split_parts']:
+        io.attn_split_ws, io.attn_split_parts = BASE + 0x200000, p['split_parts']
+    io.pq_granules = BASE + 0x300000 if p['pq_gran'] else None
+    io.attn_xchg = BASE + 0x400000 if p['xchg'] else None
+    io.gate_part = BASE + 0x500000 if p['gate_part'] else None
+    io.gate_part_k = p['gate_part_k']
+    return int(lib.st_decoder_fwd_forms(C.byref(dims), C.byref(io), FC.CUS, FC.RNG_CAPACITY))
+
+
+def word_fields(w):
+    """(forms, fin parts, k0) of a planner word"""
+    return decode(w), (w >> 12) & 15, w >> 16
+
+
+@pytest.mark.parametrize('c', FC.CASES, ids=FC.IDS)
+def test_case_reaches_its_forms(lib, c):
+    w = case_word(lib, c)
+    assert word_fields(w) == (c['want'], c['fp'], c['k0']), hex(w)
+
+
+def test_cases_cover_every_form(lib):
+    got = [word_fields(case_word(lib, c)) for c in FC.CASES]
+    assert {g[0][0] for g in got} == set(ATTN)
+    assert {g[0][1] for g in got} == set(PROD)
+    assert {g[1] for g in got} == {1, 2, 4, 8}
+    assert set().union(*(g[0][2] for g in got)) == TRAIN
+    assert len({g[2] for g in got if g[0][1] != 'none'}) >= 2                # cuts of the cell's reduction
+    # every fused form beside every host it can have at these sizes, and each mode behind the forms it is meant to reach
+    assert {(g[0][0], g[0][1]) for g in got} >= {('pq_fin', 'pq_fin'), ('pq_fin', 'none'), ('pre_fin', 'pq_pre'), ('pre_fin', 'own'),
+                                                  ('pre_fin', 'none'), ('pq_rng', 'none'), ('fin_split', 'none'), ('whole', 'none')}
+    by_mode = {}
+    for c, g in zip(FC.CASES, got):
+        by_mode.setdefault(c['mode'], set()).add((g[0][0], g[0][1]))
+    assert set(by_mode) == set(FC.MODES)
+    assert ('pq_fin', 'pq_fin') in by_mode['tf_eval'] and ('pq_fin', 'pq_fin') in by_mode['tf_partial']
+    for ds in FC.DIMS:                  # every dims set has a case with expanding dynamics
+        assert any(c['dims'] == ds and c['gain'] != 1.0 for c in FC.CASES), ds
+    assert any(c['steps'] == 1 for c in FC.CASES) and any(c['B'] == 1 and c['L'] == 1 for c in FC.CASES)
+
+
+def test_cases_cover_every_cut_the_loop_accepts(lib):
+    """split_cell_k at M16: every multiple of 16 in the range st_decoder_forward accepts, [16 * ceil(E / 16), 16 * (k-blocks of the cell))"""
+    d = FC.DIMS['M16']
+    lo, hi = 16 * ((d['E'] + 15) // 16), 16 * sum((d[k] + 15) // 16 for k in ('E', 'Q', 'D'))
+    cuts = {c['knobs']['split_cell_k'] for c in FC.CASES if c['dims'] == 'M16' and c['mode'] == 'free' and 'split_cell_k' in c['knobs']}
+    assert cuts == set(range(lo, hi, 16))
+    dims = _lib.StDecoderDims(B=20, L=11, n_mels=8, r=2, F=8, K=7, **d)
+    assert lib.st_decoder_gate_split_k(C.byref(dims)) == 16 * FC.cell_k0('M16')
+
+
+def test_bit_identical_pairs_share_everything_but_the_form():
+    for a, b in FC.BIT_IDENTICAL:
+        ca, cb = FC.BY_ID[a], FC.BY_ID[b]
+        same = ('dims', 'B', 'L', 'steps', 'mode', 'Bt', 'gain', 'k0')
+        assert [ca[k] for k in same] == [cb[k] for k in same], (a, b)
+        assert ca['want'][:2] == ('pq_fin', 'pq_fin') and cb['want'][:2] == ('pre_fin', 'own')

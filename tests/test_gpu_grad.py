@@ -553,8 +553,7 @@ def test_decoder_backward_against_oracle(dev, B, L, steps, tiled):
     """Decoder only, dropout masks drawn by the oracle and replayed through the HIP path; B=20 exercises the padded rows of the step
     tapes (Bp=32).  tiled=False: dimensions that are not multiples of the tile sizes (six launches per backward step);
     tiled=True: dimensions the fused form takes -- the cells' pointwise backward in the epilogues of the loop's products."""
-    from helpers import masks_to, split_masks
-    from oracle import tts_oracle as O
+    from helpers import decoder_fp64_reference, masks_to, split_masks
     from semi_tts_amd.module import Decoder
     hp = dict(n_frames_per_step=2, prenet_dim=24, prenet_dropout=0.5, query_rnn_dim=40, dec_rnn_dim=36, query_dropout=0.1,
               dec_dropout=0.1, attn_dim=32, n_location_filters=8, location_kernel_size=7, loc_aware=True,
@@ -569,28 +568,11 @@ def test_decoder_backward_against_oracle(dev, B, L, steps, tiled):
     memory, spk = rnd(B, L, E, seed=1), rnd(B, S, seed=2)
     teacher = torch.rand(B, steps * 2, n_mels, generator=torch.Generator().manual_seed(3))
     hpo = dict(hp, n_mels=n_mels)
-    drop = O.DropoutSource('rng', generator=torch.Generator().manual_seed(11))
-    torch.set_default_dtype(torch.float64)
-    try:
-        Wd = {k: v.double().requires_grad_() for k, v in W.items()}
-        mem_r, spk_r = memory.double().requires_grad_(), spk.double().requires_grad_()
-
-        class Drop64(O.DropoutSource):
-            def __call__(self, x, p, training):
-                if (not training) or p == 0.0:
-                    return x
-                keep = torch.full(x.shape, 1.0 - p, dtype=torch.float32)
-                mk = torch.bernoulli(keep, generator=self.gen) / (1.0 - p)
-                self.used.append(mk)
-                return x * mk.double()
-        drop = Drop64('rng', generator=torch.Generator().manual_seed(11))
-        outs = O.decoder_forward(Wd, mem_r, teacher.double(), spk_r, hpo, 1.0, None, True, drop, lambda: 0.0)
-    finally:
-        torch.set_default_dtype(torch.float32)
+    outs, used, Wd, mem_r, spk_r = decoder_fp64_reference(W, memory, teacher, spk, hpo, 1.0, None, True, seed=11, grad=True)
     douts = [rnd(*outs[0].shape, seed=1), rnd(*outs[1].shape, seed=2), rnd(*outs[2].shape, seed=3)]
     torch.autograd.backward(list(outs), [d.double() for d in douts])
     src = list(range(steps))
-    masks = masks_to(split_masks(drop.used, hpo, True, 1.0, B, B, steps, src, hp['prenet_dim']), dev)
+    masks = masks_to(split_masks(used, hpo, True, 1.0, B, B, steps, src, hp['prenet_dim']), dev)
     mem_d, spk_d = memory.to(dev).requires_grad_(), spk.to(dev).requires_grad_()
     mel, align, stop = dec(mem_d, None, teacher.to(dev), spk_d, tf_rate=1.0, _masks=masks)
     torch.autograd.backward([mel, align, stop], [d.to(dev) for d in douts])
