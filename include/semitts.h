@@ -1291,7 +1291,10 @@ int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized,
  * aug (B, Ta_pad, n_mels) (null: not written) is the augmented mel: its own framing aug_win[b] / aug_hop[b] (the time-stretched
  * win / hop of :366-373), and s = x + coeff_b n with coeff_b = sqrt(sum x^2 / sum n^2 * 10^(-snr_db[b] / 10)) over the utterance
  * (snr_db null, or NaN for an utterance: no noise).  n: `noise`, packed like x, or, when null, the built-in counter-based
- * generator (Philox4x32-10, standard normal by Box-Muller) of (seed, b, sample index): no noise buffer exists.
+ * generator (Philox4x32-10, standard normal by Box-Muller) of (seed, utt0 + b, sample index): no noise buffer exists.  utt0 is
+ * the position of this call's first utterance in the caller's whole batch (0 for a batch issued in one call): a batch above 64
+ * issued in several calls then draws the noise st_feature_noise() gives for each utterance's position in the batch.  Only the
+ * generator reads utt0; off, len, aug_win, aug_hop, snr_db and the output rows are relative to this call.
  * Host arrays: off, len, aug_win, aug_hop, snr_db (B entries, read before the call returns); everything else is on the device.
  * Supported: n_fft in {512, 1024, 2048, 4096}, 0 < 2 * hop <= win <= n_fft for both framings, len[b] > n_fft / 2, B <= 64
  * (anything else returns -22).  ws: st_features_workspace_floats(B) floats.  One launch (clean + augmented framings as the
@@ -1299,8 +1302,8 @@ int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized,
  * repeatable for a given seed. */
 size_t st_features_workspace_floats(int B);
 int st_audio_features(const float* x, long n_samples, const float* noise, unsigned long long seed, const long* off, const int* len,
-                      const int* aug_win, const int* aug_hop, const float* snr_db, int B, int n_fft, int win, int hop, float preemph,
-                      const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels, float* mel,
+                      const int* aug_win, const int* aug_hop, const float* snr_db, int B, int utt0, int n_fft, int win, int hop,
+                      float preemph, const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels, float* mel,
                       float* linear, int T_pad, float* aug, int Ta_pad, float* ws, void* stream);
 /* out[i] = the built-in generator's standard normal for (seed, utterance utt, sample i), i < n (for tests) */
 int st_feature_noise(float* out, long n, int utt, unsigned long long seed, void* stream);

@@ -356,7 +356,7 @@ SIGNATURES = {
     'st_istft': [P, P, I, I, I, I, I, P, P],
     'st_griffin_lim': [P, C.c_long, C.c_long, C.c_long, I, F, P, P, I, I, I, I, I, I, I, P, P],
     'st_features_workspace_floats': [I],
-    'st_audio_features': [P, C.c_long, P, C.c_ulonglong, P, P, P, P, P, I, I, I, I, F, P, P, P, P, I, P, P, I, P, I, P, P],
+    'st_audio_features': [P, C.c_long, P, C.c_ulonglong, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, I, P, P, I, P, I, P, P],
     'st_feature_noise': [P, C.c_long, I, C.c_ulonglong, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,

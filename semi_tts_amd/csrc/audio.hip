@@ -8,6 +8,7 @@
 // iteration (iSTFT -> STFT -> phase projection) is ONE launch of one workgroup per (utterance, frame), with no atomics (every
 // result is bitwise repeatable).
 #include "st_common.h"
+#include <limits.h>
 #include <math.h>
 #include <mutex>
 
@@ -408,7 +409,7 @@ struct FeatMeta {
     float snr[FEAT_MAX_B];     // dB; NaN: no noise for this utterance (:356-359)
 };
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter (i, b, 0, 0), key = the seed.
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter (i lo, i hi, utterance, 0), key = the seed.
 __device__ __forceinline__ uint4 philox4x32(uint4 c, uint2 k) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -436,11 +437,12 @@ __global__ void feat_noise_kernel(float* __restrict__ out, long n, int b, unsign
 
 // The power sums of snr_coeff (:434-437): sum x^2 and sum n^2 of utterance b in POW_PARTS fixed slices, one workgroup each,
 // fixed-order double sums into part[(b * POW_PARTS + p) * 2 + {0, 1}]; the frame kernel adds the slices in order (feat_coeff).
-// No atomics: deterministic.
+// No atomics: deterministic.  The generator is keyed on utt0 + b, the utterance's position in the whole batch (meta and `part`
+// are relative to this call's first utterance).
 constexpr int POW_THREADS = 256;
 constexpr int POW_PARTS = 64;
 __global__ __launch_bounds__(POW_THREADS) void feat_power_kernel(const float* __restrict__ x, const float* __restrict__ noise,
-                                                                 unsigned long long seed, FeatMeta meta, double* __restrict__ part) {
+                                                                 unsigned long long seed, int utt0, FeatMeta meta, double* __restrict__ part) {
     __shared__ double sx[POW_THREADS], sn[POW_THREADS];
     const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const long off = meta.off[b];
@@ -451,7 +453,7 @@ __global__ __launch_bounds__(POW_THREADS) void feat_power_kernel(const float* __
     if (!isnan(meta.snr[b])) {
         for (int i = i0 + tid; i < i1; i += POW_THREADS) {
             const double v = x[off + i];
-            const double n = noise ? (double)noise[off + i] : (double)feat_normal(seed, b, i);
+            const double n = noise ? (double)noise[off + i] : (double)feat_normal(seed, utt0 + b, i);
             ax += v * v;
             an += n * n;
         }
@@ -495,7 +497,7 @@ __device__ __forceinline__ float feat_norm_db(float a) {
 // t >= 1 + L_b / hop are written as 0 (SPEC_PAD_VALUE).  Mel m sums mag[fb_start[m] + j] * fb_w[fb_off[m] + j], j < fb_cnt[m].
 template <int N>
 __global__ __launch_bounds__(GL_THREADS) void features_kernel(const float* __restrict__ x, const float* __restrict__ noise,
-                                                            unsigned long long seed, const double* __restrict__ part, FeatMeta meta,
+                                                            unsigned long long seed, int utt0, const double* __restrict__ part, FeatMeta meta,
                                                             float c, int win, int hop, const int* __restrict__ fb_start,
                                                             const int* __restrict__ fb_cnt, const int* __restrict__ fb_off,
                                                             const float* __restrict__ fb_w, int n_mels, float* __restrict__ mel,
@@ -530,7 +532,7 @@ __global__ __launch_bounds__(GL_THREADS) void features_kernel(const float* __res
     const float cn = cn_s;
     auto sample = [&](int i) -> float {                      // x + coeff n (add_noise, :411-416)
         float v = xb[i];
-        if (cn != 0.0f) v = fmaf(cn, nb ? nb[i] : feat_normal(seed, b, i), v);
+        if (cn != 0.0f) v = fmaf(cn, nb ? nb[i] : feat_normal(seed, utt0 + b, i), v);
         return v;
     };
     const int left = (N - win) / 2;
@@ -566,11 +568,11 @@ __global__ __launch_bounds__(GL_THREADS) void features_kernel(const float* __res
 }
 
 template <int N>
-void launch_features(const float* x, const float* noise, unsigned long long seed, const double* part, const FeatMeta& meta, float c,
+void launch_features(const float* x, const float* noise, unsigned long long seed, int utt0, const double* part, const FeatMeta& meta, float c,
                      int win, int hop, const int* fs, const int* fc, const int* fo, const float* fw, int n_mels, float* mel,
                      float* linear, float* aug, int B, int T_pad, int Ta_pad, hipStream_t s) {
     const dim3 grid(max(T_pad, aug ? Ta_pad : 0), B, aug ? 2 : 1);
-    hipLaunchKernelGGL((features_kernel<N>), grid, dim3(GL_THREADS), 0, s, x, noise, seed, part, meta, c, win, hop, fs, fc, fo, fw,
+    hipLaunchKernelGGL((features_kernel<N>), grid, dim3(GL_THREADS), 0, s, x, noise, seed, utt0, part, meta, c, win, hop, fs, fc, fo, fw,
                        n_mels, mel, linear, aug, T_pad, Ta_pad);
 }
 
@@ -705,13 +707,14 @@ extern "C" int st_feature_noise(float* out, long n, int utt, unsigned long long 
 }
 
 extern "C" int st_audio_features(const float* x, long n_samples, const float* noise, unsigned long long seed, const long* off, const int* len,
-                                 const int* aug_win, const int* aug_hop, const float* snr_db, int B, int n_fft, int win, int hop,
-                                 float preemph, const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels,
+                                 const int* aug_win, const int* aug_hop, const float* snr_db, int B, int utt0, int n_fft, int win,
+                                 int hop, float preemph, const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels,
                                  float* mel, float* linear, int T_pad, float* aug, int Ta_pad, float* ws, void* stream) {
     (void)hipGetLastError();
     ST_CHECK_ARG(x && off && len && fb_start && fb_cnt && fb_off && fb_w && mel && ws, "st_audio_features: null pointer");
     ST_CHECK_ARG(!aug || (aug_win && aug_hop), "st_audio_features: the augmented framing needs aug_win / aug_hop");
     ST_CHECK_ARG(B > 0 && B <= FEAT_MAX_B, "st_audio_features: batch %d outside [1, %d]", B, FEAT_MAX_B);
+    ST_CHECK_ARG(utt0 >= 0 && utt0 <= INT_MAX - FEAT_MAX_B, "st_audio_features: first utterance index %d", utt0);
     ST_CHECK_ARG(n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096,
                  "st_audio_features: n_fft %d not supported (512, 1024, 2048, 4096)", n_fft);
     ST_CHECK_ARG(n_mels > 0 && n_mels <= n_fft / 2 + 1, "st_audio_features: %d mels for n_fft %d", n_mels, n_fft);
@@ -746,8 +749,8 @@ extern "C" int st_audio_features(const float* x, long n_samples, const float* no
     hipStream_t s = (hipStream_t)stream;
     const bool noisy = aug && snr_db;
     double* part = reinterpret_cast<double*>(ws);
-    if (noisy) hipLaunchKernelGGL(feat_power_kernel, dim3(POW_PARTS, B), dim3(POW_THREADS), 0, s, x, noise, seed, meta, part);
-    ST_AUDIO_DISPATCH(n_fft, launch_features, x, noise, seed, noisy ? part : nullptr, meta, preemph, win, hop, fb_start, fb_cnt, fb_off, fb_w,
+    if (noisy) hipLaunchKernelGGL(feat_power_kernel, dim3(POW_PARTS, B), dim3(POW_THREADS), 0, s, x, noise, seed, utt0, meta, part);
+    ST_AUDIO_DISPATCH(n_fft, launch_features, x, noise, seed, utt0, noisy ? part : nullptr, meta, preemph, win, hop, fb_start, fb_cnt, fb_off, fb_w,
                       n_mels, mel, linear, aug, B, T_pad, Ta_pad, s);
     ST_LAUNCH_CHECK();
     return 0;

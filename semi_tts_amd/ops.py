@@ -1838,7 +1838,8 @@ def audio_features(x, off, lens, n_fft, win, hop, preemph, fb, T_pad, with_linea
     fb = (start, count, offset, weights) device tensors of the banded mel filterbank.  -> (mel (B, T_pad, n_mels),
     linear (B, T_pad, n_fft // 2 + 1) or None, aug (B, Ta_pad, n_mels) or None); the augmented mel when aug_win / aug_hop (per
     utterance) are given, with noise at snr_db[b] (NaN: none) from `noise` (packed like x) or the built-in generator of `seed`.
-    Batches above FEATURES_MAX_BATCH are issued in chunks of it."""
+    Batches above FEATURES_MAX_BATCH are issued in chunks of it; the generator is keyed on the position in the whole batch
+    (feature_noise(n, b, seed) is utterance b's noise whatever B is)."""
     assert x.dim() == 1 and x.is_contiguous() and (noise is None or (noise.shape == x.shape and noise.is_contiguous()))
     fs, fc, fo, fw = fb
     n_mels, F = fs.shape[0], n_fft // 2 + 1
@@ -1861,7 +1862,7 @@ def audio_features(x, off, lens, n_fft, win, hop, preemph, fb, T_pad, with_linea
     for b0 in range(0, B, FEATURES_MAX_BATCH):
         nb = min(FEATURES_MAX_BATCH, B - b0)
         check(lib.st_audio_features(_p(x), x.numel(), _p(noise), int(seed) & (2 ** 64 - 1), hp(off, b0), hp(lens, b0),
-                                    hp(aug_win, b0), hp(aug_hop, b0), hp(snr_db, b0), nb, n_fft, win, hop, float(preemph),
+                                    hp(aug_win, b0), hp(aug_hop, b0), hp(snr_db, b0), nb, b0, n_fft, win, hop, float(preemph),
                                     _p(fs, torch.int32), _p(fc, torch.int32), _p(fo, torch.int32), _p(fw), n_mels, _p(mel[b0:]),
                                     _p(lin[b0:]) if lin is not None else None, T_pad, _p(aug[b0:]) if aug is not None else None,
                                     Ta_pad or 0, _p(ws), stream_handle()), 'st_audio_features')
