@@ -1278,6 +1278,28 @@ int st_istft(const float* spec, float* x, int B, int T, int n_fft, int hop, int 
  * iteration, final overlap-add). */
 int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases, float* wav,
                    int B, int T, int n_fft, int hop, int win, int n_iter, int post, float* ws, void* stream);
+/* lin (B, T, F) contiguous = the mel -> linear product of melspecgram_to_specgram (ref: src/audio.py:194-205):
+ * lin[b, t, k] = sum_m basis[m, k] a[b, t, m], mel(b, t, m) = mel[b * sb + t * st + m * sm] (strides in floats), basis (n_mels, F)
+ * row-major = pinverse(mel filterbank) transposed (computed by the caller, once).  normalized = 1: a = _db_to_amp(_denormalize(mel)
+ * + REF_LEVEL_DB), the expressions of the Griffin-Lim kernels; 0: a = mel.  take_abs = 1 stores |lin| (what _griffin_lim takes, :217);
+ * 0 the signed product the reference method returns.  Supported: 1 <= n_mels <= 256, F = n_fft / 2 + 1 of a supported n_fft
+ * (anything else returns -22).  One launch; each output is an fmaf chain over ascending m: bitwise independent of batch and tiling. */
+int st_mel_to_linear(const float* mel, long sb, long st, long sm, const float* basis, float* lin, int B, int T, int n_mels, int F,
+                     int normalized, int take_abs, void* stream);
+/* Griffin-Lim over a batch whose utterances have their own frame counts, from linear or mel input.
+ * basis == NULL, n_in == n_fft / 2 + 1: feat is the linear spectrogram, exactly as the uniform entry point above takes it.
+ * basis != NULL, n_in == n_mels: feat is the mel spectrogram (B, T, n_mels) through the same strides; the magnitude is
+ * |mel -> linear product| (one more launch, into the workspace) and power must be 1 (the reference's mel branch is isAmp, :402-408).
+ * frames: DEVICE int32 array of B frame counts, or NULL for T everywhere (then the launches are those of the uniform entry point).
+ * Utterance b has T_b = frames[b] frames and L_b = hop * (T_b - 1) samples: reflect padding, overlap-add, envelope, inverse
+ * pre-emphasis and clip are those of a T_b-frame utterance vocoded alone (bitwise).  Storage keeps the strides of T: feat rows and
+ * phase columns t >= T_b are never read; wav is (B, hop * (T - 1)), row b written on [0, L_b) and zero after.  The kernels clamp
+ * frames[b] into [n_fft / 2 / hop + 2, T] (the fewest frames the reflect padding takes; T itself is checked), so no value indexes
+ * outside the workspace; validating frames is the caller's.  ws: st_gl_batch_workspace_floats() floats. */
+size_t st_gl_batch_workspace_floats(int B, int T, int n_fft, int hop, int win);
+int st_griffin_lim_batch(const float* feat, long sb, long st, long sf, int n_in, const float* basis, int normalized, float power,
+                         const float* phases, const int* frames, float* wav, int B, int T, int n_fft, int hop, int win, int n_iter,
+                         int post, float* ws, void* stream);
 
 /* ------------------------------------------------------------------ feature extraction (waveforms -> normalised spectrograms)
  * Replaces AudioProcessor.extract_feature_from_waveform (ref: src/audio.py:156-177) and AudioConverter.wave_to_feat's feature

@@ -18,11 +18,15 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/semi-single-spkr-paired-data.yaml --align-wav-dir DIR [--phn-dir DIR2 --vocab FILE]
     python main.py --config config/semi-single-spkr-paired-data.yaml --build-lm-phn-dir DIR --lm-order 2 --lm FILE [--lm-smooth 1 --vocab F]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --lm FILE [--lm-weight 0.5 --ins-bonus 0]
+    python main.py --config config/supervised.yaml --vocode-dir DIR [--vocode-feat spec|mel --batch-size 32]
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
 `--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
 (semi_tts_amd/ngram.py: a plain .npy of shape (V^(order-1), V) in the layout of the reference's NgramPrior, src/lm.py:233-290) on the host.
 `--align-wav-dir` (not a mode of the reference either) aligns .wav files to their .phn transcripts by CTC forced alignment
 (solver.Aligner): <file>.ali per utterance and segments.csv in the layout of the reference's segment_file.
+`--vocode-dir` (the reference's util/gen_wav_from_specgram.py) vocodes the -spec.npy or -mel.npy files `--gen-specgram` writes into
+<stem>.wav by Griffin-Lim, a batch of differing lengths per call (solver.Vocoder); `--gen-wav-feat mel` makes `--gen-specgram --gen-wav`
+vocode the predicted mel instead of the predicted linear spectrogram.
 """
 import argparse
 import random
@@ -87,6 +91,12 @@ parser.add_argument('--build-lm-phn-dir', default=None, type=str, help='count an
                     'transcripts of this directory (ids or --vocab symbols, id 0 skipped) and write it to --lm; no GPU, no other mode')
 parser.add_argument('--lm-order', default=None, type=int, help='--build-lm-phn-dir: order of the table (1 .. 4)')
 parser.add_argument('--lm-smooth', default=None, type=float, help='--build-lm-phn-dir: add-K smoothing over the non-blank phones (default 1)')
+parser.add_argument('--gen-wav-feat', default='linear', choices=('linear', 'mel'), help='--gen-specgram --gen-wav: vocode the predicted '
+                    'linear spectrogram (default) or the predicted mel (through the filterbank\'s pseudo-inverse) into <name>-pred.wav')
+parser.add_argument('--vocode-dir', default=None, type=str, help='vocode the saved spectrograms of this directory (the *-spec.npy / '
+                    '*-mel.npy files --gen-specgram writes; sorted by name, batched by --batch-size, each at its own length) by '
+                    'Griffin-Lim into <logdir>/<name>/<stem>.wav; no checkpoint, no model')
+parser.add_argument('--vocode-feat', default=None, choices=('spec', 'mel'), help='--vocode-dir: read *-spec.npy (default) or *-mel.npy')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -134,6 +144,18 @@ def parse_args(argv=None):
             parser.error('--align-wav-dir does not combine with --dev-batches')
     elif paras.phn_dir is not None:
         parser.error('--phn-dir names the transcripts of --align-wav-dir; it needs that flag')
+    if paras.vocode_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir'):
+            if getattr(paras, flag):
+                parser.error('--vocode-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--vocode-dir does not combine with --dev-batches')
+    elif paras.vocode_feat is not None:
+        parser.error('--vocode-feat names the files --vocode-dir reads; it needs that flag')
+    if paras.vocode_feat is None:
+        paras.vocode_feat = 'spec'
+    if paras.gen_wav_feat != 'linear' and not (paras.gen_specgram and paras.gen_wav):
+        parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
         for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir'):
             if getattr(paras, flag):
@@ -198,7 +220,10 @@ def main(argv=None):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('nccl')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    if paras.transcribe_wav_dir is not None:
+    if paras.vocode_dir is not None:
+        from semi_tts_amd.solver import Vocoder as Solver
+        mode = 'test'
+    elif paras.transcribe_wav_dir is not None:
         from semi_tts_amd.solver import Transcriber as Solver
         mode = 'test'
     elif paras.align_wav_dir is not None:

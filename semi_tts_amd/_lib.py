@@ -355,6 +355,9 @@ SIGNATURES = {
     'st_stft_fwd': [P, P, I, I, I, I, I, P],
     'st_istft': [P, P, I, I, I, I, I, P, P],
     'st_griffin_lim': [P, C.c_long, C.c_long, C.c_long, I, F, P, P, I, I, I, I, I, I, I, P, P],
+    'st_mel_to_linear': [P, C.c_long, C.c_long, C.c_long, P, P, I, I, I, I, I, I, P],
+    'st_gl_batch_workspace_floats': [I, I, I, I, I],
+    'st_griffin_lim_batch': [P, C.c_long, C.c_long, C.c_long, I, P, I, F, P, P, P, I, I, I, I, I, I, I, P, P],
     'st_features_workspace_floats': [I],
     'st_audio_features': [P, C.c_long, P, C.c_ulonglong, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, I, P, P, I, P, I, P, P],
     'st_feature_noise': [P, C.c_long, I, C.c_ulonglong, P],
@@ -363,6 +366,7 @@ _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,
              'st_gemm_wgrad_workspace_floats': C.c_size_t, 'st_gemm_wgrad_batch_workspace_floats': C.c_size_t, 'st_freq_loss_workspace_floats': C.c_size_t, 'st_attn_fin_split_workspace_floats': C.c_size_t, 'st_attn_rng_xchg_words': C.c_size_t, 'st_colreduce_workspace_floats': C.c_size_t, 'st_mt_blocks': C.c_size_t, 'st_mt_table_misses': C.c_long,
              'st_bn_bank_workspace_floats': C.c_size_t, 'st_istft_workspace_floats': C.c_size_t, 'st_gl_workspace_floats': C.c_size_t,
+             'st_gl_batch_workspace_floats': C.c_size_t,
              'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t}
 
 _lib = None

@@ -5,8 +5,11 @@ spectrogram -> waveform by Griffin-Lim (st_griffin_lim / st_stft_fwd / st_istft)
     wav, sr = conv.feat_to_wave(linear_pred)          # (T, F) or (B, T, F), CPU or device tensor -> float64 numpy
     write_wav('utt-pred.wav', wav[0], sr)
 
-Only the linear branch of feat_to_wave (src/audio.py:397-407) is here: the mel -> linear pseudo-inverse (:194-205) raises
-NotImplementedError.
+feat_to_wave keeps to the linear branch of src/audio.py:397-407; the mel branch (the pseudo-inverse of :194-205, st_mel_to_linear)
+is mel_to_wave, and a list of utterances of differing lengths is vocoded in one call by vocode_batch (st_griffin_lim_batch):
+
+    wav, sr = conv.mel_to_wave(mel_pred)                # (T, n_mels) or (B, T, n_mels)
+    wavs = conv.vocode_batch([np.load(f) for f in files], 'spec')      # [(T_i, F)] -> [hop * (T_i - 1) samples]
 
 Analysis side (st_audio_features): waveform -> normalised mel / linear spectrograms and the augmented mel of the training loader.
 
@@ -50,6 +53,28 @@ def check_dims(n_fft, hop, win, T):
                          'i.e. T >= %d' % (T, hop, n_fft, n_fft // 2 // hop + 2))
 
 
+def min_frames(n_fft, hop):
+    """the fewest frames check_dims takes: hop * (T - 1) > n_fft // 2"""
+    return n_fft // 2 // hop + 2
+
+
+def check_frames(frames, B, n_fft, hop, T):
+    """per-utterance frame counts of a ragged batch -> int32 array (B,); raises ValueError unless they are B integers in
+    [min_frames, T] (check_dims' "too few" rule for every utterance)"""
+    arr = np.asarray(frames.cpu() if torch.is_tensor(frames) else frames)
+    if arr.shape != (B,) or not (np.issubdtype(arr.dtype, np.integer) or (arr.dtype.kind == 'f' and np.all(arr == np.floor(arr)))):
+        raise ValueError('Griffin-Lim: frames must be %d integers (one per utterance), got %s of shape %s'
+                         % (B, arr.dtype, arr.shape))
+    lo = min_frames(n_fft, hop)
+    for b, n in enumerate(arr.tolist()):
+        if n < lo:
+            raise ValueError('Griffin-Lim: utterance %d: %d frames are too few: reflect padding needs hop * (T - 1) > n_fft // 2 '
+                             '(hop %d, n_fft %d), i.e. T >= %d' % (b, n, hop, n_fft, lo))
+        if n > T:
+            raise ValueError('Griffin-Lim: utterance %d: %d frames, the batch holds %d' % (b, n, T))
+    return arr.astype(np.int32)
+
+
 def draw_phases(shape):
     """initial phases as src/audio.py:214-216: uniform in [0, 2 pi) from np.random, wrapped by np.angle(np.exp(1j phi)), float32"""
     return np.angle(np.exp(2j * np.pi * np.random.rand(*shape))).astype(np.float32)
@@ -61,12 +86,19 @@ def _device():
     return torch.device('cuda', torch.cuda.current_device())
 
 
-def _run(feat_btf, phases, n_fft, hop, win, n_iter, normalized, power, post):
-    """feat_btf: (B, T, F) view, any strides; phases: (B, F, T) array/tensor or None (drawn).  -> (B, hop * (T - 1)) device tensor"""
-    B, T, F = feat_btf.shape
-    if F != n_fft // 2 + 1:
-        raise ValueError('Griffin-Lim: %d frequency bins, expected n_fft // 2 + 1 = %d' % (F, n_fft // 2 + 1))
+def _run(feat_btf, phases, n_fft, hop, win, n_iter, normalized, power, post, basis=None, frames=None):
+    """feat_btf: (B, T, F) view, any strides -- or (B, T, n_mels) with `basis`, a callable device -> (n_mels, F) tensor, called
+    once every check has passed; phases: (B, F, T) array/tensor or None (drawn); frames: per-utterance frame counts or None.
+    -> (B, hop * (T - 1)) device tensor.  Every refusal is raised before a device is touched."""
+    B, T, D = feat_btf.shape
+    F = n_fft // 2 + 1
+    if basis is None and D != F:
+        raise ValueError('Griffin-Lim: %d frequency bins, expected n_fft // 2 + 1 = %d' % (D, F))
+    if basis is not None and power != 1.0:
+        raise ValueError('Griffin-Lim: mel input is an amplitude (the reference\'s isAmp branch): power must be 1, got %g' % power)
     check_dims(n_fft, hop, win, T)
+    if frames is not None:
+        frames = check_frames(frames, B, n_fft, hop, T)
     if phases is None:
         phases = draw_phases((B, F, T))
     phases = torch.as_tensor(phases, dtype=torch.float32)
@@ -74,8 +106,12 @@ def _run(feat_btf, phases, n_fft, hop, win, n_iter, normalized, power, post):
         raise ValueError('Griffin-Lim: phases of shape %s, expected %s' % (tuple(phases.shape), (B, F, T)))
     dev = feat_btf.device if feat_btf.is_cuda else _device()
     feat_btf = feat_btf.to(dev, torch.float32)
-    return ops.griffin_lim(feat_btf, phases.to(dev).contiguous(), n_fft, hop, win, n_iter=n_iter, normalized=normalized,
-                           power=power, post=post)
+    if basis is None and frames is None:
+        return ops.griffin_lim(feat_btf, phases.to(dev).contiguous(), n_fft, hop, win, n_iter=n_iter, normalized=normalized,
+                               power=power, post=post)
+    return ops.griffin_lim_batch(feat_btf, phases.to(dev).contiguous(), n_fft, hop, win, n_iter=n_iter, normalized=normalized,
+                                 power=power, post=post, basis=None if basis is None else basis(dev),
+                                 frames=None if frames is None else torch.from_numpy(frames).to(dev))
 
 
 def griffin_lim(amp, phases=None, n_iter=GFL_ITER, n_fft=DEFAULT_N_FFT, hop=DEFAULT_HOP, win=DEFAULT_WIN):
@@ -99,6 +135,7 @@ class AudioConverter:
         self.frame_length_ms, self.frame_shift_ms = frame_length_ms, frame_shift_ms
         self.snr_range, self.time_stretch_range = list(snr_range), list(time_stretch_range)
         self._fb = {}
+        self._basis = {}
         self.num_freq, self.n_mels = num_freq, num_mels
         self.preemphasis_coeff = preemphasis_coeff       # read by the reference's _preemphasis only, never by the inverse (:274-276)
         self.sr = sample_rate
@@ -120,11 +157,86 @@ class AudioConverter:
 
     def feat_to_wave(self, feat, phases=None):
         """src/audio.py:397-407: the decoder's (T, F) or (B, T, F) linear output -> (float64 waveform(s), sample rate).
-        The reference transposes to (F, T) and draws its phases in that shape; here the first kernel reads (B, T, F) directly."""
+        The reference transposes to (F, T) and draws its phases in that shape; here the first kernel reads (B, T, F) directly.
+        Mel-sized input is refused here; mel_to_wave is the reference's mel branch."""
         if feat.size(-1) == self.feat_dim[0] and feat.size(-1) != self.num_freq:
             raise NotImplementedError('feat_to_wave: mel input (%d bins): the mel -> linear pseudo-inverse of src/audio.py:194-205 '
                                       "needs librosa's filterbank and is not implemented; pass the linear spectrogram" % feat.size(-1))
         return self.specgram_to_waveform(feat.transpose(-2, -1), phases=phases), self.sr
+
+    def mel_basis(self, device=None):
+        """mel_basis(sr, n_fft, n_mels) of this converter, computed once: the float32 numpy array (device None) or its copy on
+        `device`, cached per device like filterbank.  Raises ValueError for a rank-deficient bank."""
+        if None not in self._basis:
+            self._basis[None] = mel_basis(self.sr, self.n_fft, self.n_mels)
+        if device is None:
+            return self._basis[None]
+        key = str(device)
+        if key not in self._basis:
+            self._basis[key] = torch.from_numpy(self._basis[None]).to(device)
+        return self._basis[key]
+
+    def _check_mel(self, width):
+        if width != self.n_mels:
+            raise ValueError('mel vocoding: %d mel bins, expected num_mels = %d' % (width, self.n_mels))
+        if self.n_fft not in SUPPORTED_N_FFT:
+            raise ValueError('mel vocoding: n_fft %d not supported (one of %s)' % (self.n_fft, SUPPORTED_N_FFT))
+        if not 1 <= self.n_mels <= ops.MEL_MAX:
+            raise ValueError('mel vocoding: %d mels outside [1, %d]' % (self.n_mels, ops.MEL_MAX))
+        self.mel_basis()                                 # (a rank-deficient bank raises here, on the host)
+
+    def melspecgram_to_specgram(self, melspecgram):
+        """src/audio.py:194-205: normalised mel (n_mels, T) or (B, n_mels, T) -> the signed amplitude spectrogram (F, T) /
+        (B, F, T) = pinverse(fb).T @ db_to_amp(denormalize(mel) + REF_LEVEL_DB), on the device"""
+        squeeze = melspecgram.dim() == 2
+        m = melspecgram.unsqueeze(0) if squeeze else melspecgram
+        self._check_mel(m.size(1))
+        dev = m.device if m.is_cuda else _device()
+        lin = ops.mel_to_linear(m.to(dev, torch.float32).transpose(1, 2), self.mel_basis(dev), normalized=True, take_abs=False)
+        lin = lin.transpose(1, 2)
+        return lin[0] if squeeze else lin
+
+    def mel_to_wave(self, mel, phases=None, frames=None):
+        """The mel branch of src/audio.py:397-407: the decoder's (T, n_mels) or (B, T, n_mels) mel output -> (float64 waveform(s),
+        sample rate).  phases: (F, T) / (B, F, T) as the reference draws them; frames: per-utterance frame counts of a padded batch
+        (row b is then zero beyond hop * (frames[b] - 1) samples).  Product, Griffin-Lim, inverse pre-emphasis and clip on the device."""
+        squeeze = mel.dim() == 2
+        m = mel.unsqueeze(0) if squeeze else mel
+        if phases is not None and squeeze:
+            phases = torch.as_tensor(phases).unsqueeze(0)
+        wav = self.gen_wav_device(m, phases, frames=frames, mel=True).cpu().numpy().astype(np.float64)
+        return (wav[0] if squeeze else wav), self.sr
+
+    def vocode_batch(self, feats, kind='spec'):
+        """Utterances of differing lengths in one st_griffin_lim_batch call (the file loop of the reference's
+        util/gen_wav_from_specgram.py as one batch): feats, a list of (T_i, D) normalised spectrograms, D = num_freq for kind 'spec'
+        or num_mels for 'mel' -> list of float64 waveforms of hop * (T_i - 1) samples, in the given order.  The initial phases are
+        drawn per utterance in that order as draw_phases((F, T_i)): one np.random seed gives the reference loop's phases."""
+        if kind not in ('spec', 'mel'):
+            raise ValueError("vocode_batch: kind %r is neither 'spec' nor 'mel'" % (kind,))
+        feats = [torch.as_tensor(f) for f in feats]
+        if not feats:
+            raise ValueError('vocode_batch: an empty batch')
+        D = self.num_freq if kind == 'spec' else self.n_mels
+        for i, f in enumerate(feats):
+            if f.dim() != 2 or f.size(1) != D:
+                raise ValueError('vocode_batch: utterance %d has shape %s, expected (T, %d) for kind %r' % (i, tuple(f.shape), D, kind))
+        if kind == 'mel':
+            self._check_mel(D)
+        F = self.n_fft // 2 + 1
+        lens = [int(f.size(0)) for f in feats]
+        B, T = len(feats), max(lens)
+        check_dims(self.n_fft, self.hop_length, self.win_length, T)
+        check_frames(lens, B, self.n_fft, self.hop_length, T)
+        phases = np.zeros((B, F, T), np.float32)
+        for b, n in enumerate(lens):
+            phases[b, :, :n] = draw_phases((F, n))
+        dev = feats[0].device if feats[0].is_cuda else _device()
+        batch = torch.zeros(B, T, D, device=dev, dtype=torch.float32)
+        for b, f in enumerate(feats):
+            batch[b, :lens[b]] = f.to(dev, torch.float32)
+        wav = self.gen_wav_device(batch, phases, frames=lens, mel=kind == 'mel').cpu().numpy().astype(np.float64)
+        return [wav[b, :self.hop_length * (n - 1)] for b, n in enumerate(lens)]
 
     # -- analysis side (src/audio.py:68-77, 156-177, 329-395)
     def load(self, wav_path):
@@ -221,12 +333,15 @@ class AudioConverter:
                                            snr_db=snr_db, noise=nz, seed=seed)
         return mel, aug, lin
 
-    def gen_wav_device(self, lin, phases=None):
-        """feat_to_wave for a device batch (B, T, F) without the host copy: -> (B, hop * (T - 1)) device tensor (SpecgramGenerator)"""
-        if lin.size(-1) != self.num_freq:
+    def gen_wav_device(self, lin, phases=None, frames=None, mel=False):
+        """feat_to_wave for a device batch (B, T, F) without the host copy: -> (B, hop * (T - 1)) device tensor (SpecgramGenerator).
+        mel=True: `lin` is the mel output (B, T, n_mels) instead (mel_to_wave).  frames: per-utterance frame counts (vocode_batch)."""
+        if mel:
+            self._check_mel(lin.size(-1))
+        elif lin.size(-1) != self.num_freq:
             raise NotImplementedError('gen_wav: only the linear spectrogram (%d bins) is vocoded, got %d' % (self.num_freq, lin.size(-1)))
         return _run(lin, phases, self.n_fft, self.hop_length, self.win_length, GFL_ITER, normalized=True, power=1.0,
-                    post=ops.GL_CLIP | ops.GL_INV_PREEMPHASIS)
+                    post=ops.GL_CLIP | ops.GL_INV_PREEMPHASIS, basis=self.mel_basis if mel else None, frames=frames)
 
 
 def load_audio_transform(num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear=True,
@@ -282,6 +397,22 @@ def mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     fall = (f[2:, None] - freqs[None, :]) / (f[2:] - f[1:-1])[:, None]
     w = np.maximum(0.0, np.minimum(rise, fall)) * (2.0 / (f[2:] - f[:-2]))[:, None]
     return w.astype(np.float32)
+
+
+RANK_RATIO_MIN = 1e-6             # smallest / largest singular value below which a filterbank counts as rank deficient
+
+
+def mel_basis(sr, n_fft, n_mels):
+    """(n_mels, n_fft // 2 + 1) float32: pinverse(mel_filterbank).T, the matrix of melspecgram_to_specgram (src/audio.py:202), in
+    float64 and cast once.  A rank-deficient bank (smallest / largest singular value < 1e-6: mel bands narrower than one FFT bin
+    give zero rows) raises ValueError: its pseudo-inverse is not a usable inverse (the reference's float32 torch.pinverse returns
+    values off by orders of magnitude there)."""
+    fb = mel_filterbank(sr, n_fft, n_mels).astype(np.float64)
+    sv = np.linalg.svd(fb, compute_uv=False)
+    if not sv[-1] >= RANK_RATIO_MIN * sv[0]:
+        raise ValueError('mel_basis: the mel filterbank (%d Hz, n_fft %d, %d mels) is rank deficient (singular values %.3g .. %.3g): '
+                         'mel -> linear has no usable pseudo-inverse; use fewer mels or a larger n_fft' % (sr, n_fft, n_mels, sv[-1], sv[0]))
+    return np.ascontiguousarray(np.linalg.pinv(fb).T.astype(np.float32))
 
 
 def band_pack(fb):

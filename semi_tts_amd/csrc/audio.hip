@@ -174,6 +174,11 @@ __device__ __forceinline__ float ola_at(const float* __restrict__ fr, int i, int
     return acc;
 }
 
+// Ragged batches (st_griffin_lim_batch): utterance b has nfr[b] of the T stored frames, clamped into [tmin, T] with tmin the
+// fewest frames check_dims takes (hop (tmin - 1) > n_fft / 2), so whatever nfr holds, every index stays inside the storage of
+// the utterance's T frames.  Storage strides stay those of T; reflect padding, overlap-add and envelope use the utterance's own.
+__device__ __forceinline__ int ragged_frames(const int* __restrict__ nfr, int b, int tmin, int T) { return min(max(nfr[b], tmin), T); }
+
 // C2R of the frame's spectrum (already merged + conjugated into buf) -> window -> frames_out.  buf holds conj(Z').
 template <int N>
 __device__ __forceinline__ void inverse_to_frame(float2* buf, const float2* __restrict__ tw, const float* __restrict__ wnd,
@@ -193,50 +198,69 @@ __device__ __forceinline__ void inverse_to_frame(float2* buf, const float2* __re
 // ------------------------------------------------------------------ setup: window and inverse envelope (double)
 // wnd[n] = hann_window(win, periodic)[n] (ref: src/audio.py:35); inv_env[i] = 1 / sum_t' wpad(i + N/2 - t' hop)^2 for the
 // trimmed iSTFT output i in [0, L) (ref: lib/istft.py window_envelop, trimmed by n_fft//2).
+__device__ __forceinline__ float inv_envelope_at(int idx, int N, int T, int hop, int win) {
+    const int half = N / 2, left = (N - win) / 2;
+    const int s = idx + half - left;
+    const int hi = min(T - 1, s / hop);
+    const int lo = s - win + 1 <= 0 ? 0 : (s - win + hop) / hop;
+    double env = 0.0;
+    for (int tp = lo; tp <= hi; ++tp) {
+        const double w = 0.5 - 0.5 * cospi(2.0 * (double)(s - tp * hop) / (double)win);
+        env += w * w;
+    }
+    return (float)(1.0 / env);
+}
+
 __global__ void gl_setup_kernel(float* __restrict__ wnd, float* __restrict__ inv_env, int N, int T, int hop, int win, int L) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < win) wnd[idx] = (float)(0.5 - 0.5 * cospi(2.0 * (double)idx / (double)win));
-    if (inv_env && idx < L) {
-        const int half = N / 2, left = (N - win) / 2;
-        const int s = idx + half - left;
-        const int hi = min(T - 1, s / hop);
-        const int lo = s - win + 1 <= 0 ? 0 : (s - win + hop) / hop;
-        double env = 0.0;
-        for (int tp = lo; tp <= hi; ++tp) {
-            const double w = 0.5 - 0.5 * cospi(2.0 * (double)(s - tp * hop) / (double)win);
-            env += w * w;
-        }
-        inv_env[idx] = (float)(1.0 / env);
-    }
+    if (inv_env && idx < L) inv_env[idx] = inv_envelope_at(idx, N, T, hop, win);
+}
+
+// The ragged form: one envelope per utterance (its own frame count: the right edge differs), env_stride floats apart.  Grid (., B).
+__global__ void gl_setup_ragged_kernel(float* __restrict__ wnd, float* __restrict__ inv_env, size_t env_stride, int N, int T, int hop,
+                                       int win, const int* __restrict__ nfr, int tmin) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (b == 0 && idx < win) wnd[idx] = (float)(0.5 - 0.5 * cospi(2.0 * (double)idx / (double)win));
+    const int Tb = ragged_frames(nfr, b, tmin, T);
+    if (idx < hop * (Tb - 1)) inv_env[b * env_stride + idx] = inv_envelope_at(idx, N, Tb, hop, win);
 }
 
 // ------------------------------------------------------------------ first iSTFT
-// FROM_FEAT: Y = amp * e^{i phase} with amp from the (normalised) decoder output read through strides (the (B, T, F) -> (B, F, T)
+// SRC_FEAT: Y = amp * e^{i phase} with amp from the (normalised) decoder output read through strides (the (B, T, F) -> (B, F, T)
 // transpose of src/audio.py:401 and the denormalisation of :186-188, :281-288 fused here; amp is also written to amp_out as
-// (B, T, F) for the iterations).  Else Y is a complex spectrum (B, T, F, 2).  Grid (T, B).
-template <int N, bool FROM_FEAT>
+// (B, T, F) for the iterations).  SRC_AMP: feat is that (B, T, F) magnitude already (mel_to_linear_kernel wrote it): read, not
+// written again.  SRC_SPEC: Y is a complex spectrum (B, T, F, 2).  Grid (T, B).  RAGGED: frames t >= nfr[b] leave at once.
+enum { SRC_SPEC = 0, SRC_FEAT = 1, SRC_AMP = 2 };
+
+template <int N, int SRC, bool RAGGED>
 __global__ __launch_bounds__(GL_THREADS) void gl_first_istft_kernel(const float* __restrict__ feat, long sb, long st, long sf,
                                                                   int normalized, float power, const float* __restrict__ phases,
                                                                   const float2* __restrict__ spec, float* __restrict__ amp_out,
                                                                   const float* __restrict__ wnd, float* __restrict__ frames, int T,
-                                                                  int win) {
+                                                                  int win, const int* __restrict__ nfr, int tmin) {
     constexpr int M = N / 2, F = M + 1;
     __shared__ float2 buf[M];
     const float2* tw = tw_table<N>();
     const int t = blockIdx.x, b = blockIdx.y;
+    if constexpr (RAGGED) {
+        if (t >= ragged_frames(nfr, b, tmin, T)) return;
+    }
     const size_t frame = (size_t)b * T + t;
     auto load_y = [&](int k) -> float2 {
-        if constexpr (FROM_FEAT) {
+        if constexpr (SRC != SRC_SPEC) {
             float a = feat[b * sb + t * st + k * sf];
-            if (normalized) {
-                a = MIN_LEVEL_DB + fminf(fmaxf(a, 0.0f), 1.0f) * -MIN_LEVEL_DB;     // _denormalize  (:287-288)
-                a = powf(10.0f, 0.05f * (a + REF_LEVEL_DB));                        // _db_to_amp(x + REF_LEVEL_DB)  (:187, :284)
-                if (power != 1.0f) a = powf(a, power);                               // ** power  (:188)
+            if constexpr (SRC == SRC_FEAT) {
+                if (normalized) {
+                    a = MIN_LEVEL_DB + fminf(fmaxf(a, 0.0f), 1.0f) * -MIN_LEVEL_DB;     // _denormalize  (:287-288)
+                    a = powf(10.0f, 0.05f * (a + REF_LEVEL_DB));                        // _db_to_amp(x + REF_LEVEL_DB)  (:187, :284)
+                    if (power != 1.0f) a = powf(a, power);                               // ** power  (:188)
+                }
+                a = fabsf(a);                                                            // magnitude = specgram.abs()  (:217)
+                amp_out[frame * F + k] = a;
             }
-            a = fabsf(a);                                                            // magnitude = specgram.abs()  (:217)
-            amp_out[frame * F + k] = a;
             const float ph = phases[((size_t)b * F + k) * T + t];
-            return make_float2(a * cosf(ph), a * sinf(ph));                         // _to_complex  (:264-268)
+            return make_float2(a * cosf(ph), a * sinf(ph));                             // _to_complex  (:264-268)
         } else {
             return spec[frame * F + k];
         }
@@ -255,24 +279,33 @@ __global__ __launch_bounds__(GL_THREADS) void gl_first_istft_kernel(const float*
 
 // ------------------------------------------------------------------ one Griffin-Lim iteration (ref: src/audio.py:219-225)
 // x = istft(Y_prev) gathered from the previous frames (overlap-add / envelope, reflect-padded), STFT frame t of x, phase
-// projection Y = amp * X / |X| (angle(0) = 0: amp + 0i), then this frame of the next istft.  Grid (T, B).
-template <int N>
+// projection Y = amp * X / |X| (angle(0) = 0: amp + 0i), then this frame of the next istft.  Grid (T, B).  RAGGED: utterance b
+// has Tb = nfr[b] frames and Lb = hop (Tb - 1) samples (padding, overlap-add and envelope are its own); frames t >= Tb leave at once.
+template <int N, bool RAGGED>
 __global__ __launch_bounds__(GL_THREADS) void gl_iter_kernel(const float* __restrict__ frames_in, float* __restrict__ frames_out,
                                                            const float* __restrict__ amp, const float* __restrict__ wnd,
-                                                           const float* __restrict__ inv_env, int T, int hop, int win, int L) {
+                                                           const float* __restrict__ inv_env, int T, int hop, int win, int L,
+                                                           const int* __restrict__ nfr, int tmin, size_t env_stride) {
     constexpr int M = N / 2, F = M + 1, HALF = N / 2;
     __shared__ float2 buf[M];
     float* xr = reinterpret_cast<float*>(buf);
     const float2* tw = tw_table<N>();
     const int t = blockIdx.x, b = blockIdx.y;
+    int Tb = T, Lb = L;
+    if constexpr (RAGGED) {
+        Tb = ragged_frames(nfr, b, tmin, T);
+        if (t >= Tb) return;
+        Lb = hop * (Tb - 1);
+        inv_env += b * env_stride;
+    }
     const int left = (N - win) / 2;
     const float* fr = frames_in + (size_t)b * T * win;
     for (int n = threadIdx.x; n < N; n += GL_THREADS) {
         const int nn = n - left;
         float v = 0.0f;
         if (nn >= 0 && nn < win) {
-            const int i = reflect_index(t * hop + n - HALF, L);
-            v = ola_at(fr, i, T, hop, win, HALF, left) * inv_env[i] * wnd[nn];
+            const int i = reflect_index(t * hop + n - HALF, Lb);
+            v = ola_at(fr, i, Tb, hop, win, HALF, left) * inv_env[i] * wnd[nn];
         }
         xr[n] = v;
     }
@@ -335,8 +368,11 @@ __global__ __launch_bounds__(GL_THREADS) void stft_kernel(const float* __restric
 // the 1024 chunk ends, the carry of one 16384-sample tile into the next; post & 2: clip to [-1, 1] (:192).
 __device__ __forceinline__ int ola_slot(int j) { return (j >> 4) * (OLA_CHUNK + 1) + (j & (OLA_CHUNK - 1)); }   // padded: no bank conflicts
 
+// RAGGED: row b holds Lb = hop (nfr[b] - 1) samples of its own overlap-add, scan and clip, and zeros from there to L.
+template <bool RAGGED>
 __global__ __launch_bounds__(OLA_THREADS) void gl_ola_post_kernel(const float* __restrict__ frames, const float* __restrict__ inv_env,
-                                                                 float* __restrict__ out, int N, int T, int hop, int win, int L, int post) {
+                                                                 float* __restrict__ out, int N, int T, int hop, int win, int L, int post,
+                                                                 const int* __restrict__ nfr, int tmin, size_t env_stride) {
     __shared__ float xs[OLA_THREADS * (OLA_CHUNK + 1)];
     __shared__ float scan[2][OLA_THREADS];
     __shared__ float carry;
@@ -344,6 +380,12 @@ __global__ __launch_bounds__(OLA_THREADS) void gl_ola_post_kernel(const float* _
     const int half = N / 2, left = (N - win) / 2;
     const float* fr = frames + (size_t)b * T * win;
     float* ob = out + (size_t)b * L;
+    if constexpr (RAGGED) {
+        T = ragged_frames(nfr, b, tmin, T);
+        for (int i = hop * (T - 1) + tid; i < L; i += OLA_THREADS) ob[i] = 0.0f;
+        L = hop * (T - 1);
+        inv_env += b * env_stride;
+    }
     const float m16 = powf(INV_PREEMPH, (float)OLA_CHUNK);
     if (tid == 0) carry = 0.0f;
     for (int base = 0; base < L; base += OLA_TILE) {
@@ -393,6 +435,59 @@ __global__ __launch_bounds__(OLA_THREADS) void gl_ola_post_kernel(const float* _
         }
         __syncthreads();
     }
+}
+
+// ------------------------------------------------------------------ mel -> linear amplitude (ref: src/audio.py:194-205)
+// lin[b, t, k] = sum_m basis[m, k] a[b, t, m], basis (n_mels, F) = pinverse(filterbank)^T, a = _db_to_amp(_denormalize(mel) +
+// REF_LEVEL_DB) (normalized) or mel itself.  One workgroup: MEL_TILE frames x 256 bins; the tile's a values are staged in LDS
+// once, a thread keeps one accumulator per frame for its bin, so a basis element read once (coalesced along k) serves every
+// frame of the tile.  Each accumulator runs over ascending m with fmaf from 0: a row's result depends on neither the tile, the
+// batch nor its position in them.  Grid (ceil(F / 256), ceil(T / MEL_TILE), B).  nfr (or null): frames t >= nfr[b] are neither
+// read nor written.
+constexpr int MEL_TILE = 16;
+constexpr int MEL_MAX = 256;
+
+__global__ __launch_bounds__(GL_THREADS) void mel_to_linear_kernel(const float* __restrict__ mel, long sb, long st, long sm,
+                                                                  const float* __restrict__ basis, float* __restrict__ lin, int T,
+                                                                  int n_mels, int F, int normalized, int take_abs,
+                                                                  const int* __restrict__ nfr, int tmin) {
+    __shared__ __attribute__((aligned(16))) float a_s[MEL_MAX * MEL_TILE];      // [m][frame of the tile]
+    const int k = blockIdx.x * GL_THREADS + threadIdx.x, t0 = blockIdx.y * MEL_TILE, b = blockIdx.z;
+    const int nt = min(MEL_TILE, (nfr ? ragged_frames(nfr, b, tmin, T) : T) - t0);
+    if (nt <= 0) return;                                     // (the whole workgroup: before the barrier)
+    for (int idx = threadIdx.x; idx < MEL_TILE * n_mels; idx += GL_THREADS) {
+        const int f = idx / n_mels, m = idx - f * n_mels;
+        float a = 0.0f;
+        if (f < nt) {
+            a = mel[b * sb + (t0 + f) * st + m * sm];
+            if (normalized) {
+                a = MIN_LEVEL_DB + fminf(fmaxf(a, 0.0f), 1.0f) * -MIN_LEVEL_DB;         // the expressions of gl_first_istft_kernel
+                a = powf(10.0f, 0.05f * (a + REF_LEVEL_DB));
+            }
+        }
+        a_s[m * MEL_TILE + f] = a;
+    }
+    __syncthreads();
+    if (k >= F) return;
+    float acc[MEL_TILE];
+#pragma unroll
+    for (int f = 0; f < MEL_TILE; ++f) acc[f] = 0.0f;
+    for (int m = 0; m < n_mels; ++m) {
+        const float w = basis[(size_t)m * F + k];
+        const float4* av = reinterpret_cast<const float4*>(a_s + m * MEL_TILE);
+#pragma unroll
+        for (int q = 0; q < MEL_TILE / 4; ++q) {
+            const float4 v = av[q];
+            acc[4 * q] = fmaf(w, v.x, acc[4 * q]);
+            acc[4 * q + 1] = fmaf(w, v.y, acc[4 * q + 1]);
+            acc[4 * q + 2] = fmaf(w, v.z, acc[4 * q + 2]);
+            acc[4 * q + 3] = fmaf(w, v.w, acc[4 * q + 3]);
+        }
+    }
+    float* o = lin + ((size_t)b * T + t0) * F + k;
+#pragma unroll
+    for (int f = 0; f < MEL_TILE; ++f)
+        if (f < nt) o[(size_t)f * F] = take_abs ? fabsf(acc[f]) : acc[f];
 }
 
 // ------------------------------------------------------------------ feature extraction (ref: src/audio.py:156-177, 329-395, 409-437)
@@ -601,17 +696,52 @@ template <int N>
 void launch_first(bool from_feat, const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases,
                   const float* spec, float* amp, const float* wnd, float* frames, int B, int T, int win, hipStream_t s) {
     if (from_feat)
-        hipLaunchKernelGGL((gl_first_istft_kernel<N, true>), dim3(T, B), dim3(GL_THREADS), 0, s, feat, sb, st, sf, normalized, power,
-                           phases, (const float2*)nullptr, amp, wnd, frames, T, win);
+        hipLaunchKernelGGL((gl_first_istft_kernel<N, SRC_FEAT, false>), dim3(T, B), dim3(GL_THREADS), 0, s, feat, sb, st, sf, normalized,
+                           power, phases, (const float2*)nullptr, amp, wnd, frames, T, win, (const int*)nullptr, 0);
     else
-        hipLaunchKernelGGL((gl_first_istft_kernel<N, false>), dim3(T, B), dim3(GL_THREADS), 0, s, (const float*)nullptr, 0L, 0L, 0L,
-                           0, 1.0f, (const float*)nullptr, (const float2*)spec, (float*)nullptr, wnd, frames, T, win);
+        hipLaunchKernelGGL((gl_first_istft_kernel<N, SRC_SPEC, false>), dim3(T, B), dim3(GL_THREADS), 0, s, (const float*)nullptr, 0L, 0L,
+                           0L, 0, 1.0f, (const float*)nullptr, (const float2*)spec, (float*)nullptr, wnd, frames, T, win,
+                           (const int*)nullptr, 0);
 }
 
 template <int N>
 void launch_iter(const float* fin, float* fout, const float* amp, const float* wnd, const float* inv_env, int B, int T, int hop, int win,
                  int L, hipStream_t s) {
-    hipLaunchKernelGGL((gl_iter_kernel<N>), dim3(T, B), dim3(GL_THREADS), 0, s, fin, fout, amp, wnd, inv_env, T, hop, win, L);
+    hipLaunchKernelGGL((gl_iter_kernel<N, false>), dim3(T, B), dim3(GL_THREADS), 0, s, fin, fout, amp, wnd, inv_env, T, hop, win, L,
+                       (const int*)nullptr, 0, (size_t)0);
+}
+
+// the ragged forms, and the first iSTFT from a magnitude already in the workspace (st_griffin_lim_batch)
+template <int N>
+void launch_first_ragged(bool from_amp, const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases,
+                         float* amp, const float* wnd, float* frames, int B, int T, int win, const int* nfr, int tmin, hipStream_t s) {
+    if (from_amp)
+        hipLaunchKernelGGL((gl_first_istft_kernel<N, SRC_AMP, true>), dim3(T, B), dim3(GL_THREADS), 0, s, feat, sb, st, sf, 0, 1.0f,
+                           phases, (const float2*)nullptr, (float*)nullptr, wnd, frames, T, win, nfr, tmin);
+    else
+        hipLaunchKernelGGL((gl_first_istft_kernel<N, SRC_FEAT, true>), dim3(T, B), dim3(GL_THREADS), 0, s, feat, sb, st, sf, normalized,
+                           power, phases, (const float2*)nullptr, amp, wnd, frames, T, win, nfr, tmin);
+}
+
+template <int N>
+void launch_first_amp(const float* amp, const float* phases, const float* wnd, float* frames, int B, int T, int win, hipStream_t s) {
+    hipLaunchKernelGGL((gl_first_istft_kernel<N, SRC_AMP, false>), dim3(T, B), dim3(GL_THREADS), 0, s, amp, (long)T * (N / 2 + 1),
+                       (long)(N / 2 + 1), 1L, 0, 1.0f, phases, (const float2*)nullptr, (float*)nullptr, wnd, frames, T, win,
+                       (const int*)nullptr, 0);
+}
+
+template <int N>
+void launch_iter_ragged(const float* fin, float* fout, const float* amp, const float* wnd, const float* inv_env, size_t env_stride, int B,
+                        int T, int hop, int win, int L, const int* nfr, int tmin, hipStream_t s) {
+    hipLaunchKernelGGL((gl_iter_kernel<N, true>), dim3(T, B), dim3(GL_THREADS), 0, s, fin, fout, amp, wnd, inv_env, T, hop, win, L, nfr,
+                       tmin, env_stride);
+}
+
+void launch_mel_to_linear(const float* mel, long sb, long st, long sm, const float* basis, float* lin, int B, int T, int n_mels, int F,
+                          int normalized, int take_abs, const int* nfr, int tmin, hipStream_t s) {
+    const dim3 grid((F + GL_THREADS - 1) / GL_THREADS, (T + MEL_TILE - 1) / MEL_TILE, B);
+    hipLaunchKernelGGL(mel_to_linear_kernel, grid, dim3(GL_THREADS), 0, s, mel, sb, st, sm, basis, lin, T, n_mels, F, normalized,
+                       take_abs, nfr, tmin);
 }
 
 #define ST_AUDIO_DISPATCH(n_fft, F, ...) \
@@ -665,7 +795,8 @@ extern "C" int st_istft(const float* spec, float* x, int B, int T, int n_fft, in
     float* frames = inv_env + round64(L);
     hipLaunchKernelGGL(gl_setup_kernel, dim3((max(L, win) + 255) / 256), dim3(256), 0, s, wnd, inv_env, n_fft, T, hop, win, L);
     ST_AUDIO_DISPATCH(n_fft, launch_first, false, nullptr, 0, 0, 0, 0, 1.0f, nullptr, spec, nullptr, wnd, frames, B, T, win, s);
-    hipLaunchKernelGGL(gl_ola_post_kernel, dim3(B), dim3(OLA_THREADS), 0, s, frames, inv_env, x, n_fft, T, hop, win, L, 0);
+    hipLaunchKernelGGL(gl_ola_post_kernel<false>, dim3(B), dim3(OLA_THREADS), 0, s, frames, inv_env, x, n_fft, T, hop, win, L, 0,
+                       (const int*)nullptr, 0, (size_t)0);
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -690,7 +821,82 @@ extern "C" int st_griffin_lim(const float* feat, long sb, long st, long sf, int 
     ST_AUDIO_DISPATCH(n_fft, launch_first, true, feat, sb, st, sf, normalized, power, phases, nullptr, amp, wnd, fr[0], B, T, win, s);
     for (int it = 0; it < n_iter; ++it)
         ST_AUDIO_DISPATCH(n_fft, launch_iter, fr[it & 1], fr[(it + 1) & 1], amp, wnd, inv_env, B, T, hop, win, L, s);
-    hipLaunchKernelGGL(gl_ola_post_kernel, dim3(B), dim3(OLA_THREADS), 0, s, fr[n_iter & 1], inv_env, wav, n_fft, T, hop, win, L, post);
+    hipLaunchKernelGGL(gl_ola_post_kernel<false>, dim3(B), dim3(OLA_THREADS), 0, s, fr[n_iter & 1], inv_env, wav, n_fft, T, hop, win, L,
+                       post, (const int*)nullptr, 0, (size_t)0);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_mel_to_linear(const float* mel, long sb, long st, long sm, const float* basis, float* lin, int B, int T, int n_mels, int F,
+                                int normalized, int take_abs, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(mel && basis && lin, "st_mel_to_linear: null pointer");
+    ST_CHECK_ARG(n_mels >= 1 && n_mels <= MEL_MAX, "st_mel_to_linear: %d mels outside [1, %d]", n_mels, MEL_MAX);
+    ST_CHECK_ARG(F == 257 || F == 513 || F == 1025 || F == 2049, "st_mel_to_linear: %d bins is not n_fft / 2 + 1 of a supported n_fft", F);
+    ST_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && (T + MEL_TILE - 1) / MEL_TILE <= 65535 && (long)T * B * 4096 < (1L << 40),
+                 "st_mel_to_linear: bad batch %d / frames %d", B, T);
+    launch_mel_to_linear(mel, sb, st, sm, basis, lin, B, T, n_mels, F, normalized != 0, take_abs != 0, nullptr, 0, (hipStream_t)stream);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t st_gl_batch_workspace_floats(int B, int T, int n_fft, int hop, int win) {
+    if (B <= 0 || T <= 1 || hop <= 0 || win <= 0 || n_fft <= 0) return 0;
+    return WND_FLOATS + (size_t)B * round64((size_t)hop * (T - 1)) + round64((size_t)B * T * (n_fft / 2 + 1)) +
+           2 * round64((size_t)B * T * win);
+}
+
+extern "C" int st_griffin_lim_batch(const float* feat, long sb, long st, long sf, int n_in, const float* basis, int normalized, float power,
+                                    const float* phases, const int* frames, float* wav, int B, int T, int n_fft, int hop, int win,
+                                    int n_iter, int post, float* ws, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(feat && phases && wav && ws, "st_griffin_lim_batch: null pointer");
+    ST_CHECK_ARG(n_iter >= 0 && (post & ~3) == 0 && power > 0.0f, "st_griffin_lim_batch: bad n_iter %d / post %d / power", n_iter, post);
+    int rc = check_dims("st_griffin_lim_batch", B, n_fft, hop, win, T, (long)hop * (T - 1));
+    if (rc) return rc;
+    const int L = hop * (T - 1);
+    const int F = n_fft / 2 + 1;
+    if (basis) {
+        ST_CHECK_ARG(n_in >= 1 && n_in <= MEL_MAX, "st_griffin_lim_batch: %d mels outside [1, %d]", n_in, MEL_MAX);
+        ST_CHECK_ARG(power == 1.0f, "st_griffin_lim_batch: mel input is an amplitude (isAmp): power must be 1");
+        ST_CHECK_ARG((T + MEL_TILE - 1) / MEL_TILE <= 65535, "st_griffin_lim_batch: too many frames %d", T);
+    } else {
+        ST_CHECK_ARG(n_in == F, "st_griffin_lim_batch: %d bins, expected n_fft / 2 + 1 = %d", n_in, F);
+    }
+    if ((rc = ensure_twiddles(stream)) != 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int tmin = n_fft / 2 / hop + 2;                     // the fewest frames check_dims takes (T itself passed it)
+    const size_t env_stride = round64(L);
+    float* wnd = ws;
+    float* inv_env = wnd + WND_FLOATS;
+    float* amp = inv_env + (size_t)B * env_stride;
+    float* fr[2] = {amp + round64((size_t)B * T * F), nullptr};
+    fr[1] = fr[0] + round64((size_t)B * T * win);
+    if (frames)
+        hipLaunchKernelGGL(gl_setup_ragged_kernel, dim3((max(L, win) + 255) / 256, B), dim3(256), 0, s, wnd, inv_env, env_stride, n_fft, T,
+                           hop, win, frames, tmin);
+    else
+        hipLaunchKernelGGL(gl_setup_kernel, dim3((max(L, win) + 255) / 256), dim3(256), 0, s, wnd, inv_env, n_fft, T, hop, win, L);
+    if (basis) launch_mel_to_linear(feat, sb, st, sf, basis, amp, B, T, n_in, F, normalized != 0, 1, frames, tmin, s);
+    if (frames) {
+        ST_AUDIO_DISPATCH(n_fft, launch_first_ragged, basis != nullptr, basis ? amp : feat, basis ? (long)T * F : sb, basis ? (long)F : st,
+                          basis ? 1L : sf, normalized, power, phases, amp, wnd, fr[0], B, T, win, frames, tmin, s);
+        for (int it = 0; it < n_iter; ++it)
+            ST_AUDIO_DISPATCH(n_fft, launch_iter_ragged, fr[it & 1], fr[(it + 1) & 1], amp, wnd, inv_env, env_stride, B, T, hop, win, L,
+                              frames, tmin, s);
+        hipLaunchKernelGGL(gl_ola_post_kernel<true>, dim3(B), dim3(OLA_THREADS), 0, s, fr[n_iter & 1], inv_env, wav, n_fft, T, hop, win, L,
+                           post, frames, tmin, env_stride);
+    } else {
+        if (basis) {
+            ST_AUDIO_DISPATCH(n_fft, launch_first_amp, amp, phases, wnd, fr[0], B, T, win, s);
+        } else {
+            ST_AUDIO_DISPATCH(n_fft, launch_first, true, feat, sb, st, sf, normalized, power, phases, nullptr, amp, wnd, fr[0], B, T, win, s);
+        }
+        for (int it = 0; it < n_iter; ++it)
+            ST_AUDIO_DISPATCH(n_fft, launch_iter, fr[it & 1], fr[(it + 1) & 1], amp, wnd, inv_env, B, T, hop, win, L, s);
+        hipLaunchKernelGGL(gl_ola_post_kernel<false>, dim3(B), dim3(OLA_THREADS), 0, s, fr[n_iter & 1], inv_env, wav, n_fft, T, hop, win, L,
+                           post, (const int*)nullptr, 0, (size_t)0);
+    }
     ST_LAUNCH_CHECK();
     return 0;
 }

@@ -1828,6 +1828,45 @@ def griffin_lim(feat, phases, n_fft, hop, win, n_iter=30, normalized=False, powe
     return wav
 
 
+MEL_TO_LINEAR_TILE = 16          # frames per workgroup of st_mel_to_linear (MEL_TILE in audio.hip): the tests straddle it
+MEL_MAX = 256                    # most mel bins st_mel_to_linear takes (MEL_MAX in audio.hip)
+
+
+def mel_to_linear(mel, basis, normalized=True, take_abs=False):
+    """st_mel_to_linear: mel (B, T, n_mels) in any strides, basis (n_mels, F) contiguous (the transposed pseudo-inverse of the mel
+    filterbank) -> (B, T, F) = sum_m basis[m, k] a[b, t, m], a the denormalised amplitude of mel (normalized) or mel itself;
+    take_abs stores the magnitude Griffin-Lim takes."""
+    assert mel.dim() == 3 and basis.dim() == 2 and basis.is_contiguous() and basis.shape[0] == mel.shape[2]
+    B, T, n_mels = mel.shape
+    F = basis.shape[1]
+    lin = torch.empty(B, T, F, device=mel.device, dtype=torch.float32)
+    sb, st, sm = mel.stride()
+    check(_lib.load().st_mel_to_linear(_p(mel), sb, st, sm, _p(basis), _p(lin), B, T, n_mels, F, int(bool(normalized)),
+                                       int(bool(take_abs)), stream_handle()), 'st_mel_to_linear')
+    return lin
+
+
+def griffin_lim_batch(feat, phases, n_fft, hop, win, n_iter=30, normalized=False, power=1.0, post=0, basis=None, frames=None):
+    """st_griffin_lim_batch: griffin_lim() for utterances of their own lengths and for mel input.  feat (B, T, F) linear, or
+    (B, T, n_mels) with basis (n_mels, F) as mel_to_linear() takes it; frames: device int32 (B,) frame counts (None: T for all).
+    -> waveform (B, hop * (T - 1)), row b filled on [0, hop * (frames[b] - 1)) and zero after.  feat rows and phase columns
+    beyond an utterance's frames are never read."""
+    F = n_fft // 2 + 1
+    assert feat.dim() == 3 and feat.shape[2] == (F if basis is None else basis.shape[0])
+    B, T, n_in = feat.shape
+    assert phases.shape == (B, F, T) and phases.is_contiguous()
+    assert basis is None or (basis.shape == (n_in, F) and basis.is_contiguous())
+    assert frames is None or (frames.shape == (B,) and frames.dtype == torch.int32 and frames.is_contiguous() and frames.is_cuda)
+    lib = _lib.load()
+    ws = _audio_ws(lib.st_gl_batch_workspace_floats, B, T, n_fft, hop, win, feat.device)
+    wav = torch.empty(B, hop * (T - 1), device=feat.device, dtype=torch.float32)
+    sb, st, sf = feat.stride()
+    check(lib.st_griffin_lim_batch(_p(feat), sb, st, sf, n_in, _p(basis) if basis is not None else None, int(bool(normalized)),
+                                   float(power), _p(phases), _p(frames, torch.int32) if frames is not None else None, _p(wav), B, T,
+                                   n_fft, hop, win, int(n_iter), int(post), _p(ws), stream_handle()), 'st_griffin_lim_batch')
+    return wav
+
+
 # --------------------------------------------------------------------------------------------- feature extraction (src/audio.py)
 FEATURES_MAX_BATCH = 64          # utterances per st_audio_features call (its per-utterance metadata travels by value)
 

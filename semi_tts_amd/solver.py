@@ -140,7 +140,10 @@ class SpecgramGenerator(BaseSolver):
                 raise RuntimeError('gen_specgram: non-finite spectrogram for batch starting at %s -- nothing written' % names[0])
             wavs = None
             if gen_wav:                                 # gen_specgram.py:114-115: Griffin-Lim of this rank's lin, on the device
-                wavs = self.audio_converter.gen_wav_device(lin).cpu().numpy()
+                if getattr(self.paras, 'gen_wav_feat', 'linear') == 'mel':      # --gen-wav-feat mel: of its mel instead
+                    wavs = self.audio_converter.gen_wav_device(mel, mel=True).cpu().numpy()
+                else:
+                    wavs = self.audio_converter.gen_wav_device(lin).cpu().numpy()
             enc_step = (text != 0).sum(dim=-1).cpu().tolist()
             dec_step = [int(n * FRAME_PHN_RATIO) // r for n in enc_step]
             for i, (msp, sp, ali) in enumerate(zip(mel, lin, align)):
@@ -157,6 +160,71 @@ class SpecgramGenerator(BaseSolver):
             self.verbose('Save %d spectrograms%s (%d frames) in %s, %.2f s' %
                          (cnt, ' on rank 0 of %d' % world if world > 1 else '', frames_out, output_dir, dt))
         return cnt
+
+
+VOCODE_SUFFIX = {'spec': '-spec.npy', 'mel': '-mel.npy'}
+
+
+def list_vocode_files(feat_dir, kind, conv):
+    """the saved spectrograms of --vocode-dir: the files of `feat_dir` ending in -spec.npy (kind 'spec') or -mel.npy ('mel'), sorted
+    by name -> [(file name, stem)], the stem being the name without that ending (the .wav written is <stem>.wav, as the reference's
+    util/gen_wav_from_specgram.py names it).  Every file's header is read: one that is not (T, bins) with the converter's bin
+    count, or has fewer frames than Griffin-Lim takes, raises ValueError naming it."""
+    from .audio import min_frames
+    suffix = VOCODE_SUFFIX[kind]
+    names = sorted(f for f in os.listdir(feat_dir) if f.endswith(suffix))
+    if not names:
+        raise ValueError('--vocode-dir %s: no *%s files' % (feat_dir, suffix))
+    bins = conv.num_freq if kind == 'spec' else conv.n_mels
+    lo = min_frames(conv.n_fft, conv.hop_length)
+    for f in names:
+        shape = np.load(os.path.join(feat_dir, f), mmap_mode='r', allow_pickle=False).shape
+        if len(shape) != 2 or shape[1] != bins:
+            raise ValueError('--vocode-dir: %s has shape %s, expected (frames, %d) for --vocode-feat %s' % (f, tuple(shape), bins, kind))
+        if shape[0] < lo:
+            raise ValueError('--vocode-dir: %s has %d frames, too few: Griffin-Lim needs at least %d (hop %d, n_fft %d)'
+                             % (f, shape[0], lo, conv.hop_length, conv.n_fft))
+    return [(f, f[:-len(suffix)]) for f in names]
+
+
+class Vocoder:
+    """main.py --vocode-dir: the saved -spec.npy (or, with --vocode-feat mel, -mel.npy) files of a directory, sorted by name, in
+    batches of --batch-size -> AudioConverter.vocode_batch (one Griffin-Lim call per batch, each utterance at its own length) ->
+    <logdir>/<stem>.wav.  The counterpart of the reference's util/gen_wav_from_specgram.py; it reads no checkpoint and builds no
+    model.  Every file is checked in load_data: a bad one stops the run before anything is written."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.exp_name = getattr(paras, 'name', None) or 'synthetic'
+        self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
+        self.kind = getattr(paras, 'vocode_feat', 'spec')
+
+    def load_data(self):
+        from .audio import load_audio_transform
+        self.audio_converter = load_audio_transform(**self.config['data']['audio'])
+        self.feat_dir = self.paras.vocode_dir
+        self.files = list_vocode_files(self.feat_dir, self.kind, self.audio_converter)
+        if self.kind == 'mel':
+            self.audio_converter.mel_basis()             # (a rank-deficient filterbank stops the run here too)
+        return self
+
+    def set_model(self):
+        return self
+
+    def exec(self):
+        from .audio import write_wav
+        os.makedirs(self.logdir, exist_ok=True)
+        B = int(self.paras.batch_size)
+        t0, n = time.perf_counter(), 0
+        for i in range(0, len(self.files), B):
+            chunk = self.files[i:i + B]
+            wavs = self.audio_converter.vocode_batch([np.load(os.path.join(self.feat_dir, f), allow_pickle=False) for f, _ in chunk], self.kind)
+            for (_, stem), w in zip(chunk, wavs):
+                write_wav(os.path.join(self.logdir, stem + '.wav'), w, self.audio_converter.sr)
+                n += 1
+        if getattr(self.paras, 'verbose', True):
+            print('[INFO]', 'Vocoded %d %s files into %s, %.2f s' % (n, VOCODE_SUFFIX[self.kind], self.logdir, time.perf_counter() - t0))
+        return n
 
 
 SPECIAL_TOKENS = ('<pad>', '<space>', '<eos>')     # ids 0, 1, 2 of the phone vocabulary (src/text.py); phones start at id 3
