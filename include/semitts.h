@@ -1330,6 +1330,28 @@ int st_audio_features(const float* x, long n_samples, const float* noise, unsign
 /* out[i] = the built-in generator's standard normal for (seed, utterance utt, sample i), i < n (for tests) */
 int st_feature_noise(float* out, long n, int utt, unsigned long long seed, void* stream);
 
+/* ------------------------------------------------------------------ sample-rate conversion (waveforms -> waveforms)
+ * Not a step of the reference (its AudioProcessor.load refuses a foreign rate, src/audio.py:70-77, and leaves conversion to an
+ * offline tool).  Windowed-sinc interpolation with a Hann window (the default of torchaudio.functional.resample:
+ * lowpass_filter_width lpw = 6, rolloff 0.99) for the ratio o / n = orig_sr / new_sr in lowest terms.  With base = min(o, n) *
+ * rolloff, W = lpw * o / base and tau_m = m o / n:
+ *     y[m] = (base / o) sum_{i : |i - tau_m| < W} sinc(pi base (i - tau_m) / o) cos^2(pi base (i - tau_m) / (2 lpw o)) x[i],
+ * x[i] = 0 outside [0, L), m = 0 .. ceil(n L / o) - 1.  The weights depend on the phase p = m mod n only: the host tabulates
+ * them (semi_tts_amd.audio.resample_table: float64, rounded once) as table (n, taps), row p holding the weights (scale included)
+ * of x[floor(tau_m) + first[p] + k], k < taps, zero where |i - tau| >= W.  The kernel forms
+ *     y[m] = fma(table[p][taps-1], x[..], ... fma(table[p][0], x[floor(tau_m) + first[p]], 0))
+ * one chain in ascending tap order, so a sample's bits do not depend on the tile, the batch or the position in it.
+ * x: the packed input, float32 or (pcm16 != 0) int16 PCM scaled by 1 / 32768 in the kernel (exact); utterance b is
+ * x[off[b] .. off[b] + len[b]) and is written to y[out_off[b] .. out_off[b] + ceil(n len[b] / o)); nothing else of y is written.
+ * Host arrays: off, len, out_off (B entries, read before the call returns); first (n ints) and table are on the device.
+ * first_min / first_max: bounds of first[] (the kernel clamps its reads into the staged span, so an inconsistent `first` cannot
+ * index outside it).  Limits (anything else returns -22): B <= 64, len[b] >= 1, o n < 2^31, min(n, 1024) * ((taps | 1) + 1) <=
+ * 9216 floats of staged table and ceil(1023 o / n) + first_max - first_min + taps <= 6912 staged input samples: one workgroup
+ * (1024 outputs of one utterance) holds both in LDS, at most 63 KB.  One launch, no atomics, no workspace. */
+int st_resample_batch(const void* x, int pcm16, long n_samples, const long* off, const int* len, int B, int o, int n, int taps,
+                      int first_min, int first_max, const int* first, const float* table, float* y, long n_out, const long* out_off,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/semi-single-spkr-paired-data.yaml --build-lm-phn-dir DIR --lm-order 2 --lm FILE [--lm-smooth 1 --vocab F]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --lm FILE [--lm-weight 0.5 --ins-bonus 0]
     python main.py --config config/supervised.yaml --vocode-dir DIR [--vocode-feat spec|mel --batch-size 32]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --resample      (files of any sample rate)
+    python main.py --resample-wav-dir DIR --resample-out DIR2 --resample-rate 16000 [--batch-size 32]
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
 `--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
 (semi_tts_amd/ngram.py: a plain .npy of shape (V^(order-1), V) in the layout of the reference's NgramPrior, src/lm.py:233-290) on the host.
@@ -27,8 +29,12 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
 `--vocode-dir` (the reference's util/gen_wav_from_specgram.py) vocodes the -spec.npy or -mel.npy files `--gen-specgram` writes into
 <stem>.wav by Griffin-Lim, a batch of differing lengths per call (solver.Vocoder); `--gen-wav-feat mel` makes `--gen-specgram --gen-wav`
 vocode the predicted mel instead of the predicted linear spectrogram.
+`--resample` (with --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir) converts files whose rate is not data.audio.sample_rate on
+the GPU (semi_tts_amd.audio.resample: Hann-windowed sinc, st_resample_batch) where the reference, and this path without the flag, refuse
+them; `--resample-wav-dir` converts a directory of .wav files to another rate and writes them as 16-bit mono (solver.Resampler).
 """
 import argparse
+import os
 import random
 
 import numpy as np
@@ -97,6 +103,14 @@ parser.add_argument('--vocode-dir', default=None, type=str, help='vocode the sav
                     '*-mel.npy files --gen-specgram writes; sorted by name, batched by --batch-size, each at its own length) by '
                     'Griffin-Lim into <logdir>/<name>/<stem>.wav; no checkpoint, no model')
 parser.add_argument('--vocode-feat', default=None, choices=('spec', 'mel'), help='--vocode-dir: read *-spec.npy (default) or *-mel.npy')
+parser.add_argument('--resample', action='store_true', help='--unpair-wav-dir / --transcribe-wav-dir / --align-wav-dir: convert files whose '
+                    'sample rate is not data.audio.sample_rate on the GPU (windowed sinc) instead of refusing them')
+parser.add_argument('--resample-wav-dir', default=None, type=str, help='convert channel 0 of the .wav files of this directory (sorted by name, '
+                    'batched by --batch-size) to --resample-rate on the GPU and write them as 16-bit mono into --resample-out/<same name>; '
+                    'no checkpoint, no model')
+parser.add_argument('--resample-out', default=None, type=str, help='--resample-wav-dir: the directory to write (not the one read)')
+parser.add_argument('--resample-rate', default=None, type=int, help='--resample-wav-dir: the output rate in Hz (default: data.audio.sample_rate '
+                    'of --config)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -154,6 +168,24 @@ def parse_args(argv=None):
         parser.error('--vocode-feat names the files --vocode-dir reads; it needs that flag')
     if paras.vocode_feat is None:
         paras.vocode_feat = 'spec'
+    if paras.resample and paras.unpair_wav_dir is None and paras.transcribe_wav_dir is None and paras.align_wav_dir is None:
+        parser.error('--resample converts the files of --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir; it needs one of them')
+    if paras.resample_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir'):
+            if getattr(paras, flag):
+                parser.error('--resample-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--resample-wav-dir does not combine with --dev-batches')
+        if paras.resample_out is None:
+            parser.error('--resample-wav-dir needs --resample-out DIR (the directory to write)')
+        if os.path.realpath(paras.resample_out) == os.path.realpath(paras.resample_wav_dir):
+            parser.error('--resample-out must not be the directory --resample-wav-dir reads')
+        if paras.resample_rate is not None and paras.resample_rate < 1:
+            parser.error('--resample-rate must be a positive number of Hz')
+        if paras.resample_rate is None and paras.config is None:
+            parser.error('--resample-wav-dir needs --resample-rate N or --config (its data.audio.sample_rate)')
+    elif paras.resample_out is not None or paras.resample_rate is not None:
+        parser.error('--resample-out and --resample-rate belong to --resample-wav-dir; they need that flag')
     if paras.gen_wav_feat != 'linear' and not (paras.gen_specgram and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
@@ -206,7 +238,11 @@ def main(argv=None):
         print(build_lm_from_phn_dir(paras.build_lm_phn_dir, paras.lm, paras.lm_order, smooth=paras.lm_smooth,
                                     vocab=read_vocab(paras.vocab) if paras.vocab else None)['summary'])
         return
-    config = yaml.load(open(paras.config, 'r'), Loader=yaml.FullLoader)
+    if paras.resample_wav_dir is not None and paras.config is None:      # (the rate was given: this mode reads nothing else of a config)
+        config = None
+        paras.batch_size = paras.batch_size or 8
+    else:
+        config = yaml.load(open(paras.config, 'r'), Loader=yaml.FullLoader)
     if paras.batch_size is None:
         paras.batch_size = config['data']['corpus'].get('batch_size', 8)
     random.seed(paras.seed)
@@ -214,13 +250,15 @@ def main(argv=None):
     torch.manual_seed(paras.seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(paras.seed)
-    import os
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:      # one process per GPU (torch.distributed.run), RCCL over xGMI
         import torch.distributed as dist
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('nccl')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    if paras.vocode_dir is not None:
+    if paras.resample_wav_dir is not None:
+        from semi_tts_amd.solver import Resampler as Solver
+        mode = 'test'
+    elif paras.vocode_dir is not None:
         from semi_tts_amd.solver import Vocoder as Solver
         mode = 'test'
     elif paras.transcribe_wav_dir is not None:

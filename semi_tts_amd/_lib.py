@@ -361,6 +361,7 @@ SIGNATURES = {
     'st_features_workspace_floats': [I],
     'st_audio_features': [P, C.c_long, P, C.c_ulonglong, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, I, P, P, I, P, I, P, P],
     'st_feature_noise': [P, C.c_long, I, C.c_ulonglong, P],
+    'st_resample_batch': [P, I, C.c_long, P, P, I, I, I, I, I, I, P, P, P, C.c_long, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,

@@ -16,6 +16,12 @@ Analysis side (st_audio_features): waveform -> normalised mel / linear spectrogr
     conv = load_audio_transform(**config['data']['audio'])
     msp, msp_aug, sp = conv.wave_to_feat('utt.wav')              # (T, n_mels), (T', n_mels), (T, F): src/audio.py:329-395
     mel, aug_mel, linear = conv.extract_batch(wavs, r=5)       # a ragged batch on the device, longest first (src/data.py:130)
+
+Sample-rate conversion (st_resample_batch; not a step of the reference, whose load refuses a foreign rate): Hann-windowed sinc.
+
+    wb = resample(wavs48k, 48000, 22050)                         # list of 1-D float / int16 waveforms -> WaveBatch on the device
+    wb = conv.load_batch(paths, resample=True)                   # .wav files of any rate -> one WaveBatch at conv.sr
+    mel, aug_mel, linear = conv.extract_batch(wb, r=5)
 """
 import random
 import wave
@@ -243,6 +249,34 @@ class AudioConverter:
         """src/audio.py:68-77: (channels, samples) float32; a different sample rate raises"""
         return load_wav(wav_path, self.sr)
 
+    def load_batch(self, paths, resample=False):
+        """Channel 0 of the .wav files `paths` as one WaveBatch at self.sr on the device (`.order`: the position in `paths` of each
+        utterance).  A file at another rate raises load()'s error -- or, with resample=True, is converted on the GPU: the files are
+        grouped by source rate and each foreign group is uploaded as int16 PCM and resampled in one resample() call.  Every file
+        is read and every rate checked before a device is touched."""
+        paths = [str(p) for p in paths]
+        if not paths:
+            raise ValueError('load_batch: no files')
+        read = [_read_pcm(p) for p in paths]
+        groups = {}
+        for i, ((_, sr), p) in enumerate(zip(read, paths)):
+            if sr != self.sr:
+                if not resample:
+                    raise ValueError('Sample rate mismatch. Expected %d but get %d (%s)' % (self.sr, sr, p))
+                resample_table(sr, self.sr)                       # (a ratio the kernel does not take raises here)
+                groups.setdefault(sr, []).append(i)
+        dev = _device()
+        waves = [None] * len(paths)
+        for i, (pcm, sr) in enumerate(read):
+            if sr == self.sr:
+                waves[i] = torch.from_numpy(pcm[:, 0].astype(np.float32) / 32768.0).to(dev)
+        for sr, idx in sorted(groups.items()):
+            wb = _resample([torch.from_numpy(read[i][0][:, 0].copy()) for i in idx], sr, self.sr)
+            y = wb.packed(dev)
+            for row, k in enumerate(wb.order):
+                waves[idx[k]] = y[int(wb.offsets[row]):int(wb.offsets[row] + wb.lens[row])]
+        return WaveBatch(waves)
+
     def stretch_dims(self, rate):
         """(win, hop) of the augmented framing at stretch `rate`, exactly as src/audio.py:366-373"""
         stretch_sr = int(self.sr * rate)
@@ -443,6 +477,22 @@ def load_wav(path, sample_rate=None):
     return torch.from_numpy(np.ascontiguousarray(pcm.reshape(-1, ch).T, dtype=np.float32) / 32768.0)
 
 
+def _read_pcm(path):
+    """16-bit PCM .wav through the standard library: -> ((samples, channels) int16 array, sample rate)"""
+    with wave.open(str(path), 'rb') as w:
+        sr, ch, width = w.getframerate(), w.getnchannels(), w.getsampwidth()
+        if width != 2:
+            raise ValueError('read_wav: %s is %d-bit; only 16-bit PCM is read' % (path, 8 * width))
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2')
+    return pcm.reshape(-1, ch), sr
+
+
+def read_wav(path):
+    """load_wav at the file's own rate: -> ((channels, samples) float32 scaled by 1 / 32768, sample rate)"""
+    pcm, sr = _read_pcm(path)
+    return torch.from_numpy(np.ascontiguousarray(pcm.T, dtype=np.float32) / 32768.0), sr
+
+
 def write_wav(path, wav, sr):
     """16-bit PCM mono .wav through the standard library (soundfile's default subtype for .wav): round(clip(x, -1, 1) * 32767)"""
     wav = np.asarray(wav, dtype=np.float64).reshape(-1)
@@ -452,3 +502,102 @@ def write_wav(path, wav, sr):
         w.setsampwidth(2)
         w.setframerate(int(sr))
         w.writeframes(pcm.tobytes())
+
+
+# -- sample-rate conversion (st_resample_batch; the definition is in include/semitts.h and DESIGN.md 3.14)
+RESAMPLE_LPW, RESAMPLE_ROLLOFF = 6, 0.99      # torchaudio.functional.resample's defaults
+_RESAMPLE = {}                                # (o, n, lpw, rolloff) -> host table; (.., device) -> its copy on that device
+
+
+def _ratio(orig_sr, new_sr):
+    """(o, n) = the two rates in lowest terms; anything but positive integers raises ValueError"""
+    for v, what in ((orig_sr, 'orig_sr'), (new_sr, 'new_sr')):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+            raise ValueError('resample: %s must be a positive integer, got %r' % (what, v))
+    g = np.gcd(int(orig_sr), int(new_sr))
+    return int(orig_sr) // int(g), int(new_sr) // int(g)
+
+
+def resampled_len(L, orig_sr, new_sr):
+    """samples of an L-sample waveform after conversion: ceil(L new_sr / orig_sr), in integers"""
+    o, n = _ratio(orig_sr, new_sr)
+    return (n * int(L) + o - 1) // o
+
+
+def resample_table(orig_sr, new_sr, lowpass_filter_width=RESAMPLE_LPW, rolloff=RESAMPLE_ROLLOFF, device=None):
+    """The polyphase filter of orig_sr -> new_sr: (o, n, taps, first, table), o / n the ratio in lowest terms.  Output m (phase
+    p = m mod n) is sum_k table[p, k] * x[floor(m o / n) + first[p] + k]: table (n, taps) float32 holds the Hann-windowed sinc of
+    the header's definition, scale base / o included, computed in float64 and rounded once, exactly 0 where |i - tau| >= W (rows
+    with fewer taps than the widest are padded with such zeros).  first (n,) int32.  device None: numpy arrays; else the copies on
+    that device.  Cached per ratio and per device.  Raises ValueError, before any device is touched, for rates that are not
+    positive integers and for a ratio the kernel does not take (ops.RESAMPLE_MAX_TABLE_FLOATS / RESAMPLE_MAX_STAGE_FLOATS)."""
+    o, n = _ratio(orig_sr, new_sr)
+    lpw, rolloff = int(lowpass_filter_width), float(rolloff)
+    if lpw != lowpass_filter_width or lpw < 1 or not 0.0 < rolloff <= 1.0:
+        raise ValueError('resample: need an integer lowpass_filter_width >= 1 and 0 < rolloff <= 1, got %r and %r'
+                         % (lowpass_filter_width, rolloff))
+    key = (o, n, lpw, rolloff)
+    if key not in _RESAMPLE:
+        if o * n >= 2 ** 31:
+            raise ValueError('resample: %d -> %d Hz is the ratio %d / %d; the kernel needs o * n < 2^31' % (orig_sr, new_sr, o, n))
+        base = min(o, n) * rolloff
+        W = lpw * o / base
+        frac = ((np.arange(n, dtype=np.int64) * o) % n) / float(n)       # tau - floor(tau) of each phase
+        first = np.floor(frac - W).astype(np.int64) + 1
+        last = np.ceil(frac + W).astype(np.int64) - 1
+        taps = int((last - first + 1).max())
+        tab_f, stage_f = ops.resample_lds_floats(o, n, taps, int(first.min()), int(first.max()))
+        if tab_f > ops.RESAMPLE_MAX_TABLE_FLOATS or stage_f > ops.RESAMPLE_MAX_STAGE_FLOATS:
+            raise ValueError('resample: %d -> %d Hz (ratio %d / %d, %d taps) needs %d floats of staged table (limit %d) and %d of staged '
+                             'input (limit %d)' % (orig_sr, new_sr, o, n, taps, tab_f, ops.RESAMPLE_MAX_TABLE_FLOATS, stage_f,
+                                                   ops.RESAMPLE_MAX_STAGE_FLOATS))
+        t = (first[:, None] + np.arange(taps)[None, :]) - frac[:, None]  # i - tau
+        a = np.pi * base * t / o
+        h = (base / o) * np.where(a == 0.0, 1.0, np.sin(a) / np.where(a == 0.0, 1.0, a)) * np.cos(a / (2.0 * lpw)) ** 2
+        table = np.ascontiguousarray(np.where(np.abs(t) < W, h, 0.0).astype(np.float32))
+        _RESAMPLE[key] = (o, n, taps, first.astype(np.int32), table)
+    if device is None:
+        return _RESAMPLE[key]
+    dkey = key + (str(device),)
+    if dkey not in _RESAMPLE:
+        _, _, taps, first, table = _RESAMPLE[key]
+        _RESAMPLE[dkey] = (o, n, taps, torch.from_numpy(first).to(device), torch.from_numpy(table).to(device))
+    return _RESAMPLE[dkey]
+
+
+def resample(wavs, orig_sr, new_sr):
+    """Sample-rate conversion of a ragged batch on the GPU (st_resample_batch, one launch per 64 utterances): wavs, a list of 1-D
+    waveforms (tensors or arrays, floating point or int16 PCM -- int16 counts as x / 32768 and is uploaded as PCM) or a WaveBatch
+    -> a WaveBatch at new_sr on the device, ready for extract_batch: sorted longest first again, `.order[i]` the index in the
+    caller's list of the i-th utterance.  orig_sr == new_sr launches nothing and returns the input's values as they are (a
+    WaveBatch itself).  Every refusal (resample_table's, an empty batch or utterance, a dtype that is neither) raises ValueError
+    before a device is touched."""
+    o, n, _, first, _ = resample_table(orig_sr, new_sr)
+    given = wavs if isinstance(wavs, WaveBatch) else None
+    src = given._wavs if given is not None else [torch.as_tensor(w).reshape(-1) for w in wavs]
+    if not src:
+        raise ValueError('resample: an empty batch')
+    for i, w in enumerate(src):
+        if not (w.dtype == torch.int16 or w.dtype.is_floating_point):
+            raise ValueError('resample: utterance %d is %s; waveforms are floating point or int16 PCM' % (i, w.dtype))
+        if w.numel() < 1 or resampled_len(w.numel(), o, n) >= 2 ** 31:
+            raise ValueError('resample: utterance %d has %d samples' % (i, w.numel()))
+    pcm = all(w.dtype == torch.int16 for w in src)
+    as_float = lambda w: w.to(torch.float32) / 32768.0 if w.dtype == torch.int16 else w.to(torch.float32)      # noqa: E731
+    if o == n:
+        return given if given is not None else WaveBatch([as_float(w) if w.dtype == torch.int16 else w for w in src])
+    dev = next((w.device for w in src if w.is_cuda), None) or _device()
+    x = torch.cat([w.to(dev) if pcm else as_float(w).to(dev) for w in src]).contiguous()
+    lens = np.array([w.numel() for w in src], np.int64)
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    _, _, _, first_d, table_d = resample_table(orig_sr, new_sr, device=dev)
+    y, out_off, out_lens = ops.resample_batch(x, off, lens, o, n, first_d, table_d, int(first.min()), int(first.max()))
+    out = WaveBatch([y[int(a):int(a + b)] for a, b in zip(out_off, out_lens)])
+    if np.array_equal(out.order, np.arange(len(src))):
+        out._packed[str(dev)] = y                       # already packed in the sorted order: no second copy
+    if given is not None:
+        out.order = np.asarray(given.order)[out.order]
+    return out
+
+
+_resample = resample      # (AudioConverter.load_batch has an argument of that name)

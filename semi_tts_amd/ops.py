@@ -1913,3 +1913,43 @@ def feature_noise(n, utt, seed, device):
     out = torch.empty(n, device=device, dtype=torch.float32)
     check(_lib.load().st_feature_noise(_p(out), n, utt, int(seed) & (2 ** 64 - 1), stream_handle()), 'st_feature_noise')
     return out
+
+
+# --------------------------------------------------------------------------------------------- sample-rate conversion
+RESAMPLE_TILE = 1024                 # outputs per workgroup of st_resample_batch (RS_TILE in resample.hip): the tests straddle it
+RESAMPLE_MAX_TABLE_FLOATS = 9216     # LDS floats of the staged table: min(n, RESAMPLE_TILE) rows of (taps | 1) + 1 (RS_MAX_TABLE)
+RESAMPLE_MAX_STAGE_FLOATS = 6912     # LDS floats of a tile's input span (RS_MAX_STAGE)
+
+
+def resample_lds_floats(o, n, taps, first_min, first_max):
+    """(staged table floats, staged input floats) of one st_resample_batch workgroup at the ratio o / n: what the two limits bound"""
+    return min(n, RESAMPLE_TILE) * ((taps | 1) + 1), ((RESAMPLE_TILE - 1) * o + n - 1) // n + first_max - first_min + taps
+
+
+def resample_batch(x, off, lens, o, n, first, table, first_min, first_max, out=None):
+    """st_resample_batch on a ragged batch: x the packed waveforms on the device, float32 or int16 PCM (scaled by 1 / 32768 in the
+    kernel); utterance b = x[off[b]:off[b] + lens[b]].  first (n,) int32 and table (n, taps) float32: the device copies of
+    audio.resample_table(); first_min / first_max the bounds of first.  -> (y, out_off, out_lens): the packed float32 output
+    (`out`, a contiguous 1-D float32 device tensor of exactly the summed output lengths, or a new one), utterance b =
+    y[out_off[b]:out_off[b] + out_lens[b]], out_lens[b] = ceil(n lens[b] / o).  Batches above FEATURES_MAX_BATCH are issued in
+    chunks of it."""
+    assert x.dim() == 1 and x.is_contiguous() and x.dtype in (torch.float32, torch.int16)
+    assert table.dim() == 2 and table.shape[0] == n and table.is_contiguous() and table.dtype == torch.float32
+    assert first.shape == (n,) and first.dtype == torch.int32 and first.is_contiguous()
+    B = len(lens)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    out_lens = (lens.astype(np.int64) * n + o - 1) // o
+    out_off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(out_lens)[:-1]]), dtype=np.int64)
+    total = int(out_lens.sum())
+    if out is None:
+        out = torch.empty(total, device=x.device, dtype=torch.float32)
+    assert out.dim() == 1 and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == total and out.device == x.device
+    lib = _lib.load()
+    hp = lambda a, b0: a.ctypes.data + b0 * a.itemsize     # noqa: E731  (host array from row b0)
+    for b0 in range(0, B, FEATURES_MAX_BATCH):
+        nb = min(FEATURES_MAX_BATCH, B - b0)
+        check(lib.st_resample_batch(_p(x, x.dtype), int(x.dtype == torch.int16), x.numel(), hp(off, b0), hp(lens, b0), nb, int(o), int(n),
+                                    table.shape[1], int(first_min), int(first_max), _p(first, torch.int32), _p(table), _p(out), total,
+                                    hp(out_off, b0), stream_handle()), 'st_resample_batch')
+    return out, out_off, out_lens

@@ -227,6 +227,66 @@ class Vocoder:
         return n
 
 
+class Resampler:
+    """main.py --resample-wav-dir DIR --resample-out DIR2 [--resample-rate N]: channel 0 of every .wav of DIR (sorted by name, batches of
+    --batch-size) converted to N Hz (default: data.audio.sample_rate of --config) on the GPU (audio.resample, the files of a batch
+    grouped by their rate, uploaded as int16 PCM) and written as 16-bit mono to DIR2/<same name> through write_wav.  No checkpoint,
+    no model.  Every header is read in load_data: an unreadable file or a ratio the kernel refuses stops the run before anything
+    is written."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        rate = getattr(paras, 'resample_rate', None)
+        self.rate = int(rate if rate is not None else config['data']['audio']['sample_rate'])
+
+    def load_data(self):
+        import wave
+        from .audio import resample_table
+        self.wav_dir, self.out_dir = self.paras.resample_wav_dir, self.paras.resample_out
+        if os.path.realpath(self.wav_dir) == os.path.realpath(self.out_dir):
+            raise ValueError('--resample-out %s is the directory --resample-wav-dir reads' % self.out_dir)
+        self.files = sorted(f for f in os.listdir(self.wav_dir) if f.lower().endswith('.wav'))
+        if not self.files:
+            raise ValueError('--resample-wav-dir %s: no .wav files' % self.wav_dir)
+        for f in self.files:
+            with wave.open(os.path.join(self.wav_dir, f), 'rb') as w:
+                if w.getsampwidth() != 2:
+                    raise ValueError('--resample-wav-dir: %s is %d-bit; only 16-bit PCM is read' % (f, 8 * w.getsampwidth()))
+                if w.getnframes() < 1:
+                    raise ValueError('--resample-wav-dir: %s holds no samples' % f)
+                resample_table(w.getframerate(), self.rate)
+        return self
+
+    def set_model(self):
+        return self
+
+    def exec(self):
+        from .audio import _read_pcm, resample, write_wav
+        os.makedirs(self.out_dir, exist_ok=True)
+        B = int(self.paras.batch_size)
+        t0, n = time.perf_counter(), 0
+        for i in range(0, len(self.files), B):
+            names = self.files[i:i + B]
+            read = [_read_pcm(os.path.join(self.wav_dir, f)) for f in names]
+            groups = {}
+            for k, (_, sr) in enumerate(read):
+                groups.setdefault(sr, []).append(k)
+            for sr, idx in sorted(groups.items()):
+                if sr == self.rate:                                 # nothing to convert: channel 0 as it is
+                    for k in idx:
+                        write_wav(os.path.join(self.out_dir, names[k]), read[k][0][:, 0] / 32768.0, self.rate)
+                        n += 1
+                    continue
+                wb = resample([torch.from_numpy(read[k][0][:, 0].copy()) for k in idx], sr, self.rate)
+                y = wb.packed(wb.device).cpu().numpy()
+                for row, k in enumerate(wb.order):
+                    write_wav(os.path.join(self.out_dir, names[idx[k]]), y[wb.offsets[row]:wb.offsets[row] + wb.lens[row]], self.rate)
+                    n += 1
+        if getattr(self.paras, 'verbose', True):
+            print('[INFO]', 'Resampled %d files to %d Hz into %s, %.2f s' % (n, self.rate, self.out_dir, time.perf_counter() - t0))
+        return n
+
+
 SPECIAL_TOKENS = ('<pad>', '<space>', '<eos>')     # ids 0, 1, 2 of the phone vocabulary (src/text.py); phones start at id 3
 
 
@@ -293,10 +353,16 @@ class Transcriber(BaseSolver):
             self.bonus = torch.from_numpy(host).to(self.device)
         return self
 
+    def load_waves(self, names):
+        """channel 0 of the files `names` of the .wav directory as one WaveBatch on the device (AudioConverter.load_batch); with
+        --resample a file at another rate is converted on the GPU, without it it raises"""
+        return self.audio_converter.load_batch([os.path.join(self.wav_dir, f) for f in names],
+                                               resample=bool(getattr(self.paras, 'resample', False)))
+
     def transcribe_batch(self, waves):
-        """waves: 1-D waveforms on the device -> (hyp, hyp_len, score) as numpy arrays in the order of `waves`"""
+        """waves: 1-D waveforms on the device (or a WaveBatch) -> (hyp, hyp_len, score) as numpy arrays in the order of `waves`"""
         from .audio import WaveBatch, SNR_OFF
-        wb = WaveBatch(waves)
+        wb = waves if isinstance(waves, WaveBatch) else WaveBatch(waves)
         mel, _, _ = self.audio_converter.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
         frames = 1 + wb.lens // self.audio_converter.hop_length
         hyp, hyp_len, score = self.model.transcribe(mel, frames, int(self.paras.beam_width), int(self.paras.top_paths),
@@ -309,11 +375,9 @@ class Transcriber(BaseSolver):
         os.makedirs(self.logdir, exist_ok=True)
         B = int(self.paras.batch_size)
         t0, n = time.perf_counter(), 0
-        wav_dir = self.paras.transcribe_wav_dir
         for i in range(0, len(self.files), B):
             names = self.files[i:i + B]
-            waves = [self.audio_converter.load(os.path.join(wav_dir, f))[0].to(self.device) for f in names]
-            hyp, hyp_len, score = self.transcribe_batch(waves)
+            hyp, hyp_len, score = self.transcribe_batch(self.load_waves(names))
             for f, h, hl, sc in zip(names, hyp, hyp_len, score):
                 with open(os.path.join(self.logdir, os.path.splitext(f)[0] + '.phn'), 'w') as out:
                     out.write(format_phn(sc.tolist(), [h[k, :hl[k]].tolist() for k in range(len(hl))], self.vocab))
@@ -343,15 +407,15 @@ class Aligner(Transcriber):
         return self
 
     def align_batch(self, waves, transcripts):
-        """waves: 1-D waveforms on the device, transcripts: their id lists -> (score, tok_start, tok_end, encoder frames) as numpy
-        arrays in the order of `waves`"""
+        """waves: 1-D waveforms on the device (or a WaveBatch), transcripts: their id lists -> (score, tok_start, tok_end, encoder
+        frames) as numpy arrays in the order of `waves`"""
         from .audio import WaveBatch, SNR_OFF
-        wb = WaveBatch(waves)
+        wb = waves if isinstance(waves, WaveBatch) else WaveBatch(waves)
         mel, _, _ = self.audio_converter.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
         frames = 1 + wb.lens // self.audio_converter.hop_length
         L = max(1, max(len(t) for t in transcripts))
-        text = np.zeros((len(waves), L), np.int64)
-        tl = np.zeros(len(waves), np.int32)
+        text = np.zeros((len(wb.lens), L), np.int64)
+        tl = np.zeros(len(wb.lens), np.int32)
         for row, k in enumerate(wb.order):                          # the batch is sorted by length: row `row` is waves[k]
             text[row, :len(transcripts[k])], tl[row] = transcripts[k], len(transcripts[k])
         score, path, ts, te = self.model.align(mel, frames, torch.from_numpy(text).to(self.device), tl.tolist(), source=self.paras.asr_output)
@@ -369,8 +433,7 @@ class Aligner(Transcriber):
         rows = [SEGMENTS_HEADER]
         for i in range(0, len(self.files), B):
             names, trs = self.files[i:i + B], self.transcripts[i:i + B]
-            waves = [self.audio_converter.load(os.path.join(self.wav_dir, f))[0].to(self.device) for f in names]
-            score, ts, te, t_enc = self.align_batch(waves, trs)
+            score, ts, te, t_enc = self.align_batch(self.load_waves(names), trs)
             for f, tr, sc, a, b, T in zip(names, trs, score.tolist(), ts, te, t_enc.tolist()):
                 targets = [x for x in tr if x != 0]                 # id 0 is the blank: not a target
                 S = len(targets)
@@ -1015,7 +1078,7 @@ class VqvaeTrainer(TtsTrainer):
         a world of w taking files k::w, in batches of Bu.  The waveforms are read once and stay on the device; fetch_data extracts
         the features again on every fetch (fresh SNR / stretch draws, as the reference's loader does every epoch).  text / sid stay
         synthetic: the speech-first cycle does not read the unpaired text."""
-        from .audio import WaveBatch, load_audio_transform
+        from .audio import load_audio_transform
         world = int(os.environ.get('WORLD_SIZE', 1))
         files = sorted(f for f in os.listdir(wav_dir) if f.lower().endswith('.wav'))[rank::world]
         if not files:
@@ -1023,8 +1086,9 @@ class VqvaeTrainer(TtsTrainer):
         self.audio_converter = load_audio_transform(**self.config['data']['audio'])
         if self.audio_converter.n_mels != self.n_mels:
             raise ValueError('--unpair-wav-dir: data.audio has %d mels, the model %d' % (self.audio_converter.n_mels, self.n_mels))
-        waves = [self.audio_converter.load(os.path.join(wav_dir, f))[0].to(self.device) for f in files]
-        self.unpair_waves = [WaveBatch(waves[i:i + Bu]) for i in range(0, len(waves), Bu)]
+        paths = [os.path.join(wav_dir, f) for f in files]
+        self.unpair_waves = [self.audio_converter.load_batch(paths[i:i + Bu], resample=bool(getattr(self.paras, 'resample', False)))
+                             for i in range(0, len(paths), Bu)]
         self.unpair_set = [mk(len(wb.lens), uframes, 500000 + 1000 * rank + i + seed) for i, wb in enumerate(self.unpair_waves)]
 
     def fetch_data(self, iter_name):
