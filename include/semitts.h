@@ -818,22 +818,38 @@ int st_decoder_fwd_forms(const st_decoder_dims* d, const st_decoder_io* io, int 
 
 /* ------------------------------------------------------------------ decoder backward (training, teacher forcing)
  * ref: what torch autograd derives for Decoder.forward / decode_one_step, src/module.py:184-288 */
-/* Backward of one attention step (recomputes the location features and tanh from the saved weights).
- * dctx / dw_direct: up to three addends each (row strides ld_*); dcum (B,L) carries dL/dcum_t across steps
- * (+ dcum_add).  Outputs needed by the recurrence: dpq (B,A) and dhist (B,2,L) = gradient w.r.t.
- * [w_{t-1}; cum_{t-1}] through the location conv.  Everything that is a sum over steps is left to the caller:
- * the kernel writes this step's slices ds_t (B,L,A), loc_t / dloc_t (B,L,F), hist_t (B,L,2) channels-last,
- * dctx_t (B,E), dv_t (B,A), from which dpm = sum_t ds, dW_l = ds^T loc, dW_c = conv weight gradient of
- * (dloc, hist), dmem[b] = w^T dctx, dv = sum dv_t. */
-int st_attn_step_bwd(const float* pq, const float* pm, const float* memory,
-                     const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                     const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                     const float* const* dctx, const int* ld_dctx, int n_dctx,
-                     const float* const* dw_direct, const int* ld_dw, int n_dw,
-                     float* dcum, const float* dcum_add, int ld_dcum_add,
-                     float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                     float* dctx_t, float* dv_t,
-                     int B, int L, int A, int E, int F, int K, void* stream);
+/* Backward of one attention step: the one description of it, taken by the stand-alone launch below and by the launches that host the step
+ * beside a product of the BPTT loop (st_skinny_linear_packed_lstm_bwd_attn_bwd, st_skinny_partial_attn_bwd; backward of
+ * src/module.py:247-283).  The location features and tanh are recomputed from the saved weights, or S = pm + W_l loc of the step is given
+ * (s_in, (B,L,A), e.g. kept by the forward): then loc_t is not written and may be NULL.
+ * dctx / dw_direct: up to three addends each (row strides ld_*; a NULL addend is absent); dcum (B,L) carries dL/dcum_t across steps
+ * (+ dcum_add).  Outputs needed by the recurrence: dpq (B,A) -- with dpq_t16.base also as a second copy in the T16 tile layout (K = A),
+ * the operand of the packed W_q^T product that follows -- and dhist (B,2,L) = gradient w.r.t. [w_{t-1}; cum_{t-1}] through the location
+ * conv.  Everything that is a sum over steps is left to the caller: the kernel writes this step's slices ds_t (B,L,A), loc_t / dloc_t
+ * (B,L,F), hist_t (B,L,2) channels-last, dctx_t (B,E), dv_t (B,A), from which dpm = sum_t ds, dW_l = ds^T loc, dW_c = conv weight
+ * gradient of (dloc, hist), dmem[b] = w^T dctx, dv = sum dv_t. */
+typedef struct st_attn_bwd_job {
+    const float* pq; const float* pm; const float* memory;
+    const float* w_prev; int ld_wprev; const float* w_cum_prev; const float* w; int ld_w;
+    const float* loc_conv_w; const float* loc_lin_w; const float* v;
+    const float* dctx[3]; int ld_dctx[3]; int n_dctx;
+    const float* dw_direct[3]; int ld_dw[3]; int n_dw;
+    float* dcum; const float* dcum_add; int ld_dcum_add;
+    float* dpq; st_t16_view dpq_t16; float* dhist; float* ds_t; float* loc_t; float* dloc_t; float* hist_t;
+    float* dctx_t; float* dv_t; const float* s_in;
+    int B, L, A, E, F, K;
+    /* parts > 1 (2 or 4; 0 / 1 = the whole step in one workgroup per utterance): `parts` workgroups per utterance, each taking A / parts
+     * attention dims of the energy gradient; ds_t / dpq / dv_t / dctx_t are complete afterwards, the location-feature gradient only as
+     * `parts` partial sums in dloc_part (parts, B, L, F).  dhist / dloc_t / hist_t are NOT written and dcum is read-only (it must hold
+     * the total gradient w.r.t. cum_t; dcum_add must be NULL): the caller runs st_attn_hist_job next, which forms them. */
+    int parts; float* dloc_part;
+    /* up to three more addends of the context gradient, behind dctx[0 .. n_dctx): the slabs of a K-split product (the gradient w.r.t.
+     * ctx_{t} inside dxq_{t+1} when that launch ran in the partial form) */
+    const float* dctx_more[3]; int ld_dctx_more[3]; int n_dctx_more;
+} st_attn_bwd_job;
+/* one attention-step backward, one workgroup per utterance (the whole step); job->s_in NULL: S is recomputed and loc_t written;
+ * job->dpq_t16.base NULL: no T16 copy of dpq; job->parts must be 0 or 1 (the split forms exist only hosted) */
+int st_attn_step_bwd(const st_attn_bwd_job* job, void* stream);
 
 /* dmem(b,l,:) = sum_t align(b,t,l) * dctx_tape(t,b,:)   (gradient of the encoder memory through the contexts) */
 int st_attn_dmem(const float* align, const float* dctx_tape, float* dmem, int B, int steps, int L, int E, void* stream);
@@ -926,48 +942,6 @@ int st_decoder_bwd_fuse_dims(const st_decoder_dims* d);
  * attention workgroups per utterance (1, 2 or 4), bits 12..15 the decoder cell's K-split slabs (0 without the partial product), bits
  * 16..19 the query cell's (0 without it) */
 int st_decoder_bwd_forms(const st_decoder_dims* d, const st_decoder_bwd_io* io);
-/* st_attn_step_bwd with S = pm + W_l loc of the step given (s_in, (B,L,A)): loc_t is not written (may be NULL) */
-int st_attn_step_bwd_s(const float* pq, const float* pm, const float* memory,
-                       const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                       const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                       const float* const* dctx, const int* ld_dctx, int n_dctx,
-                       const float* const* dw_direct, const int* ld_dw, int n_dw,
-                       float* dcum, const float* dcum_add, int ld_dcum_add,
-                       float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                       float* dctx_t, float* dv_t, const float* s_in,
-                       int B, int L, int A, int E, int F, int K, void* stream);
-/* st_attn_step_bwd_s with a second copy of dpq in the T16 tile layout (K = A): the operand of the packed W_q^T product that follows */
-int st_attn_step_bwd_t16(const float* pq, const float* pm, const float* memory,
-                         const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                         const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                         const float* const* dctx, const int* ld_dctx, int n_dctx,
-                         const float* const* dw_direct, const int* ld_dw, int n_dw,
-                         float* dcum, const float* dcum_add, int ld_dcum_add,
-                         float* dpq, const st_t16_view* dpq_t16, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                         float* dctx_t, float* dv_t, const float* s_in,
-                         int B, int L, int A, int E, int F, int K, void* stream);
-/* The arguments of st_attn_step_bwd_t16 as a struct, for the launch that hosts the attention backward of BPTT step t beside the
- * decoder cell's backward product of step t-1 (the decoder cell's recurrence does not depend on the attention / query chain of the
- * same step; backward of src/module.py:247-283): st_skinny_linear_packed_lstm_bwd_fwd + st_attn_step_bwd_t16 in ONE launch. */
-typedef struct st_attn_bwd_job {
-    const float* pq; const float* pm; const float* memory;
-    const float* w_prev; int ld_wprev; const float* w_cum_prev; const float* w; int ld_w;
-    const float* loc_conv_w; const float* loc_lin_w; const float* v;
-    const float* dctx[3]; int ld_dctx[3]; int n_dctx;
-    const float* dw_direct[3]; int ld_dw[3]; int n_dw;
-    float* dcum; const float* dcum_add; int ld_dcum_add;
-    float* dpq; st_t16_view dpq_t16; float* dhist; float* ds_t; float* loc_t; float* dloc_t; float* hist_t;
-    float* dctx_t; float* dv_t; const float* s_in;
-    int B, L, A, E, F, K;
-    /* parts > 1 (2 or 4; 0 / 1 = the whole step in one workgroup per utterance): `parts` workgroups per utterance, each taking A / parts
-     * attention dims of the energy gradient; ds_t / dpq / dv_t / dctx_t are complete afterwards, the location-feature gradient only as
-     * `parts` partial sums in dloc_part (parts, B, L, F).  dhist / dloc_t / hist_t are NOT written and dcum is read-only (it must hold
-     * the total gradient w.r.t. cum_t; dcum_add must be NULL): the caller runs st_attn_hist_job next, which forms them. */
-    int parts; float* dloc_part;
-    /* up to three more addends of the context gradient, behind dctx[0 .. n_dctx): the slabs of a K-split product (the gradient w.r.t.
-     * ctx_{t} inside dxq_{t+1} when that launch ran in the partial form) */
-    const float* dctx_more[3]; int ld_dctx_more[3]; int n_dctx_more;
-} st_attn_bwd_job;
 /* What a split attention backward (st_attn_bwd_job.parts > 1) leaves behind, one workgroup per utterance: dloc = the partial sums added in
  * part order -> dloc_t (B, L, F); hist_t (B, L, 2) = [w_{t-1}, cum_{t-1}]; dhist (B, 2, L) = the gradient w.r.t. that history through the
  * location conv (the transposed convolution of dloc with loc_conv_w (F, 2, K)); dcum (B, L; may be NULL) += dhist(:, 1, :), the gradient
@@ -979,15 +953,17 @@ typedef struct st_attn_hist_job {
     float* dloc_t; float* hist_t; float* dhist; float* dcum;
     int B, L, F, K;
 } st_attn_hist_job;
-/* job may be NULL (the plain product); ab->s_in must be given (the forward kept S) */
 /* two st_skinny_linear_packed_lstm_bwd_fwd of one shape in one launch (arrays of two; y2 or its entries may be NULL) */
 int st_skinny_linear_packed_lstm_bwd_pair_fwd(const float* const* packed_w2, const st_t16_view* x2, int K, float* const* y2, int ldy,
                                               int B, int N, const st_lstm_pw_job* job2, void* stream);
+/* st_skinny_linear_packed_lstm_bwd_fwd + st_attn_step_bwd in ONE launch: the attention backward of BPTT step t beside the decoder cell's
+ * backward product of step t-1 (the decoder cell's recurrence does not depend on the attention / query chain of the same step).  job may
+ * be NULL (the plain product); ab->s_in must be given (the forward kept S) */
 int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
                                               const st_lstm_pw_job* job, const st_attn_bwd_job* ab, void* stream);
 /* 1 when the attention backward's 48-position block (+ a hosting product's 8 KB) fits the LDS for these dims: what parts > 1 needs */
 int st_attn_bwd_wide_fits(int L, int A, int E, int F, int K);
-/* The launch an attention-step backward takes, from shapes alone (touches no memory): hosted = 0 st_attn_step_bwd[_s|_t16] (parts must be
+/* The launch an attention-step backward takes, from shapes alone (touches no memory): hosted = 0 st_attn_step_bwd (parts must be
  * 1), 1 st_skinny_linear_packed_lstm_bwd_attn_bwd beside a product of N outputs for B rows, 2 st_skinny_partial_attn_bwd; has_s: the
  * forward's S is given (s_in); loc_lin_w only for its alignment.  Returns kernel | wide << 4 | opt_in << 5 | s << 6 | wl_fast << 7 |
  * mem_pf << 8 --
@@ -999,10 +975,6 @@ int st_attn_bwd_wide_fits(int L, int A, int E, int F, int K);
  * -- or a refusal: -1 bad dims, -2 the plain launch needs more than 160 KiB of LDS, -3 hosted without S, -4 parts not possible (not 2 or
  * 4, A does not split, or the lean image does not fit), -5 not the partial form's two-part job or rows */
 int st_attn_bwd_variant(int L, int A, int E, int F, int K, int has_s, int parts, int hosted, int B, int N, const float* loc_lin_w);
-/* st_skinny_linear_packed_lstm_bwd_fwd with an st_attn_hist_job beside it in the same launch (the BPTT step's W_q^T dpq product, which
- * occupies half of the compute units, hosts the history part of the step's split attention backward) */
-int st_skinny_linear_packed_lstm_bwd_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                               const st_lstm_pw_job* job, const st_attn_hist_job* hist, void* stream);
 /* K-split partial product for 16 < B <= 32 rows: part(s, b, n) = sum over the s-th of S equal ranges of k of x(b, k) W(n, k) -- two row
  * tiles and both batch tiles per workgroup (half the bytes per output of st_skinny_linear_packed_fwd, whose workgroups each re-read a
  * whole batch tile of x), N / 32 * S workgroups; N % 32 == 0, (K / 16) % S == 0; part (S, B, N).  With `ab` (an st_attn_bwd_job with
@@ -1022,7 +994,8 @@ int st_skinny_partial_attn_bwd(const float* packed_w, const st_t16_view* x, int 
  * st_lstm_pw_job.dh1_slabs) */
 int st_skinny_partial_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* part, int S, int B, int N,
                                 const st_attn_hist_job* hist, void* stream);
-/* st_skinny_linear_packed_lstm_bwd_attn_hist with an st_partial_sum_job as well (same launch); hist may be NULL */
+/* st_skinny_linear_packed_lstm_bwd_fwd with an st_attn_hist_job and an st_partial_sum_job beside it in the same launch (the BPTT step's
+ * W_q^T dpq product, which occupies half of the compute units); hist may be NULL */
 int st_skinny_linear_packed_lstm_bwd_attn_hist_sum(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
                                                    const st_lstm_pw_job* job, const st_attn_hist_job* hist,
                                                    const st_partial_sum_job* sum, void* stream);

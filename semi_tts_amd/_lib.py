@@ -263,12 +263,7 @@ SIGNATURES = {
     'st_decoder_pack': [C.POINTER(StDecoderWeights), C.POINTER(StDecoderDims), P, P],
     'st_decoder_forward': [C.POINTER(StDecoderWeights), C.POINTER(StDecoderDims), C.POINTER(StDecoderIO), P],
     'st_decoder_fwd_forms': [C.POINTER(StDecoderDims), C.POINTER(StDecoderIO), I, I],
-    'st_attn_step_bwd': [P, P, P, P, I, P, P, I, P, P, P, C.POINTER(P), C.POINTER(I), I, C.POINTER(P), C.POINTER(I), I,
-                         P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
-    'st_attn_step_bwd_s': [P, P, P, P, I, P, P, I, P, P, P, C.POINTER(P), C.POINTER(I), I, C.POINTER(P), C.POINTER(I), I,
-                           P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
-    'st_attn_step_bwd_t16': [P, P, P, P, I, P, P, I, P, P, P, C.POINTER(P), C.POINTER(I), I, C.POINTER(P), C.POINTER(I), I,
-                             P, P, I, P, C.POINTER(StT16View), P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    'st_attn_step_bwd': [C.POINTER(StAttnBwdJob), P],
     'st_skinny_linear_packed_lstm_bwd_fwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), P],
     'st_skinny_linear_packed_lstm_bwd_attn_bwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), C.POINTER(StAttnBwdJob), P],
     'st_attn_bwd_wide_fits': [I, I, I, I, I],
@@ -282,7 +277,6 @@ SIGNATURES = {
     'st_skinny_partial_attn_bwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StAttnBwdJob), P],
     'st_skinny_linear_packed_lstm_bwd_attn_hist_sum': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), C.POINTER(StAttnHistJob),
                                                        C.POINTER(StPartialSumJob), P],
-    'st_skinny_linear_packed_lstm_bwd_attn_hist': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), C.POINTER(StAttnHistJob), P],
     'st_lstm_seq2_fwd': [C.POINTER(P), C.POINTER(P), C.POINTER(P), P, I, C.POINTER(I), P, C.POINTER(P), C.POINTER(P), I, I, I, P],
     'st_lstm_seq2_persist_supported': [I, I, I, I, I, I],
     'st_lstm_seq2_persist_fwd': [C.POINTER(P), C.POINTER(P), C.POINTER(P), P, I, C.POINTER(I), C.POINTER(P), C.POINTER(P), I, I, I, P, P],

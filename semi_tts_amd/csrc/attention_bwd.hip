@@ -100,24 +100,16 @@ extern "C" int st_attn_dmem(const float* align, const float* dctx_tape, float* d
     return 0;
 }
 
-static int ab_step_impl(const st_t16_view* dpq_t16, const float* pq, const float* pm, const float* memory,
-                                const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                                const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                const float* const* dctx, const int* ld_dctx, int n_dctx,
-                                const float* const* dw_direct, const int* ld_dw, int n_dw,
-                                float* dcum, const float* dcum_add, int ld_dcum_add,
-                                float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                                float* dctx_t, float* dv_t, const float* s_in,
-                                int B, int L, int A, int E, int F, int K, void* stream) {
+// one attention-step backward, one workgroup per utterance (the job is include/semitts.h's st_attn_bwd_job; the split forms exist only hosted)
+extern "C" int st_attn_step_bwd(const st_attn_bwd_job* job, void* stream) {
     (void)hipGetLastError();
+    ST_CHECK_ARG(job, "st_attn_step_bwd: null job");
+    ST_CHECK_ARG(job->parts == 0 || job->parts == 1, "st_attn_step_bwd: parts = %d (the split forms exist only hosted: 0 or 1 here)", job->parts);
     AbArgs a;
-    if (ab_fill(a, dpq_t16, pq, pm, memory, w_prev, ld_wprev, w_cum_prev, w, ld_w, loc_conv_w, loc_lin_w, v, dctx, ld_dctx, n_dctx,
-                dw_direct, ld_dw, n_dw, dcum, dcum_add, ld_dcum_add, dpq, dhist, ds_t, loc_t, dloc_t, hist_t, dctx_t, dv_t, s_in,
-                B, L, A, E, F, K)) return -1;
+    if (ab_fill(a, job)) return -1;
     // the wide block when the forward kept S and its LDS image fits; two workgroups of it never share a compute unit anyway (B workgroups)
-    const AbPlan pl = ab_plan(L, A, E, F, K, s_in != nullptr, 1, 0, B, B, 0, st_aligned16(loc_lin_w));
-    ST_CHECK_ARG(pl.code >= 0, "st_attn_step_bwd: L=%d needs %zu bytes of LDS (> 160 KiB)", L, pl.lds);
-    const bool wide = pl.wide;
+    const AbPlan pl = ab_plan(a.L, a.A, a.E, a.F, a.K, a.s_in != nullptr, 1, 0, a.B, a.B, 0, st_aligned16(a.loc_lin_w));
+    ST_CHECK_ARG(pl.code >= 0, "st_attn_step_bwd: L=%d needs %zu bytes of LDS (> 160 KiB)", a.L, pl.lds);
     const size_t lds = pl.lds;
     static size_t lds_enabled = 0;
     if (pl.opt_in && lds > lds_enabled) {
@@ -126,14 +118,14 @@ static int ab_step_impl(const st_t16_view* dpq_t16, const float* pq, const float
         ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_kernel<true, AB_LBLK_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_enabled = lds;
     }
-    if (wide) hipLaunchKernelGGL((ab_kernel<true, AB_LBLK_MAX>), dim3(B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
-    else if (s_in) hipLaunchKernelGGL((ab_kernel<true, 16>), dim3(B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((ab_kernel<false, 16>), dim3(B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
+    if (pl.wide) hipLaunchKernelGGL((ab_kernel<true, AB_LBLK_MAX>), dim3(a.B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
+    else if (a.s_in) hipLaunchKernelGGL((ab_kernel<true, 16>), dim3(a.B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((ab_kernel<false, 16>), dim3(a.B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
     ST_LAUNCH_CHECK();
     return 0;
 }
 
-// the launch st_attn_step_bwd[_s|_t16] (hosted = 0), st_skinny_linear_packed_lstm_bwd_attn_bwd (1) or st_skinny_partial_attn_bwd (2) takes
+// the launch st_attn_step_bwd (hosted = 0), st_skinny_linear_packed_lstm_bwd_attn_bwd (1) or st_skinny_partial_attn_bwd (2) takes
 // for these dims (see AbPlan); touches no memory
 extern "C" int st_attn_bwd_variant(int L, int A, int E, int F, int K, int has_s, int parts, int hosted, int B, int N, const float* loc_lin_w) {
     if (hosted < 0 || hosted > 2 || (hosted == 0 && parts > 1)) return AB_R_DIMS;
@@ -144,47 +136,4 @@ extern "C" int st_attn_bwd_variant(int L, int A, int E, int F, int K, int has_s,
 extern "C" int st_attn_bwd_wide_fits(int L, int A, int E, int F, int K) {
     if (L <= 0 || A <= 0 || E <= 0 || F <= 0 || K <= 0) return 0;
     return (size_t)ab_layout(L, A, E, F, K, AB_LBLK_MAX, true).total * sizeof(float) + 8 * 64 * sizeof(f32x4) <= 160 * 1024 ? 1 : 0;
-}
-
-extern "C" int st_attn_step_bwd_s(const float* pq, const float* pm, const float* memory,
-                                  const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                                  const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                  const float* const* dctx, const int* ld_dctx, int n_dctx,
-                                  const float* const* dw_direct, const int* ld_dw, int n_dw,
-                                  float* dcum, const float* dcum_add, int ld_dcum_add,
-                                  float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                                  float* dctx_t, float* dv_t, const float* s_in,
-                                  int B, int L, int A, int E, int F, int K, void* stream) {
-    return ab_step_impl(nullptr, pq, pm, memory, w_prev, ld_wprev, w_cum_prev, w, ld_w, loc_conv_w, loc_lin_w, v, dctx, ld_dctx, n_dctx,
-                        dw_direct, ld_dw, n_dw, dcum, dcum_add, ld_dcum_add, dpq, dhist, ds_t, loc_t, dloc_t, hist_t, dctx_t, dv_t, s_in,
-                        B, L, A, E, F, K, stream);
-}
-
-// the same with a second copy of dpq in the T16 tile layout (the x operand of the packed W_q^T product that follows in the BPTT loop)
-extern "C" int st_attn_step_bwd_t16(const float* pq, const float* pm, const float* memory,
-                                    const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                                    const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                    const float* const* dctx, const int* ld_dctx, int n_dctx,
-                                    const float* const* dw_direct, const int* ld_dw, int n_dw,
-                                    float* dcum, const float* dcum_add, int ld_dcum_add,
-                                    float* dpq, const st_t16_view* dpq_t16, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                                    float* dctx_t, float* dv_t, const float* s_in,
-                                    int B, int L, int A, int E, int F, int K, void* stream) {
-    return ab_step_impl(dpq_t16, pq, pm, memory, w_prev, ld_wprev, w_cum_prev, w, ld_w, loc_conv_w, loc_lin_w, v, dctx, ld_dctx, n_dctx,
-                        dw_direct, ld_dw, n_dw, dcum, dcum_add, ld_dcum_add, dpq, dhist, ds_t, loc_t, dloc_t, hist_t, dctx_t, dv_t, s_in,
-                        B, L, A, E, F, K, stream);
-}
-
-extern "C" int st_attn_step_bwd(const float* pq, const float* pm, const float* memory,
-                                const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                                const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                const float* const* dctx, const int* ld_dctx, int n_dctx,
-                                const float* const* dw_direct, const int* ld_dw, int n_dw,
-                                float* dcum, const float* dcum_add, int ld_dcum_add,
-                                float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                                float* dctx_t, float* dv_t,
-                                int B, int L, int A, int E, int F, int K, void* stream) {
-    return st_attn_step_bwd_s(pq, pm, memory, w_prev, ld_wprev, w_cum_prev, w, ld_w, loc_conv_w, loc_lin_w, v, dctx, ld_dctx, n_dctx,
-                              dw_direct, ld_dw, n_dw, dcum, dcum_add, ld_dcum_add, dpq, dhist, ds_t, loc_t, dloc_t, hist_t, dctx_t, dv_t,
-                              nullptr, B, L, A, E, F, K, stream);
 }

@@ -662,33 +662,29 @@ __device__ __forceinline__ void ab_hist_body(const AbHistArgs& h, const int b, f
     AB_PROF(5);
 }
 
-// argument block of one step from the C-ABI arguments (shared by the plain and the hosted launch); returns 0 or -1 with the error set
-inline int ab_fill(AbArgs& a, const st_t16_view* dpq_t16, const float* pq, const float* pm, const float* memory,
-                   const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                   const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                   const float* const* dctx, const int* ld_dctx, int n_dctx,
-                   const float* const* dw_direct, const int* ld_dw, int n_dw,
-                   float* dcum, const float* dcum_add, int ld_dcum_add,
-                   float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                   float* dctx_t, float* dv_t, const float* s_in,
-                   int B, int L, int A, int E, int F, int K) {
-    ST_CHECK_ARG(pq && pm && memory && w_cum_prev && w && loc_conv_w && loc_lin_w && v, "st_attn_step_bwd: null input");
-    ST_CHECK_ARG(dpq && dhist && ds_t && (loc_t || s_in) && dloc_t && hist_t && dctx_t && dv_t, "st_attn_step_bwd: null output");
-    ST_CHECK_ARG(B > 0 && L > 0 && A > 0 && E > 0 && F > 0 && K > 0 && (K & 1), "st_attn_step_bwd: bad dims (K must be odd)");
-    ST_CHECK_ARG(A <= AB_THREADS / 2 && AB_THREADS % A == 0, "st_attn_step_bwd: attn_dim=%d must divide %d", A, AB_THREADS / 2);
-    ST_CHECK_ARG((E & 3) == 0 && st_aligned16(memory), "st_attn_step_bwd: E=%d must be a multiple of 4 (16-byte aligned rows)", E);
-    ST_CHECK_ARG(F <= AB_FMAX, "st_attn_step_bwd: n_location_filters=%d > %d", F, AB_FMAX);
-    ST_CHECK_ARG(n_dctx >= 0 && n_dctx <= AB_NDCTX && n_dw >= 0 && n_dw <= 3, "st_attn_step_bwd: at most %d context addends, 3 weight addends", AB_NDCTX);
+// argument block of one step from its job (shared by the plain and the hosted launches): the context addends are dctx[0 .. n_dctx) followed
+// by dctx_more[0 .. n_dctx_more); parts / dloc_part stay with the caller's plan.  Returns 0 or -1 with the error set
+inline int ab_fill(AbArgs& a, const st_attn_bwd_job* j) {
+    ST_CHECK_ARG(j->pq && j->pm && j->memory && j->w_cum_prev && j->w && j->loc_conv_w && j->loc_lin_w && j->v, "st_attn_step_bwd: null input");
+    ST_CHECK_ARG(j->dpq && j->dhist && j->ds_t && (j->loc_t || j->s_in) && j->dloc_t && j->hist_t && j->dctx_t && j->dv_t, "st_attn_step_bwd: null output");
+    ST_CHECK_ARG(j->B > 0 && j->L > 0 && j->A > 0 && j->E > 0 && j->F > 0 && j->K > 0 && (j->K & 1), "st_attn_step_bwd: bad dims (K must be odd)");
+    ST_CHECK_ARG(j->A <= AB_THREADS / 2 && AB_THREADS % j->A == 0, "st_attn_step_bwd: attn_dim=%d must divide %d", j->A, AB_THREADS / 2);
+    ST_CHECK_ARG((j->E & 3) == 0 && st_aligned16(j->memory), "st_attn_step_bwd: E=%d must be a multiple of 4 (16-byte aligned rows)", j->E);
+    ST_CHECK_ARG(j->F <= AB_FMAX, "st_attn_step_bwd: n_location_filters=%d > %d", j->F, AB_FMAX);
+    ST_CHECK_ARG(j->n_dctx >= 0 && j->n_dctx <= 3 && j->n_dctx_more >= 0 && j->n_dctx_more <= 3 && j->n_dw >= 0 && j->n_dw <= 3,
+                 "st_attn_step_bwd: at most 3 + 3 context addends, 3 weight addends");
     memset(&a, 0, sizeof(a));
-    a.pq = pq; a.pm = pm; a.memory = memory; a.w_prev = w_prev; a.ld_wprev = ld_wprev; a.w_cum_prev = w_cum_prev;
-    a.w = w; a.ld_w = ld_w; a.loc_conv_w = loc_conv_w; a.loc_lin_w = loc_lin_w; a.v = v;
-    for (int j = 0; j < n_dctx; ++j) { a.dctx[j] = dctx[j]; a.ld_dctx[j] = ld_dctx[j]; }
-    for (int j = 0; j < n_dw; ++j) { a.dw_direct[j] = dw_direct[j]; a.ld_dw[j] = ld_dw[j]; }
-    a.dcum = dcum; a.dcum_add = dcum_add; a.ld_dcum_add = ld_dcum_add;
-    a.dpq = dpq; a.dhist = dhist; a.ds_t = ds_t; a.loc_t = loc_t; a.dloc_t = dloc_t; a.hist_t = hist_t; a.dctx_t = dctx_t; a.dv_t = dv_t;
-    a.s_in = s_in;
-    if (dpq_t16 && dpq_t16->base) { a.dpq_t16 = dpq_t16->base; a.dpq_kbs = dpq_t16->kb_stride; a.dpq_kb0 = dpq_t16->kb0; }
-    a.B = B; a.L = L; a.A = A; a.E = E; a.F = F; a.K = K;
+    a.pq = j->pq; a.pm = j->pm; a.memory = j->memory; a.w_prev = j->w_prev; a.ld_wprev = j->ld_wprev; a.w_cum_prev = j->w_cum_prev;
+    a.w = j->w; a.ld_w = j->ld_w; a.loc_conv_w = j->loc_conv_w; a.loc_lin_w = j->loc_lin_w; a.v = j->v;
+    int n = 0;
+    for (int q = 0; q < j->n_dctx; ++q) { a.dctx[n] = j->dctx[q]; a.ld_dctx[n++] = j->ld_dctx[q]; }
+    for (int q = 0; q < j->n_dctx_more; ++q) { a.dctx[n] = j->dctx_more[q]; a.ld_dctx[n++] = j->ld_dctx_more[q]; }
+    for (int q = 0; q < j->n_dw; ++q) { a.dw_direct[q] = j->dw_direct[q]; a.ld_dw[q] = j->ld_dw[q]; }
+    a.dcum = j->dcum; a.dcum_add = j->dcum_add; a.ld_dcum_add = j->ld_dcum_add;
+    a.dpq = j->dpq; a.dhist = j->dhist; a.ds_t = j->ds_t; a.loc_t = j->loc_t; a.dloc_t = j->dloc_t; a.hist_t = j->hist_t; a.dctx_t = j->dctx_t;
+    a.dv_t = j->dv_t; a.s_in = j->s_in;
+    if (j->dpq_t16.base) { a.dpq_t16 = j->dpq_t16.base; a.dpq_kbs = j->dpq_t16.kb_stride; a.dpq_kb0 = j->dpq_t16.kb0; }
+    a.B = j->B; a.L = j->L; a.A = j->A; a.E = j->E; a.F = j->F; a.K = j->K;
     return 0;
 }
 
@@ -700,7 +696,7 @@ inline size_t ab_lds_bytes(const AbArgs& a, bool wide, int parts = 1) {
     return (size_t)ab_layout(a.L, a.A / parts, a.E, a.F, a.K, wide ? AB_LBLK_MAX : 16, a.s_in != nullptr, parts > 1).total * sizeof(float);
 }
 
-// The launch an attention-step backward takes: one plan for the plain entry points (ab_step_impl) and the two hosted ones
+// The launch an attention-step backward takes: one plan for the plain entry point (st_attn_step_bwd) and the two hosted ones
 // (st_skinny_linear_packed_lstm_bwd_attn_bwd, st_skinny_partial_attn_bwd).  Shapes and flags only -- pointer checks stay with the callers.
 // st_attn_bwd_variant reports `code` (include/semitts.h); a refusal is a negative code and the callers' error message.
 enum AbKernel { AB_K_PLAIN = 0, AB_K_HOSTED = 1, AB_K_FALLBACK = 2, AB_K_DUAL = 3, AB_K_NB2 = 4, AB_K_PARTS2 = 5, AB_K_PARTS4 = 6,

@@ -16,37 +16,6 @@
 #include "st_common.h"
 #include "loop_graph.h"
 
-extern "C" int st_attn_step_bwd(const float* pq, const float* pm, const float* memory,
-                                const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                                const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                const float* const* dctx, const int* ld_dctx, int n_dctx,
-                                const float* const* dw_direct, const int* ld_dw, int n_dw,
-                                float* dcum, const float* dcum_add, int ld_dcum_add,
-                                float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                                float* dctx_t, float* dv_t,
-                                int B, int L, int A, int E, int F, int K, void* stream);
-extern "C" int st_attn_step_bwd_s(const float* pq, const float* pm, const float* memory,
-                                  const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                                  const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                  const float* const* dctx, const int* ld_dctx, int n_dctx,
-                                  const float* const* dw_direct, const int* ld_dw, int n_dw,
-                                  float* dcum, const float* dcum_add, int ld_dcum_add,
-                                  float* dpq, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                                  float* dctx_t, float* dv_t, const float* s_in,
-                                  int B, int L, int A, int E, int F, int K, void* stream);
-
-extern "C" int st_attn_step_bwd_t16(const float* pq, const float* pm, const float* memory,
-                                    const float* w_prev, int ld_wprev, const float* w_cum_prev, const float* w, int ld_w,
-                                    const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                    const float* const* dctx, const int* ld_dctx, int n_dctx,
-                                    const float* const* dw_direct, const int* ld_dw, int n_dw,
-                                    float* dcum, const float* dcum_add, int ld_dcum_add,
-                                    float* dpq, const st_t16_view* dpq_t16, float* dhist, float* ds_t, float* loc_t, float* dloc_t, float* hist_t,
-                                    float* dctx_t, float* dv_t, const float* s_in,
-                                    int B, int L, int A, int E, int F, int K, void* stream);
-
-extern "C" int st_attn_bwd_wide_fits(int L, int A, int E, int F, int K);
-
 namespace {
 // which forms the fused BPTT loop takes (see st_decoder_bwd_forms): parts of the hosted attention backward, the two partial products
 struct BwdForms { int parts; bool partial_d, partial_q; int dsplits, qsplits; };
@@ -167,6 +136,31 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
                  "operands, dimensions st_decoder_bwd_fuse_dims rejects, or a step tape that is not 16-byte aligned)");
     ST_CHECK_ARG(packed || (w->q_w_cat_t && w->d_w_cat_t), "st_decoder_backward: neither packed nor natural [W_ih | W_hh]^T");
     ST_CHECK_ARG(fuse_pw || w->attn_query_w_t, "st_decoder_backward: natural W_q^T missing (needed without fuse_pw)");
+    // the attention backward of step t (c. above): ONE description (st_attn_bwd_job) for the four launches that run it -- the stand-alone one of
+    // either loop and the three that host it beside a product.  dxq_next: where the gradient w.r.t. [dec_in | ctx | h_q] of step t+1 starts
+    // (NULL: no such addend); dcum_add: what is added to the carried dcum.  The fused loop adds its T16 copy, slabs and split to this.
+    auto attn_job = [&](int t, const float* dxq_next, const float* dcum_add) {
+        const float* dxo = io->dxo + (size_t)t * Bp * XO;
+        const float* dhist_next = io->dhist[(t + 1) & 1];
+        st_attn_bwd_job ab;
+        memset(&ab, 0, sizeof(ab));
+        ab.pq = io->pq_all + (size_t)t * Bp * A; ab.pm = io->pm; ab.memory = io->memory;
+        ab.w_prev = t > 0 ? io->align + (size_t)(t - 1) * L : nullptr; ab.ld_wprev = ldal; ab.w_cum_prev = io->wcum_tape + (size_t)t * BL;
+        ab.w = io->align + (size_t)t * L; ab.ld_w = ldal;
+        ab.loc_conv_w = w->attn_loc_conv_w; ab.loc_lin_w = w->attn_loc_lin_w; ab.v = w->attn_v;
+        ab.dctx[0] = dxo + D; ab.dctx[1] = io->dxd + (size_t)t * Bp * XD; ab.dctx[2] = dxq_next ? dxq_next + P : nullptr;
+        ab.ld_dctx[0] = XO; ab.ld_dctx[1] = XD; ab.ld_dctx[2] = XQ; ab.n_dctx = 3;
+        ab.dw_direct[0] = dhist_next; ab.dw_direct[1] = io->dalign ? io->dalign + (size_t)t * L : nullptr; ab.ld_dw[0] = 2 * L; ab.ld_dw[1] = ldal;
+        ab.n_dw = io->dalign ? 2 : 1;
+        ab.dcum = io->dcum; ab.dcum_add = dcum_add; ab.ld_dcum_add = 2 * L;
+        ab.dpq = io->dpq + (size_t)t * Bp * A; ab.dhist = io->dhist[t & 1]; ab.ds_t = io->ds_tape + (size_t)t * BL * A;
+        ab.loc_t = io->loc_tape + (size_t)t * BL * d->F; ab.dloc_t = io->dloc_tape + (size_t)t * BL * d->F;
+        ab.hist_t = io->hist_tape + (size_t)t * BL * 2; ab.dctx_t = io->dctx_tape + (size_t)t * B * E; ab.dv_t = io->dv_tape + (size_t)t * B * A;
+        // S_t from the forward when it kept it (S_0 = pm: no history before the first step); loc_tape is then an input
+        ab.s_in = io->attn_s_tape ? (t == 0 ? io->pm : io->attn_s_tape + (size_t)t * BL * A) : nullptr;
+        ab.B = B; ab.L = L; ab.A = A; ab.E = E; ab.F = d->F; ab.K = d->K;
+        return ab;
+    };
     if (fuse_pw) {
         // Four launches per step instead of six: the pointwise half of each cell's backward step runs in the epilogue of the product
         // that makes its dh -- dgates_d(t) . [W_ih_d | W_hh_d] makes dh_d(t-1) in its last D columns (so the decoder cell's pointwise
@@ -201,16 +195,7 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
             float* dxd = io->dxd + (size_t)t * Bp * XD;
             st_t16_view x_v = {dgd_buf[t & 1], kbd, 0};
             st_lstm_pw_job j;
-            memset(&j, 0, sizeof(j));
-            if (t > 0) {
-                j.n0 = E + Q; j.H = D;
-                j.dh1 = io->dxo + (size_t)(t - 1) * Bp * XO; j.ld1 = XO;
-                j.mask = io->d_mask ? io->d_mask + (size_t)(t - 1) * BD : nullptr;
-                j.gates = io->gates_d_tape + (size_t)(t - 1) * 4 * BD;
-                j.c = io->cd_tape + (size_t)t * BD; j.ldc = D; j.c_prev = io->cd_tape + (size_t)(t - 1) * BD; j.ldcp = D;
-                j.dc = io->dcd; j.dgates = io->dgd + (size_t)(t - 1) * Bp * 4 * D; j.ldg = 4 * D;
-                j.dgates_t16.base = dgd_buf[(t - 1) & 1]; j.dgates_t16.kb_stride = kbd; j.dgates_t16.kb0 = 0;
-            }
+            if (t > 0) pw_d(t, j);
             if (ab) return st_skinny_linear_packed_lstm_bwd_attn_bwd(w->d_w_cat_t_p16, &x_v, 4 * D, dxd, XD, B, XD, t > 0 ? &j : nullptr, ab, stream);
             if (t > 0) return st_skinny_linear_packed_lstm_bwd_fwd(w->d_w_cat_t_p16, &x_v, 4 * D, dxd, XD, B, XD, &j, stream);
             return st_skinny_linear_packed_fwd(w->d_w_cat_t_p16, &x_v, 4 * D, nullptr, ST_ACT_NONE, nullptr, 0, dxd, XD, nullptr,
@@ -225,51 +210,27 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
         const size_t qslab = (size_t)B * XQ;                 // one slab of dxq_part; a step holds qsplits of them
         if (overlap) { rc = product_d(steps - 1, nullptr); if (rc) return rc; }
         for (int t = steps - 1; t >= 0; --t) {
-            const float* dxo = io->dxo + (size_t)t * Bp * XO;
             float* dxd = io->dxd + (size_t)t * Bp * XD;
             float* dxq = io->dxq + (size_t)t * Bp * XQ;
             // (no step behind the last one: absent addends instead of a zero slot -- the tapes need not start from zeros)
             const float* dxq_next = t + 1 < steps ? (partial_q ? io->dxq_part + (size_t)(t + 1) * qsplits * qslab : io->dxq + (size_t)(t + 1) * Bp * XQ) : nullptr;
-            float* dpq = io->dpq + (size_t)t * Bp * A;
             float* dhist_cur = io->dhist[t & 1];
             const float* dhist_next = io->dhist[(t + 1) & 1];
             if (!overlap) { rc = product_d(t, nullptr); if (rc) return rc; }
-            // c. attention (dpq also in T16)
-            st_attn_bwd_job ab;
-            memset(&ab, 0, sizeof(ab));
-            ab.pq = io->pq_all + (size_t)t * Bp * A; ab.pm = io->pm; ab.memory = io->memory;
-            ab.w_prev = t > 0 ? io->align + (size_t)(t - 1) * L : nullptr; ab.ld_wprev = ldal; ab.w_cum_prev = io->wcum_tape + (size_t)t * BL;
-            ab.w = io->align + (size_t)t * L; ab.ld_w = ldal;
-            ab.loc_conv_w = w->attn_loc_conv_w; ab.loc_lin_w = w->attn_loc_lin_w; ab.v = w->attn_v;
-            ab.dctx[0] = dxo + D; ab.dctx[1] = dxd; ab.dctx[2] = dxq_next ? dxq_next + P : nullptr; ab.ld_dctx[0] = XO; ab.ld_dctx[1] = XD; ab.ld_dctx[2] = XQ; ab.n_dctx = 3;
+            // c. attention (dpq also in T16; split form: the history job of step t+1 has already added dhist(t+1)[1] into dcum)
+            st_attn_bwd_job ab = attn_job(t, dxq_next, parts > 1 ? nullptr : dhist_next + L);
+            ab.dpq_t16 = dpq_v;
             if (partial_q && dxq_next) {     // the other slabs of dxq_{t+1} (slab order = addend order: fixed)
                 for (int sl = 1; sl < qsplits; ++sl) { ab.dctx_more[sl - 1] = dxq_next + (size_t)sl * qslab + P; ab.ld_dctx_more[sl - 1] = XQ; }
                 ab.n_dctx_more = qsplits - 1;
             }
-            ab.dw_direct[0] = dhist_next; ab.dw_direct[1] = io->dalign ? io->dalign + (size_t)t * L : nullptr; ab.ld_dw[0] = 2 * L; ab.ld_dw[1] = ldal;
-            ab.n_dw = io->dalign ? 2 : 1;
-            // (split form: the history job of step t+1 has already added dhist(t+1)[1] into dcum)
-            ab.dcum = io->dcum; ab.dcum_add = parts > 1 ? nullptr : dhist_next + L; ab.ld_dcum_add = 2 * L;
             const bool split = parts > 1 && overlap && t > 0;
             if (split) { ab.parts = parts; ab.dloc_part = io->dloc_part; }
-            ab.dpq = dpq; ab.dpq_t16 = dpq_v; ab.dhist = dhist_cur; ab.ds_t = io->ds_tape + (size_t)t * BL * A;
-            ab.loc_t = io->loc_tape + (size_t)t * BL * d->F; ab.dloc_t = io->dloc_tape + (size_t)t * BL * d->F;
-            ab.hist_t = io->hist_tape + (size_t)t * BL * 2; ab.dctx_t = io->dctx_tape + (size_t)t * B * E; ab.dv_t = io->dv_tape + (size_t)t * B * A;
-            ab.s_in = io->attn_s_tape ? (t == 0 ? io->pm : io->attn_s_tape + (size_t)t * BL * A) : nullptr;
-            ab.B = B; ab.L = L; ab.A = A; ab.E = E; ab.F = d->F; ab.K = d->K;
             if (split && partial) {      // [attention backward of t, two parts | K-split partial product of the decoder cell, step t-1]
                 st_t16_view x_v = {dgd_buf[(t - 1) & 1], kbd, 0};
                 rc = st_skinny_partial_attn_bwd(w->d_w_cat_t_p16, &x_v, 4 * D, io->dxd_part, dsplits, B, XD, &ab, stream);
             } else if (overlap && t > 0) rc = product_d(t - 1, &ab);        // [attention backward of t | decoder cell product of t-1]: one launch
-            else {
-                const float* dcx[6]; int ldx[6]; int ncx = 0;       // (the standalone call takes the slabs of dxq_{t+1} in one addend list)
-                for (int q_ = 0; q_ < ab.n_dctx; ++q_) { dcx[ncx] = ab.dctx[q_]; ldx[ncx++] = ab.ld_dctx[q_]; }
-                for (int q_ = 0; q_ < ab.n_dctx_more; ++q_) { dcx[ncx] = ab.dctx_more[q_]; ldx[ncx++] = ab.ld_dctx_more[q_]; }
-                rc = st_attn_step_bwd_t16(ab.pq, ab.pm, ab.memory, ab.w_prev, ab.ld_wprev, ab.w_cum_prev, ab.w, ab.ld_w, ab.loc_conv_w, ab.loc_lin_w,
-                                           ab.v, dcx, ldx, ncx, ab.dw_direct, ab.ld_dw, ab.n_dw, ab.dcum, ab.dcum_add, ab.ld_dcum_add,
-                                           ab.dpq, &ab.dpq_t16, ab.dhist, ab.ds_t, ab.loc_t, ab.dloc_t, ab.hist_t, ab.dctx_t, ab.dv_t, ab.s_in,
-                                           B, L, A, E, d->F, d->K, stream);
-            }
+            else rc = st_attn_step_bwd(&ab, stream);
             if (rc) return rc;
             // d + e. dh_q = W_q^T dpq + (W_hh_q^T dgates_q)_{t+1} + std * d(adapted h_q): the query cell's pointwise part in the epilogue
             {
@@ -325,7 +286,6 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
         float* dgd = io->dgd + (size_t)t * Bp * 4 * D;
         float* dgq = io->dgq + (size_t)t * Bp * 4 * Q;
         float* dpq = io->dpq + (size_t)t * Bp * A;
-        float* dhist_cur = io->dhist[t & 1];
         const float* dhist_next = io->dhist[(t + 1) & 1];
 
         if (own) {
@@ -389,22 +349,9 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
             rc = st_skinny_linear_fwd(&seg, 1, nullptr, ST_ACT_NONE, nullptr, 0, dxd, XD, 0, nullptr, 0, 0, B, XD, stream);
         }
         if (rc) return rc;
-        // c. attention
-        const float* dctx[3] = {dxo + D, dxd, dxq_next + P};
-        const int ld_dctx[3] = {XO, XD, XQ};
-        const float* dwd[2] = {dhist_next, io->dalign ? io->dalign + (size_t)t * L : nullptr};
-        const int ld_dw[2] = {2 * L, ldal};
-        // S_t from the forward when it kept it (S_0 = pm: no history before the first step); loc_tape is then an input
-        const float* s_in = io->attn_s_tape ? (t == 0 ? io->pm : io->attn_s_tape + (size_t)t * BL * A) : nullptr;
-        rc = st_attn_step_bwd_s(io->pq_all + (size_t)t * Bp * A, io->pm, io->memory,
-                              t > 0 ? io->align + (size_t)(t - 1) * L : nullptr, ldal, io->wcum_tape + (size_t)t * BL,
-                              io->align + (size_t)t * L, ldal, w->attn_loc_conv_w, w->attn_loc_lin_w, w->attn_v,
-                              dctx, ld_dctx, 3, dwd, ld_dw, io->dalign ? 2 : 1,
-                              io->dcum, dhist_next + L, 2 * L,
-                              dpq, dhist_cur, io->ds_tape + (size_t)t * BL * A, io->loc_tape + (size_t)t * BL * d->F,
-                              io->dloc_tape + (size_t)t * BL * d->F, io->hist_tape + (size_t)t * BL * 2,
-                              io->dctx_tape + (size_t)t * B * E, io->dv_tape + (size_t)t * B * A, s_in,
-                              B, L, A, E, d->F, d->K, stream);
+        // c. attention (dxq_next is never NULL here: behind the last step it is the zero slot)
+        const st_attn_bwd_job ab = attn_job(t, dxq_next, dhist_next + L);
+        rc = st_attn_step_bwd(&ab, stream);
         if (rc) return rc;
         // d. through the query projection
         seg.x = dpq; seg.ldx = A; seg.w = w->attn_query_w_t; seg.ldw = A; seg.k = A;

@@ -744,18 +744,6 @@ __global__ __launch_bounds__(KW * 64) __attribute__((amdgpu_waves_per_eu((NS > 1
     pk_body<2, NB, KW, TRIP>(a, j - by * tiles_a, by, red, &pw);
 }
 
-// the argument block of an attention-backward job: its context addends dctx[0 .. n_dctx) followed by dctx_more[0 .. n_dctx_more)
-static int ab_fill_job(AbArgs& t, const st_attn_bwd_job* ab) {
-    const float* dctx[AB_NDCTX]; int ld[AB_NDCTX]; int n = 0;
-    ST_CHECK_ARG(ab->n_dctx >= 0 && ab->n_dctx <= 3 && ab->n_dctx_more >= 0 && ab->n_dctx_more <= 3, "attention backward job: at most 3 + 3 context addends");
-    for (int j = 0; j < ab->n_dctx; ++j) { dctx[n] = ab->dctx[j]; ld[n++] = ab->ld_dctx[j]; }
-    for (int j = 0; j < ab->n_dctx_more; ++j) { dctx[n] = ab->dctx_more[j]; ld[n++] = ab->ld_dctx_more[j]; }
-    return ab_fill(t, &ab->dpq_t16, ab->pq, ab->pm, ab->memory, ab->w_prev, ab->ld_wprev, ab->w_cum_prev, ab->w, ab->ld_w, ab->loc_conv_w,
-                   ab->loc_lin_w, ab->v, dctx, ld, n, ab->dw_direct, ab->ld_dw, ab->n_dw, ab->dcum, ab->dcum_add,
-                   ab->ld_dcum_add, ab->dpq, ab->dhist, ab->ds_t, ab->loc_t, ab->dloc_t, ab->hist_t, ab->dctx_t, ab->dv_t, ab->s_in,
-                   ab->B, ab->L, ab->A, ab->E, ab->F, ab->K);
-}
-
 // (timing ablations only, in the SEPARATE library tools/gpu_ablate.sh builds with -DST_ABLATE: ST_EXP makes parts of the hosted BPTT
 // launches return at once -- results are then garbage.  The product library has no such switch: the flag is the constant 0.)
 #ifdef ST_ABLATE
@@ -1691,39 +1679,17 @@ extern "C" int st_skinny_linear_packed_fwd(const float* packed_w, const st_t16_v
                           n_split2, act2, mask2, ldmask2, y3_dst, B, N, nullptr, stream);
 }
 
-extern "C" int st_skinny_linear_packed_lstm_bwd_fwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                    const st_lstm_pw_job* job, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(y && job && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_lstm_bwd_fwd: bad arguments");
-    const int H = job->H;
-    ST_CHECK_ARG(H > 0 && H % 4 == 0 && job->n0 >= 0 && job->n0 % 16 == 0 && job->n0 + H <= N && (N % 16 == 0 || job->n0 + H <= (N & ~15)),
-                 "st_skinny_linear_packed_lstm_bwd_fwd: the cell's columns [%d, %d) must be whole tiles of the %d outputs", job->n0, job->n0 + H, N);
-    ST_CHECK_ARG(job->gates && job->c && job->dc && job->dgates && job->ldg >= 4 * H && job->ldg % 4 == 0 && job->ldc % 4 == 0 &&
-                 (!job->c_prev || job->ldcp % 4 == 0) && (!job->dh1 || job->ld1 % 4 == 0) && (!job->dh2 || job->ld2 % 4 == 0) && ldy % 4 == 0,
-                 "st_skinny_linear_packed_lstm_bwd_fwd: null operand or a row stride that is not a multiple of 4");
-    ST_CHECK_ARG(st_aligned16(job->gates) && st_aligned16(job->c) && st_aligned16(job->dc) && st_aligned16(job->dgates) && st_aligned16(y) &&
-                 (!job->c_prev || st_aligned16(job->c_prev)) && (!job->dh1 || st_aligned16(job->dh1)) && (!job->dh2 || st_aligned16(job->dh2)) &&
-                 (!job->scale2 || st_aligned16(job->scale2)) && (!job->mask || st_aligned16(job->mask)) &&
-                 (!job->dgates_t16.base || st_aligned16(job->dgates_t16.base)), "st_skinny_linear_packed_lstm_bwd_fwd: operands must be 16-byte aligned");
-    PkArgs a;
+// the plain product y = x W^T (no bias, activation or cell epilogue of its own) as a PkArgs block
+static int pk_plain_fill(PkArgs& a, const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N, const char* who) {
     memset(&a, 0, sizeof(a));
-    int rc = pk_fill(a, packed_w, x, K, "st_skinny_linear_packed_lstm_bwd_fwd");
+    int rc = pk_fill(a, packed_w, x, K, who);
     if (rc) return rc;
     a.B = B; a.N = N; a.H = 0; a.act = ST_ACT_NONE;
     a.y = y; a.ldy = ldy;
-    PkPw q;
-    memset(&q, 0, sizeof(q));
-    q.n0 = job->n0; q.H = H; q.dh1 = job->dh1; q.ld1 = job->ld1; q.dh1_slabs = job->dh1_slabs; q.dh1_slab_stride = job->dh1_slab_stride; q.dh2 = job->dh2; q.ld2 = job->ld2; q.scale2 = job->scale2; q.mask = job->mask;
-    q.gates = job->gates; q.c = job->c; q.ldc = job->ldc; q.c_prev = job->c_prev; q.ldcp = job->ldcp; q.dc = job->dc;
-    q.dgates = job->dgates; q.ldg = job->ldg; q.dg_t16 = pk_out(&job->dgates_t16);
-    const int tiles = (N + 15) / 16, BT = (B + 15) >> 4;
-    // one batch tile per workgroup, as the plain linear of these shapes runs (pk_dispatch<1>)
-    hipLaunchKernelGGL((pk_pw_kernel<1, 8, 2>), dim3(tiles, BT), dim3(8 * 64), 0, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B,
-                       a.N, a, q);
-    ST_LAUNCH_CHECK();
     return 0;
 }
 
+// the pointwise LSTM backward that rides in a product's epilogue (st_lstm_pw_job) as a PkPw block; y NULL: the product is only consumed there
 static int pk_pw_fill(PkPw& q, const st_lstm_pw_job* job, int N, int ldy, const float* y, const char* who) {
     memset(&q, 0, sizeof(q));
     const int H = job->H;
@@ -1742,6 +1708,45 @@ static int pk_pw_fill(PkPw& q, const st_lstm_pw_job* job, int N, int ldy, const 
     return 0;
 }
 
+// the history part of a split attention backward (st_attn_hist_job) as an AbHistArgs block
+static int pk_hist_fill(AbHistArgs& h, const st_attn_hist_job* hj, const char* who) {
+    ST_CHECK_ARG(hj->dloc_part && hj->parts >= 1 && hj->parts <= 4 && hj->loc_conv_w && hj->w_cum_prev && hj->dloc_t && hj->hist_t && hj->dhist &&
+                 hj->B > 0 && hj->L > 0 && hj->F > 0 && hj->K > 0 && (hj->K & 1) && hj->K <= 31, "%s: bad history job (odd K <= 31)", who);
+    memset(&h, 0, sizeof(h));
+    h.dloc_part = hj->dloc_part; h.parts = hj->parts; h.loc_conv_w = hj->loc_conv_w; h.w_prev = hj->w_prev; h.ld_wprev = hj->ld_wprev;
+    h.w_cum_prev = hj->w_cum_prev; h.dloc_t = hj->dloc_t; h.hist_t = hj->hist_t; h.dhist = hj->dhist; h.dcum = hj->dcum;
+    h.B = hj->B; h.L = hj->L; h.F = hj->F; h.K = hj->K;
+    return 0;
+}
+
+// the K-split partial product of two batch tiles (pk_part_body) as a PkPartArgs block
+static int pk_part_fill(PkPartArgs& p, const float* packed_w, const st_t16_view* x, int K, float* part, int S, int B, int N, const char* who) {
+    ST_CHECK_ARG(packed_w && x && x->base && part && K > 0 && K % 16 == 0 && S >= 1 && (K / 16) % S == 0 && B > 16 && B <= 32 && N > 0 && N % 32 == 0 &&
+                 st_aligned16(part), "%s: needs 16 < B <= 32 (two batch tiles), N %% 32 == 0, K %% (16 S) == 0 (B=%d N=%d K=%d S=%d)", who, B, N, K, S);
+    p.w = reinterpret_cast<const f32x4*>(packed_w); p.w_kbs = K / 16;
+    p.x = reinterpret_cast<const f32x4*>(x->base) + (size_t)x->kb0 * 64; p.x_kbs = x->kb_stride;
+    p.KB = K / 16; p.S = S; p.B = B; p.N = N; p.part = part;
+    return 0;
+}
+
+extern "C" int st_skinny_linear_packed_lstm_bwd_fwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
+                                                    const st_lstm_pw_job* job, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(y && job && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_lstm_bwd_fwd: bad arguments");
+    PkArgs a;
+    int rc = pk_plain_fill(a, packed_w, x, K, y, ldy, B, N, "st_skinny_linear_packed_lstm_bwd_fwd");
+    if (rc) return rc;
+    PkPw q;
+    rc = pk_pw_fill(q, job, N, ldy, y, "st_skinny_linear_packed_lstm_bwd_fwd");
+    if (rc) return rc;
+    const int tiles = (N + 15) / 16, BT = (B + 15) >> 4;
+    // one batch tile per workgroup, as the plain linear of these shapes runs (pk_dispatch<1>)
+    hipLaunchKernelGGL((pk_pw_kernel<1, 8, 2>), dim3(tiles, BT), dim3(8 * 64), 0, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B,
+                       a.N, a, q);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
 // two st_skinny_linear_packed_lstm_bwd_fwd of the same shape in one launch (arrays of two; y2 entries may be NULL: the product is
 // only consumed by its epilogue): the two directions of a bidirectional LSTM layer's BPTT step
 extern "C" int st_skinny_linear_packed_lstm_bwd_pair_fwd(const float* const* packed_w2, const st_t16_view* x2, int K, float* const* y2, int ldy,
@@ -1751,11 +1756,8 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_pair_fwd(const float* const* pac
     PkArgs a[2];
     PkPw q[2];
     for (int d = 0; d < 2; ++d) {
-        memset(&a[d], 0, sizeof(PkArgs));
-        int rc = pk_fill(a[d], packed_w2[d], &x2[d], K, "st_skinny_linear_packed_lstm_bwd_pair_fwd");
+        int rc = pk_plain_fill(a[d], packed_w2[d], &x2[d], K, y2 ? y2[d] : nullptr, ldy, B, N, "st_skinny_linear_packed_lstm_bwd_pair_fwd");
         if (rc) return rc;
-        a[d].B = B; a[d].N = N; a[d].H = 0; a[d].act = ST_ACT_NONE;
-        a[d].y = y2 ? y2[d] : nullptr; a[d].ldy = ldy;
         rc = pk_pw_fill(q[d], &job2[d], N, ldy, a[d].y, "st_skinny_linear_packed_lstm_bwd_pair_fwd");
         if (rc) return rc;
     }
@@ -1765,40 +1767,26 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_pair_fwd(const float* const* pac
     return 0;
 }
 
-// st_skinny_linear_packed_lstm_bwd_fwd (job may be NULL: the plain product) with one attention-step backward (the arguments of
-// st_attn_step_bwd_t16 as a struct; the forward must have kept S: s_in != NULL) in the same launch
+// st_skinny_linear_packed_lstm_bwd_fwd (job may be NULL: the plain product) with one attention-step backward (st_attn_step_bwd's job;
+// the forward must have kept S: s_in != NULL) in the same launch
 extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
                                                          const st_lstm_pw_job* job, const st_attn_bwd_job* ab, void* stream) {
     (void)hipGetLastError();
     ST_CHECK_ARG(y && ab && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_lstm_bwd_attn_bwd: bad arguments");
     PkArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = pk_fill(a, packed_w, x, K, "st_skinny_linear_packed_lstm_bwd_attn_bwd");
+    int rc = pk_plain_fill(a, packed_w, x, K, y, ldy, B, N, "st_skinny_linear_packed_lstm_bwd_attn_bwd");
     if (rc) return rc;
-    a.B = B; a.N = N; a.H = 0; a.act = ST_ACT_NONE;
-    a.y = y; a.ldy = ldy;
     PkPw q;
     memset(&q, 0, sizeof(q));
     if (job) {
-        const int H = job->H;
-        ST_CHECK_ARG(H > 0 && H % 4 == 0 && job->n0 >= 0 && job->n0 % 16 == 0 && job->n0 + H <= N && (N % 16 == 0 || job->n0 + H <= (N & ~15)),
-                     "st_skinny_linear_packed_lstm_bwd_attn_bwd: the cell's columns [%d, %d) must be whole tiles of the %d outputs", job->n0, job->n0 + H, N);
-        ST_CHECK_ARG(job->gates && job->c && job->dc && job->dgates && job->ldg >= 4 * H && job->ldg % 4 == 0 && job->ldc % 4 == 0 &&
-                     (!job->c_prev || job->ldcp % 4 == 0) && (!job->dh1 || job->ld1 % 4 == 0) && (!job->dh2 || job->ld2 % 4 == 0) && ldy % 4 == 0,
-                     "st_skinny_linear_packed_lstm_bwd_attn_bwd: null operand or a row stride that is not a multiple of 4");
-        ST_CHECK_ARG(st_aligned16(job->gates) && st_aligned16(job->c) && st_aligned16(job->dc) && st_aligned16(job->dgates) && st_aligned16(y) &&
-                     (!job->c_prev || st_aligned16(job->c_prev)) && (!job->dh1 || st_aligned16(job->dh1)) && (!job->dh2 || st_aligned16(job->dh2)) &&
-                     (!job->scale2 || st_aligned16(job->scale2)) && (!job->mask || st_aligned16(job->mask)) &&
-                     (!job->dgates_t16.base || st_aligned16(job->dgates_t16.base)), "st_skinny_linear_packed_lstm_bwd_attn_bwd: operands must be 16-byte aligned");
-        q.n0 = job->n0; q.H = H; q.dh1 = job->dh1; q.ld1 = job->ld1; q.dh1_slabs = job->dh1_slabs; q.dh1_slab_stride = job->dh1_slab_stride; q.dh2 = job->dh2; q.ld2 = job->ld2; q.scale2 = job->scale2; q.mask = job->mask;
-        q.gates = job->gates; q.c = job->c; q.ldc = job->ldc; q.c_prev = job->c_prev; q.ldcp = job->ldcp; q.dc = job->dc;
-        q.dgates = job->dgates; q.ldg = job->ldg; q.dg_t16 = pk_out(&job->dgates_t16);
+        rc = pk_pw_fill(q, job, N, ldy, y, "st_skinny_linear_packed_lstm_bwd_attn_bwd");
+        if (rc) return rc;
     }      // (no job: H = 0, no column belongs to a cell -- the plain product)
     AbArgs t;
-    if (ab_fill_job(t, ab)) return -1;
+    if (ab_fill(t, ab)) return -1;
     ST_CHECK_ARG(t.s_in, "st_skinny_linear_packed_lstm_bwd_attn_bwd: the hosted attention backward starts from the forward's S (s_in)");
-    // the launch (AbPlan, attention_bwd_body.h): parts > 1 is the split form (see pk_pw_ab_kernel); the caller then runs
-    // st_skinny_linear_packed_lstm_bwd_attn_hist next
+    // the launch (AbPlan, attention_bwd_body.h): parts > 1 is the split form (see pk_pw_ab_kernel); the caller then runs the history job
+    // beside a later product of the step (st_skinny_linear_packed_attn_hist, st_skinny_linear_packed_lstm_bwd_attn_hist_sum)
     const AbPlan pl = ab_plan(t.L, t.A, t.E, t.F, t.K, true, ab->parts, 1, t.B, B, N, st_aligned16(t.loc_lin_w));
     const int parts = pl.parts;
     const size_t lds = pl.lds;
@@ -1816,10 +1804,9 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
         else rc = st_skinny_linear_packed_fwd(packed_w, x, K, nullptr, ST_ACT_NONE, nullptr, 0, y, ldy, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0,
                                               nullptr, B, N, stream);
         if (rc) return rc;
-        return st_attn_step_bwd_t16(ab->pq, ab->pm, ab->memory, ab->w_prev, ab->ld_wprev, ab->w_cum_prev, ab->w, ab->ld_w, ab->loc_conv_w,
-                                    ab->loc_lin_w, ab->v, t.dctx, t.ld_dctx, AB_NDCTX, ab->dw_direct, ab->ld_dw, ab->n_dw, ab->dcum,
-                                    ab->dcum_add, ab->ld_dcum_add, ab->dpq, &ab->dpq_t16, ab->dhist, ab->ds_t, ab->loc_t, ab->dloc_t,
-                                    ab->hist_t, ab->dctx_t, ab->dv_t, ab->s_in, ab->B, ab->L, ab->A, ab->E, ab->F, ab->K, stream);
+        st_attn_bwd_job whole = *ab;        // (the two-launch fallback has always run the whole step per workgroup: ab->parts is ignored)
+        whole.parts = 0; whole.dloc_part = nullptr;
+        return st_attn_step_bwd(&whole, stream);
     }
     const int tiles = (N + 15) / 16, BT = (B + 15) >> 4;
     if (pl.kernel == AB_K_NB2) {
@@ -1863,32 +1850,6 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
     return 0;
 }
 
-// st_skinny_linear_packed_lstm_bwd_fwd with the history part of a split attention backward (st_attn_hist_job) in the same launch
-static int pk_hist_sum_impl(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                            const st_lstm_pw_job* job, const st_attn_hist_job* hj, const st_partial_sum_job* sj, void* stream);
-
-extern "C" int st_skinny_linear_packed_lstm_bwd_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                          const st_lstm_pw_job* job, const st_attn_hist_job* hj, void* stream) {
-    ST_CHECK_ARG(job && hj, "st_skinny_linear_packed_lstm_bwd_attn_hist: null job");
-    return pk_hist_sum_impl(packed_w, x, K, y, ldy, B, N, job, hj, nullptr, stream);
-}
-
-// ... and with the sum of a K-split partial product (st_partial_sum_job: the slabs st_skinny_partial_attn_bwd wrote in the launch before);
-// hj may be NULL here (the history part can ride in another launch: st_skinny_linear_packed_attn_hist)
-extern "C" int st_skinny_linear_packed_lstm_bwd_attn_hist_sum(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                              const st_lstm_pw_job* job, const st_attn_hist_job* hj,
-                                                              const st_partial_sum_job* sj, void* stream) {
-    ST_CHECK_ARG(job && sj, "st_skinny_linear_packed_lstm_bwd_attn_hist_sum: null job");
-    return pk_hist_sum_impl(packed_w, x, K, y, ldy, B, N, job, hj, sj, stream);
-}
-
-// the plain product y = x W^T (st_skinny_linear_packed_fwd without epilogue) with an st_attn_hist_job beside it
-extern "C" int st_skinny_linear_packed_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                 const st_attn_hist_job* hj, void* stream) {
-    ST_CHECK_ARG(hj, "st_skinny_linear_packed_attn_hist: null history job");
-    return pk_hist_sum_impl(packed_w, x, K, y, ldy, B, N, nullptr, hj, nullptr, stream);
-}
-
 static int pk_sum_fill(PkSumArgs& sa, const st_partial_sum_job* sj, int B, const char* who) {
     memset(&sa, 0, sizeof(sa));
     ST_CHECK_ARG(sj->part && sj->S >= 1 && sj->N > 0 && sj->N % 4 == 0 && sj->y && sj->ldy >= sj->N && sj->ldy % 4 == 0 && st_aligned16(sj->part) &&
@@ -1901,32 +1862,27 @@ static int pk_sum_fill(PkSumArgs& sa, const st_partial_sum_job* sj, int B, const
     return 0;
 }
 
+// a product (with the pointwise LSTM backward of `job` in its epilogue, or plain) with the history part of a split attention backward
+// (st_attn_hist_job) and / or the sum of a K-split partial product (st_partial_sum_job) in the same launch
 static int pk_hist_sum_impl(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
                             const st_lstm_pw_job* job, const st_attn_hist_job* hj, const st_partial_sum_job* sj, void* stream) {
     (void)hipGetLastError();
     ST_CHECK_ARG(y && (hj || sj) && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_*_attn_hist: bad arguments");
     PkArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = pk_fill(a, packed_w, x, K, "st_skinny_linear_packed_*_attn_hist");
+    int rc = pk_plain_fill(a, packed_w, x, K, y, ldy, B, N, "st_skinny_linear_packed_*_attn_hist");
     if (rc) return rc;
-    a.B = B; a.N = N; a.H = 0; a.act = ST_ACT_NONE;
-    a.y = y; a.ldy = ldy;
     PkPw q;
     memset(&q, 0, sizeof(q));
     if (job) {
-        rc = pk_pw_fill(q, job, N, ldy, y, "st_skinny_linear_packed_lstm_bwd_attn_hist");
+        rc = pk_pw_fill(q, job, N, ldy, y, "st_skinny_linear_packed_lstm_bwd_attn_hist_sum");
         if (rc) return rc;
     }
     AbHistArgs h;
     memset(&h, 0, sizeof(h));
     size_t lds = 0;
     if (hj) {
-        ST_CHECK_ARG(hj->dloc_part && hj->parts >= 1 && hj->parts <= 4 && hj->loc_conv_w && hj->w_cum_prev && hj->dloc_t && hj->hist_t && hj->dhist &&
-                     hj->B > 0 && hj->L > 0 && hj->F > 0 && hj->K > 0 && (hj->K & 1) && hj->K <= 31,
-                     "st_skinny_linear_packed_*_attn_hist: bad history job (odd K <= 31)");
-        h.dloc_part = hj->dloc_part; h.parts = hj->parts; h.loc_conv_w = hj->loc_conv_w; h.w_prev = hj->w_prev; h.ld_wprev = hj->ld_wprev;
-        h.w_cum_prev = hj->w_cum_prev; h.dloc_t = hj->dloc_t; h.hist_t = hj->hist_t; h.dhist = hj->dhist; h.dcum = hj->dcum;
-        h.B = hj->B; h.L = hj->L; h.F = hj->F; h.K = hj->K;
+        rc = pk_hist_fill(h, hj, "st_skinny_linear_packed_*_attn_hist");
+        if (rc) return rc;
         lds = (size_t)ab_hist_lds_floats(h.L, h.F, h.K) * sizeof(float);
     }
     const size_t red_bytes = (size_t)8 * 1 * 64 * sizeof(f32x4);
@@ -1954,23 +1910,32 @@ static int pk_hist_sum_impl(const float* packed_w, const st_t16_view* x, int K, 
     return 0;
 }
 
+// st_skinny_linear_packed_lstm_bwd_fwd with the sum of a K-split partial product (st_partial_sum_job: the slabs st_skinny_partial_attn_bwd
+// wrote in the launch before) and the history part of a split attention backward; hj may be NULL (it can ride in another launch:
+// st_skinny_linear_packed_attn_hist)
+extern "C" int st_skinny_linear_packed_lstm_bwd_attn_hist_sum(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
+                                                              const st_lstm_pw_job* job, const st_attn_hist_job* hj,
+                                                              const st_partial_sum_job* sj, void* stream) {
+    ST_CHECK_ARG(job && sj, "st_skinny_linear_packed_lstm_bwd_attn_hist_sum: null job");
+    return pk_hist_sum_impl(packed_w, x, K, y, ldy, B, N, job, hj, sj, stream);
+}
+
+// the plain product y = x W^T (st_skinny_linear_packed_fwd without epilogue) with an st_attn_hist_job beside it
+extern "C" int st_skinny_linear_packed_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
+                                                 const st_attn_hist_job* hj, void* stream) {
+    ST_CHECK_ARG(hj, "st_skinny_linear_packed_attn_hist: null history job");
+    return pk_hist_sum_impl(packed_w, x, K, y, ldy, B, N, nullptr, hj, nullptr, stream);
+}
+
 // st_skinny_partial_attn_bwd's product with an st_attn_hist_job beside it instead of the attention backward
 extern "C" int st_skinny_partial_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* part, int S, int B, int N,
                                            const st_attn_hist_job* hj, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(packed_w && x && x->base && part && hj && K > 0 && K % 16 == 0 && S >= 1 && (K / 16) % S == 0 && B > 16 && B <= 32 && N > 0 && N % 32 == 0 &&
-                 st_aligned16(part), "st_skinny_partial_attn_hist: needs 16 < B <= 32 (two batch tiles), N %% 32 == 0, K %% (16 S) == 0 (B=%d N=%d K=%d S=%d)", B, N, K, S);
-    ST_CHECK_ARG(hj->dloc_part && hj->parts >= 1 && hj->parts <= 4 && hj->loc_conv_w && hj->w_cum_prev && hj->dloc_t && hj->hist_t && hj->dhist &&
-                 hj->B > 0 && hj->L > 0 && hj->F > 0 && hj->K > 0 && (hj->K & 1) && hj->K <= 31, "st_skinny_partial_attn_hist: bad history job (odd K <= 31)");
+    ST_CHECK_ARG(hj, "st_skinny_partial_attn_hist: null history job");
     PkPartArgs p;
-    p.w = reinterpret_cast<const f32x4*>(packed_w); p.w_kbs = K / 16;
-    p.x = reinterpret_cast<const f32x4*>(x->base) + (size_t)x->kb0 * 64; p.x_kbs = x->kb_stride;
-    p.KB = K / 16; p.S = S; p.B = B; p.N = N; p.part = part;
+    if (pk_part_fill(p, packed_w, x, K, part, S, B, N, "st_skinny_partial_attn_hist")) return -1;
     AbHistArgs h;
-    memset(&h, 0, sizeof(h));
-    h.dloc_part = hj->dloc_part; h.parts = hj->parts; h.loc_conv_w = hj->loc_conv_w; h.w_prev = hj->w_prev; h.ld_wprev = hj->ld_wprev;
-    h.w_cum_prev = hj->w_cum_prev; h.dloc_t = hj->dloc_t; h.hist_t = hj->hist_t; h.dhist = hj->dhist; h.dcum = hj->dcum;
-    h.B = hj->B; h.L = hj->L; h.F = hj->F; h.K = hj->K;
+    if (pk_hist_fill(h, hj, "st_skinny_partial_attn_hist")) return -1;
     const size_t lds = (size_t)ab_hist_lds_floats(h.L, h.F, h.K) * sizeof(float);
     ST_CHECK_ARG(lds + 8 * 4 * 64 * sizeof(f32x4) <= 160 * 1024, "st_skinny_partial_attn_hist: L=%d needs %zu bytes of LDS", h.L, lds);
     auto kern = pk_part_hist_kernel<8, 2>;
@@ -1990,12 +1955,8 @@ extern "C" int st_skinny_partial_attn_hist(const float* packed_w, const st_t16_v
 extern "C" int st_skinny_partial_attn_bwd(const float* packed_w, const st_t16_view* x, int K, float* part, int S, int B, int N,
                                           const st_attn_bwd_job* ab, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(packed_w && x && x->base && part && K > 0 && K % 16 == 0 && S >= 1 && (K / 16) % S == 0 && B > 16 && B <= 32 && N > 0 && N % 32 == 0 &&
-                 st_aligned16(part), "st_skinny_partial_attn_bwd: needs 16 < B <= 32 (two batch tiles), N %% 32 == 0, K %% (16 S) == 0 (B=%d N=%d K=%d S=%d)", B, N, K, S);
     PkPartArgs p;
-    p.w = reinterpret_cast<const f32x4*>(packed_w); p.w_kbs = K / 16;
-    p.x = reinterpret_cast<const f32x4*>(x->base) + (size_t)x->kb0 * 64; p.x_kbs = x->kb_stride;
-    p.KB = K / 16; p.S = S; p.B = B; p.N = N; p.part = part;
+    if (pk_part_fill(p, packed_w, x, K, part, S, B, N, "st_skinny_partial_attn_bwd")) return -1;
     const int n_prod = (N / 32) * S;
     if (!ab) {
         hipLaunchKernelGGL((pk_part_kernel<8, 2>), dim3(n_prod), dim3(8 * 64), 0, (hipStream_t)stream, p);
@@ -2003,7 +1964,7 @@ extern "C" int st_skinny_partial_attn_bwd(const float* packed_w, const st_t16_vi
         return 0;
     }
     AbArgs t;
-    if (ab_fill_job(t, ab)) return -1;
+    if (ab_fill(t, ab)) return -1;
     const AbPlan pl = ab_plan(t.L, t.A, t.E, t.F, t.K, t.s_in != nullptr, ab->parts, 2, t.B, B, N, st_aligned16(t.loc_lin_w));
     ST_CHECK_ARG(ab->dloc_part && !ab->dcum_add && pl.code >= 0, "st_skinny_partial_attn_bwd: the attention job must be the two-part form (parts = 2, dloc_part, S kept, "
                  "no dcum_add) with A = %d splitting into halves that divide %d", t.A, AB_THREADS);

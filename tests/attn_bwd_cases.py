@@ -3,8 +3,8 @@
 it) and the GPU test (test_gpu_attn_bwd.py: every runnable step row and every loop form against a float64 reference).
 
 A step row: B utterances of L positions, A attention dims, E context dims, F location filters, K taps;
-  s      -- the forward's S is given (st_attn_step_bwd_s; without it the kernel recomputes S from pm and the location conv);
-  hosted -- 0 st_attn_step_bwd[_s|_t16], 1 st_skinny_linear_packed_lstm_bwd_attn_bwd beside a product of N outputs, 2 st_skinny_partial_attn_bwd;
+  s      -- the forward's S is given (st_attn_bwd_job.s_in; without it the kernel recomputes S from pm and the location conv);
+  hosted -- 0 st_attn_step_bwd, 1 st_skinny_linear_packed_lstm_bwd_attn_bwd beside a product of N outputs, 2 st_skinny_partial_attn_bwd;
   parts  -- attention workgroups per utterance (hosted only);  wl -- 'al' a 16-byte aligned W_l, 'off1' one float past a boundary;
   env    -- environment switches of the hosted launches;  gpu -- the GPU test runs the row (the refusals and the longest texts it does not);
   want   -- the launch (step_name()) or the refusal (REFUSALS) st_attn_bwd_variant reports."""

@@ -206,37 +206,50 @@ def P(t):
     return None if t is None else (t if isinstance(t, int) else t.data_ptr())
 
 
+def fill_job(c, di, o, t16v=None, s_in=None, loc_t=None):
+    """the StAttnBwdJob of one step from the device inputs `di` and the output views `o`: the first three context addends in dctx, the rest
+    in dctx_more (the slabs of a K-split product)"""
+    from semi_tts_amd import _lib
+    j = _lib.StAttnBwdJob()
+    j.pq, j.pm, j.memory = P(di['pq']), P(di['pm']), P(di['memory'])
+    j.w_prev, j.ld_wprev, j.w_cum_prev, j.w, j.ld_w = P(di['w_prev']), di['ld_wprev'], P(di['cum_prev']), P(di['w']), di['ld_w']
+    j.loc_conv_w, j.loc_lin_w, j.v = P(di['Wc']), di['Wl_p'], P(di['v'])
+    for q, (t, ld) in enumerate(di['dctx']):
+        if q < 3:
+            j.dctx[q], j.ld_dctx[q] = P(t), ld
+        else:
+            j.dctx_more[q - 3], j.ld_dctx_more[q - 3] = P(t), ld
+    j.n_dctx, j.n_dctx_more = min(len(di['dctx']), 3), max(len(di['dctx']) - 3, 0)
+    for q, (t, ld) in enumerate(di['dw']):
+        j.dw_direct[q], j.ld_dw[q] = P(t), ld
+    j.n_dw = len(di['dw'])
+    j.dcum, j.dcum_add, j.ld_dcum_add = P(di['dcum']), P(di['dcum_add']), di['ld_dcum_add']
+    j.dpq, j.dhist, j.ds_t, j.loc_t = P(o['dpq']), P(o['dhist']), P(o['ds']), P(loc_t)
+    if t16v is not None:
+        j.dpq_t16 = t16v
+    j.dloc_t, j.hist_t, j.dctx_t, j.dv_t, j.s_in = P(o['dloc']), P(o['hist_t']), P(o['dctx']), P(o['dv']), P(s_in)
+    j.B, j.L, j.A, j.E, j.F, j.K = c['B'], c['L'], c['A'], c['E'], c['F'], c['K']
+    return j
+
+
 def run_plain(c, x, dev, entry='t16'):
-    """st_attn_step_bwd_t16 (S given) / st_attn_step_bwd_s / st_attn_step_bwd (recomputes S); returns outputs (CPU)"""
+    """st_attn_step_bwd with the T16 copy of dpq and S per the row ('t16'), with S given and no T16 copy ('s'), or with neither ('plain':
+    S is recomputed); returns outputs (CPU)"""
     from semi_tts_amd import _lib, ops
     lib = _lib.load()
     bufs = Bufs(dev)
     di = dev_inputs(x, c, dev, bufs)
     t16v = out_bufs(c, bufs)
     o = {k: bufs.view(k) for k in ('dpq', 'dhist', 'ds', 'loc', 'dloc', 'hist_t', 'dctx', 'dv')}
-    nd, nw = len(di['dctx']), len(di['dw'])
-    dctx = (C.c_void_p * 6)(*([P(t) for t, _ in di['dctx']] + [None] * (6 - nd)))
-    ldc = (C.c_int * 6)(*([ld for _, ld in di['dctx']] + [0] * (6 - nd)))
-    dw = (C.c_void_p * 3)(*([P(t) for t, _ in di['dw']] + [None] * (3 - nw)))
-    ldw = (C.c_int * 3)(*([ld for _, ld in di['dw']] + [0] * (3 - nw)))
-    B, L, A, E, F, K = c['B'], c['L'], c['A'], c['E'], c['F'], c['K']
-    head = [P(di['pq']), P(di['pm']), P(di['memory']), P(di['w_prev']), di['ld_wprev'], P(di['cum_prev']), P(di['w']), di['ld_w'],
-            P(di['Wc']), di['Wl_p'], P(di['v']), dctx, ldc, nd, dw, ldw, nw, P(di['dcum']), P(di['dcum_add']), di['ld_dcum_add']]
-    tail = [P(o['dhist']), P(o['ds']), P(o['loc']), P(o['dloc']), P(o['hist_t']), P(o['dctx']), P(o['dv'])]
-    dims = [B, L, A, E, F, K, ops.stream_handle()]
-    if entry == 't16':
-        rc = lib.st_attn_step_bwd_t16(*head, P(o['dpq']), C.byref(t16v), *tail, P(di['S']) if c['s'] else None, *dims)
-    elif entry == 's':
-        rc = lib.st_attn_step_bwd_s(*head, P(o['dpq']), *tail, P(di['S']), *dims)
-    else:
-        rc = lib.st_attn_step_bwd(*head, P(o['dpq']), *tail, *dims)
-    _lib.check(rc, 'st_attn_step_bwd')
+    s_in = di['S'] if (entry == 's' or (entry == 't16' and c['s'])) else None
+    j = fill_job(c, di, o, t16v if entry == 't16' else None, s_in, o['loc'])
+    _lib.check(lib.st_attn_step_bwd(C.byref(j), ops.stream_handle()), 'st_attn_step_bwd')
     torch.cuda.synchronize()
     bufs.guards_intact()
     res = {k: v.cpu() for k, v in o.items()}
     res['dcum'] = di['dcum'].cpu()
     if entry == 't16':
-        res['dpq_t16'] = ops.untile_rows(bufs.outs['dpq_t16'][0], B, A).cpu()
+        res['dpq_t16'] = ops.untile_rows(bufs.outs['dpq_t16'][0], c['B'], c['A']).cpu()
     return res
 
 
@@ -294,7 +307,7 @@ def test_step_against_float64(dev, c, monkeypatch):
 
 @pytest.mark.parametrize('L', [17, 49, 97])
 def test_given_s_and_recomputed_s_agree(dev, L):
-    """st_attn_step_bwd_s (the forward's S) and st_attn_step_bwd (S recomputed from pm and the location conv): each within its bound of
+    """st_attn_step_bwd with the forward's S (s_in) and with S recomputed from pm and the location conv: each within its bound of
     the float64 reference, so within the sum of the bounds of each other"""
     c = T.S('x', L, B=3)
     x = make_step(c, seed=7)
@@ -330,6 +343,28 @@ def test_context_and_weight_addends(dev, n_dctx, n_dw, dcum_add, t0):
         assert torch.equal(g1['dctx'], got['dctx'])
 
 
+def test_plain_entry_refuses_parts(dev):
+    """the split forms exist only hosted: st_attn_step_bwd with parts = 2 (and a dloc_part buffer) is an argument error before any launch --
+    the message names `parts` and every output still holds its sentinel"""
+    from semi_tts_amd import _lib, ops
+    lib = _lib.load()
+    c = T.S('x', 43, B=4)
+    x = make_step(c, seed=31)
+    bufs = Bufs(dev)
+    di = dev_inputs(x, c, dev, bufs)
+    t16v = out_bufs(c, bufs, parts=2)
+    o = {k: bufs.view(k) for k in ('dpq', 'dhist', 'ds', 'loc', 'dloc', 'hist_t', 'dctx', 'dv')}
+    j = fill_job(c, di, o, t16v, di['S'], o['loc'])
+    j.parts, j.dloc_part = 2, P(bufs.view('dloc_part'))
+    dcum0 = di['dcum'].clone()
+    with pytest.raises(RuntimeError, match='parts'):
+        _lib.check(lib.st_attn_step_bwd(C.byref(j), ops.stream_handle()), 'st_attn_step_bwd')
+    torch.cuda.synchronize()
+    for k, (t, _) in bufs.outs.items():
+        assert bool((t == SENT).all()), k + ' was written'
+    assert torch.equal(di['dcum'], dcum0)
+
+
 # ------------------------------------------------------------------------------------------------ hosted forms
 def run_hosted(c, x, dev):
     """the hosted launch (beside a product y = xp W^T of N outputs, or the K-split partial product) and, for parts > 1, the history job in
@@ -350,23 +385,7 @@ def run_hosted(c, x, dev):
     di = dev_inputs(x, c, dev, bufs)
     t16v = out_bufs(c, bufs, parts)
     o = {k: bufs.view(k) for k in ('dpq', 'dhist', 'ds', 'loc', 'dloc', 'hist_t', 'dctx', 'dv')}
-    j = _lib.StAttnBwdJob()
-    j.pq, j.pm, j.memory = P(di['pq']), P(di['pm']), P(di['memory'])
-    j.w_prev, j.ld_wprev, j.w_cum_prev, j.w, j.ld_w = P(di['w_prev']), di['ld_wprev'], P(di['cum_prev']), P(di['w']), di['ld_w']
-    j.loc_conv_w, j.loc_lin_w, j.v = P(di['Wc']), di['Wl_p'], P(di['v'])
-    for q, (t, ld) in enumerate(di['dctx']):       # three addends, then the rest as dctx_more (the slabs of a K-split product)
-        if q < 3:
-            j.dctx[q], j.ld_dctx[q] = P(t), ld
-        else:
-            j.dctx_more[q - 3], j.ld_dctx_more[q - 3] = P(t), ld
-    j.n_dctx, j.n_dctx_more = min(len(di['dctx']), 3), max(len(di['dctx']) - 3, 0)
-    for q, (t, ld) in enumerate(di['dw']):
-        j.dw_direct[q], j.ld_dw[q] = P(t), ld
-    j.n_dw = len(di['dw'])
-    j.dcum, j.dcum_add, j.ld_dcum_add = P(di['dcum']), P(di['dcum_add']), di['ld_dcum_add']
-    j.dpq, j.dpq_t16, j.dhist, j.ds_t, j.loc_t = P(o['dpq']), t16v, P(o['dhist']), P(o['ds']), None
-    j.dloc_t, j.hist_t, j.dctx_t, j.dv_t, j.s_in = P(o['dloc']), P(o['hist_t']), P(o['dctx']), P(o['dv']), P(di['S'])
-    j.B, j.L, j.A, j.E, j.F, j.K = B, L, A, E, F, K
+    j = fill_job(c, di, o, t16v, di['S'])
     if parts > 1:
         j.parts, j.dloc_part = parts, P(bufs.view('dloc_part'))
     prod = {}

@@ -34,18 +34,25 @@ int main() {
     float* dpq = dalloc((size_t)B * A, 0), *dhist = dalloc((size_t)B * 2 * L, 0);
     float* ds = dalloc((size_t)B * L * A, 0), *loc = dalloc((size_t)B * L * F, 0), *dloc = dalloc((size_t)B * L * F, 0);
     float* hist = dalloc((size_t)B * L * 2, 0), *dctx = dalloc((size_t)B * E, 0), *dv = dalloc((size_t)B * A, 0);
-    const float* dctxs[3] = {d0, d1, d2}; const int ldc[3] = {E, E, E};
-    const float* dws[1] = {dwa}; const int ldw[1] = {2 * L};
-    const bool has_s = getenv("MB_S") != nullptr;      // S of the step given (training keeps it): no conv / W_l recompute
-    auto run = [&] { int rc = st_attn_step_bwd_s(pq, pm, mem, wprev, L, wcum, w, L, wc, wl, v, dctxs, ldc, 3, dws, ldw, 1, dcum, dwa + L, 2 * L,
-                                                dpq, dhist, ds, loc, dloc, hist, dctx, dv, has_s ? pm : nullptr, B, L, A, E, F, K, nullptr);
+    // the step as st_attn_step_bwd takes it (three context addends, one weight addend, dcum_add = the second half of dwa's rows)
+    st_attn_bwd_job job = {};
+    job.pq = pq; job.pm = pm; job.memory = mem; job.w_prev = wprev; job.ld_wprev = L; job.w_cum_prev = wcum; job.w = w; job.ld_w = L;
+    job.loc_conv_w = wc; job.loc_lin_w = wl; job.v = v;
+    job.dctx[0] = d0; job.dctx[1] = d1; job.dctx[2] = d2; job.ld_dctx[0] = job.ld_dctx[1] = job.ld_dctx[2] = E; job.n_dctx = 3;
+    job.dw_direct[0] = dwa; job.ld_dw[0] = 2 * L; job.n_dw = 1;
+    job.dcum = dcum; job.dcum_add = dwa + L; job.ld_dcum_add = 2 * L;
+    job.dpq = dpq; job.dhist = dhist; job.ds_t = ds; job.loc_t = loc; job.dloc_t = dloc; job.hist_t = hist; job.dctx_t = dctx; job.dv_t = dv;
+    job.B = B; job.L = L; job.A = A; job.E = E; job.F = F; job.K = K;
+    job.s_in = getenv("MB_S") ? pm : nullptr;          // S of the step given (training keeps it): no conv / W_l recompute
+    auto run = [&] { int rc = st_attn_step_bwd(&job, nullptr);
         if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
     const int ns = getenv("MB_NS") ? atoi(getenv("MB_NS")) : 1;
     float* dloc_part = dalloc((size_t)4 * B * L * F, 0);
     auto run_split = [&] {
+        st_attn_bwd_job sj = job;        // (the split form: S given, dcum holds the total gradient w.r.t. cum_t)
+        sj.s_in = pm; sj.dcum_add = nullptr; sj.ld_dcum_add = 0;
         AbArgs a;
-        if (ab_fill(a, nullptr, pq, pm, mem, wprev, L, wcum, w, L, wc, wl, v, dctxs, ldc, 3, dws, ldw, 1, dcum, nullptr, 0, dpq, dhist, ds, loc, dloc, hist, dctx, dv,
-                    pm, B, L, A, E, F, K)) { printf("%s\n", st_last_error()); exit(1); }
+        if (ab_fill(a, &sj)) { printf("%s\n", st_last_error()); exit(1); }
         a.dloc_part = dloc_part;
         const size_t lds = ab_lds_bytes(a, true, ns);
         if (ns == 2) { CK(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
