@@ -134,24 +134,6 @@ int st_untile_rows(const st_t16_view* src, float* dst, int ld, int B, int K, voi
  * state goes to up to two T16 destinations; optionally also the AdaIN-adapted hidden state
  * hadapt = ada_std * (h_out - ada_mean)  (ada_* natural (B,H)).
  * ref: as st_lstm_cell_fwd, AdaIN src/module.py:268-269 */
-int st_lstm_cell_packed_fwd(const float* packed_w, const st_t16_view* x, int K,
-                            const float* b_ih, const float* b_hh,
-                            const float* c_prev, int ldc_prev, const float* mask,
-                            const st_t16_view* h_dst0, const st_t16_view* h_dst1,
-                            float* c_out, int ldc, float* gates_out,
-                            const float* ada_std, const float* ada_mean, const st_t16_view* hadapt_dst,
-                            int B, int H, void* stream);
-/* st_lstm_cell_packed_fwd (without AdaIN) over the LEADING K columns of a cell whose packed matrix has w_kbs k-blocks per row tile; the gate
- * products over the remaining columns come as `part` (B, 4H), written by an st_partial_product_job of an earlier launch, and are added to
- * the reduced gates.  16 < B <= 32, H / 4 even.  ref: nn.LSTMCell, src/module.py:275-280 */
-int st_lstm_cell_packed_part_fwd(const float* packed_w, int w_kbs, const st_t16_view* x, int K, const float* part,
-                                 const float* b_ih, const float* b_hh,
-                                 const float* c_prev, int ldc_prev, const float* mask,
-                                 const st_t16_view* h_dst0, const st_t16_view* h_dst1,
-                                 float* c_out, int ldc, float* gates_out, int B, int H, void* stream);
-/* The arguments of st_lstm_cell_packed_fwd as a struct, and two independent cells in ONE launch: under teacher forcing the decoder
- * cell of step t and the query cell of step t+1 both only wait for the attention of step t (src/module.py:216-288 with a teacher
- * frame as the next input).  Falls back to one launch per cell for shapes the 2-D tiled kernel does not take. */
 typedef struct st_lstm_cell_packed_job {
     const float* packed_w; st_t16_view x; int K;
     const float* b_ih; const float* b_hh;
@@ -160,9 +142,15 @@ typedef struct st_lstm_cell_packed_job {
     float* c_out; int ldc; float* gates_out;
     const float* ada_std; const float* ada_mean; st_t16_view hadapt_dst;   /* hadapt_dst.base may be NULL */
     int B, H;
-    const float* part; int w_kbs;   /* optional (as st_lstm_cell_packed_part_fwd): K covers the LEADING k-blocks of a matrix packed with w_kbs
-                                     * k-blocks per tile; the gate products over the others arrive as the (B, 4 H) slab `part` */
+    const float* part; int w_kbs;   /* optional: K covers the LEADING k-blocks of a matrix packed with w_kbs k-blocks per row tile; the gate
+                                     * products over the others arrive as the (B, 4 H) slab `part`, written by an st_partial_product_job of an
+                                     * earlier launch, and are added to the reduced gates.  16 < B <= 32, H / 4 even.  NULL: the whole cell.
+                                     * ref: nn.LSTMCell, src/module.py:275-280 */
 } st_lstm_cell_packed_job;
+int st_lstm_cell_packed_fwd(const st_lstm_cell_packed_job* job, void* stream);
+/* Two independent cells in ONE launch: under teacher forcing the decoder cell of step t and the query cell of step t+1 both only wait
+ * for the attention of step t (src/module.py:216-288 with a teacher frame as the next input).  Falls back to one launch per cell for
+ * shapes the 2-D tiled kernel does not take. */
 int st_lstm_cell_packed_pair_fwd(const st_lstm_cell_packed_job* j0, const st_lstm_cell_packed_job* j1, void* stream);
 /* st_skinny_linear_fwd on packed operands; output natural (y) and/or T16 (y_dst).
  * Optional third row range [n_split2, N): v = act2(v) * mask2(b, n - n_split2) -> y3_dst column
@@ -184,36 +172,23 @@ int st_skinny_linear_packed_fwd(const float* packed_w, const st_t16_view* x, int
  *   ctx   = sum_l w_l memory_l                  -> ctx (B,E)
  *   if h_q != NULL: h_adapt = ada_std * (h_q - ada_mean)                          (B,Q)
  * pq (B,A) = query_layer(h_q) is produced by st_skinny_linear_fwd. */
-int st_attn_step_fwd(const float* pq, const float* pm, const float* memory,
-                     const float* w_prev, int ld_wprev, const float* w_cum_prev,
-                     float* w_out, int ld_wout, float* w_cum_out,
-                     const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                     float* ctx, int ld_ctx,
-                     const float* h_q, int ld_hq, const float* ada_std, const float* ada_mean,
-                     float* h_adapt, int Q,
-                     int B, int L, int A, int E, int F, int K, void* stream);
-/* same step with the context written to up to 3 T16 destinations (and optionally natural); no
- * AdaIN (the decode loop fuses it into the query LSTM epilogue) */
-int st_attn_step_t16_fwd(const float* pq, const float* pm, const float* memory,
-                         const float* w_prev, int ld_wprev, const float* w_cum_prev,
-                         float* w_out, int ld_wout, float* w_cum_out,
-                         const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                         const st_t16_view* ctx_dst, int n_ctx_dst, float* ctx, int ld_ctx,
-                         int B, int L, int A, int E, int F, int K, void* stream);
+typedef struct st_attn_step_job {
+    const float* pq; const float* pm; const float* memory;
+    const float* w_prev; int ld_wprev; const float* w_cum_prev;
+    float* w_out; int ld_wout; float* w_cum_out;
+    const float* loc_conv_w; const float* loc_lin_w; const float* v;
+    st_t16_view ctx_dst[3]; int n_ctx_dst;   /* the context goes to up to 3 T16 destinations (the decode loop) ... */
+    float* ctx; int ld_ctx;                  /* ... and / or to a natural (B, E) one */
+    const float* h_q; int ld_hq; const float* ada_std; const float* ada_mean; float* h_adapt; int Q;   /* optional AdaIN; not together
+                                              * with T16 destinations (the decode loop fuses it into the query LSTM epilogue) */
+    int L, A, E, F, K;
+} st_attn_step_job;
+int st_attn_step_fwd(const st_attn_step_job* job, int B, void* stream);
 /* The same step in two launches.  `pre` only needs the PREVIOUS step's attention weights: location conv and
  * S(b,l,:) = pm(b,l,:) + W_l conv([w_prev; w_cum_prev])(l) -> s_buf (B,L,A); it can run while the rest of the decode step
  * does (st_skinny_linear_packed_attnpre_fwd runs it as extra workgroups of the proj launch).  `fin` = energies
  * v . tanh(pq + S), softmax, cumulative weights, context.  (pq + W_l cf) + pm becomes pq + (pm + W_l cf): fp32
- * re-association only. */
-int st_attn_pre_fwd(const float* pm, const float* w_prev, int ld_wprev, const float* w_cum_prev,
-                    const float* loc_conv_w, const float* loc_lin_w, float* s_buf, int parts,
-                    int B, int L, int A, int F, int K, void* stream);   /* parts = workgroups per utterance: 1, 2 or 4 */
-int st_attn_fin_t16_fwd(const float* pq, const float* s_buf, const float* memory, const float* w_cum_prev,
-                        float* w_out, int ld_wout, float* w_cum_out, const float* v,
-                        const st_t16_view* ctx_dst, int n_ctx_dst, float* ctx, int ld_ctx, int parts,
-                        int B, int L, int A, int E, int F, int K, void* stream);
-/* (parts = workgroups per utterance of the fin part: each takes E/parts context dims and repeats the energies + softmax;
- *  1, 2, 4 or 8 with E % (4*parts) == 0) */
+ * re-association only.  Both take their job struct, declared below: st_attn_pre_job, st_attn_fin_job. */
 /* st_skinny_linear_packed_fwd plus, as extra workgroups of the same launch (one per utterance), st_attn_pre_fwd for the NEXT
  * decode step: the proj (+) gate launch of step t leaves most compute units idle and the attention weights of step t are
  * already known, so S of step t+1 is ready when its attention launch starts. */
@@ -229,6 +204,7 @@ typedef struct st_attn_pre_job {
      * launch then has N / 16 x 2 + B x parts + job->N / 32 workgroups) */
     const struct st_partial_product_job* part;
 } st_attn_pre_job;
+int st_attn_pre_fwd(const st_attn_pre_job* job, int B, void* stream);   /* the pre part as a launch of its own: no cf_out, no part */
 int st_skinny_linear_packed_attnpre_fwd(const float* packed_w, const st_t16_view* x, int K,
                                         const float* bias, int act, const float* mask, int ldmask,
                                         float* y, int ldy, const st_t16_view* y_dst,
@@ -259,30 +235,30 @@ int st_skinny_linear_packed_lstm_bwd_fwd(const float* packed_w, const st_t16_vie
 
 /* The fin part for LONG texts: every utterance split over `parts` (2..64) ranges of positions -- local softmax statistics and an
  * un-normalised partial context per range (flash-decoding style), then a combine launch.  S and the memory rows are read once in
- * total; st_attn_fin_t16_fwd re-reads S in each of its context slices and one compute unit has to pull ~2 L A 4 bytes (12 us at
- * L = 171).  Same arithmetic as softmax(e) @ memory up to fp32 rounding (~1e-7).  workspace: B * parts * (4 + E) floats. */
+ * total; st_attn_fin_fwd re-reads S in each of its context slices and one compute unit has to pull ~2 L A 4 bytes (12 us at
+ * L = 171).  Same arithmetic as softmax(e) @ memory up to fp32 rounding (~1e-7).  workspace: B * parts * (4 + E) floats.
+ * (st_attn_fin_split_fwd, declared with the fin job below: job->parts = 2..64; F, K and status are unused there) */
 size_t st_attn_fin_split_workspace_floats(int B, int E, int parts);
-int st_attn_fin_split_fwd(const float* pq, const float* s_buf, const float* memory, const float* w_cum_prev,
-                          float* w_out, int ld_wout, float* w_cum_out, const float* v,
-                          const st_t16_view* ctx_dst, int n_ctx_dst, float* ctx, int ld_ctx, float* workspace, int parts,
-                          int B, int L, int A, int E, void* stream);
-
 /* Query projection + attention fin part in ONE launch: pq = W_q h_q (ref: src/module.py:380) is computed by the first workgroups
- * and handed to the fin workgroups of the same launch (st_attn_fin_t16_fwd's work: :389-406, :262-264) as 8-byte
+ * and handed to the fin workgroups of the same launch (st_attn_fin_fwd's work: :389-406, :262-264) as 8-byte
  * {value, tag} words in `granules` ((B, A) 64-bit words, device memory, ZEROED by the caller before the first step of a
  * forward); `epoch` = decode step + 1 (never 0) is the tag this launch writes and waits for.  The fin workgroups request S, v
  * and the memory rows while pq is being computed: one kernel boundary and one exposed load round trip less per decode step.
  * Needs A % 16 == 0, A <= 256 and (A / 16) * ceil(B / 16) + B * parts workgroups resident at once (<= compute units); when that
- * does not hold the call fails and the caller uses st_skinny_linear_packed_fwd + st_attn_fin_t16_fwd. */
+ * does not hold the call fails and the caller uses st_skinny_linear_packed_fwd + st_attn_fin_fwd. */
 typedef struct st_attn_fin_job {
     const float* s_buf; const float* memory; const float* w_cum_prev;
     float* w_out; int ld_wout; float* w_cum_out; const float* v;
     st_t16_view ctx_dst[3]; int n_ctx_dst;
-    int parts;          /* workgroups per utterance (slices of the context dims): 1, 2, 4, 8 */
+    int parts;          /* workgroups per utterance: each takes E / parts context dims and repeats the energies + softmax; 1, 2, 4 or 8
+                         * with E % (4 * parts) == 0 */
     int L, A, E, F, K;
     unsigned* status;   /* optional device word: bit 0 is set when a fin workgroup gave up waiting for its granules (the query is
                          * then poisoned with NaN as well); never cleared by the library -- the caller zeroes and reads it */
+    float* ctx; int ld_ctx;   /* optional natural (B, E) context output, beside or instead of the T16 destinations */
 } st_attn_fin_job;
+int st_attn_fin_fwd(const float* pq, const st_attn_fin_job* job, int B, void* stream);   /* the fin part as a launch of its own, pq (B, A) */
+int st_attn_fin_split_fwd(const float* pq, const st_attn_fin_job* job, float* workspace, int B, void* stream);
 int st_query_attn_fin_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
                           const st_attn_fin_job* job, int B, void* stream);
 /* A partial product part (B, N) = x[:, kb0 .. kb0 + KB) W[:, kb0 .. kb0 + KB)^T over a k-block range of a P16 matrix (w_kbs k-blocks per row
@@ -308,7 +284,7 @@ int st_partial_product_fwd(const st_partial_product_job* job, int B, void* strea
  * as 8-byte {value, tag} granules through `xchg` (st_attn_rng_xchg_words(B, E, parts) 64-bit words, zero before the first epoch of a
  * forward) and each finishes E / parts context dims and the weights of its own positions.  One launch instead of three.
  * Needs E % (4 * parts) == 0, E / parts <= 256 and every workgroup resident at once: st_query_attn_rng_fits(B, A, parts) != 0
- * (occupancy query of the kernel x compute units); otherwise use the two / three launch forms. */
+ * (occupancy query of the kernel x compute units); otherwise use the two / three launch forms.  No natural output: job->ctx must be NULL. */
 int st_query_attn_rng_fits(int B, int A, int parts);
 size_t st_attn_rng_xchg_words(int B, int E, int parts);
 int st_query_attn_rng_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules,
@@ -790,7 +766,7 @@ typedef struct st_decoder_io {
                                         * cell's gate products over operands that are known BEFORE the attention runs -- the tail of the cell's
                                         * reduction [ctx | AdaIN(h_q(t)) | h_d(t-1)] from column gate_part_k on -- ride beside the pq / fin launch
                                         * on compute units it leaves idle (st_query_attn_fin_part_fwd); the cell launch then reduces the first
-                                        * gate_part_k columns and adds this slab (st_lstm_cell_packed_part_fwd).  fp32 re-association only.
+                                        * gate_part_k columns and adds this slab (st_lstm_cell_packed_job.part).  fp32 re-association only.
                                         * NULL = off */
     int gate_part_k;                   /* the cell's own share of the reduction: a multiple of 16 in [kb16(E) * 16, K_d); 0 = the callee's rule
                                         * (st_decoder_gate_split_k: half of the reduction in whole rounds of 16 k-blocks -- C2: 1280 of 2560,

@@ -158,7 +158,23 @@ class StAttnFinJob(C.Structure):
     _fields_ = [('s_buf', C.c_void_p), ('memory', C.c_void_p), ('w_cum_prev', C.c_void_p),
                 ('w_out', C.c_void_p), ('ld_wout', C.c_int), ('w_cum_out', C.c_void_p), ('v', C.c_void_p),
                 ('ctx_dst', StT16View * 3), ('n_ctx_dst', C.c_int), ('parts', C.c_int),
-                ('L', C.c_int), ('A', C.c_int), ('E', C.c_int), ('F', C.c_int), ('K', C.c_int), ('status', C.c_void_p)]
+                ('L', C.c_int), ('A', C.c_int), ('E', C.c_int), ('F', C.c_int), ('K', C.c_int), ('status', C.c_void_p),
+                ('ctx', C.c_void_p), ('ld_ctx', C.c_int)]
+
+
+class StAttnStepJob(C.Structure):
+    _fields_ = [('pq', C.c_void_p), ('pm', C.c_void_p), ('memory', C.c_void_p),
+                ('w_prev', C.c_void_p), ('ld_wprev', C.c_int), ('w_cum_prev', C.c_void_p),
+                ('w_out', C.c_void_p), ('ld_wout', C.c_int), ('w_cum_out', C.c_void_p),
+                ('loc_conv_w', C.c_void_p), ('loc_lin_w', C.c_void_p), ('v', C.c_void_p),
+                ('ctx_dst', StT16View * 3), ('n_ctx_dst', C.c_int), ('ctx', C.c_void_p), ('ld_ctx', C.c_int),
+                ('h_q', C.c_void_p), ('ld_hq', C.c_int), ('ada_std', C.c_void_p), ('ada_mean', C.c_void_p), ('h_adapt', C.c_void_p),
+                ('Q', C.c_int), ('L', C.c_int), ('A', C.c_int), ('E', C.c_int), ('F', C.c_int), ('K', C.c_int)]
+
+
+class StPartialProductJob(C.Structure):
+    _fields_ = [('packed_w', C.c_void_p), ('w_kbs', C.c_int), ('kb0', C.c_int), ('KB', C.c_int), ('x', StT16View), ('N', C.c_int),
+                ('part', C.c_void_p)]
 
 
 P, I, F, Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -181,7 +197,7 @@ SIGNATURES = {
     'st_event_destroy': [P],
     'st_lstm_cell_fwd': [C.POINTER(StSeg), I, P, P, P, I, P, I, P, P, I, P, I, P, I, I, P],
     'st_skinny_linear_fwd': [C.POINTER(StSeg), I, P, I, P, I, P, I, I, P, I, I, I, I, P],
-    'st_attn_step_fwd': [P, P, P, P, I, P, P, I, P, P, P, P, P, I, P, I, P, P, P, I, I, I, I, I, I, I, P],
+    'st_attn_step_fwd': [C.POINTER(StAttnStepJob), I, P],
     'st_gemm_fwd': [P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, C.POINTER(StGemmEpilogue), P],
     'st_gemm_fwd_batch': [C.POINTER(StGemmJob), I, P],
     'st_gemm_fwd_variant': [P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, C.POINTER(StGemmEpilogue)],
@@ -230,23 +246,19 @@ SIGNATURES = {
     'st_pack_weight_batch': [P, I, P],
     'st_tile_rows': [P, I, C.POINTER(StT16View), I, I, P],
     'st_untile_rows': [C.POINTER(StT16View), P, I, I, I, P],
-    'st_lstm_cell_packed_fwd': [P, C.POINTER(StT16View), I, P, P, P, I, P, C.POINTER(StT16View), C.POINTER(StT16View),
-                                P, I, P, P, P, C.POINTER(StT16View), I, I, P],
-    'st_lstm_cell_packed_part_fwd': [P, I, C.POINTER(StT16View), I, P, P, P, P, I, P, C.POINTER(StT16View), C.POINTER(StT16View),
-                                     P, I, P, I, I, P],
+    'st_lstm_cell_packed_fwd': [C.POINTER(StLstmCellPackedJob), P],
     'st_lstm_cell_packed_pair_fwd': [C.POINTER(StLstmCellPackedJob), C.POINTER(StLstmCellPackedJob), P],
     'st_skinny_linear_packed_fwd': [P, C.POINTER(StT16View), I, P, I, P, I, P, I, C.POINTER(StT16View), I, P, I, I,
                                     I, I, P, I, C.POINTER(StT16View), I, I, P],
-    'st_attn_step_t16_fwd': [P, P, P, P, I, P, P, I, P, P, P, P, C.POINTER(StT16View), I, P, I, I, I, I, I, I, I, P],
     'st_skinny_linear_packed_attnpre_fwd': [P, C.POINTER(StT16View), I, P, I, P, I, P, I, C.POINTER(StT16View), I, P, I, I,
                                             I, I, P, I, C.POINTER(StT16View), I, I, C.POINTER(StAttnPreJob), P],
-    'st_attn_pre_fwd': [P, P, I, P, P, P, P, I, I, I, I, I, I, P],
-    'st_attn_fin_t16_fwd': [P, P, P, P, P, I, P, P, C.POINTER(StT16View), I, P, I, I, I, I, I, I, I, I, P],
+    'st_attn_pre_fwd': [C.POINTER(StAttnPreJob), I, P],
+    'st_attn_fin_fwd': [P, C.POINTER(StAttnFinJob), I, P],
     'st_attn_fin_split_workspace_floats': [I, I, I],
-    'st_attn_fin_split_fwd': [P, P, P, P, P, I, P, P, C.POINTER(StT16View), I, P, I, P, I, I, I, I, I, P],
+    'st_attn_fin_split_fwd': [P, C.POINTER(StAttnFinJob), P, I, P],
     'st_query_attn_fin_fwd': [P, C.POINTER(StT16View), I, P, C.c_uint, C.POINTER(StAttnFinJob), I, P],
-    'st_query_attn_fin_part_fwd': [P, C.POINTER(StT16View), I, P, C.c_uint, C.POINTER(StAttnFinJob), I, P, P],
-    'st_partial_product_fwd': [P, I, P],
+    'st_query_attn_fin_part_fwd': [P, C.POINTER(StT16View), I, P, C.c_uint, C.POINTER(StAttnFinJob), I, C.POINTER(StPartialProductJob), P],
+    'st_partial_product_fwd': [C.POINTER(StPartialProductJob), I, P],
     'st_layer_norm_fwd': [P, I, P, P, F, P, I, P, P, I, I, P],
     'st_layer_norm_bwd': [P, I, P, I, P, P, P, P, I, P, I, I, P],
     'st_log_softmax_fwd': [P, P, I, I, P],

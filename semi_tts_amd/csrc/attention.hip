@@ -20,7 +20,7 @@ int at_launch(const AtArgs& a, hipStream_t stream) {
     const AtLds o = at_layout(a.L, a.A, a.E, a.F, a.K, PART, at_pos_per(a.L, pre_parts), PART == 1 && vec && a.F == 32 && a.A % 16 == 0);
     const size_t lds_bytes = (size_t)o.total * sizeof(float);
     ST_CHECK_ARG(lds_bytes <= 160 * 1024, "attention step: L=%d needs %zu B of LDS (> 160 KiB)%s", a.L, lds_bytes,
-                 PART == 0 ? "; the split form (st_attn_pre_fwd with more parts + st_attn_fin_t16_fwd) takes longer texts" : "");
+                 PART == 0 ? "; the split form (st_attn_pre_fwd with more parts + st_attn_fin_fwd) takes longer texts" : "");
     static bool configured = false;
     if (!configured) {
         ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(at_kernel<true, PART>),
@@ -201,90 +201,44 @@ __global__ __launch_bounds__(AT_THREADS) void at_combine_kernel(const AcArgs a) 
 
 }  // namespace
 
-extern "C" int st_attn_step_fwd(const float* pq, const float* pm, const float* memory,
-                                const float* w_prev, int ld_wprev, const float* w_cum_prev,
-                                float* w_out, int ld_wout, float* w_cum_out,
-                                const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                float* ctx, int ld_ctx,
-                                const float* h_q, int ld_hq, const float* ada_std, const float* ada_mean,
-                                float* h_adapt, int Q,
-                                int B, int L, int A, int E, int F, int K, void* stream) {
+// the whole step: context to a natural buffer and / or up to 3 T16 destinations (the decode loop), or with AdaIN of the query state
+extern "C" int st_attn_step_fwd(const st_attn_step_job* job, int B, void* stream) {
     (void)hipGetLastError();  // drop stale errors left by other HIP users of this thread
     AtArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pq = pq; a.pm = pm; a.memory = memory; a.w_prev = w_prev; a.ld_wprev = ld_wprev; a.w_cum_prev = w_cum_prev;
-    a.w_out = w_out; a.ld_wout = ld_wout; a.w_cum_out = w_cum_out;
-    a.loc_conv_w = loc_conv_w; a.loc_lin_w = loc_lin_w; a.v = v; a.ctx = ctx; a.ld_ctx = ld_ctx;
-    a.h_q = h_q; a.ld_hq = ld_hq; a.ada_std = ada_std; a.ada_mean = ada_mean; a.h_adapt = h_adapt; a.Q = Q;
-    a.B = B; a.L = L; a.A = A; a.E = E; a.F = F; a.K = K;
-    return at_launch<0>(a, (hipStream_t)stream);
-}
-
-// decode-loop variant: context written to up to 3 T16 destinations (and optionally natural)
-extern "C" int st_attn_step_t16_fwd(const float* pq, const float* pm, const float* memory,
-                                    const float* w_prev, int ld_wprev, const float* w_cum_prev,
-                                    float* w_out, int ld_wout, float* w_cum_out,
-                                    const float* loc_conv_w, const float* loc_lin_w, const float* v,
-                                    const st_t16_view* ctx_dst, int n_ctx_dst, float* ctx, int ld_ctx,
-                                    int B, int L, int A, int E, int F, int K, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(n_ctx_dst >= 0 && n_ctx_dst <= 3 && (n_ctx_dst == 0 || ctx_dst), "st_attn_step_t16_fwd: n_ctx_dst=%d", n_ctx_dst);
-    AtArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pq = pq; a.pm = pm; a.memory = memory; a.w_prev = w_prev; a.ld_wprev = ld_wprev; a.w_cum_prev = w_cum_prev;
-    a.w_out = w_out; a.ld_wout = ld_wout; a.w_cum_out = w_cum_out;
-    a.loc_conv_w = loc_conv_w; a.loc_lin_w = loc_lin_w; a.v = v; a.ctx = ctx; a.ld_ctx = ld_ctx;
-    for (int d = 0; d < n_ctx_dst; ++d) a.ctx_dst[d] = ctx_dst[d];
-    a.B = B; a.L = L; a.A = A; a.E = E; a.F = F; a.K = K;
+    if (at_step_fill(a, job, B, "st_attn_step_fwd")) return -1;
     return at_launch<0>(a, (hipStream_t)stream);
 }
 
 // The step in two parts (see attention_body.h): `pre` needs only the previous step's weights (w_prev, w_cum_prev) and writes
 // S = pm + W_l conv(hist); `fin` needs the processed query and S.  pre(t+1) can run any time after fin(t).
-extern "C" int st_attn_pre_fwd(const float* pm, const float* w_prev, int ld_wprev, const float* w_cum_prev,
-                               const float* loc_conv_w, const float* loc_lin_w, float* s_buf, int parts,
-                               int B, int L, int A, int F, int K, void* stream) {
+extern "C" int st_attn_pre_fwd(const st_attn_pre_job* job, int B, void* stream) {
     (void)hipGetLastError();
+    ST_CHECK_ARG(!job || (!job->part && !job->cf_out), "st_attn_pre_fwd: a partial product or cf_out needs st_skinny_linear_packed_attnpre_fwd");
     AtArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pm = pm; a.w_prev = w_prev; a.ld_wprev = ld_wprev; a.w_cum_prev = w_cum_prev;
-    a.loc_conv_w = loc_conv_w; a.loc_lin_w = loc_lin_w; a.s_buf = s_buf;
-    a.pre_parts = (parts >= 2 && parts <= 64 && (parts & (parts - 1)) == 0) ? parts : 1;
-    a.B = B; a.L = L; a.A = A; a.E = 4; a.F = F; a.K = K;
+    if (at_pre_fill(a, job, B, "st_attn_pre_fwd")) return -1;
     return at_launch<1>(a, (hipStream_t)stream);
 }
 
-extern "C" int st_attn_fin_t16_fwd(const float* pq, const float* s_buf, const float* memory, const float* w_cum_prev,
-                                   float* w_out, int ld_wout, float* w_cum_out, const float* v,
-                                   const st_t16_view* ctx_dst, int n_ctx_dst, float* ctx, int ld_ctx, int parts,
-                                   int B, int L, int A, int E, int F, int K, void* stream) {
+extern "C" int st_attn_fin_fwd(const float* pq, const st_attn_fin_job* job, int B, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(n_ctx_dst >= 0 && n_ctx_dst <= 3 && (n_ctx_dst == 0 || ctx_dst), "st_attn_fin_t16_fwd: n_ctx_dst=%d", n_ctx_dst);
-    ST_CHECK_ARG(parts == 1 || ((parts == 2 || parts == 4 || parts == 8) && E % (4 * parts) == 0),
-                 "st_attn_fin_t16_fwd: parts=%d must be 1, 2, 4 or 8 with E=%d a multiple of 4*parts", parts, E);
     AtArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pq = pq; a.pm = s_buf; a.s_buf = const_cast<float*>(s_buf); a.memory = memory; a.w_cum_prev = w_cum_prev;
-    a.w_out = w_out; a.ld_wout = ld_wout; a.w_cum_out = w_cum_out; a.v = v; a.ctx = ctx; a.ld_ctx = ld_ctx;
-    a.loc_lin_w = s_buf;     // (unused by this part; only its alignment is looked at)
-    a.fin_parts = parts;
-    for (int d = 0; d < n_ctx_dst; ++d) a.ctx_dst[d] = ctx_dst[d];
-    a.B = B; a.L = L; a.A = A; a.E = E; a.F = F; a.K = K;
+    if (at_fin_fill(a, pq, job, B, "st_attn_fin_fwd")) return -1;
     return at_launch<2>(a, (hipStream_t)stream);
 }
 
 extern "C" size_t st_attn_fin_split_workspace_floats(int B, int E, int parts) { return (size_t)B * parts * (4 + E); }
 
-// st_attn_fin_t16_fwd with the utterance split over `parts` POSITION ranges (2..64) + a combine launch: for long texts, where one
+// st_attn_fin_fwd with the utterance split over `job->parts` POSITION ranges (2..64) + a combine launch: for long texts, where one
 // compute unit cannot pull an utterance's S and memory rows fast enough (see at_split_kernel).  workspace:
 // st_attn_fin_split_workspace_floats(B, E, parts) floats.
-extern "C" int st_attn_fin_split_fwd(const float* pq, const float* s_buf, const float* memory, const float* w_cum_prev,
-                                     float* w_out, int ld_wout, float* w_cum_out, const float* v,
-                                     const st_t16_view* ctx_dst, int n_ctx_dst, float* ctx, int ld_ctx, float* workspace, int parts,
-                                     int B, int L, int A, int E, void* stream) {
+extern "C" int st_attn_fin_split_fwd(const float* pq, const st_attn_fin_job* job, float* workspace, int B, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(pq && s_buf && memory && w_cum_prev && w_out && w_cum_out && v && workspace && B > 0 && L > 0, "st_attn_fin_split_fwd: bad arguments");
-    ST_CHECK_ARG(n_ctx_dst >= 0 && n_ctx_dst <= 3 && (n_ctx_dst == 0 || ctx_dst) && (ctx || n_ctx_dst > 0), "st_attn_fin_split_fwd: context outputs");
+    ST_CHECK_ARG(job, "st_attn_fin_split_fwd: null job");
+    const float* s_buf = job->s_buf; const float* memory = job->memory; const float* v = job->v;
+    const int n_ctx_dst = job->n_ctx_dst, L = job->L, A = job->A, E = job->E;
+    int parts = job->parts;
+    ST_CHECK_ARG(pq && s_buf && memory && job->w_cum_prev && job->w_out && job->w_cum_out && v && workspace && B > 0 && L > 0, "st_attn_fin_split_fwd: bad arguments");
+    ST_CHECK_ARG(n_ctx_dst >= 0 && n_ctx_dst <= 3 && (job->ctx || n_ctx_dst > 0), "st_attn_fin_split_fwd: context outputs");
     ST_CHECK_ARG(A % 4 == 0 && A >= 4 && A <= 256 && E % 4 == 0 && E / 4 <= AT_THREADS && AT_THREADS % (E / 4) == 0,
                  "st_attn_fin_split_fwd: A=%d must be a multiple of 4 up to 256, E=%d / 4 a divisor of %d", A, E, AT_THREADS);
     ST_CHECK_ARG(parts >= 2 && parts <= 64, "st_attn_fin_split_fwd: parts=%d (2..64)", parts);
@@ -298,14 +252,14 @@ extern "C" int st_attn_fin_split_fwd(const float* pq, const float* s_buf, const 
                  "st_attn_fin_split_fwd: operands must be 16-byte aligned");
     AsArgs s;
     memset(&s, 0, sizeof(s));
-    s.pq = pq; s.s_buf = s_buf; s.memory = memory; s.v = v; s.w_tmp = w_out; s.ld_w = ld_wout; s.ws = workspace;
+    s.pq = pq; s.s_buf = s_buf; s.memory = memory; s.v = v; s.w_tmp = job->w_out; s.ld_w = job->ld_wout; s.ws = workspace;
     s.B = B; s.L = L; s.A = A; s.E = E; s.P = parts; s.Lp = Lp;
     hipLaunchKernelGGL(at_split_kernel, dim3(B * parts), dim3(AT_THREADS), 0, (hipStream_t)stream, s);
     ST_LAUNCH_CHECK();
     AcArgs c;
     memset(&c, 0, sizeof(c));
-    c.ws = workspace; c.w = w_out; c.ld_w = ld_wout; c.w_cum_prev = w_cum_prev; c.w_cum_out = w_cum_out; c.ctx = ctx; c.ld_ctx = ld_ctx;
-    for (int d = 0; d < n_ctx_dst; ++d) c.ctx_dst[d] = ctx_dst[d];
+    c.ws = workspace; c.w = job->w_out; c.ld_w = job->ld_wout; c.w_cum_prev = job->w_cum_prev; c.w_cum_out = job->w_cum_out; c.ctx = job->ctx; c.ld_ctx = job->ld_ctx;
+    for (int d = 0; d < n_ctx_dst; ++d) c.ctx_dst[d] = job->ctx_dst[d];
     c.B = B; c.L = L; c.E = E; c.P = parts; c.Lp = Lp;
     hipLaunchKernelGGL(at_combine_kernel, dim3(B), dim3(AT_THREADS), 0, (hipStream_t)stream, c);
     ST_LAUNCH_CHECK();

@@ -784,4 +784,57 @@ __global__ __launch_bounds__(NT) void at_kernel(const float* pq, const float* pm
     at_body<VEC, PART, NT>(a, blockIdx.x, at_lds);
 }
 
+// ---- host: the job structs of semitts.h as an AtArgs block, one fill per part of the step.  `who` names the entry point in the messages;
+// what depends on the launch a part rides in (residency, LDS, granule alignment) is checked by that launch.
+inline int at_ctx_dst_fill(AtArgs& a, const st_t16_view* ctx_dst, int n_ctx_dst, const char* who) {
+    ST_CHECK_ARG(n_ctx_dst >= 0 && n_ctx_dst <= 3, "%s: n_ctx_dst=%d", who, n_ctx_dst);
+    for (int d = 0; d < n_ctx_dst; ++d) a.ctx_dst[d] = ctx_dst[d];
+    return 0;
+}
+
+// the whole step (at_kernel<., 0>)
+inline int at_step_fill(AtArgs& a, const st_attn_step_job* j, int B, const char* who) {
+    ST_CHECK_ARG(j, "%s: null job", who);
+    ST_CHECK_ARG(!j->h_q || j->n_ctx_dst == 0, "%s: AdaIN and T16 context destinations do not go together", who);
+    memset(&a, 0, sizeof(a));
+    if (at_ctx_dst_fill(a, j->ctx_dst, j->n_ctx_dst, who)) return -1;
+    a.pq = j->pq; a.pm = j->pm; a.memory = j->memory; a.w_prev = j->w_prev; a.ld_wprev = j->ld_wprev; a.w_cum_prev = j->w_cum_prev;
+    a.w_out = j->w_out; a.ld_wout = j->ld_wout; a.w_cum_out = j->w_cum_out;
+    a.loc_conv_w = j->loc_conv_w; a.loc_lin_w = j->loc_lin_w; a.v = j->v; a.ctx = j->ctx; a.ld_ctx = j->ld_ctx;
+    a.h_q = j->h_q; a.ld_hq = j->ld_hq; a.ada_std = j->ada_std; a.ada_mean = j->ada_mean; a.h_adapt = j->h_adapt; a.Q = j->Q;
+    a.B = B; a.L = j->L; a.A = j->A; a.E = j->E; a.F = j->F; a.K = j->K;
+    return 0;
+}
+
+// the pre part (at_kernel<., 1>, or extra workgroups of a linear's launch)
+inline int at_pre_fill(AtArgs& a, const st_attn_pre_job* j, int B, const char* who) {
+    ST_CHECK_ARG(j && j->pm && j->w_prev && j->w_cum_prev && j->loc_conv_w && j->loc_lin_w && j->L > 0 && j->A > 0 && j->F > 0 && j->K > 0 &&
+                 (j->K & 1), "%s: bad attention job", who);
+    memset(&a, 0, sizeof(a));
+    a.pm = j->pm; a.w_prev = j->w_prev; a.ld_wprev = j->ld_wprev; a.w_cum_prev = j->w_cum_prev;
+    a.loc_conv_w = j->loc_conv_w; a.loc_lin_w = j->loc_lin_w; a.s_buf = j->s_buf; a.cf_out = j->cf_out;
+    a.pre_parts = (j->parts >= 2 && j->parts <= 64 && (j->parts & (j->parts - 1)) == 0) ? j->parts : 1;
+    a.B = B; a.L = j->L; a.A = j->A; a.E = 4; a.F = j->F; a.K = j->K;
+    return 0;
+}
+
+// the fin part (at_kernel<., 2>, or the fin workgroups of the query projection's launch: pq NULL, it arrives as granules)
+inline int at_fin_fill(AtArgs& a, const float* pq, const st_attn_fin_job* j, int B, const char* who) {
+    ST_CHECK_ARG(j, "%s: null job", who);
+    ST_CHECK_ARG(j->parts == 1 || ((j->parts == 2 || j->parts == 4 || j->parts == 8) && j->E % (4 * j->parts) == 0),
+                 "%s: parts=%d must be 1, 2, 4 or 8 with E=%d a multiple of 4*parts", who, j->parts, j->E);
+    ST_CHECK_ARG(j->s_buf && j->memory && j->w_cum_prev && j->w_out && j->w_cum_out && j->v, "%s: null attention operand", who);
+    ST_CHECK_ARG(((j->A % 4 != 0) || (st_aligned16(j->s_buf) && st_aligned16(j->v))) && st_aligned16(j->memory) && j->E % 4 == 0 &&
+                 j->E / 4 <= AT_THREADS, "%s: operands must be 16-byte aligned, E a multiple of 4", who);
+    memset(&a, 0, sizeof(a));
+    if (at_ctx_dst_fill(a, j->ctx_dst, j->n_ctx_dst, who)) return -1;
+    a.pq = pq; a.pm = j->s_buf; a.s_buf = const_cast<float*>(j->s_buf); a.memory = j->memory; a.w_cum_prev = j->w_cum_prev;
+    a.w_out = j->w_out; a.ld_wout = j->ld_wout; a.w_cum_out = j->w_cum_out; a.v = j->v; a.ctx = j->ctx; a.ld_ctx = j->ld_ctx;
+    a.loc_lin_w = j->s_buf;     // (unused by this part; only its alignment is looked at)
+    a.fin_parts = j->parts;
+    a.B = B; a.L = j->L; a.A = j->A; a.E = j->E; a.F = j->F; a.K = j->K;
+    a.status = j->status;
+    return 0;
+}
+
 }  // namespace

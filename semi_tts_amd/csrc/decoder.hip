@@ -395,37 +395,64 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
     st_partial_product_job pj_d;      // the tail of the decoder cell's gate product (f.prod), wherever it runs
     memset(&pj_d, 0, sizeof(pj_d));
     pj_d.packed_w = io->packed + pl.d; pj_d.w_kbs = sv.d_kbs; pj_d.kb0 = f.d_k0; pj_d.KB = sv.d_kbs - f.d_k0; pj_d.N = 4 * D; pj_d.part = io->gate_part;
+    const bool part = f.prod != PROD_NONE;      // the decoder cell reduces its first d_k0 k-blocks and adds the slab
+    // the two cells of step t (1. and 4. below)
+    auto cell_q = [&](int t) {      // x = xq_t, h_q_t -> xq_{t+1}[h part], AdaIN(h_q_t) -> xd_t[hadapt part]
+        st_lstm_cell_packed_job j;
+        memset(&j, 0, sizeof(j));
+        j.packed_w = io->packed + pl.q; j.x = st_t16_view{io->xq_tape + (size_t)t * sv.q_floats, sv.q_kbs, 0}; j.K = Kq;
+        j.b_ih = w->q_b_ih; j.b_hh = w->q_b_hh;
+        j.c_prev = io->cq_tape + (size_t)t * BQ; j.ldc_prev = Q; j.mask = io->q_mask ? io->q_mask + (size_t)t * BQ : nullptr;
+        j.h_dst0 = st_t16_view{io->xq_tape + (size_t)(t + 1) * sv.q_floats, sv.q_kbs, sv.q_h};
+        j.c_out = io->cq_tape + (size_t)(t + 1) * BQ; j.ldc = Q;
+        j.gates_out = io->gates_q_tape ? io->gates_q_tape + (size_t)t * 4 * BQ : nullptr;
+        j.ada_std = io->ada_std; j.ada_mean = io->ada_mean; j.hadapt_dst = st_t16_view{io->xd_tape + (size_t)t * sv.d_floats, sv.d_kbs, sv.d_ha};
+        j.B = B; j.H = Q;
+        return j;
+    };
+    auto cell_d = [&](int t) {      // x = xd_t, h_d_t -> xd_{t+1}[h part], xo_t[h part]
+        st_lstm_cell_packed_job j;
+        memset(&j, 0, sizeof(j));
+        j.packed_w = io->packed + pl.d; j.x = st_t16_view{io->xd_tape + (size_t)t * sv.d_floats, sv.d_kbs, 0}; j.K = Kd;
+        j.b_ih = w->d_b_ih; j.b_hh = w->d_b_hh;
+        if (part) { j.K = 16 * f.d_k0; j.part = io->gate_part; j.w_kbs = sv.d_kbs; }
+        j.c_prev = io->cd_tape + (size_t)t * BD; j.ldc_prev = D; j.mask = io->d_mask ? io->d_mask + (size_t)t * BD : nullptr;
+        j.h_dst0 = st_t16_view{io->xd_tape + (size_t)(t + 1) * sv.d_floats, sv.d_kbs, sv.d_h};
+        j.h_dst1 = st_t16_view{io->xo_tape + (size_t)t * sv.o_floats, sv.o_kbs, 0};
+        j.c_out = io->cd_tape + (size_t)(t + 1) * BD; j.ldc = D;
+        j.gates_out = io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr;
+        j.B = B; j.H = D;
+        return j;
+    };
+    // the attention pre part of step t (needs only the weights of step t-1): beside the pq launch of step t or the proj launch of step t-1
+    auto pre_job = [&](int t, int parts) {
+        return st_attn_pre_job{io->pm, io->align_out + (size_t)(t - 1) * L, ldal, io->wcum_tape + (size_t)t * BL,
+                               w->attn_loc_conv_w, w->attn_loc_lin_w,
+                               f.attn != ATTN_WHOLE ? io->attn_s_buf + (size_t)t * io->attn_s_step_floats : nullptr, L, A, d->F, d->K,
+                               parts, io->attn_loc_tape ? io->attn_loc_tape + (size_t)t * BL * d->F : nullptr, nullptr};
+    };
     int rc = 0;
     for (int t = 0; t < steps; ++t) {
-        float* xq = io->xq_tape + (size_t)t * sv.q_floats;
         float* xq_next = io->xq_tape + (size_t)(t + 1) * sv.q_floats;
         float* xd = io->xd_tape + (size_t)t * sv.d_floats;
-        float* xd_next = io->xd_tape + (size_t)(t + 1) * sv.d_floats;
         float* xo = io->xo_tape + (size_t)t * sv.o_floats;
         pj_d.x = st_t16_view{xd, sv.d_kbs, f.d_k0};
 
         // 1. query LSTM (+ AdaIN of the new hidden state)                ref: :227-231, :267-269
         //    h_q_t -> xq_{t+1}[h part] (next step's recurrent input, also the query projection's input)
         //    adapted h_q_t -> xd_t[hadapt part]
-        st_t16_view xq_v = {xq, sv.q_kbs, 0};
         st_t16_view hq_dst = {xq_next, sv.q_kbs, sv.q_h};
-        st_t16_view ha_dst = {xd, sv.d_kbs, sv.d_ha};
         // (pair_cells: the query cell of step t > 0 ran beside the decoder cell of step t-1, see step 4)
         if (!(f.pair_cells && t > 0) && !ST_SKIPPED(0)) {
-            rc = st_lstm_cell_packed_fwd(io->packed + pl.q, &xq_v, Kq, w->q_b_ih, w->q_b_hh,
-                                         io->cq_tape + (size_t)t * BQ, Q, io->q_mask ? io->q_mask + (size_t)t * BQ : nullptr,
-                                         &hq_dst, nullptr, io->cq_tape + (size_t)(t + 1) * BQ, Q,
-                                         io->gates_q_tape ? io->gates_q_tape + (size_t)t * 4 * BQ : nullptr,
-                                         io->ada_std, io->ada_mean, &ha_dst, B, Q, stream);
+            const st_lstm_cell_packed_job jq = cell_q(t);
+            rc = st_lstm_cell_packed_fwd(&jq, stream);
             if (rc) return rc;
         }
 
         // 2. processed query (the merged forms issue it with step 3)    ref: :380
         if (f.attn != ATTN_PQ_FIN && f.attn != ATTN_PQ_RNG && !ST_SKIPPED(1)) {
             if (f.pre_in_pq && t > 0) {   // attention pre part of THIS step rides along (needs only the weights of step t-1)
-                st_attn_pre_job job = {io->pm, io->align_out + (size_t)(t - 1) * L, ldal, io->wcum_tape + (size_t)t * BL,
-                                       w->attn_loc_conv_w, w->attn_loc_lin_w, io->attn_s_buf + (size_t)t * io->attn_s_step_floats, L, A, d->F,
-                                       d->K, f.pq_pre_parts, io->attn_loc_tape ? io->attn_loc_tape + (size_t)t * BL * d->F : nullptr};
+                st_attn_pre_job job = pre_job(t, f.pq_pre_parts);
                 if (f.prod == PROD_PQ_PRE) job.part = &pj_d;      // ... and the tail of the decoder cell's gate product of this step
                 rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), nullptr, ST_ACT_NONE, nullptr, 0,
                                                          io->pq_buf, A, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, A,
@@ -441,7 +468,7 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         st_t16_view ctx_dst[3] = {{xq_next, sv.q_kbs, sv.q_ctx}, {xd, sv.d_kbs, 0}, {xo, sv.o_kbs, sv.o_ctx}};
         // S of this step: written by the pre part (step 0: no history yet, S = pm)
         const float* s_t = t == 0 || f.attn == ATTN_WHOLE ? io->pm : io->attn_s_buf + (size_t)t * io->attn_s_step_floats;
-        auto fin_job = [&](int parts) {      // the attention of the merged launches
+        auto fin_job = [&](int parts) {      // the fin part of the step, in whichever launch it runs
             st_attn_fin_job fj;
             memset(&fj, 0, sizeof(fj));
             fj.s_buf = s_t; fj.memory = io->memory; fj.w_cum_prev = io->wcum_tape + (size_t)t * BL;
@@ -453,24 +480,30 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         };
         switch (f.attn) {
         case ATTN_WHOLE:
-            if (!ST_SKIPPED(2))
-                rc = st_attn_step_t16_fwd(io->pq_buf, io->pm, io->memory, t == 0 ? io->zero_row : io->align_out + (size_t)(t - 1) * L,
-                                          t == 0 ? L : ldal, io->wcum_tape + (size_t)t * BL, io->align_out + (size_t)t * L, ldal,
-                                          io->wcum_tape + (size_t)(t + 1) * BL,
-                                          w->attn_loc_conv_w, w->attn_loc_lin_w, w->attn_v, ctx_dst, 3, nullptr, 0,
-                                          B, L, A, E, d->F, d->K, stream);
+            if (!ST_SKIPPED(2)) {
+                st_attn_step_job sj;
+                memset(&sj, 0, sizeof(sj));
+                sj.pq = io->pq_buf; sj.pm = io->pm; sj.memory = io->memory;
+                sj.w_prev = t == 0 ? io->zero_row : io->align_out + (size_t)(t - 1) * L; sj.ld_wprev = t == 0 ? L : ldal;
+                sj.w_cum_prev = io->wcum_tape + (size_t)t * BL;
+                sj.w_out = io->align_out + (size_t)t * L; sj.ld_wout = ldal; sj.w_cum_out = io->wcum_tape + (size_t)(t + 1) * BL;
+                sj.loc_conv_w = w->attn_loc_conv_w; sj.loc_lin_w = w->attn_loc_lin_w; sj.v = w->attn_v;
+                for (int c = 0; c < 3; ++c) sj.ctx_dst[c] = ctx_dst[c];
+                sj.n_ctx_dst = 3; sj.L = L; sj.A = A; sj.E = E; sj.F = d->F; sj.K = d->K;
+                rc = st_attn_step_fwd(&sj, B, stream);
+            }
             break;
         case ATTN_PRE_FIN:
-            if (!ST_SKIPPED(2))
-                rc = st_attn_fin_t16_fwd(io->pq_buf, s_t, io->memory, io->wcum_tape + (size_t)t * BL,
-                                         io->align_out + (size_t)t * L, ldal, io->wcum_tape + (size_t)(t + 1) * BL, w->attn_v,
-                                         ctx_dst, 3, nullptr, 0, f.fin_parts, B, L, A, E, d->F, d->K, stream);
+            if (!ST_SKIPPED(2)) {
+                const st_attn_fin_job fj = fin_job(f.fin_parts);
+                rc = st_attn_fin_fwd(io->pq_buf, &fj, B, stream);
+            }
             break;
         case ATTN_FIN_SPLIT:
-            if (!ST_SKIPPED(2))
-                rc = st_attn_fin_split_fwd(io->pq_buf, s_t, io->memory, io->wcum_tape + (size_t)t * BL, io->align_out + (size_t)t * L, ldal,
-                                           io->wcum_tape + (size_t)(t + 1) * BL, w->attn_v, ctx_dst, 3, nullptr, 0, io->attn_split_ws, sp_parts,
-                                           B, L, A, E, stream);
+            if (!ST_SKIPPED(2)) {
+                const st_attn_fin_job fj = fin_job(sp_parts);
+                rc = st_attn_fin_split_fwd(io->pq_buf, &fj, io->attn_split_ws, B, stream);
+            }
             break;
         case ATTN_PQ_FIN:       // 2 + 3 as one launch: the fin workgroups wait for pq inside the launch (granule hand-off)
             if (!(ST_SKIPPED(1) || ST_SKIPPED(2))) {
@@ -494,40 +527,14 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
             rc = st_partial_product_fwd(&pj_d, B, stream);
             if (rc) return rc;
         }
-        st_t16_view xd_v = {xd, sv.d_kbs, 0};
-        st_t16_view hd_dst0 = {xd_next, sv.d_kbs, sv.d_h};
-        st_t16_view hd_dst1 = {xo, sv.o_kbs, 0};
-        const bool part = f.prod != PROD_NONE;      // the cell reduces its first d_k0 k-blocks and adds the slab
         if (!ST_SKIPPED(3)) {
+            const st_lstm_cell_packed_job jd = cell_d(t);
             if (f.pair_cells && t + 1 < steps) {
                 // teacher forcing: the query cell of step t+1 needs ctx_t, h_q_t and a teacher frame -- not h_d_t.  Both cells in one launch.
-                st_lstm_cell_packed_job jd, jq;
-                memset(&jd, 0, sizeof(jd)); memset(&jq, 0, sizeof(jq));
-                jd.packed_w = io->packed + pl.d; jd.x = xd_v; jd.K = Kd; jd.b_ih = w->d_b_ih; jd.b_hh = w->d_b_hh;
-                if (part) { jd.K = 16 * f.d_k0; jd.part = io->gate_part; jd.w_kbs = sv.d_kbs; }
-                jd.c_prev = io->cd_tape + (size_t)t * BD; jd.ldc_prev = D; jd.mask = io->d_mask ? io->d_mask + (size_t)t * BD : nullptr;
-                jd.h_dst0 = hd_dst0; jd.h_dst1 = hd_dst1; jd.c_out = io->cd_tape + (size_t)(t + 1) * BD; jd.ldc = D;
-                jd.gates_out = io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr;
-                jd.B = B; jd.H = D;
-                float* xq_next2 = io->xq_tape + (size_t)(t + 2) * sv.q_floats;
-                jq.packed_w = io->packed + pl.q; jq.x = st_t16_view{xq_next, sv.q_kbs, 0}; jq.K = Kq; jq.b_ih = w->q_b_ih; jq.b_hh = w->q_b_hh;
-                jq.c_prev = io->cq_tape + (size_t)(t + 1) * BQ; jq.ldc_prev = Q; jq.mask = io->q_mask ? io->q_mask + (size_t)(t + 1) * BQ : nullptr;
-                jq.h_dst0 = st_t16_view{xq_next2, sv.q_kbs, sv.q_h}; jq.c_out = io->cq_tape + (size_t)(t + 2) * BQ; jq.ldc = Q;
-                jq.gates_out = io->gates_q_tape ? io->gates_q_tape + (size_t)(t + 1) * 4 * BQ : nullptr;
-                jq.ada_std = io->ada_std; jq.ada_mean = io->ada_mean; jq.hadapt_dst = st_t16_view{xd_next, sv.d_kbs, sv.d_ha};
-                jq.B = B; jq.H = Q;
+                const st_lstm_cell_packed_job jq = cell_q(t + 1);
                 rc = st_lstm_cell_packed_pair_fwd(&jd, &jq, stream);
-            } else if (part)
-                rc = st_lstm_cell_packed_part_fwd(io->packed + pl.d, sv.d_kbs, &xd_v, 16 * f.d_k0, io->gate_part, w->d_b_ih, w->d_b_hh,
-                                                  io->cd_tape + (size_t)t * BD, D, io->d_mask ? io->d_mask + (size_t)t * BD : nullptr,
-                                                  &hd_dst0, &hd_dst1, io->cd_tape + (size_t)(t + 1) * BD, D,
-                                                  io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr, B, D, stream);
-            else
-                rc = st_lstm_cell_packed_fwd(io->packed + pl.d, &xd_v, Kd, w->d_b_ih, w->d_b_hh,
-                                             io->cd_tape + (size_t)t * BD, D, io->d_mask ? io->d_mask + (size_t)t * BD : nullptr,
-                                             &hd_dst0, &hd_dst1, io->cd_tape + (size_t)(t + 1) * BD, D,
-                                             io->gates_d_tape ? io->gates_d_tape + (size_t)t * 4 * BD : nullptr,
-                                             nullptr, nullptr, nullptr, B, D, stream);
+            } else
+                rc = st_lstm_cell_packed_fwd(&jd, stream);
             if (rc) return rc;
         }
 
@@ -538,10 +545,7 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         const bool fuse = d->fuse_pre0 != 0;
         if (f.defer) continue;         // mel / stop of all steps come from one GEMM over the xo tape (caller)
         const bool split_attn = f.attn != ATTN_WHOLE;
-        st_attn_pre_job job = {io->pm, io->align_out + (size_t)t * L, ldal, io->wcum_tape + (size_t)(t + 1) * BL,
-                               w->attn_loc_conv_w, w->attn_loc_lin_w,
-                               split_attn ? io->attn_s_buf + (size_t)(t + 1) * io->attn_s_step_floats : nullptr, L, A, d->F, d->K,
-                               io->attn_pre_parts, io->attn_loc_tape ? io->attn_loc_tape + (size_t)(t + 1) * BL * d->F : nullptr};
+        const st_attn_pre_job job = pre_job(t + 1, io->attn_pre_parts);
         if (!ST_SKIPPED(4)) {
             rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pg, &xo_v, ST_SKIPPED(7) ? Ko / 4 : Ko, w->projgate_b, ST_ACT_NONE, nullptr, 0,
                                                      io->mel_out + (size_t)t * in_dim, (int)ldmel, fuse ? nullptr : &mel_dst, in_dim,

@@ -1371,54 +1371,6 @@ extern "C" int st_untile_rows(const st_t16_view* src, float* dst, int ld, int B,
     return 0;
 }
 
-static int lstm_cell_packed_impl(const float* packed_w, const st_t16_view* x, int K,
-                                 const float* b_ih, const float* b_hh,
-                                 const float* c_prev, int ldc_prev, const float* mask,
-                                 const st_t16_view* h_dst0, const st_t16_view* h_dst1,
-                                 float* c_out, int ldc, float* gates_out,
-                                 const float* ada_std, const float* ada_mean, const st_t16_view* hadapt_dst,
-                                 int B, int H, int w_kbs, const float* part, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(B > 0 && H > 0 && H % 4 == 0 && c_out && h_dst0 && h_dst0->base, "st_lstm_cell_packed_fwd: bad arguments");
-    PkArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = pk_fill(a, packed_w, x, K, "st_lstm_cell_packed_fwd");
-    if (rc) return rc;
-    if (part) {      // K covers the leading k-blocks only; the products over the others arrive as a slab (2-D tiled form, B = 17..32)
-        ST_CHECK_ARG(pk_rt2_shape(B, H / 4) && ((B + 15) >> 4) == 2 && w_kbs >= a.KB && st_aligned16(part),
-                     "st_lstm_cell_packed_part_fwd: needs B = 17..32, an even number of row tiles, w_kbs >= K / 16 and a 16-byte aligned slab");
-        a.part = part; a.w_kbs = w_kbs;
-    }
-    a.B = B; a.N = 4 * H; a.H = H;
-    a.b_ih = b_ih; a.b_hh = b_hh;
-    a.c_prev = c_prev; a.ldc_prev = ldc_prev; a.mask = mask;
-    a.c_out = c_out; a.ldc = ldc; a.gates_out = gates_out;
-    a.h_dst[0] = pk_out(h_dst0); a.h_dst[1] = pk_out(h_dst1);
-    a.ada_std = ada_std; a.ada_mean = ada_mean; a.ha_dst = pk_out(hadapt_dst);
-    return pk_dispatch<0>(a, H / 4, (hipStream_t)stream);
-}
-
-extern "C" int st_lstm_cell_packed_fwd(const float* packed_w, const st_t16_view* x, int K,
-                                       const float* b_ih, const float* b_hh,
-                                       const float* c_prev, int ldc_prev, const float* mask,
-                                       const st_t16_view* h_dst0, const st_t16_view* h_dst1,
-                                       float* c_out, int ldc, float* gates_out,
-                                       const float* ada_std, const float* ada_mean, const st_t16_view* hadapt_dst,
-                                       int B, int H, void* stream) {
-    return lstm_cell_packed_impl(packed_w, x, K, b_ih, b_hh, c_prev, ldc_prev, mask, h_dst0, h_dst1, c_out, ldc, gates_out, ada_std, ada_mean,
-                                 hadapt_dst, B, H, 0, nullptr, stream);
-}
-
-extern "C" int st_lstm_cell_packed_part_fwd(const float* packed_w, int w_kbs, const st_t16_view* x, int K, const float* part,
-                                            const float* b_ih, const float* b_hh,
-                                            const float* c_prev, int ldc_prev, const float* mask,
-                                            const st_t16_view* h_dst0, const st_t16_view* h_dst1,
-                                            float* c_out, int ldc, float* gates_out, int B, int H, void* stream) {
-    ST_CHECK_ARG(part, "st_lstm_cell_packed_part_fwd: null slab");
-    return lstm_cell_packed_impl(packed_w, x, K, b_ih, b_hh, c_prev, ldc_prev, mask, h_dst0, h_dst1, c_out, ldc, gates_out, nullptr, nullptr,
-                                 nullptr, B, H, w_kbs, part, stream);
-}
-
 static int pk_lstm_fill(PkArgs& a, const st_lstm_cell_packed_job* j, const char* who) {
     ST_CHECK_ARG(j && j->B > 0 && j->H > 0 && j->H % 4 == 0 && j->c_out && j->h_dst0.base, "%s: bad arguments", who);
     memset(&a, 0, sizeof(a));
@@ -1430,7 +1382,7 @@ static int pk_lstm_fill(PkArgs& a, const st_lstm_cell_packed_job* j, const char*
     a.c_out = j->c_out; a.ldc = j->ldc; a.gates_out = j->gates_out;
     a.h_dst[0] = pk_out(&j->h_dst0); a.h_dst[1] = pk_out(&j->h_dst1);
     a.ada_std = j->ada_std; a.ada_mean = j->ada_mean; a.ha_dst = pk_out(&j->hadapt_dst);
-    if (j->part) {       // (as lstm_cell_packed_impl: K covers the leading k-blocks, the others arrive as a slab)
+    if (j->part) {       // K covers the leading k-blocks only; the products over the others arrive as a slab (2-D tiled form, B = 17..32)
         ST_CHECK_ARG(pk_rt2_shape(j->B, j->H / 4) && ((j->B + 15) >> 4) == 2 && j->w_kbs >= a.KB && st_aligned16(j->part),
                      "%s: a slab needs B = 17..32, an even number of row tiles, w_kbs >= K / 16 and 16-byte alignment", who);
         a.part = j->part; a.w_kbs = j->w_kbs;
@@ -1438,7 +1390,27 @@ static int pk_lstm_fill(PkArgs& a, const st_lstm_cell_packed_job* j, const char*
     return 0;
 }
 
-// two independent LSTM cells (the arguments of st_lstm_cell_packed_fwd as structs): one launch when both take the 2-D tiled kernel
+extern "C" int st_lstm_cell_packed_fwd(const st_lstm_cell_packed_job* job, void* stream) {
+    (void)hipGetLastError();
+    PkArgs a;
+    int rc = pk_lstm_fill(a, job, "st_lstm_cell_packed_fwd");
+    if (rc) return rc;
+    return pk_dispatch<0>(a, a.H / 4, (hipStream_t)stream);
+}
+
+// the K-split partial product of an st_partial_product_job (pk_part_body, one split) as a PkPartArgs block
+static int pk_part_job_fill(PkPartArgs& pp, const st_partial_product_job* pj, int B, const char* who) {
+    ST_CHECK_ARG(pj && pj->packed_w && pj->x.base && pj->part && pj->KB > 0 && pj->kb0 >= 0 && pj->kb0 + pj->KB <= pj->w_kbs &&
+                 pj->x.kb0 + pj->KB <= pj->x.kb_stride && B > 16 && B <= 32 && pj->N > 0 && pj->N % 32 == 0 && st_aligned16(pj->packed_w) &&
+                 st_aligned16(pj->x.base) && st_aligned16(pj->part), "%s: bad partial product (B = 17..32, N %% 32 == 0)", who);
+    memset(&pp, 0, sizeof(pp));
+    pp.w = reinterpret_cast<const f32x4*>(pj->packed_w) + (size_t)pj->kb0 * 64; pp.w_kbs = pj->w_kbs;
+    pp.x = reinterpret_cast<const f32x4*>(pj->x.base) + (size_t)pj->x.kb0 * 64; pp.x_kbs = pj->x.kb_stride;
+    pp.KB = pj->KB; pp.S = 1; pp.B = B; pp.N = pj->N; pp.part = pj->part;
+    return 0;
+}
+
+// two independent LSTM cells: one launch when both take the 2-D tiled kernel
 // with one batch tile per workgroup (B = 17..32), otherwise one launch each
 extern "C" int st_lstm_cell_packed_pair_fwd(const st_lstm_cell_packed_job* j0, const st_lstm_cell_packed_job* j1, void* stream) {
     (void)hipGetLastError();
@@ -1481,26 +1453,13 @@ static int pk_linear_impl(const float* packed_w, const st_t16_view* x, int K,
     a.n_split2 = n_split2; a.act2 = act2; a.mask2 = mask2; a.ldmask2 = ldmask2; a.y3_dst = pk_out(y3_dst);
     const int tiles = (N + 15) / 16;
     if (pre && pre->s_buf) {
-        ST_CHECK_ARG(pre->pm && pre->w_prev && pre->w_cum_prev && pre->loc_conv_w && pre->loc_lin_w && pre->L > 0 && pre->A > 0 &&
-                     pre->F > 0 && pre->K > 0 && (pre->K & 1), "st_skinny_linear_packed_attnpre_fwd: bad attention job");
         AtArgs t;
-        memset(&t, 0, sizeof(t));
-        t.pm = pre->pm; t.w_prev = pre->w_prev; t.ld_wprev = pre->ld_wprev; t.w_cum_prev = pre->w_cum_prev;
-        t.loc_conv_w = pre->loc_conv_w; t.loc_lin_w = pre->loc_lin_w; t.s_buf = pre->s_buf; t.cf_out = pre->cf_out;
-        t.B = B; t.L = pre->L; t.A = pre->A; t.E = 4; t.F = pre->F; t.K = pre->K;
-        t.pre_parts = (pre->parts >= 2 && pre->parts <= 64 && (pre->parts & (pre->parts - 1)) == 0) ? pre->parts : 1;
+        if (at_pre_fill(t, pre, B, "st_skinny_linear_packed_attnpre_fwd")) return -1;
         const int BT = (B + 15) >> 4;
         if (pre->part) {
-            const st_partial_product_job* pj = pre->part;
-            ST_CHECK_ARG(pj->packed_w && pj->x.base && pj->part && pj->KB > 0 && pj->kb0 >= 0 && pj->kb0 + pj->KB <= pj->w_kbs &&
-                         pj->x.kb0 + pj->KB <= pj->x.kb_stride && B > 16 && B <= 32 && pj->N > 0 && pj->N % 32 == 0 && st_aligned16(pj->packed_w) &&
-                         st_aligned16(pj->x.base) && st_aligned16(pj->part) && tiles <= 128,
-                         "st_skinny_linear_packed_attnpre_fwd: bad partial product (B = 17..32, N %% 32 == 0, a linear of at most 128 row tiles)");
+            ST_CHECK_ARG(tiles <= 128, "st_skinny_linear_packed_attnpre_fwd: a partial product rides beside a linear of at most 128 row tiles");
             PkPartArgs pp;
-            memset(&pp, 0, sizeof(pp));
-            pp.w = reinterpret_cast<const f32x4*>(pj->packed_w) + (size_t)pj->kb0 * 64; pp.w_kbs = pj->w_kbs;
-            pp.x = reinterpret_cast<const f32x4*>(pj->x.base) + (size_t)pj->x.kb0 * 64; pp.x_kbs = pj->x.kb_stride;
-            pp.KB = pj->KB; pp.S = 1; pp.B = B; pp.N = pj->N; pp.part = pj->part;
+            if (pk_part_job_fill(pp, pre->part, B, "st_skinny_linear_packed_attnpre_fwd")) return -1;
             return pk_launch_attnpre<1>(a, tiles, t, (hipStream_t)stream, &pp);
         }
         if (BT == 1 || tiles <= 128) return pk_launch_attnpre<1>(a, tiles, t, (hipStream_t)stream);
@@ -1517,11 +1476,7 @@ static int query_attn_fin_impl(const float* packed_wq, const st_t16_view* h_q, i
     ST_CHECK_ARG(packed_wq && h_q && h_q->base && granules && epoch != 0 && job && B > 0, "st_query_attn_fin_fwd: bad arguments");
     const int L = job->L, A = job->A, E = job->E, parts = job->parts;
     ST_CHECK_ARG(L > 0 && E > 0 && A > 0 && A % 16 == 0 && A <= 256, "st_query_attn_fin_fwd: attention dim %d must be a multiple of 16, at most 256", A);
-    ST_CHECK_ARG(parts == 1 || ((parts == 2 || parts == 4 || parts == 8) && E % (4 * parts) == 0), "st_query_attn_fin_fwd: parts=%d, E=%d", parts, E);
-    ST_CHECK_ARG(job->s_buf && job->memory && job->w_cum_prev && job->w_out && job->w_cum_out && job->v, "st_query_attn_fin_fwd: null attention operand");
-    ST_CHECK_ARG(job->n_ctx_dst >= 0 && job->n_ctx_dst <= 3, "st_query_attn_fin_fwd: n_ctx_dst=%d", job->n_ctx_dst);
-    ST_CHECK_ARG(st_aligned16(job->s_buf) && st_aligned16(job->memory) && st_aligned16(job->v) && (reinterpret_cast<uintptr_t>(granules) & 7) == 0 &&
-                 E % 4 == 0 && E / 4 <= AT_THREADS, "st_query_attn_fin_fwd: operands must be 16-byte aligned, E a multiple of 4");
+    ST_CHECK_ARG((reinterpret_cast<uintptr_t>(granules) & 7) == 0, "st_query_attn_fin_fwd: granules must be 8-byte aligned");
     PkArgs a;
     memset(&a, 0, sizeof(a));
     int rc = pk_fill(a, packed_wq, h_q, Q, "st_query_attn_fin_fwd");
@@ -1529,13 +1484,8 @@ static int query_attn_fin_impl(const float* packed_wq, const st_t16_view* h_q, i
     a.B = B; a.N = A; a.H = 0; a.act = ST_ACT_NONE;
     a.gran = granules; a.epoch = epoch;
     AtArgs t;
-    memset(&t, 0, sizeof(t));
-    t.pm = job->s_buf; t.s_buf = const_cast<float*>(job->s_buf); t.memory = job->memory; t.w_cum_prev = job->w_cum_prev;
-    t.w_out = job->w_out; t.ld_wout = job->ld_wout; t.w_cum_out = job->w_cum_out; t.v = job->v; t.loc_lin_w = job->s_buf;
-    t.fin_parts = parts;
-    for (int d = 0; d < job->n_ctx_dst; ++d) t.ctx_dst[d] = job->ctx_dst[d];
-    t.B = B; t.L = L; t.A = A; t.E = E; t.F = job->F; t.K = job->K;
-    t.pq_gran = granules; t.epoch = epoch; t.status = job->status;
+    if (at_fin_fill(t, nullptr, job, B, "st_query_attn_fin_fwd")) return -1;
+    t.pq_gran = granules; t.epoch = epoch;
     const int tiles = A / 16, BT = (B + 15) >> 4;
     const int n_lin = tiles * BT, n_fin = B * parts;
     // the waiting workgroups hold their compute units: everything must be resident at once
@@ -1546,17 +1496,11 @@ static int query_attn_fin_impl(const float* packed_wq, const st_t16_view* h_q, i
     constexpr int KW = 8;
     ST_CHECK_ARG(lds + sizeof(f32x4) * KW * 64 <= 160 * 1024, "st_query_attn_fin_fwd: L=%d needs too much LDS", L);
     if (pj) {       // + the workgroups of the hosted partial product, one compute unit each like everything else in this launch
-        ST_CHECK_ARG(pj->packed_w && pj->x.base && pj->part && pj->KB > 0 && pj->kb0 >= 0 && pj->kb0 + pj->KB <= pj->w_kbs &&
-                     pj->x.kb0 + pj->KB <= pj->x.kb_stride && B > 16 && B <= 32 && pj->N > 0 && pj->N % 32 == 0 && st_aligned16(pj->packed_w) &&
-                     st_aligned16(pj->x.base) && st_aligned16(pj->part), "st_query_attn_fin_part_fwd: bad partial product (B = 17..32, N %% 32 == 0)");
+        PkPartArgs pp;
+        if (pk_part_job_fill(pp, pj, B, "st_query_attn_fin_part_fwd")) return -1;
         const int n_part = pj->N >> 5;
         ST_CHECK_ARG(n_lin + n_fin + n_part <= st_device_cus(), "st_query_attn_fin_part_fwd: %d + %d + %d workgroups do not fit the device at once",
                      n_lin, n_fin, n_part);
-        PkPartArgs pp;
-        memset(&pp, 0, sizeof(pp));
-        pp.w = reinterpret_cast<const f32x4*>(pj->packed_w) + (size_t)pj->kb0 * 64; pp.w_kbs = pj->w_kbs;
-        pp.x = reinterpret_cast<const f32x4*>(pj->x.base) + (size_t)pj->x.kb0 * 64; pp.x_kbs = pj->x.kb_stride;
-        pp.KB = pj->KB; pp.S = 1; pp.B = B; pp.N = pj->N; pp.part = pj->part;
         if (lds < sizeof(f32x4) * KW * 4 * 64) lds = sizeof(f32x4) * KW * 4 * 64;        // (the part workgroups' reduction buffer lives in the dynamic region)
         auto kernp = pk_attnfin_part_kernel<1, KW, PK_TRIP_SMALL>;
         static size_t configured_p = 0;
@@ -1595,14 +1539,8 @@ extern "C" int st_query_attn_fin_part_fwd(const float* packed_wq, const st_t16_v
 // the partial product as a launch of its own (the decode loop's two-launch pq / fin form: same arithmetic, one launch more)
 extern "C" int st_partial_product_fwd(const st_partial_product_job* pj, int B, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(pj && pj->packed_w && pj->x.base && pj->part && pj->KB > 0 && pj->kb0 >= 0 && pj->kb0 + pj->KB <= pj->w_kbs &&
-                 pj->x.kb0 + pj->KB <= pj->x.kb_stride && B > 16 && B <= 32 && pj->N > 0 && pj->N % 32 == 0 && st_aligned16(pj->packed_w) &&
-                 st_aligned16(pj->x.base) && st_aligned16(pj->part), "st_partial_product_fwd: bad job (B = 17..32, N %% 32 == 0)");
     PkPartArgs pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.w = reinterpret_cast<const f32x4*>(pj->packed_w) + (size_t)pj->kb0 * 64; pp.w_kbs = pj->w_kbs;
-    pp.x = reinterpret_cast<const f32x4*>(pj->x.base) + (size_t)pj->x.kb0 * 64; pp.x_kbs = pj->x.kb_stride;
-    pp.KB = pj->KB; pp.S = 1; pp.B = B; pp.N = pj->N; pp.part = pj->part;
+    if (pk_part_job_fill(pp, pj, B, "st_partial_product_fwd")) return -1;
     hipLaunchKernelGGL((pk_part_kernel<8, 2>), dim3(pj->N >> 5), dim3(8 * 64), 0, (hipStream_t)stream, pp);
     ST_LAUNCH_CHECK();
     return 0;
@@ -1640,6 +1578,7 @@ extern "C" int st_query_attn_rng_fwd(const float* packed_wq, const st_t16_view* 
     ST_CHECK_ARG(Lp <= 512 && (parts - 1) * Lp < L, "st_query_attn_rng_fwd: L=%d over %d parts leaves an empty or oversized range", L, parts);
     ST_CHECK_ARG(job->s_buf && job->memory && job->w_cum_prev && job->w_out && job->w_cum_out && job->v, "st_query_attn_rng_fwd: null attention operand");
     ST_CHECK_ARG(job->n_ctx_dst >= 1 && job->n_ctx_dst <= 3, "st_query_attn_rng_fwd: n_ctx_dst=%d", job->n_ctx_dst);
+    ST_CHECK_ARG(!job->ctx, "st_query_attn_rng_fwd: no natural context output in this form (job->ctx must be NULL)");
     ST_CHECK_ARG(st_aligned16(job->s_buf) && st_aligned16(job->memory) && st_aligned16(job->v) && (reinterpret_cast<uintptr_t>(granules) & 7) == 0 &&
                  (reinterpret_cast<uintptr_t>(xchg) & 7) == 0, "st_query_attn_rng_fwd: operands must be 16-byte aligned");
     PkArgs a;

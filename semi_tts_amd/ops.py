@@ -202,16 +202,18 @@ def linear_small(x, w, bias=None, act=None, mask=None, out=None):
 
 def attn_step(pq, pm, memory, w_prev, w_cum_prev, w_out, w_cum_out, loc_conv_w, loc_lin_w, v, ctx,
               h_q=None, ada_std=None, ada_mean=None, h_adapt=None):
-    lib = _lib.load()
     B, L, E = memory.shape
-    A = pm.shape[-1]
-    F_, _, K = loc_conv_w.shape
-    Q = h_q.shape[-1] if h_q is not None else 0
-    check(lib.st_attn_step_fwd(_p(pq), _p(pm), _p(memory), _p(w_prev), int(w_prev.stride(0)), _p(w_cum_prev),
-                               _p(w_out), int(w_out.stride(0)), _p(w_cum_out), _p(loc_conv_w), _p(loc_lin_w), _p(v),
-                               _p(ctx), int(ctx.stride(0)), _p(h_q), int(h_q.stride(0)) if h_q is not None else 0,
-                               _p(ada_std), _p(ada_mean), _p(h_adapt), Q, B, L, A, E, F_, K, stream_handle()),
-          'st_attn_step_fwd')
+    job = _lib.StAttnStepJob()
+    job.pq, job.pm, job.memory = _p(pq), _p(pm), _p(memory)
+    job.w_prev, job.ld_wprev, job.w_cum_prev = _p(w_prev), int(w_prev.stride(0)), _p(w_cum_prev)
+    job.w_out, job.ld_wout, job.w_cum_out = _p(w_out), int(w_out.stride(0)), _p(w_cum_out)
+    job.loc_conv_w, job.loc_lin_w, job.v = _p(loc_conv_w), _p(loc_lin_w), _p(v)
+    job.ctx, job.ld_ctx = _p(ctx), int(ctx.stride(0))
+    if h_q is not None:
+        job.h_q, job.ld_hq, job.Q = _p(h_q), int(h_q.stride(0)), h_q.shape[-1]
+    job.ada_std, job.ada_mean, job.h_adapt = _p(ada_std), _p(ada_mean), _p(h_adapt)
+    job.L, job.A, job.E, job.F, job.K = L, pm.shape[-1], E, loc_conv_w.shape[0], loc_conv_w.shape[2]
+    check(_lib.load().st_attn_step_fwd(C.byref(job), B, stream_handle()), 'st_attn_step_fwd')
 
 
 def attn_pre(pm, w_prev, w_cum_prev, loc_conv_w, loc_lin_w, s_buf=None, parts=1):
@@ -220,42 +222,49 @@ def attn_pre(pm, w_prev, w_cum_prev, loc_conv_w, loc_lin_w, s_buf=None, parts=1)
     F_, _, K = loc_conv_w.shape
     if s_buf is None:
         s_buf = torch.empty(B, L, A, device=pm.device, dtype=torch.float32)
-    check(_lib.load().st_attn_pre_fwd(_p(pm), _p(w_prev), int(w_prev.stride(0)), _p(w_cum_prev), _p(loc_conv_w), _p(loc_lin_w),
-                                      _p(s_buf), int(parts), B, L, A, F_, K, stream_handle()), 'st_attn_pre_fwd')
+    job = _lib.StAttnPreJob(pm=_p(pm), w_prev=_p(w_prev), ld_wprev=int(w_prev.stride(0)), w_cum_prev=_p(w_cum_prev), loc_conv_w=_p(loc_conv_w),
+                            loc_lin_w=_p(loc_lin_w), s_buf=_p(s_buf), L=L, A=A, F=F_, K=K, parts=int(parts))
+    check(_lib.load().st_attn_pre_fwd(C.byref(job), B, stream_handle()), 'st_attn_pre_fwd')
     return s_buf
 
 
-def attn_fin(pq, s_buf, memory, w_cum_prev, v, w_out, w_cum_out, ctx, F_, K, parts=1):
+def _fin_job(s_buf, memory, w_cum_prev, v, w_out, w_cum_out, parts, F_=0, K=0, ctx=None, ctx_t16=None, status=None):
+    """StAttnFinJob of one step: the context goes to `ctx` (natural (B, E)) and / or `ctx_t16` (a T16 buffer of (B, E))"""
     B, L, E = memory.shape
-    A = s_buf.shape[-1]
-    check(_lib.load().st_attn_fin_t16_fwd(_p(pq), _p(s_buf), _p(memory), _p(w_cum_prev), _p(w_out), int(w_out.stride(0)),
-                                          _p(w_cum_out), _p(v), None, 0, _p(ctx), int(ctx.stride(0)), int(parts), B, L, A, E, int(F_), int(K),
-                                          stream_handle()), 'st_attn_fin_t16_fwd')
+    job = _lib.StAttnFinJob()
+    job.s_buf, job.memory, job.w_cum_prev = _p(s_buf), _p(memory), _p(w_cum_prev)
+    job.w_out, job.ld_wout, job.w_cum_out, job.v = _p(w_out), int(w_out.stride(0)), _p(w_cum_out), _p(v)
+    if ctx_t16 is not None:
+        job.ctx_dst[0] = t16_view(ctx_t16, K=E)
+        job.n_ctx_dst = 1
+    if ctx is not None:
+        job.ctx, job.ld_ctx = _p(ctx), int(ctx.stride(0))
+    job.parts, job.L, job.A, job.E, job.F, job.K = int(parts), L, s_buf.shape[-1], E, int(F_), int(K)
+    job.status = _p(status, torch.int32)
+    return job
+
+
+def attn_fin(pq, s_buf, memory, w_cum_prev, v, w_out, w_cum_out, ctx, F_, K, parts=1, ctx_t16=None):
+    job = _fin_job(s_buf, memory, w_cum_prev, v, w_out, w_cum_out, parts, F_, K, ctx=ctx, ctx_t16=ctx_t16)
+    check(_lib.load().st_attn_fin_fwd(_p(pq), C.byref(job), memory.shape[0], stream_handle()), 'st_attn_fin_fwd')
 
 
 def attn_fin_split(pq, s_buf, memory, w_cum_prev, v, w_out, w_cum_out, ctx, parts):
     """the fin part over `parts` position ranges + a combine launch (long texts): st_attn_fin_split_fwd"""
     lib = _lib.load()
     B, L, E = memory.shape
-    A = s_buf.shape[-1]
     ws = torch.empty(int(lib.st_attn_fin_split_workspace_floats(B, E, int(parts))), device=memory.device, dtype=torch.float32)
-    check(lib.st_attn_fin_split_fwd(_p(pq), _p(s_buf), _p(memory), _p(w_cum_prev), _p(w_out), int(w_out.stride(0)), _p(w_cum_out), _p(v),
-                                    None, 0, _p(ctx), int(ctx.stride(0)), _p(ws), int(parts), B, L, A, E, stream_handle()),
-          'st_attn_fin_split_fwd')
+    job = _fin_job(s_buf, memory, w_cum_prev, v, w_out, w_cum_out, parts, ctx=ctx)
+    check(lib.st_attn_fin_split_fwd(_p(pq), C.byref(job), _p(ws), B, stream_handle()), 'st_attn_fin_split_fwd')
 
 
 def query_attn_fin(packed_wq, h_q_t16, Q, s_buf, memory, w_cum_prev, v, w_out, w_cum_out, ctx_t16, F_, K, parts=2, epoch=1, granules=None):
     """query projection + attention fin part in ONE launch (pq handed over inside the launch): st_query_attn_fin_fwd.
     h_q_t16 / ctx_t16: T16 buffers of (B, Q) / (B, E); `granules` (B, 2 A floats) must be zero before the first epoch."""
-    B, L, E = memory.shape
-    A = s_buf.shape[-1]
+    B, A = memory.shape[0], s_buf.shape[-1]
     if granules is None:
         granules = torch.zeros(B, 2 * A, device=memory.device, dtype=torch.float32)
-    job = _lib.StAttnFinJob()
-    job.s_buf, job.memory, job.w_cum_prev = _p(s_buf), _p(memory), _p(w_cum_prev)
-    job.w_out, job.ld_wout, job.w_cum_out, job.v = _p(w_out), int(w_out.stride(0)), _p(w_cum_out), _p(v)
-    job.ctx_dst[0] = t16_view(ctx_t16, K=E)
-    job.n_ctx_dst, job.parts, job.L, job.A, job.E, job.F, job.K = 1, int(parts), L, A, E, int(F_), int(K)
+    job = _fin_job(s_buf, memory, w_cum_prev, v, w_out, w_cum_out, parts, F_, K, ctx_t16=ctx_t16)
     hv = t16_view(h_q_t16, K=Q)
     check(_lib.load().st_query_attn_fin_fwd(_p(packed_wq), C.byref(hv), 16 * kb16(Q), _p(granules), int(epoch), C.byref(job), B,
                                             stream_handle()), 'st_query_attn_fin_fwd')
@@ -273,12 +282,7 @@ def query_attn_rng(packed_wq, h_q_t16, Q, s_buf, memory, w_cum_prev, v, w_out, w
         granules = torch.zeros(B, 2 * A, device=memory.device, dtype=torch.float32)
     if xchg is None:
         xchg = torch.zeros(2 * int(lib.st_attn_rng_xchg_words(B, E, int(parts))), device=memory.device, dtype=torch.float32)
-    job = _lib.StAttnFinJob()
-    job.s_buf, job.memory, job.w_cum_prev = _p(s_buf), _p(memory), _p(w_cum_prev)
-    job.w_out, job.ld_wout, job.w_cum_out, job.v = _p(w_out), int(w_out.stride(0)), _p(w_cum_out), _p(v)
-    job.ctx_dst[0] = t16_view(ctx_t16, K=E)
-    job.n_ctx_dst, job.parts, job.L, job.A, job.E, job.F, job.K = 1, int(parts), L, A, E, 0, 0
-    job.status = _p(status, torch.int32)
+    job = _fin_job(s_buf, memory, w_cum_prev, v, w_out, w_cum_out, parts, ctx_t16=ctx_t16, status=status)
     hv = t16_view(h_q_t16, K=Q)
     check(lib.st_query_attn_rng_fwd(_p(packed_wq), C.byref(hv), 16 * kb16(Q), _p(granules), _p(xchg), int(epoch), C.byref(job), B,
                                     stream_handle()), 'st_query_attn_rng_fwd')
@@ -1695,21 +1699,39 @@ def _vp(v):
     return C.byref(v) if v is not None else None
 
 
+def lstm_cell_job(packed_w, x_view, Kpad, b_ih, b_hh, c_prev, h_dst0, c_out, B, H, h_dst1=None, mask=None,
+                  gates_out=None, ada_std=None, ada_mean=None, hadapt_dst=None, part=None, w_kbs=0):
+    """StLstmCellPackedJob; x_view / *_dst: StT16View (see t16_view); Kpad = 16 * (k-blocks to reduce over).  `part` (B, 4H): the cell runs over
+    its LEADING Kpad columns and adds this slab of the products over the others; w_kbs = k-blocks per row tile of the whole packed matrix"""
+    job = _lib.StLstmCellPackedJob(packed_w=_p(packed_w), x=x_view, K=int(Kpad), b_ih=_p(b_ih), b_hh=_p(b_hh), c_prev=_p(c_prev), ldc_prev=H,
+                                   mask=_p(mask), h_dst0=h_dst0, c_out=_p(c_out), ldc=H, gates_out=_p(gates_out), ada_std=_p(ada_std),
+                                   ada_mean=_p(ada_mean), B=int(B), H=int(H), part=_p(part), w_kbs=int(w_kbs))
+    if h_dst1 is not None:
+        job.h_dst1 = h_dst1
+    if hadapt_dst is not None:
+        job.hadapt_dst = hadapt_dst
+    return job
+
+
 def lstm_cell_packed(packed_w, x_view, Kpad, b_ih, b_hh, c_prev, h_dst0, c_out, B, H, h_dst1=None, mask=None,
                      gates_out=None, ada_std=None, ada_mean=None, hadapt_dst=None):
-    """x_view / *_dst: StT16View (see t16_view); Kpad = 16 * (k-blocks to reduce over)"""
-    check(_lib.load().st_lstm_cell_packed_fwd(_p(packed_w), C.byref(x_view), int(Kpad), _p(b_ih), _p(b_hh),
-                                              _p(c_prev), H, _p(mask), C.byref(h_dst0), _vp(h_dst1), _p(c_out), H,
-                                              _p(gates_out), _p(ada_std), _p(ada_mean), _vp(hadapt_dst), int(B), int(H),
-                                              stream_handle()), 'st_lstm_cell_packed_fwd')
+    job = lstm_cell_job(packed_w, x_view, Kpad, b_ih, b_hh, c_prev, h_dst0, c_out, B, H, h_dst1, mask, gates_out, ada_std, ada_mean, hadapt_dst)
+    check(_lib.load().st_lstm_cell_packed_fwd(C.byref(job), stream_handle()), 'st_lstm_cell_packed_fwd')
 
 
 def lstm_cell_packed_part(packed_w, w_kbs, x_view, Kpad, part, b_ih, b_hh, c_prev, h_dst0, c_out, B, H, h_dst1=None, mask=None, gates_out=None):
-    """the cell over its LEADING Kpad columns + the slab `part` (B, 4H) of the products over the others (st_lstm_cell_packed_part_fwd);
-    w_kbs = k-blocks per row tile of the whole packed matrix"""
-    check(_lib.load().st_lstm_cell_packed_part_fwd(_p(packed_w), int(w_kbs), C.byref(x_view), int(Kpad), _p(part), _p(b_ih), _p(b_hh),
-                                                   _p(c_prev), H, _p(mask), C.byref(h_dst0), _vp(h_dst1), _p(c_out), H, _p(gates_out),
-                                                   int(B), int(H), stream_handle()), 'st_lstm_cell_packed_part_fwd')
+    """the cell over its LEADING Kpad columns + the slab `part` (B, 4H) of the products over the others"""
+    assert part is not None
+    job = lstm_cell_job(packed_w, x_view, Kpad, b_ih, b_hh, c_prev, h_dst0, c_out, B, H, h_dst1, mask, gates_out, part=part, w_kbs=w_kbs)
+    check(_lib.load().st_lstm_cell_packed_fwd(C.byref(job), stream_handle()), 'st_lstm_cell_packed_fwd')
+
+
+def partial_product(packed_w, w_kbs, kb0, KB, x_view, N, part, B):
+    """part (B, N) = x[:, kb0 .. kb0 + KB) W[:, kb0 .. kb0 + KB)^T over a k-block range of a P16 matrix (st_partial_product_fwd); x_view.kb0 =
+    the range's first k-block in the T16 buffer"""
+    job = _lib.StPartialProductJob(packed_w=_p(packed_w), w_kbs=int(w_kbs), kb0=int(kb0), KB=int(KB), x=x_view, N=int(N), part=_p(part))
+    check(_lib.load().st_partial_product_fwd(C.byref(job), int(B), stream_handle()), 'st_partial_product_fwd')
+    return part
 
 
 def skinny_linear_packed(packed_w, x_view, Kpad, B, N, y=None, y_dst=None, bias=None, act=None, mask=None,

@@ -150,6 +150,69 @@ def test_lstm_cell_packed(dev, B, H, Ks):
     assert maxdiff(gts[:, 3], torch.sigmoid(o)) < 1e-5
 
 
+@pytest.mark.parametrize('B', [17, 32])
+@pytest.mark.parametrize('k0', [1, 2])
+def test_lstm_cell_packed_partial_through_the_job(dev, B, k0):
+    """the cell over its leading k0 k-blocks + the slab of st_partial_product_fwd over the others == the whole cell, through
+    st_lstm_cell_packed_fwd and as one of the two jobs of st_lstm_cell_packed_pair_fwd (the other: the whole cell).  H = 8 is two row
+    tiles, the fewest the 2-D tiled cell takes; float reference and tolerance of test_lstm_cell_packed (K = 48 is no larger than there)."""
+    import ctypes as C
+    from semi_tts_amd import _lib, ops
+    H, Ks = 8, (16, 16, 16)
+    K, w_kbs = sum(Ks), len(Ks)
+    xs = [rnd(B, k, seed=10 + i) for i, k in enumerate(Ks)]
+    c = rnd(B, H, seed=3)
+    w = rnd(4 * H, K, scale=K ** -0.5, seed=4)
+    b_ih, b_hh = rnd(4 * H, scale=0.1, seed=6), rnd(4 * H, scale=0.1, seed=7)
+    mask = (torch.rand(B, H) > 0.1).float() / 0.9
+    gates = torch.cat(xs, 1) @ w.t() + b_ih + b_hh
+    i, f, g, o = [gates[:, j * H:(j + 1) * H] for j in range(4)]
+    c_ref = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+    h_ref = torch.sigmoid(o) * torch.tanh(c_ref) * mask
+    wd = w.to(dev)
+    packed = ops.pack_weight([wd[:, 16 * j:] for j in range(w_kbs)], Ks, 4 * H, lstm_H=H, ldws=[K] * w_kbs)
+    xbuf, stride = _combined_t16(ops, xs, Ks, dev)
+    assert stride == w_kbs
+    slab = torch.full((B, 4 * H), float('nan'), device=dev)
+    ops.partial_product(packed, w_kbs, k0, w_kbs - k0, ops.t16_view(xbuf, stride, k0), 4 * H, slab, B)
+    cd, md, bi, bh = c.to(dev), mask.to(dev), b_ih.to(dev), b_hh.to(dev)
+
+    def outputs():
+        return torch.zeros(ops.t16_floats(B, H), device=dev), torch.full((B, H), float('nan'), device=dev)
+
+    def check_cell(what, h_t16, c_out):
+        e_h, e_c = maxdiff(ops.untile_rows(h_t16, B, H), h_ref), maxdiff(c_out, c_ref)
+        report('lstm_cell_packed_partial', what=what, B=B, k0=k0, err_h=e_h, err_c=e_c)
+        assert e_h < 1e-5 and e_c < 1e-5
+
+    h1, c1 = outputs()
+    ops.lstm_cell_packed_part(packed, w_kbs, ops.t16_view(xbuf, stride), 16 * k0, slab, bi, bh, cd, ops.t16_view(h1, K=H), c1, B, H, mask=md)
+    check_cell('job', h1, c1)
+    h2, c2 = outputs()
+    h3, c3 = outputs()
+    j_part = ops.lstm_cell_job(packed, ops.t16_view(xbuf, stride), 16 * k0, bi, bh, cd, ops.t16_view(h2, K=H), c2, B, H, mask=md, part=slab,
+                               w_kbs=w_kbs)
+    j_whole = ops.lstm_cell_job(packed, ops.t16_view(xbuf, stride), 16 * w_kbs, bi, bh, cd, ops.t16_view(h3, K=H), c3, B, H, mask=md)
+    ops.check(_lib.load().st_lstm_cell_packed_pair_fwd(C.byref(j_part), C.byref(j_whole), ops.stream_handle()), 'st_lstm_cell_packed_pair_fwd')
+    check_cell('pair, partial', h2, c2)
+    check_cell('pair, whole', h3, c3)
+
+
+def test_attention_fin_natural_and_t16_context_at_once(dev):
+    """st_attn_fin_fwd writes the context to a natural (B, E) buffer and to a T16 destination in one launch: the same values"""
+    from semi_tts_amd import ops
+    B, L, A, E = 5, 13, 24, 40
+    pq, S, mem = rnd(B, A, seed=1), rnd(B, L, A, seed=2), rnd(B, L, E, seed=3)
+    w_cum, v = torch.rand(B, L, generator=torch.Generator().manual_seed(4)), rnd(1, A, seed=7)
+    d = [t.to(dev) for t in (pq, S, mem, w_cum, v)]
+    w_out, c_out = torch.empty(B, L, device=dev), torch.empty(B, L, device=dev)
+    ctx = torch.full((B, E), float('nan'), device=dev)
+    ctx_t16 = torch.zeros(ops.t16_floats(B, E), device=dev)
+    ops.attn_fin(d[0], d[1], d[2], d[3], d[4], w_out, c_out, ctx, 6, 7, ctx_t16=ctx_t16)
+    assert bool(torch.isfinite(ctx).all())
+    assert torch.equal(ctx, ops.untile_rows(ctx_t16, B, E))
+
+
 @pytest.mark.parametrize('K,cols', [(64, (32,)), (4096, (256, 512, 1024)), (100, (24, 40)), (37, (5, 18, 9)), (128, (1024,)), (48, (30, 34))])
 def test_pack_weight_transposed_concat(dev, K, cols):
     """st_pack_weight_t: the P16 image of cat(ws, 1).t() straight from the parameters == st_pack_weight of the materialised

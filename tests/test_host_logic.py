@@ -59,6 +59,44 @@ def test_product_path_refuses_cpu_tensors():
         m(torch.zeros(1, 5, 64), None, 6, torch.zeros(1, 128))
 
 
+def test_decode_step_jobs_refuse_what_they_cannot_express():
+    """the job entry points of the decode step refuse, before anything is launched, the combinations their launches have no form for
+    (the checks are host arithmetic on the job: they return here, without a device; the pointers are host memory nobody reads)"""
+    from semi_tts_amd import _lib
+    lib = _lib.load()
+    raw = ctypes.create_string_buffer(1 << 16)
+    p = (ctypes.addressof(raw) + 255) & ~255          # 256-byte aligned, like a device allocation
+    view = _lib.StT16View(base=p, kb_stride=4, kb0=0)
+
+    def refused(rc, why):
+        assert rc != 0
+        assert why in lib.st_last_error().decode(), lib.st_last_error()
+
+    def pre_job(**kw):
+        return _lib.StAttnPreJob(pm=p, w_prev=p, ld_wprev=13, w_cum_prev=p, loc_conv_w=p, loc_lin_w=p, s_buf=p, L=13, A=24, F=6, K=7, parts=1, **kw)
+
+    pj = _lib.StPartialProductJob(packed_w=p, w_kbs=3, kb0=1, KB=2, x=view, N=32, part=p)
+    refused(lib.st_attn_pre_fwd(ctypes.byref(pre_job(part=ctypes.addressof(pj))), 5, None), 'st_attn_pre_fwd: a partial product or cf_out')
+    refused(lib.st_attn_pre_fwd(ctypes.byref(pre_job(cf_out=p)), 5, None), 'st_attn_pre_fwd: a partial product or cf_out')
+
+    sj = _lib.StAttnStepJob(pq=p, pm=p, memory=p, w_prev=p, ld_wprev=13, w_cum_prev=p, w_out=p, ld_wout=13, w_cum_out=p, loc_conv_w=p,
+                            loc_lin_w=p, v=p, n_ctx_dst=1, h_q=p, ld_hq=48, ada_std=p, ada_mean=p, h_adapt=p, Q=48, L=13, A=24, E=40, F=6, K=7)
+    sj.ctx_dst[0] = view
+    refused(lib.st_attn_step_fwd(ctypes.byref(sj), 5, None), 'AdaIN and T16 context destinations')
+
+    def fin_job(**kw):
+        return _lib.StAttnFinJob(s_buf=p, memory=p, w_cum_prev=p, w_out=p, ld_wout=13, w_cum_out=p, v=p, parts=1, L=13, A=32, E=64, F=6, K=7, **kw)
+
+    refused(lib.st_attn_fin_fwd(p, ctypes.byref(fin_job()), 5, None), 'no context output')
+    fj = fin_job(n_ctx_dst=1, ctx=p, ld_ctx=64)
+    fj.parts = 2
+    fj.ctx_dst[0] = view
+    refused(lib.st_query_attn_rng_fwd(p, ctypes.byref(view), 48, p, p, 1, ctypes.byref(fj), 5, None), 'no natural context output')
+
+    cell = _lib.StLstmCellPackedJob(packed_w=p, x=view, K=16, c_prev=p, ldc_prev=8, h_dst0=view, c_out=p, ldc=8, B=16, H=8, part=p, w_kbs=3)
+    refused(lib.st_lstm_cell_packed_fwd(ctypes.byref(cell), None), 'a slab needs B = 17..32')
+
+
 def test_state_dict_keys_match_reference():
     """same parameter/buffer names and shapes as the reference modules, so its checkpoints load"""
     from semi_tts_amd.embed import L2Embedding, SeperateEmbedding

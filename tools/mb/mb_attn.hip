@@ -25,8 +25,11 @@ int main() {
     for (int mode = 0; mode < 5; ++mode) {     // 0..2: fin with 1/2/4 parts; 3..4: pre with 1/2 parts
         const int parts = mode < 3 ? (1 << mode) : (mode - 2);
         auto run = [&] {
-            int rc = mode < 3 ? st_attn_fin_t16_fwd(pq, s, mem, cum, wout, L, cumo, v, nullptr, 0, ctx, E, parts, B, L, A, E, F, K, nullptr)
-                              : st_attn_pre_fwd(s, wprev, L, cum, wc, wl, s, parts, B, L, A, F, K, nullptr);
+            st_attn_fin_job fj = {};
+            fj.s_buf = s; fj.memory = mem; fj.w_cum_prev = cum; fj.w_out = wout; fj.ld_wout = L; fj.w_cum_out = cumo; fj.v = v;
+            fj.ctx = ctx; fj.ld_ctx = E; fj.parts = parts; fj.L = L; fj.A = A; fj.E = E; fj.F = F; fj.K = K;
+            const st_attn_pre_job pj = {s, wprev, L, cum, wc, wl, s, L, A, F, K, parts, nullptr, nullptr};
+            int rc = mode < 3 ? st_attn_fin_fwd(pq, &fj, B, nullptr) : st_attn_pre_fwd(&pj, B, nullptr);
             if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
         for (int i = 0; i < 3; ++i) run();
         CK(hipDeviceSynchronize());

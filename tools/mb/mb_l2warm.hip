@@ -51,7 +51,8 @@ int main(int argc, char** argv) {
     CK(hipMemset(bh, 0, 16 * H)); CK(hipMemset(as, 0, B * H * 4)); CK(hipMemset(am, 0, B * H * 4));
     auto cell = [&](int i) {
         st_t16_view xv = {x[i], (Ks[i] + 15) / 16, 0}, d0 = {h0, H / 16, 0}, da = {ha, H / 16, 0};
-        int rc = st_lstm_cell_packed_fwd(w[i], &xv, Ks[i], bi, bh, c0, H, nullptr, &d0, nullptr, c1, H, nullptr, as, am, &da, B, H, nullptr);
+        const st_lstm_cell_packed_job j = {w[i], xv, Ks[i], bi, bh, c0, H, nullptr, d0, {}, c1, H, nullptr, as, am, da, B, H, nullptr, 0};
+        int rc = st_lstm_cell_packed_fwd(&j, nullptr);
         if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
     auto warm = [&](int i, bool real) {
         const int kbs = (Ks[i] + 15) / 16;

@@ -1,6 +1,6 @@
 // Micro-benchmark (development tool): the two LSTM cells of a teacher-forced step (query cell of step t+1, decoder cell of step t) are
 // independent -- what would one launch for both buy?  Each alone, back to back on one stream, flooding two streams.
-// hipcc --offload-arch=gfx950 -O3 -o mb_overlap2 mb_overlap2.hip ../../semi_tts_amd/csrc/runtime.hip
+// hipcc --offload-arch=gfx950 -O3 -o mb_overlap2 mb_overlap2.hip ../../semi_tts_amd/csrc/runtime.hip ../../semi_tts_amd/csrc/attention_bwd.hip
 #include <hip/hip_runtime.h>
 #include "../../semi_tts_amd/csrc/skinny_packed.hip"
 #include <cstdio>
@@ -27,7 +27,8 @@ int main() {
     auto run = [&](int i, hipStream_t st) {
         Cell& c = cells[i];
         st_t16_view xv = {c.x, (c.K + 15) / 16, 0}, d0 = {c.h0, H / 16, 0}, d1 = {c.h1, H / 16, 0}, da = {c.ha, H / 16, 0};
-        int rc = st_lstm_cell_packed_fwd(c.w, &xv, c.K, c.bi, c.bh, c.c0, H, nullptr, &d0, &d1, c.c1, H, nullptr, c.as, c.am, &da, B, H, st);
+        const st_lstm_cell_packed_job j = {c.w, xv, c.K, c.bi, c.bh, c.c0, H, nullptr, d0, d1, c.c1, H, nullptr, c.as, c.am, da, B, H, nullptr, 0};
+        int rc = st_lstm_cell_packed_fwd(&j, st);
         if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
     hipStream_t s1, s2; CK(hipStreamCreate(&s1)); CK(hipStreamCreate(&s2));
     for (int i = 0; i < 5; ++i) { run(0, s1); run(1, s1); }

@@ -1,5 +1,5 @@
 // Micro-benchmark (development tool): phase timing of the packed LSTM-cell kernel (pk_kernel<0>) at the decode shapes.
-// hipcc --offload-arch=gfx950 -O3 -o mb_pk mb_pk.hip ../../semi_tts_amd/csrc/runtime.hip
+// hipcc --offload-arch=gfx950 -O3 -o mb_pk mb_pk.hip ../../semi_tts_amd/csrc/runtime.hip ../../semi_tts_amd/csrc/attention_bwd.hip
 #include <hip/hip_runtime.h>
 __device__ unsigned long long g_prof[256 * 8 * 8];
 #define PK_PROF(n) do { if ((threadIdx.x & 63) == 0) g_prof[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (n)] = __builtin_readcyclecounter(); } while (0)
@@ -33,7 +33,8 @@ int main() {
         CK(hipMemset(w, 0, wf * 4)); CK(hipMemset(x, 0, xf * 4)); CK(hipMemset(c0, 0, B * H * 4)); CK(hipMemset(bi, 0, 16 * H)); CK(hipMemset(bh, 0, 16 * H));
         CK(hipMemset(as, 0, B * H * 4)); CK(hipMemset(am, 0, B * H * 4)); CK(hipMemset(h0, 0, hf * 4)); CK(hipMemset(h1, 0, hf * 4)); CK(hipMemset(ha, 0, hf * 4));
         st_t16_view xv = {x, (K + 15) / 16, 0}, d0 = {h0, H / 16, 0}, d1 = {h1, H / 16, 0}, da = {ha, H / 16, 0};
-        auto run = [&] { int rc = st_lstm_cell_packed_fwd(w, &xv, K, bi, bh, c0, H, nullptr, &d0, &d1, c1, H, nullptr, as, am, &da, B, H, nullptr);
+        const st_lstm_cell_packed_job j = {w, xv, K, bi, bh, c0, H, nullptr, d0, d1, c1, H, nullptr, as, am, da, B, H, nullptr, 0};
+        auto run = [&] { int rc = st_lstm_cell_packed_fwd(&j, nullptr);
             if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
         float* sink; CK(hipMalloc(&sink, 64));
         float* junk; CK(hipMalloc(&junk, 64 << 20));

@@ -1,5 +1,5 @@
 // Micro-benchmark (development tool): phase stamps of the 2-D tiled LSTM cell (pk_lstm_rt2_kernel) at the C2 decode shapes, the two
-// cells alternating as in the loop.  hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-kernarg-preload-count=16 -o mb_rt2 mb_rt2.hip ../../semi_tts_amd/csrc/runtime.hip
+// cells alternating as in the loop.  hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-kernarg-preload-count=16 -o mb_rt2 mb_rt2.hip ../../semi_tts_amd/csrc/runtime.hip ../../semi_tts_amd/csrc/attention_bwd.hip
 #include <hip/hip_runtime.h>
 __device__ unsigned long long g_rt2[2 * 128 * 8 * 8];
 #define RT2_PROF(n) do { if ((threadIdx.x & 63) == 0) g_rt2[(((blockIdx.y * gridDim.x + blockIdx.x) * 8) + (threadIdx.x >> 6)) * 8 + (n)] = __builtin_readcyclecounter(); } while (0)
@@ -27,7 +27,8 @@ int main() {
     CK(hipMemset(bh, 0, 16 * H)); CK(hipMemset(as, 0, B * H * 4)); CK(hipMemset(am, 0, B * H * 4));
     auto run = [&](int i) {
         st_t16_view xv = {x[i], (Ks[i] + 15) / 16, 0}, d0 = {h0, H / 16, 0}, da = {ha, H / 16, 0};
-        int rc = st_lstm_cell_packed_fwd(w[i], &xv, Ks[i], bi, bh, c0, H, nullptr, &d0, nullptr, c1, H, nullptr, as, am, &da, B, H, nullptr);
+        const st_lstm_cell_packed_job j = {w[i], xv, Ks[i], bi, bh, c0, H, nullptr, d0, {}, c1, H, nullptr, as, am, da, B, H, nullptr, 0};
+        int rc = st_lstm_cell_packed_fwd(&j, nullptr);
         if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
     for (int i = 0; i < 20; ++i) run(i & 1);
     CK(hipDeviceSynchronize());
