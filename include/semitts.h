@@ -152,15 +152,27 @@ int st_lstm_cell_packed_fwd(const st_lstm_cell_packed_job* job, void* stream);
  * for the attention of step t (src/module.py:216-288 with a teacher frame as the next input).  Falls back to one launch per cell for
  * shapes the 2-D tiled kernel does not take. */
 int st_lstm_cell_packed_pair_fwd(const st_lstm_cell_packed_job* j0, const st_lstm_cell_packed_job* j1, void* stream);
-/* st_skinny_linear_fwd on packed operands; output natural (y) and/or T16 (y_dst).
- * Optional third row range [n_split2, N): v = act2(v) * mask2(b, n - n_split2) -> y3_dst column
- * n - n_split2 (used to emit prenet layer 1 of the next step from the same launch as proj/gate). */
-int st_skinny_linear_packed_fwd(const float* packed_w, const st_t16_view* x, int K,
-                                const float* bias, int act, const float* mask, int ldmask,
-                                float* y, int ldy, const st_t16_view* y_dst,
-                                int n_split, float* y2, int ldy2, int rep,
-                                int n_split2, int act2, const float* mask2, int ldmask2, const st_t16_view* y3_dst,
-                                int B, int N, void* stream);
+/* The operands of every packed weight-streaming product: y (B, N) = x W^T, x = K logical columns starting at view x (by value, as in
+ * st_lstm_cell_packed_job), W a P16 buffer of N rows, y natural with row stride ldy >= N.  The K-split partial products
+ * (st_skinny_partial_attn_*, st_partial_product_fwd) keep arguments of their own: their output is S slabs, not a (y, ldy) pair. */
+typedef struct st_packed_product {
+    const float* packed_w; st_t16_view x; int K;
+    float* y; int ldy;
+    int B, N;
+} st_packed_product;
+/* st_skinny_linear_fwd on packed operands; output natural (p.y) and/or T16 (y_dst).  A zero-initialised job with only `p` set is the
+ * plain product y = x W^T. */
+typedef struct st_packed_linear_job {
+    st_packed_product p;                            /* p.y may be NULL when y_dst.base is given */
+    const float* bias; int act; const float* mask; int ldmask;   /* v = act(x W^T + bias) * mask(b, n), as st_skinny_linear_fwd */
+    st_t16_view y_dst;                              /* .base NULL = none (as h_dst1 of the cell job) */
+    int n_split; float* y2; int ldy2; int rep;      /* n_split > 0: columns n >= n_split go to y2[b, (n - n_split) * rep + j], j < rep,
+                                                     * instead (y = mel, y2 = stop.  ref: proj (+) gate_layer src/module.py:285-287) */
+    /* optional third row range [n_split2, N), n_split2 >= n_split: v = act2(v) * mask2(b, n - n_split2) -> y3_dst column n - n_split2
+     * (used to emit prenet layer 1 of the next step from the same launch as proj/gate) */
+    int n_split2; int act2; const float* mask2; int ldmask2; st_t16_view y3_dst;
+} st_packed_linear_job;
+int st_skinny_linear_packed_fwd(const st_packed_linear_job* job, void* stream);
 
 /* ------------------------------------------------------------------ location-sensitive attention
  * One decode step for the whole batch, one workgroup per utterance.
@@ -205,12 +217,7 @@ typedef struct st_attn_pre_job {
     const struct st_partial_product_job* part;
 } st_attn_pre_job;
 int st_attn_pre_fwd(const st_attn_pre_job* job, int B, void* stream);   /* the pre part as a launch of its own: no cf_out, no part */
-int st_skinny_linear_packed_attnpre_fwd(const float* packed_w, const st_t16_view* x, int K,
-                                        const float* bias, int act, const float* mask, int ldmask,
-                                        float* y, int ldy, const st_t16_view* y_dst,
-                                        int n_split, float* y2, int ldy2, int rep,
-                                        int n_split2, int act2, const float* mask2, int ldmask2, const st_t16_view* y3_dst,
-                                        int B, int N, const st_attn_pre_job* pre, void* stream);
+int st_skinny_linear_packed_attnpre_fwd(const st_packed_linear_job* job, const st_attn_pre_job* pre, void* stream);   /* pre NULL or without s_buf: the linear alone */
 
 /* st_skinny_linear_packed_fwd (no bias / activation, natural y) whose output columns [n0, n0 + H) are dh of an LSTM cell: the pointwise
  * half of that cell's backward step (st_lstm_cell_bwd_pointwise with dh0 = those columns of y) runs in the EPILOGUE of the product
@@ -230,8 +237,7 @@ typedef struct st_lstm_pw_job {
     int dh1_slabs; long dh1_slab_stride;              /* > 1: dh1 is the first of that many slabs (dh1_slab_stride floats apart) of a K-split
                                                        * product (st_skinny_partial_attn_*): the addend is their sum, in slab order */
 } st_lstm_pw_job;
-int st_skinny_linear_packed_lstm_bwd_fwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                         const st_lstm_pw_job* job, void* stream);
+int st_skinny_linear_packed_lstm_bwd_fwd(const st_packed_product* p, const st_lstm_pw_job* job, void* stream);
 
 /* The fin part for LONG texts: every utterance split over `parts` (2..64) ranges of positions -- local softmax statistics and an
  * un-normalised partial context per range (flash-decoding style), then a combine launch.  S and the memory rows are read once in
@@ -259,8 +265,6 @@ typedef struct st_attn_fin_job {
 } st_attn_fin_job;
 int st_attn_fin_fwd(const float* pq, const st_attn_fin_job* job, int B, void* stream);   /* the fin part as a launch of its own, pq (B, A) */
 int st_attn_fin_split_fwd(const float* pq, const st_attn_fin_job* job, float* workspace, int B, void* stream);
-int st_query_attn_fin_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
-                          const st_attn_fin_job* job, int B, void* stream);
 /* A partial product part (B, N) = x[:, kb0 .. kb0 + KB) W[:, kb0 .. kb0 + KB)^T over a k-block range of a P16 matrix (w_kbs k-blocks per row
  * tile; LSTM row order when the matrix is a cell's) and of a T16 activation buffer (x.kb0 = the range's first k-block in it): two row tiles
  * and both batch tiles per workgroup (16 < B <= 32, N % 32 == 0), N / 32 workgroups. */
@@ -270,11 +274,11 @@ typedef struct st_partial_product_job {
     int N;
     float* part;
 } st_partial_product_job;
-/* st_query_attn_fin_fwd with such a job beside it in the same launch (every workgroup on a compute unit of its own: (A / 16) ceil(B / 16) +
- * B * parts + N / 32 <= compute units).  The decode step's use: the part of nn.LSTMCell's gate product (ref: src/module.py:275-280) whose
- * operands do not depend on the attention of the step runs WHILE the attention runs. */
-int st_query_attn_fin_part_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
-                               const st_attn_fin_job* job, int B, const st_partial_product_job* part, void* stream);
+/* The query projection + fin launch; `part` (may be NULL) is such a job beside it in the same launch (every workgroup on a compute unit of
+ * its own: (A / 16) ceil(B / 16) + B * parts + N / 32 <= compute units).  The decode step's use: the part of nn.LSTMCell's gate product
+ * (ref: src/module.py:275-280) whose operands do not depend on the attention of the step runs WHILE the attention runs. */
+int st_query_attn_fin_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
+                          const st_attn_fin_job* job, int B, const st_partial_product_job* part, void* stream);
 /* ... and the job as a launch of its own: what the decode loop issues in its two-launch pq / fin form (a starved hand-off degrades to it),
  * so that both forms compute the same arithmetic bit for bit */
 int st_partial_product_fwd(const st_partial_product_job* job, int B, void* stream);
@@ -765,7 +769,7 @@ typedef struct st_decoder_io {
     float* gate_part;                  /* optional (B, 4 D) scratch: in the one-launch pq + fin form (pq_granules) with 16 < B <= 32 the decoder
                                         * cell's gate products over operands that are known BEFORE the attention runs -- the tail of the cell's
                                         * reduction [ctx | AdaIN(h_q(t)) | h_d(t-1)] from column gate_part_k on -- ride beside the pq / fin launch
-                                        * on compute units it leaves idle (st_query_attn_fin_part_fwd); the cell launch then reduces the first
+                                        * on compute units it leaves idle (st_query_attn_fin_fwd with `part`); the cell launch then reduces the first
                                         * gate_part_k columns and adds this slab (st_lstm_cell_packed_job.part).  fp32 re-association only.
                                         * NULL = off */
     int gate_part_k;                   /* the cell's own share of the reduction: a multiple of 16 in [kb16(E) * 16, K_d); 0 = the callee's rule
@@ -929,14 +933,13 @@ typedef struct st_attn_hist_job {
     float* dloc_t; float* hist_t; float* dhist; float* dcum;
     int B, L, F, K;
 } st_attn_hist_job;
-/* two st_skinny_linear_packed_lstm_bwd_fwd of one shape in one launch (arrays of two; y2 or its entries may be NULL) */
-int st_skinny_linear_packed_lstm_bwd_pair_fwd(const float* const* packed_w2, const st_t16_view* x2, int K, float* const* y2, int ldy,
-                                              int B, int N, const st_lstm_pw_job* job2, void* stream);
+/* two st_skinny_linear_packed_lstm_bwd_fwd of one shape in one launch (arrays of two; p2[d].y may be NULL: the product is only consumed
+ * by its epilogue); products whose K, B, N or ldy differ are refused */
+int st_skinny_linear_packed_lstm_bwd_pair_fwd(const st_packed_product* p2, const st_lstm_pw_job* job2, void* stream);
 /* st_skinny_linear_packed_lstm_bwd_fwd + st_attn_step_bwd in ONE launch: the attention backward of BPTT step t beside the decoder cell's
  * backward product of step t-1 (the decoder cell's recurrence does not depend on the attention / query chain of the same step).  job may
  * be NULL (the plain product); ab->s_in must be given (the forward kept S) */
-int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                              const st_lstm_pw_job* job, const st_attn_bwd_job* ab, void* stream);
+int st_skinny_linear_packed_lstm_bwd_attn_bwd(const st_packed_product* p, const st_lstm_pw_job* job, const st_attn_bwd_job* ab, void* stream);
 /* 1 when the attention backward's 48-position block (+ a hosting product's 8 KB) fits the LDS for these dims: what parts > 1 needs */
 int st_attn_bwd_wide_fits(int L, int A, int E, int F, int K);
 /* The launch an attention-step backward takes, from shapes alone (touches no memory): hosted = 0 st_attn_step_bwd (parts must be
@@ -972,13 +975,11 @@ int st_skinny_partial_attn_hist(const float* packed_w, const st_t16_view* x, int
                                 const st_attn_hist_job* hist, void* stream);
 /* st_skinny_linear_packed_lstm_bwd_fwd with an st_attn_hist_job and an st_partial_sum_job beside it in the same launch (the BPTT step's
  * W_q^T dpq product, which occupies half of the compute units); hist may be NULL */
-int st_skinny_linear_packed_lstm_bwd_attn_hist_sum(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                   const st_lstm_pw_job* job, const st_attn_hist_job* hist,
+int st_skinny_linear_packed_lstm_bwd_attn_hist_sum(const st_packed_product* p, const st_lstm_pw_job* job, const st_attn_hist_job* hist,
                                                    const st_partial_sum_job* sum, void* stream);
 /* y = x W^T (no epilogue) with an st_attn_hist_job beside it: the BPTT step's dgates_q . [W_ih | W_hh] launch leaves 32 compute units idle
  * for 9 us -- the history part of the step's split attention backward hides there completely */
-int st_skinny_linear_packed_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                      const st_attn_hist_job* hist, void* stream);
+int st_skinny_linear_packed_attn_hist(const st_packed_product* p, const st_attn_hist_job* hist, void* stream);
 int st_decoder_backward(const st_decoder_bwd_weights* w, const st_decoder_dims* d, const st_decoder_bwd_io* io, void* stream);
 /* The two loops of a training step (st_decoder_forward with defer_proj, st_decoder_backward) are called with bit-identical arguments step after
  * step once the caller's allocator repeats its addresses: at the second sighting of an argument set the loop's launches are captured into a

@@ -177,6 +177,16 @@ class StPartialProductJob(C.Structure):
                 ('part', C.c_void_p)]
 
 
+class StPackedProduct(C.Structure):
+    _fields_ = [('packed_w', C.c_void_p), ('x', StT16View), ('K', C.c_int), ('y', C.c_void_p), ('ldy', C.c_int), ('B', C.c_int), ('N', C.c_int)]
+
+
+class StPackedLinearJob(C.Structure):
+    _fields_ = [('p', StPackedProduct), ('bias', C.c_void_p), ('act', C.c_int), ('mask', C.c_void_p), ('ldmask', C.c_int), ('y_dst', StT16View),
+                ('n_split', C.c_int), ('y2', C.c_void_p), ('ldy2', C.c_int), ('rep', C.c_int),
+                ('n_split2', C.c_int), ('act2', C.c_int), ('mask2', C.c_void_p), ('ldmask2', C.c_int), ('y3_dst', StT16View)]
+
+
 P, I, F, Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/semitts.h
@@ -248,16 +258,13 @@ SIGNATURES = {
     'st_untile_rows': [C.POINTER(StT16View), P, I, I, I, P],
     'st_lstm_cell_packed_fwd': [C.POINTER(StLstmCellPackedJob), P],
     'st_lstm_cell_packed_pair_fwd': [C.POINTER(StLstmCellPackedJob), C.POINTER(StLstmCellPackedJob), P],
-    'st_skinny_linear_packed_fwd': [P, C.POINTER(StT16View), I, P, I, P, I, P, I, C.POINTER(StT16View), I, P, I, I,
-                                    I, I, P, I, C.POINTER(StT16View), I, I, P],
-    'st_skinny_linear_packed_attnpre_fwd': [P, C.POINTER(StT16View), I, P, I, P, I, P, I, C.POINTER(StT16View), I, P, I, I,
-                                            I, I, P, I, C.POINTER(StT16View), I, I, C.POINTER(StAttnPreJob), P],
+    'st_skinny_linear_packed_fwd': [C.POINTER(StPackedLinearJob), P],
+    'st_skinny_linear_packed_attnpre_fwd': [C.POINTER(StPackedLinearJob), C.POINTER(StAttnPreJob), P],
     'st_attn_pre_fwd': [C.POINTER(StAttnPreJob), I, P],
     'st_attn_fin_fwd': [P, C.POINTER(StAttnFinJob), I, P],
     'st_attn_fin_split_workspace_floats': [I, I, I],
     'st_attn_fin_split_fwd': [P, C.POINTER(StAttnFinJob), P, I, P],
-    'st_query_attn_fin_fwd': [P, C.POINTER(StT16View), I, P, C.c_uint, C.POINTER(StAttnFinJob), I, P],
-    'st_query_attn_fin_part_fwd': [P, C.POINTER(StT16View), I, P, C.c_uint, C.POINTER(StAttnFinJob), I, C.POINTER(StPartialProductJob), P],
+    'st_query_attn_fin_fwd': [P, C.POINTER(StT16View), I, P, C.c_uint, C.POINTER(StAttnFinJob), I, C.POINTER(StPartialProductJob), P],
     'st_partial_product_fwd': [C.POINTER(StPartialProductJob), I, P],
     'st_layer_norm_fwd': [P, I, P, P, F, P, I, P, P, I, I, P],
     'st_layer_norm_bwd': [P, I, P, I, P, P, P, P, I, P, I, I, P],
@@ -276,18 +283,18 @@ SIGNATURES = {
     'st_decoder_forward': [C.POINTER(StDecoderWeights), C.POINTER(StDecoderDims), C.POINTER(StDecoderIO), P],
     'st_decoder_fwd_forms': [C.POINTER(StDecoderDims), C.POINTER(StDecoderIO), I, I],
     'st_attn_step_bwd': [C.POINTER(StAttnBwdJob), P],
-    'st_skinny_linear_packed_lstm_bwd_fwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), P],
-    'st_skinny_linear_packed_lstm_bwd_attn_bwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), C.POINTER(StAttnBwdJob), P],
+    'st_skinny_linear_packed_lstm_bwd_fwd': [C.POINTER(StPackedProduct), C.POINTER(StLstmPwJob), P],
+    'st_skinny_linear_packed_lstm_bwd_attn_bwd': [C.POINTER(StPackedProduct), C.POINTER(StLstmPwJob), C.POINTER(StAttnBwdJob), P],
     'st_attn_bwd_wide_fits': [I, I, I, I, I],
     'st_attn_bwd_variant': [I, I, I, I, I, I, I, I, I, I, P],
-    'st_skinny_linear_packed_attn_hist': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StAttnHistJob), P],
+    'st_skinny_linear_packed_attn_hist': [C.POINTER(StPackedProduct), C.POINTER(StAttnHistJob), P],
     'st_skinny_partial_attn_hist': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StAttnHistJob), P],
     'st_decoder_bwd_forms': [C.POINTER(StDecoderDims), C.POINTER(StDecoderBwdIO)],
     'st_decoder_bwd_fuse_dims': [C.POINTER(StDecoderDims)],
     'st_loop_graph_stats': [P, P],
     'st_loop_graphs_enable': [I],
     'st_skinny_partial_attn_bwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StAttnBwdJob), P],
-    'st_skinny_linear_packed_lstm_bwd_attn_hist_sum': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StLstmPwJob), C.POINTER(StAttnHistJob),
+    'st_skinny_linear_packed_lstm_bwd_attn_hist_sum': [C.POINTER(StPackedProduct), C.POINTER(StLstmPwJob), C.POINTER(StAttnHistJob),
                                                        C.POINTER(StPartialSumJob), P],
     'st_lstm_seq2_fwd': [C.POINTER(P), C.POINTER(P), C.POINTER(P), P, I, C.POINTER(I), P, C.POINTER(P), C.POINTER(P), I, I, I, P],
     'st_lstm_seq2_persist_supported': [I, I, I, I, I, I],
@@ -297,7 +304,7 @@ SIGNATURES = {
     'st_lstm_seq2_bwd': [P, I, C.POINTER(I), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), P, I, I, I, P],
     'st_skinny_linear_pair_fwd': [P, C.POINTER(P), I, I, I, P],
     'st_lstm_seq2_bwd_packed': [P, I, C.POINTER(I), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), P, P, I, I, I, P],
-    'st_skinny_linear_packed_lstm_bwd_pair_fwd': [C.POINTER(P), C.POINTER(StT16View), I, C.POINTER(P), I, I, I, C.POINTER(StLstmPwJob), P],
+    'st_skinny_linear_packed_lstm_bwd_pair_fwd': [C.POINTER(StPackedProduct), C.POINTER(StLstmPwJob), P],
     'st_lstm_cell_pair_fwd': [P, C.POINTER(P), C.POINTER(P), I, C.POINTER(P), I, C.POINTER(P), I, C.POINTER(P), I, C.POINTER(P), I, I, P],
     'st_attn_dmem': [P, P, P, I, I, I, I, P],
     'st_decoder_backward': [C.POINTER(StDecoderBwdWeights), C.POINTER(StDecoderDims), C.POINTER(StDecoderBwdIO), P],

@@ -111,13 +111,11 @@ extern "C" int st_attn_step_bwd(const st_attn_bwd_job* job, void* stream) {
     const AbPlan pl = ab_plan(a.L, a.A, a.E, a.F, a.K, a.s_in != nullptr, 1, 0, a.B, a.B, 0, st_aligned16(a.loc_lin_w));
     ST_CHECK_ARG(pl.code >= 0, "st_attn_step_bwd: L=%d needs %zu bytes of LDS (> 160 KiB)", a.L, pl.lds);
     const size_t lds = pl.lds;
-    static size_t lds_enabled = 0;
-    if (pl.opt_in && lds > lds_enabled) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_kernel<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_kernel<true, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ab_kernel<true, AB_LBLK_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_enabled = lds;
-    }
+    static size_t lds_enabled[3] = {0, 0, 0};      // (all three kernels are raised together, whichever of them this call launches)
+    int rc = st_lds_opt_in(reinterpret_cast<const void*>(ab_kernel<false, 16>), lds, pl.opt_in, lds_enabled[0]);
+    if (!rc) rc = st_lds_opt_in(reinterpret_cast<const void*>(ab_kernel<true, 16>), lds, pl.opt_in, lds_enabled[1]);
+    if (!rc) rc = st_lds_opt_in(reinterpret_cast<const void*>(ab_kernel<true, AB_LBLK_MAX>), lds, pl.opt_in, lds_enabled[2]);
+    if (rc) return rc;
     if (pl.wide) hipLaunchKernelGGL((ab_kernel<true, AB_LBLK_MAX>), dim3(a.B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
     else if (a.s_in) hipLaunchKernelGGL((ab_kernel<true, 16>), dim3(a.B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((ab_kernel<false, 16>), dim3(a.B), dim3(AB_THREADS), lds, (hipStream_t)stream, a);

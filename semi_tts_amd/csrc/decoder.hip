@@ -114,8 +114,8 @@ int prenet_own(const st_decoder_weights* w, const st_decoder_dims* d, const st_d
         const int b0 = io->step_src[t] == -1 ? 0 : io->Bt;
         for (int l = 0; l < 2; ++l) {
             float* y = io->pre_nat_tape ? io->pre_nat_tape + ((size_t)t * 2 + l) * BP : io->pre_nat;
-            rc = st_skinny_linear_packed_fwd(pw[l], srcs[l], Ks[l], nullptr, ST_ACT_NONE, nullptr, 0, y, d->P, nullptr, 0,
-                                             nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, d->B, d->P, stream);
+            const st_packed_linear_job lj = st_plain_linear_job(pw[l], *srcs[l], Ks[l], y, d->P, d->B, d->P);
+            rc = st_skinny_linear_packed_fwd(&lj, stream);
             if (rc) return rc;
             rc = st_prenet_norm_fwd(y, d->P, d->prenet_norm, w->pre_norm_w[l], w->pre_norm_b[l], w->pre_norm_rm[l], w->pre_norm_rv[l],
                                     w->pre_norm_nbt[l], w->pre_norm_eps, w->pre_norm_momentum, ms[l], d->P, dsts[l], b0, d->B, d->P, stream);
@@ -123,13 +123,16 @@ int prenet_own(const st_decoder_weights* w, const st_decoder_dims* d, const st_d
         }
         return 0;
     }
-    if (!layer1_done)
-        rc = st_skinny_linear_packed_fwd(io->packed + pl.p0, &mel, 16 * kb16(in_dim), nullptr, ST_ACT_RELU, m1, d->P,
-                                         nullptr, 0, &pre1, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, d->B, d->P, stream);
+    // a prenet layer: relu(x W^T) * mask -> a T16 destination only
+    auto layer = [&](const float* packed_w, const st_t16_view& x, int K, const float* mask, const st_t16_view& dst) {
+        st_packed_linear_job lj = st_plain_linear_job(packed_w, x, K, nullptr, 0, d->B, d->P);
+        lj.act = ST_ACT_RELU; lj.mask = mask; lj.ldmask = d->P; lj.y_dst = dst;
+        return st_skinny_linear_packed_fwd(&lj, stream);
+    };
+    if (!layer1_done) rc = layer(io->packed + pl.p0, mel, 16 * kb16(in_dim), m1, pre1);
     if (rc) return rc;
     st_t16_view next = {io->xq_tape + (size_t)(t + 1) * sv.q_floats, sv.q_kbs, 0};
-    return st_skinny_linear_packed_fwd(io->packed + pl.p1, &pre1, 16 * kb16(d->P), nullptr, ST_ACT_RELU, m2, d->P,
-                                       nullptr, 0, &next, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, d->B, d->P, stream);
+    return layer(io->packed + pl.p1, pre1, 16 * kb16(d->P), m2, next);
 }
 
 }  // namespace
@@ -451,15 +454,13 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
 
         // 2. processed query (the merged forms issue it with step 3)    ref: :380
         if (f.attn != ATTN_PQ_FIN && f.attn != ATTN_PQ_RNG && !ST_SKIPPED(1)) {
+            const st_packed_linear_job pq = st_plain_linear_job(io->packed + pl.pq, hq_dst, 16 * kb16(Q), io->pq_buf, A, B, A);
             if (f.pre_in_pq && t > 0) {   // attention pre part of THIS step rides along (needs only the weights of step t-1)
                 st_attn_pre_job job = pre_job(t, f.pq_pre_parts);
                 if (f.prod == PROD_PQ_PRE) job.part = &pj_d;      // ... and the tail of the decoder cell's gate product of this step
-                rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), nullptr, ST_ACT_NONE, nullptr, 0,
-                                                         io->pq_buf, A, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, A,
-                                                         &job, stream);
+                rc = st_skinny_linear_packed_attnpre_fwd(&pq, &job, stream);
             } else
-                rc = st_skinny_linear_packed_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), nullptr, ST_ACT_NONE, nullptr, 0,
-                                                 io->pq_buf, A, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, A, stream);
+                rc = st_skinny_linear_packed_fwd(&pq, stream);
             if (rc) return rc;
         }
 
@@ -508,9 +509,8 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         case ATTN_PQ_FIN:       // 2 + 3 as one launch: the fin workgroups wait for pq inside the launch (granule hand-off)
             if (!(ST_SKIPPED(1) || ST_SKIPPED(2))) {
                 const st_attn_fin_job fj = fin_job(f.fin_parts);
-                rc = f.prod == PROD_PQ_FIN
-                         ? st_query_attn_fin_part_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, (unsigned)(t + 1), &fj, B, &pj_d, stream)
-                         : st_query_attn_fin_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, (unsigned)(t + 1), &fj, B, stream);
+                rc = st_query_attn_fin_fwd(io->packed + pl.pq, &hq_dst, 16 * kb16(Q), io->pq_granules, (unsigned)(t + 1), &fj, B,
+                                           f.prod == PROD_PQ_FIN ? &pj_d : nullptr, stream);
             }
             break;
         case ATTN_PQ_RNG:       // 2 + 3 + combine as one launch (long texts)
@@ -547,13 +547,17 @@ static int decoder_forward_issue(const st_decoder_weights* w, const st_decoder_d
         const bool split_attn = f.attn != ATTN_WHOLE;
         const st_attn_pre_job job = pre_job(t + 1, io->attn_pre_parts);
         if (!ST_SKIPPED(4)) {
-            rc = st_skinny_linear_packed_attnpre_fwd(io->packed + pl.pg, &xo_v, ST_SKIPPED(7) ? Ko / 4 : Ko, w->projgate_b, ST_ACT_NONE, nullptr, 0,
-                                                     io->mel_out + (size_t)t * in_dim, (int)ldmel, fuse ? nullptr : &mel_dst, in_dim,
-                                                     io->stop_out + (size_t)t * d->r, steps * d->r, d->r,
-                                                     fuse ? in_dim + 1 : 0, ST_ACT_RELU,
-                                                     io->prenet_mask ? io->prenet_mask + (size_t)t * 2 * B * P : nullptr, P,
-                                                     fuse ? &pre1_dst : nullptr, B, in_dim + 1 + (fuse ? P : 0),
-                                                     split_attn && t + 1 < steps && !ST_SKIPPED(6) ? &job : nullptr, stream);
+            // mel (B, in_dim) natural (+ T16 for the prenet launches when they follow), the stop logit repeated per frame, and, fused, prenet
+            // layer 1 of the next input as the third range
+            st_packed_linear_job pg = st_plain_linear_job(io->packed + pl.pg, xo_v, ST_SKIPPED(7) ? Ko / 4 : Ko, io->mel_out + (size_t)t * in_dim,
+                                                          (int)ldmel, B, in_dim + 1 + (fuse ? P : 0));
+            pg.bias = w->projgate_b;
+            if (!fuse) pg.y_dst = mel_dst;
+            pg.n_split = in_dim; pg.y2 = io->stop_out + (size_t)t * d->r; pg.ldy2 = steps * d->r; pg.rep = d->r;
+            pg.n_split2 = fuse ? in_dim + 1 : 0; pg.act2 = ST_ACT_RELU;
+            pg.mask2 = io->prenet_mask ? io->prenet_mask + (size_t)t * 2 * B * P : nullptr; pg.ldmask2 = P;
+            if (fuse) pg.y3_dst = pre1_dst;
+            rc = st_skinny_linear_packed_attnpre_fwd(&pg, split_attn && t + 1 < steps && !ST_SKIPPED(6) ? &job : nullptr, stream);
             if (rc) return rc;
         }
 

@@ -196,10 +196,10 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
             st_t16_view x_v = {dgd_buf[t & 1], kbd, 0};
             st_lstm_pw_job j;
             if (t > 0) pw_d(t, j);
-            if (ab) return st_skinny_linear_packed_lstm_bwd_attn_bwd(w->d_w_cat_t_p16, &x_v, 4 * D, dxd, XD, B, XD, t > 0 ? &j : nullptr, ab, stream);
-            if (t > 0) return st_skinny_linear_packed_lstm_bwd_fwd(w->d_w_cat_t_p16, &x_v, 4 * D, dxd, XD, B, XD, &j, stream);
-            return st_skinny_linear_packed_fwd(w->d_w_cat_t_p16, &x_v, 4 * D, nullptr, ST_ACT_NONE, nullptr, 0, dxd, XD, nullptr,
-                                               0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, XD, stream);
+            const st_packed_linear_job lj = st_plain_linear_job(w->d_w_cat_t_p16, x_v, 4 * D, dxd, XD, B, XD);
+            if (ab) return st_skinny_linear_packed_lstm_bwd_attn_bwd(&lj.p, t > 0 ? &j : nullptr, ab, stream);
+            if (t > 0) return st_skinny_linear_packed_lstm_bwd_fwd(&lj.p, &j, stream);
+            return st_skinny_linear_packed_fwd(&lj, stream);
         };
         // the decoder cell's recurrence (dgates_d(t-1) from dgates_d(t) . W_hh_d and the output gradients) does not touch the attention /
         // query chain of step t: with overlap_attn its product runs ONE STEP AHEAD, beside the attention backward of step t
@@ -245,6 +245,7 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
                 j.c = io->cq_tape + (size_t)(t + 1) * BQ; j.ldc = Q; j.c_prev = io->cq_tape + (size_t)t * BQ; j.ldcp = Q;
                 j.dc = io->dcq; j.dgates = io->dgq + (size_t)t * Bp * 4 * Q; j.ldg = 4 * Q;
                 j.dgates_t16 = dgq_v;
+                const st_packed_product dhq = {w->attn_query_w_t_p16, dpq_v, A, io->dhq_attn, Q, B, Q};
                 if (split && partial) {
                     // ... with the slabs of launch 1's partial product beside it: dxd_{t-1} + the decoder cell's pointwise step of t-2
                     st_lstm_pw_job jd;
@@ -252,11 +253,12 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
                     memset(&sj, 0, sizeof(sj));
                     sj.part = io->dxd_part; sj.S = dsplits; sj.N = XD; sj.y = io->dxd + (size_t)(t - 1) * Bp * XD; sj.ldy = XD;
                     if (t - 1 > 0) { pw_d(t - 1, jd); sj.pw = &jd; }
-                    rc = st_skinny_linear_packed_lstm_bwd_attn_hist_sum(w->attn_query_w_t_p16, &dpq_v, A, io->dhq_attn, Q, B, Q, &j, nullptr, &sj, stream);
-                } else rc = st_skinny_linear_packed_lstm_bwd_fwd(w->attn_query_w_t_p16, &dpq_v, A, io->dhq_attn, Q, B, Q, &j, stream);
+                    rc = st_skinny_linear_packed_lstm_bwd_attn_hist_sum(&dhq, &j, nullptr, &sj, stream);
+                } else rc = st_skinny_linear_packed_lstm_bwd_fwd(&dhq, &j, stream);
                 if (rc) return rc;
             }
             // f. gradient w.r.t. [dec_in_t | ctx_{t-1} | h_q_{t-1}]
+            const st_packed_linear_job dxq_job = st_plain_linear_job(w->q_w_cat_t_p16, dgq_v, 4 * Q, dxq, XQ, B, XQ);
             if (split) {
                 // ... with what the split attention backward of this step left behind (the sum of its partial dloc, the history tape, the
                 // conv-transpose to dhist, the carried dcum) on the compute units this product leaves idle
@@ -267,11 +269,10 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
                 hj.dloc_t = ab.dloc_t; hj.hist_t = ab.hist_t; hj.dhist = dhist_cur; hj.dcum = io->dcum;
                 hj.B = B; hj.L = L; hj.F = d->F; hj.K = d->K;
                 if (partial_q) rc = st_skinny_partial_attn_hist(w->q_w_cat_t_p16, &dgq_v, 4 * Q, io->dxq_part + (size_t)t * qsplits * qslab, qsplits, B, XQ, &hj, stream);
-                else rc = st_skinny_linear_packed_attn_hist(w->q_w_cat_t_p16, &dgq_v, 4 * Q, dxq, XQ, B, XQ, &hj, stream);
+                else rc = st_skinny_linear_packed_attn_hist(&dxq_job.p, &hj, stream);
                 if (rc) return rc;
             } else if (t > 0 || io->need_dxq0) {
-                rc = st_skinny_linear_packed_fwd(w->q_w_cat_t_p16, &dgq_v, 4 * Q, nullptr, ST_ACT_NONE, nullptr, 0, dxq, XQ, nullptr,
-                                                 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, XQ, stream);
+                rc = st_skinny_linear_packed_fwd(&dxq_job, stream);
                 if (rc) return rc;
             }
         }
@@ -342,8 +343,8 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
         // b. gradient w.r.t. [ctx_t | adapted h_q_t | h_d_{t-1}]
         st_seg seg;
         if (packed) {   // W^T streamed in MFMA lane order (P16), dgates in T16
-            rc = st_skinny_linear_packed_fwd(w->d_w_cat_t_p16, &dgd_v, 4 * D, nullptr, ST_ACT_NONE, nullptr, 0, dxd, XD, nullptr,
-                                             0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, XD, stream);
+            const st_packed_linear_job lj = st_plain_linear_job(w->d_w_cat_t_p16, dgd_v, 4 * D, dxd, XD, B, XD);
+            rc = st_skinny_linear_packed_fwd(&lj, stream);
         } else {
             seg.x = dgd; seg.ldx = 4 * D; seg.w = w->d_w_cat_t; seg.ldw = 4 * D; seg.k = 4 * D;
             rc = st_skinny_linear_fwd(&seg, 1, nullptr, ST_ACT_NONE, nullptr, 0, dxd, XD, 0, nullptr, 0, 0, B, XD, stream);
@@ -366,8 +367,8 @@ static int decoder_backward_issue(const st_decoder_bwd_weights* w, const st_deco
         // f. gradient w.r.t. [dec_in_t | ctx_{t-1} | h_q_{t-1}]  (step 0: go frame and zero initial state, nothing to do)
         if (t > 0 || io->need_dxq0) {
             if (packed) {
-                rc = st_skinny_linear_packed_fwd(w->q_w_cat_t_p16, &dgq_v, 4 * Q, nullptr, ST_ACT_NONE, nullptr, 0, dxq, XQ, nullptr,
-                                                 0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, XQ, stream);
+                const st_packed_linear_job lj = st_plain_linear_job(w->q_w_cat_t_p16, dgq_v, 4 * Q, dxq, XQ, B, XQ);
+                rc = st_skinny_linear_packed_fwd(&lj, stream);
             } else {
                 seg.x = dgq; seg.ldx = 4 * Q; seg.w = w->q_w_cat_t; seg.ldw = 4 * Q; seg.k = 4 * Q;
                 rc = st_skinny_linear_fwd(&seg, 1, nullptr, ST_ACT_NONE, nullptr, 0, dxq, XQ, 0, nullptr, 0, 0, B, XQ, stream);

@@ -1172,10 +1172,7 @@ extern "C" int st_highway_stack_fwd(const float* x, int ldx, const float* const*
     const int LD = C + 4;
     const size_t lds = (size_t)(2 * HW_ROWS * LD + 2 * C * LD) * sizeof(float);
     static size_t lds_set = 0;
-    if (lds > 48 * 1024 && lds > lds_set) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(highway_stack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
+    if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(highway_stack_kernel), lds, lds > 48 * 1024, lds_set)) return rc;
     hipLaunchKernelGGL(highway_stack_kernel, dim3((M + HW_ROWS - 1) / HW_ROWS), dim3(256), lds, (hipStream_t)stream, a);
     ST_LAUNCH_CHECK();
     return 0;

@@ -1225,12 +1225,12 @@ extern "C" int st_lstm_seq2_bwd_packed(const float* dout, int ldd, const int* dc
         ST_LAUNCH_CHECK();
     }
     for (int s = T - 1; s >= 1; --s) {        // dh_rec(s-1) = dgates(s) . W_hh, and the pointwise backward of step s-1 in the epilogue
-        st_t16_view xv[2];
+        st_packed_product prod[2];      // dh_rec = dgates W_hh^T, consumed by the epilogue only (no y)
         st_lstm_pw_job job[2];
         for (int d = 0; d < 2; ++d) {
             const int s1 = s - 1;
             const int t = d ? T - 1 - s1 : s1, tp = d ? t + 1 : t - 1;
-            xv[d].base = buf(d, s & 1); xv[d].kb_stride = kbs; xv[d].kb0 = 0;
+            prod[d] = st_packed_product{w_hh_t_p16_2[d], st_t16_view{buf(d, s & 1), kbs, 0}, 4 * H, nullptr, H, B, H};
             memset(&job[d], 0, sizeof(st_lstm_pw_job));
             job[d].n0 = 0; job[d].H = H;
             job[d].dh1 = dout + (size_t)t * ldd + dcol2[d]; job[d].ld1 = T * ldd;
@@ -1239,7 +1239,7 @@ extern "C" int st_lstm_seq2_bwd_packed(const float* dout, int ldd, const int* dc
             job[d].dc = ws + (size_t)d * bh; job[d].dgates = dxproj2[d] + (size_t)t * 4 * H; job[d].ldg = T * 4 * H;
             job[d].dgates_t16.base = buf(d, s1 & 1); job[d].dgates_t16.kb_stride = kbs; job[d].dgates_t16.kb0 = 0;
         }
-        int rc = st_skinny_linear_packed_lstm_bwd_pair_fwd(w_hh_t_p16_2, xv, 4 * H, nullptr, H, B, H, job, stream);
+        int rc = st_skinny_linear_packed_lstm_bwd_pair_fwd(prod, job, stream);
         if (rc) return rc;
     }
     return 0;

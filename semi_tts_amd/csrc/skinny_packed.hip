@@ -203,7 +203,7 @@ struct PkArgs {
     // optional: the plain range leaves as 8-byte {value, tag = epoch} granules (B, N) for consumer workgroups of the SAME launch
     unsigned long long* gran; unsigned epoch;
     // optional (LSTM cell, 2-D tiled form): a slab (B, N) of a partial product of the SAME weight rows over the k-blocks this launch does
-    // not reduce (pk_part_body of an earlier launch, st_query_attn_fin_part_fwd), added to the gates
+    // not reduce (pk_part_body of an earlier launch, st_query_attn_fin_fwd), added to the gates
     const float* part;
 };
 
@@ -1132,35 +1132,26 @@ template <int NB>
 int pk_launch_attnpre(const PkArgs& a, int tiles, const AtArgs& t, hipStream_t st, const PkPartArgs* pp = nullptr) {
     constexpr int KW = 8, TRIP = NB == 1 ? PK_TRIP_SMALL : 2;
     const int BT = (a.B + 15) >> 4, gy = (BT + NB - 1) / NB;
-    if constexpr (NB == 1) if (pp) {       // + the workgroups of a hosted partial product (their reduction buffer lives in the dynamic LDS region)
-        const bool vec = (t.A % 4 == 0) && (t.F % 4 == 0) && st_aligned16(t.pm) && st_aligned16(t.loc_lin_w) && st_aligned16(t.s_buf);
-        const AtLds o = at_layout(t.L, t.A, t.E, t.F, t.K, 1, at_pos_per(t.L, t.pre_parts > 1 ? t.pre_parts : 1), vec && t.F == 32 && t.A % 16 == 0);
-        size_t lds = (size_t)o.total * sizeof(float);
-        if (lds < sizeof(f32x4) * KW * 4 * 64) lds = sizeof(f32x4) * KW * 4 * 64;
-        ST_CHECK_ARG(lds + sizeof(f32x4) * KW * NB * 64 <= 160 * 1024, "linear + attention-pre launch: L=%d needs too much LDS (use more parts)", t.L);
+    const bool vec = (t.A % 4 == 0) && (t.F % 4 == 0) && st_aligned16(t.pm) && st_aligned16(t.loc_lin_w) && st_aligned16(t.s_buf);
+    const AtLds o = at_layout(t.L, t.A, t.E, t.F, t.K, 1, at_pos_per(t.L, t.pre_parts > 1 ? t.pre_parts : 1), vec && t.F == 32 && t.A % 16 == 0);
+    size_t lds = (size_t)o.total * sizeof(float);
+    if (pp && lds < sizeof(f32x4) * KW * 4 * 64) lds = sizeof(f32x4) * KW * 4 * 64;      // (a hosted partial product's reduction buffer lives in the dynamic LDS region)
+    ST_CHECK_ARG(lds + sizeof(f32x4) * KW * NB * 64 <= 160 * 1024, "linear + attention-pre launch: L=%d needs too much LDS (use more parts)", t.L);
+    const int n_at = t.B * (t.pre_parts > 1 ? t.pre_parts : 1);
+    if constexpr (NB == 1) if (pp) {       // + the workgroups of a hosted partial product
         auto kern = vec ? pk_attnpre_part_kernel<NB, KW, TRIP, true> : pk_attnpre_part_kernel<NB, KW, TRIP, false>;
         static size_t configured[2] = {0, 0};
-        if (lds > 32 * 1024 && lds > configured[vec ? 1 : 0]) {
-            ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            configured[vec ? 1 : 0] = lds;
-        }
-        const int n_at = t.B * (t.pre_parts > 1 ? t.pre_parts : 1);
+        // (32 KiB rather than 48 on purpose: the kernel also has a static reduction buffer)
+        if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, lds > 32 * 1024, configured[vec ? 1 : 0])) return rc;
         hipLaunchKernelGGL(kern, dim3(tiles * gy + n_at + (pp->N >> 5)), dim3(KW * 64), lds, st, a.w, a.x, a.w_kbs, a.x_kbs,
                            a.KB, a.B, a.N, tiles, tiles * gy, t.pm, t.w_prev, t.L, a, t, n_at, *pp);
         ST_LAUNCH_CHECK();
         return 0;
     }
-    const bool vec = (t.A % 4 == 0) && (t.F % 4 == 0) && st_aligned16(t.pm) && st_aligned16(t.loc_lin_w) && st_aligned16(t.s_buf);
-    const AtLds o = at_layout(t.L, t.A, t.E, t.F, t.K, 1, at_pos_per(t.L, t.pre_parts > 1 ? t.pre_parts : 1), vec && t.F == 32 && t.A % 16 == 0);
-    const size_t lds = (size_t)o.total * sizeof(float);
-    ST_CHECK_ARG(lds + sizeof(f32x4) * KW * NB * 64 <= 160 * 1024, "linear + attention-pre launch: L=%d needs too much LDS (use more parts)", t.L);
     auto kern = vec ? pk_attnpre_kernel<NB, KW, TRIP, true> : pk_attnpre_kernel<NB, KW, TRIP, false>;
     static size_t configured[2] = {0, 0};
-    if (lds > 48 * 1024 && lds > configured[vec ? 1 : 0]) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured[vec ? 1 : 0] = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles * gy + t.B * (t.pre_parts > 1 ? t.pre_parts : 1)), dim3(KW * 64), lds, st, a.w, a.x, a.w_kbs, a.x_kbs,
+    if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, lds > 48 * 1024, configured[vec ? 1 : 0])) return rc;
+    hipLaunchKernelGGL(kern, dim3(tiles * gy + n_at), dim3(KW * 64), lds, st, a.w, a.x, a.w_kbs, a.x_kbs,
                        a.KB, a.B, a.N, tiles, tiles * gy, t.pm, t.w_prev, t.L, a, t);
     ST_LAUNCH_CHECK();
     return 0;
@@ -1432,26 +1423,42 @@ extern "C" int st_lstm_cell_packed_pair_fwd(const st_lstm_cell_packed_job* j0, c
     return 0;
 }
 
-static int pk_linear_impl(const float* packed_w, const st_t16_view* x, int K,
-                          const float* bias, int act, const float* mask, int ldmask,
-                          float* y, int ldy, const st_t16_view* y_dst,
-                          int n_split, float* y2, int ldy2, int rep,
-                          int n_split2, int act2, const float* mask2, int ldmask2,
-                          const st_t16_view* y3_dst,
-                          int B, int N, const st_attn_pre_job* pre, void* stream) {
-    ST_CHECK_ARG(n_split2 <= 0 || (y3_dst && y3_dst->base && n_split2 >= n_split), "st_skinny_linear_packed_fwd: third range");
-    ST_CHECK_ARG(B > 0 && N > 0 && (y || (y_dst && y_dst->base)), "st_skinny_linear_packed_fwd: bad arguments");
-    ST_CHECK_ARG(n_split <= 0 || (y2 && rep >= 1), "st_skinny_linear_packed_fwd: n_split without y2/rep");
-    PkArgs a;
+// the plain product y = x W^T (no bias, activation or cell epilogue of its own) of an st_packed_product as a PkArgs block; need_y: a caller
+// whose epilogue is the only consumer may leave p->y NULL
+static int pk_product_fill(PkArgs& a, const st_packed_product* p, bool need_y, const char* who) {
+    ST_CHECK_ARG(p, "%s: null product", who);
+    ST_CHECK_ARG(p->B > 0 && p->N > 0 && (p->y || !need_y) && p->ldy >= p->N, "%s: bad arguments", who);
     memset(&a, 0, sizeof(a));
-    int rc = pk_fill(a, packed_w, x, K, "st_skinny_linear_packed_fwd");
+    int rc = pk_fill(a, p->packed_w, &p->x, p->K, who);
     if (rc) return rc;
-    a.B = B; a.N = N; a.H = 0;
-    a.bias = bias; a.act = act; a.lmask = mask; a.ldmask = ldmask;
-    a.y = y; a.ldy = ldy; a.y_dst = pk_out(y_dst);
-    a.n_split = n_split; a.y2 = y2; a.ldy2 = ldy2; a.rep = rep;
-    a.n_split2 = n_split2; a.act2 = act2; a.mask2 = mask2; a.ldmask2 = ldmask2; a.y3_dst = pk_out(y3_dst);
-    const int tiles = (N + 15) / 16;
+    a.B = p->B; a.N = p->N; a.H = 0; a.act = ST_ACT_NONE;
+    a.y = p->y; a.ldy = p->ldy;
+    return 0;
+}
+
+// an st_packed_linear_job as a PkArgs block
+static int pk_linear_fill(PkArgs& a, const st_packed_linear_job* j, const char* who) {
+    ST_CHECK_ARG(j, "%s: null job", who);
+    ST_CHECK_ARG(j->n_split2 <= 0 || (j->y3_dst.base && j->n_split2 >= j->n_split), "%s: third range", who);
+    ST_CHECK_ARG(j->p.B > 0 && j->p.N > 0 && (j->p.y || j->y_dst.base), "%s: bad arguments", who);
+    ST_CHECK_ARG(j->n_split <= 0 || (j->y2 && j->rep >= 1), "%s: n_split without y2/rep", who);
+    memset(&a, 0, sizeof(a));
+    int rc = pk_fill(a, j->p.packed_w, &j->p.x, j->p.K, who);
+    if (rc) return rc;
+    a.B = j->p.B; a.N = j->p.N; a.H = 0;
+    a.bias = j->bias; a.act = j->act; a.lmask = j->mask; a.ldmask = j->ldmask;
+    a.y = j->p.y; a.ldy = j->p.ldy; a.y_dst = pk_out(&j->y_dst);
+    a.n_split = j->n_split; a.y2 = j->y2; a.ldy2 = j->ldy2; a.rep = j->rep;
+    a.n_split2 = j->n_split2; a.act2 = j->act2; a.mask2 = j->mask2; a.ldmask2 = j->ldmask2; a.y3_dst = pk_out(&j->y3_dst);
+    return 0;
+}
+
+static int pk_linear_impl(const st_packed_linear_job* job, const st_attn_pre_job* pre, void* stream) {
+    (void)hipGetLastError();
+    PkArgs a;
+    int rc = pk_linear_fill(a, job, "st_skinny_linear_packed_fwd");
+    if (rc) return rc;
+    const int B = a.B, tiles = (a.N + 15) / 16;
     if (pre && pre->s_buf) {
         AtArgs t;
         if (at_pre_fill(t, pre, B, "st_skinny_linear_packed_attnpre_fwd")) return -1;
@@ -1470,8 +1477,14 @@ static int pk_linear_impl(const float* packed_w, const st_t16_view* x, int K,
     return pk_dispatch<1>(a, tiles, (hipStream_t)stream);
 }
 
-static int query_attn_fin_impl(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
-                               const st_attn_fin_job* job, int B, const st_partial_product_job* pj, void* stream) {
+extern "C" int st_skinny_linear_packed_fwd(const st_packed_linear_job* job, void* stream) { return pk_linear_impl(job, nullptr, stream); }
+
+extern "C" int st_skinny_linear_packed_attnpre_fwd(const st_packed_linear_job* job, const st_attn_pre_job* pre, void* stream) {
+    return pk_linear_impl(job, pre, stream);
+}
+
+extern "C" int st_query_attn_fin_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
+                                     const st_attn_fin_job* job, int B, const st_partial_product_job* pj, void* stream) {
     (void)hipGetLastError();
     ST_CHECK_ARG(packed_wq && h_q && h_q->base && granules && epoch != 0 && job && B > 0, "st_query_attn_fin_fwd: bad arguments");
     const int L = job->L, A = job->A, E = job->E, parts = job->parts;
@@ -1495,45 +1508,25 @@ static int query_attn_fin_impl(const float* packed_wq, const st_t16_view* h_q, i
     size_t lds = (size_t)o.total * sizeof(float);
     constexpr int KW = 8;
     ST_CHECK_ARG(lds + sizeof(f32x4) * KW * 64 <= 160 * 1024, "st_query_attn_fin_fwd: L=%d needs too much LDS", L);
+    PkPartArgs pp;
+    int n_part = 0;
     if (pj) {       // + the workgroups of the hosted partial product, one compute unit each like everything else in this launch
-        PkPartArgs pp;
-        if (pk_part_job_fill(pp, pj, B, "st_query_attn_fin_part_fwd")) return -1;
-        const int n_part = pj->N >> 5;
-        ST_CHECK_ARG(n_lin + n_fin + n_part <= st_device_cus(), "st_query_attn_fin_part_fwd: %d + %d + %d workgroups do not fit the device at once",
+        if (pk_part_job_fill(pp, pj, B, "st_query_attn_fin_fwd")) return -1;
+        n_part = pj->N >> 5;
+        ST_CHECK_ARG(n_lin + n_fin + n_part <= st_device_cus(), "st_query_attn_fin_fwd: %d + %d + %d workgroups do not fit the device at once",
                      n_lin, n_fin, n_part);
         if (lds < sizeof(f32x4) * KW * 4 * 64) lds = sizeof(f32x4) * KW * 4 * 64;        // (the part workgroups' reduction buffer lives in the dynamic region)
-        auto kernp = pk_attnfin_part_kernel<1, KW, PK_TRIP_SMALL>;
-        static size_t configured_p = 0;
-        if (lds > 48 * 1024 && lds > configured_p) {
-            ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            configured_p = lds;
-        }
-        hipLaunchKernelGGL(kernp, dim3(n_lin + n_fin + n_part), dim3(KW * 64), lds, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N,
-                           tiles, n_lin, a, t, n_lin + n_fin, pp);
-        ST_LAUNCH_CHECK();
-        return 0;
     }
+    auto kernp = pk_attnfin_part_kernel<1, KW, PK_TRIP_SMALL>;
     auto kern = pk_attnfin_kernel<1, KW, PK_TRIP_SMALL>;
-    static size_t configured = 0;
-    if (lds > 48 * 1024 && lds > configured) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_lin + n_fin), dim3(KW * 64), lds, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N,
-                       tiles, n_lin, a, t);
+    static size_t configured[2] = {0, 0};
+    rc = st_lds_opt_in(pj ? reinterpret_cast<const void*>(kernp) : reinterpret_cast<const void*>(kern), lds, lds > 48 * 1024, configured[pj ? 1 : 0]);
+    if (rc) return rc;
+    const dim3 grid(n_lin + n_fin + n_part), block(KW * 64);
+    if (pj) hipLaunchKernelGGL(kernp, grid, block, lds, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N, tiles, n_lin, a, t, n_lin + n_fin, pp);
+    else hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N, tiles, n_lin, a, t);
     ST_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int st_query_attn_fin_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
-                                     const st_attn_fin_job* job, int B, void* stream) {
-    return query_attn_fin_impl(packed_wq, h_q, Q, granules, epoch, job, B, nullptr, stream);
-}
-
-extern "C" int st_query_attn_fin_part_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,
-                                          const st_attn_fin_job* job, int B, const st_partial_product_job* part, void* stream) {
-    ST_CHECK_ARG(part, "st_query_attn_fin_part_fwd: null partial product job");
-    return query_attn_fin_impl(packed_wq, h_q, Q, granules, epoch, job, B, part, stream);
 }
 
 // the partial product as a launch of its own (the decode loop's two-launch pq / fin form: same arithmetic, one launch more)
@@ -1606,28 +1599,6 @@ extern "C" int st_query_attn_rng_fwd(const float* packed_wq, const st_t16_view* 
     return 0;
 }
 
-extern "C" int st_skinny_linear_packed_fwd(const float* packed_w, const st_t16_view* x, int K,
-                                           const float* bias, int act, const float* mask, int ldmask,
-                                           float* y, int ldy, const st_t16_view* y_dst,
-                                           int n_split, float* y2, int ldy2, int rep,
-                                           int n_split2, int act2, const float* mask2, int ldmask2,
-                                           const st_t16_view* y3_dst,
-                                           int B, int N, void* stream) {
-    (void)hipGetLastError();
-    return pk_linear_impl(packed_w, x, K, bias, act, mask, ldmask, y, ldy, y_dst, n_split, y2, ldy2, rep,
-                          n_split2, act2, mask2, ldmask2, y3_dst, B, N, nullptr, stream);
-}
-
-// the plain product y = x W^T (no bias, activation or cell epilogue of its own) as a PkArgs block
-static int pk_plain_fill(PkArgs& a, const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N, const char* who) {
-    memset(&a, 0, sizeof(a));
-    int rc = pk_fill(a, packed_w, x, K, who);
-    if (rc) return rc;
-    a.B = B; a.N = N; a.H = 0; a.act = ST_ACT_NONE;
-    a.y = y; a.ldy = ldy;
-    return 0;
-}
-
 // the pointwise LSTM backward that rides in a product's epilogue (st_lstm_pw_job) as a PkPw block; y NULL: the product is only consumed there
 static int pk_pw_fill(PkPw& q, const st_lstm_pw_job* job, int N, int ldy, const float* y, const char* who) {
     memset(&q, 0, sizeof(q));
@@ -1668,15 +1639,15 @@ static int pk_part_fill(PkPartArgs& p, const float* packed_w, const st_t16_view*
     return 0;
 }
 
-extern "C" int st_skinny_linear_packed_lstm_bwd_fwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                    const st_lstm_pw_job* job, void* stream) {
+extern "C" int st_skinny_linear_packed_lstm_bwd_fwd(const st_packed_product* p, const st_lstm_pw_job* job, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(y && job && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_lstm_bwd_fwd: bad arguments");
     PkArgs a;
-    int rc = pk_plain_fill(a, packed_w, x, K, y, ldy, B, N, "st_skinny_linear_packed_lstm_bwd_fwd");
+    int rc = pk_product_fill(a, p, true, "st_skinny_linear_packed_lstm_bwd_fwd");
     if (rc) return rc;
+    ST_CHECK_ARG(job, "st_skinny_linear_packed_lstm_bwd_fwd: bad arguments");
+    const int B = a.B, N = a.N;
     PkPw q;
-    rc = pk_pw_fill(q, job, N, ldy, y, "st_skinny_linear_packed_lstm_bwd_fwd");
+    rc = pk_pw_fill(q, job, N, a.ldy, a.y, "st_skinny_linear_packed_lstm_bwd_fwd");
     if (rc) return rc;
     const int tiles = (N + 15) / 16, BT = (B + 15) >> 4;
     // one batch tile per workgroup, as the plain linear of these shapes runs (pk_dispatch<1>)
@@ -1686,21 +1657,22 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_fwd(const float* packed_w, const
     return 0;
 }
 
-// two st_skinny_linear_packed_lstm_bwd_fwd of the same shape in one launch (arrays of two; y2 entries may be NULL: the product is
+// two st_skinny_linear_packed_lstm_bwd_fwd of the same shape in one launch (arrays of two; p2[d].y may be NULL: the product is
 // only consumed by its epilogue): the two directions of a bidirectional LSTM layer's BPTT step
-extern "C" int st_skinny_linear_packed_lstm_bwd_pair_fwd(const float* const* packed_w2, const st_t16_view* x2, int K, float* const* y2, int ldy,
-                                                         int B, int N, const st_lstm_pw_job* job2, void* stream) {
+extern "C" int st_skinny_linear_packed_lstm_bwd_pair_fwd(const st_packed_product* p2, const st_lstm_pw_job* job2, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(packed_w2 && x2 && job2 && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_lstm_bwd_pair_fwd: bad arguments");
+    ST_CHECK_ARG(p2 && job2, "st_skinny_linear_packed_lstm_bwd_pair_fwd: bad arguments");
+    ST_CHECK_ARG(p2[0].K == p2[1].K && p2[0].B == p2[1].B && p2[0].N == p2[1].N && p2[0].ldy == p2[1].ldy,
+                 "st_skinny_linear_packed_lstm_bwd_pair_fwd: the two products differ in K, B, N or ldy");
     PkArgs a[2];
     PkPw q[2];
     for (int d = 0; d < 2; ++d) {
-        int rc = pk_plain_fill(a[d], packed_w2[d], &x2[d], K, y2 ? y2[d] : nullptr, ldy, B, N, "st_skinny_linear_packed_lstm_bwd_pair_fwd");
+        int rc = pk_product_fill(a[d], &p2[d], false, "st_skinny_linear_packed_lstm_bwd_pair_fwd");
         if (rc) return rc;
-        rc = pk_pw_fill(q[d], &job2[d], N, ldy, a[d].y, "st_skinny_linear_packed_lstm_bwd_pair_fwd");
+        rc = pk_pw_fill(q[d], &job2[d], a[d].N, a[d].ldy, a[d].y, "st_skinny_linear_packed_lstm_bwd_pair_fwd");
         if (rc) return rc;
     }
-    const int tiles = (N + 15) / 16, BT = (B + 15) >> 4;
+    const int tiles = (a[0].N + 15) / 16, BT = (a[0].B + 15) >> 4;
     hipLaunchKernelGGL((pk_pw_pair_kernel<1, 8, 2>), dim3(2 * tiles * BT), dim3(8 * 64), 0, (hipStream_t)stream, tiles * BT, tiles, a[0], q[0], a[1], q[1]);
     ST_LAUNCH_CHECK();
     return 0;
@@ -1708,17 +1680,18 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_pair_fwd(const float* const* pac
 
 // st_skinny_linear_packed_lstm_bwd_fwd (job may be NULL: the plain product) with one attention-step backward (st_attn_step_bwd's job;
 // the forward must have kept S: s_in != NULL) in the same launch
-extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                         const st_lstm_pw_job* job, const st_attn_bwd_job* ab, void* stream) {
+extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const st_packed_product* p, const st_lstm_pw_job* job, const st_attn_bwd_job* ab,
+                                                         void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(y && ab && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_lstm_bwd_attn_bwd: bad arguments");
     PkArgs a;
-    int rc = pk_plain_fill(a, packed_w, x, K, y, ldy, B, N, "st_skinny_linear_packed_lstm_bwd_attn_bwd");
+    int rc = pk_product_fill(a, p, true, "st_skinny_linear_packed_lstm_bwd_attn_bwd");
     if (rc) return rc;
+    ST_CHECK_ARG(ab, "st_skinny_linear_packed_lstm_bwd_attn_bwd: bad arguments");
+    const int B = a.B, N = a.N;
     PkPw q;
     memset(&q, 0, sizeof(q));
     if (job) {
-        rc = pk_pw_fill(q, job, N, ldy, y, "st_skinny_linear_packed_lstm_bwd_attn_bwd");
+        rc = pk_pw_fill(q, job, N, a.ldy, a.y, "st_skinny_linear_packed_lstm_bwd_attn_bwd");
         if (rc) return rc;
     }      // (no job: H = 0, no column belongs to a cell -- the plain product)
     AbArgs t;
@@ -1739,9 +1712,11 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
     if (pl.kernel == AB_K_FALLBACK) {
         // a text so long that the attention backward needs (nearly) all the LDS of a compute unit for itself: the two launches one after
         // the other (they are independent: any order)
-        if (job) rc = st_skinny_linear_packed_lstm_bwd_fwd(packed_w, x, K, y, ldy, B, N, job, stream);
-        else rc = st_skinny_linear_packed_fwd(packed_w, x, K, nullptr, ST_ACT_NONE, nullptr, 0, y, ldy, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0,
-                                              nullptr, B, N, stream);
+        if (job) rc = st_skinny_linear_packed_lstm_bwd_fwd(p, job, stream);
+        else {
+            const st_packed_linear_job plain = st_plain_linear_job(p->packed_w, p->x, p->K, p->y, p->ldy, B, N);
+            rc = st_skinny_linear_packed_fwd(&plain, stream);
+        }
         if (rc) return rc;
         st_attn_bwd_job whole = *ab;        // (the two-launch fallback has always run the whole step per workgroup: ab->parts is ignored)
         whole.parts = 0; whole.dloc_part = nullptr;
@@ -1753,10 +1728,7 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
         // workgroups + 2 B attention workgroups <= 256: one round, a compute unit each
         auto k2 = pk_pw_ab_kernel<2, 8, 2, AB_LBLK_MAX, 2>;
         static size_t lds_nb2 = 0;
-        if (pl.opt_in && lds > lds_nb2) {
-            ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_nb2 = lds;
-        }
+        if ((rc = st_lds_opt_in(reinterpret_cast<const void*>(k2), lds, pl.opt_in, lds_nb2))) return rc;
         hipLaunchKernelGGL(k2, dim3(2 * t.B + tiles), dim3(8 * 64), lds, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N, tiles,
                            2 * t.B, a, q, t);
         ST_LAUNCH_CHECK();
@@ -1765,10 +1737,7 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
     if (pl.kernel == AB_K_DUAL) {
         auto kd = pk_pw_ab_dual_kernel<8, 2, AB_LBLK_MAX, 2>;
         static size_t lds_dual = 0;
-        if (pl.opt_in && lds > lds_dual) {
-            ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_dual = lds;
-        }
+        if ((rc = st_lds_opt_in(reinterpret_cast<const void*>(kd), lds, pl.opt_in, lds_dual))) return rc;
         hipLaunchKernelGGL(kd, dim3(2 * t.B + tiles), dim3(2 * 8 * 64), lds, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N,
                            2 * t.B, a, q, t, st_exp_flag());
         ST_LAUNCH_CHECK();
@@ -1779,10 +1748,7 @@ extern "C" int st_skinny_linear_packed_lstm_bwd_attn_bwd(const float* packed_w, 
                 : wide ? pk_pw_ab_kernel<1, 8, 2, AB_LBLK_MAX, 1> : pk_pw_ab_kernel<1, 8, 2, 16, 1>;
     static size_t lds_set[4] = {0, 0, 0, 0};
     const int ki = parts == 4 ? 3 : parts == 2 ? 2 : wide ? 1 : 0;
-    if (pl.opt_in && lds > lds_set[ki]) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set[ki] = lds;
-    }
+    if ((rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, pl.opt_in, lds_set[ki]))) return rc;
     hipLaunchKernelGGL(kern, dim3(parts * t.B + tiles * BT), dim3(8 * 64), lds, (hipStream_t)stream, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N, tiles,
                        parts * t.B, a, q, t);
     ST_LAUNCH_CHECK();
@@ -1803,17 +1769,18 @@ static int pk_sum_fill(PkSumArgs& sa, const st_partial_sum_job* sj, int B, const
 
 // a product (with the pointwise LSTM backward of `job` in its epilogue, or plain) with the history part of a split attention backward
 // (st_attn_hist_job) and / or the sum of a K-split partial product (st_partial_sum_job) in the same launch
-static int pk_hist_sum_impl(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                            const st_lstm_pw_job* job, const st_attn_hist_job* hj, const st_partial_sum_job* sj, void* stream) {
+static int pk_hist_sum_impl(const st_packed_product* p, const st_lstm_pw_job* job, const st_attn_hist_job* hj, const st_partial_sum_job* sj,
+                            void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(y && (hj || sj) && B > 0 && N > 0 && ldy >= N, "st_skinny_linear_packed_*_attn_hist: bad arguments");
     PkArgs a;
-    int rc = pk_plain_fill(a, packed_w, x, K, y, ldy, B, N, "st_skinny_linear_packed_*_attn_hist");
+    int rc = pk_product_fill(a, p, true, "st_skinny_linear_packed_*_attn_hist");
     if (rc) return rc;
+    ST_CHECK_ARG(hj || sj, "st_skinny_linear_packed_*_attn_hist: bad arguments");
+    const int B = a.B, N = a.N;
     PkPw q;
     memset(&q, 0, sizeof(q));
     if (job) {
-        rc = pk_pw_fill(q, job, N, ldy, y, "st_skinny_linear_packed_lstm_bwd_attn_hist_sum");
+        rc = pk_pw_fill(q, job, N, a.ldy, a.y, "st_skinny_linear_packed_lstm_bwd_attn_hist_sum");
         if (rc) return rc;
     }
     AbHistArgs h;
@@ -1828,11 +1795,7 @@ static int pk_hist_sum_impl(const float* packed_w, const st_t16_view* x, int K, 
     ST_CHECK_ARG(lds + red_bytes <= 160 * 1024, "st_skinny_linear_packed_*_attn_hist: L=%d needs %zu bytes of LDS", h.L, lds);
     auto kern = job ? pk_pw_hist_kernel<2, 1, 8, 2> : pk_pw_hist_kernel<1, 1, 8, 2>;
     static size_t lds_sets[2] = {0, 0};
-    size_t& lds_set = lds_sets[job ? 1 : 0];
-    if (lds > 48 * 1024 && lds > lds_set) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
+    if ((rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, lds > 48 * 1024, lds_sets[job ? 1 : 0]))) return rc;
     PkSumArgs sa;
     memset(&sa, 0, sizeof(sa));
     int n_sum = 0;
@@ -1852,18 +1815,16 @@ static int pk_hist_sum_impl(const float* packed_w, const st_t16_view* x, int K, 
 // st_skinny_linear_packed_lstm_bwd_fwd with the sum of a K-split partial product (st_partial_sum_job: the slabs st_skinny_partial_attn_bwd
 // wrote in the launch before) and the history part of a split attention backward; hj may be NULL (it can ride in another launch:
 // st_skinny_linear_packed_attn_hist)
-extern "C" int st_skinny_linear_packed_lstm_bwd_attn_hist_sum(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                              const st_lstm_pw_job* job, const st_attn_hist_job* hj,
+extern "C" int st_skinny_linear_packed_lstm_bwd_attn_hist_sum(const st_packed_product* p, const st_lstm_pw_job* job, const st_attn_hist_job* hj,
                                                               const st_partial_sum_job* sj, void* stream) {
     ST_CHECK_ARG(job && sj, "st_skinny_linear_packed_lstm_bwd_attn_hist_sum: null job");
-    return pk_hist_sum_impl(packed_w, x, K, y, ldy, B, N, job, hj, sj, stream);
+    return pk_hist_sum_impl(p, job, hj, sj, stream);
 }
 
 // the plain product y = x W^T (st_skinny_linear_packed_fwd without epilogue) with an st_attn_hist_job beside it
-extern "C" int st_skinny_linear_packed_attn_hist(const float* packed_w, const st_t16_view* x, int K, float* y, int ldy, int B, int N,
-                                                 const st_attn_hist_job* hj, void* stream) {
+extern "C" int st_skinny_linear_packed_attn_hist(const st_packed_product* p, const st_attn_hist_job* hj, void* stream) {
     ST_CHECK_ARG(hj, "st_skinny_linear_packed_attn_hist: null history job");
-    return pk_hist_sum_impl(packed_w, x, K, y, ldy, B, N, nullptr, hj, nullptr, stream);
+    return pk_hist_sum_impl(p, nullptr, hj, nullptr, stream);
 }
 
 // st_skinny_partial_attn_bwd's product with an st_attn_hist_job beside it instead of the attention backward
@@ -1879,10 +1840,8 @@ extern "C" int st_skinny_partial_attn_hist(const float* packed_w, const st_t16_v
     ST_CHECK_ARG(lds + 8 * 4 * 64 * sizeof(f32x4) <= 160 * 1024, "st_skinny_partial_attn_hist: L=%d needs %zu bytes of LDS", h.L, lds);
     auto kern = pk_part_hist_kernel<8, 2>;
     static size_t lds_set = 0;
-    if (lds > 32 * 1024 && lds > lds_set) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
+    // (32 KiB rather than 48 on purpose: the kernel also has a static reduction buffer, of 32 KiB)
+    if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, lds > 32 * 1024, lds_set)) return rc;
     hipLaunchKernelGGL(kern, dim3(h.B + (N / 32) * S), dim3(8 * 64), lds, (hipStream_t)stream, p, h.B, h);
     ST_LAUNCH_CHECK();
     return 0;
@@ -1913,23 +1872,8 @@ extern "C" int st_skinny_partial_attn_bwd(const float* packed_w, const st_t16_vi
     auto kern = kw16 ? pk_part_ab_kernel<16, 2, AB_LBLK_MAX, 2> : pk_part_ab_kernel<8, 2, AB_LBLK_MAX, 2>;      // (TRIP = 3 / 4, i.e. deeper groups in flight: 14.4 / 13.8 us against 12.8)
     const int trip = 2 + kw16;
     static size_t lds_set[5] = {0, 0, 0, 0, 0};
-    if (pl.opt_in && lds > lds_set[trip]) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set[trip] = lds;
-    }
+    if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, pl.opt_in, lds_set[trip])) return rc;
     hipLaunchKernelGGL(kern, dim3(2 * t.B + n_prod), dim3((kw16 ? 16 : 8) * 64), lds, (hipStream_t)stream, p, 2 * t.B, t, st_exp_flag());
     ST_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int st_skinny_linear_packed_attnpre_fwd(const float* packed_w, const st_t16_view* x, int K,
-                                                   const float* bias, int act, const float* mask, int ldmask,
-                                                   float* y, int ldy, const st_t16_view* y_dst,
-                                                   int n_split, float* y2, int ldy2, int rep,
-                                                   int n_split2, int act2, const float* mask2, int ldmask2,
-                                                   const st_t16_view* y3_dst,
-                                                   int B, int N, const st_attn_pre_job* pre, void* stream) {
-    (void)hipGetLastError();
-    return pk_linear_impl(packed_w, x, K, bias, act, mask, ldmask, y, ldy, y_dst, n_split, y2, ldy2, rep,
-                          n_split2, act2, mask2, ldmask2, y3_dst, B, N, pre, stream);
 }

@@ -46,6 +46,22 @@ static inline int st_device_cus() {
     return n;
 }
 
+// raise a kernel's dynamic-LDS limit when `needed` and `lds` exceeds what this kernel was last given; `seen` is the caller's static mark
+static inline int st_lds_opt_in(const void* kern, size_t lds, bool needed, size_t& seen) {
+    if (!needed || lds <= seen) return 0;
+    ST_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    seen = lds;
+    return 0;
+}
+
+// the plain product y (B, N) = x W^T as a linear job: no bias, activation, T16 destination or further range (the caller adds what it needs)
+static inline st_packed_linear_job st_plain_linear_job(const float* packed_w, const st_t16_view& x, int K, float* y, int ldy, int B, int N) {
+    st_packed_linear_job j;
+    memset(&j, 0, sizeof(j));
+    j.p = st_packed_product{packed_w, x, K, y, ldy, B, N};
+    return j;
+}
+
 static __host__ __device__ inline bool st_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---------------------------------------------------------------- device helpers (wave = 64)

@@ -266,7 +266,7 @@ def query_attn_fin(packed_wq, h_q_t16, Q, s_buf, memory, w_cum_prev, v, w_out, w
         granules = torch.zeros(B, 2 * A, device=memory.device, dtype=torch.float32)
     job = _fin_job(s_buf, memory, w_cum_prev, v, w_out, w_cum_out, parts, F_, K, ctx_t16=ctx_t16)
     hv = t16_view(h_q_t16, K=Q)
-    check(_lib.load().st_query_attn_fin_fwd(_p(packed_wq), C.byref(hv), 16 * kb16(Q), _p(granules), int(epoch), C.byref(job), B,
+    check(_lib.load().st_query_attn_fin_fwd(_p(packed_wq), C.byref(hv), 16 * kb16(Q), _p(granules), int(epoch), C.byref(job), B, None,
                                             stream_handle()), 'st_query_attn_fin_fwd')
     return granules
 
@@ -1695,10 +1695,6 @@ def untile_tape(flat, slots, Bp, kb_stride, segs):
     return out
 
 
-def _vp(v):
-    return C.byref(v) if v is not None else None
-
-
 def lstm_cell_job(packed_w, x_view, Kpad, b_ih, b_hh, c_prev, h_dst0, c_out, B, H, h_dst1=None, mask=None,
                   gates_out=None, ada_std=None, ada_mean=None, hadapt_dst=None, part=None, w_kbs=0):
     """StLstmCellPackedJob; x_view / *_dst: StT16View (see t16_view); Kpad = 16 * (k-blocks to reduce over).  `part` (B, 4H): the cell runs over
@@ -1734,14 +1730,23 @@ def partial_product(packed_w, w_kbs, kb0, KB, x_view, N, part, B):
     return part
 
 
+def packed_product(packed_w, x_view, Kpad, y, ldy, B, N):
+    """StPackedProduct: y (B, N) = x W^T on packed operands (x_view: StT16View, Kpad = 16 * (k-blocks to reduce over); y may be None where the
+    entry point allows it)"""
+    return _lib.StPackedProduct(packed_w=_p(packed_w), x=x_view, K=int(Kpad), y=_p(y), ldy=int(ldy), B=int(B), N=int(N))
+
+
 def skinny_linear_packed(packed_w, x_view, Kpad, B, N, y=None, y_dst=None, bias=None, act=None, mask=None,
                          n_split=0, y2=None, rep=0, n_split2=0, act2=None, mask2=None, y3_dst=None):
-    check(_lib.load().st_skinny_linear_packed_fwd(
-        _p(packed_w), C.byref(x_view), int(Kpad), _p(bias), ACT[act], _p(mask),
-        int(mask.stride(0)) if mask is not None else 0, _p(y), int(y.stride(0)) if y is not None else 0, _vp(y_dst),
-        int(n_split), _p(y2), int(y2.stride(0)) if y2 is not None else 0, int(rep),
-        int(n_split2), ACT[act2], _p(mask2), int(mask2.stride(0)) if mask2 is not None else 0, _vp(y3_dst),
-        int(B), int(N), stream_handle()), 'st_skinny_linear_packed_fwd')
+    ld = lambda t: int(t.stride(0)) if t is not None else 0
+    job = _lib.StPackedLinearJob(p=packed_product(packed_w, x_view, Kpad, y, ld(y), B, N), bias=_p(bias), act=ACT[act], mask=_p(mask), ldmask=ld(mask),
+                                 n_split=int(n_split), y2=_p(y2), ldy2=ld(y2), rep=int(rep),
+                                 n_split2=int(n_split2), act2=ACT[act2], mask2=_p(mask2), ldmask2=ld(mask2))
+    if y_dst is not None:
+        job.y_dst = y_dst
+    if y3_dst is not None:
+        job.y3_dst = y3_dst
+    check(_lib.load().st_skinny_linear_packed_fwd(C.byref(job), stream_handle()), 'st_skinny_linear_packed_fwd')
 
 
 # --------------------------------------------------------------------------------------------- graphs

@@ -391,8 +391,9 @@ def run_hosted(c, x, dev):
     prod = {}
     if c['hosted'] == 1:
         y = bufs.out('y', B, N)
-        _lib.check(lib.st_skinny_linear_packed_lstm_bwd_attn_bwd(P(packed), C.byref(xv), KP, P(y), N, B, N, None, C.byref(j),
-                                                                 ops.stream_handle()), 'st_skinny_linear_packed_lstm_bwd_attn_bwd')
+        prd = ops.packed_product(packed, xv, KP, y, N, B, N)
+        _lib.check(lib.st_skinny_linear_packed_lstm_bwd_attn_bwd(C.byref(prd), None, C.byref(j), ops.stream_handle()),
+                   'st_skinny_linear_packed_lstm_bwd_attn_bwd')
         prod['y'] = (lambda: bufs.view('y'))
     else:
         S_ = 2
@@ -407,8 +408,8 @@ def run_hosted(c, x, dev):
         hj.dloc_t, hj.hist_t, hj.dhist, hj.dcum = P(o['dloc']), P(o['hist_t']), P(o['dhist']), P(di['dcum'])
         hj.B, hj.L, hj.F, hj.K = B, L, F, K
         y2 = bufs.out('y2', B, N)
-        _lib.check(lib.st_skinny_linear_packed_attn_hist(P(packed), C.byref(xv), KP, P(y2), N, B, N, C.byref(hj), ops.stream_handle()),
-                   'st_skinny_linear_packed_attn_hist')
+        prd2 = ops.packed_product(packed, xv, KP, y2, N, B, N)
+        _lib.check(lib.st_skinny_linear_packed_attn_hist(C.byref(prd2), C.byref(hj), ops.stream_handle()), 'st_skinny_linear_packed_attn_hist')
         prod['y2'] = (lambda: bufs.view('y2'))
     torch.cuda.synchronize()
     bufs.guards_intact()

@@ -260,6 +260,19 @@ def test_skinny_linear_packed(dev, B, N, Ks):
         lin = torch.cat(xs, 1).double() @ w.double().t() + b.double()
         assert maxdiff(y1, lin[:, :N - 1]) < 2e-5 and maxdiff(y2, lin[:, N - 1:].repeat(1, 3)) < 2e-5
         assert torch.equal(ops.untile_rows(t1, B, N - 1), y1)
+    # third range (proj + gate + prenet layer 1 of the next step): one column to y2, the last 8 through act2 and mask2 to y3_dst;
+    # the bias is added before act2, as the kernel's epilogue does
+    if N > 24:
+        y1 = torch.zeros(B, N - 9, device=dev)
+        y2 = torch.zeros(B, 3, device=dev)
+        t1 = torch.zeros(ops.t16_floats(B, N - 9), device=dev)
+        t3 = torch.zeros(ops.t16_floats(B, 8), device=dev)
+        mask2 = (torch.rand(B, 8) > 0.5).float() * 2
+        ops.skinny_linear_packed(packed, xv, 16 * stride, B, N, y=y1, y_dst=ops.t16_view(t1, K=N - 9), bias=b.to(dev),
+                                 n_split=N - 9, y2=y2, rep=3, n_split2=N - 8, act2='relu', mask2=mask2.to(dev), y3_dst=ops.t16_view(t3, K=8))
+        assert maxdiff(y1, lin[:, :N - 9]) < 2e-5 and maxdiff(y2, lin[:, N - 9:N - 8].repeat(1, 3)) < 2e-5
+        assert torch.equal(ops.untile_rows(t1, B, N - 9), y1)
+        assert maxdiff(ops.untile_rows(t3, B, 8), torch.relu(lin[:, N - 8:]) * mask2.double()) < 2e-5
 
 
 @pytest.mark.parametrize('B,L,A,E,F,K,Q', [(2, 7, 16, 32, 4, 5, 48), (4, 12, 256, 512, 32, 31, 1024),

@@ -96,6 +96,41 @@ def test_decode_step_jobs_refuse_what_they_cannot_express():
     cell = _lib.StLstmCellPackedJob(packed_w=p, x=view, K=16, c_prev=p, ldc_prev=8, h_dst0=view, c_out=p, ldc=8, B=16, H=8, part=p, w_kbs=3)
     refused(lib.st_lstm_cell_packed_fwd(ctypes.byref(cell), None), 'a slab needs B = 17..32')
 
+    # the packed products: one operand struct, one linear job
+    def product(**kw):
+        return _lib.StPackedProduct(**dict(dict(packed_w=p, x=view, K=32, y=p, ldy=24, B=5, N=24), **kw))
+
+    def linear(prod=None, **kw):
+        return _lib.StPackedLinearJob(p=prod or product(), **kw)
+
+    refused(lib.st_skinny_linear_packed_fwd(None, None), 'st_skinny_linear_packed_fwd: null job')
+    refused(lib.st_skinny_linear_packed_attnpre_fwd(None, ctypes.byref(pre_job()), None), 'st_skinny_linear_packed_fwd: null job')
+    refused(lib.st_skinny_linear_packed_fwd(ctypes.byref(linear(n_split=16, rep=2)), None), 'n_split without y2/rep')
+    refused(lib.st_skinny_linear_packed_fwd(ctypes.byref(linear(n_split=16, y2=p, ldy2=2)), None), 'n_split without y2/rep')
+    refused(lib.st_skinny_linear_packed_fwd(ctypes.byref(linear(n_split2=16, act2=1, mask2=p, ldmask2=8)), None), 'third range')
+    refused(lib.st_skinny_linear_packed_fwd(ctypes.byref(linear(n_split=17, y2=p, ldy2=2, rep=2, n_split2=16, y3_dst=view)), None), 'third range')
+    refused(lib.st_skinny_linear_packed_fwd(ctypes.byref(linear(product(y=None))), None), 'st_skinny_linear_packed_fwd: bad arguments')
+    refused(lib.st_skinny_linear_packed_fwd(ctypes.byref(linear(product(N=0))), None), 'st_skinny_linear_packed_fwd: bad arguments')
+    refused(lib.st_skinny_linear_packed_fwd(ctypes.byref(linear(product(K=80))), None), 'outside the T16 buffer')
+
+    pw = _lib.StLstmPwJob(n0=0, H=16, gates=p, c=p, ldc=16, dc=p, dgates=p, ldg=64)
+    refused(lib.st_skinny_linear_packed_lstm_bwd_fwd(None, ctypes.byref(pw), None), 'st_skinny_linear_packed_lstm_bwd_fwd: null product')
+    refused(lib.st_skinny_linear_packed_lstm_bwd_fwd(ctypes.byref(product(ldy=20)), ctypes.byref(pw), None), 'st_skinny_linear_packed_lstm_bwd_fwd: bad arguments')
+    refused(lib.st_skinny_linear_packed_lstm_bwd_fwd(ctypes.byref(product(y=None)), ctypes.byref(pw), None), 'st_skinny_linear_packed_lstm_bwd_fwd: bad arguments')
+    refused(lib.st_skinny_linear_packed_lstm_bwd_fwd(ctypes.byref(product()), None, None), 'st_skinny_linear_packed_lstm_bwd_fwd: bad arguments')
+    pair, pws = (_lib.StPackedProduct * 2)(product(y=None), product(y=None, N=16, ldy=16)), (_lib.StLstmPwJob * 2)(pw, pw)
+    refused(lib.st_skinny_linear_packed_lstm_bwd_pair_fwd(pair, pws, None), 'the two products differ in K, B, N or ldy')
+    pair[1] = product(y=None, ldy=20)
+    refused(lib.st_skinny_linear_packed_lstm_bwd_pair_fwd(pair, pws, None), 'the two products differ in K, B, N or ldy')
+    pair[0] = product(y=None, ldy=20)
+    refused(lib.st_skinny_linear_packed_lstm_bwd_pair_fwd(pair, pws, None), 'st_skinny_linear_packed_lstm_bwd_pair_fwd: bad arguments')
+    refused(lib.st_skinny_linear_packed_lstm_bwd_attn_bwd(ctypes.byref(product()), None, None, None), 'st_skinny_linear_packed_lstm_bwd_attn_bwd: bad arguments')
+    hj = _lib.StAttnHistJob(dloc_part=p, parts=2, loc_conv_w=p, w_prev=p, ld_wprev=13, w_cum_prev=p, dloc_t=p, hist_t=p, dhist=p, B=5, L=13, F=6, K=7)
+    refused(lib.st_skinny_linear_packed_lstm_bwd_attn_hist_sum(ctypes.byref(product()), ctypes.byref(pw), ctypes.byref(hj), None, None),
+            'st_skinny_linear_packed_lstm_bwd_attn_hist_sum: null job')
+    refused(lib.st_skinny_linear_packed_attn_hist(ctypes.byref(product()), None, None), 'st_skinny_linear_packed_attn_hist: null history job')
+    refused(lib.st_skinny_linear_packed_attn_hist(ctypes.byref(product(ldy=20)), ctypes.byref(hj), None), 'attn_hist: bad arguments')
+
 
 def test_state_dict_keys_match_reference():
     """same parameter/buffer names and shapes as the reference modules, so its checkpoints load"""

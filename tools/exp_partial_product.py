@@ -23,8 +23,7 @@ for N in (2560, 1792):
         def run_part():
             _lib.check(lib.st_skinny_partial_attn_bwd(ops._p(pw), C.byref(xv), K, ops._p(part), S, B, N, None, ops.stream_handle()), 'part')
         def run_plain():
-            _lib.check(lib.st_skinny_linear_packed_fwd(ops._p(pw), C.byref(xv), K, None, 0, None, 0, ops._p(y), N, None, 0, None, 0, 0, 0, 0, None, 0, None, B, N,
-                                                       ops.stream_handle()), 'plain')
+            ops.skinny_linear_packed(pw, xv, K, B, N, y=y)
         for name, fn in (('partial S=%d' % S, run_part),) + ((('plain', run_plain),) if S == 1 else ()):
             for _ in range(3):
                 fn()

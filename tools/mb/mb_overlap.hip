@@ -44,8 +44,8 @@ int main() {
     hipStream_t s1, s2; CK(hipStreamCreate(&s1)); CK(hipStreamCreate(&s2));
     auto ab = [&](hipStream_t st) { int rc = st_attn_step_bwd(&job, st);
         if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
-    auto pk = [&](hipStream_t st) { int rc = st_skinny_linear_packed_fwd(pw, &xv, KD, nullptr, ST_ACT_NONE, nullptr, 0, py, ND, nullptr, 0, nullptr, 0, 0, 0, 0,
-                                                                         nullptr, 0, nullptr, B, ND, st);
+    const st_packed_linear_job lj = st_plain_linear_job(pw, xv, KD, py, ND, B, ND);
+    auto pk = [&](hipStream_t st) { int rc = st_skinny_linear_packed_fwd(&lj, st);
         if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
     for (int i = 0; i < 5; ++i) { ab(s1); pk(s1); }
     CK(hipDeviceSynchronize());

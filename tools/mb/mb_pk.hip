@@ -85,8 +85,9 @@ int main() {
         CK(hipMalloc(&w, wf * 4)); CK(hipMalloc(&x, xf * 4)); CK(hipMalloc(&y, B * N * 4)); CK(hipMalloc(&bias, N * 4));
         CK(hipMemset(w, 0, wf * 4)); CK(hipMemset(x, 0, xf * 4)); CK(hipMemset(bias, 0, N * 4));
         st_t16_view xv = {x, (K + 15) / 16, 0};
-        auto run = [&] { int rc = st_skinny_linear_packed_fwd(w, &xv, K, bias, which == 1 ? ST_ACT_RELU : ST_ACT_NONE, nullptr, 0, y, N, nullptr,
-                                                              0, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, B, N, nullptr);
+        st_packed_linear_job lj = st_plain_linear_job(w, xv, K, y, N, B, N);
+        lj.bias = bias; lj.act = which == 1 ? ST_ACT_RELU : ST_ACT_NONE;
+        auto run = [&] { int rc = st_skinny_linear_packed_fwd(&lj, nullptr);
             if (rc) { printf("rc=%d %s\n", rc, st_last_error()); exit(1); } };
         float* junk; CK(hipMalloc(&junk, 64 << 20));
         for (int i = 0; i < 3; ++i) run();
