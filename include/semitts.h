@@ -1279,6 +1279,32 @@ int st_audio_features(const float* x, long n_samples, const float* noise, unsign
                       float* linear, int T_pad, float* aug, int Ta_pad, float* ws, void* stream);
 /* out[i] = the built-in generator's standard normal for (seed, utterance utt, sample i), i < n (for tests) */
 int st_feature_noise(float* out, long n, int utt, unsigned long long seed, void* stream);
+/* MFCC with derivatives (ref: AudioProcessor.extract_mfcc_from_waveform, src/audio.py:119-154) for a ragged batch packed as above
+ * (host off / len, B <= 64): out (B, T_pad, 3 * n_mfcc).  Frame t of utterance b is the frame of st_audio_features' clean framing
+ * (same pre-emphasis, reflect padding, window, filterbank and norm) at the caller's win / hop -- the reference's MFCC framing is
+ * win = int(0.025 sr), hop = int(0.010 sr) in the model's n_fft.  Columns [0, n_mfcc): c[k] = sum_m dct[k, m] mel[m] over the
+ * NORMALISED [0, 1] mel (librosa.feature.mfcc(S=mel, n_mfcc) = scipy.fftpack.dct(mel, axis=0, type=2, norm='ortho')[:n_mfcc]; the
+ * reference hands it the normalised mel, kept here), dct (n_mfcc, n_mels) row-major on the device, tabulated by the caller:
+ * dct[k, m] = sqrt(2 / n_mels) cos(pi (2 m + 1) k / (2 n_mels)), row 0 divided by sqrt(2).  Each c[k] is one fmaf chain over
+ * ascending m.  Columns [n_mfcc, 2 n_mfcc) and [2 n_mfcc, 3 n_mfcc): librosa.feature.delta(c) and delta(c, order=2) =
+ * scipy.signal.savgol_filter(c, 9, deriv=o, polyorder=o, axis=time, mode='interp'), which is the 9-tap filter with its centre
+ * clamped into [4, T_b - 5]: with tc = min(max(t, 4), T_b - 5),
+ *     delta[t] = sum_{j=-4..4} (j / 60) c[tc + j],   delta2[t] = sum_j w2[j] c[tc + j],  w2 = (28, 7, -8, -17, -20, -17, -8, 7, 28) / 462
+ * (order 2 is the second derivative of c, not a delta of the delta), each one fmaf chain over ascending j.  T_b = 1 + len[b] / hop;
+ * rows t >= T_b are written as 0, T_pad >= max T_b.  mel_out (B, T_pad, n_mels) (null: not written): the normalised mel at this
+ * framing.  A frame's bits depend on neither the batch nor the position in it.  Supported (anything else returns -22): n_fft in
+ * {512, 1024, 2048, 4096}, 0 < 2 * hop <= win <= n_fft, len[b] > n_fft / 2, 1 <= n_mfcc <= n_mels <= 256, len[b] >= 8 * hop (T_b >= 9:
+ * librosa refuses a width above the frame count), B <= 64.  Two launches (frames, then derivatives); no atomics, no workspace. */
+int st_audio_mfcc(const float* x, long n_samples, const long* off, const int* len, int B, int n_fft, int win, int hop, float preemph,
+                  const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels, const float* dct, int n_mfcc,
+                  float* out, float* mel_out, int T_pad, void* stream);
+/* Phone segments (ref: AudioProcessor.segment, src/audio.py:94-117): out (S, max_len, D) contiguous, 16-byte aligned, from
+ * feat (B, T_pad, D) with feat(b, t, d) = feat[b * sb + t * st + d] (strides in floats, st >= D).  Row i < seg_len[s] of segment s
+ * is feat[seg_utt[s], seg_start[s] + i, :] copied exactly; every other row is 0.  seg_utt, seg_start, seg_len: DEVICE int32 arrays
+ * of S entries.  The utterance index is clamped into [0, B) and the frame index into [0, T_pad), so a wrong table cannot index
+ * outside feat.  S == 0 or max_len == 0 returns 0 without a launch.  One launch, 16-byte stores, any D. */
+int st_segment_gather(const float* feat, long sb, long st, int B, int T_pad, int D, const int* seg_utt, const int* seg_start,
+                      const int* seg_len, int S, int max_len, float* out, void* stream);
 
 /* ------------------------------------------------------------------ sample-rate conversion (waveforms -> waveforms)
  * Not a step of the reference (its AudioProcessor.load refuses a foreign rate, src/audio.py:70-77, and leaves conversion to an

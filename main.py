@@ -21,6 +21,7 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --vocode-dir DIR [--vocode-feat spec|mel --batch-size 32]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --resample      (files of any sample rate)
     python main.py --resample-wav-dir DIR --resample-out DIR2 --resample-rate 16000 [--batch-size 32]
+    python main.py --config config/supervised.yaml --feat-wav-dir DIR --feat mfcc|mel|linear [--segment-file FILE --min-segment-len 2]
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
 `--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
 (semi_tts_amd/ngram.py: a plain .npy of shape (V^(order-1), V) in the layout of the reference's NgramPrior, src/lm.py:233-290) on the host.
@@ -32,6 +33,9 @@ vocode the predicted mel instead of the predicted linear spectrogram.
 `--resample` (with --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir) converts files whose rate is not data.audio.sample_rate on
 the GPU (semi_tts_amd.audio.resample: Hann-windowed sinc, st_resample_batch) where the reference, and this path without the flag, refuse
 them; `--resample-wav-dir` converts a directory of .wav files to another rate and writes them as 16-bit mono (solver.Resampler).
+`--feat-wav-dir` writes the MFCC (13 cepstra and their two derivatives, src/audio.py:119-154), mel or linear features of .wav files as
+<stem>-<feat>.npy and, with `--segment-file` (the segments.csv of --align-wav-dir), the same cut at the phone boundaries as
+<stem>-<feat>-seg.npy (solver.FeatureWriter; the reference's segment_file / segment_feat / min_segment_len, src/audio.py:309-354).
 """
 import argparse
 import os
@@ -111,6 +115,14 @@ parser.add_argument('--resample-wav-dir', default=None, type=str, help='convert 
 parser.add_argument('--resample-out', default=None, type=str, help='--resample-wav-dir: the directory to write (not the one read)')
 parser.add_argument('--resample-rate', default=None, type=int, help='--resample-wav-dir: the output rate in Hz (default: data.audio.sample_rate '
                     'of --config)')
+parser.add_argument('--feat-wav-dir', default=None, type=str, help='extract --feat from the .wav files of this directory (sorted by name, batched '
+                    'by --batch-size) on the GPU into <logdir>/<name>/<stem>-<feat>.npy (frames, dim); no checkpoint, no model')
+parser.add_argument('--feat', default=None, choices=('mfcc', 'mel', 'linear'), help='--feat-wav-dir: the feature written: 39-dimensional MFCC '
+                    '(25 / 10 ms framing), or the clean mel / linear spectrogram of data.audio')
+parser.add_argument('--segment-file', default=None, type=str, help='--feat-wav-dir: a segment table (file,seg: the segments.csv of '
+                    '--align-wav-dir); also write <stem>-<feat>-seg.npy (segments, longest piece, dim), the feature cut at its boundaries')
+parser.add_argument('--min-segment-len', default=None, type=int, help='--segment-file: the fewest frames of a segment; a shorter piece joins '
+                    'the next one (default 2)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -186,6 +198,23 @@ def parse_args(argv=None):
             parser.error('--resample-wav-dir needs --resample-rate N or --config (its data.audio.sample_rate)')
     elif paras.resample_out is not None or paras.resample_rate is not None:
         parser.error('--resample-out and --resample-rate belong to --resample-wav-dir; they need that flag')
+    if paras.feat_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir'):
+            if getattr(paras, flag):
+                parser.error('--feat-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--feat-wav-dir does not combine with --dev-batches')
+        if paras.config is None or paras.feat is None:
+            parser.error('--feat-wav-dir needs --config (its data.audio) and --feat mfcc|mel|linear')
+        if paras.min_segment_len is not None and paras.segment_file is None:
+            parser.error('--min-segment-len belongs to --segment-file; it needs that flag')
+        if paras.min_segment_len is not None and paras.min_segment_len < 1:
+            parser.error('--min-segment-len must be >= 1')
+    elif paras.feat is not None or paras.segment_file is not None or paras.min_segment_len is not None:
+        parser.error('--feat, --segment-file and --min-segment-len belong to --feat-wav-dir; they need that flag')
+    if paras.min_segment_len is None:
+        paras.min_segment_len = 2
     if paras.gen_wav_feat != 'linear' and not (paras.gen_specgram and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
@@ -260,6 +289,9 @@ def main(argv=None):
         mode = 'test'
     elif paras.vocode_dir is not None:
         from semi_tts_amd.solver import Vocoder as Solver
+        mode = 'test'
+    elif paras.feat_wav_dir is not None:
+        from semi_tts_amd.solver import FeatureWriter as Solver
         mode = 'test'
     elif paras.transcribe_wav_dir is not None:
         from semi_tts_amd.solver import Transcriber as Solver

@@ -374,6 +374,8 @@ SIGNATURES = {
     'st_features_workspace_floats': [I],
     'st_audio_features': [P, C.c_long, P, C.c_ulonglong, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, I, P, P, I, P, I, P, P],
     'st_feature_noise': [P, C.c_long, I, C.c_ulonglong, P],
+    'st_audio_mfcc': [P, C.c_long, P, P, I, I, I, I, F, P, P, P, P, I, P, I, P, P, I, P],
+    'st_segment_gather': [P, C.c_long, C.c_long, I, I, I, P, P, P, I, I, P, P],
     'st_resample_batch': [P, I, C.c_long, P, P, I, I, I, I, I, I, P, P, P, C.c_long, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,

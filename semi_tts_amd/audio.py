@@ -22,7 +22,16 @@ Sample-rate conversion (st_resample_batch; not a step of the reference, whose lo
     wb = resample(wavs48k, 48000, 22050)                         # list of 1-D float / int16 waveforms -> WaveBatch on the device
     wb = conv.load_batch(paths, resample=True)                   # .wav files of any rate -> one WaveBatch at conv.sr
     mel, aug_mel, linear = conv.extract_batch(wb, r=5)
+
+MFCC and phone segments (st_audio_mfcc, st_segment_gather; src/audio.py:94-154, 309-354):
+
+    mfcc = conv.extract_mfcc_from_waveform(wave)                  # (39, T): 13 cepstra, their first and second derivatives
+    mfcc = conv.extract_mfcc_batch(wavs)                          # device (B, T_pad, 39), longest first
+    conv = load_audio_transform(**config['data']['audio'], segment_file='segments.csv', segment_feat='mfcc')
+    seg = conv.segment_features('utt.wav')                        # (S, max_len, 39): the utterance cut at its phone boundaries
+    seg, counts = conv.segment_batch(mfcc, frames, keys)          # a whole batch in one launch: (S_total, max_len, 39)
 """
+import csv
 import random
 import wave
 
@@ -30,6 +39,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .ctc_align import segment_key      # a file's key in a segment table: its name up to the first '.' (src/audio.py:342)
 
 GFL_ITER = 30                     # src/audio.py:15
 MIN_LEVEL_DB = -100               # src/audio.py:17
@@ -37,6 +47,12 @@ REF_LEVEL_DB = 20                 # src/audio.py:18
 INV_PREEMPHASIS_COEFF = 0.97      # the literal of src/audio.py:276 (_inv_preemphasis ignores preemphasis_coeff)
 SUPPORTED_N_FFT = (512, 1024, 2048, 4096)
 SNR_OFF = float('nan')            # extract_batch(snr=SNR_OFF): no noise (the reference's -1 in snr_range)
+MFCC_HOP_LEN_MS, MFCC_WIN_LEN_MS, N_MFCC_NO_DELTA = 10, 25, 13      # src/audio.py:19-21
+MFCC_DIM = 3 * N_MFCC_NO_DELTA    # cepstra + first and second derivatives (the reference's literal 39, :317)
+SEGMENT_FEAT_KINDS = ('mfcc', 'mel', 'linear')
+# librosa.feature.delta's 9-frame Savitzky-Golay filters in ascending frame order: order 1 (polyorder 1) and order 2 (polyorder 2)
+MFCC_DELTA_TAPS = tuple(j / 60.0 for j in range(-4, 5))
+MFCC_DELTA2_TAPS = tuple(v / 462.0 for v in (28, 7, -8, -17, -20, -17, -8, 7, 28))
 
 # the shipped configs' data.audio (identical in all three YAMLs): num_freq 1025, 12.5 / 50 ms at 22050 Hz
 DEFAULT_N_FFT, DEFAULT_HOP, DEFAULT_WIN = 2048, 275, 1102
@@ -57,6 +73,79 @@ def check_dims(n_fft, hop, win, T):
         # torch.stft's reflect padding of n_fft // 2 needs a longer signal than the hop * (T - 1) samples the iSTFT gives
         raise ValueError('Griffin-Lim: %d frames are too few: reflect padding needs hop * (T - 1) > n_fft // 2 (hop %d, n_fft %d), '
                          'i.e. T >= %d' % (T, hop, n_fft, n_fft // 2 // hop + 2))
+
+
+def mfcc_dims(sample_rate):
+    """(win, hop) of the MFCC framing exactly as AudioProcessor.__init__ derives them (src/audio.py:33-34)"""
+    return int(MFCC_WIN_LEN_MS / 1000 * sample_rate), int(MFCC_HOP_LEN_MS / 1000 * sample_rate)
+
+
+def mfcc_dct(n_mfcc, n_mels):
+    """(n_mfcc, n_mels) float64: the first rows of the orthonormal DCT-II over the mel axis (scipy.fftpack.dct(type=2, norm='ortho'),
+    what librosa.feature.mfcc applies): sqrt(2 / M) cos(pi (2 m + 1) k / (2 M)), row 0 divided by sqrt(2).  The kernel takes it
+    rounded once to float32."""
+    k, m = np.arange(n_mfcc, dtype=np.float64)[:, None], np.arange(n_mels, dtype=np.float64)[None, :]
+    d = np.sqrt(2.0 / n_mels) * np.cos(np.pi * (2.0 * m + 1.0) * k / (2.0 * n_mels))
+    d[0] /= np.sqrt(2.0)
+    return d
+
+
+def clamped_filter(c, taps):
+    """c (..., T) float64, T >= len(taps) -> the filter `taps` (ascending frame order, odd length 2 h + 1) along the last axis with
+    its centre clamped into [h, T - 1 - h]: y[t] = sum_j taps[j] c[min(max(t, h), T - 1 - h) + j - h].  With MFCC_DELTA_TAPS /
+    MFCC_DELTA2_TAPS this is scipy.signal.savgol_filter(c, 9, deriv=o, polyorder=o, mode='interp'); the host
+    statement of what mfcc_delta_kernel computes."""
+    c = np.asarray(c, np.float64)
+    h, T = len(taps) // 2, c.shape[-1]
+    if T < len(taps):
+        raise ValueError('clamped_filter: %d frames, the filter has %d taps' % (T, len(taps)))
+    tc = np.clip(np.arange(T), h, T - 1 - h)
+    return sum(w * c[..., tc + j - h] for j, w in enumerate(taps))
+
+
+def compute_len_ratio(seg):
+    """'t1_t2_..._tlast' -> [t / tlast]: a row's boundary times as ratios of the utterance (src/audio.py:425-432)"""
+    times = [float(t) for t in seg.split('_')]
+    return [t / times[-1] for t in times]
+
+
+def read_segment_table(path):
+    """a segment_file (header `file,seg`, one row per utterance: key, boundary times joined by '_'; what --align-wav-dir writes as
+    segments.csv) -> {key: boundary ratios}.  A missing column, a malformed row or a duplicate key raises ValueError naming the file."""
+    table = {}
+    with open(path, newline='') as f:
+        rows = csv.reader(f)
+        header = next(rows, None)
+        if header is None or [h.strip() for h in header] != ['file', 'seg']:
+            raise ValueError('%s: a segment file starts with the header file,seg (got %r)' % (path, header))
+        for n, row in enumerate(rows, 2):
+            if not row:
+                continue
+            try:
+                key, ratios = row[0], compute_len_ratio(row[1])
+                if len(row) != 2 or not all(np.isfinite(ratios)):
+                    raise ValueError
+            except (IndexError, ValueError, ZeroDivisionError):
+                raise ValueError('%s, line %d: expected `key,t1_t2_..._tlast` with a last time above 0, got %r' % (path, n, row))
+            if key in table:
+                raise ValueError('%s, line %d: the key %r appears twice' % (path, n, key))
+            table[key] = ratios
+    return table
+
+
+def segment_points(boundary, feat_len, min_segment_len=2):
+    """Where a feature of feat_len frames is cut (the rule of AudioProcessor.segment, src/audio.py:94-117): every boundary ratio b
+    gives the frame round(b * feat_len) -- Python's round, halves to even.  The piece from the end of the last emitted piece to that
+    frame is emitted when it holds at least min_segment_len frames; a shorter one is not, and its frames go to the next piece.
+    -> ([(start, end)], max_len), max_len the longest candidate piece seen (emitted or not): the padded length of the segments."""
+    pieces, start, max_len = [], 0, 0
+    for b in boundary:
+        end = round(b * feat_len)
+        max_len = max(max_len, end - start)
+        if end - start >= min_segment_len:
+            pieces.append((start, end))
+            start = end
+    return pieces, max_len
 
 
 def min_frames(n_fft, hop):
@@ -136,8 +225,10 @@ class AudioConverter:
     the synthesis methods for the linear branch."""
 
     def __init__(self, num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear=True,
-                 snr_range=(-1, -1), time_stretch_range=(1.0, 1.0), **_unused):
+                 snr_range=(-1, -1), time_stretch_range=(1.0, 1.0), segment_file=None, segment_feat=None, min_segment_len=2, **_unused):
         self.n_fft, self.hop_length, self.win_length = stft_dims(num_freq, frame_shift_ms, frame_length_ms, sample_rate)
+        self.win_length_mfcc, self.hop_length_mfcc = mfcc_dims(sample_rate)
+        self._dct = {}
         self.frame_length_ms, self.frame_shift_ms = frame_length_ms, frame_shift_ms
         self.snr_range, self.time_stretch_range = list(snr_range), list(time_stretch_range)
         self._fb = {}
@@ -147,6 +238,15 @@ class AudioConverter:
         self.sr = sample_rate
         self.use_linear = use_linear
         self.feat_dim = (num_mels, num_freq) if use_linear else (num_mels, None)      # src/audio.py:307
+        self.use_segment = segment_file is not None                                   # src/audio.py:309-327
+        if self.use_segment:
+            self.segment_src = segment_file
+            self.segment_feat = str(segment_feat).lower()
+            self.min_segment_len = min_segment_len
+            if self.segment_feat not in SEGMENT_FEAT_KINDS:
+                raise NotImplementedError('segment_feat %r: one of %s' % (segment_feat, ', '.join(SEGMENT_FEAT_KINDS)))
+            self.seg_feat_dim = {'mfcc': MFCC_DIM, 'mel': num_mels, 'linear': num_freq}[self.segment_feat]
+            self.boundary_table = read_segment_table(segment_file)
 
     def specgram_to_waveform(self, specgram, power=1.0, inv_preemphasis=True, isAmp=False, phases=None, n_iter=GFL_ITER):
         """src/audio.py:179-192: specgram (F, T) or (B, F, T) -> float64 numpy waveform(s), clipped to [-1, 1].
@@ -316,6 +416,116 @@ class AudioConverter:
                                          self.preemphasis_coeff if preemphasis else 0.0, self.filterbank(dev), T)
         return lin[0].t().to(x.device), mel[0].t().to(x.device)
 
+    # -- MFCC (src/audio.py:119-154) and phone segments (:94-117, :339-354)
+    def mfcc_table(self, device):
+        """the (13, n_mels) DCT table as the kernel takes it (mfcc_dct rounded once to float32), cached per device"""
+        key = str(device)
+        if key not in self._dct:
+            self._dct[key] = torch.from_numpy(mfcc_dct(N_MFCC_NO_DELTA, self.n_mels).astype(np.float32)).to(device)
+        return self._dct[key]
+
+    def _check_mfcc(self, lens):
+        """every refusal of st_audio_mfcc, raised before any device is touched"""
+        win, hop = self.win_length_mfcc, self.hop_length_mfcc
+        if self.n_fft not in SUPPORTED_N_FFT:
+            raise ValueError('mfcc: n_fft %d not supported (one of %s)' % (self.n_fft, SUPPORTED_N_FFT))
+        if not (0 < 2 * hop <= win <= self.n_fft):
+            raise ValueError('mfcc: the MFCC framing needs 0 < 2 * hop <= win <= n_fft (hop %d, win %d, n_fft %d)' % (hop, win, self.n_fft))
+        if not N_MFCC_NO_DELTA <= self.n_mels <= ops.MEL_MAX:
+            raise ValueError('mfcc: %d mels outside [%d, %d]' % (self.n_mels, N_MFCC_NO_DELTA, ops.MEL_MAX))
+        for L in lens:
+            if L <= self.n_fft // 2 or L >= 2 ** 30:
+                raise ValueError('mfcc: an utterance of %d samples: reflect padding needs more than n_fft // 2 = %d (and fewer than 2^30)'
+                                 % (L, self.n_fft // 2))
+            if 1 + L // hop < ops.MFCC_MIN_FRAMES:
+                raise ValueError('mfcc: an utterance of %d samples has fewer than 9 MFCC frames (%d at hop %d): the 9-frame derivatives '
+                                 'need at least %d samples' % (L, 1 + L // hop, hop, (ops.MFCC_MIN_FRAMES - 1) * hop))
+
+    def extract_mfcc_batch(self, wavs, preemphasis=True, with_mel=False):
+        """extract_mfcc_from_waveform for a ragged batch in one st_audio_mfcc call: wavs, a list of 1-D waveforms (or a WaveBatch),
+        sorted longest first -> device (B, T_pad, 39), T_pad the longest utterance's 1 + L // hop_length_mfcc, rows past an utterance's
+        own frames 0.  Each utterance is bitwise what it gives alone.  with_mel: -> (mfcc, mel (B, T_pad, n_mels) at the MFCC framing)."""
+        wb = wavs if isinstance(wavs, WaveBatch) else WaveBatch(wavs)
+        self._check_mfcc(wb.lens.tolist())
+        dev = wb.device if wb.device is not None else _device()
+        T_pad = int(1 + wb.lens.max() // self.hop_length_mfcc)
+        mfcc, mel = ops.audio_mfcc(wb.packed(dev), wb.offsets, wb.lens, self.n_fft, self.win_length_mfcc, self.hop_length_mfcc,
+                                   self.preemphasis_coeff if preemphasis else 0.0, self.filterbank(dev), self.mfcc_table(dev), T_pad,
+                                   with_mel=with_mel)
+        return (mfcc, mel) if with_mel else mfcc
+
+    def extract_mfcc_from_waveform(self, waveform, preemphasis=True, channel=0):
+        """src/audio.py:132-154: waveform (channels, samples) -> (39, T) of `channel`, T = 1 + samples // hop_length_mfcc: 13 cepstra of
+        the normalised mel at the 25 / 10 ms framing, their first and second derivatives; on the waveform's device (computed on the GPU
+        either way)"""
+        x = torch.as_tensor(waveform)
+        x = x[channel] if x.dim() == 2 else x
+        return self.extract_mfcc_batch([x], preemphasis=preemphasis)[0].t().to(x.device)
+
+    def extract_mfcc_from_file(self, wav_path, preemphasis=True, channel=0):
+        """src/audio.py:119-130: the file-taking form of extract_mfcc_from_waveform"""
+        return self.extract_mfcc_from_waveform(self.load(wav_path), preemphasis, channel)
+
+    def boundary(self, file):
+        """the boundary ratios of `file` (a path or a key) from the segment table; KeyError naming the file when it has no row"""
+        if not self.use_segment:
+            raise ValueError('segments: this converter was built without a segment_file')
+        key = segment_key(str(file))
+        if key not in self.boundary_table:
+            raise KeyError('%s: no row %r in the segment file %s' % (file, key, self.segment_src))
+        return self.boundary_table[key]
+
+    def segment(self, feat, boundary):
+        """src/audio.py:94-117: feat (T, D), boundary ratios -> (S, max_len, D), segment s the rows [start_s, end_s) of feat
+        (segment_points), zero-padded to the longest candidate piece; on feat's device (gathered on the GPU either way)"""
+        feat = torch.as_tensor(feat)
+        if feat.dim() != 2:
+            raise ValueError('segment: feat of shape %s, expected (T, D)' % (tuple(feat.shape),))
+        seg, _ = self._gather(feat.unsqueeze(0), [feat.size(0)], [boundary])
+        return seg.to(feat.device)
+
+    def segment_batch(self, feats, lens, keys):
+        """A whole batch cut in one st_segment_gather call: feats (B, T_pad, D), lens the frames of each utterance, keys their files
+        (paths or table keys) -> (device (S_total, max_len, D), the segments of utterance 0 first, max_len the longest candidate piece
+        of the batch; [segments per utterance]).  A key without a row is a KeyError before a device is touched."""
+        feats = torch.as_tensor(feats)
+        if feats.dim() != 3 or not len(lens) == len(keys) == feats.size(0):
+            raise ValueError('segment_batch: feats of shape %s for %d lengths and %d keys' % (tuple(feats.shape), len(lens), len(keys)))
+        return self._gather(feats, lens, [self.boundary(k) for k in keys])
+
+    def _gather(self, feats, lens, boundaries):
+        min_len = getattr(self, 'min_segment_len', 2)
+        utt, start, length, counts, max_len = [], [], [], [], 0
+        for b, (T, bd) in enumerate(zip(lens, boundaries)):
+            if not 0 <= int(T) <= feats.size(1):
+                raise ValueError('segments: utterance %d has %d frames, the batch holds %d' % (b, T, feats.size(1)))
+            pieces, longest = segment_points(bd, int(T), min_len)
+            max_len = max(max_len, longest)
+            counts.append(len(pieces))
+            for lo, hi in pieces:
+                utt.append(b)
+                start.append(lo)
+                length.append(hi - lo)
+        dev = feats.device if feats.is_cuda else _device()
+        feats = feats.to(dev, torch.float32)
+        if feats.stride(2) != 1:
+            feats = feats.contiguous()
+        table = torch.tensor([utt, start, length], dtype=torch.int32).reshape(3, len(utt)).to(dev)
+        return ops.segment_gather(feats, table[0], table[1], table[2], max_len), counts
+
+    def segment_features(self, file):
+        """the segmented feature of src/audio.py:339-354, which wave_to_feat computes there and does not return: segment_feat
+        ('mfcc': the file's MFCC, what the reference's undefined `_mfcc` plainly means; 'mel' / 'linear': its clean spectrograms) of
+        `file` cut at its row of the segment table -> CPU (S, max_len, seg_feat_dim)"""
+        boundary = self.boundary(file)
+        wave = self.load(file)
+        if self.segment_feat == 'mfcc':
+            feat = self.extract_mfcc_from_waveform(wave)
+        else:
+            sp, msp = self.extract_feature_from_waveform(wave)
+            feat = msp if self.segment_feat == 'mel' else sp
+        return self.segment(feat.t(), boundary).cpu()
+
     def _draw(self):
         """one utterance's augmentation draws in the order of src/audio.py:356-364: (snr or None, stretch rate)"""
         snr = None if -1 in self.snr_range else random.uniform(self.snr_range[0], self.snr_range[1])
@@ -380,7 +590,7 @@ class AudioConverter:
 
 def load_audio_transform(num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear=True,
                          **kwargs):
-    """src/audio.py:439-448 (segment_file / segment_feat / min_segment_len -- the phone-segment features -- are accepted and unused)"""
+    """src/audio.py:439-448 (segment_file / segment_feat / min_segment_len travel in kwargs: AudioConverter reads them)"""
     return AudioConverter(num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear, **kwargs)
 
 

@@ -1,5 +1,6 @@
 // audio.hip -- Griffin-Lim vocoder: linear spectrogram -> waveform (ref: src/audio.py:179-262, 274-288), and feature extraction:
-// waveforms -> normalised mel / linear spectrograms, clean and augmented (ref: src/audio.py:156-177, 329-395)
+// waveforms -> normalised mel / linear spectrograms, clean and augmented (ref: src/audio.py:156-177, 329-395), MFCC with derivatives
+// (ref: :119-154) and the phone-segment gather (ref: :94-117)
 //
 // Every FFT is a real n_fft-point transform done as an (n_fft/2)-point complex Stockham FFT in LDS (radix 4, one radix-2 stage
 // when log2(n_fft/2) is odd) plus the real split pass.  Twiddles e^{-2 pi i k / n_fft} come from tables computed in double on the
@@ -586,6 +587,49 @@ __device__ __forceinline__ float feat_norm_db(float a) {
     return fminf(fmaxf((db - MIN_LEVEL_DB) / -MIN_LEVEL_DB, 0.0f), 1.0f);
 }
 
+// The three steps a feature frame shares (features_kernel, mfcc_frame_kernel).  frame_load: frame t (centre, reflect padding at L)
+// of the pre-emphasised signal y[i] = s[i] - c s[i-1], s = sample(i), under the periodic Hann window of `win` centred in N -> xr[N].
+template <int N, class Sample>
+__device__ __forceinline__ void frame_load(float* xr, Sample sample, float c, int t, int win, int hop, int L) {
+    const int left = (N - win) / 2;
+    for (int n = threadIdx.x; n < N; n += GL_THREADS) {
+        const int nn = n - left;
+        float v = 0.0f;
+        if (nn >= 0 && nn < win) {
+            const float w = (float)(0.5 - 0.5 * cospi(2.0 * (double)nn / (double)win));
+            const int i = reflect_index(t * hop + n - N / 2, L);
+            const float y = i == 0 ? sample(0) : fmaf(-c, sample(i - 1), sample(i));     // _preemphasis (:228-232)
+            v = y * w;
+        }
+        xr[n] = v;
+    }
+    __syncthreads();
+}
+
+// |X[k]|, k <= N / 2, of the real frame in buf -> mag.  Ends with a barrier.
+template <int N>
+__device__ __forceinline__ void frame_magnitudes(float2* buf, const float2* __restrict__ tw, float* mag) {
+    constexpr int M = N / 2;
+    fft_lds<M>(buf, tw);
+    for (int k = threadIdx.x; k <= M / 2; k += GL_THREADS) {
+        float2 xk, xc;
+        real_split(buf[k], buf[(M - k) & (M - 1)], tw[k], xk, xc);
+        mag[k] = sqrtf(xk.x * xk.x + xk.y * xk.y);
+        if (k != M / 2) mag[M - k] = sqrtf(xc.x * xc.x + xc.y * xc.y);
+    }
+    __syncthreads();
+}
+
+// normalised mel m of the magnitudes mag[F]: the band's fmaf chain in ascending bin order
+__device__ __forceinline__ float band_mel(const float* mag, int F, int m, const int* __restrict__ fb_start, const int* __restrict__ fb_cnt,
+                                          const int* __restrict__ fb_off, const float* __restrict__ fb_w) {
+    const int k0 = min(max(fb_start[m], 0), F), cnt = min(fb_cnt[m], F - k0);           // (a malformed band reads nothing outside mag)
+    const float* w = fb_w + fb_off[m];
+    float a = 0.0f;
+    for (int j = 0; j < cnt; ++j) a = fmaf(mag[k0 + j], w[j], a);
+    return feat_norm_db(a);
+}
+
 // Grid (max(T_pad, Ta_pad), B, 1 or 2).  z = 0: the clean framing (win, hop) -> mel (B, T_pad, n_mels) and linear (B, T_pad, F)
 // when non-null; z = 1: the augmented framing (meta.awin / ahop, noise times coeff[b]) -> aug (B, Ta_pad, n_mels).  Frame t of
 // utterance b is the torch.stft frame (centre, reflect padding at L_b) of y[i] = s[i] - c s[i-1], s = x + coeff n; frames
@@ -597,7 +641,7 @@ __global__ __launch_bounds__(GL_THREADS) void features_kernel(const float* __res
                                                             const int* __restrict__ fb_cnt, const int* __restrict__ fb_off,
                                                             const float* __restrict__ fb_w, int n_mels, float* __restrict__ mel,
                                                             float* __restrict__ linear, float* __restrict__ aug, int T_pad, int Ta_pad) {
-    constexpr int M = N / 2, F = M + 1, HALF = N / 2;
+    constexpr int M = N / 2, F = M + 1;
     __shared__ float2 buf[M];
     __shared__ float mag[F];
     float* xr = reinterpret_cast<float*>(buf);
@@ -630,36 +674,11 @@ __global__ __launch_bounds__(GL_THREADS) void features_kernel(const float* __res
         if (cn != 0.0f) v = fmaf(cn, nb ? nb[i] : feat_normal(seed, utt0 + b, i), v);
         return v;
     };
-    const int left = (N - win) / 2;
-    for (int n = threadIdx.x; n < N; n += GL_THREADS) {
-        const int nn = n - left;
-        float v = 0.0f;
-        if (nn >= 0 && nn < win) {
-            const float w = (float)(0.5 - 0.5 * cospi(2.0 * (double)nn / (double)win));
-            const int i = reflect_index(t * hop + n - HALF, L);
-            const float y = i == 0 ? sample(0) : fmaf(-c, sample(i - 1), sample(i));     // _preemphasis (:228-232)
-            v = y * w;
-        }
-        xr[n] = v;
-    }
-    __syncthreads();
-    fft_lds<M>(buf, tw);
-    for (int k = threadIdx.x; k <= M / 2; k += GL_THREADS) {
-        float2 xk, xc;
-        real_split(buf[k], buf[(M - k) & (M - 1)], tw[k], xk, xc);
-        mag[k] = sqrtf(xk.x * xk.x + xk.y * xk.y);
-        if (k != M / 2) mag[M - k] = sqrtf(xc.x * xc.x + xc.y * xc.y);
-    }
-    __syncthreads();
+    frame_load<N>(xr, sample, c, t, win, hop, L);
+    frame_magnitudes<N>(buf, tw, mag);
     if (lrow)
         for (int k = threadIdx.x; k < F; k += GL_THREADS) lrow[k] = feat_norm_db(mag[k]);
-    for (int m = threadIdx.x; m < n_mels; m += GL_THREADS) {
-        const int k0 = min(max(fb_start[m], 0), F), cnt = min(fb_cnt[m], F - k0);       // (a malformed band reads nothing outside mag)
-        const float* w = fb_w + fb_off[m];
-        float a = 0.0f;
-        for (int j = 0; j < cnt; ++j) a = fmaf(mag[k0 + j], w[j], a);
-        mrow[m] = feat_norm_db(a);
-    }
+    for (int m = threadIdx.x; m < n_mels; m += GL_THREADS) mrow[m] = band_mel(mag, F, m, fb_start, fb_cnt, fb_off, fb_w);
 }
 
 template <int N>
@@ -669,6 +688,137 @@ void launch_features(const float* x, const float* noise, unsigned long long seed
     const dim3 grid(max(T_pad, aug ? Ta_pad : 0), B, aug ? 2 : 1);
     hipLaunchKernelGGL((features_kernel<N>), grid, dim3(GL_THREADS), 0, s, x, noise, seed, utt0, part, meta, c, win, hop, fs, fc, fo, fw,
                        n_mels, mel, linear, aug, T_pad, Ta_pad);
+}
+
+// ------------------------------------------------------------------ MFCC (ref: src/audio.py:119-154)
+// 39 = 3 * n_mfcc columns per frame: the first n_mfcc cepstra of the NORMALISED mel (librosa.feature.mfcc(S=mel): the orthonormal
+// DCT-II over the mel axis, tabulated by the host as dct (n_mfcc, n_mels)), then their first and second Savitzky-Golay derivatives
+// over 9 frames (librosa.feature.delta, order 1 and 2).  Two launches: the frame kernel (the FFT, mel and cepstra of one frame per
+// workgroup, the frame loop of features_kernel without noise) and the delta kernel over (B, T, n_mfcc), which reads the cepstra
+// columns the first wrote and writes the two derivative columns.
+struct MfccMeta {
+    long off[FEAT_MAX_B];      // first sample of utterance b in the packed buffer
+    int len[FEAT_MAX_B];       // its length L_b
+};
+
+constexpr int DELTA_HALF = 4;                                // the 9-frame window of librosa.feature.delta
+// savgol_coeffs(9, polyorder = deriv = 1) = j / 60 and (9, 2, 2) = (28, 7, -8, -17, -20, -17, -8, 7, 28) / 462, in ascending frame order
+__constant__ float DELTA_W1[2 * DELTA_HALF + 1] = {(float)(-4.0 / 60), (float)(-3.0 / 60), (float)(-2.0 / 60), (float)(-1.0 / 60), 0.0f,
+                                                   (float)(1.0 / 60),  (float)(2.0 / 60),  (float)(3.0 / 60),  (float)(4.0 / 60)};
+__constant__ float DELTA_W2[2 * DELTA_HALF + 1] = {(float)(28.0 / 462),  (float)(7.0 / 462),   (float)(-8.0 / 462),
+                                                   (float)(-17.0 / 462), (float)(-20.0 / 462), (float)(-17.0 / 462),
+                                                   (float)(-8.0 / 462),  (float)(7.0 / 462),   (float)(28.0 / 462)};
+
+// Grid (T_pad, B).  Frame t of utterance b as in features_kernel (z = 0) at the MFCC framing (win, hop); the normalised mel row
+// stays in LDS (and goes to mel_out (B, T_pad, n_mels) when non-null); out[b, t, k] = sum_m dct[k, m] mel[m], k < n_mfcc, one fmaf
+// chain over ascending m.  Frames t >= 1 + L_b / hop: all 3 n_mfcc columns (and the mel row) written as 0.
+template <int N>
+__global__ __launch_bounds__(GL_THREADS) void mfcc_frame_kernel(const float* __restrict__ x, MfccMeta meta, float c, int win, int hop,
+                                                              const int* __restrict__ fb_start, const int* __restrict__ fb_cnt,
+                                                              const int* __restrict__ fb_off, const float* __restrict__ fb_w, int n_mels,
+                                                              const float* __restrict__ dct, int n_mfcc, float* __restrict__ out,
+                                                              float* __restrict__ mel_out, int T_pad) {
+    constexpr int M = N / 2, F = M + 1;
+    __shared__ float2 buf[M];
+    __shared__ float mag[F];
+    __shared__ float mels[MEL_MAX];
+    float* xr = reinterpret_cast<float*>(buf);
+    const float2* tw = tw_table<N>();
+    const int t = blockIdx.x, b = blockIdx.y;
+    const int L = meta.len[b];
+    float* orow = out + ((size_t)b * T_pad + t) * (3 * n_mfcc);
+    float* mrow = mel_out ? mel_out + ((size_t)b * T_pad + t) * n_mels : nullptr;
+    if (t >= 1 + L / hop) {                                  // padding frame
+        for (int k = threadIdx.x; k < 3 * n_mfcc; k += GL_THREADS) orow[k] = 0.0f;
+        if (mrow)
+            for (int m = threadIdx.x; m < n_mels; m += GL_THREADS) mrow[m] = 0.0f;
+        return;
+    }
+    const float* xb = x + meta.off[b];
+    frame_load<N>(xr, [&](int i) -> float { return xb[i]; }, c, t, win, hop, L);
+    frame_magnitudes<N>(buf, tw, mag);
+    for (int m = threadIdx.x; m < n_mels; m += GL_THREADS) {
+        const float v = band_mel(mag, F, m, fb_start, fb_cnt, fb_off, fb_w);
+        mels[m] = v;
+        if (mrow) mrow[m] = v;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < n_mfcc; k += GL_THREADS) {
+        const float* d = dct + (size_t)k * n_mels;
+        float a = 0.0f;
+        for (int m = 0; m < n_mels; ++m) a = fmaf(d[m], mels[m], a);
+        orow[k] = a;
+    }
+}
+
+// Grid (ceil(T_pad n_mfcc / 256), B), after mfcc_frame_kernel on the same stream.  delta[t] = sum_j W1[j] c[tc + j - 4] and
+// delta2[t] = sum_j W2[j] c[tc + j - 4] with tc = min(max(t, 4), T_b - 5): scipy's savgol_filter(mode='interp') fits the edge
+// polynomial of degree = deriv order to the outermost window, whose derivative of that order is the constant the centred window
+// gives.  T_b >= 9 (the entry point refuses less).  Reads columns [0, n_mfcc), writes [n_mfcc, 3 n_mfcc) of frames t < T_b.
+__global__ __launch_bounds__(256) void mfcc_delta_kernel(float* __restrict__ out, MfccMeta meta, int hop, int n_mfcc, int T_pad) {
+    const int idx = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    const int t = idx / n_mfcc, k = idx - t * n_mfcc;
+    const int Tb = min(1 + meta.len[b] / hop, T_pad);
+    if (t >= Tb || Tb < 2 * DELTA_HALF + 1) return;
+    const int W = 3 * n_mfcc;
+    const int tc = min(max(t, DELTA_HALF), Tb - 1 - DELTA_HALF);
+    const float* cp = out + ((size_t)b * T_pad + tc - DELTA_HALF) * W + k;
+    float d1 = 0.0f, d2 = 0.0f;
+#pragma unroll
+    for (int j = 0; j <= 2 * DELTA_HALF; ++j) {
+        const float v = cp[(size_t)j * W];
+        d1 = fmaf(DELTA_W1[j], v, d1);
+        d2 = fmaf(DELTA_W2[j], v, d2);
+    }
+    float* orow = out + ((size_t)b * T_pad + t) * W;
+    orow[n_mfcc + k] = d1;
+    orow[2 * n_mfcc + k] = d2;
+}
+
+template <int N>
+void launch_mfcc_frames(const float* x, const MfccMeta& meta, float c, int win, int hop, const int* fs, const int* fc, const int* fo,
+                        const float* fw, int n_mels, const float* dct, int n_mfcc, float* out, float* mel_out, int B, int T_pad, hipStream_t s) {
+    hipLaunchKernelGGL((mfcc_frame_kernel<N>), dim3(T_pad, B), dim3(GL_THREADS), 0, s, x, meta, c, win, hop, fs, fc, fo, fw, n_mels, dct,
+                       n_mfcc, out, mel_out, T_pad);
+}
+
+// ------------------------------------------------------------------ phone segments (ref: src/audio.py:94-117)
+// out (S, max_len, D) contiguous: row i < seg_len[s] of segment s = feat[seg_utt[s], seg_start[s] + i, :], every other row 0.
+// One thread per four consecutive floats of the flat output (one 16-byte store; the last thread stores the 1 .. 3 left over one by
+// one), whatever D is: a quad may straddle rows.  The utterance and frame indices are clamped into feat.
+__global__ __launch_bounds__(256) void segment_gather_kernel(const float* __restrict__ feat, long sb, long st, int B, int T_pad, int D,
+                                                            const int* __restrict__ seg_utt, const int* __restrict__ seg_start,
+                                                            const int* __restrict__ seg_len, long total, int max_len,
+                                                            float* __restrict__ out) {
+    const long e0 = 4 * ((long)blockIdx.x * 256 + threadIdx.x);
+    if (e0 >= total) return;
+    long row = e0 / D;
+    int d = (int)(e0 - row * D);
+    const float* src = nullptr;                              // the feat row of output row `row`; null: a padding row
+    auto open_row = [&](long r) {
+        const int s = (int)(r / max_len), i = (int)(r - (long)s * max_len);
+        src = nullptr;
+        if (i < seg_len[s]) {
+            const int u = min(max(seg_utt[s], 0), B - 1);
+            const long tt = min(max((long)seg_start[s] + i, 0L), (long)T_pad - 1);
+            src = feat + u * sb + tt * st;
+        }
+    };
+    open_row(row);
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int n = (int)min(4L, total - e0);
+    for (int r = 0; r < n; ++r) {
+        v[r] = src ? src[d] : 0.0f;
+        if (++d == D && r + 1 < n) {
+            d = 0;
+            open_row(++row);
+        }
+    }
+    if (n == 4) {
+        *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int r = 0; r < n; ++r) out[e0 + r] = v[r];
+    }
 }
 
 // ------------------------------------------------------------------ host side
@@ -958,6 +1108,65 @@ extern "C" int st_audio_features(const float* x, long n_samples, const float* no
     if (noisy) hipLaunchKernelGGL(feat_power_kernel, dim3(POW_PARTS, B), dim3(POW_THREADS), 0, s, x, noise, seed, utt0, meta, part);
     ST_AUDIO_DISPATCH(n_fft, launch_features, x, noise, seed, utt0, noisy ? part : nullptr, meta, preemph, win, hop, fb_start, fb_cnt, fb_off, fb_w,
                       n_mels, mel, linear, aug, B, T_pad, Ta_pad, s);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_audio_mfcc(const float* x, long n_samples, const long* off, const int* len, int B, int n_fft, int win, int hop, float preemph,
+                             const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels, const float* dct,
+                             int n_mfcc, float* out, float* mel_out, int T_pad, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(x && off && len && fb_start && fb_cnt && fb_off && fb_w && dct && out, "st_audio_mfcc: null pointer");
+    ST_CHECK_ARG(B > 0 && B <= FEAT_MAX_B, "st_audio_mfcc: batch %d outside [1, %d]", B, FEAT_MAX_B);
+    ST_CHECK_ARG(n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096, "st_audio_mfcc: n_fft %d not supported (512, 1024, 2048, 4096)",
+                 n_fft);
+    ST_CHECK_ARG(1 <= n_mfcc && n_mfcc <= n_mels && n_mels <= MEL_MAX, "st_audio_mfcc: need 1 <= n_mfcc <= n_mels <= %d (n_mfcc %d, n_mels %d)",
+                 MEL_MAX, n_mfcc, n_mels);
+    ST_CHECK_ARG(hop > 0 && 2 * hop <= win && win <= n_fft, "st_audio_mfcc: need 0 < 2 * hop <= win <= n_fft (hop %d, win %d, n_fft %d)", hop,
+                 win, n_fft);
+    MfccMeta meta;
+    int tmax = 0;
+    for (int b = 0; b < B; ++b) {
+        ST_CHECK_ARG(len[b] > n_fft / 2 && len[b] < (1 << 30),
+                     "st_audio_mfcc: utterance %d has %d samples: reflect padding needs more than n_fft / 2 = %d", b, len[b], n_fft / 2);
+        ST_CHECK_ARG(len[b] / hop >= 2 * DELTA_HALF, "st_audio_mfcc: utterance %d has %d frames: the 9-frame derivatives need at least 9", b,
+                     1 + len[b] / hop);
+        ST_CHECK_ARG(off[b] >= 0 && off[b] + len[b] <= n_samples, "st_audio_mfcc: utterance %d [%ld, +%d) outside the %ld samples", b, off[b],
+                     len[b], n_samples);
+        meta.off[b] = off[b];
+        meta.len[b] = len[b];
+        tmax = max(tmax, 1 + len[b] / hop);
+    }
+    for (int b = B; b < FEAT_MAX_B; ++b) {
+        meta.off[b] = 0;
+        meta.len[b] = 0;
+    }
+    ST_CHECK_ARG(T_pad >= tmax && (long)T_pad * n_mfcc < (1L << 30), "st_audio_mfcc: T_pad %d below the longest utterance (%d frames) or too large",
+                 T_pad, tmax);
+    int rc = ensure_twiddles(stream);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ST_AUDIO_DISPATCH(n_fft, launch_mfcc_frames, x, meta, preemph, win, hop, fb_start, fb_cnt, fb_off, fb_w, n_mels, dct, n_mfcc, out, mel_out, B,
+                      T_pad, s);
+    hipLaunchKernelGGL(mfcc_delta_kernel, dim3((T_pad * n_mfcc + 255) / 256, B), dim3(256), 0, s, out, meta, hop, n_mfcc, T_pad);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_segment_gather(const float* feat, long sb, long st, int B, int T_pad, int D, const int* seg_utt, const int* seg_start,
+                                 const int* seg_len, int S, int max_len, float* out, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(S >= 0 && max_len >= 0, "st_segment_gather: %d segments of %d rows", S, max_len);
+    if (S == 0 || max_len == 0) return 0;
+    ST_CHECK_ARG(feat && seg_utt && seg_start && seg_len && out, "st_segment_gather: null pointer");
+    ST_CHECK_ARG(B > 0 && T_pad > 0 && D > 0 && st >= D && sb >= 0, "st_segment_gather: bad feat (%d, %d, %d), strides %ld / %ld", B, T_pad, D, sb,
+                 st);
+    ST_CHECK_ARG(((size_t)out & 15) == 0, "st_segment_gather: out must be 16-byte aligned");
+    const long total = (long)S * max_len * D;
+    ST_CHECK_ARG((long)S * max_len < (1L << 31) && total < (1L << 38), "st_segment_gather: output (%d, %d, %d) too large", S, max_len, D);
+    const long quads = (total + 3) / 4;
+    hipLaunchKernelGGL(segment_gather_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, feat, sb, st, B, T_pad, D,
+                       seg_utt, seg_start, seg_len, total, max_len, out);
     ST_LAUNCH_CHECK();
     return 0;
 }

@@ -1942,6 +1942,48 @@ def feature_noise(n, utt, seed, device):
     return out
 
 
+MFCC_MIN_FRAMES = 9              # fewest frames per utterance st_audio_mfcc takes: the width of the derivative filters
+
+
+def audio_mfcc(x, off, lens, n_fft, win, hop, preemph, fb, dct, T_pad, with_mel=False):
+    """st_audio_mfcc on a ragged batch packed as for audio_features: dct (n_mfcc, n_mels) float32 on the device (audio.mfcc_dct);
+    win / hop: the MFCC framing.  -> (mfcc (B, T_pad, 3 * n_mfcc): cepstra, first and second derivatives; mel (B, T_pad, n_mels) at
+    that framing, or None without with_mel).  Batches above FEATURES_MAX_BATCH are issued in chunks of it."""
+    assert x.dim() == 1 and x.is_contiguous()
+    fs, fc, fo, fw = fb
+    n_mels = fs.shape[0]
+    assert dct.dim() == 2 and dct.shape[1] == n_mels and dct.is_contiguous()
+    n_mfcc = dct.shape[0]
+    B = len(lens)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    out = torch.empty(B, T_pad, 3 * n_mfcc, device=x.device, dtype=torch.float32)
+    mel = torch.empty(B, T_pad, n_mels, device=x.device, dtype=torch.float32) if with_mel else None
+    lib = _lib.load()
+    hp = lambda a, b0: a.ctypes.data + b0 * a.itemsize     # noqa: E731  (host array from row b0)
+    for b0 in range(0, B, FEATURES_MAX_BATCH):
+        nb = min(FEATURES_MAX_BATCH, B - b0)
+        check(lib.st_audio_mfcc(_p(x), x.numel(), hp(off, b0), hp(lens, b0), nb, n_fft, win, hop, float(preemph), _p(fs, torch.int32),
+                                _p(fc, torch.int32), _p(fo, torch.int32), _p(fw), n_mels, _p(dct), n_mfcc, _p(out[b0:]),
+                                _p(mel[b0:]) if mel is not None else None, T_pad, stream_handle()), 'st_audio_mfcc')
+    return out, mel
+
+
+def segment_gather(feat, seg_utt, seg_start, seg_len, max_len):
+    """st_segment_gather: feat (B, T_pad, D) float32 on the device, rows contiguous; seg_utt / seg_start / seg_len: device int32 (S,).
+    -> (S, max_len, D): row i < seg_len[s] of segment s = feat[seg_utt[s], seg_start[s] + i], every other row 0."""
+    assert feat.dim() == 3 and feat.stride(2) == 1
+    B, T_pad, D = feat.shape
+    S = seg_utt.shape[0]
+    for a in (seg_utt, seg_start, seg_len):
+        assert a.shape == (S,) and a.dtype == torch.int32 and a.is_contiguous() and a.device == feat.device
+    out = torch.empty(S, max_len, D, device=feat.device, dtype=torch.float32)
+    check(_lib.load().st_segment_gather(_p(feat), feat.stride(0), feat.stride(1), B, T_pad, D, _p(seg_utt, torch.int32),
+                                        _p(seg_start, torch.int32), _p(seg_len, torch.int32), S, int(max_len), _p(out), stream_handle()),
+          'st_segment_gather')
+    return out
+
+
 # --------------------------------------------------------------------------------------------- sample-rate conversion
 RESAMPLE_TILE = 1024                 # outputs per workgroup of st_resample_batch (RS_TILE in resample.hip): the tests straddle it
 RESAMPLE_MAX_TABLE_FLOATS = 9216     # LDS floats of the staged table: min(n, RESAMPLE_TILE) rows of (taps | 1) + 1 (RS_MAX_TABLE)

@@ -287,6 +287,79 @@ class Resampler:
         return n
 
 
+class FeatureWriter:
+    """main.py --feat-wav-dir DIR --feat mfcc|mel|linear [--segment-file FILE --min-segment-len N]: channel 0 of the .wav files of DIR,
+    sorted by name, in batches of --batch-size -> AudioConverter.extract_mfcc_batch (mfcc) or the clean extract_batch (mel, linear) ->
+    <logdir>/<stem>-<feat>.npy, (frames, dim) float32.  With --segment-file each utterance is also cut at its row of that table
+    (AudioConverter.segment_batch, one launch per batch) into <stem>-<feat>-seg.npy, (segments, its longest piece, dim): what
+    AudioConverter.segment_features gives for the file.  No checkpoint, no model.  Every key is looked up in load_data: a file
+    without a row stops the run before anything is written."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.exp_name = getattr(paras, 'name', None) or 'synthetic'
+        self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
+        self.feat = paras.feat
+
+    def load_data(self):
+        from .audio import load_audio_transform
+        self.wav_dir = self.paras.feat_wav_dir
+        self.files = sorted(f for f in os.listdir(self.wav_dir) if f.lower().endswith('.wav'))
+        if not self.files:
+            raise ValueError('--feat-wav-dir %s: no .wav files' % self.wav_dir)
+        audio = dict(self.config['data']['audio'])
+        self.segment_file = getattr(self.paras, 'segment_file', None)
+        if self.segment_file is not None:
+            audio.update(segment_file=self.segment_file, segment_feat=self.feat, min_segment_len=int(getattr(self.paras, 'min_segment_len', 2)))
+        self.audio_converter = conv = load_audio_transform(**audio)
+        if self.feat == 'linear' and not conv.use_linear:
+            raise ValueError('--feat linear: data.audio.use_linear is off')
+        if self.segment_file is not None:
+            for f in self.files:
+                conv.boundary(f)                          # (KeyError naming the file)
+        return self
+
+    def set_model(self):
+        return self
+
+    def extract(self, names):
+        """the files `names` of the .wav directory -> (features (B, T_pad, D) on the device in the sorted order, frames per row, order)"""
+        from .audio import SNR_OFF
+        conv = self.audio_converter
+        wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names])
+        if self.feat == 'mfcc':
+            return conv.extract_mfcc_batch(wb), 1 + wb.lens // conv.hop_length_mfcc, wb.order
+        mel, _, lin = conv.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
+        return (mel if self.feat == 'mel' else lin), 1 + wb.lens // conv.hop_length, wb.order
+
+    def exec(self):
+        from .audio import segment_points
+        os.makedirs(self.logdir, exist_ok=True)
+        conv, B = self.audio_converter, int(self.paras.batch_size)
+        t0, n, n_seg = time.perf_counter(), 0, 0
+        for i in range(0, len(self.files), B):
+            names = self.files[i:i + B]
+            feats, frames, order = self.extract(names)
+            rows = [names[k] for k in order]                         # the batch is sorted by length: row `row` is names[order[row]]
+            host = feats.cpu().numpy()
+            seg = counts = None
+            if self.segment_file is not None:
+                seg, counts = conv.segment_batch(feats, frames.tolist(), rows)
+                seg, first = seg.cpu().numpy(), np.concatenate([[0], np.cumsum(counts)])
+            for row, f in enumerate(rows):
+                stem = os.path.join(self.logdir, '%s-%s' % (os.path.splitext(f)[0], self.feat))
+                np.save(stem + '.npy', host[row, :frames[row]], allow_pickle=False)
+                if seg is not None:                                  # padded to the utterance's own longest piece, not the batch's
+                    own = segment_points(conv.boundary(f), int(frames[row]), conv.min_segment_len)[1]
+                    np.save(stem + '-seg.npy', seg[first[row]:first[row + 1], :own], allow_pickle=False)
+                    n_seg += counts[row]
+                n += 1
+        if getattr(self.paras, 'verbose', True):
+            print('[INFO]', 'Wrote %s features of %d files%s into %s, %.2f s'
+                  % (self.feat, n, '' if self.segment_file is None else ' (%d segments)' % n_seg, self.logdir, time.perf_counter() - t0))
+        return n
+
+
 SPECIAL_TOKENS = ('<pad>', '<space>', '<eos>')     # ids 0, 1, 2 of the phone vocabulary (src/text.py); phones start at id 3
 
 
