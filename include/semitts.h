@@ -1211,23 +1211,14 @@ int st_mean_rows(const float* src, float* dst, int B, int T, int D, void* stream
  * signals longer than n_fft / 2 samples (anything else returns -22).  Spectra are frame-major (B, T, n_fft / 2 + 1) complex
  * (re, im interleaved): the (B, F, T) tensor of torch.stft transposed.  No atomics: results are bitwise repeatable.  The first
  * call on a device uploads the FFT twiddle tables (computed in double on the host) and may not be inside a stream capture. */
-/* workspace floats of st_istft / st_griffin_lim */
+/* the framing of every entry point of this family; a refusal names the framing first, then batch / frames (T < 2), then a short signal */
+typedef struct st_framing { int n_fft, win, hop; } st_framing;
 size_t st_istft_workspace_floats(int B, int T, int n_fft, int hop, int win);
-size_t st_gl_workspace_floats(int B, int T, int n_fft, int hop, int win);
 /* spec (B, 1 + L / hop, n_fft / 2 + 1, 2) = torch.stft(x (B, L), ...)    ref: AudioProcessor._stft src/audio.py:234-246 */
 int st_stft_fwd(const float* x, float* spec, int B, int L, int n_fft, int hop, int win, void* stream);
 /* x (B, hop * (T - 1)) = istft(spec (B, T, n_fft / 2 + 1, 2))    ref: AudioProcessor._istft src/audio.py:248-262, lib/istft.py
  * ws: st_istft_workspace_floats() floats.  3 launches. */
 int st_istft(const float* spec, float* x, int B, int T, int n_fft, int hop, int win, float* ws, void* stream);
-/* wav (B, hop * (T - 1)) = Griffin-Lim of n_iter iterations (ref: _griffin_lim src/audio.py:208-226, GFL_ITER = 30).
- * feat(b, t, f) = feat[b * sb + t * st + f * sf] (strides in floats; the decoder's (B, T, F) is sb = T F, st = F, sf = 1);
- * normalized = 1: feat is the normalised spectrogram and the magnitude is _db_to_amp(_denormalize(feat) + REF_LEVEL_DB) ** power
- * (:186-188, :281-288); 0: feat is the magnitude.  phases: initial phases (B, F, T) contiguous (:214-216, drawn by the caller).
- * post: bit 0 = inverse pre-emphasis y[n] = x[n] + 0.97 y[n-1] (the literal of :274-276, scipy.signal.lfilter([1], [1, -0.97])),
- * bit 1 = clip to [-1, 1] (:192).  ws: st_gl_workspace_floats() floats.  n_iter + 3 launches (setup, first iSTFT, one per
- * iteration, final overlap-add). */
-int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized, float power, const float* phases, float* wav,
-                   int B, int T, int n_fft, int hop, int win, int n_iter, int post, float* ws, void* stream);
 /* lin (B, T, F) contiguous = the mel -> linear product of melspecgram_to_specgram (ref: src/audio.py:194-205):
  * lin[b, t, k] = sum_m basis[m, k] a[b, t, m], mel(b, t, m) = mel[b * sb + t * st + m * sm] (strides in floats), basis (n_mels, F)
  * row-major = pinverse(mel filterbank) transposed (computed by the caller, once).  normalized = 1: a = _db_to_amp(_denormalize(mel)
@@ -1236,52 +1227,63 @@ int st_griffin_lim(const float* feat, long sb, long st, long sf, int normalized,
  * (anything else returns -22).  One launch; each output is an fmaf chain over ascending m: bitwise independent of batch and tiling. */
 int st_mel_to_linear(const float* mel, long sb, long st, long sm, const float* basis, float* lin, int B, int T, int n_mels, int F,
                      int normalized, int take_abs, void* stream);
-/* Griffin-Lim over a batch whose utterances have their own frame counts, from linear or mel input.
- * basis == NULL, n_in == n_fft / 2 + 1: feat is the linear spectrogram, exactly as the uniform entry point above takes it.
+/* Griffin-Lim, the one vocoder entry: wav (B, hop * (T - 1)) after n_iter iterations (ref: _griffin_lim src/audio.py:208-226,
+ * GFL_ITER = 30), from linear or mel input, for utterances of one frame count or of their own.
+ * feat(b, t, f) = feat[b * sb + t * st + f * sf] (strides in floats; the decoder's (B, T, F) is sb = T F, st = F, sf = 1).
+ * basis == NULL, n_in == n_fft / 2 + 1: feat is the linear spectrogram.  normalized = 1: it is the normalised spectrogram and the
+ * magnitude is _db_to_amp(_denormalize(feat) + REF_LEVEL_DB) ** power (:186-188, :281-288); 0: feat is the magnitude.
  * basis != NULL, n_in == n_mels: feat is the mel spectrogram (B, T, n_mels) through the same strides; the magnitude is
  * |mel -> linear product| (one more launch, into the workspace) and power must be 1 (the reference's mel branch is isAmp, :402-408).
- * frames: DEVICE int32 array of B frame counts, or NULL for T everywhere (then the launches are those of the uniform entry point).
+ * phases: initial phases (B, F, T) contiguous (:214-216, drawn by the caller).  post: bit 0 = inverse pre-emphasis y[n] = x[n] +
+ * 0.97 y[n-1] (the literal of :274-276, scipy.signal.lfilter([1], [1, -0.97])), bit 1 = clip to [-1, 1] (:192).
+ * frames: DEVICE int32 array of B frame counts, or NULL for T everywhere (the uniform kernels: one envelope, no per-utterance clamp).
  * Utterance b has T_b = frames[b] frames and L_b = hop * (T_b - 1) samples: reflect padding, overlap-add, envelope, inverse
  * pre-emphasis and clip are those of a T_b-frame utterance vocoded alone (bitwise).  Storage keeps the strides of T: feat rows and
  * phase columns t >= T_b are never read; wav is (B, hop * (T - 1)), row b written on [0, L_b) and zero after.  The kernels clamp
  * frames[b] into [n_fft / 2 / hop + 2, T] (the fewest frames the reflect padding takes; T itself is checked), so no value indexes
- * outside the workspace; validating frames is the caller's.  ws: st_gl_batch_workspace_floats() floats. */
+ * outside the workspace; validating frames is the caller's.  ws: st_gl_batch_workspace_floats() floats.  n_iter + 3 launches (+ 1: mel). */
+typedef struct st_gl_job {
+    const float* feat; long sb, st, sf; int n_in; const float* basis;       /* basis NULL: feat is linear, n_in = n_fft / 2 + 1 */
+    int normalized; float power; const float* phases; const int* frames;   /* frames NULL: T for every utterance */
+    float* wav; int B, T, n_iter, post;
+} st_gl_job;
 size_t st_gl_batch_workspace_floats(int B, int T, int n_fft, int hop, int win);
-int st_griffin_lim_batch(const float* feat, long sb, long st, long sf, int n_in, const float* basis, int normalized, float power,
-                         const float* phases, const int* frames, float* wav, int B, int T, int n_fft, int hop, int win, int n_iter,
-                         int post, float* ws, void* stream);
+int st_griffin_lim_batch(const st_gl_job* job, const st_framing* fr, float* ws, void* stream);
 
 /* ------------------------------------------------------------------ feature extraction (waveforms -> normalised spectrograms)
- * Replaces AudioProcessor.extract_feature_from_waveform (ref: src/audio.py:156-177) and AudioConverter.wave_to_feat's feature
- * and augmentation steps (:329-395, add_noise / snr_coeff :409-416, :434-437) for a ragged batch: utterance b is
- * x[off[b] .. off[b] + len[b]).  Each frame is the torch.stft frame (same conventions as st_stft_fwd, reflect padding at the
- * utterance's own length) of the pre-emphasised signal y[0] = s[0], y[i] = s[i] - preemph * s[i-1] (preemph 0: none), built on
- * the fly; the magnitude |X| gives linear = norm(|X|) and mel[m] = norm(sum_j |X|[fb_start[m] + j] * fb_w[fb_off[m] + j], j <
- * fb_cnt[m]) -- the Slaney / area-normalised filterbank as contiguous bands -- with norm(a) = clamp((20 log10(max(a, 1e-5)) - 20
- * + 100) / 100, 0, 1) (_amp_to_db, _normalize).  Outputs are time-major: mel (B, T_pad, n_mels), linear (B, T_pad, n_fft / 2 + 1)
- * (null: not written), frames t >= 1 + len[b] / hop written as 0 (SPEC_PAD_VALUE), T_pad >= 1 + max len / hop.
- * aug (B, Ta_pad, n_mels) (null: not written) is the augmented mel: its own framing aug_win[b] / aug_hop[b] (the time-stretched
- * win / hop of :366-373), and s = x + coeff_b n with coeff_b = sqrt(sum x^2 / sum n^2 * 10^(-snr_db[b] / 10)) over the utterance
- * (snr_db null, or NaN for an utterance: no noise).  n: `noise`, packed like x, or, when null, the built-in counter-based
- * generator (Philox4x32-10, standard normal by Box-Muller) of (seed, utt0 + b, sample index): no noise buffer exists.  utt0 is
- * the position of this call's first utterance in the caller's whole batch (0 for a batch issued in one call): a batch above 64
- * issued in several calls then draws the noise st_feature_noise() gives for each utterance's position in the batch.  Only the
- * generator reads utt0; off, len, aug_win, aug_hop, snr_db and the output rows are relative to this call.
- * Host arrays: off, len, aug_win, aug_hop, snr_db (B entries, read before the call returns); everything else is on the device.
+ * Host arrays (B entries, read before the call returns): off, len, and win / hop / snr_db of st_feat_aug; all else is on the device. */
+/* ragged batch of packed float32 waveforms: utterance b is x[off[b] .. off[b] + len[b]) of the n_samples in x; B <= 64 */
+typedef struct st_wave_batch { const float* x; long n_samples; const long* off; const int* len; int B; } st_wave_batch;
+/* banded mel filterbank (Slaney / area-normalised): mel[m] = sum_j |X|[start[m] + j] * w[off[m] + j], j < cnt[m] */
+typedef struct st_mel_bank { const int* start; const int* cnt; const int* off; const float* w; int n_mels; } st_mel_bank;
+/* the augmented framing of st_audio_features (a NULL st_feat_aug* or out == NULL: none).  out (B, Ta_pad, n_mels) is the augmented
+ * mel: its own framing win[b] / hop[b] (the time-stretched win / hop of src/audio.py:366-373), and s = x + coeff_b n with coeff_b =
+ * sqrt(sum x^2 / sum n^2 * 10^(-snr_db[b] / 10)) over the utterance (snr_db null, or NaN for an utterance: no noise).  n: `noise`,
+ * packed like x, or, when null, the built-in counter-based generator (Philox4x32-10, standard normal by Box-Muller) of (seed,
+ * utt0 + b, sample index): no noise buffer exists.  utt0 is the position of this call's first utterance in the caller's whole batch
+ * (0 for a batch issued in one call): a batch above 64 issued in several calls then draws the noise st_feature_noise() gives for
+ * each utterance's position in the batch.  Only the generator reads utt0; the arrays and the output rows are relative to this call. */
+typedef struct st_feat_aug { const int* win; const int* hop; const float* snr_db; const float* noise;
+                             unsigned long long seed; int utt0; float* out; int Ta_pad; } st_feat_aug;
+/* Replaces AudioProcessor.extract_feature_from_waveform (ref: src/audio.py:156-177) and AudioConverter.wave_to_feat's feature
+ * and augmentation steps (:329-395, add_noise / snr_coeff :409-416, :434-437) for a ragged batch.  Each frame is the torch.stft
+ * frame (same conventions as st_stft_fwd, reflect padding at the utterance's own length) of the pre-emphasised signal y[0] = s[0],
+ * y[i] = s[i] - preemph * s[i-1] (preemph 0: none), built on the fly; the magnitude |X| gives linear = norm(|X|) and mel[m] =
+ * norm(the band sum of st_mel_bank) with norm(a) = clamp((20 log10(max(a, 1e-5)) - 20 + 100) / 100, 0, 1) (_amp_to_db, _normalize).
+ * Outputs are time-major: mel (B, T_pad, n_mels), linear (B, T_pad, n_fft / 2 + 1) (null: not written), frames t >= 1 + len[b] / hop
+ * written as 0 (SPEC_PAD_VALUE), T_pad >= 1 + max len / hop; likewise aug->out with Ta_pad at the augmented framing.
  * Supported: n_fft in {512, 1024, 2048, 4096}, 0 < 2 * hop <= win <= n_fft for both framings, len[b] > n_fft / 2, B <= 64
- * (anything else returns -22).  ws: st_features_workspace_floats(B) floats.  One launch (clean + augmented framings as the
- * two z-slices of one grid), plus one before it for the per-utterance power sums when there is noise.  No atomics: bitwise
- * repeatable for a given seed. */
+ * (anything else returns -22, before any device call).  ws: st_features_workspace_floats(B) floats.  One launch (clean + augmented
+ * framings as the two z-slices of one grid), plus one before it for the per-utterance power sums when there is noise.  No atomics:
+ * bitwise repeatable for a given seed. */
 size_t st_features_workspace_floats(int B);
-int st_audio_features(const float* x, long n_samples, const float* noise, unsigned long long seed, const long* off, const int* len,
-                      const int* aug_win, const int* aug_hop, const float* snr_db, int B, int utt0, int n_fft, int win, int hop,
-                      float preemph, const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels, float* mel,
-                      float* linear, int T_pad, float* aug, int Ta_pad, float* ws, void* stream);
+int st_audio_features(const st_wave_batch* w, const st_framing* fr, float preemph, const st_mel_bank* fb, const st_feat_aug* aug,
+                      float* mel, float* linear, int T_pad, float* ws, void* stream);
 /* out[i] = the built-in generator's standard normal for (seed, utterance utt, sample i), i < n (for tests) */
 int st_feature_noise(float* out, long n, int utt, unsigned long long seed, void* stream);
-/* MFCC with derivatives (ref: AudioProcessor.extract_mfcc_from_waveform, src/audio.py:119-154) for a ragged batch packed as above
- * (host off / len, B <= 64): out (B, T_pad, 3 * n_mfcc).  Frame t of utterance b is the frame of st_audio_features' clean framing
- * (same pre-emphasis, reflect padding, window, filterbank and norm) at the caller's win / hop -- the reference's MFCC framing is
+/* MFCC with derivatives (ref: AudioProcessor.extract_mfcc_from_waveform, src/audio.py:119-154) for a ragged batch (st_wave_batch):
+ * out (B, T_pad, 3 * n_mfcc).  Frame t of utterance b is the frame of st_audio_features' clean framing
+ * (same pre-emphasis, reflect padding, window, filterbank and norm) at the caller's framing -- the reference's MFCC framing is
  * win = int(0.025 sr), hop = int(0.010 sr) in the model's n_fft.  Columns [0, n_mfcc): c[k] = sum_m dct[k, m] mel[m] over the
  * NORMALISED [0, 1] mel (librosa.feature.mfcc(S=mel, n_mfcc) = scipy.fftpack.dct(mel, axis=0, type=2, norm='ortho')[:n_mfcc]; the
  * reference hands it the normalised mel, kept here), dct (n_mfcc, n_mels) row-major on the device, tabulated by the caller:
@@ -1295,8 +1297,7 @@ int st_feature_noise(float* out, long n, int utt, unsigned long long seed, void*
  * framing.  A frame's bits depend on neither the batch nor the position in it.  Supported (anything else returns -22): n_fft in
  * {512, 1024, 2048, 4096}, 0 < 2 * hop <= win <= n_fft, len[b] > n_fft / 2, 1 <= n_mfcc <= n_mels <= 256, len[b] >= 8 * hop (T_b >= 9:
  * librosa refuses a width above the frame count), B <= 64.  Two launches (frames, then derivatives); no atomics, no workspace. */
-int st_audio_mfcc(const float* x, long n_samples, const long* off, const int* len, int B, int n_fft, int win, int hop, float preemph,
-                  const int* fb_start, const int* fb_cnt, const int* fb_off, const float* fb_w, int n_mels, const float* dct, int n_mfcc,
+int st_audio_mfcc(const st_wave_batch* w, const st_framing* fr, float preemph, const st_mel_bank* fb, const float* dct, int n_mfcc,
                   float* out, float* mel_out, int T_pad, void* stream);
 /* Phone segments (ref: AudioProcessor.segment, src/audio.py:94-117): out (S, max_len, D) contiguous, 16-byte aligned, from
  * feat (B, T_pad, D) with feat(b, t, d) = feat[b * sb + t * st + d] (strides in floats, st >= D).  Row i < seg_len[s] of segment s

@@ -187,6 +187,29 @@ class StPackedLinearJob(C.Structure):
                 ('n_split2', C.c_int), ('act2', C.c_int), ('mask2', C.c_void_p), ('ldmask2', C.c_int), ('y3_dst', StT16View)]
 
 
+class StFraming(C.Structure):
+    _fields_ = [('n_fft', C.c_int), ('win', C.c_int), ('hop', C.c_int)]
+
+
+class StGlJob(C.Structure):
+    _fields_ = [('feat', C.c_void_p), ('sb', C.c_long), ('st', C.c_long), ('sf', C.c_long), ('n_in', C.c_int), ('basis', C.c_void_p),
+                ('normalized', C.c_int), ('power', C.c_float), ('phases', C.c_void_p), ('frames', C.c_void_p), ('wav', C.c_void_p),
+                ('B', C.c_int), ('T', C.c_int), ('n_iter', C.c_int), ('post', C.c_int)]
+
+
+class StWaveBatch(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('n_samples', C.c_long), ('off', C.c_void_p), ('len', C.c_void_p), ('B', C.c_int)]
+
+
+class StMelBank(C.Structure):
+    _fields_ = [('start', C.c_void_p), ('cnt', C.c_void_p), ('off', C.c_void_p), ('w', C.c_void_p), ('n_mels', C.c_int)]
+
+
+class StFeatAug(C.Structure):
+    _fields_ = [('win', C.c_void_p), ('hop', C.c_void_p), ('snr_db', C.c_void_p), ('noise', C.c_void_p), ('seed', C.c_ulonglong),
+                ('utt0', C.c_int), ('out', C.c_void_p), ('Ta_pad', C.c_int)]
+
+
 P, I, F, Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/semitts.h
@@ -364,24 +387,22 @@ SIGNATURES = {
     'st_copy2d': [P, I, P, I, I, I, P],
     'st_mean_rows': [P, P, I, I, I, P],
     'st_istft_workspace_floats': [I, I, I, I, I],
-    'st_gl_workspace_floats': [I, I, I, I, I],
     'st_stft_fwd': [P, P, I, I, I, I, I, P],
     'st_istft': [P, P, I, I, I, I, I, P, P],
-    'st_griffin_lim': [P, C.c_long, C.c_long, C.c_long, I, F, P, P, I, I, I, I, I, I, I, P, P],
     'st_mel_to_linear': [P, C.c_long, C.c_long, C.c_long, P, P, I, I, I, I, I, I, P],
     'st_gl_batch_workspace_floats': [I, I, I, I, I],
-    'st_griffin_lim_batch': [P, C.c_long, C.c_long, C.c_long, I, P, I, F, P, P, P, I, I, I, I, I, I, I, P, P],
+    'st_griffin_lim_batch': [C.POINTER(StGlJob), C.POINTER(StFraming), P, P],
     'st_features_workspace_floats': [I],
-    'st_audio_features': [P, C.c_long, P, C.c_ulonglong, P, P, P, P, P, I, I, I, I, I, F, P, P, P, P, I, P, P, I, P, I, P, P],
+    'st_audio_features': [C.POINTER(StWaveBatch), C.POINTER(StFraming), F, C.POINTER(StMelBank), C.POINTER(StFeatAug), P, P, I, P, P],
     'st_feature_noise': [P, C.c_long, I, C.c_ulonglong, P],
-    'st_audio_mfcc': [P, C.c_long, P, P, I, I, I, I, F, P, P, P, P, I, P, I, P, P, I, P],
+    'st_audio_mfcc': [C.POINTER(StWaveBatch), C.POINTER(StFraming), F, C.POINTER(StMelBank), P, I, P, P, I, P],
     'st_segment_gather': [P, C.c_long, C.c_long, I, I, I, P, P, P, I, I, P, P],
     'st_resample_batch': [P, I, C.c_long, P, P, I, I, I, I, I, I, P, P, P, C.c_long, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,
              'st_gemm_wgrad_workspace_floats': C.c_size_t, 'st_gemm_wgrad_batch_workspace_floats': C.c_size_t, 'st_freq_loss_workspace_floats': C.c_size_t, 'st_attn_fin_split_workspace_floats': C.c_size_t, 'st_attn_rng_xchg_words': C.c_size_t, 'st_colreduce_workspace_floats': C.c_size_t, 'st_mt_blocks': C.c_size_t, 'st_mt_table_misses': C.c_long,
-             'st_bn_bank_workspace_floats': C.c_size_t, 'st_istft_workspace_floats': C.c_size_t, 'st_gl_workspace_floats': C.c_size_t,
+             'st_bn_bank_workspace_floats': C.c_size_t, 'st_istft_workspace_floats': C.c_size_t,
              'st_gl_batch_workspace_floats': C.c_size_t,
              'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t}
 

@@ -1,5 +1,5 @@
 """The reference's src/audio.py on the HIP kernels (semi_tts_amd/csrc/audio.hip, include/semitts.h).  Synthesis side: linear
-spectrogram -> waveform by Griffin-Lim (st_griffin_lim / st_stft_fwd / st_istft).
+spectrogram -> waveform by Griffin-Lim (st_griffin_lim_batch / st_stft_fwd / st_istft).
 
     conv = load_audio_transform(**config['data']['audio'])
     wav, sr = conv.feat_to_wave(linear_pred)          # (T, F) or (B, T, F), CPU or device tensor -> float64 numpy
@@ -201,9 +201,6 @@ def _run(feat_btf, phases, n_fft, hop, win, n_iter, normalized, power, post, bas
         raise ValueError('Griffin-Lim: phases of shape %s, expected %s' % (tuple(phases.shape), (B, F, T)))
     dev = feat_btf.device if feat_btf.is_cuda else _device()
     feat_btf = feat_btf.to(dev, torch.float32)
-    if basis is None and frames is None:
-        return ops.griffin_lim(feat_btf, phases.to(dev).contiguous(), n_fft, hop, win, n_iter=n_iter, normalized=normalized,
-                               power=power, post=post)
     return ops.griffin_lim_batch(feat_btf, phases.to(dev).contiguous(), n_fft, hop, win, n_iter=n_iter, normalized=normalized,
                                  power=power, post=post, basis=None if basis is None else basis(dev),
                                  frames=None if frames is None else torch.from_numpy(frames).to(dev))

@@ -1841,18 +1841,9 @@ GL_INV_PREEMPHASIS, GL_CLIP = 1, 2
 
 
 def griffin_lim(feat, phases, n_fft, hop, win, n_iter=30, normalized=False, power=1.0, post=0):
-    """st_griffin_lim: feat (B, T, F) in any strides (the decoder's (B, T, F) output or a transposed (B, F, T) magnitude),
-    phases (B, F, T) contiguous -> waveform (B, hop * (T - 1)).  post: GL_INV_PREEMPHASIS | GL_CLIP."""
-    assert feat.dim() == 3 and feat.shape[2] == n_fft // 2 + 1
-    B, T, F = feat.shape
-    assert phases.shape == (B, F, T) and phases.is_contiguous()
-    lib = _lib.load()
-    ws = _audio_ws(lib.st_gl_workspace_floats, B, T, n_fft, hop, win, feat.device)
-    wav = torch.empty(B, hop * (T - 1), device=feat.device, dtype=torch.float32)
-    sb, st, sf = feat.stride()
-    check(lib.st_griffin_lim(_p(feat), sb, st, sf, int(bool(normalized)), float(power), _p(phases), _p(wav), B, T, n_fft, hop, win,
-                             int(n_iter), int(post), _p(ws), stream_handle()), 'st_griffin_lim')
-    return wav
+    """griffin_lim_batch() on a linear spectrogram with one frame count: feat (B, T, F) in any strides (the decoder's (B, T, F) output
+    or a transposed (B, F, T) magnitude), phases (B, F, T) contiguous -> waveform (B, hop * (T - 1)).  post: GL_INV_PREEMPHASIS | GL_CLIP."""
+    return griffin_lim_batch(feat, phases, n_fft, hop, win, n_iter=n_iter, normalized=normalized, power=power, post=post)
 
 
 MEL_TO_LINEAR_TILE = 16          # frames per workgroup of st_mel_to_linear (MEL_TILE in audio.hip): the tests straddle it
@@ -1874,10 +1865,10 @@ def mel_to_linear(mel, basis, normalized=True, take_abs=False):
 
 
 def griffin_lim_batch(feat, phases, n_fft, hop, win, n_iter=30, normalized=False, power=1.0, post=0, basis=None, frames=None):
-    """st_griffin_lim_batch: griffin_lim() for utterances of their own lengths and for mel input.  feat (B, T, F) linear, or
-    (B, T, n_mels) with basis (n_mels, F) as mel_to_linear() takes it; frames: device int32 (B,) frame counts (None: T for all).
-    -> waveform (B, hop * (T - 1)), row b filled on [0, hop * (frames[b] - 1)) and zero after.  feat rows and phase columns
-    beyond an utterance's frames are never read."""
+    """st_griffin_lim_batch, the one vocoder entry: utterances of one length or of their own, linear or mel input.  feat (B, T, F)
+    linear in any strides, or (B, T, n_mels) with basis (n_mels, F) as mel_to_linear() takes it; phases (B, F, T) contiguous; frames:
+    device int32 (B,) frame counts (None: T for all).  -> waveform (B, hop * (T - 1)), row b filled on [0, hop * (frames[b] - 1))
+    and zero after.  feat rows and phase columns beyond an utterance's frames are never read."""
     F = n_fft // 2 + 1
     assert feat.dim() == 3 and feat.shape[2] == (F if basis is None else basis.shape[0])
     B, T, n_in = feat.shape
@@ -1888,14 +1879,42 @@ def griffin_lim_batch(feat, phases, n_fft, hop, win, n_iter=30, normalized=False
     ws = _audio_ws(lib.st_gl_batch_workspace_floats, B, T, n_fft, hop, win, feat.device)
     wav = torch.empty(B, hop * (T - 1), device=feat.device, dtype=torch.float32)
     sb, st, sf = feat.stride()
-    check(lib.st_griffin_lim_batch(_p(feat), sb, st, sf, n_in, _p(basis) if basis is not None else None, int(bool(normalized)),
-                                   float(power), _p(phases), _p(frames, torch.int32) if frames is not None else None, _p(wav), B, T,
-                                   n_fft, hop, win, int(n_iter), int(post), _p(ws), stream_handle()), 'st_griffin_lim_batch')
+    job = _lib.StGlJob(feat=_p(feat), sb=sb, st=st, sf=sf, n_in=n_in, basis=_p(basis), normalized=int(bool(normalized)), power=float(power),
+                       phases=_p(phases), frames=_p(frames, torch.int32), wav=_p(wav), B=B, T=T, n_iter=int(n_iter), post=int(post))
+    check(lib.st_griffin_lim_batch(C.byref(job), C.byref(_lib.StFraming(n_fft, win, hop)), _p(ws), stream_handle()), 'st_griffin_lim_batch')
     return wav
 
 
 # --------------------------------------------------------------------------------------------- feature extraction (src/audio.py)
 FEATURES_MAX_BATCH = 64          # utterances per st_audio_features call (its per-utterance metadata travels by value)
+
+
+def _chunks(B):
+    """(first utterance, count) of every call a batch of B utterances is issued in"""
+    return [(b0, min(FEATURES_MAX_BATCH, B - b0)) for b0 in range(0, B, FEATURES_MAX_BATCH)]
+
+
+def _host_ptr(a, b0):
+    """address of row b0 of a contiguous host array (None stays None)"""
+    return None if a is None else a.ctypes.data + b0 * a.itemsize
+
+
+def _host_off_lens(off, lens):
+    return np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(lens, dtype=np.int32)
+
+
+def _wave_operands(x, n_fft, win, hop, fb):
+    """the operands st_audio_features and st_audio_mfcc share: (StWaveBatch without its per-call off / len / B, StFraming, StMelBank)"""
+    assert x.dim() == 1 and x.is_contiguous()
+    fs, fc, fo, fw = fb
+    return (_lib.StWaveBatch(x=_p(x), n_samples=x.numel()), _lib.StFraming(n_fft, win, hop),
+            _lib.StMelBank(start=_p(fs, torch.int32), cnt=_p(fc, torch.int32), off=_p(fo, torch.int32), w=_p(fw), n_mels=fs.shape[0]))
+
+
+def _wave_chunk(w, off, lens, b0, nb):
+    """points the StWaveBatch `w` (modified in place) at utterances [b0, b0 + nb) and returns a reference to it"""
+    w.off, w.len, w.B = _host_ptr(off, b0), _host_ptr(lens, b0), nb
+    return C.byref(w)
 
 
 def audio_features(x, off, lens, n_fft, win, hop, preemph, fb, T_pad, with_linear=True, aug_win=None, aug_hop=None, Ta_pad=None,
@@ -1906,12 +1925,11 @@ def audio_features(x, off, lens, n_fft, win, hop, preemph, fb, T_pad, with_linea
     utterance) are given, with noise at snr_db[b] (NaN: none) from `noise` (packed like x) or the built-in generator of `seed`.
     Batches above FEATURES_MAX_BATCH are issued in chunks of it; the generator is keyed on the position in the whole batch
     (feature_noise(n, b, seed) is utterance b's noise whatever B is)."""
-    assert x.dim() == 1 and x.is_contiguous() and (noise is None or (noise.shape == x.shape and noise.is_contiguous()))
-    fs, fc, fo, fw = fb
-    n_mels, F = fs.shape[0], n_fft // 2 + 1
+    assert noise is None or (noise.shape == x.shape and noise.is_contiguous())
+    w, fr, bank = _wave_operands(x, n_fft, win, hop, fb)
+    n_mels, F = bank.n_mels, n_fft // 2 + 1
     B = len(lens)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    off, lens = _host_off_lens(off, lens)
     use_aug = aug_win is not None
     dev = x.device
     mel = torch.empty(B, T_pad, n_mels, device=dev, dtype=torch.float32)
@@ -1924,14 +1942,11 @@ def audio_features(x, off, lens, n_fft, win, hop, preemph, fb, T_pad, with_linea
         snr_db = np.ascontiguousarray(snr_db, dtype=np.float32)
     lib = _lib.load()
     ws = torch.empty(lib.st_features_workspace_floats(min(B, FEATURES_MAX_BATCH)), device=dev, dtype=torch.float32)
-    hp = lambda a, b0: None if a is None else a.ctypes.data + b0 * a.itemsize     # noqa: E731  (host array from row b0)
-    for b0 in range(0, B, FEATURES_MAX_BATCH):
-        nb = min(FEATURES_MAX_BATCH, B - b0)
-        check(lib.st_audio_features(_p(x), x.numel(), _p(noise), int(seed) & (2 ** 64 - 1), hp(off, b0), hp(lens, b0),
-                                    hp(aug_win, b0), hp(aug_hop, b0), hp(snr_db, b0), nb, b0, n_fft, win, hop, float(preemph),
-                                    _p(fs, torch.int32), _p(fc, torch.int32), _p(fo, torch.int32), _p(fw), n_mels, _p(mel[b0:]),
-                                    _p(lin[b0:]) if lin is not None else None, T_pad, _p(aug[b0:]) if aug is not None else None,
-                                    Ta_pad or 0, _p(ws), stream_handle()), 'st_audio_features')
+    a = _lib.StFeatAug(noise=_p(noise), seed=int(seed) & (2 ** 64 - 1), Ta_pad=Ta_pad or 0)
+    for b0, nb in _chunks(B):
+        a.win, a.hop, a.snr_db, a.utt0, a.out = _host_ptr(aug_win, b0), _host_ptr(aug_hop, b0), _host_ptr(snr_db, b0), b0, _p(aug[b0:]) if use_aug else None
+        check(lib.st_audio_features(_wave_chunk(w, off, lens, b0, nb), C.byref(fr), float(preemph), C.byref(bank), C.byref(a), _p(mel[b0:]),
+                                    _p(lin[b0:]) if with_linear else None, T_pad, _p(ws), stream_handle()), 'st_audio_features')
     return mel, lin, aug
 
 
@@ -1949,23 +1964,18 @@ def audio_mfcc(x, off, lens, n_fft, win, hop, preemph, fb, dct, T_pad, with_mel=
     """st_audio_mfcc on a ragged batch packed as for audio_features: dct (n_mfcc, n_mels) float32 on the device (audio.mfcc_dct);
     win / hop: the MFCC framing.  -> (mfcc (B, T_pad, 3 * n_mfcc): cepstra, first and second derivatives; mel (B, T_pad, n_mels) at
     that framing, or None without with_mel).  Batches above FEATURES_MAX_BATCH are issued in chunks of it."""
-    assert x.dim() == 1 and x.is_contiguous()
-    fs, fc, fo, fw = fb
-    n_mels = fs.shape[0]
+    w, fr, bank = _wave_operands(x, n_fft, win, hop, fb)
+    n_mels = bank.n_mels
     assert dct.dim() == 2 and dct.shape[1] == n_mels and dct.is_contiguous()
     n_mfcc = dct.shape[0]
     B = len(lens)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    off, lens = _host_off_lens(off, lens)
     out = torch.empty(B, T_pad, 3 * n_mfcc, device=x.device, dtype=torch.float32)
     mel = torch.empty(B, T_pad, n_mels, device=x.device, dtype=torch.float32) if with_mel else None
     lib = _lib.load()
-    hp = lambda a, b0: a.ctypes.data + b0 * a.itemsize     # noqa: E731  (host array from row b0)
-    for b0 in range(0, B, FEATURES_MAX_BATCH):
-        nb = min(FEATURES_MAX_BATCH, B - b0)
-        check(lib.st_audio_mfcc(_p(x), x.numel(), hp(off, b0), hp(lens, b0), nb, n_fft, win, hop, float(preemph), _p(fs, torch.int32),
-                                _p(fc, torch.int32), _p(fo, torch.int32), _p(fw), n_mels, _p(dct), n_mfcc, _p(out[b0:]),
-                                _p(mel[b0:]) if mel is not None else None, T_pad, stream_handle()), 'st_audio_mfcc')
+    for b0, nb in _chunks(B):
+        check(lib.st_audio_mfcc(_wave_chunk(w, off, lens, b0, nb), C.byref(fr), float(preemph), C.byref(bank), _p(dct), n_mfcc, _p(out[b0:]),
+                                _p(mel[b0:]) if with_mel else None, T_pad, stream_handle()), 'st_audio_mfcc')
     return out, mel
 
 
@@ -2006,8 +2016,7 @@ def resample_batch(x, off, lens, o, n, first, table, first_min, first_max, out=N
     assert table.dim() == 2 and table.shape[0] == n and table.is_contiguous() and table.dtype == torch.float32
     assert first.shape == (n,) and first.dtype == torch.int32 and first.is_contiguous()
     B = len(lens)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    off, lens = _host_off_lens(off, lens)
     out_lens = (lens.astype(np.int64) * n + o - 1) // o
     out_off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(out_lens)[:-1]]), dtype=np.int64)
     total = int(out_lens.sum())
@@ -2015,10 +2024,8 @@ def resample_batch(x, off, lens, o, n, first, table, first_min, first_max, out=N
         out = torch.empty(total, device=x.device, dtype=torch.float32)
     assert out.dim() == 1 and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == total and out.device == x.device
     lib = _lib.load()
-    hp = lambda a, b0: a.ctypes.data + b0 * a.itemsize     # noqa: E731  (host array from row b0)
-    for b0 in range(0, B, FEATURES_MAX_BATCH):
-        nb = min(FEATURES_MAX_BATCH, B - b0)
-        check(lib.st_resample_batch(_p(x, x.dtype), int(x.dtype == torch.int16), x.numel(), hp(off, b0), hp(lens, b0), nb, int(o), int(n),
-                                    table.shape[1], int(first_min), int(first_max), _p(first, torch.int32), _p(table), _p(out), total,
-                                    hp(out_off, b0), stream_handle()), 'st_resample_batch')
+    for b0, nb in _chunks(B):
+        check(lib.st_resample_batch(_p(x, x.dtype), int(x.dtype == torch.int16), x.numel(), _host_ptr(off, b0), _host_ptr(lens, b0), nb,
+                                    int(o), int(n), table.shape[1], int(first_min), int(first_max), _p(first, torch.int32), _p(table),
+                                    _p(out), total, _host_ptr(out_off, b0), stream_handle()), 'st_resample_batch')
     return out, out_off, out_lens

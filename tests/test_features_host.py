@@ -114,3 +114,49 @@ def test_feature_argument_checks_fire_before_the_device(monkeypatch, tmp_path):
     audio.write_wav(tmp_path / 'b.wav', np.zeros(4000), 16000)
     with pytest.raises(ValueError, match='Sample rate mismatch'):
         conv.wave_to_feat(tmp_path / 'b.wav')
+
+
+def test_extractor_entries_refuse_what_they_cannot_frame():
+    """st_audio_features and st_audio_mfcc refuse a bad batch, framing or filterbank with the entry's own name in the message, before
+    anything is launched (the checks are host arithmetic on the operand structs: they return here, without a device; the device
+    pointers are host memory nobody reads)"""
+    import ctypes as C
+    from semi_tts_amd import _lib
+    lib = _lib.load()
+    raw = C.create_string_buffer(1 << 12)
+    p = (C.addressof(raw) + 255) & ~255          # 256-byte aligned, like a device allocation
+
+    def call(entry, lens=(4000,), off=None, n_samples=1 << 20, fr=(1024, 1024, 256), T_pad=None, n_mels=40, n_mfcc=13, aug=None, x=p,
+             batch=True):
+        lens = np.asarray(lens, dtype=np.int32)
+        off = np.asarray(np.arange(len(lens)) * 8000 if off is None else off, dtype=np.int64)
+        w = _lib.StWaveBatch(x=x, n_samples=n_samples, off=off.ctypes.data, len=lens.ctypes.data, B=len(lens))
+        bank = _lib.StMelBank(start=p, cnt=p, off=p, w=p, n_mels=n_mels)
+        T_pad = 1 + int(lens.max()) // max(fr[2], 1) if T_pad is None else T_pad
+        wp, frp = C.byref(w) if batch else None, C.byref(_lib.StFraming(*fr))
+        if entry == 'st_audio_features':
+            rc = lib.st_audio_features(wp, frp, 0.97, C.byref(bank), None if aug is None else C.byref(aug), p, p, T_pad, p, None)
+        else:
+            rc = lib.st_audio_mfcc(wp, frp, 0.97, C.byref(bank), p, n_mfcc, p, None, T_pad, None)
+        return rc, lib.st_last_error().decode()
+
+    def refused(entry, why, **kw):
+        rc, msg = call(entry, **kw)
+        assert rc != 0 and msg.startswith(entry + ': ') and why in msg, (rc, msg)
+
+    for entry in ('st_audio_features', 'st_audio_mfcc'):
+        refused(entry, 'not supported', fr=(1536, 1024, 256))
+        refused(entry, 'need 0 < 2 * hop <= win <= n_fft', fr=(2048, 1102, 600))
+        refused(entry, 'reflect padding', lens=(4000, 512))                       # n_fft / 2 samples
+        refused(entry, 'outside the', lens=(4000, 4000), off=(0, 4001), n_samples=8000)
+        refused(entry, 'outside [1, 64]', lens=(4000,) * 65)
+        refused(entry, 'T_pad', lens=(4000, 4096), T_pad=16)                      # the longest utterance has 17 frames
+        refused(entry, 'null pointer', batch=False)
+        refused(entry, 'null pointer', x=None)
+    aug_win, aug_hop = np.asarray([1102, 1102], dtype=np.int32), np.asarray([275, 600], dtype=np.int32)
+    refused('st_audio_features', 'augmented framing needs', aug=_lib.StFeatAug(out=p, Ta_pad=64))
+    refused('st_audio_features', 'augmented framing needs 0 <', fr=(2048, 1024, 256), lens=(4000, 4000),
+            aug=_lib.StFeatAug(win=aug_win.ctypes.data, hop=aug_hop.ctypes.data, out=p, Ta_pad=64))
+    refused('st_audio_features', 'first utterance index', aug=_lib.StFeatAug(utt0=-1))
+    refused('st_audio_mfcc', 'derivatives need at least 9', fr=(512, 512, 128), lens=(4000, 8 * 128 - 1))
+    refused('st_audio_mfcc', 'n_mfcc', n_mels=12)

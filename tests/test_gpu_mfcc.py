@@ -156,6 +156,31 @@ def test_16k_n_fft_512(dev):
         assert _maxabs(mel[b, :T], r_mel.T) <= MEL_TOL
 
 
+def test_batch_across_the_chunk_boundary(dev):
+    """FEATURES_MAX_BATCH + 1 utterances go out as two st_audio_mfcc calls (64 + 1): every utterance's rows are bitwise those of the
+    utterance extracted alone (a frame's bits depend on neither the batch nor the position in it), rows past its frames are zero"""
+    c16 = load_audio_transform(**AUDIO_16K)
+    n_fft, win, hop = 512, 32, 16
+    B = ops.FEATURES_MAX_BATCH + 1
+    lens = np.array([257 + b for b in range(B)])                                 # 17 .. 21 frames: above n_fft / 2 samples and 9 frames
+    frames = 1 + lens // hop
+    assert B == 65 and frames.min() == 17 and frames.max() == 21
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    x = torch.from_numpy(_speech(int(lens.sum()), 90, sr=16000)).to(dev)
+    fb, dct, T_pad = c16.filterbank(dev), c16.mfcc_table(dev), int(frames.max())
+
+    def run(off, lens):
+        return ops.audio_mfcc(x, off, lens, n_fft, win, hop, c16.preemphasis_coeff, fb, dct, T_pad, with_mel=True)
+
+    mfcc, mel = run(off, lens)
+    assert mfcc.shape == (B, T_pad, 39) and mel.shape == (B, T_pad, 40)
+    for b in range(B):
+        T = int(frames[b])
+        alone, alone_mel = run(off[b:b + 1], lens[b:b + 1])
+        assert torch.equal(mfcc[b], alone[0]) and torch.equal(mel[b], alone_mel[0]), b
+        assert bool((mfcc[b, T:] == 0).all()) and bool((mel[b, T:] == 0).all()) and bool((mfcc[b, :T] != 0).any()), b
+
+
 def test_extract_mfcc_from_waveform(conv, dev, wavs, batch, tmp_path):
     x = torch.from_numpy(wavs[2])
     got = conv.extract_mfcc_from_waveform(x[None])

@@ -234,6 +234,9 @@ def test_ragged_through_the_converter(dev, dims, T, frames):
 
 @pytest.mark.parametrize('kind', ['linear', 'mel'])
 def test_frames_none_is_the_uniform_vocoder(dev, mel_case, kind):
+    """ops.griffin_lim is ops.griffin_lim_batch without basis / frames since the uniform entry point was removed, so the first linear
+    assertion compares one routine with itself; the second of each kind (frames = T everywhere against frames = None) still compares
+    the ragged kernels with the uniform ones"""
     from semi_tts_amd import ops
     c = mel_case
     ph = torch.from_numpy(c['phases']).to(dev)

@@ -268,3 +268,28 @@ def test_vocode_flags(capsys):
         with pytest.raises(SystemExit):
             main.parse_args(['--config', 'c'] + argv)
     capsys.readouterr()
+
+
+def test_vocoder_entry_refuses_what_it_cannot_vocode():
+    """st_griffin_lim_batch, the one vocoder entry, refuses a bad job before anything is launched (host arithmetic on the job and
+    framing structs: it returns here, without a device; the device pointers are host memory nobody reads)"""
+    import ctypes as C
+    from semi_tts_amd import _lib
+    lib = _lib.load()
+    raw = C.create_string_buffer(1 << 12)
+    p = (C.addressof(raw) + 255) & ~255          # 256-byte aligned, like a device allocation
+    fr = _lib.StFraming(n_fft=1024, win=1024, hop=256)
+
+    def refused(why, **kw):
+        job = _lib.StGlJob(**dict(dict(feat=p, sb=12 * 513, st=513, sf=1, n_in=513, normalized=1, power=1.0, phases=p, wav=p, B=3, T=12,
+                                       n_iter=2, post=3), **kw))
+        rc = lib.st_griffin_lim_batch(C.byref(job), C.byref(fr), p, None)
+        msg = lib.st_last_error().decode()
+        assert rc != 0 and msg.startswith('st_griffin_lim_batch: ') and why in msg, (rc, msg)
+
+    refused('power must be 1', basis=p, n_in=80, sb=12 * 80, st=80, power=1.5)
+    refused('bins, expected', n_in=512)
+    refused('bad n_iter', post=4)
+    refused('bad batch', T=1)
+    assert lib.st_griffin_lim_batch(None, C.byref(fr), p, None) != 0 and 'null' in lib.st_last_error().decode()
+    assert lib.st_griffin_lim_batch(C.byref(_lib.StGlJob()), None, p, None) != 0 and 'null' in lib.st_last_error().decode()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Griffin-Lim vocoder (semi_tts_amd.audio, st_griffin_lim) on a C2 batch: 32 utterances x 258 frames of a normalised linear
+"""Griffin-Lim vocoder (semi_tts_amd.audio, st_griffin_lim_batch) on a C2 batch: 32 utterances x 258 frames of a normalised linear
 spectrogram (n_fft 2048, hop 275, win 1102), 30 iterations, denormalisation + inverse pre-emphasis + clip included.  One JSON line:
 ms per batch, audio seconds per second, launches, the estimated floors (`roofline`) from the kernels' byte counts, and the same
 algorithm as torch CPU STFT / iSTFT on the same inputs (`cpu_baseline`, fp32, 16 threads; --cpu-fp64 adds the fp64 oracle).

@@ -4,9 +4,11 @@ hop 275 / win 1102, 80 mels, 30 iterations, denormalisation + inverse pre-emphas
 
   mel_to_linear     the product alone: ms, its bytes (mel in, basis once, output out) and the fraction of the HBM floor of those bytes
   gl_from_mel / gl_from_linear     Griffin-Lim through st_griffin_lim_batch from each input kind
-  batch_uniform / griffin_lim      st_griffin_lim_batch(frames=NULL, basis=NULL) against st_griffin_lim (the same launches)
+  batch_uniform / griffin_lim      ops.griffin_lim_batch(frames=None, basis=None) against ops.griffin_lim.  The two are ONE routine since the
+                    uniform entry point st_griffin_lim was removed (ops.griffin_lim calls griffin_lim_batch): the row times one code
+                    path twice and is kept so that the figures under profiles/ stay comparable
   ragged / ragged_as_singles / ragged_as_uniform     32 lengths spread evenly over 129 .. 258 frames in one ragged call, as 32
-                    single calls of st_griffin_lim, and as the uniform T = 258 batch (which vocodes the padding too)
+                    single calls of ops.griffin_lim, and as the uniform T = 258 batch (which vocodes the padding too)
 
 Every variant is warmed up, then the variants are timed in turn, round after round (device events around each call), so drift of
 the machine falls on all of them alike; per variant: the median, the minimum and the spread (max - min) / median over the rounds.
