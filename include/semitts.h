@@ -1101,6 +1101,32 @@ int st_ctc_forced_align(const float* prob, int B, int T, int V, const int32_t* l
                         float* score /* (B) */, int32_t* path /* (B, T) */,
                         int32_t* tok_start /* (B, L) */, int32_t* tok_end /* (B, L) */, void* ws, void* stream);
 
+/* Dynamic time warping of B ragged pairs of feature sequences: the cheapest monotone path through the grid of frame distances, its cost
+ * and the path (the warp under mel-cepstral distortion, semi_tts_amd.metrics.mcd; the reference has no such measure).
+ * x(b, i, k) = x[b x_sb + i x_st + k], likewise y; strides in floats.  Only the columns k in [d0, d1) are read.  Pair b is the first
+ * n = x_len[b] rows of x against the first m = y_len[b] rows of y (lengths (B) int32 on the device, NULL = all Tx / Ty; clamped to
+ * [0, Tx] / [0, Ty]); nothing beyond is read for its value.
+ * Cost: d(i, j) = scale * sqrtf(sum_{k = d0}^{d1 - 1} (x[i,k] - y[j,k])^2), the sum in fp32 over ascending k (whether the compiler
+ * contracts it to fma is not specified).  Recurrence: D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), predecessors outside
+ * the grid absent, D(0, 0) = d(0, 0); the addition is ONE fp32 add of the chosen predecessor and d.  Ties: the diagonal wins, then
+ * (i-1, j), then (i, j-1) (a candidate replaces the best only when strictly smaller).  This is the unweighted symmetric step pattern.
+ * Outputs: total (B) = D(n-1, m-1); path_len (B) = P, the cells on the path traced back from (n-1, m-1); path (B, Tx + Ty - 1, 2) int32,
+ * path[b, p, :] = (i_p, j_p) for p < P in forward order from (0, 0) to (n-1, m-1), -1 for p >= P.  path == NULL: only total and path_len.
+ * Without raising: n == 0 or m == 0, or a NaN among the read columns of the valid rows of either side: total NaN, path_len 0, path -1
+ * everywhere.  (Infinite inputs are outside the contract: the path is still a valid one, its cost may be NaN.)
+ * fp32 compare / add only, no float atomics: a pair's outputs depend on that pair alone (bitwise repeatable, independent of B, of the
+ * pair's position in the batch and of what lies beyond its lengths, NaN included).  One launch (the trace-back is part of it), no host read.
+ * Limits (-22 past them): B >= 1, 1 <= Tx, Ty <= 4096, 0 <= d0 < d1, d1 - d0 <= 64, x_st and y_st >= d1, x_sb and y_sb >= 0, scale finite
+ * and positive.
+ * ws: st_dtw_workspace_bytes(B, Tx, Ty) bytes, no initialisation needed -- 0 (ws may be NULL) when the 2-bit back-pointers of a
+ * (Tx, Ty) grid fit LDS beside the three rolling diagonals, which utterances of a few seconds at a 10 ms hop do. */
+size_t st_dtw_workspace_bytes(int B, int Tx, int Ty);
+int st_dtw_batch(const float* x, long x_sb, long x_st, const int32_t* x_len /* NULL = all Tx */, int Tx,
+                 const float* y, long y_sb, long y_st, const int32_t* y_len /* NULL = all Ty */, int Ty,
+                 int B, int d0, int d1, float scale,
+                 float* total /* (B) */, int32_t* path_len /* (B) */, int32_t* path /* (B, Tx + Ty - 1, 2) or NULL */,
+                 void* ws, void* stream);
+
 /* The trainer's scalar arithmetic on loss values as one launch (ref: bin/train_vqvae.py:208-233: total_loss = asr_weight * asr_loss +
  * tts_weight * (mel_loss + linear_loss) + unpair_speech_weight * ... -- a chain of one-element torch kernels there):
  * *outs[j] = sum_i W[j * n + i] * *xs[i] for j < m (m <= 4 outputs, n <= ST_SCALAR_MAX terms, W on the host; in rows j > 0 a zero weight means the term is not a member of that sum).

@@ -22,6 +22,7 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --resample      (files of any sample rate)
     python main.py --resample-wav-dir DIR --resample-out DIR2 --resample-rate 16000 [--batch-size 32]
     python main.py --config config/supervised.yaml --feat-wav-dir DIR --feat mfcc|mel|linear [--segment-file FILE --min-segment-len 2]
+    python main.py --config config/supervised.yaml --mcd-wav-dir SYN --mcd-ref-dir REF [--mcd-path --batch-size 32]
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
 `--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
 (semi_tts_amd/ngram.py: a plain .npy of shape (V^(order-1), V) in the layout of the reference's NgramPrior, src/lm.py:233-290) on the host.
@@ -36,6 +37,9 @@ them; `--resample-wav-dir` converts a directory of .wav files to another rate an
 `--feat-wav-dir` writes the MFCC (13 cepstra and their two derivatives, src/audio.py:119-154), mel or linear features of .wav files as
 <stem>-<feat>.npy and, with `--segment-file` (the segments.csv of --align-wav-dir), the same cut at the phone boundaries as
 <stem>-<feat>-seg.npy (solver.FeatureWriter; the reference's segment_file / segment_feat / min_segment_len, src/audio.py:309-354).
+`--mcd-wav-dir` (not a mode of the reference) scores synthesised .wav files against the recordings of `--mcd-ref-dir` by mel-cepstral
+distortion along a dynamic-time-warping path (solver.McdScorer, semi_tts_amd.metrics.mcd): mcd.csv, one row per pair, and with
+`--mcd-path` the warp of every pair as <key>.dtw.npy.
 """
 import argparse
 import os
@@ -123,6 +127,12 @@ parser.add_argument('--segment-file', default=None, type=str, help='--feat-wav-d
                     '--align-wav-dir); also write <stem>-<feat>-seg.npy (segments, longest piece, dim), the feature cut at its boundaries')
 parser.add_argument('--min-segment-len', default=None, type=int, help='--segment-file: the fewest frames of a segment; a shorter piece joins '
                     'the next one (default 2)')
+parser.add_argument('--mcd-wav-dir', default=None, type=str, help='score the synthesised .wav files of this directory (sorted by name, batched by '
+                    '--batch-size) against their recordings in --mcd-ref-dir by mel-cepstral distortion along a DTW path on the GPU: '
+                    '<logdir>/<name>/mcd.csv (file,frames,ref_frames,path_len,mcd_db); no checkpoint, no model')
+parser.add_argument('--mcd-ref-dir', default=None, type=str, help='--mcd-wav-dir: the directory of the recordings, <key>.wav for every synthesised '
+                    'file (key: its name up to the first ".", without one trailing "-pred")')
+parser.add_argument('--mcd-path', action='store_true', help='--mcd-wav-dir: also write the warp of every pair as <key>.dtw.npy, (path_len, 2) int32')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -215,6 +225,17 @@ def parse_args(argv=None):
         parser.error('--feat, --segment-file and --min-segment-len belong to --feat-wav-dir; they need that flag')
     if paras.min_segment_len is None:
         paras.min_segment_len = 2
+    if paras.mcd_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir'):
+            if getattr(paras, flag):
+                parser.error('--mcd-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--mcd-wav-dir does not combine with --dev-batches')
+        if paras.config is None or paras.mcd_ref_dir is None:
+            parser.error('--mcd-wav-dir needs --config (its data.audio) and --mcd-ref-dir DIR (the recordings)')
+    elif paras.mcd_ref_dir is not None or paras.mcd_path:
+        parser.error('--mcd-ref-dir and --mcd-path belong to --mcd-wav-dir; they need that flag')
     if paras.gen_wav_feat != 'linear' and not (paras.gen_specgram and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
@@ -292,6 +313,9 @@ def main(argv=None):
         mode = 'test'
     elif paras.feat_wav_dir is not None:
         from semi_tts_amd.solver import FeatureWriter as Solver
+        mode = 'test'
+    elif paras.mcd_wav_dir is not None:
+        from semi_tts_amd.solver import McdScorer as Solver
         mode = 'test'
     elif paras.transcribe_wav_dir is not None:
         from semi_tts_amd.solver import Transcriber as Solver

@@ -263,6 +263,8 @@ SIGNATURES = {
     'st_ctc_beam_search_lm': [P, I, I, I, P, I, I, I, I, F, P, I, I, P, P, P, P, P],
     'st_ctc_align_workspace_bytes': [I, I, I],
     'st_ctc_forced_align': [P, I, I, I, P, P, I, P, I, I, F, P, P, P, P, P, P],
+    'st_dtw_workspace_bytes': [I, I, I],
+    'st_dtw_batch': [P, C.c_long, C.c_long, P, I, P, C.c_long, C.c_long, P, I, I, I, I, F, P, P, P, P, P],
     'st_scalar_combine': [P, I, P, I, P, P],
     'st_scalar_fanout': [P, P, I, P, P],
     'st_softmax_bwd': [P, P, P, C.c_float, P, P, I, I, P],
@@ -404,7 +406,8 @@ _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t,
              'st_gemm_wgrad_workspace_floats': C.c_size_t, 'st_gemm_wgrad_batch_workspace_floats': C.c_size_t, 'st_freq_loss_workspace_floats': C.c_size_t, 'st_attn_fin_split_workspace_floats': C.c_size_t, 'st_attn_rng_xchg_words': C.c_size_t, 'st_colreduce_workspace_floats': C.c_size_t, 'st_mt_blocks': C.c_size_t, 'st_mt_table_misses': C.c_long,
              'st_bn_bank_workspace_floats': C.c_size_t, 'st_istft_workspace_floats': C.c_size_t,
              'st_gl_batch_workspace_floats': C.c_size_t,
-             'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t}
+             'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t,
+             'st_dtw_workspace_bytes': C.c_size_t}
 
 _lib = None
 

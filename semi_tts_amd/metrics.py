@@ -5,6 +5,13 @@ utterance.  Here one HIP launch per batch (st_ctc_greedy_edit_distance) gives ev
 and reference length as device tensors; nothing is read back until somebody asks for a Python number.
 
     from semi_tts_amd.metrics import cal_per        # replaces `from src.util import cal_per` (bin/train_vqvae.py:11)
+
+Mel-cepstral distortion along a dynamic-time-warping path (MCD-DTW), the objective distance between a synthesised utterance and the
+recording it imitates (the reference has no such measure): `dtw` warps two feature sequences of differing lengths onto each other in
+one HIP launch per batch (st_dtw_batch, semi_tts_amd/csrc/dtw.hip), `mcd` is the metric on the project's MFCC.
+
+    from semi_tts_amd.metrics import mcd
+    mcd_db, path_len, path = mcd(conv.extract_mfcc_batch(syn), syn_frames, conv.extract_mfcc_batch(ref), ref_frames)
 """
 import math
 
@@ -16,6 +23,9 @@ from . import ops
 # (data/cmu_phn.vocab), not a special token: the reference drops it from both transcripts all the same, and so does this module,
 # so that the numbers agree with the reference's.
 IGNORE_INDICES = (0, 1, 2, 42)
+
+# dB of mel-cepstral distortion per unit of Euclidean distance between two rows of the project's MFCC (columns 1 .. n_cep - 1): see mcd
+MCD_SCALE = 50.0 * math.sqrt(2.0)
 
 
 def _on_device(pred, truth):
@@ -62,3 +72,41 @@ def cal_per(pred, truth):
     if pred is None:
         return math.nan
     return float(per_sum(pred, truth)) / pred.shape[0]
+
+
+def dtw(x, y, x_len=None, y_len=None, cols=None, scale=1.0, want_path=True):
+    """Dynamic time warping of B pairs of feature sequences on one GPU: x (B, Tx, D) against y (B, Ty, D), float32, of x_len / y_len
+    valid rows each (None: all; a host sequence is checked, a device tensor is clamped by the kernel).  The frame distance is
+    d(i, j) = scale * ||x[i, d0:d1] - y[j, d0:d1]||_2 with cols = (d0, d1) (None: all D columns, at most 64); the accumulated cost is
+    D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)) with D(0, 0) = d(0, 0) -- the unweighted symmetric step pattern, the
+    default of librosa.sequence.dtw -- and a tie goes to the diagonal, then to (i-1, j), then to (i, j-1).
+    -> (total (B,) float32 = D(n-1, m-1), path_len (B,) int32, path (B, Tx + Ty - 1, 2) int32: the cells (i, j) of the optimal path
+    from (0, 0) to (n-1, m-1), -1 past path_len; None when want_path is false), device tensors.  An empty side or a NaN among the
+    compared values gives total NaN, path_len 0 and a path of -1.  A pair's result depends on that pair alone and is bitwise
+    repeatable.  One launch, no host read; bad arguments raise ValueError before the device is touched."""
+    return ops.dtw(x, y, x_len, y_len, cols, scale, want_path)
+
+
+def mcd(mfcc_x, x_len, mfcc_y, y_len, n_cep=13):
+    """Mel-cepstral distortion along the DTW path, in dB per aligned frame pair: mfcc_x (B, Tx, >= n_cep) and mfcc_y (B, Ty, >= n_cep)
+    as AudioConverter.extract_mfcc_batch gives them (cepstra in the first 13 columns), x_len / y_len their frame counts (as in dtw).
+    -> (mcd_db (B,) float32 = total / path_len of dtw over the columns [1, n_cep) at scale MCD_SCALE, path_len (B,) int32, path).
+
+    Why 50 sqrt(2).  The usual definition is MCD = (10 / ln 10) sqrt(2 sum_{k >= 1} (c_k - c'_k)^2) on cepstra of the natural-log
+    spectrum.  The project's MFCC is the orthonormal DCT of the normalised mel n = (20 log10 a + 80) / 100 of the mel amplitude a, so
+    ln a = 5 ln 10 * n + const, and the constant falls out of every coefficient k >= 1 (the DCT rows past the first sum to zero).  The
+    DCT is linear: a difference of natural-log cepstra is 5 ln 10 times the difference of the project's, and
+    (10 / ln 10) sqrt(2 sum_{k >= 1} dc_ln^2) = (10 / ln 10) * sqrt(2) * 5 ln 10 * ||dc_n|| = 50 sqrt(2) ||dc_n||.
+
+    Two caveats.  Where the normalisation clamps n into [0, 1] (mel levels below -80 dB or above +20 dB) the clamped value is what is
+    compared.  And the orthonormal scaling of the DCT makes the figure comparable within this project -- between checkpoints, vocoder
+    settings, Griffin-Lim iteration counts -- not with MCD tables computed from SPTK mel-cepstra.
+    An empty utterance or a NaN among the cepstra gives NaN."""
+    n_cep = int(n_cep)
+    ops._dtw_side('mfcc_x', mfcc_x)
+    ops._dtw_side('mfcc_y', mfcc_y)
+    width = min(mfcc_x.shape[2], mfcc_y.shape[2])
+    if not 2 <= n_cep <= width:
+        raise ValueError('mcd: n_cep = %d: at least 2 (the 0th coefficient is left out) and at most the %d columns given' % (n_cep, width))
+    total, path_len, path = ops.dtw(mfcc_x, mfcc_y, x_len, y_len, (1, n_cep), MCD_SCALE, True)
+    return total / path_len.to(torch.float32), path_len, path

@@ -1041,6 +1041,80 @@ def ctc_forced_align(prob, text, lengths=None, text_lengths=None, blank=0, log_i
     return score, path, tok_start, tok_end
 
 
+DTW_MAX_T, DTW_MAX_D = 4096, 64          # st_dtw_batch's limits
+
+
+def _dtw_side(name, t):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError('dtw: %s must be a (B, T, D) float32 GPU tensor (got %s)'
+                         % (name, '%s %s on %s' % (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+
+
+def _dtw_lengths(name, v, B, hi, dev):
+    """x_len / y_len of dtw: as _ca_lengths (None, host integers checked against [0, hi], or a device tensor the kernel clamps)"""
+    if v is None:
+        return None
+    if torch.is_tensor(v) and v.is_cuda:
+        if v.device != dev or v.shape != (B,) or v.dtype.is_floating_point or v.dtype == torch.bool:
+            raise ValueError('dtw: %s must be (B,) integers on the device of x (got %s %s on %s)' % (name, tuple(v.shape), v.dtype, v.device))
+    else:
+        host = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+        if host.shape != (B,) or host.dtype.kind not in 'iu' or (host < 0).any() or (host > hi).any():
+            raise ValueError('dtw: %s must be %d integers in [0, %d] (got %s)' % (name, B, hi, host.tolist()))
+    return torch.as_tensor(v).to(dev, torch.int32).contiguous()
+
+
+def dtw(x, y, x_len=None, y_len=None, cols=None, scale=1.0, want_path=True):
+    """Dynamic time warping of x (B, Tx, D) against y (B, Ty, D), fp32 on one GPU, pair by pair (see st_dtw_batch): Euclidean frame
+    distance over the columns cols = (d0, d1) (None: all D) times `scale`, unweighted symmetric steps, ties to the diagonal, then
+    (i-1, j).  Any batch / row strides (the last dimension has stride 1: a column window of a wider tensor is passed as cols, not as
+    a slice).  x_len / y_len: None (all rows), or (B,) integers -- a host tensor / sequence is checked against [0, Tx] / [0, Ty] here,
+    a device tensor is taken as it is (the kernel clamps it).
+    -> (total (B,) float32, path_len (B,) int32, path (B, Tx + Ty - 1, 2) int32 or None when want_path is false) device tensors;
+    one launch, no host read.  Anything the kernel would refuse raises ValueError before the device is touched."""
+    _dtw_side('x', x)
+    _dtw_side('y', y)
+    dev = x.device
+    if y.device != dev:
+        raise ValueError('dtw: x on %s, y on %s' % (x.device, y.device))
+    B, Tx, D = x.shape
+    Ty = y.shape[1]
+    if y.shape[0] != B or y.shape[2] != D:
+        raise ValueError('dtw: x is %s, y is %s: the pairs and the columns must match' % (tuple(x.shape), tuple(y.shape)))
+    if B < 1 or not (1 <= Tx <= DTW_MAX_T and 1 <= Ty <= DTW_MAX_T) or D < 1:
+        raise ValueError('dtw: B=%d, Tx=%d, Ty=%d, D=%d outside B >= 1, 1 <= Tx, Ty <= %d, D >= 1' % (B, Tx, Ty, D, DTW_MAX_T))
+    if cols is None:
+        cols = (0, D)
+    try:
+        d0, d1 = (int(c) for c in cols)
+    except (TypeError, ValueError):
+        raise ValueError('dtw: cols must be a pair (d0, d1) (got %r)' % (cols,))
+    if not (0 <= d0 < d1 <= D and d1 - d0 <= DTW_MAX_D):
+        raise ValueError('dtw: cols [%d, %d) outside 0 <= d0 < d1 <= D = %d, at most %d columns' % (d0, d1, D, DTW_MAX_D))
+    scale = float(scale)
+    if not 0.0 < scale < float('inf'):
+        raise ValueError('dtw: scale must be finite and positive (got %r)' % (scale,))
+    strides = []
+    for name, t in (('x', x), ('y', y)):
+        sb, st = (t.stride(0) if B > 1 else 0), (t.stride(1) if t.shape[1] > 1 else max(t.stride(1), d1))     # (a 1-long dimension's stride is free)
+        if (t.stride(2) != 1 and D > 1) or st < d1 or sb < 0:
+            raise ValueError('dtw: %s has strides %s: the last dimension needs stride 1 and rows at least d1 = %d floats apart'
+                             % (name, tuple(t.stride()), d1))
+        strides.append((sb, st))
+    x_len = _dtw_lengths('x_len', x_len, B, Tx, dev)
+    y_len = _dtw_lengths('y_len', y_len, B, Ty, dev)
+    lib = _lib.load()
+    total = torch.empty(B, device=dev, dtype=torch.float32)
+    path_len = torch.empty(B, device=dev, dtype=torch.int32)
+    path = torch.empty(B, Tx + Ty - 1, 2, device=dev, dtype=torch.int32) if want_path else None
+    nbytes = int(lib.st_dtw_workspace_bytes(B, Tx, Ty))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    check(lib.st_dtw_batch(_p(x), strides[0][0], strides[0][1], _p(x_len, torch.int32), Tx, _p(y), strides[1][0], strides[1][1],
+                           _p(y_len, torch.int32), Ty, B, d0, d1, scale, _p(total), _p(path_len, torch.int32), _p(path, torch.int32),
+                           _p(ws, torch.uint8), stream_handle()), 'st_dtw_batch')
+    return total, path_len, path
+
+
 def hyp_edit_distance(hyp, hyp_len, text, ignore):
     """edit distance of transcripts that are already collapsed (a beam search's) to `text`, per utterance (see st_hyp_edit_distance):
     hyp (B, Lh) int64 with hyp_len (B,) int32 tokens each, text (B, L) int64, ignore: the ids dropped from both sides.  -> (dist,

@@ -360,6 +360,123 @@ class FeatureWriter:
         return n
 
 
+MCD_PRED_SUFFIX = '-pred'           # what --gen-specgram --gen-wav appends to an utterance's name
+MCD_MAX_BATCH = 64                  # pairs per st_dtw_batch call
+MCD_HEADER = 'file,frames,ref_frames,path_len,mcd_db'
+
+
+def mcd_key(filename):
+    """the key of a synthesised file: its name up to the first '.', without one trailing '-pred'"""
+    key = os.path.basename(filename).split('.')[0]
+    return key[:-len(MCD_PRED_SUFFIX)] if key.endswith(MCD_PRED_SUFFIX) else key
+
+
+def mcd_pairs(syn_dir, ref_dir):
+    """the .wav files of syn_dir sorted by name, each with its recording <key>.wav of ref_dir -> [(file, key, recording)] (names, not
+    paths).  ValueError naming the file when syn_dir holds none, a recording is missing or two files share one."""
+    files = sorted(f for f in os.listdir(syn_dir) if f.lower().endswith('.wav'))
+    if not files:
+        raise ValueError('--mcd-wav-dir %s: no .wav files' % syn_dir)
+    pairs = []
+    for f in files:
+        key = mcd_key(f)
+        ref = key + '.wav'
+        if not key or not os.path.isfile(os.path.join(ref_dir, ref)):
+            raise ValueError('--mcd-wav-dir: %s has no recording %s' % (f, os.path.join(ref_dir, ref)))
+        if any(key == k for _, k, _ in pairs):
+            raise ValueError('--mcd-wav-dir: %s and %s share the recording %s' % ([g for g, k, _ in pairs if k == key][0], f, ref))
+        pairs.append((f, key, ref))
+    return pairs
+
+
+class McdScorer:
+    """main.py --mcd-wav-dir SYN --mcd-ref-dir REF [--mcd-path]: every .wav of SYN (sorted by name) against REF/<key>.wav (mcd_key), in
+    batches of --batch-size (at most 64 pairs a call) -> AudioConverter.extract_mfcc_batch on both sides -> metrics.mcd (DTW over the
+    cepstra 1 .. 12, one launch) -> one host read per batch -> <logdir>/mcd.csv (MCD_HEADER, one row per pair) and, with --mcd-path,
+    <logdir>/<key>.dtw.npy, the (path_len, 2) int32 warp (synthesised frame, recording frame).  No checkpoint, no model.  Every pair is
+    looked up and every header read in load_data: a missing recording, an unreadable file, a foreign sample rate or an utterance
+    the MFCC or the DTW kernel does not take stops the run, naming the file, before any device work."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.exp_name = getattr(paras, 'name', None) or 'synthetic'
+        self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
+
+    def _check_file(self, path):
+        import wave
+        conv = self.audio_converter
+        try:
+            with wave.open(path, 'rb') as w:
+                sr, width, L = w.getframerate(), w.getsampwidth(), w.getnframes()
+        except (OSError, EOFError, wave.Error) as e:
+            raise ValueError('--mcd-wav-dir: %s is not a readable .wav file (%s)' % (path, e))
+        if width != 2:
+            raise ValueError('--mcd-wav-dir: %s is %d-bit; only 16-bit PCM is read' % (path, 8 * width))
+        if sr != conv.sr:
+            raise ValueError('--mcd-wav-dir: sample rate mismatch. Expected %d but get %d (%s)' % (conv.sr, sr, path))
+        try:
+            conv._check_mfcc([L])
+        except ValueError as e:
+            raise ValueError('--mcd-wav-dir: %s: %s' % (path, e))
+        if 1 + L // conv.hop_length_mfcc > ops.DTW_MAX_T:
+            raise ValueError('--mcd-wav-dir: %s has %d MFCC frames; the warp takes at most %d' % (path, 1 + L // conv.hop_length_mfcc, ops.DTW_MAX_T))
+
+    def load_data(self):
+        from .audio import load_audio_transform
+        self.syn_dir, self.ref_dir = self.paras.mcd_wav_dir, self.paras.mcd_ref_dir
+        self.pairs = mcd_pairs(self.syn_dir, self.ref_dir)
+        self.audio_converter = load_audio_transform(**dict(self.config['data']['audio']))
+        for f, _, ref in self.pairs:
+            self._check_file(os.path.join(self.syn_dir, f))
+            self._check_file(os.path.join(self.ref_dir, ref))
+        return self
+
+    def set_model(self):
+        return self
+
+    def score(self, pairs, want_path=False):
+        """the pairs [(file, key, recording)] in one call -> per pair, in the given order: (frames, ref_frames, path_len, mcd_db, path
+        (path_len, 2) int32 or None); one host read"""
+        from .metrics import mcd
+        conv = self.audio_converter
+        ws = conv.load_batch([os.path.join(self.syn_dir, f) for f, _, _ in pairs])
+        wr = conv.load_batch([os.path.join(self.ref_dir, r) for _, _, r in pairs])
+        fs, fr = 1 + ws.lens // conv.hop_length_mfcc, 1 + wr.lens // conv.hop_length_mfcc
+        cs, cr = conv.extract_mfcc_batch(ws), conv.extract_mfcc_batch(wr)
+        # both batches are sorted by length: bring the recordings into the row order of the synthesised side
+        perm = np.argsort(wr.order)[ws.order]
+        cr = cr.index_select(0, torch.from_numpy(perm).to(cr.device))
+        fr = fr[perm]
+        db, plen, path = mcd(cs, fs.tolist(), cr, fr.tolist())
+        B = len(pairs)
+        cols = [db.view(torch.int32).reshape(B, 1), plen.reshape(B, 1)] + ([path.reshape(B, -1)] if want_path else [])
+        host = torch.cat(cols, dim=1).cpu().numpy()                 # (the one host read)
+        out = [None] * B
+        for row, k in enumerate(ws.order):
+            P = int(host[row, 1])
+            out[k] = (int(fs[row]), int(fr[row]), P, float(host[row, :1].view(np.float32)[0]),
+                      host[row, 2:2 + 2 * P].reshape(P, 2).copy() if want_path else None)
+        return out
+
+    def exec(self):
+        os.makedirs(self.logdir, exist_ok=True)
+        B = max(1, min(int(self.paras.batch_size), MCD_MAX_BATCH))
+        want_path = bool(getattr(self.paras, 'mcd_path', False))
+        t0, rows, vals = time.perf_counter(), [MCD_HEADER], []
+        for i in range(0, len(self.pairs), B):
+            pairs = self.pairs[i:i + B]
+            for (f, key, _), (n, m, P, db, path) in zip(pairs, self.score(pairs, want_path)):
+                rows.append('%s,%d,%d,%d,%.4f' % (f, n, m, P, db))
+                vals.append(db)
+                if want_path:
+                    np.save(os.path.join(self.logdir, key + '.dtw.npy'), path.astype(np.int32), allow_pickle=False)
+        with open(os.path.join(self.logdir, 'mcd.csv'), 'w') as f:
+            f.write('\n'.join(rows) + '\n')
+        self.mean_mcd = float(np.mean(vals))
+        print('[INFO]', 'MCD-DTW of %d pairs: mean %.4f dB; %s, %.2f s' % (len(vals), self.mean_mcd, os.path.join(self.logdir, 'mcd.csv'), time.perf_counter() - t0))
+        return len(vals)
+
+
 SPECIAL_TOKENS = ('<pad>', '<space>', '<eos>')     # ids 0, 1, 2 of the phone vocabulary (src/text.py); phones start at id 3
 
 
