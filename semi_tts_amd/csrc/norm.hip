@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void prenet_norm_kernel(const PnArgs a) {
 // Backward of one normalised prenet layer of a decode step, in place: dn (rows, P) = gradient at the norm's output (the ReLU /
 // mask backward already applied)  ->  gradient at the Linear's output y; dgamma / dbeta get this step's sums ADDED (the steps of a
 // backward run one after the other on one stream, one thread owns a column: fixed order, no atomics).  Statistics are recomputed
-// from y.  One thread per column; LayerNorm first leaves the four per-row scalars in LDS (every block for all rows).
+// from y.  One thread per column; LayerNorm first leaves the four per-row scalars in LDS and runs as a single workgroup.
 struct PnbArgs {
     float* dn; int ld; const float* y; int ldy; int mode;
     const float* gamma; const float* run_mean; const float* run_var; float eps;
@@ -195,19 +195,22 @@ __global__ __launch_bounds__(256) void prenet_norm_bwd_kernel(const PnbArgs a) {
             if (lane == 0) { pnb_lds[r * 4 + 0] = mean; pnb_lds[r * 4 + 1] = rstd; pnb_lds[r * 4 + 2] = c1; pnb_lds[r * 4 + 3] = c2; }
         }
         __syncthreads();
-        if (n >= P) return;
-        const float g = a.gamma[n];
-        float dg = 0.0f, db = 0.0f;
-        for (int r = 0; r < R; ++r) {
-            const float mean = pnb_lds[r * 4 + 0], rstd = pnb_lds[r * 4 + 1], c1 = pnb_lds[r * 4 + 2], c2 = pnb_lds[r * 4 + 3];
-            const float xh = (a.y[(size_t)r * a.ldy + n] - mean) * rstd;
-            const float d = a.dn[(size_t)r * a.ld + n];
-            dg = fmaf(d, xh, dg);
-            db += d;
-            a.dn[(size_t)r * a.ld + n] = rstd * (d * g - c1 - xh * c2);
+        // ONE workgroup walks all columns (the launch below): the row scalars above are sums over every column of dn, which this loop
+        // overwrites in place -- a second workgroup could still be reading the columns this one has already replaced
+        for (int c = n; c < P; c += gridDim.x * 256) {
+            const float g = a.gamma[c];
+            float dg = 0.0f, db = 0.0f;
+            for (int r = 0; r < R; ++r) {
+                const float mean = pnb_lds[r * 4 + 0], rstd = pnb_lds[r * 4 + 1], c1 = pnb_lds[r * 4 + 2], c2 = pnb_lds[r * 4 + 3];
+                const float xh = (a.y[(size_t)r * a.ldy + c] - mean) * rstd;
+                const float d = a.dn[(size_t)r * a.ld + c];
+                dg = fmaf(d, xh, dg);
+                db += d;
+                a.dn[(size_t)r * a.ld + c] = rstd * (d * g - c1 - xh * c2);
+            }
+            a.dgamma[c] += dg;
+            a.dbeta[c] += db;
         }
-        a.dgamma[n] += dg;
-        a.dbeta[n] += db;
         return;
     }
     if (n >= P) return;
@@ -249,7 +252,7 @@ extern "C" int st_prenet_norm_bwd(float* dn, int ld, const float* y, int ldy, in
     PnbArgs a;
     a.dn = dn; a.ld = ld; a.y = y; a.ldy = ldy; a.mode = mode; a.gamma = gamma; a.run_mean = run_mean; a.run_var = run_var; a.eps = eps;
     a.dgamma = dgamma; a.dbeta = dbeta; a.rows = rows; a.P = P;
-    hipLaunchKernelGGL(prenet_norm_bwd_kernel, dim3((P + 255) / 256), dim3(256), mode == 1 ? (size_t)rows * 4 * sizeof(float) : 0,
+    hipLaunchKernelGGL(prenet_norm_bwd_kernel, dim3(mode == 1 ? 1 : (P + 255) / 256), dim3(256), mode == 1 ? (size_t)rows * 4 * sizeof(float) : 0,
                        (hipStream_t)stream, a);
     ST_LAUNCH_CHECK();
     return 0;

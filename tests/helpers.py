@@ -20,6 +20,44 @@ def report(test, **vals):
         pass
 
 
+U = 2.0 ** -24          # float32 unit roundoff
+SENTINEL = -12345.6789
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def bits(t):
+    """float32 tensor as its bit pattern (bitwise comparison that also holds for NaN)"""
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+def same_bits(a, b):
+    return torch.equal(bits(a), bits(b))
+
+
+def guarded(rows, cols, ld, dev, pad_rows=2, off=3, fill=SENTINEL):
+    """(buffer, view): a (rows, cols) view with leading dimension ld inside a buffer filled with `fill` (a sentinel, or NaN so that a
+    read outside the view poisons the result) with guard rows above and below and guard columns left (off) and right (ld - off - cols)"""
+    assert ld >= cols + off
+    buf = torch.full((rows + 2 * pad_rows, ld), fill, device=dev)
+    return buf, buf[pad_rows:pad_rows + rows, off:off + cols]
+
+
+def guard_ok(buf, view_mask_fn, fill=SENTINEL):
+    """every element of buf outside the view still holds the fill value, bit for bit"""
+    keep = view_mask_fn(torch.zeros(buf.shape, dtype=torch.bool))
+    return bool((bits(buf)[~keep] == bits(torch.tensor([fill], dtype=torch.float32))[0]).all())
+
+
+def inside(rows, cols, pad_rows=2, off=3):
+    def f(m):
+        m[pad_rows:pad_rows + rows, off:off + cols] = True
+        return m
+    return f
+
+
 def maxdiff(a, b):
     return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
 

@@ -16,16 +16,14 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from helpers import report   # noqa: E402
+from helpers import SENTINEL, U, bits, gen, guard_ok, guarded, inside, report, same_bits   # noqa: E402,F401
 from semi_tts_amd import _lib, ops   # noqa: E402
 from semi_tts_amd import autograd as AG   # noqa: E402
 from oracle import tts_oracle as O   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24          # float32 unit roundoff
 NAN, INF = float('nan'), float('inf')
-SENTINEL = -12345.6789
 
 
 @pytest.fixture(scope='module')
@@ -34,45 +32,10 @@ def dev():
     return torch.device('cuda:0')
 
 
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def bits(t):
-    """float32 tensor as its bit pattern (bitwise comparison that also holds for NaN)"""
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return torch.equal(bits(a), bits(b))
-
-
 def rel_max(got, ref):
     """max |got - ref| / max |ref| over the elements (both finite there)"""
     got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
     return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-300)
-
-
-def guarded(rows, cols, ld, dev, pad_rows=2, off=3):
-    """(buffer, view): a (rows, cols) view with leading dimension ld inside a sentinel-filled buffer with guard rows above and below
-    and guard columns left (off) and right (ld - off - cols)"""
-    assert ld >= cols + off
-    buf = torch.full((rows + 2 * pad_rows, ld), SENTINEL, device=dev)
-    return buf, buf[pad_rows:pad_rows + rows, off:off + cols]
-
-
-def guard_ok(buf, view_mask_fn):
-    """every element of buf outside the view still holds the sentinel"""
-    keep = view_mask_fn(torch.zeros(buf.shape, dtype=torch.bool))
-    outside = buf.detach().cpu()[~keep]
-    return bool((outside == SENTINEL).all())
-
-
-def inside(rows, cols, pad_rows=2, off=3):
-    def f(m):
-        m[pad_rows:pad_rows + rows, off:off + cols] = True
-        return m
-    return f
 
 
 # ===================================================================================================== freq_loss
