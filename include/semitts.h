@@ -1127,6 +1127,28 @@ int st_dtw_batch(const float* x, long x_sb, long x_st, const int32_t* x_len /* N
                  float* total /* (B) */, int32_t* path_len /* (B) */, int32_t* path /* (B, Tx + Ty - 1, 2) or NULL */,
                  void* ws, void* stream);
 
+/* Where an utterance ends, read off the decoder's attention, and the alignment diagnostics of the same pass (the model has no trained
+ * stop gate: the reference decodes to the length of the ground-truth mel; semi_tts_amd.metrics.attention_endpoints, main.py --synth-phn-dir).
+ * align(b, t, j) = align[b a_sb + t a_st + j], strides in floats, unit stride in j; all L columns of all S rows are read.  n = enc_len[b]
+ * ((B) int32 on the device, clamped to [1, L]) is the count of real phones of utterance b.
+ * Peak: peak[t] = the lowest column among the maxima of row t over all L columns; a NaN entry never wins, a row without a non-NaN entry
+ * has peak 0.  maxw[t] = that maximum, 0 for such a row.
+ * End: flag[t] = peak[t] >= n - 1.  t0 = the smallest t with t + K <= S and flag[t .. t + K - 1] all set (K = patience).  With such a
+ * t0: end = t0 + K, reached = 1; without: end = S, reached = 0 (a run of fewer than K flags that touches step S - 1 is no detection).
+ * Over the steps [0, end): focus = the fp32 mean of maxw; n_back = the t >= 1 with peak[t] < peak[t-1]; n_skip = the t >= 1 with
+ * peak[t] > peak[t-1] + max_jump; dur[j] = the steps with peak == j, for every j < L; covered = the j < n with dur[j] > 0.
+ * nonfinite = 1 when any entry of the S rows is NaN or +-inf, else 0.
+ * Outputs: stats (B, 6) int32 = (end, reached, n_back, n_skip, covered, nonfinite); focus (B); peak (B, S) int32, all S steps;
+ * dur (B, L) int32.  No output needs initialising.
+ * Integer compares and LDS integer atomics; the focus sum has a fixed order that depends on `end` alone: every output of an utterance
+ * is bitwise repeatable and independent of B, of its position in the batch and of the other utterances (NaN included).
+ * One launch (one workgroup per utterance), no workspace, no host read.
+ * Limits (-22 past them): B >= 1, 1 <= S <= 4096, 1 <= L <= 2048, a_st >= L, a_sb >= 0, patience >= 1, max_jump >= 1. */
+int st_attn_endpoint(const float* align, long a_sb, long a_st, const int32_t* enc_len /* (B) */,
+                     int B, int S, int L, int patience, int max_jump,
+                     int32_t* stats /* (B, 6) */, float* focus /* (B) */,
+                     int32_t* peak /* (B, S) */, int32_t* dur /* (B, L) */, void* stream);
+
 /* The trainer's scalar arithmetic on loss values as one launch (ref: bin/train_vqvae.py:208-233: total_loss = asr_weight * asr_loss +
  * tts_weight * (mel_loss + linear_loss) + unpair_speech_weight * ... -- a chain of one-element torch kernels there):
  * *outs[j] = sum_i W[j * n + i] * *xs[i] for j < m (m <= 4 outputs, n <= ST_SCALAR_MAX terms, W on the host; in rows j > 0 a zero weight means the term is not a member of that sum).

@@ -23,6 +23,7 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --resample-wav-dir DIR --resample-out DIR2 --resample-rate 16000 [--batch-size 32]
     python main.py --config config/supervised.yaml --feat-wav-dir DIR --feat mfcc|mel|linear [--segment-file FILE --min-segment-len 2]
     python main.py --config config/supervised.yaml --mcd-wav-dir SYN --mcd-ref-dir REF [--mcd-path --batch-size 32]
+    python main.py --config config/supervised.yaml --synth-phn-dir DIR [--load ckpt.pth --vocab FILE --synth-sid 0 --gen-wav --batch-size 8]
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
 `--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
 (semi_tts_amd/ngram.py: a plain .npy of shape (V^(order-1), V) in the layout of the reference's NgramPrior, src/lm.py:233-290) on the host.
@@ -40,6 +41,10 @@ them; `--resample-wav-dir` converts a directory of .wav files to another rate an
 `--mcd-wav-dir` (not a mode of the reference) scores synthesised .wav files against the recordings of `--mcd-ref-dir` by mel-cepstral
 distortion along a dynamic-time-warping path (solver.McdScorer, semi_tts_amd.metrics.mcd): mcd.csv, one row per pair, and with
 `--mcd-path` the warp of every pair as <key>.dtw.npy.
+`--synth-phn-dir` (not a mode of the reference, which decodes to the length of the ground-truth mel) synthesises the .phn transcripts of a
+directory -- what `--transcribe-wav-dir` writes, as it is -- and finds where each utterance ends from its attention on the GPU
+(solver.Synthesiser, semi_tts_amd.metrics.attention_endpoints): <name>-mel.npy, -spec.npy, -align.npy, -dur.npy cut at the end, with
+`--gen-wav` <name>-pred.wav, and synth.csv with the alignment diagnostics of every utterance.
 """
 import argparse
 import os
@@ -133,6 +138,17 @@ parser.add_argument('--mcd-wav-dir', default=None, type=str, help='score the syn
 parser.add_argument('--mcd-ref-dir', default=None, type=str, help='--mcd-wav-dir: the directory of the recordings, <key>.wav for every synthesised '
                     'file (key: its name up to the first ".", without one trailing "-pred")')
 parser.add_argument('--mcd-path', action='store_true', help='--mcd-wav-dir: also write the warp of every pair as <key>.dtw.npy, (path_len, 2) int32')
+parser.add_argument('--synth-phn-dir', default=None, type=str, help='synthesise the .phn transcripts of this directory (sorted by name, batched by '
+                    '--batch-size; ids or --vocab symbols, the files of --transcribe-wav-dir as they are), each cut where its attention has '
+                    'stayed on the last phone: <logdir>/<name>/<file>-mel.npy, -spec.npy, -align.npy, -dur.npy, with --gen-wav -pred.wav, and '
+                    'synth.csv (file,tokens,steps,frames,seconds,reached,focus,backward,skips,covered)')
+parser.add_argument('--synth-sid', default=None, type=int, help='--synth-phn-dir: the speaker id of every utterance (default 0)')
+parser.add_argument('--end-patience', default=None, type=int, help='--synth-phn-dir: decoder steps the attention peak must stay at or past '
+                    'the last phone before the utterance ends (default 3)')
+parser.add_argument('--end-max-jump', default=None, type=int, help='--synth-phn-dir: a step whose attention peak moves forward by more '
+                    'phones than this counts as a skip (default 4)')
+parser.add_argument('--max-frames-per-phone', default=None, type=float, help='--synth-phn-dir: frames decoded per phone of the longest '
+                    'transcript of a batch, before the margin of 40 (default 12, twice the corpus ratio)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -236,7 +252,33 @@ def parse_args(argv=None):
             parser.error('--mcd-wav-dir needs --config (its data.audio) and --mcd-ref-dir DIR (the recordings)')
     elif paras.mcd_ref_dir is not None or paras.mcd_path:
         parser.error('--mcd-ref-dir and --mcd-path belong to --mcd-wav-dir; they need that flag')
-    if paras.gen_wav_feat != 'linear' and not (paras.gen_specgram and paras.gen_wav):
+    if paras.synth_phn_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir'):
+            if getattr(paras, flag):
+                parser.error('--synth-phn-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--synth-phn-dir does not combine with --dev-batches')
+        if paras.config is None:
+            parser.error('--synth-phn-dir needs --config (its model and data.audio)')
+        if paras.synth_sid is not None and paras.synth_sid < 0:
+            parser.error('--synth-sid must be >= 0')
+        for flag in ('end_patience', 'end_max_jump'):
+            v = getattr(paras, flag)
+            if v is not None and v < 1:
+                parser.error('--%s must be >= 1' % flag.replace('_', '-'))
+        if paras.max_frames_per_phone is not None and not 0.0 < paras.max_frames_per_phone < float('inf'):
+            parser.error('--max-frames-per-phone must be finite and positive')
+    elif (paras.synth_sid is not None or paras.end_patience is not None or paras.end_max_jump is not None
+          or paras.max_frames_per_phone is not None):
+        parser.error('--synth-sid, --end-patience, --end-max-jump and --max-frames-per-phone belong to --synth-phn-dir; they need that flag')
+    if paras.synth_sid is None:
+        paras.synth_sid = 0
+    if paras.end_patience is None:
+        paras.end_patience = 3
+    if paras.end_max_jump is None:
+        paras.end_max_jump = 4
+    if paras.gen_wav_feat != 'linear' and not ((paras.gen_specgram or paras.synth_phn_dir is not None) and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
         for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir'):
@@ -271,8 +313,8 @@ def parse_args(argv=None):
         paras.lm_smooth = 1.0
     if paras.verbose:
         for flag in IGNORED_FLAGS:
-            if flag == 'gen_wav' and paras.gen_specgram:
-                continue             # read by gen_specgram alone (bin/gen_specgram.py:114-126), as in the reference
+            if flag == 'gen_wav' and (paras.gen_specgram or paras.synth_phn_dir is not None):
+                continue             # read by gen_specgram (bin/gen_specgram.py:114-126), as in the reference, and by --synth-phn-dir
             if flag == 'store_best_per' and paras.dev_batches > 0:
                 continue             # read by VqvaeTrainer.validate (bin/train_vqvae.py:376-382)
             if getattr(paras, flag):
@@ -316,6 +358,9 @@ def main(argv=None):
         mode = 'test'
     elif paras.mcd_wav_dir is not None:
         from semi_tts_amd.solver import McdScorer as Solver
+        mode = 'test'
+    elif paras.synth_phn_dir is not None:
+        from semi_tts_amd.solver import Synthesiser as Solver
         mode = 'test'
     elif paras.transcribe_wav_dir is not None:
         from semi_tts_amd.solver import Transcriber as Solver

@@ -265,6 +265,7 @@ SIGNATURES = {
     'st_ctc_forced_align': [P, I, I, I, P, P, I, P, I, I, F, P, P, P, P, P, P],
     'st_dtw_workspace_bytes': [I, I, I],
     'st_dtw_batch': [P, C.c_long, C.c_long, P, I, P, C.c_long, C.c_long, P, I, I, I, I, F, P, P, P, P, P],
+    'st_attn_endpoint': [P, C.c_long, C.c_long, P, I, I, I, I, I, P, P, P, P, P],
     'st_scalar_combine': [P, I, P, I, P, P],
     'st_scalar_fanout': [P, P, I, P, P],
     'st_softmax_bwd': [P, P, P, C.c_float, P, P, I, I, P],

@@ -7,7 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libsemitts_hip.so')
-SOURCES = ['skinny.hip', 'skinny_packed.hip', 'attention.hip', 'gemm.hip', 'rnn.hip', 'vq.hip', 'runtime.hip', 'decoder.hip', 'grad.hip', 'attention_bwd.hip', 'decoder_bwd.hip', 'loss.hip', 'optim.hip', 'norm.hip', 'audio.hip', 'ctc_decode.hip', 'ctc_align.hip', 'resample.hip', 'dtw.hip']
+SOURCES = ['skinny.hip', 'skinny_packed.hip', 'attention.hip', 'gemm.hip', 'rnn.hip', 'vq.hip', 'runtime.hip', 'decoder.hip', 'grad.hip', 'attention_bwd.hip', 'decoder_bwd.hip', 'loss.hip', 'optim.hip', 'norm.hip', 'audio.hip', 'ctc_decode.hip', 'ctc_align.hip', 'resample.hip', 'dtw.hip',
+           'attn_stats.hip']
 
 
 def _hipcc():

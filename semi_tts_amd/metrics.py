@@ -12,7 +12,15 @@ one HIP launch per batch (st_dtw_batch, semi_tts_amd/csrc/dtw.hip), `mcd` is the
 
     from semi_tts_amd.metrics import mcd
     mcd_db, path_len, path = mcd(conv.extract_mfcc_batch(syn), syn_frames, conv.extract_mfcc_batch(ref), ref_frames)
+
+Where a synthesised utterance ends, read off the decoder's attention (the model has no trained stop gate), with the alignment diagnostics
+of the same pass: `attention_endpoints`, one HIP launch per batch (st_attn_endpoint, semi_tts_amd/csrc/attn_stats.hip).
+
+    from semi_tts_amd.metrics import attention_endpoints
+    mel, linear, align, enc_len = model.synthesise(transcripts, sid)
+    ep = attention_endpoints(align, enc_len)        # ep.end[b] decoder steps = r * ep.end[b] frames
 """
+import collections
 import math
 
 import torch
@@ -110,3 +118,22 @@ def mcd(mfcc_x, x_len, mfcc_y, y_len, n_cep=13):
         raise ValueError('mcd: n_cep = %d: at least 2 (the 0th coefficient is left out) and at most the %d columns given' % (n_cep, width))
     total, path_len, path = ops.dtw(mfcc_x, mfcc_y, x_len, y_len, (1, n_cep), MCD_SCALE, True)
     return total / path_len.to(torch.float32), path_len, path
+
+
+AttentionEndpoints = collections.namedtuple('AttentionEndpoints', 'end reached n_back n_skip covered nonfinite focus peak dur')
+
+
+def attention_endpoints(align, enc_len, patience=3, max_jump=4):
+    """End of speech and alignment diagnostics from the attention of a free-running decode: align (B, S, L) float32 on one GPU (a
+    sliced view with unit stride in L is read where it lies, as VQVAE.text_to_speech returns one), enc_len the real phones n of every
+    utterance (a list, an array or a device tensor; the appended index 0 at position n and the batch padding are not counted).
+    The peak of step t is the lowest column among the maxima of align[b, t, :] over all L columns (NaN never wins; 0 for a row of
+    NaN).  The utterance ends after the first `patience` consecutive steps whose peak is at or past the last phone n - 1:
+    end = t0 + patience, reached = 1; without such a run end = S, reached = 0.  Over the steps [0, end): focus = the mean peak weight,
+    n_back = steps whose peak lies before the previous one, n_skip = steps whose peak lies more than max_jump phones past it,
+    dur[j] = steps whose peak is column j, covered = real phones with dur > 0.  nonfinite = 1 when align holds a NaN or an infinity.
+    -> AttentionEndpoints(end, reached, n_back, n_skip, covered, nonfinite: (B,) int32; focus (B,) float32; peak (B, S) int32;
+    dur (B, L) int32), device tensors.  An utterance's result depends on it alone and is bitwise repeatable.  One launch, no host
+    read; bad arguments raise ValueError before the device is touched."""
+    stats, focus, peak, dur = ops.attn_endpoint(align, enc_len, patience, max_jump)
+    return AttentionEndpoints(*stats.unbind(1), focus, peak, dur)

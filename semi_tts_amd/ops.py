@@ -1115,6 +1115,49 @@ def dtw(x, y, x_len=None, y_len=None, cols=None, scale=1.0, want_path=True):
     return total, path_len, path
 
 
+AE_MAX_S, AE_MAX_L = 4096, 2048          # st_attn_endpoint's limits
+
+
+def attn_endpoint(align, enc_len, patience=3, max_jump=4):
+    """End of speech and alignment diagnostics of align (B, S, L), fp32 on one GPU, utterance by utterance (see st_attn_endpoint).
+    Any batch / row strides with unit stride in L (a sliced view is read where it lies).  enc_len: (B,) real phones per utterance -- a
+    host sequence / tensor is checked against [1, L] here, a device tensor is taken as it is (the kernel clamps it).
+    -> (stats (B, 6) int32 = (end, reached, n_back, n_skip, covered, nonfinite), focus (B,) float32, peak (B, S) int32,
+    dur (B, L) int32) device tensors; one launch, no host read.  Anything the kernel would refuse raises ValueError before the
+    device is touched."""
+    if not torch.is_tensor(align) or not align.is_cuda or align.dim() != 3 or align.dtype != torch.float32:
+        raise ValueError('attn_endpoint: align must be a (B, S, L) float32 GPU tensor (got %s)'
+                         % ('%s %s on %s' % (tuple(align.shape), align.dtype, align.device) if torch.is_tensor(align) else type(align).__name__))
+    dev = align.device
+    B, S, L = align.shape
+    if B < 1 or not (1 <= S <= AE_MAX_S and 1 <= L <= AE_MAX_L):
+        raise ValueError('attn_endpoint: B=%d, S=%d, L=%d outside B >= 1, 1 <= S <= %d, 1 <= L <= %d' % (B, S, L, AE_MAX_S, AE_MAX_L))
+    for name, v in (('patience', patience), ('max_jump', max_jump)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 2 ** 31 - 1:
+            raise ValueError('attn_endpoint: %s must be an integer >= 1 (got %r)' % (name, v))
+    sb, st = (align.stride(0) if B > 1 else 0), (align.stride(1) if S > 1 else max(align.stride(1), L))     # (a 1-long dimension's stride is free)
+    if (align.stride(2) != 1 and L > 1) or st < L or sb < 0:
+        raise ValueError('attn_endpoint: align has strides %s: the last dimension needs stride 1 and rows at least L = %d floats apart'
+                         % (tuple(align.stride()), L))
+    if torch.is_tensor(enc_len) and enc_len.is_cuda:
+        if enc_len.device != dev or enc_len.shape != (B,) or enc_len.dtype.is_floating_point or enc_len.dtype == torch.bool:
+            raise ValueError('attn_endpoint: enc_len must be (B,) integers on the device of align (got %s %s on %s)'
+                             % (tuple(enc_len.shape), enc_len.dtype, enc_len.device))
+    else:
+        host = np.asarray(enc_len.cpu() if torch.is_tensor(enc_len) else enc_len)
+        if host.shape != (B,) or host.dtype.kind not in 'iu' or (host < 1).any() or (host > L).any():
+            raise ValueError('attn_endpoint: enc_len must be %d integers in [1, %d] (got %s)' % (B, L, host.tolist()))
+    enc_len = torch.as_tensor(enc_len).to(dev, torch.int32).contiguous()
+    lib = _lib.load()
+    # one allocation, carved into the four contiguous outputs (the call is latency-bound: three more torch.empty cost as much as the kernel)
+    flat = torch.empty(B * (7 + S + L), device=dev, dtype=torch.int32)
+    stats, focus = flat[:6 * B].view(B, 6), flat[6 * B:7 * B].view(torch.float32)
+    peak, dur = flat[7 * B:(7 + S) * B].view(B, S), flat[(7 + S) * B:].view(B, L)
+    check(lib.st_attn_endpoint(_p(align), sb, st, _p(enc_len, torch.int32), B, S, L, int(patience), int(max_jump), _p(stats, torch.int32),
+                               _p(focus), _p(peak, torch.int32), _p(dur, torch.int32), stream_handle()), 'st_attn_endpoint')
+    return stats, focus, peak, dur
+
+
 def hyp_edit_distance(hyp, hyp_len, text, ignore):
     """edit distance of transcripts that are already collapsed (a beam search's) to `text`, per utterance (see st_hyp_edit_distance):
     hyp (B, Lh) int64 with hyp_len (B,) int32 tokens each, text (B, L) int64, ignore: the ids dropped from both sides.  -> (dist,

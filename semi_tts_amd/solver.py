@@ -16,9 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .vqvae import VQVAE, FRAME_PHN_RATIO
-
-INFERENCE_MARGIN_FRAMES = 40        # ref: bin/gen_specgram.py:17
+from .vqvae import VQVAE, FRAME_PHN_RATIO, INFERENCE_MARGIN_FRAMES, SYNTH_MAX_FRAMES_PER_PHONE
 
 
 class BaseSolver:
@@ -642,6 +640,133 @@ class Aligner(Transcriber):
         self.verbose('Aligned %d files (%d without an alignment, %s posteriors) into %s, %.2f s'
                      % (n, n_bad, self.paras.asr_output, self.logdir, time.perf_counter() - t0))
         return n
+
+
+SYNTH_HEADER = 'file,tokens,steps,frames,seconds,reached,focus,backward,skips,covered'
+
+
+def synth_row(file, tokens, steps, frames, seconds, reached, focus, backward, skips, covered):
+    """one row of synth.csv (SYNTH_HEADER): the .phn file, its phones, the decoder steps and frames kept, the length of the waveform in
+    seconds (%.4f), whether the end was detected, the mean peak attention weight (%.4f), backward jumps, skips, phones attended"""
+    return '%s,%d,%d,%d,%.4f,%d,%.4f,%d,%d,%d' % (file, tokens, steps, frames, seconds, reached, focus, backward, skips, covered)
+
+
+def read_synth_transcripts(phn_dir, vocab, vocab_size):
+    """the .phn files of --synth-phn-dir sorted by name -> ([file], [id list]) through ctc_align.read_phn (ids or `vocab` symbols, the
+    `score<TAB>tokens` lines of --transcribe-wav-dir as they are) and vqvae.check_transcript.  ValueError naming the file for an
+    unreadable or empty transcript, an id 0 inside one or an id outside the vocabulary; also when the directory holds none."""
+    from .ctc_align import read_phn
+    from .vqvae import check_transcript
+    files = sorted(f for f in os.listdir(phn_dir) if f.endswith('.phn'))
+    if not files:
+        raise ValueError('--synth-phn-dir %s: no .phn files' % phn_dir)
+    transcripts = []
+    for f in files:
+        try:
+            transcripts.append(check_transcript(read_phn(os.path.join(phn_dir, f), vocab), vocab_size))
+        except ValueError as e:
+            raise ValueError('--synth-phn-dir: %s: %s' % (f, e))
+    return files, transcripts
+
+
+class Synthesiser(BaseSolver):
+    """main.py --synth-phn-dir DIR: the .phn transcripts of DIR, sorted by name, in batches of --batch-size -> VQVAE.synthesise (speaker
+    --synth-sid, --max-frames-per-phone frames of decode budget per phone) -> metrics.attention_endpoints (--end-patience,
+    --end-max-jump) -> one host read of the end steps per batch -> every utterance cut to frames = max(r * end, audio.min_frames) and
+    written as <logdir>/<name>-mel.npy, -spec.npy, -align.npy (align[:end, :n]), -dur.npy (int32 (n,), frames per phone) and, with
+    --gen-wav, -pred.wav (AudioConverter.vocode_batch on the trimmed device tensors: each utterance is what it gives alone;
+    --gen-wav-feat mel vocodes the mel), plus one synth.csv (SYNTH_HEADER).  -dur.npy is r * dur[:n] of attention_endpoints with the
+    steps whose peak lies past the last phone -- on the appended index 0 or the padding, which the end rule counts as the last phone
+    too -- added to the last phone, so the durations sum to r * end.  An utterance whose end was not found (reached == 0) or whose
+    attention holds a NaN or an infinity gets a [WARNING] line and is written at full length.
+    Padded phones are seen by the encoder and the attention, unmasked: this follows the reference and every batch the model was
+    trained on, so an utterance's output depends on its batch's longest transcript; --batch-size 1 gives the alone result.
+    Every transcript is read in load_data: a bad one (read_synth_transcripts), one too long for the kernel or a --synth-sid outside the
+    speaker table stops the run, naming the file, before anything is written.  Without --load the synthetic weights are used."""
+
+    def load_data(self):
+        from .audio import load_audio_transform
+        from .vqvae import synth_frames
+        vocab = getattr(self.paras, 'vocab', None)
+        self.vocab = read_vocab(vocab) if vocab else None
+        self.phn_dir = self.paras.synth_phn_dir
+        self.files, self.transcripts = read_synth_transcripts(self.phn_dir, self.vocab, self.vocab_size)
+        self.sid = int(getattr(self.paras, 'synth_sid', 0) or 0)
+        if not 0 <= self.sid < self.n_spkr:
+            raise ValueError('--synth-sid %d: the speaker table has ids 0 .. %d' % (self.sid, self.n_spkr - 1))
+        mfpp = getattr(self.paras, 'max_frames_per_phone', None)
+        self.max_frames_per_phone = float(SYNTH_MAX_FRAMES_PER_PHONE if mfpp is None else mfpp)
+        self.patience, self.max_jump = int(getattr(self.paras, 'end_patience', 3)), int(getattr(self.paras, 'end_max_jump', 4))
+        r = int(self.config['model']['decoder']['decoder']['n_frames_per_step'])
+        for f, t in zip(self.files, self.transcripts):
+            steps = synth_frames(len(t), r, self.max_frames_per_phone) // r
+            if len(t) + 1 > ops.AE_MAX_L or steps > ops.AE_MAX_S:
+                raise ValueError('--synth-phn-dir: %s: %d phones decode %d steps; the end-of-speech kernel takes at most %d phones and %d steps'
+                                 % (f, len(t), steps, ops.AE_MAX_L - 1, ops.AE_MAX_S))
+        self.audio_converter = load_audio_transform(**self.config['data']['audio'])
+        return self
+
+    def set_model(self):
+        self.model = self._build_model().eval()
+        self.n_frames_per_step = self.model.n_frames_per_step
+        if not self.load_ckpt():
+            from .synthetic import load_synthetic
+            load_synthetic(self.model, seed=getattr(self.paras, 'seed', 0) + 1234)
+        return self
+
+    def write_batch(self, files, transcripts, mel, lin, align, enc_len):
+        """one decoded batch (device tensors; enc_len as attention_endpoints takes it) -> the files of its utterances in self.logdir;
+        -> the rows of synth.csv.  One host read of the end steps, the diagnostics and the durations, all integers of a few KiB."""
+        from .audio import min_frames, write_wav
+        from .metrics import attention_endpoints
+        conv, r = self.audio_converter, self.n_frames_per_step
+        B, S, T = align.shape[0], align.shape[1], mel.shape[1]
+        ep = attention_endpoints(align, enc_len, self.patience, self.max_jump)
+        host = torch.cat([torch.stack([ep.end, ep.reached, ep.n_back, ep.n_skip, ep.covered, ep.nonfinite, ep.focus.view(torch.int32)], 1),
+                          ep.dur], 1).cpu().numpy()                  # (the one host read)
+        floor = min_frames(conv.n_fft, conv.hop_length)
+        kept, rows = [], []
+        for i, (f, tr) in enumerate(zip(files, transcripts)):
+            n = len(tr)
+            end, reached, back, skip, cov, bad = (int(v) for v in host[i, :6])
+            focus = float(host[i, 6:7].view(np.float32)[0])
+            if not reached or bad:
+                print('[WARNING] %s: %s; written at full length (%d steps)'
+                      % (f, 'the attention holds a NaN or an infinity' if bad else
+                         'the attention did not stay on the last phone for %d steps' % self.patience, S))
+                end = S
+            frames = min(max(r * end, floor), T)
+            dur = host[i, 7:7 + n].astype(np.int32)
+            dur[n - 1] += host[i, 7 + n:].sum()                      # peaks past the last phone: its trailing steps
+            stem = os.path.join(self.logdir, os.path.splitext(f)[0])
+            np.save(stem + '-mel.npy', mel[i, :frames].cpu().numpy().astype(np.float32), allow_pickle=False)
+            np.save(stem + '-spec.npy', lin[i, :frames].cpu().numpy().astype(np.float32), allow_pickle=False)
+            np.save(stem + '-align.npy', align[i, :end, :n].cpu().numpy(), allow_pickle=False)
+            np.save(stem + '-dur.npy', (r * dur).astype(np.int32), allow_pickle=False)
+            kept.append((stem, frames))
+            rows.append(synth_row(f, n, end, frames, conv.hop_length * (frames - 1) / conv.sr, reached, focus, back, skip, cov))
+        if getattr(self.paras, 'gen_wav', False):
+            use_mel = getattr(self.paras, 'gen_wav_feat', 'linear') == 'mel'
+            src = mel if use_mel else lin
+            wavs = conv.vocode_batch([src[i, :frames] for i, (_, frames) in enumerate(kept)], 'mel' if use_mel else 'spec')
+            for (stem, _), w in zip(kept, wavs):
+                write_wav(stem + '-pred.wav', w, conv.sr)
+        return rows
+
+    def exec(self):
+        os.makedirs(self.logdir, exist_ok=True)
+        B = max(1, int(self.paras.batch_size))
+        t0, rows = time.perf_counter(), [SYNTH_HEADER]
+        for i in range(0, len(self.files), B):
+            files, trs = self.files[i:i + B], self.transcripts[i:i + B]
+            mel, lin, align, enc_len = self.model.synthesise(trs, self.sid, self.max_frames_per_phone)
+            ops.check_persist_status(self.device)
+            rows += self.write_batch(files, trs, mel, lin, align, enc_len)
+        with open(os.path.join(self.logdir, 'synth.csv'), 'w') as out:
+            out.write('\n'.join(rows) + '\n')
+        self.verbose('Synthesised %d transcripts (speaker %d, patience %d) into %s, %.2f s'
+                     % (len(rows) - 1, self.sid, self.patience, self.logdir, time.perf_counter() - t0))
+        return len(rows) - 1
 
 
 class LazyStats(dict):

@@ -6,6 +6,9 @@ Mirrors the reference's src/vqvae.py: constructor arguments and config splatting
 `mean_forward` (:218-257), `padded_concat` (:259-271).
 State-dict prefixes are the reference's (`asr.*`, `codebook.*`, `spkr_embed.weight`, `tts.*`).
 """
+import math
+import numbers
+
 import torch
 import torch.nn as nn
 
@@ -16,9 +19,36 @@ from .embed import L2Embedding, SeperateEmbedding
 from .tts import Tacotron2
 
 FRAME_PHN_RATIO = 6.0          # ref: src/vqvae.py:18
+SYNTH_MAX_FRAMES_PER_PHONE = 2.0 * FRAME_PHN_RATIO     # synthesise: the decode budget per phone, twice the corpus average
+INFERENCE_MARGIN_FRAMES = 40   # ref: bin/gen_specgram.py:17
 PRETRAINED_ENCODER_PREFIX = 'encoder.'      # ref: src/vqvae.py:13-15
 PRETRAINED_DECODER_PREFIX = 'decoder.'
 PRETRAINED_POSTNET_PREFIX = 'postnet.'
+
+
+def check_transcript(ids, vocab_size):
+    """a transcript synthesise takes: at least one id, every id in [1, vocab_size) (index 0 is the token appended after the last phone
+    and the batch padding: inside a transcript it would end it early).  ValueError saying what is wrong otherwise."""
+    ids = list(ids)
+    if not ids:
+        raise ValueError('empty transcript')
+    for k, i in enumerate(ids):
+        if isinstance(i, bool) or int(i) != i:
+            raise ValueError('token %d is %r, not an id' % (k, i))
+        if i == 0:
+            raise ValueError('token %d is id 0, the end / padding index' % k)
+        if not 0 < i < vocab_size:
+            raise ValueError('token %d is id %d, outside the vocabulary of %d' % (k, i, vocab_size))
+    return [int(i) for i in ids]
+
+
+def synth_frames(n_max, r, max_frames_per_phone=SYNTH_MAX_FRAMES_PER_PHONE):
+    """frames synthesise decodes for a batch whose longest transcript has n_max phones: n_max * max_frames_per_phone plus the
+    reference's margin, rounded up to whole decoder steps of r frames"""
+    if not (n_max >= 1 and r >= 1 and 0.0 < max_frames_per_phone < float('inf')):
+        raise ValueError('synth_frames: n_max=%r, r=%r, max_frames_per_phone=%r: need n_max, r >= 1 and a finite positive budget'
+                         % (n_max, r, max_frames_per_phone))
+    return int(r) * int(math.ceil((n_max * max_frames_per_phone + INFERENCE_MARGIN_FRAMES) / r))
 
 
 class VQVAE(nn.Module):
@@ -177,6 +207,39 @@ class VQVAE(nn.Module):
                 return forced_align(prob, text, lengths.clamp(0, prob.shape[1]), text_lengths, log_input=source == 'post')
         finally:
             self.train(was_training)
+
+    def synthesise(self, transcripts, sid, max_frames_per_phone=SYNTH_MAX_FRAMES_PER_PHONE):
+        """Free-running synthesis of phone transcripts, in eval mode without gradients (the mode is restored after).  transcripts: a
+        list of id lists (check_transcript: non-empty, ids in [1, vocab_size)); sid: one speaker id for all, or one per transcript.
+        Each transcript becomes ids + [0] -- the index 0 PhoneTextEncoder appends (src/text.py:65) -- and the batch is padded with 0 to
+        its longest, as training batches are.  The decoder runs synth_frames(n_max, r, max_frames_per_phone) frames at tf_rate 0
+        through text_to_speech unchanged; where each utterance ends is for metrics.attention_endpoints to say.
+        Padded phones are seen by the encoder and the attention, unmasked: this follows the reference and every batch the model was
+        trained on, so an utterance's output depends on its batch's longest transcript.  A batch of one gives the alone result.
+        -> (mel (B, T, n_mels), linear (B, T, linear_dim), align (B, T / r, n_max + 1), enc_len (B,) int32: the real phones of each
+        utterance), device tensors."""
+        rows = [check_transcript(t, self.vocab_size) for t in transcripts]
+        if not rows:
+            raise ValueError('synthesise: no transcripts')
+        B, dev = len(rows), self.spkr_embed.weight.device
+        sids = [int(sid)] * B if isinstance(sid, numbers.Integral) else [int(s) for s in (sid.reshape(-1).tolist() if torch.is_tensor(sid) else sid)]
+        if len(sids) != B or any(not 0 <= s < self.n_spkr for s in sids):
+            raise ValueError('synthesise: sid %r: one id, or one per transcript, in [0, %d)' % (sid, self.n_spkr))
+        n_max = max(len(t) for t in rows)
+        frames = synth_frames(n_max, self.n_frames_per_step, float(max_frames_per_phone))
+        text = torch.zeros(B, n_max + 1, dtype=torch.int64)
+        for b, t in enumerate(rows):
+            text[b, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        enc_len = torch.tensor([len(t) for t in rows], dtype=torch.int32)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                mel, linear, align, _, _, _, _, _ = self.text_to_speech(
+                    text.to(dev), torch.tensor(sids, dtype=torch.int64).to(dev), None, None, None, None, frames, None, tf_rate=0.0)
+        finally:
+            self.train(was_training)
+        return mel, linear, align, enc_len.to(dev)
 
     def text_to_speech(self, paired_text, paired_sid, unpaired_sid, unpaired_latent, unpaired_text, unpaired_latent_len,
                        paired_teacher, unpaired_teacher, tf_rate, _masks=None):
