@@ -1377,6 +1377,46 @@ int st_resample_batch(const void* x, int pcm16, long n_samples, const long* off,
                       int first_min, int first_max, const int* first, const float* table, float* y, long n_out, const long* out_off,
                       void* stream);
 
+/* ------------------------------------------------------------------ pitch (waveforms -> F0 tracks) and F0 figures along a warp
+ * Not a step of the reference (it has no pitch tracker).  st_f0_yin is the YIN estimator (de Cheveigne & Kawahara 2002, steps 2 - 5)
+ * on the RAW waveform (no pre-emphasis) of a ragged batch (st_wave_batch, B <= 64).
+ * Frames.  Utterance b with L = len[b] samples x[0 .. L) has the frames t = 0 .. T - 1, T = 1 + L / hop (the MFCC frame count at
+ * hop = hop_length_mfcc: a DTW path over MFCC rows indexes F0 rows directly).  Frame t starts at s0 = t hop - W / 2 (integer
+ * division) and reads the W + tau_max samples x[s0 .. s0 + W + tau_max), with x[i] = 0 for i outside [0, L).
+ * Difference function, the DIRECT form in fp32:  d(tau) = sum_{j = 0}^{W - 1} (x[s0 + j] - x[s0 + j + tau])^2,  tau = 0 .. tau_max,
+ * every term non-negative, formed as one chain acc = fmaf(e, e, acc), e = x[s0 + j] - x[s0 + j + tau], over ascending j.  (The
+ * autocorrelation / FFT form r(0) + r_tau(0) - 2 r(tau) cancels and is not used.)
+ * Cumulative-mean-normalised difference:  c(tau) = sum_{k = 1}^{tau} d(k) (an fp32 prefix sum whose order depends on tau_max alone),
+ * d'(0) = 1,  d'(tau) = d(tau) * tau / c(tau) (one fp32 product, one correctly rounded quotient), or 1 where c(tau) = 0 (digital silence).
+ * Search.  tau0 = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold.  Without one the frame is unvoiced: f0 = 0,
+ * aper = min_{tau in [tau_min, tau_max]} d'(tau).  Otherwise tau* = the smallest tau >= tau0 with tau = tau_max or d'(tau + 1) >= d'(tau).
+ * Parabolic refinement with a, b, c = d'(tau* - 1), d'(tau*), d'(tau* + 1): when tau* < tau_max and a > b,
+ * delta = 0.5 (a - c) / ((a - b) + (c - b)) (the denominator a - 2b + c, positive by construction; delta in (-0.5, 0.5]); otherwise
+ * delta = 0.  f0 = sample_rate / (tau* + delta), aper = b.
+ * Outputs: f0 (B, T_pad) in Hz, aper (B, T_pad) or NULL; rows t >= T up to T_pad are written 0.  A NaN or an infinity among the
+ * samples a frame reads makes that frame's f0 and aper NaN, and only that frame's.  A frame depends on its utterance alone: bitwise
+ * repeatable, independent of B, of the position in the batch and of T_pad.  One launch, no workspace, no atomics, no host read.
+ * Limits (-22 past them, before any device call): 1 <= B <= 64, every len >= 1, hop >= 1, 2 <= tau_min < tau_max <= 1024,
+ * 1 <= W <= 2048, T_pad >= the largest T, 0 < threshold <= 1 (finite), sample_rate finite and positive.
+ * st_f0_run_length: the consecutive frames one workgroup takes from one staged span at this framing (8, fewer when 7 hop + W + tau_max
+ * would pass 10240 samples; 0 outside the limits) -- for tests that straddle it. */
+int st_f0_run_length(int hop, int W, int tau_max);
+int st_f0_yin(const st_wave_batch* w, int hop, int W, int tau_min, int tau_max, float sample_rate, float threshold,
+              float* f0 /* (B, T_pad) */, float* aper /* (B, T_pad) or NULL */, int T_pad, void* stream);
+
+/* F0 figures of B pairs of tracks along a warp: f0_x(b, i) = f0_x[b x_sb + i], i < Tx, likewise f0_y (strides in floats); path
+ * (B, P, 2) int32 and path_len (B) exactly as st_dtw_batch writes them (P = its Tx + Ty - 1; -1 past path_len).  Only the first
+ * path_len[b] (clamped to [0, P]) entries are read; an index outside [0, Tx) x [0, Ty) among them is NOT checked.
+ * A frame is voiced iff f0 > 0 (NaN: unvoiced).  counts (B, 4) int32 = (n_pairs = path_len, n_both = pairs with both sides voiced,
+ * n_vuv = pairs whose voicing differs, n_gross = both-voiced pairs with |fx - fy| > 0.2 fy, compared in float64).  sums (B, 2) fp32 =
+ * (sum c^2, sum c) over the both-voiced pairs, c = 1200 log2(fx / fy) cents evaluated in float64 and rounded once to fp32.
+ * Summation order: thread tid of 256 adds its entries p = tid, tid + 256, ... in ascending p (c^2 by fmaf) into fp32 partials; the 64
+ * partials of a wave combine by the xor butterfly (lane offsets 32, 16, 8, 4, 2, 1), the four wave sums as (w0 + w1) + (w2 + w3):
+ * bitwise repeatable.  path_len 0 gives zeros.  One launch, one workgroup per pair.  Limits (-22): B, Tx, Ty, P >= 1, strides >= 0. */
+int st_f0_path_scores(const float* f0_x, long x_sb, int Tx, const float* f0_y, long y_sb, int Ty,
+                      const int32_t* path /* (B, P, 2) */, const int32_t* path_len /* (B) */, int B, int P,
+                      int32_t* counts /* (B, 4) */, float* sums /* (B, 2) */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --resample      (files of any sample rate)
     python main.py --resample-wav-dir DIR --resample-out DIR2 --resample-rate 16000 [--batch-size 32]
     python main.py --config config/supervised.yaml --feat-wav-dir DIR --feat mfcc|mel|linear [--segment-file FILE --min-segment-len 2]
-    python main.py --config config/supervised.yaml --mcd-wav-dir SYN --mcd-ref-dir REF [--mcd-path --batch-size 32]
+    python main.py --config config/supervised.yaml --feat-wav-dir DIR --feat f0 [--f0-min 60 --f0-max 500 --f0-threshold 0.15]
+    python main.py --config config/supervised.yaml --mcd-wav-dir SYN --mcd-ref-dir REF [--mcd-path --mcd-f0 --batch-size 32]
     python main.py --config config/supervised.yaml --synth-phn-dir DIR [--load ckpt.pth --vocab FILE --synth-sid 0 --gen-wav --batch-size 8]
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
 `--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
@@ -41,6 +42,9 @@ them; `--resample-wav-dir` converts a directory of .wav files to another rate an
 `--mcd-wav-dir` (not a mode of the reference) scores synthesised .wav files against the recordings of `--mcd-ref-dir` by mel-cepstral
 distortion along a dynamic-time-warping path (solver.McdScorer, semi_tts_amd.metrics.mcd): mcd.csv, one row per pair, and with
 `--mcd-path` the warp of every pair as <key>.dtw.npy.
+`--feat f0` writes the pitch track of every file as <stem>-f0.npy (frames,) in Hz, 0 where unvoiced (the YIN tracker of
+AudioConverter.extract_f0_batch at the MFCC hop), and `--mcd-f0` adds f0.csv to --mcd-wav-dir: F0 RMSE in cents, voicing error and gross
+pitch error of every pair along the warp of its MCD (semi_tts_amd.metrics.f0_scores).
 `--synth-phn-dir` (not a mode of the reference, which decodes to the length of the ground-truth mel) synthesises the .phn transcripts of a
 directory -- what `--transcribe-wav-dir` writes, as it is -- and finds where each utterance ends from its attention on the GPU
 (solver.Synthesiser, semi_tts_amd.metrics.attention_endpoints): <name>-mel.npy, -spec.npy, -align.npy, -dur.npy cut at the end, with
@@ -126,8 +130,9 @@ parser.add_argument('--resample-rate', default=None, type=int, help='--resample-
                     'of --config)')
 parser.add_argument('--feat-wav-dir', default=None, type=str, help='extract --feat from the .wav files of this directory (sorted by name, batched '
                     'by --batch-size) on the GPU into <logdir>/<name>/<stem>-<feat>.npy (frames, dim); no checkpoint, no model')
-parser.add_argument('--feat', default=None, choices=('mfcc', 'mel', 'linear'), help='--feat-wav-dir: the feature written: 39-dimensional MFCC '
-                    '(25 / 10 ms framing), or the clean mel / linear spectrogram of data.audio')
+parser.add_argument('--feat', default=None, choices=('mfcc', 'mel', 'linear', 'f0'), help='--feat-wav-dir: the feature written: 39-dimensional MFCC '
+                    '(25 / 10 ms framing), the clean mel / linear spectrogram of data.audio, or f0: the pitch track in Hz at the MFCC hop, '
+                    '<stem>-f0.npy (frames,), 0 where unvoiced (not with --segment-file)')
 parser.add_argument('--segment-file', default=None, type=str, help='--feat-wav-dir: a segment table (file,seg: the segments.csv of '
                     '--align-wav-dir); also write <stem>-<feat>-seg.npy (segments, longest piece, dim), the feature cut at its boundaries')
 parser.add_argument('--min-segment-len', default=None, type=int, help='--segment-file: the fewest frames of a segment; a shorter piece joins '
@@ -138,6 +143,12 @@ parser.add_argument('--mcd-wav-dir', default=None, type=str, help='score the syn
 parser.add_argument('--mcd-ref-dir', default=None, type=str, help='--mcd-wav-dir: the directory of the recordings, <key>.wav for every synthesised '
                     'file (key: its name up to the first ".", without one trailing "-pred")')
 parser.add_argument('--mcd-path', action='store_true', help='--mcd-wav-dir: also write the warp of every pair as <key>.dtw.npy, (path_len, 2) int32')
+parser.add_argument('--mcd-f0', action='store_true', help='--mcd-wav-dir: also track the pitch of both sides and write <logdir>/<name>/f0.csv '
+                    '(file,path_len,voiced_pairs,f0_rmse_cents,vuv_error,gross_error,mean_cents) along the warp of the MCD')
+parser.add_argument('--f0-min', default=None, type=float, help='--feat f0 / --mcd-f0: the lowest pitch searched, in Hz (default 60)')
+parser.add_argument('--f0-max', default=None, type=float, help='--feat f0 / --mcd-f0: the highest pitch searched, in Hz (default 500)')
+parser.add_argument('--f0-threshold', default=None, type=float, help='--feat f0 / --mcd-f0: the YIN threshold on the normalised difference, in '
+                    '(0, 1] (default 0.15)')
 parser.add_argument('--synth-phn-dir', default=None, type=str, help='synthesise the .phn transcripts of this directory (sorted by name, batched by '
                     '--batch-size; ids or --vocab symbols, the files of --transcribe-wav-dir as they are), each cut where its attention has '
                     'stayed on the last phone: <logdir>/<name>/<file>-mel.npy, -spec.npy, -align.npy, -dur.npy, with --gen-wav -pred.wav, and '
@@ -252,6 +263,15 @@ def parse_args(argv=None):
             parser.error('--mcd-wav-dir needs --config (its data.audio) and --mcd-ref-dir DIR (the recordings)')
     elif paras.mcd_ref_dir is not None or paras.mcd_path:
         parser.error('--mcd-ref-dir and --mcd-path belong to --mcd-wav-dir; they need that flag')
+    elif paras.mcd_f0:
+        parser.error('--mcd-f0 belongs to --mcd-wav-dir; it needs that flag')
+    if not (paras.feat == 'f0' or paras.mcd_f0) and any(v is not None for v in (paras.f0_min, paras.f0_max, paras.f0_threshold)):
+        parser.error('--f0-min, --f0-max and --f0-threshold set the pitch tracker of --feat f0 and --mcd-f0; they need one of them')
+    paras.f0_min = 60.0 if paras.f0_min is None else paras.f0_min
+    paras.f0_max = 500.0 if paras.f0_max is None else paras.f0_max
+    paras.f0_threshold = 0.15 if paras.f0_threshold is None else paras.f0_threshold
+    if not (0.0 < paras.f0_min < paras.f0_max) or not (0.0 < paras.f0_threshold <= 1.0):
+        parser.error('--f0-min, --f0-max and --f0-threshold need 0 < --f0-min < --f0-max and 0 < --f0-threshold <= 1')
     if paras.synth_phn_dir is not None:
         for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
                      'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir'):

@@ -401,6 +401,9 @@ SIGNATURES = {
     'st_audio_mfcc': [C.POINTER(StWaveBatch), C.POINTER(StFraming), F, C.POINTER(StMelBank), P, I, P, P, I, P],
     'st_segment_gather': [P, C.c_long, C.c_long, I, I, I, P, P, P, I, I, P, P],
     'st_resample_batch': [P, I, C.c_long, P, P, I, I, I, I, I, I, P, P, P, C.c_long, P, P],
+    'st_f0_run_length': [I, I, I],
+    'st_f0_yin': [C.POINTER(StWaveBatch), I, I, I, I, F, F, P, P, I, P],
+    'st_f0_path_scores': [P, C.c_long, I, P, C.c_long, I, P, P, I, I, P, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,

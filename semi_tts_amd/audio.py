@@ -32,6 +32,7 @@ MFCC and phone segments (st_audio_mfcc, st_segment_gather; src/audio.py:94-154, 
     seg, counts = conv.segment_batch(mfcc, frames, keys)          # a whole batch in one launch: (S_total, max_len, 39)
 """
 import csv
+import math
 import random
 import wave
 
@@ -458,6 +459,47 @@ class AudioConverter:
         x = torch.as_tensor(waveform)
         x = x[channel] if x.dim() == 2 else x
         return self.extract_mfcc_batch([x], preemphasis=preemphasis)[0].t().to(x.device)
+
+    # -- pitch (not a step of the reference): the YIN tracker st_f0_yin at the MFCC hop
+    def f0_lags(self, fmin=60., fmax=500., window=None):
+        """(tau_min, tau_max, W) of extract_f0_batch: tau_max = ceil(sr / fmin), tau_min = floor(sr / fmax), W = window or 2 tau_max;
+        ValueError naming the limit of st_f0_yin an fmin / fmax / window leaves"""
+        fmin, fmax = float(fmin), float(fmax)
+        if not (0.0 < fmin < fmax < float('inf')):
+            raise ValueError('f0: needs 0 < fmin < fmax (got fmin %r, fmax %r)' % (fmin, fmax))
+        tau_max, tau_min = int(math.ceil(self.sr / fmin)), int(math.floor(self.sr / fmax))       # (fmin < fmax: tau_min < tau_max)
+        if tau_max > ops.F0_MAX_TAU:
+            raise ValueError('f0: fmin %g Hz at %d Hz needs lags up to tau_max = %d; the limit is tau_max <= %d (fmin >= %.2f Hz)'
+                             % (fmin, self.sr, tau_max, ops.F0_MAX_TAU, self.sr / ops.F0_MAX_TAU))
+        if tau_min < 2:
+            raise ValueError('f0: fmax %g Hz at %d Hz gives tau_min = %d; the limit is tau_min >= 2 (fmax <= %.1f Hz)'
+                             % (fmax, self.sr, tau_min, self.sr / 2.0))
+        W = 2 * tau_max if window is None else int(window)
+        if not 1 <= W <= ops.F0_MAX_W:
+            raise ValueError('f0: window %d outside the limit 1 <= W <= %d' % (W, ops.F0_MAX_W))
+        return tau_min, tau_max, W
+
+    def extract_f0_batch(self, wavs, fmin=60., fmax=500., threshold=0.15, window=None, with_aper=False):
+        """F0 in Hz of a ragged batch in one st_f0_yin call: wavs as extract_mfcc_batch takes them (a list of 1-D waveforms or a
+        WaveBatch), sorted longest first -> device (B, T_pad), frame t of an utterance centred on sample t * hop_length_mfcc, T_pad the
+        longest utterance's 1 + L // hop_length_mfcc (the rows of extract_mfcc_batch), 0 on unvoiced frames and past an utterance's own
+        frames.  The raw waveform, no pre-emphasis.  Lags and window: f0_lags.  with_aper: -> (f0, aper (B, T_pad)), the normalised
+        difference d' at the chosen lag (the minimum of d' on an unvoiced frame).  Each utterance is bitwise what it gives alone."""
+        tau_min, tau_max, W = self.f0_lags(fmin, fmax, window)
+        wb = wavs if isinstance(wavs, WaveBatch) else WaveBatch(wavs)
+        hop = self.hop_length_mfcc
+        ops._f0_check(wb.lens, hop, W, tau_min, tau_max, self.sr, threshold)
+        dev = wb.device if wb.device is not None else _device()
+        T_pad = int(1 + wb.lens.max() // hop)
+        f0, aper = ops.f0_yin(wb.packed(dev), wb.offsets, wb.lens, hop, W, tau_min, tau_max, float(self.sr), threshold, T_pad, with_aper=with_aper)
+        return (f0, aper) if with_aper else f0
+
+    def extract_f0_from_waveform(self, waveform, fmin=60., fmax=500., threshold=0.15, window=None, channel=0):
+        """the single-utterance form of extract_f0_batch: waveform (channels, samples) or (samples,) -> (T,) F0 in Hz of `channel`,
+        T = 1 + samples // hop_length_mfcc, on the waveform's device (computed on the GPU either way)"""
+        x = torch.as_tensor(waveform)
+        x = x[channel] if x.dim() == 2 else x
+        return self.extract_f0_batch([x], fmin, fmax, threshold, window)[0].to(x.device)
 
     def extract_mfcc_from_file(self, wav_path, preemphasis=True, channel=0):
         """src/audio.py:119-130: the file-taking form of extract_mfcc_from_waveform"""

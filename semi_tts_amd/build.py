@@ -9,6 +9,8 @@ LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libsemitts_hip.so')
 SOURCES = ['skinny.hip', 'skinny_packed.hip', 'attention.hip', 'gemm.hip', 'rnn.hip', 'vq.hip', 'runtime.hip', 'decoder.hip', 'grad.hip', 'attention_bwd.hip', 'decoder_bwd.hip', 'loss.hip', 'optim.hip', 'norm.hip', 'audio.hip', 'ctc_decode.hip', 'ctc_align.hip', 'resample.hip', 'dtw.hip',
            'attn_stats.hip']
+# the pitch kernels (st_f0_yin, st_f0_path_scores), listed apart: tests/test_synth_host.py pins the twenty entries above
+PITCH_SOURCES = ['f0.hip']
 
 
 def _hipcc():
@@ -33,7 +35,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES:
+    for src in SOURCES + PITCH_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

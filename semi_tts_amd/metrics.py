@@ -19,6 +19,13 @@ of the same pass: `attention_endpoints`, one HIP launch per batch (st_attn_endpo
     from semi_tts_amd.metrics import attention_endpoints
     mel, linear, align, enc_len = model.synthesise(transcripts, sid)
     ep = attention_endpoints(align, enc_len)        # ep.end[b] decoder steps = r * ep.end[b] frames
+
+Pitch along the same warp: F0 RMSE in cents, voicing error and gross pitch error of two F0 tracks (AudioConverter.extract_f0_batch, the
+YIN tracker st_f0_yin) over the frame pairs of the path `mcd` returned: `f0_scores`, one HIP launch per batch (st_f0_path_scores,
+semi_tts_amd/csrc/f0.hip).
+
+    from semi_tts_amd.metrics import f0_scores
+    s = f0_scores(conv.extract_f0_batch(syn), conv.extract_f0_batch(ref), path, path_len)     # s['f0_rmse_cents'][b], s['vuv_error'][b]
 """
 import collections
 import math
@@ -137,3 +144,24 @@ def attention_endpoints(align, enc_len, patience=3, max_jump=4):
     read; bad arguments raise ValueError before the device is touched."""
     stats, focus, peak, dur = ops.attn_endpoint(align, enc_len, patience, max_jump)
     return AttentionEndpoints(*stats.unbind(1), focus, peak, dur)
+
+
+def f0_scores(f0_x, f0_y, path, path_len):
+    """Pitch figures of B pairs of F0 tracks along a warp: f0_x (B, Tx), f0_y (B, Ty) float32 in Hz as AudioConverter.extract_f0_batch
+    gives them (0 or NaN: unvoiced), path (B, Tx + Ty - 1, 2) and path_len (B,) as `dtw` / `mcd` return them for sequences of Tx and Ty
+    frames -- the path MUST come from there: its entries index the tracks unchecked.  Over the path_len frame pairs (i, j) of a pair:
+      n_pairs, n_both (both frames voiced), n_vuv (one voiced, one not), n_gross (both voiced and |fx - fy| > 0.2 fy): int32;
+      f0_rmse_cents = sqrt(sum c^2 / n_both), mean_cents = sum c / n_both with c = 1200 log2(fx / fy), NaN where n_both = 0;
+      vuv_error = n_vuv / n_pairs, gross_error = n_gross / n_both (NaN where the denominator is 0).
+    -> a dict of (B,) device tensors (the four counts, the four figures, and sum_sq_cents / sum_cents as the kernel summed them).
+    One launch and a few element-wise divisions on the device; no host read.  Bitwise repeatable."""
+    counts, sums = ops.f0_path_scores(f0_x, f0_y, path, path_len)
+    n_pairs, n_both, n_vuv, n_gross = counts.unbind(1)
+    nan = torch.full_like(sums[:, 0], math.nan)
+    both, pairs = n_both.to(torch.float32), n_pairs.to(torch.float32)
+    some, any_pair = n_both > 0, n_pairs > 0
+    return {'n_pairs': n_pairs, 'n_both': n_both, 'n_vuv': n_vuv, 'n_gross': n_gross, 'sum_sq_cents': sums[:, 0], 'sum_cents': sums[:, 1],
+            'f0_rmse_cents': torch.where(some, torch.sqrt(sums[:, 0] / both.clamp_min(1.0)), nan),
+            'mean_cents': torch.where(some, sums[:, 1] / both.clamp_min(1.0), nan),
+            'vuv_error': torch.where(any_pair, n_vuv.to(torch.float32) / pairs.clamp_min(1.0), nan),
+            'gross_error': torch.where(some, n_gross.to(torch.float32) / both.clamp_min(1.0), nan)}

@@ -2146,3 +2146,103 @@ def resample_batch(x, off, lens, o, n, first, table, first_min, first_max, out=N
                                     int(o), int(n), table.shape[1], int(first_min), int(first_max), _p(first, torch.int32), _p(table),
                                     _p(out), total, _host_ptr(out_off, b0), stream_handle()), 'st_resample_batch')
     return out, out_off, out_lens
+
+
+# --------------------------------------------------------------------------------------------- pitch (st_f0_yin, st_f0_path_scores)
+F0_MAX_TAU, F0_MAX_W = 1024, 2048    # st_f0_yin's limits
+F0_RUN, F0_MAX_SPAN = 8, 10240       # frames a workgroup takes from one staged span, and the samples such a span may hold (f0.hip)
+
+
+def f0_run_length(hop, W, tau_max):
+    """the consecutive frames one st_f0_yin workgroup takes at this framing (st_f0_run_length): the tests straddle it"""
+    r = F0_RUN
+    while r > 1 and (r - 1) * int(hop) + int(W) + int(tau_max) > F0_MAX_SPAN:
+        r -= 1
+    return r
+
+
+def _f0_check(lens, hop, W, tau_min, tau_max, sample_rate, threshold):
+    """every refusal of st_f0_yin that does not need the buffers, raised before any device is touched"""
+    for name, v in (('hop', hop), ('W', W), ('tau_min', tau_min), ('tau_max', tau_max)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError('f0_yin: %s must be an integer (got %r)' % (name, v))
+    if hop < 1:
+        raise ValueError('f0_yin: hop %d below 1' % hop)
+    if not 2 <= tau_min < tau_max <= F0_MAX_TAU:
+        raise ValueError('f0_yin: lags [%d, %d] outside 2 <= tau_min < tau_max <= %d' % (tau_min, tau_max, F0_MAX_TAU))
+    if not 1 <= W <= F0_MAX_W:
+        raise ValueError('f0_yin: window W = %d outside [1, %d]' % (W, F0_MAX_W))
+    threshold, sample_rate = float(threshold), float(sample_rate)
+    if not 0.0 < threshold <= 1.0:
+        raise ValueError('f0_yin: threshold must lie in (0, 1] (got %r)' % (threshold,))
+    if not 0.0 < sample_rate < float('inf'):
+        raise ValueError('f0_yin: sample_rate must be finite and positive (got %r)' % (sample_rate,))
+    lens = np.asarray(lens)
+    if lens.ndim != 1 or lens.shape[0] < 1 or lens.dtype.kind not in 'iu' or (lens < 1).any() or (lens >= 2 ** 31).any():
+        raise ValueError('f0_yin: lens must be B >= 1 integers in [1, 2^31) (got %s)' % (lens.tolist(),))
+
+
+def f0_yin(x, off, lens, hop, W, tau_min, tau_max, sample_rate, threshold, T_pad, with_aper=False):
+    """st_f0_yin on a ragged batch packed as for audio_features: x the packed float32 waveforms on the device, utterance b =
+    x[off[b]:off[b] + lens[b]].  -> (f0 (B, T_pad) in Hz, 0 on unvoiced frames and on the rows past 1 + lens[b] // hop; aper (B, T_pad),
+    the normalised difference at the chosen lag, or None without with_aper).  Batches above FEATURES_MAX_BATCH are issued in chunks
+    of it.  Anything the kernel would refuse raises ValueError before the device is touched."""
+    _f0_check(lens, hop, W, tau_min, tau_max, sample_rate, threshold)
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('f0_yin: x must be a packed 1-D contiguous float32 GPU tensor (got %s)'
+                         % ('%s %s on %s' % (tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x).__name__))
+    B = len(lens)
+    off, lens = _host_off_lens(off, lens)
+    if off.shape != (B,) or (off < 0).any() or (off + lens > x.numel()).any():
+        raise ValueError('f0_yin: an utterance lies outside the %d packed samples (off %s, lens %s)' % (x.numel(), off.tolist(), lens.tolist()))
+    T_pad = int(T_pad)
+    if T_pad < 1 + int(lens.max()) // hop:
+        raise ValueError('f0_yin: T_pad %d below the %d frames of the longest utterance' % (T_pad, 1 + int(lens.max()) // hop))
+    lib = _lib.load()
+    f0 = torch.empty(B, T_pad, device=x.device, dtype=torch.float32)
+    aper = torch.empty(B, T_pad, device=x.device, dtype=torch.float32) if with_aper else None
+    w = _lib.StWaveBatch(x=_p(x), n_samples=x.numel())
+    for b0, nb in _chunks(B):
+        check(lib.st_f0_yin(_wave_chunk(w, off, lens, b0, nb), int(hop), int(W), int(tau_min), int(tau_max), float(sample_rate), float(threshold),
+                            _p(f0[b0:]), _p(aper[b0:]) if with_aper else None, T_pad, stream_handle()), 'st_f0_yin')
+    return f0, aper
+
+
+def f0_path_scores(f0_x, f0_y, path, path_len):
+    """st_f0_path_scores: f0_x (B, Tx) and f0_y (B, Ty) float32 tracks on one GPU (unit stride along a row, any row stride), path
+    (B, P, 2) int32 and path_len (B,) int32 on the same device.  THE PATH MUST COME FROM metrics.dtw / metrics.mcd over sequences of
+    Tx and Ty rows (P = Tx + Ty - 1): the kernel reads its first path_len entries as indices without checking them.
+    -> (counts (B, 4) int32 = (n_pairs, n_both, n_vuv, n_gross), sums (B, 2) float32 = (sum c^2, sum c) in cents over the both-voiced
+    pairs) device tensors; one launch, no host read.  Anything else raises ValueError before the device is touched."""
+    for name, t in (('f0_x', f0_x), ('f0_y', f0_y)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError('f0_path_scores: %s must be a (B, T) float32 GPU tensor (got %s)'
+                             % (name, '%s %s on %s' % (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+    dev = f0_x.device
+    B, Tx = f0_x.shape
+    Ty = f0_y.shape[1]
+    if f0_y.device != dev or f0_y.shape[0] != B or B < 1 or Tx < 1 or Ty < 1:
+        raise ValueError('f0_path_scores: f0_x is %s on %s, f0_y is %s on %s: B >= 1 pairs of at least one frame on one device'
+                         % (tuple(f0_x.shape), f0_x.device, tuple(f0_y.shape), f0_y.device))
+    strides = []
+    for name, t in (('f0_x', f0_x), ('f0_y', f0_y)):
+        sb = t.stride(0) if B > 1 else 0
+        if (t.stride(1) != 1 and t.shape[1] > 1) or sb < 0:
+            raise ValueError('f0_path_scores: %s has strides %s: a row needs unit stride' % (name, tuple(t.stride())))
+        strides.append(sb)
+    if (not torch.is_tensor(path) or not path.is_cuda or path.device != dev or path.dtype != torch.int32
+            or tuple(path.shape) != (B, Tx + Ty - 1, 2) or not path.is_contiguous()):
+        raise ValueError('f0_path_scores: path must be the contiguous (B, Tx + Ty - 1, 2) = (%d, %d, 2) int32 tensor of metrics.dtw on the device '
+                         'of the tracks (got %s)' % (B, Tx + Ty - 1, '%s %s on %s' % (tuple(path.shape), path.dtype, path.device)
+                                                     if torch.is_tensor(path) else type(path).__name__))
+    if (not torch.is_tensor(path_len) or not path_len.is_cuda or path_len.device != dev or path_len.dtype != torch.int32
+            or tuple(path_len.shape) != (B,) or not path_len.is_contiguous()):
+        raise ValueError('f0_path_scores: path_len must be the (B,) int32 tensor of metrics.dtw on the device of the tracks (got %s)'
+                         % ('%s %s on %s' % (tuple(path_len.shape), path_len.dtype, path_len.device) if torch.is_tensor(path_len)
+                            else type(path_len).__name__))
+    lib = _lib.load()
+    counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    sums = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    check(lib.st_f0_path_scores(_p(f0_x), strides[0], Tx, _p(f0_y), strides[1], Ty, _p(path, torch.int32), _p(path_len, torch.int32), B,
+                                Tx + Ty - 1, _p(counts, torch.int32), _p(sums), stream_handle()), 'st_f0_path_scores')
+    return counts, sums

@@ -291,13 +291,16 @@ class FeatureWriter:
     <logdir>/<stem>-<feat>.npy, (frames, dim) float32.  With --segment-file each utterance is also cut at its row of that table
     (AudioConverter.segment_batch, one launch per batch) into <stem>-<feat>-seg.npy, (segments, its longest piece, dim): what
     AudioConverter.segment_features gives for the file.  No checkpoint, no model.  Every key is looked up in load_data: a file
-    without a row stops the run before anything is written."""
+    without a row stops the run before anything is written.
+    --feat f0 [--f0-min 60 --f0-max 500 --f0-threshold 0.15]: AudioConverter.extract_f0_batch -> <stem>-f0.npy, (frames,) float32 in Hz at
+    the MFCC hop, 0 where unvoiced; a pitch track has no phone segments: --segment-file with it is refused in load_data."""
 
     def __init__(self, config, paras, mode):
         self.config, self.paras, self.mode = config, paras, mode
         self.exp_name = getattr(paras, 'name', None) or 'synthetic'
         self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
         self.feat = paras.feat
+        self.f0_args = f0_args(paras)
 
     def load_data(self):
         from .audio import load_audio_transform
@@ -307,11 +310,15 @@ class FeatureWriter:
             raise ValueError('--feat-wav-dir %s: no .wav files' % self.wav_dir)
         audio = dict(self.config['data']['audio'])
         self.segment_file = getattr(self.paras, 'segment_file', None)
+        if self.feat == 'f0' and self.segment_file is not None:
+            raise ValueError('--feat f0 does not combine with --segment-file: a pitch track is not cut into phone segments')
         if self.segment_file is not None:
             audio.update(segment_file=self.segment_file, segment_feat=self.feat, min_segment_len=int(getattr(self.paras, 'min_segment_len', 2)))
         self.audio_converter = conv = load_audio_transform(**audio)
         if self.feat == 'linear' and not conv.use_linear:
             raise ValueError('--feat linear: data.audio.use_linear is off')
+        if self.feat == 'f0':
+            conv.f0_lags(self.f0_args['fmin'], self.f0_args['fmax'])       # (ValueError naming the limit)
         if self.segment_file is not None:
             for f in self.files:
                 conv.boundary(f)                          # (KeyError naming the file)
@@ -327,6 +334,8 @@ class FeatureWriter:
         wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names])
         if self.feat == 'mfcc':
             return conv.extract_mfcc_batch(wb), 1 + wb.lens // conv.hop_length_mfcc, wb.order
+        if self.feat == 'f0':
+            return conv.extract_f0_batch(wb, **self.f0_args), 1 + wb.lens // conv.hop_length_mfcc, wb.order
         mel, _, lin = conv.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
         return (mel if self.feat == 'mel' else lin), 1 + wb.lens // conv.hop_length, wb.order
 
@@ -361,6 +370,14 @@ class FeatureWriter:
 MCD_PRED_SUFFIX = '-pred'           # what --gen-specgram --gen-wav appends to an utterance's name
 MCD_MAX_BATCH = 64                  # pairs per st_dtw_batch call
 MCD_HEADER = 'file,frames,ref_frames,path_len,mcd_db'
+F0_HEADER = 'file,path_len,voiced_pairs,f0_rmse_cents,vuv_error,gross_error,mean_cents'
+F0_FIGURES = ('f0_rmse_cents', 'vuv_error', 'gross_error', 'mean_cents')
+
+
+def f0_args(paras):
+    """the pitch tracker's settings from --f0-min / --f0-max / --f0-threshold (their defaults when the flags are absent)"""
+    return dict(fmin=float(getattr(paras, 'f0_min', None) or 60.0), fmax=float(getattr(paras, 'f0_max', None) or 500.0),
+                threshold=float(getattr(paras, 'f0_threshold', None) or 0.15))
 
 
 def mcd_key(filename):
@@ -393,12 +410,17 @@ class McdScorer:
     cepstra 1 .. 12, one launch) -> one host read per batch -> <logdir>/mcd.csv (MCD_HEADER, one row per pair) and, with --mcd-path,
     <logdir>/<key>.dtw.npy, the (path_len, 2) int32 warp (synthesised frame, recording frame).  No checkpoint, no model.  Every pair is
     looked up and every header read in load_data: a missing recording, an unreadable file, a foreign sample rate or an utterance
-    the MFCC or the DTW kernel does not take stops the run, naming the file, before any device work."""
+    the MFCC or the DTW kernel does not take stops the run, naming the file, before any device work.
+    --mcd-f0 [--f0-min 60 --f0-max 500 --f0-threshold 0.15]: AudioConverter.extract_f0_batch on both sides as well, and
+    metrics.f0_scores along the path of the same metrics.mcd call (requested with or without --mcd-path) -> <logdir>/f0.csv (F0_HEADER);
+    the figures ride in the batch's one host read.  mcd.csv and the .dtw.npy files are what they are without the flag."""
 
     def __init__(self, config, paras, mode):
         self.config, self.paras, self.mode = config, paras, mode
         self.exp_name = getattr(paras, 'name', None) or 'synthetic'
         self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
+        self.want_f0 = bool(getattr(paras, 'mcd_f0', False))
+        self.f0_args = f0_args(paras)
 
     def _check_file(self, path):
         import wave
@@ -424,6 +446,8 @@ class McdScorer:
         self.syn_dir, self.ref_dir = self.paras.mcd_wav_dir, self.paras.mcd_ref_dir
         self.pairs = mcd_pairs(self.syn_dir, self.ref_dir)
         self.audio_converter = load_audio_transform(**dict(self.config['data']['audio']))
+        if self.want_f0:
+            self.audio_converter.f0_lags(self.f0_args['fmin'], self.f0_args['fmax'])       # (ValueError naming the limit)
         for f, _, ref in self.pairs:
             self._check_file(os.path.join(self.syn_dir, f))
             self._check_file(os.path.join(self.ref_dir, ref))
@@ -434,8 +458,9 @@ class McdScorer:
 
     def score(self, pairs, want_path=False):
         """the pairs [(file, key, recording)] in one call -> per pair, in the given order: (frames, ref_frames, path_len, mcd_db, path
-        (path_len, 2) int32 or None); one host read"""
-        from .metrics import mcd
+        (path_len, 2) int32 or None), with --mcd-f0 followed by (voiced_pairs, f0_rmse_cents, vuv_error, gross_error, mean_cents); one
+        host read"""
+        from .metrics import f0_scores, mcd
         conv = self.audio_converter
         ws = conv.load_batch([os.path.join(self.syn_dir, f) for f, _, _ in pairs])
         wr = conv.load_batch([os.path.join(self.ref_dir, r) for _, _, r in pairs])
@@ -448,12 +473,20 @@ class McdScorer:
         db, plen, path = mcd(cs, fs.tolist(), cr, fr.tolist())
         B = len(pairs)
         cols = [db.view(torch.int32).reshape(B, 1), plen.reshape(B, 1)] + ([path.reshape(B, -1)] if want_path else [])
+        if self.want_f0:                                            # the figures as trailing columns of the same read
+            ps, pr = conv.extract_f0_batch(ws, **self.f0_args), conv.extract_f0_batch(wr, **self.f0_args)
+            pr = pr.index_select(0, torch.from_numpy(perm).to(pr.device))
+            sc = f0_scores(ps, pr, path, plen)
+            cols += [sc['n_both'].reshape(B, 1)] + [sc[k].view(torch.int32).reshape(B, 1) for k in F0_FIGURES]
         host = torch.cat(cols, dim=1).cpu().numpy()                 # (the one host read)
         out = [None] * B
         for row, k in enumerate(ws.order):
             P = int(host[row, 1])
             out[k] = (int(fs[row]), int(fr[row]), P, float(host[row, :1].view(np.float32)[0]),
                       host[row, 2:2 + 2 * P].reshape(P, 2).copy() if want_path else None)
+            if self.want_f0:
+                tail = host[row, -5:]
+                out[k] += (int(tail[0]),) + tuple(float(v) for v in tail[1:].view(np.float32))
         return out
 
     def exec(self):
@@ -461,17 +494,29 @@ class McdScorer:
         B = max(1, min(int(self.paras.batch_size), MCD_MAX_BATCH))
         want_path = bool(getattr(self.paras, 'mcd_path', False))
         t0, rows, vals = time.perf_counter(), [MCD_HEADER], []
+        f0_rows, f0_vals = [F0_HEADER], []
         for i in range(0, len(self.pairs), B):
             pairs = self.pairs[i:i + B]
-            for (f, key, _), (n, m, P, db, path) in zip(pairs, self.score(pairs, want_path)):
+            for (f, key, _), res in zip(pairs, self.score(pairs, want_path)):
+                n, m, P, db, path = res[:5]
                 rows.append('%s,%d,%d,%d,%.4f' % (f, n, m, P, db))
                 vals.append(db)
                 if want_path:
                     np.save(os.path.join(self.logdir, key + '.dtw.npy'), path.astype(np.int32), allow_pickle=False)
+                if self.want_f0:
+                    f0_rows.append('%s,%d,%d,%.2f,%.4f,%.4f,%.2f' % ((f, P) + res[5:]))
+                    f0_vals.append(res[6:])
         with open(os.path.join(self.logdir, 'mcd.csv'), 'w') as f:
             f.write('\n'.join(rows) + '\n')
         self.mean_mcd = float(np.mean(vals))
         print('[INFO]', 'MCD-DTW of %d pairs: mean %.4f dB; %s, %.2f s' % (len(vals), self.mean_mcd, os.path.join(self.logdir, 'mcd.csv'), time.perf_counter() - t0))
+        if self.want_f0:
+            with open(os.path.join(self.logdir, 'f0.csv'), 'w') as f:
+                f.write('\n'.join(f0_rows) + '\n')
+            with np.errstate(all='ignore'):                           # (a pair without a both-voiced frame has NaN figures: left out of the means)
+                self.mean_f0 = dict(zip(F0_FIGURES, np.nanmean(np.asarray(f0_vals, np.float64), axis=0).tolist()))
+            print('[INFO]', 'F0 along the warp: mean RMSE %.2f cents, V/UV error %.4f, gross error %.4f, mean deviation %.2f cents; %s'
+                  % (tuple(self.mean_f0[k] for k in F0_FIGURES) + (os.path.join(self.logdir, 'f0.csv'),)))
         return len(vals)
 
 
