@@ -109,6 +109,12 @@ typedef struct st_t16_view {   /* a k-block range [kb0, kb0 + ceil(k/16)) of a T
     int kb_stride;    /* k-blocks per batch tile of the WHOLE buffer                 */
     int kb0;          /* first k-block of this view                                  */
 } st_t16_view;
+/* CONTRACT (finite neighbours): a product that takes more than one batch tile per workgroup (st_packed_fwd_variant: nb > 1)
+ * reads its activation operand through ONE descriptor over all the batch tiles it spans.  When the reduced
+ * range is not a multiple of the load group (16 k-blocks), the k-blocks that FOLLOW the view's range in every spanned batch tile but
+ * the last are loaded too and multiplied with weight blocks that read as zero.  0 * finite adds exactly 0; 0 * Inf or 0 * NaN would
+ * poison the sum.  So EVERY k-block of the batch tiles an operand spans -- the other views of the same T16 buffer, pad rows and pad
+ * columns included -- must hold finite values: allocate T16 buffers zero-filled, never uninitialised. */
 /* Several logical activations that one consumer multiplies with ONE packed weight matrix share one
  * T16 buffer (e.g. [dec_in | ctx | h_q] for the query LSTM): each producer writes its k-block range
  * of every consumer's buffer, so a consumer streams exactly one contiguous activation run. */
@@ -218,6 +224,27 @@ typedef struct st_attn_pre_job {
 } st_attn_pre_job;
 int st_attn_pre_fwd(const st_attn_pre_job* job, int B, void* stream);   /* the pre part as a launch of its own: no cf_out, no part */
 int st_skinny_linear_packed_attnpre_fwd(const st_packed_linear_job* job, const st_attn_pre_job* pre, void* stream);   /* pre NULL or without s_buf: the linear alone */
+/* The launch(es) a forward product on packed operands takes, from shapes alone (touches no memory; the launchers decide through the
+ * same code).  mode: ST_PK_MODE_CELL st_lstm_cell_packed_fwd (n = H), ST_PK_MODE_LINEAR st_skinny_linear_packed_fwd /
+ * st_skinny_linear_packed_attnpre_fwd (n = N), ST_PK_MODE_CELL_PAIR st_lstm_cell_packed_pair_fwd (jobs (B, n = H) and (B1, n1 = H1)).
+ * Linear only: pre_parts > 0 -- an attention-pre job with that many workgroups per utterance rides along (pre_A, pre_F its dims,
+ * pre_aligned: pm, loc_lin_w and s_buf 16-byte aligned); part_n > 0 -- and a hosted partial product of part_n rows.
+ * Fills out[0] (out[0..1] for a pair that falls back to one launch per cell) and returns the number of launches, or -1 for a refusal.
+ *   family: the kernel; nb: batch tiles per workgroup; grid_x, grid_y: the grid (attention-pre forms: one-dimensional, the linear's
+ *   workgroups, then B * pre_parts attention workgroups, then part_n / 32 of the partial product); vec: the attention-pre workgroups
+ *   use 16-byte loads.
+ * The linear picks the fewest batch tiles per workgroup (at most 4, and at most ceil(B / 16)) that keep the grid within 512. */
+#define ST_PK_MODE_CELL 0
+#define ST_PK_MODE_LINEAR 1
+#define ST_PK_MODE_CELL_PAIR 2
+#define ST_PK_KERNEL 0          /* pk_kernel<mode, nb>: one row tile x nb batch tiles per workgroup */
+#define ST_PK_LSTM_RT2 1        /* pk_lstm_rt2_kernel<nb>: two row tiles x nb batch tiles */
+#define ST_PK_LSTM_RT2_PAIR 2   /* pk_lstm_rt2_pair_kernel: two cells, nb = 1 */
+#define ST_PK_ATTNPRE 3         /* pk_attnpre_kernel<nb, vec> */
+#define ST_PK_ATTNPRE_PART 4    /* pk_attnpre_part_kernel<1, vec> */
+typedef struct st_packed_fwd_query { int mode; int B, n; int B1, n1; int pre_parts, pre_A, pre_F, pre_aligned; int part_n; } st_packed_fwd_query;
+typedef struct st_packed_fwd_launch { int family, nb, grid_x, grid_y, vec; } st_packed_fwd_launch;
+int st_packed_fwd_variant(const st_packed_fwd_query* q, st_packed_fwd_launch* out);
 
 /* st_skinny_linear_packed_fwd (no bias / activation, natural y) whose output columns [n0, n0 + H) are dh of an LSTM cell: the pointwise
  * half of that cell's backward step (st_lstm_cell_bwd_pointwise with dh0 = those columns of y) runs in the EPILOGUE of the product

@@ -187,6 +187,19 @@ class StPackedLinearJob(C.Structure):
                 ('n_split2', C.c_int), ('act2', C.c_int), ('mask2', C.c_void_p), ('ldmask2', C.c_int), ('y3_dst', StT16View)]
 
 
+class StPackJob(C.Structure):
+    _fields_ = [('w', C.c_void_p * 3), ('ldw', C.c_int * 3), ('k', C.c_int * 3), ('nseg', C.c_int), ('N', C.c_int), ('lstm_H', C.c_int),
+                ('packed', C.c_void_p)]
+
+
+class StPackedFwdQuery(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('mode', 'B', 'n', 'B1', 'n1', 'pre_parts', 'pre_A', 'pre_F', 'pre_aligned', 'part_n')]
+
+
+class StPackedFwdLaunch(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('family', 'nb', 'grid_x', 'grid_y', 'vec')]
+
+
 class StFraming(C.Structure):
     _fields_ = [('n_fft', C.c_int), ('win', C.c_int), ('hop', C.c_int)]
 
@@ -279,7 +292,7 @@ SIGNATURES = {
     'st_pack_weight_t': [C.POINTER(P), C.POINTER(I), C.POINTER(I), I, I, P, P],
     'st_relayout_blocks': [I, I, I],
     'st_relayout_batch': [P, I, I, P, P],
-    'st_pack_weight_batch': [P, I, P],
+    'st_pack_weight_batch': [C.POINTER(StPackJob), I, P],
     'st_tile_rows': [P, I, C.POINTER(StT16View), I, I, P],
     'st_untile_rows': [C.POINTER(StT16View), P, I, I, I, P],
     'st_lstm_cell_packed_fwd': [C.POINTER(StLstmCellPackedJob), P],
@@ -287,6 +300,7 @@ SIGNATURES = {
     'st_skinny_linear_packed_fwd': [C.POINTER(StPackedLinearJob), P],
     'st_skinny_linear_packed_attnpre_fwd': [C.POINTER(StPackedLinearJob), C.POINTER(StAttnPreJob), P],
     'st_attn_pre_fwd': [C.POINTER(StAttnPreJob), I, P],
+    'st_packed_fwd_variant': [C.POINTER(StPackedFwdQuery), C.POINTER(StPackedFwdLaunch)],
     'st_attn_fin_fwd': [P, C.POINTER(StAttnFinJob), I, P],
     'st_attn_fin_split_workspace_floats': [I, I, I],
     'st_attn_fin_split_fwd': [P, C.POINTER(StAttnFinJob), P, I, P],

@@ -304,7 +304,8 @@ __device__ __forceinline__ void pk_body(const PkArgs& a, const int tile, const i
     PkSrc src;
     src.w = __builtin_amdgcn_make_buffer_rsrc((void*)(a.w + (size_t)tile * a.w_kbs * 64), 0, KB * 1024, 0x00020000);
     // (measured on gfx950: the scalar offset IS part of the range check, so the activation descriptor spans all NB batch
-    // tiles; a k-block past KB of an earlier tile then reads finite data of the same buffer against a zero weight block)
+    // tiles; a k-block past KB of an earlier tile then reads finite data of the same buffer against a zero weight block -- the
+    // finite-neighbours contract of include/semitts.h (st_t16_view), which the 2-D tiled cell with NB = 2 relies on as well)
     src.x = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + (size_t)bt_base * a.x_kbs * 64), 0, ((NB - 1) * a.x_kbs + KB) * 1024, 0x00020000);
     src.voff = (unsigned)lane * 16u;
     src.x_kbs = a.x_kbs;
@@ -1128,11 +1129,60 @@ __global__ __launch_bounds__(KW * 64, 4) void pk_attnrng_kernel(const f32x4* w, 
 #endif
 int pk_fill(PkArgs& a, const float* packed_w, const st_t16_view* x, int K, const char* who);
 
+// shapes the 2-D tiled LSTM cell takes (two row tiles x half the batch tiles per workgroup)
+inline bool pk_rt2_shape(int B, int tiles) {
+    const int BT = (B + 15) >> 4;
+    return (tiles & 1) == 0 && (BT == 2 || BT == 4) && B > 16 * (BT - 1);
+}
+
+// ------------------------------------------------------------------------------ which launch a forward product takes
+// The ONE place where the kernel family, the batch tiles per workgroup (nb) and the grid of a forward product are decided: pk_dispatch,
+// st_lstm_cell_packed_pair_fwd and pk_linear_impl launch what these functions return, st_packed_fwd_variant reports it.
+struct PkPlan { int family, nb, gx, gy, vec; };      // family: ST_PK_* (include/semitts.h)
+
+// mode 0: LSTM cell (tiles = H / 4), mode 1: linear (tiles = ceil(N / 16))
+inline PkPlan pk_plan(int mode, int B, int tiles) {
+    const int BT = (B + 15) >> 4;
+    // LSTM cell with an even number of batch tiles (B = 17..32 or 49..64): 2-D tiling, two row tiles x half the batch tiles per
+    // workgroup (pk_lstm_rt2_kernel).  Measured: B = 32 9.54 -> 9.05 us per cell (3.16 -> 3.09 ms per C2 pass), B = 64 15.0 -> 13.7 us.
+    if (mode == 0 && pk_rt2_shape(B, tiles)) return PkPlan{ST_PK_LSTM_RT2, BT == 2 ? 1 : 2, tiles / 2, 2, 0};
+    // a small linear (few row tiles) is bound by what ONE compute unit can pull in (its weight tile + the whole activation
+    // operand): one batch tile per workgroup halves the activation bytes per workgroup and doubles the workgroups
+    // ... and a linear with MANY row tiles still wants every compute unit pulling (one CU takes in ~30 GB/s): the fewest batch
+    // tiles per workgroup that keep the grid within 512 workgroups (the 2560-row dgates . W^T of the decoder-LSTM backward: 160
+    // workgroups of two batch tiles -> 320 of one; the second reader of a weight tile is gridDim.x workgroups on: same XCD, an L2 hit)
+    // -- but never more than there are: pk_body<1, NB> spans NB batch tiles with ONE activation descriptor from batch tile
+    // max(BT - NB, 0) on, so NB > BT would read (and discard) k-blocks past the end of the T16 buffer
+    int nb;
+    if (mode == 1) {
+        nb = 1;
+        while (nb < 4 && nb < BT && tiles * ((BT + nb - 1) / nb) > 512) ++nb;
+    } else nb = BT < 4 ? BT : 4;
+    return PkPlan{ST_PK_KERNEL, nb, tiles, (BT + nb - 1) / nb, 0};
+}
+
+// two cells in one launch: both 2-D tiled with one batch tile per workgroup (B = 17..32) and whole row-tile pairs
+inline bool pk_pair_shape(int B0, int H0, int B1, int H1) {
+    return pk_rt2_shape(B0, H0 / 4) && pk_rt2_shape(B1, H1 / 4) && ((B0 + 15) >> 4) == 2 && ((B1 + 15) >> 4) == 2 && H0 % 8 == 0 && H1 % 8 == 0;
+}
+
+// the attention-pre workgroups take 16-byte loads when A and F are multiples of 4 and pm, W_l and S are 16-byte aligned
+inline bool pk_attnpre_vec(int A, int F, bool aligned) { return (A % 4 == 0) && (F % 4 == 0) && aligned; }
+
+// a linear with n_at attention-pre workgroups (and the part_n / 32 workgroups of a hosted partial product, part_n > 0) behind its own:
+// a one-dimensional grid; more than one batch tile per workgroup only past 128 row tiles, then all of them (up to 4)
+inline PkPlan pk_attnpre_plan(int B, int tiles, int n_at, int part_n, bool vec) {
+    const int BT = (B + 15) >> 4;
+    const int nb = (part_n > 0 || BT == 1 || tiles <= 128) ? 1 : (BT < 4 ? BT : 4);
+    const int gy = (BT + nb - 1) / nb;
+    return PkPlan{part_n > 0 ? ST_PK_ATTNPRE_PART : ST_PK_ATTNPRE, nb, tiles * gy + n_at + (part_n >> 5), 1, vec ? 1 : 0};
+}
+
 template <int NB>
-int pk_launch_attnpre(const PkArgs& a, int tiles, const AtArgs& t, hipStream_t st, const PkPartArgs* pp = nullptr) {
+int pk_launch_attnpre(const PkArgs& a, int tiles, const AtArgs& t, const PkPlan& pl, hipStream_t st, const PkPartArgs* pp = nullptr) {
     constexpr int KW = 8, TRIP = NB == 1 ? PK_TRIP_SMALL : 2;
     const int BT = (a.B + 15) >> 4, gy = (BT + NB - 1) / NB;
-    const bool vec = (t.A % 4 == 0) && (t.F % 4 == 0) && st_aligned16(t.pm) && st_aligned16(t.loc_lin_w) && st_aligned16(t.s_buf);
+    const bool vec = pl.vec != 0;
     const AtLds o = at_layout(t.L, t.A, t.E, t.F, t.K, 1, at_pos_per(t.L, t.pre_parts > 1 ? t.pre_parts : 1), vec && t.F == 32 && t.A % 16 == 0);
     size_t lds = (size_t)o.total * sizeof(float);
     if (pp && lds < sizeof(f32x4) * KW * 4 * 64) lds = sizeof(f32x4) * KW * 4 * 64;      // (a hosted partial product's reduction buffer lives in the dynamic LDS region)
@@ -1143,7 +1193,7 @@ int pk_launch_attnpre(const PkArgs& a, int tiles, const AtArgs& t, hipStream_t s
         static size_t configured[2] = {0, 0};
         // (32 KiB rather than 48 on purpose: the kernel also has a static reduction buffer)
         if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, lds > 32 * 1024, configured[vec ? 1 : 0])) return rc;
-        hipLaunchKernelGGL(kern, dim3(tiles * gy + n_at + (pp->N >> 5)), dim3(KW * 64), lds, st, a.w, a.x, a.w_kbs, a.x_kbs,
+        hipLaunchKernelGGL(kern, dim3(pl.gx), dim3(KW * 64), lds, st, a.w, a.x, a.w_kbs, a.x_kbs,
                            a.KB, a.B, a.N, tiles, tiles * gy, t.pm, t.w_prev, t.L, a, t, n_at, *pp);
         ST_LAUNCH_CHECK();
         return 0;
@@ -1151,20 +1201,19 @@ int pk_launch_attnpre(const PkArgs& a, int tiles, const AtArgs& t, hipStream_t s
     auto kern = vec ? pk_attnpre_kernel<NB, KW, TRIP, true> : pk_attnpre_kernel<NB, KW, TRIP, false>;
     static size_t configured[2] = {0, 0};
     if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(kern), lds, lds > 48 * 1024, configured[vec ? 1 : 0])) return rc;
-    hipLaunchKernelGGL(kern, dim3(tiles * gy + n_at), dim3(KW * 64), lds, st, a.w, a.x, a.w_kbs, a.x_kbs,
+    hipLaunchKernelGGL(kern, dim3(pl.gx), dim3(KW * 64), lds, st, a.w, a.x, a.w_kbs, a.x_kbs,
                        a.KB, a.B, a.N, tiles, tiles * gy, t.pm, t.w_prev, t.L, a, t);
     ST_LAUNCH_CHECK();
     return 0;
 }
 
 template <int MODE, int NB>
-int pk_launch(const PkArgs& a, int tiles, hipStream_t st) {
+int pk_launch(const PkArgs& a, const PkPlan& pl, hipStream_t st) {
     // 8 waves x 2 k-blocks in flight, double buffered.  Measured alternatives on MI355X (us per launch in
     // the decode graph, pq / proj / prenet): 16 waves x 6 single-buffered 7.2 / 8.8 / 7.3; 8 waves x 6
     // single-buffered 8.6 / 10.6 / 5.7; this configuration 6.1 / 8.8 / 4.8.
     constexpr int KW = 8, TRIP = (MODE == 1 && NB == 1) ? PK_TRIP_SMALL : 2;
-    const int BT = (a.B + 15) >> 4;
-    dim3 grid(tiles, (BT + NB - 1) / NB);
+    dim3 grid(pl.gx, pl.gy);
     hipLaunchKernelGGL((pk_kernel<MODE, NB, KW, TRIP>), grid, dim3(KW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.N, a.H, a);
     ST_LAUNCH_CHECK();
     return 0;
@@ -1177,54 +1226,36 @@ int pk_launch(const PkArgs& a, int tiles, hipStream_t st) {
 #ifndef PK_LSTM_TRIP
 #define PK_LSTM_TRIP 2
 #endif
-// shapes the 2-D tiled LSTM cell takes (two row tiles x half the batch tiles per workgroup)
-inline bool pk_rt2_shape(int B, int tiles) {
-    const int BT = (B + 15) >> 4;
-    return (tiles & 1) == 0 && (BT == 2 || BT == 4) && B > 16 * (BT - 1);
-}
-
 template <int MODE>
 int pk_dispatch(const PkArgs& a, int tiles, hipStream_t st) {
-    const int BT = (a.B + 15) >> 4;
-    // LSTM cell with an even number of batch tiles (B = 17..32 or 49..64): 2-D tiling, two row tiles x half the batch tiles per
-    // workgroup (pk_lstm_rt2_kernel).  Measured: B = 32 9.54 -> 9.05 us per cell (3.16 -> 3.09 ms per C2 pass), B = 64 15.0 -> 13.7 us.
-    if (MODE == 0 && pk_rt2_shape(a.B, tiles)) {
+    const PkPlan pl = pk_plan(MODE, a.B, tiles);
+    if (pl.family == ST_PK_LSTM_RT2) {
+        if constexpr (MODE == 0) {
         constexpr int LKW = PK_LSTM_KW, LTR = PK_LSTM_TRIP;
+        const dim3 grid(pl.gx, pl.gy);
 #if defined(PK_AUX_Q0) || defined(PK_AUX_D0)      // cache-policy experiment (tools/gpu_lstm_variants.sh): long reductions (the decoder cell) vs short ones
-        if (BT == 2 && a.KB > 128)
-            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 1, PK_AUX_D0, PK_AUX_D1>), dim3(tiles / 2, 2), dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
-        else if (BT == 2)
-            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 1, PK_AUX_Q0, PK_AUX_Q1>), dim3(tiles / 2, 2), dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
+        if (pl.nb == 1 && a.KB > 128)
+            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 1, PK_AUX_D0, PK_AUX_D1>), grid, dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
+        else if (pl.nb == 1)
+            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 1, PK_AUX_Q0, PK_AUX_Q1>), grid, dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
         else
 #endif
-        if (BT == 2)
-            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 1>), dim3(tiles / 2, 2), dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
+        if (pl.nb == 1)
+            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 1>), grid, dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
 #ifdef PK_C5_NB4      // experiment (round 4, tools/gpu_c5_nb4.sh): two row tiles x ALL FOUR batch tiles per workgroup -- 0.75 operand loads per MFMA instead of 1.0, half the workgroups
         else if (getenv("ST_C5_NB4"))
             hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 4>), dim3(tiles / 2, 1), dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
 #endif
         else
-            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 2>), dim3(tiles / 2, 2), dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
+            hipLaunchKernelGGL((pk_lstm_rt2_kernel<LKW, LTR, 2>), grid, dim3(LKW * 64), 0, st, a.w, a.x, a.w_kbs, a.x_kbs, a.KB, a.B, a.H, a);
         ST_LAUNCH_CHECK();
+        }
         return 0;
     }
-    // a small linear (few row tiles) is bound by what ONE compute unit can pull in (its weight tile + the whole activation
-    // operand): one batch tile per workgroup halves the activation bytes per workgroup and doubles the workgroups
-    // ... and a linear with MANY row tiles still wants every compute unit pulling (one CU takes in ~30 GB/s): the fewest batch
-    // tiles per workgroup that keep the grid within 512 workgroups (the 2560-row dgates . W^T of the decoder-LSTM backward: 160
-    // workgroups of two batch tiles -> 320 of one; the second reader of a weight tile is gridDim.x workgroups on: same XCD, an L2 hit)
-    if (MODE == 1 && BT > 1) {
-        int nb = 1;
-        while (nb < 4 && tiles * ((BT + nb - 1) / nb) > 512) ++nb;
-        if (nb == 1) return pk_launch<MODE, 1>(a, tiles, st);
-        if (nb == 2) return pk_launch<MODE, 2>(a, tiles, st);
-        if (nb == 3) return pk_launch<MODE, 3>(a, tiles, st);
-        return pk_launch<MODE, 4>(a, tiles, st);
-    }
-    if (BT == 1) return pk_launch<MODE, 1>(a, tiles, st);
-    if (BT == 2) return pk_launch<MODE, 2>(a, tiles, st);
-    if (BT == 3) return pk_launch<MODE, 3>(a, tiles, st);
-    return pk_launch<MODE, 4>(a, tiles, st);
+    if (pl.nb == 1) return pk_launch<MODE, 1>(a, pl, st);
+    if (pl.nb == 2) return pk_launch<MODE, 2>(a, pl, st);
+    if (pl.nb == 3) return pk_launch<MODE, 3>(a, pl, st);
+    return pk_launch<MODE, 4>(a, pl, st);
 }
 
 PkOut pk_out(const st_t16_view* v) {
@@ -1411,9 +1442,7 @@ extern "C" int st_lstm_cell_packed_pair_fwd(const st_lstm_cell_packed_job* j0, c
     rc = pk_lstm_fill(a1, j1, "st_lstm_cell_packed_pair_fwd");
     if (rc) return rc;
     const int t0 = a0.H / 4, t1 = a1.H / 4;
-    const bool pair = pk_rt2_shape(a0.B, t0) && pk_rt2_shape(a1.B, t1) && ((a0.B + 15) >> 4) == 2 && ((a1.B + 15) >> 4) == 2 &&
-                      a0.H % 8 == 0 && a1.H % 8 == 0;
-    if (!pair) {
+    if (!pk_pair_shape(a0.B, a0.H, a1.B, a1.H)) {
         rc = pk_dispatch<0>(a0, t0, (hipStream_t)stream);
         if (rc) return rc;
         return pk_dispatch<0>(a1, t1, (hipStream_t)stream);
@@ -1462,17 +1491,19 @@ static int pk_linear_impl(const st_packed_linear_job* job, const st_attn_pre_job
     if (pre && pre->s_buf) {
         AtArgs t;
         if (at_pre_fill(t, pre, B, "st_skinny_linear_packed_attnpre_fwd")) return -1;
-        const int BT = (B + 15) >> 4;
+        const bool vec = pk_attnpre_vec(t.A, t.F, st_aligned16(t.pm) && st_aligned16(t.loc_lin_w) && st_aligned16(t.s_buf));
+        const int n_at = t.B * (t.pre_parts > 1 ? t.pre_parts : 1);
         if (pre->part) {
             ST_CHECK_ARG(tiles <= 128, "st_skinny_linear_packed_attnpre_fwd: a partial product rides beside a linear of at most 128 row tiles");
             PkPartArgs pp;
             if (pk_part_job_fill(pp, pre->part, B, "st_skinny_linear_packed_attnpre_fwd")) return -1;
-            return pk_launch_attnpre<1>(a, tiles, t, (hipStream_t)stream, &pp);
+            return pk_launch_attnpre<1>(a, tiles, t, pk_attnpre_plan(B, tiles, n_at, pp.N, vec), (hipStream_t)stream, &pp);
         }
-        if (BT == 1 || tiles <= 128) return pk_launch_attnpre<1>(a, tiles, t, (hipStream_t)stream);
-        if (BT == 2) return pk_launch_attnpre<2>(a, tiles, t, (hipStream_t)stream);
-        if (BT == 3) return pk_launch_attnpre<3>(a, tiles, t, (hipStream_t)stream);
-        return pk_launch_attnpre<4>(a, tiles, t, (hipStream_t)stream);
+        const PkPlan pl = pk_attnpre_plan(B, tiles, n_at, 0, vec);
+        if (pl.nb == 1) return pk_launch_attnpre<1>(a, tiles, t, pl, (hipStream_t)stream);
+        if (pl.nb == 2) return pk_launch_attnpre<2>(a, tiles, t, pl, (hipStream_t)stream);
+        if (pl.nb == 3) return pk_launch_attnpre<3>(a, tiles, t, pl, (hipStream_t)stream);
+        return pk_launch_attnpre<4>(a, tiles, t, pl, (hipStream_t)stream);
     }
     return pk_dispatch<1>(a, tiles, (hipStream_t)stream);
 }
@@ -1481,6 +1512,37 @@ extern "C" int st_skinny_linear_packed_fwd(const st_packed_linear_job* job, void
 
 extern "C" int st_skinny_linear_packed_attnpre_fwd(const st_packed_linear_job* job, const st_attn_pre_job* pre, void* stream) {
     return pk_linear_impl(job, pre, stream);
+}
+
+// which launch(es) a forward product takes (host arithmetic only; the launchers above decide through the same functions)
+extern "C" int st_packed_fwd_variant(const st_packed_fwd_query* q, st_packed_fwd_launch* out) {
+    if (!q || !out || q->B <= 0 || q->n <= 0) return -1;
+    auto put = [](st_packed_fwd_launch& o, const PkPlan& p) { o.family = p.family; o.nb = p.nb; o.grid_x = p.gx; o.grid_y = p.gy; o.vec = p.vec; };
+    if (q->mode == ST_PK_MODE_CELL) {
+        if (q->n % 4 != 0 || q->pre_parts > 0 || q->part_n > 0) return -1;
+        put(out[0], pk_plan(0, q->B, q->n / 4));
+        return 1;
+    }
+    if (q->mode == ST_PK_MODE_CELL_PAIR) {
+        if (q->n % 4 != 0 || q->B1 <= 0 || q->n1 <= 0 || q->n1 % 4 != 0 || q->pre_parts > 0 || q->part_n > 0) return -1;
+        if (pk_pair_shape(q->B, q->n, q->B1, q->n1)) {
+            put(out[0], PkPlan{ST_PK_LSTM_RT2_PAIR, 1, q->n / 4 + q->n1 / 4, 1, 0});
+            return 1;
+        }
+        put(out[0], pk_plan(0, q->B, q->n / 4));
+        put(out[1], pk_plan(0, q->B1, q->n1 / 4));
+        return 2;
+    }
+    if (q->mode != ST_PK_MODE_LINEAR) return -1;
+    const int tiles = (q->n + 15) / 16;
+    if (q->pre_parts <= 0) {
+        if (q->part_n > 0) return -1;       // a partial product is hosted beside the attention-pre workgroups only
+        put(out[0], pk_plan(1, q->B, tiles));
+        return 1;
+    }
+    if (q->part_n > 0 && (tiles > 128 || q->B <= 16 || q->B > 32 || q->part_n % 32 != 0)) return -1;      // (pk_linear_impl, pk_part_job_fill)
+    put(out[0], pk_attnpre_plan(q->B, tiles, q->B * q->pre_parts, q->part_n > 0 ? q->part_n : 0, pk_attnpre_vec(q->pre_A, q->pre_F, q->pre_aligned != 0)));
+    return 1;
 }
 
 extern "C" int st_query_attn_fin_fwd(const float* packed_wq, const st_t16_view* h_q, int Q, unsigned long long* granules, unsigned epoch,

@@ -222,10 +222,17 @@ def attn_pre(pm, w_prev, w_cum_prev, loc_conv_w, loc_lin_w, s_buf=None, parts=1)
     F_, _, K = loc_conv_w.shape
     if s_buf is None:
         s_buf = torch.empty(B, L, A, device=pm.device, dtype=torch.float32)
-    job = _lib.StAttnPreJob(pm=_p(pm), w_prev=_p(w_prev), ld_wprev=int(w_prev.stride(0)), w_cum_prev=_p(w_cum_prev), loc_conv_w=_p(loc_conv_w),
-                            loc_lin_w=_p(loc_lin_w), s_buf=_p(s_buf), L=L, A=A, F=F_, K=K, parts=int(parts))
+    job = attn_pre_job(pm, w_prev, w_cum_prev, loc_conv_w, loc_lin_w, s_buf, parts)
     check(_lib.load().st_attn_pre_fwd(C.byref(job), B, stream_handle()), 'st_attn_pre_fwd')
     return s_buf
+
+
+def attn_pre_job(pm, w_prev, w_cum_prev, loc_conv_w, loc_lin_w, s_buf, parts=1):
+    """StAttnPreJob of one step (the arguments of attn_pre)"""
+    B, L, A = pm.shape
+    F_, _, K = loc_conv_w.shape
+    return _lib.StAttnPreJob(pm=_p(pm), w_prev=_p(w_prev), ld_wprev=int(w_prev.stride(0)), w_cum_prev=_p(w_cum_prev), loc_conv_w=_p(loc_conv_w),
+                             loc_lin_w=_p(loc_lin_w), s_buf=_p(s_buf), L=L, A=A, F=F_, K=K, parts=int(parts))
 
 
 def _fin_job(s_buf, memory, w_cum_prev, v, w_out, w_cum_out, parts, F_=0, K=0, ctx=None, ctx_t16=None, status=None):
@@ -1853,8 +1860,9 @@ def packed_product(packed_w, x_view, Kpad, y, ldy, B, N):
     return _lib.StPackedProduct(packed_w=_p(packed_w), x=x_view, K=int(Kpad), y=_p(y), ldy=int(ldy), B=int(B), N=int(N))
 
 
-def skinny_linear_packed(packed_w, x_view, Kpad, B, N, y=None, y_dst=None, bias=None, act=None, mask=None,
-                         n_split=0, y2=None, rep=0, n_split2=0, act2=None, mask2=None, y3_dst=None):
+def packed_linear_job(packed_w, x_view, Kpad, B, N, y=None, y_dst=None, bias=None, act=None, mask=None,
+                      n_split=0, y2=None, rep=0, n_split2=0, act2=None, mask2=None, y3_dst=None):
+    """StPackedLinearJob (the arguments of skinny_linear_packed)"""
     ld = lambda t: int(t.stride(0)) if t is not None else 0
     job = _lib.StPackedLinearJob(p=packed_product(packed_w, x_view, Kpad, y, ld(y), B, N), bias=_p(bias), act=ACT[act], mask=_p(mask), ldmask=ld(mask),
                                  n_split=int(n_split), y2=_p(y2), ldy2=ld(y2), rep=int(rep),
@@ -1863,7 +1871,20 @@ def skinny_linear_packed(packed_w, x_view, Kpad, B, N, y=None, y_dst=None, bias=
         job.y_dst = y_dst
     if y3_dst is not None:
         job.y3_dst = y3_dst
+    return job
+
+
+def skinny_linear_packed(packed_w, x_view, Kpad, B, N, **kw):
+    job = packed_linear_job(packed_w, x_view, Kpad, B, N, **kw)
     check(_lib.load().st_skinny_linear_packed_fwd(C.byref(job), stream_handle()), 'st_skinny_linear_packed_fwd')
+
+
+def skinny_linear_packed_attnpre(job, pre, part=None):
+    """the linear `job` (packed_linear_job) with the attention-pre job `pre` (attn_pre_job) as extra workgroups of the same launch and,
+    optionally, a hosted partial product `part` (StPartialProductJob) behind them: st_skinny_linear_packed_attnpre_fwd"""
+    if part is not None:
+        pre.part = C.addressof(part)
+    check(_lib.load().st_skinny_linear_packed_attnpre_fwd(C.byref(job), C.byref(pre), stream_handle()), 'st_skinny_linear_packed_attnpre_fwd')
 
 
 # --------------------------------------------------------------------------------------------- graphs
