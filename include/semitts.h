@@ -1244,15 +1244,24 @@ int st_mt_clip_scale_pre(float* const* g, const long* n, int nt, const float* no
 /* dst_t[i] = src_t[i] for nt tensors in a handful of launches (gradients that autograd allocated elsewhere are gathered into their
  * all-reduce bucket by one call per bucket) */
 int st_mt_copy(float* const* dst, float* const* src, const long* n, int nt, void* stream);
+/* Host arithmetic only (like st_gemm_fwd_variant / st_packed_fwd_variant: no device, nothing behind the sizes is touched): the launches
+ * the KERNEL-ARGUMENT form makes for a size list -- the form taken during a stream capture, when no device-side table can be made.
+ * kind 0: the optimiser passes (norm, clip, Adam: 24 tensor slots, 640 blocks of 32768 floats per launch); kind 1: st_mt_copy (96 slots,
+ * 512 blocks of 4096 floats).  Returns the number of launches and writes blocks[i] / tensors[i] (blocks and tensor slots of launch i; a
+ * tensor cut across launches takes a slot in each) for the first `cap` of them; 0 for a list of empty tensors; negative for a refusal
+ * (bad arguments, or a tensor too long for the 16-bit chunk index).  The launchers run the same splitting code. */
+int st_mt_launch_plan(const long* n, int nt, int kind, int* blocks, int* tensors, int cap);
 /* torch.optim.Adam (no weight decay, no amsgrad): m = m + (g-m)(1-b1); v = b2 v + (1-b2) g^2;
- * p -= step_size * m / (sqrt(v)/bias_correction2_sqrt + eps), step_size = lr / (1 - b1^t) */
+ * p -= step_size * m / (sqrt(v)/bias_correction2_sqrt + eps), step_size = lr / (1 - b1^t).  The betas travel as doubles: the kernel
+ * multiplies by (float)b2 and by (float)(1.0 - b), each rounded once from the double as torch's Adam rounds them (1.0f - (float)0.999
+ * would be 0.00099998713, 1.3e-5 away from the 0.001 on g^2) */
 int st_mt_adam(float* const* p, float* const* g, float* const* m, float* const* v, const long* n, int nt,
-               float beta1, float beta2, float eps, float step_size, float bias_correction2_sqrt, void* stream);
+               double beta1, double beta2, float eps, float step_size, float bias_correction2_sqrt, void* stream);
 /* st_mt_adam that leaves parameters and moments untouched when *guard_norm (a device scalar: the gradient norm st_mt_grad_norm wrote)
  * is NaN or inf -- BaseSolver.backward's `if math.isnan(grad_norm): ... else: self.optimizer.step()` (src/solver.py:147-150) decided
  * on the device, so a training loop need not wait for the norm on the host every step.  guard_norm NULL = st_mt_adam. */
 int st_mt_adam_guarded(float* const* p, float* const* g, float* const* m, float* const* v, const long* n, int nt,
-                       float beta1, float beta2, float eps, float step_size, float bias_correction2_sqrt,
+                       double beta1, double beta2, float eps, float step_size, float bias_correction2_sqrt,
                        const float* guard_norm, void* stream);
 
 /* ------------------------------------------------------------------ small utilities */

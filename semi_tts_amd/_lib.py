@@ -359,8 +359,9 @@ SIGNATURES = {
     'st_mt_grad_norm_scaled': [P, P, I, P, P, F, P],
     'st_mt_clip_scale_pre': [P, P, I, P, F, F, P],
     'st_mt_copy': [P, P, P, I, P],
-    'st_mt_adam': [P, P, P, P, P, I, F, F, F, F, F, P],
-    'st_mt_adam_guarded': [P, P, P, P, P, I, F, F, F, F, F, P, P],
+    'st_mt_launch_plan': [P, I, I, C.POINTER(I), C.POINTER(I), I],
+    'st_mt_adam': [P, P, P, P, P, I, C.c_double, C.c_double, F, F, F, P],
+    'st_mt_adam_guarded': [P, P, P, P, P, I, C.c_double, C.c_double, F, F, F, P, P],
     'st_freq_loss': [P, P, P, P, P, I, I, I, I, F, F, F, I, P],
     'st_freq_loss_workspace_floats': [],
     'st_scale_by': [P, P, P, Z, P],

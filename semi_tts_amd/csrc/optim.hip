@@ -15,7 +15,7 @@ struct MtOp {
     float* partial; int partial_base;            // sumsq
     const float* norm; float max_norm;           // scale
     float pre_scale;                             // scale: every gradient is first multiplied by this (1 / world: the ranks' SUM -> average)
-    float b1, b2, eps, step_size, bc2_sqrt;      // adam
+    float omb1, b2, omb2, eps, step_size, bc2_sqrt;      // adam (omb = 1 - beta, rounded ONCE from the host's double: torch's scalars)
 };
 struct MtArgs {
     float* p[MT_T]; float* g[MT_T]; float* m[MT_T]; float* v[MT_T];
@@ -41,26 +41,34 @@ __device__ __forceinline__ void mt_body(float* __restrict__ tp, float* __restric
     if (OP == 0) {
         float acc = 0.0f, acc2 = 0.0f;
         const f32x4* g4 = reinterpret_cast<const f32x4*>(g + beg);
-        long i = threadIdx.x;
-        // (eight pieces in flight per thread; the two running sums keep the pairing of the two-piece form: pieces 0, 2, 4, 6 of a round
-        // go to acc, 1, 3, 5, 7 to acc2 -- the same additions in the same order as four two-piece rounds)
-        for (; i + 7 * MT_THREADS < nvec; i += 8 * MT_THREADS) {
-            f32x4 x[8];
+        // A sum depends on its order, so the unaligned tensor takes the SAME four-float pieces, in the same rounds, into the same two
+        // running sums, only loaded float by float: a gradient gives the same norm bit for bit at any address (the element-wise
+        // passes below do by construction; here a thread-strided scalar loop of its own added in another order)
+        const long npc = (end - beg) >> 2;
+        auto sum_pieces = [&](auto piece) {
+            long i = threadIdx.x;
+            // (eight pieces in flight per thread; the two running sums keep the pairing of the two-piece form: pieces 0, 2, 4, 6 of a round
+            // go to acc, 1, 3, 5, 7 to acc2 -- the same additions in the same order as four two-piece rounds)
+            for (; i + 7 * MT_THREADS < npc; i += 8 * MT_THREADS) {
+                f32x4 x[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = g4[i + u * MT_THREADS];
+                for (int u = 0; u < 8; ++u) x[u] = piece(i + u * MT_THREADS);
 #pragma unroll
-            for (int u = 0; u < 8; u += 2) {
-                acc = fmaf(x[u][0], x[u][0], acc); acc = fmaf(x[u][1], x[u][1], acc); acc = fmaf(x[u][2], x[u][2], acc); acc = fmaf(x[u][3], x[u][3], acc);
-                acc2 = fmaf(x[u + 1][0], x[u + 1][0], acc2); acc2 = fmaf(x[u + 1][1], x[u + 1][1], acc2); acc2 = fmaf(x[u + 1][2], x[u + 1][2], acc2); acc2 = fmaf(x[u + 1][3], x[u + 1][3], acc2);
+                for (int u = 0; u < 8; u += 2) {
+                    acc = fmaf(x[u][0], x[u][0], acc); acc = fmaf(x[u][1], x[u][1], acc); acc = fmaf(x[u][2], x[u][2], acc); acc = fmaf(x[u][3], x[u][3], acc);
+                    acc2 = fmaf(x[u + 1][0], x[u + 1][0], acc2); acc2 = fmaf(x[u + 1][1], x[u + 1][1], acc2); acc2 = fmaf(x[u + 1][2], x[u + 1][2], acc2); acc2 = fmaf(x[u + 1][3], x[u + 1][3], acc2);
+                }
             }
-        }
-        for (; i + MT_THREADS < nvec; i += 2 * MT_THREADS) {
-            const f32x4 x = g4[i], y = g4[i + MT_THREADS];
-            acc = fmaf(x[0], x[0], acc); acc = fmaf(x[1], x[1], acc); acc = fmaf(x[2], x[2], acc); acc = fmaf(x[3], x[3], acc);
-            acc2 = fmaf(y[0], y[0], acc2); acc2 = fmaf(y[1], y[1], acc2); acc2 = fmaf(y[2], y[2], acc2); acc2 = fmaf(y[3], y[3], acc2);
-        }
-        for (; i < nvec; i += MT_THREADS) { const f32x4 x = g4[i]; acc = fmaf(x[0], x[0], acc); acc = fmaf(x[1], x[1], acc); acc = fmaf(x[2], x[2], acc); acc = fmaf(x[3], x[3], acc); }
-        for (long j = beg + nvec * 4 + threadIdx.x; j < end; j += MT_THREADS) { const float x = g[j]; acc = fmaf(x, x, acc); }
+            for (; i + MT_THREADS < npc; i += 2 * MT_THREADS) {
+                const f32x4 x = piece(i), y = piece(i + MT_THREADS);
+                acc = fmaf(x[0], x[0], acc); acc = fmaf(x[1], x[1], acc); acc = fmaf(x[2], x[2], acc); acc = fmaf(x[3], x[3], acc);
+                acc2 = fmaf(y[0], y[0], acc2); acc2 = fmaf(y[1], y[1], acc2); acc2 = fmaf(y[2], y[2], acc2); acc2 = fmaf(y[3], y[3], acc2);
+            }
+            for (; i < npc; i += MT_THREADS) { const f32x4 x = piece(i); acc = fmaf(x[0], x[0], acc); acc = fmaf(x[1], x[1], acc); acc = fmaf(x[2], x[2], acc); acc = fmaf(x[3], x[3], acc); }
+        };
+        if (vec) sum_pieces([&](long i) { return g4[i]; });
+        else sum_pieces([&](long i) { const float* q = g + beg + 4 * i; f32x4 x; x[0] = q[0]; x[1] = q[1]; x[2] = q[2]; x[3] = q[3]; return x; });
+        for (long j = beg + npc * 4 + threadIdx.x; j < end; j += MT_THREADS) { const float x = g[j]; acc = fmaf(x, x, acc); }
         acc = st_wave_sum(acc + acc2);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
         __syncthreads();
@@ -84,7 +92,8 @@ __device__ __forceinline__ void mt_body(float* __restrict__ tp, float* __restric
         // reference takes on the host (`if math.isnan(grad_norm)`: skip optimizer.step(), src/solver.py:147-150) without a host round trip
         if (a.norm && !(fabsf(*a.norm) <= 3.0e38f)) return;
         float* __restrict__ p = tp; float* __restrict__ m = tm; float* __restrict__ v = tv;
-        const float omb1 = 1.0f - a.b1, omb2 = 1.0f - a.b2;
+        // (1 - beta comes from the host: 1.0f - (float)0.999 is 0.00099998713, 1.3e-5 away from the 0.001 torch's Adam multiplies g^2 by)
+        const float omb1 = a.omb1, omb2 = a.omb2;
         // no contraction left to the compiler (the fused multiply-adds are the explicit ones): the 16-byte loop and the scalar loop
         // (unaligned tensors, tails) must round alike -- a gradient that lives in an all-reduce bucket slot and one in a tensor of
         // its own then give the same weights bit for bit (r04: the two loops were contracted differently; invisible in a one-step test)
@@ -283,6 +292,35 @@ static const MtTabEntry* mt_table(float* const* p, float* const* g, float* const
     return hit;
 }
 
+// ---- the kernel-argument form: a tensor list cut into launches ---------------------------------------------------------------------
+// A launch takes up to T tensor slots and NB blocks of `chunk` floats.  Tensors are taken in list order (empty ones skipped), chunks in
+// order; a launch is closed when either limit is reached, and a tensor whose chunks do not fit is registered again at the next launch's
+// next free slot with its remaining chunks.  reg(slot, t): tensor t of the list takes slot `slot` of the current launch; blk(b, slot, c):
+// block b of the launch works on chunk c of that slot; flush(slots, blocks) issues the launch (non-zero: stop and return it).
+// The ONE statement of the rule: mt_run, st_mt_copy and st_mt_launch_plan all go through it.
+template <class Reg, class Blk, class Flush>
+static int mt_split(const long* n, int nt, int T, int NB, int chunk, Reg reg, Blk blk, Flush flush) {
+    int ti = 0, bl = 0;
+    for (int t = 0; t < nt; ++t) {
+        if (n[t] <= 0) continue;
+        const int chunks = (int)((n[t] + chunk - 1) / chunk);
+        int c = 0;
+        while (c < chunks) {
+            if (ti == T || bl == NB) { int rc = flush(ti, bl); if (rc) return rc; ti = 0; bl = 0; }
+            reg(ti, t);
+            while (c < chunks && bl < NB) { blk(bl, ti, c); ++bl; ++c; }
+            ++ti;
+        }
+    }
+    return bl ? flush(ti, bl) : 0;
+}
+
+// the first tensor with more than n_max elements (its chunk index would not fit the 16 bits of the block map), or -1
+static int mt_split_refused(const long* n, int nt, long n_max) {
+    for (int t = 0; t < nt; ++t) if (n[t] > n_max) return t;
+    return -1;
+}
+
 template <int OP>
 int mt_run(MtArgs& a, float* const* p, float* const* g, float* const* m, float* const* v, const long* n, int nt, hipStream_t st,
            int* blocks_total) {
@@ -297,29 +335,19 @@ int mt_run(MtArgs& a, float* const* p, float* const* g, float* const* m, float* 
             return 0;
         }
     }
-    int ti = 0, bl = 0, base = 0;
-    auto flush = [&]() -> int {
-        if (bl == 0) { ti = 0; return 0; }
-        a.op.partial_base = base;
-        hipLaunchKernelGGL((mt_kernel<OP>), dim3(bl), dim3(MT_THREADS), 0, st, a);
-        ST_LAUNCH_CHECK();
-        base += bl; ti = 0; bl = 0;
-        return 0;
-    };
-    for (int t = 0; t < nt; ++t) {
-        if (n[t] <= 0) continue;
-        const int chunks = (int)((n[t] + MT_CHUNK - 1) / MT_CHUNK);
-        ST_CHECK_ARG(chunks <= 65535, "multi-tensor op: tensor %d has %ld elements (> 2^31)", t, n[t]);
-        int c = 0;
-        while (c < chunks) {
-            if (ti == MT_T || bl == MT_NB) { int rc = flush(); if (rc) return rc; }
-            // (re)register this tensor in the current launch
-            a.p[ti] = p ? p[t] : nullptr; a.g[ti] = g[t]; a.m[ti] = m ? m[t] : nullptr; a.v[ti] = v ? v[t] : nullptr; a.n[ti] = n[t];
-            while (c < chunks && bl < MT_NB) { a.blk_tensor[bl] = (unsigned char)ti; a.blk_chunk[bl] = (unsigned short)c; ++bl; ++c; }
-            ++ti;
-        }
-    }
-    int rc = flush();
+    const int bad = mt_split_refused(n, nt, (long)65535 * MT_CHUNK);
+    ST_CHECK_ARG(bad < 0, "multi-tensor op: tensor %d has %ld elements (> 2^31)", bad, n[bad]);
+    int base = 0;
+    int rc = mt_split(n, nt, MT_T, MT_NB, MT_CHUNK,
+        [&](int ti, int t) { a.p[ti] = p ? p[t] : nullptr; a.g[ti] = g[t]; a.m[ti] = m ? m[t] : nullptr; a.v[ti] = v ? v[t] : nullptr; a.n[ti] = n[t]; },
+        [&](int bl, int ti, int c) { a.blk_tensor[bl] = (unsigned char)ti; a.blk_chunk[bl] = (unsigned short)c; },
+        [&](int, int bl) -> int {
+            a.op.partial_base = base;
+            hipLaunchKernelGGL((mt_kernel<OP>), dim3(bl), dim3(MT_THREADS), 0, st, a);
+            ST_LAUNCH_CHECK();
+            base += bl;
+            return 0;
+        });
     if (rc) return rc;
     if (blocks_total) *blocks_total = base;
     return 0;
@@ -371,41 +399,47 @@ extern "C" int st_mt_copy(float* const* dst, float* const* src, const long* n, i
     (void)hipGetLastError();
     ST_CHECK_ARG(dst && src && n && nt > 0, "st_mt_copy: bad arguments");
     McArgs a;
-    int ti = 0, bl = 0;
-    auto flush = [&]() -> int {
-        if (bl == 0) { ti = 0; return 0; }
-        hipLaunchKernelGGL(mc_kernel, dim3(bl), dim3(MT_THREADS), 0, (hipStream_t)stream, a);
-        ST_LAUNCH_CHECK();
-        ti = 0; bl = 0;
-        return 0;
-    };
-    for (int t = 0; t < nt; ++t) {
-        if (n[t] <= 0) continue;
-        ST_CHECK_ARG(n[t] < (long)65535 * MC_CHUNK, "st_mt_copy: tensor %d has %ld elements", t, n[t]);
-        const int chunks = (int)((n[t] + MC_CHUNK - 1) / MC_CHUNK);
-        int c = 0;
-        while (c < chunks) {
-            if (ti == MC_T || bl == MC_NB) { int rc = flush(); if (rc) return rc; }
-            a.dst[ti] = dst[t]; a.src[ti] = src[t]; a.n[ti] = (int)n[t];
-            while (c < chunks && bl < MC_NB) { a.blk_tensor[bl] = (unsigned char)ti; a.blk_chunk[bl] = (unsigned short)c; ++bl; ++c; }
-            ++ti;
-        }
-    }
-    return flush();
+    const int bad = mt_split_refused(n, nt, (long)65535 * MC_CHUNK - 1);
+    ST_CHECK_ARG(bad < 0, "st_mt_copy: tensor %d has %ld elements", bad, n[bad]);
+    return mt_split(n, nt, MC_T, MC_NB, MC_CHUNK,
+        [&](int ti, int t) { a.dst[ti] = dst[t]; a.src[ti] = src[t]; a.n[ti] = (int)n[t]; },
+        [&](int bl, int ti, int c) { a.blk_tensor[bl] = (unsigned char)ti; a.blk_chunk[bl] = (unsigned short)c; },
+        [&](int, int bl) -> int {
+            hipLaunchKernelGGL(mc_kernel, dim3(bl), dim3(MT_THREADS), 0, (hipStream_t)stream, a);
+            ST_LAUNCH_CHECK();
+            return 0;
+        });
+}
+
+// Host arithmetic only (no device, no memory behind the sizes is touched): the launches the kernel-argument form makes for a size list,
+// from the splitting code the launchers themselves run.  kind 0: the optimiser passes (norm, clip, Adam); kind 1: st_mt_copy.
+extern "C" int st_mt_launch_plan(const long* n, int nt, int kind, int* blocks, int* tensors, int cap) {
+    ST_CHECK_ARG(n && nt > 0 && (kind == 0 || kind == 1) && cap >= 0 && (cap == 0 || (blocks && tensors)), "st_mt_launch_plan: bad arguments");
+    const int T = kind ? MC_T : MT_T, NB = kind ? MC_NB : MT_NB, chunk = kind ? MC_CHUNK : MT_CHUNK;
+    const int bad = mt_split_refused(n, nt, kind ? (long)65535 * MC_CHUNK - 1 : (long)65535 * MT_CHUNK);
+    ST_CHECK_ARG(bad < 0, "st_mt_launch_plan: tensor %d has %ld elements", bad, n[bad]);
+    int launches = 0;
+    (void)mt_split(n, nt, T, NB, chunk, [](int, int) {}, [](int, int, int) {},
+        [&](int ti, int bl) -> int {
+            if (launches < cap) { blocks[launches] = bl; tensors[launches] = ti; }
+            ++launches;
+            return 0;
+        });
+    return launches;
 }
 extern "C" int st_mt_adam_guarded(float* const* p, float* const* g, float* const* m, float* const* v, const long* n, int nt,
-                                  float beta1, float beta2, float eps, float step_size, float bias_correction2_sqrt,
+                                  double beta1, double beta2, float eps, float step_size, float bias_correction2_sqrt,
                                   const float* guard_norm, void* stream) {
     (void)hipGetLastError();
     ST_CHECK_ARG(p && g && m && v && n && nt > 0 && bias_correction2_sqrt > 0.0f, "st_mt_adam: bad arguments");
     MtArgs a;
     memset(&a, 0, sizeof(a));
-    a.op.b1 = beta1; a.op.b2 = beta2; a.op.eps = eps; a.op.step_size = step_size; a.op.bc2_sqrt = bias_correction2_sqrt;
+    a.op.omb1 = (float)(1.0 - beta1); a.op.b2 = (float)beta2; a.op.omb2 = (float)(1.0 - beta2); a.op.eps = eps; a.op.step_size = step_size; a.op.bc2_sqrt = bias_correction2_sqrt;
     a.op.norm = guard_norm;
     return mt_run<2>(a, p, g, m, v, n, nt, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int st_mt_adam(float* const* p, float* const* g, float* const* m, float* const* v, const long* n, int nt,
-                          float beta1, float beta2, float eps, float step_size, float bias_correction2_sqrt, void* stream) {
+                          double beta1, double beta2, float eps, float step_size, float bias_correction2_sqrt, void* stream) {
     return st_mt_adam_guarded(p, g, m, v, n, nt, beta1, beta2, eps, step_size, bias_correction2_sqrt, nullptr, stream);
 }

@@ -156,12 +156,22 @@ class FusedAdam(torch.optim.Optimizer):
                 buckets.setdefault(st['_step'], []).append(p)
             for step, plist in buckets.items():        # parameters share one step count unless some were frozen for a while
                 key = (gi, tuple(id(p) for p in plist))
-                if key not in cache:                   # pointer tables of parameters and moments are stable across steps
+                # pointer tables of parameters and moments are stable across steps -- as long as the parameters keep their storage:
+                # `p.data = ...` (embed.py loading a pretrained table) or module.to() moves one, and a table made before that would
+                # send the update to the old, possibly freed, address.  The entry remembers the addresses it was made for (the moments
+                # are this object's own; load_state_dict, the only place that replaces them, drops the cache)
+                ptrs = [p.data_ptr() for p in plist]
+                hit = cache.get(key)
+                if hit is None or hit[4] != ptrs:
+                    for p in plist:                    # (a replaced storage is held to what the first step checked)
+                        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+                                and p.numel() == self.state[p]['exp_avg'].numel()):
+                            raise RuntimeError('FusedAdam: parameters must stay contiguous fp32 device tensors of their size')
                     pp, sizes = _tables(plist)
                     mp, _ = _tables([self.state[p]['exp_avg'] for p in plist])
                     vp, _ = _tables([self.state[p]['exp_avg_sq'] for p in plist])
-                    cache[key] = (pp, mp, vp, sizes)
-                pp, mp, vp, sizes = cache[key]
+                    hit = cache[key] = (pp, mp, vp, sizes, ptrs)
+                pp, mp, vp, sizes = hit[:4]
                 grads = [p.grad for p in plist]
                 if not all(g.is_contiguous() and g.dtype == torch.float32 for g in grads):
                     raise RuntimeError('FusedAdam: gradients must be contiguous fp32 tensors')
