@@ -1042,6 +1042,24 @@ size_t st_ctc_workspace_floats(int B, int T);
 int st_ctc_loss(const float* prob, const int64_t* text, float eps, float* loss, float* dprob, float* ws,
                 int B, int T, int V, int L, int log_input, void* stream);
 
+/* st_ctc_loss with per-utterance frame counts (paras.actual_len = True, bin/train_vqvae.py:436-444): in_len (B) int32 on the device, or
+ * NULL (= st_ctc_loss, bit for bit).  Utterance b uses the frames t < T_b = clamp(in_len[b], 0, T): alpha runs to T_b - 1, beta starts there,
+ * the nll is read there.  Every gradient row t >= T_b is written as exact +0, for an infeasible utterance too (torch.nn.CTCLoss); an
+ * infeasible utterance gives +inf and NaN rows for t < T_b.  T_b = 0: +inf when the utterance has tokens, 0 when it has none, all rows 0.
+ * Targets stay "the non-zero tokens in order".  With actual_len the reference passes the padded 2-D targets and takes the first S_b of each
+ * row; the two agree when a row's zeros are all at its end, which is how the corpus loader pads. */
+int st_ctc_loss_len(const float* prob, const int64_t* text, const int32_t* in_len, float eps, float* loss, float* dprob, float* ws,
+                    int B, int T, int V, int L, int log_input, void* stream);
+
+/* The frame counts st_ctc_loss_len takes, computed on the device in one launch (no host read).
+ * x != NULL (compute_ctcloss, bin/train_vqvae.py:437-438): x (B, T, D) fp32,
+ *   out[b] = (number of frames t whose D values are not all == pad_value) / div     -- such frames anywhere, not only trailing ones.
+ * x == NULL (the text-first branch, bin/train_vqvae.py:238-240): text (B, L) int64,
+ *   len6 = 6 * (number of non-zero tokens of row b);  out[b] = 1 + (len6 + len6 % r) / div.
+ * out (B) int32.  div >= 1, r >= 1. */
+int st_frame_lengths(const float* x, int B, int T, int D, float pad_value, const int64_t* text, int L, int r, int div, int32_t* out,
+                     void* stream);
+
 /* greedy CTC transcript and its edit distance to the reference transcript (ref: src/util.py:169-181, cal_per -- which copies the argmax to
  * the host and runs a Python loop and editdistance.eval per utterance).  Per utterance b of prob (B, T, V), text (B, L) int64:
  *   p[t] = argmax_v prob[b, t, v] over all T frames (ties: the first maximal index; a NaN is the maximum, the first NaN wins: torch.argmax);

@@ -4,7 +4,7 @@ The dispatch is the reference's (main.py:49-63): `--gen-specgram` runs batched f
 (bin/gen_specgram.py), the default mode runs `VqvaeTrainer` -- the alternating speech -> text -> speech /
 text -> speech -> text cycles of bin/train_vqvae.py:111-270 (CTC speech encoder, codebook, run-length merge,
 TTS branch, CTC + freq losses, backward, clip + Adam, all on the HIP kernels) -- on synthetic paired and
-unpaired batches (the corpus is not available).  `--tts-only` keeps the paired TTS step alone (TtsTrainer).
+unpaired batches, or with `--corpus` on the files `data.corpus` names.  `--tts-only` keeps the paired TTS step alone (TtsTrainer).
 `--dev-batches K` adds the reference's validation (bin/train_vqvae.py:313-314,330-428) on K synthetic dev batches: at step 1
 and every `--valid-step` (hparas.valid_step) steps it logs `Dv stat` (dev TTS loss, PER, post PER) and writes tts_<step>.pth /
 asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-per, best_per.pth / best_post_per.pth -- under
@@ -12,6 +12,8 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
 
     python main.py --config config/semi-single-spkr-paired-data.yaml --max-step 20 [--frames 256 --batch-size 8]
     python main.py --config config/semi-single-spkr-paired-data.yaml --max-step 20000 --dev-batches 4 [--valid-step 5000] [--store-best-per]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --corpus --max-step 20000 --dev-batches -1 [--actual-len --max-frames 800]
+    python main.py --config config/supervised.yaml --tts-only --corpus --max-step 20000 [--corpus-max-gb 8 --resample]
     python main.py --config config/supervised.yaml --gen-specgram [--load ckpt.pth] [--frames 256 --batch-size 32]
     python main.py --config config/supervised.yaml --tts-only --max-step 20 [--frames 256 --batch-size 32]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR [--beam-width 16 --top-paths 1 --vocab FILE]
@@ -25,6 +27,11 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --feat-wav-dir DIR --feat f0 [--f0-min 60 --f0-max 500 --f0-threshold 0.15]
     python main.py --config config/supervised.yaml --mcd-wav-dir SYN --mcd-ref-dir REF [--mcd-path --mcd-f0 --batch-size 32]
     python main.py --config config/supervised.yaml --synth-phn-dir DIR [--load ckpt.pth --vocab FILE --synth-sid 0 --gen-wav --batch-size 8]
+`--corpus` trains on the reference's corpus layout (semi_tts_amd/corpus.py: partition table, map table, speaker map, vocabulary file and
+<path>/<speaker>/<id>.wav, src/data.py + corpus/vctk.py + src/text.py): each split of the rank's shard is read once and stays on the device as
+one packed buffer, every fetch extracts mel / augmented mel / linear from it on the GPU, `--dev-batches K` (-1: all) validates on the real dev
+split, vocab_size and n_spkr come from the files.  `--actual-len` gives the CTC terms the frame counts of each utterance (computed on the
+device) instead of the padded length, as bin/train_vqvae.py:436-444 and :237-240.
 `--transcribe-wav-dir` (not a mode of the reference) transcribes .wav files by CTC prefix beam search (solver.Transcriber); with
 `--lm FILE` a phone n-gram table weights the search inside the kernel.  `--build-lm-phn-dir` counts such a table from .phn transcripts
 (semi_tts_amd/ngram.py: a plain .npy of shape (V^(order-1), V) in the layout of the reference's NgramPrior, src/lm.py:233-290) on the host.
@@ -73,7 +80,7 @@ parser.add_argument('--asr-decode', action='store_true', help='ASR beam decode (
 parser.add_argument('--gen-specgram', action='store_true', help='Generating mel/linear spectrogram.')
 parser.add_argument('--gen-gt-specgram', action='store_true', help='(the reference dispatches to bin/gen_gt_specgram.py, which its tree lacks)')
 parser.add_argument('--no-msg', action='store_true', help='Hide all messages.')
-parser.add_argument('--actual-len', action='store_true', help='Using actual len for CTC loss. (synthetic inputs are full length: no effect)')
+parser.add_argument('--actual-len', action='store_true', help='Using actual len for CTC loss: frames of each utterance that are not padding, counted on the device.')
 parser.add_argument('--store-best-per', action='store_true', help='Only store the model with best PER. (with --dev-batches; without a dev set: no effect)')
 parser.add_argument('--asr-only', action='store_true', help='(the reference dispatches to bin/train_asr.py, which its tree lacks)')
 parser.add_argument('--gen-wav', action='store_true', help='Generate waveform using Griffin-Lim. (--gen-specgram: writes <name>-pred.wav)')
@@ -86,12 +93,19 @@ parser.add_argument('--unpair-frames', default=None, type=int, help='mel frames 
 parser.add_argument('--unpair-wav-dir', default=None, type=str, help='unpaired batches: (mel, aug_mel, linear) extracted on the GPU from the '
                     '.wav files of this directory, sorted by name, batched by --unpair-batch-size, fresh augmentation every fetch '
                     '(text / sid stay synthetic)')
+parser.add_argument('--corpus', action='store_true', help='train on the files data.corpus names (partition_table, map_table, spkr_map, vocab_file, '
+                    '<path>/<speaker>/<id>.wav) instead of synthetic batches: the paired / unpaired / dev splits stay on the device as packed '
+                    'waveforms, features are extracted on every fetch; vocab_size and n_spkr come from the files')
+parser.add_argument('--corpus-max-gb', default=None, type=float, help='--corpus: the most device memory one split may take, in GB (default: half '
+                    'of the free device memory when the split is loaded)')
+parser.add_argument('--max-frames', default=None, type=int, help='--corpus: drop utterances of more mel frames than this (default: keep all)')
 parser.add_argument('--stretch', action='store_true', help='aug_mel lengths drawn from data.audio.time_stretch_range (default: unstretched)')
 parser.add_argument('--tts-only', action='store_true', help='train the paired TTS branch alone (TtsTrainer) instead of the two cycles')
 parser.add_argument('--max-step', default=None, type=int, help='training steps (default: hparas.max_step)')
 parser.add_argument('--save', action='store_true', help='write ckpt/<name>/latest.pth ({model, optimizer, global_step}) after training')
 parser.add_argument('--dev-batches', default=0, type=int, help='validate on K synthetic dev batches (paired shapes) at step 1 and every '
-                    'valid step: dev TTS loss, PER, post PER, checkpoints by the reference\'s rules (default 0: no validation)')
+                    'valid step: dev TTS loss, PER, post PER, checkpoints by the reference\'s rules (default 0: no validation); with --corpus '
+                    'the first K batches of the dev split, -1: the whole split')
 parser.add_argument('--valid-step', default=None, type=int, help='steps between validations (default: hparas.valid_step)')
 parser.add_argument('--transcribe-wav-dir', default=None, type=str, help='transcribe the .wav files of this directory (sorted by name, '
                     'batched by --batch-size) by CTC prefix beam search into <logdir>/<name>/<file>.phn: --top-paths lines of score<TAB>tokens')
@@ -167,7 +181,7 @@ parser.add_argument('--async-stats', action='store_true', help='training: no hos
 # Flags of the reference (main.py:23-33) with nothing to do on this path (--gen-wav outside --gen-specgram), and those whose solver files are
 # absent from the reference tree itself (main.py:49-60 import bin/asr_decode.py, bin/gen_gt_specgram.py,
 # bin/train_asr.py, none of which exist): accepted by the parser so that existing launch lines keep working.
-IGNORED_FLAGS = ('debug', 'no_pin', 'actual_len', 'store_best_per', 'gen_wav')
+IGNORED_FLAGS = ('debug', 'no_pin', 'store_best_per', 'gen_wav')
 MISSING_SOLVERS = {'asr_decode': 'bin/asr_decode.py', 'gen_gt_specgram': 'bin/gen_gt_specgram.py',
                    'asr_only': 'bin/train_asr.py'}
 
@@ -186,9 +200,23 @@ def parse_args(argv=None):
     if paras.unpair_wav_dir is not None and (paras.tts_only or paras.gen_specgram):
         parser.error('--unpair-wav-dir feeds the unpaired batches of the two cycles; it does not combine with --%s'
                      % ('tts-only' if paras.tts_only else 'gen-specgram'))
-    if paras.dev_batches < 0 or (paras.valid_step is not None and paras.valid_step < 1):
-        parser.error('--dev-batches must be >= 0 and --valid-step >= 1')
-    if paras.dev_batches > 0 and (paras.tts_only or paras.gen_specgram):
+    if paras.corpus:
+        for flag in ('unpair_wav_dir', 'gen_specgram', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir', 'resample_wav_dir',
+                     'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir'):
+            if getattr(paras, flag):
+                parser.error('--corpus trains on the splits of data.corpus (the unpaired one included); it does not combine with --%s'
+                             % flag.replace('_', '-'))
+        if paras.config is None:
+            parser.error('--corpus needs --config (its data.corpus and data.audio)')
+        if paras.corpus_max_gb is not None and not 0.0 < paras.corpus_max_gb < float('inf'):
+            parser.error('--corpus-max-gb must be finite and positive')
+        if paras.max_frames is not None and paras.max_frames < 1:
+            parser.error('--max-frames must be >= 1')
+    elif paras.corpus_max_gb is not None or paras.max_frames is not None:
+        parser.error('--corpus-max-gb and --max-frames belong to --corpus; they need that flag')
+    if paras.dev_batches < (-1 if paras.corpus else 0) or (paras.valid_step is not None and paras.valid_step < 1):
+        parser.error('--dev-batches must be >= 0 (with --corpus: -1 walks the whole dev split) and --valid-step >= 1')
+    if paras.dev_batches != 0 and (paras.tts_only or paras.gen_specgram):
         parser.error('--dev-batches validates the two cycles (VqvaeTrainer); it does not combine with --%s'
                      % ('tts-only' if paras.tts_only else 'gen-specgram'))
     if paras.transcribe_wav_dir is not None:
@@ -217,8 +245,9 @@ def parse_args(argv=None):
         parser.error('--vocode-feat names the files --vocode-dir reads; it needs that flag')
     if paras.vocode_feat is None:
         paras.vocode_feat = 'spec'
-    if paras.resample and paras.unpair_wav_dir is None and paras.transcribe_wav_dir is None and paras.align_wav_dir is None:
-        parser.error('--resample converts the files of --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir; it needs one of them')
+    if paras.resample and paras.unpair_wav_dir is None and paras.transcribe_wav_dir is None and paras.align_wav_dir is None and not paras.corpus:
+        parser.error('--resample converts the files of --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir, or the splits of --corpus; it needs one '
+                     'of them')
     if paras.resample_wav_dir is not None:
         for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir'):
             if getattr(paras, flag):
@@ -335,7 +364,7 @@ def parse_args(argv=None):
         for flag in IGNORED_FLAGS:
             if flag == 'gen_wav' and (paras.gen_specgram or paras.synth_phn_dir is not None):
                 continue             # read by gen_specgram (bin/gen_specgram.py:114-126), as in the reference, and by --synth-phn-dir
-            if flag == 'store_best_per' and paras.dev_batches > 0:
+            if flag == 'store_best_per' and paras.dev_batches != 0:
                 continue             # read by VqvaeTrainer.validate (bin/train_vqvae.py:376-382)
             if getattr(paras, flag):
                 print('[INFO] --%s accepted for compatibility; it has no effect on this path' % flag.replace('_', '-'))

@@ -268,6 +268,8 @@ SIGNATURES = {
     'st_vq_l2_workspace_floats': [I, I],
     'st_ctc_workspace_floats': [I, I],
     'st_ctc_loss': [P, P, C.c_float, P, P, P, I, I, I, I, I, P],
+    'st_ctc_loss_len': [P, P, P, C.c_float, P, P, P, I, I, I, I, I, P],
+    'st_frame_lengths': [P, I, I, I, C.c_float, P, I, I, I, P, P],
     'st_ctc_greedy_edit_distance': [P, I, I, I, P, I, P, I, P, P, P, P, P],
     'st_ids_edit_distance': [P, I, I, P, I, P, I, P, P, P, P, P],
     'st_hyp_edit_distance': [P, P, I, I, P, I, P, I, P, P, P],

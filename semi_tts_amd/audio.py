@@ -649,6 +649,28 @@ class WaveBatch:
         self.device = self._wavs[0].device if self._wavs[0].is_cuda else None
         self._packed = {}
 
+    @classmethod
+    def window(cls, buffer, offsets, lens):
+        """a batch that lives inside a larger packed float32 device buffer (the corpus loader's split): utterance b is
+        buffer[offsets[b] : offsets[b] + lens[b]], nothing is copied and the offsets need not be cumulative.  The utterances must come
+        longest first already (what the constructor's stable sort would leave as it is)."""
+        lens, offsets = np.asarray(lens, np.int64), np.asarray(offsets, np.int64)
+        if not (buffer.is_cuda and buffer.dtype == torch.float32 and buffer.dim() == 1 and buffer.is_contiguous()):
+            raise ValueError('features: a window needs a contiguous 1-D float32 device buffer')
+        if lens.ndim != 1 or lens.shape != offsets.shape or len(lens) == 0:
+            raise ValueError('features: an empty batch')
+        if (lens < 1).any() or (offsets < 0).any() or (offsets + lens > buffer.numel()).any():
+            raise ValueError('features: a window outside its buffer of %d samples' % buffer.numel())
+        if (np.diff(lens) > 0).any():
+            raise ValueError('features: the utterances of a window come longest first')
+        wb = cls.__new__(cls)
+        wb.order = np.arange(len(lens))
+        wb._wavs = None
+        wb.lens, wb.offsets = lens.copy(), offsets.copy()
+        wb.device = buffer.device
+        wb._packed = {str(buffer.device): buffer}
+        return wb
+
     def packed(self, device):
         key = str(device)
         if key not in self._packed:

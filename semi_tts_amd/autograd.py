@@ -908,8 +908,8 @@ class _CtcLossFn(Function):
     gradient by the incoming scalar (like freq_loss)."""
 
     @staticmethod
-    def forward(ctx, prob, text, eps, log_input=False):
-        loss, dprob = ops.ctc_loss(prob.contiguous(), text.contiguous(), eps, want_grad=True, log_input=log_input)
+    def forward(ctx, prob, text, eps, log_input=False, in_len=None):
+        loss, dprob = ops.ctc_loss(prob.contiguous(), text.contiguous(), eps, want_grad=True, log_input=log_input, in_len=in_len)
         ctx.save_for_backward(dprob)
         return loss
 
@@ -920,13 +920,14 @@ class _CtcLossFn(Function):
         out = torch.empty_like(dprob)
         _lib.check(_lib.load().st_scale_by(ops._p(dprob), ops._p(dloss.contiguous()), ops._p(out), dprob.numel(), ops.stream_handle()),
                    'st_scale_by')
-        return out, None, None, None
+        return out, None, None, None, None
 
 
-def ctc_loss(prob, text, eps=1e-10, apply_log=True):
+def ctc_loss(prob, text, eps=1e-10, apply_log=True, in_len=None):
     """prob (B, T, V) posteriors over the codebook (index 0 = blank), text (B, L) int64 (zeros = padding);
-    apply_log=False: prob holds log-probabilities already (compute_ctcloss(..., apply_log=False), bin/train_vqvae.py:430-434)"""
-    return _CtcLossFn.apply(prob, text, eps, not apply_log)
+    apply_log=False: prob holds log-probabilities already (compute_ctcloss(..., apply_log=False), bin/train_vqvae.py:430-434);
+    in_len: (B,) int32 device tensor of frame counts (paras.actual_len, :436-438; ops.frame_lengths), None: every frame counts"""
+    return _CtcLossFn.apply(prob, text, eps, not apply_log, in_len)
 
 
 # --------------------------------------------------------------------------------------------- decoder loop

@@ -74,7 +74,14 @@ __global__ __launch_bounds__(256) void scale_by_kernel(const float* x, const flo
 // d loss / d prob with the formula ATen's CPU kernel uses (grad wrt lp = exp(lp) - exp(log sum_{s in c}(alpha beta) + nll - lp),
 // chained through the log): one thread per state of the blank-extended target (2 S + 1 <= 256), lp values gathered per chunk of
 // CTC_TC frames into LDS, ONE LDS barrier per frame (double-buffered state), every reduction in a fixed order.
+// in_len != NULL (paras.actual_len, bin/train_vqvae.py:436-444): utterance b uses the frames t < T_b = clamp(in_len[b], 0, T) only -- alpha
+// runs to T_b - 1, beta starts there, the gradient rows t >= T_b are exact zeros.  T_b is uniform per workgroup (b = blockIdx.x) and read
+// ONCE into a register, so every thread of a workgroup runs the same number of st_lds_barrier iterations.  With in_len the reference hands
+// CTCLoss the padded 2-D targets and takes the first S_b of each row; here the targets stay "the non-zero tokens in order": the two agree
+// whenever the zeros of a row are all at its end, which is how the corpus loader pads.
 constexpr int CTC_NT = 256, CTC_TC = 16;
+
+__device__ __forceinline__ int ctc_frames(const int32_t* in_len, int b, int T) { return in_len ? min(max(in_len[b], 0), T) : T; }
 
 __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
     const float m = fmaxf(a, fmaxf(b, c));
@@ -113,7 +120,8 @@ __device__ __forceinline__ void ctc_setup(const int64_t* text, int b, int L, int
 // on another compute unit -- the two recursions only meet in the gradient (ctc_grad_kernel); one workgroup doing both in turn took
 // 295 us at T = 128.  grid (B, 1) when no gradient is wanted.
 __global__ __launch_bounds__(CTC_NT) void ctc_loss_kernel(const float* prob, const int64_t* text, float eps, float* nll_out,
-                                                          float* log_alpha, float* log_beta, int B, int T, int V, int L, int log_input) {
+                                                          float* log_alpha, float* log_beta, const int32_t* in_len,
+                                                          int B, int T, int V, int L, int log_input) {
     extern __shared__ int ctc_dyn[];                 // cls_first[V]
     __shared__ int lab[CTC_NT], nxt[CTC_NT];
     __shared__ float st_a[2][CTC_NT];
@@ -121,6 +129,7 @@ __global__ __launch_bounds__(CTC_NT) void ctc_loss_kernel(const float* prob, con
     __shared__ int S_s, bad_s;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* pb = prob + (size_t)b * T * V;
+    const int Tb = ctc_frames(in_len, b, T);         // the frames of this utterance: uniform over the workgroup
     ctc_setup(text, b, L, V, lab, nxt, ctc_dyn, &S_s, &bad_s);
     const int S = S_s, SP = 2 * S + 1;
     const bool on = tid < SP;
@@ -137,8 +146,8 @@ __global__ __launch_bounds__(CTC_NT) void ctc_loss_kernel(const float* prob, con
     if (blockIdx.y == 0) {
         // ---- alpha
         float* la = log_alpha + (size_t)b * T * CTC_NT;
-        for (int t0 = 0; t0 < T; t0 += CTC_TC) {
-            const int nt = min(CTC_TC, T - t0);
+        for (int t0 = 0; t0 < Tb; t0 += CTC_TC) {
+            const int nt = min(CTC_TC, Tb - t0);
             __syncthreads();
             gather(t0, nt, 1);
             __syncthreads();
@@ -164,6 +173,7 @@ __global__ __launch_bounds__(CTC_NT) void ctc_loss_kernel(const float* prob, con
             const float l1 = pa[SP - 1], l2 = SP >= 2 ? pa[SP - 2] : -INFINITY;
             const float m = fmaxf(l1, l2);
             float v = m == -INFINITY ? INFINITY : -(m + logf(expf(l1 - m) + expf(l2 - m)));
+            if (Tb == 0) v = S > 0 ? INFINITY : 0.0f;             // no frame: only the empty transcript has an alignment (the empty one)
             if (bad_s) v = __builtin_nanf("");
             nll_out[b] = v;
         }
@@ -171,7 +181,7 @@ __global__ __launch_bounds__(CTC_NT) void ctc_loss_kernel(const float* prob, con
     }
     // ---- beta
     float* lb = log_beta + (size_t)b * T * CTC_NT;
-    for (int t1 = T - 1; t1 >= 0; t1 -= CTC_TC) {
+    for (int t1 = Tb - 1; t1 >= 0; t1 -= CTC_TC) {
         const int nt = min(CTC_TC, t1 + 1);
         __syncthreads();
         gather(t1, nt, -1);
@@ -180,7 +190,7 @@ __global__ __launch_bounds__(CTC_NT) void ctc_loss_kernel(const float* prob, con
             const int t = t1 - i;
             const float lps = lpS[i][tid];
             float bt;
-            if (t == T - 1) bt = (on && tid >= SP - 2) ? lps : -INFINITY;
+            if (t == Tb - 1) bt = (on && tid >= SP - 2) ? lps : -INFINITY;
             else {
                 const float* pbt = st_a[cur ^ 1];
                 const float b0 = on ? pbt[tid] : -INFINITY, b1 = (on && tid + 1 < SP) ? pbt[tid + 1] : -INFINITY;
@@ -200,13 +210,19 @@ __global__ __launch_bounds__(CTC_NT) void ctc_loss_kernel(const float* prob, con
 // once alpha and beta are known.  Same expressions and summation orders as when this was the tail of the beta walk.
 __global__ __launch_bounds__(CTC_NT) void ctc_grad_kernel(const float* prob, const int64_t* text, float eps, const float* nll_in,
                                                           float* dprob, const float* log_alpha, const float* log_beta,
-                                                          int B, int T, int V, int L, int log_input) {
+                                                          const int32_t* in_len, int B, int T, int V, int L, int log_input) {
     extern __shared__ int ctc_dyn[];                 // cls_first[V]
     __shared__ int lab[CTC_NT], nxt[CTC_NT];
     __shared__ float gam[2][CTC_NT];
     __shared__ int S_s, bad_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const float* pb = prob + (size_t)b * T * V;
+    const int Tb = ctc_frames(in_len, b, T);
+    const int t0 = blockIdx.y * CTC_TC, t1 = min(T, t0 + CTC_TC), tv = min(t1, Tb);
+    // the rows at or past T_b are exact zeros, for an infeasible utterance too (torch.nn.CTCLoss); a workgroup with nothing else to do
+    // leaves here, all of its threads together and before any barrier
+    for (size_t i = (size_t)max(t0, tv) * V + tid; i < (size_t)t1 * V; i += CTC_NT) dprob[(size_t)b * T * V + i] = 0.0f;
+    if (tv <= t0) return;
     int* cls_first = ctc_dyn;
     ctc_setup(text, b, L, V, lab, nxt, cls_first, &S_s, &bad_s);
     const int S = S_s, SP = 2 * S + 1;
@@ -217,9 +233,8 @@ __global__ __launch_bounds__(CTC_NT) void ctc_grad_kernel(const float* prob, con
     const float gr = (bad_s || nll == INFINITY) ? __builtin_nanf("") : 1.0f / ((float)max(S, 1) * (float)B);
     const float* la = log_alpha + (size_t)b * T * CTC_NT;
     const float* lb = log_beta + (size_t)b * T * CTC_NT;
-    const int t0 = blockIdx.y * CTC_TC, t1 = min(T, t0 + CTC_TC);
     int cur = 0;
-    for (int t = t0; t < t1; ++t) {
+    for (int t = t0; t < tv; ++t) {
         const float pv = on ? pb[(size_t)t * V + my] : 0.0f;
         const float lps = on ? (log_input ? pv : logf(pv + eps)) : -INFINITY;
         const float ab = on ? la[(size_t)t * CTC_NT + tid] + lb[(size_t)t * CTC_NT + tid] : -INFINITY;
@@ -259,6 +274,37 @@ __global__ __launch_bounds__(64) void ctc_loss_final_kernel(const float* nll, co
         __syncthreads();
     }
     if (threadIdx.x == 0) *loss = s / (float)B;
+}
+
+// the frame counts st_ctc_loss_len takes (see st_frame_lengths): one workgroup per utterance.  Spectrogram mode: thread i takes the frames
+// i, i + 256, ... and walks the D values of each; the threads' counts meet in LDS (integers: any order).
+// Text mode (x == NULL): the non-zero tokens of the row, then the reference's integer arithmetic.
+__global__ __launch_bounds__(256) void frame_lengths_kernel(const float* x, int T, int D, float pad_value, const int64_t* text, int L,
+                                                            int r, int div, int32_t* out) {
+    __shared__ int cnt;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) cnt = 0;
+    __syncthreads();
+    int n = 0;
+    if (x) {
+        const float* xb = x + (size_t)b * T * D;
+        for (int t = tid; t < T; t += 256) {         // a thread owns a frame: its D loads are independent of one another and of any vote
+            const float* f = xb + (size_t)t * D;
+            bool live = false;
+#pragma unroll 8
+            for (int d = 0; d < D; ++d) live |= f[d] != pad_value;
+            n += live;
+        }
+        if (n) atomicAdd(&cnt, n);
+    } else {
+        for (int i = tid; i < L; i += 256) n += text[(size_t)b * L + i] != 0;
+        if (n) atomicAdd(&cnt, n);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (x) out[b] = cnt / div;
+        else { const int len6 = 6 * cnt; out[b] = 1 + (len6 + len6 % r) / div; }
+    }
 }
 
 // the trainer's scalar arithmetic on loss values (total = sum_i w_i loss_i, plus the sums the log prints) as ONE launch:
@@ -311,6 +357,11 @@ extern "C" size_t st_ctc_workspace_floats(int B, int T) { return 2 * (size_t)B *
 
 extern "C" int st_ctc_loss(const float* prob, const int64_t* text, float eps, float* loss, float* dprob, float* ws,
                            int B, int T, int V, int L, int log_input, void* stream) {
+    return st_ctc_loss_len(prob, text, nullptr, eps, loss, dprob, ws, B, T, V, L, log_input, stream);
+}
+
+extern "C" int st_ctc_loss_len(const float* prob, const int64_t* text, const int32_t* in_len, float eps, float* loss, float* dprob, float* ws,
+                               int B, int T, int V, int L, int log_input, void* stream) {
     (void)hipGetLastError();
     ST_CHECK_ARG(prob && text && loss && ws && B > 0 && T > 0 && V > 1 && L > 0, "st_ctc_loss: bad arguments");
     ST_CHECK_ARG(2 * L + 1 <= CTC_NT, "st_ctc_loss: transcripts of up to %d tokens (L=%d)", (CTC_NT - 1) / 2, L);
@@ -320,14 +371,26 @@ extern "C" int st_ctc_loss(const float* prob, const int64_t* text, float eps, fl
     hipStream_t st = (hipStream_t)stream;
     float* lbeta = ws + (size_t)B * T * CTC_NT;
     float* nll = ws + 2 * (size_t)B * T * CTC_NT;
-    hipLaunchKernelGGL(ctc_loss_kernel, dim3(B, dprob ? 2 : 1), dim3(CTC_NT), (size_t)V * sizeof(int), st, prob, text, eps, nll, ws, lbeta, B, T, V, L, log_input);
+    hipLaunchKernelGGL(ctc_loss_kernel, dim3(B, dprob ? 2 : 1), dim3(CTC_NT), (size_t)V * sizeof(int), st, prob, text, eps, nll, ws, lbeta, in_len,
+                       B, T, V, L, log_input);
     ST_LAUNCH_CHECK();
     if (dprob) {
         hipLaunchKernelGGL(ctc_grad_kernel, dim3(B, (T + CTC_TC - 1) / CTC_TC), dim3(CTC_NT), (size_t)V * sizeof(int), st, prob, text, eps, nll, dprob, ws, lbeta,
-                           B, T, V, L, log_input);
+                           in_len, B, T, V, L, log_input);
         ST_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(ctc_loss_final_kernel, dim3(1), dim3(64), 0, st, nll, text, B, L, loss);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_frame_lengths(const float* x, int B, int T, int D, float pad_value, const int64_t* text, int L, int r, int div, int32_t* out,
+                                void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(out && B > 0 && div >= 1, "st_frame_lengths: bad arguments");
+    ST_CHECK_ARG(x ? (T > 0 && D > 0) : (text && L > 0 && r >= 1), "st_frame_lengths: x (B, T, D), or text (B, L) with r >= 1");
+    ST_CHECK_ARG(x || L <= (1 << 24), "st_frame_lengths: L=%d too large", L);
+    hipLaunchKernelGGL(frame_lengths_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, T, D, pad_value, text, L, r, div, out);
     ST_LAUNCH_CHECK();
     return 0;
 }

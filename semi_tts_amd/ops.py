@@ -854,17 +854,52 @@ def rowscale_combine(a, alpha, x=None, r=None, beta=0.0, c=None):
     return out
 
 
-def ctc_loss(prob, text, eps, want_grad=True, log_input=False):
-    """-> (loss scalar tensor, d loss / d prob or None); see st_ctc_loss (log_input: prob holds log-probabilities)"""
+CTC_MAX_TOKENS, CTC_TC = 127, 16      # st_ctc_loss: the longest transcript (one thread per blank-extended state), the frames per tile
+
+
+def ctc_loss(prob, text, eps, want_grad=True, log_input=False, in_len=None, dprob=None):
+    """-> (loss scalar tensor, d loss / d prob or None); see st_ctc_loss (log_input: prob holds log-probabilities).
+    in_len: (B,) int32 device tensor, utterance b uses its first clamp(in_len[b], 0, T) frames (st_ctc_loss_len); None: every frame.
+    dprob: a caller's (B, T, V) buffer for the gradient (every element is written)."""
     lib = _lib.load()
     B, T, V = prob.shape
     L = text.shape[1]
     loss = torch.empty((), device=prob.device, dtype=torch.float32)
-    dprob = torch.empty_like(prob) if want_grad else None
+    if dprob is not None:
+        if tuple(dprob.shape) != (B, T, V) or not dprob.is_contiguous():
+            raise ValueError('ctc_loss: dprob must be a contiguous (B, T, V) buffer')
+    elif want_grad:
+        dprob = torch.empty_like(prob)
     ws = torch.empty(int(lib.st_ctc_workspace_floats(B, T)), device=prob.device, dtype=torch.float32)
-    check(lib.st_ctc_loss(_p(prob), _p(text, torch.int64), float(eps), _p(loss), _p(dprob), _p(ws), B, T, V, L, 1 if log_input else 0,
-                          stream_handle()), 'st_ctc_loss')
+    if in_len is None:
+        check(lib.st_ctc_loss(_p(prob), _p(text, torch.int64), float(eps), _p(loss), _p(dprob), _p(ws), B, T, V, L, 1 if log_input else 0,
+                              stream_handle()), 'st_ctc_loss')
+    else:
+        if tuple(in_len.shape) != (B,) or not in_len.is_contiguous():
+            raise ValueError('ctc_loss: in_len must be a contiguous (B,) int32 tensor')
+        check(lib.st_ctc_loss_len(_p(prob), _p(text, torch.int64), _p(in_len, torch.int32), float(eps), _p(loss), _p(dprob), _p(ws),
+                                  B, T, V, L, 1 if log_input else 0, stream_handle()), 'st_ctc_loss_len')
     return loss, dprob
+
+
+def frame_lengths(x=None, pad_value=0.0, div=1, text=None, r=1):
+    """(B,) int32 frame counts for ctc_loss(in_len=...), on the device, one launch, no host read (see st_frame_lengths):
+    x (B, T, D) fp32 -> (frames of x[b] not entirely == pad_value) // div;
+    text (B, L) int64 (x None) -> 1 + (len6 + len6 % r) // div with len6 = 6 * nonzero(text[b]): the text-first branch"""
+    if (x is None) == (text is None):
+        raise ValueError('frame_lengths: either x or text')
+    src = x if x is not None else text
+    if src.dim() != (3 if x is not None else 2) or not src.is_contiguous():
+        raise ValueError('frame_lengths: a contiguous (B, T, D) spectrogram or (B, L) text')
+    B = src.shape[0]
+    out = torch.empty(B, device=src.device, dtype=torch.int32)
+    if x is not None:
+        check(_lib.load().st_frame_lengths(_p(x), B, x.shape[1], x.shape[2], float(pad_value), None, 0, 1, int(div), _p(out, torch.int32),
+                                           stream_handle()), 'st_frame_lengths')
+    else:
+        check(_lib.load().st_frame_lengths(None, B, 0, 0, 0.0, _p(text, torch.int64), text.shape[1], int(r), int(div), _p(out, torch.int32),
+                                           stream_handle()), 'st_frame_lengths')
+    return out
 
 
 GED_MAX_T, GED_MAX_V, GED_MAX_L, GED_MAX_IGNORE = 4096, 10240, 1024, 64      # st_ctc_greedy_edit_distance's limits

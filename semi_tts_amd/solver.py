@@ -55,6 +55,15 @@ class BaseSolver:
         if not path:
             return False
         ckpt = torch.load(path, map_location=self.device)
+        if getattr(self, 'corpus', None) is not None:
+            # --corpus: vocab_size and n_spkr come from the corpus files; a checkpoint trained on other tables is refused by name
+            own = self.model.state_dict()
+            n_ck = ckpt['model']['spkr_embed.weight'].shape[0] if 'spkr_embed.weight' in ckpt['model'] else self.n_spkr
+            off = [k for k, v in ckpt['model'].items() if k.startswith('codebook.') and k in own and tuple(v.shape) != tuple(own[k].shape)]
+            if n_ck != self.n_spkr or off:
+                raise ValueError('--load %s disagrees with the corpus (vocab_size %d, n_spkr %d): the checkpoint has %d speakers%s'
+                                 % (path, self.vocab_size, self.n_spkr, n_ck,
+                                    ''.join('; %s is %s' % (k, tuple(ckpt['model'][k].shape)) for k in off[:3])))
         # strict, like the reference (bin/gen_specgram.py:80, bin/train_vqvae.py:106): a checkpoint of another architecture
         # must not leave the constructor's random weights in place silently
         self.model.load_state_dict(ckpt['model'], strict=True)
@@ -897,9 +906,29 @@ class TtsTrainer(BaseSolver):
         if getattr(paras, 'async_stats', False):
             self.async_stats = True
 
+    def _load_corpus(self, splits, batch_sizes):
+        """--corpus: the splits of data.corpus as device-resident sets (semi_tts_amd/corpus.py); vocab_size and n_spkr from its files"""
+        from .audio import load_audio_transform
+        from .corpus import load_splits
+        pa = self.paras
+        self.r = self.config['model']['decoder']['decoder']['n_frames_per_step']
+        self.audio_converter = load_audio_transform(**self.config['data']['audio'])
+        if self.audio_converter.n_mels != self.n_mels:
+            raise ValueError('--corpus: data.audio has %d mels, the model %d' % (self.audio_converter.n_mels, self.n_mels))
+        self.corpus, self.corpus_sets = load_splits(
+            self.config['data']['corpus'], self.audio_converter, self.r, splits, batch_sizes, seed=int(getattr(pa, 'seed', 0)),
+            rank=int(os.environ.get('RANK', 0)), world=int(os.environ.get('WORLD_SIZE', 1)), resample=bool(getattr(pa, 'resample', False)),
+            max_frames=getattr(pa, 'max_frames', None), max_gb=getattr(pa, 'corpus_max_gb', None), verbose=self.verbose)
+        self.vocab_size, self.n_spkr = self.corpus.vocab_size, self.corpus.n_spkr
+        return self.corpus_sets
+
     def load_data(self):
         from .synthetic import synthetic_train_batch
         B = int(getattr(self.paras, 'batch_size', None) or self.config['data']['corpus'].get('batch_size', 8))
+        if getattr(self.paras, 'corpus', False):              # --tts-only --corpus: the paired split
+            self._load_corpus(['paired'], {'paired': B})
+            self.batches = None
+            return self
         frames = int(getattr(self.paras, 'frames', 256))
         n = int(getattr(self.paras, 'n_batches', 1))
         self.r = self.config['model']['decoder']['decoder']['n_frames_per_step']
@@ -1122,7 +1151,10 @@ class TtsTrainer(BaseSolver):
         t0 = time.perf_counter()
         frames = 0
         while self.step < self.max_step:
-            text, sid, mel, linear = (t.to(self.device) for t in self.batches[self.step % len(self.batches)])
+            if self.batches is None:                          # --corpus
+                mel, _, linear, text, sid = self.corpus_sets['paired'].fetch()
+            else:
+                text, sid, mel, linear = (t.to(self.device) for t in self.batches[self.step % len(self.batches)])
             st = self.train_step(text, sid, mel, linear)
             frames += mel.shape[0] * mel.shape[1]
             self.log.append(st)
@@ -1141,6 +1173,7 @@ class TtsTrainer(BaseSolver):
 
 
 EPS = 1e-10                      # ref: bin/train_vqvae.py:18
+SPEC_PAD_VALUE = 0.0             # ref: bin/train_vqvae.py:15 (what collect_fn pads spectrograms with)
 CKPT_STEP = 10000                # ref: bin/train_vqvae.py:17
 BEST_TTS_LOSS_INIT, BEST_PER_INIT = 100.0, 2.0          # ref: bin/train_vqvae.py:26-27 (a PER of 2.0 or more never saves)
 
@@ -1190,27 +1223,34 @@ class VqvaeTrainer(TtsTrainer):
     the TTS branch, the CTC loss (autograd.ctc_loss)."""
     STATIC_GRAPH = False     # the cycles' autograd graphs depend on the data (ignore_speech_cycle, skip_prob draws, txt_update_codebook)
 
-    def ctc_loss(self, prob, text):
-        """compute_ctcloss with paras.actual_len = False (bin/train_vqvae.py:430-444): every frame counts, the targets are the
-        non-zero tokens; torch.nn.CTCLoss() defaults (blank 0, mean over the batch of nll / target length)"""
+    def ctc_loss(self, prob, text, model_input=None, apply_log=True):
+        """compute_ctcloss (bin/train_vqvae.py:430-444): the targets are the non-zero tokens; torch.nn.CTCLoss() defaults (blank 0, mean
+        over the batch of nll / target length).  Without paras.actual_len every frame counts.  With it utterance b counts the frames of
+        `model_input` (B, T, n_mels) that are not entirely SPEC_PAD_VALUE, divided by the encoder's time reduction (:437-438): computed
+        and consumed on the device (ops.frame_lengths -> st_ctc_loss_len), no host read."""
         from . import autograd as AG
-        return AG.ctc_loss(prob, text, EPS)
+        return AG.ctc_loss(prob, text, EPS, apply_log=apply_log, in_len=self._ctc_in_len(model_input))
+
+    def _ctc_in_len(self, model_input):
+        if not getattr(self.paras, 'actual_len', False) or model_input is None:
+            return None
+        return ops.frame_lengths(model_input.contiguous(), SPEC_PAD_VALUE, int(self.model.time_reduce_factor))
 
     def _async(self):
         from .optim import FusedAdam
         return self.async_stats and isinstance(getattr(self.optimizer, 'opt', None), FusedAdam)
 
-    def _paired_losses(self, pair_prob, pair_post_prob, pm, pl, mel, linear, text, terms, stats, linear_loss=None):
+    def _paired_losses(self, pair_prob, pair_post_prob, pm, pl, mel, linear, text, terms, stats, linear_loss=None, aug_mel=None):
         """the terms both cycles share (bin/train_vqvae.py:208-224): CTC on the paired posteriors (+ the ASRPostnet term) and
         freq_loss on the paired reconstruction.  Appends (weight, loss, statistics name) to `terms`: the weighted sum itself -- and the
         partial sums the log prints -- are ONE launch in _finish_step (the reference's chain of one-element kernels)."""
         hp = self.hp
-        asr_loss = self.ctc_loss(pair_prob, text)                                                 # :209
+        asr_loss = self.ctc_loss(pair_prob, text, aug_mel)                                        # :209
         asr_w = float(hp.get('asr_weight', 1.0))
         if self.model.use_asr_postnet:                                                            # :210-213
             from . import autograd as AG
             pw = float(self.model.asr_postnet_weight)
-            asr_post_loss = AG.ctc_loss(pair_post_prob, text, EPS, apply_log=False)               # compute_ctcloss(..., apply_log=False)
+            asr_post_loss = self.ctc_loss(pair_post_prob, text, aug_mel, apply_log=False)         # compute_ctcloss(..., apply_log=False)
             terms += [(asr_w * (1.0 - pw), asr_loss, None), (asr_w * pw, asr_post_loss, None)]
             stats['asr_post_loss'] = asr_post_loss.detach()
         else:
@@ -1327,7 +1367,7 @@ class VqvaeTrainer(TtsTrainer):
                                  ([] if ignore_speech_cycle else [(w, lambda: self.freq_loss(upl, unpair_linear), 'unpair_speech_loss')]))
         lin = side[1] if side is not None else [None, None]
         stats, terms = {}, []
-        self._paired_losses(pair_prob, pair_post_prob, pm, pl, mel, linear, text, terms, stats, linear_loss=lin[0])
+        self._paired_losses(pair_prob, pair_post_prob, pm, pl, mel, linear, text, terms, stats, linear_loss=lin[0], aug_mel=aug_mel)
         if not ignore_speech_cycle:                                                               # :227-233
             terms += [(w, self.freq_loss(upm, unpair_mel), 'unpair_speech_loss'),
                       (w, lin[1] if side is not None else self.freq_loss(upl, unpair_linear), 'unpair_speech_loss')]
@@ -1338,7 +1378,7 @@ class VqvaeTrainer(TtsTrainer):
         paired text (teacher forced) and, when given, the unpaired text (rows without a teacher feed their own output back); the
         unpaired prediction is DETACHED and goes through speech_to_text next to the paired mel with `using_fake_mel` (the codebook
         table is detached for the fake part); losses: the paired terms, plus CTC of the unpaired posteriors against the unpaired text
-        (paras.actual_len = False: every frame counts).  A NaN / inf unpaired term is counted and dropped, as the reference does."""
+        (every frame counts; with paras.actual_len the frames the text predicts, :237-240).  A NaN / inf unpaired term is counted and dropped, as the reference does."""
         hp = self.hp
         tf_rate = self._begin_step()
         use_unpair_text = unpair_text is not None                                                 # the caller gates it (:128,:149-152)
@@ -1358,9 +1398,15 @@ class VqvaeTrainer(TtsTrainer):
                                             **({'_masks': _asr_masks} if _asr_masks is not None else {}))   # :203-205
         pair_prob, _, unpair_prob, _, _, pair_post_prob, _ = asr
         stats, terms = {}, []
-        self._paired_losses(pair_prob, pair_post_prob, pm, pl, mel, linear, text, terms, stats, linear_loss=side[1][0] if side is not None else None)
+        self._paired_losses(pair_prob, pair_post_prob, pm, pl, mel, linear, text, terms, stats, linear_loss=side[1][0] if side is not None else None,
+                            aug_mel=aug_mel)
         if use_unpair_text:                                                                       # :234-250
-            ut = self.ctc_loss(unpair_prob, unpair_text)
+            if getattr(self.paras, 'actual_len', False):                                          # :237-240, on the device
+                from . import autograd as AG
+                ut = AG.ctc_loss(unpair_prob, unpair_text, EPS, in_len=ops.frame_lengths(
+                    text=unpair_text.contiguous(), r=int(self.model.n_frames_per_step), div=int(self.model.time_reduce_factor)))
+            else:
+                ut = self.ctc_loss(unpair_prob, unpair_text)
             stats['unpair_text_loss'] = ut.detach()
             # :246-248: a non-finite unpaired term is dropped (and counted).  That decides what backward() sees, so it is the one scalar
             # this cycle reads inside the step (only configurations with unpair_text_weight > 0 get here; none of the shipped ones)
@@ -1402,11 +1448,25 @@ class VqvaeTrainer(TtsTrainer):
         """Synthetic counterparts of the reference's pair_set / unpair_set loaders (bin/train_vqvae.py:55-69; src/data.py is
         outside the path): `n_batches` seeded batches each, a different seed per rank (utterance-level data parallelism), mel / linear
         zero-padded to a multiple of r and aug_mel unpadded exactly as fetch_data delivers them (:33-53).  The unpaired set has its
-        own batch size and length (--unpair-batch-size / --unpair-frames; default: the paired ones)."""
+        own batch size and length (--unpair-batch-size / --unpair-frames; default: the paired ones).
+        --corpus: the three sets are the paired / unpaired / dev splits of data.corpus instead (semi_tts_amd/corpus.py: device-resident
+        waveforms, features extracted on every fetch, real text and speaker ids for the unpaired split too); nothing synthetic is drawn."""
         from .synthetic import synthetic_cycle_batch
         pa = self.paras
         B = int(getattr(pa, 'batch_size', None) or self.config['data']['corpus'].get('batch_size', 8))
         Bu = int(getattr(pa, 'unpair_batch_size', None) or B)
+        if getattr(pa, 'corpus', False):
+            # --corpus: pair_set / unpair_set / dev_set are the splits of data.corpus, resident on the device; --dev-batches K walks the
+            # first K batches of the dev split, -1 all of it, 0 none (the split is then not loaded)
+            k = int(getattr(pa, 'dev_batches', 0) or 0)
+            sets = self._load_corpus(['paired', 'unpaired'] + (['dev'] if k != 0 else []), {'paired': B, 'unpaired': Bu, 'dev': B})
+            self.pair_set, self.unpair_set = sets['paired'], sets['unpaired']
+            self.unpair_waves = None
+            n_dev = sets['dev'].n_batches() if k != 0 else 0
+            self.dev_set = [None] * (n_dev if k < 0 else min(k, n_dev))      # (validate walks len(dev_set) batches from the start)
+            self.dev_iter = self.pair_iter = self.unpair_iter = 0
+            self.batches = None
+            return self
         frames = int(getattr(pa, 'frames', 256))
         uframes = int(getattr(pa, 'unpair_frames', None) or frames)
         n = int(getattr(pa, 'n_batches', 1))
@@ -1456,6 +1516,8 @@ class VqvaeTrainer(TtsTrainer):
         data = getattr(self, iter_name.replace('iter', 'set'))
         i = getattr(self, iter_name)
         setattr(self, iter_name, i + 1)
+        if getattr(self, 'corpus', None) is not None:       # --corpus: features extracted from the resident waveforms on every fetch
+            return self.corpus_sets[{'pair_iter': 'paired', 'unpair_iter': 'unpaired', 'dev_iter': 'dev'}[iter_name]].fetch()
         if iter_name == 'unpair_iter' and self.unpair_waves is not None:
             j = i % len(self.unpair_waves)
             mel, aug_mel, linear = self.audio_converter.extract_batch(self.unpair_waves[j], r=self.r)
@@ -1485,6 +1547,8 @@ class VqvaeTrainer(TtsTrainer):
         ops.side_pending(None)
         self.model.eval()
         tts, per, post = [], [], []
+        if getattr(self, 'corpus', None) is not None and self.dev_set:
+            self.corpus_sets['dev'].rewind()                 # the dev split is walked from its first batch every time
         try:
             with torch.no_grad():
                 for _ in range(len(self.dev_set)):
