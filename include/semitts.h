@@ -1471,6 +1471,37 @@ int st_f0_path_scores(const float* f0_x, long x_sb, int Tx, const float* f0_y, l
                       const int32_t* path /* (B, P, 2) */, const int32_t* path_len /* (B) */, int B, int P,
                       int32_t* counts /* (B, 4) */, float* sums /* (B, 2) */, void* stream);
 
+/* ------------------------------------------------------------------ silence trimming (waveforms -> sample bounds, non-silent intervals)
+ * Not a step of the reference (it leaves trimming to an offline tool).  The definition is that of librosa.effects.trim / split with
+ * ref = max, center = True and zero padding, on the RAW waveform of a ragged batch (st_wave_batch, B <= 64).
+ * Frames.  Utterance b with L = len[b] samples x[0 .. L) has the frames t = 0 .. T - 1, T = 1 + L / hop.  Frame t reads the
+ * frame_length samples x[t hop - frame_length / 2 + j], j < frame_length (integer division), with x[i] = 0 for i outside [0, L) --
+ * never a neighbouring utterance's samples of the packed buffer.
+ * Energy.  energy[b, t] = (sum_j x^2) / frame_length in fp32; rows t >= T up to T_pad are written 0.  Summation order: with
+ * j = 64 q + l, lane l < 64 forms ONE chain acc = fmaf(x, x, acc) over its j in ascending q; the 64 partials combine by the xor
+ * butterfly (lane offsets 32, 16, 8, 4, 2, 1); the quotient by frame_length is one correctly rounded division.  A frame's bits depend
+ * on its utterance's samples and the framing alone: not on B, the position in the batch, T_pad or what lies next to the utterance.
+ * A NaN or an infinity among the samples makes exactly the frames that read it NaN / inf (IEEE), as in the pitch tracker above.
+ * Decision.  e_t = max(energy_t, 1e-10f), ref = max_t e_t; frame t is non-silent iff e_t > ref * ratio (one fp32 product, a strict
+ * comparison), ratio = 10^(-top_db / 10) computed in double by the caller and rounded once.  0 < ratio < 1, so the loudest frame is
+ * always non-silent and digital silence is kept whole.  (Should the product round up to ref itself -- a ratio within 2^-23 of 1 --
+ * the frames with e_t = ref count as non-silent, as they would with the exact product.)
+ * bounds[b] = (start, end, n_nonsilent, flags): with f0 / f1 the first / last non-silent frame, start = max(0, f0 hop - pad),
+ * end = min(L, (f1 + 1) hop + pad).  An utterance with any non-finite energy gets (0, L, -1, 1) and n_iv = 0, every interval entry
+ * -1; the other utterances of the batch are unaffected.
+ * intervals (when not NULL): the maximal runs of non-silent frames [fa, fb] as (fa hop, min(L, (fb + 1) hop)), ascending, pad NOT
+ * applied; n_iv[b] (when not NULL) the true number of runs, even above max_iv; entries past min(n_iv, max_iv) are written -1.
+ * Two launches (energies: a workgroup stages the span of a run of consecutive frames in LDS once; decision: one workgroup per
+ * utterance), no atomics, no workspace beyond `energy`, no host read: bitwise repeatable.
+ * Limits (-22 past them, before any device call): 1 <= B <= 64, every len >= 1, 1 <= hop <= frame_length <= 8192, T_pad >= the
+ * largest T, 0 < ratio < 1 (finite), pad >= 0, max_iv >= 0 and max_iv == 0 exactly when intervals is NULL.
+ * st_trim_run_length: the consecutive frames one workgroup takes from one staged span at this framing (16, fewer when
+ * 15 hop + frame_length would pass 12288 samples; 0 outside the limits) -- for tests that straddle it. */
+int st_trim_run_length(int frame_length, int hop);
+int st_trim_silence(const st_wave_batch* w, int frame_length, int hop, float ratio, int pad, int max_iv,
+                    float* energy /* (B, T_pad) */, int T_pad, int32_t* bounds /* (B, 4) */,
+                    int32_t* intervals /* (B, max_iv, 2) or NULL */, int32_t* n_iv /* (B) or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

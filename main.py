@@ -27,6 +27,8 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --feat-wav-dir DIR --feat f0 [--f0-min 60 --f0-max 500 --f0-threshold 0.15]
     python main.py --config config/supervised.yaml --mcd-wav-dir SYN --mcd-ref-dir REF [--mcd-path --mcd-f0 --batch-size 32]
     python main.py --config config/supervised.yaml --synth-phn-dir DIR [--load ckpt.pth --vocab FILE --synth-sid 0 --gen-wav --batch-size 8]
+    python main.py --config config/supervised.yaml --trim-wav-dir DIR --trim-out DIR2 [--trim-top-db 60 --trim-frame-length 2048 --trim-hop 512]
+    python main.py --config config/semi-multi-spkr-paired-data.yaml --corpus --trim-silence [--trim-pad-ms 0]
 `--corpus` trains on the reference's corpus layout (semi_tts_amd/corpus.py: partition table, map table, speaker map, vocabulary file and
 <path>/<speaker>/<id>.wav, src/data.py + corpus/vctk.py + src/text.py): each split of the rank's shard is read once and stays on the device as
 one packed buffer, every fetch extracts mel / augmented mel / linear from it on the GPU, `--dev-batches K` (-1: all) validates on the real dev
@@ -43,6 +45,10 @@ vocode the predicted mel instead of the predicted linear spectrogram.
 `--resample` (with --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir) converts files whose rate is not data.audio.sample_rate on
 the GPU (semi_tts_amd.audio.resample: Hann-windowed sinc, st_resample_batch) where the reference, and this path without the flag, refuse
 them; `--resample-wav-dir` converts a directory of .wav files to another rate and writes them as 16-bit mono (solver.Resampler).
+`--trim-silence` (not a step of the reference, which leaves trimming to an offline tool) cuts the leading and trailing silence of every
+utterance that --corpus, --unpair-wav-dir, --transcribe-wav-dir, --mcd-wav-dir or --feat-wav-dir load, on the GPU and without a copy
+(semi_tts_amd.audio.AudioConverter.trim_batch, st_trim_silence: the definition of librosa.effects.trim); `--trim-wav-dir` writes the kept
+span of every .wav of a directory, bit for bit, and trim.csv (solver.Trimmer).
 `--feat-wav-dir` writes the MFCC (13 cepstra and their two derivatives, src/audio.py:119-154), mel or linear features of .wav files as
 <stem>-<feat>.npy and, with `--segment-file` (the segments.csv of --align-wav-dir), the same cut at the phone boundaries as
 <stem>-<feat>-seg.npy (solver.FeatureWriter; the reference's segment_file / segment_feat / min_segment_len, src/audio.py:309-354).
@@ -174,6 +180,17 @@ parser.add_argument('--end-max-jump', default=None, type=int, help='--synth-phn-
                     'phones than this counts as a skip (default 4)')
 parser.add_argument('--max-frames-per-phone', default=None, type=float, help='--synth-phn-dir: frames decoded per phone of the longest '
                     'transcript of a batch, before the margin of 40 (default 12, twice the corpus ratio)')
+parser.add_argument('--trim-silence', action='store_true', help='--corpus / --unpair-wav-dir / --transcribe-wav-dir / --mcd-wav-dir (both sides) / '
+                    '--feat-wav-dir (without --segment-file): cut the leading and trailing silence of every utterance on the GPU after loading '
+                    '(AudioConverter.trim_batch: frames less than --trim-top-db dB under the loudest frame are silent)')
+parser.add_argument('--trim-top-db', default=None, type=float, help='--trim-silence / --trim-wav-dir: the threshold in dB under the loudest frame (default 60)')
+parser.add_argument('--trim-frame-length', default=None, type=int, help='--trim-silence / --trim-wav-dir: samples per energy frame (default 2048, at most 8192)')
+parser.add_argument('--trim-hop', default=None, type=int, help='--trim-silence / --trim-wav-dir: samples between energy frames (default 512)')
+parser.add_argument('--trim-pad-ms', default=None, type=float, help='--trim-silence / --trim-wav-dir: milliseconds kept on both sides of the speech (default 0)')
+parser.add_argument('--trim-wav-dir', default=None, type=str, help='cut the leading and trailing silence of the .wav files of this directory (sorted by '
+                    'name, batched by --batch-size, at data.audio.sample_rate of --config) and write the kept span of channel 0 -- the exact 16-bit '
+                    'samples -- to --trim-out/<same name>, with --trim-out/trim.csv (file, samples, start, end, seconds, kept_seconds, n_intervals); no model')
+parser.add_argument('--trim-out', default=None, type=str, help='--trim-wav-dir: the directory to write (not the one read)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -202,7 +219,7 @@ def parse_args(argv=None):
                      % ('tts-only' if paras.tts_only else 'gen-specgram'))
     if paras.corpus:
         for flag in ('unpair_wav_dir', 'gen_specgram', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir', 'resample_wav_dir',
-                     'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir'):
+                     'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir'):
             if getattr(paras, flag):
                 parser.error('--corpus trains on the splits of data.corpus (the unpaired one included); it does not combine with --%s'
                              % flag.replace('_', '-'))
@@ -327,6 +344,35 @@ def parse_args(argv=None):
         paras.end_patience = 3
     if paras.end_max_jump is None:
         paras.end_max_jump = 4
+    if paras.trim_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_silence'):
+            if getattr(paras, flag):
+                parser.error('--trim-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--trim-wav-dir does not combine with --dev-batches')
+        if paras.trim_out is None or paras.config is None:
+            parser.error('--trim-wav-dir needs --trim-out DIR (the directory to write) and --config (its data.audio)')
+        if os.path.realpath(paras.trim_out) == os.path.realpath(paras.trim_wav_dir):
+            parser.error('--trim-out must not be the directory --trim-wav-dir reads')
+    elif paras.trim_out is not None:
+        parser.error('--trim-out belongs to --trim-wav-dir; it needs that flag')
+    if paras.trim_silence:
+        if paras.align_wav_dir is not None:
+            parser.error('--trim-silence does not combine with --align-wav-dir: its times refer to the untrimmed file')
+        if paras.segment_file is not None:
+            parser.error('--trim-silence does not combine with --segment-file: its times refer to the untrimmed file')
+        if not (paras.corpus or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir'))):
+            parser.error('--trim-silence trims what --corpus, --unpair-wav-dir, --transcribe-wav-dir, --mcd-wav-dir or --feat-wav-dir load; it needs one '
+                         'of them')
+    elif paras.trim_wav_dir is None and any(v is not None for v in (paras.trim_top_db, paras.trim_frame_length, paras.trim_hop, paras.trim_pad_ms)):
+        parser.error('--trim-top-db, --trim-frame-length, --trim-hop and --trim-pad-ms set --trim-silence or --trim-wav-dir; they need one of them')
+    paras.trim_top_db = 60.0 if paras.trim_top_db is None else paras.trim_top_db
+    paras.trim_frame_length = 2048 if paras.trim_frame_length is None else paras.trim_frame_length
+    paras.trim_hop = 512 if paras.trim_hop is None else paras.trim_hop
+    paras.trim_pad_ms = 0.0 if paras.trim_pad_ms is None else paras.trim_pad_ms
+    if not 0.0 < paras.trim_top_db < float('inf') or not 1 <= paras.trim_hop <= paras.trim_frame_length <= 8192 or not 0.0 <= paras.trim_pad_ms < float('inf'):
+        parser.error('--trim-top-db must be finite and positive, 1 <= --trim-hop <= --trim-frame-length <= 8192 and --trim-pad-ms finite and >= 0')
     if paras.gen_wav_feat != 'linear' and not ((paras.gen_specgram or paras.synth_phn_dir is not None) and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
@@ -398,6 +444,9 @@ def main(argv=None):
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
     if paras.resample_wav_dir is not None:
         from semi_tts_amd.solver import Resampler as Solver
+        mode = 'test'
+    elif paras.trim_wav_dir is not None:
+        from semi_tts_amd.solver import Trimmer as Solver
         mode = 'test'
     elif paras.vocode_dir is not None:
         from semi_tts_amd.solver import Vocoder as Solver

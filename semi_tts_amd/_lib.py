@@ -421,6 +421,8 @@ SIGNATURES = {
     'st_f0_run_length': [I, I, I],
     'st_f0_yin': [C.POINTER(StWaveBatch), I, I, I, I, F, F, P, P, I, P],
     'st_f0_path_scores': [P, C.c_long, I, P, C.c_long, I, P, P, I, I, P, P, P],
+    'st_trim_run_length': [I, I],
+    'st_trim_silence': [C.POINTER(StWaveBatch), I, I, F, I, I, P, I, P, P, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,

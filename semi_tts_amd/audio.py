@@ -347,14 +347,18 @@ class AudioConverter:
         """src/audio.py:68-77: (channels, samples) float32; a different sample rate raises"""
         return load_wav(wav_path, self.sr)
 
-    def load_batch(self, paths, resample=False):
+    def load_batch(self, paths, resample=False, trim=None):
         """Channel 0 of the .wav files `paths` as one WaveBatch at self.sr on the device (`.order`: the position in `paths` of each
         utterance).  A file at another rate raises load()'s error -- or, with resample=True, is converted on the GPU: the files are
         grouped by source rate and each foreign group is uploaded as int16 PCM and resampled in one resample() call.  Every file
-        is read and every rate checked before a device is touched."""
+        is read and every rate checked before a device is touched.  trim: a dict of trim_batch's keyword arguments (top_db,
+        frame_length, hop_length, pad_ms); the leading and trailing silence of every utterance is then cut, after resampling (`.bounds`:
+        the kept (start, end) of each file, in the order of `paths`)."""
         paths = [str(p) for p in paths]
         if not paths:
             raise ValueError('load_batch: no files')
+        if trim is not None:
+            self._check_trim(**trim)
         read = [_read_pcm(p) for p in paths]
         groups = {}
         for i, ((_, sr), p) in enumerate(zip(read, paths)):
@@ -373,7 +377,65 @@ class AudioConverter:
             y = wb.packed(dev)
             for row, k in enumerate(wb.order):
                 waves[idx[k]] = y[int(wb.offsets[row]):int(wb.offsets[row] + wb.lens[row])]
-        return WaveBatch(waves)
+        if trim is None:
+            return WaveBatch(waves)
+        res = self.trim_batch(waves, **trim)
+        res[0].bounds = res[1]
+        return res[0]
+
+    # -- silence trimming (not a step of the reference): st_trim_silence, the definition of librosa.effects.trim / split
+    def _check_trim(self, top_db=60., frame_length=2048, hop_length=512, pad_ms=0., with_intervals=False, lens=(1,)):
+        """every refusal of trim_batch that does not need the waveforms -> pad in samples"""
+        if isinstance(pad_ms, bool) or not isinstance(pad_ms, (int, float, np.integer, np.floating)) or not 0.0 <= pad_ms < float('inf'):
+            raise ValueError('trim: pad_ms must be a finite number >= 0 (got %r)' % (pad_ms,))
+        pad = int(round(float(pad_ms) / 1000.0 * self.sr))
+        ops._trim_check(np.asarray(lens, np.int64), frame_length, hop_length, top_db, pad, 0)
+        return pad
+
+    def trim_batch(self, wavs, top_db=60., frame_length=2048, hop_length=512, pad_ms=0., with_intervals=False):
+        """Leading and trailing silence of a ragged batch cut on the device (one st_trim_silence call per 64 utterances, ONE host read):
+        wavs, a list of 1-D waveforms or a WaveBatch.  A frame of frame_length samples every hop_length is non-silent when its mean
+        square lies less than top_db dB under the loudest frame's; the kept span runs from the first to the last non-silent frame,
+        widened by pad_ms milliseconds on both sides.  -> (WaveBatch, bounds, n_short[, intervals]):
+            WaveBatch   the trimmed utterances INSIDE the packed buffer of the input (nothing is copied: moved offsets, shorter lens),
+                        sorted longest first again (stable), `.order[i]` the position in the caller's list of the i-th utterance
+            bounds      host int64 (B, 2): the kept samples [start, end) of utterance i of `wavs` (a list's position; a WaveBatch's row)
+            n_short     utterances whose kept span would hold n_fft // 2 samples or fewer -- the feature kernels refuse those --
+                        and are therefore returned untrimmed
+            intervals   (with_intervals) per utterance of `wavs`, an int64 (n, 2) array of its non-silent intervals in samples (no pad),
+                        what librosa.effects.split returns
+        An utterance with a non-finite sample is returned whole."""
+        wb = wavs if isinstance(wavs, WaveBatch) else WaveBatch(wavs)
+        pad = self._check_trim(top_db, frame_length, hop_length, pad_ms, lens=wb.lens)
+        dev = wb.device if wb.device is not None else _device()
+        B = len(wb.lens)
+        max_iv = (2 + int(wb.lens.max()) // hop_length) // 2 if with_intervals else 0      # runs of T frames: at most ceil(T / 2)
+        x = wb.packed(dev)
+        _, bounds, iv, n_iv = ops.trim_silence(x, wb.offsets, wb.lens, frame_length, hop_length, top_db, pad=pad, max_iv=max_iv)
+        if with_intervals:
+            host = torch.cat([bounds.reshape(-1), n_iv, iv.reshape(-1)]).cpu().numpy().astype(np.int64)
+            n_iv, iv = host[4 * B:5 * B], host[5 * B:].reshape(B, max_iv, 2)
+        else:
+            host = bounds.cpu().numpy().astype(np.int64).reshape(-1)
+        start, end = host[0:4 * B:4].copy(), host[1:4 * B:4].copy()
+        short = end - start <= self.n_fft // 2
+        start[short], end[short] = 0, wb.lens[short]
+        rows = np.argsort(-(end - start), kind='stable')
+        out = WaveBatch.window(x, (wb.offsets + start)[rows], (end - start)[rows])
+        out.order = np.asarray(wb.order)[rows]
+        given = isinstance(wavs, WaveBatch)
+        inv = np.arange(B) if given else np.argsort(np.asarray(wb.order), kind='stable')     # row of wb of utterance i of a list
+        res = (out, np.stack([start, end], 1)[inv], int(short.sum()))
+        if with_intervals:
+            res += ([iv[r, :n_iv[r]].copy() for r in inv],)
+        return res
+
+    def nonsilent_intervals(self, waveform, top_db=60., frame_length=2048, hop_length=512, channel=0):
+        """librosa.effects.split for one utterance: waveform (channels, samples) or (samples,) -> int64 (n, 2), the non-silent
+        intervals [start, end) of `channel` in samples (computed on the GPU)"""
+        x = torch.as_tensor(waveform)
+        x = x[channel] if x.dim() == 2 else x
+        return self.trim_batch([x], top_db, frame_length, hop_length, with_intervals=True)[3][0]
 
     def stretch_dims(self, rate):
         """(win, hop) of the augmented framing at stretch `rate`, exactly as src/audio.py:366-373"""

@@ -11,6 +11,8 @@ SOURCES = ['skinny.hip', 'skinny_packed.hip', 'attention.hip', 'gemm.hip', 'rnn.
            'attn_stats.hip']
 # the pitch kernels (st_f0_yin, st_f0_path_scores), listed apart: tests/test_synth_host.py pins the twenty entries above
 PITCH_SOURCES = ['f0.hip']
+# the silence-trimming kernels (st_trim_silence), listed apart for the same reason
+TRIM_SOURCES = ['trim.hip']
 
 
 def _hipcc():
@@ -35,7 +37,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES + PITCH_SOURCES:
+    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

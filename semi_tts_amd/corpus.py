@@ -209,15 +209,17 @@ class Sampler:
         N < B                  one batch of all rows
     A batch is an array of positions in the list `lengths` was taken from."""
 
-    def __init__(self, lengths, batch_size, bucketing=False, train=True, seed=0, rank=0, world=1):
+    def __init__(self, lengths, batch_size, bucketing=False, train=True, seed=0, rank=0, world=1, sharded=False):
+        """sharded: `lengths` are those of this rank's rows alone (a split trimmed after its upload): every row is taken, sorted as
+        above, and `rank` only seeds the generator."""
         lengths = np.asarray(lengths, np.int64)
         if batch_size < 1 or not 0 <= rank < world:
             raise ValueError('Sampler: batch size %d, rank %d of %d' % (batch_size, rank, world))
-        self.rows = np.argsort(-lengths, kind='stable')[rank::world]
+        self.rows = np.argsort(-lengths, kind='stable')[slice(None) if sharded else slice(rank, None, world)]
         if len(self.rows) == 0:
             raise ValueError('Sampler: no utterance for rank %d of %d (%d in the split)' % (rank, world, len(lengths)))
         self.B, self.train, self.bucketing = int(batch_size), bool(train), bool(bucketing) and bool(train)
-        self.seed, self.rank = int(seed), int(rank)
+        self.seed, self.rank, self.world = int(seed), int(rank), int(world)
         self.rewind()
 
     def n_batches(self):
@@ -260,6 +262,43 @@ def too_large(name, n_utt, n_samples, max_bytes):
             % (name, n_utt, n_samples, 4 * n_samples / 2.0 ** 30, 4 * n_samples, max_bytes / 2.0 ** 30, max_bytes))
 
 
+TRIM_CALL = 64                                       # utterances per trimming call of a split (ops.FEATURES_MAX_BATCH)
+
+
+def apply_bounds(rows, mine, offsets, lens, start, end, sampler, n_fft, hop, max_frames=None):
+    """What a split becomes once its rank's rows are trimmed: rows / offsets / lens of the whole split, `mine` the positions this
+    rank uploaded, start / end the kept samples [start, end) of each of them (st_trim_silence's bounds).  The rows of other ranks
+    leave the split (their trimmed lengths are not known here); offsets move by start, lens become end - start; `select` runs
+    again on the trimmed lengths (too short for the reflect padding, over max_frames), and the sampler is rebuilt over the
+    survivors with the batch size, flags, seed and rank of `sampler` (Sampler(sharded=True)).  The rows are COPIES whose .samples
+    is the trimmed count.  -> (rows, offsets, lens, sampler, counts of the dropped)"""
+    import copy
+    mine = np.asarray(mine, np.int64)
+    start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+    if start.shape != mine.shape or end.shape != mine.shape or (start < 0).any() or (end > lens[mine]).any() or (start > end).any():
+        raise ValueError('corpus: trim bounds outside their utterances')
+    cand = []
+    for i, a, b in zip(mine, start, end):
+        u = copy.copy(rows[int(i)])
+        u.samples = int(b - a)
+        cand.append((u, int(offsets[int(i)] + a)))
+    kept, counts = select([u for u, _ in cand], n_fft, hop, float('inf'), max_frames)
+    if not kept:
+        raise ValueError('corpus: no utterance left after trimming (%d trimmed)' % len(cand))
+    keep = set(id(u) for u in kept)
+    new_off = np.array([o for u, o in cand if id(u) in keep], np.int64)
+    new_lens = np.array([u.samples for u in kept], np.int64)
+    new_sampler = Sampler(new_lens, sampler.B, sampler.bucketing, sampler.train, sampler.seed, sampler.rank, sampler.world, sharded=True)
+    return kept, new_off, new_lens, new_sampler, counts
+
+
+def trim_report(name, sample_rate, before, after, n_before, counts):
+    """the one line per split that says what trimming did: seconds before / after, the share removed, the drops"""
+    return ('%s: trimmed %.1f s -> %.1f s (%.1f%% removed) | %d of %d utterances kept | dropped after trimming: %d too short, %d over the frame limit'
+            % (name, before / float(sample_rate), after / float(sample_rate), 100.0 * (before - after) / max(before, 1),
+               n_before - counts['short'] - counts['frames'], n_before, counts['short'], counts['frames']))
+
+
 class DeviceSplit:
     """One split of one rank on the device: every waveform read ONCE (AudioConverter's _read_pcm / resampling path) into one packed
     float32 buffer, with host offsets / lens.  A batch is not copied out of it: fetch() hands ops.audio_features the buffer with the
@@ -271,9 +310,15 @@ class DeviceSplit:
     utterances longest first (WaveBatch's stable order by samples; text and sid follow), mel / linear zero-padded to a multiple of r with
     at least one extra frame, aug_mel to its own longest with fresh SNR / stretch draws (a dev split, train=False, draws nothing: no
     noise, no stretch, seed 0), text padded with 0 to the batch's longest.
-    last_fetch = (file ids in batch order, seed, snr, stretch) of the latest batch."""
+    last_fetch = (file ids in batch order, seed, snr, stretch) of the latest batch.
 
-    def __init__(self, conv, rows, sampler, r, name='split', train=True, resample=False, max_bytes=None):
+    trim: a dict of AudioConverter.trim_batch's arguments (top_db, frame_length, hop_length, pad_ms).  Sharding and the size check
+    stay on the header lengths; after the upload the rank's rows are trimmed on the device in calls of 64 utterances with ONE host
+    read for the split, and the split becomes what apply_bounds says (rows / lens / offsets of this rank's survivors, a sampler over
+    the trimmed lengths; the trimmed samples stay resident, nothing is copied).  trim_report: the line that says what it did.
+    max_frames: the frame limit select() applied, applied again to the trimmed lengths."""
+
+    def __init__(self, conv, rows, sampler, r, name='split', train=True, resample=False, max_bytes=None, trim=None, max_frames=None):
         import torch
         from .audio import _device
         self.conv, self.rows, self.sampler, self.r, self.name, self.train = conv, list(rows), sampler, int(r), name, bool(train)
@@ -288,8 +333,28 @@ class DeviceSplit:
             max_bytes = torch.cuda.mem_get_info(dev)[0] // 2
         if self.nbytes > max_bytes:
             raise ValueError(too_large(name, len(mine), total, max_bytes))
+        if trim is not None:
+            pad = conv._check_trim(**trim)
         self.buffer = self._upload(mine, total, dev, resample)
         self.last_fetch = None
+        self.trim_report = None
+        if trim is not None:
+            self._trim(pad, max_frames, **trim)
+
+    def _trim(self, pad, max_frames, top_db=60., frame_length=2048, hop_length=512, pad_ms=0.):
+        import torch
+        from . import ops
+        mine = np.asarray(self.sampler.rows, np.int64)             # (longest first: a call's T_pad is its first utterance's)
+        parts = [ops.trim_silence(self.buffer, self.offsets[mine[i:i + TRIM_CALL]], self.lens[mine[i:i + TRIM_CALL]], frame_length, hop_length,
+                                  top_db, pad=pad)[1] for i in range(0, len(mine), TRIM_CALL)]
+        bounds = torch.cat(parts).cpu().numpy().astype(np.int64)   # the split's one host read
+        before = int(self.lens[mine].sum())
+        by_row = np.argsort(mine)                                  # (the surviving rows keep their listed order)
+        mine, bounds = mine[by_row], bounds[by_row]
+        self.rows, self.offsets, self.lens, self.sampler, counts = apply_bounds(
+            self.rows, mine, self.offsets, self.lens, bounds[:, 0], bounds[:, 1], self.sampler, self.conv.n_fft, self.conv.hop_length, max_frames)
+        self.trim_counts = counts
+        self.trim_report = trim_report(self.name, self.conv.sr, before, int(self.lens.sum()), len(mine), counts)
 
     def _upload(self, mine, total, dev, resample):
         """the rank's utterances -> one device buffer.  Files at the converter's rate are laid out on the host and go up in ONE copy; with
@@ -358,13 +423,16 @@ class DeviceSplit:
 
 
 def load_splits(corpus_cfg, conv, r, splits, batch_sizes, seed=0, rank=0, world=1, resample=False, max_frames=None, max_gb=None,
-                verbose=print):
+                verbose=print, trim=None):
     """Corpus + one DeviceSplit per name in `splits` (of 'paired', 'unpaired', 'dev').  batch_sizes: dict split -> B.  Everything the
-    tables, the headers and the limits can refuse is raised for EVERY split before the first device allocation.
+    tables, the headers and the limits can refuse is raised for EVERY split before the first device allocation.  trim: every split
+    (dev included) is trimmed with these settings after its upload (DeviceSplit), one report line per split.
     -> (Corpus, dict split -> DeviceSplit)"""
     from . import ops
     corpus = Corpus(**corpus_cfg)
     conv._check([], [])                                        # (the framing itself: n_fft, hop, win)
+    if trim is not None:
+        conv._check_trim(**trim)
     plan = []
     for s in splits:
         rows = corpus.measure(s, conv.sr, resample)
@@ -381,5 +449,8 @@ def load_splits(corpus_cfg, conv, r, splits, batch_sizes, seed=0, rank=0, world=
             raise ValueError(too_large(s, len(sampler.rows), n, max_bytes))
     sets = {}
     for s, kept, sampler, train in plan:
-        sets[s] = DeviceSplit(conv, kept, sampler, r, name=s, train=train, resample=resample, max_bytes=max_bytes)
+        sets[s] = DeviceSplit(conv, kept, sampler, r, name=s, train=train, resample=resample, max_bytes=max_bytes, trim=trim,
+                              max_frames=max_frames)
+        if trim is not None:
+            verbose(sets[s].trim_report)
     return corpus, sets

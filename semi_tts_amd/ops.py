@@ -2302,3 +2302,80 @@ def f0_path_scores(f0_x, f0_y, path, path_len):
     check(lib.st_f0_path_scores(_p(f0_x), strides[0], Tx, _p(f0_y), strides[1], Ty, _p(path, torch.int32), _p(path_len, torch.int32), B,
                                 Tx + Ty - 1, _p(counts, torch.int32), _p(sums), stream_handle()), 'st_f0_path_scores')
     return counts, sums
+
+
+# --------------------------------------------------------------------------------------------- silence trimming (st_trim_silence)
+TRIM_MAX_FRAME_LENGTH = 8192         # st_trim_silence's limit
+TRIM_RUN, TRIM_MAX_SPAN = 16, 12288  # frames a workgroup takes from one staged span, and the samples such a span may hold (trim.hip)
+TRIM_CHUNK = 256                     # frames per step of the decision launch: the tests straddle it
+
+
+def trim_run_length(frame_length, hop):
+    """the consecutive frames one st_trim_silence workgroup takes at this framing (st_trim_run_length): the tests straddle it"""
+    r = TRIM_RUN
+    while r > 1 and (r - 1) * int(hop) + int(frame_length) > TRIM_MAX_SPAN:
+        r -= 1
+    return r
+
+
+def trim_ratio(top_db):
+    """the threshold ratio of st_trim_silence: 10^(-top_db / 10) in double, rounded once to float32"""
+    return float(np.float32(10.0 ** (-float(top_db) / 10.0)))
+
+
+def _trim_check(lens, frame_length, hop, top_db, pad=0, max_iv=0):
+    """every refusal of st_trim_silence that does not need the buffers, raised before any device is touched"""
+    for name, v in (('frame_length', frame_length), ('hop', hop), ('pad', pad), ('max_iv', max_iv)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError('trim_silence: %s must be an integer (got %r)' % (name, v))
+    if not 1 <= hop <= frame_length <= TRIM_MAX_FRAME_LENGTH:
+        raise ValueError('trim_silence: needs 1 <= hop <= frame_length <= %d (hop %d, frame_length %d)' % (TRIM_MAX_FRAME_LENGTH, hop, frame_length))
+    if isinstance(top_db, bool) or not isinstance(top_db, (int, float, np.integer, np.floating)) or not np.isfinite(top_db):
+        raise ValueError('trim_silence: top_db must be a finite number (got %r)' % (top_db,))
+    if not 0.0 < trim_ratio(top_db) < 1.0:
+        raise ValueError('trim_silence: top_db %r gives the ratio %r; it must lie strictly inside (0, 1) in float32'
+                         % (top_db, trim_ratio(top_db)))
+    if not 0 <= pad < 2 ** 31:
+        raise ValueError('trim_silence: pad %d outside [0, 2^31)' % pad)
+    if not 0 <= max_iv < 2 ** 30:
+        raise ValueError('trim_silence: max_iv %d outside [0, 2^30)' % max_iv)
+    lens = np.asarray(lens)
+    if lens.ndim != 1 or lens.shape[0] < 1 or lens.dtype.kind not in 'iu' or (lens < 1).any() or (lens >= 2 ** 31).any():
+        raise ValueError('trim_silence: lens must be B >= 1 integers in [1, 2^31) (got %s)' % (lens.tolist(),))
+
+
+def trim_silence(x, off, lens, frame_length, hop, top_db, pad=0, max_iv=0, T_pad=None, energy=None):
+    """st_trim_silence on a ragged batch packed as for audio_features: x the packed float32 waveforms on the device, utterance b =
+    x[off[b]:off[b] + lens[b]] (the offsets need not be cumulative).  -> device tensors (energy (B, T_pad) float32, 0 on the rows past
+    1 + lens[b] // hop; bounds (B, 4) int32 = (start, end, non-silent frames, flags); intervals (B, max_iv, 2) int32 and n_iv (B,)
+    int32, or None, None with max_iv = 0).  T_pad None: the longest utterance's frames.  Batches above FEATURES_MAX_BATCH are
+    issued in chunks of it.  energy: a contiguous (B, T_pad) float32 tensor on x's device to write the energies into (default: a new one).
+    Anything the kernel would refuse raises ValueError before the device is touched."""
+    _trim_check(lens, frame_length, hop, top_db, pad, max_iv)
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('trim_silence: x must be a packed 1-D contiguous float32 GPU tensor (got %s)'
+                         % ('%s %s on %s' % (tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x).__name__))
+    B = len(lens)
+    off, lens = _host_off_lens(off, lens)
+    if off.shape != (B,) or (off < 0).any() or (off + lens > x.numel()).any():
+        raise ValueError('trim_silence: an utterance lies outside the %d packed samples (off %s, lens %s)' % (x.numel(), off.tolist(), lens.tolist()))
+    frames = 1 + int(lens.max()) // hop
+    T_pad = frames if T_pad is None else int(T_pad)
+    if T_pad < frames:
+        raise ValueError('trim_silence: T_pad %d below the %d frames of the longest utterance' % (T_pad, frames))
+    lib = _lib.load()
+    dev = x.device
+    if energy is None:
+        energy = torch.empty(B, T_pad, device=dev, dtype=torch.float32)
+    elif not (torch.is_tensor(energy) and energy.shape == (B, T_pad) and energy.dtype == torch.float32 and energy.is_contiguous() and energy.device == dev):
+        raise ValueError('trim_silence: energy must be a contiguous (%d, %d) float32 tensor on %s' % (B, T_pad, dev))
+    bounds = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    iv = torch.empty(B, max_iv, 2, device=dev, dtype=torch.int32) if max_iv else None
+    n_iv = torch.empty(B, device=dev, dtype=torch.int32) if max_iv else None
+    ratio = trim_ratio(top_db)
+    w = _lib.StWaveBatch(x=_p(x), n_samples=x.numel())
+    for b0, nb in _chunks(B):
+        check(lib.st_trim_silence(_wave_chunk(w, off, lens, b0, nb), int(frame_length), int(hop), ratio, int(pad), int(max_iv), _p(energy[b0:]),
+                                  T_pad, _p(bounds[b0:], torch.int32), _p(iv[b0:], torch.int32) if max_iv else None,
+                                  _p(n_iv[b0:], torch.int32) if max_iv else None, stream_handle()), 'st_trim_silence')
+    return energy, bounds, iv, n_iv

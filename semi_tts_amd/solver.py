@@ -294,6 +294,83 @@ class Resampler:
         return n
 
 
+def trim_args(paras):
+    """the `trim` argument of AudioConverter.load_batch / corpus.load_splits from --trim-silence and its options; None without the flag"""
+    if not getattr(paras, 'trim_silence', False):
+        return None
+    return dict(top_db=float(getattr(paras, 'trim_top_db', 60.0)), frame_length=int(getattr(paras, 'trim_frame_length', 2048)),
+                hop_length=int(getattr(paras, 'trim_hop', 512)), pad_ms=float(getattr(paras, 'trim_pad_ms', 0.0)))
+
+
+class Trimmer:
+    """main.py --trim-wav-dir DIR --trim-out DIR2 --config CFG [--trim-top-db 60 --trim-frame-length 2048 --trim-hop 512 --trim-pad-ms 0]:
+    channel 0 of every .wav of DIR (sorted by name, batches of --batch-size, at data.audio.sample_rate) trimmed on the GPU
+    (AudioConverter.trim_batch) and its kept span written to DIR2/<same name> as the exact int16 samples of the file -- the bounds come
+    from the device, the samples never leave the host as floats.  DIR2/trim.csv: file, samples, start, end, seconds, kept_seconds,
+    n_intervals (the non-silent intervals of librosa.effects.split inside the file).  A file whose kept span would hold n_fft // 2 samples
+    or fewer is written whole (trim_batch's rule).  No checkpoint, no model.  Every header is read in load_data: an unreadable file or a
+    foreign rate stops the run before anything is written."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.trim = dict(top_db=float(paras.trim_top_db), frame_length=int(paras.trim_frame_length), hop_length=int(paras.trim_hop),
+                         pad_ms=float(paras.trim_pad_ms))
+
+    def load_data(self):
+        import wave
+        from .audio import load_audio_transform
+        self.wav_dir, self.out_dir = self.paras.trim_wav_dir, self.paras.trim_out
+        if os.path.realpath(self.wav_dir) == os.path.realpath(self.out_dir):
+            raise ValueError('--trim-out %s is the directory --trim-wav-dir reads' % self.out_dir)
+        self.files = sorted(f for f in os.listdir(self.wav_dir) if f.lower().endswith('.wav'))
+        if not self.files:
+            raise ValueError('--trim-wav-dir %s: no .wav files' % self.wav_dir)
+        self.audio_converter = conv = load_audio_transform(**self.config['data']['audio'])
+        conv._check_trim(**self.trim)
+        for f in self.files:
+            with wave.open(os.path.join(self.wav_dir, f), 'rb') as w:
+                if w.getsampwidth() != 2:
+                    raise ValueError('--trim-wav-dir: %s is %d-bit; only 16-bit PCM is read' % (f, 8 * w.getsampwidth()))
+                if w.getnframes() < 1:
+                    raise ValueError('--trim-wav-dir: %s holds no samples' % f)
+                if w.getframerate() != conv.sr:
+                    raise ValueError('Sample rate mismatch. Expected %d but get %d (%s)' % (conv.sr, w.getframerate(), f))
+        return self
+
+    def set_model(self):
+        return self
+
+    def exec(self):
+        import csv
+        import wave
+        from .audio import _read_pcm
+        conv = self.audio_converter
+        os.makedirs(self.out_dir, exist_ok=True)
+        B = int(self.paras.batch_size)
+        t0, rows = time.perf_counter(), []
+        for i in range(0, len(self.files), B):
+            names = self.files[i:i + B]
+            pcm = [_read_pcm(os.path.join(self.wav_dir, f))[0][:, 0] for f in names]
+            waves = [torch.from_numpy(p.astype(np.float32) / 32768.0) for p in pcm]
+            _, bounds, _, intervals = conv.trim_batch(waves, with_intervals=True, **self.trim)
+            for f, p, (a, b), iv in zip(names, pcm, bounds.tolist(), intervals):
+                with wave.open(os.path.join(self.out_dir, f), 'wb') as w:
+                    w.setnchannels(1)
+                    w.setsampwidth(2)
+                    w.setframerate(conv.sr)
+                    w.writeframes(np.ascontiguousarray(p[a:b], dtype='<i2').tobytes())
+                rows.append([f, len(p), a, b, '%.6f' % (len(p) / conv.sr), '%.6f' % ((b - a) / conv.sr), len(iv)])
+        with open(os.path.join(self.out_dir, 'trim.csv'), 'w', newline='') as fh:
+            out = csv.writer(fh)
+            out.writerow(['file', 'samples', 'start', 'end', 'seconds', 'kept_seconds', 'n_intervals'])
+            out.writerows(rows)
+        if getattr(self.paras, 'verbose', True):
+            total, kept = sum(r[1] for r in rows), sum(r[3] - r[2] for r in rows)
+            print('[INFO]', 'Trimmed %d files into %s: %.1f s -> %.1f s, %.2f s' % (len(rows), self.out_dir, total / conv.sr, kept / conv.sr,
+                                                                                  time.perf_counter() - t0))
+        return len(rows)
+
+
 class FeatureWriter:
     """main.py --feat-wav-dir DIR --feat mfcc|mel|linear [--segment-file FILE --min-segment-len N]: channel 0 of the .wav files of DIR,
     sorted by name, in batches of --batch-size -> AudioConverter.extract_mfcc_batch (mfcc) or the clean extract_batch (mel, linear) ->
@@ -340,7 +417,7 @@ class FeatureWriter:
         """the files `names` of the .wav directory -> (features (B, T_pad, D) on the device in the sorted order, frames per row, order)"""
         from .audio import SNR_OFF
         conv = self.audio_converter
-        wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names])
+        wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names], trim=trim_args(self.paras))
         if self.feat == 'mfcc':
             return conv.extract_mfcc_batch(wb), 1 + wb.lens // conv.hop_length_mfcc, wb.order
         if self.feat == 'f0':
@@ -471,8 +548,8 @@ class McdScorer:
         host read"""
         from .metrics import f0_scores, mcd
         conv = self.audio_converter
-        ws = conv.load_batch([os.path.join(self.syn_dir, f) for f, _, _ in pairs])
-        wr = conv.load_batch([os.path.join(self.ref_dir, r) for _, _, r in pairs])
+        ws = conv.load_batch([os.path.join(self.syn_dir, f) for f, _, _ in pairs], trim=trim_args(self.paras))
+        wr = conv.load_batch([os.path.join(self.ref_dir, r) for _, _, r in pairs], trim=trim_args(self.paras))
         fs, fr = 1 + ws.lens // conv.hop_length_mfcc, 1 + wr.lens // conv.hop_length_mfcc
         cs, cr = conv.extract_mfcc_batch(ws), conv.extract_mfcc_batch(wr)
         # both batches are sorted by length: bring the recordings into the row order of the synthesised side
@@ -599,7 +676,7 @@ class Transcriber(BaseSolver):
         """channel 0 of the files `names` of the .wav directory as one WaveBatch on the device (AudioConverter.load_batch); with
         --resample a file at another rate is converted on the GPU, without it it raises"""
         return self.audio_converter.load_batch([os.path.join(self.wav_dir, f) for f in names],
-                                               resample=bool(getattr(self.paras, 'resample', False)))
+                                               resample=bool(getattr(self.paras, 'resample', False)), trim=trim_args(self.paras))
 
     def transcribe_batch(self, waves):
         """waves: 1-D waveforms on the device (or a WaveBatch) -> (hyp, hyp_len, score) as numpy arrays in the order of `waves`"""
@@ -918,7 +995,8 @@ class TtsTrainer(BaseSolver):
         self.corpus, self.corpus_sets = load_splits(
             self.config['data']['corpus'], self.audio_converter, self.r, splits, batch_sizes, seed=int(getattr(pa, 'seed', 0)),
             rank=int(os.environ.get('RANK', 0)), world=int(os.environ.get('WORLD_SIZE', 1)), resample=bool(getattr(pa, 'resample', False)),
-            max_frames=getattr(pa, 'max_frames', None), max_gb=getattr(pa, 'corpus_max_gb', None), verbose=self.verbose)
+            max_frames=getattr(pa, 'max_frames', None), max_gb=getattr(pa, 'corpus_max_gb', None), verbose=self.verbose,
+            trim=trim_args(pa))
         self.vocab_size, self.n_spkr = self.corpus.vocab_size, self.corpus.n_spkr
         return self.corpus_sets
 
@@ -1507,7 +1585,8 @@ class VqvaeTrainer(TtsTrainer):
         if self.audio_converter.n_mels != self.n_mels:
             raise ValueError('--unpair-wav-dir: data.audio has %d mels, the model %d' % (self.audio_converter.n_mels, self.n_mels))
         paths = [os.path.join(wav_dir, f) for f in files]
-        self.unpair_waves = [self.audio_converter.load_batch(paths[i:i + Bu], resample=bool(getattr(self.paras, 'resample', False)))
+        self.unpair_waves = [self.audio_converter.load_batch(paths[i:i + Bu], resample=bool(getattr(self.paras, 'resample', False)),
+                                                             trim=trim_args(self.paras))
                              for i in range(0, len(paths), Bu)]
         self.unpair_set = [mk(len(wb.lens), uframes, 500000 + 1000 * rank + i + seed) for i, wb in enumerate(self.unpair_waves)]
 
