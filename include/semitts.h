@@ -1502,6 +1502,31 @@ int st_trim_silence(const st_wave_batch* w, int frame_length, int hop, float rat
                     float* energy /* (B, T_pad) */, int T_pad, int32_t* bounds /* (B, 4) */,
                     int32_t* intervals /* (B, max_iv, 2) or NULL */, int32_t* n_iv /* (B) or NULL */, void* stream);
 
+/* ------------------------------------------------------------------ transcript scoring (Levenshtein alignment with its trace-back)
+ * Not a step of the reference (its cal_per returns a distance only).  hyp (B, N, Lh) int64 holds N >= 1 transcripts per utterance, already
+ * collapsed (st_ctc_beam_search's paths), of hyp_len (B, N) tokens; ref (B, Lr) int64 of ref_len (B) tokens (NULL: all Lr).  Lengths
+ * are clamped into [0, L] by the kernel.  The ignored ids (at most 64) are dropped from both sides wherever they sit, as in
+ * st_hyp_edit_distance; r[0 .. n) is the filtered reference and h[0 .. m) the filtered hypothesis of pair p = b N + k.
+ * Definition.  D(i, 0) = i, D(0, j) = j, D(i, j) = min(D(i-1, j-1) + [r_i != h_j], D(i-1, j) + 1, D(i, j-1) + 1).  The alignment is
+ * the trace-back from (n, m): at (i, j) with i, j > 0 the diagonal if D(i-1, j-1) + [r_i != h_j] = D(i, j), else the deletion
+ * (i-1, j) if D(i-1, j) + 1 = D(i, j), else the insertion (i, j-1); on the border the one move that exists.  This fixes one alignment.
+ * counts[p] = (correct, substitutions, deletions, insertions): dist = S + D + I, n = C + S + D, m = C + S + I.  ali_len[p] =
+ * C + S + D + I.  ali[p] (when not NULL): the aligned pairs in forward order as (reference token, hypothesis token), -1 for a gap
+ * (tokens as their low 32 bits), (-1, -1) past ali_len.  confusion (when not NULL) is ADDED into, never zeroed: path k = 0 of each
+ * utterance adds 1 to [r, h] for a correct or substituted pair, to [r, V] for a deletion and to [V, h] for an insertion; a pair
+ * with a token outside [0, V) is aligned and counted like any other but touches no cell.  The additions are integer atomics, exact
+ * in any order.  counts and ali depend on their pair alone and are bitwise repeatable.  An empty side gives all deletions or all
+ * insertions (all zeros when both are empty).
+ * ws: st_edit_align_workspace_bytes(B N, Lr, Lh) bytes, no initialisation needed -- 0 (ws may be NULL) when the 2-bit moves of a
+ * pair fit the LDS of a CU beside its tokens (Lh <= 256, or Lr <= 563 at Lh = 1024).
+ * One launch, one wave per pair, no host read.  Limits (-22 past them, before anything is launched): B, N >= 1,
+ * 1 <= Lh, Lr <= 1024, 1 <= V <= 1024, 0 <= n_ignore <= 64. */
+size_t st_edit_align_workspace_bytes(int pairs, int Lr, int Lh);
+int st_edit_align(const int64_t* hyp /* (B, N, Lh) */, const int32_t* hyp_len /* (B, N) */, int B, int N, int Lh,
+                  const int64_t* ref /* (B, Lr) */, const int32_t* ref_len /* (B) or NULL */, int Lr, const int32_t* ignore, int n_ignore,
+                  int V, int32_t* counts /* (B, N, 4) */, int32_t* ali_len /* (B, N) */, int32_t* ali /* (B, N, Lr + Lh, 2) or NULL */,
+                  int32_t* confusion /* (V + 1, V + 1) or NULL */, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

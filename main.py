@@ -29,6 +29,7 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --synth-phn-dir DIR [--load ckpt.pth --vocab FILE --synth-sid 0 --gen-wav --batch-size 8]
     python main.py --config config/supervised.yaml --trim-wav-dir DIR --trim-out DIR2 [--trim-top-db 60 --trim-frame-length 2048 --trim-hop 512]
     python main.py --config config/semi-multi-spkr-paired-data.yaml --corpus --trim-silence [--trim-pad-ms 0]
+    python main.py --score-phn-dir HYP --score-ref-dir REF [--vocab FILE --score-ignore 0,1,2 --score-nbest --score-ali --batch-size 64]
 `--corpus` trains on the reference's corpus layout (semi_tts_amd/corpus.py: partition table, map table, speaker map, vocabulary file and
 <path>/<speaker>/<id>.wav, src/data.py + corpus/vctk.py + src/text.py): each split of the rank's shard is read once and stays on the device as
 one packed buffer, every fetch extracts mel / augmented mel / linear from it on the GPU, `--dev-batches K` (-1: all) validates on the real dev
@@ -62,6 +63,10 @@ pitch error of every pair along the warp of its MCD (semi_tts_amd.metrics.f0_sco
 directory -- what `--transcribe-wav-dir` writes, as it is -- and finds where each utterance ends from its attention on the GPU
 (solver.Synthesiser, semi_tts_amd.metrics.attention_endpoints): <name>-mel.npy, -spec.npy, -align.npy, -dur.npy cut at the end, with
 `--gen-wav` <name>-pred.wav, and synth.csv with the alignment diagnostics of every utterance.
+`--score-phn-dir HYP --score-ref-dir REF` (not a mode of the reference, whose cal_per returns one rate) scores .phn transcripts -- what
+`--transcribe-wav-dir` writes -- against reference transcripts by Levenshtein alignment with its trace-back on the GPU (solver.PhnScorer,
+semi_tts_amd.metrics.align_transcripts): per.csv with correct / substituted / deleted / inserted phones per file, confusion.npy,
+confusions.csv, phones.csv, with `--score-ali` <key>.ops per file and with `--score-nbest` the lowest error over the paths of a file.
 """
 import argparse
 import os
@@ -191,6 +196,17 @@ parser.add_argument('--trim-wav-dir', default=None, type=str, help='cut the lead
                     'name, batched by --batch-size, at data.audio.sample_rate of --config) and write the kept span of channel 0 -- the exact 16-bit '
                     'samples -- to --trim-out/<same name>, with --trim-out/trim.csv (file, samples, start, end, seconds, kept_seconds, n_intervals); no model')
 parser.add_argument('--trim-out', default=None, type=str, help='--trim-wav-dir: the directory to write (not the one read)')
+parser.add_argument('--score-phn-dir', default=None, type=str, help='score the .phn transcripts of this directory (sorted by name, batched by '
+                    '--batch-size; ids or --vocab symbols, the files of --transcribe-wav-dir as they are) against the references of '
+                    '--score-ref-dir by Levenshtein alignment on the GPU: <logdir>/<name>/per.csv (file,ref_tokens,hyp_tokens,correct,sub,del,ins,per), '
+                    'confusion.npy, confusions.csv, phones.csv; no config, no checkpoint, no model')
+parser.add_argument('--score-ref-dir', default=None, type=str, help='--score-phn-dir: the directory of the reference transcripts, <key>.phn for every '
+                    'scored file (key: its name up to the first ".", without one trailing "-pred")')
+parser.add_argument('--score-ignore', default=None, type=str, help='--score-phn-dir: comma-separated ids dropped from both sides (default 0,1,2: the '
+                    'three special tokens; 0,1,2,42 reproduces the filter of cal_per, which also drops the last phone of the reference\'s vocabulary)')
+parser.add_argument('--score-nbest', action='store_true', help='--score-phn-dir: score every line of a hypothesis file (the paths of --top-paths) and add '
+                    'nbest_per,nbest_path to per.csv: the lowest error over the paths and the first path that attains it')
+parser.add_argument('--score-ali', action='store_true', help='--score-phn-dir: also write the alignment of every file as <key>.ops (REF / HYP / OP lines)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -373,6 +389,23 @@ def parse_args(argv=None):
     paras.trim_pad_ms = 0.0 if paras.trim_pad_ms is None else paras.trim_pad_ms
     if not 0.0 < paras.trim_top_db < float('inf') or not 1 <= paras.trim_hop <= paras.trim_frame_length <= 8192 or not 0.0 <= paras.trim_pad_ms < float('inf'):
         parser.error('--trim-top-db must be finite and positive, 1 <= --trim-hop <= --trim-frame-length <= 8192 and --trim-pad-ms finite and >= 0')
+    if paras.score_phn_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir', 'trim_silence', 'corpus'):
+            if getattr(paras, flag):
+                parser.error('--score-phn-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches != 0:
+            parser.error('--score-phn-dir does not combine with --dev-batches')
+        if paras.score_ref_dir is None:
+            parser.error('--score-phn-dir needs --score-ref-dir DIR (the reference transcripts)')
+        try:
+            paras.score_ignore = tuple(int(t) for t in (paras.score_ignore if paras.score_ignore is not None else '0,1,2').split(',') if t.strip())
+        except ValueError:
+            parser.error('--score-ignore takes comma-separated integer ids (got %r)' % paras.score_ignore)
+        if len(paras.score_ignore) > 64 or any(not 0 <= t < 2 ** 31 for t in paras.score_ignore):
+            parser.error('--score-ignore takes at most 64 ids in [0, 2^31)')
+    elif paras.score_ref_dir is not None or paras.score_ignore is not None or paras.score_nbest or paras.score_ali:
+        parser.error('--score-ref-dir, --score-ignore, --score-nbest and --score-ali belong to --score-phn-dir; they need that flag')
     if paras.gen_wav_feat != 'linear' and not ((paras.gen_specgram or paras.synth_phn_dir is not None) and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
@@ -428,6 +461,9 @@ def main(argv=None):
     if paras.resample_wav_dir is not None and paras.config is None:      # (the rate was given: this mode reads nothing else of a config)
         config = None
         paras.batch_size = paras.batch_size or 8
+    elif paras.score_phn_dir is not None:                                # (transcripts against transcripts: no config is read)
+        config = None
+        paras.batch_size = paras.batch_size or 64
     else:
         config = yaml.load(open(paras.config, 'r'), Loader=yaml.FullLoader)
     if paras.batch_size is None:
@@ -456,6 +492,9 @@ def main(argv=None):
         mode = 'test'
     elif paras.mcd_wav_dir is not None:
         from semi_tts_amd.solver import McdScorer as Solver
+        mode = 'test'
+    elif paras.score_phn_dir is not None:
+        from semi_tts_amd.solver import PhnScorer as Solver
         mode = 'test'
     elif paras.synth_phn_dir is not None:
         from semi_tts_amd.solver import Synthesiser as Solver

@@ -423,6 +423,8 @@ SIGNATURES = {
     'st_f0_path_scores': [P, C.c_long, I, P, C.c_long, I, P, P, I, I, P, P, P],
     'st_trim_run_length': [I, I],
     'st_trim_silence': [C.POINTER(StWaveBatch), I, I, F, I, I, P, I, P, P, P, P],
+    'st_edit_align_workspace_bytes': [I, I, I],
+    'st_edit_align': [P, P, I, I, I, P, P, I, P, I, I, P, P, P, P, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,
@@ -430,7 +432,7 @@ _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t,
              'st_bn_bank_workspace_floats': C.c_size_t, 'st_istft_workspace_floats': C.c_size_t,
              'st_gl_batch_workspace_floats': C.c_size_t,
              'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t,
-             'st_dtw_workspace_bytes': C.c_size_t}
+             'st_dtw_workspace_bytes': C.c_size_t, 'st_edit_align_workspace_bytes': C.c_size_t}
 
 _lib = None
 

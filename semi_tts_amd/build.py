@@ -13,6 +13,8 @@ SOURCES = ['skinny.hip', 'skinny_packed.hip', 'attention.hip', 'gemm.hip', 'rnn.
 PITCH_SOURCES = ['f0.hip']
 # the silence-trimming kernels (st_trim_silence), listed apart for the same reason
 TRIM_SOURCES = ['trim.hip']
+# the transcript-scoring kernel (st_edit_align), listed apart for the same reason
+SCORE_SOURCES = ['edit_align.hip']
 
 
 def _hipcc():
@@ -37,7 +39,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES:
+    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

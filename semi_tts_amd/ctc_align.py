@@ -53,6 +53,36 @@ def read_phn(path, vocab=None):
     return ids
 
 
+def read_phn_paths(path, vocab=None):
+    """every transcript of a .phn file, in order, as a list of lists of ids: one per non-empty line, read as read_phn reads the first
+    (line k is path k of --transcribe-wav-dir --top-paths N).  A line that holds a score and no tokens is an empty transcript; a file
+    without a non-empty line gives one empty transcript.  The errors of read_phn, naming the file."""
+    try:
+        with open(path) as f:
+            lines = f.read().splitlines()
+    except (OSError, UnicodeDecodeError) as e:
+        raise ValueError('%s: cannot read the transcript (%s)' % (path, e))
+    index = {s: i for i, s in reversed(list(enumerate(vocab)))} if vocab is not None else {}
+    paths = []
+    for line in lines:
+        if line.strip(' \r\n') == '':
+            continue
+        if '\t' in line:
+            line = line.rsplit('\t', 1)[1]
+        ids = []
+        for tok in line.split():
+            if tok in index:
+                ids.append(index[tok])
+            elif tok.isascii() and tok.isdigit():
+                ids.append(int(tok))
+            else:
+                raise ValueError('%s: unknown symbol %r (not in the vocabulary, not a decimal id)' % (path, tok))
+        if len(ids) > MAX_TOKENS:
+            raise ValueError('%s: %d tokens, at most %d are read' % (path, len(ids), MAX_TOKENS))
+        paths.append(ids)
+    return paths or [[]]
+
+
 def _symbol(i, vocab):
     return vocab[i] if vocab is not None and 0 <= i < len(vocab) else str(i)
 

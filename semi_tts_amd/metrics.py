@@ -165,3 +165,66 @@ def f0_scores(f0_x, f0_y, path, path_len):
             'mean_cents': torch.where(some, sums[:, 1] / both.clamp_min(1.0), nan),
             'vuv_error': torch.where(any_pair, n_vuv.to(torch.float32) / pairs.clamp_min(1.0), nan),
             'gross_error': torch.where(some, n_gross.to(torch.float32) / both.clamp_min(1.0), nan)}
+
+
+TranscriptAlignment = collections.namedtuple('TranscriptAlignment', 'correct sub dele ins dist ref_len hyp_len ali_len ali confusion')
+
+
+def align_transcripts(hyp, hyp_len, ref, ref_len=None, ignore=IGNORE_INDICES, n_classes=None, confusion=None, want_ali=True):
+    """Phone-error breakdown of transcripts on one GPU: hyp (B, Lh) int64, or (B, N, Lh) for N paths per utterance (already collapsed,
+    as ctc_decode.beam_search gives them), of hyp_len (B,) / (B, N) tokens, against ref (B, Lr) int64 of ref_len (B,) tokens (None: all
+    Lr).  A host sequence of lengths is checked against [0, L], a device tensor is clamped by the kernel.  The ids in `ignore` are
+    dropped from both sides wherever they sit (cal_per's filter by default); r[0 .. n) is the filtered reference and h[0 .. m) the
+    filtered hypothesis.
+
+    Definition.  D(i, 0) = i, D(0, j) = j, D(i, j) = min(D(i-1, j-1) + [r_i != h_j], D(i-1, j) + 1, D(i, j-1) + 1).  The alignment is
+    the trace-back from (n, m): at (i, j) with i, j > 0 the diagonal if D(i-1, j-1) + [r_i != h_j] = D(i, j), otherwise the deletion
+    (i-1, j) if D(i-1, j) + 1 = D(i, j), otherwise the insertion (i, j-1); on the border only one move exists.  This is the tie order
+    of `dtw` -- diagonal, then (i-1, j), then (i, j-1) -- and fixes one alignment among the optimal ones.
+
+    -> TranscriptAlignment of device tensors, (B,) or (B, N) like hyp_len: correct, sub, dele, ins (int32; dist = sub + dele + ins,
+    ref_len = correct + sub + dele = n, hyp_len = correct + sub + ins = m, ali_len = their sum); ali (..., Lr + Lh, 2) int32, the
+    aligned pairs in forward order as (reference token, hypothesis token) with -1 for a gap and (-1, -1) past ali_len (None when
+    want_ali is false); confusion (V + 1, V + 1) int32 or None.
+    The confusion matrix counts path 0 of every utterance: [r, h] a correct or substituted pair, [r, V] a deletion, [V, h] an
+    insertion; a pair with a token outside [0, V) is counted in correct / sub / dele / ins but touches no cell.  With `confusion`
+    given, that tensor is added into and returned (V = its size - 1), so a corpus keeps one matrix on the device and reads it once;
+    with n_classes = V alone a zeroed matrix is made; with neither, none is kept.
+    One launch (st_edit_align), no host read; integers only, bitwise repeatable; bad arguments raise ValueError before the device is
+    touched."""
+    if not torch.is_tensor(hyp) or hyp.dim() not in (2, 3):
+        raise ValueError('align_transcripts: hyp must be a (B, Lh) or (B, N, Lh) tensor (got %s)'
+                         % (tuple(hyp.shape) if torch.is_tensor(hyp) else type(hyp).__name__))
+    single = hyp.dim() == 2
+    if single:
+        hyp = hyp.unsqueeze(1)
+        if torch.is_tensor(hyp_len):
+            hyp_len = hyp_len.unsqueeze(1) if hyp_len.dim() == 1 else hyp_len
+        else:
+            hyp_len = [[v] for v in hyp_len]
+    if confusion is not None and n_classes is None and torch.is_tensor(confusion) and confusion.dim() == 2:
+        n_classes = confusion.shape[0] - 1
+    if confusion is None and n_classes is not None:
+        confusion = True            # (a zeroed matrix, made once the arguments have passed their checks)
+    counts, ali_len, ali, confusion = ops.edit_align(hyp, hyp_len, ref, ref_len, ignore, 1 if n_classes is None else n_classes, confusion,
+                                                     want_ali)
+    if single:
+        counts, ali_len = counts[:, 0], ali_len[:, 0]
+        ali = None if ali is None else ali[:, 0]
+    c, s, d, i = counts.unbind(-1)
+    return TranscriptAlignment(c, s, d, i, s + d + i, c + s + d, c + s + i, ali_len, ali, confusion)
+
+
+NBest = collections.namedtuple('NBest', 'dist path')
+
+
+def nbest_per(dist):
+    """The n-best "oracle" of align_transcripts(...).dist (B, N): per utterance the lowest distance over the N paths and the lowest
+    path index k that attains it -> NBest(dist (B,) int32, path (B,) int64), device tensors, no host read."""
+    if not torch.is_tensor(dist) or dist.dim() != 2 or dist.shape[1] < 1:
+        raise ValueError('nbest_per: dist must be a (B, N) tensor with N >= 1')
+    best = dist.min(dim=1).values
+    N = dist.shape[1]
+    k = torch.arange(N, device=dist.device).expand_as(dist)
+    path = torch.where(dist == best.unsqueeze(1), k, torch.full_like(k, N)).min(dim=1).values
+    return NBest(best, path)

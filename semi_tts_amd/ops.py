@@ -1236,6 +1236,88 @@ def hyp_edit_distance(hyp, hyp_len, text, ignore):
     return dist, ref_len
 
 
+EA_MAX_L, EA_MAX_V, EA_MAX_IGNORE = 1024, 1024, 64          # st_edit_align's limits
+
+
+def _ea_lengths(name, v, shape, hi, dev):
+    """hyp_len / ref_len of edit_align: host integers checked against [0, hi], or a device tensor the kernel clamps"""
+    if torch.is_tensor(v) and v.is_cuda:
+        if v.device != dev or tuple(v.shape) != shape or v.dtype.is_floating_point or v.dtype == torch.bool:
+            raise ValueError('edit_align: %s must be %s integers on the device of hyp (got %s %s on %s)'
+                             % (name, shape, tuple(v.shape), v.dtype, v.device))
+    else:
+        host = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+        if host.shape != shape or host.dtype.kind not in 'iu' or (host < 0).any() or (host > hi).any():
+            raise ValueError('edit_align: %s must be %s integers in [0, %d] (got %s)' % (name, shape, hi, host.tolist()))
+    return torch.as_tensor(v).to(dev, torch.int32).contiguous()
+
+
+def edit_align(hyp, hyp_len, ref, ref_len=None, ignore=(), n_classes=1, confusion=None, want_ali=True):
+    """Levenshtein alignment with its trace-back, pair by pair on one GPU (see st_edit_align): hyp (B, N, Lh) int64 transcripts of
+    hyp_len (B, N) tokens, N paths per utterance, against ref (B, Lr) int64 of ref_len (B,) tokens (None: all Lr); a host sequence of
+    lengths is checked against [0, L] here, a device tensor is taken as it is (the kernel clamps it).  ignore: the ids dropped from
+    both sides.  confusion: None, a (n_classes + 1, n_classes + 1) int32 device tensor that path 0 of every utterance is added into, or
+    True for a zeroed one made here.
+    -> (counts (B, N, 4) int32 = correct, substitutions, deletions, insertions; ali_len (B, N) int32; ali (B, N, Lr + Lh, 2) int32 or
+    None when want_ali is false; the confusion tensor or None) device tensors; one launch, no host read.  Anything the kernel would refuse raises ValueError before
+    the device is touched."""
+    for name, t in (('hyp', hyp), ('ref', ref)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int64:
+            raise ValueError('edit_align: %s must be an int64 GPU tensor (got %s)'
+                             % (name, '%s %s on %s' % (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+    dev = hyp.device
+    if ref.device != dev:
+        raise ValueError('edit_align: hyp on %s, ref on %s' % (hyp.device, ref.device))
+    if hyp.dim() != 3 or ref.dim() != 2:
+        raise ValueError('edit_align: hyp must be (B, N, Lh) and ref (B, Lr) (got %s, %s)' % (tuple(hyp.shape), tuple(ref.shape)))
+    B, N, Lh = hyp.shape
+    Lr = ref.shape[1]
+    if ref.shape[0] != B:
+        raise ValueError('edit_align: %d utterances of hypotheses, %d references: they must match' % (B, ref.shape[0]))
+    if B < 1 or N < 1 or B * N > 2 ** 24:
+        raise ValueError('edit_align: B=%d, N=%d outside B >= 1, N >= 1, B N <= 2^24' % (B, N))
+    if not (1 <= Lh <= EA_MAX_L and 1 <= Lr <= EA_MAX_L):
+        raise ValueError('edit_align: Lh=%d, Lr=%d outside 1 <= Lh, Lr <= %d' % (Lh, Lr, EA_MAX_L))
+    V = n_classes
+    if isinstance(V, bool) or not isinstance(V, (int, np.integer)) or not 1 <= int(V) <= EA_MAX_V:
+        raise ValueError('edit_align: n_classes must be an integer in [1, %d] (got %r)' % (EA_MAX_V, V))
+    V = int(V)
+    try:
+        ignore = tuple(int(i) for i in ignore)
+    except (TypeError, ValueError):
+        raise ValueError('edit_align: ignore must be a sequence of integer ids (got %r)' % (ignore,))
+    if len(ignore) > EA_MAX_IGNORE:
+        raise ValueError('edit_align: %d ignored ids, at most %d' % (len(ignore), EA_MAX_IGNORE))
+    if any(not -2 ** 31 <= i < 2 ** 31 for i in ignore):
+        raise ValueError('edit_align: ignored ids must fit int32')
+    if confusion is not None and confusion is not True:
+        if (not torch.is_tensor(confusion) or not confusion.is_cuda or confusion.device != dev or confusion.dtype != torch.int32
+                or tuple(confusion.shape) != (V + 1, V + 1) or not confusion.is_contiguous()):
+            raise ValueError('edit_align: confusion must be a contiguous (%d, %d) int32 tensor on the device of hyp (got %s)'
+                             % (V + 1, V + 1, '%s %s on %s' % (tuple(confusion.shape), confusion.dtype, confusion.device)
+                                if torch.is_tensor(confusion) else type(confusion).__name__))
+    hyp_len = _ea_lengths('hyp_len', hyp_len, (B, N), Lh, dev)
+    ref_len = None if ref_len is None else _ea_lengths('ref_len', ref_len, (B,), Lr, dev)
+    lib = _lib.load()
+    ign = _IGNORE_DEV.get((dev, ignore))
+    if ign is None:
+        ign = _IGNORE_DEV[(dev, ignore)] = torch.tensor(ignore if ignore else [0], dtype=torch.int32).to(dev)
+    hyp, ref = hyp.contiguous(), ref.contiguous()
+    if confusion is True:
+        confusion = torch.zeros(V + 1, V + 1, device=dev, dtype=torch.int32)
+    # one allocation, carved into the outputs (the call is latency-bound)
+    AL = Lr + Lh
+    flat = torch.empty(B * N * (5 + (2 * AL if want_ali else 0)), device=dev, dtype=torch.int32)
+    counts, ali_len = flat[:4 * B * N].view(B, N, 4), flat[4 * B * N:5 * B * N].view(B, N)
+    ali = flat[5 * B * N:].view(B, N, AL, 2) if want_ali else None
+    nbytes = int(lib.st_edit_align_workspace_bytes(B * N, Lr, Lh))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+    check(lib.st_edit_align(_p(hyp, torch.int64), _p(hyp_len, torch.int32), B, N, Lh, _p(ref, torch.int64), _p(ref_len, torch.int32), Lr,
+                            _p(ign, torch.int32), len(ignore), V, _p(counts, torch.int32), _p(ali_len, torch.int32), _p(ali, torch.int32),
+                            _p(confusion, torch.int32), _p(ws, torch.uint8), stream_handle()), 'st_edit_align')
+    return counts, ali_len, ali, confusion
+
+
 def softmax_argmax(logits):
     lib = _lib.load()
     V = logits.shape[-1]

@@ -606,7 +606,210 @@ class McdScorer:
         return len(vals)
 
 
+SCORE_MAX_BATCH = 64                # utterances per st_edit_align call
+PER_HEADER = 'file,ref_tokens,hyp_tokens,correct,sub,del,ins,per'
+PER_NBEST_HEADER = PER_HEADER + ',nbest_per,nbest_path'
+CONFUSIONS_HEADER = 'ref,hyp,count'
+PHONES_HEADER = 'phone,ref_count,correct,sub,del,ins_as_hyp'
+
+
+def phn_pairs(hyp_dir, ref_dir):
+    """the .phn files of hyp_dir sorted by name, each with its reference <key>.phn of ref_dir (key: mcd_key, so x-pred.phn scores
+    against x.phn) -> [(file, key, reference)] (names, not paths).  ValueError naming the file when hyp_dir holds none, a reference is
+    missing or two files share one."""
+    files = sorted(f for f in os.listdir(hyp_dir) if f.lower().endswith('.phn'))
+    if not files:
+        raise ValueError('--score-phn-dir %s: no .phn files' % hyp_dir)
+    pairs, seen = [], {}
+    for f in files:
+        key = mcd_key(f)
+        ref = key + '.phn'
+        if not key or not os.path.isfile(os.path.join(ref_dir, ref)):
+            raise ValueError('--score-phn-dir: %s has no reference %s' % (f, os.path.join(ref_dir, ref)))
+        if key in seen:
+            raise ValueError('--score-phn-dir: %s and %s share the reference %s' % (seen[key], f, ref))
+        seen[key] = f
+        pairs.append((f, key, ref))
+    return pairs
+
+
+def _phone(vocab, t):
+    return vocab[t] if vocab is not None and 0 <= t < len(vocab) else str(t)
+
+
+def per_row(file, counts, nbest=None):
+    """one row of per.csv: counts = (correct, sub, del, ins) of the scored path; nbest = (lowest dist over the paths, its path) or None"""
+    c, s, d, i = (int(v) for v in counts)
+    n = c + s + d
+    row = '%s,%d,%d,%d,%d,%d,%d,%s' % (file, n, c + s + i, c, s, d, i, '%.6f' % ((s + d + i) / n) if n else 'nan')
+    if nbest is not None:
+        row += ',%s,%d' % ('%.6f' % (int(nbest[0]) / n) if n else 'nan', int(nbest[1]))
+    return row
+
+
+def format_confusions(conf, vocab=None):
+    """the text of confusions.csv from the (V + 1, V + 1) matrix: every non-zero cell off the diagonal, the deletion column as <del> and
+    the insertion row as <ins>, by count descending, then reference id, then hypothesis id"""
+    conf = np.asarray(conf)
+    V = conf.shape[0] - 1
+    a, b = np.nonzero(conf)
+    keep = a != b
+    a, b = a[keep], b[keep]
+    cnt = conf[a, b]
+    lines = [CONFUSIONS_HEADER]
+    for k in np.lexsort((b, a, -cnt)):
+        lines.append('%s,%s,%d' % ('<ins>' if a[k] == V else _phone(vocab, int(a[k])), '<del>' if b[k] == V else _phone(vocab, int(b[k])), cnt[k]))
+    return '\n'.join(lines) + '\n'
+
+
+def format_phones(conf, vocab=None):
+    """the text of phones.csv: one row per class that occurs on either side -- how often it stands in a reference, and how often that was
+    correct, substituted or deleted; how often it was inserted"""
+    conf = np.asarray(conf)
+    V = conf.shape[0] - 1
+    lines = [PHONES_HEADER]
+    for t in range(V):
+        n_ref = int(conf[t].sum())
+        if n_ref == 0 and int(conf[:, t].sum()) == 0:
+            continue
+        ok, dele = int(conf[t, t]), int(conf[t, V])
+        lines.append('%s,%d,%d,%d,%d,%d' % (_phone(vocab, t), n_ref, ok, n_ref - ok - dele, dele, int(conf[V, t])))
+    return '\n'.join(lines) + '\n'
+
+
+def format_ops(ali, vocab=None):
+    """the text of one <key>.ops file from the aligned pairs (ali_len, 2): three lines REF: / HYP: / OP: whose columns line up -- the
+    symbols (or ids) padded to the wider of the two, * for a gap, and C S D I"""
+    cols = [[], [], []]
+    for r, h in np.asarray(ali).reshape(-1, 2).tolist():
+        x, y = ('*' if r < 0 else _phone(vocab, r)), ('*' if h < 0 else _phone(vocab, h))
+        op = 'I' if r < 0 else 'D' if h < 0 else 'C' if r == h else 'S'
+        w = max(len(x), len(y))
+        for col, text in zip(cols, (x, y, op)):
+            col.append(text.ljust(w))
+    return ''.join((tag + ' '.join(col)).rstrip() + '\n' for tag, col in zip(('REF: ', 'HYP: ', 'OP:  '), cols))
+
+
+class PhnScorer:
+    """main.py --score-phn-dir HYP --score-ref-dir REF [--vocab FILE --score-ignore 0,1,2 --score-nbest --score-ali]: every .phn of HYP
+    (sorted by name) against REF/<key>.phn (mcd_key), in batches of --batch-size (at most 64 utterances a call) ->
+    metrics.align_transcripts (st_edit_align: the Levenshtein alignment with its trace-back, one launch) -> one host read per batch ->
+    <logdir>/per.csv (PER_HEADER), confusion.npy (int64 (V + 1, V + 1): [r, h] pairs, column V deletions, row V insertions),
+    confusions.csv, phones.csv and, with --score-ali, <key>.ops.  The confusion matrix stays on the device across the run and is read
+    once at the end.  Without --score-nbest the first line of a hypothesis file is scored; with it every line (the paths of
+    --top-paths), and per.csv gains the lowest error over the paths and the first path that attains it (a file with fewer paths than
+    the widest of its batch is filled up with copies of its first).  V = the size of --vocab, or 1 + the largest id seen.  No config,
+    no checkpoint, no model.  Every file is paired and read in load_data: a missing or shared reference, an unreadable file or an
+    unknown symbol stops the run, naming the file, before any device work."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.exp_name = getattr(paras, 'name', None) or 'synthetic'
+        self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
+        self.nbest = bool(getattr(paras, 'score_nbest', False))
+        self.want_ali = bool(getattr(paras, 'score_ali', False))
+        ignore = getattr(paras, 'score_ignore', None)
+        self.ignore = SCORE_DEFAULT_IGNORE if ignore is None else tuple(int(t) for t in ignore)
+
+    def load_data(self):
+        from .ctc_align import read_phn, read_phn_paths
+        self.hyp_dir, self.ref_dir = self.paras.score_phn_dir, self.paras.score_ref_dir
+        self.pairs = phn_pairs(self.hyp_dir, self.ref_dir)
+        vocab_file = getattr(self.paras, 'vocab', None)
+        try:
+            self.vocab = read_vocab(vocab_file) if vocab_file else None
+        except (OSError, UnicodeDecodeError) as e:
+            raise ValueError('--vocab %s: cannot read the vocabulary (%s)' % (vocab_file, e))
+        self.hyps, self.refs, top = [], [], -1
+        for f, _, ref in self.pairs:
+            paths = read_phn_paths(os.path.join(self.hyp_dir, f), self.vocab)
+            self.hyps.append(paths if self.nbest else paths[:1])
+            self.refs.append(read_phn(os.path.join(self.ref_dir, ref), self.vocab))
+            top = max([top] + self.refs[-1] + [t for p in self.hyps[-1] for t in p])
+        self.n_classes = len(self.vocab) if self.vocab is not None else max(1, top + 1)
+        if self.n_classes > ops.EA_MAX_V:
+            raise ValueError('--score-phn-dir: %d classes (%s); the confusion matrix takes at most %d'
+                             % (self.n_classes, 'the size of --vocab' if self.vocab is not None else '1 + the largest id', ops.EA_MAX_V))
+        if len(self.ignore) > ops.EA_MAX_IGNORE:
+            raise ValueError('--score-ignore: %d ids, at most %d' % (len(self.ignore), ops.EA_MAX_IGNORE))
+        return self
+
+    def set_model(self):
+        return self
+
+    def score(self, lo, hi):
+        """utterances [lo, hi) in one call, their path 0 added into self.confusion -> per utterance (counts (N, 4) int32, (lowest dist,
+        its path) or None, ali (ali_len, 2) int32 of path 0 or None); one host read"""
+        from .metrics import align_transcripts, nbest_per
+        hyps, refs = self.hyps[lo:hi], self.refs[lo:hi]
+        B, N = len(hyps), max(len(p) for p in hyps)
+        Lh, Lr = max(1, max(len(t) for p in hyps for t in p)), max(1, max(len(r) for r in refs))
+        hyp, ref = np.zeros((B, N, Lh), np.int64), np.zeros((B, Lr), np.int64)
+        hyp_len, ref_len = np.zeros((B, N), np.int32), np.zeros(B, np.int32)
+        for b, (paths, r) in enumerate(zip(hyps, refs)):
+            ref[b, :len(r)], ref_len[b] = r, len(r)
+            for k in range(N):
+                t = paths[k] if k < len(paths) else paths[0]
+                hyp[b, k, :len(t)], hyp_len[b, k] = t, len(t)
+        dev = self.confusion.device
+        res = align_transcripts(torch.from_numpy(hyp).to(dev), hyp_len.tolist(), torch.from_numpy(ref).to(dev), ref_len.tolist(),
+                                ignore=self.ignore, confusion=self.confusion, want_ali=self.want_ali)
+        cols = [torch.stack([res.correct, res.sub, res.dele, res.ins], dim=-1).reshape(B, 4 * N)]
+        if self.nbest:
+            nb = nbest_per(res.dist)
+            cols += [nb.dist.reshape(B, 1), nb.path.to(torch.int32).reshape(B, 1)]
+        if self.want_ali:
+            cols += [res.ali_len[:, :1], res.ali[:, 0].reshape(B, -1)]
+        host = torch.cat(cols, dim=1).cpu().numpy()                 # (the one host read)
+        out = []
+        for b in range(B):
+            row = host[b]
+            nb = (int(row[4 * N]), int(row[4 * N + 1])) if self.nbest else None
+            ali = None
+            if self.want_ali:
+                o = 4 * N + (2 if self.nbest else 0)
+                ali = row[o + 1:o + 1 + 2 * int(row[o])].reshape(-1, 2).copy()
+            out.append((row[:4 * N].reshape(N, 4).copy(), nb, ali))
+        return out
+
+    def exec(self):
+        os.makedirs(self.logdir, exist_ok=True)
+        B = max(1, min(int(self.paras.batch_size), SCORE_MAX_BATCH))
+        V = self.n_classes
+        self.confusion = torch.zeros(V + 1, V + 1, device=torch.device('cuda', torch.cuda.current_device()), dtype=torch.int32)
+        t0, rows = time.perf_counter(), [PER_NBEST_HEADER if self.nbest else PER_HEADER]
+        tot, best_tot, rates = np.zeros(4, np.int64), 0, []
+        for lo in range(0, len(self.pairs), B):
+            for (f, key, _), (counts, nb, ali) in zip(self.pairs[lo:lo + B], self.score(lo, min(lo + B, len(self.pairs)))):
+                rows.append(per_row(f, counts[0], nb))
+                tot += counts[0]
+                n = int(counts[0][:3].sum())
+                if n:
+                    rates.append(float(counts[0][1:].sum()) / n)
+                if nb is not None:
+                    best_tot += nb[0]
+                if ali is not None:
+                    with open(os.path.join(self.logdir, key + '.ops'), 'w') as fh:
+                        fh.write(format_ops(ali, self.vocab))
+        conf = self.confusion.cpu().numpy().astype(np.int64)        # (the one read of the matrix)
+        self.confusion_host = conf
+        np.save(os.path.join(self.logdir, 'confusion.npy'), conf, allow_pickle=False)
+        for name, text in (('per.csv', '\n'.join(rows) + '\n'), ('confusions.csv', format_confusions(conf, self.vocab)),
+                           ('phones.csv', format_phones(conf, self.vocab))):
+            with open(os.path.join(self.logdir, name), 'w') as fh:
+                fh.write(text)
+        n_ref = int(tot[:3].sum())
+        share = lambda v: float(v) / n_ref if n_ref else math.nan
+        self.corpus_per, self.mean_per = share(tot[1:].sum()), float(np.mean(rates)) if rates else math.nan
+        self.oracle_per = share(best_tot) if self.nbest else None
+        print('[INFO]', 'PER of %d transcripts (%d reference phones): corpus %.4f, mean per utterance %.4f; sub %.4f, del %.4f, ins %.4f%s; %s, %.2f s'
+              % (len(self.pairs), n_ref, self.corpus_per, self.mean_per, share(tot[1]), share(tot[2]), share(tot[3]),
+                 '; n-best oracle %.4f' % self.oracle_per if self.nbest else '', os.path.join(self.logdir, 'per.csv'), time.perf_counter() - t0))
+        return len(self.pairs)
+
+
 SPECIAL_TOKENS = ('<pad>', '<space>', '<eos>')     # ids 0, 1, 2 of the phone vocabulary (src/text.py); phones start at id 3
+SCORE_DEFAULT_IGNORE = (0, 1, 2)                   # --score-ignore: the special tokens (cal_per's filter also drops id 42)
 
 
 def read_vocab(path):
