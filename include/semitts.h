@@ -1527,6 +1527,58 @@ int st_edit_align(const int64_t* hyp /* (B, N, Lh) */, const int32_t* hyp_len /*
                   int V, int32_t* counts /* (B, N, 4) */, int32_t* ali_len /* (B, N) */, int32_t* ali /* (B, N, Lr + Lh, 2) or NULL */,
                   int32_t* confusion /* (V + 1, V + 1) or NULL */, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ loudness (ITU-R BS.1770-4 / EBU R 128 integrated loudness, gain)
+ * Not a step of the reference (its features are absolute levels: a quieter recording is a different input).  Mono, channel 0, the RAW
+ * waveform (no pre-emphasis) of a ragged batch (st_wave_batch, B <= 64).  Utterance b is x[0 .. L), L = len[b]; its filter state
+ * starts at zero and it never sees a neighbouring utterance's samples of the packed buffer.  Out of scope: multichannel weighting,
+ * true (oversampled) peak, loudness range (EBU Tech 3342) and short-term loudness.
+ * K-weighting at the sample rate fs: two biquads, coefficients computed by the caller in float64.
+ *   Stage 1 (shelf): f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196; K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *   Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2; b = (Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2) / a0,
+ *   a = (1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0).
+ *   Stage 2 (high-pass): f0 = 38.13547087602444, Q = 0.5003270373238773, the same K and a0 formulas; b = (1, -2, 1) exactly,
+ *   a = (1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0).
+ *   At fs = 48000 these are the standard's table to its 14 printed digits.  A 0 dBFS 997 Hz sine reads -3.0103 LKFS there and -2.970
+ *   at 16 kHz (the bilinear warp).
+ * Hops and blocks.  hop = (fs + 5) / 10 samples (integer division, 100 ms); H = L / hop full hops, the tail is not metered.
+ * e[h] = sum of y^2 over hop h of the filtered signal y.  Block j = 0 .. H - 4: z_j = (e[j] + e[j+1] + e[j+2] + e[j+3]) / (4 hop),
+ * l_j = -0.691 + 10 log10 z_j.
+ * Gating.  A = { j : l_j > -70 }; Gr = -0.691 + 10 log10(mean of z over A) - 10; R = { j in A : l_j > Gr }; the integrated loudness
+ * L_I = -0.691 + 10 log10(mean of z over R).  Both comparisons are strict.
+ * Arithmetic.  The recurrence, its carry across threads and hops and the sums of squares are float64 on the device; e[h] is rounded
+ * once to fp32 into hop_energy, and blocks, gates and statistics are formed in float64 FROM those fp32 values, each result rounded once.
+ * Outputs.  hop_energy (B, H_pad): e[h], rows h >= H written 0.
+ *   stats (B, 8) fp32: 0 L_I; 1 max_j l_j (momentary maximum); 2 Gr; 3 the sample peak max |x| over all L samples, tail included;
+ *   4 the ungated loudness over all blocks; 5 the gain g; 6, 7 zero.
+ *   counts (B, 4) int32: (max(H - 3, 0), |A|, |R|, flags).
+ *   flags: 1 a non-finite sample -- slots 0 .. 4 NaN, g = 1, |A| = |R| = 0, hop_energy NaN from the hop that holds it on (IEEE), the
+ *   other utterances untouched; 2 H < 4, no block -- slots 0, 1, 2, 4 NaN, g = 1; 4 A is empty -- L_I = Gr = -inf, g = 1;
+ *   8 the gain is limited by the peak ceiling; 16 the gain is limited by max_gain_db (of 8 and 16 the one that binds; 8 on a tie).
+ * Gain.  g = min(10^((target - L_I) / 20), 10^(peak_db / 20) / peak, 10^(max_gain_db / 20)) in float64 on the device, rounded once.
+ * target NaN: measure only, g = 1 and neither 8 nor 16.
+ * tables: ST_LOUDNESS_TABLE_DOUBLES float64 values on the device, with r = st_loudness_run_length(fs), pad = 256 r - hop and A the 4 x 4
+ * state matrix of the cascade in DF2-transposed form, state (shelf s1, shelf s2, high-pass s1, high-pass s2), matrices row-major:
+ *   [0, 8) b0 b1 b2 a1 a2 of stage 1, a1 a2 of stage 2, 0;  [8, 136) A^(r 2^k), k < 8;  [136, 152) A^hop;
+ *   [152, 152 + 256 * 16) A^max(0, t r - pad), t < 256.
+ * ws: B (H_pad + 1) 9 doubles, no initialisation needed.
+ * Four launches (run end states and peaks; the carry over the hops, one wave per utterance; hop energies; gating and gain, one
+ * workgroup per utterance), no atomics, no host read: every output depends on its utterance's samples, fs and the three gain arguments
+ * alone -- not on B, the position in the batch, H_pad or the neighbours -- and is bitwise repeatable.
+ * Limits (-22 past them, before any device call): 1 <= B <= 64, every len >= 1, 8000 <= fs <= 48000, H_pad >= the largest H, finite
+ * peak_db and max_gain_db, target finite or NaN.
+ * st_loudness_run_length: the samples r = ceil(hop / 256) one thread owns at this rate (4 .. 19; 0 outside the limits) -- for tests
+ * that straddle it.
+ * st_wave_gain: out[off[b] + i] = x[off[b] + i] * g_b, ONE fp32 product, g_b = stats[8 b + 5] read on the device (no host read between
+ * the meter and the gain).  out_f32 (n_samples floats, packed as x) may be x itself; out_i16 (n_samples int16, packed as x) is
+ * rint(clip((double)(x g), -1, 1) * 32767), a 16-bit .wav writer's formula.  Either may be NULL, not both.  Samples of the buffers
+ * outside the utterances are not touched.  Limits as above (B, len). */
+#define ST_LOUDNESS_TABLE_DOUBLES (152 + 256 * 16)
+int st_loudness_run_length(int fs);
+int st_loudness_batch(const st_wave_batch* w, int fs, const double* tables, double target, double peak_db, double max_gain_db,
+                      float* hop_energy /* (B, H_pad) */, int H_pad, float* stats /* (B, 8) */, int32_t* counts /* (B, 4) */,
+                      double* ws, void* stream);
+int st_wave_gain(const st_wave_batch* w, const float* stats /* (B, 8) */, float* out_f32, int16_t* out_i16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,8 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --trim-wav-dir DIR --trim-out DIR2 [--trim-top-db 60 --trim-frame-length 2048 --trim-hop 512]
     python main.py --config config/semi-multi-spkr-paired-data.yaml --corpus --trim-silence [--trim-pad-ms 0]
     python main.py --score-phn-dir HYP --score-ref-dir REF [--vocab FILE --score-ignore 0,1,2 --score-nbest --score-ali --batch-size 64]
+    python main.py --config config/supervised.yaml --loudness-wav-dir DIR [--loudness-out DIR2 --loudness-target -23 --loudness-peak -1 --loudness-max-gain 30]
+    python main.py --config config/semi-multi-spkr-paired-data.yaml --corpus --normalize-loudness [--loudness-target -23]
 `--corpus` trains on the reference's corpus layout (semi_tts_amd/corpus.py: partition table, map table, speaker map, vocabulary file and
 <path>/<speaker>/<id>.wav, src/data.py + corpus/vctk.py + src/text.py): each split of the rank's shard is read once and stays on the device as
 one packed buffer, every fetch extracts mel / augmented mel / linear from it on the GPU, `--dev-batches K` (-1: all) validates on the real dev
@@ -50,6 +52,14 @@ them; `--resample-wav-dir` converts a directory of .wav files to another rate an
 utterance that --corpus, --unpair-wav-dir, --transcribe-wav-dir, --mcd-wav-dir or --feat-wav-dir load, on the GPU and without a copy
 (semi_tts_amd.audio.AudioConverter.trim_batch, st_trim_silence: the definition of librosa.effects.trim); `--trim-wav-dir` writes the kept
 span of every .wav of a directory, bit for bit, and trim.csv (solver.Trimmer).
+`--normalize-loudness` (not a step of the reference, whose features are absolute levels) brings every utterance that --corpus,
+--unpair-wav-dir, --transcribe-wav-dir, --feat-wav-dir or --mcd-wav-dir (both sides) load, and every waveform that --gen-specgram --gen-wav,
+--vocode-dir or --synth-phn-dir --gen-wav write, to --loudness-target LUFS of integrated loudness (ITU-R BS.1770-4 / EBU R 128, mono: K-weighting,
+400 ms blocks, gates at -70 LKFS and 10 LU under the mean) on the GPU, in place, after resampling and trimming
+(semi_tts_amd.audio.AudioConverter.loudness_batch, st_loudness_batch + st_wave_gain); the gain stops where the sample peak would pass
+--loudness-peak dBFS or the gain --loudness-max-gain dB, and utterances with a non-finite sample, under 400 ms or under the absolute gate keep
+their level.  This first version does not combine with --align-wav-dir or --segment-file.  `--loudness-wav-dir` meters every .wav of a directory
+into loudness.csv and, with `--loudness-out`, writes every file normalised as 16-bit mono (solver.LoudnessWriter).
 `--feat-wav-dir` writes the MFCC (13 cepstra and their two derivatives, src/audio.py:119-154), mel or linear features of .wav files as
 <stem>-<feat>.npy and, with `--segment-file` (the segments.csv of --align-wav-dir), the same cut at the phone boundaries as
 <stem>-<feat>-seg.npy (solver.FeatureWriter; the reference's segment_file / segment_feat / min_segment_len, src/audio.py:309-354).
@@ -196,6 +206,21 @@ parser.add_argument('--trim-wav-dir', default=None, type=str, help='cut the lead
                     'name, batched by --batch-size, at data.audio.sample_rate of --config) and write the kept span of channel 0 -- the exact 16-bit '
                     'samples -- to --trim-out/<same name>, with --trim-out/trim.csv (file, samples, start, end, seconds, kept_seconds, n_intervals); no model')
 parser.add_argument('--trim-out', default=None, type=str, help='--trim-wav-dir: the directory to write (not the one read)')
+parser.add_argument('--normalize-loudness', action='store_true', help='--corpus / --unpair-wav-dir / --transcribe-wav-dir / --feat-wav-dir (without '
+                    '--segment-file) / --mcd-wav-dir (both sides): bring every loaded utterance to --loudness-target LUFS on the GPU (ITU-R BS.1770-4 '
+                    'integrated loudness, AudioConverter.loudness_batch), after resampling and trimming; --gen-specgram --gen-wav / --vocode-dir / '
+                    '--synth-phn-dir --gen-wav: the written waveforms instead')
+parser.add_argument('--loudness-target', default=None, type=float, help='--normalize-loudness / --loudness-wav-dir: the integrated loudness to reach, in LUFS, '
+                    'within [-70, 0] (default -23, EBU R 128)')
+parser.add_argument('--loudness-peak', default=None, type=float, help='--normalize-loudness / --loudness-wav-dir: the sample peak the gain must not pass, in dBFS, '
+                    'at most 0 (default -1)')
+parser.add_argument('--loudness-max-gain', default=None, type=float, help='--normalize-loudness / --loudness-wav-dir: the largest gain applied, in dB, at least 0 '
+                    '(default 30)')
+parser.add_argument('--loudness-wav-dir', default=None, type=str, help='meter the .wav files of this directory (sorted by name, batched by --batch-size, at '
+                    'data.audio.sample_rate of --config; --resample and --trim-silence are honoured) and write loudness.csv (file, samples, seconds, lufs, '
+                    'momentary_max, rel_gate, peak_dbfs, n_blocks, n_abs, n_rel, gain_db, flags) into --loudness-out, or into the directory itself without it; no model')
+parser.add_argument('--loudness-out', default=None, type=str, help='--loudness-wav-dir: also write every file normalised as 16-bit mono into this directory '
+                    '(not the one read); a file the meter flags (non-finite, under 400 ms, silent) keeps its level')
 parser.add_argument('--score-phn-dir', default=None, type=str, help='score the .phn transcripts of this directory (sorted by name, batched by '
                     '--batch-size; ids or --vocab symbols, the files of --transcribe-wav-dir as they are) against the references of '
                     '--score-ref-dir by Levenshtein alignment on the GPU: <logdir>/<name>/per.csv (file,ref_tokens,hyp_tokens,correct,sub,del,ins,per), '
@@ -235,7 +260,7 @@ def parse_args(argv=None):
                      % ('tts-only' if paras.tts_only else 'gen-specgram'))
     if paras.corpus:
         for flag in ('unpair_wav_dir', 'gen_specgram', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir', 'resample_wav_dir',
-                     'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir'):
+                     'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir', 'loudness_wav_dir'):
             if getattr(paras, flag):
                 parser.error('--corpus trains on the splits of data.corpus (the unpaired one included); it does not combine with --%s'
                              % flag.replace('_', '-'))
@@ -278,7 +303,8 @@ def parse_args(argv=None):
         parser.error('--vocode-feat names the files --vocode-dir reads; it needs that flag')
     if paras.vocode_feat is None:
         paras.vocode_feat = 'spec'
-    if paras.resample and paras.unpair_wav_dir is None and paras.transcribe_wav_dir is None and paras.align_wav_dir is None and not paras.corpus:
+    if (paras.resample and paras.unpair_wav_dir is None and paras.transcribe_wav_dir is None and paras.align_wav_dir is None and not paras.corpus
+            and paras.loudness_wav_dir is None):
         parser.error('--resample converts the files of --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir, or the splits of --corpus; it needs one '
                      'of them')
     if paras.resample_wav_dir is not None:
@@ -378,7 +404,8 @@ def parse_args(argv=None):
             parser.error('--trim-silence does not combine with --align-wav-dir: its times refer to the untrimmed file')
         if paras.segment_file is not None:
             parser.error('--trim-silence does not combine with --segment-file: its times refer to the untrimmed file')
-        if not (paras.corpus or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir'))):
+        if not (paras.corpus or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir',
+                                                                            'loudness_wav_dir'))):
             parser.error('--trim-silence trims what --corpus, --unpair-wav-dir, --transcribe-wav-dir, --mcd-wav-dir or --feat-wav-dir load; it needs one '
                          'of them')
     elif paras.trim_wav_dir is None and any(v is not None for v in (paras.trim_top_db, paras.trim_frame_length, paras.trim_hop, paras.trim_pad_ms)):
@@ -389,6 +416,39 @@ def parse_args(argv=None):
     paras.trim_pad_ms = 0.0 if paras.trim_pad_ms is None else paras.trim_pad_ms
     if not 0.0 < paras.trim_top_db < float('inf') or not 1 <= paras.trim_hop <= paras.trim_frame_length <= 8192 or not 0.0 <= paras.trim_pad_ms < float('inf'):
         parser.error('--trim-top-db must be finite and positive, 1 <= --trim-hop <= --trim-frame-length <= 8192 and --trim-pad-ms finite and >= 0')
+    if paras.loudness_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir', 'score_phn_dir', 'normalize_loudness'):
+            if getattr(paras, flag):
+                parser.error('--loudness-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches > 0:
+            parser.error('--loudness-wav-dir does not combine with --dev-batches')
+        if paras.config is None:
+            parser.error('--loudness-wav-dir needs --config (its data.audio.sample_rate)')
+        if paras.loudness_out is not None and os.path.realpath(paras.loudness_out) == os.path.realpath(paras.loudness_wav_dir):
+            parser.error('--loudness-out must not be the directory --loudness-wav-dir reads')
+    elif paras.loudness_out is not None:
+        parser.error('--loudness-out belongs to --loudness-wav-dir; it needs that flag')
+    if paras.normalize_loudness:
+        if paras.align_wav_dir is not None:
+            parser.error('--normalize-loudness does not combine with --align-wav-dir in this version (times would not change; the listed modes only)')
+        if paras.segment_file is not None:
+            parser.error('--normalize-loudness does not combine with --segment-file in this version (times would not change; the listed modes only)')
+        writes = paras.vocode_dir is not None or (paras.gen_wav and (paras.gen_specgram or paras.synth_phn_dir is not None))
+        if not (paras.corpus or writes or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir'))):
+            parser.error('--normalize-loudness normalises what --corpus, --unpair-wav-dir, --transcribe-wav-dir, --feat-wav-dir or --mcd-wav-dir load and what '
+                         '--gen-specgram --gen-wav, --vocode-dir or --synth-phn-dir --gen-wav write; it needs one of them')
+    elif paras.loudness_wav_dir is None and any(v is not None for v in (paras.loudness_target, paras.loudness_peak, paras.loudness_max_gain)):
+        parser.error('--loudness-target, --loudness-peak and --loudness-max-gain set --normalize-loudness or --loudness-wav-dir; they need one of them')
+    paras.loudness_target = -23.0 if paras.loudness_target is None else paras.loudness_target
+    paras.loudness_peak = -1.0 if paras.loudness_peak is None else paras.loudness_peak
+    paras.loudness_max_gain = 30.0 if paras.loudness_max_gain is None else paras.loudness_max_gain
+    if not -70.0 <= paras.loudness_target <= 0.0:
+        parser.error('--loudness-target must lie in [-70, 0] LUFS')
+    if not float('-inf') < paras.loudness_peak <= 0.0:
+        parser.error('--loudness-peak must be finite and at most 0 dBFS')
+    if not 0.0 <= paras.loudness_max_gain < float('inf'):
+        parser.error('--loudness-max-gain must be finite and at least 0 dB')
     if paras.score_phn_dir is not None:
         for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
                      'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir', 'trim_silence', 'corpus'):
@@ -483,6 +543,9 @@ def main(argv=None):
         mode = 'test'
     elif paras.trim_wav_dir is not None:
         from semi_tts_amd.solver import Trimmer as Solver
+        mode = 'test'
+    elif paras.loudness_wav_dir is not None:
+        from semi_tts_amd.solver import LoudnessWriter as Solver
         mode = 'test'
     elif paras.vocode_dir is not None:
         from semi_tts_amd.solver import Vocoder as Solver

@@ -425,6 +425,9 @@ SIGNATURES = {
     'st_trim_silence': [C.POINTER(StWaveBatch), I, I, F, I, I, P, I, P, P, P, P],
     'st_edit_align_workspace_bytes': [I, I, I],
     'st_edit_align': [P, P, I, I, I, P, P, I, P, I, I, P, P, P, P, P, P],
+    'st_loudness_run_length': [I],
+    'st_loudness_batch': [C.POINTER(StWaveBatch), I, P, C.c_double, C.c_double, C.c_double, P, I, P, P, P, P],
+    'st_wave_gain': [C.POINTER(StWaveBatch), P, P, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,

@@ -311,11 +311,12 @@ class AudioConverter:
         wav = self.gen_wav_device(m, phases, frames=frames, mel=True).cpu().numpy().astype(np.float64)
         return (wav[0] if squeeze else wav), self.sr
 
-    def vocode_batch(self, feats, kind='spec'):
+    def vocode_batch(self, feats, kind='spec', loudness=None):
         """Utterances of differing lengths in one st_griffin_lim_batch call (the file loop of the reference's
         util/gen_wav_from_specgram.py as one batch): feats, a list of (T_i, D) normalised spectrograms, D = num_freq for kind 'spec'
         or num_mels for 'mel' -> list of float64 waveforms of hop * (T_i - 1) samples, in the given order.  The initial phases are
-        drawn per utterance in that order as draw_phases((F, T_i)): one np.random seed gives the reference loop's phases."""
+        drawn per utterance in that order as draw_phases((F, T_i)): one np.random seed gives the reference loop's phases.
+        loudness: a dict of loudness_batch's arguments; each waveform is then normalised on the device before the copy to the host."""
         if kind not in ('spec', 'mel'):
             raise ValueError("vocode_batch: kind %r is neither 'spec' nor 'mel'" % (kind,))
         feats = [torch.as_tensor(f) for f in feats]
@@ -339,7 +340,10 @@ class AudioConverter:
         batch = torch.zeros(B, T, D, device=dev, dtype=torch.float32)
         for b, f in enumerate(feats):
             batch[b, :lens[b]] = f.to(dev, torch.float32)
-        wav = self.gen_wav_device(batch, phases, frames=lens, mel=kind == 'mel').cpu().numpy().astype(np.float64)
+        wav = self.gen_wav_device(batch, phases, frames=lens, mel=kind == 'mel')
+        if loudness is not None:
+            self.normalize_rows(wav, [self.hop_length * (n - 1) for n in lens], **loudness)
+        wav = wav.cpu().numpy().astype(np.float64)
         return [wav[b, :self.hop_length * (n - 1)] for b, n in enumerate(lens)]
 
     # -- analysis side (src/audio.py:68-77, 156-177, 329-395)
@@ -347,18 +351,22 @@ class AudioConverter:
         """src/audio.py:68-77: (channels, samples) float32; a different sample rate raises"""
         return load_wav(wav_path, self.sr)
 
-    def load_batch(self, paths, resample=False, trim=None):
+    def load_batch(self, paths, resample=False, trim=None, loudness=None):
         """Channel 0 of the .wav files `paths` as one WaveBatch at self.sr on the device (`.order`: the position in `paths` of each
         utterance).  A file at another rate raises load()'s error -- or, with resample=True, is converted on the GPU: the files are
         grouped by source rate and each foreign group is uploaded as int16 PCM and resampled in one resample() call.  Every file
         is read and every rate checked before a device is touched.  trim: a dict of trim_batch's keyword arguments (top_db,
         frame_length, hop_length, pad_ms); the leading and trailing silence of every utterance is then cut, after resampling (`.bounds`:
-        the kept (start, end) of each file, in the order of `paths`)."""
+        the kept (start, end) of each file, in the order of `paths`).  loudness: a dict of loudness_batch's keyword arguments (target,
+        peak_db, max_gain_db); every utterance is then metered and, with a target, normalised in place -- after resampling and
+        trimming, so the meter sees the kept span (`.loudness`: loudness_batch's dict, in the order of `paths`)."""
         paths = [str(p) for p in paths]
         if not paths:
             raise ValueError('load_batch: no files')
         if trim is not None:
             self._check_trim(**trim)
+        if loudness is not None:
+            self._check_loudness(**loudness)
         read = [_read_pcm(p) for p in paths]
         groups = {}
         for i, ((_, sr), p) in enumerate(zip(read, paths)):
@@ -378,10 +386,88 @@ class AudioConverter:
             for row, k in enumerate(wb.order):
                 waves[idx[k]] = y[int(wb.offsets[row]):int(wb.offsets[row] + wb.lens[row])]
         if trim is None:
-            return WaveBatch(waves)
-        res = self.trim_batch(waves, **trim)
-        res[0].bounds = res[1]
-        return res[0]
+            wb = WaveBatch(waves)
+        else:
+            res = self.trim_batch(waves, **trim)
+            wb = res[0]
+            wb.bounds = res[1]
+        if loudness is not None:
+            rows = np.asarray(wb.order)
+            res = self.loudness_batch(wb, **loudness)
+            info, out = res if isinstance(res, tuple) else (res, wb)
+            out.order = rows
+            if trim is not None:
+                out.bounds = wb.bounds
+            out.loudness = {}
+            for k, v in info.items():                              # row i of the batch is file rows[i]
+                out.loudness[k] = np.empty_like(v)
+                out.loudness[k][rows] = v
+            wb = out
+        return wb
+
+    # -- loudness (not a step of the reference): st_loudness_batch, ITU-R BS.1770-4 / EBU R 128 integrated loudness
+    def _check_loudness(self, target=None, peak_db=-1.0, max_gain_db=30.0, lens=(1,)):
+        """every refusal of loudness_batch that does not need the waveforms"""
+        lens = np.asarray(lens, np.int64)
+        ops._loudness_check(lens[:ops.FEATURES_MAX_BATCH], self.sr, target, peak_db, max_gain_db)
+        if (lens < 1).any() or (lens >= 2 ** 31).any():
+            raise ValueError('loudness: every length must lie in [1, 2^31)')
+
+    def normalize_rows(self, wav, lens=None, target=None, peak_db=-1.0, max_gain_db=30.0):
+        """The rows of a contiguous (B, N) float32 device tensor of waveforms (what gen_wav_device returns), row b its first lens[b]
+        samples (None: all N), metered and multiplied by their gains IN PLACE on the device: no host read.  Rows of no samples and
+        flagged rows (non-finite, under 400 ms, silent) keep their level.  -> wav"""
+        if not (torch.is_tensor(wav) and wav.is_cuda and wav.dim() == 2 and wav.dtype == torch.float32 and wav.is_contiguous()):
+            raise ValueError('normalize_rows: a contiguous (B, N) float32 device tensor is needed')
+        B, N = wav.shape
+        lens = np.full(B, N, np.int64) if lens is None else np.asarray(lens, np.int64)
+        if lens.shape != (B,) or (lens > N).any():
+            raise ValueError('normalize_rows: lens must be %d lengths of at most %d samples' % (B, N))
+        rows = np.flatnonzero(lens >= 1)
+        if target is None or len(rows) == 0:
+            return wav
+        self._check_loudness(target, peak_db, max_gain_db, lens=lens[rows])
+        x = wav.view(-1)
+        for b0 in range(0, len(rows), ops.FEATURES_MAX_BATCH):
+            r = rows[b0:b0 + ops.FEATURES_MAX_BATCH]
+            _, stats, _ = ops.loudness(x, r * N, lens[r], self.sr, target, peak_db, max_gain_db)
+            ops.wave_gain(x, r * N, lens[r], stats, out=x)
+        return wav
+
+    def loudness_batch(self, wavs, target=None, peak_db=-1.0, max_gain_db=30.0):
+        """Integrated loudness (ITU-R BS.1770-4, mono) of a ragged batch on the device, one st_loudness_batch call per 64 utterances and
+        ONE host read: wavs, a list of 1-D waveforms or a WaveBatch.  -> a dict of host arrays, entry i for utterance i of `wavs` (a
+        list's position; a WaveBatch's row): lufs, momentary_max, rel_gate, peak (linear), ungated, gain_db (float64) and n_blocks, n_abs,
+        n_rel, flags (int64; ops.LOUDNESS_FLAGS).  With a target (LUFS) the utterances are also multiplied by the gain that brings them
+        to it, limited so that the sample peak stays at or under peak_db dBFS and the gain at or under max_gain_db -- flagged
+        utterances (non-finite, shorter than 400 ms, silent) keep their level -- and (dict, WaveBatch) is returned: the normalised
+        batch with the input's rows, offsets and lens.  A WaveBatch is normalised IN PLACE in its packed buffer; a list is not touched."""
+        wb = wavs if isinstance(wavs, WaveBatch) else WaveBatch(wavs)
+        self._check_loudness(target, peak_db, max_gain_db, lens=wb.lens)
+        dev = wb.device if wb.device is not None else _device()
+        B = len(wb.lens)
+        x = wb.packed(dev)
+        parts = []
+        for b0 in range(0, B, ops.FEATURES_MAX_BATCH):
+            sl = slice(b0, min(B, b0 + ops.FEATURES_MAX_BATCH))
+            _, stats, counts = ops.loudness(x, wb.offsets[sl], wb.lens[sl], self.sr, target, peak_db, max_gain_db)
+            if target is not None:
+                ops.wave_gain(x, wb.offsets[sl], wb.lens[sl], stats, out=x)
+            parts.append((stats, counts))
+        host = torch.cat([p[0].reshape(-1).view(torch.int32) for p in parts] + [p[1].reshape(-1) for p in parts]).cpu().numpy()
+        stats = host[:8 * B].view(np.float32).reshape(B, 8).astype(np.float64)
+        counts = host[8 * B:].reshape(B, 4).astype(np.int64)
+        given = isinstance(wavs, WaveBatch)
+        inv = np.arange(B) if given else np.argsort(np.asarray(wb.order), kind='stable')     # row of wb of utterance i of a list
+        with np.errstate(divide='ignore'):
+            info = dict(lufs=stats[inv, 0], momentary_max=stats[inv, 1], rel_gate=stats[inv, 2], peak=stats[inv, 3], ungated=stats[inv, 4],
+                        gain_db=20.0 * np.log10(stats[inv, 5]), n_blocks=counts[inv, 0], n_abs=counts[inv, 1], n_rel=counts[inv, 2],
+                        flags=counts[inv, 3])
+        if target is None:
+            return info
+        out = WaveBatch.window(x, wb.offsets, wb.lens)
+        out.order = np.asarray(wb.order)
+        return info, out
 
     # -- silence trimming (not a step of the reference): st_trim_silence, the definition of librosa.effects.trim / split
     def _check_trim(self, top_db=60., frame_length=2048, hop_length=512, pad_ms=0., with_intervals=False, lens=(1,)):
@@ -896,6 +982,60 @@ def resample_table(orig_sr, new_sr, lowpass_filter_width=RESAMPLE_LPW, rolloff=R
         _, _, taps, first, table = _RESAMPLE[key]
         _RESAMPLE[dkey] = (o, n, taps, torch.from_numpy(first).to(device), torch.from_numpy(table).to(device))
     return _RESAMPLE[dkey]
+
+
+# -- K-weighting (st_loudness_batch; the definition is in include/semitts.h and DESIGN.md 3.22)
+_KWEIGHT = {}                                 # sr -> host table; (sr, device) -> its copy on that device
+
+
+def kweight_coeffs(sr):
+    """The two biquads of the BS.1770 K-weighting at the sample rate sr, in float64: ((b, a) of the shelf, (b, a) of the high-pass),
+    each three coefficients with a[0] = 1.  The standard's table at 48 kHz to its 14 printed digits."""
+    sr = float(sr)
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = np.tan(np.pi * f0 / sr)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    b1 = np.array([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0])
+    a1 = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = np.tan(np.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    b2 = np.array([1.0, -2.0, 1.0])
+    a2 = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    return (b1, a1), (b2, a2)
+
+
+def kweight_state_matrix(sr):
+    """A of s' = A s + B x for the cascade of the two biquads in DF2-transposed form, state (shelf s1, s2, high-pass s1, s2), float64"""
+    (_, a), (_, p) = kweight_coeffs(sr)
+    return np.array([[-a[1], 1.0, 0.0, 0.0], [-a[2], 0.0, 0.0, 0.0], [-2.0 - p[1], 0.0, -p[1], 1.0], [1.0 - p[2], 0.0, -p[2], 0.0]])
+
+
+def kweight_tables(sr, device=None):
+    """What st_loudness_batch needs at the rate sr, ops.LOUDNESS_TABLE_DOUBLES float64 values laid out as include/semitts.h says: the
+    coefficients, A^(r 2^k) for k < 8, A^hop and A^max(0, t r - pad) for t < 256 (r the samples a thread owns, pad = 256 r - hop).
+    device None: a numpy array; else its copy on that device.  Cached per rate and per device."""
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or not ops.LOUDNESS_MIN_SR <= sr <= ops.LOUDNESS_MAX_SR:
+        raise ValueError('loudness: the sample rate must be an integer in [%d, %d] (got %r)' % (ops.LOUDNESS_MIN_SR, ops.LOUDNESS_MAX_SR, sr))
+    sr = int(sr)
+    if sr not in _KWEIGHT:
+        (b, a), (_, p) = kweight_coeffs(sr)
+        A = kweight_state_matrix(sr)
+        hop, r, nt = ops.loudness_hop(sr), ops.loudness_run_length(sr), ops.LOUDNESS_THREADS
+        pad = nt * r - hop
+        power = np.linalg.matrix_power
+        tab = np.concatenate([[b[0], b[1], b[2], a[1], a[2], p[1], p[2], 0.0]] + [power(A, r << k).reshape(-1) for k in range(8)]
+                             + [power(A, hop).reshape(-1)] + [power(A, max(0, t * r - pad)).reshape(-1) for t in range(nt)])
+        assert tab.shape == (ops.LOUDNESS_TABLE_DOUBLES,) and tab.dtype == np.float64
+        _KWEIGHT[sr] = tab
+    if device is None:
+        return _KWEIGHT[sr]
+    dkey = (sr, str(device))
+    if dkey not in _KWEIGHT:
+        _KWEIGHT[dkey] = torch.from_numpy(_KWEIGHT[sr]).to(device)
+    return _KWEIGHT[dkey]
 
 
 def resample(wavs, orig_sr, new_sr):

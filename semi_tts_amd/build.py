@@ -15,6 +15,8 @@ PITCH_SOURCES = ['f0.hip']
 TRIM_SOURCES = ['trim.hip']
 # the transcript-scoring kernel (st_edit_align), listed apart for the same reason
 SCORE_SOURCES = ['edit_align.hip']
+# the loudness kernels (st_loudness_batch, st_wave_gain), listed apart for the same reason
+LOUDNESS_SOURCES = ['loudness.hip']
 
 
 def _hipcc():
@@ -39,7 +41,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES:
+    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

@@ -292,6 +292,17 @@ def apply_bounds(rows, mine, offsets, lens, start, end, sampler, n_fft, hop, max
     return kept, new_off, new_lens, new_sampler, counts
 
 
+def loudness_report(name, info, target):
+    """the one line per split that says what the loudness pass found and did: utterances, mean / min / max LUFS before, and how many
+    were peak-limited, gain-limited or left alone, by flag"""
+    flags, lufs = np.asarray(info['flags']), np.asarray(info['lufs'], np.float64)
+    ok = lufs[np.isfinite(lufs)]
+    span = 'mean %.2f min %.2f max %.2f LUFS before' % (ok.mean(), ok.min(), ok.max()) if len(ok) else 'no utterance with a loudness'
+    return ('%s: loudness of %d utterances, %s | %s | %d peak-limited, %d gain-limited | left alone: %d non-finite, %d under 400 ms, %d silent'
+            % (name, len(flags), span, 'measured only' if target is None else 'normalised to %.1f LUFS' % target, int((flags & 8 != 0).sum()),
+               int((flags & 16 != 0).sum()), int((flags & 1 != 0).sum()), int((flags & 2 != 0).sum()), int((flags & 4 != 0).sum())))
+
+
 def trim_report(name, sample_rate, before, after, n_before, counts):
     """the one line per split that says what trimming did: seconds before / after, the share removed, the drops"""
     return ('%s: trimmed %.1f s -> %.1f s (%.1f%% removed) | %d of %d utterances kept | dropped after trimming: %d too short, %d over the frame limit'
@@ -316,9 +327,15 @@ class DeviceSplit:
     stay on the header lengths; after the upload the rank's rows are trimmed on the device in calls of 64 utterances with ONE host
     read for the split, and the split becomes what apply_bounds says (rows / lens / offsets of this rank's survivors, a sampler over
     the trimmed lengths; the trimmed samples stay resident, nothing is copied).  trim_report: the line that says what it did.
-    max_frames: the frame limit select() applied, applied again to the trimmed lengths."""
+    max_frames: the frame limit select() applied, applied again to the trimmed lengths.
 
-    def __init__(self, conv, rows, sampler, r, name='split', train=True, resample=False, max_bytes=None, trim=None, max_frames=None):
+    loudness: a dict of AudioConverter.loudness_batch's arguments (target, peak_db, max_gain_db).  After the upload, and after the
+    trimming if any, this rank's rows are metered (ITU-R BS.1770-4) and multiplied by their gains IN PLACE in the resident buffer, in
+    calls of 64 utterances with ONE host read for the split; offsets and lens do not change.  loudness_report: the line that says
+    what it did; loudness_info: loudness_batch's dict over this rank's rows (`rows`: their positions)."""
+
+    def __init__(self, conv, rows, sampler, r, name='split', train=True, resample=False, max_bytes=None, trim=None, max_frames=None,
+                 loudness=None):
         import torch
         from .audio import _device
         self.conv, self.rows, self.sampler, self.r, self.name, self.train = conv, list(rows), sampler, int(r), name, bool(train)
@@ -335,11 +352,25 @@ class DeviceSplit:
             raise ValueError(too_large(name, len(mine), total, max_bytes))
         if trim is not None:
             pad = conv._check_trim(**trim)
+        if loudness is not None:
+            conv._check_loudness(**loudness)
         self.buffer = self._upload(mine, total, dev, resample)
         self.last_fetch = None
         self.trim_report = None
+        self.loudness_report = self.loudness_info = None
         if trim is not None:
             self._trim(pad, max_frames, **trim)
+        if loudness is not None:
+            self._normalise(**loudness)
+
+    def _normalise(self, target=None, peak_db=-1.0, max_gain_db=30.0):
+        from .audio import WaveBatch
+        mine = np.flatnonzero(self.offsets >= 0)
+        mine = mine[np.argsort(-self.lens[mine], kind='stable')]
+        info = self.conv.loudness_batch(WaveBatch.window(self.buffer, self.offsets[mine], self.lens[mine]), target, peak_db, max_gain_db)
+        info = info[0] if isinstance(info, tuple) else info
+        self.loudness_info = dict(info, rows=mine)
+        self.loudness_report = loudness_report(self.name, info, target)
 
     def _trim(self, pad, max_frames, top_db=60., frame_length=2048, hop_length=512, pad_ms=0.):
         import torch
@@ -423,16 +454,19 @@ class DeviceSplit:
 
 
 def load_splits(corpus_cfg, conv, r, splits, batch_sizes, seed=0, rank=0, world=1, resample=False, max_frames=None, max_gb=None,
-                verbose=print, trim=None):
+                verbose=print, trim=None, loudness=None):
     """Corpus + one DeviceSplit per name in `splits` (of 'paired', 'unpaired', 'dev').  batch_sizes: dict split -> B.  Everything the
     tables, the headers and the limits can refuse is raised for EVERY split before the first device allocation.  trim: every split
-    (dev included) is trimmed with these settings after its upload (DeviceSplit), one report line per split.
+    (dev included) is trimmed with these settings after its upload (DeviceSplit), one report line per split.  loudness: every split
+    (dev included) is then metered and normalised in place with these settings (DeviceSplit), one report line per split.
     -> (Corpus, dict split -> DeviceSplit)"""
     from . import ops
     corpus = Corpus(**corpus_cfg)
     conv._check([], [])                                        # (the framing itself: n_fft, hop, win)
     if trim is not None:
         conv._check_trim(**trim)
+    if loudness is not None:
+        conv._check_loudness(**loudness)
     plan = []
     for s in splits:
         rows = corpus.measure(s, conv.sr, resample)
@@ -450,7 +484,9 @@ def load_splits(corpus_cfg, conv, r, splits, batch_sizes, seed=0, rank=0, world=
     sets = {}
     for s, kept, sampler, train in plan:
         sets[s] = DeviceSplit(conv, kept, sampler, r, name=s, train=train, resample=resample, max_bytes=max_bytes, trim=trim,
-                              max_frames=max_frames)
+                              max_frames=max_frames, loudness=loudness)
         if trim is not None:
             verbose(sets[s].trim_report)
+        if loudness is not None:
+            verbose(sets[s].loudness_report)
     return corpus, sets

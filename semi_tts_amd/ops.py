@@ -2461,3 +2461,105 @@ def trim_silence(x, off, lens, frame_length, hop, top_db, pad=0, max_iv=0, T_pad
                                   T_pad, _p(bounds[b0:], torch.int32), _p(iv[b0:], torch.int32) if max_iv else None,
                                   _p(n_iv[b0:], torch.int32) if max_iv else None, stream_handle()), 'st_trim_silence')
     return energy, bounds, iv, n_iv
+
+
+# --------------------------------------------------------------------------------------------- loudness (st_loudness_batch, st_wave_gain)
+LOUDNESS_MIN_SR, LOUDNESS_MAX_SR = 8000, 48000     # st_loudness_batch's limits
+LOUDNESS_THREADS = 256                             # runs a hop is cut into (loudness.hip)
+LOUDNESS_TABLE_DOUBLES = 152 + 256 * 16            # ST_LOUDNESS_TABLE_DOUBLES
+LOUDNESS_FLAGS = {'nonfinite': 1, 'short': 2, 'silent': 4, 'peak_limited': 8, 'gain_limited': 16}
+
+
+def loudness_hop(sr):
+    """samples of a 100 ms hop at this rate: (sr + 5) // 10"""
+    return (int(sr) + 5) // 10
+
+
+def loudness_run_length(sr):
+    """the samples one st_loudness_batch thread owns at this rate (st_loudness_run_length): the tests straddle it"""
+    return (loudness_hop(sr) + LOUDNESS_THREADS - 1) // LOUDNESS_THREADS
+
+
+def _loudness_check(lens, sr, target=None, peak_db=-1.0, max_gain_db=30.0, H_pad=None):
+    """every refusal of st_loudness_batch that does not need the buffers, raised before any device is touched -> (hop, H_pad)"""
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or not LOUDNESS_MIN_SR <= sr <= LOUDNESS_MAX_SR:
+        raise ValueError('loudness: the sample rate must be an integer in [%d, %d] (got %r)' % (LOUDNESS_MIN_SR, LOUDNESS_MAX_SR, sr))
+    for name, v in (('peak_db', peak_db), ('max_gain_db', max_gain_db)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError('loudness: %s must be a finite number (got %r)' % (name, v))
+    if target is not None and (isinstance(target, bool) or not isinstance(target, (int, float, np.integer, np.floating)) or np.isinf(target)):
+        raise ValueError('loudness: target must be a finite number, or None / NaN to measure only (got %r)' % (target,))
+    lens = np.asarray(lens)
+    if lens.ndim != 1 or not 1 <= lens.shape[0] <= FEATURES_MAX_BATCH or lens.dtype.kind not in 'iu':
+        raise ValueError('loudness: lens must be 1 .. %d integers, one call takes no more utterances (got %s)'
+                         % (FEATURES_MAX_BATCH, 'shape %s, %s' % (lens.shape, lens.dtype)))
+    if (lens < 1).any() or (lens >= 2 ** 31).any():
+        raise ValueError('loudness: every length must lie in [1, 2^31) (got %s)' % (lens.tolist(),))
+    hop = loudness_hop(sr)
+    hops = int(lens.max()) // hop
+    if H_pad is None:
+        H_pad = max(1, hops)
+    if isinstance(H_pad, bool) or not isinstance(H_pad, (int, np.integer)) or H_pad < hops or H_pad >= 2 ** 31:
+        raise ValueError('loudness: H_pad %r below the %d hops of the longest utterance' % (H_pad, hops))
+    return hop, int(H_pad)
+
+
+def _wave_args(what, x, off, lens):
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('%s: x must be a packed 1-D contiguous float32 GPU tensor (got %s)'
+                         % (what, '%s %s on %s' % (tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x).__name__))
+    B = len(lens)
+    off, lens = _host_off_lens(off, lens)
+    if off.shape != (B,) or (off < 0).any() or (off + lens > x.numel()).any():
+        raise ValueError('%s: an utterance lies outside the %d packed samples (off %s, lens %s)' % (what, x.numel(), off.tolist(), lens.tolist()))
+    return off, lens
+
+
+def loudness(x, off, lens, sr, target=None, peak_db=-1.0, max_gain_db=30.0, H_pad=None):
+    """st_loudness_batch (ITU-R BS.1770-4 integrated loudness; the definition is in include/semitts.h) on a ragged batch packed as for
+    audio_features: x the packed float32 waveforms on the device, utterance b = x[off[b]:off[b] + lens[b]], at most FEATURES_MAX_BATCH
+    of them (the callers above split).  -> device tensors (hop_energy (B, H_pad) float32, stats (B, 8) float32 = (L_I, momentary
+    maximum, relative gate, sample peak, ungated, gain, 0, 0), counts (B, 4) int32 = (blocks, above the absolute gate, above the
+    relative gate, flags)).  target None (or NaN): measure only, gain 1.  H_pad None: the longest utterance's hops (at least 1).
+    Four launches, no host read.  Anything the kernel would refuse raises ValueError before the device is touched."""
+    hop, H_pad = _loudness_check(lens, sr, target, peak_db, max_gain_db, H_pad)
+    off, lens = _wave_args('loudness', x, off, lens)
+    from .audio import kweight_tables                          # (here: audio imports this module)
+    lib = _lib.load()
+    dev = x.device
+    tab = kweight_tables(sr, dev)
+    B = len(lens)
+    hop_energy = torch.empty(B, H_pad, device=dev, dtype=torch.float32)
+    stats = torch.empty(B, 8, device=dev, dtype=torch.float32)
+    counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    ws = torch.empty(B * (H_pad + 1) * 9, device=dev, dtype=torch.float64)
+    w = _lib.StWaveBatch(x=_p(x), n_samples=x.numel())
+    check(lib.st_loudness_batch(_wave_chunk(w, off, lens, 0, B), int(sr), _p(tab, torch.float64), float('nan') if target is None else float(target),
+                                float(peak_db), float(max_gain_db), _p(hop_energy), H_pad, _p(stats), _p(counts, torch.int32),
+                                _p(ws, torch.float64), stream_handle()), 'st_loudness_batch')
+    return hop_energy, stats, counts
+
+
+def wave_gain(x, off, lens, stats, out=None, pcm16=False):
+    """st_wave_gain: utterance b of the packed batch times the gain stats[b, 5] of `loudness`, read on the device (no host read).
+    pcm16 False -> float32, one product a sample, written into `out` (a packed buffer like x; x itself is allowed: in place; default a
+    new buffer of zeros).  pcm16 True -> int16, rint(clip(x g, -1, 1) * 32767) as audio.write_wav, into `out` (int16, x's size) or a
+    new buffer of zeros.  Samples outside the utterances are not written.  At most FEATURES_MAX_BATCH utterances a call."""
+    lens_a = np.asarray(lens)
+    if lens_a.ndim != 1 or not 1 <= lens_a.shape[0] <= FEATURES_MAX_BATCH or lens_a.dtype.kind not in 'iu' or (lens_a < 1).any() or (lens_a >= 2 ** 31).any():
+        raise ValueError('wave_gain: lens must be 1 .. %d integers in [1, 2^31) (got %s)' % (FEATURES_MAX_BATCH, lens_a.tolist()))
+    off, lens = _wave_args('wave_gain', x, off, lens)
+    B = len(lens)
+    dt = torch.int16 if pcm16 else torch.float32
+    if not (torch.is_tensor(stats) and stats.is_cuda and stats.device == x.device and stats.dtype == torch.float32 and tuple(stats.shape) == (B, 8)
+            and stats.is_contiguous()):
+        raise ValueError('wave_gain: stats must be the contiguous (%d, 8) float32 tensor of loudness() on %s' % (B, x.device))
+    if out is None:
+        out = torch.zeros(x.numel(), device=x.device, dtype=dt)
+    elif not (torch.is_tensor(out) and out.device == x.device and out.dtype == dt and out.dim() == 1 and out.numel() == x.numel() and out.is_contiguous()):
+        raise ValueError('wave_gain: out must be a contiguous 1-D %s tensor of %d samples on %s' % (dt, x.numel(), x.device))
+    lib = _lib.load()
+    w = _lib.StWaveBatch(x=_p(x), n_samples=x.numel())
+    check(lib.st_wave_gain(_wave_chunk(w, off, lens, 0, B), _p(stats), None if pcm16 else _p(out), _p(out, torch.int16) if pcm16 else None,
+                           stream_handle()), 'st_wave_gain')
+    return out

@@ -148,9 +148,12 @@ class SpecgramGenerator(BaseSolver):
             wavs = None
             if gen_wav:                                 # gen_specgram.py:114-115: Griffin-Lim of this rank's lin, on the device
                 if getattr(self.paras, 'gen_wav_feat', 'linear') == 'mel':      # --gen-wav-feat mel: of its mel instead
-                    wavs = self.audio_converter.gen_wav_device(mel, mel=True).cpu().numpy()
+                    wavs = self.audio_converter.gen_wav_device(mel, mel=True)
                 else:
-                    wavs = self.audio_converter.gen_wav_device(lin).cpu().numpy()
+                    wavs = self.audio_converter.gen_wav_device(lin)
+                if loudness_args(self.paras) is not None:           # --normalize-loudness: on the device, before the copy to the host
+                    self.audio_converter.normalize_rows(wavs, None, **loudness_args(self.paras))
+                wavs = wavs.cpu().numpy()
             enc_step = (text != 0).sum(dim=-1).cpu().tolist()
             dec_step = [int(n * FRAME_PHN_RATIO) // r for n in enc_step]
             for i, (msp, sp, ali) in enumerate(zip(mel, lin, align)):
@@ -225,7 +228,7 @@ class Vocoder:
         t0, n = time.perf_counter(), 0
         for i in range(0, len(self.files), B):
             chunk = self.files[i:i + B]
-            wavs = self.audio_converter.vocode_batch([np.load(os.path.join(self.feat_dir, f), allow_pickle=False) for f, _ in chunk], self.kind)
+            wavs = vocode(self.audio_converter, [np.load(os.path.join(self.feat_dir, f), allow_pickle=False) for f, _ in chunk], self.kind, self.paras)
             for (_, stem), w in zip(chunk, wavs):
                 write_wav(os.path.join(self.logdir, stem + '.wav'), w, self.audio_converter.sr)
                 n += 1
@@ -300,6 +303,124 @@ def trim_args(paras):
         return None
     return dict(top_db=float(getattr(paras, 'trim_top_db', 60.0)), frame_length=int(getattr(paras, 'trim_frame_length', 2048)),
                 hop_length=int(getattr(paras, 'trim_hop', 512)), pad_ms=float(getattr(paras, 'trim_pad_ms', 0.0)))
+
+
+def loudness_args(paras):
+    """the `loudness` argument of AudioConverter.load_batch / vocode_batch / corpus.load_splits from --normalize-loudness and its options;
+    None without the flag"""
+    if not getattr(paras, 'normalize_loudness', False):
+        return None
+    return dict(target=float(getattr(paras, 'loudness_target', -23.0)), peak_db=float(getattr(paras, 'loudness_peak', -1.0)),
+                max_gain_db=float(getattr(paras, 'loudness_max_gain', 30.0)))
+
+
+def vocode(conv, feats, kind, paras):
+    """AudioConverter.vocode_batch, with --normalize-loudness the waveforms normalised on the device before the copy to the host
+    (without the flag the call is the one it always was)"""
+    args = loudness_args(paras)
+    return conv.vocode_batch(feats, kind) if args is None else conv.vocode_batch(feats, kind, loudness=args)
+
+
+class LoudnessWriter:
+    """main.py --loudness-wav-dir DIR [--loudness-out DIR2] --config CFG [--loudness-target -23 --loudness-peak -1 --loudness-max-gain 30
+    --resample --trim-silence ...]: channel 0 of every .wav of DIR (sorted by name, batches of --batch-size, at data.audio.sample_rate;
+    with --resample files of another rate are converted, with --trim-silence the kept span is metered) measured on the GPU
+    (st_loudness_batch: ITU-R BS.1770-4 integrated loudness) into loudness.csv: file, samples, seconds, lufs, momentary_max, rel_gate,
+    peak_dbfs, n_blocks, n_abs, n_rel, gain_db (what brings the file to the target within the two limits), flags
+    (ops.LOUDNESS_FLAGS).  With --loudness-out every file is also written there normalised, as 16-bit mono from the device's int16
+    output (st_wave_gain); a file the meter flags as non-finite, under 400 ms or silent is copied at the level it has (channel 0 of its
+    own samples when it is at the rate already).  The table goes
+    into DIR2, or into DIR when nothing is written back.  No checkpoint, no model."""
+
+    COLUMNS = ['file', 'samples', 'seconds', 'lufs', 'momentary_max', 'rel_gate', 'peak_dbfs', 'n_blocks', 'n_abs', 'n_rel', 'gain_db', 'flags']
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.args = dict(target=float(paras.loudness_target), peak_db=float(paras.loudness_peak), max_gain_db=float(paras.loudness_max_gain))
+
+    def load_data(self):
+        import wave
+        from .audio import load_audio_transform
+        self.wav_dir, self.out_dir = self.paras.loudness_wav_dir, getattr(self.paras, 'loudness_out', None)
+        if self.out_dir is not None and os.path.realpath(self.wav_dir) == os.path.realpath(self.out_dir):
+            raise ValueError('--loudness-out %s is the directory --loudness-wav-dir reads' % self.out_dir)
+        self.files = sorted(f for f in os.listdir(self.wav_dir) if f.lower().endswith('.wav'))
+        if not self.files:
+            raise ValueError('--loudness-wav-dir %s: no .wav files' % self.wav_dir)
+        self.audio_converter = conv = load_audio_transform(**self.config['data']['audio'])
+        conv._check_loudness(**self.args)
+        if trim_args(self.paras) is not None:
+            conv._check_trim(**trim_args(self.paras))
+        for f in self.files:
+            with wave.open(os.path.join(self.wav_dir, f), 'rb') as w:
+                if w.getsampwidth() != 2:
+                    raise ValueError('--loudness-wav-dir: %s is %d-bit; only 16-bit PCM is read' % (f, 8 * w.getsampwidth()))
+                if w.getnframes() < 1:
+                    raise ValueError('--loudness-wav-dir: %s holds no samples' % f)
+                if w.getframerate() != conv.sr and not getattr(self.paras, 'resample', False):
+                    raise ValueError('Sample rate mismatch. Expected %d but get %d (%s)' % (conv.sr, w.getframerate(), f))
+        return self
+
+    def set_model(self):
+        return self
+
+    @staticmethod
+    def _db(v):
+        return '%.3f' % v
+
+    def exec(self):
+        import csv
+        import wave
+        from . import ops
+        from .audio import _read_pcm
+        conv = self.audio_converter
+        if self.out_dir is not None:
+            os.makedirs(self.out_dir, exist_ok=True)
+        B = int(self.paras.batch_size)
+        t0, rows = time.perf_counter(), []
+        for i in range(0, len(self.files), B):
+            names = self.files[i:i + B]
+            wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names], resample=bool(getattr(self.paras, 'resample', False)),
+                                 trim=trim_args(self.paras))
+            x = wb.packed(wb.device)
+            pcm = torch.zeros(x.numel(), device=x.device, dtype=torch.int16) if self.out_dir is not None else None
+            parts = []
+            for b0 in range(0, len(wb.lens), ops.FEATURES_MAX_BATCH):
+                sl = slice(b0, b0 + ops.FEATURES_MAX_BATCH)
+                _, stats, counts = ops.loudness(x, wb.offsets[sl], wb.lens[sl], conv.sr, **self.args)
+                if pcm is not None:
+                    ops.wave_gain(x, wb.offsets[sl], wb.lens[sl], stats, out=pcm, pcm16=True)
+                parts.append((stats, counts))
+            stats = torch.cat([p[0] for p in parts]).cpu().numpy().astype(np.float64)
+            counts = torch.cat([p[1] for p in parts]).cpu().numpy()
+            pcm = None if pcm is None else pcm.cpu().numpy()
+            batch = [None] * len(names)
+            for row, k in enumerate(wb.order):
+                f, n, st, ct = names[k], int(wb.lens[row]), stats[row], counts[row]
+                with np.errstate(divide='ignore'):
+                    batch[k] = [f, n, '%.6f' % (n / conv.sr), self._db(st[0]), self._db(st[1]), self._db(st[2]), self._db(20.0 * np.log10(st[3])),
+                                int(ct[0]), int(ct[1]), int(ct[2]), self._db(20.0 * np.log10(st[5])), int(ct[3])]
+                if pcm is not None:
+                    data = pcm[int(wb.offsets[row]):int(wb.offsets[row]) + n]
+                    if int(ct[3]) & 7:                              # left alone: the file's own samples (of the kept span), not a requantisation
+                        raw, sr = _read_pcm(os.path.join(self.wav_dir, f))
+                        if sr == conv.sr:
+                            lo, hi = wb.bounds[k] if hasattr(wb, 'bounds') else (0, raw.shape[0])
+                            data = raw[int(lo):int(hi), 0]
+                    with wave.open(os.path.join(self.out_dir, f), 'wb') as w:
+                        w.setnchannels(1)
+                        w.setsampwidth(2)
+                        w.setframerate(conv.sr)
+                        w.writeframes(np.ascontiguousarray(data, dtype='<i2').tobytes())
+            rows += batch
+        with open(os.path.join(self.out_dir if self.out_dir is not None else self.wav_dir, 'loudness.csv'), 'w', newline='') as fh:
+            out = csv.writer(fh)
+            out.writerow(self.COLUMNS)
+            out.writerows(rows)
+        if getattr(self.paras, 'verbose', True):
+            print('[INFO]', 'Metered %d files%s, %.2f s' % (len(rows), '' if self.out_dir is None else ' and wrote them at %.1f LUFS into %s'
+                                                            % (self.args['target'], self.out_dir), time.perf_counter() - t0))
+        return len(rows)
 
 
 class Trimmer:
@@ -417,7 +538,7 @@ class FeatureWriter:
         """the files `names` of the .wav directory -> (features (B, T_pad, D) on the device in the sorted order, frames per row, order)"""
         from .audio import SNR_OFF
         conv = self.audio_converter
-        wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names], trim=trim_args(self.paras))
+        wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names], trim=trim_args(self.paras), loudness=loudness_args(self.paras))
         if self.feat == 'mfcc':
             return conv.extract_mfcc_batch(wb), 1 + wb.lens // conv.hop_length_mfcc, wb.order
         if self.feat == 'f0':
@@ -548,8 +669,8 @@ class McdScorer:
         host read"""
         from .metrics import f0_scores, mcd
         conv = self.audio_converter
-        ws = conv.load_batch([os.path.join(self.syn_dir, f) for f, _, _ in pairs], trim=trim_args(self.paras))
-        wr = conv.load_batch([os.path.join(self.ref_dir, r) for _, _, r in pairs], trim=trim_args(self.paras))
+        ws = conv.load_batch([os.path.join(self.syn_dir, f) for f, _, _ in pairs], trim=trim_args(self.paras), loudness=loudness_args(self.paras))
+        wr = conv.load_batch([os.path.join(self.ref_dir, r) for _, _, r in pairs], trim=trim_args(self.paras), loudness=loudness_args(self.paras))
         fs, fr = 1 + ws.lens // conv.hop_length_mfcc, 1 + wr.lens // conv.hop_length_mfcc
         cs, cr = conv.extract_mfcc_batch(ws), conv.extract_mfcc_batch(wr)
         # both batches are sorted by length: bring the recordings into the row order of the synthesised side
@@ -879,7 +1000,8 @@ class Transcriber(BaseSolver):
         """channel 0 of the files `names` of the .wav directory as one WaveBatch on the device (AudioConverter.load_batch); with
         --resample a file at another rate is converted on the GPU, without it it raises"""
         return self.audio_converter.load_batch([os.path.join(self.wav_dir, f) for f in names],
-                                               resample=bool(getattr(self.paras, 'resample', False)), trim=trim_args(self.paras))
+                                               resample=bool(getattr(self.paras, 'resample', False)), trim=trim_args(self.paras),
+                                               loudness=loudness_args(self.paras))
 
     def transcribe_batch(self, waves):
         """waves: 1-D waveforms on the device (or a WaveBatch) -> (hyp, hyp_len, score) as numpy arrays in the order of `waves`"""
@@ -1082,7 +1204,7 @@ class Synthesiser(BaseSolver):
         if getattr(self.paras, 'gen_wav', False):
             use_mel = getattr(self.paras, 'gen_wav_feat', 'linear') == 'mel'
             src = mel if use_mel else lin
-            wavs = conv.vocode_batch([src[i, :frames] for i, (_, frames) in enumerate(kept)], 'mel' if use_mel else 'spec')
+            wavs = vocode(conv, [src[i, :frames] for i, (_, frames) in enumerate(kept)], 'mel' if use_mel else 'spec', self.paras)
             for (stem, _), w in zip(kept, wavs):
                 write_wav(stem + '-pred.wav', w, conv.sr)
         return rows
@@ -1199,7 +1321,7 @@ class TtsTrainer(BaseSolver):
             self.config['data']['corpus'], self.audio_converter, self.r, splits, batch_sizes, seed=int(getattr(pa, 'seed', 0)),
             rank=int(os.environ.get('RANK', 0)), world=int(os.environ.get('WORLD_SIZE', 1)), resample=bool(getattr(pa, 'resample', False)),
             max_frames=getattr(pa, 'max_frames', None), max_gb=getattr(pa, 'corpus_max_gb', None), verbose=self.verbose,
-            trim=trim_args(pa))
+            trim=trim_args(pa), loudness=loudness_args(pa))
         self.vocab_size, self.n_spkr = self.corpus.vocab_size, self.corpus.n_spkr
         return self.corpus_sets
 
@@ -1789,7 +1911,7 @@ class VqvaeTrainer(TtsTrainer):
             raise ValueError('--unpair-wav-dir: data.audio has %d mels, the model %d' % (self.audio_converter.n_mels, self.n_mels))
         paths = [os.path.join(wav_dir, f) for f in files]
         self.unpair_waves = [self.audio_converter.load_batch(paths[i:i + Bu], resample=bool(getattr(self.paras, 'resample', False)),
-                                                             trim=trim_args(self.paras))
+                                                             trim=trim_args(self.paras), loudness=loudness_args(self.paras))
                              for i in range(0, len(paths), Bu)]
         self.unpair_set = [mk(len(wb.lens), uframes, 500000 + 1000 * rank + i + seed) for i, wb in enumerate(self.unpair_waves)]
 
