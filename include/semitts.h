@@ -1579,6 +1579,49 @@ int st_loudness_batch(const st_wave_batch* w, int fs, const double* tables, doub
                       double* ws, void* stream);
 int st_wave_gain(const st_wave_batch* w, const float* stats /* (B, 8) */, float* out_f32, int16_t* out_i16, void* stream);
 
+/* ------------------------------------------------------------------ ABX phone discrimination: pairwise DTW of short items, triple counts
+ * Not a step of the reference (it scores no representation); the measure of ZeroSpeech / Libri-light (semi_tts_amd.metrics.abx,
+ * main.py --abx-ali-dir).
+ * st_dtw_pairs: the path-normalised DTW distance of P pairs of items of one packed feature buffer.  feat(r, k) = feat[r st + k], n_rows
+ * rows of D columns, row stride st >= D floats.  Item q is the rows [item_start[q], item_start[q] + item_len[q]) (device int32, n_items
+ * entries); pair p is item a = pair_a[p] (n rows) against item b = pair_b[p] (m rows) (device int32, P entries).
+ * Frame distance d(i, j) of row i of a (x) and row j of b (y), fp32, sums over ascending k (fma contraction not specified):
+ *   ST_ABX_EUCLID   sqrtf(sum_k (x_k - y_k)^2) -- st_dtw_batch's distance at scale 1.
+ *   ST_ABX_ANGULAR  u = x / ||x|| (x times the rounded reciprocal of sqrtf(sum x_k^2), one reciprocal a row; a zero row stays zero),
+ *                   d = (2 / pi) atan2f(||u - v||, ||u + v||), in [0, 1]: the angle, in the form that keeps its digits for near-parallel
+ *                   frames (acos of an fp32 cosine loses half of them there).  A zero row is at 0.5 from a non-zero row, at 0 from a zero row.
+ *   ST_ABX_KL       0.5 sum_k (x_k - y_k) (logf(x_k + 1e-10) - logf(y_k + 1e-10)), the symmetrised KL divergence of two probability
+ *                   rows with the project's log(p + 1e-10); a negative entry makes the pair NaN.
+ * Recurrence and ties as st_dtw_batch: D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), ONE fp32 add; the diagonal wins, then
+ * (i-1, j), then (i, j-1) (a candidate replaces the best only when strictly smaller).  The path length is carried beside the cost:
+ * L(0, 0) = 1, L(i, j) = L(chosen predecessor) + 1 -- the length of the path a trace-back would find; no back-pointers exist.
+ * Outputs: cost (P) = D(n-1, m-1) and path_len (P) = L(n-1, m-1) (either may be NULL); dist (P) = cost / (float)path_len, one correctly
+ * rounded fp32 division (the DTW of ABXpy / Libri-light's ABX evaluation).
+ * Without raising, dist and cost NaN and path_len 0 for a pair with: an item index outside [0, n_items); an item_len outside
+ * [1, max_len]; an item reaching outside [0, n_rows); a NaN among the rows of either item.  Nothing outside feat is read in any case.
+ * A pair depends on its two items alone: bitwise repeatable, independent of P, of its position in the list, of the other pairs, of
+ * max_len and of the rows that belong to neither item.  d(a, b) and d(b, a) have the same cost, but under exact ties they may differ in
+ * path_len (the rule prefers (i-1, j) to (i, j-1), which swaps with the sides) and hence in dist.
+ * Limits (-22 past them): P >= 1, n_items >= 1, n_rows >= 1, 1 <= D <= 512, 1 <= max_len <= 64, metric one of the three, st >= D.
+ * One launch (the waves stride over the pairs when P passes one grid), no workspace, no atomics, no host read. */
+#define ST_ABX_EUCLID 0
+#define ST_ABX_ANGULAR 1
+#define ST_ABX_KL 2
+int st_dtw_pairs(const float* feat, long n_rows, int D, long st, const int32_t* item_start, const int32_t* item_len, int n_items,
+                 const int32_t* pair_a, const int32_t* pair_b, int P, int metric, int max_len,
+                 float* dist /* (P) */, float* cost /* (P) or NULL */, int32_t* path_len /* (P) or NULL */, void* stream);
+
+/* st_abx_count: ABX triple counts from finished distances.  dmat: dmat_len floats, the dense symmetric (n_c, n_c) matrices of the
+ * cells laid end to end (the diagonal is never read).  blk (NB, 6) int64 on the device: (mat_off, n_c, a_lo, a_hi, b_lo, b_hi) -- the
+ * matrix of the block's cell starts at dmat[mat_off]; classes a and b are the local index ranges [a_lo, a_hi) and [b_lo, b_hi), clamped
+ * into [0, n_c] (an inverted range is empty).  count (NB, 4) int64 = (wrong, tied, nan, triples) over all X, A in a with A != X (by
+ * index) and all B in b: nan = the triples with a NaN in d(A, X) or d(B, X), counted nowhere else; wrong = #{d(A, X) > d(B, X)};
+ * tied = #{d(A, X) == d(B, X)}; triples = n_a (n_a - 1) n_b.  d(., X) is read from row X of the matrix.
+ * A block whose matrix does not lie inside dmat (mat_off < 0, n_c < 0 or above 2^20, mat_off + n_c^2 > dmat_len) reads nothing and
+ * gets -1 in all four columns.  Integer sums, no atomics: exact and repeatable.  One launch, one workgroup a block (blocks with more
+ * triples than threads are strided over).  Limits (-22): NB >= 1, dmat_len >= 1. */
+int st_abx_count(const float* dmat, long dmat_len, const int64_t* blk /* (NB, 6) */, int NB, int64_t* count /* (NB, 4) */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

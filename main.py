@@ -32,6 +32,7 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --score-phn-dir HYP --score-ref-dir REF [--vocab FILE --score-ignore 0,1,2 --score-nbest --score-ali --batch-size 64]
     python main.py --config config/supervised.yaml --loudness-wav-dir DIR [--loudness-out DIR2 --loudness-target -23 --loudness-peak -1 --loudness-max-gain 30]
     python main.py --config config/semi-multi-spkr-paired-data.yaml --corpus --normalize-loudness [--loudness-target -23]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --abx-ali-dir ALI --abx-wav-dir WAVS [--abx-feat mfcc|mel|latent|code --load ckpt.pth]
 `--corpus` trains on the reference's corpus layout (semi_tts_amd/corpus.py: partition table, map table, speaker map, vocabulary file and
 <path>/<speaker>/<id>.wav, src/data.py + corpus/vctk.py + src/text.py): each split of the rank's shard is read once and stays on the device as
 one packed buffer, every fetch extracts mel / augmented mel / linear from it on the GPU, `--dev-batches K` (-1: all) validates on the real dev
@@ -77,6 +78,10 @@ directory -- what `--transcribe-wav-dir` writes, as it is -- and finds where eac
 `--transcribe-wav-dir` writes -- against reference transcripts by Levenshtein alignment with its trace-back on the GPU (solver.PhnScorer,
 semi_tts_amd.metrics.align_transcripts): per.csv with correct / substituted / deleted / inserted phones per file, confusion.npy,
 confusions.csv, phones.csv, with `--score-ali` <key>.ops per file and with `--score-nbest` the lowest error over the paths of a file.
+`--abx-ali-dir ALI --abx-wav-dir WAVS` (not a mode of the reference) scores a representation itself -- MFCC, mel, the speech-encoder latents or
+the codebook posteriors -- by the ABX phone-discrimination error of ZeroSpeech / Libri-light: the phone tokens the .ali files of
+`--align-wav-dir` delimit are compared within speaker and context by path-normalised DTW, one wave per pair on the GPU (solver.AbxScorer,
+semi_tts_amd.metrics.abx, st_dtw_pairs + st_abx_count): abx.csv with the error of every ordered phone pair, abx_phones.csv with the tokens used.
 """
 import argparse
 import os
@@ -232,6 +237,25 @@ parser.add_argument('--score-ignore', default=None, type=str, help='--score-phn-
 parser.add_argument('--score-nbest', action='store_true', help='--score-phn-dir: score every line of a hypothesis file (the paths of --top-paths) and add '
                     'nbest_per,nbest_path to per.csv: the lowest error over the paths and the first path that attains it')
 parser.add_argument('--score-ali', action='store_true', help='--score-phn-dir: also write the alignment of every file as <key>.ops (REF / HYP / OP lines)')
+parser.add_argument('--abx-ali-dir', default=None, type=str, help='score a representation by the ABX phone-discrimination error on the GPU: every '
+                    '<stem>.ali of this directory (the files of --align-wav-dir) gives the phone boundaries of --abx-wav-dir/<stem>.wav; writes '
+                    '<logdir>/<name>/abx.csv (phone_a,phone_b,cells,triples,error) and abx_phones.csv (phone,tokens,items,too_short,too_long)')
+parser.add_argument('--abx-wav-dir', default=None, type=str, help='--abx-ali-dir: the directory of the waveforms')
+parser.add_argument('--abx-feat', default=None, choices=('mfcc', 'mel', 'latent', 'code'), help='--abx-ali-dir: the representation scored: MFCC '
+                    '(default) or clean mel (no checkpoint, no model), or the speech-encoder latents / codebook posteriors of the model of '
+                    '--load (the synthetic weights without it)')
+parser.add_argument('--abx-metric', default=None, choices=('angular', 'kl', 'euclid'), help='--abx-ali-dir: the frame distance under the DTW '
+                    '(default angular; kl for --abx-feat code)')
+parser.add_argument('--abx-context', default=None, choices=('triphone', 'none'), help='--abx-ali-dir: compare tokens that share speaker, previous '
+                    'and next symbol (triphone, default; the utterance\'s edge is a symbol of its own) or the speaker alone (none)')
+parser.add_argument('--abx-spk-map', default=None, type=str, help='--abx-ali-dir: a key,speaker CSV (key: the file\'s stem); without it all files '
+                    'are one speaker.  ABX is taken within speaker only')
+parser.add_argument('--abx-ignore', default=None, type=str, help='--abx-ali-dir: comma-separated symbols that are never items (they still count as '
+                    'context)')
+parser.add_argument('--abx-max-items', default=None, type=int, help='--abx-ali-dir: the most tokens of one phone in one cell; above it a seeded '
+                    'subsample (--seed) is scored (default 50)')
+parser.add_argument('--abx-min-frames', default=None, type=int, help='--abx-ali-dir: tokens of fewer feature rows are dropped (default 1; tokens '
+                    'of more than 64 rows always are)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -304,7 +328,7 @@ def parse_args(argv=None):
     if paras.vocode_feat is None:
         paras.vocode_feat = 'spec'
     if (paras.resample and paras.unpair_wav_dir is None and paras.transcribe_wav_dir is None and paras.align_wav_dir is None and not paras.corpus
-            and paras.loudness_wav_dir is None):
+            and paras.loudness_wav_dir is None and paras.abx_ali_dir is None):
         parser.error('--resample converts the files of --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir, or the splits of --corpus; it needs one '
                      'of them')
     if paras.resample_wav_dir is not None:
@@ -405,7 +429,7 @@ def parse_args(argv=None):
         if paras.segment_file is not None:
             parser.error('--trim-silence does not combine with --segment-file: its times refer to the untrimmed file')
         if not (paras.corpus or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir',
-                                                                            'loudness_wav_dir'))):
+                                                                            'loudness_wav_dir', 'abx_ali_dir'))):
             parser.error('--trim-silence trims what --corpus, --unpair-wav-dir, --transcribe-wav-dir, --mcd-wav-dir or --feat-wav-dir load; it needs one '
                          'of them')
     elif paras.trim_wav_dir is None and any(v is not None for v in (paras.trim_top_db, paras.trim_frame_length, paras.trim_hop, paras.trim_pad_ms)):
@@ -435,7 +459,7 @@ def parse_args(argv=None):
         if paras.segment_file is not None:
             parser.error('--normalize-loudness does not combine with --segment-file in this version (times would not change; the listed modes only)')
         writes = paras.vocode_dir is not None or (paras.gen_wav and (paras.gen_specgram or paras.synth_phn_dir is not None))
-        if not (paras.corpus or writes or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir'))):
+        if not (paras.corpus or writes or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir', 'abx_ali_dir'))):
             parser.error('--normalize-loudness normalises what --corpus, --unpair-wav-dir, --transcribe-wav-dir, --feat-wav-dir or --mcd-wav-dir load and what '
                          '--gen-specgram --gen-wav, --vocode-dir or --synth-phn-dir --gen-wav write; it needs one of them')
     elif paras.loudness_wav_dir is None and any(v is not None for v in (paras.loudness_target, paras.loudness_peak, paras.loudness_max_gain)):
@@ -466,6 +490,27 @@ def parse_args(argv=None):
             parser.error('--score-ignore takes at most 64 ids in [0, 2^31)')
     elif paras.score_ref_dir is not None or paras.score_ignore is not None or paras.score_nbest or paras.score_ali:
         parser.error('--score-ref-dir, --score-ignore, --score-nbest and --score-ali belong to --score-phn-dir; they need that flag')
+    abx_flags = ('abx_wav_dir', 'abx_feat', 'abx_metric', 'abx_context', 'abx_spk_map', 'abx_ignore', 'abx_max_items', 'abx_min_frames')
+    if paras.abx_ali_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir', 'loudness_wav_dir', 'score_phn_dir', 'corpus'):
+            if getattr(paras, flag):
+                parser.error('--abx-ali-dir does not combine with --%s' % flag.replace('_', '-'))
+        if paras.dev_batches != 0:
+            parser.error('--abx-ali-dir does not combine with --dev-batches')
+        if paras.config is None or paras.abx_wav_dir is None:
+            parser.error('--abx-ali-dir needs --config (its data.audio and model) and --abx-wav-dir DIR (the waveforms)')
+        paras.abx_feat = paras.abx_feat or 'mfcc'
+        paras.abx_metric = paras.abx_metric or ('kl' if paras.abx_feat == 'code' else 'angular')
+        paras.abx_context = paras.abx_context or 'triphone'
+        paras.abx_ignore = tuple(s.strip() for s in (paras.abx_ignore or '').split(',') if s.strip())
+        paras.abx_max_items = 50 if paras.abx_max_items is None else paras.abx_max_items
+        paras.abx_min_frames = 1 if paras.abx_min_frames is None else paras.abx_min_frames
+        if paras.abx_max_items < 2 or not 1 <= paras.abx_min_frames <= 64:
+            parser.error('--abx-max-items must be >= 2 and --abx-min-frames in [1, 64]')
+    elif any(getattr(paras, f) is not None for f in abx_flags):
+        parser.error('--abx-wav-dir, --abx-feat, --abx-metric, --abx-context, --abx-spk-map, --abx-ignore, --abx-max-items and --abx-min-frames belong to '
+                     '--abx-ali-dir; they need that flag')
     if paras.gen_wav_feat != 'linear' and not ((paras.gen_specgram or paras.synth_phn_dir is not None) and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
@@ -555,6 +600,9 @@ def main(argv=None):
         mode = 'test'
     elif paras.mcd_wav_dir is not None:
         from semi_tts_amd.solver import McdScorer as Solver
+        mode = 'test'
+    elif paras.abx_ali_dir is not None:
+        from semi_tts_amd.solver import AbxScorer as Solver
         mode = 'test'
     elif paras.score_phn_dir is not None:
         from semi_tts_amd.solver import PhnScorer as Solver

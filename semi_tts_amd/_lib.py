@@ -428,6 +428,8 @@ SIGNATURES = {
     'st_loudness_run_length': [I],
     'st_loudness_batch': [C.POINTER(StWaveBatch), I, P, C.c_double, C.c_double, C.c_double, P, I, P, P, P, P],
     'st_wave_gain': [C.POINTER(StWaveBatch), P, P, P, P],
+    'st_dtw_pairs': [P, C.c_long, I, C.c_long, P, P, I, P, P, I, I, I, P, P, P, P],
+    'st_abx_count': [P, C.c_long, P, I, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,

@@ -17,6 +17,8 @@ TRIM_SOURCES = ['trim.hip']
 SCORE_SOURCES = ['edit_align.hip']
 # the loudness kernels (st_loudness_batch, st_wave_gain), listed apart for the same reason
 LOUDNESS_SOURCES = ['loudness.hip']
+# the ABX kernels (st_dtw_pairs, st_abx_count), listed apart for the same reason
+ABX_SOURCES = ['abx.hip']
 
 
 def _hipcc():
@@ -41,7 +43,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES:
+    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES + ABX_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

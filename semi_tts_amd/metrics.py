@@ -228,3 +228,71 @@ def nbest_per(dist):
     k = torch.arange(N, device=dist.device).expand_as(dist)
     path = torch.where(dist == best.unsqueeze(1), k, torch.full_like(k, N)).min(dim=1).values
     return NBest(best, path)
+
+
+def _abx_table(what, name, v, dev):
+    """an item / pair table as a contiguous int32 tensor on dev: a device tensor is taken as it is, host integers are copied over"""
+    if torch.is_tensor(v) and v.is_cuda:
+        return v
+    import numpy as np
+    host = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+    if host.ndim != 1 or host.dtype.kind not in 'iu' or (host.size and (host.min() < -2 ** 31 or host.max() >= 2 ** 31)):
+        raise ValueError('%s: %s must be a 1-d sequence of int32 integers (got %s %s)' % (what, name, host.shape, host.dtype))
+    return torch.from_numpy(host.astype(np.int32)).to(dev)
+
+
+def dtw_pairs(feat, item_start, item_len, pair_a, pair_b, metric='angular', want_cost=False, max_len=None):
+    """Path-normalised DTW distances of many pairs of short items of one packed feature buffer, one launch (st_dtw_pairs,
+    semi_tts_amd/csrc/abx.hip): feat (n_rows, D) float32 on one GPU; item q is the rows [item_start[q], item_start[q] + item_len[q]),
+    1 .. 64 of them; pair p compares item pair_a[p] with item pair_b[p].  The tables are int32 device tensors, or host integer
+    sequences (copied over).  metric: 'angular' (the angle between the frames over pi, formed as 2 atan2(|u - v|, |u + v|) / pi of the
+    unit vectors, in [0, 1]), 'kl' (the symmetrised KL divergence of probability rows) or 'euclid'; the recurrence and the tie rule are dtw's, the path
+    length is carried beside the cost and dist = cost / path_len, the DTW of ABXpy and Libri-light's ABX evaluation.
+    max_len sizes the kernel's LDS: None takes the longest item of a host item_len and 64 for a device tensor.
+    -> dist (P,) float32, or (dist, cost, path_len) with want_cost: device tensors.  A pair with a bad index, an item outside
+    [1, max_len] rows or outside feat, or a NaN among its rows gets NaN (path_len 0).  Bad arguments raise ValueError before the
+    device is touched."""
+    if not torch.is_tensor(feat) or not feat.is_cuda:
+        raise ValueError('dtw_pairs: feat must be a (n_rows, D) float32 GPU tensor (got %s)' % (type(feat).__name__ if not torch.is_tensor(feat) else feat.device))
+    if max_len is None:
+        max_len = ops.ABX_MAX_LEN
+        if not (torch.is_tensor(item_len) and item_len.is_cuda) and len(item_len):
+            max_len = min(max(int(max(int(v) for v in item_len)), 1), ops.ABX_MAX_LEN)
+    tabs = [_abx_table('dtw_pairs', n, v, feat.device) for n, v in (('item_start', item_start), ('item_len', item_len), ('pair_a', pair_a), ('pair_b', pair_b))]
+    return ops.dtw_pairs(feat, tabs[0], tabs[1], tabs[2], tabs[3], metric, max_len, want_cost)
+
+
+AbxResult = collections.namedtuple('AbxResult', 'blocks block_cell block_a block_b counts table score pairs keep')
+
+
+def abx(feat, item_start, item_len, label, cell, metric='angular', max_items=50, seed=0):
+    """ABX phone-discrimination error of the items of a packed feature buffer (see semi_tts_amd.abx for the terms): feat (n_rows, D)
+    float32 on one GPU; item_start / item_len / label / cell host integer sequences, one entry per item (label: the phone, cell: the
+    context within which items are compared).  A (cell, label) group above max_items is subsampled (abx.subsample, seeded).  Every
+    unordered pair of a cell goes through dtw_pairs once (sorted by the first item), is mirrored into the cell's dense matrix by one
+    indexed store, and st_abx_count counts, per ordered (a, b) of a cell, the triples X, A in a, B in b with d(A, X) > d(B, X) (wrong)
+    and == (tied).  The counts are read once and aggregated on the host in float64 (abx.aggregate: block error
+    (wrong + tied / 2) / (triples - nan), mean over cells, then over the ordered phone pairs).
+    -> AbxResult(blocks (NB, 6), block_cell, block_a, block_b, counts (NB, 4) int64 numpy, table [(a, b, cells, triples, error)],
+    score, pairs = the DTW pairs computed, keep = the items used).  Without a block: empty tables and score NaN."""
+    import numpy as np
+    from . import abx as A
+    if not torch.is_tensor(feat) or not feat.is_cuda or feat.dim() != 2 or feat.dtype != torch.float32:
+        raise ValueError('abx: feat must be a (n_rows, D) float32 GPU tensor')
+    start, length = np.asarray(item_start, np.int64).reshape(-1), np.asarray(item_len, np.int64).reshape(-1)
+    if not (len(start) == len(length) == len(label) == len(cell)):
+        raise ValueError('abx: %d starts, %d lengths, %d labels, %d cells: one of each per item' % (len(start), len(length), len(label), len(cell)))
+    pl = A.plan(label, cell, max_items, seed)
+    if len(pl.blocks) == 0:
+        return AbxResult(pl.blocks, pl.block_cell, pl.block_a, pl.block_b, np.zeros((0, 4), np.int64), [], float('nan'), 0, pl.keep)
+    dev = feat.device
+    max_len = int(min(max(length[pl.keep].max(), 1), ops.ABX_MAX_LEN))
+    tabs = torch.from_numpy(np.concatenate([start, length]).astype(np.int32)).to(dev)
+    pairs = torch.from_numpy(np.concatenate([pl.pair_a, pl.pair_b])).to(dev)
+    n, P = len(start), len(pl.pair_a)
+    dist = ops.dtw_pairs(feat, tabs[:n], tabs[n:], pairs[:P], pairs[P:], metric, max_len)
+    dmat = torch.zeros(pl.dmat_len, device=dev, dtype=torch.float32)
+    dmat[torch.from_numpy(np.concatenate([pl.pos_ab, pl.pos_ba])).to(dev)] = torch.cat([dist, dist])        # (the one mirrored store)
+    counts = ops.abx_count(dmat, torch.from_numpy(pl.blocks).to(dev)).cpu().numpy()                          # (the one host read)
+    agg = A.aggregate(pl.block_a, pl.block_b, counts)
+    return AbxResult(pl.blocks, pl.block_cell, pl.block_a, pl.block_b, counts, agg.table, agg.score, P, pl.keep)

@@ -1157,6 +1157,80 @@ def dtw(x, y, x_len=None, y_len=None, cols=None, scale=1.0, want_path=True):
     return total, path_len, path
 
 
+ABX_MAX_LEN, ABX_MAX_D = 64, 512         # st_dtw_pairs' limits
+ABX_METRICS = {'euclid': 0, 'angular': 1, 'kl': 2}
+
+
+def _abx_ints(what, name, t, dev, dtype=torch.int32, dim=1):
+    if (not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dim() != dim or t.dtype != dtype or not t.is_contiguous()):
+        raise ValueError('%s: %s must be a contiguous %d-d %s tensor on the device of the features (got %s)'
+                         % (what, name, dim, str(dtype).replace('torch.', ''),
+                            '%s %s on %s' % (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+
+
+def dtw_pairs(feat, item_start, item_len, pair_a, pair_b, metric='angular', max_len=ABX_MAX_LEN, want_cost=False):
+    """Path-normalised DTW distance of P pairs of items of one packed feature buffer, one wave a pair (see st_dtw_pairs): feat (n_rows, D)
+    float32 on one GPU with unit column stride (a column slice of a wider tensor keeps its row stride); item q is the rows
+    [item_start[q], item_start[q] + item_len[q]); pair p is item pair_a[p] against item pair_b[p] -- four contiguous int32 device tensors.
+    metric: 'euclid', 'angular' or 'kl' (or its number).  max_len: the longest item the launch takes (it sizes LDS; at most 64).
+    -> dist (P,) float32, or (dist, cost (P,) float32, path_len (P,) int32) with want_cost; NaN / 0 for a pair the kernel refuses (a bad
+    index, a length outside [1, max_len], rows outside feat, a NaN among its rows).  One launch, no host read.  Anything the C entry
+    point would refuse raises ValueError before the device is touched."""
+    if not torch.is_tensor(feat) or not feat.is_cuda or feat.dim() != 2 or feat.dtype != torch.float32:
+        raise ValueError('dtw_pairs: feat must be a (n_rows, D) float32 GPU tensor (got %s)'
+                         % ('%s %s on %s' % (tuple(feat.shape), feat.dtype, feat.device) if torch.is_tensor(feat) else type(feat).__name__))
+    dev = feat.device
+    n_rows, D = feat.shape
+    if n_rows < 1 or not 1 <= D <= ABX_MAX_D:
+        raise ValueError('dtw_pairs: feat is %s: n_rows >= 1 and 1 <= D <= %d' % (tuple(feat.shape), ABX_MAX_D))
+    st = feat.stride(0) if n_rows > 1 else max(feat.stride(0), D)          # (a 1-long dimension's stride is free)
+    if (feat.stride(1) != 1 and D > 1) or st < D:
+        raise ValueError('dtw_pairs: feat has strides %s: the columns need stride 1 and the rows at least D = %d floats apart'
+                         % (tuple(feat.stride()), D))
+    if isinstance(metric, str):
+        if metric not in ABX_METRICS:
+            raise ValueError('dtw_pairs: metric %r is none of %s' % (metric, sorted(ABX_METRICS)))
+        metric = ABX_METRICS[metric]
+    if isinstance(metric, bool) or not isinstance(metric, (int, np.integer)) or int(metric) not in ABX_METRICS.values():
+        raise ValueError('dtw_pairs: metric %r is none of %s' % (metric, sorted(ABX_METRICS)))
+    if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)) or not 1 <= int(max_len) <= ABX_MAX_LEN:
+        raise ValueError('dtw_pairs: max_len must be an integer in [1, %d] (got %r)' % (ABX_MAX_LEN, max_len))
+    for name, t in (('item_start', item_start), ('item_len', item_len), ('pair_a', pair_a), ('pair_b', pair_b)):
+        _abx_ints('dtw_pairs', name, t, dev)
+    n_items, P = item_start.shape[0], pair_a.shape[0]
+    if n_items < 1 or item_len.shape[0] != n_items:
+        raise ValueError('dtw_pairs: %d item starts, %d item lengths: at least one item, as many of each'
+                         % (n_items, item_len.shape[0]))
+    if P < 1 or pair_b.shape[0] != P or P >= 2 ** 31:
+        raise ValueError('dtw_pairs: %d first items, %d second items: at least one pair, below 2^31, as many of each' % (P, pair_b.shape[0]))
+    lib = _lib.load()
+    dist = torch.empty(P, device=dev, dtype=torch.float32)
+    cost = torch.empty(P, device=dev, dtype=torch.float32) if want_cost else None
+    path_len = torch.empty(P, device=dev, dtype=torch.int32) if want_cost else None
+    check(lib.st_dtw_pairs(_p(feat), n_rows, D, st, _p(item_start, torch.int32), _p(item_len, torch.int32), n_items, _p(pair_a, torch.int32),
+                           _p(pair_b, torch.int32), P, int(metric), int(max_len), _p(dist), _p(cost), _p(path_len, torch.int32),
+                           stream_handle()), 'st_dtw_pairs')
+    return (dist, cost, path_len) if want_cost else dist
+
+
+def abx_count(dmat, blk):
+    """ABX triple counts from finished distances (see st_abx_count): dmat, a contiguous 1-d float32 GPU tensor holding the dense symmetric
+    matrices of the cells end to end; blk (NB, 6) int64 on the same device, rows (mat_off, n_c, a_lo, a_hi, b_lo, b_hi).
+    -> count (NB, 4) int64 = (wrong, tied, nan, triples) per block, a device tensor; one launch, exact, no host read.  Bad arguments
+    raise ValueError before the device is touched."""
+    if not torch.is_tensor(dmat) or not dmat.is_cuda or dmat.dim() != 1 or dmat.dtype != torch.float32 or not dmat.is_contiguous():
+        raise ValueError('abx_count: dmat must be a contiguous 1-d float32 GPU tensor (got %s)'
+                         % ('%s %s on %s' % (tuple(dmat.shape), dmat.dtype, dmat.device) if torch.is_tensor(dmat) else type(dmat).__name__))
+    _abx_ints('abx_count', 'blk', blk, dmat.device, torch.int64, 2)
+    NB = blk.shape[0]
+    if blk.shape[1] != 6 or NB < 1 or NB >= 2 ** 31 or dmat.shape[0] < 1:
+        raise ValueError('abx_count: blk is %s over %d distances: (NB, 6) with NB >= 1, at least one distance' % (tuple(blk.shape), dmat.shape[0]))
+    lib = _lib.load()
+    count = torch.empty(NB, 4, device=dmat.device, dtype=torch.int64)
+    check(lib.st_abx_count(_p(dmat), dmat.shape[0], _p(blk, torch.int64), NB, _p(count, torch.int64), stream_handle()), 'st_abx_count')
+    return count
+
+
 AE_MAX_S, AE_MAX_L = 4096, 2048          # st_attn_endpoint's limits
 
 

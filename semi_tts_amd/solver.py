@@ -727,6 +727,151 @@ class McdScorer:
         return len(vals)
 
 
+ABX_FEATS = ('mfcc', 'mel', 'latent', 'code')
+
+
+def abx_metric(paras):
+    """--abx-metric, or its default: kl for the codebook posteriors (probability rows), angular for everything else"""
+    return getattr(paras, 'abx_metric', None) or ('kl' if getattr(paras, 'abx_feat', 'mfcc') == 'code' else 'angular')
+
+
+class AbxScorer:
+    """main.py --abx-ali-dir DIR --abx-wav-dir WAVS [--abx-feat mfcc|mel|latent|code --abx-metric angular|kl|euclid --abx-context
+    triphone|none --abx-spk-map FILE --abx-ignore a,b --abx-max-items 50 --abx-min-frames 1]: the ABX phone-discrimination error of a
+    representation, within speaker (semi_tts_amd.abx for the terms, metrics.abx for the computation).  Every <stem>.ali of DIR (what
+    --align-wav-dir writes) names the phone boundaries of WAVS/<stem>.wav.  The features of the files (sorted by name, batches of
+    --batch-size) are extracted on the GPU -- mfcc: AudioConverter.extract_mfcc_batch, mel: the clean extract_batch, neither needs a
+    checkpoint or a model; latent / code: VQVAE.represent of the model of --load, or of the synthetic weights -- and packed into one
+    (rows, D) device buffer; every token becomes an item of that buffer (abx.utterance_items at the feature's frame period:
+    hop_length_mfcc / sr, hop_length / sr, time_reduce_factor hop_length / sr), keyed into cells by speaker and context; one
+    metrics.abx call scores them.  -> <logdir>/<name>/abx.csv (phone_a,phone_b,cells,triples,error) and abx_phones.csv
+    (phone,tokens,items,too_short,too_long), and one printed line.  A missing waveform, a malformed .ali, an .ali without tokens or a file
+    the speaker map lacks stops the run in load_data, naming the file, before any device work."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.exp_name = getattr(paras, 'name', None) or 'synthetic'
+        self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
+        self.feat = getattr(paras, 'abx_feat', None) or 'mfcc'
+        self.metric = abx_metric(paras)
+        self.context = getattr(paras, 'abx_context', None) or 'triphone'
+        self.ignore = tuple(getattr(paras, 'abx_ignore', None) or ())
+        self.max_items = int(getattr(paras, 'abx_max_items', None) or 50)
+        self.min_frames = int(getattr(paras, 'abx_min_frames', None) or 1)
+
+    def load_data(self):
+        import wave
+        from . import abx as A
+        from .audio import load_audio_transform
+        self.ali_dir, self.wav_dir = self.paras.abx_ali_dir, self.paras.abx_wav_dir
+        self.pairs = A.ali_pairs(self.ali_dir, self.wav_dir)
+        self.alis = [A.read_ali(os.path.join(self.ali_dir, f)) for f, _, _ in self.pairs]
+        spk_map = getattr(self.paras, 'abx_spk_map', None)
+        self.speakers = ['spk'] * len(self.pairs)
+        if spk_map:
+            table = A.read_spk_map(spk_map)
+            for k, (f, stem, _) in enumerate(self.pairs):
+                key = stem if stem in table else stem.split('.')[0]
+                if key not in table:
+                    raise ValueError('--abx-spk-map %s has no row for %s' % (spk_map, f))
+                self.speakers[k] = table[key]
+        self.audio_converter = conv = load_audio_transform(**dict(self.config['data']['audio']))
+        for _, _, w in self.pairs:
+            path = os.path.join(self.wav_dir, w)
+            try:
+                with wave.open(path, 'rb') as h:
+                    sr, L = h.getframerate(), h.getnframes()
+            except (OSError, EOFError, wave.Error) as e:
+                raise ValueError('--abx-wav-dir: %s is not a readable .wav file (%s)' % (path, e))
+            if sr != conv.sr and not getattr(self.paras, 'resample', False):
+                raise ValueError('--abx-wav-dir: sample rate mismatch. Expected %d but get %d (%s); --resample converts it' % (conv.sr, sr, path))
+            if self.feat == 'mfcc' and sr == conv.sr:
+                try:
+                    conv._check_mfcc([L])
+                except ValueError as e:
+                    raise ValueError('--abx-wav-dir: %s: %s' % (path, e))
+        return self
+
+    def set_model(self):
+        self.model = None
+        if self.feat in ('latent', 'code'):
+            self.model = Transcriber(self.config, self.paras, self.mode).set_model().model
+        return self
+
+    def frame_s(self):
+        conv = self.audio_converter
+        if self.feat == 'mfcc':
+            return conv.hop_length_mfcc / float(conv.sr)
+        if self.feat == 'mel':
+            return conv.hop_length / float(conv.sr)
+        return self.model.time_reduce_factor * conv.hop_length / float(conv.sr)
+
+    def extract(self, names):
+        """the files `names` of the .wav directory -> (features (B, T_pad, D) on the device in the batch's sorted order, rows per
+        utterance, order)"""
+        from .audio import SNR_OFF
+        conv = self.audio_converter
+        wb = conv.load_batch([os.path.join(self.wav_dir, f) for f in names], resample=bool(getattr(self.paras, 'resample', False)),
+                             trim=trim_args(self.paras), loudness=loudness_args(self.paras))
+        if self.feat == 'mfcc':
+            return conv.extract_mfcc_batch(wb), 1 + wb.lens // conv.hop_length_mfcc, wb.order
+        mel, _, _ = conv.extract_batch(wb, snr=SNR_OFF, stretch=1.0)
+        frames = 1 + wb.lens // conv.hop_length
+        if self.feat == 'mel':
+            return mel, frames, wb.order
+        rep, rows = self.model.represent(mel, frames, self.feat)
+        return rep, rows.numpy(), wb.order
+
+    def features(self):
+        """-> (the packed (rows, D) device buffer of all files, the first row of every file, its rows), files in the order of self.pairs"""
+        B = max(1, int(self.paras.batch_size))
+        parts, n_rows = [], []
+        for i in range(0, len(self.pairs), B):
+            names = [w for _, _, w in self.pairs[i:i + B]]
+            feats, frames, order = self.extract(names)
+            back = np.empty(len(order), np.int64)
+            back[np.asarray(order)] = np.arange(len(order))          # the batch row of the k-th given file
+            for k in range(len(names)):
+                r = int(min(int(frames[back[k]]), feats.shape[1]))
+                parts.append(feats[back[k], :r])
+                n_rows.append(r)
+        first = np.concatenate([[0], np.cumsum(n_rows)[:-1]]).astype(np.int64)
+        return torch.cat(parts, 0).float().contiguous(), first, np.asarray(n_rows, np.int64)
+
+    def items(self, first, n_rows):
+        """-> (item_start, item_len, label ids, cell ids, the phone names of the label ids, stats per phone)"""
+        from . import abx as A
+        fs = self.frame_s()
+        rows, stats = [], {}
+        for k, ali in enumerate(self.alis):
+            its, st = A.utterance_items(ali, fs, int(n_rows[k]), self.ignore, self.min_frames)
+            for sym, v in st.items():
+                stats[sym] = [a + b for a, b in zip(stats.get(sym, [0, 0, 0, 0]), v)]
+            rows += [(sym, int(first[k]) + r0, n, A.cell_key(self.speakers[k], prev, nxt, self.context)) for sym, r0, n, prev, nxt in its]
+        names = sorted({r[0] for r in rows})
+        cells = {c: i for i, c in enumerate(sorted({r[3] for r in rows}))}
+        lab = {s: i for i, s in enumerate(names)}
+        return (np.array([r[1] for r in rows], np.int64), np.array([r[2] for r in rows], np.int64), np.array([lab[r[0]] for r in rows], np.int64),
+                np.array([cells[r[3]] for r in rows], np.int64), names, stats)
+
+    def exec(self):
+        from . import abx as A
+        from .metrics import abx
+        t0 = time.perf_counter()
+        feat, first, n_rows = self.features()
+        start, length, label, cell, names, stats = self.items(first, n_rows)
+        os.makedirs(self.logdir, exist_ok=True)
+        self.result = res = abx(feat, start, length, label, cell, self.metric, self.max_items, int(getattr(self.paras, 'seed', 0)))
+        with open(os.path.join(self.logdir, 'abx.csv'), 'w') as f:
+            f.write(A.format_abx_csv(res.table, names))
+        with open(os.path.join(self.logdir, 'abx_phones.csv'), 'w') as f:
+            f.write(A.format_phones_csv(stats))
+        print('[INFO]', 'ABX error of %s (%s, context %s): %.2f %% over %d phone pairs, %d triples, %d pairs of DTW; %s, %.2f s'
+              % (self.feat, self.metric, self.context, 100.0 * res.score, len(res.table), sum(r[3] for r in res.table), res.pairs,
+                 os.path.join(self.logdir, 'abx.csv'), time.perf_counter() - t0))
+        return len(res.table)
+
+
 SCORE_MAX_BATCH = 64                # utterances per st_edit_align call
 PER_HEADER = 'file,ref_tokens,hyp_tokens,correct,sub,del,ins,per'
 PER_NBEST_HEADER = PER_HEADER + ',nbest_per,nbest_path'

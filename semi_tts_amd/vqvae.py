@@ -184,6 +184,27 @@ class VQVAE(nn.Module):
         finally:
             self.train(was_training)
 
+    def represent(self, mel, mel_lengths, source='latent'):
+        """The representations ABX scores (metrics.abx), in eval mode without gradients (the mode is restored after).  mel (B, T, n_mels)
+        padded batch on the device, mel_lengths its valid frames per utterance (host integers).  source 'latent': the speech encoder's
+        output, what feeds the codebook; 'code': p_code, the codebook posteriors of speech_to_text.  The encoder runs on the padded batch,
+        as in transcribe; only the first encoder_lengths rows of an utterance are its own.
+        -> ((B, T', D) float32 on the device, encoder_lengths (B,) int64 host tensor clamped to T')."""
+        if source not in ('latent', 'code'):
+            raise ValueError("represent: source must be 'latent' or 'code' (got %r)" % (source,))
+        lengths = self.encoder_lengths(mel_lengths)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                if source == 'latent':
+                    out = self.asr(mel)
+                else:
+                    out = self.speech_to_text(paired_mel=mel, unpaired_mel=None)[0]
+                return out.float().contiguous(), lengths.clamp(0, out.shape[1])
+        finally:
+            self.train(was_training)
+
     def align(self, mel, mel_lengths, text, text_lengths=None, source='code'):
         """CTC forced alignment of transcripts to the speech encoder's posteriors, in eval mode without gradients (the mode is restored
         after).  mel (B, T, n_mels) padded batch on the device, mel_lengths its valid frames per utterance (host integers); text (B, L)
