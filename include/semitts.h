@@ -215,7 +215,7 @@ typedef struct st_attn_pre_job {
     const float* pm; const float* w_prev; int ld_wprev; const float* w_cum_prev;
     const float* loc_conv_w; const float* loc_lin_w; float* s_buf;
     int L, A, F, K;
-    int parts;      /* workgroups per utterance (ranges of positions): 1, 2 or 4 */
+    int parts;      /* workgroups per utterance (ranges of positions): a power of two from 2 to 64; any other value runs as 1 */
     float* cf_out;  /* optional (B, L, F): the location features of the step, kept for the backward pass */
     /* optional: a K-split partial product (st_partial_product_job, below) on the compute units the launch leaves idle -- teacher-forced
      * training hosts the tail of the decoder cell's gate reduction beside the query projection + attention pre part (B = 17..32; the
@@ -292,6 +292,35 @@ typedef struct st_attn_fin_job {
 } st_attn_fin_job;
 int st_attn_fin_fwd(const float* pq, const st_attn_fin_job* job, int B, void* stream);   /* the fin part as a launch of its own, pq (B, A) */
 int st_attn_fin_split_fwd(const float* pq, const st_attn_fin_job* job, float* workspace, int B, void* stream);
+/* The launch a forward attention call takes, from shapes and operand alignment alone (touches no memory; the launchers decide through
+ * the same code).  part: 0 st_attn_step_fwd, 1 st_attn_pre_fwd, 2 st_attn_fin_fwd, 3 st_attn_fin_split_fwd.  parts: the job's `parts`
+ * (ignored by part 0).  aligned: ST_ATTN_AL_* bits of the operands that are 16-byte aligned (set the bits of operands the part does
+ * not take).  Returns 0 and fills *out, or a refusal (out then holds what was decided before it):
+ *   vec: the 16-byte-load kernel (at_kernel<true, part>), else the scalar one;  wl_vec: W_l is fetched with 16-byte loads;
+ *   s_mfma: the pre part forms S on the matrix cores;  kp32: the conv reads 32-tap filter rows (K <= 32), else the generic loop;
+ *   lds_bytes: dynamic LDS of a workgroup;  opt_in: the launch raises the kernel's dynamic-LDS limit first (> 64 KiB);
+ *   workgroups: of the launch (part 3: of the range launch; the combine launch adds B);
+ *   parts, Lp: part 1 -- position ranges per utterance as run (a power of two from 2 to 64, anything else 1) and positions per range
+ *   (a multiple of 12); part 2 -- context slices, L; part 3 -- ranges that hold positions (trailing empty ones are dropped), ceil(L / parts);
+ *   L_64k, L_160k: parts 0..2, the last L whose image stays within 64 KiB (no opt-in) and within 160 KiB (not refused) at these dims. */
+#define ST_ATTN_AL_PM 1
+#define ST_ATTN_AL_PQ 2
+#define ST_ATTN_AL_V 4
+#define ST_ATTN_AL_WL 8
+#define ST_ATTN_AL_MEM 16
+#define ST_ATTN_AL_S 32
+#define ST_ATTN_AL_WS 64           /* the workspace of part 3 */
+#define ST_ATTN_R_DIMS (-1)        /* a dimension <= 0, or no such part */
+#define ST_ATTN_R_K_EVEN (-2)      /* the location kernel size must be odd */
+#define ST_ATTN_R_E (-3)           /* E must be a multiple of 4, at most 2048 */
+#define ST_ATTN_R_ALIGN (-4)       /* memory (always), pm / pq / v / S (A % 4 == 0), every operand of part 3 */
+#define ST_ATTN_R_LDS (-5)         /* the image exceeds 160 KiB */
+#define ST_ATTN_R_PARTS (-6)       /* part 2: 1, 2, 4 or 8 with E % (4 parts) == 0; part 3: 2..64 */
+#define ST_ATTN_R_RANGE_DIMS (-7)  /* part 3: A a multiple of 4 in 4..256, E / 4 a divisor of 512 */
+#define ST_ATTN_R_LP (-8)          /* part 3: more than 512 positions per range */
+typedef struct st_attn_fwd_query { int part; int B, L, A, E, F, K; int parts; unsigned aligned; } st_attn_fwd_query;
+typedef struct st_attn_fwd_plan { int vec, wl_vec, s_mfma, kp32; long lds_bytes; int opt_in, workgroups, parts, Lp, L_64k, L_160k; } st_attn_fwd_plan;
+int st_attn_fwd_variant(const st_attn_fwd_query* q, st_attn_fwd_plan* out);
 /* A partial product part (B, N) = x[:, kb0 .. kb0 + KB) W[:, kb0 .. kb0 + KB)^T over a k-block range of a P16 matrix (w_kbs k-blocks per row
  * tile; LSTM row order when the matrix is a cell's) and of a T16 activation buffer (x.kb0 = the range's first k-block in it): two row tiles
  * and both batch tiles per workgroup (16 < B <= 32, N % 32 == 0), N / 32 workgroups. */
@@ -766,7 +795,7 @@ typedef struct st_decoder_io {
     float* attn_s_buf;        /* (B,L,A) or NULL: split the attention step -- its location conv + W_l part for step t+1 runs inside
                                * the proj (+) gate launch of step t (st_skinny_linear_packed_attnpre_fwd), the attention launch
                                * itself starts from S (free-running fused-prenet inference) */
-    int attn_pre_parts;       /* workgroups per utterance of the pre part (1, 2, 4) */
+    int attn_pre_parts;       /* workgroups per utterance of the pre part (a power of two up to 64; anything else runs as 1) */
     int attn_fin_parts;       /* workgroups per utterance of the fin part (0/1, 2, 4, 8; E % (4*parts) == 0) */
     int defer_proj;           /* pure teacher forcing only: skip the per-step proj (+) gate launch; the caller computes mel /
                                * stop for all steps with one GEMM over xo_tape afterwards (mel_out / stop_out untouched) */

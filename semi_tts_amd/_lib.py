@@ -172,6 +172,15 @@ class StAttnStepJob(C.Structure):
                 ('Q', C.c_int), ('L', C.c_int), ('A', C.c_int), ('E', C.c_int), ('F', C.c_int), ('K', C.c_int)]
 
 
+class StAttnFwdQuery(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('part', 'B', 'L', 'A', 'E', 'F', 'K', 'parts')] + [('aligned', C.c_uint)]
+
+
+class StAttnFwdPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('vec', 'wl_vec', 's_mfma', 'kp32')] + [('lds_bytes', C.c_long)] + \
+               [(n, C.c_int) for n in ('opt_in', 'workgroups', 'parts', 'Lp', 'L_64k', 'L_160k')]
+
+
 class StPartialProductJob(C.Structure):
     _fields_ = [('packed_w', C.c_void_p), ('w_kbs', C.c_int), ('kb0', C.c_int), ('KB', C.c_int), ('x', StT16View), ('N', C.c_int),
                 ('part', C.c_void_p)]
@@ -304,6 +313,7 @@ SIGNATURES = {
     'st_attn_pre_fwd': [C.POINTER(StAttnPreJob), I, P],
     'st_packed_fwd_variant': [C.POINTER(StPackedFwdQuery), C.POINTER(StPackedFwdLaunch)],
     'st_attn_fin_fwd': [P, C.POINTER(StAttnFinJob), I, P],
+    'st_attn_fwd_variant': [C.POINTER(StAttnFwdQuery), C.POINTER(StAttnFwdPlan)],
     'st_attn_fin_split_workspace_floats': [I, I, I],
     'st_attn_fin_split_fwd': [P, C.POINTER(StAttnFinJob), P, I, P],
     'st_query_attn_fin_fwd': [P, C.POINTER(StT16View), I, P, C.c_uint, C.POINTER(StAttnFinJob), I, C.POINTER(StPartialProductJob), P],

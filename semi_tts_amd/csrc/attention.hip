@@ -3,33 +3,34 @@
 
 namespace {
 
+// ST_ATTN_AL_* bits of the operands of a launch (an operand the part does not take is NULL: aligned)
+inline unsigned at_align_bits(const AtArgs& a, const void* ws) {
+    return (st_aligned16(a.pm) ? ST_ATTN_AL_PM : 0) | (st_aligned16(a.pq) ? ST_ATTN_AL_PQ : 0) | (st_aligned16(a.v) ? ST_ATTN_AL_V : 0) |
+           (st_aligned16(a.loc_lin_w) ? ST_ATTN_AL_WL : 0) | (st_aligned16(a.memory) ? ST_ATTN_AL_MEM : 0) |
+           (st_aligned16(a.s_buf) ? ST_ATTN_AL_S : 0) | (st_aligned16(ws) ? ST_ATTN_AL_WS : 0);
+}
+
 template <int PART>
 int at_launch(const AtArgs& a, hipStream_t stream) {
-    ST_CHECK_ARG(a.B > 0 && a.L > 0 && a.A > 0 && a.E > 0 && a.F > 0 && a.K > 0, "attention step: bad dims");
-    ST_CHECK_ARG(a.K % 2 == 1, "attention step: location kernel size %d must be odd", a.K);
-    ST_CHECK_ARG(a.E % 4 == 0 && a.E / 4 <= AT_THREADS, "attention step: E=%d must be a multiple of 4 and <= %d", a.E, 4 * AT_THREADS);
-    ST_CHECK_ARG(PART == 1 || st_aligned16(a.memory), "attention step: memory must be 16-byte aligned");
-    ST_CHECK_ARG((a.A % 4 != 0) || (st_aligned16(a.pm) && st_aligned16(a.pq) && st_aligned16(a.v)),
-                 "attention step: pm/pq/v must be 16-byte aligned");
+    const AtPlan pl = at_plan(PART, a.B, a.L, a.A, a.E, a.F, a.K, PART == 1 ? a.pre_parts : PART == 2 ? a.fin_parts : 1, at_align_bits(a, nullptr));
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_DIMS, "attention step: bad dims");
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_K_EVEN, "attention step: location kernel size %d must be odd", a.K);
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_PARTS, "attention step: parts=%d must be 1, 2, 4 or 8 with E=%d a multiple of 4*parts", a.fin_parts, a.E);
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_E, "attention step: E=%d must be a multiple of 4 and <= %d", a.E, 4 * AT_THREADS);
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_ALIGN, "attention step: memory, pm/pq/v and the S buffer must be 16-byte aligned");
     ST_CHECK_ARG(PART == 1 || a.ctx || a.ctx_dst[0].base, "attention step: no context output");
-    ST_CHECK_ARG(PART == 0 || (a.s_buf && ((a.A % 4 != 0) || st_aligned16(a.s_buf))), "attention step: S buffer missing / unaligned");
+    ST_CHECK_ARG(PART == 0 || a.s_buf, "attention step: S buffer missing");
     ST_CHECK_ARG(!a.h_q || (a.ada_std && a.ada_mean && a.h_adapt), "attention step: AdaIN pointers");
-    const bool vec = (a.A % 4 == 0) && (a.F % 4 == 0) && st_aligned16(a.pm) && (PART == 1 || (st_aligned16(a.pq) && st_aligned16(a.v))) &&
-                     st_aligned16(a.loc_lin_w);
-    const int pre_parts = PART == 1 && a.pre_parts > 1 ? a.pre_parts : 1;
-    const AtLds o = at_layout(a.L, a.A, a.E, a.F, a.K, PART, at_pos_per(a.L, pre_parts), PART == 1 && vec && a.F == 32 && a.A % 16 == 0);
-    const size_t lds_bytes = (size_t)o.total * sizeof(float);
-    ST_CHECK_ARG(lds_bytes <= 160 * 1024, "attention step: L=%d needs %zu B of LDS (> 160 KiB)%s", a.L, lds_bytes,
+    const size_t lds_bytes = pl.lds;
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_LDS, "attention step: L=%d needs %zu B of LDS (> 160 KiB)%s", a.L, lds_bytes,
                  PART == 0 ? "; the split form (st_attn_pre_fwd with more parts + st_attn_fin_fwd) takes longer texts" : "");
-    static bool configured = false;
-    if (!configured) {
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(at_kernel<true, PART>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ST_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(at_kernel<false, PART>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured = true;
-    }
-    const int nwg = a.B * (PART == 1 && a.pre_parts > 1 ? a.pre_parts : PART == 2 && a.fin_parts > 1 ? a.fin_parts : 1);
+    ST_CHECK_ARG(pl.code == 0, "attention step: refused (%d)", pl.code);
+    static size_t configured[2] = {0, 0};      // (both kernels are raised together, to the limit, the first time an image needs it)
+    int rc = st_lds_opt_in(reinterpret_cast<const void*>(at_kernel<true, PART>), 160 * 1024, pl.opt_in, configured[0]);
+    if (!rc) rc = st_lds_opt_in(reinterpret_cast<const void*>(at_kernel<false, PART>), 160 * 1024, pl.opt_in, configured[1]);
+    if (rc) return rc;
+    const bool vec = pl.vec;
+    const int nwg = pl.nwg;
     // (a 256-thread form of the fin part -- one wave per SIMD -- measured SLOWER: 11968 vs 10376 cycles; the serial stretches
     // are bound by dependent-issue latency, not by two waves sharing a SIMD)
     if (vec) hipLaunchKernelGGL((at_kernel<true, PART>), dim3(nwg), dim3(AT_THREADS), lds_bytes, stream, a.pq, a.pm, a.v, a.w_cum_prev, a.memory,
@@ -173,8 +174,16 @@ __global__ __launch_bounds__(AT_THREADS) void at_combine_kernel(const AcArgs a) 
         const float m = tid < P ? wsb[(size_t)tid * (4 + E)] : -INFINITY;
         const float s = tid < P ? wsb[(size_t)tid * (4 + E) + 1] : 0.0f;
         const float M = st_wave_max_dpp(m);
-        const float t = tid < P ? s * __expf(m - M) : 0.0f;
-        const float D = st_wave_sum_dpp(t);
+        // up to 8 parts -- the counts the one-launch form of the same split takes (st_query_attn_rng_fwd) -- the denominator is added
+        // part by part in the expression at_range_body uses, so that the two forms agree bit for bit (a tree over the lanes rounds it
+        // differently in the last bit, and with it every weight and the context); more parts keep the tree, whose error grows with
+        // log P and not with P
+        float D = 0.0f;
+        if (P <= 8) {
+            for (int q = 0; q < P; ++q) D += st_lane(s, q) * __expf(st_lane(m, q) - M);
+        } else {
+            D = st_wave_sum_dpp(tid < P ? s * __expf(m - M) : 0.0f);
+        }
         sc[tid] = tid < P ? __expf(m - M) / D : 0.0f;
     }
     __syncthreads();
@@ -226,6 +235,21 @@ extern "C" int st_attn_fin_fwd(const float* pq, const st_attn_fin_job* job, int 
     return at_launch<2>(a, (hipStream_t)stream);
 }
 
+// the launch a forward attention call takes (at_plan: the launchers above decide through it); touches no memory
+extern "C" int st_attn_fwd_variant(const st_attn_fwd_query* q, st_attn_fwd_plan* out) {
+    if (!q || !out) return ST_ATTN_R_DIMS;
+    memset(out, 0, sizeof(*out));
+    const AtPlan p = at_plan(q->part, q->B, q->L, q->A, q->E, q->F, q->K, q->parts, q->aligned);
+    out->vec = p.vec; out->wl_vec = p.wl_vec; out->s_mfma = p.s_mfma; out->kp32 = p.kp32;
+    out->lds_bytes = (long)p.lds; out->opt_in = p.opt_in; out->workgroups = p.nwg; out->parts = p.parts; out->Lp = p.Lp;
+    if ((p.code == 0 || p.code == ST_ATTN_R_LDS) && q->part != 3) {
+        const int E = q->part == 1 ? 4 : q->E, pp = q->part == 1 ? p.parts : 1;
+        out->L_64k = at_plan_last_L(q->part, q->A, E, q->F, q->K, pp, p.s_mfma, 64 * 1024);
+        out->L_160k = at_plan_last_L(q->part, q->A, E, q->F, q->K, pp, p.s_mfma, 160 * 1024);
+    }
+    return p.code;
+}
+
 extern "C" size_t st_attn_fin_split_workspace_floats(int B, int E, int parts) { return (size_t)B * parts * (4 + E); }
 
 // st_attn_fin_fwd with the utterance split over `job->parts` POSITION ranges (2..64) + a combine launch: for long texts, where one
@@ -236,25 +260,22 @@ extern "C" int st_attn_fin_split_fwd(const float* pq, const st_attn_fin_job* job
     ST_CHECK_ARG(job, "st_attn_fin_split_fwd: null job");
     const float* s_buf = job->s_buf; const float* memory = job->memory; const float* v = job->v;
     const int n_ctx_dst = job->n_ctx_dst, L = job->L, A = job->A, E = job->E;
-    int parts = job->parts;
     ST_CHECK_ARG(pq && s_buf && memory && job->w_cum_prev && job->w_out && job->w_cum_out && v && workspace && B > 0 && L > 0, "st_attn_fin_split_fwd: bad arguments");
     ST_CHECK_ARG(n_ctx_dst >= 0 && n_ctx_dst <= 3 && (job->ctx || n_ctx_dst > 0), "st_attn_fin_split_fwd: context outputs");
-    ST_CHECK_ARG(A % 4 == 0 && A >= 4 && A <= 256 && E % 4 == 0 && E / 4 <= AT_THREADS && AT_THREADS % (E / 4) == 0,
-                 "st_attn_fin_split_fwd: A=%d must be a multiple of 4 up to 256, E=%d / 4 a divisor of %d", A, E, AT_THREADS);
-    ST_CHECK_ARG(parts >= 2 && parts <= 64, "st_attn_fin_split_fwd: parts=%d (2..64)", parts);
-    const int Lp = (L + parts - 1) / parts;
-    ST_CHECK_ARG(Lp <= 512, "st_attn_fin_split_fwd: %d positions per part (> 512): use more parts", Lp);
-    // ceil(L / parts) positions per part can leave trailing parts EMPTY (L = 9, parts = 4: 3 + 3 + 3 + 0); an empty part would
-    // prefetch row L of its utterance -- the next utterance's, or one row past the end of s_buf for the last one.  Only the parts
-    // that hold positions are launched and combined (the workspace is sized for the requested count, which is never smaller).
-    parts = (L + Lp - 1) / Lp;
-    ST_CHECK_ARG(st_aligned16(pq) && st_aligned16(s_buf) && st_aligned16(memory) && st_aligned16(v) && st_aligned16(workspace),
-                 "st_attn_fin_split_fwd: operands must be 16-byte aligned");
+    const unsigned al = (st_aligned16(pq) ? ST_ATTN_AL_PQ : 0) | (st_aligned16(s_buf) ? ST_ATTN_AL_S : 0) | (st_aligned16(memory) ? ST_ATTN_AL_MEM : 0) |
+                        (st_aligned16(v) ? ST_ATTN_AL_V : 0) | (st_aligned16(workspace) ? ST_ATTN_AL_WS : 0) | ST_ATTN_AL_PM | ST_ATTN_AL_WL;
+    const AtPlan pl = at_plan(3, B, L, A, E, 0, 0, job->parts, al);      // (the trimmed part count: see at_plan)
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_RANGE_DIMS, "st_attn_fin_split_fwd: A=%d must be a multiple of 4 up to 256, E=%d / 4 a divisor of %d", A, E, AT_THREADS);
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_PARTS, "st_attn_fin_split_fwd: parts=%d (2..64)", job->parts);
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_LP, "st_attn_fin_split_fwd: %d positions per part (> 512): use more parts", pl.Lp);
+    ST_CHECK_ARG(pl.code != ST_ATTN_R_ALIGN, "st_attn_fin_split_fwd: operands must be 16-byte aligned");
+    ST_CHECK_ARG(pl.code == 0, "st_attn_fin_split_fwd: refused (%d)", pl.code);
+    const int parts = pl.parts, Lp = pl.Lp;
     AsArgs s;
     memset(&s, 0, sizeof(s));
     s.pq = pq; s.s_buf = s_buf; s.memory = memory; s.v = v; s.w_tmp = job->w_out; s.ld_w = job->ld_wout; s.ws = workspace;
     s.B = B; s.L = L; s.A = A; s.E = E; s.P = parts; s.Lp = Lp;
-    hipLaunchKernelGGL(at_split_kernel, dim3(B * parts), dim3(AT_THREADS), 0, (hipStream_t)stream, s);
+    hipLaunchKernelGGL(at_split_kernel, dim3(pl.nwg), dim3(AT_THREADS), 0, (hipStream_t)stream, s);
     ST_LAUNCH_CHECK();
     AcArgs c;
     memset(&c, 0, sizeof(c));

@@ -43,7 +43,7 @@ struct AtArgs {
     const float* h_q; int ld_hq; const float* ada_std; const float* ada_mean; float* h_adapt; int Q;
     float* s_buf;      // (B, L, A): S = pm + W_l cf, written by the pre part, read by the fin part
     float* cf_out;     // pre part only, optional: location features (B, L, F) of this step, saved for the backward pass
-    int pre_parts;     // pre part only: workgroups per utterance, each a contiguous range of positions (1, 2 or 4)
+    int pre_parts;     // pre part only: workgroups per utterance, each a contiguous range of positions (a power of two up to 64)
     int fin_parts;     // fin part only: workgroups per utterance, each a slice of the context dims E (1, 2, 4 or 8); every one
                        // repeats the energies + softmax (cheap), so the memory rows -- the bulk of the bytes -- are spread over more CUs
     int B, L, A, E, F, K;
@@ -92,7 +92,8 @@ __host__ __device__ inline int at_pos_per(int L, int nparts) {
 
 // part: 0 = the whole step, 1 = pre (history and conv features are held for the workgroup's OWN range of `Lr` positions only,
 // and W_l^T is not staged when S runs on the matrix cores), 2 = fin (energies + context partials only) -- so the split step has
-// no practical limit on the text length (the whole step keeps an utterance's conv features in LDS: L up to ~400)
+// no practical limit on the text length (the whole step keeps an utterance's conv features in LDS: at A = 256, E = 512, F = 32,
+// K = 31 its image reaches 160 KiB at L = 804; st_attn_fwd_variant reports the limit of any dims)
 __host__ __device__ inline AtLds at_layout(int L, int A, int E, int F, int K, int part = 0, int Lr = 0, bool pre_mfma = false) {
     AtLds o;
     int p = 0;
@@ -786,6 +787,11 @@ __global__ __launch_bounds__(NT) void at_kernel(const float* pq, const float* pm
 
 // ---- host: the job structs of semitts.h as an AtArgs block, one fill per part of the step.  `who` names the entry point in the messages;
 // what depends on the launch a part rides in (residency, LDS, granule alignment) is checked by that launch.
+// workgroups per utterance the pre part runs with: a power of two from 2 to 64 as asked, anything else as 1
+inline int at_pre_parts_eff(int parts) { return (parts >= 2 && parts <= 64 && (parts & (parts - 1)) == 0) ? parts : 1; }
+// context slices of the fin part: 1, or 2 / 4 / 8 whole float4 columns each
+inline bool at_fin_parts_ok(int parts, int E) { return parts == 1 || ((parts == 2 || parts == 4 || parts == 8) && E % (4 * parts) == 0); }
+
 inline int at_ctx_dst_fill(AtArgs& a, const st_t16_view* ctx_dst, int n_ctx_dst, const char* who) {
     ST_CHECK_ARG(n_ctx_dst >= 0 && n_ctx_dst <= 3, "%s: n_ctx_dst=%d", who, n_ctx_dst);
     for (int d = 0; d < n_ctx_dst; ++d) a.ctx_dst[d] = ctx_dst[d];
@@ -813,7 +819,7 @@ inline int at_pre_fill(AtArgs& a, const st_attn_pre_job* j, int B, const char* w
     memset(&a, 0, sizeof(a));
     a.pm = j->pm; a.w_prev = j->w_prev; a.ld_wprev = j->ld_wprev; a.w_cum_prev = j->w_cum_prev;
     a.loc_conv_w = j->loc_conv_w; a.loc_lin_w = j->loc_lin_w; a.s_buf = j->s_buf; a.cf_out = j->cf_out;
-    a.pre_parts = (j->parts >= 2 && j->parts <= 64 && (j->parts & (j->parts - 1)) == 0) ? j->parts : 1;
+    a.pre_parts = at_pre_parts_eff(j->parts);
     a.B = B; a.L = j->L; a.A = j->A; a.E = 4; a.F = j->F; a.K = j->K;
     return 0;
 }
@@ -821,7 +827,7 @@ inline int at_pre_fill(AtArgs& a, const st_attn_pre_job* j, int B, const char* w
 // the fin part (at_kernel<., 2>, or the fin workgroups of the query projection's launch: pq NULL, it arrives as granules)
 inline int at_fin_fill(AtArgs& a, const float* pq, const st_attn_fin_job* j, int B, const char* who) {
     ST_CHECK_ARG(j, "%s: null job", who);
-    ST_CHECK_ARG(j->parts == 1 || ((j->parts == 2 || j->parts == 4 || j->parts == 8) && j->E % (4 * j->parts) == 0),
+    ST_CHECK_ARG(at_fin_parts_ok(j->parts, j->E),
                  "%s: parts=%d must be 1, 2, 4 or 8 with E=%d a multiple of 4*parts", who, j->parts, j->E);
     ST_CHECK_ARG(j->s_buf && j->memory && j->w_cum_prev && j->w_out && j->w_cum_out && j->v, "%s: null attention operand", who);
     ST_CHECK_ARG(((j->A % 4 != 0) || (st_aligned16(j->s_buf) && st_aligned16(j->v))) && st_aligned16(j->memory) && j->E % 4 == 0 &&
@@ -835,6 +841,75 @@ inline int at_fin_fill(AtArgs& a, const float* pq, const st_attn_fin_job* j, int
     a.B = B; a.L = j->L; a.A = j->A; a.E = j->E; a.F = j->F; a.K = j->K;
     a.status = j->status;
     return 0;
+}
+
+// ---- host: which launch a forward attention call takes, from shapes and operand alignment alone.  at_launch and st_attn_fin_split_fwd
+// (attention.hip) launch what this says; st_attn_fwd_variant exports it.  part: 0 whole step, 1 pre, 2 fin, 3 fin over position ranges.
+// `al`: ST_ATTN_AL_* bits of the operands that are 16-byte aligned (an operand a part does not take counts as aligned; the fin part
+// reads S where the whole step reads pm and has no W_l: both follow the S bit there).
+struct AtPlan {
+    int code;                 // 0, or an ST_ATTN_R_* refusal
+    bool vec, wl_vec, s_mfma, kp32, opt_in;
+    size_t lds;               // dynamic LDS bytes
+    int nwg;                  // workgroups (part 3: of the range launch; the combine launch adds B)
+    int parts, Lp;            // part 1: ranges per utterance and positions per range; 2: context slices; 3: ranges that hold positions, Lp
+};
+
+inline size_t at_plan_lds(int part, int L, int A, int E, int F, int K, int pre_parts, bool s_mfma) {
+    return (size_t)at_layout(L, A, E, F, K, part, at_pos_per(L, pre_parts), s_mfma).total * sizeof(float);
+}
+
+inline AtPlan at_plan(int part, int B, int L, int A, int E, int F, int K, int parts, unsigned al) {
+    AtPlan p;
+    memset(&p, 0, sizeof(p));
+    p.parts = 1; p.Lp = L;
+    auto ok = [&](unsigned bit) { return (al & bit) != 0; };
+    if (part == 3) {
+        if (B <= 0 || L <= 0) { p.code = ST_ATTN_R_DIMS; return p; }
+        if (!(A % 4 == 0 && A >= 4 && A <= 256 && E % 4 == 0 && E >= 4 && E / 4 <= AT_THREADS && AT_THREADS % (E / 4) == 0)) { p.code = ST_ATTN_R_RANGE_DIMS; return p; }
+        if (parts < 2 || parts > 64) { p.code = ST_ATTN_R_PARTS; return p; }
+        p.Lp = (L + parts - 1) / parts;
+        // ceil(L / parts) positions per part can leave trailing parts EMPTY (L = 9, parts = 4: 3 + 3 + 3 + 0); an empty part would
+        // prefetch row L of its utterance -- the next utterance's, or one row past the end of s_buf for the last one.  Only the parts
+        // that hold positions are launched and combined (the workspace is sized for the requested count, which is never smaller).
+        p.parts = (L + p.Lp - 1) / p.Lp;
+        if (p.Lp > 512) { p.code = ST_ATTN_R_LP; return p; }
+        if (!(ok(ST_ATTN_AL_PQ) && ok(ST_ATTN_AL_S) && ok(ST_ATTN_AL_MEM) && ok(ST_ATTN_AL_V) && ok(ST_ATTN_AL_WS))) { p.code = ST_ATTN_R_ALIGN; return p; }
+        p.vec = true;
+        p.nwg = B * p.parts;
+        return p;
+    }
+    if (part < 0 || part > 3 || B <= 0 || L <= 0 || A <= 0 || F <= 0 || K <= 0 || (part != 1 && E <= 0)) { p.code = ST_ATTN_R_DIMS; return p; }
+    if (K % 2 != 1) { p.code = ST_ATTN_R_K_EVEN; return p; }
+    if (part == 1) E = 4;       // (the pre part forms no context)
+    if (part == 2 && !at_fin_parts_ok(parts, E)) { p.code = ST_ATTN_R_PARTS; return p; }
+    if (E % 4 != 0 || E / 4 > AT_THREADS) { p.code = ST_ATTN_R_E; return p; }
+    const bool al_pm = ok(part == 2 ? ST_ATTN_AL_S : ST_ATTN_AL_PM), al_wl = ok(part == 2 ? ST_ATTN_AL_S : ST_ATTN_AL_WL);
+    const bool al_q = part == 1 || (ok(ST_ATTN_AL_PQ) && ok(ST_ATTN_AL_V));
+    if (part != 1 && !ok(ST_ATTN_AL_MEM)) { p.code = ST_ATTN_R_ALIGN; return p; }
+    if (A % 4 == 0 && !(al_pm && al_q && (part == 0 || ok(ST_ATTN_AL_S)))) { p.code = ST_ATTN_R_ALIGN; return p; }
+    p.vec = (A % 4 == 0) && (F % 4 == 0) && al_pm && al_q && al_wl;
+    p.wl_vec = part != 2 && (p.vec || (F % 4 == 0 && al_wl));
+    p.s_mfma = part == 1 && p.vec && F == 32 && A % 16 == 0;
+    p.kp32 = part != 2 && K <= 32;
+    p.parts = part == 1 ? at_pre_parts_eff(parts) : part == 2 ? parts : 1;
+    p.Lp = part == 1 ? at_pos_per(L, p.parts) : L;
+    p.lds = at_plan_lds(part, L, A, E, F, K, part == 1 ? p.parts : 1, p.s_mfma);
+    p.opt_in = p.lds > 64 * 1024;
+    p.nwg = B * p.parts;
+    if (p.lds > 160 * 1024) p.code = ST_ATTN_R_LDS;
+    return p;
+}
+
+// the last L whose LDS image stays within `limit` bytes for these dims (0: not even L = 1); the image grows with L
+inline int at_plan_last_L(int part, int A, int E, int F, int K, int pre_parts, bool s_mfma, size_t limit) {
+    if (at_plan_lds(part, 1, A, E, F, K, pre_parts, s_mfma) > limit) return 0;
+    int lo = 1, hi = 1 << 20;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (at_plan_lds(part, mid, A, E, F, K, pre_parts, s_mfma) <= limit) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 }  // namespace
