@@ -1651,6 +1651,49 @@ int st_dtw_pairs(const float* feat, long n_rows, int D, long st, const int32_t* 
  * triples than threads are strided over).  Limits (-22): NB >= 1, dmat_len >= 1. */
 int st_abx_count(const float* dmat, long dmat_len, const int64_t* blk /* (NB, 6) */, int NB, int64_t* count /* (NB, 4) */, void* stream);
 
+/* ------------------------------------------------------------------ intelligibility: STOI and ESTOI of (clean, processed) waveform pairs
+ * Not a step of the reference (it scores no waveform).  STOI: Taal, Hendriks, Heusdens, Jensen 2011; ESTOI: Jensen, Taal 2016
+ * (semi_tts_amd.metrics.stoi, main.py --stoi-wav-dir).  Both signals of a pair are at 10 kHz, time-aligned and of one length: x is a
+ * ragged batch (st_wave_batch, 0 <= B <= 64) of clean signals, y a second packed buffer with the SAME offsets and lengths that holds
+ * the processed ones.  A pair never sees a neighbour's samples of the packed buffers.
+ * Window.  w[n] = 0.5 - 0.5 cos(2 pi (n + 1) / 257), n < 256 (hanning(258) without its two zeros), computed in double, rounded once.
+ * Frames.  Frame i starts at 128 i for every i with 128 i < L - 256 (strict, as the authors' code): F = st_stoi_frames(L) of them,
+ * 0 when L <= 256.
+ * Silent frames.  energy[b, i] = ||w x_i||_2 in fp32 (rows i >= F up to F_pad written 0): the products w[j] x[j] are rounded, lane
+ * l < 64 forms ONE chain acc = fmaf(v, v, acc) over j = l, l + 64, l + 128, l + 192, the 64 partials combine by the xor butterfly
+ * (offsets 32 .. 1) and the root is one sqrtf.  Frame i is kept iff e_i + EPS > 0.01f (max_i e_i + EPS) with EPS = 2^-52: the 40 dB
+ * range below the loudest frame of 20 log10(e + EPS), without the logarithm; one fp32 product, a strict comparison.  The clean signal
+ * alone decides.  kept[b, k], k < K, are the kept frame indices in ascending order; entries k >= K up to F_pad are -1.
+ * Bands.  The kept windowed frames of each side, overlap-added at hop 128 in kept order, give (K - 1) 128 + 256 samples; that signal
+ * is framed by the same rule (M = K - 1 frames: the strict bound drops the last one), windowed again, zero-padded to 512 and
+ * transformed.  It is never written to memory: output frame m is gathered from the kept frames m - 1, m, m + 1.  Band j < 15 is
+ * sqrtf of the sum of |X[k]|^2 over the bins [lo_j, hi_j) nearest to 150 * 2^((2 j -+ 1) / 6) Hz on the grid k 10000 / 512:
+ * (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109) (109,138) (138,174) (174,219).
+ * bands[b, side, j, m] (side 0 clean, 1 processed); columns m >= M up to F_pad are written 0.
+ * Segments.  Segment s = 0 .. M - 30 holds the columns [s, s + 30) of both sides; S = M - 29 of them, 0 when M < 30.
+ * STOI.  Per segment and band, with x, y the two rows: c = ||x|| / (||y|| + EPS), y' = min(c y, (1 + 10^(15 / 20)) x) (a NaN stays a
+ * NaN); both rows minus their means, each divided by (its norm + EPS); d = the sum of the products over all bands and segments / (15 S).
+ * ESTOI.  Per segment the rows of x and of y minus their means and divided by (norm + EPS), then the columns likewise;
+ * d_e = the sum of the products / (30 S).  Both correlations are formed in float64 on the device from the fp32 bands, the segments
+ * are summed in a fixed order and each score is rounded once.
+ * Outputs.  score (B, 2) = (d, d_e); counts (B, 4) int32 = (F, K, M, S).  S = 0 (too short, or too few kept frames): both scores are
+ * the sentinel 1e-5f.  A non-finite frame norm of the clean signal: K = M = S = 0, every kept entry -1, both scores NaN.  A non-finite
+ * sample of y inside a kept frame makes both scores NaN through the arithmetic.  Digital silence on either side scores 0.
+ * energy, kept, bands: each may be NULL (the workspace holds it then).
+ * ws: st_stoi_workspace_floats(B, F_pad) floats, 8-byte aligned, no initialisation needed.
+ * Five launches (frame norms: a workgroup stages the span of 16 consecutive frames in LDS once; selection: one workgroup per pair,
+ * a block scan over chunks of 256 frames; bands: one wave per (output frame, side, pair); correlations: one wave per (pair, segment);
+ * the sum over segments: one wave per pair), three when F_pad <= 30, none when B = 0.  No atomics, no allocation, no host read: every
+ * output of a pair depends on its samples alone -- not on B, the position in the batch, F_pad or the neighbours -- and is bitwise
+ * repeatable.  The first call on a device uploads the twiddle and window tables and may not be inside a stream capture.
+ * Limits (-22 past them, before any device call): 0 <= B <= 64, 1 <= len <= 2^22 = 4194304, F_pad >= max(1, the largest F).
+ * st_stoi_frames: F of a signal of len samples (-1 outside the limits). */
+int st_stoi_frames(int len);
+size_t st_stoi_workspace_floats(int B, int F_pad);
+int st_stoi_batch(const st_wave_batch* x, const float* y, float* score /* (B, 2) */, int32_t* counts /* (B, 4) */, int F_pad,
+                  float* energy /* (B, F_pad) or NULL */, int32_t* kept /* (B, F_pad) or NULL */,
+                  float* bands /* (B, 2, 15, F_pad) or NULL */, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,10 @@ confusions.csv, phones.csv, with `--score-ali` <key>.ops per file and with `--sc
 the codebook posteriors -- by the ABX phone-discrimination error of ZeroSpeech / Libri-light: the phone tokens the .ali files of
 `--align-wav-dir` delimit are compared within speaker and context by path-normalised DTW, one wave per pair on the GPU (solver.AbxScorer,
 semi_tts_amd.metrics.abx, st_dtw_pairs + st_abx_count): abx.csv with the error of every ordered phone pair, abx_phones.csv with the tokens used.
+`--stoi-wav-dir SYN --stoi-ref-dir REF` (not a mode of the reference) scores processed .wav files -- what `--vocode-dir`, `--gen-specgram --gen-wav`,
+`--resample-wav-dir` or `--loudness-out` write -- against the time-aligned recordings they were made from by short-time objective
+intelligibility on the GPU (solver.StoiScorer, semi_tts_amd.metrics.stoi, st_stoi_batch): stoi.csv with STOI and ESTOI of every pair.  The
+measure needs the two signals sample-aligned; it is not for `--synth-phn-dir`, whose timing is the model's own (`--mcd-wav-dir` warps time).
 """
 import argparse
 import os
@@ -256,6 +260,13 @@ parser.add_argument('--abx-max-items', default=None, type=int, help='--abx-ali-d
                     'subsample (--seed) is scored (default 50)')
 parser.add_argument('--abx-min-frames', default=None, type=int, help='--abx-ali-dir: tokens of fewer feature rows are dropped (default 1; tokens '
                     'of more than 64 rows always are)')
+parser.add_argument('--stoi-wav-dir', default=None, type=str, help='score the processed .wav files of this directory (sorted by name, batched by '
+                    '--batch-size; 16-bit mono PCM of any rate the resampler takes) against their time-aligned recordings in --stoi-ref-dir by STOI and '
+                    'ESTOI on the GPU: <logdir>/<name>/stoi.csv (file,samples,frames,kept,segments,stoi,estoi); no config, no checkpoint, no model')
+parser.add_argument('--stoi-ref-dir', default=None, type=str, help='--stoi-wav-dir: the directory of the recordings, <key>.wav for every processed '
+                    'file (key: its name up to the first ".", without one trailing "-pred"), at the rate of its processed file')
+parser.add_argument('--stoi-max-len-diff', default=None, type=float, help='--stoi-wav-dir: the most seconds the two files of a pair may differ in '
+                    'length; the longer one is cut at its end (default 0.05: three decoder frames and a vocoder\'s partial hop)')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -410,6 +421,25 @@ def parse_args(argv=None):
         paras.end_patience = 3
     if paras.end_max_jump is None:
         paras.end_max_jump = 4
+    if paras.stoi_wav_dir is not None:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir', 'loudness_wav_dir', 'score_phn_dir',
+                     'abx_ali_dir', 'corpus'):
+            if getattr(paras, flag):
+                parser.error('--stoi-wav-dir does not combine with --%s' % flag.replace('_', '-'))
+        for flag in ('trim_silence', 'normalize_loudness'):
+            if getattr(paras, flag):
+                parser.error('--stoi-wav-dir does not combine with --%s: changing the two sides separately destroys the alignment the measure needs'
+                             % flag.replace('_', '-'))
+        if paras.dev_batches != 0:
+            parser.error('--stoi-wav-dir does not combine with --dev-batches')
+        if paras.stoi_ref_dir is None:
+            parser.error('--stoi-wav-dir needs --stoi-ref-dir DIR (the recordings)')
+        paras.stoi_max_len_diff = 0.05 if paras.stoi_max_len_diff is None else paras.stoi_max_len_diff
+        if not 0.0 <= paras.stoi_max_len_diff < float('inf'):
+            parser.error('--stoi-max-len-diff must be finite and at least 0 seconds')
+    elif paras.stoi_ref_dir is not None or paras.stoi_max_len_diff is not None:
+        parser.error('--stoi-ref-dir and --stoi-max-len-diff belong to --stoi-wav-dir; they need that flag')
     if paras.trim_wav_dir is not None:
         for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
                      'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_silence'):
@@ -569,6 +599,9 @@ def main(argv=None):
     elif paras.score_phn_dir is not None:                                # (transcripts against transcripts: no config is read)
         config = None
         paras.batch_size = paras.batch_size or 64
+    elif paras.stoi_wav_dir is not None:                                 # (waveforms against waveforms at their own rates: no config is read)
+        config = None
+        paras.batch_size = paras.batch_size or 32
     else:
         config = yaml.load(open(paras.config, 'r'), Loader=yaml.FullLoader)
     if paras.batch_size is None:
@@ -600,6 +633,9 @@ def main(argv=None):
         mode = 'test'
     elif paras.mcd_wav_dir is not None:
         from semi_tts_amd.solver import McdScorer as Solver
+        mode = 'test'
+    elif paras.stoi_wav_dir is not None:
+        from semi_tts_amd.solver import StoiScorer as Solver
         mode = 'test'
     elif paras.abx_ali_dir is not None:
         from semi_tts_amd.solver import AbxScorer as Solver

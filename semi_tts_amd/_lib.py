@@ -440,6 +440,9 @@ SIGNATURES = {
     'st_wave_gain': [C.POINTER(StWaveBatch), P, P, P, P],
     'st_dtw_pairs': [P, C.c_long, I, C.c_long, P, P, I, P, P, I, I, I, P, P, P, P],
     'st_abx_count': [P, C.c_long, P, I, P, P],
+    'st_stoi_frames': [I],
+    'st_stoi_workspace_floats': [I, I],
+    'st_stoi_batch': [C.POINTER(StWaveBatch), P, P, P, I, P, P, P, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,
@@ -447,7 +450,8 @@ _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t,
              'st_bn_bank_workspace_floats': C.c_size_t, 'st_istft_workspace_floats': C.c_size_t,
              'st_gl_batch_workspace_floats': C.c_size_t,
              'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t,
-             'st_dtw_workspace_bytes': C.c_size_t, 'st_edit_align_workspace_bytes': C.c_size_t}
+             'st_dtw_workspace_bytes': C.c_size_t, 'st_edit_align_workspace_bytes': C.c_size_t,
+             'st_stoi_workspace_floats': C.c_size_t}
 
 _lib = None
 

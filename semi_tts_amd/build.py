@@ -19,6 +19,8 @@ SCORE_SOURCES = ['edit_align.hip']
 LOUDNESS_SOURCES = ['loudness.hip']
 # the ABX kernels (st_dtw_pairs, st_abx_count), listed apart for the same reason
 ABX_SOURCES = ['abx.hip']
+# the intelligibility kernels (st_stoi_batch), listed apart for the same reason
+STOI_SOURCES = ['stoi.hip']
 
 
 def _hipcc():
@@ -43,7 +45,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES + ABX_SOURCES:
+    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES + ABX_SOURCES + STOI_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

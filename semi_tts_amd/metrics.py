@@ -26,6 +26,13 @@ semi_tts_amd/csrc/f0.hip).
 
     from semi_tts_amd.metrics import f0_scores
     s = f0_scores(conv.extract_f0_batch(syn), conv.extract_f0_batch(ref), path, path_len)     # s['f0_rmse_cents'][b], s['vuv_error'][b]
+
+Intelligibility of a waveform against the time-aligned recording it was made from (a vocoder's output, a resampled or gain-changed
+file): `stoi`, STOI and ESTOI from short-time third-octave envelopes (st_stoi_batch, semi_tts_amd/csrc/stoi.hip).  Not for
+free-running synthesis, whose timing is the model's own: `mcd` along the warp is the measure there.
+
+    from semi_tts_amd.metrics import stoi
+    r = stoi(recordings, vocoded, 22050)            # r.score[b] = (STOI, ESTOI), r.counts[b] = (frames, kept, band frames, segments)
 """
 import collections
 import math
@@ -296,3 +303,71 @@ def abx(feat, item_start, item_len, label, cell, metric='angular', max_items=50,
     counts = ops.abx_count(dmat, torch.from_numpy(pl.blocks).to(dev)).cpu().numpy()                          # (the one host read)
     agg = A.aggregate(pl.block_a, pl.block_b, counts)
     return AbxResult(pl.blocks, pl.block_cell, pl.block_a, pl.block_b, counts, agg.table, agg.score, P, pl.keep)
+
+
+StoiResult = collections.namedtuple('StoiResult', 'score counts energy kept bands')
+
+
+def _stoi_side(what, wavs):
+    """one side of metrics.stoi as a WaveBatch (nothing is uploaded here)"""
+    from .audio import WaveBatch
+    if isinstance(wavs, WaveBatch):
+        return wavs
+    if torch.is_tensor(wavs) and wavs.dim() == 1:
+        wavs = [wavs]
+    try:
+        n = len(wavs)
+    except TypeError:
+        raise ValueError('stoi: %s must be a list of 1-D waveforms or a WaveBatch (got %s)' % (what, type(wavs).__name__))
+    if n == 0:
+        raise ValueError('stoi: %s is an empty batch' % what)
+    wavs = [torch.as_tensor(w) for w in wavs]
+    for i, w in enumerate(wavs):
+        if w.dim() != 1 or w.numel() < 1 or not (w.dtype.is_floating_point or w.dtype == torch.int16):
+            raise ValueError('stoi: %s[%d] must be a non-empty 1-D floating point or int16 waveform (got %s %s)' % (what, i, tuple(w.shape), w.dtype))
+    return WaveBatch([w.to(torch.float32) / 32768.0 if w.dtype == torch.int16 else w for w in wavs])
+
+
+def stoi(clean, degraded, sample_rate, want_parts=False):
+    """Short-time objective intelligibility of B (clean, processed) waveform pairs on one GPU: STOI (Taal, Hendriks, Heusdens, Jensen
+    2011) and ESTOI (Jensen, Taal 2016); the definition is in include/semitts.h (st_stoi_batch, semi_tts_amd/csrc/stoi.hip).  clean,
+    degraded: lists of 1-D waveforms (tensors or arrays; int16 PCM counts as x / 32768) or WaveBatches, pairwise of EQUAL length and
+    time-aligned -- the measure correlates short-time envelopes frame by frame, it does not search for a delay.  sample_rate: the rate
+    of both sides; anything but 10000 Hz goes through audio.resample first (the project's Hann-windowed sinc, so the values differ
+    slightly from pystoi's, which emulates Octave's resample).  More than ops.STOI_MAX_BATCH pairs are issued in chunks of it.
+    -> StoiResult of device tensors in the caller's order: score (B, 2) float32 = (STOI, ESTOI); counts (B, 4) int32 = (frames, kept
+    frames, band frames M, segments S); with want_parts energy (B, F_pad), kept (B, F_pad) int32 (-1 past the kept ones) and bands
+    (B, 2, 15, F_pad) (0 past M), else None.  A pair with S = 0 (shorter than 30 band frames) scores ops.STOI_SENTINEL twice; a
+    non-finite clean signal scores NaN.  A pair's figures depend on that pair alone and are bitwise repeatable.  No host read.
+    Unequal lengths, an empty input, a rate the resampler refuses or a signal past ops.STOI_MAX_LEN samples at 10 kHz raise ValueError
+    before the device is touched."""
+    import numpy as np
+    from . import audio
+    xb, yb = _stoi_side('clean', clean), _stoi_side('degraded', degraded)
+    if len(xb.lens) != len(yb.lens):
+        raise ValueError('stoi: %d clean and %d processed signals: one of each per pair' % (len(xb.lens), len(yb.lens)))
+    ox, oy = np.asarray(xb.order), np.asarray(yb.order)
+    lx, ly = np.empty_like(xb.lens), np.empty_like(yb.lens)
+    lx[ox], ly[oy] = xb.lens, yb.lens                                   # (lengths in the caller's order)
+    if (lx != ly).any():
+        i = int(np.nonzero(lx != ly)[0][0])
+        raise ValueError('stoi: pair %d has %d clean and %d processed samples: the two sides must be equally long' % (i, lx[i], ly[i]))
+    if not np.array_equal(ox, oy):
+        raise ValueError('stoi: the two WaveBatches are ordered differently')
+    audio.resample_table(sample_rate, ops.STOI_FS)                       # (the resampler's refusals, raised here)
+    longest = audio.resampled_len(int(lx.max()), sample_rate, ops.STOI_FS)
+    if longest > ops.STOI_MAX_LEN:
+        raise ValueError('stoi: the longest signal has %d samples at %d Hz, above the limit of %d' % (longest, ops.STOI_FS, ops.STOI_MAX_LEN))
+    if int(sample_rate) != ops.STOI_FS:
+        xb, yb = audio.resample(xb, int(sample_rate), ops.STOI_FS), audio.resample(yb, int(sample_rate), ops.STOI_FS)
+    order, lens, off = np.asarray(xb.order), xb.lens, xb.offsets         # (equal lengths sort alike: yb's are the same)
+    dev = xb.device or yb.device or audio._device()
+    x, y = xb.packed(dev), yb.packed(dev)
+    if not np.array_equal(off, yb.offsets) or x.numel() != y.numel():    # (two windows of differently laid out buffers)
+        raise ValueError('stoi: the two WaveBatches are laid out differently')
+    B = len(lens)
+    F_pad = max(1, max(ops.stoi_frames(v) for v in lens))             # one width for every chunk: the parts concatenate
+    outs = [ops.stoi_batch(x, y, off[b0:b0 + ops.STOI_MAX_BATCH], lens[b0:b0 + ops.STOI_MAX_BATCH], F_pad, want_parts)
+            for b0 in range(0, B, ops.STOI_MAX_BATCH)]
+    inv = torch.from_numpy(np.argsort(order, kind='stable')).to(dev)     # row i of the result is the caller's pair i
+    return StoiResult(*[torch.cat(parts).index_select(0, inv) if parts[0] is not None else None for parts in zip(*outs)])

@@ -2637,3 +2637,65 @@ def wave_gain(x, off, lens, stats, out=None, pcm16=False):
     check(lib.st_wave_gain(_wave_chunk(w, off, lens, 0, B), _p(stats), None if pcm16 else _p(out), _p(out, torch.int16) if pcm16 else None,
                            stream_handle()), 'st_wave_gain')
     return out
+
+
+# --------------------------------------------------------------------------------------------- intelligibility (st_stoi_batch)
+STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT = 10000, 256, 128, 512
+STOI_BANDS, STOI_SEG = 15, 30
+STOI_MAX_BATCH = 64                  # st_stoi_batch's limits: pairs a call ...
+STOI_MAX_LEN = 1 << 22               # ... and samples of the longest signal (7 minutes at 10 kHz)
+STOI_CHUNK = 256                     # frames per step of the selection launch's scan: the tests straddle it
+STOI_SENTINEL = 1e-5                 # both scores of a pair with fewer than 30 band frames (pystoi's convention)
+STOI_BAND_EDGES = ((7, 9), (9, 11), (11, 14), (14, 17), (17, 22), (22, 27), (27, 34), (34, 43), (43, 55), (55, 69), (69, 87), (87, 109),
+                   (109, 138), (138, 174), (174, 219))
+
+
+def stoi_frames(L):
+    """F of an L-sample signal at 10 kHz: the frames i with 128 i < L - 256 (strict, as the authors' code); 0 when L <= 256"""
+    L = int(L)
+    return (L - STOI_FRAME + STOI_HOP - 1) // STOI_HOP if L > STOI_FRAME else 0
+
+
+def _stoi_check(lens, F_pad=None):
+    """every refusal of st_stoi_batch that does not need the buffers, raised before any device is touched -> F_pad"""
+    lens = np.asarray(lens)
+    if lens.ndim != 1 or not 0 <= lens.shape[0] <= STOI_MAX_BATCH or (lens.shape[0] and lens.dtype.kind not in 'iu'):
+        raise ValueError('stoi_batch: lens must be 0 .. %d integers, one call takes no more pairs (got %s)'
+                         % (STOI_MAX_BATCH, 'shape %s, %s' % (lens.shape, lens.dtype)))
+    if lens.shape[0] and ((lens < 1).any() or (lens > STOI_MAX_LEN).any()):
+        raise ValueError('stoi_batch: every length must lie in [1, %d] (got %s)' % (STOI_MAX_LEN, lens.tolist()))
+    frames = max([1] + [stoi_frames(v) for v in lens])
+    if F_pad is None:
+        F_pad = frames
+    if isinstance(F_pad, bool) or not isinstance(F_pad, (int, np.integer)) or F_pad < frames or F_pad >= 2 ** 24:
+        raise ValueError('stoi_batch: F_pad %r below the %d frames of the longest signal (at least 1)' % (F_pad, frames))
+    return int(F_pad)
+
+
+def stoi_batch(x, y, off, lens, F_pad=None, want_parts=False):
+    """st_stoi_batch (STOI and ESTOI; the definition is in include/semitts.h) on a ragged batch of pairs at 10 kHz: x the packed float32
+    clean signals on the device, y the processed ones packed the same way (x's size), pair b = x / y[off[b]:off[b] + lens[b]], at most
+    STOI_MAX_BATCH of them (metrics.stoi splits).  -> device tensors (score (B, 2) float32 = (STOI, ESTOI), counts (B, 4) int32 =
+    (frames F, kept K, band frames M, segments S), and with want_parts energy (B, F_pad) float32, kept (B, F_pad) int32 with -1 past K,
+    bands (B, 2, 15, F_pad) float32 with 0 past M; None, None, None without).  F_pad None: the longest signal's frames (at least 1).
+    B = 0 launches nothing.  No host read.  Anything the kernel would refuse raises ValueError before the device is touched."""
+    F_pad = _stoi_check(lens, F_pad)
+    if not torch.is_tensor(y) or not torch.is_tensor(x) or y.shape != x.shape or y.device != x.device or y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError('stoi_batch: y must be a packed 1-D contiguous float32 tensor of x\'s size on x\'s device (got %s)'
+                         % ('%s %s on %s' % (tuple(y.shape), y.dtype, y.device) if torch.is_tensor(y) else type(y).__name__))
+    off, lens = _wave_args('stoi_batch', x, off, lens)
+    lib = _lib.load()
+    dev = x.device
+    B = len(lens)
+    score = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    counts = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    energy = torch.empty(B, F_pad, device=dev, dtype=torch.float32) if want_parts else None
+    kept = torch.empty(B, F_pad, device=dev, dtype=torch.int32) if want_parts else None
+    bands = torch.empty(B, 2, STOI_BANDS, F_pad, device=dev, dtype=torch.float32) if want_parts else None
+    if B == 0:
+        return score, counts, energy, kept, bands
+    ws = torch.empty(int(lib.st_stoi_workspace_floats(B, F_pad)), device=dev, dtype=torch.float32)
+    w = _lib.StWaveBatch(x=_p(x), n_samples=x.numel())
+    check(lib.st_stoi_batch(_wave_chunk(w, off, lens, 0, B), _p(y), _p(score), _p(counts, torch.int32), F_pad, _p(energy), _p(kept, torch.int32),
+                            _p(bands), _p(ws), stream_handle()), 'st_stoi_batch')
+    return score, counts, energy, kept, bands

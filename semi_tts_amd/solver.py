@@ -593,20 +593,21 @@ def mcd_key(filename):
     return key[:-len(MCD_PRED_SUFFIX)] if key.endswith(MCD_PRED_SUFFIX) else key
 
 
-def mcd_pairs(syn_dir, ref_dir):
+def mcd_pairs(syn_dir, ref_dir, flag='--mcd-wav-dir'):
     """the .wav files of syn_dir sorted by name, each with its recording <key>.wav of ref_dir -> [(file, key, recording)] (names, not
-    paths).  ValueError naming the file when syn_dir holds none, a recording is missing or two files share one."""
+    paths).  ValueError naming the file when syn_dir holds none, a recording is missing or two files share one.  flag: the command-line
+    flag the messages name (--stoi-wav-dir pairs by the same rule)."""
     files = sorted(f for f in os.listdir(syn_dir) if f.lower().endswith('.wav'))
     if not files:
-        raise ValueError('--mcd-wav-dir %s: no .wav files' % syn_dir)
+        raise ValueError('%s %s: no .wav files' % (flag, syn_dir))
     pairs = []
     for f in files:
         key = mcd_key(f)
         ref = key + '.wav'
         if not key or not os.path.isfile(os.path.join(ref_dir, ref)):
-            raise ValueError('--mcd-wav-dir: %s has no recording %s' % (f, os.path.join(ref_dir, ref)))
+            raise ValueError('%s: %s has no recording %s' % (flag, f, os.path.join(ref_dir, ref)))
         if any(key == k for _, k, _ in pairs):
-            raise ValueError('--mcd-wav-dir: %s and %s share the recording %s' % ([g for g, k, _ in pairs if k == key][0], f, ref))
+            raise ValueError('%s: %s and %s share the recording %s' % (flag, [g for g, k, _ in pairs if k == key][0], f, ref))
         pairs.append((f, key, ref))
     return pairs
 
@@ -725,6 +726,121 @@ class McdScorer:
             print('[INFO]', 'F0 along the warp: mean RMSE %.2f cents, V/UV error %.4f, gross error %.4f, mean deviation %.2f cents; %s'
                   % (tuple(self.mean_f0[k] for k in F0_FIGURES) + (os.path.join(self.logdir, 'f0.csv'),)))
         return len(vals)
+
+
+STOI_HEADER = 'file,samples,frames,kept,segments,stoi,estoi'
+STOI_MAX_LEN_DIFF = 0.05            # seconds: r = 3 decoder frames of 12.5 ms plus the vocoder's lost partial hop
+
+
+def stoi_row(file, samples, counts, score):
+    """one line of stoi.csv: counts = (frames, kept, band frames, segments), score = (stoi, estoi)"""
+    return '%s,%d,%d,%d,%d,%.6f,%.6f' % (file, samples, counts[0], counts[1], counts[3], score[0], score[1])
+
+
+class StoiScorer:
+    """main.py --stoi-wav-dir SYN --stoi-ref-dir REF [--stoi-max-len-diff 0.05]: every .wav of SYN (sorted by name) against REF/<key>.wav
+    (mcd_key, the pairing of --mcd-wav-dir), in batches of --batch-size (at most 64 pairs a call) -> metrics.stoi (both sides resampled
+    to 10 kHz on the device when the files are at another rate, then st_stoi_batch) -> one host read per batch -> <logdir>/stoi.csv
+    (STOI_HEADER, one row per pair: the samples scored at the files' rate, the frames at 10 kHz, the frames kept, the segments, STOI,
+    ESTOI).  The two files of a pair must be time-aligned: a vocoded spectrogram against its recording, not free-running synthesis.
+    A pair whose lengths differ by at most --stoi-max-len-diff seconds is cut to the shorter side at its end.  A pair too short for one
+    segment (under 30 band frames) gets the sentinel row (segments 0, both scores 1e-5), a warning naming it, and no part in the means.
+    No config, no checkpoint, no model.  Every pair is looked up and every header read in load_data: a missing or shared recording, an
+    unreadable, multichannel or non-16-bit file, two rates within a pair, a rate the resampler refuses, a larger length difference or a
+    signal past the kernel's limit stops the run, naming the file, before any device work."""
+
+    def __init__(self, config, paras, mode):
+        self.config, self.paras, self.mode = config, paras, mode
+        self.exp_name = getattr(paras, 'name', None) or 'synthetic'
+        self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
+        d = getattr(paras, 'stoi_max_len_diff', None)
+        self.max_len_diff = STOI_MAX_LEN_DIFF if d is None else float(d)
+
+    @staticmethod
+    def _header(path):
+        import wave
+        try:
+            with wave.open(path, 'rb') as w:
+                sr, ch, width, L = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
+        except (OSError, EOFError, wave.Error) as e:
+            raise ValueError('--stoi-wav-dir: %s is not a readable .wav file (%s)' % (path, e))
+        if width != 2 or ch != 1:
+            raise ValueError('--stoi-wav-dir: %s is %d-bit with %d channels; only 16-bit mono PCM is read' % (path, 8 * width, ch))
+        if L < 1:
+            raise ValueError('--stoi-wav-dir: %s holds no samples' % path)
+        return sr, L
+
+    def load_data(self):
+        from . import audio
+        self.syn_dir, self.ref_dir = self.paras.stoi_wav_dir, self.paras.stoi_ref_dir
+        self.pairs = mcd_pairs(self.syn_dir, self.ref_dir, '--stoi-wav-dir')
+        self.rates, self.samples = [], []
+        for f, _, ref in self.pairs:
+            ps, pr = os.path.join(self.syn_dir, f), os.path.join(self.ref_dir, ref)
+            (sr, L), (sr_ref, L_ref) = self._header(ps), self._header(pr)
+            if sr != sr_ref:
+                raise ValueError('--stoi-wav-dir: %s is at %d Hz and its recording %s at %d Hz; the two files of a pair share one rate' % (ps, sr, pr, sr_ref))
+            try:
+                audio.resample_table(sr, ops.STOI_FS)
+            except ValueError as e:
+                raise ValueError('--stoi-wav-dir: %s: %s' % (ps, e))
+            if abs(L - L_ref) > self.max_len_diff * sr:
+                raise ValueError('--stoi-wav-dir: %s has %d samples and its recording %s %d: they differ by %.4f s, above --stoi-max-len-diff %g; '
+                                 'the measure needs time-aligned signals' % (ps, L, pr, L_ref, abs(L - L_ref) / float(sr), self.max_len_diff))
+            n = min(L, L_ref)
+            if audio.resampled_len(n, sr, ops.STOI_FS) > ops.STOI_MAX_LEN:
+                raise ValueError('--stoi-wav-dir: %s has %d samples at %d Hz; the measure takes at most %d' % (ps, audio.resampled_len(n, sr, ops.STOI_FS),
+                                                                                                        ops.STOI_FS, ops.STOI_MAX_LEN))
+            self.rates.append(sr)
+            self.samples.append(n)
+        return self
+
+    def set_model(self):
+        return self
+
+    def score(self, lo, hi):
+        """pairs [lo, hi) -> per pair (counts (4,) int32, score (2,) float32), one metrics.stoi call per sample rate among them and one
+        host read"""
+        from . import audio
+        from .metrics import stoi
+        idx, cols = [], []
+        for sr in sorted(set(self.rates[lo:hi])):
+            sel = [i for i in range(lo, hi) if self.rates[i] == sr]
+            syn, rec = [], []
+            for i in sel:
+                f, _, ref = self.pairs[i]
+                n = self.samples[i]
+                syn.append(audio.read_wav(os.path.join(self.syn_dir, f))[0][0, :n])
+                rec.append(audio.read_wav(os.path.join(self.ref_dir, ref))[0][0, :n])
+            res = stoi(rec, syn, sr)
+            cols.append(torch.cat([res.counts, res.score.view(torch.int32)], dim=1))
+            idx += sel
+        host = torch.cat(cols, dim=0).cpu().numpy()                 # (the one host read)
+        out = [None] * (hi - lo)
+        for row, i in enumerate(idx):
+            out[i - lo] = (host[row, :4].copy(), host[row, 4:6].copy().view(np.float32))
+        return out
+
+    def exec(self):
+        os.makedirs(self.logdir, exist_ok=True)
+        B = max(1, min(int(self.paras.batch_size), ops.STOI_MAX_BATCH))
+        t0, rows, vals = time.perf_counter(), [STOI_HEADER], []
+        for lo in range(0, len(self.pairs), B):
+            hi = min(lo + B, len(self.pairs))
+            for i, (counts, score) in zip(range(lo, hi), self.score(lo, hi)):
+                f = self.pairs[i][0]
+                rows.append(stoi_row(f, self.samples[i], counts, score))
+                if counts[3] == 0 and not np.isnan(score[0]):
+                    print('[WARNING]', '--stoi-wav-dir: %s has %d band frames, fewer than the %d of one segment: the sentinel %g is written and '
+                          'the file is left out of the means' % (f, counts[2], ops.STOI_SEG, ops.STOI_SENTINEL))
+                else:
+                    vals.append(score)
+        with open(os.path.join(self.logdir, 'stoi.csv'), 'w') as fh:
+            fh.write('\n'.join(rows) + '\n')
+        self.mean_stoi, self.mean_estoi = (float(v) for v in np.mean(np.asarray(vals, np.float64), axis=0)) if vals else (math.nan, math.nan)
+        print('[INFO]', 'STOI of %d pairs (%d scored): mean STOI %.4f, mean ESTOI %.4f; %s, %.2f s'
+              % (len(self.pairs), len(vals), self.mean_stoi, self.mean_estoi, os.path.join(self.logdir, 'stoi.csv'), time.perf_counter() - t0))
+        return len(self.pairs)
 
 
 ABX_FEATS = ('mfcc', 'mel', 'latent', 'code')
