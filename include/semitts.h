@@ -1694,6 +1694,56 @@ int st_stoi_batch(const st_wave_batch* x, const float* y, float* score /* (B, 2)
                   float* energy /* (B, F_pad) or NULL */, int32_t* kept /* (B, F_pad) or NULL */,
                   float* bands /* (B, 2, 15, F_pad) or NULL */, float* ws, void* stream);
 
+/* ------------------------------------------------------------------ waveform alignment: integer-delay search, SI-SDR / SNR, span copy
+ * Not a step of the reference.  What lets st_stoi_batch score pairs that are shifted against each other (semi_tts_amd.metrics.delay,
+ * si_sdr, align_pairs; main.py --stoi-align, --stoi-sdr).  x is a ragged batch of references, y a SECOND st_wave_batch of processed
+ * signals with its own buffer, offsets and lengths; B is the same on both sides, Lx = x->len[b] and Ly = y->len[b] may differ.  A pair
+ * never sees a neighbour's samples of the packed buffers.
+ * st_xcorr_delay.  For pair b and every lag d in [-D, D], D = max_lag:
+ *   r[b, d] = sum over n of x[n] y[n + d],  max(0, -d) <= n < min(Lx, Ly - d)   (0 for an empty range)
+ * the plain cross-correlation in its direct form: not normalised per lag, not GCC-PHAT, no FFT.  A positive d: y is late by d samples.
+ * Each product is (double)x * (double)y, which is exact (24 + 24 bits), and the products are accumulated in float64.  The samples of x
+ * are cut into chunks of 1024 m samples, m = ceil(Lx / 32768) (at most 32 chunks); a lag's chunk sum is ONE chain of fma over ascending
+ * n, and the chunk sums are added in ascending order.  The cut depends on the pair's own Lx alone.  On input that is a multiple of 2^-15
+ * with magnitude at most 1 (16-bit PCM / 32768) every product is a multiple of 2^-30 and a sum of 2^22 of them stays below 2^53 units:
+ * r is then EXACT, whatever the order.
+ * Outputs.  delay (B) int32: the lag of the largest r; ties go to the smallest |d|, then to the non-negative one (the order 0, +1, -1,
+ * +2, -2, ...); the argmax by that rule also when every r is 0 or negative.  coef (B) float32 = r[d*] / sqrt(sum x^2 * sum y^2), the
+ * sums over the whole signals in float64 (fma chains, a fixed order; exact on PCM input), the quotient rounded once; 0 / 0 is NaN.
+ * corr (B, 2 D + 1) float64 or NULL: the whole r, column d + D.  If any r[b, d] is NaN, delay[b] = 0 and coef[b] = NaN.
+ * ws: st_xcorr_workspace_bytes(B, max_len, D) bytes (max_len: the longest signal of either side), 8-byte aligned, no initialisation
+ * needed: B * min(32, ceil(max_len / 1024)) * (2 D + 1) float64.
+ * Two launches (partials: grid (tiles of 2048 lags, chunks, pairs), a piece of 1024 samples of x and the span of y it meets staged
+ * in LDS as float64, a register tile of 8 lags x 8 samples a thread; finish: one workgroup per pair), none when B = 0.
+ * st_sisdr_batch.  delay: a DEVICE int32 (B) or NULL for 0 (it is not read on the host: any value is taken).  The scored span of pair
+ * b is the overlap the delay d leaves: d >= 0: x from 0, y from d; d < 0: x from -d, y from 0; n = min(Lx - x0, Ly - y0) samples.
+ * sums (B, 6) float64 = (n, sum x, sum y, sum x^2, sum y^2, sum x y) over the span, float64 sums of exact terms in a fixed order
+ * (chunks of 8192 samples, then the chunks): exact on PCM input.  score (B, 3) float32 = (SI-SDR dB, SNR dB, gain dB), evaluated on the
+ * device in float64 from the sums, every operation rounded on its own (no contraction), each figure rounded once:
+ *   zero_mean != 0: Cxx = Sxx - (Sx Sx) / n, Cyy = Syy - (Sy Sy) / n, Cxy = Sxy - (Sx Sy) / n;  zero_mean == 0: C = S
+ *   si_sdr = 10 log10((Cxy Cxy) / (Cxx Cyy - Cxy Cxy))            (Le Roux, Wisdom, Erdogan, Hershey 2019)
+ *   snr    = 10 log10(Cxx / ((Cxx - 2 Cxy) + Cyy))
+ *   gain   = 20 log10 |Cxy / Cxx|
+ * IEEE semantics are kept: y = a x with zero_mean = 0 gives +inf; a silent reference gives NaN (0 / 0) in SI-SDR and gain and -inf
+ * (log10 0) in SNR.  n <= 0 (the delay is longer than a side):
+ * the three scores are NaN and the six sums 0.
+ * ws: st_sisdr_workspace_bytes(B, max_len) bytes, 8-byte aligned.  Two launches (chunk partials; one wave per pair), none when B = 0.
+ * st_wave_gather.  dst[dst_off[b] + i] = src[src_off[b] + i], i < len[b], for B spans in ONE launch (src_off, dst_off, len: host
+ * arrays, as st_wave_batch's); nothing else of dst is written.  src and dst are different buffers.  It gives the two overlaps an
+ * alignment leaves, which start at different places of their buffers, the one common layout st_stoi_batch requires.
+ * No atomics, no allocation, no host read anywhere: every output of a pair depends on its own samples, lengths and D alone -- not on
+ * B, the position in the batch or the neighbours -- and is bitwise repeatable.
+ * Limits (-22 past them, before any device call): 0 <= B <= 64, 1 <= len <= 2^22 = 4194304 on both sides, 0 <= max_lag <= 16384
+ * (+-0.34 s at 48 kHz), every span inside its buffer.  The workspace functions return 0 outside the limits. */
+size_t st_xcorr_workspace_bytes(int B, int max_len, int max_lag);
+int st_xcorr_delay(const st_wave_batch* x, const st_wave_batch* y, int max_lag, int32_t* delay /* (B) */, float* coef /* (B) */,
+                   double* corr /* (B, 2 max_lag + 1) or NULL */, void* ws, void* stream);
+size_t st_sisdr_workspace_bytes(int B, int max_len);
+int st_sisdr_batch(const st_wave_batch* x, const st_wave_batch* y, const int32_t* delay /* device (B) or NULL */, int zero_mean,
+                   double* sums /* (B, 6) */, float* score /* (B, 3) */, void* ws, void* stream);
+int st_wave_gather(const float* src, long src_n, const long* src_off, float* dst, long dst_n, const long* dst_off, const int* len, int B,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

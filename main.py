@@ -86,6 +86,9 @@ semi_tts_amd.metrics.abx, st_dtw_pairs + st_abx_count): abx.csv with the error o
 `--resample-wav-dir` or `--loudness-out` write -- against the time-aligned recordings they were made from by short-time objective
 intelligibility on the GPU (solver.StoiScorer, semi_tts_amd.metrics.stoi, st_stoi_batch): stoi.csv with STOI and ESTOI of every pair.  The
 measure needs the two signals sample-aligned; it is not for `--synth-phn-dir`, whose timing is the model's own (`--mcd-wav-dir` warps time).
+With `--stoi-align` a constant shift between the two files of a pair -- a codec's, another vocoder's, a foreign cutter's -- is searched first, to
+the sample, within +-`--stoi-max-delay` seconds by an exact float64 cross-correlation on the GPU (semi_tts_amd.metrics.align_pairs,
+st_xcorr_delay), the overlap is scored and delay.csv written; `--stoi-sdr` adds sdr.csv with SI-SDR, SNR and gain (st_sisdr_batch).
 """
 import argparse
 import os
@@ -267,6 +270,13 @@ parser.add_argument('--stoi-ref-dir', default=None, type=str, help='--stoi-wav-d
                     'file (key: its name up to the first ".", without one trailing "-pred"), at the rate of its processed file')
 parser.add_argument('--stoi-max-len-diff', default=None, type=float, help='--stoi-wav-dir: the most seconds the two files of a pair may differ in '
                     'length; the longer one is cut at its end (default 0.05: three decoder frames and a vocoder\'s partial hop)')
+parser.add_argument('--stoi-align', action='store_true', help='--stoi-wav-dir: search each pair\'s integer delay at the files\' own rate within '
+                    '+-(--stoi-max-delay) seconds on the GPU and score the overlap it leaves; <logdir>/<name>/delay.csv '
+                    '(file,delay_samples,delay_s,coef), positive: the processed file is late')
+parser.add_argument('--stoi-max-delay', default=None, type=float, help='--stoi-align: the search bound in seconds (default 0.05; at most 16384 '
+                    'samples at the files\' rate); the two lengths of a pair may then differ by --stoi-max-len-diff plus this')
+parser.add_argument('--stoi-sdr', action='store_true', help='--stoi-wav-dir: also write <logdir>/<name>/sdr.csv (file,samples,si_sdr,snr,gain_db) on '
+                    'the same samples: the aligned overlap with --stoi-align, delay 0 without')
 parser.add_argument('--async-stats', action='store_true', help='training: no host read of loss / gradient norm inside a step (read when logged; '
                     'a NaN gradient norm skips the update on the device)')
 
@@ -438,8 +448,16 @@ def parse_args(argv=None):
         paras.stoi_max_len_diff = 0.05 if paras.stoi_max_len_diff is None else paras.stoi_max_len_diff
         if not 0.0 <= paras.stoi_max_len_diff < float('inf'):
             parser.error('--stoi-max-len-diff must be finite and at least 0 seconds')
+        if paras.stoi_max_delay is not None and not paras.stoi_align:
+            parser.error('--stoi-max-delay belongs to --stoi-align; it needs that flag')
+        if paras.stoi_align:
+            paras.stoi_max_delay = 0.05 if paras.stoi_max_delay is None else paras.stoi_max_delay
+            if not 0.0 <= paras.stoi_max_delay < float('inf'):
+                parser.error('--stoi-max-delay must be finite and at least 0 seconds')
     elif paras.stoi_ref_dir is not None or paras.stoi_max_len_diff is not None:
         parser.error('--stoi-ref-dir and --stoi-max-len-diff belong to --stoi-wav-dir; they need that flag')
+    elif paras.stoi_align or paras.stoi_sdr or paras.stoi_max_delay is not None:
+        parser.error('--stoi-align, --stoi-max-delay and --stoi-sdr belong to --stoi-wav-dir; they need that flag')
     if paras.trim_wav_dir is not None:
         for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
                      'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_silence'):

@@ -443,6 +443,11 @@ SIGNATURES = {
     'st_stoi_frames': [I],
     'st_stoi_workspace_floats': [I, I],
     'st_stoi_batch': [C.POINTER(StWaveBatch), P, P, P, I, P, P, P, P, P],
+    'st_xcorr_workspace_bytes': [I, I, I],
+    'st_xcorr_delay': [C.POINTER(StWaveBatch), C.POINTER(StWaveBatch), I, P, P, P, P, P],
+    'st_sisdr_workspace_bytes': [I, I],
+    'st_sisdr_batch': [C.POINTER(StWaveBatch), C.POINTER(StWaveBatch), P, I, P, P, P, P],
+    'st_wave_gather': [P, C.c_long, P, P, C.c_long, P, P, I, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,
@@ -451,7 +456,7 @@ _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t,
              'st_gl_batch_workspace_floats': C.c_size_t,
              'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t,
              'st_dtw_workspace_bytes': C.c_size_t, 'st_edit_align_workspace_bytes': C.c_size_t,
-             'st_stoi_workspace_floats': C.c_size_t}
+             'st_stoi_workspace_floats': C.c_size_t, 'st_xcorr_workspace_bytes': C.c_size_t, 'st_sisdr_workspace_bytes': C.c_size_t}
 
 _lib = None
 

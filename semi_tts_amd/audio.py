@@ -819,6 +819,26 @@ class WaveBatch:
         wb._packed = {str(buffer.device): buffer}
         return wb
 
+    @classmethod
+    def from_packed(cls, buffer, lens, order):
+        """a batch over a packed float32 device buffer that holds the utterances back to back in the order given: the i-th stretch of
+        `buffer` is utterance order[i] of the caller's list and has lens[order[i]] samples (lens: in the caller's order).  Nothing is
+        sorted or copied here -- the layout is the caller's statement, and the lengths must not grow along it."""
+        lens, order = np.asarray(lens, np.int64), np.asarray(order, np.int64)
+        if not (buffer.is_cuda and buffer.dtype == torch.float32 and buffer.dim() == 1 and buffer.is_contiguous()):
+            raise ValueError('features: a packed batch needs a contiguous 1-D float32 device buffer')
+        if lens.ndim != 1 or len(lens) == 0 or (lens < 1).any() or not np.array_equal(np.sort(order), np.arange(len(lens))):
+            raise ValueError('features: a packed batch needs positive lengths and a permutation of their indices')
+        if int(lens.sum()) != buffer.numel() or (np.diff(lens[order]) > 0).any():
+            raise ValueError('features: the buffer holds the utterances back to back, longest first')
+        off = np.concatenate([[0], np.cumsum(lens[order])[:-1]])
+        views = [None] * len(lens)
+        for i, o in zip(order, off):
+            views[i] = buffer[int(o):int(o + lens[i])]
+        wb = cls(views, order=order)
+        wb._packed[str(buffer.device)] = buffer
+        return wb
+
     def packed(self, device):
         key = str(device)
         if key not in self._packed:

@@ -21,6 +21,8 @@ LOUDNESS_SOURCES = ['loudness.hip']
 ABX_SOURCES = ['abx.hip']
 # the intelligibility kernels (st_stoi_batch), listed apart for the same reason
 STOI_SOURCES = ['stoi.hip']
+# the alignment kernels (st_xcorr_delay, st_sisdr_batch, st_wave_gather), listed apart for the same reason
+ALIGN_SOURCES = ['xcorr.hip']
 
 
 def _hipcc():
@@ -45,7 +47,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES + ABX_SOURCES + STOI_SOURCES:
+    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES + ABX_SOURCES + STOI_SOURCES + ALIGN_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

@@ -33,6 +33,15 @@ free-running synthesis, whose timing is the model's own: `mcd` along the warp is
 
     from semi_tts_amd.metrics import stoi
     r = stoi(recordings, vocoded, 22050)            # r.score[b] = (STOI, ESTOI), r.counts[b] = (frames, kept, band frames, segments)
+
+Pairs that are shifted against each other (a codec, another vocoder, a file cut elsewhere): `delay`, the integer delay by an exact float64
+cross-correlation (st_xcorr_delay, semi_tts_amd/csrc/xcorr.hip); `align_pairs`, both sides cut to the overlap in the layout `stoi` takes;
+`si_sdr`, SI-SDR / SNR / gain on the overlap (st_sisdr_batch).
+
+    from semi_tts_amd.metrics import align_pairs, si_sdr, stoi
+    ref, deg, d, coef = align_pairs(recordings, decoded, max_lag=1102)      # +-50 ms at 22050 Hz; d[b] > 0: decoded[b] is late
+    r = stoi(ref, deg, 22050)
+    s = si_sdr(recordings, decoded, d)              # s.score[b] = (SI-SDR dB, SNR dB, gain dB)
 """
 import collections
 import math
@@ -308,8 +317,8 @@ def abx(feat, item_start, item_len, label, cell, metric='angular', max_items=50,
 StoiResult = collections.namedtuple('StoiResult', 'score counts energy kept bands')
 
 
-def _stoi_side(what, wavs):
-    """one side of metrics.stoi as a WaveBatch (nothing is uploaded here)"""
+def _stoi_side(what, wavs, who='stoi'):
+    """one side of metrics.stoi (or of `who`, the function the messages name) as a WaveBatch (nothing is uploaded here)"""
     from .audio import WaveBatch
     if isinstance(wavs, WaveBatch):
         return wavs
@@ -318,13 +327,13 @@ def _stoi_side(what, wavs):
     try:
         n = len(wavs)
     except TypeError:
-        raise ValueError('stoi: %s must be a list of 1-D waveforms or a WaveBatch (got %s)' % (what, type(wavs).__name__))
+        raise ValueError('%s: %s must be a list of 1-D waveforms or a WaveBatch (got %s)' % (who, what, type(wavs).__name__))
     if n == 0:
-        raise ValueError('stoi: %s is an empty batch' % what)
+        raise ValueError('%s: %s is an empty batch' % (who, what))
     wavs = [torch.as_tensor(w) for w in wavs]
     for i, w in enumerate(wavs):
         if w.dim() != 1 or w.numel() < 1 or not (w.dtype.is_floating_point or w.dtype == torch.int16):
-            raise ValueError('stoi: %s[%d] must be a non-empty 1-D floating point or int16 waveform (got %s %s)' % (what, i, tuple(w.shape), w.dtype))
+            raise ValueError('%s: %s[%d] must be a non-empty 1-D floating point or int16 waveform (got %s %s)' % (who, what, i, tuple(w.shape), w.dtype))
     return WaveBatch([w.to(torch.float32) / 32768.0 if w.dtype == torch.int16 else w for w in wavs])
 
 
@@ -332,7 +341,8 @@ def stoi(clean, degraded, sample_rate, want_parts=False):
     """Short-time objective intelligibility of B (clean, processed) waveform pairs on one GPU: STOI (Taal, Hendriks, Heusdens, Jensen
     2011) and ESTOI (Jensen, Taal 2016); the definition is in include/semitts.h (st_stoi_batch, semi_tts_amd/csrc/stoi.hip).  clean,
     degraded: lists of 1-D waveforms (tensors or arrays; int16 PCM counts as x / 32768) or WaveBatches, pairwise of EQUAL length and
-    time-aligned -- the measure correlates short-time envelopes frame by frame, it does not search for a delay.  sample_rate: the rate
+    time-aligned -- the measure correlates short-time envelopes frame by frame and searches no delay itself: `align_pairs` finds a
+    constant shift and returns the two overlaps in the form this function takes.  sample_rate: the rate
     of both sides; anything but 10000 Hz goes through audio.resample first (the project's Hann-windowed sinc, so the values differ
     slightly from pystoi's, which emulates Octave's resample).  More than ops.STOI_MAX_BATCH pairs are issued in chunks of it.
     -> StoiResult of device tensors in the caller's order: score (B, 2) float32 = (STOI, ESTOI); counts (B, 4) int32 = (frames, kept
@@ -371,3 +381,119 @@ def stoi(clean, degraded, sample_rate, want_parts=False):
             for b0 in range(0, B, ops.STOI_MAX_BATCH)]
     inv = torch.from_numpy(np.argsort(order, kind='stable')).to(dev)     # row i of the result is the caller's pair i
     return StoiResult(*[torch.cat(parts).index_select(0, inv) if parts[0] is not None else None for parts in zip(*outs)])
+
+
+DelayResult = collections.namedtuple('DelayResult', 'delay coef corr')
+SiSdrResult = collections.namedtuple('SiSdrResult', 'score sums')
+
+
+def _pair_sides(what, clean, degraded):
+    """both sides of a batch of pairs whose lengths may differ -> (x buffer, y buffer, and in the CALLER's order the int64 arrays
+    x offsets, x lengths, y offsets, y lengths).  Every refusal is raised before anything is uploaded."""
+    import numpy as np
+    xb, yb = _stoi_side('clean', clean, what), _stoi_side('degraded', degraded, what)
+    if len(xb.lens) != len(yb.lens):
+        raise ValueError('%s: %d clean and %d processed signals: one of each per pair' % (what, len(xb.lens), len(yb.lens)))
+    longest = int(max(xb.lens.max(), yb.lens.max()))
+    if longest > ops.XCORR_MAX_LEN:
+        raise ValueError('%s: the longest signal has %d samples, above the limit of %d' % (what, longest, ops.XCORR_MAX_LEN))
+    ix, iy = np.argsort(np.asarray(xb.order), kind='stable'), np.argsort(np.asarray(yb.order), kind='stable')
+    return xb, yb, xb.offsets[ix], xb.lens[ix], yb.offsets[iy], yb.lens[iy]
+
+
+def _check_lag(what, max_lag):
+    import numpy as np
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag <= ops.XCORR_MAX_LAG:
+        raise ValueError('%s: max_lag must be an integer in [0, %d] (got %r)' % (what, ops.XCORR_MAX_LAG, max_lag))
+    return int(max_lag)
+
+
+def delay(clean, degraded, max_lag, want_corr=False):
+    """The integer delay of each of B (clean, processed) waveform pairs on one GPU: the lag in [-max_lag, max_lag] samples at which the
+    plain cross-correlation r[d] = sum_n x[n] y[n + d] is largest (st_xcorr_delay, semi_tts_amd/csrc/xcorr.hip; the definition is in
+    include/semitts.h).  A positive delay: the processed signal is late.  clean, degraded: lists of 1-D waveforms (tensors or arrays;
+    int16 PCM counts as x / 32768) or WaveBatches; the two lengths of a pair may differ.  The search is in float64 and exact on 16-bit
+    PCM input, so the decision has no tolerance there; ties go to the smallest |d|, then to the non-negative lag.  More than
+    ops.XCORR_MAX_BATCH pairs are issued in chunks of it.
+    -> DelayResult of device tensors in the caller's order: delay (B,) int32; coef (B,) float32 = r[d*] / sqrt(sum x^2 sum y^2); corr
+    (B, 2 max_lag + 1) float64 with want_corr (column d + max_lag), else None.  A NaN anywhere in r: delay 0, coef NaN.  A pair's
+    figures depend on that pair alone and are bitwise repeatable.  No host read.  Every refusal raises ValueError before the device is
+    touched."""
+    D = _check_lag('delay', max_lag)
+    from . import audio
+    xb, yb, xo, xl, yo, yl = _pair_sides('delay', clean, degraded)
+    dev = xb.device or yb.device or audio._device()
+    x, y = xb.packed(dev), yb.packed(dev)
+    M = ops.XCORR_MAX_BATCH
+    outs = [ops.xcorr_delay(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], D, want_corr) for b0 in range(0, len(xl), M)]
+    return DelayResult(*[torch.cat(parts) if parts[0] is not None else None for parts in zip(*outs)])
+
+
+def si_sdr(clean, degraded, delay=None, zero_mean=True):
+    """Scale-invariant signal-to-distortion ratio (Le Roux, Wisdom, Erdogan, Hershey 2019), SNR and gain of B waveform pairs on the
+    overlap a delay leaves (st_sisdr_batch; the definition is in include/semitts.h).  clean, degraded as for `delay`.  delay: None (0),
+    one int for every pair, or the device int32 tensor `delay(...)` returned (it stays on the device).  With d >= 0 the clean signal is
+    scored from 0 and the processed one from d; with d < 0 the clean one from -d and the processed one from 0; n = the shorter remainder.
+    zero_mean: the means over the overlap are removed first (the usual definition).
+    -> SiSdrResult of device tensors in the caller's order: score (B, 3) float32 = (SI-SDR dB, SNR dB, gain dB); sums (B, 6) float64 =
+    (n, sum x, sum y, sum x^2, sum y^2, sum x y), exact on 16-bit PCM input.  IEEE semantics: a scaled copy scores +inf without
+    zero_mean, a silent reference NaN (SNR -inf), a delay longer than a side NaN with n = 0.  No host read.  Every refusal raises ValueError
+    before the device is touched."""
+    import numpy as np
+    from . import audio
+    xb, yb, xo, xl, yo, yl = _pair_sides('si_sdr', clean, degraded)
+    B = len(xl)
+    if delay is not None and not torch.is_tensor(delay):
+        if isinstance(delay, bool) or not isinstance(delay, (int, np.integer)) or not -2 ** 31 < delay < 2 ** 31:
+            raise ValueError('si_sdr: delay must be None, an int or the device tensor metrics.delay returned (got %r)' % (delay,))
+    elif delay is not None and not (delay.is_cuda and delay.dtype == torch.int32 and tuple(delay.shape) == (B,)):
+        raise ValueError('si_sdr: a delay tensor must be int32 of shape (%d,) on the device (got %s %s on %s)'
+                         % (B, tuple(delay.shape), delay.dtype, delay.device))
+    dev = xb.device or yb.device or (delay.device if torch.is_tensor(delay) else None) or audio._device()
+    x, y = xb.packed(dev), yb.packed(dev)
+    if delay is not None:
+        delay = delay.contiguous() if torch.is_tensor(delay) else torch.full((B,), int(delay), device=dev, dtype=torch.int32)
+    M = ops.XCORR_MAX_BATCH
+    outs = [ops.sisdr_batch(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], None if delay is None else delay[b0:b0 + M], zero_mean)
+            for b0 in range(0, B, M)]
+    return SiSdrResult(*[torch.cat(parts) for parts in zip(*outs)])
+
+
+def overlap(lx, ly, d):
+    """the span a delay d leaves of a pair of lx and ly samples -> (first clean sample, first processed sample, samples; <= 0: none)"""
+    x0, y0 = max(0, -int(d)), max(0, int(d))
+    return x0, y0, min(int(lx) - x0, int(ly) - y0)
+
+
+def align_pairs(clean, degraded, max_lag):
+    """Searches each pair's delay (`delay`) and cuts both sides to the overlap it leaves.  -> (clean', degraded', delay, coef): the two
+    sides as WaveBatches over two NEW packed device buffers with one common layout and equal lengths -- what `stoi` accepts as it
+    stands -- and the device tensors of `delay`, in the caller's order.  The cut lengths reorder the batch (a WaveBatch is sorted longest
+    first); the order travels in the WaveBatches, so `stoi(clean', degraded', sr)` returns its rows in the caller's order.  One host
+    read: the B delays.  The spans are copied by one st_wave_gather launch per side and 64 pairs.  A pair whose best lag leaves no
+    overlap (possible only when max_lag reaches a signal's length) raises ValueError."""
+    import numpy as np
+    from . import audio
+    D = _check_lag('align_pairs', max_lag)
+    xb, yb, xo, xl, yo, yl = _pair_sides('align_pairs', clean, degraded)
+    dev = xb.device or yb.device or audio._device()
+    x, y = xb.packed(dev), yb.packed(dev)
+    M, B = ops.XCORR_MAX_BATCH, len(xl)
+    outs = [ops.xcorr_delay(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], D) for b0 in range(0, B, M)]
+    dl, coef = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+    d_host = dl.cpu().numpy()                                            # (the one host read)
+    spans = [overlap(xl[i], yl[i], d_host[i]) for i in range(B)]
+    for i, (_, _, n) in enumerate(spans):
+        if n < 1:
+            raise ValueError('align_pairs: pair %d: the best lag %d leaves no overlap of its %d and %d samples' % (i, d_host[i], xl[i], yl[i]))
+    n = np.array([s[2] for s in spans], np.int64)
+    order = np.argsort(-n, kind='stable')                                # longest overlap first; WaveBatch.from_packed is told this order
+    off = np.empty(B, np.int64)
+    off[order] = np.concatenate([[0], np.cumsum(n[order])[:-1]])         # (offsets in the caller's order)
+    sides = []
+    for buf, so in ((x, xo + np.array([s[0] for s in spans], np.int64)), (y, yo + np.array([s[1] for s in spans], np.int64))):
+        out = torch.empty(int(n.sum()), device=dev, dtype=torch.float32)
+        for b0 in range(0, B, M):
+            ops.wave_gather(buf, so[b0:b0 + M], out, off[b0:b0 + M], n[b0:b0 + M])
+        sides.append(audio.WaveBatch.from_packed(out, n, order))
+    return sides[0], sides[1], dl, coef

@@ -2699,3 +2699,120 @@ def stoi_batch(x, y, off, lens, F_pad=None, want_parts=False):
     check(lib.st_stoi_batch(_wave_chunk(w, off, lens, 0, B), _p(y), _p(score), _p(counts, torch.int32), F_pad, _p(energy), _p(kept, torch.int32),
                             _p(bands), _p(ws), stream_handle()), 'st_stoi_batch')
     return score, counts, energy, kept, bands
+
+
+# --------------------------------------------------------------------------------------------- alignment (st_xcorr_delay, st_sisdr_batch, st_wave_gather)
+XCORR_MAX_BATCH = 64                 # st_xcorr_delay's limits: pairs a call ...
+XCORR_MAX_LEN = 1 << 22              # ... samples of the longest signal of either side ...
+XCORR_MAX_LAG = 16384                # ... and the search bound D (+-0.34 s at 48 kHz)
+XCORR_CHUNK = 1024                   # samples of a staged piece, the smallest chunk of x: the tests straddle it
+XCORR_LAG_TILE = 2048                # lags a workgroup owns: the tests straddle it
+XCORR_MAX_CHUNKS = 32                # chunks of the longest signal: past 32 * 1024 samples the chunk grows
+SISDR_CHUNK = 8192                   # samples a workgroup of st_sisdr_batch's first launch sums
+
+
+def xcorr_chunk_len(L):
+    """samples of one chunk of an L-sample reference: XCORR_CHUNK times the smallest factor that leaves at most XCORR_MAX_CHUNKS chunks"""
+    return XCORR_CHUNK * ((int(L) + XCORR_CHUNK * XCORR_MAX_CHUNKS - 1) // (XCORR_CHUNK * XCORR_MAX_CHUNKS))
+
+
+def _pair_check(what, xlens, ylens, max_lag=0):
+    """every refusal of st_xcorr_delay / st_sisdr_batch that does not need the buffers, raised before any device is touched"""
+    xl, yl = np.asarray(xlens), np.asarray(ylens)
+    for name, v in (('x', xl), ('y', yl)):
+        if v.ndim != 1 or not 0 <= v.shape[0] <= XCORR_MAX_BATCH or (v.shape[0] and v.dtype.kind not in 'iu'):
+            raise ValueError('%s: the lengths of %s must be 0 .. %d integers, one call takes no more pairs (got %s)'
+                             % (what, name, XCORR_MAX_BATCH, 'shape %s, %s' % (v.shape, v.dtype)))
+        if v.shape[0] and ((v < 1).any() or (v > XCORR_MAX_LEN).any()):
+            raise ValueError('%s: every length of %s must lie in [1, %d] (got %s)' % (what, name, XCORR_MAX_LEN, v.tolist()))
+    if xl.shape[0] != yl.shape[0]:
+        raise ValueError('%s: %d references and %d processed signals: one of each per pair' % (what, xl.shape[0], yl.shape[0]))
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag <= XCORR_MAX_LAG:
+        raise ValueError('%s: max_lag must be an integer in [0, %d] (got %r)' % (what, XCORR_MAX_LAG, max_lag))
+
+
+def _pair_args(what, x, xoff, xlens, y, yoff, ylens):
+    xoff, xlens = _wave_args(what, x, xoff, xlens)
+    if not torch.is_tensor(y) or y.device != x.device:
+        raise ValueError('%s: y must be a packed 1-D contiguous float32 tensor on x\'s device' % what)
+    yoff, ylens = _wave_args(what, y, yoff, ylens)
+    wx, wy = _lib.StWaveBatch(x=_p(x), n_samples=x.numel()), _lib.StWaveBatch(x=_p(y), n_samples=y.numel())
+    B = len(xlens)
+    return _wave_chunk(wx, xoff, xlens, 0, B), _wave_chunk(wy, yoff, ylens, 0, B), (wx, wy, xoff, xlens, yoff, ylens)
+
+
+def xcorr_delay(x, xoff, xlens, y, yoff, ylens, max_lag, want_corr=False):
+    """st_xcorr_delay (the definition is in include/semitts.h): the integer delay of B pairs by direct float64 cross-correlation over
+    the lags [-max_lag, max_lag].  x, y: two packed float32 device buffers, pair b = x[xoff[b]:xoff[b] + xlens[b]] against
+    y[yoff[b]:yoff[b] + ylens[b]] (the lengths may differ, the offsets need not be cumulative), at most XCORR_MAX_BATCH pairs
+    (metrics.delay splits).  -> device tensors (delay (B,) int32, positive: y is late; coef (B,) float32; corr (B, 2 max_lag + 1)
+    float64 with want_corr, else None).  B = 0 launches nothing.  No host read.  Anything the kernel would refuse raises ValueError
+    before the device is touched."""
+    _pair_check('xcorr_delay', xlens, ylens, max_lag)
+    px, py, keep = _pair_args('xcorr_delay', x, xoff, xlens, y, yoff, ylens)
+    lib = _lib.load()
+    dev, B, D = x.device, len(keep[3]), int(max_lag)
+    delay = torch.empty(B, device=dev, dtype=torch.int32)
+    coef = torch.empty(B, device=dev, dtype=torch.float32)
+    corr = torch.empty(B, 2 * D + 1, device=dev, dtype=torch.float64) if want_corr else None
+    if B == 0:
+        return delay, coef, corr
+    max_len = int(max(keep[3].max(), keep[5].max()))
+    ws = torch.empty(int(lib.st_xcorr_workspace_bytes(B, max_len, D)) // 8, device=dev, dtype=torch.float64)
+    check(lib.st_xcorr_delay(px, py, D, _p(delay, torch.int32), _p(coef), _p(corr, torch.float64), _p(ws, torch.float64), stream_handle()),
+          'st_xcorr_delay')
+    return delay, coef, corr
+
+
+def sisdr_batch(x, xoff, xlens, y, yoff, ylens, delay=None, zero_mean=True):
+    """st_sisdr_batch (the definition is in include/semitts.h): SI-SDR, SNR and gain of B pairs on the overlap a delay leaves.  x, y as
+    for xcorr_delay.  delay: None (0) or a DEVICE int32 tensor (B,), read on the device only: the caller checks its values where they
+    come from the host.  -> device tensors (score (B, 3) float32 = (SI-SDR dB, SNR dB, gain dB), sums (B, 6) float64 = (n, sum x, sum y,
+    sum x^2, sum y^2, sum x y)).  B = 0 launches nothing.  No host read."""
+    _pair_check('sisdr_batch', xlens, ylens)
+    B = len(xlens)
+    if delay is not None and not (torch.is_tensor(delay) and delay.is_cuda and delay.dtype == torch.int32 and tuple(delay.shape) == (B,)
+                                  and delay.is_contiguous() and torch.is_tensor(x) and delay.device == x.device):
+        raise ValueError('sisdr_batch: delay must be None or a contiguous (%d,) int32 tensor on x\'s device (got %s)'
+                         % (B, '%s %s on %s' % (tuple(delay.shape), delay.dtype, delay.device) if torch.is_tensor(delay) else type(delay).__name__))
+    px, py, keep = _pair_args('sisdr_batch', x, xoff, xlens, y, yoff, ylens)
+    lib = _lib.load()
+    dev = x.device
+    score = torch.empty(B, 3, device=dev, dtype=torch.float32)
+    sums = torch.empty(B, 6, device=dev, dtype=torch.float64)
+    if B == 0:
+        return score, sums
+    max_len = int(max(keep[3].max(), keep[5].max()))
+    ws = torch.empty(int(lib.st_sisdr_workspace_bytes(B, max_len)) // 8, device=dev, dtype=torch.float64)
+    check(lib.st_sisdr_batch(px, py, _p(delay, torch.int32), int(bool(zero_mean)), _p(sums, torch.float64), _p(score), _p(ws, torch.float64),
+                             stream_handle()), 'st_sisdr_batch')
+    return score, sums
+
+
+def wave_gather(src, src_off, dst, dst_off, lens):
+    """st_wave_gather: dst[dst_off[b]:dst_off[b] + lens[b]] = src[src_off[b]:src_off[b] + lens[b]] for at most XCORR_MAX_BATCH spans in one
+    launch; src, dst: two different contiguous 1-D float32 buffers on one device; nothing else of dst is written.  -> dst"""
+    la = np.asarray(lens)
+    if la.ndim != 1 or not 0 <= la.shape[0] <= XCORR_MAX_BATCH or (la.shape[0] and (la.dtype.kind not in 'iu' or (la < 1).any() or (la > XCORR_MAX_LEN).any())):
+        raise ValueError('wave_gather: lens must be 0 .. %d integers in [1, %d] (got %s)' % (XCORR_MAX_BATCH, XCORR_MAX_LEN, la.tolist()))
+    B = la.shape[0]
+    so, do = np.asarray(src_off), np.asarray(dst_off)
+    if so.shape != (B,) or do.shape != (B,) or (B and (so.dtype.kind not in 'iu' or do.dtype.kind not in 'iu')):
+        raise ValueError('wave_gather: src_off and dst_off must hold %d integers each' % B)
+    for name, t in (('src', src), ('dst', dst)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 1 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('wave_gather: %s must be a contiguous 1-D float32 GPU tensor (got %s)'
+                             % (name, '%s %s on %s' % (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__))
+    if src.device != dst.device or src.data_ptr() == dst.data_ptr():
+        raise ValueError('wave_gather: src and dst must be two different buffers on one device')
+    if B == 0:
+        return dst
+    so, do = np.ascontiguousarray(so, dtype=np.int64), np.ascontiguousarray(do, dtype=np.int64)
+    la = np.ascontiguousarray(la, dtype=np.int32)
+    if (so < 0).any() or (so + la > src.numel()).any() or (do < 0).any() or (do + la > dst.numel()).any():
+        raise ValueError('wave_gather: a span lies outside its buffer (src %d samples, dst %d; src_off %s, dst_off %s, lens %s)'
+                         % (src.numel(), dst.numel(), so.tolist(), do.tolist(), la.tolist()))
+    lib = _lib.load()
+    check(lib.st_wave_gather(_p(src), src.numel(), so.ctypes.data, _p(dst), dst.numel(), do.ctypes.data, la.ctypes.data, B, stream_handle()),
+          'st_wave_gather')
+    return dst

@@ -730,6 +730,9 @@ class McdScorer:
 
 STOI_HEADER = 'file,samples,frames,kept,segments,stoi,estoi'
 STOI_MAX_LEN_DIFF = 0.05            # seconds: r = 3 decoder frames of 12.5 ms plus the vocoder's lost partial hop
+STOI_MAX_DELAY = 0.05               # seconds: --stoi-align's default search bound
+DELAY_HEADER = 'file,delay_samples,delay_s,coef'
+SDR_HEADER = 'file,samples,si_sdr,snr,gain_db'
 
 
 def stoi_row(file, samples, counts, score):
@@ -742,7 +745,9 @@ class StoiScorer:
     (mcd_key, the pairing of --mcd-wav-dir), in batches of --batch-size (at most 64 pairs a call) -> metrics.stoi (both sides resampled
     to 10 kHz on the device when the files are at another rate, then st_stoi_batch) -> one host read per batch -> <logdir>/stoi.csv
     (STOI_HEADER, one row per pair: the samples scored at the files' rate, the frames at 10 kHz, the frames kept, the segments, STOI,
-    ESTOI).  The two files of a pair must be time-aligned: a vocoded spectrogram against its recording, not free-running synthesis.
+    ESTOI).  The two files of a pair must be time-aligned: a vocoded spectrogram against its recording, not free-running synthesis --
+    or shifted by a constant delay that --stoi-align [--stoi-max-delay 0.05] searches first (metrics.align_pairs: the overlap is scored,
+    delay.csv written, a best lag on the bound warned about); --stoi-sdr adds sdr.csv (metrics.si_sdr).  Without those flags nothing changes.
     A pair whose lengths differ by at most --stoi-max-len-diff seconds is cut to the shorter side at its end.  A pair too short for one
     segment (under 30 band frames) gets the sentinel row (segments 0, both scores 1e-5), a warning naming it, and no part in the means.
     No config, no checkpoint, no model.  Every pair is looked up and every header read in load_data: a missing or shared recording, an
@@ -755,6 +760,9 @@ class StoiScorer:
         self.logdir = os.path.join(getattr(paras, 'logdir', 'log/'), self.exp_name)
         d = getattr(paras, 'stoi_max_len_diff', None)
         self.max_len_diff = STOI_MAX_LEN_DIFF if d is None else float(d)
+        self.align, self.sdr = bool(getattr(paras, 'stoi_align', False)), bool(getattr(paras, 'stoi_sdr', False))
+        d = getattr(paras, 'stoi_max_delay', None)
+        self.max_delay = (STOI_MAX_DELAY if d is None else float(d)) if self.align else 0.0
 
     @staticmethod
     def _header(path):
@@ -774,7 +782,7 @@ class StoiScorer:
         from . import audio
         self.syn_dir, self.ref_dir = self.paras.stoi_wav_dir, self.paras.stoi_ref_dir
         self.pairs = mcd_pairs(self.syn_dir, self.ref_dir, '--stoi-wav-dir')
-        self.rates, self.samples = [], []
+        self.rates, self.samples, self.lens = [], [], []
         for f, _, ref in self.pairs:
             ps, pr = os.path.join(self.syn_dir, f), os.path.join(self.ref_dir, ref)
             (sr, L), (sr_ref, L_ref) = self._header(ps), self._header(pr)
@@ -784,15 +792,26 @@ class StoiScorer:
                 audio.resample_table(sr, ops.STOI_FS)
             except ValueError as e:
                 raise ValueError('--stoi-wav-dir: %s: %s' % (ps, e))
-            if abs(L - L_ref) > self.max_len_diff * sr:
+            if self.align:
+                if not 0.0 <= self.max_delay < math.inf or self.max_delay * sr > ops.XCORR_MAX_LAG:
+                    raise ValueError('--stoi-align: %s is at %d Hz: --stoi-max-delay %g must be finite, at least 0 and at most %d samples = %.4f s at '
+                                     'that rate' % (ps, sr, self.max_delay, ops.XCORR_MAX_LAG, ops.XCORR_MAX_LAG / float(sr)))
+                if abs(L - L_ref) > (self.max_len_diff + self.max_delay) * sr:
+                    raise ValueError('--stoi-wav-dir: %s has %d samples and its recording %s %d: they differ by %.4f s, above --stoi-max-len-diff %g '
+                                     'plus --stoi-max-delay %g' % (ps, L, pr, L_ref, abs(L - L_ref) / float(sr), self.max_len_diff, self.max_delay))
+            elif abs(L - L_ref) > self.max_len_diff * sr:
                 raise ValueError('--stoi-wav-dir: %s has %d samples and its recording %s %d: they differ by %.4f s, above --stoi-max-len-diff %g; '
                                  'the measure needs time-aligned signals' % (ps, L, pr, L_ref, abs(L - L_ref) / float(sr), self.max_len_diff))
             n = min(L, L_ref)
             if audio.resampled_len(n, sr, ops.STOI_FS) > ops.STOI_MAX_LEN:
                 raise ValueError('--stoi-wav-dir: %s has %d samples at %d Hz; the measure takes at most %d' % (ps, audio.resampled_len(n, sr, ops.STOI_FS),
                                                                                                         ops.STOI_FS, ops.STOI_MAX_LEN))
+            if (self.align or self.sdr) and max(L, L_ref) > ops.XCORR_MAX_LEN:
+                raise ValueError('--stoi-wav-dir: %s and its recording have up to %d samples; --stoi-align and --stoi-sdr take at most %d'
+                                 % (ps, max(L, L_ref), ops.XCORR_MAX_LEN))
             self.rates.append(sr)
             self.samples.append(n)
+            self.lens.append((L, L_ref))
         return self
 
     def set_model(self):
@@ -821,7 +840,48 @@ class StoiScorer:
             out[i - lo] = (host[row, :4].copy(), host[row, 4:6].copy().view(np.float32))
         return out
 
+    def lag(self, sr):
+        """--stoi-max-delay in samples at this rate"""
+        return int(math.floor(self.max_delay * sr + 1e-6))
+
+    def score_aligned(self, lo, hi):
+        """pairs [lo, hi) with --stoi-align and / or --stoi-sdr -> per pair (counts (4,) int32, score (2,) float32, delay, coef, sdr (3,)
+        float32).  Per sample rate among them the files are uploaded once; the delay search (one host read of the delays inside
+        metrics.align_pairs), the gather of the overlaps, metrics.stoi on the cut batches and metrics.si_sdr all read the device buffers;
+        one more host read returns every figure."""
+        from . import audio, metrics
+        idx, cols = [], []
+        for sr in sorted(set(self.rates[lo:hi])):
+            sel = [i for i in range(lo, hi) if self.rates[i] == sr]
+            syn, rec = [], []
+            for i in sel:
+                f, _, ref = self.pairs[i]
+                L, L_ref = self.lens[i] if self.align else (self.samples[i], self.samples[i])
+                syn.append(audio.read_wav(os.path.join(self.syn_dir, f))[0][0, :L])
+                rec.append(audio.read_wav(os.path.join(self.ref_dir, ref))[0][0, :L_ref])
+            syn, rec = audio.WaveBatch(syn), audio.WaveBatch(rec)
+            dev = audio._device()
+            syn.packed(dev), rec.packed(dev)                            # (the one upload of each side)
+            syn.device = rec.device = dev
+            if self.align:
+                cut_rec, cut_syn, dl, coef = metrics.align_pairs(rec, syn, self.lag(sr))
+            else:
+                cut_rec, cut_syn = rec, syn
+                dl, coef = torch.zeros(len(sel), device=dev, dtype=torch.int32), torch.full((len(sel),), math.nan, device=dev)
+            res = metrics.stoi(cut_rec, cut_syn, sr)
+            sdr = metrics.si_sdr(rec, syn, dl if self.align else None).score if self.sdr else torch.full((len(sel), 3), math.nan, device=dev)
+            cols.append(torch.cat([res.counts, res.score.view(torch.int32), dl.view(-1, 1), coef.view(torch.int32).view(-1, 1), sdr.view(torch.int32)], dim=1))
+            idx += sel
+        host = torch.cat(cols, dim=0).cpu().numpy()                     # (the one host read of the scores)
+        out = [None] * (hi - lo)
+        for row, i in enumerate(idx):
+            out[i - lo] = (host[row, :4].copy(), host[row, 4:6].copy().view(np.float32), int(host[row, 6]), float(host[row, 7:8].copy().view(np.float32)[0]),
+                           host[row, 8:11].copy().view(np.float32))
+        return out
+
     def exec(self):
+        if self.align or self.sdr:
+            return self.exec_aligned()
         os.makedirs(self.logdir, exist_ok=True)
         B = max(1, min(int(self.paras.batch_size), ops.STOI_MAX_BATCH))
         t0, rows, vals = time.perf_counter(), [STOI_HEADER], []
@@ -840,6 +900,46 @@ class StoiScorer:
         self.mean_stoi, self.mean_estoi = (float(v) for v in np.mean(np.asarray(vals, np.float64), axis=0)) if vals else (math.nan, math.nan)
         print('[INFO]', 'STOI of %d pairs (%d scored): mean STOI %.4f, mean ESTOI %.4f; %s, %.2f s'
               % (len(self.pairs), len(vals), self.mean_stoi, self.mean_estoi, os.path.join(self.logdir, 'stoi.csv'), time.perf_counter() - t0))
+        return len(self.pairs)
+
+    def exec_aligned(self):
+        """exec with --stoi-align and / or --stoi-sdr: stoi.csv on the scored samples (the overlap), delay.csv, sdr.csv"""
+        from .metrics import overlap
+        os.makedirs(self.logdir, exist_ok=True)
+        B = max(1, min(int(self.paras.batch_size), ops.STOI_MAX_BATCH))
+        t0, rows, vals, drows, srows, delays, sdrs = time.perf_counter(), [STOI_HEADER], [], [DELAY_HEADER], [SDR_HEADER], [], []
+        for lo in range(0, len(self.pairs), B):
+            hi = min(lo + B, len(self.pairs))
+            for i, (counts, score, d, coef, sdr) in zip(range(lo, hi), self.score_aligned(lo, hi)):
+                f, sr = self.pairs[i][0], self.rates[i]
+                if self.align:
+                    self.samples[i] = overlap(self.lens[i][1], self.lens[i][0], d)[2]
+                    drows.append('%s,%d,%.6f,%.6f' % (f, d, d / float(sr), coef))
+                    delays.append(abs(d) / float(sr))
+                    if self.lag(sr) > 0 and abs(d) == self.lag(sr):
+                        print('[WARNING]', '--stoi-align: the best lag of %s, %d samples, sits on the search bound of +-%d samples (--stoi-max-delay %g): '
+                              'the true delay may lie outside it' % (f, d, self.lag(sr), self.max_delay))
+                if self.sdr:
+                    srows.append('%s,%d,%.4f,%.4f,%.4f' % (f, self.samples[i], sdr[0], sdr[1], sdr[2]))
+                    sdrs.append(float(sdr[0]))
+                rows.append(stoi_row(f, self.samples[i], counts, score))
+                if counts[3] == 0 and not np.isnan(score[0]):
+                    print('[WARNING]', '--stoi-wav-dir: %s has %d band frames, fewer than the %d of one segment: the sentinel %g is written and '
+                          'the file is left out of the means' % (f, counts[2], ops.STOI_SEG, ops.STOI_SENTINEL))
+                else:
+                    vals.append(score)
+        for name, lines, on in (('stoi.csv', rows, True), ('delay.csv', drows, self.align), ('sdr.csv', srows, self.sdr)):
+            if on:
+                with open(os.path.join(self.logdir, name), 'w') as fh:
+                    fh.write('\n'.join(lines) + '\n')
+        self.mean_stoi, self.mean_estoi = (float(v) for v in np.mean(np.asarray(vals, np.float64), axis=0)) if vals else (math.nan, math.nan)
+        self.mean_abs_delay = float(np.mean(delays)) if delays else math.nan
+        finite = [v for v in sdrs if math.isfinite(v)]
+        self.mean_si_sdr = float(np.mean(finite)) if finite else math.nan
+        extra = (', mean |delay| %.6f s' % self.mean_abs_delay if self.align else '') + \
+                (', mean SI-SDR %.2f dB over %d finite' % (self.mean_si_sdr, len(finite)) if self.sdr else '')
+        print('[INFO]', 'STOI of %d pairs (%d scored): mean STOI %.4f, mean ESTOI %.4f%s; %s, %.2f s'
+              % (len(self.pairs), len(vals), self.mean_stoi, self.mean_estoi, extra, os.path.join(self.logdir, 'stoi.csv'), time.perf_counter() - t0))
         return len(self.pairs)
 
 
