@@ -603,6 +603,13 @@ def parse_args(argv=None):
     return paras
 
 
+# (attribute of paras, class of semi_tts_amd.solver): the modes that do not train; the first one whose flag is given runs
+TOOLS = (('resample_wav_dir', 'Resampler'), ('trim_wav_dir', 'Trimmer'), ('loudness_wav_dir', 'LoudnessWriter'), ('vocode_dir', 'Vocoder'),
+         ('feat_wav_dir', 'FeatureWriter'), ('mcd_wav_dir', 'McdScorer'), ('stoi_wav_dir', 'StoiScorer'), ('abx_ali_dir', 'AbxScorer'),
+         ('score_phn_dir', 'PhnScorer'), ('synth_phn_dir', 'Synthesiser'), ('transcribe_wav_dir', 'Transcriber'), ('align_wav_dir', 'Aligner'),
+         ('gen_specgram', 'SpecgramGenerator'))
+
+
 def main(argv=None):
     paras = parse_args(argv)
     if paras.build_lm_phn_dir is not None:                  # host only: no config, no seed, no device
@@ -634,45 +641,10 @@ def main(argv=None):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('nccl')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    if paras.resample_wav_dir is not None:
-        from semi_tts_amd.solver import Resampler as Solver
-        mode = 'test'
-    elif paras.trim_wav_dir is not None:
-        from semi_tts_amd.solver import Trimmer as Solver
-        mode = 'test'
-    elif paras.loudness_wav_dir is not None:
-        from semi_tts_amd.solver import LoudnessWriter as Solver
-        mode = 'test'
-    elif paras.vocode_dir is not None:
-        from semi_tts_amd.solver import Vocoder as Solver
-        mode = 'test'
-    elif paras.feat_wav_dir is not None:
-        from semi_tts_amd.solver import FeatureWriter as Solver
-        mode = 'test'
-    elif paras.mcd_wav_dir is not None:
-        from semi_tts_amd.solver import McdScorer as Solver
-        mode = 'test'
-    elif paras.stoi_wav_dir is not None:
-        from semi_tts_amd.solver import StoiScorer as Solver
-        mode = 'test'
-    elif paras.abx_ali_dir is not None:
-        from semi_tts_amd.solver import AbxScorer as Solver
-        mode = 'test'
-    elif paras.score_phn_dir is not None:
-        from semi_tts_amd.solver import PhnScorer as Solver
-        mode = 'test'
-    elif paras.synth_phn_dir is not None:
-        from semi_tts_amd.solver import Synthesiser as Solver
-        mode = 'test'
-    elif paras.transcribe_wav_dir is not None:
-        from semi_tts_amd.solver import Transcriber as Solver
-        mode = 'test'
-    elif paras.align_wav_dir is not None:
-        from semi_tts_amd.solver import Aligner as Solver
-        mode = 'test'
-    elif paras.gen_specgram:
-        from semi_tts_amd.solver import SpecgramGenerator as Solver
-        mode = 'test'
+    tool = next((name for flag, name in TOOLS if getattr(paras, flag) not in (None, False)), None)
+    if tool is not None:
+        import semi_tts_amd.solver
+        Solver, mode = getattr(semi_tts_amd.solver, tool), 'test'
     elif paras.tts_only:
         from semi_tts_amd.solver import TtsTrainer as Solver
         mode = 'train'

@@ -458,7 +458,7 @@ class AudioConverter:
         stats = host[:8 * B].view(np.float32).reshape(B, 8).astype(np.float64)
         counts = host[8 * B:].reshape(B, 4).astype(np.int64)
         given = isinstance(wavs, WaveBatch)
-        inv = np.arange(B) if given else np.argsort(np.asarray(wb.order), kind='stable')     # row of wb of utterance i of a list
+        inv = np.arange(B) if given else wb.inverse()                       # row of wb of utterance i of a list
         with np.errstate(divide='ignore'):
             info = dict(lufs=stats[inv, 0], momentary_max=stats[inv, 1], rel_gate=stats[inv, 2], peak=stats[inv, 3], ungated=stats[inv, 4],
                         gain_db=20.0 * np.log10(stats[inv, 5]), n_blocks=counts[inv, 0], n_abs=counts[inv, 1], n_rel=counts[inv, 2],
@@ -510,7 +510,7 @@ class AudioConverter:
         out = WaveBatch.window(x, (wb.offsets + start)[rows], (end - start)[rows])
         out.order = np.asarray(wb.order)[rows]
         given = isinstance(wavs, WaveBatch)
-        inv = np.arange(B) if given else np.argsort(np.asarray(wb.order), kind='stable')     # row of wb of utterance i of a list
+        inv = np.arange(B) if given else wb.inverse()                       # row of wb of utterance i of a list
         res = (out, np.stack([start, end], 1)[inv], int(short.sum()))
         if with_intervals:
             res += ([iv[r, :n_iv[r]].copy() for r in inv],)
@@ -839,6 +839,10 @@ class WaveBatch:
         wb._packed[str(buffer.device)] = buffer
         return wb
 
+    def inverse(self):
+        """the inverse of `order`: element i is the row of this batch that holds the i-th given utterance"""
+        return np.argsort(np.asarray(self.order), kind='stable')
+
     def packed(self, device):
         key = str(device)
         if key not in self._packed:
@@ -935,12 +939,16 @@ def read_wav(path):
 def write_wav(path, wav, sr):
     """16-bit PCM mono .wav through the standard library (soundfile's default subtype for .wav): round(clip(x, -1, 1) * 32767)"""
     wav = np.asarray(wav, dtype=np.float64).reshape(-1)
-    pcm = np.rint(np.clip(wav, -1.0, 1.0) * 32767.0).astype('<i2')
+    write_pcm16(path, np.rint(np.clip(wav, -1.0, 1.0) * 32767.0), sr)
+
+
+def write_pcm16(path, pcm, sr):
+    """16-bit PCM mono .wav of samples that are int16 values already"""
     with wave.open(str(path), 'wb') as w:
         w.setnchannels(1)
         w.setsampwidth(2)
         w.setframerate(int(sr))
-        w.writeframes(pcm.tobytes())
+        w.writeframes(np.ascontiguousarray(pcm, dtype='<i2').tobytes())
 
 
 # -- sample-rate conversion (st_resample_batch; the definition is in include/semitts.h and DESIGN.md 3.14)

@@ -379,7 +379,7 @@ def stoi(clean, degraded, sample_rate, want_parts=False):
     F_pad = max(1, max(ops.stoi_frames(v) for v in lens))             # one width for every chunk: the parts concatenate
     outs = [ops.stoi_batch(x, y, off[b0:b0 + ops.STOI_MAX_BATCH], lens[b0:b0 + ops.STOI_MAX_BATCH], F_pad, want_parts)
             for b0 in range(0, B, ops.STOI_MAX_BATCH)]
-    inv = torch.from_numpy(np.argsort(order, kind='stable')).to(dev)     # row i of the result is the caller's pair i
+    inv = torch.from_numpy(xb.inverse()).to(dev)                         # row i of the result is the caller's pair i
     return StoiResult(*[torch.cat(parts).index_select(0, inv) if parts[0] is not None else None for parts in zip(*outs)])
 
 
@@ -397,7 +397,7 @@ def _pair_sides(what, clean, degraded):
     longest = int(max(xb.lens.max(), yb.lens.max()))
     if longest > ops.XCORR_MAX_LEN:
         raise ValueError('%s: the longest signal has %d samples, above the limit of %d' % (what, longest, ops.XCORR_MAX_LEN))
-    ix, iy = np.argsort(np.asarray(xb.order), kind='stable'), np.argsort(np.asarray(yb.order), kind='stable')
+    ix, iy = xb.inverse(), yb.inverse()
     return xb, yb, xb.offsets[ix], xb.lens[ix], yb.offsets[iy], yb.lens[iy]
 
 
