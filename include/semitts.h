@@ -585,13 +585,66 @@ int st_copy3d(float* dst, long dst_sb, long dst_st, const float* src, long src_s
 int st_scatter_add_rows(const float* dout, const int64_t* idx, float* dtable, int n, int D, int V, void* stream);
 
 /* ------------------------------------------------------------------ recurrent sequence layers */
-/* One direction of nn.LSTM over a full sequence: xproj (B,T,4H) = x W_ih^T + b_ih
- * (from st_gemm_fwd; b_hh is added in the cell), out(b, t, ocol : ocol+H) = h_t.  Workspace ws: 3*B*H floats.
- * Training: gates_tape (T,B,4,H) receives the activated gates and c_tape (T,B,H) every cell state (both
- * indexed by time step); NULL in inference.
- * ref: nn.LSTM src/module.py:432-438,:458-460 (lengths ignored, zero initial state). */
-int st_lstm_seq_fwd(const float* xproj, const float* w_hh, const float* b_hh, float* out, int ldo, int ocol,
-                    float* ws, float* gates_tape, float* c_tape, int B, int T, int H, int reverse, void* stream);
+/* One nn.LSTM layer (ndir = 1, or 2 for bidirectional=True) over a full sequence, lengths ignored, zero initial state.
+ * xproj[d] (B,T,4H) = x W_ih[d]^T + b_ih[d] (from st_gemm_fwd; b_hh is added in the cell), out(b, t, ocol[d] : ocol[d]+H) = h_t of
+ * direction d.  Of two directions, 0 walks t = s and 1 walks t = T-1-s; one direction walks backward with `reverse`.  Training:
+ * gates_tape[d] (T,B,4,H) receives the activated gates and c_tape[d] (T,B,H) every cell state (both indexed by time step).
+ * The backward takes dout(b, t, dcol[d] : dcol[d]+H) to dxproj[d] (B,T,4H) (= gradient of the input projection incl. both biases); the
+ * caller finishes with dW_hh = st_gemm_wgrad(dxproj, out shifted by one step) and db = st_colsum(dxproj).
+ * st_lstm_seq_variant is the one place a form is chosen (host arithmetic only; -1: null pointer, or a shape no form takes):
+ *   ST_LSTM_STEP     one launch per time step (backward: a pointwise and a W_hh^T launch, w = W_hh^T (H,4H): ST_LSTM_W_T).
+ *                    ws_floats: forward (2 ndir + 1) B H, backward 2 ndir B H.
+ *   ST_LSTM_PACKED   backward, ndir == 2, H % 16 == 0: one launch per time step, dgates(s) . W_hh with the pointwise backward of step s-1
+ *                    in its epilogue; w = st_pack_weight_t of W_hh (N = H, K = 4H): ST_LSTM_W_PACKED_T.  ws_floats: 2 B H +
+ *                    4 st_t16_floats(B, 4H), ws 16-byte aligned.
+ *   ST_LSTM_PERSIST  ndir == 2: ALL time steps in ONE launch, its workgroups resident at once on cus - cu_reserve compute units (cus == 0:
+ *                    this device's).  The plain (4H,H) weights (ST_LSTM_W_NATURAL) and the cell states / dL/dc stay in registers; the
+ *                    hand-over between steps is polled straight out of out / dxproj, which the entry first fills with a sentinel (every
+ *                    word is written exactly once: the data is the flag).  Forward: H = 64, 128, 256 or 512, B <= 64, disjoint output
+ *                    columns.  Backward: H = 32, 64, 128 or 256.  ld and col multiples of 4, every ST_LSTM_AL_* operand of the pass 16-byte
+ *                    aligned, allow_persist != 0.  *status (optional device word): bit 1 set when a wait timed out -- the launch was
+ *                    starved of compute units, the affected rows are NaN.  The plan names the launch: grid, block, rt row tiles, nkb
+ *                    k-blocks per wave, rg batch rows per workgroup (backward), xcd_map (forward); 0 for the other forms.
+ * The run entry points plan from the job itself and refuse one whose `weights` is not the plan's or whose ws is NULL while ws_floats > 0.
+ * ref: nn.LSTM src/module.py:432-438,:458-460 and its backward */
+#define ST_LSTM_STEP 0
+#define ST_LSTM_PACKED 1
+#define ST_LSTM_PERSIST 2
+#define ST_LSTM_W_NATURAL 0
+#define ST_LSTM_W_T 1
+#define ST_LSTM_W_PACKED_T 2
+#define ST_LSTM_AL_OUT 1           /* forward: out, and w_hh[d] (<< d) */
+#define ST_LSTM_AL_W0 2
+#define ST_LSTM_AL_DOUT 1          /* backward: dout, and gates_tape[d], c_tape[d], dxproj[d] (<< d) */
+#define ST_LSTM_AL_GATES0 2
+#define ST_LSTM_AL_C0 8
+#define ST_LSTM_AL_DX0 32
+typedef struct st_lstm_seq_job {
+    int ndir, reverse;                /* ndir 1 or 2; reverse only with ndir == 1 */
+    const float *xproj[2], *w_hh[2], *b_hh[2];
+    float* out; int ldo; int ocol[2];
+    float *gates_tape[2], *c_tape[2]; /* NULL in inference */
+    int B, T, H;
+    float* ws;                        /* plan.ws_floats floats */
+    unsigned* status;                 /* one-launch form only */
+    int allow_persist, cu_reserve;
+} st_lstm_seq_job;
+typedef struct st_lstm_seq_bwd_job {
+    int ndir, reverse;
+    const float* dout; int ldd; int dcol[2];
+    const float *gates_tape[2], *c_tape[2];
+    const float* w[2];                /* in the layout plan.weights names */
+    int weights;                      /* ST_LSTM_W_*: what w[] holds */
+    float* dxproj[2];
+    int B, T, H;
+    float* ws; unsigned* status; int allow_persist, cu_reserve;
+} st_lstm_seq_bwd_job;
+/* ld, col: ldo, ocol (forward) or ldd, dcol (backward) */
+typedef struct st_lstm_seq_query { int backward, ndir, B, T, H, ld, col[2]; unsigned aligned; int allow_persist, cus, cu_reserve; } st_lstm_seq_query;
+typedef struct st_lstm_seq_plan { int form, weights; size_t ws_floats; int grid_x, grid_y, grid_z, block, rt, nkb, rg, xcd_map; } st_lstm_seq_plan;
+int st_lstm_seq_variant(const st_lstm_seq_query* q, st_lstm_seq_plan* out);
+int st_lstm_seq_fwd(const st_lstm_seq_job* j, void* stream);
+int st_lstm_seq_bwd(const st_lstm_seq_bwd_job* j, void* stream);
 /* Pointwise half of one LSTM cell backward step (shared by the encoder BiLSTM and the decoder's two cells):
  * dh = (dh0 + dh1 + dh2 * scale2) * mask;  from dh and the carried dc (B,H, updated in place to dL/dc_{t-1})
  * to dgates (B,4H) w.r.t. the pre-activation gates in torch order (i,f,g,o).  dh1, dh2, scale2, mask, c_prev
@@ -601,47 +654,12 @@ int st_lstm_cell_bwd_pointwise(const float* dh0, int ld0, const float* dh1, int 
                                const float* scale2, const float* mask, const float* gates, const float* c, int ldc,
                                const float* c_prev, int ldcp, float* dc, float* dgates, int ldg,
                                const st_t16_view* dgates_t16, int B, int H, void* stream);
-/* Both directions of nn.LSTM(bidirectional=True) in one pass: per time step ONE launch advances direction 0 at t = s and direction
- * 1 at t = T-1-s (st_lstm_cell_pair_fwd: two cells of the same shape, blockIdx.z picks the job).  Arguments as st_lstm_seq_fwd in
- * arrays of two; ws: 6*B*H floats.  ref: nn.LSTM src/module.py:432-438,458-460 */
+/* Two LSTM cells / two plain linears of the same shape in ONE launch (the two directions of a bidirectional layer at their own time
+ * steps): arrays of two, one segment each */
 int st_lstm_cell_pair_fwd(const st_seg* segs2, const float* const* b_hh2, const float* const* pre2, int ldpre,
                           const float* const* c_prev2, int ldc_prev, float* const* h_out2, int ldh,
                           float* const* c_out2, int ldc, float* const* gates_out2, int B, int H, void* stream);
-int st_lstm_seq2_fwd(const float* const* xproj2, const float* const* w_hh2, const float* const* b_hh2, float* out, int ldo,
-                     const int* ocol2, float* ws, float* const* gates_tape2, float* const* c_tape2,
-                     int B, int T, int H, void* stream);
-/* The same layer as ONE launch for all T steps (H % 64 == 0, H <= 512, B <= 64, 2 * H/4 workgroups resident at once): the recurrent
- * weights and the cell states stay in registers, h_{t-1} is polled straight out of `out`, which the entry first fills with a sentinel
- * (every h is written exactly once: the data is the flag).  *status (optional device word): bit 1 set when a wait timed out -- the launch
- * was starved of compute units, the affected rows are NaN.  st_lstm_seq2_persist_supported tells whether a shape is taken.
- * ref: nn.LSTM src/module.py:432-438,458-460 */
-int st_lstm_seq2_persist_supported(int B, int T, int H, int ldo, int ocol0, int ocol1);
-int st_lstm_seq2_persist_fwd(const float* const* xproj2, const float* const* w_hh2, const float* const* b_hh2, float* out, int ldo,
-                             const int* ocol2, float* const* gates_tape2, float* const* c_tape2,
-                             int B, int T, int H, unsigned* status, void* stream);
-/* backward of both directions at once (see st_lstm_seq_bwd; arrays of two, ws: 4*B*H floats): one pointwise launch and one
- * W_hh^T launch per time step for the two directions */
-int st_lstm_seq2_bwd(const float* dout, int ldd, const int* dcol2, const float* const* gates_tape2, const float* const* c_tape2,
-                     const float* const* w_hh_t2, float* const* dxproj2, float* ws, int B, int T, int H, void* stream);
-/* The same loop as ONE launch for all T steps (H % 32 == 0, H <= 256, 2 * H/16 * ceil(B/16) workgroups resident at once): the
- * 4H x 16 slices of W_hh (the plain (4H, H) parameters, no transposed copy) and the carried dL/dc stay in registers, the gate gradients
- * of the step before are polled straight out of dxproj2[d] (B, T, 4H), which the entry first fills with a sentinel (every word is
- * written exactly once).  *status: as st_lstm_seq2_persist_fwd.  ref: backward of nn.LSTM src/module.py:432-438,458-460 */
-int st_lstm_seq2_bwd_persist_supported(int B, int T, int H, int ldd, int dcol0, int dcol1);
-int st_lstm_seq2_bwd_persist(const float* dout, int ldd, const int* dcol2, const float* const* gates_tape2, const float* const* c_tape2,
-                             const float* const* w_hh2, float* const* dxproj2, int B, int T, int H, unsigned* status, void* stream);
 int st_skinny_linear_pair_fwd(const st_seg* segs2, float* const* y2, int ldy, int B, int N, void* stream);
-/* st_lstm_seq2_bwd on packed operands: ONE launch per time step for the two directions -- dgates(s) . W_hh with the pointwise backward of
- * step s-1 in its epilogue (st_skinny_linear_packed_lstm_bwd_pair_fwd).  w_hh_t_p16_2: st_pack_weight_t of each direction's W_hh (N = H,
- * K = 4H); dg_t16_ws: 4 * st_t16_floats(B, 4H) floats (two ping-pong T16 copies of dgates per direction).  ws: 2*B*H floats (dc carries). */
-int st_lstm_seq2_bwd_packed(const float* dout, int ldd, const int* dcol2, const float* const* gates_tape2, const float* const* c_tape2,
-                            const float* const* w_hh_t_p16_2, float* const* dxproj2, float* ws, float* dg_t16_ws,
-                            int B, int T, int H, void* stream);
-/* Backward through time of st_lstm_seq_fwd: dout(b, t, dcol : dcol+H) -> dxproj (B,T,4H) (= gradient of the
- * input projection incl. both biases).  w_hh_t = W_hh^T (H, 4H).  ws: 2*B*H floats.  The caller finishes with
- * dW_hh = st_gemm_wgrad(dxproj, out shifted by one step) and db = st_colsum(dxproj). */
-int st_lstm_seq_bwd(const float* dout, int ldd, int dcol, const float* gates_tape, const float* c_tape,
-                    const float* w_hh_t, float* dxproj, float* ws, int B, int T, int H, int reverse, void* stream);
 /* nn.GRU, ndir directions in one launch (direction 1 runs time-reversed), one workgroup per
  * (utterance, direction) keeps W_hh rows in registers and h in LDS for all T steps.
  * gi[d] (B,T,3H) = x W_ih[d]^T + b_ih[d] (from st_gemm_fwd); out(b, t, d*H : (d+1)*H) = h_t.

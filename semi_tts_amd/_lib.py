@@ -101,6 +101,28 @@ class StDecoderBwdIO(C.Structure):
                  ('dpre_norm_w', C.c_void_p * 2), ('dpre_norm_b', C.c_void_p * 2), ('attn_parts', C.c_int), ('dloc_part', C.c_void_p),
                  ('dxd_part', C.c_void_p), ('dxd_splits', C.c_int), ('dxq_part', C.c_void_p), ('dxq_splits', C.c_int)])
 
+class StLstmSeqJob(C.Structure):
+    _fields_ = [('ndir', C.c_int), ('reverse', C.c_int), ('xproj', C.c_void_p * 2), ('w_hh', C.c_void_p * 2), ('b_hh', C.c_void_p * 2),
+                ('out', C.c_void_p), ('ldo', C.c_int), ('ocol', C.c_int * 2), ('gates_tape', C.c_void_p * 2), ('c_tape', C.c_void_p * 2),
+                ('B', C.c_int), ('T', C.c_int), ('H', C.c_int), ('ws', C.c_void_p), ('status', C.c_void_p),
+                ('allow_persist', C.c_int), ('cu_reserve', C.c_int)]
+
+
+class StLstmSeqBwdJob(C.Structure):
+    _fields_ = [('ndir', C.c_int), ('reverse', C.c_int), ('dout', C.c_void_p), ('ldd', C.c_int), ('dcol', C.c_int * 2),
+                ('gates_tape', C.c_void_p * 2), ('c_tape', C.c_void_p * 2), ('w', C.c_void_p * 2), ('weights', C.c_int),
+                ('dxproj', C.c_void_p * 2), ('B', C.c_int), ('T', C.c_int), ('H', C.c_int), ('ws', C.c_void_p), ('status', C.c_void_p),
+                ('allow_persist', C.c_int), ('cu_reserve', C.c_int)]
+
+
+class StLstmSeqQuery(C.Structure):
+    _fields_ = [('backward', C.c_int), ('ndir', C.c_int), ('B', C.c_int), ('T', C.c_int), ('H', C.c_int), ('ld', C.c_int),
+                ('col', C.c_int * 2), ('aligned', C.c_uint), ('allow_persist', C.c_int), ('cus', C.c_int), ('cu_reserve', C.c_int)]
+
+
+class StLstmSeqPlan(C.Structure):
+    _fields_ = [('form', C.c_int), ('weights', C.c_int), ('ws_floats', C.c_size_t)] + [
+        (n, C.c_int) for n in ('grid_x', 'grid_y', 'grid_z', 'block', 'rt', 'nkb', 'rg', 'xcd_map')]
 
 
 class StLstmPwJob(C.Structure):
@@ -263,9 +285,10 @@ SIGNATURES = {
     'st_bn_stats': [P, I, I, I, I, P, P, P, P, F, P, P, P],
     'st_colreduce_workspace_floats': [I, I],
     'st_bn_apply': [P, I, I, I, I, P, P, P, P, F, I, P],
-    'st_lstm_seq_fwd': [P, P, P, P, I, I, P, P, P, I, I, I, I, P],
+    'st_lstm_seq_variant': [C.POINTER(StLstmSeqQuery), C.POINTER(StLstmSeqPlan)],
+    'st_lstm_seq_fwd': [C.POINTER(StLstmSeqJob), P],
     'st_lstm_cell_bwd_pointwise': [P, I, P, I, P, I, P, P, P, P, I, P, I, P, P, I, C.POINTER(StT16View), I, I, P],
-    'st_lstm_seq_bwd': [P, I, I, P, P, P, P, P, I, I, I, I, P],
+    'st_lstm_seq_bwd': [C.POINTER(StLstmSeqBwdJob), P],
     'st_gru_seq_fwd': [P, P, P, P, P, P, P, I, P, I, I, I, I, P],
     'st_gru_seq_bwd': [P, I, P, I, P, P, P, P, P, P, P, I, I, I, I, P],
     'st_gru_seq_variant': [I, I],
@@ -348,14 +371,7 @@ SIGNATURES = {
     'st_skinny_partial_attn_bwd': [P, C.POINTER(StT16View), I, P, I, I, I, C.POINTER(StAttnBwdJob), P],
     'st_skinny_linear_packed_lstm_bwd_attn_hist_sum': [C.POINTER(StPackedProduct), C.POINTER(StLstmPwJob), C.POINTER(StAttnHistJob),
                                                        C.POINTER(StPartialSumJob), P],
-    'st_lstm_seq2_fwd': [C.POINTER(P), C.POINTER(P), C.POINTER(P), P, I, C.POINTER(I), P, C.POINTER(P), C.POINTER(P), I, I, I, P],
-    'st_lstm_seq2_persist_supported': [I, I, I, I, I, I],
-    'st_lstm_seq2_persist_fwd': [C.POINTER(P), C.POINTER(P), C.POINTER(P), P, I, C.POINTER(I), C.POINTER(P), C.POINTER(P), I, I, I, P, P],
-    'st_lstm_seq2_bwd_persist_supported': [I, I, I, I, I, I],
-    'st_lstm_seq2_bwd_persist': [P, I, C.POINTER(I), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), I, I, I, P, P],
-    'st_lstm_seq2_bwd': [P, I, C.POINTER(I), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), P, I, I, I, P],
     'st_skinny_linear_pair_fwd': [P, C.POINTER(P), I, I, I, P],
-    'st_lstm_seq2_bwd_packed': [P, I, C.POINTER(I), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), P, P, I, I, I, P],
     'st_skinny_linear_packed_lstm_bwd_pair_fwd': [C.POINTER(StPackedProduct), C.POINTER(StLstmPwJob), P],
     'st_lstm_cell_pair_fwd': [P, C.POINTER(P), C.POINTER(P), I, C.POINTER(P), I, C.POINTER(P), I, C.POINTER(P), I, C.POINTER(P), I, I, P],
     'st_attn_dmem': [P, P, P, I, I, I, I, P],

@@ -139,10 +139,9 @@ class CTC(nn.Module):
             g = lambda n, rev: getattr(self.rnn, '%s_l%d%s' % (n, layer, '_reverse' if rev else ''))
             if self.rnn_bid:
                 xp = [ops.gemm(x, g('weight_ih', rev), bias=g('bias_ih', rev)) for rev in (False, True)]
-                ops.lstm_seq2(xp[0], xp[1], g('weight_hh', False), g('weight_hh', True), g('bias_hh', False), g('bias_hh', True), out)
+                ops.lstm_layer(xp, (g('weight_hh', False), g('weight_hh', True)), (g('bias_hh', False), g('bias_hh', True)), out)
             else:
-                ops.lstm_seq(ops.gemm(x, g('weight_ih', False), bias=g('bias_ih', False)), g('weight_hh', False), g('bias_hh', False),
-                             out, 0, False)
+                ops.lstm_layer((ops.gemm(x, g('weight_ih', False), bias=g('bias_ih', False)),), (g('weight_hh', False),), (g('bias_hh', False),), out)
             x = out
             if layer == self.rnn_layers - 1 and self.layer_norm:
                 ln = self.norm_layer
@@ -178,7 +177,7 @@ class ASRPostnet(nn.Module):
             else:
                 out = torch.empty(B, T, 2 * H, device=x.device, dtype=torch.float32)
                 xp = [ops.gemm(x, g('weight_ih', rev), bias=g('bias_ih', rev)) for rev in (False, True)]
-                ops.lstm_seq2(xp[0], xp[1], g('weight_hh', False), g('weight_hh', True), g('bias_hh', False), g('bias_hh', True), out)
+                ops.lstm_layer(xp, (g('weight_hh', False), g('weight_hh', True)), (g('bias_hh', False), g('bias_hh', True)), out)
                 x = out
             if p > 0 or _masks is not None:   # nn.LSTM's inter-layer dropout after layer 0, self.dropout after layer 1
                 if _masks is not None:

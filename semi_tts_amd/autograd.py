@@ -801,75 +801,48 @@ def st_onehot_code(p, table, idx):
     return _StOnehotCodeFn.apply(p, table, idx)
 
 
-class _BiLstmFn(Function):
-    """Bidirectional nn.LSTM layer over precomputed input projections (lengths ignored, zero initial state).
+class _LstmLayerFn(Function):
+    """One nn.LSTM layer over precomputed input projections (lengths ignored, zero initial state), ndir = 1 (forward in time: the speech
+    encoder with `rnn_bid: False`, src/asr.py:35-37) or 2 directions.  Arguments: the ndir projections, then (w_hh, b_hh) per direction.
     ref: src/module.py:432-438,:458-460"""
 
     @staticmethod
-    def forward(ctx, xp_f, xp_b, w_hh_f, b_hh_f, w_hh_b, b_hh_b):
-        B, T, H4 = xp_f.shape
+    def forward(ctx, *args):
+        ndir = len(args) // 3
+        xps, w_hhs, b_hhs = args[:ndir], args[ndir::2], args[ndir + 1::2]
+        B, T, H4 = xps[0].shape
         H = H4 // 4
-        dev = xp_f.device
-        out = torch.empty(B, T, 2 * H, device=dev, dtype=torch.float32)
-        gs = [torch.empty(T, B, 4, H, device=dev, dtype=torch.float32) for _ in range(2)]
-        cs = [torch.empty(T, B, H, device=dev, dtype=torch.float32) for _ in range(2)]
-        ops.lstm_seq2(xp_f.contiguous(), xp_b.contiguous(), w_hh_f, w_hh_b, b_hh_f, b_hh_b, out, gs, cs)
-        ctx.save_for_backward(out, w_hh_f, w_hh_b, gs[0], cs[0], gs[1], cs[1], b_hh_f, b_hh_b)
+        dev = xps[0].device
+        out = torch.empty(B, T, ndir * H, device=dev, dtype=torch.float32)
+        gs = [torch.empty(T, B, 4, H, device=dev, dtype=torch.float32) for _ in range(ndir)]
+        cs = [torch.empty(T, B, H, device=dev, dtype=torch.float32) for _ in range(ndir)]
+        ops.lstm_layer([xp.contiguous() for xp in xps], w_hhs, b_hhs, out, gs, cs)
+        ctx.save_for_backward(out, *w_hhs, *b_hhs, *gs, *cs)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        out, w_hh_f, w_hh_b, g_f, c_f, g_b, c_b, b_hh_f, b_hh_b = ctx.saved_tensors
-        dout = dout.contiguous()
-        H = w_hh_f.shape[1]
-        res = []
-        if H % 16 == 0:     # packed operands: one launch per step for both directions (product + pointwise backward in its epilogue)
-            dxps = ops.lstm_seq2_bwd(dout, (g_f, g_b), (c_f, c_b), None, (w_hh_f, w_hh_b))
-        else:
-            dxps = ops.lstm_seq2_bwd(dout, (g_f, g_b), (c_f, c_b), (ops.dx_weight(w_hh_f.detach())[0], ops.dx_weight(w_hh_b.detach())[0]))
-        par = ((w_hh_f, b_hh_f), (w_hh_b, b_hh_b))
-        for d in range(2):
-            dxp = dxps[d]
+        out, *rest = ctx.saved_tensors
+        ndir = len(rest) // 4
+        w_hhs, b_hhs, gs, cs = (rest[i * ndir:(i + 1) * ndir] for i in range(4))
+        H = w_hhs[0].shape[1]
+        dxps = ops.lstm_layer_bwd(dout.contiguous(), gs, cs, w_hhs)
+        grads = []
+        for d in range(ndir):
+            par = (w_hhs[d], b_hhs[d])
             # h_{t-1} of the forward direction is out[t-1] (zero at t = 0): a 1-tap "conv" with pad +1 / -1
             # (the bias gradient = the column sums of dxp rides in the product's launches; the product itself may wait: ops.flush_wgrads)
-            dw, db = ops.gemm_wgrad(dxp, out[:, :, d * H:(d + 1) * H], 1, 1 if d == 0 else -1, out=ops.grad_slot((w_hh_f, w_hh_b)[d]),
-                                    with_db=True, db_out=ops.grad_slot((b_hh_f, b_hh_b)[d]), later=ops.grad_first(*par[d]), params=par[d])
-            res.append((dxp, dw, db))
-        return res[0][0], res[1][0], res[0][1], res[0][2], res[1][1], res[1][2]
+            grads += ops.gemm_wgrad(dxps[d], out[:, :, d * H:(d + 1) * H], 1, 1 if d == 0 else -1, out=ops.grad_slot(par[0]),
+                                    with_db=True, db_out=ops.grad_slot(par[1]), later=ops.grad_first(*par), params=par)
+        return (*dxps, *grads)
 
 
 def bilstm(xp_f, xp_b, w_hh_f, b_hh_f, w_hh_b, b_hh_b):
-    return _BiLstmFn.apply(xp_f, xp_b, w_hh_f, b_hh_f, w_hh_b, b_hh_b)
-
-
-class _LstmFn(Function):
-    """Unidirectional nn.LSTM layer (forward in time) over precomputed input projections, zero initial state: the speech encoder
-    with `rnn_bid: False` (src/asr.py:35-37).  One launch per time step (st_lstm_seq_fwd / st_lstm_seq_bwd)."""
-
-    @staticmethod
-    def forward(ctx, xp, w_hh, b_hh):
-        B, T, H4 = xp.shape
-        H = H4 // 4
-        dev = xp.device
-        out = torch.empty(B, T, H, device=dev, dtype=torch.float32)
-        g = torch.empty(T, B, 4, H, device=dev, dtype=torch.float32)
-        c = torch.empty(T, B, H, device=dev, dtype=torch.float32)
-        ops.lstm_seq(xp.contiguous(), w_hh, b_hh, out, 0, False, gates_tape=g, c_tape=c)
-        ctx.save_for_backward(out, w_hh, g, c, b_hh)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        out, w_hh, g, c, b_hh = ctx.saved_tensors
-        dxp = ops.lstm_seq_bwd(dout.contiguous(), 0, g, c, ops.dx_weight(w_hh.detach())[0], False)
-        # h_{t-1} is out[t-1] (zero at t = 0): a 1-tap "conv" with pad +1
-        dw, db = ops.gemm_wgrad(dxp, out, 1, 1, out=ops.grad_slot(w_hh), with_db=True, db_out=ops.grad_slot(b_hh),
-                                later=ops.grad_first(w_hh, b_hh), params=(w_hh, b_hh))
-        return dxp, dw, db
+    return _LstmLayerFn.apply(xp_f, xp_b, w_hh_f, b_hh_f, w_hh_b, b_hh_b)
 
 
 def lstm(xp, w_hh, b_hh):
-    return _LstmFn.apply(xp, w_hh, b_hh)
+    return _LstmLayerFn.apply(xp, w_hh, b_hh)
 
 
 class _BiGruFn(Function):

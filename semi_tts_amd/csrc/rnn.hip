@@ -802,88 +802,96 @@ extern "C" int st_gru_seq_fwd(const float* gi_fwd, const float* gi_bwd, const fl
     return 0;
 }
 
-extern "C" int st_lstm_seq_fwd(const float* xproj, const float* w_hh, const float* b_hh, float* out, int ldo, int ocol,
-                               float* ws, float* gates_tape, float* c_tape, int B, int T, int H, int reverse, void* stream) {
-    (void)hipGetLastError();  // drop stale errors left by other HIP users of this thread
-    ST_CHECK_ARG(xproj && w_hh && out && ws && B > 0 && T > 0 && H > 0, "st_lstm_seq_fwd: bad arguments");
-    ST_CHECK_ARG(ldo >= ocol + H, "st_lstm_seq_fwd: ldo=%d < ocol+H", ldo);
-    hipStream_t st = (hipStream_t)stream;
+// ---- nn.LSTM sequence layers: the only place a form is chosen -------------------------------------------------------------------------
+static int lstm_plan(const st_lstm_seq_query& q, st_lstm_seq_plan& p) {
+    const int B = q.B, H = q.H, ld = q.ld, c0 = q.col[0], c1 = q.col[1], rt = (B + 15) / 16;
+    if ((q.ndir != 1 && q.ndir != 2) || B <= 0 || q.T <= 0 || H <= 0 || q.cu_reserve < 0) return -1;
+    for (int d = 0; d < q.ndir; ++d)
+        if (q.col[d] < 0 || ld < q.col[d] + H) return -1;
     const size_t bh = (size_t)B * H;
-    float* cbuf[2] = {ws, ws + bh};
-    float* zero = ws + 2 * bh;
-    ST_HIP(hipMemsetAsync(zero, 0, bh * sizeof(float), st));
-    for (int s = 0; s < T; ++s) {
-        const int t = reverse ? T - 1 - s : s;
-        const int tp = reverse ? t + 1 : t - 1;
-        st_seg seg;
-        seg.w = w_hh; seg.ldw = H; seg.k = H;
-        if (s == 0) { seg.x = zero; seg.ldx = H; }
-        else { seg.x = out + (size_t)tp * ldo + ocol; seg.ldx = T * ldo; }
-        // training keeps every c_t and the activated gates (tapes indexed by t, not by processing order)
-        const float* cprev = s == 0 ? zero : (c_tape ? c_tape + (size_t)tp * bh : cbuf[(s - 1) & 1]);
-        float* cnew = c_tape ? c_tape + (size_t)t * bh : cbuf[s & 1];
-        int rc = st_lstm_cell_fwd(&seg, 1, nullptr, b_hh, xproj + (size_t)t * 4 * H, T * 4 * H,
-                                  cprev, H, nullptr, out + (size_t)t * ldo + ocol, T * ldo,
-                                  cnew, H, gates_tape ? gates_tape + (size_t)t * 4 * bh : nullptr, B, H, stream);
-        if (rc) return rc;
+    const unsigned al = q.backward ? 127u : 7u;      // every ST_LSTM_AL_* bit of the pass
+    // the one-launch forms: both directions, rows of 16-byte pieces, all workgroups resident at once beside the compute units kept free
+    const bool one = q.allow_persist && q.ndir == 2 && ld % 4 == 0 && c0 % 4 == 0 && c1 % 4 == 0 && (q.aligned & al) == al;
+    const int cus = !one ? 0 : q.cus > 0 ? q.cus : st_device_cus();
+    p = st_lstm_seq_plan{ST_LSTM_STEP, ST_LSTM_W_NATURAL};
+    if (!q.backward) {
+        // (tile, d) owns four hidden units: 2 * H/4 workgroups of four waves, wave w holds H/64 k-blocks; at most four row tiles
+        if (one && B <= 64 && (H == 64 || H == 128 || H == 256 || H == 512) && (c0 + H <= c1 || c1 + H <= c0) && 2 * (H / 4) <= cus - q.cu_reserve) {
+            p.form = ST_LSTM_PERSIST; p.grid_x = H / 4; p.grid_y = 2; p.grid_z = 1; p.block = 256;
+            p.rt = rt; p.nkb = H / 64; p.xcd_map = (H / 4) % 4 == 0;
+        } else p.ws_floats = (size_t)(2 * q.ndir + 1) * bh;       // two c buffers per direction, one block of zeros
+    } else if (one && (H == 32 || H == 64 || H == 128 || H == 256) && 2 * (H / 16) * rt <= cus - q.cu_reserve) {
+        // (tile, bg, d) owns 16 hidden units and rg batch rows: 2 * H/16 * ceil(B/rg) workgroups of eight waves, wave w holds H/32 k-blocks.
+        // Eight batch rows per workgroup while the workgroups fill at most half the device (the hand-off is bound by what a workgroup takes
+        // in per step: 220 -> 192 us per C2 layer; four rows -- every compute unit of the device -- gave 188 and leaves no room to be resident)
+        p.rg = 2 * (H / 16) * ((B + 7) / 8) <= cus / 2 ? 8 : 16;
+        p.form = ST_LSTM_PERSIST; p.grid_x = H / 16; p.grid_y = (B + p.rg - 1) / p.rg; p.grid_z = 2; p.block = 512;
+        p.rt = rt; p.nkb = H / 32;
+    } else if (q.ndir == 2 && H % 16 == 0) {      // packed operands: one launch per step (product + pointwise backward of the step before)
+        p.form = ST_LSTM_PACKED; p.weights = ST_LSTM_W_PACKED_T;
+        p.ws_floats = 2 * bh + 4 * st_t16_floats(B, 4 * H);      // dc carries, then two ping-pong T16 copies of dgates per direction
+    } else {
+        p.weights = ST_LSTM_W_T;
+        p.ws_floats = (size_t)(2 * q.ndir) * bh;      // per direction: the carried dL/dc, dL/dh_{t-1} through W_hh
     }
     return 0;
 }
 
-extern "C" int st_lstm_cell_pair_fwd(const st_seg* segs2, const float* const* b_hh2, const float* const* pre2, int ldpre,
-                                     const float* const* c_prev2, int ldc_prev, float* const* h_out2, int ldh,
-                                     float* const* c_out2, int ldc, float* const* gates_out2, int B, int H, void* stream);
+extern "C" int st_lstm_seq_variant(const st_lstm_seq_query* q, st_lstm_seq_plan* out) { return q && out ? lstm_plan(*q, *out) : -1; }
 
-// Both directions of a bidirectional LSTM layer, one launch per time step for the two of them (direction 0 walks t = s,
-// direction 1 walks t = T-1-s).  Arguments as st_lstm_seq_fwd, in arrays of two; ws: 6*B*H floats.
-extern "C" int st_lstm_seq2_fwd(const float* const* xproj2, const float* const* w_hh2, const float* const* b_hh2, float* out, int ldo,
-                                const int* ocol2, float* ws, float* const* gates_tape2, float* const* c_tape2,
-                                int B, int T, int H, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(xproj2 && w_hh2 && out && ws && ocol2 && xproj2[0] && xproj2[1] && w_hh2[0] && w_hh2[1] && B > 0 && T > 0 && H > 0,
-                 "st_lstm_seq2_fwd: bad arguments");
-    ST_CHECK_ARG(ldo >= ocol2[0] + H && ldo >= ocol2[1] + H, "st_lstm_seq2_fwd: ldo=%d too small", ldo);
-    hipStream_t st = (hipStream_t)stream;
+// Direction d of a layer at processing step s: its time step t and the time step tp processed before it (s > 0), and the slices of the
+// tensors there.  Tapes are indexed by time step: gates (T, B, 4, H), c (T, B, H); out, dout, xproj and dxproj are (B, T, ld) with
+// batch-row stride T * ld.
+struct LstmAt {
+    size_t t, tp, bh;
+    LstmAt(int ndir, int reverse, int d, int s, int T, size_t bh_) : bh(bh_) {
+        const bool rev = ndir == 2 ? d == 1 : reverse != 0;
+        t = rev ? T - 1 - s : s;
+        tp = rev ? t + 1 : t - 1;
+    }
+    template <typename F> F* gates(F* tape) const { return tape + t * 4 * bh; }
+    template <typename F> F* c(F* tape) const { return tape + t * bh; }
+    template <typename F> F* c_prev(F* tape) const { return tape + tp * bh; }
+    template <typename F> F* row(F* x, int ld, int col) const { return x + t * ld + col; }
+    template <typename F> F* row_prev(F* x, int ld, int col) const { return x + tp * ld + col; }
+};
+
+// One launch per time step: st_lstm_cell_fwd for one direction, st_lstm_cell_pair_fwd for the two (direction 0 at t = s, direction 1 at
+// t = T-1-s).  ws: per direction two c buffers (inference), then B*H zeros (h and c before the first step).
+static int lstm_fwd_steps(const st_lstm_seq_job& j, void* stream) {
+    const int B = j.B, T = j.T, H = j.H, ndir = j.ndir;
     const size_t bh = (size_t)B * H;
-    float* zero = ws + 4 * bh;
-    ST_HIP(hipMemsetAsync(zero, 0, bh * sizeof(float), st));
+    float* zero = j.ws + (size_t)(2 * ndir) * bh;
+    ST_HIP(hipMemsetAsync(zero, 0, bh * sizeof(float), (hipStream_t)stream));
     for (int s = 0; s < T; ++s) {
         st_seg seg[2];
-        const float *bh2[2], *pre[2], *cprev[2];
+        const float *pre[2], *cprev[2];
         float *hout[2], *cnew[2], *gout[2];
-        for (int d = 0; d < 2; ++d) {
-            const int t = d ? T - 1 - s : s, tp = d ? t + 1 : t - 1;
-            float* cbuf[2] = {ws + (size_t)(2 * d) * bh, ws + (size_t)(2 * d + 1) * bh};
-            float* ct = c_tape2 ? c_tape2[d] : nullptr;
-            float* gt = gates_tape2 ? gates_tape2[d] : nullptr;
-            seg[d].w = w_hh2[d]; seg[d].ldw = H; seg[d].k = H;
+        for (int d = 0; d < ndir; ++d) {
+            const LstmAt at(ndir, j.reverse, d, s, T, bh);
+            float* cbuf[2] = {j.ws + (size_t)(2 * d) * bh, j.ws + (size_t)(2 * d + 1) * bh};
+            float* ct = j.c_tape[d];      // training keeps every c_t and the activated gates
+            seg[d].w = j.w_hh[d]; seg[d].ldw = H; seg[d].k = H;
             if (s == 0) { seg[d].x = zero; seg[d].ldx = H; }
-            else { seg[d].x = out + (size_t)tp * ldo + ocol2[d]; seg[d].ldx = T * ldo; }
-            bh2[d] = b_hh2 ? b_hh2[d] : nullptr;
-            pre[d] = xproj2[d] + (size_t)t * 4 * H;
-            cprev[d] = s == 0 ? zero : (ct ? ct + (size_t)tp * bh : cbuf[(s - 1) & 1]);
-            cnew[d] = ct ? ct + (size_t)t * bh : cbuf[s & 1];
-            hout[d] = out + (size_t)t * ldo + ocol2[d];
-            gout[d] = gt ? gt + (size_t)t * 4 * bh : nullptr;
+            else { seg[d].x = at.row_prev(j.out, j.ldo, j.ocol[d]); seg[d].ldx = T * j.ldo; }
+            pre[d] = at.row(j.xproj[d], 4 * H, 0);
+            cprev[d] = s == 0 ? zero : (ct ? at.c_prev(ct) : cbuf[(s - 1) & 1]);
+            cnew[d] = ct ? at.c(ct) : cbuf[s & 1];
+            hout[d] = at.row(j.out, j.ldo, j.ocol[d]);
+            gout[d] = j.gates_tape[d] ? at.gates(j.gates_tape[d]) : nullptr;
         }
-        int rc = st_lstm_cell_pair_fwd(seg, bh2, pre, T * 4 * H, cprev, H, hout, T * ldo, cnew, H, gout, B, H, stream);
+        const int rc = ndir == 1 ? st_lstm_cell_fwd(seg, 1, nullptr, j.b_hh[0], pre[0], T * 4 * H, cprev[0], H, nullptr, hout[0], T * j.ldo,
+                                                    cnew[0], H, gout[0], B, H, stream)
+                                 : st_lstm_cell_pair_fwd(seg, j.b_hh, pre, T * 4 * H, cprev, H, hout, T * j.ldo, cnew, H, gout, B, H, stream);
         if (rc) return rc;
     }
     return 0;
-}
-
-// The whole bidirectional layer as ONE launch (lstm_seq2_persist_kernel): shapes it takes
-extern "C" int st_lstm_seq2_persist_supported(int B, int T, int H, int ldo, int ocol0, int ocol1) {
-    const int nkb = H / 64;
-    return B > 0 && B <= 64 && T > 0 && H > 0 && H % 64 == 0 && (nkb == 1 || nkb == 2 || nkb == 4 || nkb == 8) &&
-           ldo % 4 == 0 && ocol0 % 4 == 0 && ocol1 % 4 == 0 && ocol0 >= 0 && ocol1 >= 0 && ldo >= ocol0 + H && ldo >= ocol1 + H &&
-           (ocol0 + H <= ocol1 || ocol1 + H <= ocol0) && 2 * (H / 4) <= st_device_cus();
 }
 
 template <int RT>
-static void lp_launch(const LpArgs& a, hipStream_t st) {
-    const dim3 grid(a.H / 4, 2), block(256);
-    switch (a.H / 64) {
+static void lp_launch(const LpArgs& a, const st_lstm_seq_plan& p, hipStream_t st) {
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    switch (p.nkb) {
         case 1: hipLaunchKernelGGL((lstm_seq2_persist_kernel<RT, 1>), grid, block, 0, st, a); break;
         case 2: hipLaunchKernelGGL((lstm_seq2_persist_kernel<RT, 2>), grid, block, 0, st, a); break;
         case 4: hipLaunchKernelGGL((lstm_seq2_persist_kernel<RT, 4>), grid, block, 0, st, a); break;
@@ -891,34 +899,41 @@ static void lp_launch(const LpArgs& a, hipStream_t st) {
     }
 }
 
-extern "C" int st_lstm_seq2_persist_fwd(const float* const* xproj2, const float* const* w_hh2, const float* const* b_hh2, float* out, int ldo,
-                                        const int* ocol2, float* const* gates_tape2, float* const* c_tape2,
-                                        int B, int T, int H, unsigned* status, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(xproj2 && w_hh2 && out && ocol2 && xproj2[0] && xproj2[1] && w_hh2[0] && w_hh2[1], "st_lstm_seq2_persist_fwd: bad arguments");
-    ST_CHECK_ARG(st_lstm_seq2_persist_supported(B, T, H, ldo, ocol2[0], ocol2[1]),
-                 "st_lstm_seq2_persist_fwd: unsupported shape B=%d T=%d H=%d ldo=%d (see st_lstm_seq2_persist_supported)", B, T, H, ldo);
-    ST_CHECK_ARG(st_aligned16(out) && st_aligned16(w_hh2[0]) && st_aligned16(w_hh2[1]), "st_lstm_seq2_persist_fwd: out / w_hh must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
+// The whole bidirectional layer as ONE launch (lstm_seq2_persist_kernel), after the sentinel fill of the output columns
+static int lstm_fwd_persist(const st_lstm_seq_job& j, const st_lstm_seq_plan& p, hipStream_t st) {
     LpArgs a;
     for (int d = 0; d < 2; ++d) {
-        a.xproj[d] = xproj2[d]; a.w_hh[d] = w_hh2[d]; a.b_hh[d] = b_hh2 ? b_hh2[d] : nullptr; a.ocol[d] = ocol2[d];
-        a.gates_tape[d] = gates_tape2 ? gates_tape2[d] : nullptr; a.c_tape[d] = c_tape2 ? c_tape2[d] : nullptr;
+        a.xproj[d] = j.xproj[d]; a.w_hh[d] = j.w_hh[d]; a.b_hh[d] = j.b_hh[d]; a.ocol[d] = j.ocol[d];
+        a.gates_tape[d] = j.gates_tape[d]; a.c_tape[d] = j.c_tape[d];
     }
-    a.out = out; a.ldo = ldo; a.B = B; a.T = T; a.H = H; a.status = status;
-    a.xcd_map = (H / 4) % 4 == 0 ? 1 : 0;
-    const size_t pieces = (size_t)B * T * (H / 2);
+    a.out = j.out; a.ldo = j.ldo; a.B = j.B; a.T = j.T; a.H = j.H; a.status = j.status;
+    a.xcd_map = p.xcd_map;
+    const size_t pieces = (size_t)j.B * j.T * (j.H / 2);
     hipLaunchKernelGGL(lp_fill_kernel, dim3((unsigned)((pieces + 255) / 256 < 1024 ? (pieces + 255) / 256 : 1024)), dim3(256), 0, st,
-                       out, ldo, ocol2[0], ocol2[1], H, B * T);
+                       j.out, j.ldo, j.ocol[0], j.ocol[1], j.H, j.B * j.T);
     ST_LAUNCH_CHECK();
-    const int rt = (B + 15) / 16;
-    if (rt == 1) lp_launch<1>(a, st); else if (rt == 2) lp_launch<2>(a, st); else if (rt == 3) lp_launch<3>(a, st); else lp_launch<4>(a, st);
+    if (p.rt == 1) lp_launch<1>(a, p, st); else if (p.rt == 2) lp_launch<2>(a, p, st); else if (p.rt == 3) lp_launch<3>(a, p, st); else lp_launch<4>(a, p, st);
     ST_LAUNCH_CHECK();
     return 0;
 }
 
+extern "C" int st_lstm_seq_fwd(const st_lstm_seq_job* j, void* stream) {
+    (void)hipGetLastError();  // drop stale errors left by other HIP users of this thread
+    ST_CHECK_ARG(j && (j->ndir == 1 || (j->ndir == 2 && !j->reverse)) && j->out, "st_lstm_seq_fwd: bad arguments");
+    st_lstm_seq_query q = {0, j->ndir, j->B, j->T, j->H, j->ldo, {j->ocol[0], j->ocol[1]}, st_aligned16(j->out) ? ST_LSTM_AL_OUT : 0u,
+                           j->allow_persist, 0, j->cu_reserve};
+    for (int d = 0; d < j->ndir; ++d) {
+        ST_CHECK_ARG(j->xproj[d] && j->w_hh[d], "st_lstm_seq_fwd: direction %d: null xproj / w_hh", d);
+        if (st_aligned16(j->w_hh[d])) q.aligned |= ST_LSTM_AL_W0 << d;
+    }
+    st_lstm_seq_plan p;
+    ST_CHECK_ARG(lstm_plan(q, p) == 0, "st_lstm_seq_fwd: no form takes ndir=%d B=%d T=%d H=%d ldo=%d", j->ndir, j->B, j->T, j->H, j->ldo);
+    ST_CHECK_ARG(p.ws_floats == 0 || j->ws, "st_lstm_seq_fwd: ws is NULL (%zu floats needed)", p.ws_floats);
+    return p.form == ST_LSTM_PERSIST ? lstm_fwd_persist(*j, p, (hipStream_t)stream) : lstm_fwd_steps(*j, stream);
+}
+
 // ---- BPTT of both directions of a bidirectional LSTM layer, ALL time steps in ONE launch ----------------------------------------------------
-// The per-step form (st_lstm_seq2_bwd_packed) is one launch of ~7.4 us per step: dh_rec = dgates(t+1) . W_hh with the pointwise backward
+// The per-step form (ST_LSTM_PACKED of st_lstm_seq_bwd) is one launch of ~7.4 us per step: dh_rec = dgates(t+1) . W_hh with the pointwise backward
 // of step t in its epilogue.  Here the loop is one launch of (H/16) x ceil(B/RG) x 2 workgroups of eight waves, all resident at once.
 // Workgroup (tile, bg, d) owns 16 hidden units and RG = 8 or 16 batch rows of direction d: the 4H x 16 slice of W_hh it multiplies by stays in
 // REGISTERS (wave w holds the k-blocks w NKB .. w NKB + NKB - 1 of K = 4H), the carried dL/dc of its 16 x 16 cells stays in
@@ -1066,48 +1081,10 @@ __global__ __launch_bounds__(512) void lstm_seq2_bwd_persist_kernel(const LbArgs
 
 }  // namespace
 
-extern "C" int st_lstm_seq2_bwd_persist_supported(int B, int T, int H, int ldd, int dcol0, int dcol1) {
-    const int nkb = H / 32;
-    return B > 0 && T > 0 && H > 0 && H % 32 == 0 && (nkb == 1 || nkb == 2 || nkb == 4 || nkb == 8) && ldd % 4 == 0 && dcol0 % 4 == 0 &&
-           dcol1 % 4 == 0 && dcol0 >= 0 && dcol1 >= 0 && ldd >= dcol0 + H && ldd >= dcol1 + H && 2 * (H / 16) * ((B + 15) / 16) <= st_device_cus();
-}
-
-extern "C" int st_lstm_seq2_bwd_persist(const float* dout, int ldd, const int* dcol2, const float* const* gates_tape2, const float* const* c_tape2,
-                                        const float* const* w_hh2, float* const* dxproj2, int B, int T, int H, unsigned* status, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(dout && dcol2 && gates_tape2 && c_tape2 && w_hh2 && dxproj2 && gates_tape2[0] && gates_tape2[1] && c_tape2[0] && c_tape2[1] &&
-                 w_hh2[0] && w_hh2[1] && dxproj2[0] && dxproj2[1], "st_lstm_seq2_bwd_persist: bad arguments");
-    ST_CHECK_ARG(st_lstm_seq2_bwd_persist_supported(B, T, H, ldd, dcol2[0], dcol2[1]),
-                 "st_lstm_seq2_bwd_persist: unsupported shape B=%d T=%d H=%d ldd=%d (see st_lstm_seq2_bwd_persist_supported)", B, T, H, ldd);
-    ST_CHECK_ARG(st_aligned16(dout) && st_aligned16(gates_tape2[0]) && st_aligned16(gates_tape2[1]) && st_aligned16(c_tape2[0]) &&
-                 st_aligned16(c_tape2[1]) && st_aligned16(dxproj2[0]) && st_aligned16(dxproj2[1]), "st_lstm_seq2_bwd_persist: operands must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    LbArgs a;
-    for (int d = 0; d < 2; ++d) {
-        a.dcol[d] = dcol2[d]; a.gates_tape[d] = gates_tape2[d]; a.c_tape[d] = c_tape2[d]; a.w_hh[d] = w_hh2[d]; a.dxp[d] = dxproj2[d];
-    }
-    // every word = LP_SENTINEL (one fill when the two tensors lie back to back: ops.lstm_seq2_bwd allocates them so)
-    const size_t words = (size_t)B * T * 4 * H;
-    if (dxproj2[1] == dxproj2[0] + words) ST_HIP(hipMemsetAsync(dxproj2[0], 0xFF, 2 * words * sizeof(float), st));
-    else {
-        ST_HIP(hipMemsetAsync(dxproj2[0], 0xFF, words * sizeof(float), st));
-        ST_HIP(hipMemsetAsync(dxproj2[1], 0xFF, words * sizeof(float), st));
-    }
-    a.dout = dout; a.ldd = ldd; a.B = B; a.T = T; a.H = H; a.status = status;
-    // eight batch rows per workgroup while the workgroups fill at most half the device (the hand-off is bound by what a workgroup takes in
-    // per step: 220 -> 192 us per C2 layer; four rows -- every compute unit of the device -- gave 188 and leaves no room to be resident)
-    const int rg = 2 * (H / 16) * ((B + 7) / 8) <= st_device_cus() / 2 ? 8 : 16;
-    const dim3 grid(H / 16, (B + rg - 1) / rg, 2), block(512);
-#define LB_LAUNCH(NKB_) do { \
-        if (rg == 8) hipLaunchKernelGGL((lstm_seq2_bwd_persist_kernel<NKB_, 8>), grid, block, 0, st, a); \
-        else hipLaunchKernelGGL((lstm_seq2_bwd_persist_kernel<NKB_, 16>), grid, block, 0, st, a); } while (0)
-    switch (H / 32) {
-        case 1: LB_LAUNCH(1); break;
-        case 2: LB_LAUNCH(2); break;
-        case 4: LB_LAUNCH(4); break;
-        default: LB_LAUNCH(8); break;
-    }
-#undef LB_LAUNCH
+static int lstm_bwd_pw_launch(const LstmPwArgs* a, int ndir, hipStream_t st) {
+    const int blocks = (a[0].B * a[0].H + 255) / 256;
+    if (ndir == 1) hipLaunchKernelGGL(lstm_bwd_pw_kernel, dim3(blocks), dim3(256), 0, st, a[0]);
+    else hipLaunchKernelGGL(lstm_bwd_pw_pair_kernel, dim3(blocks, 2), dim3(256), 0, st, a[0], a[1]);
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -1124,125 +1101,137 @@ extern "C" int st_lstm_cell_bwd_pointwise(const float* dh0, int ld0, const float
     a.dg_t16 = dgates_t16 ? dgates_t16->base : nullptr;
     a.t16_kbs = dgates_t16 ? dgates_t16->kb_stride : 0; a.t16_kb0 = dgates_t16 ? dgates_t16->kb0 : 0;
     a.B = B; a.H = H;
-    const int blocks = (B * H + 255) / 256;
-    hipLaunchKernelGGL(lstm_bwd_pw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    ST_LAUNCH_CHECK();
-    return 0;
+    return lstm_bwd_pw_launch(&a, 1, (hipStream_t)stream);
 }
 
-extern "C" int st_lstm_seq_bwd(const float* dout, int ldd, int dcol, const float* gates_tape, const float* c_tape,
-                               const float* w_hh_t, float* dxproj, float* ws, int B, int T, int H, int reverse, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(dout && gates_tape && c_tape && w_hh_t && dxproj && ws && B > 0 && T > 0 && H > 0, "st_lstm_seq_bwd: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bh = (size_t)B * H;
-    float* dc = ws;            // carried dL/dc
-    float* dhrec = ws + bh;    // dL/dh_{t-1} through W_hh
-    ST_HIP(hipMemsetAsync(ws, 0, 2 * bh * sizeof(float), st));
-    for (int s = T - 1; s >= 0; --s) {                  // s = processing index of the forward
-        const int t = reverse ? T - 1 - s : s;
-        const int tp = reverse ? t + 1 : t - 1;
-        float* dg = dxproj + (size_t)t * 4 * H;          // row stride T*4H
-        int rc = st_lstm_cell_bwd_pointwise(dout + (size_t)t * ldd + dcol, T * ldd, dhrec, H, nullptr, 0, nullptr, nullptr,
-                                            gates_tape + (size_t)t * 4 * bh, c_tape + (size_t)t * bh, H,
-                                            s == 0 ? nullptr : c_tape + (size_t)tp * bh, H, dc, dg, T * 4 * H, nullptr, B, H, stream);
-        if (rc) return rc;
-        if (s == 0) break;
-        st_seg seg;
-        seg.x = dg; seg.ldx = T * 4 * H; seg.w = w_hh_t; seg.ldw = 4 * H; seg.k = 4 * H;
-        rc = st_skinny_linear_fwd(&seg, 1, nullptr, ST_ACT_NONE, nullptr, 0, dhrec, H, 0, nullptr, 0, 0, B, H, stream);
-        if (rc) return rc;
-    }
-    return 0;
+// the pointwise backward of direction d at processing step s: dout(:, t) and the tapes in, dxproj(:, t) out, dc carried
+static LstmPwArgs lstm_bwd_pw_args(const st_lstm_seq_bwd_job& j, int d, int s, float* dc) {
+    const LstmAt at(j.ndir, j.reverse, d, s, j.T, (size_t)j.B * j.H);
+    LstmPwArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dh0 = at.row(j.dout, j.ldd, j.dcol[d]); a.ld0 = j.T * j.ldd;
+    a.gates = at.gates(j.gates_tape[d]); a.c = at.c(j.c_tape[d]); a.ldc = j.H;
+    a.c_prev = s == 0 ? nullptr : at.c_prev(j.c_tape[d]); a.ldcp = j.H;
+    a.dc = dc; a.dgates = at.row(j.dxproj[d], 4 * j.H, 0); a.ldg = j.T * 4 * j.H; a.B = j.B; a.H = j.H;
+    return a;
 }
 
-extern "C" int st_skinny_linear_pair_fwd(const st_seg* segs2, float* const* y2, int ldy, int B, int N, void* stream);
-
-// Backward through time of both directions of a bidirectional LSTM layer: per time step ONE pointwise launch and ONE W_hh^T
-// launch serve the two directions (st_lstm_seq_bwd: two launches per step and direction).  ws: 4*B*H floats.
-extern "C" int st_lstm_seq2_bwd(const float* dout, int ldd, const int* dcol2, const float* const* gates_tape2, const float* const* c_tape2,
-                                const float* const* w_hh_t2, float* const* dxproj2, float* ws, int B, int T, int H, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(dout && dcol2 && gates_tape2 && c_tape2 && w_hh_t2 && dxproj2 && ws && B > 0 && T > 0 && H > 0, "st_lstm_seq2_bwd: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
+// Backward through time, per time step ONE pointwise launch and ONE W_hh^T launch for the one direction or the two.
+// ws: per direction the carried dL/dc, then dL/dh_{t-1} through W_hh.
+static int lstm_bwd_steps(const st_lstm_seq_bwd_job& j, void* stream) {
+    const int B = j.B, T = j.T, H = j.H, ndir = j.ndir;
     const size_t bh = (size_t)B * H;
-    ST_HIP(hipMemsetAsync(ws, 0, 4 * bh * sizeof(float), st));
-    const int blocks = (B * H + 255) / 256;
+    hipStream_t st = (hipStream_t)stream;
+    ST_HIP(hipMemsetAsync(j.ws, 0, (size_t)(2 * ndir) * bh * sizeof(float), st));
     for (int s = T - 1; s >= 0; --s) {                  // s = processing index of the forward
         LstmPwArgs a[2];
         st_seg seg[2];
-        float* dh2[2];
-        for (int d = 0; d < 2; ++d) {
-            const int t = d ? T - 1 - s : s, tp = d ? t + 1 : t - 1;
-            float* dc = ws + (size_t)(2 * d) * bh;
-            float* dhrec = ws + (size_t)(2 * d + 1) * bh;
-            float* dg = dxproj2[d] + (size_t)t * 4 * H;          // row stride T*4H
-            memset(&a[d], 0, sizeof(LstmPwArgs));
-            a[d].dh0 = dout + (size_t)t * ldd + dcol2[d]; a[d].ld0 = T * ldd; a[d].dh1 = dhrec; a[d].ld1 = H;
-            a[d].gates = gates_tape2[d] + (size_t)t * 4 * bh; a[d].c = c_tape2[d] + (size_t)t * bh; a[d].ldc = H;
-            a[d].c_prev = s == 0 ? nullptr : c_tape2[d] + (size_t)tp * bh; a[d].ldcp = H;
-            a[d].dc = dc; a[d].dgates = dg; a[d].ldg = T * 4 * H; a[d].B = B; a[d].H = H;
-            seg[d].x = dg; seg[d].ldx = T * 4 * H; seg[d].w = w_hh_t2[d]; seg[d].ldw = 4 * H; seg[d].k = 4 * H;
-            dh2[d] = dhrec;
+        float* dhrec[2];
+        for (int d = 0; d < ndir; ++d) {
+            dhrec[d] = j.ws + (size_t)(2 * d + 1) * bh;
+            a[d] = lstm_bwd_pw_args(j, d, s, j.ws + (size_t)(2 * d) * bh);
+            a[d].dh1 = dhrec[d]; a[d].ld1 = H;
+            seg[d].x = a[d].dgates; seg[d].ldx = T * 4 * H; seg[d].w = j.w[d]; seg[d].ldw = 4 * H; seg[d].k = 4 * H;
         }
-        hipLaunchKernelGGL(lstm_bwd_pw_pair_kernel, dim3(blocks, 2), dim3(256), 0, st, a[0], a[1]);
-        ST_LAUNCH_CHECK();
+        int rc = lstm_bwd_pw_launch(a, ndir, st);
+        if (rc) return rc;
         if (s == 0) break;
-        int rc = st_skinny_linear_pair_fwd(seg, dh2, H, B, H, stream);
+        rc = ndir == 1 ? st_skinny_linear_fwd(seg, 1, nullptr, ST_ACT_NONE, nullptr, 0, dhrec[0], H, 0, nullptr, 0, 0, B, H, stream)
+                       : st_skinny_linear_pair_fwd(seg, dhrec, H, B, H, stream);
         if (rc) return rc;
     }
     return 0;
 }
 
-extern "C" int st_lstm_seq2_bwd_packed(const float* dout, int ldd, const int* dcol2, const float* const* gates_tape2, const float* const* c_tape2,
-                                       const float* const* w_hh_t_p16_2, float* const* dxproj2, float* ws, float* dg_t16_ws,
-                                       int B, int T, int H, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(dout && dcol2 && gates_tape2 && c_tape2 && w_hh_t_p16_2 && dxproj2 && ws && dg_t16_ws && B > 0 && T > 0 && H > 0 && H % 16 == 0,
-                 "st_lstm_seq2_bwd_packed: bad arguments (H must be a multiple of 16)");
+// The same loop on packed operands: ONE launch per time step for the two directions -- dgates(s) . W_hh with the pointwise backward of
+// step s-1 in its epilogue (st_skinny_linear_packed_lstm_bwd_pair_fwd).  w: st_pack_weight_t of each direction's W_hh (N = H, K = 4H).
+// ws: the dc carries (2*B*H), then two ping-pong T16 copies of dgates per direction.
+static int lstm_bwd_packed(const st_lstm_seq_bwd_job& j, void* stream) {
+    const int B = j.B, T = j.T, H = j.H;
+    ST_CHECK_ARG(st_aligned16(j.ws), "st_lstm_seq_bwd: ws must be 16-byte aligned");      // (H % 16 == 0 keeps the T16 part aligned then)
     hipStream_t st = (hipStream_t)stream;
     const size_t bh = (size_t)B * H;
     const size_t t16 = st_t16_floats(B, 4 * H);
     const int kbs = (4 * H + 15) >> 4;
-    ST_HIP(hipMemsetAsync(ws, 0, 2 * bh * sizeof(float), st));
-    ST_HIP(hipMemsetAsync(dg_t16_ws, 0, 4 * t16 * sizeof(float), st));       // (rows past B of the tiles stay zero)
-    auto buf = [&](int d, int par) { return dg_t16_ws + (size_t)(2 * d + par) * t16; };
-    const int blocks = (B * H + 255) / 256;
+    float* t16_ws = j.ws + 2 * bh;
+    ST_HIP(hipMemsetAsync(j.ws, 0, 2 * bh * sizeof(float), st));
+    ST_HIP(hipMemsetAsync(t16_ws, 0, 4 * t16 * sizeof(float), st));       // (rows past B of the tiles stay zero)
+    auto buf = [&](int d, int par) { return st_t16_view{t16_ws + (size_t)(2 * d + par) * t16, kbs, 0}; };
     {   // the last processed step: nothing recurrent arrives yet
         const int s = T - 1;
         LstmPwArgs a[2];
         for (int d = 0; d < 2; ++d) {
-            const int t = d ? T - 1 - s : s, tp = d ? t + 1 : t - 1;
-            memset(&a[d], 0, sizeof(LstmPwArgs));
-            a[d].dh0 = dout + (size_t)t * ldd + dcol2[d]; a[d].ld0 = T * ldd;
-            a[d].gates = gates_tape2[d] + (size_t)t * 4 * bh; a[d].c = c_tape2[d] + (size_t)t * bh; a[d].ldc = H;
-            a[d].c_prev = s == 0 ? nullptr : c_tape2[d] + (size_t)tp * bh; a[d].ldcp = H;
-            a[d].dc = ws + (size_t)d * bh; a[d].dgates = dxproj2[d] + (size_t)t * 4 * H; a[d].ldg = T * 4 * H;
-            a[d].dg_t16 = buf(d, s & 1); a[d].t16_kbs = kbs; a[d].t16_kb0 = 0;
-            a[d].B = B; a[d].H = H;
+            a[d] = lstm_bwd_pw_args(j, d, s, j.ws + (size_t)d * bh);
+            a[d].dg_t16 = buf(d, s & 1).base; a[d].t16_kbs = kbs; a[d].t16_kb0 = 0;
         }
-        hipLaunchKernelGGL(lstm_bwd_pw_pair_kernel, dim3(blocks, 2), dim3(256), 0, st, a[0], a[1]);
-        ST_LAUNCH_CHECK();
+        const int rc = lstm_bwd_pw_launch(a, 2, st);
+        if (rc) return rc;
     }
-    for (int s = T - 1; s >= 1; --s) {        // dh_rec(s-1) = dgates(s) . W_hh, and the pointwise backward of step s-1 in the epilogue
+    for (int s = T - 2; s >= 0; --s) {        // dh_rec(s) = dgates(s+1) . W_hh, and the pointwise backward of step s in the epilogue
         st_packed_product prod[2];      // dh_rec = dgates W_hh^T, consumed by the epilogue only (no y)
         st_lstm_pw_job job[2];
         for (int d = 0; d < 2; ++d) {
-            const int s1 = s - 1;
-            const int t = d ? T - 1 - s1 : s1, tp = d ? t + 1 : t - 1;
-            prod[d] = st_packed_product{w_hh_t_p16_2[d], st_t16_view{buf(d, s & 1), kbs, 0}, 4 * H, nullptr, H, B, H};
+            const LstmAt at(2, 0, d, s, T, bh);
+            prod[d] = st_packed_product{j.w[d], buf(d, (s + 1) & 1), 4 * H, nullptr, H, B, H};
             memset(&job[d], 0, sizeof(st_lstm_pw_job));
             job[d].n0 = 0; job[d].H = H;
-            job[d].dh1 = dout + (size_t)t * ldd + dcol2[d]; job[d].ld1 = T * ldd;
-            job[d].gates = gates_tape2[d] + (size_t)t * 4 * bh; job[d].c = c_tape2[d] + (size_t)t * bh; job[d].ldc = H;
-            job[d].c_prev = s1 == 0 ? nullptr : c_tape2[d] + (size_t)tp * bh; job[d].ldcp = H;
-            job[d].dc = ws + (size_t)d * bh; job[d].dgates = dxproj2[d] + (size_t)t * 4 * H; job[d].ldg = T * 4 * H;
-            job[d].dgates_t16.base = buf(d, s1 & 1); job[d].dgates_t16.kb_stride = kbs; job[d].dgates_t16.kb0 = 0;
+            job[d].dh1 = at.row(j.dout, j.ldd, j.dcol[d]); job[d].ld1 = T * j.ldd;
+            job[d].gates = at.gates(j.gates_tape[d]); job[d].c = at.c(j.c_tape[d]); job[d].ldc = H;
+            job[d].c_prev = s == 0 ? nullptr : at.c_prev(j.c_tape[d]); job[d].ldcp = H;
+            job[d].dc = j.ws + (size_t)d * bh; job[d].dgates = at.row(j.dxproj[d], 4 * H, 0); job[d].ldg = T * 4 * H;
+            job[d].dgates_t16 = buf(d, s & 1);
         }
         int rc = st_skinny_linear_packed_lstm_bwd_pair_fwd(prod, job, stream);
         if (rc) return rc;
     }
     return 0;
+}
+
+// The whole loop of both directions as ONE launch (lstm_seq2_bwd_persist_kernel), after the sentinel fill of dxproj
+static int lstm_bwd_persist(const st_lstm_seq_bwd_job& j, const st_lstm_seq_plan& p, hipStream_t st) {
+    LbArgs a;
+    for (int d = 0; d < 2; ++d) {
+        a.dcol[d] = j.dcol[d]; a.gates_tape[d] = j.gates_tape[d]; a.c_tape[d] = j.c_tape[d]; a.w_hh[d] = j.w[d]; a.dxp[d] = j.dxproj[d];
+    }
+    a.dout = j.dout; a.ldd = j.ldd; a.B = j.B; a.T = j.T; a.H = j.H; a.status = j.status;
+    // every word = LP_SENTINEL (one fill when the two tensors lie back to back: ops.lstm_layer_bwd allocates them so)
+    const size_t words = (size_t)j.B * j.T * 4 * j.H;
+    if (j.dxproj[1] == j.dxproj[0] + words) ST_HIP(hipMemsetAsync(j.dxproj[0], 0xFF, 2 * words * sizeof(float), st));
+    else {
+        ST_HIP(hipMemsetAsync(j.dxproj[0], 0xFF, words * sizeof(float), st));
+        ST_HIP(hipMemsetAsync(j.dxproj[1], 0xFF, words * sizeof(float), st));
+    }
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.block);
+#define LB_LAUNCH(NKB_) do { \
+        if (p.rg == 8) hipLaunchKernelGGL((lstm_seq2_bwd_persist_kernel<NKB_, 8>), grid, block, 0, st, a); \
+        else hipLaunchKernelGGL((lstm_seq2_bwd_persist_kernel<NKB_, 16>), grid, block, 0, st, a); } while (0)
+    switch (p.nkb) {
+        case 1: LB_LAUNCH(1); break;
+        case 2: LB_LAUNCH(2); break;
+        case 4: LB_LAUNCH(4); break;
+        default: LB_LAUNCH(8); break;
+    }
+#undef LB_LAUNCH
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_lstm_seq_bwd(const st_lstm_seq_bwd_job* j, void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(j && (j->ndir == 1 || (j->ndir == 2 && !j->reverse)) && j->dout, "st_lstm_seq_bwd: bad arguments");
+    st_lstm_seq_query q = {1, j->ndir, j->B, j->T, j->H, j->ldd, {j->dcol[0], j->dcol[1]}, st_aligned16(j->dout) ? ST_LSTM_AL_DOUT : 0u,
+                           j->allow_persist, 0, j->cu_reserve};
+    for (int d = 0; d < j->ndir; ++d) {
+        ST_CHECK_ARG(j->gates_tape[d] && j->c_tape[d] && j->w[d] && j->dxproj[d], "st_lstm_seq_bwd: direction %d: null tape / w / dxproj", d);
+        q.aligned |= (st_aligned16(j->gates_tape[d]) ? ST_LSTM_AL_GATES0 << d : 0u) | (st_aligned16(j->c_tape[d]) ? ST_LSTM_AL_C0 << d : 0u) |
+                     (st_aligned16(j->dxproj[d]) ? ST_LSTM_AL_DX0 << d : 0u);
+    }
+    st_lstm_seq_plan p;
+    ST_CHECK_ARG(lstm_plan(q, p) == 0, "st_lstm_seq_bwd: no form takes ndir=%d B=%d T=%d H=%d ldd=%d", j->ndir, j->B, j->T, j->H, j->ldd);
+    ST_CHECK_ARG(j->weights == p.weights, "st_lstm_seq_bwd: w holds layout %d, the plan names %d (see st_lstm_seq_variant)", j->weights, p.weights);
+    ST_CHECK_ARG(p.ws_floats == 0 || j->ws, "st_lstm_seq_bwd: ws is NULL (%zu floats needed)", p.ws_floats);
+    if (p.form == ST_LSTM_PERSIST) return lstm_bwd_persist(*j, p, (hipStream_t)stream);
+    return p.form == ST_LSTM_PACKED ? lstm_bwd_packed(*j, stream) : lstm_bwd_steps(*j, stream);
 }
 
 extern "C" int st_gru_seq_bwd(const float* dout, int ldd, const float* out, int ldo, const float* tape,

@@ -302,7 +302,6 @@ extern "C" int st_lstm_cell_pair_fwd(const st_seg* segs2, const float* const* b_
     (void)hipGetLastError();
     ST_CHECK_ARG(B > 0 && H > 0 && H % 4 == 0 && segs2 && h_out2 && c_out2, "st_lstm_cell_pair_fwd: bad arguments");
     SkArgs a[2];
-    bool vec = true;
     for (int j = 0; j < 2; ++j) {
         memset(&a[j], 0, sizeof(SkArgs));
         int rc = sk_fill_segs(a[j], segs2 + j, 1);
@@ -313,10 +312,7 @@ extern "C" int st_lstm_cell_pair_fwd(const st_seg* segs2, const float* const* b_
         a[j].c_prev = c_prev2 ? c_prev2[j] : nullptr; a[j].ldc_prev = ldc_prev;
         a[j].h_out = h_out2[j]; a[j].ldh = ldh; a[j].c_out = c_out2[j]; a[j].ldc = ldc;
         a[j].gates_out = gates_out2 ? gates_out2[j] : nullptr;
-        const st_seg& g = a[j].seg[0];
-        vec = vec && st_aligned16(g.x) && st_aligned16(g.w) && (g.ldx % 4 == 0) && (g.ldw % 4 == 0) && (g.k % 4 == 0);
     }
-    (void)vec;
     return sk_dispatch_pair<0>(a, H / 4, (hipStream_t)stream);
 }
 

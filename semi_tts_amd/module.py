@@ -203,7 +203,7 @@ class Encoder(nn.Module):
             ops.gemm_flush(jobs)
             # the two directions advance together: the whole layer as ONE launch where the shape allows (H % 64 == 0: every shipped
             # config), else one launch per time step for both
-            ops.lstm_seq2(xp_f, xp_b, g('weight_hh'), g('weight_hh', True), g('bias_hh'), g('bias_hh', True), out)
+            ops.lstm_layer((xp_f, xp_b), (g('weight_hh'), g('weight_hh', True)), (g('bias_hh'), g('bias_hh', True)), out)
             x = out
         return x
 

@@ -615,17 +615,7 @@ def bn_apply(x2d, coff, N, mean, var, w, b, eps, act=None):
                           float(eps), ACT[act], stream_handle()), 'st_bn_apply')
 
 
-def lstm_seq(xproj, w_hh, b_hh, out, ocol, reverse, ws=None, gates_tape=None, c_tape=None):
-    lib = _lib.load()
-    B, T, H4 = xproj.shape
-    H = H4 // 4
-    if ws is None:
-        ws = torch.empty(3 * B * H, device=xproj.device, dtype=torch.float32)
-    check(lib.st_lstm_seq_fwd(_p(xproj), _p(w_hh), _p(b_hh), _p(out), int(out.stride(1)), int(ocol), _p(ws),
-                              _p(gates_tape), _p(c_tape), B, T, H, 1 if reverse else 0, stream_handle()), 'st_lstm_seq_fwd')
-
-
-LSTM_PERSIST = True      # bidirectional LSTM layers as one launch for all steps where the shape allows (st_lstm_seq2_persist_fwd)
+LSTM_PERSIST = True      # bidirectional LSTM layers as one launch for all steps where st_lstm_seq_variant takes the shape (the jobs' allow_persist)
 _PERSIST_STATUS = {}
 
 
@@ -670,96 +660,97 @@ def check_persist_status(device=None):
                                'as one launch per time step.' % v)
 
 
-def lstm_seq2(xproj_f, xproj_b, w_hh_f, w_hh_b, b_hh_f, b_hh_b, out, gates_tapes=None, c_tapes=None):
-    """both directions of a bidirectional LSTM layer; out (B,T,2H): forward direction in columns [0,H), reverse in [H,2H).
-    One launch for the whole layer where st_lstm_seq2_persist_supported takes the shape, else one launch per time step."""
-    lib = _lib.load()
-    B, T, H4 = xproj_f.shape
-    H = H4 // 4
-    P2 = C.c_void_p * 2
-    arr = lambda a, b_: P2(_p(a), _p(b_))
-    g2 = arr(*gates_tapes) if gates_tapes is not None else None
-    c2 = arr(*c_tapes) if c_tapes is not None else None
-    if LSTM_PERSIST and out.stride(2) == 1 and out.stride(0) == T * out.stride(1) and \
-            all(t.data_ptr() % 16 == 0 for t in (out, w_hh_f, w_hh_b)) and w_hh_f.is_contiguous() and w_hh_b.is_contiguous() and \
-            lib.st_lstm_seq2_persist_supported(B, T, H, int(out.stride(1)), 0, H):
+LSTM_STEP, LSTM_PACKED, LSTM_ONE_LAUNCH = 0, 1, 2        # ST_LSTM_STEP / _PACKED / _PERSIST of include/semitts.h
+LSTM_W_NATURAL, LSTM_W_T, LSTM_W_PACKED_T = 0, 1, 2      # ST_LSTM_W_*
+
+
+def lstm_plan(backward, ndir, x, cols, H, aligned_ops, cu_reserve=0):
+    """st_lstm_seq_variant for the (B, T, >= cols[d] + H) output (forward) or output gradient (backward) x: the form the layer takes, the
+    weight layout and workspace it needs.  aligned_ops: the operands of the ST_LSTM_AL_* bits, in bit order."""
+    B, T = x.shape[:2]
+    if x.stride(2) != 1 or x.stride(0) != T * x.stride(1):
+        raise ValueError('semi_tts_amd: LSTM layer: a (B, T, ld) tensor with strides (T * ld, ld, 1) is needed, got %s' % (tuple(x.stride()),))
+    q = _lib.StLstmSeqQuery(int(bool(backward)), ndir, B, T, H, int(x.stride(1)), (C.c_int * 2)(*cols),
+                            sum(1 << i for i, t in enumerate(aligned_ops) if t.data_ptr() % 16 == 0), 1 if LSTM_PERSIST else 0, 0, cu_reserve)
+    plan = _lib.StLstmSeqPlan()
+    if _lib.load().st_lstm_seq_variant(C.byref(q), C.byref(plan)):
+        raise ValueError('semi_tts_amd: no LSTM layer form takes ndir=%d B=%d T=%d H=%d ld=%d cols=%s' % (ndir, B, T, H, x.stride(1), tuple(cols)))
+    return plan
+
+
+def _lstm_weights(w_hhs):
+    if not all(w.is_contiguous() for w in w_hhs):
+        raise ValueError('semi_tts_amd: LSTM layer: the recurrent weights must be contiguous')
+    return [w.detach() for w in w_hhs]
+
+
+def _lstm_run(entry, j, plan, device):
+    if plan.form == LSTM_ONE_LAUNCH:
         join_side()               # (its workgroups wait for each other inside the launch: nothing else may hold compute units meanwhile)
-        # all T steps in one launch (recurrent weights in registers, h handed over through `out` itself)
-        check(lib.st_lstm_seq2_persist_fwd(arr(xproj_f, xproj_b), arr(w_hh_f, w_hh_b), arr(b_hh_f, b_hh_b), _p(out), int(out.stride(1)),
-                                           (C.c_int * 2)(0, H), g2, c2, B, T, H, _p(persist_status(out.device), torch.int32), stream_handle()),
-              'st_lstm_seq2_persist_fwd')
-        return
-    ws = torch.empty(6 * B * H, device=xproj_f.device, dtype=torch.float32)
-    check(lib.st_lstm_seq2_fwd(arr(xproj_f, xproj_b), arr(w_hh_f, w_hh_b), arr(b_hh_f, b_hh_b), _p(out), int(out.stride(1)),
-                               (C.c_int * 2)(0, H), _p(ws), g2, c2, B, T, H, stream_handle()), 'st_lstm_seq2_fwd')
+        j.status = _p(persist_status(device), torch.int32)
+    ws = torch.empty(plan.ws_floats, device=device, dtype=torch.float32) if plan.ws_floats else None
+    j.ws = _p(ws)
+    check(getattr(_lib.load(), entry)(C.byref(j), stream_handle()), entry)
 
 
-def lstm_seq_bwd(dout, dcol, gates_tape, c_tape, w_hh_t, reverse):
-    """dout (B,T,>=dcol+H) -> dxproj (B,T,4H)"""
-    T, B, _, H = gates_tape.shape
-    dxproj = torch.empty(B, T, 4 * H, device=dout.device, dtype=torch.float32)
-    ws = torch.empty(2 * B * H, device=dout.device, dtype=torch.float32)
-    check(_lib.load().st_lstm_seq_bwd(_p(dout), int(dout.stride(1)), int(dcol), _p(gates_tape), _p(c_tape), _p(w_hh_t),
-                                      _p(dxproj), _p(ws), B, T, H, 1 if reverse else 0, stream_handle()), 'st_lstm_seq_bwd')
-    return dxproj
+def lstm_layer(xprojs, w_hhs, b_hhs, out, gates_tapes=None, c_tapes=None, reverse=False, ocols=None):
+    """One nn.LSTM layer over its input projections xprojs[d] (B,T,4H), ndir = len(xprojs) directions: out(:, :, ocols[d] : ocols[d]+H) =
+    h of direction d (default: direction d in columns [d H, (d+1) H)).  One direction walks forward in time, or backward with `reverse`;
+    of two, the second walks backward.  One launch for the whole layer where st_lstm_seq_variant says so, else one launch per time step."""
+    ndir = len(xprojs)
+    B, T, H4 = xprojs[0].shape
+    H = H4 // 4
+    w_hhs = _lstm_weights(w_hhs)
+    j = _lib.StLstmSeqJob(ndir=ndir, reverse=1 if reverse else 0, out=_p(out), ldo=int(out.stride(1)), B=B, T=T, H=H,
+                          allow_persist=1 if LSTM_PERSIST else 0)
+    for d in range(ndir):
+        j.xproj[d], j.w_hh[d], j.b_hh[d], j.ocol[d] = _p(xprojs[d]), _p(w_hhs[d]), _p(b_hhs[d]), d * H if ocols is None else int(ocols[d])
+        j.gates_tape[d] = _p(gates_tapes[d]) if gates_tapes is not None else None
+        j.c_tape[d] = _p(c_tapes[d]) if c_tapes is not None else None
+    plan = lstm_plan(False, ndir, out, j.ocol, H, [out] + w_hhs)
+    _lstm_run('st_lstm_seq_fwd', j, plan, out.device)
 
 
 PERSIST_CU_RESERVE = int(os.environ.get('ST_PERSIST_CU_RESERVE', '32'))      # compute units left to RCCL's channels beside the one-launch BiLSTM backward
-_N_CU = {}
 
 
-def _persist_bwd_headroom(B, H):
-    """The one-launch BiLSTM backward needs all of its workgroups co-resident.  Under data parallelism the decoder's gradient buckets are
-    all-reduced by RCCL kernels on another stream exactly while the encoder's BiLSTM backward runs (advisor, round 5): with more than one
-    rank and asynchronous buckets in flight the launch must leave PERSIST_CU_RESERVE compute units free, or the per-step form runs instead
-    (a starved launch costs a skipped step and switches LSTM_PERSIST off for good)."""
+def _persist_bwd_headroom():
+    """Compute units the one-launch BiLSTM backward must leave free.  It needs all of its workgroups co-resident, and under data
+    parallelism the decoder's gradient buckets are all-reduced by RCCL kernels on another stream exactly while the encoder's BiLSTM
+    backward runs (advisor, round 5): with more than one rank and asynchronous buckets in flight the launch leaves PERSIST_CU_RESERVE
+    compute units free, or the per-step form runs instead (a starved launch costs a skipped step and switches LSTM_PERSIST off for good)."""
     sink = _GRAD_SINK
-    if sink is None or not getattr(sink, '_active', False):
-        return True
+    if sink is None or not getattr(sink, '_active', False) or not any(w is not None for w in getattr(sink, 'works', ())):
+        return 0
     try:
         import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-            return True
+        return PERSIST_CU_RESERVE if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 else 0
     except Exception:
-        return True
-    if not any(w is not None for w in getattr(sink, 'works', ())):
-        return True
-    dev = torch.cuda.current_device()
-    if dev not in _N_CU:
-        _N_CU[dev] = device_info()['n_cu']
-    return 2 * (H // 16) * ((B + 15) // 16) <= _N_CU[dev] - PERSIST_CU_RESERVE
+        return 0
 
 
-def lstm_seq2_bwd(dout, gates_tapes, c_tapes, w_hh_ts, w_hhs=None):
-    """both directions at once: dout (B,T,2H) -> (dxproj_f, dxproj_b), each (B,T,4H).  w_hhs = the two W_hh parameters (4H, H): with
-    H % 16 == 0 the loop runs on packed operands, one launch per step (product + pointwise backward of the previous step)."""
+def lstm_layer_bwd(dout, gates_tapes, c_tapes, w_hhs, reverse=False, dcols=None):
+    """Backward through time of lstm_layer: dout (B,T,>= dcols[d]+H) -> [dxproj of direction d (B,T,4H)].  w_hhs: the W_hh parameters
+    (4H, H); the layout the form st_lstm_seq_variant chooses needs (transposed, packed) is built here."""
+    ndir = len(gates_tapes)
     T, B, _, H = gates_tapes[0].shape
-    dx = list(torch.empty(2, B, T, 4 * H, device=dout.device, dtype=torch.float32).unbind(0))      # (back to back: one sentinel fill)
-    lib = _lib.load()
-    P2 = C.c_void_p * 2
-    arr = lambda a, b_: P2(_p(a), _p(b_))
-    if LSTM_PERSIST and w_hhs is not None and dout.stride(2) == 1 and dout.stride(0) == T * dout.stride(1) and dout.data_ptr() % 16 == 0 and \
-            all(w.is_contiguous() for w in w_hhs) and lib.st_lstm_seq2_bwd_persist_supported(B, T, H, int(dout.stride(1)), 0, H) and \
-            _persist_bwd_headroom(B, H):
-        # all T steps in one launch (slices of W_hh and the carried dL/dc in registers, the gate gradients handed over through dx itself)
-        join_side()
-        check(lib.st_lstm_seq2_bwd_persist(_p(dout), int(dout.stride(1)), (C.c_int * 2)(0, H), arr(*gates_tapes), arr(*c_tapes),
-                                           arr(*[w.detach() for w in w_hhs]), arr(*dx), B, T, H,
-                                           _p(persist_status(dout.device), torch.int32), stream_handle()), 'st_lstm_seq2_bwd_persist')
-        return dx
-    if w_hhs is not None and H % 16 == 0:
-        packed = [pack_weight_t([w.detach()]) for w in w_hhs]                 # W_hh^T in MFMA order: N = H, K = 4H
-        ws = torch.empty(2 * B * H, device=dout.device, dtype=torch.float32)
-        t16 = torch.empty(4 * t16_floats(B, 4 * H), device=dout.device, dtype=torch.float32)
-        check(_lib.load().st_lstm_seq2_bwd_packed(_p(dout), int(dout.stride(1)), (C.c_int * 2)(0, H), arr(*gates_tapes), arr(*c_tapes),
-                                                  arr(*packed), arr(*dx), _p(ws), _p(t16), B, T, H, stream_handle()),
-              'st_lstm_seq2_bwd_packed')
-        return dx
-    ws = torch.empty(4 * B * H, device=dout.device, dtype=torch.float32)
-    P2 = C.c_void_p * 2
-    arr = lambda a, b_: P2(_p(a), _p(b_))
-    check(_lib.load().st_lstm_seq2_bwd(_p(dout), int(dout.stride(1)), (C.c_int * 2)(0, H), arr(*gates_tapes), arr(*c_tapes),
-                                       arr(*w_hh_ts), arr(*dx), _p(ws), B, T, H, stream_handle()), 'st_lstm_seq2_bwd')
+    w_hhs = _lstm_weights(w_hhs)
+    dx = list(torch.empty(ndir, B, T, 4 * H, device=dout.device, dtype=torch.float32).unbind(0))      # (back to back: one sentinel fill)
+    j = _lib.StLstmSeqBwdJob(ndir=ndir, reverse=1 if reverse else 0, dout=_p(dout), ldd=int(dout.stride(1)), B=B, T=T, H=H,
+                             allow_persist=1 if LSTM_PERSIST else 0, cu_reserve=_persist_bwd_headroom() if LSTM_PERSIST and ndir == 2 else 0)
+    for d in range(ndir):
+        j.dcol[d], j.gates_tape[d], j.c_tape[d], j.dxproj[d] = d * H if dcols is None else int(dcols[d]), _p(gates_tapes[d]), _p(c_tapes[d]), _p(dx[d])
+    plan = lstm_plan(True, ndir, dout, j.dcol, H, [dout] + list(gates_tapes) + list(c_tapes) + dx, j.cu_reserve)
+    if plan.weights == LSTM_W_T:
+        ws_w = [dx_weight(w)[0] for w in w_hhs]                 # W_hh^T (H, 4H)
+    elif plan.weights == LSTM_W_PACKED_T:
+        ws_w = [pack_weight_t([w]) for w in w_hhs]              # W_hh^T in MFMA order: N = H, K = 4H
+    else:
+        ws_w = w_hhs
+    j.weights = plan.weights
+    for d in range(ndir):
+        j.w[d] = _p(ws_w[d])
+    _lstm_run('st_lstm_seq_bwd', j, plan, dout.device)
     return dx
 
 

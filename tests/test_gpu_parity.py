@@ -480,7 +480,7 @@ def test_bilstm_sequence(dev, B, T, I, H):
     xd = x.to(dev)
     for rev, sfx in ((False, '_l0'), (True, '_l0_reverse')):
         xp = ops.gemm(xd, W['l.weight_ih' + sfx].to(dev), bias=W['l.bias_ih' + sfx].to(dev))
-        ops.lstm_seq(xp, W['l.weight_hh' + sfx].to(dev), W['l.bias_hh' + sfx].to(dev), out, H if rev else 0, rev)
+        ops.lstm_layer((xp,), (W['l.weight_hh' + sfx].to(dev),), (W['l.bias_hh' + sfx].to(dev),), out, reverse=rev, ocols=(H if rev else 0,))
     err = maxdiff(out, ref)
     report('bilstm', B=B, T=T, H=H, err=err)
     assert err < 2e-5

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""us per bidirectional LSTM layer: one launch for all steps (st_lstm_seq2_persist_fwd) against one launch per step, graph replays.
+"""us per bidirectional LSTM layer: one launch for all steps (the ST_LSTM_PERSIST form of st_lstm_seq_fwd) against one launch per step, graph replays.
    python tools/exp_lstm_persist.py [B T H [train]] ..."""
 import os
 import sys
@@ -22,10 +22,10 @@ for B, T, H, train in shapes:
         ops.LSTM_PERSIST = persist
         g = ops.Graph()
         with g.memory():
-            ops.lstm_seq2(xp[0], xp[1], w[0], w[1], b[0], b[1], out, gs, cs)
+            ops.lstm_layer(xp, w, b, out, gs, cs)
             with g.capture():
                 for _ in range(5):
-                    ops.lstm_seq2(xp[0], xp[1], w[0], w[1], b[0], b[1], out, gs, cs)
+                    ops.lstm_layer(xp, w, b, out, gs, cs)
         g.launch(); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(10):
