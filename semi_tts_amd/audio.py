@@ -39,7 +39,7 @@ import wave
 import numpy as np
 import torch
 
-from . import ops
+from . import toolops
 from .ctc_align import segment_key      # a file's key in a segment table: its name up to the first '.' (src/audio.py:342)
 
 GFL_ITER = 30                     # src/audio.py:15
@@ -202,9 +202,9 @@ def _run(feat_btf, phases, n_fft, hop, win, n_iter, normalized, power, post, bas
         raise ValueError('Griffin-Lim: phases of shape %s, expected %s' % (tuple(phases.shape), (B, F, T)))
     dev = feat_btf.device if feat_btf.is_cuda else _device()
     feat_btf = feat_btf.to(dev, torch.float32)
-    return ops.griffin_lim_batch(feat_btf, phases.to(dev).contiguous(), n_fft, hop, win, n_iter=n_iter, normalized=normalized,
-                                 power=power, post=post, basis=None if basis is None else basis(dev),
-                                 frames=None if frames is None else torch.from_numpy(frames).to(dev))
+    return toolops.griffin_lim_batch(feat_btf, phases.to(dev).contiguous(), n_fft, hop, win, n_iter=n_iter, normalized=normalized,
+                                     power=power, post=post, basis=None if basis is None else basis(dev),
+                                     frames=None if frames is None else torch.from_numpy(frames).to(dev))
 
 
 def griffin_lim(amp, phases=None, n_iter=GFL_ITER, n_fft=DEFAULT_N_FFT, hop=DEFAULT_HOP, win=DEFAULT_WIN):
@@ -253,7 +253,7 @@ class AudioConverter:
         s = specgram.unsqueeze(0) if squeeze else specgram
         if phases is not None and squeeze:
             phases = torch.as_tensor(phases).unsqueeze(0)
-        post = ops.GL_CLIP | (ops.GL_INV_PREEMPHASIS if inv_preemphasis else 0)
+        post = toolops.GL_CLIP | (toolops.GL_INV_PREEMPHASIS if inv_preemphasis else 0)
         wav = _run(s.transpose(1, 2), phases, self.n_fft, self.hop_length, self.win_length, n_iter, normalized=not isAmp,
                    power=power, post=post)
         wav = wav.cpu().numpy().astype(np.float64)
@@ -285,8 +285,8 @@ class AudioConverter:
             raise ValueError('mel vocoding: %d mel bins, expected num_mels = %d' % (width, self.n_mels))
         if self.n_fft not in SUPPORTED_N_FFT:
             raise ValueError('mel vocoding: n_fft %d not supported (one of %s)' % (self.n_fft, SUPPORTED_N_FFT))
-        if not 1 <= self.n_mels <= ops.MEL_MAX:
-            raise ValueError('mel vocoding: %d mels outside [1, %d]' % (self.n_mels, ops.MEL_MAX))
+        if not 1 <= self.n_mels <= toolops.MEL_MAX:
+            raise ValueError('mel vocoding: %d mels outside [1, %d]' % (self.n_mels, toolops.MEL_MAX))
         self.mel_basis()                                 # (a rank-deficient bank raises here, on the host)
 
     def melspecgram_to_specgram(self, melspecgram):
@@ -296,7 +296,7 @@ class AudioConverter:
         m = melspecgram.unsqueeze(0) if squeeze else melspecgram
         self._check_mel(m.size(1))
         dev = m.device if m.is_cuda else _device()
-        lin = ops.mel_to_linear(m.to(dev, torch.float32).transpose(1, 2), self.mel_basis(dev), normalized=True, take_abs=False)
+        lin = toolops.mel_to_linear(m.to(dev, torch.float32).transpose(1, 2), self.mel_basis(dev), normalized=True, take_abs=False)
         lin = lin.transpose(1, 2)
         return lin[0] if squeeze else lin
 
@@ -409,7 +409,7 @@ class AudioConverter:
     def _check_loudness(self, target=None, peak_db=-1.0, max_gain_db=30.0, lens=(1,)):
         """every refusal of loudness_batch that does not need the waveforms"""
         lens = np.asarray(lens, np.int64)
-        ops._loudness_check(lens[:ops.FEATURES_MAX_BATCH], self.sr, target, peak_db, max_gain_db)
+        toolops._loudness_check(lens[:toolops.FEATURES_MAX_BATCH], self.sr, target, peak_db, max_gain_db)
         if (lens < 1).any() or (lens >= 2 ** 31).any():
             raise ValueError('loudness: every length must lie in [1, 2^31)')
 
@@ -428,17 +428,17 @@ class AudioConverter:
             return wav
         self._check_loudness(target, peak_db, max_gain_db, lens=lens[rows])
         x = wav.view(-1)
-        for b0 in range(0, len(rows), ops.FEATURES_MAX_BATCH):
-            r = rows[b0:b0 + ops.FEATURES_MAX_BATCH]
-            _, stats, _ = ops.loudness(x, r * N, lens[r], self.sr, target, peak_db, max_gain_db)
-            ops.wave_gain(x, r * N, lens[r], stats, out=x)
+        for b0 in range(0, len(rows), toolops.FEATURES_MAX_BATCH):
+            r = rows[b0:b0 + toolops.FEATURES_MAX_BATCH]
+            _, stats, _ = toolops.loudness(x, r * N, lens[r], self.sr, target, peak_db, max_gain_db)
+            toolops.wave_gain(x, r * N, lens[r], stats, out=x)
         return wav
 
     def loudness_batch(self, wavs, target=None, peak_db=-1.0, max_gain_db=30.0):
         """Integrated loudness (ITU-R BS.1770-4, mono) of a ragged batch on the device, one st_loudness_batch call per 64 utterances and
         ONE host read: wavs, a list of 1-D waveforms or a WaveBatch.  -> a dict of host arrays, entry i for utterance i of `wavs` (a
         list's position; a WaveBatch's row): lufs, momentary_max, rel_gate, peak (linear), ungated, gain_db (float64) and n_blocks, n_abs,
-        n_rel, flags (int64; ops.LOUDNESS_FLAGS).  With a target (LUFS) the utterances are also multiplied by the gain that brings them
+        n_rel, flags (int64; toolops.LOUDNESS_FLAGS).  With a target (LUFS) the utterances are also multiplied by the gain that brings them
         to it, limited so that the sample peak stays at or under peak_db dBFS and the gain at or under max_gain_db -- flagged
         utterances (non-finite, shorter than 400 ms, silent) keep their level -- and (dict, WaveBatch) is returned: the normalised
         batch with the input's rows, offsets and lens.  A WaveBatch is normalised IN PLACE in its packed buffer; a list is not touched."""
@@ -448,11 +448,11 @@ class AudioConverter:
         B = len(wb.lens)
         x = wb.packed(dev)
         parts = []
-        for b0 in range(0, B, ops.FEATURES_MAX_BATCH):
-            sl = slice(b0, min(B, b0 + ops.FEATURES_MAX_BATCH))
-            _, stats, counts = ops.loudness(x, wb.offsets[sl], wb.lens[sl], self.sr, target, peak_db, max_gain_db)
+        for b0 in range(0, B, toolops.FEATURES_MAX_BATCH):
+            sl = slice(b0, min(B, b0 + toolops.FEATURES_MAX_BATCH))
+            _, stats, counts = toolops.loudness(x, wb.offsets[sl], wb.lens[sl], self.sr, target, peak_db, max_gain_db)
             if target is not None:
-                ops.wave_gain(x, wb.offsets[sl], wb.lens[sl], stats, out=x)
+                toolops.wave_gain(x, wb.offsets[sl], wb.lens[sl], stats, out=x)
             parts.append((stats, counts))
         host = torch.cat([p[0].reshape(-1).view(torch.int32) for p in parts] + [p[1].reshape(-1) for p in parts]).cpu().numpy()
         stats = host[:8 * B].view(np.float32).reshape(B, 8).astype(np.float64)
@@ -475,7 +475,7 @@ class AudioConverter:
         if isinstance(pad_ms, bool) or not isinstance(pad_ms, (int, float, np.integer, np.floating)) or not 0.0 <= pad_ms < float('inf'):
             raise ValueError('trim: pad_ms must be a finite number >= 0 (got %r)' % (pad_ms,))
         pad = int(round(float(pad_ms) / 1000.0 * self.sr))
-        ops._trim_check(np.asarray(lens, np.int64), frame_length, hop_length, top_db, pad, 0)
+        toolops._trim_check(np.asarray(lens, np.int64), frame_length, hop_length, top_db, pad, 0)
         return pad
 
     def trim_batch(self, wavs, top_db=60., frame_length=2048, hop_length=512, pad_ms=0., with_intervals=False):
@@ -497,7 +497,7 @@ class AudioConverter:
         B = len(wb.lens)
         max_iv = (2 + int(wb.lens.max()) // hop_length) // 2 if with_intervals else 0      # runs of T frames: at most ceil(T / 2)
         x = wb.packed(dev)
-        _, bounds, iv, n_iv = ops.trim_silence(x, wb.offsets, wb.lens, frame_length, hop_length, top_db, pad=pad, max_iv=max_iv)
+        _, bounds, iv, n_iv = toolops.trim_silence(x, wb.offsets, wb.lens, frame_length, hop_length, top_db, pad=pad, max_iv=max_iv)
         if with_intervals:
             host = torch.cat([bounds.reshape(-1), n_iv, iv.reshape(-1)]).cpu().numpy().astype(np.int64)
             n_iv, iv = host[4 * B:5 * B], host[5 * B:].reshape(B, max_iv, 2)
@@ -558,8 +558,8 @@ class AudioConverter:
         dev = x.device if x.is_cuda else _device()
         xd = x.to(dev, torch.float32).contiguous()
         T = 1 + xd.numel() // self.hop_length
-        mel, lin, _ = ops.audio_features(xd, [0], [xd.numel()], self.n_fft, self.win_length, self.hop_length,
-                                         self.preemphasis_coeff if preemphasis else 0.0, self.filterbank(dev), T)
+        mel, lin, _ = toolops.audio_features(xd, [0], [xd.numel()], self.n_fft, self.win_length, self.hop_length,
+                                             self.preemphasis_coeff if preemphasis else 0.0, self.filterbank(dev), T)
         return lin[0].t().to(x.device), mel[0].t().to(x.device)
 
     # -- MFCC (src/audio.py:119-154) and phone segments (:94-117, :339-354)
@@ -577,15 +577,15 @@ class AudioConverter:
             raise ValueError('mfcc: n_fft %d not supported (one of %s)' % (self.n_fft, SUPPORTED_N_FFT))
         if not (0 < 2 * hop <= win <= self.n_fft):
             raise ValueError('mfcc: the MFCC framing needs 0 < 2 * hop <= win <= n_fft (hop %d, win %d, n_fft %d)' % (hop, win, self.n_fft))
-        if not N_MFCC_NO_DELTA <= self.n_mels <= ops.MEL_MAX:
-            raise ValueError('mfcc: %d mels outside [%d, %d]' % (self.n_mels, N_MFCC_NO_DELTA, ops.MEL_MAX))
+        if not N_MFCC_NO_DELTA <= self.n_mels <= toolops.MEL_MAX:
+            raise ValueError('mfcc: %d mels outside [%d, %d]' % (self.n_mels, N_MFCC_NO_DELTA, toolops.MEL_MAX))
         for L in lens:
             if L <= self.n_fft // 2 or L >= 2 ** 30:
                 raise ValueError('mfcc: an utterance of %d samples: reflect padding needs more than n_fft // 2 = %d (and fewer than 2^30)'
                                  % (L, self.n_fft // 2))
-            if 1 + L // hop < ops.MFCC_MIN_FRAMES:
+            if 1 + L // hop < toolops.MFCC_MIN_FRAMES:
                 raise ValueError('mfcc: an utterance of %d samples has fewer than 9 MFCC frames (%d at hop %d): the 9-frame derivatives '
-                                 'need at least %d samples' % (L, 1 + L // hop, hop, (ops.MFCC_MIN_FRAMES - 1) * hop))
+                                 'need at least %d samples' % (L, 1 + L // hop, hop, (toolops.MFCC_MIN_FRAMES - 1) * hop))
 
     def extract_mfcc_batch(self, wavs, preemphasis=True, with_mel=False):
         """extract_mfcc_from_waveform for a ragged batch in one st_audio_mfcc call: wavs, a list of 1-D waveforms (or a WaveBatch),
@@ -595,9 +595,9 @@ class AudioConverter:
         self._check_mfcc(wb.lens.tolist())
         dev = wb.device if wb.device is not None else _device()
         T_pad = int(1 + wb.lens.max() // self.hop_length_mfcc)
-        mfcc, mel = ops.audio_mfcc(wb.packed(dev), wb.offsets, wb.lens, self.n_fft, self.win_length_mfcc, self.hop_length_mfcc,
-                                   self.preemphasis_coeff if preemphasis else 0.0, self.filterbank(dev), self.mfcc_table(dev), T_pad,
-                                   with_mel=with_mel)
+        mfcc, mel = toolops.audio_mfcc(wb.packed(dev), wb.offsets, wb.lens, self.n_fft, self.win_length_mfcc, self.hop_length_mfcc,
+                                       self.preemphasis_coeff if preemphasis else 0.0, self.filterbank(dev), self.mfcc_table(dev), T_pad,
+                                       with_mel=with_mel)
         return (mfcc, mel) if with_mel else mfcc
 
     def extract_mfcc_from_waveform(self, waveform, preemphasis=True, channel=0):
@@ -616,15 +616,15 @@ class AudioConverter:
         if not (0.0 < fmin < fmax < float('inf')):
             raise ValueError('f0: needs 0 < fmin < fmax (got fmin %r, fmax %r)' % (fmin, fmax))
         tau_max, tau_min = int(math.ceil(self.sr / fmin)), int(math.floor(self.sr / fmax))       # (fmin < fmax: tau_min < tau_max)
-        if tau_max > ops.F0_MAX_TAU:
+        if tau_max > toolops.F0_MAX_TAU:
             raise ValueError('f0: fmin %g Hz at %d Hz needs lags up to tau_max = %d; the limit is tau_max <= %d (fmin >= %.2f Hz)'
-                             % (fmin, self.sr, tau_max, ops.F0_MAX_TAU, self.sr / ops.F0_MAX_TAU))
+                             % (fmin, self.sr, tau_max, toolops.F0_MAX_TAU, self.sr / toolops.F0_MAX_TAU))
         if tau_min < 2:
             raise ValueError('f0: fmax %g Hz at %d Hz gives tau_min = %d; the limit is tau_min >= 2 (fmax <= %.1f Hz)'
                              % (fmax, self.sr, tau_min, self.sr / 2.0))
         W = 2 * tau_max if window is None else int(window)
-        if not 1 <= W <= ops.F0_MAX_W:
-            raise ValueError('f0: window %d outside the limit 1 <= W <= %d' % (W, ops.F0_MAX_W))
+        if not 1 <= W <= toolops.F0_MAX_W:
+            raise ValueError('f0: window %d outside the limit 1 <= W <= %d' % (W, toolops.F0_MAX_W))
         return tau_min, tau_max, W
 
     def extract_f0_batch(self, wavs, fmin=60., fmax=500., threshold=0.15, window=None, with_aper=False):
@@ -636,10 +636,10 @@ class AudioConverter:
         tau_min, tau_max, W = self.f0_lags(fmin, fmax, window)
         wb = wavs if isinstance(wavs, WaveBatch) else WaveBatch(wavs)
         hop = self.hop_length_mfcc
-        ops._f0_check(wb.lens, hop, W, tau_min, tau_max, self.sr, threshold)
+        toolops._f0_check(wb.lens, hop, W, tau_min, tau_max, self.sr, threshold)
         dev = wb.device if wb.device is not None else _device()
         T_pad = int(1 + wb.lens.max() // hop)
-        f0, aper = ops.f0_yin(wb.packed(dev), wb.offsets, wb.lens, hop, W, tau_min, tau_max, float(self.sr), threshold, T_pad, with_aper=with_aper)
+        f0, aper = toolops.f0_yin(wb.packed(dev), wb.offsets, wb.lens, hop, W, tau_min, tau_max, float(self.sr), threshold, T_pad, with_aper=with_aper)
         return (f0, aper) if with_aper else f0
 
     def extract_f0_from_waveform(self, waveform, fmin=60., fmax=500., threshold=0.15, window=None, channel=0):
@@ -698,7 +698,7 @@ class AudioConverter:
         if feats.stride(2) != 1:
             feats = feats.contiguous()
         table = torch.tensor([utt, start, length], dtype=torch.int32).reshape(3, len(utt)).to(dev)
-        return ops.segment_gather(feats, table[0], table[1], table[2], max_len), counts
+        return toolops.segment_gather(feats, table[0], table[1], table[2], max_len), counts
 
     def segment_features(self, file):
         """the segmented feature of src/audio.py:339-354, which wave_to_feat computes there and does not return: segment_feat
@@ -758,10 +758,10 @@ class AudioConverter:
         T = 1 + wb.lens // self.hop_length
         T_pad = int(T.max()) if r is None else int(T.max()) + r - int(T.max()) % r
         Ta_pad = max(1 + L // h for L, (_, h) in zip(wb.lens, aug_dims))
-        mel, lin, aug = ops.audio_features(x, wb.offsets, wb.lens, self.n_fft, self.win_length, self.hop_length, self.preemphasis_coeff,
-                                           self.filterbank(dev), T_pad, with_linear=self.use_linear,
-                                           aug_win=[d[0] for d in aug_dims], aug_hop=[d[1] for d in aug_dims], Ta_pad=Ta_pad,
-                                           snr_db=snr_db, noise=nz, seed=seed)
+        mel, lin, aug = toolops.audio_features(x, wb.offsets, wb.lens, self.n_fft, self.win_length, self.hop_length, self.preemphasis_coeff,
+                                               self.filterbank(dev), T_pad, with_linear=self.use_linear,
+                                               aug_win=[d[0] for d in aug_dims], aug_hop=[d[1] for d in aug_dims], Ta_pad=Ta_pad,
+                                               snr_db=snr_db, noise=nz, seed=seed)
         return mel, aug, lin
 
     def gen_wav_device(self, lin, phases=None, frames=None, mel=False):
@@ -772,7 +772,7 @@ class AudioConverter:
         elif lin.size(-1) != self.num_freq:
             raise NotImplementedError('gen_wav: only the linear spectrogram (%d bins) is vocoded, got %d' % (self.num_freq, lin.size(-1)))
         return _run(lin, phases, self.n_fft, self.hop_length, self.win_length, GFL_ITER, normalized=True, power=1.0,
-                    post=ops.GL_CLIP | ops.GL_INV_PREEMPHASIS, basis=self.mel_basis if mel else None, frames=frames)
+                    post=toolops.GL_CLIP | toolops.GL_INV_PREEMPHASIS, basis=self.mel_basis if mel else None, frames=frames)
 
 
 def load_audio_transform(num_freq, num_mels, frame_length_ms, frame_shift_ms, preemphasis_coeff, sample_rate, use_linear=True,
@@ -977,7 +977,7 @@ def resample_table(orig_sr, new_sr, lowpass_filter_width=RESAMPLE_LPW, rolloff=R
     the header's definition, scale base / o included, computed in float64 and rounded once, exactly 0 where |i - tau| >= W (rows
     with fewer taps than the widest are padded with such zeros).  first (n,) int32.  device None: numpy arrays; else the copies on
     that device.  Cached per ratio and per device.  Raises ValueError, before any device is touched, for rates that are not
-    positive integers and for a ratio the kernel does not take (ops.RESAMPLE_MAX_TABLE_FLOATS / RESAMPLE_MAX_STAGE_FLOATS)."""
+    positive integers and for a ratio the kernel does not take (toolops.RESAMPLE_MAX_TABLE_FLOATS / RESAMPLE_MAX_STAGE_FLOATS)."""
     o, n = _ratio(orig_sr, new_sr)
     lpw, rolloff = int(lowpass_filter_width), float(rolloff)
     if lpw != lowpass_filter_width or lpw < 1 or not 0.0 < rolloff <= 1.0:
@@ -993,11 +993,11 @@ def resample_table(orig_sr, new_sr, lowpass_filter_width=RESAMPLE_LPW, rolloff=R
         first = np.floor(frac - W).astype(np.int64) + 1
         last = np.ceil(frac + W).astype(np.int64) - 1
         taps = int((last - first + 1).max())
-        tab_f, stage_f = ops.resample_lds_floats(o, n, taps, int(first.min()), int(first.max()))
-        if tab_f > ops.RESAMPLE_MAX_TABLE_FLOATS or stage_f > ops.RESAMPLE_MAX_STAGE_FLOATS:
+        tab_f, stage_f = toolops.resample_lds_floats(o, n, taps, int(first.min()), int(first.max()))
+        if tab_f > toolops.RESAMPLE_MAX_TABLE_FLOATS or stage_f > toolops.RESAMPLE_MAX_STAGE_FLOATS:
             raise ValueError('resample: %d -> %d Hz (ratio %d / %d, %d taps) needs %d floats of staged table (limit %d) and %d of staged '
-                             'input (limit %d)' % (orig_sr, new_sr, o, n, taps, tab_f, ops.RESAMPLE_MAX_TABLE_FLOATS, stage_f,
-                                                   ops.RESAMPLE_MAX_STAGE_FLOATS))
+                             'input (limit %d)' % (orig_sr, new_sr, o, n, taps, tab_f, toolops.RESAMPLE_MAX_TABLE_FLOATS, stage_f,
+                                                   toolops.RESAMPLE_MAX_STAGE_FLOATS))
         t = (first[:, None] + np.arange(taps)[None, :]) - frac[:, None]  # i - tau
         a = np.pi * base * t / o
         h = (base / o) * np.where(a == 0.0, 1.0, np.sin(a) / np.where(a == 0.0, 1.0, a)) * np.cos(a / (2.0 * lpw)) ** 2
@@ -1042,21 +1042,21 @@ def kweight_state_matrix(sr):
 
 
 def kweight_tables(sr, device=None):
-    """What st_loudness_batch needs at the rate sr, ops.LOUDNESS_TABLE_DOUBLES float64 values laid out as include/semitts.h says: the
+    """What st_loudness_batch needs at the rate sr, toolops.LOUDNESS_TABLE_DOUBLES float64 values laid out as include/semitts.h says: the
     coefficients, A^(r 2^k) for k < 8, A^hop and A^max(0, t r - pad) for t < 256 (r the samples a thread owns, pad = 256 r - hop).
     device None: a numpy array; else its copy on that device.  Cached per rate and per device."""
-    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or not ops.LOUDNESS_MIN_SR <= sr <= ops.LOUDNESS_MAX_SR:
-        raise ValueError('loudness: the sample rate must be an integer in [%d, %d] (got %r)' % (ops.LOUDNESS_MIN_SR, ops.LOUDNESS_MAX_SR, sr))
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or not toolops.LOUDNESS_MIN_SR <= sr <= toolops.LOUDNESS_MAX_SR:
+        raise ValueError('loudness: the sample rate must be an integer in [%d, %d] (got %r)' % (toolops.LOUDNESS_MIN_SR, toolops.LOUDNESS_MAX_SR, sr))
     sr = int(sr)
     if sr not in _KWEIGHT:
         (b, a), (_, p) = kweight_coeffs(sr)
         A = kweight_state_matrix(sr)
-        hop, r, nt = ops.loudness_hop(sr), ops.loudness_run_length(sr), ops.LOUDNESS_THREADS
+        hop, r, nt = toolops.loudness_hop(sr), toolops.loudness_run_length(sr), toolops.LOUDNESS_THREADS
         pad = nt * r - hop
         power = np.linalg.matrix_power
         tab = np.concatenate([[b[0], b[1], b[2], a[1], a[2], p[1], p[2], 0.0]] + [power(A, r << k).reshape(-1) for k in range(8)]
                              + [power(A, hop).reshape(-1)] + [power(A, max(0, t * r - pad)).reshape(-1) for t in range(nt)])
-        assert tab.shape == (ops.LOUDNESS_TABLE_DOUBLES,) and tab.dtype == np.float64
+        assert tab.shape == (toolops.LOUDNESS_TABLE_DOUBLES,) and tab.dtype == np.float64
         _KWEIGHT[sr] = tab
     if device is None:
         return _KWEIGHT[sr]
@@ -1092,7 +1092,7 @@ def resample(wavs, orig_sr, new_sr):
     lens = np.array([w.numel() for w in src], np.int64)
     off = np.concatenate([[0], np.cumsum(lens)[:-1]])
     _, _, _, first_d, table_d = resample_table(orig_sr, new_sr, device=dev)
-    y, out_off, out_lens = ops.resample_batch(x, off, lens, o, n, first_d, table_d, int(first.min()), int(first.max()))
+    y, out_off, out_lens = toolops.resample_batch(x, off, lens, o, n, first_d, table_d, int(first.min()), int(first.max()))
     out = WaveBatch([y[int(a):int(a + b)] for a, b in zip(out_off, out_lens)])
     if np.array_equal(out.order, np.arange(len(src))):
         out._packed[str(dev)] = y                       # already packed in the sorted order: no second copy

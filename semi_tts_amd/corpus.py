@@ -262,7 +262,7 @@ def too_large(name, n_utt, n_samples, max_bytes):
             % (name, n_utt, n_samples, 4 * n_samples / 2.0 ** 30, 4 * n_samples, max_bytes / 2.0 ** 30, max_bytes))
 
 
-TRIM_CALL = 64                                       # utterances per trimming call of a split (ops.FEATURES_MAX_BATCH)
+TRIM_CALL = 64                                       # utterances per trimming call of a split (toolops.FEATURES_MAX_BATCH)
 
 
 def apply_bounds(rows, mine, offsets, lens, start, end, sampler, n_fft, hop, max_frames=None):
@@ -312,7 +312,7 @@ def trim_report(name, sample_rate, before, after, n_before, counts):
 
 class DeviceSplit:
     """One split of one rank on the device: every waveform read ONCE (AudioConverter's _read_pcm / resampling path) into one packed
-    float32 buffer, with host offsets / lens.  A batch is not copied out of it: fetch() hands ops.audio_features the buffer with the
+    float32 buffer, with host offsets / lens.  A batch is not copied out of it: fetch() hands toolops.audio_features the buffer with the
     batch's offsets (WaveBatch.window).  The transcripts stay on the host; a fetch uploads the batch's text and speaker ids as one small
     int64 array (no host READ in a fetch, no file access).
 
@@ -374,10 +374,10 @@ class DeviceSplit:
 
     def _trim(self, pad, max_frames, top_db=60., frame_length=2048, hop_length=512, pad_ms=0.):
         import torch
-        from . import ops
+        from . import toolops
         mine = np.asarray(self.sampler.rows, np.int64)             # (longest first: a call's T_pad is its first utterance's)
-        parts = [ops.trim_silence(self.buffer, self.offsets[mine[i:i + TRIM_CALL]], self.lens[mine[i:i + TRIM_CALL]], frame_length, hop_length,
-                                  top_db, pad=pad)[1] for i in range(0, len(mine), TRIM_CALL)]
+        parts = [toolops.trim_silence(self.buffer, self.offsets[mine[i:i + TRIM_CALL]], self.lens[mine[i:i + TRIM_CALL]], frame_length, hop_length,
+                                      top_db, pad=pad)[1] for i in range(0, len(mine), TRIM_CALL)]
         bounds = torch.cat(parts).cpu().numpy().astype(np.int64)   # the split's one host read
         before = int(self.lens[mine].sum())
         by_row = np.argsort(mine)                                  # (the surviving rows keep their listed order)

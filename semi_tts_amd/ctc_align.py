@@ -11,9 +11,9 @@ AudioConverter reads phone boundaries "found by MFA" from a segment_file (src/au
 """
 import os
 
-from . import ops
+from . import toolops
 
-MAX_TOKENS = ops.CA_MAX_L
+MAX_TOKENS = toolops.CA_MAX_L
 
 
 def forced_align(prob, text, lengths=None, text_lengths=None, blank=0, log_input=False, eps=1e-10):
@@ -23,7 +23,7 @@ def forced_align(prob, text, lengths=None, text_lengths=None, blank=0, log_input
     tok_end (B, L) int32 the frames [start, end) of every target token (-1 past the targets)), device tensors.  An utterance too short
     for its transcript scores -inf, one with a NaN posterior or a target outside [0, V) scores NaN; their path and spans are -1.
     One launch, no host read; bad arguments raise ValueError before the device is touched."""
-    return ops.ctc_forced_align(prob, text, lengths, text_lengths, blank, log_input, eps)
+    return toolops.ctc_forced_align(prob, text, lengths, text_lengths, blank, log_input, eps)
 
 
 def read_phn(path, vocab=None):

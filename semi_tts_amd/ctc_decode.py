@@ -17,7 +17,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import ngram, ops
+from . import ngram, toolops
 
 _BONUS_CACHE = OrderedDict()        # (table identity, weight, ins_bonus, device) -> (the table object, its fused device tensor)
 _BONUS_CACHE_SIZE = 8
@@ -64,7 +64,7 @@ def beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log_inp
     probabilities), device tensors, best first.  One launch, no host read; bad arguments raise ValueError before the device is touched.
     lm: None (the acoustic search), or an n-gram probability table (fused_bonus: array, tensor or .npy path) fused with lm_weight and
     ins_bonus; bos: the start id of the empty prefix's context.  bonus: instead of lm, a fused table already on the device
-    (ops.ctc_beam_search).  With either, score is the fused score: the log prefix probability plus the bonuses of the prefix's symbols."""
+    (toolops.ctc_beam_search).  With either, score is the fused score: the log prefix probability plus the bonuses of the prefix's symbols."""
     if lm is not None and bonus is not None:
         raise ValueError('beam_search: lm and bonus are two ways to give one table; pass one of them')
     if lm is not None:
@@ -72,5 +72,5 @@ def beam_search(prob, lengths=None, beam_width=16, top_paths=1, blank=0, log_inp
             raise ValueError('beam_search: prob must be a (B, T, V) float32 GPU tensor')
         bonus = fused_bonus(lm, lm_weight, ins_bonus, prob.device, prob.shape[2])
     if bonus is None:
-        return ops.ctc_beam_search(prob, lengths, beam_width, top_paths, blank, log_input, eps)
-    return ops.ctc_beam_search(prob, lengths, beam_width, top_paths, blank, log_input, eps, bonus=bonus, bos=bos)
+        return toolops.ctc_beam_search(prob, lengths, beam_width, top_paths, blank, log_input, eps)
+    return toolops.ctc_beam_search(prob, lengths, beam_width, top_paths, blank, log_input, eps, bonus=bonus, bos=bos)

@@ -10,7 +10,7 @@ import time
 import numpy as np
 import torch
 
-from . import ops
+from . import toolops
 
 
 class DirTool:
@@ -235,7 +235,7 @@ class LoudnessWriter(DirTool):
     with --resample files of another rate are converted, with --trim-silence the kept span is metered) measured on the GPU
     (st_loudness_batch: ITU-R BS.1770-4 integrated loudness) into loudness.csv: file, samples, seconds, lufs, momentary_max, rel_gate,
     peak_dbfs, n_blocks, n_abs, n_rel, gain_db (what brings the file to the target within the two limits), flags
-    (ops.LOUDNESS_FLAGS).  With --loudness-out every file is also written there normalised, as 16-bit mono from the device's int16
+    (toolops.LOUDNESS_FLAGS).  With --loudness-out every file is also written there normalised, as 16-bit mono from the device's int16
     output (st_wave_gain); a file the meter flags as non-finite, under 400 ms or silent is copied at the level it has (channel 0 of its
     own samples when it is at the rate already).  The table goes
     into DIR2, or into DIR when nothing is written back.  No checkpoint, no model."""
@@ -277,11 +277,11 @@ class LoudnessWriter(DirTool):
             x = wb.packed(wb.device)
             pcm = torch.zeros(x.numel(), device=x.device, dtype=torch.int16) if self.out_dir is not None else None
             parts = []
-            for b0 in range(0, len(wb.lens), ops.FEATURES_MAX_BATCH):
-                sl = slice(b0, b0 + ops.FEATURES_MAX_BATCH)
-                _, stats, counts = ops.loudness(x, wb.offsets[sl], wb.lens[sl], conv.sr, **self.args)
+            for b0 in range(0, len(wb.lens), toolops.FEATURES_MAX_BATCH):
+                sl = slice(b0, b0 + toolops.FEATURES_MAX_BATCH)
+                _, stats, counts = toolops.loudness(x, wb.offsets[sl], wb.lens[sl], conv.sr, **self.args)
                 if pcm is not None:
-                    ops.wave_gain(x, wb.offsets[sl], wb.lens[sl], stats, out=pcm, pcm16=True)
+                    toolops.wave_gain(x, wb.offsets[sl], wb.lens[sl], stats, out=pcm, pcm16=True)
                 parts.append((stats, counts))
             stats = torch.cat([p[0] for p in parts]).cpu().numpy().astype(np.float64)
             counts = torch.cat([p[1] for p in parts]).cpu().numpy()
@@ -489,8 +489,8 @@ class McdScorer(DirTool):
             conv._check_mfcc([L])
         except ValueError as e:
             raise ValueError('--mcd-wav-dir: %s: %s' % (path, e))
-        if mfcc_frames(conv, L) > ops.DTW_MAX_T:
-            raise ValueError('--mcd-wav-dir: %s has %d MFCC frames; the warp takes at most %d' % (path, mfcc_frames(conv, L), ops.DTW_MAX_T))
+        if mfcc_frames(conv, L) > toolops.DTW_MAX_T:
+            raise ValueError('--mcd-wav-dir: %s has %d MFCC frames; the warp takes at most %d' % (path, mfcc_frames(conv, L), toolops.DTW_MAX_T))
 
     def load_data(self):
         from .audio import load_audio_transform
@@ -618,13 +618,13 @@ class StoiScorer(DirTool):
             if sr != sr_ref:
                 raise ValueError('--stoi-wav-dir: %s is at %d Hz and its recording %s at %d Hz; the two files of a pair share one rate' % (ps, sr, pr, sr_ref))
             try:
-                audio.resample_table(sr, ops.STOI_FS)
+                audio.resample_table(sr, toolops.STOI_FS)
             except ValueError as e:
                 raise ValueError('--stoi-wav-dir: %s: %s' % (ps, e))
             if self.align:
-                if not 0.0 <= self.max_delay < math.inf or self.max_delay * sr > ops.XCORR_MAX_LAG:
+                if not 0.0 <= self.max_delay < math.inf or self.max_delay * sr > toolops.XCORR_MAX_LAG:
                     raise ValueError('--stoi-align: %s is at %d Hz: --stoi-max-delay %g must be finite, at least 0 and at most %d samples = %.4f s at '
-                                     'that rate' % (ps, sr, self.max_delay, ops.XCORR_MAX_LAG, ops.XCORR_MAX_LAG / float(sr)))
+                                     'that rate' % (ps, sr, self.max_delay, toolops.XCORR_MAX_LAG, toolops.XCORR_MAX_LAG / float(sr)))
                 if abs(L - L_ref) > (self.max_len_diff + self.max_delay) * sr:
                     raise ValueError('--stoi-wav-dir: %s has %d samples and its recording %s %d: they differ by %.4f s, above --stoi-max-len-diff %g '
                                      'plus --stoi-max-delay %g' % (ps, L, pr, L_ref, abs(L - L_ref) / float(sr), self.max_len_diff, self.max_delay))
@@ -632,12 +632,12 @@ class StoiScorer(DirTool):
                 raise ValueError('--stoi-wav-dir: %s has %d samples and its recording %s %d: they differ by %.4f s, above --stoi-max-len-diff %g; '
                                  'the measure needs time-aligned signals' % (ps, L, pr, L_ref, abs(L - L_ref) / float(sr), self.max_len_diff))
             n = min(L, L_ref)
-            if audio.resampled_len(n, sr, ops.STOI_FS) > ops.STOI_MAX_LEN:
-                raise ValueError('--stoi-wav-dir: %s has %d samples at %d Hz; the measure takes at most %d' % (ps, audio.resampled_len(n, sr, ops.STOI_FS),
-                                                                                                        ops.STOI_FS, ops.STOI_MAX_LEN))
-            if (self.align or self.sdr) and max(L, L_ref) > ops.XCORR_MAX_LEN:
+            if audio.resampled_len(n, sr, toolops.STOI_FS) > toolops.STOI_MAX_LEN:
+                raise ValueError('--stoi-wav-dir: %s has %d samples at %d Hz; the measure takes at most %d' % (ps, audio.resampled_len(n, sr, toolops.STOI_FS),
+                                                                                                        toolops.STOI_FS, toolops.STOI_MAX_LEN))
+            if (self.align or self.sdr) and max(L, L_ref) > toolops.XCORR_MAX_LEN:
                 raise ValueError('--stoi-wav-dir: %s and its recording have up to %d samples; --stoi-align and --stoi-sdr take at most %d'
-                                 % (ps, max(L, L_ref), ops.XCORR_MAX_LEN))
+                                 % (ps, max(L, L_ref), toolops.XCORR_MAX_LEN))
             self.rates.append(sr)
             self.samples.append(n)
             self.lens.append((L, L_ref))
@@ -696,7 +696,7 @@ class StoiScorer(DirTool):
         from .metrics import overlap
         os.makedirs(self.logdir, exist_ok=True)
         t0, rows, vals, drows, srows, delays, sdrs = time.perf_counter(), [STOI_HEADER], [], [DELAY_HEADER], [SDR_HEADER], [], []
-        for r in self.batches(range(len(self.pairs)), ops.STOI_MAX_BATCH):
+        for r in self.batches(range(len(self.pairs)), toolops.STOI_MAX_BATCH):
             for i, (counts, score, d, coef, sdr) in zip(r, self.score(r.start, r.stop)):
                 f, sr = self.pairs[i][0], self.rates[i]
                 if self.align:
@@ -712,7 +712,7 @@ class StoiScorer(DirTool):
                 rows.append(stoi_row(f, self.samples[i], counts, score))
                 if counts[3] == 0 and not np.isnan(score[0]):
                     print('[WARNING]', '--stoi-wav-dir: %s has %d band frames, fewer than the %d of one segment: the sentinel %g is written and '
-                          'the file is left out of the means' % (f, counts[2], ops.STOI_SEG, ops.STOI_SENTINEL))
+                          'the file is left out of the means' % (f, counts[2], toolops.STOI_SEG, toolops.STOI_SENTINEL))
                 else:
                     vals.append(score)
         table = self.write_lines('stoi.csv', rows)
@@ -983,11 +983,11 @@ class PhnScorer(DirTool):
             self.refs.append(read_phn(os.path.join(self.ref_dir, ref), self.vocab))
             top = max([top] + self.refs[-1] + [t for p in self.hyps[-1] for t in p])
         self.n_classes = len(self.vocab) if self.vocab is not None else max(1, top + 1)
-        if self.n_classes > ops.EA_MAX_V:
+        if self.n_classes > toolops.EA_MAX_V:
             raise ValueError('--score-phn-dir: %d classes (%s); the confusion matrix takes at most %d'
-                             % (self.n_classes, 'the size of --vocab' if self.vocab is not None else '1 + the largest id', ops.EA_MAX_V))
-        if len(self.ignore) > ops.EA_MAX_IGNORE:
-            raise ValueError('--score-ignore: %d ids, at most %d' % (len(self.ignore), ops.EA_MAX_IGNORE))
+                             % (self.n_classes, 'the size of --vocab' if self.vocab is not None else '1 + the largest id', toolops.EA_MAX_V))
+        if len(self.ignore) > toolops.EA_MAX_IGNORE:
+            raise ValueError('--score-ignore: %d ids, at most %d' % (len(self.ignore), toolops.EA_MAX_IGNORE))
         return self
 
     def score(self, lo, hi):

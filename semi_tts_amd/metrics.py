@@ -48,7 +48,7 @@ import math
 
 import torch
 
-from . import ops
+from . import toolops
 
 # <pad>, <space>, <eos> and id 42, exactly as src/util.py:16.  Id 42 is the last phoneme of the reference's 43-entry vocabulary
 # (data/cmu_phn.vocab), not a special token: the reference drops it from both transcripts all the same, and so does this module,
@@ -71,7 +71,7 @@ def edit_distances(pred, truth, ignore=IGNORE_INDICES):
     truth: (B, L) int64 transcripts.  dist[b] = edit distance between the collapsed, filtered argmax and truth[b] without the
     ignored ids; ref_len[b] = the length of the latter."""
     pred, truth = _on_device(pred, truth)
-    return ops.ctc_greedy_edit_distance(pred, truth, ignore)
+    return toolops.ctc_greedy_edit_distance(pred, truth, ignore)
 
 
 def per_sum(pred, truth, ignore=IGNORE_INDICES):
@@ -95,7 +95,7 @@ def beam_per_sum(prob, truth, beam_width, lengths=None, ignore=IGNORE_INDICES, l
     from .ctc_decode import beam_search
     prob, truth = _on_device(prob, truth)
     hyp, hyp_len, _ = beam_search(prob, lengths, beam_width, 1, log_input=log_input, lm=lm, lm_weight=lm_weight, ins_bonus=ins_bonus)
-    return _rate_sum(*ops.hyp_edit_distance(hyp[:, 0], hyp_len[:, 0], truth, ignore))
+    return _rate_sum(*toolops.hyp_edit_distance(hyp[:, 0], hyp_len[:, 0], truth, ignore))
 
 
 def cal_per(pred, truth):
@@ -115,7 +115,7 @@ def dtw(x, y, x_len=None, y_len=None, cols=None, scale=1.0, want_path=True):
     from (0, 0) to (n-1, m-1), -1 past path_len; None when want_path is false), device tensors.  An empty side or a NaN among the
     compared values gives total NaN, path_len 0 and a path of -1.  A pair's result depends on that pair alone and is bitwise
     repeatable.  One launch, no host read; bad arguments raise ValueError before the device is touched."""
-    return ops.dtw(x, y, x_len, y_len, cols, scale, want_path)
+    return toolops.dtw(x, y, x_len, y_len, cols, scale, want_path)
 
 
 def mcd(mfcc_x, x_len, mfcc_y, y_len, n_cep=13):
@@ -134,12 +134,12 @@ def mcd(mfcc_x, x_len, mfcc_y, y_len, n_cep=13):
     settings, Griffin-Lim iteration counts -- not with MCD tables computed from SPTK mel-cepstra.
     An empty utterance or a NaN among the cepstra gives NaN."""
     n_cep = int(n_cep)
-    ops._dtw_side('mfcc_x', mfcc_x)
-    ops._dtw_side('mfcc_y', mfcc_y)
+    toolops._dtw_side('mfcc_x', mfcc_x)
+    toolops._dtw_side('mfcc_y', mfcc_y)
     width = min(mfcc_x.shape[2], mfcc_y.shape[2])
     if not 2 <= n_cep <= width:
         raise ValueError('mcd: n_cep = %d: at least 2 (the 0th coefficient is left out) and at most the %d columns given' % (n_cep, width))
-    total, path_len, path = ops.dtw(mfcc_x, mfcc_y, x_len, y_len, (1, n_cep), MCD_SCALE, True)
+    total, path_len, path = toolops.dtw(mfcc_x, mfcc_y, x_len, y_len, (1, n_cep), MCD_SCALE, True)
     return total / path_len.to(torch.float32), path_len, path
 
 
@@ -158,7 +158,7 @@ def attention_endpoints(align, enc_len, patience=3, max_jump=4):
     -> AttentionEndpoints(end, reached, n_back, n_skip, covered, nonfinite: (B,) int32; focus (B,) float32; peak (B, S) int32;
     dur (B, L) int32), device tensors.  An utterance's result depends on it alone and is bitwise repeatable.  One launch, no host
     read; bad arguments raise ValueError before the device is touched."""
-    stats, focus, peak, dur = ops.attn_endpoint(align, enc_len, patience, max_jump)
+    stats, focus, peak, dur = toolops.attn_endpoint(align, enc_len, patience, max_jump)
     return AttentionEndpoints(*stats.unbind(1), focus, peak, dur)
 
 
@@ -171,7 +171,7 @@ def f0_scores(f0_x, f0_y, path, path_len):
       vuv_error = n_vuv / n_pairs, gross_error = n_gross / n_both (NaN where the denominator is 0).
     -> a dict of (B,) device tensors (the four counts, the four figures, and sum_sq_cents / sum_cents as the kernel summed them).
     One launch and a few element-wise divisions on the device; no host read.  Bitwise repeatable."""
-    counts, sums = ops.f0_path_scores(f0_x, f0_y, path, path_len)
+    counts, sums = toolops.f0_path_scores(f0_x, f0_y, path, path_len)
     n_pairs, n_both, n_vuv, n_gross = counts.unbind(1)
     nan = torch.full_like(sums[:, 0], math.nan)
     both, pairs = n_both.to(torch.float32), n_pairs.to(torch.float32)
@@ -222,8 +222,8 @@ def align_transcripts(hyp, hyp_len, ref, ref_len=None, ignore=IGNORE_INDICES, n_
         n_classes = confusion.shape[0] - 1
     if confusion is None and n_classes is not None:
         confusion = True            # (a zeroed matrix, made once the arguments have passed their checks)
-    counts, ali_len, ali, confusion = ops.edit_align(hyp, hyp_len, ref, ref_len, ignore, 1 if n_classes is None else n_classes, confusion,
-                                                     want_ali)
+    counts, ali_len, ali, confusion = toolops.edit_align(hyp, hyp_len, ref, ref_len, ignore, 1 if n_classes is None else n_classes, confusion,
+                                                         want_ali)
     if single:
         counts, ali_len = counts[:, 0], ali_len[:, 0]
         ali = None if ali is None else ali[:, 0]
@@ -271,11 +271,11 @@ def dtw_pairs(feat, item_start, item_len, pair_a, pair_b, metric='angular', want
     if not torch.is_tensor(feat) or not feat.is_cuda:
         raise ValueError('dtw_pairs: feat must be a (n_rows, D) float32 GPU tensor (got %s)' % (type(feat).__name__ if not torch.is_tensor(feat) else feat.device))
     if max_len is None:
-        max_len = ops.ABX_MAX_LEN
+        max_len = toolops.ABX_MAX_LEN
         if not (torch.is_tensor(item_len) and item_len.is_cuda) and len(item_len):
-            max_len = min(max(int(max(int(v) for v in item_len)), 1), ops.ABX_MAX_LEN)
+            max_len = min(max(int(max(int(v) for v in item_len)), 1), toolops.ABX_MAX_LEN)
     tabs = [_abx_table('dtw_pairs', n, v, feat.device) for n, v in (('item_start', item_start), ('item_len', item_len), ('pair_a', pair_a), ('pair_b', pair_b))]
-    return ops.dtw_pairs(feat, tabs[0], tabs[1], tabs[2], tabs[3], metric, max_len, want_cost)
+    return toolops.dtw_pairs(feat, tabs[0], tabs[1], tabs[2], tabs[3], metric, max_len, want_cost)
 
 
 AbxResult = collections.namedtuple('AbxResult', 'blocks block_cell block_a block_b counts table score pairs keep')
@@ -302,14 +302,14 @@ def abx(feat, item_start, item_len, label, cell, metric='angular', max_items=50,
     if len(pl.blocks) == 0:
         return AbxResult(pl.blocks, pl.block_cell, pl.block_a, pl.block_b, np.zeros((0, 4), np.int64), [], float('nan'), 0, pl.keep)
     dev = feat.device
-    max_len = int(min(max(length[pl.keep].max(), 1), ops.ABX_MAX_LEN))
+    max_len = int(min(max(length[pl.keep].max(), 1), toolops.ABX_MAX_LEN))
     tabs = torch.from_numpy(np.concatenate([start, length]).astype(np.int32)).to(dev)
     pairs = torch.from_numpy(np.concatenate([pl.pair_a, pl.pair_b])).to(dev)
     n, P = len(start), len(pl.pair_a)
-    dist = ops.dtw_pairs(feat, tabs[:n], tabs[n:], pairs[:P], pairs[P:], metric, max_len)
+    dist = toolops.dtw_pairs(feat, tabs[:n], tabs[n:], pairs[:P], pairs[P:], metric, max_len)
     dmat = torch.zeros(pl.dmat_len, device=dev, dtype=torch.float32)
     dmat[torch.from_numpy(np.concatenate([pl.pos_ab, pl.pos_ba])).to(dev)] = torch.cat([dist, dist])        # (the one mirrored store)
-    counts = ops.abx_count(dmat, torch.from_numpy(pl.blocks).to(dev)).cpu().numpy()                          # (the one host read)
+    counts = toolops.abx_count(dmat, torch.from_numpy(pl.blocks).to(dev)).cpu().numpy()                          # (the one host read)
     agg = A.aggregate(pl.block_a, pl.block_b, counts)
     return AbxResult(pl.blocks, pl.block_cell, pl.block_a, pl.block_b, counts, agg.table, agg.score, P, pl.keep)
 
@@ -344,12 +344,12 @@ def stoi(clean, degraded, sample_rate, want_parts=False):
     time-aligned -- the measure correlates short-time envelopes frame by frame and searches no delay itself: `align_pairs` finds a
     constant shift and returns the two overlaps in the form this function takes.  sample_rate: the rate
     of both sides; anything but 10000 Hz goes through audio.resample first (the project's Hann-windowed sinc, so the values differ
-    slightly from pystoi's, which emulates Octave's resample).  More than ops.STOI_MAX_BATCH pairs are issued in chunks of it.
+    slightly from pystoi's, which emulates Octave's resample).  More than toolops.STOI_MAX_BATCH pairs are issued in chunks of it.
     -> StoiResult of device tensors in the caller's order: score (B, 2) float32 = (STOI, ESTOI); counts (B, 4) int32 = (frames, kept
     frames, band frames M, segments S); with want_parts energy (B, F_pad), kept (B, F_pad) int32 (-1 past the kept ones) and bands
-    (B, 2, 15, F_pad) (0 past M), else None.  A pair with S = 0 (shorter than 30 band frames) scores ops.STOI_SENTINEL twice; a
+    (B, 2, 15, F_pad) (0 past M), else None.  A pair with S = 0 (shorter than 30 band frames) scores toolops.STOI_SENTINEL twice; a
     non-finite clean signal scores NaN.  A pair's figures depend on that pair alone and are bitwise repeatable.  No host read.
-    Unequal lengths, an empty input, a rate the resampler refuses or a signal past ops.STOI_MAX_LEN samples at 10 kHz raise ValueError
+    Unequal lengths, an empty input, a rate the resampler refuses or a signal past toolops.STOI_MAX_LEN samples at 10 kHz raise ValueError
     before the device is touched."""
     import numpy as np
     from . import audio
@@ -364,21 +364,21 @@ def stoi(clean, degraded, sample_rate, want_parts=False):
         raise ValueError('stoi: pair %d has %d clean and %d processed samples: the two sides must be equally long' % (i, lx[i], ly[i]))
     if not np.array_equal(ox, oy):
         raise ValueError('stoi: the two WaveBatches are ordered differently')
-    audio.resample_table(sample_rate, ops.STOI_FS)                       # (the resampler's refusals, raised here)
-    longest = audio.resampled_len(int(lx.max()), sample_rate, ops.STOI_FS)
-    if longest > ops.STOI_MAX_LEN:
-        raise ValueError('stoi: the longest signal has %d samples at %d Hz, above the limit of %d' % (longest, ops.STOI_FS, ops.STOI_MAX_LEN))
-    if int(sample_rate) != ops.STOI_FS:
-        xb, yb = audio.resample(xb, int(sample_rate), ops.STOI_FS), audio.resample(yb, int(sample_rate), ops.STOI_FS)
+    audio.resample_table(sample_rate, toolops.STOI_FS)                       # (the resampler's refusals, raised here)
+    longest = audio.resampled_len(int(lx.max()), sample_rate, toolops.STOI_FS)
+    if longest > toolops.STOI_MAX_LEN:
+        raise ValueError('stoi: the longest signal has %d samples at %d Hz, above the limit of %d' % (longest, toolops.STOI_FS, toolops.STOI_MAX_LEN))
+    if int(sample_rate) != toolops.STOI_FS:
+        xb, yb = audio.resample(xb, int(sample_rate), toolops.STOI_FS), audio.resample(yb, int(sample_rate), toolops.STOI_FS)
     order, lens, off = np.asarray(xb.order), xb.lens, xb.offsets         # (equal lengths sort alike: yb's are the same)
     dev = xb.device or yb.device or audio._device()
     x, y = xb.packed(dev), yb.packed(dev)
     if not np.array_equal(off, yb.offsets) or x.numel() != y.numel():    # (two windows of differently laid out buffers)
         raise ValueError('stoi: the two WaveBatches are laid out differently')
     B = len(lens)
-    F_pad = max(1, max(ops.stoi_frames(v) for v in lens))             # one width for every chunk: the parts concatenate
-    outs = [ops.stoi_batch(x, y, off[b0:b0 + ops.STOI_MAX_BATCH], lens[b0:b0 + ops.STOI_MAX_BATCH], F_pad, want_parts)
-            for b0 in range(0, B, ops.STOI_MAX_BATCH)]
+    F_pad = max(1, max(toolops.stoi_frames(v) for v in lens))             # one width for every chunk: the parts concatenate
+    outs = [toolops.stoi_batch(x, y, off[b0:b0 + toolops.STOI_MAX_BATCH], lens[b0:b0 + toolops.STOI_MAX_BATCH], F_pad, want_parts)
+            for b0 in range(0, B, toolops.STOI_MAX_BATCH)]
     inv = torch.from_numpy(xb.inverse()).to(dev)                         # row i of the result is the caller's pair i
     return StoiResult(*[torch.cat(parts).index_select(0, inv) if parts[0] is not None else None for parts in zip(*outs)])
 
@@ -395,16 +395,16 @@ def _pair_sides(what, clean, degraded):
     if len(xb.lens) != len(yb.lens):
         raise ValueError('%s: %d clean and %d processed signals: one of each per pair' % (what, len(xb.lens), len(yb.lens)))
     longest = int(max(xb.lens.max(), yb.lens.max()))
-    if longest > ops.XCORR_MAX_LEN:
-        raise ValueError('%s: the longest signal has %d samples, above the limit of %d' % (what, longest, ops.XCORR_MAX_LEN))
+    if longest > toolops.XCORR_MAX_LEN:
+        raise ValueError('%s: the longest signal has %d samples, above the limit of %d' % (what, longest, toolops.XCORR_MAX_LEN))
     ix, iy = xb.inverse(), yb.inverse()
     return xb, yb, xb.offsets[ix], xb.lens[ix], yb.offsets[iy], yb.lens[iy]
 
 
 def _check_lag(what, max_lag):
     import numpy as np
-    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag <= ops.XCORR_MAX_LAG:
-        raise ValueError('%s: max_lag must be an integer in [0, %d] (got %r)' % (what, ops.XCORR_MAX_LAG, max_lag))
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag <= toolops.XCORR_MAX_LAG:
+        raise ValueError('%s: max_lag must be an integer in [0, %d] (got %r)' % (what, toolops.XCORR_MAX_LAG, max_lag))
     return int(max_lag)
 
 
@@ -414,7 +414,7 @@ def delay(clean, degraded, max_lag, want_corr=False):
     include/semitts.h).  A positive delay: the processed signal is late.  clean, degraded: lists of 1-D waveforms (tensors or arrays;
     int16 PCM counts as x / 32768) or WaveBatches; the two lengths of a pair may differ.  The search is in float64 and exact on 16-bit
     PCM input, so the decision has no tolerance there; ties go to the smallest |d|, then to the non-negative lag.  More than
-    ops.XCORR_MAX_BATCH pairs are issued in chunks of it.
+    toolops.XCORR_MAX_BATCH pairs are issued in chunks of it.
     -> DelayResult of device tensors in the caller's order: delay (B,) int32; coef (B,) float32 = r[d*] / sqrt(sum x^2 sum y^2); corr
     (B, 2 max_lag + 1) float64 with want_corr (column d + max_lag), else None.  A NaN anywhere in r: delay 0, coef NaN.  A pair's
     figures depend on that pair alone and are bitwise repeatable.  No host read.  Every refusal raises ValueError before the device is
@@ -424,8 +424,8 @@ def delay(clean, degraded, max_lag, want_corr=False):
     xb, yb, xo, xl, yo, yl = _pair_sides('delay', clean, degraded)
     dev = xb.device or yb.device or audio._device()
     x, y = xb.packed(dev), yb.packed(dev)
-    M = ops.XCORR_MAX_BATCH
-    outs = [ops.xcorr_delay(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], D, want_corr) for b0 in range(0, len(xl), M)]
+    M = toolops.XCORR_MAX_BATCH
+    outs = [toolops.xcorr_delay(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], D, want_corr) for b0 in range(0, len(xl), M)]
     return DelayResult(*[torch.cat(parts) if parts[0] is not None else None for parts in zip(*outs)])
 
 
@@ -453,8 +453,8 @@ def si_sdr(clean, degraded, delay=None, zero_mean=True):
     x, y = xb.packed(dev), yb.packed(dev)
     if delay is not None:
         delay = delay.contiguous() if torch.is_tensor(delay) else torch.full((B,), int(delay), device=dev, dtype=torch.int32)
-    M = ops.XCORR_MAX_BATCH
-    outs = [ops.sisdr_batch(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], None if delay is None else delay[b0:b0 + M], zero_mean)
+    M = toolops.XCORR_MAX_BATCH
+    outs = [toolops.sisdr_batch(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], None if delay is None else delay[b0:b0 + M], zero_mean)
             for b0 in range(0, B, M)]
     return SiSdrResult(*[torch.cat(parts) for parts in zip(*outs)])
 
@@ -478,8 +478,8 @@ def align_pairs(clean, degraded, max_lag):
     xb, yb, xo, xl, yo, yl = _pair_sides('align_pairs', clean, degraded)
     dev = xb.device or yb.device or audio._device()
     x, y = xb.packed(dev), yb.packed(dev)
-    M, B = ops.XCORR_MAX_BATCH, len(xl)
-    outs = [ops.xcorr_delay(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], D) for b0 in range(0, B, M)]
+    M, B = toolops.XCORR_MAX_BATCH, len(xl)
+    outs = [toolops.xcorr_delay(x, xo[b0:b0 + M], xl[b0:b0 + M], y, yo[b0:b0 + M], yl[b0:b0 + M], D) for b0 in range(0, B, M)]
     dl, coef = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
     d_host = dl.cpu().numpy()                                            # (the one host read)
     spans = [overlap(xl[i], yl[i], d_host[i]) for i in range(B)]
@@ -494,6 +494,6 @@ def align_pairs(clean, degraded, max_lag):
     for buf, so in ((x, xo + np.array([s[0] for s in spans], np.int64)), (y, yo + np.array([s[1] for s in spans], np.int64))):
         out = torch.empty(int(n.sum()), device=dev, dtype=torch.float32)
         for b0 in range(0, B, M):
-            ops.wave_gather(buf, so[b0:b0 + M], out, off[b0:b0 + M], n[b0:b0 + M])
+            toolops.wave_gather(buf, so[b0:b0 + M], out, off[b0:b0 + M], n[b0:b0 + M])
         sides.append(audio.WaveBatch.from_packed(out, n, order))
     return sides[0], sides[1], dl, coef

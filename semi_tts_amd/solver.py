@@ -15,7 +15,7 @@ import time
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, toolops
 from .vqvae import VQVAE, FRAME_PHN_RATIO, INFERENCE_MARGIN_FRAMES, SYNTH_MAX_FRAMES_PER_PHONE
 
 
@@ -392,9 +392,9 @@ class Synthesiser(BaseSolver):
         r = int(self.config['model']['decoder']['decoder']['n_frames_per_step'])
         for f, t in zip(self.files, self.transcripts):
             steps = synth_frames(len(t), r, self.max_frames_per_phone) // r
-            if len(t) + 1 > ops.AE_MAX_L or steps > ops.AE_MAX_S:
+            if len(t) + 1 > toolops.AE_MAX_L or steps > toolops.AE_MAX_S:
                 raise ValueError('--synth-phn-dir: %s: %d phones decode %d steps; the end-of-speech kernel takes at most %d phones and %d steps'
-                                 % (f, len(t), steps, ops.AE_MAX_L - 1, ops.AE_MAX_S))
+                                 % (f, len(t), steps, toolops.AE_MAX_L - 1, toolops.AE_MAX_S))
         self.audio_converter = load_audio_transform(**self.config['data']['audio'])
         return self
 

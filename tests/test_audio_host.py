@@ -57,7 +57,7 @@ def test_argument_checks_fire_before_the_device(monkeypatch):
 
     def no_device(*a, **k):
         raise AssertionError('reached the device')
-    monkeypatch.setattr(ops, 'griffin_lim', no_device)
+    monkeypatch.setattr(audio.toolops, 'griffin_lim', no_device)
     monkeypatch.setattr(audio, '_device', no_device)
     conv = audio.load_audio_transform(**AUDIO_CFG)
     with pytest.raises(ValueError, match='too few'):

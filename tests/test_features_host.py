@@ -92,7 +92,7 @@ def test_feature_argument_checks_fire_before_the_device(monkeypatch, tmp_path):
 
     def no_device(*a, **k):
         raise AssertionError('reached the device')
-    monkeypatch.setattr(ops, 'audio_features', no_device)
+    monkeypatch.setattr(audio.toolops, 'audio_features', no_device)
     monkeypatch.setattr(audio, '_device', no_device)
     conv = audio.load_audio_transform(**AUDIO_CFG)
     x = torch.rand(30000) - 0.5

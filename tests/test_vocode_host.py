@@ -72,7 +72,7 @@ def _no_device(monkeypatch):
     def no_device(*a, **k):
         raise AssertionError('reached the device')
     for name in ('griffin_lim', 'griffin_lim_batch', 'mel_to_linear'):
-        monkeypatch.setattr(ops, name, no_device)
+        monkeypatch.setattr(audio.toolops, name, no_device)
     monkeypatch.setattr(audio, '_device', no_device)
     return audio
 
@@ -157,7 +157,7 @@ def test_vocode_batch_draws_phases_as_the_file_loop(monkeypatch, kind, D):
     def fake(feat, phases, n_fft, hop, win, **kw):
         seen.update(phases=phases.clone(), frames=kw['frames'].clone(), feat=feat.clone(), kw=kw)
         return torch.zeros(feat.shape[0], hop * (feat.shape[1] - 1))
-    monkeypatch.setattr(ops, 'griffin_lim_batch', fake)
+    monkeypatch.setattr(audio.toolops, 'griffin_lim_batch', fake)
     monkeypatch.setattr(audio, '_device', lambda: torch.device('cpu'))
     conv = audio.load_audio_transform(**AUDIO_CFG)
     monkeypatch.setattr(conv, 'mel_basis', lambda device=None: torch.zeros(80, 1025))
