@@ -480,55 +480,54 @@ int st_gemm_wgrad_db(const float* dC, int lddc, int dcoff, const float* A, int l
 /* out(n) (+)= sum_m X(m, xoff+n) [* Y(m, yoff+n)]      (bias gradients, AdaIN statistics gradients) */
 int st_colsum(const float* X, int ldx, int xoff, const float* Y, int ldy, int yoff, int M, int N,
               float* out, int accumulate, float* ws, void* stream);
-/* scratch of the row-split column reductions st_bn_stats / st_colsum / st_bn_bwd (M rows, N columns) */
+/* scratch of the row-split column reductions st_bn_stats / st_colsum / st_bn_bwd_reduce (M rows, N columns) */
 size_t st_colreduce_workspace_floats(int M, int N);
 /* dpre = dout * mask * act'(out)   (out = the activated forward value; mask may be NULL) */
 int st_act_bwd(const float* dout, int ldd, const float* out, int ldo, int act, const float* mask, int ldm,
                float* dpre, int ldp, int M, int N, void* stream);
-/* BatchNorm backward with batch statistics, y = act((x - mean)/sqrt(var+eps)*w + b):
- * dx = w/sigma * (dyb - mean(dyb) - xhat * mean(dyb*xhat)), dw (+)= sum dyb*xhat, db (+)= sum dyb,
- * dyb = dy * act'(y).  ws: st_colreduce_workspace_floats(M, N) floats. */
-int st_bn_bwd(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-              const float* x, int ldx, int xoff, const float* mean, const float* var, const float* w, float eps,
-              int M, int N, float* dx, int lddx, int dxoff, float* dw, float* db, int accumulate, float* ws, void* stream);
-/* The two halves of st_bn_bwd, for data-parallel training with synchronised statistics: the caller all-reduces
- * s (2N floats: sum dyb, sum dyb*xhat over the local rows) across ranks between the calls and passes the global row
- * count as Mstat (mean / var must then be the global batch statistics too).  ws as for st_bn_bwd. */
-int st_bn_bwd_reduce(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                     const float* x, int ldx, int xoff, const float* mean, const float* var, float eps,
-                     int M, int N, float* s, float* ws, void* stream);
-int st_bn_bwd_apply(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                    const float* x, int ldx, int xoff, const float* mean, const float* var, const float* w, float eps,
-                    int M, int N, const float* s, int Mstat, float* dx, int lddx, int dxoff, void* stream);
+/* BatchNorm backward with batch statistics, y = act((x - mean)/sqrt(var+eps)*w + b), in two halves so that a data-parallel caller can
+ * all-reduce the two sums in between (SyncBN):
+ *   reduce: s[0:N] = sum_rows dyb (= d bias), s[N:2N] = sum_rows dyb * xhat (= d weight) over the M local rows, dyb = dy [* mask] * act'(y);
+ *           ws: st_colreduce_workspace_floats(M, N) floats.
+ *   apply:  dx = w/sigma * (dyb - s1/Mstat - xhat * s2/Mstat) [, dres = dy * mask].  Mstat = the rows behind mean / var / s; under SyncBN
+ *           the caller all-reduces s across ranks between the calls and passes inv_total (mean / var are then the global batch's too).
+ * Both halves read the same job.  Both refuse (-22, before any launch) a NULL job, NULL dy / x / mean / var / s, M <= 0, N <= 0, and
+ * act != ST_ACT_NONE with NULL y; reduce also NULL ws; apply also NULL dx, and Mstat < M without inv_total. */
+typedef struct st_bn_bwd_job {
+    const float* dy;   int ldd;        /* (M, N) rows; a column slice comes as pointer + stride */
+    const float* y;    int ldy;        /* act(BN(x)) kept by the forward; NULL iff act == ST_ACT_NONE */
+    int act;
+    const float* x;    int ldx;
+    const float* mean; const float* var; const float* w;   /* w NULL = 1 */
+    float eps;
+    int M, N;
+    const float* mask; int ldm;        /* NULL, or dy is multiplied by it on the way in */
+    float* s;                          /* (2N): reduce writes (sum dyb, sum dyb*xhat); apply reads them */
+    int Mstat;                         /* apply: rows behind mean/var/s; ignored when inv_total is given */
+    const float* inv_total;            /* apply: NULL, or device scalar 1/(global rows) of st_bn_sync_merge */
+    float* dx;   int lddx;             /* apply: out */
+    float* dres; int lddr;             /* apply: NULL, or out = dy * mask (gradient of the residual input) */
+} st_bn_bwd_job;
+int st_bn_bwd_reduce(const st_bn_bwd_job* job, float* ws, void* stream);
+int st_bn_bwd_apply(const st_bn_bwd_job* job, void* stream);
 /* ConvLayer's tail in training (ref: src/module.py:641-646: BatchNorm -> activation -> (+ x) -> dropout) as ONE launch behind the conv:
  * Tact (M, N) = act(BatchNorm(X)) with the given batch statistics, kept for the backward (NULL: not written), Y (M, N) = (Tact + res) * mask
  * (res, mask: NULL = absent).  Contiguous rows of N floats, N % 4 == 0, 16-byte aligned.  Replaces nn.BatchNorm1d + torch.tanh + `+` +
  * nn.Dropout of the reference (one launch instead of BatchNorm apply, add, bernoulli_, div_, mul). */
 int st_bn_norm_res_mask_fwd(const float* X, float* Tact, float* Y, int M, int N, const float* mean, const float* var,
                             const float* w, const float* b, float eps, int act, const float* res, const float* mask, void* stream);
-/* The backward of that tail in the two halves of st_bn_bwd_reduce / st_bn_bwd_apply: dy is multiplied by `mask` on the way in, `y` is the
- * kept Tact; the apply half also writes dres (M, N) = dy * mask, the gradient of the residual input (NULL: none); inv_total: NULL, or the
- * device scalar of st_bn_sync_merge (s then holds the sums over all ranks). */
-int st_bn_bwd_reduce_masked(const float* dy, int ldd, const float* mask, int ldm, const float* y, int ldy, int act,
-                            const float* x, int ldx, const float* mean, const float* var, float eps,
-                            int M, int N, float* s, float* ws, void* stream);
-int st_bn_bwd_apply_masked(const float* dy, int ldd, const float* mask, int ldm, const float* y, int ldy, int act,
-                           const float* x, int ldx, const float* mean, const float* var, const float* w, float eps,
-                           int M, int N, const float* s, int Mstat, const float* inv_total, float* dx, int lddx,
-                           float* dres, int lddr, void* stream);
+/* The backward of that tail is st_bn_bwd_reduce / st_bn_bwd_apply with the job's `mask` (dy is multiplied by it on the way in, no launch
+ * of its own), `y` = the kept Tact, and `dres` (the gradient of the residual input; NULL: no residual). */
 /* SyncBN (the data-parallel form of the BatchNorm1d layers above; the reference trains on one device, ref: src/module.py:434-455,
  * so this is the path's own multi-GPU extension) with the row counts kept on the device:
  *   st_bn_stats_record   rec (2N + 1) = (mean[N], M2[N], row count) of this rank's rows -- what the ranks all-gather;
  *   st_bn_sync_merge     the gathered records (world, 2N + 1) -> mean / biased variance of the global batch, merged in rank order
  *                        (identical on every rank), running statistics updated with the unbiased variance over the global count,
  *                        *inv_total_out = 1 / (global row count);
- *   st_bn_bwd_apply_sync st_bn_bwd_apply with s summed over all ranks and divided by the global count read from *inv_total. */
+ *   st_bn_bwd_apply      with the job's inv_total: s summed over all ranks and divided by the global count read from *inv_total. */
 int st_bn_stats_record(const float* X, int ldx, int coff, int M, int N, float* rec, long long* batches_tracked, float* ws, void* stream);
 int st_bn_sync_merge(const float* rec, int world, int N, float* mean_out, float* var_out, float* run_mean, float* run_var,
                      float momentum, float* inv_total_out, void* stream);
-int st_bn_bwd_apply_sync(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                         const float* x, int ldx, int xoff, const float* mean, const float* var, const float* w, float eps,
-                         int M, int N, const float* s, const float* inv_total, float* dx, int lddx, int dxoff, void* stream);
 /* Highway combine y = H*T + x*(1-T) and its backward dH = dy*T, dT = dy*(H-x), dx_direct = dy*(1-T)
  * ref: src/module.py:551-554 */
 int st_highway_fwd(const float* H, const float* Tgate, const float* x, float* y, size_t total, void* stream);

@@ -48,6 +48,13 @@ class StBnBankSeg(C.Structure):
                 ('mean', C.c_void_p), ('var', C.c_void_p), ('dx', C.c_void_p), ('lddx', C.c_int), ('sums', C.c_void_p)]
 
 
+class StBnBwdJob(C.Structure):
+    _fields_ = [('dy', C.c_void_p), ('ldd', C.c_int), ('y', C.c_void_p), ('ldy', C.c_int), ('act', C.c_int), ('x', C.c_void_p), ('ldx', C.c_int),
+                ('mean', C.c_void_p), ('var', C.c_void_p), ('w', C.c_void_p), ('eps', C.c_float), ('M', C.c_int), ('N', C.c_int),
+                ('mask', C.c_void_p), ('ldm', C.c_int), ('s', C.c_void_p), ('Mstat', C.c_int), ('inv_total', C.c_void_p),
+                ('dx', C.c_void_p), ('lddx', C.c_int), ('dres', C.c_void_p), ('lddr', C.c_int)]
+
+
 class StDecoderWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         'prenet_w0', 'prenet_w1', 'q_w_ih', 'q_w_hh', 'q_b_ih', 'q_b_hh',
@@ -404,15 +411,11 @@ SIGNATURES = {
     'st_gemm_wgrad_split': [P, I, I, P, I, P, I, P, P, P, P, I, I, I, I, P],
     'st_colsum': [P, I, I, P, I, I, I, I, P, I, P, P],
     'st_act_bwd': [P, I, P, I, I, P, I, P, I, I, I, P],
-    'st_bn_bwd': [P, I, I, P, I, I, I, P, I, I, P, P, P, F, I, I, P, I, I, P, P, I, P, P],
-    'st_bn_bwd_reduce': [P, I, I, P, I, I, I, P, I, I, P, P, F, I, I, P, P, P],
+    'st_bn_bwd_reduce': [C.POINTER(StBnBwdJob), P, P],
     'st_bn_norm_res_mask_fwd': [P, P, P, I, I, P, P, P, P, F, I, P, P, P],
-    'st_bn_bwd_reduce_masked': [P, I, P, I, P, I, I, P, I, P, P, F, I, I, P, P, P],
-    'st_bn_bwd_apply_masked': [P, I, P, I, P, I, I, P, I, P, P, P, F, I, I, P, I, P, P, I, P, I, P],
-    'st_bn_bwd_apply': [P, I, I, P, I, I, I, P, I, I, P, P, P, F, I, I, P, I, P, I, I, P],
+    'st_bn_bwd_apply': [C.POINTER(StBnBwdJob), P],
     'st_bn_stats_record': [P, I, I, I, I, P, P, P, P],
     'st_bn_sync_merge': [P, I, I, P, P, P, P, F, P, P],
-    'st_bn_bwd_apply_sync': [P, I, I, P, I, I, I, P, I, I, P, P, P, F, I, I, P, P, P, I, I, P],
     'st_highway_fwd': [P, P, P, P, Z, P],
     'st_bn_bank_workspace_floats': [I, I, I],
     'st_bn_bank_fwd': [C.POINTER(StBnBankSeg), I, I, I, P, I, I, P, P],

@@ -135,6 +135,35 @@ class _ConvFn(Function):
         return dx, dw, db, dres, None, None, None, None, None, None
 
 
+def _bn_batch_stats(x2, N, run_mean, run_var, momentum, tracked):
+    """statistics of a training-mode BatchNorm1d over the rows of x2 (running statistics and `tracked` updated in place)
+    -> (mean, var, inv_total); inv_total is None unless parallel.sync_batchnorm is active, and then 1 / the GLOBAL row count"""
+    from . import parallel
+    if not parallel.sync_bn_active():
+        return ops.bn_stats(x2, 0, N, run_mean, run_var, momentum, tracked) + (None,)
+    # ONE collective: every rank's (mean, M2, count) record, written by the statistics launch itself and merged exactly and
+    # identically on every rank in rank order (Chan et al.) by one more launch.  The counts stay on the device -- no host
+    # round trip, and shards of different sizes (a ragged last batch, B % world != 0, different T per rank in the speech
+    # encoder) are weighted by their true row counts.
+    parallel._COUNTS['syncbn_fwd'] += 1
+    rec = parallel.all_gather_(ops.bn_stats_record(x2, 0, N, tracked))      # (world, 2N + 1)
+    return ops.bn_sync_merge(rec, N, run_mean, run_var, momentum)
+
+
+def _bn_bwd_halves(dy2, y2, act, x2, mean, var, weight, eps, inv_total, mask2d=None, want_dres=None):
+    """the BatchNorm backward behind _bn_batch_stats -> (dx, dw, db), or ((dx, dres), dw, db) when want_dres is not None (ops.bn_bwd_apply).
+    inv_total is not None (SyncBN): the two sums are all-reduced between the halves and divided by the GLOBAL row count"""
+    from . import parallel
+    M, N = x2.shape
+    s = ops.bn_bwd_reduce(dy2, y2, act, x2, mean, var, eps, mask2d=mask2d)
+    db, dw = s[:N], s[N:]                           # parameter gradients: local sums (averaged over ranks later)
+    if inv_total is not None:
+        db, dw = db.clone(), dw.clone()             # (s is all-reduced in place below; otherwise the views are handed out as they are)
+        parallel._COUNTS['syncbn_bwd'] += 1
+        parallel.all_reduce_sum_(s)
+    return ops.bn_bwd_apply(dy2, y2, act, x2, mean, var, weight, eps, s, M, inv_total, mask2d=mask2d, want_dres=want_dres), dw, db
+
+
 class _ConvLayerFn(Function):
     """ConvLayer.forward in training (src/module.py:638-648) as ONE autograd node: Conv1d (+ bias) -> BatchNorm1d over the batch ->
     activation -> (+ x) -> dropout mask.  Forward: the conv product, the statistics (two launches), ONE launch for normalisation +
@@ -144,41 +173,25 @@ class _ConvLayerFn(Function):
 
     @staticmethod
     def forward(ctx, x, w, b, bn_w, bn_b, run_mean, run_var, tracked, mask, pad, stride, act, residual, eps, momentum):
-        from . import parallel
         x = x.contiguous()
         y = ops.gemm(x, w, pad=pad, stride=stride, bias=b)
         N = y.shape[-1]
         y2 = _rows(y)
-        M = y2.shape[0]
-        sync = parallel.sync_bn_active()
-        inv_total = None
-        if sync:
-            parallel._COUNTS['syncbn_fwd'] += 1
-            rec = parallel.all_gather_(ops.bn_stats_record(y2, 0, N, tracked))
-            mean, var, inv_total = ops.bn_sync_merge(rec, N, run_mean, run_var, momentum)
-        else:
-            mean, var = ops.bn_stats(y2, 0, N, run_mean, run_var, momentum, tracked)
+        mean, var, inv_total = _bn_batch_stats(y2, N, run_mean, run_var, momentum, tracked)
         t, out = ops.bn_norm_res_mask(y2, mean, var, bn_w, bn_b, eps, act, _rows(x) if residual else None,
                                       _rows(mask) if mask is not None else None, want_t=act is not None)
         ctx.save_for_backward(x, w, b, y, t, mean, var, bn_w, mask, inv_total)
-        ctx.cfg = (pad, stride, act, residual, eps, M, sync)
+        ctx.cfg = (pad, stride, act, residual, eps)
         return out.view(y.shape)
 
     @staticmethod
     def backward(ctx, dout):
-        from . import parallel
         x, w, b, y, t, mean, var, bn_w, mask, inv_total = ctx.saved_tensors
-        pad, stride, act, residual, eps, M, sync = ctx.cfg
-        d2, y2 = _rows_strided(dout), _rows(y)
+        pad, stride, act, residual, eps = ctx.cfg
+        y2 = _rows(y)
         N = y2.shape[1]
-        m2 = _rows(mask) if mask is not None else None
-        s = ops.bn_bwd_reduce(d2, t, act, y2, mean, var, eps, mask2d=m2)
-        dbn_b, dbn_w = s[:N], s[N:]
-        if sync:
-            dbn_b, dbn_w = dbn_b.clone(), dbn_w.clone()
-            parallel._COUNTS['syncbn_bwd'] += 1
-            parallel.all_reduce_sum_(s)
-        dpre, dres = ops.bn_bwd_apply(d2, t, act, y2, mean, var, bn_w, eps, s, M, inv_total, mask2d=m2, want_dres=residual)
+        (dpre, dres), dbn_w, dbn_b = _bn_bwd_halves(_rows_strided(dout), t, act, y2, mean, var, bn_w, eps, inv_total,
+                                                    mask2d=_rows(mask) if mask is not None else None, want_dres=residual)
         Bn, Tin, Cin = x.shape
         To = y.shape[1]
         KT = w.shape[2]
@@ -424,42 +437,21 @@ class _BnTrainFn(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, run_mean, run_var, eps, momentum, act, batches_tracked=None):
-        from . import parallel
         x = x.contiguous()
         N = x.shape[-1]
         x2 = _rows(x)
-        M = x2.shape[0]
-        sync = parallel.sync_bn_active()
-        inv_total = None
-        if sync:
-            # ONE collective: every rank's (mean, M2, count) record, written by the statistics launch itself and merged exactly and
-            # identically on every rank in rank order (Chan et al.) by one more launch.  The counts stay on the device -- no host
-            # round trip, and shards of different sizes (a ragged last batch, B % world != 0, different T per rank in the speech
-            # encoder) are weighted by their true row counts.
-            parallel._COUNTS['syncbn_fwd'] += 1
-            rec = parallel.all_gather_(ops.bn_stats_record(x2, 0, N, batches_tracked))      # (world, 2N + 1)
-            mean, var, inv_total = ops.bn_sync_merge(rec, N, run_mean, run_var, momentum)   # inv_total: 1 / the GLOBAL row count
-        else:
-            mean, var = ops.bn_stats(x2, 0, N, run_mean, run_var, momentum, batches_tracked)
+        mean, var, inv_total = _bn_batch_stats(x2, N, run_mean, run_var, momentum, batches_tracked)
         y = ops.bn_norm(x2, 0, N, mean, var, weight, bias, eps, act).view(x.shape)
         ctx.save_for_backward(x, y if act is not None else None, mean, var, weight, inv_total)
-        ctx.cfg = (eps, act, M, sync)
+        ctx.cfg = (eps, act)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        from . import parallel
         x, y, mean, var, weight, inv_total = ctx.saved_tensors
-        eps, act, M, sync = ctx.cfg
+        eps, act = ctx.cfg
         dy2, y2, x2 = _rows_strided(dy), _rows(y) if y is not None else None, _rows(x)      # (dy: often a column slice of a cat's gradient)
-        N = x2.shape[1]
-        s = ops.bn_bwd_reduce(dy2, y2, act, x2, mean, var, eps)
-        db, dw = s[:N], s[N:]                           # parameter gradients: local sums (averaged over ranks later)
-        if sync:
-            db, dw = db.clone(), dw.clone()             # (s is all-reduced in place below; otherwise the views are handed out as they are)
-            parallel._COUNTS['syncbn_bwd'] += 1
-            parallel.all_reduce_sum_(s)
-        dx = ops.bn_bwd_apply(dy2, y2, act, x2, mean, var, weight, eps, s, M, inv_total)     # sync: the sums / the GLOBAL row count
+        dx, dw, db = _bn_bwd_halves(dy2, y2, act, x2, mean, var, weight, eps, inv_total)
         return dx.view(x.shape), dw, db, None, None, None, None, None, None
 
 
@@ -493,7 +485,7 @@ class _BnTrainGroupFn(Function):
                 stats.append(ops.bn_sync_merge(per[i], N, tens[6 * i + 3], tens[6 * i + 4], scal[2 * i + 1]))
         else:
             for i in range(n):
-                stats.append(ops.bn_stats(_rows(xs[i]), 0, N, tens[6 * i + 3], tens[6 * i + 4], scal[2 * i + 1], tens[6 * i + 5]) + (None,))
+                stats.append(_bn_batch_stats(_rows(xs[i]), N, tens[6 * i + 3], tens[6 * i + 4], scal[2 * i + 1], tens[6 * i + 5]))
         ys, saved = [], []
         for i in range(n):
             mean, var, inv_total = stats[i]

@@ -1107,6 +1107,20 @@ extern "C" int st_gemm_fwd(const float* A, int lda, const float* W, float* C, in
     return 0;
 }
 
+// the two launches of the batch statistics: chunk-local (mean, M2), then their merge into out0 / out1 -- (mean, biased variance) with
+// the running update, or record = 1: (mean, M2) and the row count behind them
+static int bn_stats_launch(const float* X, int ldx, int coff, int M, int N, float* out0, float* out1, float* run_mean, float* run_var,
+                           float momentum, long long* batches_tracked, int record, float* ws, void* stream) {
+    const int chunks = st_colreduce_chunks(M);
+    const int rpc = (M + chunks - 1) / chunks;
+    hipLaunchKernelGGL(bn_stats_chunk_kernel, dim3((N + 63) / 64, chunks), dim3(256), 0, (hipStream_t)stream, X, ldx, coff, M, N, rpc, ws);
+    ST_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream,
+                       ws, chunks, rpc, M, N, out0, out1, run_mean, run_var, momentum, batches_tracked, record);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int st_bn_stats(const float* X, int ldx, int coff, int M, int N, float* mean_out, float* var_out,
                            float* run_mean, float* run_var, float momentum, long long* batches_tracked, float* ws, void* stream) {
     (void)hipGetLastError();  // drop stale errors left by other HIP users of this thread
@@ -1114,15 +1128,8 @@ extern "C" int st_bn_stats(const float* X, int ldx, int coff, int M, int N, floa
     ST_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr), "st_bn_stats: run_mean/run_var must both be given");
     ST_CHECK_ARG(ws, "st_bn_stats: null workspace (st_colreduce_workspace_floats)");
     const int chunks = st_colreduce_chunks(M);
-    const int rpc = (M + chunks - 1) / chunks;
-    hipLaunchKernelGGL(bn_stats_chunk_kernel, dim3((N + 63) / 64, chunks), dim3(256), 0, (hipStream_t)stream,
-                       X, ldx, coff, M, N, rpc, ws);
-    ST_LAUNCH_CHECK();
     ST_CHECK_ARG(chunks <= 128, "st_bn_stats: %d chunks (the merge kernel holds at most 128)", chunks);
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream,
-                       ws, chunks, rpc, M, N, mean_out, var_out, run_mean, run_var, momentum, batches_tracked, 0);
-    ST_LAUNCH_CHECK();
-    return 0;
+    return bn_stats_launch(X, ldx, coff, M, N, mean_out, var_out, run_mean, run_var, momentum, batches_tracked, 0, ws, stream);
 }
 
 // SyncBN, local half: rec = (mean[N], M2[N], row count) of THIS rank's rows -- what the ranks exchange in one all-gather
@@ -1130,14 +1137,7 @@ extern "C" int st_bn_stats_record(const float* X, int ldx, int coff, int M, int 
                                   void* stream) {
     (void)hipGetLastError();
     ST_CHECK_ARG(X && rec && ws && M > 0 && N > 0, "st_bn_stats_record: bad arguments");
-    const int chunks = st_colreduce_chunks(M);
-    const int rpc = (M + chunks - 1) / chunks;
-    hipLaunchKernelGGL(bn_stats_chunk_kernel, dim3((N + 63) / 64, chunks), dim3(256), 0, (hipStream_t)stream, X, ldx, coff, M, N, rpc, ws);
-    ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream,
-                       ws, chunks, rpc, M, N, rec, rec + N, nullptr, nullptr, 0.0f, batches_tracked, 1);
-    ST_LAUNCH_CHECK();
-    return 0;
+    return bn_stats_launch(X, ldx, coff, M, N, rec, rec + N, nullptr, nullptr, 0.0f, batches_tracked, 1, ws, stream);
 }
 
 // SyncBN, merged half: the gathered records of all ranks (world, 2N + 1) -> the statistics of the global batch, merged exactly and in

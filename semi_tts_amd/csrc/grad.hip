@@ -931,7 +931,7 @@ __global__ __launch_bounds__(256) void highway_fwd_kernel(const float* H, const 
 
 // ---- the K BatchNorm1d layers of a conv bank, one launch per phase (see st_bn_bank_fwd) ----------------------------------------------------
 // The per-layer kernels above with a segment index in the grid: same chunking of the rows per segment, same merge order, so a bank of one
-// segment gives bit for bit the statistics, output and sums of st_bn_stats / st_bn_norm_fwd / st_bn_bwd.  Its dx agrees to rounding: the two
+// segment gives bit for bit the statistics, output and sums of st_bn_stats / st_bn_norm_fwd / st_bn_bwd_reduce.  Its dx agrees to rounding: the two
 // apply kernels compile to different multiply-add sequences.  part: [seg][chunk][2][N].
 struct BnBank { st_bn_bank_seg s[ST_BN_BANK_MAX]; int nseg, Bn, N; };
 
@@ -1599,98 +1599,41 @@ extern "C" int st_act_bwd(const float* dout, int ldd, const float* out, int ldo,
 // BatchNorm backward in two halves so that a data-parallel caller can all-reduce the two sums in between (SyncBN):
 //   reduce: s[0:N] = sum_rows dyb, s[N:2N] = sum_rows dyb * xhat      (local rows)
 //   apply:  dx = w/sigma * (dyb - s1/Mstat - xhat * s2/Mstat)          (Mstat = rows behind mean / var / s)
-extern "C" int st_bn_bwd_reduce(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                                const float* x, int ldx, int xoff, const float* mean, const float* var, float eps,
-                                int M, int N, float* s, float* ws, void* stream) {
+// Both read one st_bn_bwd_job.  Its mask / dres serve a layer whose forward was Y = (act(BN(x)) + res) * mask (st_bn_norm_res_mask_fwd;
+// ConvLayer, src/module.py:641-646): the incoming gradient is multiplied by the mask on the way in (no launch of its own), `y` is the kept
+// act(BN(x)), and the apply half also hands out dres = dy * mask, the gradient of the residual input (NULL: no residual).
+static bool bn_bwd_job_ok(const st_bn_bwd_job& j) {
+    return j.dy && j.x && j.mean && j.var && j.s && j.M > 0 && j.N > 0 && (j.act == ST_ACT_NONE || j.y);
+}
+
+extern "C" int st_bn_bwd_reduce(const st_bn_bwd_job* job, float* ws, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(dy && x && mean && var && s && ws && M > 0 && N > 0 && (act == ST_ACT_NONE || y), "st_bn_bwd_reduce: bad arguments");
+    ST_CHECK_ARG(job, "st_bn_bwd_reduce: null job");
+    const st_bn_bwd_job& j = *job;
+    ST_CHECK_ARG(bn_bwd_job_ok(j) && ws, "st_bn_bwd_reduce: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    float* part = ws + 2 * (size_t)N;
-    const int chunks = st_colreduce_chunks(M);
-    const int rpc = (M + chunks - 1) / chunks;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((N + 63) / 64, chunks), dim3(256), 0, st, dy, ldd, doff, y, ldy, yoff, act,
-                       x, ldx, xoff, mean, var, eps, M, N, rpc, part);
+    float* part = ws + 2 * (size_t)j.N;
+    const int chunks = st_colreduce_chunks(j.M);
+    const int rpc = (j.M + chunks - 1) / chunks;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((j.N + 63) / 64, chunks), dim3(256), 0, st, j.dy, j.ldd, 0, j.y, j.ldy, 0, j.act,
+                       j.x, j.ldx, 0, j.mean, j.var, j.eps, j.M, j.N, rpc, part, j.mask, j.ldm);
     ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(chunk_final_kernel, dim3((2 * N + 15) / 16), dim3(256), 0, st, part, chunks, 2, N, s, s + N, 0);
+    hipLaunchKernelGGL(chunk_final_kernel, dim3((2 * j.N + 15) / 16), dim3(256), 0, st, part, chunks, 2, j.N, j.s, j.s + j.N, 0);
     ST_LAUNCH_CHECK();
     return 0;
 }
 
-static int bn_bwd_apply_impl(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                             const float* x, int ldx, int xoff, const float* mean, const float* var, const float* w, float eps,
-                             int M, int N, const float* s, int Mstat, const float* inv_total, float* dx, int lddx, int dxoff, void* stream,
-                             const float* mask = nullptr, int ldm = 0, float* dres = nullptr, int lddr = 0) {
+// inv_total (device scalar, st_bn_sync_merge): s holds the sums over ALL ranks' rows and *inv_total = 1 / their count; the kernel then
+// does not read Mstat
+extern "C" int st_bn_bwd_apply(const st_bn_bwd_job* job, void* stream) {
     (void)hipGetLastError();
-    ST_CHECK_ARG(dy && x && mean && var && s && dx && M > 0 && N > 0 && Mstat >= M && (act == ST_ACT_NONE || y), "st_bn_bwd_apply: bad arguments");
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for((size_t)M * N)), dim3(256), 0, (hipStream_t)stream, dy, ldd, doff, y, ldy, yoff,
-                       act, x, ldx, xoff, mean, var, w, eps, M, N, s, s + N, dx, lddx, dxoff, Mstat, inv_total, mask, ldm, dres, lddr);
+    ST_CHECK_ARG(job, "st_bn_bwd_apply: null job");
+    const st_bn_bwd_job& j = *job;
+    ST_CHECK_ARG(bn_bwd_job_ok(j) && j.dx && (j.inv_total || j.Mstat >= j.M), "st_bn_bwd_apply: bad arguments");
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for((size_t)j.M * j.N)), dim3(256), 0, (hipStream_t)stream, j.dy, j.ldd, 0, j.y, j.ldy, 0,
+                       j.act, j.x, j.ldx, 0, j.mean, j.var, j.w, j.eps, j.M, j.N, j.s, j.s + j.N, j.dx, j.lddx, 0, j.Mstat, j.inv_total,
+                       j.mask, j.ldm, j.dres, j.lddr);
     ST_LAUNCH_CHECK();
-    return 0;
-}
-
-// The two halves of the BatchNorm backward for a layer whose forward was Y = (act(BN(x)) + res) * mask (st_bn_norm_res_mask_fwd; ConvLayer,
-// src/module.py:641-646): the incoming gradient is multiplied by the mask on the way in (no launch of its own), `y` is the kept act(BN(x)),
-// and the apply half also hands out dres = dy * mask, the gradient of the residual input (NULL: no residual).  inv_total as in
-// st_bn_bwd_apply_sync (NULL: the sums are divided by Mstat).
-extern "C" int st_bn_bwd_reduce_masked(const float* dy, int ldd, const float* mask, int ldm, const float* y, int ldy, int act,
-                                       const float* x, int ldx, const float* mean, const float* var, float eps,
-                                       int M, int N, float* s, float* ws, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(dy && x && mean && var && s && ws && M > 0 && N > 0 && (act == ST_ACT_NONE || y), "st_bn_bwd_reduce_masked: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    float* part = ws + 2 * (size_t)N;
-    const int chunks = st_colreduce_chunks(M);
-    const int rpc = (M + chunks - 1) / chunks;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((N + 63) / 64, chunks), dim3(256), 0, st, dy, ldd, 0, y, ldy, 0, act,
-                       x, ldx, 0, mean, var, eps, M, N, rpc, part, mask, ldm);
-    ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(chunk_final_kernel, dim3((2 * N + 15) / 16), dim3(256), 0, st, part, chunks, 2, N, s, s + N, 0);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int st_bn_bwd_apply_masked(const float* dy, int ldd, const float* mask, int ldm, const float* y, int ldy, int act,
-                                      const float* x, int ldx, const float* mean, const float* var, const float* w, float eps,
-                                      int M, int N, const float* s, int Mstat, const float* inv_total, float* dx, int lddx,
-                                      float* dres, int lddr, void* stream) {
-    return bn_bwd_apply_impl(dy, ldd, 0, y, ldy, 0, act, x, ldx, 0, mean, var, w, eps, M, N, s, inv_total ? M : Mstat, inv_total, dx, lddx, 0, stream,
-                             mask, ldm, dres, lddr);
-}
-
-extern "C" int st_bn_bwd_apply(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                               const float* x, int ldx, int xoff, const float* mean, const float* var, const float* w, float eps,
-                               int M, int N, const float* s, int Mstat, float* dx, int lddx, int dxoff, void* stream) {
-    return bn_bwd_apply_impl(dy, ldd, doff, y, ldy, yoff, act, x, ldx, xoff, mean, var, w, eps, M, N, s, Mstat, nullptr, dx, lddx, dxoff, stream);
-}
-
-// st_bn_bwd_apply under SyncBN: s holds the sums over ALL ranks' rows and *inv_total (device scalar, st_bn_sync_merge) = 1 / their count
-extern "C" int st_bn_bwd_apply_sync(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                                    const float* x, int ldx, int xoff, const float* mean, const float* var, const float* w, float eps,
-                                    int M, int N, const float* s, const float* inv_total, float* dx, int lddx, int dxoff, void* stream) {
-    ST_CHECK_ARG(inv_total, "st_bn_bwd_apply_sync: null inv_total");
-    return bn_bwd_apply_impl(dy, ldd, doff, y, ldy, yoff, act, x, ldx, xoff, mean, var, w, eps, M, N, s, M, inv_total, dx, lddx, dxoff, stream);
-}
-
-
-
-extern "C" int st_bn_bwd(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff, int act,
-                         const float* x, int ldx, int xoff, const float* mean, const float* var, const float* w, float eps,
-                         int M, int N, float* dx, int lddx, int dxoff, float* dw, float* db, int accumulate, float* ws,
-                         void* stream) {
-    ST_CHECK_ARG(ws, "st_bn_bwd: null workspace");
-    int rc = st_bn_bwd_reduce(dy, ldd, doff, y, ldy, yoff, act, x, ldx, xoff, mean, var, eps, M, N, ws, ws, stream);
-    if (rc) return rc;
-    rc = st_bn_bwd_apply(dy, ldd, doff, y, ldy, yoff, act, x, ldx, xoff, mean, var, w, eps, M, N, ws, M, dx, lddx, dxoff, stream);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (db) {   // d beta = s1, d gamma = s2
-        hipLaunchKernelGGL(sum_partials_kernel, dim3(blocks_for(N)), dim3(256), 0, st, ws, db, (size_t)N, 1, accumulate);
-        ST_LAUNCH_CHECK();
-    }
-    if (dw) {
-        hipLaunchKernelGGL(sum_partials_kernel, dim3(blocks_for(N)), dim3(256), 0, st, ws + N, dw, (size_t)N, 1, accumulate);
-        ST_LAUNCH_CHECK();
-    }
     return 0;
 }
 

@@ -67,7 +67,7 @@ static __host__ __device__ inline bool st_aligned16(const void* p) { return (rei
 // ---------------------------------------------------------------- device helpers (wave = 64)
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// row chunks of the split column reductions (st_bn_stats, st_colsum, st_bn_bwd): enough blocks to fill 256 CUs
+// row chunks of the split column reductions (st_bn_stats, st_colsum, st_bn_bwd_reduce): enough blocks to fill 256 CUs
 // even for 80-column tensors, chunks of >= 64 rows
 // row chunks of the column reductions (BatchNorm statistics / backward sums, bias gradients): ~32 rows per chunk, at most 128 chunks
 // (two column blocks x 128 chunks = one workgroup per compute unit for the 128-channel layers of the CBHG)

@@ -1218,56 +1218,41 @@ def act_bwd(dout2d, out2d, act, mask2d=None, dpre=None):
     return dpre
 
 
+def _bn_bwd_job(dy2d, y2d, act, x2d, mean, var, w, eps, mask2d=None):
+    """the st_bn_bwd_job both halves read: operands, row strides (a column slice is pointer + stride) and M, N = x2d.shape"""
+    ld = lambda t: int(t.stride(0)) if t is not None else 0
+    j = _lib.StBnBwdJob(dy=_p(dy2d), ldd=ld(dy2d), y=_p(y2d), ldy=ld(y2d), act=ACT[act], x=_p(x2d), ldx=ld(x2d), mean=_p(mean), var=_p(var),
+                        w=_p(w), eps=float(eps), mask=_p(mask2d), ldm=ld(mask2d))
+    j.M, j.N = x2d.shape
+    return j
+
+
 def bn_bwd(dy2d, y2d, act, x2d, mean, var, w, eps, need_wb=True):
-    """returns dx, dw, db for y = act(BN_train(x))"""
-    M, N = x2d.shape
-    dx = torch.empty(M, N, device=x2d.device, dtype=torch.float32)
-    dw = torch.empty(N, device=x2d.device, dtype=torch.float32) if need_wb else None
-    db = torch.empty(N, device=x2d.device, dtype=torch.float32) if need_wb else None
-    ws = _colreduce_ws(M, N, x2d.device)
-    check(_lib.load().st_bn_bwd(_p(dy2d), int(dy2d.stride(0)), 0, _p(y2d), int(y2d.stride(0)) if y2d is not None else 0, 0,
-                                ACT[act], _p(x2d), int(x2d.stride(0)), 0, _p(mean), _p(var), _p(w), float(eps), M, N,
-                                _p(dx), N, 0, _p(dw), _p(db), 0, _p(ws), stream_handle()), 'st_bn_bwd')
-    return dx, dw, db
+    """returns dx, dw, db for y = act(BN_train(x)): the two halves back to back"""
+    N = x2d.shape[1]
+    s = bn_bwd_reduce(dy2d, y2d, act, x2d, mean, var, eps)
+    dx = bn_bwd_apply(dy2d, y2d, act, x2d, mean, var, w, eps, s, x2d.shape[0])
+    return (dx, s[N:], s[:N]) if need_wb else (dx, None, None)
 
 
 def bn_bwd_reduce(dy2d, y2d, act, x2d, mean, var, eps, mask2d=None):
     """-> s (2N): [sum dyb, sum dyb * xhat] over the local rows; mask2d: dy is multiplied by it on the way in (st_bn_norm_res_mask_fwd's backward)"""
-    M, N = x2d.shape
-    s = torch.empty(2 * N, device=x2d.device, dtype=torch.float32)
-    ws = _colreduce_ws(M, N, x2d.device)
-    if mask2d is not None:
-        check(_lib.load().st_bn_bwd_reduce_masked(_p(dy2d), int(dy2d.stride(0)), _p(mask2d), int(mask2d.stride(0)), _p(y2d),
-                                                  int(y2d.stride(0)) if y2d is not None else 0, ACT[act], _p(x2d), int(x2d.stride(0)),
-                                                  _p(mean), _p(var), float(eps), M, N, _p(s), _p(ws), stream_handle()), 'st_bn_bwd_reduce_masked')
-        return s
-    check(_lib.load().st_bn_bwd_reduce(_p(dy2d), int(dy2d.stride(0)), 0, _p(y2d), int(y2d.stride(0)) if y2d is not None else 0, 0,
-                                       ACT[act], _p(x2d), int(x2d.stride(0)), 0, _p(mean), _p(var), float(eps), M, N, _p(s), _p(ws),
-                                       stream_handle()), 'st_bn_bwd_reduce')
+    j = _bn_bwd_job(dy2d, y2d, act, x2d, mean, var, None, eps, mask2d)
+    s = torch.empty(2 * j.N, device=x2d.device, dtype=torch.float32)
+    j.s = _p(s)
+    check(_lib.load().st_bn_bwd_reduce(C.byref(j), _p(_colreduce_ws(j.M, j.N, x2d.device)), stream_handle()), 'st_bn_bwd_reduce')
     return s
 
 
 def bn_bwd_apply(dy2d, y2d, act, x2d, mean, var, w, eps, s, Mstat, inv_total=None, mask2d=None, want_dres=None):
     """inv_total (device scalar, bn_sync_merge): s holds sums over all ranks' rows, divide them by the global count.
     want_dres is not None: the masked form -> (dx, dres or None) with dres = dy * mask (the gradient of a residual input)"""
-    M, N = x2d.shape
-    dx = torch.empty(M, N, device=x2d.device, dtype=torch.float32)
-    if want_dres is not None:
-        dres = torch.empty(M, N, device=x2d.device, dtype=torch.float32) if want_dres else None
-        check(_lib.load().st_bn_bwd_apply_masked(_p(dy2d), int(dy2d.stride(0)), _p(mask2d), int(mask2d.stride(0)) if mask2d is not None else 0,
-                                                 _p(y2d), int(y2d.stride(0)) if y2d is not None else 0, ACT[act], _p(x2d), int(x2d.stride(0)),
-                                                 _p(mean), _p(var), _p(w), float(eps), M, N, _p(s), int(Mstat), _p(inv_total), _p(dx), N,
-                                                 _p(dres), N, stream_handle()), 'st_bn_bwd_apply_masked')
-        return dx, dres
-    if inv_total is not None:
-        check(_lib.load().st_bn_bwd_apply_sync(_p(dy2d), int(dy2d.stride(0)), 0, _p(y2d), int(y2d.stride(0)) if y2d is not None else 0, 0,
-                                               ACT[act], _p(x2d), int(x2d.stride(0)), 0, _p(mean), _p(var), _p(w), float(eps), M, N,
-                                               _p(s), _p(inv_total), _p(dx), N, 0, stream_handle()), 'st_bn_bwd_apply_sync')
-        return dx
-    check(_lib.load().st_bn_bwd_apply(_p(dy2d), int(dy2d.stride(0)), 0, _p(y2d), int(y2d.stride(0)) if y2d is not None else 0, 0,
-                                      ACT[act], _p(x2d), int(x2d.stride(0)), 0, _p(mean), _p(var), _p(w), float(eps), M, N, _p(s),
-                                      int(Mstat), _p(dx), N, 0, stream_handle()), 'st_bn_bwd_apply')
-    return dx
+    j = _bn_bwd_job(dy2d, y2d, act, x2d, mean, var, w, eps, mask2d)
+    dx = torch.empty(j.M, j.N, device=x2d.device, dtype=torch.float32)
+    dres = torch.empty(j.M, j.N, device=x2d.device, dtype=torch.float32) if want_dres else None
+    j.s, j.Mstat, j.inv_total, j.dx, j.lddx, j.dres, j.lddr = _p(s), int(Mstat), _p(inv_total), _p(dx), j.N, _p(dres), j.N
+    check(_lib.load().st_bn_bwd_apply(C.byref(j), stream_handle()), 'st_bn_bwd_apply')
+    return dx if want_dres is None else (dx, dres)
 
 
 def highway_fwd(H, Tg, x):
@@ -1302,17 +1287,25 @@ def _bn_bank_segs(xs, bns, means, vars_, dxs=None, sums=None, update_running=Tru
     return segs
 
 
-def bn_bank_fwd(xs, bns, Tout):
-    """K BatchNorm1d layers (batch statistics, running statistics updated) of K tensors (Bn, T_k, N) -> the bank (Bn, Tout, K N) and the
-    (K, 2, N) statistics: 3 launches (st_bn_bank_fwd)"""
+def _bn_bank_setup(xs, stats=None):
+    """what the four bank wrappers start from: the library, segment count, Bn, N, device, the scratch of st_bn_bank_workspace_floats, the
+    (K, 2, N) statistics (allocated here in forward) and their per-segment mean / var views"""
     lib = _lib.load()
     n, (Bn, _, N) = len(xs), xs[0].shape
     dev = xs[0].device
-    stats = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
-    Y = torch.empty(Bn, Tout, n * N, device=dev, dtype=torch.float32)
+    if stats is None:
+        stats = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
     ws = torch.empty(int(lib.st_bn_bank_workspace_floats(n, int(Bn * max(x.shape[1] for x in xs)), int(N))), device=dev, dtype=torch.float32)
-    segs = _bn_bank_segs(xs, bns, [stats[k, 0] for k in range(n)], [stats[k, 1] for k in range(n)])
-    check(lib.st_bn_bank_fwd(segs, n, int(Bn), int(N), _p(Y), n * int(N), int(Tout), _p(ws), stream_handle()), 'st_bn_bank_fwd')
+    return lib, n, int(Bn), int(N), dev, ws, stats, [stats[k, 0] for k in range(n)], [stats[k, 1] for k in range(n)]
+
+
+def bn_bank_fwd(xs, bns, Tout):
+    """K BatchNorm1d layers (batch statistics, running statistics updated) of K tensors (Bn, T_k, N) -> the bank (Bn, Tout, K N) and the
+    (K, 2, N) statistics: 3 launches (st_bn_bank_fwd)"""
+    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs)
+    Y = torch.empty(Bn, Tout, n * N, device=dev, dtype=torch.float32)
+    segs = _bn_bank_segs(xs, bns, means, vars_)
+    check(lib.st_bn_bank_fwd(segs, n, Bn, N, _p(Y), n * N, int(Tout), _p(ws), stream_handle()), 'st_bn_bank_fwd')
     return Y, stats
 
 
@@ -1320,20 +1313,16 @@ def bn_bank_fwd_sync(xs, bns, Tout):
     """bn_bank_fwd under SyncBN: this rank's records -> ONE all-gather -> merge -> normalise.  Returns the bank, the (K, 2, N) global
     statistics and inv_total (K) = 1 / global row count per segment."""
     from . import parallel
-    lib = _lib.load()
-    n, (Bn, _, N) = len(xs), xs[0].shape
-    dev = xs[0].device
-    stats = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
+    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs)
     Y = torch.empty(Bn, Tout, n * N, device=dev, dtype=torch.float32)
-    ws = torch.empty(int(lib.st_bn_bank_workspace_floats(n, int(Bn * max(x.shape[1] for x in xs)), int(N))), device=dev, dtype=torch.float32)
-    segs = _bn_bank_segs(xs, bns, [stats[k, 0] for k in range(n)], [stats[k, 1] for k in range(n)])
+    segs = _bn_bank_segs(xs, bns, means, vars_)
     rec = torch.empty(n, 2 * N + 1, device=dev, dtype=torch.float32)
-    check(lib.st_bn_bank_stats_record(segs, n, int(Bn), int(N), _p(rec), _p(ws), stream_handle()), 'st_bn_bank_stats_record')
+    check(lib.st_bn_bank_stats_record(segs, n, Bn, N, _p(rec), _p(ws), stream_handle()), 'st_bn_bank_stats_record')
     allrec = parallel.all_gather_(rec).contiguous()                       # (world, n, 2N + 1)
     inv_total = torch.empty(n, device=dev, dtype=torch.float32)
-    check(lib.st_bn_bank_sync_merge(segs, n, int(Bn), int(N), _p(allrec), int(allrec.shape[0]), _p(inv_total), stream_handle()),
+    check(lib.st_bn_bank_sync_merge(segs, n, Bn, N, _p(allrec), int(allrec.shape[0]), _p(inv_total), stream_handle()),
           'st_bn_bank_sync_merge')
-    check(lib.st_bn_bank_norm(segs, n, int(Bn), int(N), _p(Y), n * int(N), int(Tout), stream_handle()), 'st_bn_bank_norm')
+    check(lib.st_bn_bank_norm(segs, n, Bn, N, _p(Y), n * N, int(Tout), stream_handle()), 'st_bn_bank_norm')
     return Y, stats, inv_total
 
 
@@ -1341,20 +1330,16 @@ def bn_bank_bwd_sync(dY, xs, bns, stats, inv_total, relu_in):
     """backward of bn_bank_fwd_sync: local sums -> ONE all-reduce -> apply.  Returns (dxs, LOCAL sums (K, 2, N)): the parameter gradients
     keep this rank's sums (the gradient reducer averages them over the ranks), dx uses the global ones."""
     from . import parallel
-    lib = _lib.load()
-    n, (Bn, _, N) = len(xs), xs[0].shape
-    dev = xs[0].device
+    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs, stats)
     dxs = [torch.empty_like(x) for x in xs]
     local = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
-    ws = torch.empty(int(lib.st_bn_bank_workspace_floats(n, int(Bn * max(x.shape[1] for x in xs)), int(N))), device=dev, dtype=torch.float32)
-    means, vars_ = [stats[k, 0] for k in range(n)], [stats[k, 1] for k in range(n)]
     segs = _bn_bank_segs(xs, bns, means, vars_, dxs, [local[k] for k in range(n)], update_running=False)
-    check(lib.st_bn_bank_bwd_reduce(segs, n, int(Bn), int(N), _p(dY), int(dY.stride(-2)), int(dY.shape[1]), _p(ws), stream_handle()),
+    check(lib.st_bn_bank_bwd_reduce(segs, n, Bn, N, _p(dY), int(dY.stride(-2)), int(dY.shape[1]), _p(ws), stream_handle()),
           'st_bn_bank_bwd_reduce')
     glob = local.clone()
     parallel.all_reduce_sum_(glob)
     segs = _bn_bank_segs(xs, bns, means, vars_, dxs, [glob[k] for k in range(n)], update_running=False)
-    check(lib.st_bn_bank_bwd_apply(segs, n, int(Bn), int(N), _p(dY), int(dY.stride(-2)), int(dY.shape[1]), 1 if relu_in else 0, _p(inv_total),
+    check(lib.st_bn_bank_bwd_apply(segs, n, Bn, N, _p(dY), int(dY.stride(-2)), int(dY.shape[1]), 1 if relu_in else 0, _p(inv_total),
                                    stream_handle()), 'st_bn_bank_bwd_apply')
     return dxs, local
 
@@ -1362,16 +1347,12 @@ def bn_bank_bwd_sync(dY, xs, bns, stats, inv_total, relu_in):
 def bn_bank_bwd(dY, xs, bns, stats, relu_in):
     """backward of bn_bank_fwd: dx_k over every row of segment k (through the ReLU in front of the norm when relu_in) and the (K, 2, N)
     sums (d bias, d weight): 3 launches"""
-    lib = _lib.load()
-    n, (Bn, _, N) = len(xs), xs[0].shape
-    dev = xs[0].device
+    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs, stats)
     dxs = [torch.empty_like(x) for x in xs]
     sums = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
-    ws = torch.empty(int(lib.st_bn_bank_workspace_floats(n, int(Bn * max(x.shape[1] for x in xs)), int(N))), device=dev, dtype=torch.float32)
-    segs = _bn_bank_segs(xs, bns, [stats[k, 0] for k in range(n)], [stats[k, 1] for k in range(n)], dxs, [sums[k] for k in range(n)],
-                         update_running=False)
-    check(lib.st_bn_bank_bwd(segs, n, int(Bn), int(N), _p(dY), int(dY.stride(-2)), int(dY.shape[1]), 1 if relu_in else 0, _p(ws),
-                             stream_handle()), 'st_bn_bank_bwd')
+    segs = _bn_bank_segs(xs, bns, means, vars_, dxs, [sums[k] for k in range(n)], update_running=False)
+    check(lib.st_bn_bank_bwd(segs, n, Bn, N, _p(dY), int(dY.stride(-2)), int(dY.shape[1]), 1 if relu_in else 0, _p(ws), stream_handle()),
+          'st_bn_bank_bwd')
     return dxs, sums
 
 

@@ -164,7 +164,7 @@ def test_bn_norm_res_mask_against_float64(dev, M, N, res, mask, act, want_t):
 
 # ------------------------------------------------------------------------------------------------------------------- backward
 BWD_ROWS = [(31, 1), (33, 65), (2064, 512), (4128, 80), (8256, 17), (16512, 64)]
-BWD_FORMS = ['plain', 'masked_dres', 'masked', 'sync']
+BWD_FORMS = ['plain', 'masked_dres', 'masked', 'sync', 'masked_sync']
 
 
 @pytest.mark.parametrize('form', BWD_FORMS)
@@ -172,8 +172,8 @@ BWD_FORMS = ['plain', 'masked_dres', 'masked', 'sync']
 @pytest.mark.parametrize('M,N', BWD_ROWS, ids=['M%d-N%d' % r for r in BWD_ROWS])
 def test_bn_backward_halves_against_float64(dev, M, N, act, form):
     """st_bn_bwd_reduce / st_bn_bwd_apply (dy a column slice of wider rows, Mstat = M), their masked forms (dy * mask on the way in,
-    dres = dy * mask out) and the SyncBN form (1 / row count read from the device) against float64 autograd of
-    (act(BN(x)) [+ res]) [* mask]: the sums are (d bias, d weight), the apply half writes dx"""
+    dres = dy * mask out), the SyncBN form (1 / row count read from the device) and the two together (the ConvLayer node under SyncBN)
+    against float64 autograd of (act(BN(x)) [+ res]) [* mask]: the sums are (d bias, d weight), the apply half writes dx"""
     from semi_tts_amd import ops
     g = gen(M * 5 + N)
     x = torch.randn(M, N, generator=g) * 1.5 + 0.3
@@ -196,6 +196,8 @@ def test_bn_backward_halves_against_float64(dev, M, N, act, form):
     dres = None
     if form == 'sync':
         dx = ops.bn_bwd_apply(dyd, t, act, xd, mean, var, wd, eps, s, M, torch.full((1,), 1.0 / M, device=dev))
+    elif form == 'masked_sync':
+        dx, dres = ops.bn_bwd_apply(dyd, t, act, xd, mean, var, wd, eps, s, M, torch.full((1,), 1.0 / M, device=dev), mask2d=kd, want_dres=True)
     elif masked:
         dx, dres = ops.bn_bwd_apply(dyd, t, act, xd, mean, var, wd, eps, s, M, mask2d=kd, want_dres=form == 'masked_dres')
     else:
@@ -203,7 +205,7 @@ def test_bn_backward_halves_against_float64(dev, M, N, act, form):
     errs = dict(dx=relerr(dx, xr.grad), db=relerr(s[:N], br.grad), dw=relerr(s[N:], wr.grad))
     report('bn_backward', M=M, N=N, act=str(act), form=form, **errs)
     assert max(errs.values()) < 2e-5, errs
-    if form == 'masked_dres':
+    if form in ('masked_dres', 'masked_sync'):
         assert torch.equal(dres.cpu(), dy * k)
     else:
         assert dres is None
@@ -325,7 +327,7 @@ def test_more_layers_than_the_bank_takes_go_through_the_group_function(dev):
 
 @pytest.mark.parametrize('N', [80, 18])
 def test_one_segment_bank_is_the_per_layer_kernels(dev, N):
-    """the comment above BnBank: a bank of one segment gives bit for bit what st_bn_stats / st_bn_norm_fwd / st_bn_bwd give -- statistics,
+    """the comment above BnBank: a bank of one segment gives bit for bit what st_bn_stats / st_bn_norm_fwd / ops.bn_bwd give -- statistics,
     running statistics, output and the two sums -- and dx to rounding: the two apply kernels compile to different multiply-add sequences
     (measured: 2.5 % / 3.6 % of the elements differ at N = 80 / 18, by at most 4.8e-7 on O(1) values); the per-layer apply on the bank's
     sums is bitwise the per-layer dx.
