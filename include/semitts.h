@@ -593,7 +593,8 @@ int st_scatter_add_rows(const float* dout, const int64_t* idx, float* dtable, in
  * st_lstm_seq_variant is the one place a form is chosen (host arithmetic only; -1: null pointer, or a shape no form takes):
  *   ST_LSTM_STEP     one launch per time step (backward: a pointwise and a W_hh^T launch, w = W_hh^T (H,4H): ST_LSTM_W_T).
  *                    ws_floats: forward (2 ndir + 1) B H, backward 2 ndir B H.
- *   ST_LSTM_PACKED   backward, ndir == 2, H % 16 == 0: one launch per time step, dgates(s) . W_hh with the pointwise backward of step s-1
+ *   ST_LSTM_PACKED   backward, ndir == 2, H % 16 == 0, ld and col multiples of 4 and every ST_LSTM_AL_* operand 16-byte aligned (else
+ *                    ST_LSTM_STEP): one launch per time step, dgates(s) . W_hh with the pointwise backward of step s-1
  *                    in its epilogue; w = st_pack_weight_t of W_hh (N = H, K = 4H): ST_LSTM_W_PACKED_T.  ws_floats: 2 B H +
  *                    4 st_t16_floats(B, 4H), ws 16-byte aligned.
  *   ST_LSTM_PERSIST  ndir == 2: ALL time steps in ONE launch, its workgroups resident at once on cus - cu_reserve compute units (cus == 0:

@@ -810,8 +810,10 @@ static int lstm_plan(const st_lstm_seq_query& q, st_lstm_seq_plan& p) {
         if (q.col[d] < 0 || ld < q.col[d] + H) return -1;
     const size_t bh = (size_t)B * H;
     const unsigned al = q.backward ? 127u : 7u;      // every ST_LSTM_AL_* bit of the pass
-    // the one-launch forms: both directions, rows of 16-byte pieces, all workgroups resident at once beside the compute units kept free
-    const bool one = q.allow_persist && q.ndir == 2 && ld % 4 == 0 && c0 % 4 == 0 && c1 % 4 == 0 && (q.aligned & al) == al;
+    // both directions, rows of 16-byte pieces: what the one-launch forms and the packed backward (16-byte loads of dout and the tapes,
+    // 16-byte stores of dxproj in its epilogue) take; the one-launch forms also need all workgroups resident beside the units kept free
+    const bool vec = q.ndir == 2 && ld % 4 == 0 && c0 % 4 == 0 && c1 % 4 == 0 && (q.aligned & al) == al;
+    const bool one = q.allow_persist && vec;
     const int cus = !one ? 0 : q.cus > 0 ? q.cus : st_device_cus();
     p = st_lstm_seq_plan{ST_LSTM_STEP, ST_LSTM_W_NATURAL};
     if (!q.backward) {
@@ -827,7 +829,7 @@ static int lstm_plan(const st_lstm_seq_query& q, st_lstm_seq_plan& p) {
         p.rg = 2 * (H / 16) * ((B + 7) / 8) <= cus / 2 ? 8 : 16;
         p.form = ST_LSTM_PERSIST; p.grid_x = H / 16; p.grid_y = (B + p.rg - 1) / p.rg; p.grid_z = 2; p.block = 512;
         p.rt = rt; p.nkb = H / 32;
-    } else if (q.ndir == 2 && H % 16 == 0) {      // packed operands: one launch per step (product + pointwise backward of the step before)
+    } else if (vec && H % 16 == 0) {      // packed operands: one launch per step (product + pointwise backward of the step before)
         p.form = ST_LSTM_PACKED; p.weights = ST_LSTM_W_PACKED_T;
         p.ws_floats = 2 * bh + 4 * st_t16_floats(B, 4 * H);      // dc carries, then two ping-pong T16 copies of dgates per direction
     } else {
@@ -1004,7 +1006,7 @@ __global__ __launch_bounds__(512) void lstm_seq2_bwd_persist_kernel(const LbArgs
             f32x4 x[NKB];
             bool ok = false;
             const int spins = dead ? 1 : LP_SPINS;
-            // (a) one canary word per producer workgroup of this wave's K range (batch row bg*16, first unit of the block)
+            // (a) one canary word per producer workgroup of this wave's K range (batch row bg*RG, first unit of the block)
             for (int sp = 0; sp < spins; ++sp) {
                 const int c = min(lane, NKB - 1);
                 gu32* cw = (gu32*)(a.dxp[d] + ((size_t)(bg * RG) * T + tn) * H4 + 16 * (wave * NKB + c));

@@ -1,12 +1,16 @@
 """The bidirectional LSTM layer as ONE launch for all time steps (the ST_LSTM_PERSIST form of st_lstm_seq_fwd: recurrent weights and cell states in
 registers, h handed from workgroup to workgroup through the output tensor) against the one-launch-per-step form and against
-torch.nn.LSTM on the CPU.  Needs a real MI355X."""
+the float64 statement of the layer on the CPU (lstm_seq_cases.lstm_ref).  Needs a real MI355X."""
 import functools
+import os
+import sys
 
 import pytest
 import torch
 
-from helpers import maxdiff
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers import maxdiff   # noqa: E402
+from lstm_seq_cases import lstm_ref, lstm_ref_bwd   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -58,18 +62,9 @@ def test_one_launch_bilstm_equals_the_per_step_form(B, T, H):
     assert maxdiff(out_p, out_s) < 3e-6
     for d in range(2):
         assert maxdiff(gs_p[d], gs_s[d]) < 3e-6 and maxdiff(cs_p[d], cs_s[d]) < 1e-5
-    # and torch.nn.LSTM given the same input projections: x = identity trick -- feed xproj through W_ih = I
-    lstm = torch.nn.LSTM(4 * H, H, batch_first=True, bidirectional=True)
-    with torch.no_grad():
-        for d, sfx in enumerate(('', '_reverse')):
-            getattr(lstm, 'weight_ih_l0' + sfx).copy_(torch.eye(4 * H))
-            getattr(lstm, 'bias_ih_l0' + sfx).zero_()
-            getattr(lstm, 'weight_hh_l0' + sfx).copy_(w[d])
-            getattr(lstm, 'bias_hh_l0' + sfx).copy_(b[d])
-        # (one input per direction: run the module twice and take each direction's half)
-        ref_f = lstm(xp[0])[0][:, :, :H]
-        ref_b = lstm(xp[1])[0][:, :, H:]
-    assert maxdiff(out_p[:, :, :H], ref_f) < 2e-5 and maxdiff(out_p[:, :, H:], ref_b) < 2e-5
+    # and the float64 statement of the layer on the same input projections
+    for d in range(2):
+        assert maxdiff(out_p[:, :, d * H:(d + 1) * H], lstm_ref(xp[d], w[d], b[d], d == 1)[0]) < 2e-5
 
 
 def test_one_launch_bilstm_is_deterministic_and_replays_in_a_graph():
@@ -138,7 +133,7 @@ def test_one_launch_bilstm_against_oracle(B, T, H, In):
 @pytest.mark.parametrize('B,T,H', [(32, 43, 256), (5, 7, 64), (33, 9, 128), (16, 129, 256), (3, 1, 32), (20, 6, 32)])
 def test_one_launch_bilstm_backward_against_float64_autograd(B, T, H):
     """The ST_LSTM_PERSIST form of st_lstm_seq_bwd (BPTT of both directions in one launch, gate gradients handed over through the returned tensor) against
-    the one-launch-per-step form and against float64 autograd through torch.nn.LSTM given the same input projections (W_ih = I).
+    the one-launch-per-step form and against float64 autograd through the plain statement of the layer (lstm_seq_cases.lstm_ref_bwd).
     ref: backward of nn.LSTM(bidirectional=True) src/module.py:432-438,458-460"""
     from semi_tts_amd import ops
     from helpers import report
@@ -162,22 +157,13 @@ def test_one_launch_bilstm_backward_against_float64_autograd(B, T, H):
         return dx
 
     dx_p, dx_p2, dx_s = bwd(True), bwd(True), bwd(False)
-    lstm = torch.nn.LSTM(4 * H, H, batch_first=True, bidirectional=True).double()
-    with torch.no_grad():
-        for d, sfx in enumerate(('', '_reverse')):
-            getattr(lstm, 'weight_ih_l0' + sfx).copy_(torch.eye(4 * H))
-            getattr(lstm, 'bias_ih_l0' + sfx).zero_()
-            getattr(lstm, 'weight_hh_l0' + sfx).copy_(w[d])
-            getattr(lstm, 'bias_hh_l0' + sfx).copy_(b[d])
     worst = 0.0
     for d in range(2):
-        x = xp[d].double().requires_grad_()
-        y = lstm(x)[0][:, :, d * H:(d + 1) * H]
-        y.backward(dout[:, :, d * H:(d + 1) * H].double())
-        scale = float(x.grad.abs().max())
+        ref = lstm_ref_bwd(xp[d], w[d], b[d], d == 1, dout[:, :, d * H:(d + 1) * H])
+        scale = float(ref.abs().max())
         assert torch.isfinite(dx_p[d]).all()
         assert torch.equal(dx_p[d], dx_p2[d])                                    # run to run: bit for bit
-        e_ref = float((dx_p[d].cpu().double() - x.grad).abs().max()) / scale
+        e_ref = float((dx_p[d].cpu().double() - ref).abs().max()) / scale
         e_step = float((dx_p[d] - dx_s[d]).abs().max()) / scale
         worst = max(worst, e_ref)
         assert e_ref < 2e-5 and e_step < 2e-5, (d, e_ref, e_step)
@@ -194,23 +180,11 @@ def test_bilstm_backward_shapes_outside_the_one_launch_form():
 # ------------------------------------------------------------------------------------------------ one direction, one launch per step
 @functools.lru_cache(maxsize=None)
 def _one_direction_reference(B, T, H):
-    """inputs of a unidirectional layer and, per walk (forward, reverse), the float64 output and gradient of the input projection:
-    torch.nn.LSTM(bidirectional=True) with the same weights in both directions and W_ih = I, each direction's half taken"""
+    """inputs of a unidirectional layer and, per walk (forward, reverse), the float64 output and gradient of the input projection
+    (lstm_seq_cases.lstm_ref / lstm_ref_bwd)"""
     xp, w, b = _layer(B, T, H, seed=31 + B + T + H)
     dout = torch.randn(B, T, H, generator=torch.Generator().manual_seed(5))
-    lstm = torch.nn.LSTM(4 * H, H, batch_first=True, bidirectional=True).double()
-    with torch.no_grad():
-        for sfx in ('', '_reverse'):
-            getattr(lstm, 'weight_ih_l0' + sfx).copy_(torch.eye(4 * H))
-            getattr(lstm, 'bias_ih_l0' + sfx).zero_()
-            getattr(lstm, 'weight_hh_l0' + sfx).copy_(w[0])
-            getattr(lstm, 'bias_hh_l0' + sfx).copy_(b[0])
-    ref = []
-    for d in range(2):
-        x = xp[0].double().requires_grad_()
-        y = lstm(x)[0][:, :, d * H:(d + 1) * H]
-        y.backward(dout.double())
-        ref.append((y.detach(), x.grad))
+    ref = [(lstm_ref(xp[0], w[0], b[0], rev)[0], lstm_ref_bwd(xp[0], w[0], b[0], rev, dout)) for rev in (False, True)]
     return xp[0], w[0], b[0], dout, ref
 
 
