@@ -1669,6 +1669,26 @@ int st_dtw_pairs(const float* feat, long n_rows, int D, long st, const int32_t* 
  * triples than threads are strided over).  Limits (-22): NB >= 1, dmat_len >= 1. */
 int st_abx_count(const float* dmat, long dmat_len, const int64_t* blk /* (NB, 6) */, int NB, int64_t* count /* (NB, 4) */, void* stream);
 
+/* st_abx_across: across-speaker ABX from finished distances -- A and B of one speaker, X of another (Libri-light's second figure).
+ * dmat as for st_abx_count, one dense (n_c, n_c) matrix per CONTEXT whose items are ordered by (speaker, label, index), so a
+ * (speaker, label) run is an index range; entries between items of one speaker are never read.
+ * grp (NG, 8) int64 on the device: (mat_off, n_c, a_lo, a_hi, b_lo, b_hi, xr_lo, xr_hi) -- A runs over [a_lo, a_hi), B over
+ * [b_lo, b_hi) (same speaker, another label), and xr[xr_lo .. xr_hi) of xr (NX, 2) int64 are the ranges (x_lo, x_hi) of label a for the
+ * speakers of the context in ascending speaker order, a list all groups of one (context, a) share.  All ranges are clamped into
+ * [0, n_c] and an inverted range is empty; the entry that equals (a_lo, a_hi) after clamping is the group's own speaker and is skipped.
+ * Per X range: the triples (A, B, X), n_a n_b n_x of them; wrong = d(A, X) > d(B, X), tied = ==, nan = either is NaN (counted nowhere
+ * else), d(., X) read from row X; pair score = (wrong + tied / 2) / (triples - nan) in float64, absent when nothing is left.
+ * err (NG) float64 = the mean of the present pair scores: their sum taken sequentially in list order, one division by their number;
+ * NaN without one.  count (NG, 5) int64 = (wrong, tied, nan, triples, x_speakers): the first four summed over all ranges but the
+ * group's own, x_speakers the number of present pair scores.
+ * A group whose matrix does not lie inside dmat (as for st_abx_count) or whose xr_lo or xr_hi lies outside [0, NX] reads nothing and
+ * gets -1 in all five columns and NaN; xr_hi <= xr_lo is an empty list.  Integer partial sums, no atomics, a fixed order: bitwise
+ * repeatable and independent of NG, of the group's position and of the other groups.  One launch, one wave a group (groups wider
+ * than a wave are strided over), no workspace, no host read.  Limits (-22): NG >= 1, dmat_len >= 1, NX >= 1, no null pointer; n_c as
+ * for st_abx_count. */
+int st_abx_across(const float* dmat, long dmat_len, const int64_t* grp /* (NG, 8) */, int NG, const int64_t* xr /* (NX, 2) */, long NX,
+                  double* err /* (NG) */, int64_t* count /* (NG, 5) */, void* stream);
+
 /* ------------------------------------------------------------------ intelligibility: STOI and ESTOI of (clean, processed) waveform pairs
  * Not a step of the reference (it scores no waveform).  STOI: Taal, Hendriks, Heusdens, Jensen 2011; ESTOI: Jensen, Taal 2016
  * (semi_tts_amd.metrics.stoi, main.py --stoi-wav-dir).  Both signals of a pair are at 10 kHz, time-aligned and of one length: x is a

@@ -82,6 +82,8 @@ confusions.csv, phones.csv, with `--score-ali` <key>.ops per file and with `--sc
 the codebook posteriors -- by the ABX phone-discrimination error of ZeroSpeech / Libri-light: the phone tokens the .ali files of
 `--align-wav-dir` delimit are compared within speaker and context by path-normalised DTW, one wave per pair on the GPU (solver.AbxScorer,
 semi_tts_amd.metrics.abx, st_dtw_pairs + st_abx_count): abx.csv with the error of every ordered phone pair, abx_phones.csv with the tokens used.
+`--abx-mode across|both --abx-spk-map FILE` takes X from another speaker of the same context instead (metrics.abx_across, st_abx_across):
+abx_across.csv and abx_across_speakers.csv; `both` runs the within-speaker path first and then the across-speaker one.
 `--stoi-wav-dir SYN --stoi-ref-dir REF` (not a mode of the reference) scores processed .wav files -- what `--vocode-dir`, `--gen-specgram --gen-wav`,
 `--resample-wav-dir` or `--loudness-out` write -- against the time-aligned recordings they were made from by short-time objective
 intelligibility on the GPU (solver.StoiScorer, semi_tts_amd.metrics.stoi, st_stoi_batch): stoi.csv with STOI and ESTOI of every pair.  The
@@ -256,13 +258,18 @@ parser.add_argument('--abx-metric', default=None, choices=('angular', 'kl', 'euc
 parser.add_argument('--abx-context', default=None, choices=('triphone', 'none'), help='--abx-ali-dir: compare tokens that share speaker, previous '
                     'and next symbol (triphone, default; the utterance\'s edge is a symbol of its own) or the speaker alone (none)')
 parser.add_argument('--abx-spk-map', default=None, type=str, help='--abx-ali-dir: a key,speaker CSV (key: the file\'s stem); without it all files '
-                    'are one speaker.  ABX is taken within speaker only')
+                    'are one speaker.  ABX is taken within speaker unless --abx-mode says otherwise')
 parser.add_argument('--abx-ignore', default=None, type=str, help='--abx-ali-dir: comma-separated symbols that are never items (they still count as '
                     'context)')
 parser.add_argument('--abx-max-items', default=None, type=int, help='--abx-ali-dir: the most tokens of one phone in one cell; above it a seeded '
                     'subsample (--seed) is scored (default 50)')
 parser.add_argument('--abx-min-frames', default=None, type=int, help='--abx-ali-dir: tokens of fewer feature rows are dropped (default 1; tokens '
                     'of more than 64 rows always are)')
+parser.add_argument('--abx-mode', default=None, choices=('within', 'across', 'both'), help='--abx-ali-dir: where X comes from: the speaker of A and '
+                    'B (within, default), another speaker of the same context (across: abx_across.csv with phone_a,phone_b,groups,triples,error and '
+                    'abx_across_speakers.csv with speaker,groups,error), or one run after the other (both); across and both need --abx-spk-map')
+parser.add_argument('--abx-max-gb', default=None, type=float, help='--abx-mode across|both: the most GiB of distance matrices and pair tables '
+                    '(default 8); above it the run is refused')
 parser.add_argument('--stoi-wav-dir', default=None, type=str, help='score the processed .wav files of this directory (sorted by name, batched by '
                     '--batch-size; 16-bit mono PCM of any rate the resampler takes) against their time-aligned recordings in --stoi-ref-dir by STOI and '
                     'ESTOI on the GPU: <logdir>/<name>/stoi.csv (file,samples,frames,kept,segments,stoi,estoi); no config, no checkpoint, no model')
@@ -556,6 +563,14 @@ def parse_args(argv=None):
         paras.abx_min_frames = 1 if paras.abx_min_frames is None else paras.abx_min_frames
         if paras.abx_max_items < 2 or not 1 <= paras.abx_min_frames <= 64:
             parser.error('--abx-max-items must be >= 2 and --abx-min-frames in [1, 64]')
+        if paras.abx_max_gb is not None and (paras.abx_mode in (None, 'within') or not 0.0 < paras.abx_max_gb < float('inf')):
+            parser.error('--abx-max-gb takes a positive number of GiB and belongs to --abx-mode across or both')
+        paras.abx_mode = paras.abx_mode or 'within'
+        paras.abx_max_gb = 8.0 if paras.abx_max_gb is None else paras.abx_max_gb
+        if paras.abx_mode != 'within' and paras.abx_spk_map is None:
+            parser.error('--abx-mode %s takes X from another speaker: it needs --abx-spk-map FILE (key,speaker) with at least two speakers' % paras.abx_mode)
+    elif paras.abx_mode is not None or paras.abx_max_gb is not None:
+        parser.error('--abx-mode and --abx-max-gb belong to --abx-ali-dir; they need that flag')
     elif any(getattr(paras, f) is not None for f in abx_flags):
         parser.error('--abx-wav-dir, --abx-feat, --abx-metric, --abx-context, --abx-spk-map, --abx-ignore, --abx-max-items and --abx-min-frames belong to '
                      '--abx-ali-dir; they need that flag')

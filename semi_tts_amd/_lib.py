@@ -459,6 +459,7 @@ SIGNATURES = {
     'st_wave_gain': [C.POINTER(StWaveBatch), P, P, P, P],
     'st_dtw_pairs': [P, C.c_long, I, C.c_long, P, P, I, P, P, I, I, I, P, P, P, P],
     'st_abx_count': [P, C.c_long, P, I, P, P],
+    'st_abx_across': [P, C.c_long, P, I, P, C.c_long, P, P, P],
     'st_stoi_frames': [I],
     'st_stoi_workspace_floats': [I, I],
     'st_stoi_batch': [C.POINTER(StWaveBatch), P, P, P, I, P, P, P, P, P],

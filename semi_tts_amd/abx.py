@@ -9,6 +9,12 @@ and the block table a launch works through, aggregates the counts and writes the
     items   one phone token each: a run of rows of the packed feature buffer, a label (the phone) and a cell (the context)
     cell    the items that may be compared: same speaker and, with context 'triphone', same previous and next symbol
     block   an ordered pair of labels (a, b) of one cell with n_a >= 2 and n_b >= 1: the triples X, A in a (A != X), B in b
+
+The across-speaker measure (plan_across, aggregate_across; st_abx_across through metrics.abx_across) takes A and B from one speaker and
+X from another speaker of the same context:
+
+    context the cell without its speaker: previous and next symbol with 'triphone', one for all with 'none'
+    group   (context, speaker s, a, b): A in (s, a), B in (s, b), X in (s', a) for every other speaker s' of the context that has a
 """
 import collections
 import math
@@ -26,6 +32,10 @@ CONTEXTS = ('triphone', 'none')
 Ali = collections.namedtuple('Ali', 'frames frame_s symbols starts ends')
 Plan = collections.namedtuple('Plan', 'keep pair_a pair_b pos_ab pos_ba dmat_len blocks block_cell block_a block_b')
 Aggregate = collections.namedtuple('Aggregate', 'table score block_error')
+ACROSS_HEADER = 'phone_a,phone_b,groups,triples,error'
+ACROSS_SPEAKERS_HEADER = 'speaker,groups,error'
+AcrossPlan = collections.namedtuple('AcrossPlan', 'keep pair_a pair_b pos_ab pos_ba dmat_len grp xr grp_context grp_speaker grp_a grp_b')
+AggregateAcross = collections.namedtuple('AggregateAcross', 'table score speakers')
 
 
 def read_ali(path):
@@ -198,6 +208,104 @@ def aggregate(block_a, block_b, counts):
     table = [(a, b, len(qs), int(valid[qs].sum()), float(np.mean(err[qs]))) for (a, b), qs in groups.items()]
     score = float(np.mean([r[4] for r in table])) if table else float('nan')
     return Aggregate(table, score, err)
+
+
+def plan_across(label, context, speaker, max_items=50, seed=0, max_bytes=None):
+    """the work of one metrics.abx_across call.  keep: subsample(label, cell) with cell the dense id of (context, speaker) in sorted
+    order, i.e. the items in (context, speaker, label, index) order -- what the within-speaker plan of the same cells keeps.  A context
+    with at least one group gets a dense (n_c, n_c) matrix at mat_off; its DTW pairs are the unordered pairs i < j (context order,
+    row-major) whose speakers differ, written to pos_ab and mirrored to pos_ba -- entries between items of one speaker stay unwritten.
+    A group is (context, speaker s, a, b): s has both labels, a != b, and another speaker of the context has a.  grp (NG, 8) int64 =
+    (mat_off, n_c, a_lo, a_hi, b_lo, b_hi, xr_lo, xr_hi), ordered by (context, speaker, a, b); xr (NX, 2) int64 holds, per (context,
+    a), the (x_lo, x_hi) of every speaker that has a in ascending speaker order (the group's own among them), shared by its groups.
+    max_bytes: ValueError as soon as the matrices (4 bytes an entry) and the pair tables (28 bytes a pair) pass it, before either is
+    laid out."""
+    label, context, speaker = (np.asarray(v, np.int64).reshape(-1) for v in (label, context, speaker))
+    if not len(label) == len(context) == len(speaker):
+        raise ValueError('abx: %d labels, %d contexts, %d speakers: one of each per item' % (len(label), len(context), len(speaker)))
+    cell = np.unique(np.stack([context, speaker], 1), axis=0, return_inverse=True)[1].reshape(-1) if len(label) else context
+    keep = subsample(label, cell, max_items, seed)
+    kc, ks, kl = context[keep], speaker[keep], label[keep]
+    pa, pb, ab, ba, grp, xr, gc, gs, ga, gb = [], [], [], [], [], [], [], [], [], []
+    off = xoff = nbytes = 0
+    bounds = np.concatenate([[0], np.flatnonzero(np.diff(kc)) + 1, [len(keep)]]) if len(keep) else np.zeros(1, np.int64)
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        nc, s, lab = int(hi - lo), ks[lo:hi], kl[lo:hi]
+        start = np.flatnonzero(np.concatenate([[True], (s[1:] != s[:-1]) | (lab[1:] != lab[:-1])]))      # the (speaker, label) runs
+        end = np.concatenate([start[1:], [nc]])
+        rs, rl = s[start], lab[start]
+        o = np.lexsort((rs, rl))                                    # the runs by (label, speaker): one label's X ranges lie together
+        labs, xfirst, xcnt = np.unique(rl[o], return_index=True, return_counts=True)
+        ia, ib = np.nonzero((rs[:, None] == rs[None, :]) & (rl[:, None] != rl[None, :]))         # runs (s, a), (s, b): sorted by (s, a, b)
+        li = np.searchsorted(labs, rl[ia])
+        ok = xcnt[li] >= 2                                          # another speaker has a
+        ia, ib, li = ia[ok], ib[ok], li[ok]
+        if len(ia) == 0:
+            continue
+        n_pairs = (nc * nc - int((np.unique(s, return_counts=True)[1].astype(np.int64) ** 2).sum())) // 2
+        nbytes += 4 * nc * nc + 28 * n_pairs
+        if max_bytes is not None and nbytes > max_bytes:
+            raise ValueError('abx: the distance matrices and pair tables of the contexts need more than %d bytes (%d bytes with the context of %d '
+                             'items); lower --abx-max-items or use --abx-context triphone' % (max_bytes, nbytes, nc))
+        i, j = np.triu_indices(nc, 1)
+        cross = s[i] != s[j]
+        i, j = i[cross].astype(np.int64), j[cross].astype(np.int64)
+        pa.append(keep[lo + i])
+        pb.append(keep[lo + j])
+        ab.append(off + i * nc + j)
+        ba.append(off + j * nc + i)
+        full = lambda v: np.full(len(ia), v, np.int64)              # noqa: E731
+        grp.append(np.stack([full(off), full(nc), start[ia], end[ia], start[ib], end[ib], xoff + xfirst[li], xoff + xfirst[li] + xcnt[li]], 1))
+        xr.append(np.stack([start[o], end[o]], 1))
+        gc.append(full(kc[lo]))
+        gs.append(rs[ia])
+        ga.append(rl[ia])
+        gb.append(rl[ib])
+        off += nc * nc
+        xoff += len(o)
+    cat = lambda v, w=None: np.concatenate(v).astype(np.int64) if v else np.zeros((0,) if w is None else (0, w), np.int64)     # noqa: E731
+    return AcrossPlan(keep, cat(pa).astype(np.int32), cat(pb).astype(np.int32), cat(ab), cat(ba), off, cat(grp, 8), cat(xr, 2),
+                      cat(gc), cat(gs), cat(ga), cat(gb))
+
+
+def _group_means(keys, err):
+    """err (already in the order the means are to be summed in) by the rows of keys -> (the distinct rows sorted, members, float64 means:
+    a sequential sum in the given order and one division)"""
+    uniq, inv, cnt = np.unique(keys, axis=0, return_inverse=True, return_counts=True)
+    return uniq, cnt, np.bincount(inv.reshape(-1), weights=err, minlength=len(uniq)) / cnt
+
+
+def aggregate_across(grp_a, grp_b, grp_speaker, err, count):
+    """Libri-light's order of means, float64: the kernel has averaged a group's pair scores over the X speakers (err, NaN without one);
+    error(a, b) = the mean of err over the groups (context, speaker) of the pair that have one; score = the mean over the ordered (a, b)
+    with at least one group.  -> AggregateAcross(table [(a, b, groups, triples, error)] sorted by (a, b) -- triples: those left after
+    the NaN ones --, score (nan without a group), speakers [(speaker, groups, error)]: the same group errors averaged per speaker of
+    A and B).  Vectorised: nothing here walks the groups."""
+    a, b, spk, err = (np.asarray(v).reshape(-1) for v in (grp_a, grp_b, grp_speaker, err))
+    count = np.asarray(count, np.int64).reshape(-1, 5)
+    if not len(a) == len(b) == len(spk) == len(err) == len(count):
+        raise ValueError('abx: %d, %d, %d group names, %d errors, %d counts: one of each per group' % (len(a), len(b), len(spk), len(err), len(count)))
+    has = (err == err) & (count[:, 4] > 0)
+    if not has.any():
+        return AggregateAcross([], float('nan'), [])
+    a, b, spk, err, left = a[has], b[has], spk[has], err[has].astype(np.float64), (count[has, 3] - count[has, 2])
+    pairs, n, e = _group_means(np.stack([a, b], 1), err)
+    tri = np.bincount(np.unique(np.stack([a, b], 1), axis=0, return_inverse=True)[1].reshape(-1), weights=left.astype(np.float64))
+    table = [(int(p[0]), int(p[1]), int(g), int(t), float(v)) for p, g, t, v in zip(pairs, n, tri, e)]
+    who, n, v = _group_means(spk.reshape(-1, 1), err)
+    return AggregateAcross(table, float(np.mean(e)), [(int(w[0]), int(g), float(x)) for w, g, x in zip(who, n, v)])
+
+
+def format_abx_across_csv(table, names=None):
+    """abx_across.csv: ACROSS_HEADER, one row per ordered phone pair"""
+    name = (lambda v: str(v)) if names is None else (lambda v: names[v])
+    return '\n'.join([ACROSS_HEADER] + ['%s,%s,%d,%d,%.6f' % (name(a), name(b), g, t, e) for a, b, g, t, e in table]) + '\n'
+
+
+def format_abx_across_speakers_csv(speakers, names=None):
+    """abx_across_speakers.csv: ACROSS_SPEAKERS_HEADER, one row per speaker of A and B"""
+    name = (lambda v: str(v)) if names is None else (lambda v: names[v])
+    return '\n'.join([ACROSS_SPEAKERS_HEADER] + ['%s,%d,%.6f' % (name(s), g, e) for s, g, e in speakers]) + '\n'
 
 
 def format_abx_csv(table, names=None):

@@ -17,7 +17,7 @@ TRIM_SOURCES = ['trim.hip']
 SCORE_SOURCES = ['edit_align.hip']
 # the loudness kernels (st_loudness_batch, st_wave_gain), listed apart for the same reason
 LOUDNESS_SOURCES = ['loudness.hip']
-# the ABX kernels (st_dtw_pairs, st_abx_count), listed apart for the same reason
+# the ABX kernels (st_dtw_pairs, st_abx_count, st_abx_across), listed apart for the same reason
 ABX_SOURCES = ['abx.hip']
 # the intelligibility kernels (st_stoi_batch), listed apart for the same reason
 STOI_SOURCES = ['stoi.hip']

@@ -1,5 +1,6 @@
 // abx.hip -- the distance engine of the ABX phone-discrimination error: path-normalised DTW of many pairs of short items of one packed
-// feature buffer, and the triple counts over finished distance matrices (contracts: st_dtw_pairs, st_abx_count in include/semitts.h).
+// feature buffer, and the triple counts over finished distance matrices (contracts: st_dtw_pairs, st_abx_count, st_abx_across in
+// include/semitts.h).
 //
 // st_dtw_pairs.  One WAVE per pair, four waves a workgroup, no workgroup barrier: a wave's pair touches only that wave's slice of LDS.
 // Phase 1: the 64 lanes go over the n x m cells (lane = cell mod 64) and write the frame distances into the wave's tile in LDS; both
@@ -18,6 +19,9 @@
 // st_abx_count.  One workgroup of 256 threads per block of the table; a thread takes the (X, A) pairs u = tid, tid + 256, ... and runs
 // over the B of the block with d(A, X) in a register, reading row X of the symmetric matrix.  Integer partials, a shuffle reduction per
 // wave, the four wave sums added by thread 0: exact and repeatable, no atomics.
+//
+// st_abx_across.  The across-speaker count: a group (context, speaker of A and B, a, b) against the list of label a's index ranges of
+// every speaker of the context.  Groups are tiny and very many, so a group is one WAVE's work (see abx_across_kernel).
 #include <math.h>
 #include "st_common.h"
 
@@ -244,6 +248,117 @@ __global__ __launch_bounds__(AX_CNT_NT) void abx_count_kernel(const float* __res
     }
 }
 
+__device__ __forceinline__ double ax_lane_f64(double v, int lane) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), lane);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// One WAVE per group, four waves a workgroup, no LDS, no barrier.  A pass hands 64 / W consecutive X ranges of the group's list to
+// segments of W lanes each, W the power of two that holds the widest range's n_x n_a (X, A) pairs (64, strided over, past 32 of them);
+// a lane keeps d(A, X) in a register and runs over B.  The three counts of a range are summed over its segment by log2 W butterfly
+// steps, the segment's first lane forms the float64 pair score, and the scores of a pass are added in lane (= range) order through
+// readlane; the totals are per-lane sums reduced over the wave once per group.
+__global__ __launch_bounds__(AX_NT) void abx_across_kernel(const float* __restrict__ dmat, long dmat_len, const int64_t* __restrict__ grp, int NG,
+                                                           const int64_t* __restrict__ xr, long NX, double* __restrict__ err,
+                                                           int64_t* __restrict__ count) {
+    const int lane = threadIdx.x & (ST_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (long g = (long)blockIdx.x * AX_WAVES + wave; g < NG; g += (long)gridDim.x * AX_WAVES) {       // (wave-uniform)
+        const int64_t* r = grp + (size_t)g * 8;
+        const long long off = r[0], nc = r[1], s_lo = r[6], s_hi = r[7];
+        const bool ok = nc >= 0 && nc <= AX_MAX_NC && off >= 0 && off <= (long long)dmat_len && nc * nc <= (long long)dmat_len - off &&
+                        s_lo >= 0 && s_lo <= (long long)NX && s_hi >= 0 && s_hi <= (long long)NX;
+        if (!ok) {
+            if (lane == 0) {
+                for (int k = 0; k < 5; ++k) count[(size_t)g * 5 + k] = -1;
+                err[g] = NAN;
+            }
+            continue;
+        }
+        const long long a_lo = ax_clamp(r[2], 0, nc), a_hi = ax_clamp(r[3], 0, nc), b_lo = ax_clamp(r[4], 0, nc), b_hi = ax_clamp(r[5], 0, nc);
+        const long long na = a_hi > a_lo ? a_hi - a_lo : 0, nb = b_hi > b_lo ? b_hi - b_lo : 0;
+        const long long nr = s_hi > s_lo ? s_hi - s_lo : 0;
+        const float* mat = dmat + off;
+        // the widest range of the list decides the lanes a range gets
+        long long widest = 0;
+        for (long long k = lane; k < nr; k += ST_WAVE) {
+            const long long x_lo = ax_clamp(xr[(size_t)(s_lo + k) * 2], 0, nc), x_hi = ax_clamp(xr[(size_t)(s_lo + k) * 2 + 1], 0, nc);
+            const long long nx = (x_lo == a_lo && x_hi == a_hi) || x_hi <= x_lo ? 0 : x_hi - x_lo;
+            widest = nx > widest ? nx : widest;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const long long o = __shfl_xor(widest, d);
+            widest = o > widest ? o : widest;
+        }
+        int lw = 6;                                         // log2 W
+        if (widest * na <= 32) {
+            lw = 0;
+            while ((1 << lw) < (int)(widest * na)) ++lw;
+        }
+        lw = __builtin_amdgcn_readfirstlane(lw);
+        const int W = 1 << lw, seg = lane >> lw, sl = lane & (W - 1), segs = ST_WAVE >> lw;
+        long long t_wrong = 0, t_tied = 0, t_nan = 0, t_tri = 0;        // this lane's share of the group's totals
+        double sum = 0.0;
+        int present = 0;
+        for (long long base = 0; base < nr; base += segs) {             // (uniform)
+            const long long k = base + seg;
+            long long x_lo = 0, nx = 0;
+            if (k < nr) {
+                x_lo = ax_clamp(xr[(size_t)(s_lo + k) * 2], 0, nc);
+                const long long x_hi = ax_clamp(xr[(size_t)(s_lo + k) * 2 + 1], 0, nc);
+                nx = (x_lo == a_lo && x_hi == a_hi) || x_hi <= x_lo ? 0 : x_hi - x_lo;      // the group's own speaker; an inverted range
+            }
+            const long long items = nx * na;
+            long long wrong = 0, tied = 0, nan = 0;
+            for (long long u = sl; u < items; u += W) {
+                const long long x = items <= 0x7fffffffll ? (long long)((unsigned)u / (unsigned)na) : u / na, a = u - x * na;
+                const float* row = mat + (x_lo + x) * nc;       // d(., X)
+                const float ax = row[a_lo + a];
+                const bool ax_nan = ax != ax;
+                for (long long b = 0; b < nb; ++b) {
+                    const float bx = row[b_lo + b];
+                    const bool isnan_ = ax_nan || bx != bx;
+                    nan += isnan_ ? 1 : 0;
+                    wrong += (!isnan_ && ax > bx) ? 1 : 0;
+                    tied += (!isnan_ && ax == bx) ? 1 : 0;
+                }
+            }
+            t_wrong += wrong;
+            t_tied += tied;
+            t_nan += nan;
+            t_tri += sl == 0 ? items * nb : 0;
+            for (int d = W >> 1; d >= 1; d >>= 1) {                     // (uniform; the partners stay inside the segment)
+                wrong += __shfl_xor(wrong, d);
+                tied += __shfl_xor(tied, d);
+                nan += __shfl_xor(nan, d);
+            }
+            const long long valid = items * nb - nan;
+            const double score = valid > 0 ? ((double)wrong + 0.5 * (double)tied) / (double)valid : 0.0;
+            unsigned long long have = __ballot(sl == 0 && valid > 0);
+            while (have) {                                              // ascending lanes are ascending ranges
+                const int src = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(have));
+                sum += ax_lane_f64(score, src);
+                ++present;
+                have &= have - 1;
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            t_wrong += __shfl_xor(t_wrong, d);
+            t_tied += __shfl_xor(t_tied, d);
+            t_nan += __shfl_xor(t_nan, d);
+            t_tri += __shfl_xor(t_tri, d);
+        }
+        if (lane == 0) {
+            int64_t* o = count + (size_t)g * 5;
+            o[0] = t_wrong; o[1] = t_tied; o[2] = t_nan; o[3] = t_tri; o[4] = present;
+            err[g] = present > 0 ? sum / (double)present : (double)NAN;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int st_dtw_pairs(const float* feat, long n_rows, int D, long st, const int32_t* item_start, const int32_t* item_len, int n_items,
@@ -278,6 +393,19 @@ extern "C" int st_abx_count(const float* dmat, long dmat_len, const int64_t* blk
     ST_CHECK_ARG(NB >= 1 && dmat_len >= 1, "st_abx_count: NB=%d blocks over %ld distances: at least one of each", NB, dmat_len);
     hipLaunchKernelGGL(abx_count_kernel, dim3(NB < AX_MAX_GRID ? NB : AX_MAX_GRID), dim3(AX_CNT_NT), 0, (hipStream_t)stream, dmat, dmat_len, blk, NB,
                        count);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int st_abx_across(const float* dmat, long dmat_len, const int64_t* grp, int NG, const int64_t* xr, long NX, double* err, int64_t* count,
+                             void* stream) {
+    (void)hipGetLastError();
+    ST_CHECK_ARG(dmat && grp && xr && err && count, "st_abx_across: bad arguments");
+    ST_CHECK_ARG(NG >= 1 && dmat_len >= 1 && NX >= 1, "st_abx_across: NG=%d groups and %ld X ranges over %ld distances: at least one of each", NG, NX,
+                 dmat_len);
+    const long wgs = ((long)NG + AX_WAVES - 1) / AX_WAVES;
+    hipLaunchKernelGGL(abx_across_kernel, dim3((unsigned)(wgs < AX_MAX_GRID ? wgs : AX_MAX_GRID)), dim3(AX_NT), 0, (hipStream_t)stream, dmat, dmat_len,
+                       grp, NG, xr, NX, err, count);
     ST_LAUNCH_CHECK();
     return 0;
 }

@@ -751,7 +751,10 @@ class AbxScorer(DirTool):
     hop_length_mfcc / sr, hop_length / sr, time_reduce_factor hop_length / sr), keyed into cells by speaker and context; one
     metrics.abx call scores them.  -> <logdir>/<name>/abx.csv (phone_a,phone_b,cells,triples,error) and abx_phones.csv
     (phone,tokens,items,too_short,too_long), and one printed line.  A missing waveform, a malformed .ali, an .ali without tokens or a file
-    the speaker map lacks stops the run in load_data, naming the file, before any device work."""
+    the speaker map lacks stops the run in load_data, naming the file, before any device work.
+    --abx-mode across | both (with --abx-spk-map, at least two speakers) scores the same features and items across speakers as well
+    (metrics.abx_across, matrices and pair tables up to --abx-max-gb): abx_across.csv (phone_a,phone_b,groups,triples,error),
+    abx_across_speakers.csv (speaker,groups,error) and a printed line of its own; `across` alone leaves abx.csv unwritten."""
 
     def __init__(self, config, paras, mode):
         super().__init__(config, paras, mode)
@@ -761,6 +764,8 @@ class AbxScorer(DirTool):
         self.ignore = tuple(getattr(paras, 'abx_ignore', None) or ())
         self.max_items = int(getattr(paras, 'abx_max_items', None) or 50)
         self.min_frames = int(getattr(paras, 'abx_min_frames', None) or 1)
+        self.abx_mode = getattr(paras, 'abx_mode', None) or 'within'
+        self.max_bytes = int(float(getattr(paras, 'abx_max_gb', None) or 8) * (1 << 30))
 
     def load_data(self):
         from . import abx as A
@@ -777,6 +782,9 @@ class AbxScorer(DirTool):
                 if key not in table:
                     raise ValueError('--abx-spk-map %s has no row for %s' % (spk_map, f))
                 self.speakers[k] = table[key]
+        if self.abx_mode != 'within' and len(set(self.speakers)) < 2:
+            raise ValueError('--abx-mode %s needs --abx-spk-map FILE with at least two speakers among the files (got %s)'
+                             % (self.abx_mode, 'no map' if not spk_map else '%d speaker' % len(set(self.speakers))))
         self.audio_converter = conv = load_audio_transform(**dict(self.config['data']['audio']))
         for _, _, w in self.pairs:
             path = os.path.join(self.wav_dir, w)
@@ -841,6 +849,7 @@ class AbxScorer(DirTool):
         names = sorted({r[0] for r in rows})
         cells = {c: i for i, c in enumerate(sorted({r[3] for r in rows}))}
         lab = {s: i for i, s in enumerate(names)}
+        self.item_keys = [r[3] for r in rows]                       # (speaker, previous, next) or (speaker,): what exec_across splits
         return (np.array([r[1] for r in rows], np.int64), np.array([r[2] for r in rows], np.int64), np.array([lab[r[0]] for r in rows], np.int64),
                 np.array([cells[r[3]] for r in rows], np.int64), names, stats)
 
@@ -850,7 +859,13 @@ class AbxScorer(DirTool):
         t0 = time.perf_counter()
         feat, first, n_rows = self.features()
         start, length, label, cell, names, stats = self.items(first, n_rows)
+        if self.abx_mode != 'within' and len({k[0] for k in self.item_keys}) < 2:
+            raise ValueError('--abx-mode %s: the kept items come from fewer than two speakers; --abx-spk-map must name at least two' % self.abx_mode)
         os.makedirs(self.logdir, exist_ok=True)
+        if self.abx_mode == 'across':
+            with open(os.path.join(self.logdir, 'abx_phones.csv'), 'w') as f:
+                f.write(A.format_phones_csv(stats))
+            return self.exec_across(feat, start, length, label, names)
         self.result = res = abx(feat, start, length, label, cell, self.metric, self.max_items, int(getattr(self.paras, 'seed', 0)))
         with open(os.path.join(self.logdir, 'abx.csv'), 'w') as f:
             f.write(A.format_abx_csv(res.table, names))
@@ -859,6 +874,29 @@ class AbxScorer(DirTool):
         print('[INFO]', 'ABX error of %s (%s, context %s): %.2f %% over %d phone pairs, %d triples, %d pairs of DTW; %s, %.2f s'
               % (self.feat, self.metric, self.context, 100.0 * res.score, len(res.table), sum(r[3] for r in res.table), res.pairs,
                  os.path.join(self.logdir, 'abx.csv'), time.perf_counter() - t0))
+        if self.abx_mode == 'both':
+            self.exec_across(feat, start, length, label, names)
+        return len(res.table)
+
+    def exec_across(self, feat, start, length, label, names):
+        """the across-speaker score of the items of exec: abx_across.csv, abx_across_speakers.csv and one printed line"""
+        from . import abx as A
+        from .metrics import abx_across
+        t0 = time.perf_counter()
+        spk_names = sorted({k[0] for k in self.item_keys})
+        ctx = {c: i for i, c in enumerate(sorted({k[1:] for k in self.item_keys}))}
+        spk = {s: i for i, s in enumerate(spk_names)}
+        speaker = np.array([spk[k[0]] for k in self.item_keys], np.int64)
+        context = np.array([ctx[k[1:]] for k in self.item_keys], np.int64)
+        self.result_across = res = abx_across(feat, start, length, label, context, speaker, self.metric, self.max_items,
+                                              int(getattr(self.paras, 'seed', 0)), self.max_bytes)
+        with open(os.path.join(self.logdir, 'abx_across.csv'), 'w') as f:
+            f.write(A.format_abx_across_csv(res.table, names))
+        with open(os.path.join(self.logdir, 'abx_across_speakers.csv'), 'w') as f:
+            f.write(A.format_abx_across_speakers_csv(res.speakers, spk_names))
+        print('[INFO]', 'across-speaker ABX error of %s (%s, context %s): %.2f %% over %d phone pairs, %d groups, %d triples, %d pairs of DTW; %s, %.2f s'
+              % (self.feat, self.metric, self.context, 100.0 * res.score, len(res.table), sum(r[2] for r in res.table),
+                 sum(r[3] for r in res.table), res.pairs, os.path.join(self.logdir, 'abx_across.csv'), time.perf_counter() - t0))
         return len(res.table)
 
 

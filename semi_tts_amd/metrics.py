@@ -314,6 +314,60 @@ def abx(feat, item_start, item_len, label, cell, metric='angular', max_items=50,
     return AbxResult(pl.blocks, pl.block_cell, pl.block_a, pl.block_b, counts, agg.table, agg.score, P, pl.keep)
 
 
+AbxAcrossResult = collections.namedtuple('AbxAcrossResult', 'grp xr grp_context grp_speaker grp_a grp_b err counts table score speakers pairs keep')
+
+
+def _abx_across_dmat(dist, pl, dev):
+    """the contexts' matrices with the distances stored and mirrored by one indexed store; entries between items of one speaker (and the
+    diagonal) are never written and never read"""
+    import numpy as np
+    dmat = torch.zeros(pl.dmat_len, device=dev, dtype=torch.float32)
+    dmat[torch.from_numpy(np.concatenate([pl.pos_ab, pl.pos_ba])).to(dev)] = torch.cat([dist, dist])
+    return dmat
+
+
+def abx_across(feat, item_start, item_len, label, context, speaker, metric='angular', max_items=50, seed=0, max_bytes=8 << 30):
+    """Across-speaker ABX phone-discrimination error (see semi_tts_amd.abx): as abx, but A and B are tokens of one speaker and X a
+    token of phone a from ANOTHER speaker of the same context -- the figure that tells whether a representation still carries the
+    speaker.  feat (n_rows, D) float32 on one GPU; item_start / item_len / label / context / speaker host integer sequences, one entry
+    per item.  A (context, speaker, label) group above max_items is subsampled as abx does.  Every cross-speaker pair of a context
+    goes through dtw_pairs once and is mirrored into the context's matrix by one indexed store; st_abx_across then forms, per group
+    (context, speaker, a, b), the pair score (wrong + tied / 2) / (triples - nan) against every other speaker and their float64 mean in
+    ascending speaker order.  err and counts are read once; abx.aggregate_across averages over (context, speaker), then over the ordered
+    phone pairs: Libri-light's order.
+    -> AbxAcrossResult(grp (NG, 8), xr (NX, 2), grp_context, grp_speaker, grp_a, grp_b, err (NG,) float64 numpy, counts (NG, 5) int64
+    numpy, table [(a, b, groups, triples, error)], score, speakers [(speaker, groups, error)], pairs, keep).  Without a group: empty
+    tables and score NaN.  ValueError before the device is touched for tables of different lengths, fewer than two speakers, and
+    matrices and pair tables above max_bytes."""
+    import numpy as np
+    from . import abx as A
+    if not torch.is_tensor(feat) or not feat.is_cuda or feat.dim() != 2 or feat.dtype != torch.float32:
+        raise ValueError('abx_across: feat must be a (n_rows, D) float32 GPU tensor')
+    start, length = np.asarray(item_start, np.int64).reshape(-1), np.asarray(item_len, np.int64).reshape(-1)
+    if not (len(start) == len(length) == len(label) == len(context) == len(speaker)):
+        raise ValueError('abx_across: %d starts, %d lengths, %d labels, %d contexts, %d speakers: one of each per item'
+                         % (len(start), len(length), len(label), len(context), len(speaker)))
+    if len(set(np.asarray(speaker).reshape(-1).tolist())) < 2:
+        raise ValueError('abx_across: the items have fewer than two speakers: X has no other speaker to come from')
+    pl = A.plan_across(label, context, speaker, max_items, seed, max_bytes)
+    if len(pl.grp) == 0:
+        return AbxAcrossResult(pl.grp, pl.xr, pl.grp_context, pl.grp_speaker, pl.grp_a, pl.grp_b, np.zeros(0), np.zeros((0, 5), np.int64), [],
+                               float('nan'), [], 0, pl.keep)
+    dev = feat.device
+    max_len = int(min(max(length[pl.keep].max(), 1), toolops.ABX_MAX_LEN))
+    tabs = torch.from_numpy(np.concatenate([start, length]).astype(np.int32)).to(dev)
+    pairs = torch.from_numpy(np.concatenate([pl.pair_a, pl.pair_b])).to(dev)
+    n, P = len(start), len(pl.pair_a)
+    dist = toolops.dtw_pairs(feat, tabs[:n], tabs[n:], pairs[:P], pairs[P:], metric, max_len)
+    dmat = _abx_across_dmat(dist, pl, dev)                                                                      # (the one mirrored store)
+    err, counts = toolops.abx_across(dmat, torch.from_numpy(pl.grp).to(dev), torch.from_numpy(pl.xr).to(dev))
+    both = torch.cat([err.view(torch.int64).unsqueeze(1), counts], 1).cpu().numpy()                             # (the one host read)
+    err, counts = both[:, 0].copy().view(np.float64), np.ascontiguousarray(both[:, 1:])
+    agg = A.aggregate_across(pl.grp_a, pl.grp_b, pl.grp_speaker, err, counts)
+    return AbxAcrossResult(pl.grp, pl.xr, pl.grp_context, pl.grp_speaker, pl.grp_a, pl.grp_b, err, counts, agg.table, agg.score, agg.speakers, P,
+                           pl.keep)
+
+
 StoiResult = collections.namedtuple('StoiResult', 'score counts energy kept bands')
 
 

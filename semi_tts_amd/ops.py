@@ -1621,7 +1621,7 @@ def device_info():
 
 # the model-free scoring and signal ops live in toolops.py; they stay reachable as ops.X (the tests, tools/ and INTEGRATION.md look them up here)
 from .toolops import (  # noqa: E402,F401
-    abx_count, _abx_ints, ABX_MAX_D, ABX_MAX_LEN, ABX_METRICS, AE_MAX_L, AE_MAX_S, attn_endpoint, audio_features, audio_mfcc, _audio_ws, CA_MAX_L,
+    abx_across, abx_count, _abx_ints, ABX_MAX_D, ABX_MAX_LEN, ABX_METRICS, AE_MAX_L, AE_MAX_S, attn_endpoint, audio_features, audio_mfcc, _audio_ws, CA_MAX_L,
     CA_MAX_T, CA_MAX_V, CA_MIN_V, CB_MAX_ORDER, CB_MAX_T, CB_MAX_TABLE, CB_MAX_V, CB_MAX_W, CB_MIN_V, _chunks, ctc_beam_search, ctc_forced_align,
     ctc_greedy_edit_distance, dtw, DTW_MAX_D, DTW_MAX_T, dtw_pairs, _dtw_side, EA_MAX_IGNORE, EA_MAX_L, EA_MAX_V, edit_align, _f0_check,
     F0_MAX_SPAN, F0_MAX_TAU, F0_MAX_W, f0_path_scores, F0_RUN, f0_run_length, f0_yin, feature_noise, FEATURES_MAX_BATCH, GED_MAX_IGNORE,

@@ -334,7 +334,30 @@ def abx_count(dmat, blk):
     return count
 
 
-AE_MAX_S, AE_MAX_L = 4096, 2048          # st_attn_endpoint's limits
+def abx_across(dmat, grp, xr):
+    """Across-speaker ABX group errors and counts from finished distances (see st_abx_across): dmat, a contiguous 1-d float32 GPU tensor
+    holding the dense matrices of the contexts end to end; grp (NG, 8) int64 on the same device, rows (mat_off, n_c, a_lo, a_hi, b_lo,
+    b_hi, xr_lo, xr_hi); xr (NX, 2) int64, the X index ranges the groups' slices name.
+    -> (err (NG,) float64, count (NG, 5) int64 = (wrong, tied, nan, triples, x_speakers)), device tensors; one launch, exact, no host
+    read.  Bad arguments raise ValueError before the device is touched."""
+    if not torch.is_tensor(dmat) or not dmat.is_cuda or dmat.dim() != 1 or dmat.dtype != torch.float32 or not dmat.is_contiguous():
+        raise ValueError('abx_across: dmat must be a contiguous 1-d float32 GPU tensor (got %s)' % _got(dmat))
+    _abx_ints('abx_across', 'grp', grp, dmat.device, torch.int64, 2)
+    _abx_ints('abx_across', 'xr', xr, dmat.device, torch.int64, 2)
+    NG, NX = grp.shape[0], xr.shape[0]
+    if grp.shape[1] != 8 or NG < 1 or NG >= 2 ** 31 or dmat.shape[0] < 1:
+        raise ValueError('abx_across: grp is %s over %d distances: (NG, 8) with NG >= 1, at least one distance' % (tuple(grp.shape), dmat.shape[0]))
+    if xr.shape[1] != 2 or NX < 1:
+        raise ValueError('abx_across: xr is %s: (NX, 2) with NX >= 1' % (tuple(xr.shape),))
+    lib = _lib.load()
+    err = torch.empty(NG, device=dmat.device, dtype=torch.float64)
+    count = torch.empty(NG, 5, device=dmat.device, dtype=torch.int64)
+    check(lib.st_abx_across(_p(dmat), dmat.shape[0], _p(grp, torch.int64), NG, _p(xr, torch.int64), NX, _p(err, torch.float64), _p(count, torch.int64),
+                            stream_handle()), 'st_abx_across')
+    return err, count
+
+
+AE_MAX_S, AE_MAX_L = 4096, 2048         # st_attn_endpoint's limits
 
 
 def attn_endpoint(align, enc_len, patience=3, max_jump=4):
