@@ -480,7 +480,7 @@ int st_gemm_wgrad_db(const float* dC, int lddc, int dcoff, const float* A, int l
 /* out(n) (+)= sum_m X(m, xoff+n) [* Y(m, yoff+n)]      (bias gradients, AdaIN statistics gradients) */
 int st_colsum(const float* X, int ldx, int xoff, const float* Y, int ldy, int yoff, int M, int N,
               float* out, int accumulate, float* ws, void* stream);
-/* scratch of the row-split column reductions st_bn_stats / st_colsum / st_bn_bwd_reduce (M rows, N columns) */
+/* scratch of the row-split column reductions st_bn_stats(_record) / st_colsum / st_bn_bwd_reduce: <= 128 chunk partials + the result, (2, N) each */
 size_t st_colreduce_workspace_floats(int M, int N);
 /* dpre = dout * mask * act'(out)   (out = the activated forward value; mask may be NULL) */
 int st_act_bwd(const float* dout, int ldd, const float* out, int ldo, int act, const float* mask, int ldm,
@@ -540,32 +540,31 @@ int st_highway_fwd(const float* H, const float* Tgate, const float* x, float* y,
  * positions of an even-k conv before trimming to T); the normalised rows t < Tout go to columns [k N, (k + 1) N) of Y (Bn * Tout rows, stride
  * ldy) -- the concatenated bank, no torch.cat.  Backward: dY (same geometry) -> dx_k over all rows of each segment (rows t >= Tout see
  * dy = 0), optionally through the ReLU in FRONT of the norm (relu_in: x_k = relu(conv), so the factor is x > 0), and (s1, s2) = (d bias, d weight).
- * ws: st_bn_bank_workspace_floats(nseg, max rows, N). */
+ * Both entries read one st_bn_bank_job and run the stages in `stages`: forward ST_BN_STATS | ST_BN_NORM (rec == NULL: 3 launches); under SyncBN
+ * ST_BN_STATS with rec (this rank's (mean, M2, row count) per segment -> rec (nseg, 2N + 1), the batch counted; mean / var not needed) ->
+ * [all-gather] -> ST_BN_MERGE (allrec (world, nseg, 2N + 1) -> global mean / var, running statistics, inv_total[k] = 1 / global rows) -> ST_BN_NORM.
+ * Backward ST_BN_REDUCE | ST_BN_APPLY; under SyncBN ST_BN_REDUCE (local sums -> segs[k].sums) -> [all-reduce] -> ST_BN_APPLY (sums = the global ones).
+ * Other `stages`, or a stage without what it reads or writes: -22 before any launch.  ws: st_bn_bank_workspace_floats(nseg, max rows, N). */
 #define ST_BN_BANK_MAX 16
 typedef struct st_bn_bank_seg {
     const float* x; int ldx; int T;                /* rows b * T + t, b < Bn */
     const float* w; const float* b;                /* weight, bias (N) or NULL */
-    float* run_mean; float* run_var; long long* batches_tracked;   /* updated in place by st_bn_bank_fwd (NULL = none) */
-    float momentum, eps;
-    float* mean; float* var;                       /* (N) out of st_bn_bank_fwd, in of st_bn_bank_bwd */
-    float* dx; int lddx;                           /* st_bn_bank_bwd: out, Bn * T rows */
-    float* sums;                                   /* st_bn_bank_bwd: out (2, N) = (sum dy, sum dy xhat) = (d bias, d weight) */
+    float* run_mean; float* run_var; long long* batches_tracked; float momentum, eps;   /* updated in place by the forward (NULL = none) */
+    float* mean; float* var;                       /* (N) out of STATS / MERGE, in of NORM and the backward */
+    float* dx; int lddx;                           /* APPLY: out, Bn * T rows */
+    float* sums;                                   /* REDUCE: out (2, N) = (sum dy, sum dy xhat) = (d bias, d weight); APPLY: in */
 } st_bn_bank_seg;
+typedef struct st_bn_bank_job {
+    const st_bn_bank_seg* segs; int nseg; int Bn, N;
+    float* Y; const float* dY; int ld; int Tout;   /* the concatenated bank (forward out / backward in), its row stride, frames kept */
+    int relu_in;                                   /* APPLY: dx through the ReLU in front of the norm */
+    float* rec; const float* allrec; int world;    /* SyncBN: this rank's records out; the gathered records in */
+    float* inv_total; float* ws;                   /* inv_total (nseg): written by MERGE, read by APPLY; NULL = local row counts */
+} st_bn_bank_job;
+enum { ST_BN_STATS = 1, ST_BN_MERGE = 2, ST_BN_NORM = 4, ST_BN_REDUCE = 1, ST_BN_APPLY = 2 };   /* stages of _fwd; of _bwd */
 size_t st_bn_bank_workspace_floats(int nseg, int max_rows, int N);
-int st_bn_bank_fwd(const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* Y, int ldy, int Tout, float* ws, void* stream);
-int st_bn_bank_bwd(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* dY, int lddy, int Tout, int relu_in, float* ws,
-                   void* stream);
-/* The same in SyncBN stages (data parallel; the collectives between the stages are the caller's -- ONE all-gather of the records and ONE
- * all-reduce of the sums for the whole bank): st_bn_bank_stats_record writes (mean, M2, row count) of this rank's rows of every segment
- * to rec (nseg, 2N + 1) and counts the batch; st_bn_bank_sync_merge turns the gathered allrec (world, nseg, 2N + 1) into the global mean /
- * var of every segment (running statistics updated) and inv_total (nseg) = 1 / global row count; st_bn_bank_norm normalises.  Backward:
- * st_bn_bank_bwd_reduce leaves this rank's sums in segs[k].sums; st_bn_bank_bwd_apply takes the all-reduced sums there and inv_total. */
-int st_bn_bank_stats_record(const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* rec, float* ws, void* stream);
-int st_bn_bank_sync_merge(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* allrec, int world, float* inv_total, void* stream);
-int st_bn_bank_norm(const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* Y, int ldy, int Tout, void* stream);
-int st_bn_bank_bwd_reduce(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* dY, int lddy, int Tout, float* ws, void* stream);
-int st_bn_bank_bwd_apply(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* dY, int lddy, int Tout, int relu_in,
-                         const float* inv_total, void* stream);
+int st_bn_bank_fwd(const st_bn_bank_job* job, int stages, void* stream);
+int st_bn_bank_bwd(const st_bn_bank_job* job, int stages, void* stream);
 int st_highway_ht_fwd(const float* ht, const float* x, float* y, int M, int C, void* stream);
 int st_highway_ht_bwd(const float* dy, const float* ht, const float* x, float* dht, float* dx_direct, int M, int C, void* stream);
 int st_highway_bwd(const float* dy, const float* H, const float* x, const float* Tgate,

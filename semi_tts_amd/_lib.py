@@ -48,6 +48,11 @@ class StBnBankSeg(C.Structure):
                 ('mean', C.c_void_p), ('var', C.c_void_p), ('dx', C.c_void_p), ('lddx', C.c_int), ('sums', C.c_void_p)]
 
 
+class StBnBankJob(C.Structure):
+    _fields_ = [('segs', C.POINTER(StBnBankSeg)), ('nseg', C.c_int), ('Bn', C.c_int), ('N', C.c_int), ('Y', C.c_void_p), ('dY', C.c_void_p), ('ld', C.c_int),
+                ('Tout', C.c_int), ('relu_in', C.c_int), ('rec', C.c_void_p), ('allrec', C.c_void_p), ('world', C.c_int), ('inv_total', C.c_void_p), ('ws', C.c_void_p)]
+
+
 class StBnBwdJob(C.Structure):
     _fields_ = [('dy', C.c_void_p), ('ldd', C.c_int), ('y', C.c_void_p), ('ldy', C.c_int), ('act', C.c_int), ('x', C.c_void_p), ('ldx', C.c_int),
                 ('mean', C.c_void_p), ('var', C.c_void_p), ('w', C.c_void_p), ('eps', C.c_float), ('M', C.c_int), ('N', C.c_int),
@@ -418,13 +423,8 @@ SIGNATURES = {
     'st_bn_sync_merge': [P, I, I, P, P, P, P, F, P, P],
     'st_highway_fwd': [P, P, P, P, Z, P],
     'st_bn_bank_workspace_floats': [I, I, I],
-    'st_bn_bank_fwd': [C.POINTER(StBnBankSeg), I, I, I, P, I, I, P, P],
-    'st_bn_bank_bwd': [C.POINTER(StBnBankSeg), I, I, I, P, I, I, I, P, P],
-    'st_bn_bank_stats_record': [C.POINTER(StBnBankSeg), I, I, I, P, P, P],
-    'st_bn_bank_sync_merge': [C.POINTER(StBnBankSeg), I, I, I, P, I, P, P],
-    'st_bn_bank_norm': [C.POINTER(StBnBankSeg), I, I, I, P, I, I, P],
-    'st_bn_bank_bwd_reduce': [C.POINTER(StBnBankSeg), I, I, I, P, I, I, P, P],
-    'st_bn_bank_bwd_apply': [C.POINTER(StBnBankSeg), I, I, I, P, I, I, I, P, P],
+    'st_bn_bank_fwd': [C.POINTER(StBnBankJob), I, P],
+    'st_bn_bank_bwd': [C.POINTER(StBnBankJob), I, P],
     'st_highway_ht_fwd': [P, P, P, I, I, P],
     'st_highway_ht_bwd': [P, P, P, P, P, I, I, P],
     'st_highway_bwd': [P, P, P, P, P, P, P, Z, P],

@@ -728,144 +728,6 @@ __global__ __launch_bounds__(256) void highway_stack_kernel(const HwArgs a) {
     }
 }
 
-// ---- training-mode BatchNorm helpers ---------------------------------------------------
-// column statistics, two launches: (1) grid = (column blocks of 64, row chunks): every block reduces its chunk of
-// rows to (mean_c, M2_c) with a chunk-local two-pass (the second pass re-reads <= 64 KB from cache);
-// (2) one thread per column merges the chunks in a fixed order (Chan et al.: exact pairwise update of mean / M2).
-__global__ __launch_bounds__(256) void bn_stats_chunk_kernel(const float* X, int ldx, int coff, int M, int N, int rows_per_chunk,
-                                                             float* part) {   // part[chunk][2][N]
-    __shared__ float red[4][64];
-    __shared__ float smean[64];
-    const int c = threadIdx.x & 63, rl = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    const bool ok = n < N;
-    const int m0 = blockIdx.y * rows_per_chunk, m1 = min(M, m0 + rows_per_chunk);
-    const float* __restrict__ xp = X + coff + min(n, N - 1);
-    // rows m0 + rl, + 4, ...: four independent running sums (rows 16 apart) keep four loads in flight per thread -- with one sum the
-    // loop is a chain of dependent round trips (12.9 us per 4 MB layer in round 2's form)
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int m = m0 + rl;
-    for (; m + 12 < m1; m += 16) {
-        s0 += xp[(size_t)m * ldx]; s1 += xp[(size_t)(m + 4) * ldx]; s2 += xp[(size_t)(m + 8) * ldx]; s3 += xp[(size_t)(m + 12) * ldx];
-    }
-    for (; m < m1; m += 4) s0 += xp[(size_t)m * ldx];
-    red[rl][c] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (rl == 0) smean[c] = (red[0][c] + red[1][c] + red[2][c] + red[3][c]) / (float)max(m1 - m0, 1);
-    __syncthreads();
-    const float mean = smean[c];
-    float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-    m = m0 + rl;
-    for (; m + 12 < m1; m += 16) {      // (second pass: the chunk's rows come from cache)
-        const float d0 = xp[(size_t)m * ldx] - mean, d1 = xp[(size_t)(m + 4) * ldx] - mean;
-        const float d2 = xp[(size_t)(m + 8) * ldx] - mean, d3 = xp[(size_t)(m + 12) * ldx] - mean;
-        q0 = fmaf(d0, d0, q0); q1 = fmaf(d1, d1, q1); q2 = fmaf(d2, d2, q2); q3 = fmaf(d3, d3, q3);
-    }
-    for (; m < m1; m += 4) { const float d = xp[(size_t)m * ldx] - mean; q0 = fmaf(d, d, q0); }
-    __syncthreads();
-    red[rl][c] = (q0 + q1) + (q2 + q3);
-    __syncthreads();
-    if (rl == 0 && ok) {
-        part[((size_t)blockIdx.y * 2 + 0) * N + n] = mean;
-        part[((size_t)blockIdx.y * 2 + 1) * N + n] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
-    }
-}
-
-// merge of the chunk records: 16 columns x 16 chunk lanes per workgroup; lane j holds chunks j, j + 16, ... (at most 8: chunks <= 128)
-// in REGISTERS -- all its loads are issued at once, one memory round trip for both sweeps -- and the 16 lanes' sums are combined
-// through LDS in a fixed order.
-//   mean = sum_c n_c mean_c / M;   M2 = sum_c [M2_c + n_c (mean_c - mean)^2]      (exact decomposition, Chan et al.)
-// (one thread per column walking all the chunks took 16 us per layer: 2 x 64 dependent-latency iterations)
-__global__ __launch_bounds__(256) void bn_stats_final_kernel(const float* part, int chunks, int rows_per_chunk, int M, int N,
-                                                             float* mean_out, float* var_out, float* run_mean, float* run_var,
-                                                             float momentum, long long* batches_tracked, int as_record) {
-    constexpr int CL = 16, PER = 8;
-    __shared__ float red[CL][16];
-    __shared__ float smean[16];
-    const int c = threadIdx.x & 15, cl = threadIdx.x >> 4;
-    const int n = blockIdx.x * 16 + c;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && batches_tracked) batches_tracked[0] += 1;      // nn.BatchNorm1d.num_batches_tracked, without a launch of its own
-    const bool ok = n < N;
-    const float* pm = part + min(n, N - 1);
-    const size_t cs = (size_t)2 * N;
-    float mu[PER], m2[PER], cnt[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int ch = cl + j * CL;
-        const bool in = ch < chunks;
-        const int chc = in ? ch : 0;
-        // (absent chunks re-read chunk 0 and are zeroed by a FACTOR: `if (!in) m2 = 0` makes the compiler branch around the load and wait)
-        mu[j] = pm[(size_t)chc * cs]; m2[j] = pm[(size_t)chc * cs + N] * (in ? 1.0f : 0.0f);
-        cnt[j] = in ? (float)max(min(M, (ch + 1) * rows_per_chunk) - ch * rows_per_chunk, 0) : 0.0f;
-    }
-    float a = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) a = fmaf(cnt[j], mu[j], a);
-    red[cl][c] = a;
-    __syncthreads();
-    if (cl == 0) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < CL; ++k) t += red[k][c];
-        smean[c] = t / (float)M;
-    }
-    __syncthreads();
-    const float mean = smean[c];
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) { const float d = mu[j] - mean; q += m2[j] + cnt[j] * d * d; }
-    __syncthreads();
-    red[cl][c] = q;
-    __syncthreads();
-    if (cl != 0 || !ok) return;
-    float m2t = 0.f;
-#pragma unroll
-    for (int k = 0; k < CL; ++k) m2t += red[k][c];
-    const float var_b = m2t / (float)M;
-    mean_out[n] = mean;
-    var_out[n] = as_record ? m2t : var_b;          // record form (SyncBN): (mean, M2, row count) of this rank's rows, one buffer
-    if (as_record && n == 0) var_out[N] = (float)M;
-    if (run_mean) {
-        const float var_u = M > 1 ? m2t / (float)(M - 1) : var_b;
-        run_mean[n] = (1.0f - momentum) * run_mean[n] + momentum * mean;
-        run_var[n] = (1.0f - momentum) * run_var[n] + momentum * var_u;
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_sync_merge_kernel(const float* rec, int world, int N, float* mean_out, float* var_out,
-                                                            float* run_mean, float* run_var, float momentum, float* inv_total_out) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t rs = (size_t)2 * N + 1;
-    float total = 0.0f;
-    for (int r = 0; r < world; ++r) total += rec[r * rs + 2 * N];
-    if (n == 0) inv_total_out[0] = 1.0f / total;
-    if (n >= N) return;
-    float a = 0.0f;
-    for (int r = 0; r < world; ++r) a = fmaf(rec[r * rs + 2 * N], rec[r * rs + n], a);
-    const float mean = a / total;
-    float m2 = 0.0f;
-    for (int r = 0; r < world; ++r) { const float d = rec[r * rs + n] - mean; m2 += rec[r * rs + N + n] + rec[r * rs + 2 * N] * d * d; }
-    mean_out[n] = mean;
-    var_out[n] = m2 / total;
-    if (run_mean) {
-        run_mean[n] = (1.0f - momentum) * run_mean[n] + momentum * mean;
-        run_var[n] = (1.0f - momentum) * run_var[n] + momentum * (m2 / fmaxf(total - 1.0f, 1.0f));
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_apply_kernel(float* X, int ldx, int coff, int M, int N,
-                                                       const float* mean, const float* var, const float* w,
-                                                       const float* b, float eps, int act) {
-    const size_t total = (size_t)M * N;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int m = (int)(i / N), n = (int)(i - (size_t)m * N);
-        float* p = X + (size_t)m * ldx + coff + n;
-        float v = (*p - mean[n]) / sqrtf(var[n] + eps);
-        v = v * (w ? w[n] : 1.0f) + (b ? b[n] : 0.0f);
-        *p = st_act(v, act);
-    }
-}
-
 }  // namespace
 
 // Tile of the LDS-DMA kernel for an (M, N) product (measured on the shapes of one C2 / C5 forward, tools/gemm_lab2.hip):
@@ -1107,53 +969,6 @@ extern "C" int st_gemm_fwd(const float* A, int lda, const float* W, float* C, in
     return 0;
 }
 
-// the two launches of the batch statistics: chunk-local (mean, M2), then their merge into out0 / out1 -- (mean, biased variance) with
-// the running update, or record = 1: (mean, M2) and the row count behind them
-static int bn_stats_launch(const float* X, int ldx, int coff, int M, int N, float* out0, float* out1, float* run_mean, float* run_var,
-                           float momentum, long long* batches_tracked, int record, float* ws, void* stream) {
-    const int chunks = st_colreduce_chunks(M);
-    const int rpc = (M + chunks - 1) / chunks;
-    hipLaunchKernelGGL(bn_stats_chunk_kernel, dim3((N + 63) / 64, chunks), dim3(256), 0, (hipStream_t)stream, X, ldx, coff, M, N, rpc, ws);
-    ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream,
-                       ws, chunks, rpc, M, N, out0, out1, run_mean, run_var, momentum, batches_tracked, record);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int st_bn_stats(const float* X, int ldx, int coff, int M, int N, float* mean_out, float* var_out,
-                           float* run_mean, float* run_var, float momentum, long long* batches_tracked, float* ws, void* stream) {
-    (void)hipGetLastError();  // drop stale errors left by other HIP users of this thread
-    ST_CHECK_ARG(X && mean_out && var_out && M > 0 && N > 0, "st_bn_stats: bad arguments");
-    ST_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr), "st_bn_stats: run_mean/run_var must both be given");
-    ST_CHECK_ARG(ws, "st_bn_stats: null workspace (st_colreduce_workspace_floats)");
-    const int chunks = st_colreduce_chunks(M);
-    ST_CHECK_ARG(chunks <= 128, "st_bn_stats: %d chunks (the merge kernel holds at most 128)", chunks);
-    return bn_stats_launch(X, ldx, coff, M, N, mean_out, var_out, run_mean, run_var, momentum, batches_tracked, 0, ws, stream);
-}
-
-// SyncBN, local half: rec = (mean[N], M2[N], row count) of THIS rank's rows -- what the ranks exchange in one all-gather
-extern "C" int st_bn_stats_record(const float* X, int ldx, int coff, int M, int N, float* rec, long long* batches_tracked, float* ws,
-                                  void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(X && rec && ws && M > 0 && N > 0, "st_bn_stats_record: bad arguments");
-    return bn_stats_launch(X, ldx, coff, M, N, rec, rec + N, nullptr, nullptr, 0.0f, batches_tracked, 1, ws, stream);
-}
-
-// SyncBN, merged half: the gathered records of all ranks (world, 2N + 1) -> the statistics of the global batch, merged exactly and in
-// rank order (Chan et al.), identically on every rank; running statistics updated as nn.BatchNorm1d does (unbiased variance over the
-// GLOBAL row count); inv_total_out = 1 / (global row count), the factor the backward's two sums are divided by
-extern "C" int st_bn_sync_merge(const float* rec, int world, int N, float* mean_out, float* var_out, float* run_mean, float* run_var,
-                                float momentum, float* inv_total_out, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(rec && mean_out && var_out && inv_total_out && world > 0 && N > 0, "st_bn_sync_merge: bad arguments");
-    ST_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr), "st_bn_sync_merge: run_mean/run_var must both be given");
-    hipLaunchKernelGGL(bn_sync_merge_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, rec, world, N, mean_out, var_out,
-                       run_mean, run_var, momentum, inv_total_out);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int st_highway_stack_supported(int C, int n_layers) { return C > 0 && C % 16 == 0 && C <= HW_MAXC && n_layers >= 1 && n_layers <= HW_MAXL; }
 
 extern "C" int st_highway_stack_fwd(const float* x, int ldx, const float* const* w_h, const float* const* b_h, const float* const* w_t,
@@ -1174,19 +989,6 @@ extern "C" int st_highway_stack_fwd(const float* x, int ldx, const float* const*
     static size_t lds_set = 0;
     if (int rc = st_lds_opt_in(reinterpret_cast<const void*>(highway_stack_kernel), lds, lds > 48 * 1024, lds_set)) return rc;
     hipLaunchKernelGGL(highway_stack_kernel, dim3((M + HW_ROWS - 1) / HW_ROWS), dim3(256), lds, (hipStream_t)stream, a);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int st_bn_apply(float* X, int ldx, int coff, int M, int N, const float* mean, const float* var,
-                           const float* w, const float* b, float eps, int act, void* stream) {
-    (void)hipGetLastError();  // drop stale errors left by other HIP users of this thread
-    ST_CHECK_ARG(X && mean && var && M > 0 && N > 0, "st_bn_apply: bad arguments");
-    const size_t total = (size_t)M * N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       X, ldx, coff, M, N, mean, var, w, b, eps, act);
     ST_LAUNCH_CHECK();
     return 0;
 }

@@ -6,9 +6,9 @@
 //    into partial slabs that a second kernel adds in a fixed order (deterministic, no atomics).
 //  * the input gradient of a conv/linear is the FORWARD kernel (st_gemm_fwd) on dC with the
 //    weight transposed and tap-flipped by the caller, so nothing is needed here for it.
-//  * column sums (bias gradients), BatchNorm backward (training statistics), activation / dropout
-//    backward, Highway backward, the fused max-pool backward, strided copies and row scatter-add.
-#include "st_common.h"
+//  * column sums (bias gradients), activation / dropout backward, Highway backward, the fused max-pool
+//    backward, strided copies and row scatter-add.  (BatchNorm, forward and backward: batchnorm.hip.)
+#include "colreduce.h"
 
 namespace {
 
@@ -665,15 +665,6 @@ __global__ __launch_bounds__(256) void colsum_wide_kernel(const float* X, int ld
     *o = r;
 }
 
-__device__ __forceinline__ float act_grad(float out, int act) {
-    switch (act) {
-        case ST_ACT_RELU: return out > 0.0f ? 1.0f : 0.0f;
-        case ST_ACT_TANH: return 1.0f - out * out;
-        case ST_ACT_SIGMOID: return out * (1.0f - out);
-        default: return 1.0f;
-    }
-}
-
 // dpre = dout * mask * act'(out)      (2-D strided views, M x N)
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* dout, int ldd, const float* out, int ldo, int act,
                                                       const float* mask, int ldm, float* dpre, int ldp, int M, int N) {
@@ -685,100 +676,6 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* dout, int ldd
         if (mask) g *= mask[m * ldm + n];
         if (act != ST_ACT_NONE) g *= act_grad(out[m * ldo + n], act);
         dpre[m * ldp + n] = g;
-    }
-}
-
-// BatchNorm (batch statistics) backward.  y = act((x - mean) / sqrt(var + eps) * w + b).
-//   pass 1 (bn_bwd_reduce): s1[n] = sum dyb, s2[n] = sum dyb * xhat     with dyb = dy * act'(y)
-//   pass 2 (bn_bwd_apply):  dx = w / sigma * (dyb - s1/M - xhat * s2/M)
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff,
-                                                            int act, const float* x, int ldx, int xoff, const float* mean,
-                                                            const float* var, float eps, int M, int N, int rows_per_chunk,
-                                                            float* part, const float* mask = nullptr, int ldm = 0) {   // part[chunk][2][N]
-    __shared__ float r1[4][64], r2[4][64];
-    const int c = threadIdx.x & 63, rl = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    const int nc = min(n, N - 1);
-    const int m0 = blockIdx.y * rows_per_chunk, m1 = min(M, m0 + rows_per_chunk);
-    const float mu = mean[nc], inv = 1.0f / sqrtf(var[nc] + eps);
-    const float* __restrict__ dp = dy + doff + nc;
-    const float* __restrict__ xp = x + xoff + nc;
-    const float* __restrict__ yp = act != ST_ACT_NONE ? y + yoff + nc : nullptr;
-    const float* __restrict__ kp = mask ? mask + nc : nullptr;        // dropout mask behind the activation: dyb = dy * mask * act'(y)
-    // two rows per pass with independent sums: (up to) six loads in flight per thread instead of a chain of dependent round trips
-    float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
-    int m = m0 + rl;
-    for (; m + 4 < m1; m += 8) {
-        float g0 = dp[(size_t)m * ldd], g1 = dp[(size_t)(m + 4) * ldd];
-        const float x0 = xp[(size_t)m * ldx], x1 = xp[(size_t)(m + 4) * ldx];
-        if (kp) { g0 *= kp[(size_t)m * ldm]; g1 *= kp[(size_t)(m + 4) * ldm]; }
-        if (yp) { g0 *= act_grad(yp[(size_t)m * ldy], act); g1 *= act_grad(yp[(size_t)(m + 4) * ldy], act); }
-        a0 += g0; a1 += g1;
-        b0 = fmaf(g0, (x0 - mu) * inv, b0); b1 = fmaf(g1, (x1 - mu) * inv, b1);
-    }
-    for (; m < m1; m += 4) {
-        float g = dp[(size_t)m * ldd];
-        if (kp) g *= kp[(size_t)m * ldm];
-        if (yp) g *= act_grad(yp[(size_t)m * ldy], act);
-        a0 += g;
-        b0 = fmaf(g, (xp[(size_t)m * ldx] - mu) * inv, b0);
-    }
-    r1[rl][c] = a0 + a1; r2[rl][c] = b0 + b1;
-    __syncthreads();
-    if (rl == 0 && n < N) {
-        part[((size_t)blockIdx.y * 2 + 0) * N + n] = r1[0][c] + r1[1][c] + r1[2][c] + r1[3][c];
-        part[((size_t)blockIdx.y * 2 + 1) * N + n] = r2[0][c] + r2[1][c] + r2[2][c] + r2[3][c];
-    }
-}
-
-// out[q][n] (+)= sum_chunks part[chunk][q][n], q < Q.  16 (q, n) pairs x 16 chunk lanes per workgroup: lane j adds chunks j, j + 16, ...
-// (at most 8, all loads issued at once), the lanes' sums are combined through LDS in a fixed order.
-__global__ __launch_bounds__(256) void chunk_final_kernel(const float* part, int chunks, int Q, int N, float* out0, float* out1,
-                                                          int accumulate) {
-    constexpr int CL = 16, PER = 8;
-    __shared__ float red[CL][16];
-    const int c = threadIdx.x & 15, cl = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + c;
-    const bool ok = i < Q * N;
-    const int ic = min(i, Q * N - 1);
-    const int q = ic / N, n = ic - q * N;
-    const float* p = part + (size_t)q * N + n;
-    const size_t cs = (size_t)Q * N;
-    float v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) { const int ch = cl + j * CL; v[j] = p[(size_t)(ch < chunks ? ch : 0) * cs] * (ch < chunks ? 1.0f : 0.0f); }   // (a factor, not a select: no branch + wait per load)
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) s += v[j];
-    red[cl][c] = s;
-    __syncthreads();
-    if (cl != 0 || !ok) return;
-    float* out = q == 0 ? out0 : out1;
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < CL; ++k) t += red[k][c];
-    out[n] = accumulate ? out[n] + t : t;
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int ldd, int doff, const float* y, int ldy, int yoff,
-                                                           int act, const float* x, int ldx, int xoff, const float* mean,
-                                                           const float* var, const float* w, float eps, int M, int N,
-                                                           const float* s1, const float* s2, float* dx, int lddx, int dxoff,
-                                                           int Mstat, const float* inv_total, const float* mask = nullptr, int ldm = 0,
-                                                           float* dres = nullptr, int lddr = 0) {
-    const size_t total = (size_t)M * N;
-    // rows the statistics (and s1, s2) were taken over: > M under SyncBN, where 1 / (global row count) comes as a device scalar
-    const float invM = inv_total ? inv_total[0] : 1.0f / (float)Mstat;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t m = i / N;
-        const int n = (int)(i - m * N);
-        float g = dy[m * ldd + doff + n];
-        if (mask) g *= mask[m * ldm + n];
-        if (dres) dres[m * lddr + n] = g;          // the gradient of a residual input added behind the activation, in front of the mask
-        if (act != ST_ACT_NONE) g *= act_grad(y[m * ldy + yoff + n], act);
-        const float inv = 1.0f / sqrtf(var[n] + eps);
-        const float xh = (x[m * ldx + xoff + n] - mean[n]) * inv;
-        dx[m * lddx + dxoff + n] = (w ? w[n] : 1.0f) * inv * (g - s1[n] * invM - xh * s2[n] * invM);
     }
 }
 
@@ -879,340 +776,11 @@ __global__ __launch_bounds__(512) void scatter_add_rows_kernel(const float* dout
     dtable[(size_t)v * D + d] += s;
 }
 
-// out-of-place BatchNorm normalisation: Y = act((X - mean) / sqrt(var + eps) * w + b); X is kept for the backward
-__global__ __launch_bounds__(256) void bn_norm_fwd_kernel(const float* X, int ldx, int xoff, float* Y, int ldy, int yoff,
-                                                          int M, int N, const float* mean, const float* var, const float* w,
-                                                          const float* b, float eps, int act) {
-    const size_t total = (size_t)M * N;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t m = i / N;
-        const int n = (int)(i - m * N);
-        float v = (X[m * ldx + xoff + n] - mean[n]) / sqrtf(var[n] + eps);
-        v = v * (w ? w[n] : 1.0f) + (b ? b[n] : 0.0f);
-        Y[m * ldy + yoff + n] = st_act(v, act);
-    }
-}
-
-// ConvLayer's tail in training (src/module.py:641-646): T = act(BatchNorm(X)) kept for the backward, Y = (T + res) * mask the layer's output
-// (res, mask optional); 16-byte pieces (N % 4 == 0, all rows 16-byte aligned)
-__global__ __launch_bounds__(256) void bn_norm_res_mask_fwd_kernel(const float* __restrict__ X, float* __restrict__ Tact, float* __restrict__ Y,
-                                                                   int N4, size_t total4, const float* __restrict__ mean,
-                                                                   const float* __restrict__ var, const float* __restrict__ w,
-                                                                   const float* __restrict__ b, float eps, int act,
-                                                                   const float* __restrict__ res, const float* __restrict__ mask) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
-        const int n = 4 * (int)(i % N4);
-        const f32x4 x = st_ld4(X + 4 * i), mu = st_ld4(mean + n), vr = st_ld4(var + n);
-        f32x4 g = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f}, r = {0.f, 0.f, 0.f, 0.f}, k = {1.f, 1.f, 1.f, 1.f};
-        if (w) g = st_ld4(w + n);
-        if (b) be = st_ld4(b + n);
-        if (res) r = st_ld4(res + 4 * i);
-        if (mask) k = st_ld4(mask + 4 * i);
-        f32x4 t, y;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float v = (x[j] - mu[j]) / sqrtf(vr[j] + eps);           // (bn_norm_fwd_kernel's expression, element for element)
-            v = v * g[j] + be[j];
-            t[j] = st_act(v, act);
-            y[j] = (t[j] + r[j]) * k[j];
-        }
-        if (Tact) *reinterpret_cast<f32x4*>(Tact + 4 * i) = t;
-        *reinterpret_cast<f32x4*>(Y + 4 * i) = y;
-    }
-}
-
 // Highway combine (training forward keeps H and T): y = H * T + x * (1 - T)      ref: src/module.py:554
 __global__ __launch_bounds__(256) void highway_fwd_kernel(const float* H, const float* T, const float* x, float* y, size_t total) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const float t = T[i];
         y[i] = st_highway(H[i], t, x[i]);
-    }
-}
-
-// ---- the K BatchNorm1d layers of a conv bank, one launch per phase (see st_bn_bank_fwd) ----------------------------------------------------
-// The per-layer kernels above with a segment index in the grid: same chunking of the rows per segment, same merge order, so a bank of one
-// segment gives bit for bit the statistics, output and sums of st_bn_stats / st_bn_norm_fwd / st_bn_bwd_reduce.  Its dx agrees to rounding: the two
-// apply kernels compile to different multiply-add sequences.  part: [seg][chunk][2][N].
-struct BnBank { st_bn_bank_seg s[ST_BN_BANK_MAX]; int nseg, Bn, N; };
-
-__global__ __launch_bounds__(256) void bnb_stats_chunk_kernel(const BnBank a, float* part, int max_chunks) {
-    __shared__ float red[4][64];
-    __shared__ float smean[64];
-    const st_bn_bank_seg& sg = a.s[blockIdx.z];
-    const int N = a.N, M = a.Bn * sg.T;
-    const int chunks = st_colreduce_chunks(M), rpc = (M + chunks - 1) / chunks;
-    if ((int)blockIdx.y >= chunks) return;
-    const int c = threadIdx.x & 63, rl = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    const bool ok = n < N;
-    const int m0 = blockIdx.y * rpc, m1 = min(M, m0 + rpc);
-    const int ldx = sg.ldx;
-    const float* __restrict__ xp = sg.x + min(n, N - 1);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int m = m0 + rl;
-    for (; m + 12 < m1; m += 16) {
-        s0 += xp[(size_t)m * ldx]; s1 += xp[(size_t)(m + 4) * ldx]; s2 += xp[(size_t)(m + 8) * ldx]; s3 += xp[(size_t)(m + 12) * ldx];
-    }
-    for (; m < m1; m += 4) s0 += xp[(size_t)m * ldx];
-    red[rl][c] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (rl == 0) smean[c] = (red[0][c] + red[1][c] + red[2][c] + red[3][c]) / (float)max(m1 - m0, 1);
-    __syncthreads();
-    const float mean = smean[c];
-    float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-    m = m0 + rl;
-    for (; m + 12 < m1; m += 16) {
-        const float d0 = xp[(size_t)m * ldx] - mean, d1 = xp[(size_t)(m + 4) * ldx] - mean;
-        const float d2 = xp[(size_t)(m + 8) * ldx] - mean, d3 = xp[(size_t)(m + 12) * ldx] - mean;
-        q0 = fmaf(d0, d0, q0); q1 = fmaf(d1, d1, q1); q2 = fmaf(d2, d2, q2); q3 = fmaf(d3, d3, q3);
-    }
-    for (; m < m1; m += 4) { const float d = xp[(size_t)m * ldx] - mean; q0 = fmaf(d, d, q0); }
-    __syncthreads();
-    red[rl][c] = (q0 + q1) + (q2 + q3);
-    __syncthreads();
-    if (rl == 0 && ok) {
-        float* pp = part + ((size_t)blockIdx.z * max_chunks + blockIdx.y) * 2 * N;
-        pp[n] = mean;
-        pp[N + n] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
-    }
-}
-
-// rec != NULL (SyncBN, local half): (mean, M2, row count) of segment k go to rec[k (2N + 1) ..]; nothing else is written but batches_tracked
-__global__ __launch_bounds__(256) void bnb_stats_final_kernel(const BnBank a, const float* part, int max_chunks, float* rec) {
-    constexpr int CL = 16, PER = 8;
-    __shared__ float red[CL][16];
-    __shared__ float smean[16];
-    const st_bn_bank_seg& sg = a.s[blockIdx.y];
-    const int N = a.N, M = a.Bn * sg.T;
-    const int chunks = st_colreduce_chunks(M), rpc = (M + chunks - 1) / chunks;
-    const int c = threadIdx.x & 15, cl = threadIdx.x >> 4;
-    const int n = blockIdx.x * 16 + c;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && sg.batches_tracked) sg.batches_tracked[0] += 1;
-    const bool ok = n < N;
-    const float* pm = part + (size_t)blockIdx.y * max_chunks * 2 * N + min(n, N - 1);
-    const size_t cs = (size_t)2 * N;
-    float mu[PER], m2[PER], cnt[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int ch = cl + j * CL;
-        const bool in = ch < chunks;
-        const int chc = in ? ch : 0;
-        mu[j] = pm[(size_t)chc * cs]; m2[j] = pm[(size_t)chc * cs + N] * (in ? 1.0f : 0.0f);
-        cnt[j] = in ? (float)max(min(M, (ch + 1) * rpc) - ch * rpc, 0) : 0.0f;
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) acc = fmaf(cnt[j], mu[j], acc);
-    red[cl][c] = acc;
-    __syncthreads();
-    if (cl == 0) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < CL; ++k) t += red[k][c];
-        smean[c] = t / (float)M;
-    }
-    __syncthreads();
-    const float mean = smean[c];
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) { const float d = mu[j] - mean; q += m2[j] + cnt[j] * d * d; }
-    __syncthreads();
-    red[cl][c] = q;
-    __syncthreads();
-    if (cl != 0 || !ok) return;
-    float m2t = 0.f;
-#pragma unroll
-    for (int k = 0; k < CL; ++k) m2t += red[k][c];
-    const float var_b = m2t / (float)M;
-    if (rec) {
-        float* r = rec + (size_t)blockIdx.y * (2 * N + 1);
-        r[n] = mean; r[N + n] = m2t;
-        if (n == 0) r[2 * N] = (float)M;
-        return;
-    }
-    sg.mean[n] = mean;
-    sg.var[n] = var_b;
-    if (sg.run_mean) {
-        const float var_u = M > 1 ? m2t / (float)(M - 1) : var_b;
-        sg.run_mean[n] = (1.0f - sg.momentum) * sg.run_mean[n] + sg.momentum * mean;
-        sg.run_var[n] = (1.0f - sg.momentum) * sg.run_var[n] + sg.momentum * var_u;
-    }
-}
-
-// SyncBN, merged half for all segments: allrec (world, nseg, 2N + 1) gathered records -> mean / var of the global batch of every segment
-// (+ running statistics) and 1 / (global row count) per segment.  The per-layer bn_sync_merge_kernel with a segment index.
-__global__ __launch_bounds__(256) void bnb_sync_merge_kernel(const BnBank a, const float* allrec, int world, float* inv_total_out) {
-    const int k = blockIdx.y;
-    const st_bn_bank_seg& sg = a.s[k];
-    const int N = a.N;
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t rs = (size_t)2 * N + 1, ws_ = rs * a.nseg;
-    const float* rec = allrec + (size_t)k * rs;
-    float total = 0.0f;
-    for (int r = 0; r < world; ++r) total += rec[r * ws_ + 2 * N];
-    if (n == 0) inv_total_out[k] = 1.0f / total;
-    if (n >= N) return;
-    float acc = 0.0f;
-    for (int r = 0; r < world; ++r) acc = fmaf(rec[r * ws_ + 2 * N], rec[r * ws_ + n], acc);
-    const float mean = acc / total;
-    float m2 = 0.0f;
-    for (int r = 0; r < world; ++r) { const float d = rec[r * ws_ + n] - mean; m2 += rec[r * ws_ + N + n] + rec[r * ws_ + 2 * N] * d * d; }
-    sg.mean[n] = mean;
-    sg.var[n] = m2 / total;
-    if (sg.run_mean) {
-        sg.run_mean[n] = (1.0f - sg.momentum) * sg.run_mean[n] + sg.momentum * mean;
-        sg.run_var[n] = (1.0f - sg.momentum) * sg.run_var[n] + sg.momentum * (m2 / fmaxf(total - 1.0f, 1.0f));
-    }
-}
-
-// Y[(b Tout + t)][k N + n] = BN_k(x_k[b T_k + t][n]), t < Tout.  blockIdx.y = segment (its fields stay in scalar registers); four
-// channels per thread when N % 4 == 0 and the rows are 16-byte addressable
-__global__ __launch_bounds__(256) void bnb_norm_kernel(const BnBank a, float* __restrict__ Y, int ldy, int Tout, int vec) {
-    const int k = blockIdx.y;
-    const st_bn_bank_seg& sg = a.s[k];
-    const int N = a.N, T = sg.T, ldx = sg.ldx;
-    const float* __restrict__ x = sg.x;
-    if (vec) {
-        const int N4 = N >> 2;
-        const size_t total = (size_t)a.Bn * Tout * N4;
-        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-            const size_t r = i / N4;
-            const int n = (int)(i - r * N4) * 4;
-            const int b = (int)(r / Tout), t = (int)(r - (size_t)b * Tout);
-            const f32x4 xv = st_ld4(x + ((size_t)b * T + t) * ldx + n);
-            const f32x4 mu = st_ld4(sg.mean + n), va = st_ld4(sg.var + n);
-            const f32x4 w4 = sg.w ? st_ld4(sg.w + n) : f32x4{1.f, 1.f, 1.f, 1.f}, b4 = sg.b ? st_ld4(sg.b + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-            f32x4 o;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) o[c] = (xv[c] - mu[c]) / sqrtf(va[c] + sg.eps) * w4[c] + b4[c];
-            *reinterpret_cast<f32x4*>(Y + r * ldy + (size_t)k * N + n) = o;
-        }
-        return;
-    }
-    const size_t total = (size_t)a.Bn * Tout * N;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / N;
-        const int n = (int)(i - r * N);
-        const int b = (int)(r / Tout), t = (int)(r - (size_t)b * Tout);
-        float v = (x[((size_t)b * T + t) * ldx + n] - sg.mean[n]) / sqrtf(sg.var[n] + sg.eps);
-        v = v * (sg.w ? sg.w[n] : 1.0f) + (sg.b ? sg.b[n] : 0.0f);
-        Y[r * ldy + (size_t)k * N + n] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void bnb_bwd_reduce_kernel(const BnBank a, const float* __restrict__ dY, int lddy, int Tout, float* part, int max_chunks) {
-    __shared__ float r1[4][64], r2[4][64];
-    const int k = blockIdx.z;
-    const st_bn_bank_seg& sg = a.s[k];
-    const int N = a.N, T = sg.T, M = a.Bn * T;
-    const int chunks = st_colreduce_chunks(M), rpc = (M + chunks - 1) / chunks;
-    if ((int)blockIdx.y >= chunks) return;
-    const int c = threadIdx.x & 63, rl = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    const int nc = min(n, N - 1);
-    const int m0 = blockIdx.y * rpc, m1 = min(M, m0 + rpc);
-    const float mu = sg.mean[nc], inv = 1.0f / sqrtf(sg.var[nc] + sg.eps);
-    const float* __restrict__ dp = dY + (size_t)k * N + nc;
-    const float* __restrict__ xp = sg.x + nc;
-    float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
-    // rows whose frame lies past the bank (t >= Tout: the trimmed position of an even-k conv) have dy = 0 and add nothing
-    auto dyrow = [&](int m) -> float {
-        const int b = m / T, t = m - b * T;
-        const float v = dp[((size_t)b * Tout + min(t, Tout - 1)) * lddy];
-        return v * (t < Tout ? 1.0f : 0.0f);
-    };
-    int m = m0 + rl;
-    for (; m + 4 < m1; m += 8) {
-        const float g0 = dyrow(m), g1 = dyrow(m + 4);
-        const float x0 = xp[(size_t)m * sg.ldx], x1 = xp[(size_t)(m + 4) * sg.ldx];
-        a0 += g0; a1 += g1;
-        b0 = fmaf(g0, (x0 - mu) * inv, b0); b1 = fmaf(g1, (x1 - mu) * inv, b1);
-    }
-    for (; m < m1; m += 4) {
-        const float g = dyrow(m);
-        a0 += g;
-        b0 = fmaf(g, (xp[(size_t)m * sg.ldx] - mu) * inv, b0);
-    }
-    r1[rl][c] = a0 + a1; r2[rl][c] = b0 + b1;
-    __syncthreads();
-    if (rl == 0 && n < N) {
-        float* pp = part + ((size_t)k * max_chunks + blockIdx.y) * 2 * N;
-        pp[n] = r1[0][c] + r1[1][c] + r1[2][c] + r1[3][c];
-        pp[N + n] = r2[0][c] + r2[1][c] + r2[2][c] + r2[3][c];
-    }
-}
-
-// sums_k[q][n] = sum over the segment's chunks of part[k][chunk][q][n]   (chunk_final_kernel's merge order)
-__global__ __launch_bounds__(256) void bnb_bwd_final_kernel(const BnBank a, const float* part, int max_chunks) {
-    constexpr int CL = 16, PER = 8;
-    __shared__ float red[CL][16];
-    const st_bn_bank_seg& sg = a.s[blockIdx.y];
-    const int N = a.N, M = a.Bn * sg.T;
-    const int chunks = st_colreduce_chunks(M);
-    const int c = threadIdx.x & 15, cl = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + c;
-    const bool ok = i < 2 * N;
-    const int ic = min(i, 2 * N - 1);
-    const float* p = part + (size_t)blockIdx.y * max_chunks * 2 * N + ic;
-    const size_t cs = (size_t)2 * N;
-    float v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) { const int ch = cl + j * CL; v[j] = p[(size_t)(ch < chunks ? ch : 0) * cs] * (ch < chunks ? 1.0f : 0.0f); }
-    float sacc = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) sacc += v[j];
-    red[cl][c] = sacc;
-    __syncthreads();
-    if (cl != 0 || !ok) return;
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < CL; ++k) t += red[k][c];
-    sg.sums[ic] = t;
-}
-
-__global__ __launch_bounds__(256) void bnb_bwd_apply_kernel(const BnBank a, const float* __restrict__ dY, int lddy, int Tout, int relu_in, int vec,
-                                                            const float* __restrict__ inv_total) {
-    const int k = blockIdx.y;
-    const st_bn_bank_seg& sg = a.s[k];
-    const int N = a.N, T = sg.T, M = a.Bn * T;
-    // SyncBN: the sums were taken over every rank's rows; 1 / (global row count) of the segment comes as a device scalar
-    const float invM = inv_total ? inv_total[k] : 1.0f / (float)M;
-    if (vec) {      // four channels per thread (N % 4 == 0, 16-byte addressable rows): one row / frame split per four elements
-        const int N4 = N >> 2;
-        const size_t total = (size_t)M * N4;
-        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-            const int m = (int)(i / N4), n = (int)(i - (size_t)m * N4) * 4;
-            const int b = m / T, t = m - b * T;
-            const f32x4 g4 = st_ld4(dY + ((size_t)b * Tout + min(t, Tout - 1)) * lddy + (size_t)k * N + n);
-            const f32x4 xv = st_ld4(sg.x + (size_t)m * sg.ldx + n);
-            const f32x4 mu = st_ld4(sg.mean + n), va = st_ld4(sg.var + n), s1 = st_ld4(sg.sums + n), s2 = st_ld4(sg.sums + N + n);
-            const f32x4 w4 = sg.w ? st_ld4(sg.w + n) : f32x4{1.f, 1.f, 1.f, 1.f};
-            const float on = t < Tout ? 1.0f : 0.0f;
-            f32x4 o;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float g = g4[c] * on;
-                const float inv = 1.0f / sqrtf(va[c] + sg.eps);
-                const float xh = (xv[c] - mu[c]) * inv;
-                float d = w4[c] * inv * (g - s1[c] * invM - xh * s2[c] * invM);
-                if (relu_in) d *= act_grad(xv[c], ST_ACT_RELU);
-                o[c] = d;
-            }
-            *reinterpret_cast<f32x4*>(sg.dx + (size_t)m * sg.lddx + n) = o;
-        }
-        return;
-    }
-    const size_t total = (size_t)M * N;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int m = (int)(i / N), n = (int)(i - (size_t)m * N);
-        const int b = m / T, t = m - b * T;
-        const float g = dY[((size_t)b * Tout + min(t, Tout - 1)) * lddy + (size_t)k * N + n] * (t < Tout ? 1.0f : 0.0f);
-        const float inv = 1.0f / sqrtf(sg.var[n] + sg.eps);
-        const float xv = sg.x[(size_t)m * sg.ldx + n];
-        const float xh = (xv - sg.mean[n]) * inv;
-        float d = (sg.w ? sg.w[n] : 1.0f) * inv * (g - sg.sums[n] * invM - xh * sg.sums[N + n] * invM);
-        if (relu_in) d *= act_grad(xv, ST_ACT_RELU);
-        sg.dx[(size_t)m * sg.lddx + n] = d;
     }
 }
 
@@ -1279,12 +847,6 @@ __global__ __launch_bounds__(256) void relayout_batch_kernel(const st_relayout_d
     if (i0 + 4 <= total && st_aligned16(d.dst + i0)) *reinterpret_cast<f32x4*>(d.dst + i0) = f32x4{v[0], v[1], v[2], v[3]};
     else
         for (int c = 0; c < 4 && i0 + c < total; ++c) d.dst[i0 + c] = v[c];
-}
-
-inline int blocks_for(size_t n, int cap = 4096) {
-    size_t b = (n + 255) / 256;
-    if (b < 1) b = 1;
-    return (int)(b > (size_t)cap ? cap : b);
 }
 
 }  // namespace
@@ -1596,47 +1158,6 @@ extern "C" int st_act_bwd(const float* dout, int ldd, const float* out, int ldo,
     return 0;
 }
 
-// BatchNorm backward in two halves so that a data-parallel caller can all-reduce the two sums in between (SyncBN):
-//   reduce: s[0:N] = sum_rows dyb, s[N:2N] = sum_rows dyb * xhat      (local rows)
-//   apply:  dx = w/sigma * (dyb - s1/Mstat - xhat * s2/Mstat)          (Mstat = rows behind mean / var / s)
-// Both read one st_bn_bwd_job.  Its mask / dres serve a layer whose forward was Y = (act(BN(x)) + res) * mask (st_bn_norm_res_mask_fwd;
-// ConvLayer, src/module.py:641-646): the incoming gradient is multiplied by the mask on the way in (no launch of its own), `y` is the kept
-// act(BN(x)), and the apply half also hands out dres = dy * mask, the gradient of the residual input (NULL: no residual).
-static bool bn_bwd_job_ok(const st_bn_bwd_job& j) {
-    return j.dy && j.x && j.mean && j.var && j.s && j.M > 0 && j.N > 0 && (j.act == ST_ACT_NONE || j.y);
-}
-
-extern "C" int st_bn_bwd_reduce(const st_bn_bwd_job* job, float* ws, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(job, "st_bn_bwd_reduce: null job");
-    const st_bn_bwd_job& j = *job;
-    ST_CHECK_ARG(bn_bwd_job_ok(j) && ws, "st_bn_bwd_reduce: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    float* part = ws + 2 * (size_t)j.N;
-    const int chunks = st_colreduce_chunks(j.M);
-    const int rpc = (j.M + chunks - 1) / chunks;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((j.N + 63) / 64, chunks), dim3(256), 0, st, j.dy, j.ldd, 0, j.y, j.ldy, 0, j.act,
-                       j.x, j.ldx, 0, j.mean, j.var, j.eps, j.M, j.N, rpc, part, j.mask, j.ldm);
-    ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(chunk_final_kernel, dim3((2 * j.N + 15) / 16), dim3(256), 0, st, part, chunks, 2, j.N, j.s, j.s + j.N, 0);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-// inv_total (device scalar, st_bn_sync_merge): s holds the sums over ALL ranks' rows and *inv_total = 1 / their count; the kernel then
-// does not read Mstat
-extern "C" int st_bn_bwd_apply(const st_bn_bwd_job* job, void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(job, "st_bn_bwd_apply: null job");
-    const st_bn_bwd_job& j = *job;
-    ST_CHECK_ARG(bn_bwd_job_ok(j) && j.dx && (j.inv_total || j.Mstat >= j.M), "st_bn_bwd_apply: bad arguments");
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for((size_t)j.M * j.N)), dim3(256), 0, (hipStream_t)stream, j.dy, j.ldd, 0, j.y, j.ldy, 0,
-                       j.act, j.x, j.ldx, 0, j.mean, j.var, j.w, j.eps, j.M, j.N, j.s, j.s + j.N, j.dx, j.lddx, 0, j.Mstat, j.inv_total,
-                       j.mask, j.ldm, j.dres, j.lddr);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int st_highway_bwd(const float* dy, const float* H, const float* x, const float* Tgate,
                               float* dH, float* dT, float* dx_direct, size_t total, void* stream) {
     (void)hipGetLastError();
@@ -1645,128 +1166,6 @@ extern "C" int st_highway_bwd(const float* dy, const float* H, const float* x, c
                        dy, H, x, Tgate, dH, dT, dx_direct, total);
     ST_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" size_t st_bn_bank_workspace_floats(int nseg, int max_rows, int N) {
-    return (size_t)nseg * st_colreduce_chunks(max_rows) * 2 * N;
-}
-
-static int bnb_fill(BnBank& a, const st_bn_bank_seg* segs, int nseg, int Bn, int N, int& max_chunks, size_t& max_rows, const char* who) {
-    ST_CHECK_ARG(segs && nseg > 0 && nseg <= ST_BN_BANK_MAX && Bn > 0 && N > 0, "%s: bad arguments (at most %d segments)", who, ST_BN_BANK_MAX);
-    a.nseg = nseg; a.Bn = Bn; a.N = N;
-    max_chunks = 1; max_rows = 0;
-    for (int k = 0; k < nseg; ++k) {
-        ST_CHECK_ARG(segs[k].x && segs[k].T > 0 && segs[k].ldx >= N && segs[k].mean && segs[k].var, "%s: segment %d incomplete", who, k);
-        a.s[k] = segs[k];
-        const int M = Bn * segs[k].T;
-        max_chunks = max(max_chunks, st_colreduce_chunks(M));
-        max_rows = max(max_rows, (size_t)M);
-    }
-    return 0;
-}
-
-static int bnb_norm_launch(const BnBank& a, const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* Y, int ldy, int Tout, hipStream_t st);
-
-extern "C" int st_bn_bank_fwd(const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* Y, int ldy, int Tout, float* ws, void* stream) {
-    (void)hipGetLastError();
-    BnBank a; int mc; size_t mr;
-    { const int rc = bnb_fill(a, segs, nseg, Bn, N, mc, mr, "st_bn_bank_fwd"); if (rc) return rc; }
-    ST_CHECK_ARG(Y && ws && Tout > 0 && ldy >= nseg * N, "st_bn_bank_fwd: bad output / workspace");
-    for (int k = 0; k < nseg; ++k) ST_CHECK_ARG(segs[k].T >= Tout, "st_bn_bank_fwd: segment %d has %d frames, the bank %d", k, segs[k].T, Tout);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bnb_stats_chunk_kernel, dim3((N + 63) / 64, mc, nseg), dim3(256), 0, st, a, ws, mc);
-    ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bnb_stats_final_kernel, dim3((N + 15) / 16, nseg), dim3(256), 0, st, a, ws, mc, (float*)nullptr);
-    ST_LAUNCH_CHECK();
-    return bnb_norm_launch(a, segs, nseg, Bn, N, Y, ldy, Tout, st);
-}
-
-// ---- the same in its SyncBN stages (the collectives between them are the caller's): records -> [all-gather] -> merge -> normalise
-extern "C" int st_bn_bank_stats_record(const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* rec, float* ws, void* stream) {
-    (void)hipGetLastError();
-    BnBank a; int mc; size_t mr;
-    { const int rc = bnb_fill(a, segs, nseg, Bn, N, mc, mr, "st_bn_bank_stats_record"); if (rc) return rc; }
-    ST_CHECK_ARG(rec && ws, "st_bn_bank_stats_record: null record / workspace");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bnb_stats_chunk_kernel, dim3((N + 63) / 64, mc, nseg), dim3(256), 0, st, a, ws, mc);
-    ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bnb_stats_final_kernel, dim3((N + 15) / 16, nseg), dim3(256), 0, st, a, ws, mc, rec);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int st_bn_bank_sync_merge(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* allrec, int world, float* inv_total,
-                                     void* stream) {
-    (void)hipGetLastError();
-    BnBank a; int mc; size_t mr;
-    { const int rc = bnb_fill(a, segs, nseg, Bn, N, mc, mr, "st_bn_bank_sync_merge"); if (rc) return rc; }
-    ST_CHECK_ARG(allrec && world > 0 && inv_total, "st_bn_bank_sync_merge: bad arguments");
-    hipLaunchKernelGGL(bnb_sync_merge_kernel, dim3((N + 255) / 256, nseg), dim3(256), 0, (hipStream_t)stream, a, allrec, world, inv_total);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int st_bn_bank_norm(const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* Y, int ldy, int Tout, void* stream) {
-    (void)hipGetLastError();
-    BnBank a; int mc; size_t mr;
-    { const int rc = bnb_fill(a, segs, nseg, Bn, N, mc, mr, "st_bn_bank_norm"); if (rc) return rc; }
-    ST_CHECK_ARG(Y && Tout > 0 && ldy >= nseg * N, "st_bn_bank_norm: bad output");
-    for (int k = 0; k < nseg; ++k) ST_CHECK_ARG(segs[k].T >= Tout, "st_bn_bank_norm: segment %d has %d frames, the bank %d", k, segs[k].T, Tout);
-    return bnb_norm_launch(a, segs, nseg, Bn, N, Y, ldy, Tout, (hipStream_t)stream);
-}
-
-static int bnb_norm_launch(const BnBank& a, const st_bn_bank_seg* segs, int nseg, int Bn, int N, float* Y, int ldy, int Tout, hipStream_t st) {
-    int vec = N % 4 == 0 && ldy % 4 == 0 && st_aligned16(Y);
-    for (int k = 0; k < nseg && vec; ++k)
-        vec = segs[k].ldx % 4 == 0 && st_aligned16(segs[k].x) && st_aligned16(segs[k].mean) && st_aligned16(segs[k].var) &&
-              (!segs[k].w || st_aligned16(segs[k].w)) && (!segs[k].b || st_aligned16(segs[k].b));
-    hipLaunchKernelGGL(bnb_norm_kernel, dim3(blocks_for((size_t)Bn * Tout * N / (vec ? 4 : 1), 1024), nseg), dim3(256), 0, st, a, Y, ldy, Tout, vec);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-static int bnb_bwd_common(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* dY, int lddy, int Tout, int relu_in, float* ws,
-                          int stage, const float* inv_total, void* stream, const char* who) {
-    BnBank a; int mc; size_t mr;
-    { const int rc = bnb_fill(a, segs, nseg, Bn, N, mc, mr, who); if (rc) return rc; }
-    ST_CHECK_ARG(dY && Tout > 0 && lddy >= nseg * N && (stage == 2 || ws), "%s: bad gradient / workspace", who);
-    for (int k = 0; k < nseg; ++k)
-        ST_CHECK_ARG(segs[k].sums && (stage == 1 || (segs[k].dx && segs[k].lddx >= N)) && segs[k].T >= Tout, "%s: segment %d incomplete", who, k);
-    hipStream_t st = (hipStream_t)stream;
-    if (stage != 2) {        // sums of this rank's rows
-        hipLaunchKernelGGL(bnb_bwd_reduce_kernel, dim3((N + 63) / 64, mc, nseg), dim3(256), 0, st, a, dY, lddy, Tout, ws, mc);
-        ST_LAUNCH_CHECK();
-        hipLaunchKernelGGL(bnb_bwd_final_kernel, dim3((2 * N + 15) / 16, nseg), dim3(256), 0, st, a, ws, mc);
-        ST_LAUNCH_CHECK();
-    }
-    if (stage != 1) {
-        int vec = N % 4 == 0 && lddy % 4 == 0 && st_aligned16(dY);
-        for (int k = 0; k < nseg && vec; ++k)
-            vec = segs[k].ldx % 4 == 0 && segs[k].lddx % 4 == 0 && st_aligned16(segs[k].x) && st_aligned16(segs[k].dx) && st_aligned16(segs[k].mean) &&
-                  st_aligned16(segs[k].var) && st_aligned16(segs[k].sums) && (!segs[k].w || st_aligned16(segs[k].w));
-        hipLaunchKernelGGL(bnb_bwd_apply_kernel, dim3(blocks_for(mr * N / (vec ? 4 : 1), 1024), nseg), dim3(256), 0, st, a, dY, lddy, Tout, relu_in, vec,
-                           inv_total);
-        ST_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-extern "C" int st_bn_bank_bwd(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* dY, int lddy, int Tout, int relu_in, float* ws,
-                              void* stream) {
-    (void)hipGetLastError();
-    return bnb_bwd_common(segs, nseg, Bn, N, dY, lddy, Tout, relu_in, ws, 0, nullptr, stream, "st_bn_bank_bwd");
-}
-
-// SyncBN stages: local sums -> [all-reduce by the caller] -> apply with the global sums and 1 / (global row count) per segment
-extern "C" int st_bn_bank_bwd_reduce(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* dY, int lddy, int Tout, float* ws, void* stream) {
-    (void)hipGetLastError();
-    return bnb_bwd_common(segs, nseg, Bn, N, dY, lddy, Tout, 0, ws, 1, nullptr, stream, "st_bn_bank_bwd_reduce");
-}
-
-extern "C" int st_bn_bank_bwd_apply(const st_bn_bank_seg* segs, int nseg, int Bn, int N, const float* dY, int lddy, int Tout, int relu_in,
-                                    const float* inv_total, void* stream) {
-    (void)hipGetLastError();
-    return bnb_bwd_common(segs, nseg, Bn, N, dY, lddy, Tout, relu_in, nullptr, 2, inv_total, stream, "st_bn_bank_bwd_apply");
 }
 
 extern "C" int st_highway_ht_fwd(const float* ht, const float* x, float* y, int M, int C, void* stream) {
@@ -1832,33 +1231,6 @@ extern "C" int st_scatter_add_rows(const float* dout, const int64_t* idx, float*
     ST_CHECK_ARG(dout && idx && dtable && n > 0 && D > 0 && V > 0, "st_scatter_add_rows: bad arguments");
     hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(V, (D + 63) / 64), dim3(512), 0, (hipStream_t)stream,
                        dout, idx, dtable, n, D, V);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int st_bn_norm_fwd(const float* X, int ldx, int xoff, float* Y, int ldy, int yoff, int M, int N,
-                              const float* mean, const float* var, const float* w, const float* b, float eps, int act,
-                              void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(X && Y && mean && var && M > 0 && N > 0, "st_bn_norm_fwd: bad arguments");
-    hipLaunchKernelGGL(bn_norm_fwd_kernel, dim3(blocks_for((size_t)M * N)), dim3(256), 0, (hipStream_t)stream,
-                       X, ldx, xoff, Y, ldy, yoff, M, N, mean, var, w, b, eps, act);
-    ST_LAUNCH_CHECK();
-    return 0;
-}
-
-// Tact (M, N) = act(BatchNorm(X)) (may be NULL when nobody needs it), Y (M, N) = (Tact + res) * mask; X, res, mask, Tact, Y contiguous rows
-// of N floats, N % 4 == 0, 16-byte aligned.  ref: ConvLayer.forward, src/module.py:641-646
-extern "C" int st_bn_norm_res_mask_fwd(const float* X, float* Tact, float* Y, int M, int N, const float* mean, const float* var,
-                                       const float* w, const float* b, float eps, int act, const float* res, const float* mask,
-                                       void* stream) {
-    (void)hipGetLastError();
-    ST_CHECK_ARG(X && Y && mean && var && M > 0 && N > 0 && N % 4 == 0, "st_bn_norm_res_mask_fwd: bad arguments (N %% 4 == 0)");
-    ST_CHECK_ARG(st_aligned16(X) && st_aligned16(Y) && st_aligned16(Tact) && st_aligned16(res) && st_aligned16(mask) && st_aligned16(mean) && st_aligned16(var) && st_aligned16(w) && st_aligned16(b),
-                 "st_bn_norm_res_mask_fwd: 16-byte aligned operands");
-    const size_t total4 = (size_t)M * (N / 4);
-    hipLaunchKernelGGL(bn_norm_res_mask_fwd_kernel, dim3(blocks_for(total4)), dim3(256), 0, (hipStream_t)stream,
-                       X, Tact, Y, N / 4, total4, mean, var, w, b, eps, act, res, mask);
     ST_LAUNCH_CHECK();
     return 0;
 }

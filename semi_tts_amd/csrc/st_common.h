@@ -67,11 +67,13 @@ static __host__ __device__ inline bool st_aligned16(const void* p) { return (rei
 // ---------------------------------------------------------------- device helpers (wave = 64)
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// row chunks of the split column reductions (st_bn_stats, st_colsum, st_bn_bwd_reduce): enough blocks to fill 256 CUs
-// even for 80-column tensors, chunks of >= 64 rows
-// row chunks of the column reductions (BatchNorm statistics / backward sums, bias gradients): ~32 rows per chunk, at most 128 chunks
-// (two column blocks x 128 chunks = one workgroup per compute unit for the 128-channel layers of the CBHG)
-static inline __host__ __device__ int st_colreduce_chunks(int M) { int c = M / 32; if (c < 1) c = 1; if (c > 128) c = 128; return c; }
+// row chunks of the column reductions (BatchNorm statistics / backward sums, bias gradients): ~32 rows per chunk, at most
+// ST_COLREDUCE_MAX_CHUNKS (two column blocks x 128 chunks = one workgroup per compute unit for the 128-channel layers of the CBHG).
+// The kernels that merge the chunks hold all of them in registers and assert the cap at compile time.
+constexpr int ST_COLREDUCE_MAX_CHUNKS = 128;
+static inline __host__ __device__ int st_colreduce_chunks(int M) {
+    int c = M / 32; if (c < 1) c = 1; if (c > ST_COLREDUCE_MAX_CHUNKS) c = ST_COLREDUCE_MAX_CHUNKS; return c;
+}
 
 #define ST_WAVE 64
 

@@ -1269,7 +1269,6 @@ def highway_bwd(dy, H, x, Tg):
 
 
 def _bn_bank_segs(xs, bns, means, vars_, dxs=None, sums=None, update_running=True):
-    import ctypes as C
     n = len(xs)
     segs = (_lib.StBnBankSeg * n)()
     for k, (x, bn) in enumerate(zip(xs, bns)):
@@ -1287,73 +1286,73 @@ def _bn_bank_segs(xs, bns, means, vars_, dxs=None, sums=None, update_running=Tru
     return segs
 
 
-def _bn_bank_setup(xs, stats=None):
-    """what the four bank wrappers start from: the library, segment count, Bn, N, device, the scratch of st_bn_bank_workspace_floats, the
-    (K, 2, N) statistics (allocated here in forward) and their per-segment mean / var views"""
-    lib = _lib.load()
-    n, (Bn, _, N) = len(xs), xs[0].shape
-    dev = xs[0].device
-    if stats is None:
-        stats = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
-    ws = torch.empty(int(lib.st_bn_bank_workspace_floats(n, int(Bn * max(x.shape[1] for x in xs)), int(N))), device=dev, dtype=torch.float32)
-    return lib, n, int(Bn), int(N), dev, ws, stats, [stats[k, 0] for k in range(n)], [stats[k, 1] for k in range(n)]
+BN_STATS, BN_MERGE, BN_NORM, BN_REDUCE, BN_APPLY = 1, 2, 4, 1, 2        # ST_BN_* of include/semitts.h: stages of st_bn_bank_fwd; of st_bn_bank_bwd
+
+
+def _bn_bank_job(xs, bns, Tout, stats=None, dY=None, relu_in=False):
+    """the st_bn_bank_job every stage of a bank reads, and the tensors it points at (by name): K segments (Bn, T_k, N), their (K, 2, N) stats
+    (allocated here in forward), scratch; forward (dY None) the bank Y (Bn, Tout, K N), backward (dY its gradient) dxs and the (K, 2, N) sums"""
+    n, (Bn, _, N), dev = len(xs), xs[0].shape, xs[0].device
+    new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+    t = dict(stats=new(n, 2, N) if stats is None else stats,
+             ws=new(int(_lib.load().st_bn_bank_workspace_floats(n, int(Bn * max(x.shape[1] for x in xs)), int(N)))))
+    means, vars_ = [t['stats'][k, 0] for k in range(n)], [t['stats'][k, 1] for k in range(n)]
+    if dY is None:
+        t['Y'] = new(Bn, Tout, n * N)
+        segs = _bn_bank_segs(xs, bns, means, vars_)
+    else:
+        t['dxs'], t['sums'] = [torch.empty_like(x) for x in xs], new(n, 2, N)
+        segs = _bn_bank_segs(xs, bns, means, vars_, t['dxs'], [t['sums'][k] for k in range(n)], update_running=False)
+    j = _lib.StBnBankJob(segs=segs, nseg=n, Bn=int(Bn), N=int(N), Y=_p(t.get('Y')), dY=_p(dY), ld=int(t.get('Y', dY).stride(-2)),
+                         Tout=int(Tout), relu_in=1 if relu_in else 0, ws=_p(t['ws']))
+    return j, t
 
 
 def bn_bank_fwd(xs, bns, Tout):
     """K BatchNorm1d layers (batch statistics, running statistics updated) of K tensors (Bn, T_k, N) -> the bank (Bn, Tout, K N) and the
     (K, 2, N) statistics: 3 launches (st_bn_bank_fwd)"""
-    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs)
-    Y = torch.empty(Bn, Tout, n * N, device=dev, dtype=torch.float32)
-    segs = _bn_bank_segs(xs, bns, means, vars_)
-    check(lib.st_bn_bank_fwd(segs, n, Bn, N, _p(Y), n * N, int(Tout), _p(ws), stream_handle()), 'st_bn_bank_fwd')
-    return Y, stats
+    j, t = _bn_bank_job(xs, bns, Tout)
+    check(_lib.load().st_bn_bank_fwd(C.byref(j), BN_STATS | BN_NORM, stream_handle()), 'st_bn_bank_fwd')
+    return t['Y'], t['stats']
 
 
 def bn_bank_fwd_sync(xs, bns, Tout):
     """bn_bank_fwd under SyncBN: this rank's records -> ONE all-gather -> merge -> normalise.  Returns the bank, the (K, 2, N) global
     statistics and inv_total (K) = 1 / global row count per segment."""
     from . import parallel
-    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs)
-    Y = torch.empty(Bn, Tout, n * N, device=dev, dtype=torch.float32)
-    segs = _bn_bank_segs(xs, bns, means, vars_)
-    rec = torch.empty(n, 2 * N + 1, device=dev, dtype=torch.float32)
-    check(lib.st_bn_bank_stats_record(segs, n, Bn, N, _p(rec), _p(ws), stream_handle()), 'st_bn_bank_stats_record')
+    j, t = _bn_bank_job(xs, bns, Tout)
+    rec = torch.empty(j.nseg, 2 * j.N + 1, device=xs[0].device, dtype=torch.float32)
+    j.rec = _p(rec)
+    check(_lib.load().st_bn_bank_fwd(C.byref(j), BN_STATS, stream_handle()), 'st_bn_bank_fwd')
     allrec = parallel.all_gather_(rec).contiguous()                       # (world, n, 2N + 1)
-    inv_total = torch.empty(n, device=dev, dtype=torch.float32)
-    check(lib.st_bn_bank_sync_merge(segs, n, Bn, N, _p(allrec), int(allrec.shape[0]), _p(inv_total), stream_handle()),
-          'st_bn_bank_sync_merge')
-    check(lib.st_bn_bank_norm(segs, n, Bn, N, _p(Y), n * N, int(Tout), stream_handle()), 'st_bn_bank_norm')
-    return Y, stats, inv_total
+    inv_total = torch.empty(j.nseg, device=xs[0].device, dtype=torch.float32)
+    j.allrec, j.world, j.inv_total = _p(allrec), int(allrec.shape[0]), _p(inv_total)
+    check(_lib.load().st_bn_bank_fwd(C.byref(j), BN_MERGE, stream_handle()), 'st_bn_bank_fwd')
+    check(_lib.load().st_bn_bank_fwd(C.byref(j), BN_NORM, stream_handle()), 'st_bn_bank_fwd')
+    return t['Y'], t['stats'], inv_total
 
 
 def bn_bank_bwd_sync(dY, xs, bns, stats, inv_total, relu_in):
     """backward of bn_bank_fwd_sync: local sums -> ONE all-reduce -> apply.  Returns (dxs, LOCAL sums (K, 2, N)): the parameter gradients
     keep this rank's sums (the gradient reducer averages them over the ranks), dx uses the global ones."""
     from . import parallel
-    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs, stats)
-    dxs = [torch.empty_like(x) for x in xs]
-    local = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
-    segs = _bn_bank_segs(xs, bns, means, vars_, dxs, [local[k] for k in range(n)], update_running=False)
-    check(lib.st_bn_bank_bwd_reduce(segs, n, Bn, N, _p(dY), int(dY.stride(-2)), int(dY.shape[1]), _p(ws), stream_handle()),
-          'st_bn_bank_bwd_reduce')
-    glob = local.clone()
+    j, t = _bn_bank_job(xs, bns, dY.shape[1], stats, dY, relu_in)
+    check(_lib.load().st_bn_bank_bwd(C.byref(j), BN_REDUCE, stream_handle()), 'st_bn_bank_bwd')
+    glob = t['sums'].clone()
     parallel.all_reduce_sum_(glob)
-    segs = _bn_bank_segs(xs, bns, means, vars_, dxs, [glob[k] for k in range(n)], update_running=False)
-    check(lib.st_bn_bank_bwd_apply(segs, n, Bn, N, _p(dY), int(dY.stride(-2)), int(dY.shape[1]), 1 if relu_in else 0, _p(inv_total),
-                                   stream_handle()), 'st_bn_bank_bwd_apply')
-    return dxs, local
+    for k in range(j.nseg):
+        j.segs[k].sums = _p(glob[k])
+    j.inv_total = _p(inv_total)
+    check(_lib.load().st_bn_bank_bwd(C.byref(j), BN_APPLY, stream_handle()), 'st_bn_bank_bwd')
+    return t['dxs'], t['sums']
 
 
 def bn_bank_bwd(dY, xs, bns, stats, relu_in):
     """backward of bn_bank_fwd: dx_k over every row of segment k (through the ReLU in front of the norm when relu_in) and the (K, 2, N)
     sums (d bias, d weight): 3 launches"""
-    lib, n, Bn, N, dev, ws, stats, means, vars_ = _bn_bank_setup(xs, stats)
-    dxs = [torch.empty_like(x) for x in xs]
-    sums = torch.empty(n, 2, N, device=dev, dtype=torch.float32)
-    segs = _bn_bank_segs(xs, bns, means, vars_, dxs, [sums[k] for k in range(n)], update_running=False)
-    check(lib.st_bn_bank_bwd(segs, n, Bn, N, _p(dY), int(dY.stride(-2)), int(dY.shape[1]), 1 if relu_in else 0, _p(ws), stream_handle()),
-          'st_bn_bank_bwd')
-    return dxs, sums
+    j, t = _bn_bank_job(xs, bns, dY.shape[1], stats, dY, relu_in)
+    check(_lib.load().st_bn_bank_bwd(C.byref(j), BN_REDUCE | BN_APPLY, stream_handle()), 'st_bn_bank_bwd')
+    return t['dxs'], t['sums']
 
 
 def cat_params(ws, transposed=False, pad_to=0):

@@ -1,6 +1,6 @@
 """Training-mode BatchNorm kernels at the row counts production runs them at, against float64: the statistics (st_bn_stats: chunk-local
 two-pass, merged over up to 128 chunks) over the M x N rows of norm_rnn_cases.py, the normalisation kernels, the two halves of the
-backward, the conv bank's kernels (st_bn_bank_*) on the vec and the scalar paths, the speech encoder's ConvLayer node and the SyncBN
+backward, the conv bank's kernels (st_bn_bank_*) on the vec and the scalar paths and over unequal segments, the speech encoder's ConvLayer node and the SyncBN
 record / merge over ragged shards.  Needs a real MI355X: pytest -m gpu
 
 Tolerances: outputs maxdiff < 1e-5 on O(1) data, gradients relerr < 2e-5 (the suite's conventions); statistics of columns whose mean
@@ -327,10 +327,11 @@ def test_more_layers_than_the_bank_takes_go_through_the_group_function(dev):
 
 @pytest.mark.parametrize('N', [80, 18])
 def test_one_segment_bank_is_the_per_layer_kernels(dev, N):
-    """the comment above BnBank: a bank of one segment gives bit for bit what st_bn_stats / st_bn_norm_fwd / ops.bn_bwd give -- statistics,
-    running statistics, output and the two sums -- and dx to rounding: the two apply kernels compile to different multiply-add sequences
-    (measured: 2.5 % / 3.6 % of the elements differ at N = 80 / 18, by at most 4.8e-7 on O(1) values); the per-layer apply on the bank's
-    sums is bitwise the per-layer dx.
+    """the comment above BnBank: st_bn_stats runs the bank's statistics kernels on one segment, so statistics and running statistics of a
+    one-segment bank and of the per-layer call are the same kernels' (equal bit for bit, whichever entry fills the segment).  Output and
+    the two sums are still two kernels each with the same chunking and merge order -- bit for bit st_bn_norm_fwd / ops.bn_bwd -- and dx
+    agrees to rounding: the two apply kernels compile to different multiply-add sequences (measured: 2.5 % / 3.6 % of the elements
+    differ at N = 80 / 18, by at most 4.8e-7 on O(1) values); the per-layer apply on the bank's sums is bitwise the per-layer dx.
     N = 80 vec path, N = 18 scalar path; B = 32, T = 258: 128 chunks."""
     from semi_tts_amd import ops
     B, T = 32, 258
@@ -355,6 +356,103 @@ def test_one_segment_bank_is_the_per_layer_kernels(dev, N):
     e = relerr(dxs[0].view(-1, N), dx)
     report('bn_bank_one_segment', N=N, dx=e, dx_maxdiff=maxdiff(dxs[0].view(-1, N), dx), dx_differing=float((dxs[0].view(-1, N) != dx).float().mean()))
     assert e < 1e-6, e
+
+
+UNEQUAL_ROWS = [(3, (5, 43, 190), 5, 20, False), (3, (5, 43, 190), 5, 20, True), (3, (5, 43, 190), 5, 18, False), (3, (5, 43, 190), 5, 18, True),
+                (17, (241,), 241, 18, False)]
+
+
+@pytest.mark.parametrize('Bn,Ts,Tout,N,relu_in', UNEQUAL_ROWS, ids=['B%d-T%s-N%d-relu%d' % (r[0], 'x'.join(map(str, r[1])), r[3], r[4]) for r in UNEQUAL_ROWS])
+def test_batch_norm_bank_with_unequal_segments(dev, Bn, Ts, Tout, N, relu_in):
+    """AG.batch_norm_bank over segments of very different length.  Bn = 3, Ts = (5, 43, 190): 15, 129 and 570 rows = 1, 4 and 17 chunks, so
+    the launches are sized for 17 chunks and the blocks past a segment's own count must return without writing; 17 chunks puts a second
+    chunk into lane 0's registers in the merge kernels; the last chunks are ragged (30 of 33 rows, 26 of 34); frames t >= Tout = 5 far
+    outnumber the kept ones.  Bn = 17, Ts = (241,): 4097 rows in 128 chunks of 33, of which chunks 125 to 127 are empty, in the statistics
+    and in the backward's sums.  N = 20 takes the four-channel (vec) kernels, N = 18 the scalar ones."""
+    from semi_tts_amd import autograd as AG
+    assert [R.chunking(Bn * T)[0] for T in Ts] == ([1, 4, 17] if Bn == 3 else [128])
+    K = len(Ts)
+    bns, g = bank_layers(K, N, seed=Bn * 1000 + N)
+    pres = [torch.randn(Bn, Ts[k], N, generator=g) * 1.5 + 0.2 for k in range(K)]
+    dy = torch.randn(Bn, Tout, K * N, generator=g)
+    bnd = [copy.deepcopy(bn).to(dev) for bn in bns]
+    xs = [(torch.relu(p.to(dev)) if relu_in else p.to(dev)).requires_grad_() for p in pres]
+    bank = AG.batch_norm_bank(xs, bnd, Tout, relu_in)
+    bank.backward(dy.to(dev))
+    yr, pr, bref = bank_reference(pres, bns, Tout, relu_in, dy)
+    errs = dict(y=maxdiff(bank, yr), dx=max(relerr(xs[k].grad, pr[k].grad) for k in range(K)),
+                dw=max(relerr(bnd[k].weight.grad, bref[k].weight.grad) for k in range(K)),
+                db=max(relerr(bnd[k].bias.grad, bref[k].bias.grad) for k in range(K)),
+                rm=max(maxdiff(bnd[k].running_mean, bref[k].running_mean) for k in range(K)),
+                rv=max(maxdiff(bnd[k].running_var, bref[k].running_var) for k in range(K)))
+    report('bn_bank_unequal', Bn=Bn, Ts=str(Ts), N=N, relu_in=int(relu_in), **errs)
+    assert bank.shape == (Bn, Tout, K * N)
+    assert max(errs['y'], errs['rm'], errs['rv']) < 1e-5, errs
+    assert max(errs['dx'], errs['dw'], errs['db']) < 2e-5, errs
+    assert all(int(bn.num_batches_tracked) == 1 for bn in bnd)
+
+
+def test_bank_sync_stages_over_ragged_shards(dev):
+    """the bank's SyncBN stages, driven through st_bn_bank_fwd / st_bn_bank_bwd directly, in one process: the batch of 4 utterances cut into
+    shards of 1 and 3, Ts = (43, 44), Tout = 43, N = 20.  STATS with rec per shard -> the records stacked (2, nseg, 2N + 1) -> MERGE on
+    every shard's job (the running statistics given on the first only) -> NORM per shard; REDUCE per shard -> the sums added -> APPLY per
+    shard with inv_total: the float64 BatchNorm of the whole batch."""
+    import ctypes as C
+    from semi_tts_amd import _lib, ops
+    lib = _lib.load()
+    Bn, Ts, Tout, N, cuts = 4, (43, 44), 43, 20, [(0, 1), (1, 4)]
+    K = len(Ts)
+    bns, g = bank_layers(K, N, seed=4344)
+    pres = [torch.randn(Bn, Ts[k], N, generator=g) * 1.5 + 0.2 for k in range(K)]
+    dy = torch.randn(Bn, Tout, K * N, generator=g)
+    bnd = [copy.deepcopy(bn).to(dev) for bn in bns]
+    xd, dyd = [p.to(dev) for p in pres], dy.to(dev)
+
+    def run(entry, j, stages):
+        ops.check(getattr(lib, entry)(C.byref(j), stages, ops.stream_handle()), '%s(%d)' % (entry, stages))
+
+    jobs = [ops._bn_bank_job([x[b0:b1] for x in xd], bnd, Tout) for b0, b1 in cuts]
+    for k in range(K):          # the second shard's job updates no running statistics and counts no batch
+        sg = jobs[1][0].segs[k]
+        sg.run_mean = sg.run_var = sg.batches_tracked = None
+    recs = [torch.empty(K, 2 * N + 1, device=dev) for _ in cuts]
+    for (j, _), rec in zip(jobs, recs):
+        j.rec = ops._p(rec)
+        run('st_bn_bank_fwd', j, ops.BN_STATS)
+    allrec = torch.stack(recs)
+    invs = [torch.empty(K, device=dev) for _ in cuts]
+    for (j, _), inv in zip(jobs, invs):
+        j.allrec, j.world, j.inv_total = ops._p(allrec), len(cuts), ops._p(inv)
+        run('st_bn_bank_fwd', j, ops.BN_MERGE)
+        run('st_bn_bank_fwd', j, ops.BN_NORM)
+    bjobs = [ops._bn_bank_job([x[b0:b1] for x in xd], bnd, Tout, t['stats'], dyd[b0:b1], False) for (b0, b1), (_, t) in zip(cuts, jobs)]
+    for j, _ in bjobs:
+        run('st_bn_bank_bwd', j, ops.BN_REDUCE)
+    glob = bjobs[0][1]['sums'] + bjobs[1][1]['sums']
+    for (j, _), inv in zip(bjobs, invs):
+        for k in range(K):
+            j.segs[k].sums = ops._p(glob[k])
+        j.inv_total = ops._p(inv)
+        run('st_bn_bank_bwd', j, ops.BN_APPLY)
+    yr, pr, bref = bank_reference(pres, bns, Tout, False, dy)
+    stats = jobs[0][1]['stats']
+    x64 = [p.double().reshape(-1, N) for p in pres]
+    errs = dict(y=maxdiff(torch.cat([t['Y'] for _, t in jobs]), yr),
+                mean=max(maxdiff(stats[k, 0], x64[k].mean(0)) for k in range(K)),
+                var=max(maxdiff(stats[k, 1], x64[k].var(0, unbiased=False)) for k in range(K)),
+                rm=max(maxdiff(bnd[k].running_mean, bref[k].running_mean) for k in range(K)),
+                rv=max(maxdiff(bnd[k].running_var, bref[k].running_var) for k in range(K)),
+                dx=max(relerr(torch.cat([t['dxs'][k] for _, t in bjobs]), pr[k].grad) for k in range(K)),
+                db=max(relerr(glob[k, 0], bref[k].bias.grad) for k in range(K)),
+                dw=max(relerr(glob[k, 1], bref[k].weight.grad) for k in range(K)))
+    report('bn_bank_sync_ragged_shards', Bn=Bn, N=N, **errs)
+    assert torch.equal(stats, jobs[1][1]['stats']) and torch.equal(invs[0], invs[1]), 'the shards merged the same records differently'
+    assert [[float(rec[k, 2 * N]) for k in range(K)] for rec in recs] == [[float((b1 - b0) * T) for T in Ts] for b0, b1 in cuts]
+    for k in range(K):
+        assert float(invs[0][k]) == pytest.approx(1.0 / (Bn * Ts[k]), rel=1e-7)
+        assert int(bnd[k].num_batches_tracked) == 1, k
+    assert max(errs['y'], errs['mean'], errs['var'], errs['rm'], errs['rv']) < 1e-5, errs
+    assert max(errs['dx'], errs['dw'], errs['db']) < 2e-5, errs
 
 
 # ------------------------------------------------------------------------------------------------------------------- ConvLayer
