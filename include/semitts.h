@@ -1781,6 +1781,57 @@ int st_sisdr_batch(const st_wave_batch* x, const st_wave_batch* y, const int32_t
 int st_wave_gather(const float* src, long src_n, const long* src_off, float* dst, long dst_n, const long* dst_off, const int* len, int B,
                    void* stream);
 
+/* ------------------------------------------------------------------ k-means over frame features: units without transcripts or a codebook
+ * Not a step of the reference (it clusters nothing); the discrete-unit baseline of ZeroSpeech / HuBERT (semi_tts_amd.kmeans,
+ * main.py --kmeans-wav-dir, --units-wav-dir, --abx-codebook).  One operand struct for every call: N rows of D columns, row n at
+ * x + n ld, ld >= D floats, so a column slice of a wider buffer is taken as it is.  cent is a contiguous (K, D) table.
+ * Limits of every entry point (-22 past them, before any launch): 1 <= D <= 256, 1 <= K <= 4096, 1 <= N, N ld < 2^40, no null pointer.
+ *
+ * st_kmeans_assign: idx[n] (int32) = the smallest k that attains the minimum over k of d(n, k), dist[n] = that minimum, with
+ *   d(n, k) = max(0, (|x_n|^2 + |c_k|^2) - 2 x_n.c_k) in fp32 -- the expanded form: the three sums are fmaf chains over ascending d,
+ *   the sum of the two norms is one rounded add, the last step one fmaf.  Exact whenever every intermediate is (small integers); else
+ *   |d - ||x - c||^2| <= (D + 3) 2^-24 (||x|| + ||c||)^2 to first order, which loses digits when a column's mean dwarfs its spread.
+ *   The centroids are visited in ascending k and a later one wins only when strictly smaller.  A row holding a NaN or an infinity (or whose |x|^2
+ *   overflows fp32) gets idx = -1 and dist = NaN.  One launch, no workspace, no atomics: a row's result depends on that row and the table alone.
+ *
+ * st_kmeans_update: cent_out, count and stats from an assignment.  A point with idx outside [0, K) (the -1 of a NaN row) is no
+ *   member.  count[k] (int32) = the members of k; cent_out[k, d] = (float)(S / (double)count[k]) with S the float64 sum of the members'
+ *   x[n, d], or cent_in[k, d] when count[k] = 0.  stats (4 doubles) = (sum of dist over the members; sum over k, d of
+ *   (cent_out - cent_in)^2 in float64; clusters with count 0; points that are no member).
+ *   Order of every sum, a function of (N, K, idx) alone: a cluster's members in ascending n are cut into slabs of 256; a slab is summed
+ *   from 0 in that order; the slabs are added in ascending order.  dist: per chunk of 1024 points, thread t of 256 adds its points
+ *   t, t + 256, .. in that order and a binary tree over the threads (t with t + s, s = 128 .. 1) joins them; the chunks and the per-cluster
+ *   shifts (each the sum over ascending d) are joined alike over 1024 threads.  No floating-point atomics; integer atomics only for
+ *   the LDS histograms, whose result does not depend on their order: two runs give the same bits.
+ *   ws: st_kmeans_update_workspace_bytes(N, D, K) bytes (0 outside the limits), 16-byte aligned.  Seven launches, no host read.
+ *
+ * st_kmeans_relocate: the e-th cluster with count[k] = 0 (ascending k) takes the row of the e-th member point in the order (dist
+ *   descending, n ascending); with fewer member points than such clusters the rest of cent is left alone.  cent (K, D) is changed in
+ *   place; the donors' clusters are not adjusted.  One launch of one workgroup, a pass over the points per empty cluster: the rare path.
+ *
+ * st_kmeans_pp_step / st_kmeans_pp_pick: k-means++ (Arthur, Vassilvitskii 2007) without a host read between the picks.  Device state:
+ *   mind (N) float32, filled with +inf by the caller; part (st_kmeans_chunks(N)) doubles; picks (K) int32; totals (K) doubles; flag (1)
+ *   int32, zeroed by the caller; u (K) doubles in [0, 1).  The caller issues pick(0), step(0), pick(1), step(1), .., pick(K-1), step(K-1).
+ *   step(j): p = picks[j]; cent[j] = row p; mind[n] = min(mind[n], sum_d (x[n, d] - x[p, d])^2) (fp32, the direct form, an fmaf chain
+ *     over ascending d: exactly 0 for a copy of row p), NaN for a row holding one; part[c] = the sum of the weights of chunk c of 1024
+ *     points, a point's weight being mind where mind > 0 and 0 elsewhere (float64, the tree of st_kmeans_update's dist).
+ *   pick(0): picks[0] = floor(u[0] N).  pick(j): total = the sum of part; cum = the float64 running sum of the weights over ascending
+ *     n (the chunks before a point's own taken from part); picks[j] = the first n whose weight is positive and cum[n] > u[j] total, or
+ *     the last n of positive weight when rounding leaves none; totals[j] = total.  total = 0 (fewer distinct rows than centres) sets
+ *     flag[0] = 1 and picks[j] = 0; the caller reads the flag once at the end.  On integer data every sum is exact and the picks are
+ *     those of a sequential float64 scan.  One launch each. */
+typedef struct st_kmeans_data { const float* x; long ld; int N; int D; } st_kmeans_data;
+int st_kmeans_assign(const st_kmeans_data* x, const float* cent /* (K, D) */, int K, int32_t* idx /* (N) */, float* dist /* (N) */, void* stream);
+size_t st_kmeans_update_workspace_bytes(int N, int D, int K);
+int st_kmeans_update(const st_kmeans_data* x, const int32_t* idx, const float* dist, const float* cent_in, int K, float* cent_out /* (K, D) */,
+                     int32_t* count /* (K) */, double* stats /* (4) */, void* ws, void* stream);
+int st_kmeans_relocate(const st_kmeans_data* x, const int32_t* idx, const float* dist, const int32_t* count, int K, float* cent /* (K, D) */,
+                       void* stream);
+long st_kmeans_chunks(int N);
+int st_kmeans_pp_step(const st_kmeans_data* x, const int32_t* picks, int j, int K, float* mind, double* part, float* cent, void* stream);
+int st_kmeans_pp_pick(const st_kmeans_data* x, const float* mind, const double* part, const double* u, int j, int K, int32_t* picks,
+                      double* totals, int32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

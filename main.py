@@ -18,7 +18,7 @@ asr_<step>.pth / best_post_per.pth / step_<step>.pth -- or, with --store-best-pe
     python main.py --config config/supervised.yaml --tts-only --max-step 20 [--frames 256 --batch-size 32]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR [--beam-width 16 --top-paths 1 --vocab FILE]
     python main.py --config config/semi-single-spkr-paired-data.yaml --align-wav-dir DIR [--phn-dir DIR2 --vocab FILE]
-    python main.py --config config/semi-single-spkr-paired-data.yaml --build-lm-phn-dir DIR --lm-order 2 --lm FILE [--lm-smooth 1 --vocab F]
+    python main.py --config config/semi-single-spkr-paired-data.yaml --build-lm-phn-dir DIR --lm-order 2 --lm FILE [--lm-smooth 1 --lm-classes 43 --vocab F]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --lm FILE [--lm-weight 0.5 --ins-bonus 0]
     python main.py --config config/supervised.yaml --vocode-dir DIR [--vocode-feat spec|mel --batch-size 32]
     python main.py --config config/semi-single-spkr-paired-data.yaml --transcribe-wav-dir DIR --resample      (files of any sample rate)
@@ -84,6 +84,12 @@ the codebook posteriors -- by the ABX phone-discrimination error of ZeroSpeech /
 semi_tts_amd.metrics.abx, st_dtw_pairs + st_abx_count): abx.csv with the error of every ordered phone pair, abx_phones.csv with the tokens used.
 `--abx-mode across|both --abx-spk-map FILE` takes X from another speaker of the same context instead (metrics.abx_across, st_abx_across):
 abx_across.csv and abx_across_speakers.csv; `both` runs the within-speaker path first and then the across-speaker one.
+`--kmeans-wav-dir DIR --kmeans-out FILE.npy` (not a mode of the reference) makes the representation those measures are compared against, the
+k-means units of ZeroSpeech / HuBERT-style baselines: the MFCC, mel or latent frames of a directory are clustered on the GPU (solver.KMeansTrainer,
+semi_tts_amd.kmeans.fit: st_kmeans_assign + st_kmeans_update per iteration, k-means++ seeding on the device) into a (K, D) codebook, with
+kmeans.csv (restart,iter,inertia,shift,empty) and kmeans_units.csv (unit,frames).  `--units-wav-dir DIR --units-codebook FILE.npy` writes the unit
+sequence of every file as <stem>.phn (ids 3 + unit, repeats merged), which `--build-lm-phn-dir --lm-classes <3 + K>` and `--score-phn-dir` read as they are, and
+`--abx-ali-dir ... --abx-codebook FILE.npy` replaces every feature row by its nearest centroid before the items are cut: the discrete-unit ABX.
 `--stoi-wav-dir SYN --stoi-ref-dir REF` (not a mode of the reference) scores processed .wav files -- what `--vocode-dir`, `--gen-specgram --gen-wav`,
 `--resample-wav-dir` or `--loudness-out` write -- against the time-aligned recordings they were made from by short-time objective
 intelligibility on the GPU (solver.StoiScorer, semi_tts_amd.metrics.stoi, st_stoi_batch): stoi.csv with STOI and ESTOI of every pair.  The
@@ -162,6 +168,8 @@ parser.add_argument('--ins-bonus', default=None, type=float, help='--lm with --t
 parser.add_argument('--build-lm-phn-dir', default=None, type=str, help='count an n-gram table of order --lm-order from the .phn '
                     'transcripts of this directory (ids or --vocab symbols, id 0 skipped) and write it to --lm; no GPU, no other mode')
 parser.add_argument('--lm-order', default=None, type=int, help='--build-lm-phn-dir: order of the table (1 .. 4)')
+parser.add_argument('--lm-classes', default=None, type=int, help='--build-lm-phn-dir: the classes V of the table (default 43: <pad>, <space>, <eos> and '
+                    '40 phones); the unit transcripts of --units-wav-dir under a codebook of K centroids take V = 3 + K')
 parser.add_argument('--lm-smooth', default=None, type=float, help='--build-lm-phn-dir: add-K smoothing over the non-blank phones (default 1)')
 parser.add_argument('--gen-wav-feat', default='linear', choices=('linear', 'mel'), help='--gen-specgram --gen-wav: vocode the predicted '
                     'linear spectrogram (default) or the predicted mel (through the filterbank\'s pseudo-inverse) into <name>-pred.wav')
@@ -270,6 +278,28 @@ parser.add_argument('--abx-mode', default=None, choices=('within', 'across', 'bo
                     'abx_across_speakers.csv with speaker,groups,error), or one run after the other (both); across and both need --abx-spk-map')
 parser.add_argument('--abx-max-gb', default=None, type=float, help='--abx-mode across|both: the most GiB of distance matrices and pair tables '
                     '(default 8); above it the run is refused')
+parser.add_argument('--abx-codebook', default=None, type=str, help='--abx-ali-dir: a (K, D) float32 .npy table of centroids (what --kmeans-out '
+                    'writes); every feature row is replaced by its nearest centroid before the items are cut (discrete-unit ABX)')
+parser.add_argument('--kmeans-wav-dir', default=None, type=str, help='fit a k-means codebook to the frames of the .wav files of this directory on '
+                    'the GPU (sorted by name, batched by --batch-size): --kmeans-out FILE.npy, <logdir>/<name>/kmeans.csv '
+                    '(restart,iter,inertia,shift,empty) and kmeans_units.csv (unit,frames)')
+parser.add_argument('--kmeans-out', default=None, type=str, help='--kmeans-wav-dir: the .npy file the (K, D) float32 codebook is written to')
+parser.add_argument('--kmeans-feat', default=None, choices=('mfcc', 'mel', 'latent'), help='--kmeans-wav-dir / --units-wav-dir: the frames '
+                    'clustered: MFCC (default) and mel need no checkpoint and no model; latent is the speech encoder of --load')
+parser.add_argument('--kmeans-k', default=None, type=int, help='--kmeans-wav-dir: the number of centroids (default 50, at most 4096)')
+parser.add_argument('--kmeans-iters', default=None, type=int, help='--kmeans-wav-dir: the most Lloyd iterations of a fit (default 100)')
+parser.add_argument('--kmeans-tol', default=None, type=float, help='--kmeans-wav-dir: a fit stops when the squared move of the centroids is at most '
+                    'this times the mean per-column variance of the frames (default 1e-4)')
+parser.add_argument('--kmeans-init', default=None, choices=('++', 'sample'), help='--kmeans-wav-dir: k-means++ seeding (default) or K distinct frames, '
+                    'both drawn from --seed')
+parser.add_argument('--kmeans-restarts', default=None, type=int, help='--kmeans-wav-dir: fits from the seeds --seed, --seed + 1, ..; the one of '
+                    'lowest inertia is written (default 1)')
+parser.add_argument('--kmeans-max-gb', default=None, type=float, help='--kmeans-wav-dir: the most GiB of packed frames (default 8), computed from '
+                    'the .wav headers; above it the run is refused before the device is touched')
+parser.add_argument('--units-wav-dir', default=None, type=str, help='write the k-means unit sequence of every .wav file of this directory under '
+                    '--units-codebook as <logdir>/<name>/<stem>.phn (ids 3 + unit, consecutive repeats merged, the score -mean squared distance)')
+parser.add_argument('--units-codebook', default=None, type=str, help='--units-wav-dir: the (K, D) float32 .npy codebook of --kmeans-out')
+parser.add_argument('--units-frames', action='store_true', help='--units-wav-dir: also write the unmerged frame-level units as <stem>-units.npy (int32)')
 parser.add_argument('--stoi-wav-dir', default=None, type=str, help='score the processed .wav files of this directory (sorted by name, batched by '
                     '--batch-size; 16-bit mono PCM of any rate the resampler takes) against their time-aligned recordings in --stoi-ref-dir by STOI and '
                     'ESTOI on the GPU: <logdir>/<name>/stoi.csv (file,samples,frames,kept,segments,stoi,estoi); no config, no checkpoint, no model')
@@ -356,7 +386,7 @@ def parse_args(argv=None):
     if paras.vocode_feat is None:
         paras.vocode_feat = 'spec'
     if (paras.resample and paras.unpair_wav_dir is None and paras.transcribe_wav_dir is None and paras.align_wav_dir is None and not paras.corpus
-            and paras.loudness_wav_dir is None and paras.abx_ali_dir is None):
+            and paras.loudness_wav_dir is None and paras.abx_ali_dir is None and paras.kmeans_wav_dir is None and paras.units_wav_dir is None):
         parser.error('--resample converts the files of --unpair-wav-dir, --transcribe-wav-dir or --align-wav-dir, or the splits of --corpus; it needs one '
                      'of them')
     if paras.resample_wav_dir is not None:
@@ -484,7 +514,7 @@ def parse_args(argv=None):
         if paras.segment_file is not None:
             parser.error('--trim-silence does not combine with --segment-file: its times refer to the untrimmed file')
         if not (paras.corpus or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir',
-                                                                            'loudness_wav_dir', 'abx_ali_dir'))):
+                                                                            'loudness_wav_dir', 'abx_ali_dir', 'kmeans_wav_dir', 'units_wav_dir'))):
             parser.error('--trim-silence trims what --corpus, --unpair-wav-dir, --transcribe-wav-dir, --mcd-wav-dir or --feat-wav-dir load; it needs one '
                          'of them')
     elif paras.trim_wav_dir is None and any(v is not None for v in (paras.trim_top_db, paras.trim_frame_length, paras.trim_hop, paras.trim_pad_ms)):
@@ -514,7 +544,7 @@ def parse_args(argv=None):
         if paras.segment_file is not None:
             parser.error('--normalize-loudness does not combine with --segment-file in this version (times would not change; the listed modes only)')
         writes = paras.vocode_dir is not None or (paras.gen_wav and (paras.gen_specgram or paras.synth_phn_dir is not None))
-        if not (paras.corpus or writes or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir', 'abx_ali_dir'))):
+        if not (paras.corpus or writes or any(getattr(paras, f) is not None for f in ('unpair_wav_dir', 'transcribe_wav_dir', 'mcd_wav_dir', 'feat_wav_dir', 'abx_ali_dir', 'kmeans_wav_dir', 'units_wav_dir'))):
             parser.error('--normalize-loudness normalises what --corpus, --unpair-wav-dir, --transcribe-wav-dir, --feat-wav-dir or --mcd-wav-dir load and what '
                          '--gen-specgram --gen-wav, --vocode-dir or --synth-phn-dir --gen-wav write; it needs one of them')
     elif paras.loudness_wav_dir is None and any(v is not None for v in (paras.loudness_target, paras.loudness_peak, paras.loudness_max_gain)):
@@ -574,6 +604,42 @@ def parse_args(argv=None):
     elif any(getattr(paras, f) is not None for f in abx_flags):
         parser.error('--abx-wav-dir, --abx-feat, --abx-metric, --abx-context, --abx-spk-map, --abx-ignore, --abx-max-items and --abx-min-frames belong to '
                      '--abx-ali-dir; they need that flag')
+    elif paras.abx_codebook is not None:
+        parser.error('--abx-codebook belongs to --abx-ali-dir; it needs that flag')
+    if paras.abx_codebook is not None and paras.abx_ali_dir is not None and paras.abx_feat == 'code':
+        parser.error('--abx-codebook quantises feature rows; it does not combine with --abx-feat code')
+    unit_tools = [f for f in ('kmeans_wav_dir', 'units_wav_dir') if getattr(paras, f) is not None]
+    for tool in unit_tools:
+        for flag in ('gen_specgram', 'tts_only', 'unpair_wav_dir', 'transcribe_wav_dir', 'align_wav_dir', 'build_lm_phn_dir', 'vocode_dir',
+                     'resample_wav_dir', 'feat_wav_dir', 'mcd_wav_dir', 'synth_phn_dir', 'trim_wav_dir', 'loudness_wav_dir', 'score_phn_dir',
+                     'stoi_wav_dir', 'abx_ali_dir', 'corpus') + (('units_wav_dir',) if tool == 'kmeans_wav_dir' else ()):
+            if getattr(paras, flag):
+                parser.error('--%s does not combine with --%s' % (tool.replace('_', '-'), flag.replace('_', '-')))
+        if paras.dev_batches > 0:
+            parser.error('--%s does not combine with --dev-batches' % tool.replace('_', '-'))
+    kmeans_flags = ('kmeans_out', 'kmeans_k', 'kmeans_iters', 'kmeans_tol', 'kmeans_init', 'kmeans_restarts', 'kmeans_max_gb')
+    if paras.kmeans_wav_dir is not None:
+        if paras.config is None or paras.kmeans_out is None:
+            parser.error('--kmeans-wav-dir needs --config (its data.audio and model) and --kmeans-out FILE.npy (the codebook to write)')
+        paras.kmeans_k = 50 if paras.kmeans_k is None else paras.kmeans_k
+        paras.kmeans_iters = 100 if paras.kmeans_iters is None else paras.kmeans_iters
+        paras.kmeans_tol = 1e-4 if paras.kmeans_tol is None else paras.kmeans_tol
+        paras.kmeans_restarts = 1 if paras.kmeans_restarts is None else paras.kmeans_restarts
+        paras.kmeans_max_gb = 8.0 if paras.kmeans_max_gb is None else paras.kmeans_max_gb
+        if not 1 <= paras.kmeans_k <= 4096 or paras.kmeans_iters < 1 or paras.kmeans_restarts < 1:
+            parser.error('--kmeans-k must lie in [1, 4096], --kmeans-iters and --kmeans-restarts must be >= 1')
+        if not 0.0 <= paras.kmeans_tol < float('inf') or not 0.0 < paras.kmeans_max_gb < float('inf'):
+            parser.error('--kmeans-tol must be finite and >= 0, --kmeans-max-gb a positive number of GiB')
+    elif any(getattr(paras, f) is not None for f in kmeans_flags):
+        parser.error('--kmeans-out, --kmeans-k, --kmeans-iters, --kmeans-tol, --kmeans-init, --kmeans-restarts and --kmeans-max-gb belong to '
+                     '--kmeans-wav-dir; they need that flag')
+    if paras.units_wav_dir is not None:
+        if paras.config is None or paras.units_codebook is None:
+            parser.error('--units-wav-dir needs --config (its data.audio and model) and --units-codebook FILE.npy (the table of --kmeans-out)')
+    elif paras.units_codebook is not None or paras.units_frames:
+        parser.error('--units-codebook and --units-frames belong to --units-wav-dir; they need that flag')
+    if paras.kmeans_feat is not None and not unit_tools:
+        parser.error('--kmeans-feat belongs to --kmeans-wav-dir or --units-wav-dir; it needs one of them')
     if paras.gen_wav_feat != 'linear' and not ((paras.gen_specgram or paras.synth_phn_dir is not None) and paras.gen_wav):
         parser.error('--gen-wav-feat chooses what --gen-specgram --gen-wav vocodes; it needs both flags')
     if paras.build_lm_phn_dir is not None:
@@ -586,6 +652,9 @@ def parse_args(argv=None):
             parser.error('--build-lm-phn-dir needs --lm FILE (the table to write) and --lm-order N')
         if not 1 <= paras.lm_order <= 4:
             parser.error('--build-lm-phn-dir needs 1 <= --lm-order <= 4')
+        paras.lm_classes = 43 if paras.lm_classes is None else paras.lm_classes
+        if paras.lm_classes < 2 or paras.lm_classes ** paras.lm_order > 2 ** 26:
+            parser.error('--lm-classes must be >= 2 with --lm-classes ^ --lm-order <= 2^26')
         if paras.lm_smooth is not None and not (0.0 <= paras.lm_smooth < float('inf')):
             parser.error('--lm-smooth must be finite and >= 0')
         if paras.lm_weight is not None or paras.ins_bonus is not None:
@@ -593,6 +662,8 @@ def parse_args(argv=None):
     else:
         if paras.lm_order is not None or paras.lm_smooth is not None:
             parser.error('--lm-order and --lm-smooth belong to --build-lm-phn-dir; they need that flag')
+        if paras.lm_classes is not None:
+            parser.error('--lm-classes belongs to --build-lm-phn-dir; it needs that flag')
         if paras.lm is not None and paras.transcribe_wav_dir is None:
             parser.error('--lm names the n-gram table of --transcribe-wav-dir or --build-lm-phn-dir; it needs one of them')
         if paras.lm is None and (paras.lm_weight is not None or paras.ins_bonus is not None):
@@ -621,6 +692,7 @@ def parse_args(argv=None):
 # (attribute of paras, class of semi_tts_amd.solver): the modes that do not train; the first one whose flag is given runs
 TOOLS = (('resample_wav_dir', 'Resampler'), ('trim_wav_dir', 'Trimmer'), ('loudness_wav_dir', 'LoudnessWriter'), ('vocode_dir', 'Vocoder'),
          ('feat_wav_dir', 'FeatureWriter'), ('mcd_wav_dir', 'McdScorer'), ('stoi_wav_dir', 'StoiScorer'), ('abx_ali_dir', 'AbxScorer'),
+         ('kmeans_wav_dir', 'KMeansTrainer'), ('units_wav_dir', 'UnitWriter'),
          ('score_phn_dir', 'PhnScorer'), ('synth_phn_dir', 'Synthesiser'), ('transcribe_wav_dir', 'Transcriber'), ('align_wav_dir', 'Aligner'),
          ('gen_specgram', 'SpecgramGenerator'))
 
@@ -630,7 +702,7 @@ def main(argv=None):
     if paras.build_lm_phn_dir is not None:                  # host only: no config, no seed, no device
         from semi_tts_amd.ngram import build_lm_from_phn_dir
         from semi_tts_amd.solver import read_vocab
-        print(build_lm_from_phn_dir(paras.build_lm_phn_dir, paras.lm, paras.lm_order, smooth=paras.lm_smooth,
+        print(build_lm_from_phn_dir(paras.build_lm_phn_dir, paras.lm, paras.lm_order, V=paras.lm_classes, smooth=paras.lm_smooth,
                                     vocab=read_vocab(paras.vocab) if paras.vocab else None)['summary'])
         return
     if paras.resample_wav_dir is not None and paras.config is None:      # (the rate was given: this mode reads nothing else of a config)

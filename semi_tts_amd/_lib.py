@@ -257,6 +257,10 @@ class StWaveBatch(C.Structure):
     _fields_ = [('x', C.c_void_p), ('n_samples', C.c_long), ('off', C.c_void_p), ('len', C.c_void_p), ('B', C.c_int)]
 
 
+class StKmeansData(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('ld', C.c_long), ('N', C.c_int), ('D', C.c_int)]
+
+
 class StMelBank(C.Structure):
     _fields_ = [('start', C.c_void_p), ('cnt', C.c_void_p), ('off', C.c_void_p), ('w', C.c_void_p), ('n_mels', C.c_int)]
 
@@ -468,6 +472,13 @@ SIGNATURES = {
     'st_sisdr_workspace_bytes': [I, I],
     'st_sisdr_batch': [C.POINTER(StWaveBatch), C.POINTER(StWaveBatch), P, I, P, P, P, P],
     'st_wave_gather': [P, C.c_long, P, P, C.c_long, P, P, I, P],
+    'st_kmeans_assign': [C.POINTER(StKmeansData), P, I, P, P, P],
+    'st_kmeans_update_workspace_bytes': [I, I, I],
+    'st_kmeans_update': [C.POINTER(StKmeansData), P, P, P, I, P, P, P, P, P],
+    'st_kmeans_relocate': [C.POINTER(StKmeansData), P, P, P, I, P, P],
+    'st_kmeans_chunks': [I],
+    'st_kmeans_pp_step': [C.POINTER(StKmeansData), P, I, I, P, P, P, P],
+    'st_kmeans_pp_pick': [C.POINTER(StKmeansData), P, P, P, I, I, P, P, P, P],
 }
 _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t, 'st_t16_floats': C.c_size_t,
              'st_decoder_packed_floats': C.c_size_t, 'st_vq_l2_workspace_floats': C.c_size_t, 'st_ctc_workspace_floats': C.c_size_t, 'st_decoder_tape_floats': C.c_size_t,
@@ -476,7 +487,8 @@ _RESTYPES = {'st_last_error': C.c_char_p, 'st_packed_weight_floats': C.c_size_t,
              'st_gl_batch_workspace_floats': C.c_size_t,
              'st_features_workspace_floats': C.c_size_t, 'st_ctc_beam_workspace_bytes': C.c_size_t, 'st_ctc_align_workspace_bytes': C.c_size_t,
              'st_dtw_workspace_bytes': C.c_size_t, 'st_edit_align_workspace_bytes': C.c_size_t,
-             'st_stoi_workspace_floats': C.c_size_t, 'st_xcorr_workspace_bytes': C.c_size_t, 'st_sisdr_workspace_bytes': C.c_size_t}
+             'st_stoi_workspace_floats': C.c_size_t, 'st_xcorr_workspace_bytes': C.c_size_t, 'st_sisdr_workspace_bytes': C.c_size_t,
+             'st_kmeans_update_workspace_bytes': C.c_size_t, 'st_kmeans_chunks': C.c_long}
 
 _lib = None
 

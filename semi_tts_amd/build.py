@@ -25,6 +25,8 @@ STOI_SOURCES = ['stoi.hip']
 ALIGN_SOURCES = ['xcorr.hip']
 # the BatchNorm kernels (st_bn_*, st_bn_bank_*), taken out of gemm.hip and grad.hip, listed apart for the same reason
 BATCHNORM_SOURCES = ['batchnorm.hip']
+# the k-means kernels (st_kmeans_assign, st_kmeans_update, st_kmeans_relocate, st_kmeans_pp_*), listed apart for the same reason
+KMEANS_SOURCES = ['kmeans.hip']
 
 
 def _hipcc():
@@ -49,7 +51,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objs = []
     procs = []
-    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES + ABX_SOURCES + STOI_SOURCES + ALIGN_SOURCES + BATCHNORM_SOURCES:
+    for src in SOURCES + PITCH_SOURCES + TRIM_SOURCES + SCORE_SOURCES + LOUDNESS_SOURCES + ABX_SOURCES + STOI_SOURCES + ALIGN_SOURCES + BATCHNORM_SOURCES + KMEANS_SOURCES:
         obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         cmd = [_hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-mllvm', '-amdgpu-kernarg-preload-count=16', '-c', os.path.join(CSRC, src), '-o', obj]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

@@ -735,12 +735,104 @@ class StoiScorer(DirTool):
 ABX_FEATS = ('mfcc', 'mel', 'latent', 'code')
 
 
+class FeatureTool(DirTool):
+    """What the tools that score or cluster a representation share (AbxScorer, KMeansTrainer, UnitWriter): the representation `self.feat`
+    -- mfcc: AudioConverter.extract_mfcc_batch, mel: the clean extract_batch, neither needs a checkpoint or a model; latent / code:
+    VQVAE.represent of the model of --load, or of the synthetic weights -- of the files of `self.wav_dir`, sorted by name, in batches of
+    --batch-size, packed into one (rows, D) device buffer.  load_data sets self.wav_dir and self.audio_converter."""
+
+    def check_waves(self, wavs, flag):
+        """the headers of the files `wavs` of self.wav_dir: a rate other than the converter's needs --resample, and an utterance the MFCC
+        kernel refuses stops the run here, naming `flag` and the file -> the samples of every file at the converter's rate"""
+        from .audio import resampled_len
+        conv, samples = self.audio_converter, []
+        for w in wavs:
+            path = os.path.join(self.wav_dir, w)
+            sr, _, _, L = wav_header(path, flag)
+            if sr != conv.sr and not getattr(self.paras, 'resample', False):
+                raise ValueError('%s: sample rate mismatch. Expected %d but get %d (%s); --resample converts it' % (flag, conv.sr, sr, path))
+            if self.feat == 'mfcc' and sr == conv.sr:
+                try:
+                    conv._check_mfcc([L])
+                except ValueError as e:
+                    raise ValueError('%s: %s: %s' % (flag, path, e))
+            samples.append(L if sr == conv.sr else resampled_len(L, sr, conv.sr))
+        return samples
+
+    def set_model(self):
+        self.model = None
+        if self.feat in ('latent', 'code'):
+            from .solver import Transcriber
+            self.model = Transcriber(self.config, self.paras, self.mode).set_model().model
+        return self
+
+    def frame_s(self):
+        conv = self.audio_converter
+        if self.feat == 'mfcc':
+            return conv.hop_length_mfcc / float(conv.sr)
+        if self.feat == 'mel':
+            return conv.hop_length / float(conv.sr)
+        return self.model.time_reduce_factor * conv.hop_length / float(conv.sr)
+
+    def feature_rows(self, samples):
+        """an upper bound of the rows of an utterance of `samples` samples (trimming and the encoder's time reduction only shorten it)"""
+        conv = self.audio_converter
+        return 1 + samples // (conv.hop_length_mfcc if self.feat == 'mfcc' else conv.hop_length)
+
+    def feature_dim(self):
+        """the columns of the representation; None for latent / code before the model is built"""
+        from .audio import MFCC_DIM
+        if self.feat in ('mfcc', 'mel'):
+            return MFCC_DIM if self.feat == 'mfcc' else self.audio_converter.n_mels
+        return None
+
+    def extract(self, names):
+        """the files `names` of the .wav directory -> (features (B, T_pad, D) on the device in the batch's sorted order, rows per
+        utterance, the WaveBatch's inverse: the batch row of the k-th given file)"""
+        conv = self.audio_converter
+        wb = load_waves(conv, self.wav_dir, names, self.paras, resample=bool(getattr(self.paras, 'resample', False)))
+        feats, frames, _ = extract_features(conv, wb, 'mfcc' if self.feat == 'mfcc' else 'mel')
+        if self.feat in ('latent', 'code'):
+            feats, frames = self.model.represent(feats, frames, self.feat)
+            frames = frames.numpy()
+        return feats, frames, wb.inverse()
+
+    def pack(self, wavs):
+        """-> (the packed (rows, D) device buffer of the files `wavs`, the first row of every file, its rows), files in the given order"""
+        parts, n_rows = [], []
+        for names in self.batches(wavs, math.inf):
+            feats, frames, back = self.extract(list(names))
+            for k in range(len(names)):
+                r = int(min(int(frames[back[k]]), feats.shape[1]))
+                parts.append(feats[back[k], :r])
+                n_rows.append(r)
+        first = np.concatenate([[0], np.cumsum(n_rows)[:-1]]).astype(np.int64)
+        return torch.cat(parts, 0).float().contiguous(), first, np.asarray(n_rows, np.int64)
+
+
+def load_codebook(flag, path, D=None):
+    """a (K, D) float32 table of centroids from the .npy file of `flag` (what --kmeans-out writes); ValueError naming the flag for a file
+    that is no such table, that holds a non-finite entry or, with D, whose rows are not D wide"""
+    try:
+        table = np.load(path, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        raise ValueError('%s %s: not a readable .npy file (%s)' % (flag, path, e))
+    if table.ndim != 2 or table.dtype != np.float32 or not 1 <= table.shape[0] <= toolops.KM_MAX_K or not 1 <= table.shape[1] <= toolops.KM_MAX_D:
+        raise ValueError('%s %s: a codebook is a (K, D) float32 array with K <= %d and D <= %d (got %s %s)'
+                         % (flag, path, toolops.KM_MAX_K, toolops.KM_MAX_D, table.shape, table.dtype))
+    if not np.isfinite(table).all():
+        raise ValueError('%s %s: the codebook holds a non-finite entry' % (flag, path))
+    if D is not None and table.shape[1] != D:
+        raise ValueError('%s %s: the codebook has D = %d columns, the features have %d' % (flag, path, table.shape[1], D))
+    return np.ascontiguousarray(table)
+
+
 def abx_metric(paras):
     """--abx-metric, or its default: kl for the codebook posteriors (probability rows), angular for everything else"""
     return getattr(paras, 'abx_metric', None) or ('kl' if getattr(paras, 'abx_feat', 'mfcc') == 'code' else 'angular')
 
 
-class AbxScorer(DirTool):
+class AbxScorer(FeatureTool):
     """main.py --abx-ali-dir DIR --abx-wav-dir WAVS [--abx-feat mfcc|mel|latent|code --abx-metric angular|kl|euclid --abx-context
     triphone|none --abx-spk-map FILE --abx-ignore a,b --abx-max-items 50 --abx-min-frames 1]: the ABX phone-discrimination error of a
     representation, within speaker (semi_tts_amd.abx for the terms, metrics.abx for the computation).  Every <stem>.ali of DIR (what
@@ -754,7 +846,9 @@ class AbxScorer(DirTool):
     the speaker map lacks stops the run in load_data, naming the file, before any device work.
     --abx-mode across | both (with --abx-spk-map, at least two speakers) scores the same features and items across speakers as well
     (metrics.abx_across, matrices and pair tables up to --abx-max-gb): abx_across.csv (phone_a,phone_b,groups,triples,error),
-    abx_across_speakers.csv (speaker,groups,error) and a printed line of its own; `across` alone leaves abx.csv unwritten."""
+    abx_across_speakers.csv (speaker,groups,error) and a printed line of its own; `across` alone leaves abx.csv unwritten.
+    --abx-codebook FILE.npy (a (K, D) table of --kmeans-out) replaces every feature row by its nearest centroid before the items are cut:
+    the discrete-unit ABX of ZeroSpeech."""
 
     def __init__(self, config, paras, mode):
         super().__init__(config, paras, mode)
@@ -766,6 +860,7 @@ class AbxScorer(DirTool):
         self.min_frames = int(getattr(paras, 'abx_min_frames', None) or 1)
         self.abx_mode = getattr(paras, 'abx_mode', None) or 'within'
         self.max_bytes = int(float(getattr(paras, 'abx_max_gb', None) or 8) * (1 << 30))
+        self.codebook_file = getattr(paras, 'abx_codebook', None)
 
     def load_data(self):
         from . import abx as A
@@ -785,56 +880,30 @@ class AbxScorer(DirTool):
         if self.abx_mode != 'within' and len(set(self.speakers)) < 2:
             raise ValueError('--abx-mode %s needs --abx-spk-map FILE with at least two speakers among the files (got %s)'
                              % (self.abx_mode, 'no map' if not spk_map else '%d speaker' % len(set(self.speakers))))
-        self.audio_converter = conv = load_audio_transform(**dict(self.config['data']['audio']))
-        for _, _, w in self.pairs:
-            path = os.path.join(self.wav_dir, w)
-            sr, _, _, L = wav_header(path, '--abx-wav-dir')
-            if sr != conv.sr and not getattr(self.paras, 'resample', False):
-                raise ValueError('--abx-wav-dir: sample rate mismatch. Expected %d but get %d (%s); --resample converts it' % (conv.sr, sr, path))
-            if self.feat == 'mfcc' and sr == conv.sr:
-                try:
-                    conv._check_mfcc([L])
-                except ValueError as e:
-                    raise ValueError('--abx-wav-dir: %s: %s' % (path, e))
+        self.audio_converter = load_audio_transform(**dict(self.config['data']['audio']))
+        self.check_waves([w for _, _, w in self.pairs], '--abx-wav-dir')
+        self.codebook = None
+        if self.codebook_file is not None:
+            if self.feat == 'code':
+                raise ValueError('--abx-codebook quantises feature rows; --abx-feat code scores probability rows and has no use for it')
+            self.codebook = load_codebook('--abx-codebook', self.codebook_file, self.feature_dim())
         return self
-
-    def set_model(self):
-        self.model = None
-        if self.feat in ('latent', 'code'):
-            from .solver import Transcriber
-            self.model = Transcriber(self.config, self.paras, self.mode).set_model().model
-        return self
-
-    def frame_s(self):
-        conv = self.audio_converter
-        if self.feat == 'mfcc':
-            return conv.hop_length_mfcc / float(conv.sr)
-        if self.feat == 'mel':
-            return conv.hop_length / float(conv.sr)
-        return self.model.time_reduce_factor * conv.hop_length / float(conv.sr)
-
-    def extract(self, names):
-        """the files `names` of the .wav directory -> (features (B, T_pad, D) on the device in the batch's sorted order, rows per
-        utterance, the WaveBatch's inverse: the batch row of the k-th given file)"""
-        conv = self.audio_converter
-        wb = load_waves(conv, self.wav_dir, names, self.paras, resample=bool(getattr(self.paras, 'resample', False)))
-        feats, frames, _ = extract_features(conv, wb, 'mfcc' if self.feat == 'mfcc' else 'mel')
-        if self.feat in ('latent', 'code'):
-            feats, frames = self.model.represent(feats, frames, self.feat)
-            frames = frames.numpy()
-        return feats, frames, wb.inverse()
 
     def features(self):
-        """-> (the packed (rows, D) device buffer of all files, the first row of every file, its rows), files in the order of self.pairs"""
-        parts, n_rows = [], []
-        for pairs in self.batches(self.pairs, math.inf):
-            feats, frames, back = self.extract([w for _, _, w in pairs])
-            for k in range(len(pairs)):
-                r = int(min(int(frames[back[k]]), feats.shape[1]))
-                parts.append(feats[back[k], :r])
-                n_rows.append(r)
-        first = np.concatenate([[0], np.cumsum(n_rows)[:-1]]).astype(np.int64)
-        return torch.cat(parts, 0).float().contiguous(), first, np.asarray(n_rows, np.int64)
+        """-> (the packed (rows, D) device buffer of all files, the first row of every file, its rows), files in the order of self.pairs;
+        with --abx-codebook every row is replaced by its nearest centroid (kmeans.quantise, then index_select)"""
+        feat, first, n_rows = self.pack([w for _, _, w in self.pairs])
+        if self.codebook is not None:
+            from .kmeans import quantise
+            if self.codebook.shape[1] != feat.shape[1]:
+                raise ValueError('--abx-codebook %s: the codebook has D = %d columns, the features have %d'
+                                 % (self.codebook_file, self.codebook.shape[1], feat.shape[1]))
+            table = torch.from_numpy(self.codebook).to(feat.device)
+            idx, _ = quantise(feat, table)
+            if int((idx < 0).sum().item()):                            # (a row without a unit has no centroid to stand for it)
+                raise ValueError('--abx-codebook: %d feature rows hold a NaN or an infinity and have no nearest centroid' % int((idx < 0).sum().item()))
+            feat = table.index_select(0, idx.long()).contiguous()
+        return feat, first, n_rows
 
     def items(self, first, n_rows):
         """-> (item_start, item_len, label ids, cell ids, the phone names of the label ids, stats per phone)"""
@@ -1096,3 +1165,135 @@ class PhnScorer(DirTool):
               % (len(self.pairs), n_ref, self.corpus_per, self.mean_per, share(tot[1]), share(tot[2]), share(tot[3]),
                  '; n-best oracle %.4f' % self.oracle_per if self.nbest else '', table, time.perf_counter() - t0))
         return len(self.pairs)
+
+
+# -- k-means units
+UNIT_FEATS = ('mfcc', 'mel', 'latent')
+UNIT_ID_OFFSET = 3                  # a unit u is written as the id 3 + u: the special ids 0 .. 2 (<pad>, <space>, <eos>) stay free
+KMEANS_HEADER = 'restart,iter,inertia,shift,empty'
+KMEANS_UNITS_HEADER = 'unit,frames'
+
+
+def merge_repeats(units):
+    """a frame-level unit sequence with consecutive repeats merged -> list of units"""
+    units = np.asarray(units).reshape(-1)
+    return units[np.concatenate([[True], units[1:] != units[:-1]])].tolist() if len(units) else []
+
+
+def format_units(units, dist):
+    """the text of one <stem>.phn of --units-wav-dir in the layout of solver.format_phn(..., vocab=None): one line `score<TAB>ids`, the
+    ids 3 + unit with consecutive repeats merged, the score -(mean squared distance of the frames to their centroids); frames without a
+    unit (-1: a NaN row) are left out"""
+    from .solver import format_phn
+    units, dist = np.asarray(units).reshape(-1), np.asarray(dist, np.float64).reshape(-1)
+    keep = units >= 0
+    score = -float(dist[keep].mean()) if keep.any() else 0.0
+    return format_phn([score], [[UNIT_ID_OFFSET + u for u in merge_repeats(units[keep])]], None)
+
+
+def packed_bytes(rows, D):
+    return int(rows) * int(D) * 4
+
+
+class KMeansTrainer(FeatureTool):
+    """main.py --kmeans-wav-dir DIR --kmeans-out FILE.npy [--kmeans-feat mfcc|mel|latent --kmeans-k 50 --kmeans-iters 100 --kmeans-tol 1e-4
+    --kmeans-init ++|sample --kmeans-restarts 1 --kmeans-max-gb 8]: fits a codebook of K centroids to the frames of the .wav files of
+    DIR (kmeans.fit over the packed (rows, D) buffer of FeatureTool.pack; --resample, --trim-silence, --normalize-loudness, --batch-size,
+    --seed and --load are honoured; mfcc and mel need neither a checkpoint nor a model).  -> FILE.npy, (K, D) float32;
+    <logdir>/<name>/kmeans.csv (restart,iter,inertia,shift,empty), kmeans_units.csv (unit,frames: the frames of the returned fit) and one
+    printed line.  The buffer's size is computed from the .wav headers in load_data; above --kmeans-max-gb the run is refused there,
+    before the device is touched."""
+
+    def __init__(self, config, paras, mode):
+        super().__init__(config, paras, mode)
+        self.feat = getattr(paras, 'kmeans_feat', None) or 'mfcc'
+        self.K = int(getattr(paras, 'kmeans_k', None) or 50)
+        self.iters = int(getattr(paras, 'kmeans_iters', None) or 100)
+        tol = getattr(paras, 'kmeans_tol', None)
+        self.tol = 1e-4 if tol is None else float(tol)
+        self.init = getattr(paras, 'kmeans_init', None) or '++'
+        self.restarts = int(getattr(paras, 'kmeans_restarts', None) or 1)
+        self.max_bytes = int(float(getattr(paras, 'kmeans_max_gb', None) or 8) * (1 << 30))
+        self.out = paras.kmeans_out
+
+    def load_data(self):
+        from .audio import load_audio_transform
+        self.wav_dir = self.paras.kmeans_wav_dir
+        self.files = list_wavs(self.wav_dir, '--kmeans-wav-dir')
+        self.audio_converter = load_audio_transform(**dict(self.config['data']['audio']))
+        samples = self.check_waves(self.files, '--kmeans-wav-dir')
+        self.max_rows = int(sum(self.feature_rows(L) for L in samples))
+        D = self.feature_dim() or toolops.KM_MAX_D               # (latent: the widest row the kernels take)
+        if packed_bytes(self.max_rows, D) > self.max_bytes:
+            raise ValueError('--kmeans-wav-dir %s: %d files give up to %d rows of %d columns, %.2f GiB of features; --kmeans-max-gb allows %.2f'
+                             % (self.wav_dir, len(self.files), self.max_rows, D, packed_bytes(self.max_rows, D) / float(1 << 30),
+                                self.max_bytes / float(1 << 30)))
+        if self.max_rows < self.K:
+            raise ValueError('--kmeans-wav-dir %s: at most %d rows for --kmeans-k %d clusters' % (self.wav_dir, self.max_rows, self.K))
+        return self
+
+    def exec(self):
+        from .kmeans import fit_all
+        t0 = time.perf_counter()
+        feat, _, n_rows = self.pack(self.files)
+        fits = fit_all(feat, self.K, self.iters, self.tol, self.init, int(getattr(self.paras, 'seed', 0)), self.restarts)
+        self.result = best = min(fits, key=lambda r: r.inertia)
+        os.makedirs(self.logdir, exist_ok=True)
+        out_dir = os.path.dirname(os.path.abspath(self.out))
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(self.out, best.centroids.cpu().numpy(), allow_pickle=False)
+        self.write_lines('kmeans.csv', [KMEANS_HEADER] + ['%d,%d,%.9g,%.9g,%d' % ((r,) + h) for r, res in enumerate(fits) for h in res.history])
+        frames = torch.bincount(best.idx[best.idx >= 0].long(), minlength=self.K).cpu().numpy()
+        table = self.write_lines('kmeans_units.csv', [KMEANS_UNITS_HEADER] + ['%d,%d' % (u, n) for u, n in enumerate(frames.tolist())])
+        print('[INFO]', 'k-means of %s: %d units from %d frames of %d files, inertia %.6g after %d iterations (%s; %d restart%s), %d units unused; %s, %s, %.2f s'
+              % (self.feat, self.K, int(n_rows.sum()), len(self.files), best.inertia, best.n_iter, 'converged' if best.converged else 'not converged',
+                 self.restarts, '' if self.restarts == 1 else 's', int((frames == 0).sum()), self.out, table, time.perf_counter() - t0))
+        return self.K
+
+
+class UnitWriter(FeatureTool):
+    """main.py --units-wav-dir DIR --units-codebook FILE.npy [--kmeans-feat mfcc|mel|latent --units-frames]: the unit sequence of every .wav
+    of DIR under the codebook of --kmeans-out (kmeans.quantise over the packed buffer of a batch) -> <logdir>/<name>/<stem>.phn in the
+    layout of --transcribe-wav-dir (format_units: ids 3 + unit, repeats merged, the score -mean squared distance), which
+    --build-lm-phn-dir --lm-classes <3 + K> and --score-phn-dir read as they are; --units-frames also writes the unmerged frame-level units as
+    <stem>-units.npy (int32).  A codebook whose D is not the feature's is refused in load_data (for latent: when the model is built)."""
+
+    def __init__(self, config, paras, mode):
+        super().__init__(config, paras, mode)
+        self.feat = getattr(paras, 'kmeans_feat', None) or 'mfcc'
+        self.want_frames = bool(getattr(paras, 'units_frames', False))
+
+    def load_data(self):
+        from .audio import load_audio_transform
+        self.wav_dir = self.paras.units_wav_dir
+        self.files = list_wavs(self.wav_dir, '--units-wav-dir')
+        self.audio_converter = load_audio_transform(**dict(self.config['data']['audio']))
+        self.check_waves(self.files, '--units-wav-dir')
+        self.codebook = load_codebook('--units-codebook', self.paras.units_codebook, self.feature_dim())
+        return self
+
+    def exec(self):
+        from .kmeans import quantise
+        os.makedirs(self.logdir, exist_ok=True)
+        t0, n, table = time.perf_counter(), 0, None
+        for names in self.batches(self.files):
+            feat, first, n_rows = self.pack(list(names))
+            if table is None:
+                if self.codebook.shape[1] != feat.shape[1]:
+                    raise ValueError('--units-codebook %s: the codebook has D = %d columns, the features have %d'
+                                     % (self.paras.units_codebook, self.codebook.shape[1], feat.shape[1]))
+                table = torch.from_numpy(self.codebook).to(feat.device)
+            idx, dist = quantise(feat, table)
+            host = torch.stack([idx.double(), dist.double()]).cpu().numpy()             # (the batch's one host read)
+            for f, r0, r in zip(names, first.tolist(), n_rows.tolist()):
+                stem = os.path.join(self.logdir, os.path.splitext(f)[0])
+                units = host[0, r0:r0 + r].astype(np.int32)
+                with open(stem + '.phn', 'w') as fh:
+                    fh.write(format_units(units, host[1, r0:r0 + r]))
+                if self.want_frames:
+                    np.save(stem + '-units.npy', units, allow_pickle=False)
+                n += r
+        if getattr(self.paras, 'verbose', True):
+            print('[INFO]', 'Wrote the units of %d files (%d frames of %s, %d centroids) into %s, %.2f s'
+                  % (len(self.files), n, self.feat, self.codebook.shape[0], self.logdir, time.perf_counter() - t0))
+        return len(self.files)

@@ -551,3 +551,7 @@ def align_pairs(clean, degraded, max_lag):
             toolops.wave_gather(buf, so[b0:b0 + M], out, off[b0:b0 + M], n[b0:b0 + M])
         sides.append(audio.WaveBatch.from_packed(out, n, order))
     return sides[0], sides[1], dl, coef
+
+
+# k-means units (semi_tts_amd/kmeans.py): the baseline representation the measures above are compared on
+from .kmeans import KMeansFit, fit as kmeans_fit, quantise  # noqa: E402,F401

@@ -151,7 +151,8 @@ def build_lm_from_phn_dir(phn_dir, out, order, V=43, smooth=1.0, vocab=None, bos
     for f in files:
         ids = [i for i in read_phn(os.path.join(phn_dir, f), vocab) if i != 0]
         if any(i >= V for i in ids):
-            raise ValueError('%s: id %d outside the %d classes of the table' % (os.path.join(phn_dir, f), max(ids), V))
+            raise ValueError('%s: id %d outside the %d classes of the table (--lm-classes; unit transcripts of K centroids need 3 + K)'
+                             % (os.path.join(phn_dir, f), max(ids), V))
         transcripts.append(ids)
     counts = count_ngrams(transcripts, V, order, bos)
     table = ngram_table(counts, smooth, 0)

@@ -1625,7 +1625,7 @@ from .toolops import (  # noqa: E402,F401
     ctc_greedy_edit_distance, dtw, DTW_MAX_D, DTW_MAX_T, dtw_pairs, _dtw_side, EA_MAX_IGNORE, EA_MAX_L, EA_MAX_V, edit_align, _f0_check,
     F0_MAX_SPAN, F0_MAX_TAU, F0_MAX_W, f0_path_scores, F0_RUN, f0_run_length, f0_yin, feature_noise, FEATURES_MAX_BATCH, GED_MAX_IGNORE,
     GED_MAX_L, GED_MAX_T, GED_MAX_V, GL_CLIP, GL_INV_PREEMPHASIS, griffin_lim, griffin_lim_batch, _host_off_lens, _host_ptr, hyp_edit_distance,
-    _IGNORE_DEV, istft, loudness, _loudness_check, LOUDNESS_FLAGS, loudness_hop, LOUDNESS_MAX_SR, LOUDNESS_MIN_SR, loudness_run_length,
+    _IGNORE_DEV, istft, KM_CHUNK, KM_MAX_D, KM_MAX_K, KM_SLAB, kmeans_assign, kmeans_pp_init, kmeans_relocate, kmeans_update, loudness, _loudness_check, LOUDNESS_FLAGS, loudness_hop, LOUDNESS_MAX_SR, LOUDNESS_MIN_SR, loudness_run_length,
     LOUDNESS_TABLE_DOUBLES, LOUDNESS_THREADS, MEL_MAX, mel_to_linear, MEL_TO_LINEAR_TILE, MFCC_MIN_FRAMES, _ngram_order_of, _pair_args,
     _pair_check, resample_batch, resample_lds_floats, RESAMPLE_MAX_STAGE_FLOATS, RESAMPLE_MAX_TABLE_FLOATS, RESAMPLE_TILE, segment_gather,
     sisdr_batch, SISDR_CHUNK, stft_fwd, STOI_BAND_EDGES, STOI_BANDS, stoi_batch, _stoi_check, STOI_CHUNK, STOI_FRAME, stoi_frames, STOI_FS,

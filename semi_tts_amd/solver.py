@@ -1265,7 +1265,8 @@ class VqvaeTrainer(TtsTrainer):
 
 # the tools that build no model live in dirtools.py; they stay reachable as solver.X (main.py, the tests and the tools look them up here)
 from .dirtools import (  # noqa: E402,F401
-    DirTool, Vocoder, Resampler, LoudnessWriter, Trimmer, FeatureWriter, McdScorer, StoiScorer, AbxScorer, PhnScorer,
+    DirTool, Vocoder, Resampler, LoudnessWriter, Trimmer, FeatureWriter, McdScorer, StoiScorer, AbxScorer, PhnScorer, FeatureTool, KMeansTrainer,
+    UnitWriter, load_codebook, merge_repeats, format_units, UNIT_FEATS, UNIT_ID_OFFSET, KMEANS_HEADER, KMEANS_UNITS_HEADER,
     list_wavs, wav_header, check_wav, check_out_dir, load_waves, mfcc_frames, extract_features,
     list_vocode_files, trim_args, loudness_args, vocode, f0_args, mcd_key, mcd_pairs, phn_pairs, per_row, format_confusions, format_phones,
     format_ops, stoi_row, abx_metric,

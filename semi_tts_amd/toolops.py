@@ -357,6 +357,130 @@ def abx_across(dmat, grp, xr):
     return err, count
 
 
+KM_MAX_D, KM_MAX_K, KM_MAX_FLOATS = 256, 4096, 2 ** 40        # the k-means entry points' limits
+KM_CHUNK = 1024                      # points of a histogram chunk of st_kmeans_update and of a seeding chunk: the tests straddle it
+KM_SLAB = 256                        # members of a summation slab of st_kmeans_update
+
+
+def _km_data(what, x):
+    """the (N, D) float32 GPU matrix every k-means op clusters (unit column stride; a column slice keeps its row stride) -> st_kmeans_data"""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError('%s: x must be a (N, D) float32 GPU tensor (got %s)' % (what, _got(x)))
+    N, D = x.shape
+    if N < 1 or N >= 2 ** 31 or not 1 <= D <= KM_MAX_D:
+        raise ValueError('%s: x is %s: 1 <= N < 2^31 and 1 <= D <= %d' % (what, tuple(x.shape), KM_MAX_D))
+    ld = x.stride(0) if N > 1 else max(x.stride(0), D)            # (a 1-long dimension's stride is free)
+    if (x.stride(1) != 1 and D > 1) or ld < D or N * ld >= KM_MAX_FLOATS:
+        raise ValueError('%s: x has strides %s: the columns need stride 1, the rows at least D = %d floats apart, N * stride below 2^40'
+                         % (what, tuple(x.stride()), D))
+    return _lib.StKmeansData(None, ld, N, D)
+
+
+def _km_tensor(what, name, t, x, shape, dtype, symbol):
+    """an operand of a k-means op: a contiguous tensor of `shape` and `dtype` on the device of x"""
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != x.device or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError('%s: %s must be a contiguous %s %s tensor on the device of x (got %s)'
+                         % (what, name, symbol, str(dtype).replace('torch.', ''), _got(t)))
+
+
+def _km_cent(what, name, cent, x):
+    """a (K, D) table of centroids for x -> K"""
+    if not torch.is_tensor(cent) or cent.dim() != 2 or not 1 <= cent.shape[0] <= KM_MAX_K:
+        raise ValueError('%s: %s must be a (K, D) tensor with 1 <= K <= %d (got %s)' % (what, name, KM_MAX_K, _got(cent)))
+    _km_tensor(what, name, cent, x, (cent.shape[0], x.shape[1]), torch.float32, '(K, D = %d)' % x.shape[1])
+    return cent.shape[0]
+
+
+def _km_fill(d, x):
+    d.x = _p(x)
+    return C.byref(d)
+
+
+def kmeans_assign(x, cent):
+    """the nearest centroid of every row (see st_kmeans_assign): x (N, D) float32 on one GPU, cent (K, D) float32 contiguous on the same
+    device -> (idx (N,) int32, the smallest k at the least squared distance, -1 for a row holding a NaN or an infinity; dist (N,) float32, that
+    distance, NaN for such a row).  One launch, no host read.  Bad arguments raise ValueError before the device is touched."""
+    d = _km_data('kmeans_assign', x)
+    K = _km_cent('kmeans_assign', 'cent', cent, x)
+    lib = _lib.load()
+    idx = torch.empty(d.N, device=x.device, dtype=torch.int32)
+    dist = torch.empty(d.N, device=x.device, dtype=torch.float32)
+    check(lib.st_kmeans_assign(_km_fill(d, x), _p(cent), K, _p(idx, torch.int32), _p(dist), stream_handle()), 'st_kmeans_assign')
+    return idx, dist
+
+
+def kmeans_update(x, idx, dist, cent_in):
+    """the centroids of an assignment (see st_kmeans_update): idx (N,) int32 and dist (N,) float32 as kmeans_assign gives them, cent_in
+    (K, D) float32 -> (cent_out (K, D) float32: the float64 mean of a cluster's members, cent_in's row for an empty cluster; count (K,)
+    int32; stats (4,) float64 = (inertia, the squared shift of the table, empty clusters, rows that are no member)).  Bitwise repeatable;
+    seven launches, no host read.  Bad arguments raise ValueError before the device is touched."""
+    d = _km_data('kmeans_update', x)
+    _km_tensor('kmeans_update', 'idx', idx, x, (d.N,), torch.int32, '(N = %d,)' % d.N)
+    _km_tensor('kmeans_update', 'dist', dist, x, (d.N,), torch.float32, '(N = %d,)' % d.N)
+    K = _km_cent('kmeans_update', 'cent_in', cent_in, x)
+    lib = _lib.load()
+    dev = x.device
+    cent_out = torch.empty(K, d.D, device=dev, dtype=torch.float32)
+    count = torch.empty(K, device=dev, dtype=torch.int32)
+    stats = torch.empty(4, device=dev, dtype=torch.float64)
+    ws = torch.empty(int(lib.st_kmeans_update_workspace_bytes(d.N, d.D, K)) // 8 + 2, device=dev, dtype=torch.float64)
+    check(lib.st_kmeans_update(_km_fill(d, x), _p(idx, torch.int32), _p(dist), _p(cent_in), K, _p(cent_out), _p(count, torch.int32),
+                               _p(stats, torch.float64), _p(ws, torch.float64), stream_handle()), 'st_kmeans_update')
+    return cent_out, count, stats
+
+
+def kmeans_relocate(x, idx, dist, count, cent):
+    """move the empty clusters (see st_kmeans_relocate): the e-th cluster with count 0 takes the row of the e-th point in the order (dist
+    descending, index ascending); cent (K, D) float32 is changed in place -> cent.  One launch.  Bad arguments raise ValueError before
+    the device is touched."""
+    d = _km_data('kmeans_relocate', x)
+    _km_tensor('kmeans_relocate', 'idx', idx, x, (d.N,), torch.int32, '(N = %d,)' % d.N)
+    _km_tensor('kmeans_relocate', 'dist', dist, x, (d.N,), torch.float32, '(N = %d,)' % d.N)
+    K = _km_cent('kmeans_relocate', 'cent', cent, x)
+    _km_tensor('kmeans_relocate', 'count', count, x, (K,), torch.int32, '(K = %d,)' % K)
+    lib = _lib.load()
+    check(lib.st_kmeans_relocate(_km_fill(d, x), _p(idx, torch.int32), _p(dist), _p(count, torch.int32), K, _p(cent), stream_handle()),
+          'st_kmeans_relocate')
+    return cent
+
+
+def kmeans_pp_init(x, K, u):
+    """k-means++ seeding (see st_kmeans_pp_step): K rows of x, the first at floor(u[0] N), the j-th drawn with probability proportional
+    to the squared distance to the nearest of the rows before it by u[j]; u: K numbers in [0, 1) (a host sequence, or a (K,) float64
+    tensor on the device of x).  -> (cent (K, D) float32, picks (K,) int32, mind (N,) float32: the squared distance of every row to the
+    nearest pick).  2 K launches and one host read, of the flag that fewer than K distinct rows exist: that raises ValueError, as bad
+    arguments do before the device is touched."""
+    d = _km_data('kmeans_pp_init', x)
+    if not _is_int(K) or not 1 <= int(K) <= KM_MAX_K:
+        raise ValueError('kmeans_pp_init: K must be an integer in [1, %d] (got %r)' % (KM_MAX_K, K))
+    K = int(K)
+    if torch.is_tensor(u) and u.is_cuda:
+        _km_tensor('kmeans_pp_init', 'u', u, x, (K,), torch.float64, '(K = %d,)' % K)
+    else:
+        host = np.asarray(u.cpu() if torch.is_tensor(u) else u, dtype=np.float64)
+        if host.shape != (K,) or not ((host >= 0.0) & (host < 1.0)).all():
+            raise ValueError('kmeans_pp_init: u must be K = %d numbers in [0, 1) (got %s)' % (K, host.tolist() if host.size <= 8 else host.shape))
+        u = host
+    lib = _lib.load()
+    dev = x.device
+    if not torch.is_tensor(u) or not u.is_cuda:
+        u = torch.from_numpy(np.ascontiguousarray(u)).to(dev)
+    cent = torch.empty(K, d.D, device=dev, dtype=torch.float32)
+    picks = torch.zeros(K, device=dev, dtype=torch.int32)
+    mind = torch.full((d.N,), float('inf'), device=dev, dtype=torch.float32)
+    part = torch.zeros(int(lib.st_kmeans_chunks(d.N)), device=dev, dtype=torch.float64)
+    totals = torch.zeros(K, device=dev, dtype=torch.float64)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    px, s = _km_fill(d, x), stream_handle()
+    for j in range(K):
+        check(lib.st_kmeans_pp_pick(px, _p(mind), _p(part, torch.float64), _p(u, torch.float64), j, K, _p(picks, torch.int32),
+                                    _p(totals, torch.float64), _p(flag, torch.int32), s), 'st_kmeans_pp_pick')
+        check(lib.st_kmeans_pp_step(px, _p(picks, torch.int32), j, K, _p(mind), _p(part, torch.float64), _p(cent), s), 'st_kmeans_pp_step')
+    if int(flag.item()):                                           # (the one host read)
+        raise ValueError('kmeans_pp_init: x holds fewer than K = %d distinct rows' % K)
+    return cent, picks, mind
+
+
 AE_MAX_S, AE_MAX_L = 4096, 2048         # st_attn_endpoint's limits
 
 
